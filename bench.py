@@ -36,6 +36,9 @@ names the commit and the hash of the kernel sources they were measured on, and b
 this build differ.
 `cpu_baseline` times the CPU oracle (oracle/, a restatement — the reference has no CPU path) on a bounded sample of
 the same workload.
+
+--dump-outputs DIR writes, after the timed steps, what they handed the caller (dump_outputs below): the same arguments give
+the same inputs in every run, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -75,6 +78,34 @@ CONFIGS = {
     4: dict(scene="cornell", width=3840, height=2160, spp=256, fps=64, bounces=8, mis=1, aperture=0.05, focus=2.8,
             scaling="strong", name="configs[4]"),
 }
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6           # --dump-outputs writes at most this much in all
+DUMP_SAMPLE_PIXELS = 1 << 20            # pixels kept of a frame too large to write whole
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, frame, counters):
+    """--dump-outputs: the output of the timed steps as out_dir/<name>.npy (float32 / float64), returns the names.
+    frame.npy     the output buffer after the last timed step: [H, W, 4] float32 (running mean, w = 0). A frame above
+                  DUMP_LIMIT_BYTES is written as a fixed, seeded sample of DUMP_SAMPLE_PIXELS pixels instead ([n, 4], in
+                  row-major pixel order), with their row-major pixel indices in frame_pixels.npy (float64): the same frame
+                  size always gives the same sample.
+    counters.npy  paths, segments, shadow rays of the timed steps, all ranks (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, np.float32)
+    files = {"counters": np.asarray(counters, np.float64)}
+    if frame.nbytes + files["counters"].nbytes + 1024 <= DUMP_LIMIT_BYTES:         # (+ the .npy headers)
+        files["frame"] = frame
+    else:
+        h, w = frame.shape[:2]
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(h * w, min(DUMP_SAMPLE_PIXELS, h * w), replace=False))
+        files["frame"] = frame.reshape(h * w, 4)[idx]
+        files["frame_pixels"] = idx.astype(np.float64)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(files)
 
 
 def shade_bytes_per_segment(do_mis, p_record, bounce0_share):
@@ -295,9 +326,11 @@ def single_process(args, cfg, overridden, steps, fps, spp):
     m.synchronize()
     dt = time.perf_counter() - t0
     st = m.stats()
+    got = m.read_output() if args.rehearse or args.dump_outputs else None      # the gathered frame of the timed steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, got, (st.paths, st.segments, st.shadow_rays))
     ok = None
     if args.rehearse:                # the gathered frame against one device's unsharded render of the same frames
-        got = m.read_output()
         with native.Context(0) as c:
             c.upload_scene(scene)
             c.resize(W, H)
@@ -377,7 +410,12 @@ def main():
                          "through host memory, rank 0 checks the gathered frame bit for bit against its own unsharded "
                          "render. Not a benchmark.")
     ap.add_argument("--timing", type=int, default=3, help="library HIP-event timing level (2 = every extend launch, 3 = every kernel)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (the output frame, the path / segment / shadow-ray "
+                         "counts) as DIR/<name>.npy, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     cfg = dict(CONFIGS[args.config])
     overridden = []
@@ -505,6 +543,8 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     leg_seconds = {"gpu_warmup_and_timed": round(time.perf_counter() - t_leg, 3)}
+    # the frame of the timed steps, before the legs below render into the same buffer again
+    dumped = frame.cpu().numpy() if args.dump_outputs and rank == 0 else None
 
     st = ctx.stats()
     # the same steps with the OTHER leaf mode (N = 1): both numbers stay in the record while the own leaves are new
@@ -548,6 +588,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         dt = float(tmax[0])
     segments, shadow_rays, paths = float(t[1]), float(t[2]), float(t[3])
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped, (paths, segments, shadow_rays))
 
     if rank == 0:
         mean_len = segments / paths

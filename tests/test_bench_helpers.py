@@ -79,6 +79,30 @@ def test_committed_valu_counters_feed_the_second_roofline():
     assert b.valu_issue(0, True, {"extend": 4, "shade": 4, "shadow": 0}, 1.0) is None or os.path.exists(b.profile_path(0, "counters"))
 
 
+def test_dump_outputs(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files, at most DUMP_LIMIT_BYTES in all; a frame above the limit becomes the same
+    seeded sample of pixels in every run, with the pixel indices beside it."""
+    import numpy as np
+    b = _bench()
+    frame = np.arange(48 * 64 * 4, dtype=np.float32).reshape(48, 64, 4)
+    assert b.dump_outputs(str(tmp_path / "a"), frame, (10, 25, 7)) == ["counters", "frame"]
+    got = np.load(tmp_path / "a" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame)
+    c = np.load(tmp_path / "a" / "counters.npy")
+    assert c.dtype == np.float64 and c.tolist() == [10, 25, 7]
+
+    b.DUMP_LIMIT_BYTES, b.DUMP_SAMPLE_PIXELS = 16 * 1024, 500            # the same frame is now too large to write whole
+    for d in ("b", "c"):
+        assert b.dump_outputs(str(tmp_path / d), frame, (10, 25, 7)) == ["counters", "frame", "frame_pixels"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= b.DUMP_LIMIT_BYTES
+    idx = np.load(tmp_path / "b" / "frame_pixels.npy")
+    assert idx.dtype == np.float64 and len(idx) == 500 and len(np.unique(idx)) == 500 and (np.diff(idx) > 0).all()
+    sample = np.load(tmp_path / "b" / "frame.npy")
+    assert sample.dtype == np.float32 and np.array_equal(sample, frame.reshape(-1, 4)[idx.astype(np.int64)])
+    for f in ("frame", "frame_pixels", "counters"):
+        assert np.array_equal(np.load(tmp_path / "b" / f"{f}.npy"), np.load(tmp_path / "c" / f"{f}.npy"))
+
+
 def _check_line(d):
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):

@@ -1,7 +1,7 @@
 """The Node host's glTF path: host/gltf.js + host/scene_prep.js restate
 src/renderer/loader.ts + src/renderer/gpu.ts:67-421 on top of the C++ BVH builder. Checked against a
-float64 numpy model of the same transforms on a synthetic TRS hierarchy, on the reference's own .glb
-assets when they are present (CPU only; never on the GPU box), and end to end against the oracle."""
+float64 numpy model of the same transforms on a synthetic TRS hierarchy, on scenes written in the shape
+of the reference's sample assets, and end to end against the oracle."""
 import json
 import os
 import shutil
@@ -15,7 +15,6 @@ from ptmi import glb_io, layout, scenes
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "wgpu-path-tracing_amd", "host")
 NODE = shutil.which("node")
-REF_MODELS = "/root/reference/public/models"
 pytestmark = pytest.mark.skipif(NODE is None, reason="node is not installed")
 
 
@@ -41,17 +40,19 @@ def trs(t=(0, 0, 0), r=(0, 0, 0, 1), s=(1, 1, 1)):
     return M
 
 
+def mesh_of(tris, material):
+    """A TRIANGLE array as one indexed glb_io mesh (three vertices per triangle)."""
+    pos = np.concatenate([tris["v0"], tris["v1"], tris["v2"]]).reshape(3, -1, 3).transpose(1, 0, 2).reshape(-1, 3)
+    nrm = np.concatenate([tris["n0"], tris["n1"], tris["n2"]]).reshape(3, -1, 3).transpose(1, 0, 2).reshape(-1, 3)
+    uv = np.concatenate([tris["uv0"], tris["uv1"], tris["uv2"]]).reshape(3, -1, 2).transpose(1, 0, 2).reshape(-1, 2)
+    return {"positions": pos, "normals": nrm, "uvs": uv, "indices": np.arange(len(pos)), "material": material}
+
+
 def synthetic_glb(path):
     """A small room: floor + emissive ceiling panel + a cube parented under a rotated, scaled node
     (child -> parent -> grandparent chain), a metal sphere, a point and a directional light."""
     box = scenes._box((0, 0, 0), (1, 1, 1), 0)
     sph = scenes._uv_sphere((0, 0, 0), 0.5, 0, segments=10, rings=6)
-
-    def mesh_of(tris, material):
-        pos = np.concatenate([tris["v0"], tris["v1"], tris["v2"]]).reshape(3, -1, 3).transpose(1, 0, 2).reshape(-1, 3)
-        nrm = np.concatenate([tris["n0"], tris["n1"], tris["n2"]]).reshape(3, -1, 3).transpose(1, 0, 2).reshape(-1, 3)
-        uv = np.concatenate([tris["uv0"], tris["uv1"], tris["uv2"]]).reshape(3, -1, 2).transpose(1, 0, 2).reshape(-1, 2)
-        return {"positions": pos, "normals": nrm, "uvs": uv, "indices": np.arange(len(pos)), "material": material}
 
     floor = scenes._quad((-2, 0, -2), (2, 0, -2), (2, 0, 2), (-2, 0, 2), (0, 1, 0), 0)
     panel = scenes._quad((-0.5, 2.5, -0.5), (0.5, 2.5, -0.5), (0.5, 2.5, 0.5), (-0.5, 2.5, 0.5), (0, -1, 0), 0)
@@ -129,17 +130,104 @@ def test_synthetic_hierarchy_matches_float64_model(tmp_path):
     assert _check_tree(sc.nodes, sc.tris) == info["bvhDepth"]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODELS), reason="reference assets are not on this machine")
-@pytest.mark.parametrize("name,tris,mats", [("cornell2", 1004, 7), ("transform", 40, 5), ("monkey", 970, 2),
-                                            ("metal", 5074, 8), ("glass_box", 11790, 15), ("untitled", 2882, 4)])
-def test_reference_assets_load(tmp_path, name, tris, mats):
-    """The reference's own sample scenes go through the host unchanged (read in place, never copied)."""
+def _pbr(name, color, metallic=0.0, roughness=0.5, emissive=None, strength=None, transmission=None):
+    """A material as the reference's sample exports write them: named, double-sided, factors only, emission through
+    emissiveFactor and KHR_materials_emissive_strength, glass through KHR_materials_transmission."""
+    m = {"name": name, "doubleSided": True,
+         "pbrMetallicRoughness": {"baseColorFactor": [*color, 1.0], "metallicFactor": metallic, "roughnessFactor": roughness}}
+    ext = {}
+    if emissive is not None:
+        m["emissiveFactor"] = list(emissive)
+    if strength is not None:
+        ext["KHR_materials_emissive_strength"] = {"emissiveStrength": strength}
+    if transmission is not None:
+        ext["KHR_materials_transmission"] = {"transmissionFactor": transmission}
+    if ext:
+        m["extensions"] = ext
+    return m
+
+
+def sample_shaped_glb(path, name):
+    """Scenes in the shape of the reference's sample assets (public/models/<name>.glb): one primitive per mesh, uint16
+    indices, POSITION / NORMAL / TEXCOORD_0, named TRS nodes (translation, rotation, scale, children in `transform`), no
+    punctual lights, materials as _pbr writes them (none of the extensions in `untitled`). Returns the triangles, the
+    primitive instances (= materials of the prepared scene) and the emissive triangles the host must produce."""
+    Q, B, S = scenes._quad, scenes._box, scenes._uv_sphere
+    panel = Q((-0.3, 0, -0.3), (0.3, 0, -0.3), (0.3, 0, 0.3), (-0.3, 0, 0.3), (0, -1, 0), 0)
+    floor = Q((-1, 0, -1), (1, 0, -1), (1, 0, 1), (-1, 0, 1), (0, 1, 0), 0)
+    light = _pbr("light", (1, 1, 1), emissive=(1, 0.85, 0.6), strength=15.0)
+    grey = _pbr("grey", (0.7, 0.7, 0.7))
+    rot = quat((0.2, 1, 0.1), 0.7)
+    if name == "cornell2":
+        walls = np.concatenate([floor, Q((-1, 2, -1), (-1, 2, 1), (1, 2, 1), (1, 2, -1), (0, -1, 0), 0),
+                                Q((-1, 0, -1), (-1, 2, -1), (1, 2, -1), (1, 0, -1), (0, 0, 1), 0)])
+        parts = [(walls, 0), (Q((-1, 0, -1), (-1, 0, 1), (-1, 2, 1), (-1, 2, -1), (1, 0, 0), 0), 1),
+                 (Q((1, 0, -1), (1, 2, -1), (1, 2, 1), (1, 0, 1), (-1, 0, 0), 0), 2),
+                 (B((0, 0, 0), (0.6, 1.2, 0.6), 0), 0), (B((0, 0, 0), (0.6, 0.6, 0.6), 0), 0), (panel, 3)]
+        materials = [_pbr("white", (0.73, 0.73, 0.73)), _pbr("red", (0.65, 0.05, 0.05)), _pbr("green", (0.12, 0.45, 0.15)), light]
+        nodes = [{"mesh": 0}, {"mesh": 1}, {"mesh": 2}, {"mesh": 3, "translation": [-0.35, 0.6, -0.3]},
+                 {"mesh": 4, "translation": [0.35, 0.3, 0.3]}, {"mesh": 5, "translation": [0, 1.99, 0]}]
+    elif name == "transform":
+        parts = [(floor, 0), (panel, 1), (B((0, 0, 0), (0.4, 0.4, 0.4), 0), 0)]
+        materials = [grey, light]
+        nodes = [{"mesh": 0}, {"mesh": 1, "translation": [0, 2, 0]},
+                 {"mesh": 2, "translation": [0, 0.5, 0], "rotation": rot, "scale": [1.5, 0.5, 1.0], "children": [3]},
+                 {"mesh": 2, "translation": [0.6, 0.4, 0], "rotation": quat((1, 0, 0), 0.4), "scale": [0.5, 1.2, 0.5], "children": [4]},
+                 {"mesh": 2, "translation": [0, 0.7, 0.2], "scale": [0.8, 0.8, 2.0]}]
+    elif name == "monkey":
+        parts = [(S((0, 0, 0), 0.5, 0, segments=40, rings=14), 0), (panel, 1)]
+        materials = [grey, light]
+        nodes = [{"mesh": 0, "translation": [0, 0.6, 0], "scale": [0.9, 1.1, 0.8]},
+                 {"mesh": 1, "translation": [0, 2, 0], "scale": [2, 1, 2]}]
+    elif name == "metal":
+        parts = [(floor, 0), (S((0, 0, 0), 0.3, 0, segments=24, rings=12), 1), (S((0, 0, 0), 0.3, 0, segments=24, rings=12), 2),
+                 (B((0, 0, 0), (0.4, 0.4, 0.4), 0), 3), (B((0, 0, 0), (0.3, 0.6, 0.3), 0), 2), (panel, 4)]
+        materials = [grey, _pbr("gold", (1.0, 0.78, 0.34), metallic=1.0, roughness=0.2),
+                     _pbr("steel", (0.56, 0.57, 0.58), metallic=1.0, roughness=0.05),
+                     _pbr("glass", (1, 1, 1), roughness=0.0, transmission=1.0), light]
+        nodes = [{"mesh": 0, "scale": [2, 1, 2]}, {"mesh": 1, "translation": [-0.5, 0.3, 0]},
+                 {"mesh": 2, "translation": [0.5, 0.3, 0], "rotation": rot, "scale": [1, 0.7, 1]},
+                 {"mesh": 3, "translation": [0, 0.2, 0.5], "rotation": quat((0, 1, 0), 0.5)},
+                 {"mesh": 4, "translation": [0, 0.3, -0.5], "rotation": rot, "scale": [0.7, 1, 0.7]},
+                 {"mesh": 5, "translation": [0, 2, 0]}]
+    elif name == "glass_box":
+        parts = [(floor, 0), (B((0, 0, 0), (1, 1, 1), 0), 1), (S((0, 0, 0), 0.2, 0, segments=16, rings=8), 2), (panel, 3)]
+        materials = [grey, _pbr("glass", (1, 1, 1), roughness=0.0, transmission=1.0),
+                     _pbr("frosted", (0.9, 0.95, 1.0), roughness=0.3, transmission=0.8), light]
+        nodes = [{"mesh": 0, "scale": [3, 1, 3]}] + [
+            {"mesh": 1 + (i % 2), "translation": [0.6 * (i % 3) - 0.6, 0.3, 0.6 * (i // 3) - 0.3],
+             "rotation": quat((0, 1, 0), 0.3 * i), "scale": [0.3, 0.3, 0.3] if i % 2 == 0 else [1, 1, 1]} for i in range(6)] + [
+            {"mesh": 3, "translation": [0, 2, 0]}, {"mesh": 3, "translation": [0.8, 2, 0], "rotation": quat((0, 0, 1), 0.2)}]
+    elif name == "untitled":
+        parts = [(floor, 0), (B((0, 0, 0), (0.5, 0.5, 0.5), 0), 1), (S((0, 0, 0), 0.4, 0, segments=20, rings=10), 2), (panel, 3)]
+        materials = [{"name": "floor", "doubleSided": True, "pbrMetallicRoughness": {"baseColorFactor": [0.8, 0.8, 0.8, 1]}},
+                     {"name": "blue", "pbrMetallicRoughness": {"baseColorFactor": [0.1, 0.2, 0.8, 1], "roughnessFactor": 0.3}},
+                     {"name": "chrome", "pbrMetallicRoughness": {"metallicFactor": 1.0, "roughnessFactor": 0.1}},
+                     {"name": "lamp", "emissiveFactor": [1, 1, 1], "pbrMetallicRoughness": {"baseColorFactor": [1, 1, 1, 1]}}]
+        nodes = [{"mesh": 0, "scale": [2, 1, 2]}, {"mesh": 1, "translation": [-0.4, 0.25, 0]},
+                 {"mesh": 2, "translation": [0.5, 0.4, 0], "scale": [1, 1.3, 1]}, {"mesh": 3, "translation": [0, 2, 0], "scale": [2, 1, 2]}]
+    else:
+        raise ValueError(name)
+    for i, n in enumerate(nodes):
+        n["name"] = f"{name}_{i}"
+    glb_io.write_glb(str(path), [mesh_of(t, m) for t, m in parts], nodes, materials)
+    emissive = [any(materials[m].get("emissiveFactor", [0, 0, 0])) for _, m in parts]
+    used = [n["mesh"] for n in nodes if "mesh" in n]
+    return sum(len(parts[k][0]) for k in used), len(used), sum(len(parts[k][0]) for k in used if emissive[k])
+
+
+@pytest.mark.parametrize("name", ["cornell2", "transform", "monkey", "metal", "glass_box", "untitled"])
+def test_sample_shaped_assets_load(tmp_path, name):
+    """Scenes in the shape of the reference's sample assets go through the host: every triangle of every node instance,
+    one material per primitive instance, one light per emissive triangle, a valid tree, unit normals."""
     _build()
-    sc, info = prepare(os.path.join(REF_MODELS, name + ".glb"), tmp_path / name)
+    tris, mats, emissive = sample_shaped_glb(tmp_path / f"{name}.glb", name)
+    sc, info = prepare(tmp_path / f"{name}.glb", tmp_path / name)
     assert (len(sc.tris), len(sc.mats)) == (tris, mats)
+    assert (info["counts"]["triangles"], info["counts"]["materials"], info["counts"]["punctualLights"]) == (tris, mats, 0)
     from test_scene_host import _check_tree
     _check_tree(sc.nodes, sc.tris)
-    assert len(sc.lights) >= 2 and np.isfinite(sc.tris["v0"]).all()
+    assert len(sc.lights) == emissive >= 2 and np.isfinite(sc.tris["v0"]).all()
     n = np.stack([sc.tris["n0"], sc.tris["n1"], sc.tris["n2"]], 1)
     assert np.abs(np.linalg.norm(n, axis=-1) - 1).max() < 1e-4
 
