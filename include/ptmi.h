@@ -128,7 +128,8 @@ typedef struct ptmi_stats {
     /* ABI 4 (ABI 3 had worklist_used, tails_used, state_used, pipeline_used here) */
     uint32_t leaves_used;       /* 1 / 2: ptmi_options.leaves as the uploaded scene's traversal image was built */
     uint32_t leaf_tris_used;    /* most triangles in a leaf of that image */
-    uint32_t extend_variant, shadow_variant;   /* of the last dispatch: PTMI_VARIANT_* the closest-hit / any-hit kernel ran as */
+    uint32_t extend_variant, shadow_variant;   /* of the last dispatch, the memory variant the closest-hit / any-hit kernel ran as:
+                                                * variant number * 10 + workgroups per CU (e.g. 102: variant 10 with two) */
     /* leaves = 2: closest hits / occluders whose reference leaf's box did not pass and rays that were therefore traced again over the
      * uploaded tree (both kernels together), since the last reset */
     uint64_t verify_failed;

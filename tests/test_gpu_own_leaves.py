@@ -87,6 +87,24 @@ def test_every_memory_variant_returns_the_oracles_hits(own_ctx, oracle, scene_fa
     assert want <= {s for _, s in ran}, (name, sorted(ran))
 
 
+
+@pytest.mark.parametrize("code", [41, 71, 102, 112])
+def test_override_takes_the_reported_code(own_ctx, oracle, scene_factory, code):
+    """PTMI_OWN_EXTEND / PTMI_OWN_SHADOW also take the code ptmi_stats reports (variant * 10 + workgroups per CU): the kernels run as
+    that variant and still return the oracle's hits and verdicts"""
+    sc = scene_factory("cornell")
+    own_ctx.upload_scene(sc)
+    os.environ["PTMI_OWN_EXTEND"] = os.environ["PTMI_OWN_SHADOW"] = str(code)
+    o, d = more_rays(sc, 20_000, 3)
+    ot, otri, _, _, _ = oracle.intersect(sc, o, d)
+    gt, gtri, _, _ = own_ctx.debug_intersect(o, d)
+    assert own_ctx.stats().extend_variant == code
+    assert np.array_equal(gtri, otri); assert_same_floats(gt, ot, f"t ({code})")
+    dist = (np.random.default_rng(4).random(len(o)) * 2.5).astype(np.float32)
+    assert np.array_equal(own_ctx.debug_occluded(o, d, dist), oracle.occluded(sc, o, d, dist))
+    assert own_ctx.stats().shadow_variant == code
+
+
 RENDERS = [("cornell", 96, 64, 6, 8, 1, 0.001), ("cornell", 64, 64, 4, 4, 0, 0.001), ("cornell_glass", 80, 60, 5, 8, 1, 0.0),
            ("feature_box", 72, 72, 6, 8, 1, 0.05), ("cornell_spheres", 64, 48, 3, 8, 1, 0.001), ("grid_1m", 96, 54, 2, 8, 1, 0.001),
            ("deep_chain", 64, 48, 2, 8, 1, 0.0), ("cornell_enclosed", 64, 48, 3, 8, 1, 0.001)]

@@ -120,19 +120,68 @@ enum { PT_VARIANT_GLOBAL = 1, PT_VARIANT_LDS = 2, PT_VARIANT_LDS_NODES = 3,
        PT_VARIANT_OWN_LDS = 4, PT_VARIANT_OWN_LDS_NODES = 5, PT_VARIANT_OWN_QLDS = 6, PT_VARIANT_OWN_QLDS_NODES = 7,
        PT_VARIANT_OWN_QGLOBAL = 8, PT_VARIANT_OWN_GLOBAL = 9,
        PT_VARIANT_OWN_LDS16_NODES = 10,         // exact nodes with 16-bit references and 16-bit stack entries (scenes up to 4 096 triangles)
-       PT_VARIANT_OWN_QLDS16_NODES = 11 };      // quantised nodes with 16-bit references: two workgroups per CU for trees of up to 2 046 nodes,
+       PT_VARIANT_OWN_QLDS16_NODES = 11,        // quantised nodes with 16-bit references: two workgroups per CU for trees of up to 2 046 nodes,
                                                 // 8 - 15 16-bit entries per lane (what the nodes leave of 80 KB), the node stack spills
+       PT_VARIANT_COUNT };
+
+// What each traversal variant is: one row per PT_VARIANT_* (pt_variant), the one place selection (ptmi_api.hip traverse_config) and
+// the launches read it from.
+enum PtNodes {                  // node format
+    PT_NODES_EXACT,             // 64-B wide nodes (PT_VARIANT_GLOBAL: or the quantised image, TraverseConfig::quantized)
+    PT_NODES_QUANT,             // 32-B quantised nodes
+    PT_NODES_EXACT16,           // exact nodes with 16-bit (compact) references
+    PT_NODES_QUANT16 };         // quantised nodes with 16-bit references
+enum PtWhere {                  // what is resident in LDS
+    PT_LDS_ALL,                 // the nodes and the triangle images
+    PT_LDS_NODES,               // the nodes; triangles through L1 / L2
+    PT_FROM_MEMORY };           // nothing: walks the scene from memory (a quantised image keeps its top levels in LDS)
+enum PtStack {                  // per-lane stack entries in LDS
+    PT_STACK_DEPTH,             // 16 or 32 by tree depth, none spill; one workgroup per CU
+    PT_STACK_NODES,             // two workgroups per CU: 15 (the tree's whole node stack); one: 16, the rest spills
+    PT_STACK_SPILL,             // 16, the rest spills; the grid is as many workgroups as are resident
+    PT_STACK_16BIT,             // 15 16-bit entries (the tree's whole node stack); two workgroups per CU
+    PT_STACK_16BIT_SPILL };     // 8 - 15 16-bit entries, what the nodes leave; the rest spills; two workgroups per CU
+struct PtVariant { PtNodes nodes; PtWhere where; PtStack stack; bool own; };
+constexpr PtVariant kPtVariants[PT_VARIANT_COUNT] = {
+    {},                                                                 // (0: none)
+    {PT_NODES_EXACT,   PT_FROM_MEMORY, PT_STACK_SPILL,       false},    // PT_VARIANT_GLOBAL
+    {PT_NODES_EXACT,   PT_LDS_ALL,     PT_STACK_DEPTH,       false},    // PT_VARIANT_LDS
+    {PT_NODES_EXACT,   PT_LDS_NODES,   PT_STACK_NODES,       false},    // PT_VARIANT_LDS_NODES
+    {PT_NODES_EXACT,   PT_LDS_ALL,     PT_STACK_DEPTH,       true},     // PT_VARIANT_OWN_LDS
+    {PT_NODES_EXACT,   PT_LDS_NODES,   PT_STACK_NODES,       true},     // PT_VARIANT_OWN_LDS_NODES
+    {PT_NODES_QUANT,   PT_LDS_ALL,     PT_STACK_DEPTH,       true},     // PT_VARIANT_OWN_QLDS
+    {PT_NODES_QUANT,   PT_LDS_NODES,   PT_STACK_NODES,       true},     // PT_VARIANT_OWN_QLDS_NODES
+    {PT_NODES_QUANT,   PT_FROM_MEMORY, PT_STACK_SPILL,       true},     // PT_VARIANT_OWN_QGLOBAL
+    {PT_NODES_EXACT,   PT_FROM_MEMORY, PT_STACK_SPILL,       true},     // PT_VARIANT_OWN_GLOBAL
+    {PT_NODES_EXACT16, PT_LDS_NODES,   PT_STACK_16BIT,       true},     // PT_VARIANT_OWN_LDS16_NODES
+    {PT_NODES_QUANT16, PT_LDS_NODES,   PT_STACK_16BIT_SPILL, true},     // PT_VARIANT_OWN_QLDS16_NODES
+};
+inline const PtVariant &pt_variant(int v) { return kPtVariants[v > 0 && v < PT_VARIANT_COUNT ? v : 0]; }
+inline bool pt_quantised(const PtVariant &r) { return r.nodes == PT_NODES_QUANT || r.nodes == PT_NODES_QUANT16; }
+// the stack spills (the caller supplies TraverseConfig::spill) with `wgs` workgroups per CU
+inline bool pt_spills(const PtVariant &r, int wgs) {
+    return r.stack == PT_STACK_SPILL || r.stack == PT_STACK_16BIT_SPILL || (r.stack == PT_STACK_NODES && wgs == 1);
+}
+// dynamic LDS of one 1024-thread workgroup: [nodes][triangle images][stack: `entries` per lane]; none for the kernels that walk memory
+inline size_t pt_lds_bytes(const PtVariant &r, uint32_t n_nodes, uint32_t n_tris, int entries) {
+    if (r.where == PT_FROM_MEMORY) return 0;
+    const bool narrow = r.nodes == PT_NODES_EXACT16 || r.nodes == PT_NODES_QUANT16;
+    return (size_t)n_nodes * (pt_quantised(r) ? 32 : 64) + (r.where == PT_LDS_ALL ? (size_t)n_tris * 48 : 0) +
+           (size_t)entries * 1024 * (narrow ? sizeof(uint16_t) : sizeof(uint32_t));
+}
 
 struct TraverseConfig {
     int variant;            // PT_VARIANT_*
-    int stack_entries;      // 15 (two workgroups per CU only), 16, 32 or 64; PT_VARIANT_OWN_QLDS16_NODES: 8 ... 15
+    int stack_entries;      // per lane: 15, 16 or 32 (PtStack); PT_VARIANT_OWN_QLDS16_NODES: 8 ... 15
     int cull;               // 0/1
-    size_t lds_scene_bytes; // LDS variant: bytes of wnodes + tripos
-    int wgs_per_cu;         // node cache: 2 (small trees, whole stack in LDS) or 1 (mid-size trees, spilling stacks)
-    uint32_t *spill;        // global variant: per-lane overflow of the node stack, pt_spill_bytes(blocks) bytes
+    int wgs_per_cu;         // workgroups per CU of the LDS variants (PtStack). ptmi_stats reports variant * 10 + wgs_per_cu
+                            // (pt_variant_code), and leaves = 1 reports PT_VARIANT_GLOBAL and PT_VARIANT_LDS with 2 here
+    size_t lds_bytes;       // dynamic LDS per workgroup (pt_lds_bytes), set where the variant is chosen
+    uint32_t *spill;        // per-lane overflow of the node stack, pt_spill_bytes(blocks) bytes
     int wants_spill;        // the variant needs one (the caller supplies `spill`: each concurrently running kernel its own)
-    int quantized;          // global variant: walk the quantised image when the scene has one
+    int quantized;          // the variant walks quantised nodes (PT_VARIANT_GLOBAL: the quantised image, when the scene has one)
 };
+inline uint32_t pt_variant_code(const TraverseConfig &cfg) { return (uint32_t)cfg.variant * 10u + (uint32_t)cfg.wgs_per_cu; }
 #ifndef PT_QCACHE_NODES
 #define PT_QCACHE_NODES 256      /* quantised nodes of the top levels staged in LDS per workgroup (8 KB) */
 #endif

@@ -434,125 +434,93 @@ int build_image(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt, const ptmi_
     return PTMI_OK;
 }
 
-// per-lane LDS entries: the node stack (<= depth - 2 deferred siblings) plus room for filed leaves
-int stack_entries_for(uint32_t depth) { return depth + 2 <= 16 ? 16 : depth + 2 <= 24 ? 24 : depth + 2 <= 32 ? 32 : 64; }
-
-// Own leaves (traverse_own.hip): which memory variant a kernel runs as. Sizes: exact nodes 64 B, quantised 32 B, triangle images
-// 48 B, 4 KB of LDS per stack entry of a 1024-thread workgroup. PTMI_OWN_EXTEND / PTMI_OWN_SHADOW (a PT_VARIANT_OWN_* number) override
-// the choice where it fits — for same-box A/Bs, not for users.
-TraverseConfig own_config(const ptmi_ctx *c, bool closest_hit) {
-    TraverseConfig cfg{};
-    cfg.cull = c->opt.cull ? 1 : 0;
-    cfg.lds_scene_bytes = c->lds_scene_bytes;
-    cfg.wgs_per_cu = 1;
-    const uint32_t depth = std::max(c->own_depth, c->bvh_depth);      // slow rays walk the uploaded tree on the same stacks
-    const size_t ne = (size_t)c->sc.n_wnodes * 64, nq = (size_t)c->sc.n_wnodes * 32, tb = (size_t)c->sc.n_own_tris * 48;
-    const bool quant = c->own_quant;
-    const int full_stack = depth + 2 <= 16 ? 16 : depth + 2 <= 32 ? 32 : 0;
-    const size_t full_b = (size_t)full_stack * 4096, two_b = (size_t)15 * 4096, spill_b = (size_t)16 * 4096;
-    const bool two_ok = depth + 1 <= 15;                              // the whole node stack in 15 entries
-    // quantised nodes with compact references, two workgroups per CU: the 16-bit entries (2 KB each per workgroup) take what the nodes leave
-    int q16_entries = (c->sc.qnodes16 && nq + 64 < kLdsMax / 2) ? std::min<int>(15, (int)((kLdsMax / 2 - 64 - nq) / 2048)) : 0;
-    if (const char *e = std::getenv("PTMI_OWN_Q16_ENTRIES"))          // tests: a shorter stack than fits (more spills), never below 8 to pass `fits`
-        q16_entries = std::min(q16_entries, std::max(8, std::atoi(e)));
-    auto fits = [&](int variant, int wgs) -> bool {
-        switch (variant) {
-        case PT_VARIANT_OWN_LDS: return full_stack && ne + tb + full_b <= kLdsMax;
-        case PT_VARIANT_OWN_QLDS: return quant && full_stack && nq + tb + full_b <= kLdsMax;
-        case PT_VARIANT_OWN_LDS_NODES: return wgs == 2 ? two_ok && ne + two_b <= kLdsMax / 2 : ne + spill_b <= kLdsMax;
-        case PT_VARIANT_OWN_QLDS_NODES: return quant && (wgs == 2 ? two_ok && nq + two_b <= kLdsMax / 2 : nq + spill_b <= kLdsMax);
-        case PT_VARIANT_OWN_QGLOBAL: return quant;
-        case PT_VARIANT_OWN_GLOBAL: return true;
-        case PT_VARIANT_OWN_LDS16_NODES: return wgs == 2 && c->sc.wnodes16 != nullptr && two_ok && ne + two_b / 2 <= kLdsMax / 2;
-        case PT_VARIANT_OWN_QLDS16_NODES: return wgs == 2 && quant && q16_entries >= 8;
-        }
-        return false;
-    };
-    auto take = [&](int variant, int wgs) {
-        cfg.variant = variant; cfg.wgs_per_cu = wgs;
-        const bool lds_full = variant == PT_VARIANT_OWN_LDS || variant == PT_VARIANT_OWN_QLDS;
-        const bool global = variant == PT_VARIANT_OWN_QGLOBAL || variant == PT_VARIANT_OWN_GLOBAL;
-        const bool q16 = variant == PT_VARIANT_OWN_QLDS16_NODES;
-        cfg.stack_entries = q16 ? q16_entries : lds_full ? full_stack : wgs == 2 ? 15 : 16;      // (16-bit entries in the compact-reference variants)
-        cfg.wants_spill = (global || q16 || (!lds_full && wgs == 1)) ? 1 : 0;
-        cfg.quantized = (variant == PT_VARIANT_OWN_QLDS || variant == PT_VARIANT_OWN_QLDS_NODES || variant == PT_VARIANT_OWN_QGLOBAL || q16) ? 1 : 0;
-    };
-    const bool big = c->lds_scene_bytes > ((size_t)4 << 20);         // beyond an XCD's L2: the quantised nodes pay (traverse_config below)
-    if (c->opt.traversal == PTMI_TRAVERSAL_GLOBAL) { take(quant ? PT_VARIANT_OWN_QGLOBAL : PT_VARIANT_OWN_GLOBAL, 1); return cfg; }
-    if (c->opt.traversal == PTMI_TRAVERSAL_GLOBAL_EXACT) { take(PT_VARIANT_OWN_GLOBAL, 1); return cfg; }
-    if (c->opt.traversal == PTMI_TRAVERSAL_LDS) {
-        if (fits(PT_VARIANT_OWN_LDS, 1)) take(PT_VARIANT_OWN_LDS, 1);
-        else if (fits(PT_VARIANT_OWN_QLDS, 1)) take(PT_VARIANT_OWN_QLDS, 1);
-        else take(PT_VARIANT_OWN_GLOBAL, 1);                          // the caller reports that it does not fit
-        return cfg;
+// Sizes `variant` (pt_variant) on the uploaded scene with `wgs` workgroups per CU: the per-lane stack, whether it spills, the LDS it
+// launches with. False: it does not fit, or the scene has no image in its node format.
+bool size_variant(const ptmi_ctx *c, int variant, int wgs, TraverseConfig &cfg) {
+    const PtVariant &r = pt_variant(variant);
+    const uint32_t depth = c->sc.own ? std::max(c->own_depth, c->bvh_depth) : c->bvh_depth;   // slow rays walk the uploaded tree on the same stacks
+    int entries = 0;
+    bool ok = true;
+    switch (r.stack) {
+    case PT_STACK_DEPTH: entries = depth + 2 <= 16 ? 16 : depth + 2 <= 32 ? 32 : 0; ok = wgs == 1 && entries != 0; break;
+    case PT_STACK_NODES: entries = wgs == 2 ? 15 : 16; ok = wgs == 1 || (wgs == 2 && depth + 1 <= 15); break;
+    case PT_STACK_SPILL: entries = 16; ok = wgs == 1; break;
+    case PT_STACK_16BIT: entries = 15; ok = wgs == 2 && depth + 1 <= 15; break;
+    case PT_STACK_16BIT_SPILL: {
+        // the 16-bit entries (2 KB each per workgroup) take what the quantised nodes leave of a CU's half
+        const size_t nq = (size_t)c->sc.n_wnodes * 32;
+        entries = (c->sc.qnodes16 && nq + 64 < kLdsMax / 2) ? std::min<int>(15, (int)((kLdsMax / 2 - 64 - nq) / 2048)) : 0;
+        if (const char *e = std::getenv("PTMI_OWN_Q16_ENTRIES"))      // tests: a shorter stack than fits (more spills), never below 8
+            entries = std::min(entries, std::max(8, std::atoi(e)));
+        ok = wgs == 2 && entries >= 8;
+        break;
     }
-    if (const char *e = std::getenv(closest_hit ? "PTMI_OWN_EXTEND" : "PTMI_OWN_SHADOW")) {
-        const int raw = std::atoi(e);
-        // e.g. 7 = quantised nodes, one workgroup; 17 = two; 20 = exact nodes with compact references; 21 = quantised nodes with compact references
-        const int v = raw == 20 ? (int)PT_VARIANT_OWN_LDS16_NODES : raw == 21 ? (int)PT_VARIANT_OWN_QLDS16_NODES : raw % 10, w = raw >= 10 ? 2 : 1;
-        if (fits(v, w)) { take(v, w); return cfg; }
     }
-    struct Pick { int variant, wgs; };
-    // Both kernels are box-step heavy over own leaves (7 - 8 dependent node fetches per ray against 3 - 4 triangle tests) and gain from
-    // the second workgroup per CU — 8 waves per SIMD to cover them — more than from resident triangles (config 1, same box: any-hit
-    // kernel from two workgroups with quantised nodes 17.1 ms beside the main stream against 21.1 from the full image, +2 % overall)
-    static const Pick closest[] = {{PT_VARIANT_OWN_LDS_NODES, 2}, {PT_VARIANT_OWN_LDS16_NODES, 2}, {PT_VARIANT_OWN_QLDS_NODES, 2}, {PT_VARIANT_OWN_QLDS16_NODES, 2},
-                                   {PT_VARIANT_OWN_LDS, 1}, {PT_VARIANT_OWN_QLDS, 1}, {PT_VARIANT_OWN_QLDS_NODES, 1}, {PT_VARIANT_OWN_LDS_NODES, 1}};
-    static const Pick any[] = {{PT_VARIANT_OWN_LDS_NODES, 2}, {PT_VARIANT_OWN_LDS16_NODES, 2}, {PT_VARIANT_OWN_QLDS_NODES, 2}, {PT_VARIANT_OWN_QLDS16_NODES, 2},
-                               {PT_VARIANT_OWN_LDS, 1}, {PT_VARIANT_OWN_QLDS, 1}, {PT_VARIANT_OWN_QLDS_NODES, 1}, {PT_VARIANT_OWN_LDS_NODES, 1}};
-    if (!big) {
-        if (closest_hit) { for (const Pick &p : closest) if (fits(p.variant, p.wgs)) { take(p.variant, p.wgs); return cfg; } }
-        else for (const Pick &p : any) if (fits(p.variant, p.wgs)) { take(p.variant, p.wgs); return cfg; }
-    }
-    take((quant && big) ? PT_VARIANT_OWN_QGLOBAL : PT_VARIANT_OWN_GLOBAL, 1);
-    return cfg;
+    ok = ok && (!pt_quantised(r) || c->own_quant) && (r.nodes != PT_NODES_EXACT16 || c->sc.wnodes16 != nullptr);
+    cfg.variant = variant; cfg.wgs_per_cu = wgs; cfg.stack_entries = entries;
+    cfg.wants_spill = pt_spills(r, wgs) ? 1 : 0;
+    cfg.quantized = pt_quantised(r) ? 1 : 0;
+    cfg.lds_bytes = pt_lds_bytes(r, c->sc.n_wnodes, c->sc.own ? c->sc.n_own_tris : c->sc.n_tris, entries);
+    return ok && cfg.lds_bytes <= kLdsMax / (size_t)wgs;
 }
 
-// closest_hit: the extend kernel may take the node-cache variant (two workgroups per CU) when it fits
+// Which memory variant a traversal kernel runs as (closest_hit: the extend kernel, else the any-hit kernel). PTMI_OWN_EXTEND /
+// PTMI_OWN_SHADOW (a code as ptmi_stats reports it, pt_variant_code: 102 = PT_VARIANT_OWN_LDS16_NODES, two workgroups per CU) override
+// the choice of the own-leaf variants where it fits — for same-box A/Bs, not for users.
 TraverseConfig traverse_config(const ptmi_ctx *c, bool closest_hit) {
-    if (c->sc.own) return own_config(c, closest_hit);
+    const bool own = c->sc.own, big = c->lds_scene_bytes > ((size_t)4 << 20);       // big: beyond an XCD's L2
+    const int traversal = c->opt.traversal;
     TraverseConfig cfg{};
-    cfg.stack_entries = stack_entries_for(c->bvh_depth);
     cfg.cull = c->opt.cull ? 1 : 0;
-    cfg.lds_scene_bytes = c->lds_scene_bytes;
-    const bool have = c->sc.root_ref != PT_REF_NONE;
-    const int lds_stack = cfg.stack_entries <= 16 ? 16 : 32;              // the sizes the LDS kernels are built for
-    const bool fits = have && cfg.stack_entries <= 32 && c->lds_scene_bytes + (size_t)lds_stack * 1024 * 4 <= kLdsMax;
-    const int small_stack = c->bvh_depth + 1 <= 15 ? 15 : 16;  // node stack <= depth - 2, plus >= 3 entries for filed leaves
-    const bool node_cache = have && c->bvh_depth + 2 <= 16 &&
-                            (size_t)c->sc.n_wnodes * 64 + (size_t)small_stack * 1024 * 4 <= kLdsMax / 2;
-    cfg.spill = nullptr; cfg.wants_spill = 0; cfg.wgs_per_cu = 2;
+    auto pick = [&](int variant, int wgs) { return size_variant(c, variant, wgs, cfg); };
     // The quantised image pays where node fetches leave the L2 (measured: the 1 M-triangle scene, 67 MB, extend -16 %); a scene
     // that an XCD's 4 MiB L2 holds is bound by the ALUs, and decoding costs more than the bytes save (cornell_spheres walked
     // from global memory: shadow +30 %). AUTO decides by size; GLOBAL asks for the quantised image, GLOBAL_EXACT for the exact one.
-    cfg.quantized = c->opt.traversal == PTMI_TRAVERSAL_GLOBAL ||
-                    (c->opt.traversal == PTMI_TRAVERSAL_AUTO && c->lds_scene_bytes > ((size_t)4 << 20));
-    if (c->opt.traversal == PTMI_TRAVERSAL_GLOBAL || c->opt.traversal == PTMI_TRAVERSAL_GLOBAL_EXACT) cfg.variant = PT_VARIANT_GLOBAL;
-#ifndef PT_SHADOW_NODE_CACHE
-#define PT_SHADOW_NODE_CACHE 0
-#endif
-    // The any-hit kernel keeps the full LDS image, one workgroup per CU. From the node cache with two workgroups (80 scalar
-    // registers since round 2) it is as fast by itself (8.53 ms per 64 spp either way) but takes every wave slot of its CUs: beside it
-    // `shade` stretches from 16.5 to 18.3 ms and config 1 loses 4 % (9 767 -> 9 344); with one workgroup it is 40 % slower itself.
-    else if ((closest_hit || PT_SHADOW_NODE_CACHE) && node_cache && c->opt.traversal == PTMI_TRAVERSAL_AUTO) {
-        cfg.variant = PT_VARIANT_LDS_NODES; cfg.stack_entries = small_stack;
-    } else if (fits) {
-        cfg.variant = PT_VARIANT_LDS; cfg.stack_entries = lds_stack;
-    }
-    else if (have && closest_hit && c->opt.traversal == PTMI_TRAVERSAL_AUTO &&
-             (size_t)c->sc.n_wnodes * 64 + (size_t)16 * 1024 * 4 <= kLdsMax) {
-        // mid-size trees (up to 1536 wide nodes): all nodes in LDS, one workgroup per CU, stacks spill. Measured on
-        // cornell_spheres against the global variant: extend -6 %, shadow +5 % (so closest hit only)
-        cfg.variant = PT_VARIANT_LDS_NODES; cfg.wgs_per_cu = 1; cfg.stack_entries = 16; cfg.wants_spill = 1;
-    }
-    else cfg.variant = PT_VARIANT_GLOBAL;
-    if (cfg.variant == PT_VARIANT_GLOBAL) { cfg.stack_entries = 16; cfg.wants_spill = 1; }   // deeper stacks spill
-    return cfg;
+    const bool mem_quant = traversal == PTMI_TRAVERSAL_GLOBAL || (traversal == PTMI_TRAVERSAL_AUTO && big);
+    auto from_memory = [&]() {
+        if (!own) { pick(PT_VARIANT_GLOBAL, 1); cfg.quantized = mem_quant; cfg.wgs_per_cu = 2; }  // (2: the code leaves = 1 has always reported)
+        else pick(c->own_quant && mem_quant ? PT_VARIANT_OWN_QGLOBAL : PT_VARIANT_OWN_GLOBAL, 1);
+        return cfg;
+    };
+    if (traversal == PTMI_TRAVERSAL_GLOBAL || traversal == PTMI_TRAVERSAL_GLOBAL_EXACT) return from_memory();
+    if (own && traversal == PTMI_TRAVERSAL_AUTO)
+        if (const char *e = std::getenv(closest_hit ? "PTMI_OWN_EXTEND" : "PTMI_OWN_SHADOW")) {
+            int code = std::atoi(e);
+            // (the earlier short form, below every own-leaf code: 1 - 9 a variant with one workgroup per CU, + 10 with two; 20 / 21
+            // variants 10 / 11 with two)
+            if (code < 40) code = code == 20 ? 102 : code == 21 ? 112 : (code % 10) * 10 + (code >= 10 ? 2 : 1);
+            if (pt_variant(code / 10).own && pick(code / 10, code % 10)) return cfg;
+        }
+    struct Pick { int variant, wgs; };
+    // Own leaves: both kernels are box-step heavy (7 - 8 dependent node fetches per ray against 3 - 4 triangle tests) and gain from the
+    // second workgroup per CU — 8 waves per SIMD to cover them — more than from resident triangles (config 1, same box: any-hit kernel
+    // from two workgroups with quantised nodes 17.1 ms beside the main stream against 21.1 from the full image, +2 % overall)
+    static const Pick own_auto[] = {{PT_VARIANT_OWN_LDS_NODES, 2}, {PT_VARIANT_OWN_LDS16_NODES, 2}, {PT_VARIANT_OWN_QLDS_NODES, 2},
+                                    {PT_VARIANT_OWN_QLDS16_NODES, 2}, {PT_VARIANT_OWN_LDS, 1}, {PT_VARIANT_OWN_QLDS, 1},
+                                    {PT_VARIANT_OWN_QLDS_NODES, 1}, {PT_VARIANT_OWN_LDS_NODES, 1}};
+    static const Pick own_lds[] = {{PT_VARIANT_OWN_LDS, 1}, {PT_VARIANT_OWN_QLDS, 1}};
+    // The reference's leaves: the any-hit kernel keeps the full LDS image, one workgroup per CU. From the node cache with two
+    // workgroups (80 scalar registers since round 2) it is as fast by itself (8.53 ms per 64 spp either way) but takes every wave slot
+    // of its CUs: beside it `shade` stretches from 16.5 to 18.3 ms and config 1 loses 4 % (9 767 -> 9 344); with one workgroup it is
+    // 40 % slower itself. Mid-size trees (up to 1536 wide nodes, the last pick): all nodes in LDS, one workgroup per CU, stacks
+    // spill; measured on cornell_spheres against the global variant: extend -6 %, shadow +5 % (so closest hit only).
+    static const Pick ref_closest[] = {{PT_VARIANT_LDS_NODES, 2}, {PT_VARIANT_LDS, 1}, {PT_VARIANT_LDS_NODES, 1}};
+    static const Pick ref_lds[] = {{PT_VARIANT_LDS, 1}};
+    auto all = [](const auto &l) { return std::make_pair(std::begin(l), std::end(l)); };
+    const auto picks = traversal == PTMI_TRAVERSAL_LDS ? (own ? all(own_lds) : all(ref_lds))
+                     : own ? (big ? std::make_pair(own_auto, own_auto) : all(own_auto)) : closest_hit ? all(ref_closest) : all(ref_lds);
+    if (own || c->sc.root_ref != PT_REF_NONE)                       // (an empty scene with the reference's leaves: the global variant)
+        for (const Pick *p = picks.first; p != picks.second; p++)
+            if (pick(p->variant, p->wgs)) {
+                if (p->variant == PT_VARIANT_LDS) cfg.wgs_per_cu = 2;  // (the code leaves = 1 has always reported)
+                return cfg;
+            }
+    return from_memory();                   // PTMI_TRAVERSAL_LDS: the caller reports that the scene does not fit
 }
 
 // the radiance sits at 16-byte stride beside kernels that wait on node fetches from memory (pt_device.h DevPaths)
 bool walks_memory_quantised(const TraverseConfig &cfg) {
-    return cfg.quantized && (cfg.variant == PT_VARIANT_GLOBAL || cfg.variant == PT_VARIANT_OWN_QGLOBAL);
+    return cfg.quantized && pt_variant(cfg.variant).where == PT_FROM_MEMORY;
 }
 
 int check_ready(ptmi_ctx *c, bool need_output) {
@@ -914,7 +882,7 @@ int ptmi_dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames) {
     const bool side = nee && c->opt.overlap != 0;
     if (npix * F > 0xFFFFFF00ull) return fail(c, PTMI_E_UNSUPPORTED, "batch of %llu paths exceeds 2^32", (unsigned long long)(npix * F));
     const TraverseConfig cfg0 = traverse_config(c, true), cfg_shadow0 = traverse_config(c, false);
-    if (c->opt.traversal == PTMI_TRAVERSAL_LDS && cfg0.variant != PT_VARIANT_LDS && cfg0.variant != PT_VARIANT_OWN_LDS && cfg0.variant != PT_VARIANT_OWN_QLDS)
+    if (c->opt.traversal == PTMI_TRAVERSAL_LDS && pt_variant(cfg0.variant).where != PT_LDS_ALL)
         return fail(c, PTMI_E_UNSUPPORTED, "scene needs %zu B of LDS plus the stack; it does not fit in %zu B", c->lds_scene_bytes, kLdsMax);
     for (;;) {
         rc = ensure_capacity(c, ln, (size_t)(npix * F));
@@ -926,15 +894,11 @@ int ptmi_dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames) {
     }
     if (cfg0.wants_spill && !ln.d_spill) HIP_TRY(c, hipMalloc(&ln.d_spill, pt_spill_bytes(c->n_cu * 8)));          // 128 MiB on 256 CUs
     if (cfg_shadow0.wants_spill && !ln.d_spill_side) HIP_TRY(c, hipMalloc(&ln.d_spill_side, pt_spill_bytes(c->n_cu * 8)));
-#ifndef PT_L_STRIDE
-#define PT_L_STRIDE 0              /* 0: by scene (pt_device.h, DevPaths); 3 or 4 floats: fixed */
-#endif
-    const bool from_memory = cfg0.variant == PT_VARIANT_GLOBAL || cfg0.variant == PT_VARIANT_OWN_QGLOBAL || cfg0.variant == PT_VARIANT_OWN_GLOBAL;
-    c->st.traversal_used = from_memory ? PTMI_TRAVERSAL_GLOBAL : PTMI_TRAVERSAL_LDS;
-    c->st.extend_variant = (uint32_t)cfg0.variant * 10u + (uint32_t)cfg0.wgs_per_cu;
-    c->st.shadow_variant = (uint32_t)cfg_shadow0.variant * 10u + (uint32_t)cfg_shadow0.wgs_per_cu;
+    c->st.traversal_used = pt_variant(cfg0.variant).where == PT_FROM_MEMORY ? PTMI_TRAVERSAL_GLOBAL : PTMI_TRAVERSAL_LDS;
+    c->st.extend_variant = pt_variant_code(cfg0);
+    c->st.shadow_variant = pt_variant_code(cfg_shadow0);
     c->st.frames_per_batch_used = F;
-    c->st.radiance_stride_bytes = 4u * (PT_L_STRIDE ? (uint32_t)PT_L_STRIDE : ((walks_memory_quantised(cfg0) || walks_memory_quantised(cfg_shadow0)) ? 4u : 3u));
+    c->st.radiance_stride_bytes = (walks_memory_quantised(cfg0) || walks_memory_quantised(cfg_shadow0)) ? 16u : 12u;
     const int blocks = c->n_cu * 8;
 #ifndef PT_SHADE_WGS_PER_CU
 #define PT_SHADE_WGS_PER_CU 16
@@ -1165,11 +1129,11 @@ int ptmi_debug_intersect(ptmi_ctx *c, uint32_t n, const float *o3, const float *
     if (rc) return rc;
     HIP_TRY(c, hipMemcpyAsync(&ln.counts[0], &n, 4, hipMemcpyHostToDevice, c->stream));
     TraverseConfig cfg = traverse_config(c, true);
-    if (c->opt.traversal == PTMI_TRAVERSAL_LDS && cfg.variant != PT_VARIANT_LDS && cfg.variant != PT_VARIANT_OWN_LDS && cfg.variant != PT_VARIANT_OWN_QLDS)
+    if (c->opt.traversal == PTMI_TRAVERSAL_LDS && pt_variant(cfg.variant).where != PT_LDS_ALL)
         return fail(c, PTMI_E_UNSUPPORTED, "scene does not fit in LDS");
     if (cfg.wants_spill && !ln.d_spill) HIP_TRY(c, hipMalloc(&ln.d_spill, pt_spill_bytes(c->n_cu * 8)));
     cfg.spill = ln.d_spill;
-    c->st.extend_variant = (uint32_t)cfg.variant * 10u + (uint32_t)cfg.wgs_per_cu;
+    c->st.extend_variant = pt_variant_code(cfg);
     (c->sc.own ? pt_launch_extend_own : pt_launch_extend)(c->stream, c->n_cu * 8, cfg, c->sc, ln.paths, nullptr, &ln.counts[0], ln.hits);
     // (u, v) are not part of the hit record: rebuilt exactly as `shade` rebuilds them (into the C stream, unused here)
     pt_launch_hit_uv(c->stream, n, c->sc, ln.paths, ln.hits, ln.paths.C);
@@ -1205,7 +1169,7 @@ int ptmi_debug_occluded(ptmi_ctx *c, uint32_t n, const float *o3, const float *d
     TraverseConfig cfg = traverse_config(c, false);
     if (cfg.wants_spill && !ln.d_spill) HIP_TRY(c, hipMalloc(&ln.d_spill, pt_spill_bytes(c->n_cu * 8)));
     cfg.spill = ln.d_spill;
-    c->st.shadow_variant = (uint32_t)cfg.variant * 10u + (uint32_t)cfg.wgs_per_cu;
+    c->st.shadow_variant = pt_variant_code(cfg);
     (c->sc.own ? pt_launch_shadow_own : pt_launch_shadow)(c->stream, c->n_cu * 8, cfg, c->sc, ln.paths, ln.sh[0], nullptr, &ln.counts[0], ln.d_occ);
     HIP_TRY(c, hipMemcpyAsync(occ, ln.d_occ, n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, sync_all(c));

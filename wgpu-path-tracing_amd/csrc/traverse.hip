@@ -30,8 +30,6 @@
 #include "pt_device.h"
 #include "pt_math.h"
 #include "traverse_common.h"
-#include <atomic>
-#include <type_traits>
 
 namespace {
 
@@ -331,16 +329,8 @@ PT_DEV void trace_wave(const Mem &m, const DevScene &sc, const IO &io, uint32_t 
 // ------------------------------------------------------------------ global ----
 constexpr int GBLOCK = 256;
 
-#ifndef PT_GLOBAL_WAVES
-#define PT_GLOBAL_WAVES 0          /* > 0: ask the register allocator for at least that many waves per SIMD */
-#endif
-#if PT_GLOBAL_WAVES > 0
-#define PT_GLOBAL_ATTR __attribute__((amdgpu_waves_per_eu(PT_GLOBAL_WAVES)))
-#else
-#define PT_GLOBAL_ATTR
-#endif
 template <int MODE, bool CULL, int STACK, bool QUANT, class IO>
-__global__ __launch_bounds__(GBLOCK) PT_GLOBAL_ATTR void k_trace_global(DevScene sc, IO io, const uint32_t *__restrict__ count_ptr,
+__global__ __launch_bounds__(GBLOCK) void k_trace_global(DevScene sc, IO io, const uint32_t *__restrict__ count_ptr,
                                                          uint32_t *__restrict__ spill) {
     __shared__ uint32_t stk[STACK * GBLOCK];
     const uint32_t count = *count_ptr;
@@ -377,16 +367,8 @@ __global__ __launch_bounds__(GBLOCK) PT_GLOBAL_ATTR void k_trace_global(DevScene
 // triangle and miss the LDS-resident triangles); ptmi_api picks per kernel.
 constexpr int LBLOCK = 1024;
 
-#ifndef PT_LDS_WAVES
-#define PT_LDS_WAVES 0             /* > 0: ask the register allocator for at least that many waves per SIMD (8 = two 1024-thread workgroups per CU) */
-#endif
-#if PT_LDS_WAVES > 0
-#define PT_LDS_ATTR __attribute__((amdgpu_waves_per_eu(PT_LDS_WAVES)))
-#else
-#define PT_LDS_ATTR
-#endif
 template <int MODE, bool CULL, int STACK, bool TRIS_IN_LDS, bool SPILL, class IO>
-__global__ __launch_bounds__(LBLOCK) PT_LDS_ATTR void k_trace_lds(DevScene sc, IO io, const uint32_t *__restrict__ count_ptr,
+__global__ __launch_bounds__(LBLOCK) void k_trace_lds(DevScene sc, IO io, const uint32_t *__restrict__ count_ptr,
                                                       uint32_t *__restrict__ spill) {
     extern __shared__ float4 smem[];
     const uint32_t count = *count_ptr;
@@ -403,69 +385,37 @@ __global__ __launch_bounds__(LBLOCK) PT_LDS_ATTR void k_trace_lds(DevScene sc, I
                                            SPILL ? spill + (size_t)blockIdx.x * LBLOCK + threadIdx.x : nullptr, gridDim.x * LBLOCK);
 }
 
-template <int MODE, bool CULL, int STACK, bool TRIS, bool SPILL = false, class IO>
-void launch_lds(hipStream_t s, int wgs, size_t bytes, const DevScene &sc, const IO &io, const uint32_t *count,
-                uint32_t *spill = nullptr) {
-    // the default dynamic-LDS cap is 64 KB; raise it once per instantiation and device
-    static std::atomic<uint64_t> raised{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(raised.load(std::memory_order_relaxed) & bit)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trace_lds<MODE, CULL, STACK, TRIS, SPILL, IO>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        raised.fetch_or(bit, std::memory_order_relaxed);
-    }
-    hipLaunchKernelGGL((k_trace_lds<MODE, CULL, STACK, TRIS, SPILL, IO>), dim3(wgs), dim3(LBLOCK), bytes, s, sc, io, count, spill);
+// wgs workgroups of the LDS kernel; the variants that spill get the caller's spill area
+template <int MODE, bool CULL, int STACK, bool TRIS, bool SPILL, class IO>
+void launch_lds(hipStream_t s, int wgs, const TraverseConfig &cfg, const DevScene &sc, const IO &io, const uint32_t *count) {
+    allow_all_lds<k_trace_lds<MODE, CULL, STACK, TRIS, SPILL, IO>>();
+    hipLaunchKernelGGL((k_trace_lds<MODE, CULL, STACK, TRIS, SPILL, IO>), dim3(wgs), dim3(LBLOCK), cfg.lds_bytes, s, sc, io, count,
+                       SPILL ? cfg.spill : nullptr);
 }
-
-// The persistent grid of the global variant is exactly the workgroups that are resident at once: every workgroup
-// carries a full share of the queue, so one more per CU than fit runs a second, almost empty round. Sweep (extend, ms
-// per 64 spp, workgroups per CU; 16 LDS entries per lane + spill area):
-//   cornell_spheres  3: 34.7  4: 30.7  5: 28.6  6: 25.9  7: 33.1  8: 30.8
-//   grid_1m          3: 28.9  4: 24.9  5: 23.7  6: 23.1  7: 28.9  8: 27.1
-// 6 is what the kernel's registers allow (4 waves per workgroup, 6 waves per SIMD); the occupancy query reports it.
-// (Before the stacks could spill, depth-29 grid_1m needed 32 LDS entries per lane: 4 workgroups per CU, 23.8 ms.)
-constexpr int GLOBAL_WGS_MAX = 8;          // what the spill area is sized for
 template <int MODE, bool CULL, bool QUANT, class IO>
-void launch_global_q(hipStream_t s, int cus, const DevScene &sc, const IO &io, const uint32_t *count, uint32_t *spill) {
-    static int per_cu = 0;
-    if (per_cu == 0) {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_trace_global<MODE, CULL, 16, QUANT, IO>, GBLOCK, 0) != hipSuccess || n < 1) n = 6;
-        per_cu = n < GLOBAL_WGS_MAX ? n : GLOBAL_WGS_MAX;
-    }
+void launch_global(hipStream_t s, int cus, const DevScene &sc, const IO &io, const uint32_t *count, uint32_t *spill) {
+    const int per_cu = resident_wgs_per_cu<k_trace_global<MODE, CULL, 16, QUANT, IO>>(GBLOCK);
     hipLaunchKernelGGL((k_trace_global<MODE, CULL, 16, QUANT, IO>), dim3(per_cu * cus), dim3(GBLOCK), 0, s, sc, io, count, spill);
 }
-template <int MODE, bool CULL, class IO>
-void launch_global(hipStream_t s, int cus, const DevScene &sc, const IO &io, const uint32_t *count, uint32_t *spill, bool quant) {
-    if (quant && sc.qnodes) launch_global_q<MODE, CULL, true>(s, cus, sc, io, count, spill);
-    else launch_global_q<MODE, CULL, false>(s, cus, sc, io, count, spill);
-}
 
+// the config -> the kernel it names; sizes come from the config (ptmi_api.hip traverse_config)
 template <int MODE, bool CULL, class IO>
-void launch(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &sc, const IO &io,
-            const uint32_t *count) {
+void launch(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &sc, const IO &io, const uint32_t *count) {
     const int cus = blocks / 8 > 0 ? blocks / 8 : 1;
-    const size_t stack_bytes = (size_t)cfg.stack_entries * LBLOCK * sizeof(uint32_t);
+    const int wgs = cfg.wgs_per_cu * cus;
     if (cfg.variant == PT_VARIANT_LDS_NODES && cfg.wgs_per_cu == 1) {
         // mid-size trees: all wide nodes in LDS next to 16 stack entries per lane (deeper stacks spill), one workgroup per CU
-        const size_t bytes = (size_t)sc.n_wnodes * 64 + (size_t)16 * LBLOCK * sizeof(uint32_t);
-        launch_lds<MODE, CULL, 16, false, true>(s, cus, bytes, sc, io, count, cfg.spill);
+        launch_lds<MODE, CULL, 16, false, true>(s, wgs, cfg, sc, io, count);
     } else if (cfg.variant == PT_VARIANT_LDS_NODES) {          // node cache, two workgroups per CU
-        const size_t bytes = (size_t)sc.n_wnodes * 64 + stack_bytes;
-#ifndef PT_SHADOW_NODE_CACHE_WGS
-#define PT_SHADOW_NODE_CACHE_WGS 2
-#endif
-        const int wgs = (MODE == MODE_SHADOW ? PT_SHADOW_NODE_CACHE_WGS : 2) * cus;
-        if (cfg.stack_entries <= 15) launch_lds<MODE, CULL, 15, false>(s, wgs, bytes, sc, io, count);
-        else launch_lds<MODE, CULL, 16, false>(s, wgs, bytes, sc, io, count);
-    } else if (cfg.variant == PT_VARIANT_LDS) {                // everything resident, one workgroup per CU
-        const size_t bytes = cfg.lds_scene_bytes + stack_bytes;
-        if (cfg.stack_entries <= 16) launch_lds<MODE, CULL, 16, true>(s, cus, bytes, sc, io, count);
-        else launch_lds<MODE, CULL, 32, true>(s, cus, bytes, sc, io, count);
+        if (cfg.stack_entries <= 15) launch_lds<MODE, CULL, 15, false, false>(s, wgs, cfg, sc, io, count);
+        else launch_lds<MODE, CULL, 16, false, false>(s, wgs, cfg, sc, io, count);
+    } else if (cfg.variant == PT_VARIANT_LDS) {                // everything resident: one workgroup per CU, whatever wgs_per_cu reports
+        if (cfg.stack_entries <= 16) launch_lds<MODE, CULL, 16, true, false>(s, cus, cfg, sc, io, count);
+        else launch_lds<MODE, CULL, 32, true, false>(s, cus, cfg, sc, io, count);
+    } else if (cfg.quantized && sc.qnodes) {
+        launch_global<MODE, CULL, true>(s, cus, sc, io, count, cfg.spill);
     } else {
-        launch_global<MODE, CULL>(s, cus, sc, io, count, cfg.spill, cfg.quantized != 0);
+        launch_global<MODE, CULL, false>(s, cus, sc, io, count, cfg.spill);
     }
 }
 
@@ -473,22 +423,16 @@ void launch(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene
 
 void pt_launch_extend(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &sc, DevPaths p,
                       const uint32_t *queue, const uint32_t *count, float2 *hits) {
-    ExtendIO io{p.O, p.D, queue, hits};
-    if (cfg.cull) launch<MODE_EXTEND, true>(s, blocks, cfg, sc, io, count);
-    else launch<MODE_EXTEND, false>(s, blocks, cfg, sc, io, count);
+    launch_extend_io(cfg, p, queue, hits, [&](auto mode, auto cull, const auto &io) {
+        launch<decltype(mode)::value, decltype(cull)::value>(s, blocks, cfg, sc, io, count);
+    });
 }
 
 void pt_launch_shadow(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &sc, DevPaths p,
                       DevShadow sh, const uint32_t *shadow_queue, const uint32_t *count, uint8_t *occ) {
-    if (occ) {                                  // ptmi_debug_occluded (never with a queue)
-        OccludedIO io{sh.SO, occ, sh.cap};
-        if (cfg.cull) launch<MODE_SHADOW, true>(s, blocks, cfg, sc, io, count);
-        else launch<MODE_SHADOW, false>(s, blocks, cfg, sc, io, count);
-        return;
-    }
-    ShadowIO io{p.L, sh.SO, shadow_queue, p.l_stride, sh.cap};
-    if (cfg.cull) launch<MODE_SHADOW, true>(s, blocks, cfg, sc, io, count);
-    else launch<MODE_SHADOW, false>(s, blocks, cfg, sc, io, count);
+    launch_shadow_io(cfg, p, sh, shadow_queue, occ, [&](auto mode, auto cull, const auto &io) {
+        launch<decltype(mode)::value, decltype(cull)::value>(s, blocks, cfg, sc, io, count);
+    });
 }
 
 size_t pt_spill_bytes(int blocks) {

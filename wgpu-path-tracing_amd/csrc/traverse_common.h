@@ -4,6 +4,8 @@
 #pragma once
 #include "pt_device.h"
 #include "pt_math.h"
+#include <atomic>
+#include <type_traits>
 
 namespace {
 
@@ -168,5 +170,57 @@ struct OccludedIO {
     PT_DEV bool fetch(uint32_t &slot, v3 &o, v3 &d, float &tlim, uint32_t &) const { return fetch(slot, o, d, tlim); }
     PT_DEV void finish(uint32_t i, const Hit &h, bool occluded, uint32_t) const { finish(i, h, occluded); }
 };
+
+// ---- launch plumbing of both files -------------------------------------------------------------------------------------
+// The persistent grid of a kernel that walks memory is exactly the workgroups that are resident at once: every workgroup carries a
+// full share of the queue, so one more per CU than fit runs a second, almost empty round. Sweep (extend, ms per 64 spp, workgroups
+// per CU; 16 LDS entries per lane + spill area):
+//   cornell_spheres  3: 34.7  4: 30.7  5: 28.6  6: 25.9  7: 33.1  8: 30.8
+//   grid_1m          3: 28.9  4: 24.9  5: 23.7  6: 23.1  7: 28.9  8: 27.1
+// 6 is what the kernel's registers allow (4 waves per workgroup, 6 waves per SIMD); the occupancy query reports it.
+// (Before the stacks could spill, depth-29 grid_1m needed 32 LDS entries per lane: 4 workgroups per CU, 23.8 ms.)
+constexpr int GLOBAL_WGS_MAX = 8;          // what the spill area is sized for (traverse.hip pt_spill_bytes)
+template <auto K>
+int resident_wgs_per_cu(int threads) {
+    static std::atomic<int> per_cu[64];      // per device; ptmi_multi_dispatch launches from one thread per device
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::atomic<int> &slot = per_cu[dev & 63];
+    int n = slot.load(std::memory_order_relaxed);
+    if (n == 0) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, K, threads, 0) != hipSuccess || n < 1) n = 6;
+        n = n < GLOBAL_WGS_MAX ? n : GLOBAL_WGS_MAX;
+        slot.store(n, std::memory_order_relaxed);
+    }
+    return n;
+}
+// the default dynamic-LDS cap is 64 KB: raise it to a CU's 160 KB once per kernel and device
+template <auto K>
+void allow_all_lds() {
+    static std::atomic<uint64_t> raised{0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const uint64_t bit = 1ull << (dev & 63);
+    if (!(raised.load(std::memory_order_relaxed) & bit)) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        raised.fetch_or(bit, std::memory_order_relaxed);
+    }
+}
+// The extend / shadow entry points of both files: the ray source / sink and `cull` become template arguments of go(mode, cull, io),
+// a generic lambda over std::integral_constant that launches the file's kernels
+template <int MODE, class IO, class Go>
+void with_cull(const TraverseConfig &cfg, const IO &io, Go go) {
+    if (cfg.cull) go(std::integral_constant<int, MODE>{}, std::true_type{}, io);
+    else go(std::integral_constant<int, MODE>{}, std::false_type{}, io);
+}
+template <class Go>
+void launch_extend_io(const TraverseConfig &cfg, DevPaths p, const uint32_t *queue, float2 *hits, Go go) {
+    with_cull<MODE_EXTEND>(cfg, ExtendIO{p.O, p.D, queue, hits}, go);
+}
+template <class Go>
+void launch_shadow_io(const TraverseConfig &cfg, DevPaths p, DevShadow sh, const uint32_t *shadow_queue, uint8_t *occ, Go go) {
+    if (occ) with_cull<MODE_SHADOW>(cfg, OccludedIO{sh.SO, occ, sh.cap}, go);       // ptmi_debug_occluded (never with a queue)
+    else with_cull<MODE_SHADOW>(cfg, ShadowIO{p.L, sh.SO, shadow_queue, p.l_stride, sh.cap}, go);
+}
 
 }  // namespace

@@ -33,8 +33,6 @@
 #include "pt_device.h"
 #include "pt_math.h"
 #include "traverse_common.h"
-#include <atomic>
-#include <type_traits>
 
 namespace {
 
@@ -142,7 +140,8 @@ struct OwnQuantMem {
 // 1024-thread workgroup are then 30 KB instead of 60, and a tree of up to 780 EXACT nodes (59 vector instructions a box step instead of
 // the quantised nodes' 66) runs two workgroups per CU.
 // STACK = 0: `nstack` entries per lane, known at the launch only (the spill area holds 32-bit words: a 16-bit entry is widened there).
-template <int MODE, bool CULL, int STACK, bool SPILL, int REFILL, class Mem, class IO, class E>
+// FROM_MEMORY: the kernels that walk the scene from memory (k_own_global), with their own refill threshold and stream lengths.
+template <int MODE, bool CULL, int STACK, bool SPILL, bool FROM_MEMORY, class Mem, class IO, class E>
 PT_DEV void trace_wave_own(const Mem &m, const DevScene &sc, const IO &io, uint32_t count, uint32_t gw,
                            uint32_t total_waves, E *stk, int stride, uint32_t *spill = nullptr, uint32_t spill_lanes = 0, int nstack = 0) {
     constexpr bool R16 = sizeof(E) == 2;
@@ -175,7 +174,7 @@ PT_DEV void trace_wave_own(const Mem &m, const DevScene &sc, const IO &io, uint3
 #ifndef PT_OWN_NODE_KEEP_SHADOW
 #define PT_OWN_NODE_KEEP_SHADOW 4
 #endif
-    constexpr bool FROM_MEMORY = REFILL == PT_REFILL_GLOBAL && PT_REFILL_GLOBAL != PT_OWN_REFILL_AT;
+    constexpr int REFILL = FROM_MEMORY ? PT_REFILL_GLOBAL : PT_OWN_REFILL_AT;
     constexpr int NODE_KEEP = FROM_MEMORY ? (ANY ? 2 : 3) : (ANY ? PT_OWN_NODE_KEEP_SHADOW : PT_OWN_NODE_KEEP_EXTEND);
     constexpr int NODE_STEPS = PT_OWN_NODE_STEPS, LEAF_STEPS = PT_OWN_LEAF_STEPS, LEAF_KEEP = PT_OWN_LEAF_KEEP;
     const uint32_t lane = threadIdx.x & 63u;
@@ -409,22 +408,13 @@ PT_DEV void trace_wave_own(const Mem &m, const DevScene &sc, const IO &io, uint3
 // ------------------------------------------------------------------ kernels ----
 constexpr int GBLOCK = 256, LBLOCK = 1024;
 
-#ifndef PT_OWN_LDS_WAVES
-#define PT_OWN_LDS_WAVES 0
-#endif
-#if PT_OWN_LDS_WAVES > 0
-#define PT_OWN_LDS_ATTR __attribute__((amdgpu_waves_per_eu(PT_OWN_LDS_WAVES)))
-#else
-#define PT_OWN_LDS_ATTR
-#endif
-
 // LAYOUT: 0 exact nodes (64 B) in LDS, 1 quantised nodes (32 B) in LDS, 2 exact nodes with compact references and 16-bit entries,
 // 3 quantised nodes with compact references and `nstack` 16-bit entries (STACK = 0, SPILL).
 // TRIS: the triangle images in LDS too. Dynamic LDS: [nodes][triangles][STACK x 1024 entries]
-// (STACK = 15 is the footprint of two workgroups per CU: 8 waves per SIMD, which the register allocator has to be told — at most 64
-// vector registers; left alone the max-ILP scheduler takes 72)
+// (STACK = 15 and LAYOUT = 3 are the footprint of two workgroups per CU: 8 waves per SIMD, which the register allocator has to be
+// told — at most 64 vector registers)
 template <int MODE, bool CULL, int STACK, int LAYOUT, bool TRIS, bool SPILL, class IO>
-__global__ __launch_bounds__(LBLOCK) __attribute__((amdgpu_waves_per_eu((STACK == 15 || LAYOUT == 3) ? 8 : 4))) PT_OWN_LDS_ATTR void k_own_lds(const DevScene *__restrict__ scp, IO io, const uint32_t *__restrict__ count_ptr,
+__global__ __launch_bounds__(LBLOCK) __attribute__((amdgpu_waves_per_eu((STACK == 15 || LAYOUT == 3) ? 8 : 4))) void k_own_lds(const DevScene *__restrict__ scp, IO io, const uint32_t *__restrict__ count_ptr,
                                                                     uint32_t *__restrict__ spill, int nstack) {
     // The scene description is read from memory where it is needed (the root boxes and limits at a refill, the uploaded tree by slow
     // rays, the leaf-box table at a verification) instead of living in scalar registers for the whole kernel: passed by value the
@@ -446,34 +436,27 @@ __global__ __launch_bounds__(LBLOCK) __attribute__((amdgpu_waves_per_eu((STACK =
     if constexpr (LAYOUT == 2) {
         OwnLdsMem<TRIS> m{(lds_f4p)smem, (lds_f4p)(smem + nw), (glb_f4p)sc.tripos};
         uint16_t *stk16 = reinterpret_cast<uint16_t *>(smem + nw + nt) + threadIdx.x;
-        trace_wave_own<MODE, CULL, STACK, false, PT_OWN_REFILL_AT>(m, sc, io, count, gw, gridDim.x * (LBLOCK / 64), stk16, LBLOCK);
+        trace_wave_own<MODE, CULL, STACK, false, false>(m, sc, io, count, gw, gridDim.x * (LBLOCK / 64), stk16, LBLOCK);
     } else if constexpr (LAYOUT == 3) {
         OwnQuantMem<true, false> m{(lds_u4p)smem, (glb_u4p)sc.qnodes16, sc.n_wnodes, (lds_f4p)nullptr, (glb_f4p)sc.tripos,
                                    sc.q_origin[0], sc.q_origin[1], sc.q_origin[2], sc.q_scale[0], sc.q_scale[1], sc.q_scale[2]};
         uint16_t *stk16 = reinterpret_cast<uint16_t *>(smem + nw + nt) + threadIdx.x;
-        trace_wave_own<MODE, CULL, 0, true, PT_OWN_REFILL_AT>(m, sc, io, count, gw, gridDim.x * (LBLOCK / 64), stk16, LBLOCK, sp, gridDim.x * LBLOCK, nstack);
+        trace_wave_own<MODE, CULL, 0, true, false>(m, sc, io, count, gw, gridDim.x * (LBLOCK / 64), stk16, LBLOCK, sp, gridDim.x * LBLOCK, nstack);
     } else if constexpr (LAYOUT == 1) {
         OwnQuantMem<true, TRIS> m{(lds_u4p)smem, (glb_u4p)sc.qnodes, sc.n_wnodes, (lds_f4p)(smem + nw), (glb_f4p)sc.tripos,
                                   sc.q_origin[0], sc.q_origin[1], sc.q_origin[2], sc.q_scale[0], sc.q_scale[1], sc.q_scale[2]};
-        trace_wave_own<MODE, CULL, STACK, SPILL, PT_OWN_REFILL_AT>(m, sc, io, count, gw, gridDim.x * (LBLOCK / 64), stk, LBLOCK, sp, gridDim.x * LBLOCK);
+        trace_wave_own<MODE, CULL, STACK, SPILL, false>(m, sc, io, count, gw, gridDim.x * (LBLOCK / 64), stk, LBLOCK, sp, gridDim.x * LBLOCK);
     } else {
         OwnLdsMem<TRIS> m{(lds_f4p)smem, (lds_f4p)(smem + nw), (glb_f4p)sc.tripos};
-        trace_wave_own<MODE, CULL, STACK, SPILL, PT_OWN_REFILL_AT>(m, sc, io, count, gw, gridDim.x * (LBLOCK / 64), stk, LBLOCK, sp, gridDim.x * LBLOCK);
+        trace_wave_own<MODE, CULL, STACK, SPILL, false>(m, sc, io, count, gw, gridDim.x * (LBLOCK / 64), stk, LBLOCK, sp, gridDim.x * LBLOCK);
     }
 }
 
 template <int MODE, bool CULL, int STACK, int LAYOUT, bool TRIS, bool SPILL, class IO>
-void launch_own_lds(hipStream_t s, int wgs, size_t bytes, const DevScene *sc, const IO &io, const uint32_t *count, uint32_t *spill, int nstack = 0) {
-    static std::atomic<uint64_t> raised{0};      // the default dynamic-LDS cap is 64 KB; raise it once per instantiation and device
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(raised.load(std::memory_order_relaxed) & bit)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_own_lds<MODE, CULL, STACK, LAYOUT, TRIS, SPILL, IO>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        raised.fetch_or(bit, std::memory_order_relaxed);
-    }
-    hipLaunchKernelGGL((k_own_lds<MODE, CULL, STACK, LAYOUT, TRIS, SPILL, IO>), dim3(wgs), dim3(LBLOCK), bytes, s, sc, io, count, spill, nstack);
+void launch_own_lds(hipStream_t s, int cus, const TraverseConfig &cfg, const DevScene *sc, const IO &io, const uint32_t *count) {
+    allow_all_lds<k_own_lds<MODE, CULL, STACK, LAYOUT, TRIS, SPILL, IO>>();
+    hipLaunchKernelGGL((k_own_lds<MODE, CULL, STACK, LAYOUT, TRIS, SPILL, IO>), dim3(cfg.wgs_per_cu * cus), dim3(LBLOCK), cfg.lds_bytes, s,
+                       sc, io, count, SPILL ? cfg.spill : nullptr, STACK ? 0 : cfg.stack_entries);
 }
 
 // from global memory: 256-thread workgroups, 16 LDS entries per lane + the spill area; QUANT: quantised nodes, the top of the tree in LDS
@@ -493,54 +476,47 @@ __global__ __launch_bounds__(GBLOCK) void k_own_global(const DevScene *__restric
         if (gw * 64u >= count) return;
         OwnQuantMem<false, false> m{(lds_u4p)qcache, (glb_u4p)sc.qnodes, nc, (lds_f4p)nullptr, (glb_f4p)sc.tripos,
                                     sc.q_origin[0], sc.q_origin[1], sc.q_origin[2], sc.q_scale[0], sc.q_scale[1], sc.q_scale[2]};
-        trace_wave_own<MODE, CULL, 16, true, PT_REFILL_GLOBAL>(m, sc, io, count, gw, gridDim.x * (GBLOCK / 64), stk + threadIdx.x, GBLOCK, sp, gridDim.x * GBLOCK);
+        trace_wave_own<MODE, CULL, 16, true, true>(m, sc, io, count, gw, gridDim.x * (GBLOCK / 64), stk + threadIdx.x, GBLOCK, sp, gridDim.x * GBLOCK);
     } else {
         if (gw * 64u >= count) return;
         OwnGlobalMem m{(glb_f4p)sc.wnodes, (glb_f4p)sc.tripos};
-        trace_wave_own<MODE, CULL, 16, true, PT_REFILL_GLOBAL>(m, sc, io, count, gw, gridDim.x * (GBLOCK / 64), stk + threadIdx.x, GBLOCK, sp, gridDim.x * GBLOCK);
+        trace_wave_own<MODE, CULL, 16, true, true>(m, sc, io, count, gw, gridDim.x * (GBLOCK / 64), stk + threadIdx.x, GBLOCK, sp, gridDim.x * GBLOCK);
     }
 }
-constexpr int GLOBAL_WGS_MAX = 8;          // what the spill area is sized for (traverse.hip pt_spill_bytes)
 template <int MODE, bool CULL, bool QUANT, class IO>
 void launch_own_global(hipStream_t s, int cus, const DevScene *sc, const IO &io, const uint32_t *count, uint32_t *spill) {
-    static int per_cu = 0;                   // the persistent grid is exactly the workgroups that are resident at once (traverse.hip)
-    if (per_cu == 0) {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_own_global<MODE, CULL, QUANT, IO>, GBLOCK, 0) != hipSuccess || n < 1) n = 6;
-        per_cu = n < GLOBAL_WGS_MAX ? n : GLOBAL_WGS_MAX;
-    }
+    const int per_cu = resident_wgs_per_cu<k_own_global<MODE, CULL, QUANT, IO>>(GBLOCK);
     hipLaunchKernelGGL((k_own_global<MODE, CULL, QUANT, IO>), dim3(per_cu * cus), dim3(GBLOCK), 0, s, sc, io, count, spill);
 }
 
+// the config -> the kernel it names; sizes come from the config (ptmi_api.hip traverse_config)
 template <int MODE, bool CULL, class IO>
 void launch_own(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &hsc, const IO &io, const uint32_t *count) {
     const int cus = blocks / 8 > 0 ? blocks / 8 : 1;
     const DevScene *sc = hsc.self;              // the kernels read the description from device memory
-    const size_t node_bytes = (size_t)hsc.n_wnodes * (cfg.variant == PT_VARIANT_OWN_LDS || cfg.variant == PT_VARIANT_OWN_LDS_NODES || cfg.variant == PT_VARIANT_OWN_LDS16_NODES ? 64 : 32);
-    const size_t tri_bytes = (size_t)hsc.n_own_tris * 48;
-    const size_t stack_bytes = (size_t)cfg.stack_entries * LBLOCK * sizeof(uint32_t);
+    const bool two = cfg.wgs_per_cu == 2;
     switch (cfg.variant) {
     case PT_VARIANT_OWN_LDS:                    // exact nodes + triangles resident, one workgroup per CU
-        if (cfg.stack_entries <= 16) launch_own_lds<MODE, CULL, 16, 0, true, false>(s, cus, node_bytes + tri_bytes + stack_bytes, sc, io, count, nullptr);
-        else launch_own_lds<MODE, CULL, 32, 0, true, false>(s, cus, node_bytes + tri_bytes + stack_bytes, sc, io, count, nullptr);
+        if (cfg.stack_entries <= 16) launch_own_lds<MODE, CULL, 16, 0, true, false>(s, cus, cfg, sc, io, count);
+        else launch_own_lds<MODE, CULL, 32, 0, true, false>(s, cus, cfg, sc, io, count);
         break;
     case PT_VARIANT_OWN_LDS_NODES:              // exact nodes resident, triangles through L1 / L2
-        if (cfg.wgs_per_cu == 2) launch_own_lds<MODE, CULL, 15, 0, false, false>(s, 2 * cus, node_bytes + stack_bytes, sc, io, count, nullptr);
-        else launch_own_lds<MODE, CULL, 16, 0, false, true>(s, cus, node_bytes + stack_bytes, sc, io, count, cfg.spill);
+        if (two) launch_own_lds<MODE, CULL, 15, 0, false, false>(s, cus, cfg, sc, io, count);
+        else launch_own_lds<MODE, CULL, 16, 0, false, true>(s, cus, cfg, sc, io, count);
         break;
     case PT_VARIANT_OWN_QLDS:                   // quantised nodes + triangles resident, one workgroup per CU
-        if (cfg.stack_entries <= 16) launch_own_lds<MODE, CULL, 16, 1, true, false>(s, cus, node_bytes + tri_bytes + stack_bytes, sc, io, count, nullptr);
-        else launch_own_lds<MODE, CULL, 32, 1, true, false>(s, cus, node_bytes + tri_bytes + stack_bytes, sc, io, count, nullptr);
+        if (cfg.stack_entries <= 16) launch_own_lds<MODE, CULL, 16, 1, true, false>(s, cus, cfg, sc, io, count);
+        else launch_own_lds<MODE, CULL, 32, 1, true, false>(s, cus, cfg, sc, io, count);
         break;
     case PT_VARIANT_OWN_QLDS_NODES:             // quantised nodes resident, triangles through L1 / L2
-        if (cfg.wgs_per_cu == 2) launch_own_lds<MODE, CULL, 15, 1, false, false>(s, 2 * cus, node_bytes + stack_bytes, sc, io, count, nullptr);
-        else launch_own_lds<MODE, CULL, 16, 1, false, true>(s, cus, node_bytes + stack_bytes, sc, io, count, cfg.spill);
+        if (two) launch_own_lds<MODE, CULL, 15, 1, false, false>(s, cus, cfg, sc, io, count);
+        else launch_own_lds<MODE, CULL, 16, 1, false, true>(s, cus, cfg, sc, io, count);
         break;
     case PT_VARIANT_OWN_LDS16_NODES:            // exact nodes with compact references, 16-bit entries: two workgroups per CU
-        launch_own_lds<MODE, CULL, 15, 2, false, false>(s, 2 * cus, node_bytes + stack_bytes / 2, sc, io, count, nullptr);
+        launch_own_lds<MODE, CULL, 15, 2, false, false>(s, cus, cfg, sc, io, count);
         break;
     case PT_VARIANT_OWN_QLDS16_NODES:           // quantised nodes with compact references: two workgroups per CU, stack_entries 16-bit entries, spills
-        launch_own_lds<MODE, CULL, 0, 3, false, true>(s, 2 * cus, node_bytes + (size_t)cfg.stack_entries * LBLOCK * sizeof(uint16_t), sc, io, count, cfg.spill, cfg.stack_entries);
+        launch_own_lds<MODE, CULL, 0, 3, false, true>(s, cus, cfg, sc, io, count);
         break;
     case PT_VARIANT_OWN_QGLOBAL: launch_own_global<MODE, CULL, true>(s, cus, sc, io, count, cfg.spill); break;
     default: launch_own_global<MODE, CULL, false>(s, cus, sc, io, count, cfg.spill); break;
@@ -551,22 +527,16 @@ void launch_own(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevS
 
 void pt_launch_extend_own(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &sc, DevPaths p,
                           const uint32_t *queue, const uint32_t *count, float2 *hits) {
-    ExtendIO io{p.O, p.D, queue, hits};
-    if (cfg.cull) launch_own<MODE_EXTEND, true>(s, blocks, cfg, sc, io, count);
-    else launch_own<MODE_EXTEND, false>(s, blocks, cfg, sc, io, count);
+    launch_extend_io(cfg, p, queue, hits, [&](auto mode, auto cull, const auto &io) {
+        launch_own<decltype(mode)::value, decltype(cull)::value>(s, blocks, cfg, sc, io, count);
+    });
 }
 
 void pt_launch_shadow_own(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &sc, DevPaths p,
                           DevShadow sh, const uint32_t *shadow_queue, const uint32_t *count, uint8_t *occ) {
-    if (occ) {                                  // ptmi_debug_occluded (never with a queue)
-        OccludedIO io{sh.SO, occ, sh.cap};
-        if (cfg.cull) launch_own<MODE_SHADOW, true>(s, blocks, cfg, sc, io, count);
-        else launch_own<MODE_SHADOW, false>(s, blocks, cfg, sc, io, count);
-        return;
-    }
-    ShadowIO io{p.L, sh.SO, shadow_queue, p.l_stride, sh.cap};
-    if (cfg.cull) launch_own<MODE_SHADOW, true>(s, blocks, cfg, sc, io, count);
-    else launch_own<MODE_SHADOW, false>(s, blocks, cfg, sc, io, count);
+    launch_shadow_io(cfg, p, sh, shadow_queue, occ, [&](auto mode, auto cull, const auto &io) {
+        launch_own<decltype(mode)::value, decltype(cull)::value>(s, blocks, cfg, sc, io, count);
+    });
 }
 
 #ifdef PT_UTIL_STATS
