@@ -151,7 +151,8 @@ int ptmi_upload_scene(ptmi_ctx *ctx,
                       const ptmi_material *materials, uint32_t n_materials,
                       const ptmi_bvh_node *bvh_nodes, uint32_t n_nodes,
                       const ptmi_light *lights, uint32_t n_lights);
-/* Binding 6. texels: width*height RGBA, row-major, texel (0,0) first. NULL/0 removes the atlas. */
+/* Binding 6. texels: width*height RGBA, row-major, texel (0,0) first. NULL/0 removes the atlas. An unknown format or a
+ * width*height*texel size that does not fit in size_t gives PTMI_E_INVALID; a call that fails leaves the current atlas in place. */
 int ptmi_upload_atlas(ptmi_ctx *ctx, const void *texels, uint32_t width, uint32_t height, int format);
 /* Binding 0: (re)allocates the width*height*16-byte output buffer, zero-filled (renderer.ts:272-279, :496-510). */
 int ptmi_resize(ptmi_ctx *ctx, uint32_t width, uint32_t height);

@@ -299,7 +299,8 @@ def test_trace_path_log(oracle):
 
 @pytest.mark.parametrize("name,mis,bounces,ap", [("cornell", 1, 8, 0.001), ("cornell", 0, 4, 0.0), ("cornell_glass", 1, 8, 0.0),
                                                  ("feature_box", 1, 8, 0.05), ("cornell_spheres", 1, 8, 0.001),
-                                                 ("random_soup", 1, 8, 0.02)])
+                                                 ("random_soup", 1, 8, 0.02), ("texture_edges", 1, 8, 0.001),
+                                                 ("texture_edges_f32", 1, 8, 0.001), ("texture_edges", 0, 1, 0.0)])
 def test_literal_transcription_equals_the_strict_build(oracle_strict, oracle_literal, scene_factory, name, mis, bounces, ap):
     """Two literal restatements of pt.wgsl that share no code — pt_oracle.c's PT_STRICT build (the contract build's control flow
     with literal arithmetic: the shading state rebuilt once for the winning triangle, RNG by pointer, guarded 1024-entry stack)

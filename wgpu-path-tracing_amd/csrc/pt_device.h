@@ -234,6 +234,9 @@ PtPrepared *pt_prepare_scene(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt
                              const ptmi_bvh_node *nodes, uint32_t nn, const ptmi_light *lights, uint32_t nl, int *rc_out);
 int pt_install_scene(ptmi_ctx *c, const PtPrepared *p);      // allocates and copies on c's device; c keeps its old scene on failure
 void pt_free_prepared(PtPrepared *p);
+// bytes of a width x height atlas of `format` (ptmi_upload_atlas); PTMI_E_INVALID, with the reason in `why`, for an unknown
+// format or a size that does not fit in size_t
+int pt_atlas_bytes(uint32_t width, uint32_t height, int format, size_t *bytes, char *why, size_t why_len);
 hipStream_t pt_ctx_stream(ptmi_ctx *c);
 float4 *pt_ctx_output(ptmi_ctx *c);
 int pt_ctx_device(const ptmi_ctx *c);

@@ -11,6 +11,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <deque>
@@ -792,18 +793,54 @@ int ptmi_upload_scene(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt, const
     return rc;
 }
 
+}  // extern "C"
+
+int pt_atlas_bytes(uint32_t w, uint32_t h, int fmt, size_t *bytes, char *why, size_t why_len) {
+    *bytes = 0;
+    if (fmt != PTMI_ATLAS_RGBA16F && fmt != PTMI_ATLAS_RGBA32F) {
+        snprintf(why, why_len, "unknown atlas format %d", fmt);
+        return PTMI_E_INVALID;
+    }
+    const size_t texel = fmt == PTMI_ATLAS_RGBA16F ? 8 : 16;
+    if ((size_t)w > SIZE_MAX / texel / h) {
+        snprintf(why, why_len, "atlas of %ux%u texels does not fit in size_t", w, h);
+        return PTMI_E_INVALID;
+    }
+    *bytes = (size_t)w * h * texel;
+    return PTMI_OK;
+}
+
+extern "C" {
+
+// Everything is checked and the new texels are on the device before the old atlas goes: a failed call leaves the context's
+// atlas, its DevScene and the device copy of that as they were.
 int ptmi_upload_atlas(ptmi_ctx *c, const void *texels, uint32_t w, uint32_t h, int fmt) {
     if (!c) return PTMI_E_INVALID;
+    const bool remove = !texels || w == 0 || h == 0;
+    size_t bytes = 0;
+    if (!remove) {
+        char why[128];
+        if (pt_atlas_bytes(w, h, fmt, &bytes, why, sizeof why) != PTMI_OK) return fail(c, PTMI_E_INVALID, "%s", why);
+    }
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, sync_all(c));
+    void *fresh = nullptr;
+    if (!remove) {
+        HIP_TRY(c, hipMalloc(&fresh, bytes));
+        const hipError_t e = hipMemcpy(fresh, texels, bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            dfree(fresh);
+            return fail(c, PTMI_E_HIP, "atlas upload failed: %s (the previous atlas, if any, is still in place)", hipGetErrorString(e));
+        }
+    }
+    const hipError_t e = sync_all(c);                 // nothing in flight reads the old atlas any more
+    if (e != hipSuccess) {
+        dfree(fresh);
+        return fail(c, PTMI_E_HIP, "sync_all failed: %s", hipGetErrorString(e));
+    }
     dfree(c->d_atlas);
-    c->sc.atlas = nullptr; c->sc.atlas_w = c->sc.atlas_h = c->sc.atlas_fmt = 0;
-    if (!texels || w == 0 || h == 0) return PTMI_OK;
-    if (fmt != PTMI_ATLAS_RGBA16F && fmt != PTMI_ATLAS_RGBA32F) return fail(c, PTMI_E_INVALID, "unknown atlas format %d", fmt);
-    size_t bytes = (size_t)w * h * (fmt == PTMI_ATLAS_RGBA16F ? 8 : 16);
-    HIP_TRY(c, hipMalloc(&c->d_atlas, bytes));
-    HIP_TRY(c, hipMemcpy(c->d_atlas, texels, bytes, hipMemcpyHostToDevice));
-    c->sc.atlas = c->d_atlas; c->sc.atlas_w = w; c->sc.atlas_h = h; c->sc.atlas_fmt = (uint32_t)fmt;
+    c->d_atlas = fresh;
+    c->sc.atlas = fresh;
+    c->sc.atlas_w = remove ? 0u : w; c->sc.atlas_h = remove ? 0u : h; c->sc.atlas_fmt = remove ? 0u : (uint32_t)fmt;
     HIP_TRY(c, hipMemcpy(c->d_scene, &c->sc, sizeof(DevScene), hipMemcpyHostToDevice));
     return PTMI_OK;
 }

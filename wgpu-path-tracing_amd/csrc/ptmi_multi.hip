@@ -252,6 +252,11 @@ int ptmi_multi_upload_scene(ptmi_multi *m, const ptmi_triangle *tris, uint32_t n
 
 int ptmi_multi_upload_atlas(ptmi_multi *m, const void *texels, uint32_t w, uint32_t h, int fmt) {
     if (!m) return PTMI_E_INVALID;
+    if (texels && w != 0 && h != 0) {       // checked once, before any device changes: a rejected atlas leaves every shard's in place
+        size_t bytes = 0;
+        char why[128];
+        if (pt_atlas_bytes(w, h, fmt, &bytes, why, sizeof why) != PTMI_OK) return mfail(m, PTMI_E_INVALID, "%s", why);
+    }
     for (size_t i = 0; i < m->ctx.size(); i++) {
         int rc = ptmi_upload_atlas(m->ctx[i], texels, w, h, fmt);
         if (rc) return cfail(m, (int)i, rc, "ptmi_upload_atlas");

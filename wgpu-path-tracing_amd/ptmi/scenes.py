@@ -11,6 +11,8 @@ Scenes
   grid_1m()           Cornell shell + 708x708 displaced height-field (999 698 + 12 triangles)
   feature_box()       small scene touching every branch of the shader (glass, metal,
                       textures incl. a normal map, point + directional + emissive lights)
+  texture_edges()     the atlas lookup at its edges: non-square atlases (f16 or f32), rects at and
+                      past the last row and column, f16 specials, an emissive-mapped probe wall
 """
 from dataclasses import dataclass, field
 
@@ -26,7 +28,7 @@ class Scene:
     mats: np.ndarray
     nodes: np.ndarray
     lights: np.ndarray
-    atlas: np.ndarray = None            # (H, W, 4) float16, or None
+    atlas: np.ndarray = None            # (H, W, 4) float16 or float32, or None
     bvh_depth: int = 0
     info: dict = field(default_factory=dict)
 
@@ -374,8 +376,138 @@ def cornell_enclosed():
     return _finish("cornell_enclosed", [base.tris, room], base.mats)
 
 
+# f16 values texture_edges places at known texels: signed zeros, the smallest and largest subnormal, the largest finite value,
+# infinities, a NaN and negative values; each sits in the red channel beside positive green / blue, so an emissive probe shows it
+_F16_SPECIALS = (0.0, -0.0, 2.0 ** -24, 1023 * 2.0 ** -24, 65504.0, np.inf, -np.inf, np.nan, -0.75, -65504.0)
+# ... and what only the f32 atlas holds
+_F32_SPECIALS = (1.0 + 2.0 ** -20, 1e-40, 3e38, -1e-40)
+_ULP_HALF_UP, _ULP_HALF_DOWN, _ULP_ONE_DOWN = 2.0 ** -11, 2.0 ** -12, 2.0 ** -11
+
+
+def texture_edge_rects(W, H):
+    """The material rects of texture_edges for a W x H atlas (x, y, w, h), by name."""
+    a, b = max(1, W // 3), max(1, H // 3)
+    return {
+        "inside": (W // 4, H // 4, max(1, W // 2), max(1, H // 2)),
+        "end": (W - a, H - b, a, b),                                  # its last texel is the atlas's last column and row
+        "cross": (W - max(1, W // 4), H - max(1, H // 4), 2 * max(1, W // 4), 2 * max(1, H // 4)),
+        "outside": (W, 0, 2, 2),
+        "none": (0xFFFFFFFF, 0, 4, 4),                                # the host packer's "no texture" with w, h > 0
+        "one": (W - 1, H - 1, 1, 1),
+        "w0": (0, 0, 0, max(1, H // 2)),
+        "h0": (0, 0, max(1, W // 2), 0),
+        "huge": (0, 0, 0x80000000, 1),
+        "specials": (0, H - _special_block(W, H)[1], *_special_block(W, H)),
+        "normal": (W - 2, 0, 2, 2),
+    }
+
+
+def _special_block(W, H, n=15):
+    """(columns, rows) of the block at the atlas's left edge that holds the n special texels"""
+    cols = 1 if W < 8 else max(4, -(-n // H))
+    return cols, -(-n // cols)
+
+
+def _edge_atlas(W, H, fmt):
+    """Every texel distinct (red from x mod 1024, green from y mod 1024, blue from the rest of x and y, all in [0.5, 0.56],
+    exact in f16; the f32 build adds 2^-16, which f16 cannot hold), then the specials block and the flat-normal block."""
+    yy, xx = np.mgrid[0:H, 0:W]
+    a = np.empty((H, W, 4), np.float64)
+    a[..., 0] = 0.5 + (xx % 1024) / 2048.0
+    a[..., 1] = 0.5 + (yy % 1024) / 2048.0
+    a[..., 2] = 0.5 + (xx // 1024 + 65 * (yy // 1024)) / 2048.0
+    a[..., 3] = 1.0
+    if fmt == "f32":
+        a[..., :3] += 2.0 ** -16
+    r = texture_edge_rects(W, H)
+    sx, sy, sw, sh = r["specials"]
+    vals = list(_F16_SPECIALS) + (list(_F32_SPECIALS) if fmt == "f32" else [])
+    vals.append("dark")                                               # no component > 0: not emissive
+    assert len(vals) <= sw * sh
+    for k, v in enumerate(vals):
+        tx, ty = sx + k % sw, sy + k // sw
+        a[ty, tx] = (-0.5, -0.0, 0.0, 1.0) if v == "dark" else (v, 0.25 + k / 64.0, 0.125, 1.0)
+    nx, ny = r["normal"][:2]
+    h = 0.5
+    for (dx, dy), t in zip(((0, 0), (1, 0), (0, 1), (1, 1)),
+                           ((h, h, 1.0), (h + _ULP_HALF_UP, h, 1.0), (h, h - _ULP_HALF_DOWN, 1.0), (h, h, 1.0 - _ULP_ONE_DOWN))):
+        if ny + dy < H:
+            a[ny + dy, nx + dx, :3] = t
+    with np.errstate(over="ignore"):
+        return np.ascontiguousarray(a.astype(np.float16 if fmt == "f16" else np.float32))
+
+
+def _uv_quad(p0, p1, p2, p3, normal, mat, uv):
+    """_quad with the corner UVs (p0 .. p3) given."""
+    t = _quad(p0, p1, p2, p3, normal, mat)
+    p = np.array([p0, p1, p2, p3], np.float32)
+    uv = np.asarray(uv, np.float32)
+    for tri in t:                                          # _quad may have reordered the corners: match UVs by position
+        for k in ("0", "1", "2"):
+            i = int(np.flatnonzero((p == tri["v" + k]).all(axis=1))[0])
+            tri["uv" + k] = uv[i]
+    return t
+
+
+def texture_edges(atlas_shape=(67, 29), fmt="f16"):
+    """The texture lookup at its edges (shade.hip texture_color / atlas_load): a non-square atlas (W, H) = atlas_shape of
+    distinct texels with f16 specials (and, for fmt="f32", values f16 cannot hold), rects inside, at, across and outside its
+    last row and column, the packer's "no texture", 1 x 1, zero and 2^31 sizes; all four maps, emissive maps included.
+    A wall of emissive probe quads (one per rect, plus the inside rect under UVs from -2.5 to 3.5, exact integers and -0.0,
+    1 - 2^-24, 1e7 .. 1e8 and inf / NaN) faces the camera; below it textured non-emissive quads and boxes, a normal-map
+    rect of the flat value (0.5, 0.5, 1) beside its one-ulp neighbours and a triangle whose three UVs are equal. Lit by a
+    point light and an emissive ceiling quad."""
+    W, H = atlas_shape
+    atlas = _edge_atlas(W, H, fmt)
+    r = texture_edge_rects(W, H)
+    probe_rects = ["inside", "end", "cross", "outside", "none", "one", "w0", "h0", "huge", "specials"]
+    unit = [(0, 0), (1, 0), (1, 1), (0, 1)]
+    one_below = float(np.float32(1.0 - 2.0 ** -24))
+    uv_sets = [
+        [(-2.5, -2.5), (3.5, -2.5), (3.5, 3.5), (-2.5, 3.5)],
+        [(-1.0, -0.0), (2.0, -0.0), (2.0, 3.0), (-1.0, 3.0)],
+        [(0.0, 0.0), (one_below, 0.0), (one_below, one_below), (0.0, one_below)],
+        [(1e7, 1e7), (1e8, 1e7), (1e8, 1e8), (1e7, 1e8)],
+        [(np.inf, 0.5), (0.5, 0.5), (0.5, np.nan), (0.5, 0.5)],
+    ]
+    mats = [_material(_WHITE)]
+    for name in probe_rects:
+        mats.append(_material((1, 1, 1), emission=(1, 1, 1), strength=1.0, emissive_map=r[name]))
+    m_probe = {name: 1 + i for i, name in enumerate(probe_rects)}
+    m_tex_a = len(mats); mats.append(_material((1, 1, 1), roughness=0.6, albedo_map=r["inside"], pbr_map=r["end"],
+                                               normal_map=r["normal"]))
+    m_tex_b = len(mats); mats.append(_material((0.9, 0.8, 0.7), metallic=1.0, roughness=1.0, albedo_map=r["cross"],
+                                               pbr_map=r["inside"], normal_map=r["inside"]))
+    m_tex_c = len(mats); mats.append(_material((0.8, 0.9, 0.8), albedo_map=r["specials"], pbr_map=r["one"],
+                                               normal_map=r["huge"]))
+    m_light = len(mats); mats.append(_material(_WHITE, emission=(1, 1, 1), strength=6.0))
+    parts = []
+    z, cols, w_, h_ = -0.5, 5, 0.96, 0.68
+    probes = [(m_probe[n], unit) for n in probe_rects] + [(m_probe["inside"], uv) for uv in uv_sets]
+    for k, (m, uv) in enumerate(probes):
+        x0 = -2.5 + (k % cols) * (w_ + 0.02)
+        y0 = 2.92 - (k // cols + 1) * (h_ + 0.02)
+        parts.append(_uv_quad((x0, y0, z), (x0 + w_, y0, z), (x0 + w_, y0 + h_, z), (x0, y0 + h_, z), (0, 0, 1), m, uv))
+    # textured floor (the flat-normal rect tiled), boxes and the equal-UV triangle
+    fl = [(-2.0, 0.0, -1.0), (2.0, 0.0, -1.0), (2.0, 0.0, 2.0), (-2.0, 0.0, 2.0)]
+    parts.append(_uv_quad(*fl, (0, 1, 0), m_tex_a, [(0, 0), (5.5, 0), (5.5, 4.25), (0, 4.25)]))
+    parts.append(_box((-0.8, 0.2, 0.3), (0.4, 0.4, 0.4), m_tex_b))
+    parts.append(_box((0.8, 0.15, 0.4), (0.5, 0.3, 0.3), m_tex_c))
+    tri = _tri_array(np.array([[(0.0, 0.05, 0.9), (0.3, 0.05, 0.6), (0.0, 0.45, 0.7)]], np.float32),
+                     np.array([[(0.0, 0.3, 1.0)] * 3], np.float32), np.full((1, 3, 2), 0.3, np.float32), m_tex_b)
+    parts.append(tri)
+    parts.append(_quad((-0.6, 3.0, -0.8), (0.6, 3.0, -0.8), (0.6, 3.0, 1.2), (-0.6, 3.0, 1.2), (0, -1, 0), m_light))
+    punctual = np.zeros(1, layout.LIGHT)
+    punctual[0]["position"], punctual[0]["light_type"] = (0.4, 1.6, 1.5), layout.LIGHT_POINT
+    punctual[0]["color"], punctual[0]["intensity"] = (1.0, 0.9, 0.8), 2.5
+    name = "texture_edges" + ("_f32" if fmt == "f32" else "") + ("" if tuple(atlas_shape) == (67, 29) else "_%dx%d" % (W, H))
+    return _finish(name, parts, mats, punctual=punctual, atlas=atlas,
+                   info={"atlas_shape": (W, H), "fmt": fmt, "probe_materials": sorted(m_probe.values())})
+
+
 SCENES = {"cornell": cornell, "cornell_glass": lambda: cornell(glass=True), "cornell_enclosed": cornell_enclosed,
-          "cornell_spheres": cornell_spheres, "grid_1m": grid_1m, "feature_box": feature_box, "deep_chain": deep_chain}
+          "cornell_spheres": cornell_spheres, "grid_1m": grid_1m, "feature_box": feature_box, "deep_chain": deep_chain,
+          "texture_edges": texture_edges, "texture_edges_f32": lambda: texture_edges(fmt="f32")}
 
 
 def make(name):
