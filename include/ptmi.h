@@ -80,11 +80,18 @@ typedef struct ptmi_options {
                                    2 = library default (currently 1) */
     uint32_t reserved_b[4];     /* must be 0 (ABI 3: worklist, tails, state, pipeline — four ways to compute the same bits, each measured
                                    slower or level and removed in round 4; numbers and the last commit that had them: profiles/README.md) */
-    uint32_t tree_builder;      /* read by ptmi_upload_scene: who builds the traversal hierarchy over the uploaded leaves (when
-                                   keep_reference_tree = 0). 1 = the host (full-sweep / binned SAH + rotations, threaded: 137 ms for the
-                                   334 174 leaves of the 1 M-triangle scene); 2 = the GPU (Morton-order linear BVH: radix sort + radix
-                                   tree + bottom-up fit, a few ms) — the same leaves and exact unions, hence the same results; a
-                                   Morton tree tests more boxes per ray (profiles/README.md). 0 = library default (1) */
+    uint32_t tree_builder;      /* read by ptmi_upload_scene: who builds the hierarchy the traversal walks (when keep_reference_tree = 0).
+                                   1 = the host. leaves = 1: full-sweep / binned SAH + rotations over the uploaded leaves (137 ms for the
+                                   334 174 leaves of the 1 M-triangle scene); leaves = 2: the same over the triangles, collapsed into own
+                                   leaves (313 ms for that scene).
+                                   2 = the GPU. leaves = 1: Morton-order linear BVH over the uploaded leaves (radix sort + radix tree +
+                                   bottom-up fit, a few ms); leaves = 2: for scenes above 4 096 triangles, PLOC clustering of the
+                                   triangles (Morton-sorted, nearest neighbour in a window of +-16), collapsed with the host's cost model,
+                                   padded and quantised on the device; smaller scenes, which get the 16-bit images and whose LDS variant
+                                   turns on a few tens of nodes, keep the host builder (a few ms).
+                                   Either way the results are the same (any topology over conservative boxes); only the
+                                   work per ray differs (profiles/README.md). A device build that fails (allocation, more than 60 levels)
+                                   falls back to the host; ptmi_stats.tree_builder_used reports who built. 0 = library default (1) */
     /* ABI 4 */
     uint32_t leaves;            /* read by ptmi_upload_scene: which leaves the traversal kernels test triangles in.
                                    1 = the uploaded BVH's own leaves (bvh.ts:86-127 cuts <= 4 triangles from 11 equal-count candidates on one
@@ -133,7 +140,10 @@ typedef struct ptmi_stats {
     /* leaves = 2: closest hits / occluders whose reference leaf's box did not pass and rays that were therefore traced again over the
      * uploaded tree (both kernels together), since the last reset */
     uint64_t verify_failed;
-    uint32_t reserved_stats[2];
+    uint32_t tree_builder_used; /* who built the hierarchy the last upload's regular rays walk: 1 the host, 2 the device (both leaf modes);
+                                   0 none: the uploaded tree is walked as it is (keep_reference_tree, an empty scene, a tree with
+                                   non-finite boxes) */
+    uint32_t reserved_stats[1];
 } ptmi_stats;
 
 /* ---- lifetime ----------------------------------------------------------- */
@@ -294,6 +304,10 @@ typedef struct ptmi_image_info {
 int ptmi_debug_build_image(const ptmi_triangle *triangles, uint32_t n_triangles, const ptmi_bvh_node *bvh_nodes, uint32_t n_nodes,
                            const ptmi_options *opt, ptmi_image_info *info, float *wnodes16, uint32_t *qnodes8, float *tripos12,
                            float *leafbox8);
+/* The traversal image the context's last ptmi_upload_scene put on its device, read back with the conventions of ptmi_debug_build_image
+ * (NULL buffers: only *info, for the sizes; leafbox8 has the uploaded scene's n_triangles rows). Before any upload *info is all zero.
+ * Synchronises. */
+int ptmi_debug_read_image(ptmi_ctx *ctx, ptmi_image_info *info, float *wnodes16, uint32_t *qnodes8, float *tripos12, float *leafbox8);
 /* arithmetic-contract probe: out[i] = op(a[i], b[i], c[i]) evaluated on the device.
  * ops: 0 a/b, 1 sqrt(a), 2 fma(a,b,c), 3 min(a,b), 4 max(a,b), 5 sin(a), 6 cos(a),
  *      7 pow5(a), 8 f32(u32 bits of a), 9 u32(a) as bits, 10 a - trunc(a), 11 tan(a), 12 1/a (the kernels' short form) */

@@ -60,9 +60,12 @@ def _p(a):
 class Image:
     """A traversal image on the host + the struct own_sim.c reads (keeps the arrays alive)."""
 
-    def __init__(self, scene, leaves, leaf_tris=0):
+    def __init__(self, scene, leaves, leaf_tris=0, arrays=None):
+        """arrays: an image as native.build_image returns it, e.g. read back from a device (Context.read_image), instead of the
+        host build of (leaves, leaf_tris)"""
         self.scene = scene
-        self.info, self.wn, self.qn, self.tp, self.lb = native.build_image(scene, leaves=leaves, leaf_tris=leaf_tris)
+        self.info, self.wn, self.qn, self.tp, self.lb = arrays if arrays is not None else \
+            native.build_image(scene, leaves=leaves, leaf_tris=leaf_tris)
         e = self.tp[:, [4, 5, 6, 8, 9, 10]].astype(np.float64).reshape(-1, 3)
         emax2 = float((e * e).sum(axis=1).max()) if len(e) else 0.0
         s = SimScene()

@@ -4,6 +4,19 @@
 #include <stdint.h>
 #include <vector>
 
+#ifndef PT_OWN_C_BOX
+#define PT_OWN_C_BOX 1.0             /* own leaves' cost model: a box-pair step (the unit) */
+#endif
+#ifndef PT_OWN_C_TRI
+#define PT_OWN_C_TRI 0.9             /* ... one triangle test (54 against ~60 vector instructions) */
+#endif
+#ifndef PT_OWN_C_OPEN
+#define PT_OWN_C_OPEN 0.35           /* ... opening a leaf (its entry leaves the lane's list, the loop is set up, a share of a vote) */
+#endif
+#ifndef PT_OWN_PAD_LOG2
+#define PT_OWN_PAD_LOG2 (-16)        /* own leaves' boxes grow by 2^this x the largest coordinate magnitude of the scene */
+#endif
+
 struct PtFastLeaf {
     float mn[3], mx[3];     // the leaf's own box, as stored in the reference node
     uint32_t ref;           // PT_REF_LEAF | (count-1) << 26 | first triangle
@@ -52,6 +65,26 @@ struct ptmi_triangle;
 // depth_limit: most levels (leaves included) the tree may have. false: a vertex is not finite (the caller keeps the reference's leaves).
 bool pt_build_own_tree(const ptmi_triangle *tris, const std::vector<uint32_t> &which, uint32_t max_leaf, uint32_t depth_limit,
                        PtOwnTree &out);
+// The same tree built on the device `s` belongs to (own_tree_gpu.hip; ptmi_options.tree_builder = 2), from the device copy of the
+// triangles: Morton-sorted clusters merged by PLOC, collapsed with the host's cost model, emitted and quantised in place. The device
+// buffers have the layouts of PtOwnTree::wnodes / tripos and of pt_quantize_nodes (qnodes: NULL when the scene has no quantised image);
+// pad, safe_origin and the root box equal the host build's bit for bit (they depend on the triangle set only). Synchronises the stream.
+// false: could not (a non-finite vertex, more than depth_limit levels, an allocation or HIP failure); nothing is left allocated.
+struct PtOwnTreeGpu {
+    float4 *wnodes = nullptr, *tripos = nullptr;
+    uint4 *qnodes = nullptr;
+    uint32_t n_wnodes = 0, n_tris = 0, root_ref = 0xFFFFFFFFu, depth = 0, n_leaves = 0, max_leaf_tris = 0, q_top = 0;
+    bool quantised = false;
+    float root_min[3] = {0, 0, 0}, root_max[3] = {0, 0, 0};
+    float pad = 0.0f, safe_origin = 0.0f;
+    float q_origin[3] = {0, 0, 0}, q_scale[3] = {0, 0, 0};
+    void release();                        // frees the device buffers (hipFree) and resets the fields
+};
+bool pt_build_own_tree_gpu(const ptmi_triangle *d_tris, const std::vector<uint32_t> &which, uint32_t max_leaf, uint32_t depth_limit,
+                           hipStream_t s, PtOwnTreeGpu &out);
+// The 16-bit grid of pt_quantize_nodes over the bounds [mn, mx]: origin = mn, the smallest scale whose last plane reaches mx (checked
+// with fmaf). false: the bounds are not finite.
+bool pt_quant_grid(const float mn[3], const float mx[3], float origin[3], float scale[3]);
 // Quantised nodes of any wide-node hierarchy whose leaf references are to stay as they are (own leaves): 2 uint4 per node as in
 // pt_quantize_tree, numbered with the top n_top <= top_nodes nodes first in breadth-first order, the rest in preorder.
 bool pt_quantize_nodes(const std::vector<float4> &wnodes, std::vector<uint4> &qnodes, float origin[3], float scale[3],

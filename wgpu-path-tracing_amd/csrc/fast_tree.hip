@@ -328,19 +328,6 @@ void pt_build_fast_tree(const std::vector<PtFastLeaf> &leaves, std::vector<float
 }
 
 // ---- own leaves -----------------------------------------------------------------------------------------------------
-#ifndef PT_OWN_C_BOX
-#define PT_OWN_C_BOX 1.0             /* cost of a box-pair step (the unit) */
-#endif
-#ifndef PT_OWN_C_TRI
-#define PT_OWN_C_TRI 0.9             /* ... of one triangle test (54 against ~60 vector instructions) */
-#endif
-#ifndef PT_OWN_C_OPEN
-#define PT_OWN_C_OPEN 0.35           /* ... of opening a leaf (its entry leaves the lane's list, the loop is set up, a share of a vote) */
-#endif
-#ifndef PT_OWN_PAD_LOG2
-#define PT_OWN_PAD_LOG2 (-16)        /* boxes grow by 2^this x the largest coordinate magnitude of the scene */
-#endif
-
 namespace {
 
 double env_or(const char *name, double dflt) {          // experiments only (tools/own_leaf_gate.py)
@@ -639,6 +626,23 @@ bool pt_quantize_tree(const std::vector<PtFastLeaf> &leaves, const std::vector<f
     return true;
 }
 
+bool pt_quant_grid(const float mn[3], const float mx[3], float origin[3], float scale[3]) {
+    for (int k = 0; k < 3; k++) {
+        origin[k] = mn[k];
+        const double ext = (double)mx[k] - (double)mn[k];
+        float s = (float)(ext / 65535.0);
+        if (!std::isfinite(s)) return false;
+        if (ext > 0.0) {
+            if (!(s > 0.0f)) s = std::numeric_limits<float>::denorm_min();
+            int guard = 0;
+            while (std::fmaf(s, 65535.0f, origin[k]) < mx[k] && guard++ < 64) s = std::nextafterf(s, INFINITY);
+            if (std::fmaf(s, 65535.0f, origin[k]) < mx[k]) return false;
+        }
+        scale[k] = s;
+    }
+    return true;
+}
+
 bool pt_quantize_nodes(const std::vector<float4> &wnodes, std::vector<uint4> &qnodes, float origin[3], float scale[3],
                        uint32_t top_nodes, uint32_t &n_top) {
     qnodes.clear(); n_top = 0;
@@ -655,19 +659,7 @@ bool pt_quantize_nodes(const std::vector<float4> &wnodes, std::vector<uint4> &qn
                 mn[k] = std::min(mn[k], lo[c][k]); mx[k] = std::max(mx[k], hi[c][k]);
             }
     }
-    for (int k = 0; k < 3; k++) {
-        origin[k] = mn[k];
-        const double ext = (double)mx[k] - (double)mn[k];
-        float s = (float)(ext / 65535.0);
-        if (!std::isfinite(s)) return false;
-        if (ext > 0.0) {
-            if (!(s > 0.0f)) s = std::numeric_limits<float>::denorm_min();
-            int guard = 0;
-            while (std::fmaf(s, 65535.0f, origin[k]) < mx[k] && guard++ < 64) s = std::nextafterf(s, INFINITY);
-            if (std::fmaf(s, 65535.0f, origin[k]) < mx[k]) return false;
-        }
-        scale[k] = s;
-    }
+    if (!pt_quant_grid(mn, mx, origin, scale)) return false;
     auto plane_lo = [&](int k, float v) -> uint32_t {
         if (!(scale[k] > 0.0f)) return 0u;
         double q = std::floor(((double)v - (double)origin[k]) / (double)scale[k]);

@@ -1,0 +1,516 @@
+// own_tree_gpu.hip — the library's OWN-leaf hierarchy (ptmi_options.leaves = 2) built on the device (ptmi_options.tree_builder = 2).
+//
+// It produces what pt_build_own_tree + pt_quantize_nodes produce on the host (fast_tree.h: the same layouts, the same padding, the same
+// quantisation rules), over another topology. Any topology is allowed: the kernels break ties by the lowest
+// triangle index and verify every winner against its reference leaf's box, so only the work per ray depends on the tree.
+//
+//   units     one box per listed triangle, min / max over a, b, c, a + (b - a), a + (c - a) as the host computes them; |coordinate|
+//             max-reduced for the padding (exact in f32)
+//   PLOC      Morton codes of the unit centroids, made unique by the unit's index and radix-sorted (hipCUB); then repeatedly: every
+//             cluster's nearest neighbour within +-PT_PLOC_RADIUS sorted positions (smallest surface area of the union, ties to the
+//             lower position), mutual pairs merged into a new node at the lower position, survivors compacted in order by a prefix sum
+//             (Meister & Bittner 2018). The key (area, lower position, higher position) is symmetric, so the globally smallest pair is
+//             always mutual and every pass merges at least once.
+//   collapse  bottom-up with one arrival counter per node (agent-scope release / acquire hand-off): the second thread to arrive
+//             computes the host's cost model (fast_tree.hip, Collapse) from both children's stored values, so the result does not
+//             depend on the order of arrival
+//   emit      every node walks up to the root summing the offsets its ancestors stored for it: its preorder number among the
+//             surviving inner nodes, its first position in leaf order, its level. Inner nodes write their wide node (child boxes
+//             padded outward exactly as the host pads them), units write their triangle (v0, bits(original index)), e1, e2
+//   quantise  the host's grid (pt_quant_grid) from the min / max of the padded boxes; the top PT_QCACHE_NODES nodes breadth-first
+//             at the front, the others in preorder; planes rounded outward and checked with the kernel's own fmaf
+//
+// Every step is deterministic: the same scene gives the same bytes on every run and every device. Scratch is sized from the scene and
+// freed on every path; any failure returns false and the caller builds on the host.
+#include "fast_tree.h"
+#include "pt_device.h"
+#include "ptmi_layout.h"
+
+#include <hipcub/hipcub.hpp>
+
+#include <cfloat>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#ifndef PT_PLOC_RADIUS
+#define PT_PLOC_RADIUS 16            /* neighbours searched on each side of a cluster (sorted positions) */
+#endif
+
+namespace {
+
+constexpr int TB = 256;
+constexpr int R = PT_PLOC_RADIUS;
+constexpr int kMaxPasses = 1024;     // PLOC passes before the build is refused (a backstop: real scenes take 40 - 70)
+
+struct Box6 { float mn[3], mx[3]; };
+
+// std::min / std::max exactly (the host's Box::grow): the first argument unless the second is strictly smaller / larger
+__device__ __forceinline__ float mn_(float a, float b) { return b < a ? b : a; }
+__device__ __forceinline__ float mx_(float a, float b) { return a < b ? b : a; }
+
+__device__ __forceinline__ Box6 unite(const Box6 &a, const Box6 &b) {
+    Box6 u;
+    for (int k = 0; k < 3; k++) { u.mn[k] = mn_(a.mn[k], b.mn[k]); u.mx[k] = mx_(a.mx[k], b.mx[k]); }
+    return u;
+}
+
+__device__ __forceinline__ double area(const Box6 &b) {          // fast_tree.hip Box::area
+    const double dx = (double)b.mx[0] - b.mn[0], dy = (double)b.mx[1] - b.mn[1], dz = (double)b.mx[2] - b.mn[2];
+    return 2.0 * (dx * dy + dy * dz + dz * dx);
+}
+
+// order-preserving float <-> uint (min / max reductions with integer atomics)
+__device__ __forceinline__ uint32_t ord(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+float unord_f(uint32_t u) { u = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u; float f; std::memcpy(&f, &u, 4); return f; }
+
+struct Red {                          // reductions of the build, zeroed before it
+    uint32_t biggest;                 // bits of max |coordinate| over the unit boxes (non-negative floats order as integers)
+    uint32_t bad;                     // a non-finite coordinate
+    uint32_t cmin[3], cmax[3];        // ord() of the unit centroids' bounds
+    uint32_t depth, max_leaf, n_top;
+    uint32_t ploc_depth;              // levels of the deepest cluster so far (a unit: 1)
+    uint32_t qmin[3], qmax[3];        // ord() of the padded child boxes' bounds
+};
+
+__global__ void k_units(uint32_t n, const ptmi_triangle *__restrict__ tris, const uint32_t *__restrict__ which, Box6 *__restrict__ box,
+                        Red *red) {
+    const uint32_t i = blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const ptmi_triangle &t = tris[which[i]];
+    Box6 u; uint32_t big = 0, bad = 0;
+    for (int k = 0; k < 3; k++) {
+        const float a = t.v0[k], b = t.v1[k], c = t.v2[k];
+        const float b2 = a + (b - a), c2 = a + (c - a);
+        if (!isfinite(a) || !isfinite(b) || !isfinite(c) || !isfinite(b2) || !isfinite(c2)) bad = 1;
+        u.mn[k] = mn_(mn_(mn_(a, b), mn_(c, b2)), c2);
+        u.mx[k] = mx_(mx_(mx_(a, b), mx_(c, b2)), c2);
+        big = max(big, max(__float_as_uint(fabsf(u.mn[k])), __float_as_uint(fabsf(u.mx[k]))));
+    }
+    box[i] = u;
+    if (bad) { atomicOr(&red->bad, 1u); return; }
+    atomicMax(&red->biggest, big);
+    for (int k = 0; k < 3; k++) {
+        const uint32_t c = ord(0.5f * u.mn[k] + 0.5f * u.mx[k]);
+        atomicMin(&red->cmin[k], c); atomicMax(&red->cmax[k], c);
+    }
+}
+
+__device__ __forceinline__ uint32_t expand10(uint32_t v) {          // 10 bits -> every third bit
+    v = (v * 0x00010001u) & 0xFF0000FFu;
+    v = (v * 0x00000101u) & 0x0F00F00Fu;
+    v = (v * 0x00000011u) & 0xC30C30C3u;
+    v = (v * 0x00000005u) & 0x49249249u;
+    return v;
+}
+
+__global__ void k_morton(uint32_t n, const Box6 *__restrict__ box, float3 lo, float3 inv, unsigned long long *__restrict__ keys) {
+    const uint32_t i = blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const Box6 b = box[i];
+    const float cx = (0.5f * b.mn[0] + 0.5f * b.mx[0] - lo.x) * inv.x;
+    const float cy = (0.5f * b.mn[1] + 0.5f * b.mx[1] - lo.y) * inv.y;
+    const float cz = (0.5f * b.mn[2] + 0.5f * b.mx[2] - lo.z) * inv.z;
+    auto q = [](float v) { v = v * 1024.0f; v = v < 0.0f ? 0.0f : (v > 1023.0f ? 1023.0f : v); return (uint32_t)v; };
+    const uint32_t code = (expand10(q(cx)) << 2) | (expand10(q(cy)) << 1) | expand10(q(cz));
+    keys[i] = ((unsigned long long)code << 32) | i;
+}
+
+__global__ void k_first_clusters(uint32_t n, const unsigned long long *__restrict__ keys, uint32_t *__restrict__ clu) {
+    const uint32_t i = blockIdx.x * TB + threadIdx.x;
+    if (i < n) clu[i] = (uint32_t)keys[i];               // low 32 bits: the unit
+}
+
+// nearest neighbour of every cluster within +-R positions; the block's boxes and its halo are staged in LDS
+__global__ void __launch_bounds__(TB) k_nearest(uint32_t m, const uint32_t *__restrict__ clu, const Box6 *__restrict__ box,
+                                                 uint32_t *__restrict__ nn) {
+    __shared__ Box6 s[TB + 2 * R];
+    const int base = (int)(blockIdx.x * TB) - R;
+    for (int k = threadIdx.x; k < TB + 2 * R; k += TB) {
+        const int j = base + k;
+        if (j >= 0 && j < (int)m) s[k] = box[clu[j]];
+    }
+    __syncthreads();
+    const int i = blockIdx.x * TB + threadIdx.x;
+    if (i >= (int)m) return;
+    const Box6 me = s[threadIdx.x + R];
+    double best = INFINITY; int bj = -1;
+    const int j0 = max(0, i - R), j1 = min((int)m - 1, i + R);
+    for (int j = j0; j <= j1; j++) {
+        if (j == i) continue;
+        const double a = area(unite(me, s[j - base]));
+        if (a < best || bj < 0) { best = a; bj = j; }              // ascending j, strict <: ties go to the lower position
+    }
+    nn[i] = (uint32_t)bj;
+}
+
+// flags: high word = this position creates a node (the lower end of a mutual pair), low word = it survives
+__global__ void k_mark(uint32_t m, const uint32_t *__restrict__ nn, unsigned long long *__restrict__ flags) {
+    const uint32_t i = blockIdx.x * TB + threadIdx.x;
+    if (i > m) return;
+    if (i == m) { flags[i] = 0ull; return; }
+    const uint32_t j = nn[i];
+    const bool mutual = nn[j] == i;
+    flags[i] = mutual ? (i < j ? ((1ull << 32) | 1ull) : 0ull) : 1ull;
+}
+
+__global__ void k_merge(uint32_t m, uint32_t n, uint32_t first_new, const uint32_t *__restrict__ clu, const uint32_t *__restrict__ nn,
+                        const unsigned long long *__restrict__ flags, const unsigned long long *__restrict__ ex, Box6 *__restrict__ box,
+                        uint2 *__restrict__ child, uint32_t *__restrict__ parent, uint8_t *__restrict__ level, uint32_t *__restrict__ out,
+                        Red *red) {
+    const uint32_t i = blockIdx.x * TB + threadIdx.x;
+    if (i >= m) return;
+    const unsigned long long f = flags[i];
+    if (!(f & 1ull)) return;
+    const unsigned long long e = ex[i];
+    uint32_t node = clu[i];
+    if (f >> 32) {
+        const uint32_t a = clu[i], b = clu[nn[i]];
+        node = first_new + (uint32_t)(e >> 32);
+        child[node - n] = make_uint2(a, b);
+        box[node] = unite(box[a], box[b]);
+        parent[a] = node; parent[b] = node;
+        const uint32_t lv = 1u + max(a < n ? 1u : (uint32_t)level[a - n], b < n ? 1u : (uint32_t)level[b - n]);
+        level[node - n] = (uint8_t)min(lv, 255u);                      // (the build is refused long before 255)
+        atomicMax(&red->ploc_depth, lv);
+    }
+    out[(uint32_t)e] = node;
+}
+
+struct Step { uint32_t parent, pre, tri, parent_leaf; };   // what a node adds on its way up: see k_emit
+
+// bottom-up: one thread per unit; the second to arrive at a node evaluates it
+__global__ void k_collapse(uint32_t n, uint32_t max_leaf, double c_box, double c_tri, double c_open, const Box6 *__restrict__ box,
+                           const uint2 *__restrict__ child, const uint32_t *__restrict__ parent, uint32_t *__restrict__ arrived,
+                           uint32_t *__restrict__ cnt, uint32_t *__restrict__ icnt, double *__restrict__ cost,
+                           uint32_t *__restrict__ leafy, Step *__restrict__ step) {
+    const uint32_t v = blockIdx.x * TB + threadIdx.x;
+    if (v >= n) return;
+    cnt[v] = 1u; icnt[v] = 0u; cost[v] = c_open + c_tri; leafy[v] = 1u;
+    uint32_t node = parent[v];
+    while (node != PT_REF_NONE) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");           // this thread's stores before its ticket
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (__hip_atomic_fetch_add(&arrived[node - n], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return;
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");           // the other child's stores are visible from here on
+        const uint2 ch = child[node - n];
+        const Box6 bl = box[ch.x], br = box[ch.y];
+        const double a = area(unite(bl, br));
+        const double lc = cost[ch.x], rc = cost[ch.y];
+        const double inner = c_box + (a > 0.0 ? (area(bl) * lc + area(br) * rc) / a : lc + rc);
+        const uint32_t k = cnt[ch.x] + cnt[ch.y];
+        const double as_leaf = c_open + c_tri * (double)k;
+        const bool lf = k <= max_leaf && as_leaf <= inner;
+        cnt[node] = k; cost[node] = lf ? as_leaf : inner; leafy[node] = lf ? 1u : 0u;
+        icnt[node] = lf ? 0u : 1u + icnt[ch.x] + icnt[ch.y];
+        step[ch.x] = Step{node, 1u, 0u, lf ? 1u : 0u};
+        step[ch.y] = Step{node, 1u + icnt[ch.x], cnt[ch.x], lf ? 1u : 0u};
+        node = parent[node];
+    }
+}
+
+__device__ __forceinline__ float lower(float x, float pad) { const float y = x - pad; return y < x ? y : nextafterf(x, -INFINITY); }
+__device__ __forceinline__ float upper(float x, float pad) { const float y = x + pad; return y > x ? y : nextafterf(x, INFINITY); }
+
+// one thread per node: walk to the root, then write what this node owns in the image
+__global__ void k_emit(uint32_t n_all, uint32_t n, uint32_t root, float pad, const ptmi_triangle *__restrict__ tris,
+                       const uint32_t *__restrict__ which, const Box6 *__restrict__ box, const uint2 *__restrict__ child,
+                       const uint32_t *__restrict__ cnt, const uint32_t *__restrict__ icnt, const uint32_t *__restrict__ leafy,
+                       const Step *__restrict__ step, float4 *__restrict__ wn, float4 *__restrict__ tp, Red *red) {
+    const uint32_t v = blockIdx.x * TB + threadIdx.x;
+    if (v >= n_all) return;
+    if (v >= n && leafy[v]) return;                              // a collapsed node: its units write its triangles
+    uint32_t pre = 0, tri = 0, lvl = 1, u = v;
+    bool emitted = true;
+    while (u != root) {
+        const Step s = step[u];
+        pre += s.pre; tri += s.tri; lvl++;
+        if (s.parent_leaf) emitted = false;
+        u = s.parent;
+    }
+    if (v < n) {                                                 // a unit: its triangle at its place in leaf order
+        const uint32_t orig = which[v];
+        const ptmi_triangle &t = tris[orig];
+        tp[3 * (size_t)tri + 0] = make_float4(t.v0[0], t.v0[1], t.v0[2], __uint_as_float(orig));
+        tp[3 * (size_t)tri + 1] = make_float4(t.v1[0] - t.v0[0], t.v1[1] - t.v0[1], t.v1[2] - t.v0[2], 0.0f);
+        tp[3 * (size_t)tri + 2] = make_float4(t.v2[0] - t.v0[0], t.v2[1] - t.v0[1], t.v2[2] - t.v0[2], 0.0f);
+        return;
+    }
+    if (!emitted) return;
+    const uint2 ch = child[v - n];
+    const uint32_t c[2] = {ch.x, ch.y};
+    const uint32_t cpre[2] = {pre + 1u, pre + 1u + icnt[ch.x]}, ctri[2] = {tri, tri + cnt[ch.x]};
+    Box6 b[2]; uint32_t ref[2];
+    for (int s = 0; s < 2; s++) {
+        const Box6 e = box[c[s]];
+        for (int k = 0; k < 3; k++) {
+            b[s].mn[k] = lower(e.mn[k], pad); b[s].mx[k] = upper(e.mx[k], pad);
+            atomicMin(&red->qmin[k], ord(b[s].mn[k])); atomicMax(&red->qmax[k], ord(b[s].mx[k]));
+        }
+        if (leafy[c[s]]) {
+            ref[s] = PT_REF_LEAF | ((cnt[c[s]] - 1u) << PT_LEAF_OFF_BITS) | ctri[s];
+            atomicMax(&red->max_leaf, cnt[c[s]]);
+        } else {
+            ref[s] = cpre[s];
+        }
+    }
+    atomicMax(&red->depth, lvl + 1u);                            // the children sit one level down
+    float4 *w = wn + 4 * (size_t)pre;
+    w[0] = make_float4(b[0].mn[0], b[0].mn[1], b[0].mn[2], b[0].mx[0]);
+    w[1] = make_float4(b[0].mx[1], b[0].mx[2], b[1].mn[0], b[1].mn[1]);
+    w[2] = make_float4(b[1].mn[2], b[1].mx[0], b[1].mx[1], b[1].mx[2]);
+    w[3] = make_float4(__uint_as_float(ref[0]), __uint_as_float(ref[1]), 0.0f, 0.0f);
+}
+
+// the top `top` nodes breadth-first from the root (one thread: a few hundred steps)
+__global__ void k_top(const float4 *__restrict__ wn, uint32_t top, uint32_t *__restrict__ renum, Red *red) {
+    __shared__ uint32_t bfs[PT_QCACHE_NODES];
+    uint32_t len = 0;
+    bfs[len++] = 0u;
+    for (uint32_t h = 0; h < len && len < top; h++) {
+        const float4 r = wn[4 * (size_t)bfs[h] + 3];
+        const uint32_t refs[2] = {__float_as_uint(r.x), __float_as_uint(r.y)};
+        for (int c = 0; c < 2 && len < top; c++)
+            if (!(refs[c] & PT_REF_LEAF)) bfs[len++] = refs[c];
+    }
+    for (uint32_t k = 0; k < len; k++) renum[bfs[k]] = k;
+    red->n_top = len;
+}
+
+__global__ void k_rest_flags(uint32_t m, const uint32_t *__restrict__ renum, uint32_t *__restrict__ flags) {
+    const uint32_t i = blockIdx.x * TB + threadIdx.x;
+    if (i < m) flags[i] = renum[i] == PT_REF_NONE ? 1u : 0u;
+}
+
+struct Grid { float origin[3], scale[3]; };
+
+__device__ __forceinline__ uint32_t plane_lo(const Grid &g, int k, float v) {     // fast_tree.hip pt_quantize_nodes
+    if (!(g.scale[k] > 0.0f)) return 0u;
+    const double q = floor(((double)v - (double)g.origin[k]) / (double)g.scale[k]);
+    uint32_t u = q <= 0.0 ? 0u : q >= 65535.0 ? 65535u : (uint32_t)q;
+    while (u > 0u && fmaf(g.scale[k], (float)u, g.origin[k]) > v) u--;
+    return u;
+}
+__device__ __forceinline__ uint32_t plane_hi(const Grid &g, int k, float v) {
+    if (!(g.scale[k] > 0.0f)) return 0u;
+    const double q = ceil(((double)v - (double)g.origin[k]) / (double)g.scale[k]);
+    uint32_t u = q <= 0.0 ? 0u : q >= 65535.0 ? 65535u : (uint32_t)q;
+    while (u < 65535u && fmaf(g.scale[k], (float)u, g.origin[k]) < v) u++;
+    return u;
+}
+
+__global__ void k_quantise(uint32_t m, Grid g, const float4 *__restrict__ wn, const uint32_t *__restrict__ renum,
+                           const uint32_t *__restrict__ rest, const Red *red, uint4 *__restrict__ qn, double *__restrict__ growth,
+                           uint32_t *__restrict__ grown) {
+    const uint32_t i = blockIdx.x * TB + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t n_top = red->n_top;
+    auto number = [&](uint32_t j) { const uint32_t r = renum[j]; return r != PT_REF_NONE ? r : n_top + rest[j]; };
+    const float4 *w = wn + 4 * (size_t)i;
+    const float lo[2][3] = {{w[0].x, w[0].y, w[0].z}, {w[1].z, w[1].w, w[2].x}};
+    const float hi[2][3] = {{w[0].w, w[1].x, w[1].y}, {w[2].y, w[2].z, w[2].w}};
+    const uint32_t refs[2] = {__float_as_uint(w[3].x), __float_as_uint(w[3].y)};
+    const uint32_t me = number(i);
+    double gsum = 0.0; uint32_t gn = 0;
+    for (int c = 0; c < 2; c++) {
+        uint32_t ql[3], qh[3]; float dl[3], dh[3];
+        for (int k = 0; k < 3; k++) {
+            ql[k] = plane_lo(g, k, lo[c][k]); qh[k] = plane_hi(g, k, hi[c][k]);
+            dl[k] = fmaf(g.scale[k], (float)ql[k], g.origin[k]); dh[k] = fmaf(g.scale[k], (float)qh[k], g.origin[k]);
+        }
+        const uint32_t ref = (refs[c] & PT_REF_LEAF) ? refs[c] : number(refs[c]);
+        qn[(size_t)me * 2 + c] = make_uint4(ql[0] | (ql[1] << 16), ql[2] | (qh[0] << 16), qh[1] | (qh[2] << 16), ref);
+        const double ax = (double)hi[c][0] - lo[c][0], ay = (double)hi[c][1] - lo[c][1], az = (double)hi[c][2] - lo[c][2];
+        const double a0 = 2.0 * (ax * ay + ay * az + az * ax);
+        const double bx = (double)dh[0] - dl[0], by = (double)dh[1] - dl[1], bz = (double)dh[2] - dl[2];
+        if (a0 > 0.0) { gsum += fmin(2.0 * (bx * by + by * bz + bz * bx) / a0 - 1.0, 1e6); gn++; }
+    }
+    growth[i] = gsum; grown[i] = gn;
+}
+
+template <class T> void dfree(T *&p) { if (p) { (void)hipFree(p); p = nullptr; } }
+
+}  // namespace
+
+#define GT(expr) do { if ((expr) != hipSuccess) goto done; } while (0)
+
+bool pt_build_own_tree_gpu(const ptmi_triangle *d_tris, const std::vector<uint32_t> &which, uint32_t max_leaf, uint32_t depth_limit,
+                           hipStream_t s, PtOwnTreeGpu &out) {
+    out.release();
+    const uint32_t n = (uint32_t)which.size();
+    if (n < 2 || n > PT_LEAF_OFF_MASK) return false;
+    max_leaf = std::max(1u, std::min(max_leaf, PT_LEAF_MAX_TRIS));
+    const uint32_t n_all = 2 * n - 1;
+    auto blocks = [](uint32_t k) { return dim3((k + TB - 1) / TB); };
+    bool ok = false;
+    uint32_t *d_which = nullptr, *d_clu[2] = {nullptr, nullptr}, *d_nn = nullptr, *d_parent = nullptr, *d_arr = nullptr;
+    uint32_t *d_cnt = nullptr, *d_icnt = nullptr, *d_leafy = nullptr, *d_renum = nullptr, *d_rest_f = nullptr, *d_rest = nullptr;
+    uint32_t *d_grown = nullptr, *d_grown_sum = nullptr;
+    uint8_t *d_level = nullptr;
+    double *d_cost = nullptr, *d_growth = nullptr, *d_growth_sum = nullptr;
+    unsigned long long *d_keys = nullptr, *d_keys2 = nullptr, *d_flags = nullptr, *d_ex = nullptr;
+    Box6 *d_box = nullptr; uint2 *d_child = nullptr; Step *d_step = nullptr; Red *d_red = nullptr;
+    float4 *d_wn = nullptr, *d_tp = nullptr; uint4 *d_qn = nullptr;
+    void *d_tmp = nullptr; size_t tmp_bytes = 0;
+    Red h{};
+    uint32_t m = n, next = n, root = 0, n_inner = 0;
+    float pad = 0.0f;
+    double biggest = 0.0;
+
+    GT(hipMalloc(&d_which, (size_t)n * 4)); GT(hipMalloc(&d_box, (size_t)n_all * sizeof(Box6)));
+    GT(hipMalloc(&d_red, sizeof(Red)));
+    GT(hipMemcpyAsync(d_which, which.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    {
+        Red r0{}; r0.biggest = 0; r0.bad = 0;
+        for (int k = 0; k < 3; k++) { r0.cmin[k] = r0.qmin[k] = 0xFFFFFFFFu; r0.cmax[k] = r0.qmax[k] = 0u; }
+        GT(hipMemcpyAsync(d_red, &r0, sizeof r0, hipMemcpyHostToDevice, s));
+        k_units<<<blocks(n), TB, 0, s>>>(n, d_tris, d_which, d_box, d_red);
+        GT(hipMemcpyAsync(&h, d_red, sizeof h, hipMemcpyDeviceToHost, s));
+        GT(hipStreamSynchronize(s));
+        GT(hipGetLastError());
+    }
+    if (h.bad) goto done;                                        // a non-finite vertex: the host refuses it too
+    {
+        std::memcpy(&pad, &h.biggest, 4);
+        biggest = (double)pad;
+        pad = std::max((float)std::ldexp(biggest, PT_OWN_PAD_LOG2), FLT_MIN);
+        if (!std::isfinite(pad)) goto done;
+        float lo[3], inv[3];
+        for (int k = 0; k < 3; k++) {
+            lo[k] = unord_f(h.cmin[k]);
+            const float e = unord_f(h.cmax[k]) - lo[k];
+            inv[k] = (e > 0.0f && std::isfinite(1.0f / e)) ? 1.0f / e : 0.0f;
+        }
+        GT(hipMalloc(&d_keys, (size_t)n * 8)); GT(hipMalloc(&d_keys2, (size_t)n * 8));
+        k_morton<<<blocks(n), TB, 0, s>>>(n, d_box, make_float3(lo[0], lo[1], lo[2]), make_float3(inv[0], inv[1], inv[2]), d_keys);
+    }
+    {   // scratch for the sort, the per-pass scan and the final reductions: the largest of them
+        size_t a = 0, b = 0, c = 0, d = 0;
+        GT(hipcub::DeviceRadixSort::SortKeys(nullptr, a, d_keys, d_keys2, (int)n, 0, 62, s));
+        GT(hipcub::DeviceScan::ExclusiveSum(nullptr, b, d_flags, d_ex, (int)n + 1, s));
+        GT(hipcub::DeviceScan::ExclusiveSum(nullptr, c, d_rest_f, d_rest, (int)n, s));
+        GT(hipcub::DeviceReduce::Sum(nullptr, d, d_growth, d_growth_sum, (int)n, s));
+        tmp_bytes = std::max(std::max(a, b), std::max(c, d));
+        size_t d2 = 0;
+        GT(hipcub::DeviceReduce::Sum(nullptr, d2, d_grown, d_grown_sum, (int)n, s));
+        tmp_bytes = std::max(tmp_bytes, d2);
+        GT(hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 16));
+    }
+    GT(hipcub::DeviceRadixSort::SortKeys(d_tmp, tmp_bytes, d_keys, d_keys2, (int)n, 0, 62, s));
+    GT(hipMalloc(&d_clu[0], (size_t)n * 4)); GT(hipMalloc(&d_clu[1], (size_t)n * 4)); GT(hipMalloc(&d_nn, (size_t)n * 4));
+    GT(hipMalloc(&d_flags, (size_t)(n + 1) * 8)); GT(hipMalloc(&d_ex, (size_t)(n + 1) * 8));
+    GT(hipMalloc(&d_child, (size_t)(n - 1) * sizeof(uint2))); GT(hipMalloc(&d_parent, (size_t)n_all * 4));
+    GT(hipMemsetAsync(d_parent, 0xFF, (size_t)n_all * 4, s));
+    GT(hipMalloc(&d_level, (size_t)(n - 1)));
+    k_first_clusters<<<blocks(n), TB, 0, s>>>(n, d_keys2, d_clu[0]);
+    // PLOC passes: each merges at least the globally closest pair. Collapsing takes at most max_leaf - 1 levels off a path, so a cluster
+    // deeper than depth_limit + max_leaf - 1 levels can never give a tree within the limit: the build is refused as soon as one appears
+    // (nested triangles along a line merge one pair per pass into a chain), before the passes and the emit walk grow with the depth.
+    // The number of passes is capped as well (measured: 39 for 3 876 triangles, 62 for a million).
+    for (int cur = 0, pass = 0; m > 1; cur ^= 1, pass++) {
+        if (pass >= kMaxPasses) goto done;
+        k_nearest<<<blocks(m), TB, 0, s>>>(m, d_clu[cur], d_box, d_nn);
+        k_mark<<<blocks(m + 1), TB, 0, s>>>(m, d_nn, d_flags);
+        GT(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_flags, d_ex, (int)m + 1, s));
+        k_merge<<<blocks(m), TB, 0, s>>>(m, n, next, d_clu[cur], d_nn, d_flags, d_ex, d_box, d_child, d_parent, d_level, d_clu[cur ^ 1],
+                                         d_red);
+        unsigned long long tot = 0;
+        uint32_t deepest = 0;
+        GT(hipMemcpyAsync(&tot, d_ex + m, 8, hipMemcpyDeviceToHost, s));
+        GT(hipMemcpyAsync(&deepest, &d_red->ploc_depth, 4, hipMemcpyDeviceToHost, s));
+        GT(hipStreamSynchronize(s));
+        const uint32_t made = (uint32_t)(tot >> 32), left = (uint32_t)tot;
+        if (made == 0 || left + made != m) goto done;            // cannot happen (see the top); refuse rather than loop
+        if (deepest > depth_limit + max_leaf - 1u) goto done;   // too deep for any collapse: the host builds
+        next += made; m = left;
+    }
+    GT(hipGetLastError());
+    root = next - 1;
+    if (root != n_all - 1) goto done;
+    // collapse
+    GT(hipMalloc(&d_arr, (size_t)(n - 1) * 4)); GT(hipMalloc(&d_cnt, (size_t)n_all * 4)); GT(hipMalloc(&d_icnt, (size_t)n_all * 4));
+    GT(hipMalloc(&d_leafy, (size_t)n_all * 4)); GT(hipMalloc(&d_cost, (size_t)n_all * 8)); GT(hipMalloc(&d_step, (size_t)n_all * sizeof(Step)));
+    GT(hipMemsetAsync(d_arr, 0, (size_t)(n - 1) * 4, s));
+    k_collapse<<<blocks(n), TB, 0, s>>>(n, max_leaf, PT_OWN_C_BOX, PT_OWN_C_TRI, PT_OWN_C_OPEN, d_box, d_child, d_parent, d_arr,
+                                        d_cnt, d_icnt, d_cost, d_leafy, d_step);
+    {
+        uint32_t rl = 0;
+        GT(hipMemcpyAsync(&n_inner, d_icnt + root, 4, hipMemcpyDeviceToHost, s));
+        GT(hipMemcpyAsync(&rl, d_leafy + root, 4, hipMemcpyDeviceToHost, s));
+        GT(hipStreamSynchronize(s));
+        GT(hipGetLastError());
+        if (rl || n_inner == 0) goto done;                       // a single leaf (never above 32 triangles): the host's case
+    }
+    dfree(d_clu[0]); dfree(d_clu[1]); dfree(d_nn); dfree(d_flags); dfree(d_ex); dfree(d_arr); dfree(d_cost);
+    // emit
+    GT(hipMalloc(&d_wn, (size_t)n_inner * 64)); GT(hipMalloc(&d_tp, (size_t)n * 48));
+    k_emit<<<blocks(n_all), TB, 0, s>>>(n_all, n, root, pad, d_tris, d_which, d_box, d_child, d_cnt, d_icnt, d_leafy, d_step, d_wn, d_tp, d_red);
+    {
+        Box6 rb;
+        GT(hipMemcpyAsync(&rb, d_box + root, sizeof rb, hipMemcpyDeviceToHost, s));
+        GT(hipMemcpyAsync(&h, d_red, sizeof h, hipMemcpyDeviceToHost, s));
+        GT(hipStreamSynchronize(s));
+        GT(hipGetLastError());
+        if (h.depth > depth_limit) goto done;
+        // padding and the root box exactly as the host derives them (fast_tree.hip pt_build_own_tree): they depend on the triangle set only
+        auto lower_h = [&](float x) { const float y = x - pad; return y < x ? y : std::nextafterf(x, -INFINITY); };
+        auto upper_h = [&](float x) { const float y = x + pad; return y > x ? y : std::nextafterf(x, INFINITY); };
+        for (int k = 0; k < 3; k++) {
+            out.root_min[k] = lower_h(rb.mn[k]); out.root_max[k] = upper_h(rb.mx[k]);
+            if (!std::isfinite(out.root_min[k]) || !std::isfinite(out.root_max[k])) goto done;
+        }
+    }
+    out.pad = pad;
+    out.safe_origin = (float)std::min(8.0 * biggest, 3.0e38);
+    out.root_ref = 0u; out.depth = h.depth; out.n_wnodes = n_inner; out.n_tris = n;
+    out.n_leaves = n_inner + 1u; out.max_leaf_tris = h.max_leaf;
+    dfree(d_step); dfree(d_child); dfree(d_box); dfree(d_parent); dfree(d_cnt); dfree(d_icnt); dfree(d_leafy);
+    // quantised nodes (none when the 16-bit grid is too coarse for the scene, as on the host)
+    out.quantised = false;
+    {
+        float mn[3], mx[3];
+        for (int k = 0; k < 3; k++) { mn[k] = unord_f(h.qmin[k]); mx[k] = unord_f(h.qmax[k]); }
+        Grid g;
+        if (pt_quant_grid(mn, mx, g.origin, g.scale)) {
+            GT(hipMalloc(&d_qn, (size_t)n_inner * 32)); GT(hipMalloc(&d_renum, (size_t)n_inner * 4));
+            GT(hipMalloc(&d_rest_f, (size_t)n_inner * 4)); GT(hipMalloc(&d_rest, (size_t)n_inner * 4));
+            GT(hipMalloc(&d_growth, (size_t)n_inner * 8)); GT(hipMalloc(&d_grown, (size_t)n_inner * 4));
+            GT(hipMalloc(&d_growth_sum, 8)); GT(hipMalloc(&d_grown_sum, 4));
+            GT(hipMemsetAsync(d_renum, 0xFF, (size_t)n_inner * 4, s));
+            k_top<<<1, 1, 0, s>>>(d_wn, std::min<uint32_t>(PT_QCACHE_NODES, n_inner), d_renum, d_red);
+            k_rest_flags<<<blocks(n_inner), TB, 0, s>>>(n_inner, d_renum, d_rest_f);
+            GT(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_rest_f, d_rest, (int)n_inner, s));
+            k_quantise<<<blocks(n_inner), TB, 0, s>>>(n_inner, g, d_wn, d_renum, d_rest, d_red, d_qn, d_growth, d_grown);
+            GT(hipcub::DeviceReduce::Sum(d_tmp, tmp_bytes, d_growth, d_growth_sum, (int)n_inner, s));
+            GT(hipcub::DeviceReduce::Sum(d_tmp, tmp_bytes, d_grown, d_grown_sum, (int)n_inner, s));
+            double growth = 0.0; uint32_t grown = 0;
+            GT(hipMemcpyAsync(&growth, d_growth_sum, 8, hipMemcpyDeviceToHost, s));
+            GT(hipMemcpyAsync(&grown, d_grown_sum, 4, hipMemcpyDeviceToHost, s));
+            GT(hipMemcpyAsync(&h, d_red, sizeof h, hipMemcpyDeviceToHost, s));
+            GT(hipStreamSynchronize(s));
+            GT(hipGetLastError());
+            if (!(grown && growth / (double)grown > 0.25)) {
+                out.quantised = true; out.q_top = h.n_top;
+                for (int k = 0; k < 3; k++) { out.q_origin[k] = g.origin[k]; out.q_scale[k] = g.scale[k]; }
+            }
+        }
+    }
+    if (!out.quantised) dfree(d_qn);
+    out.wnodes = d_wn; out.tripos = d_tp; out.qnodes = d_qn;
+    d_wn = nullptr; d_tp = nullptr; d_qn = nullptr;
+    ok = true;
+done:
+    (void)hipStreamSynchronize(s);                               // nothing of ours may still run when the scratch goes
+    dfree(d_which); dfree(d_clu[0]); dfree(d_clu[1]); dfree(d_nn); dfree(d_parent); dfree(d_arr); dfree(d_cnt); dfree(d_icnt);
+    dfree(d_leafy); dfree(d_renum); dfree(d_rest_f); dfree(d_rest); dfree(d_grown); dfree(d_grown_sum); dfree(d_cost);
+    dfree(d_growth); dfree(d_growth_sum); dfree(d_keys); dfree(d_keys2); dfree(d_flags); dfree(d_ex); dfree(d_box); dfree(d_child);
+    dfree(d_step); dfree(d_red); dfree(d_level); dfree(d_wn); dfree(d_tp); dfree(d_qn); dfree(d_tmp);
+    if (!ok) { (void)hipGetLastError(); out.release(); }
+    return ok;
+}
+
+void PtOwnTreeGpu::release() {
+    dfree(wnodes); dfree(tripos); dfree(qnodes);
+    *this = PtOwnTreeGpu();
+}

@@ -232,7 +232,7 @@ struct ptmi_ctx;
 struct PtPrepared;               // a scene prepared on the host: validation + traversal image (ptmi_api.hip)
 PtPrepared *pt_prepare_scene(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt, const ptmi_material *mats, uint32_t nm,
                              const ptmi_bvh_node *nodes, uint32_t nn, const ptmi_light *lights, uint32_t nl, int *rc_out);
-int pt_install_scene(ptmi_ctx *c, const PtPrepared *p);      // allocates and copies on c's device; c keeps its old scene on failure
+int pt_install_scene(ptmi_ctx *c, PtPrepared *p);            // allocates and copies on c's device; c keeps its old scene on failure
 void pt_free_prepared(PtPrepared *p);
 // bytes of a width x height atlas of `format` (ptmi_upload_atlas); PTMI_E_INVALID, with the reason in `why`, for an unknown
 // format or a size that does not fit in size_t

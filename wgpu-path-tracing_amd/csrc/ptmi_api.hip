@@ -66,6 +66,7 @@ struct ptmi_ctx {
     bool own_quant = false;                  // ... and whether it has a quantised image
     bool have_scene = false;
     size_t lds_scene_bytes = 0;
+    ptmi_image_info img{};                   // what the last upload put on the device (ptmi_debug_read_image)
 
     // output (binding 0)
     uint32_t W = 0, H = 0;
@@ -239,6 +240,41 @@ struct Built {
     std::vector<float4> own_wnodes16, ref_wnodes16;   // the two hierarchies with 16-bit child references (empty: the scene is too large for them)
     std::vector<uint4> own_qnodes16;         // own_qnodes with 16-bit child references (empty: no quantised image, or too large)
     uint32_t own_root16 = PT_REF_NONE, ref_root16 = PT_REF_NONE;
+    // tree_builder = 2 with own leaves: the own tree was built on device `dev_device` into own_dev (own_tree then holds its scalars
+    // only, own_qnodes stays empty), from d_tris, the device copy of the triangles the upload takes over
+    bool own_gpu = false;
+    PtOwnTreeGpu own_dev;
+    void *d_tris = nullptr;
+    int dev_device = -1;
+
+    Built() = default;
+    Built(const Built &) = delete;
+    Built &operator=(const Built &) = delete;
+    ~Built() { own_dev.release(); if (d_tris) (void)hipFree(d_tris); }
+
+    // the image the kernels walk: its wide nodes, triangle records and whether it has quantised nodes
+    const std::vector<float4> &walk() const { return own ? own_tree.wnodes : !fast_wnodes.empty() ? fast_wnodes : wnodes; }
+    size_t walk_nodes() const { return own_gpu ? own_dev.n_wnodes : walk().size() / 4; }
+    size_t walk_tris() const { return own_gpu ? own_dev.n_tris : (own ? own_tree.tripos.size() : tripos.size()) / 3; }
+    bool quantised() const { return own_gpu ? own_dev.quantised : !(own ? own_qnodes : qnodes).empty(); }
+    uint32_t builder_used() const { return own ? (own_gpu ? 2u : 1u) : !fast_wnodes.empty() ? (gpu_tree ? 2u : 1u) : 0u; }
+    void info(ptmi_image_info *out) const {
+        const bool fast = own || !fast_wnodes.empty();
+        std::memset(out, 0, sizeof *out);
+        out->leaves_used = own ? 2u : 1u;
+        out->n_wnodes = (uint32_t)walk_nodes(); out->n_tris = (uint32_t)walk_tris();
+        out->root_ref = own ? own_tree.root_ref : fast ? fast_root : root_ref;
+        out->depth = own ? own_tree.depth : fast ? fast_depth : depth;
+        out->n_leaves = own ? own_tree.n_leaves : 0u;
+        out->max_leaf_tris = own ? own_tree.max_leaf_tris : max_leaf_tris;
+        out->quantised = quantised() ? 1u : 0u;
+        for (int k = 0; k < 3; k++) {
+            out->root_min[k] = own ? own_tree.root_min[k] : root_min[k]; out->root_max[k] = own ? own_tree.root_max[k] : root_max[k];
+            out->q_origin[k] = q_origin[k]; out->q_scale[k] = q_scale[k];
+        }
+        out->pad = own ? own_tree.pad : 0.0f; out->safe_origin = own ? own_tree.safe_origin : 0.0f;
+        out->ref_depth = depth;
+    }
 };
 
 // a copy of a wide-node image whose child references fit 16 bits: an internal node's index, or 0x8000 | (count - 1) << 12 | first
@@ -276,6 +312,46 @@ bool compact_refs(const std::vector<float4> &w, uint32_t root, std::vector<float
 
 uint32_t leaf_ref(const ptmi_bvh_node &n) {
     return PT_REF_LEAF | ((n.triangle_count - 1u) << PT_LEAF_OFF_BITS) | n.triangle_offset;
+}
+
+// The own tree on c's device (own_tree_gpu.hip) from a device copy of the triangles, made first and kept in b for the upload to take over.
+// false: not built (the caller builds on the host); b then holds no device-built image.
+bool own_tree_on_device(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt, const std::vector<uint32_t> &which, uint32_t k_max,
+                        uint32_t limit, Built &b) {
+    if (!b.d_tris) {
+        const size_t bytes = (size_t)nt * sizeof(ptmi_triangle);
+        if (hipMalloc(&b.d_tris, bytes) != hipSuccess) { b.d_tris = nullptr; (void)hipGetLastError(); return false; }
+        if (hipMemcpy(b.d_tris, tris, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(b.d_tris); b.d_tris = nullptr; (void)hipGetLastError(); return false;
+        }
+        b.dev_device = c->device;
+    }
+    PtOwnTreeGpu &g = b.own_dev;
+    if (!pt_build_own_tree_gpu(static_cast<const ptmi_triangle *>(b.d_tris), which, k_max, limit, c->stream, g)) return false;
+    PtOwnTree &t = b.own_tree;
+    t = PtOwnTree();
+    t.root_ref = g.root_ref; t.depth = g.depth; t.n_leaves = g.n_leaves; t.max_leaf_tris = g.max_leaf_tris;
+    t.pad = g.pad; t.safe_origin = g.safe_origin;
+    for (int k = 0; k < 3; k++) { t.root_min[k] = g.root_min[k]; t.root_max[k] = g.root_max[k]; }
+    if (g.quantised) {
+        b.q_top = g.q_top;
+        for (int k = 0; k < 3; k++) { b.q_origin[k] = g.q_origin[k]; b.q_scale[k] = g.q_scale[k]; }
+    }
+    if (nt <= 4096u) {                                  // small scenes: the 16-bit copies, made on the host from a read-back
+        std::vector<float4> w((size_t)g.n_wnodes * 4);
+        std::vector<uint4> q(g.quantised ? (size_t)g.n_wnodes * 2 : 0);
+        bool ok = hipMemcpy(w.data(), g.wnodes, w.size() * 16, hipMemcpyDeviceToHost) == hipSuccess;
+        ok = ok && (q.empty() || hipMemcpy(q.data(), g.qnodes, q.size() * 16, hipMemcpyDeviceToHost) == hipSuccess);
+        if (!ok) { (void)hipGetLastError(); g.release(); return false; }
+        if (!compact_refs(w, t.root_ref, b.own_wnodes16, b.own_root16) || !compact_refs(b.wnodes, b.root_ref, b.ref_wnodes16, b.ref_root16)) {
+            b.own_wnodes16.clear(); b.ref_wnodes16.clear();
+        }
+        if (!q.empty() && !b.own_wnodes16.empty()) {
+            b.own_qnodes16 = q;
+            for (uint4 &x : b.own_qnodes16) if (!compact_ref(x.w, x.w)) { b.own_qnodes16.clear(); break; }
+        }
+    }
+    return true;
 }
 
 int build_image(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt, const ptmi_bvh_node *nodes, uint32_t nn, Built &b) {
@@ -376,12 +452,20 @@ int build_image(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt, const ptmi_
         const uint32_t k_max = c->opt.leaf_tris ? c->opt.leaf_tris : (uint32_t)PT_LEAF_TRIS_DEFAULT;
         // small scenes: at most 14 levels, so that a lane's whole node stack fits the 15 LDS entries of two workgroups per CU
         const uint32_t limit = which.size() <= 2048 ? 14u : 60u;
-        b.own = pt_build_own_tree(tris, which, k_max, limit, b.own_tree);
-        if (b.own && nt <= 4096u) {                     // small scenes: both hierarchies once more with 16-bit child references
+        // tree_builder = 2: on the device for scenes above 4 096 triangles. Smaller scenes keep the host builder (a few ms): they get the
+        // 16-bit images, and which of the LDS variants fits them turns on a few tens of nodes (cornell_spheres: the host tree has 2 038,
+        // within the 2 046 of the quantised 16-bit variant; the device tree 2 109). Also on the host: without a device (the host-only
+        // debug entry points) and when the device build fails
+        if (c->opt.tree_builder == 2u && c->stream && nt > 4096u && which.size() > 2048u)
+            b.own_gpu = own_tree_on_device(c, tris, nt, which, k_max, limit, b);
+        b.own = b.own_gpu || pt_build_own_tree(tris, which, k_max, limit, b.own_tree);
+        if (b.own_gpu) {
+            // the device build made the quantised nodes and the 16-bit copies
+        } else if (b.own && nt <= 4096u) {                     // small scenes: both hierarchies once more with 16-bit child references
             if (!compact_refs(b.own_tree.wnodes, b.own_tree.root_ref, b.own_wnodes16, b.own_root16) ||
                 !compact_refs(b.wnodes, b.root_ref, b.ref_wnodes16, b.ref_root16)) { b.own_wnodes16.clear(); b.ref_wnodes16.clear(); }
         }
-        if (b.own) {
+        if (b.own && !b.own_gpu) {
             float qo[3], qs[3];
             if (pt_quantize_nodes(b.own_tree.wnodes, b.own_qnodes, qo, qs, PT_QCACHE_NODES, b.q_top))
                 for (int k = 0; k < 3; k++) { b.q_origin[k] = qo[k]; b.q_scale[k] = qs[k]; }
@@ -390,7 +474,7 @@ int build_image(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt, const ptmi_
                 b.own_qnodes16 = b.own_qnodes;
                 for (uint4 &q : b.own_qnodes16) if (!compact_ref(q.w, q.w)) { b.own_qnodes16.clear(); break; }
             }
-        } else {
+        } else if (!b.own) {
             b.leafbox.clear();
         }
         b.tree_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -658,6 +742,7 @@ struct PtPrepared {
     const ptmi_light *lights; uint32_t nl;
     double build_ms;
     ptmi_options opt;                        // what it was built under (leaves, leaf_tris, keep_reference_tree, tree_builder)
+    bool take_device_buffers = false;        // the one install may take b's device buffers instead of copying them (single device)
 };
 
 PtPrepared *pt_prepare_scene(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt, const ptmi_material *mats, uint32_t nm,
@@ -685,13 +770,13 @@ PtPrepared *pt_prepare_scene(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt
 }
 void pt_free_prepared(PtPrepared *p) { delete p; }
 
-int pt_install_scene(ptmi_ctx *c, const PtPrepared *prep) {
+int pt_install_scene(ptmi_ctx *c, PtPrepared *prep) {
     if (!c || !prep) return PTMI_E_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
     using clk = std::chrono::steady_clock;
     auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
     const auto t_start = clk::now();
-    const Built &b = prep->b;
+    Built &b = prep->b;
     const ptmi_triangle *tris = prep->tris; const uint32_t nt = prep->nt;
     const ptmi_material *mats = prep->mats; const uint32_t nm = prep->nm;
     const ptmi_light *lights = prep->lights; const uint32_t nl = prep->nl;
@@ -702,29 +787,44 @@ int pt_install_scene(ptmi_ctx *c, const PtPrepared *prep) {
     float4 *n_w16 = nullptr, *n_r16 = nullptr;
     const bool has16 = b.own && !b.own_wnodes16.empty();
     uint4 *n_qnodes = nullptr, *n_q16 = nullptr; uint32_t *n_stream = nullptr;
-    const bool own = b.own;
+    const bool own = b.own, dev = b.own_gpu;
     const bool hasq16 = has16 && !b.own_qnodes16.empty();
     const std::vector<uint4> &qn = own ? b.own_qnodes : b.qnodes;
-    const bool quant = !qn.empty();
+    const bool quant = b.quantised();
     auto up = [&](void **dst, const void *src, size_t bytes) -> hipError_t {
         if (bytes == 0) { hipError_t e = hipMalloc(dst, 16); if (e != hipSuccess) return e; return hipMemset(*dst, 0, 16); }
         hipError_t e = hipMalloc(dst, bytes); if (e != hipSuccess) return e;
         return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
     };
+    // buffers the preparation made on a device: taken over (one install on that device), or copied device to device
+    const bool take = prep->take_device_buffers && b.dev_device == c->device;
+    auto from_dev = [&](void **dst, void *src, size_t bytes, auto &&release) -> hipError_t {
+        if (take) { *dst = src; release(); return hipSuccess; }
+        hipError_t e = hipMalloc(dst, bytes ? bytes : 16); if (e != hipSuccess) return e;
+        return b.dev_device == c->device ? hipMemcpy(*dst, src, bytes, hipMemcpyDeviceToDevice)
+                                         : hipMemcpyPeer(*dst, c->device, src, b.dev_device, bytes);
+    };
     // n_fast: the hierarchy the regular rays walk when it is not the uploaded one — rebuilt over the reference's leaves, or the own tree
     const std::vector<float4> &walk = own ? b.own_tree.wnodes : b.fast_wnodes;
     const bool fast = own || !b.fast_wnodes.empty();
-    hipError_t e = up(&n_tris, tris, (size_t)nt * sizeof(ptmi_triangle));
+    hipError_t e = b.d_tris ? from_dev(&n_tris, b.d_tris, (size_t)nt * sizeof(ptmi_triangle), [&] { b.d_tris = nullptr; })
+                            : up(&n_tris, tris, (size_t)nt * sizeof(ptmi_triangle));
     if (e == hipSuccess) e = up(&n_mats, mats, (size_t)nm * sizeof(ptmi_material));
     if (e == hipSuccess) e = up(&n_lights, lights, (size_t)nl * sizeof(ptmi_light));
     if (e == hipSuccess) e = up(reinterpret_cast<void **>(&n_wnodes), b.wnodes.data(), b.wnodes.size() * 16);
     if (e == hipSuccess) e = up(reinterpret_cast<void **>(&n_tripos), b.tripos.data(), b.tripos.size() * 16);
-    if (e == hipSuccess && fast) e = up(reinterpret_cast<void **>(&n_fast), walk.data(), walk.size() * 16);
-    if (e == hipSuccess && own) e = up(reinterpret_cast<void **>(&n_own_tripos), b.own_tree.tripos.data(), b.own_tree.tripos.size() * 16);
+    const size_t walk_nodes = b.walk_nodes(), walk_tris = b.walk_tris();
+    if (dev) {
+        if (e == hipSuccess) e = from_dev(reinterpret_cast<void **>(&n_fast), b.own_dev.wnodes, walk_nodes * 64, [&] { b.own_dev.wnodes = nullptr; });
+        if (e == hipSuccess) e = from_dev(reinterpret_cast<void **>(&n_own_tripos), b.own_dev.tripos, walk_tris * 48, [&] { b.own_dev.tripos = nullptr; });
+        if (e == hipSuccess && quant) e = from_dev(reinterpret_cast<void **>(&n_qnodes), b.own_dev.qnodes, walk_nodes * 32, [&] { b.own_dev.qnodes = nullptr; });
+    }
+    if (e == hipSuccess && fast && !dev) e = up(reinterpret_cast<void **>(&n_fast), walk.data(), walk.size() * 16);
+    if (e == hipSuccess && own && !dev) e = up(reinterpret_cast<void **>(&n_own_tripos), b.own_tree.tripos.data(), b.own_tree.tripos.size() * 16);
     if (e == hipSuccess && own) e = up(reinterpret_cast<void **>(&n_leafbox), b.leafbox.data(), b.leafbox.size() * 16);
     if (e == hipSuccess && has16) e = up(reinterpret_cast<void **>(&n_w16), b.own_wnodes16.data(), b.own_wnodes16.size() * 16);
     if (e == hipSuccess && has16) e = up(reinterpret_cast<void **>(&n_r16), b.ref_wnodes16.data(), b.ref_wnodes16.size() * 16);
-    if (e == hipSuccess && quant) e = up(reinterpret_cast<void **>(&n_qnodes), qn.data(), qn.size() * 16);
+    if (e == hipSuccess && quant && !dev) e = up(reinterpret_cast<void **>(&n_qnodes), qn.data(), qn.size() * 16);
     if (e == hipSuccess && hasq16) e = up(reinterpret_cast<void **>(&n_q16), b.own_qnodes16.data(), b.own_qnodes16.size() * 16);
     if (e == hipSuccess && quant && !own) e = up(reinterpret_cast<void **>(&n_stream), b.leaf_stream.data(), b.leaf_stream.size() * 4);
     if (e != hipSuccess) {
@@ -747,7 +847,7 @@ int pt_install_scene(ptmi_ctx *c, const PtPrepared *prep) {
     s.lights = static_cast<const ptmi_light *>(c->d_lights); s.n_lights = nl;
     s.ref_wnodes = c->d_wnodes; s.ref_root_ref = b.root_ref; s.has_fast = fast ? 1u : 0u;
     s.wnodes = fast ? c->d_fast_wnodes : c->d_wnodes;
-    s.n_wnodes = (uint32_t)((fast ? walk.size() : b.wnodes.size()) / 4);
+    s.n_wnodes = (uint32_t)(fast ? walk_nodes : b.wnodes.size() / 4);
     s.tripos = own ? c->d_own_tripos : c->d_tripos;
     s.ref_tripos = c->d_tripos;
     s.qnodes = c->d_qnodes; s.leaf_stream = c->d_leaf_stream;
@@ -760,7 +860,7 @@ int pt_install_scene(ptmi_ctx *c, const PtPrepared *prep) {
     }
     s.root_ref = own ? b.own_tree.root_ref : fast ? b.fast_root : b.root_ref;
     s.own = own ? 1u : 0u;
-    s.n_own_tris = own ? (uint32_t)(b.own_tree.tripos.size() / 3) : 0u;
+    s.n_own_tris = own ? (uint32_t)walk_tris : 0u;
     s.tri_leafbox = c->d_leafbox;
     s.wnodes16 = c->d_wnodes16; s.ref_wnodes16 = c->d_ref_wnodes16; s.qnodes16 = c->d_qnodes16;
     s.root_ref16 = has16 ? b.own_root16 : PT_REF_NONE; s.ref_root_ref16 = has16 ? b.ref_root16 : PT_REF_NONE;
@@ -771,10 +871,12 @@ int pt_install_scene(ptmi_ctx *c, const PtPrepared *prep) {
     c->bvh_depth = std::max(b.depth, b.fast_depth);           // stacks must hold either tree (irregular rays use the uploaded one)
     c->own_depth = own ? b.own_tree.depth : 0u;
     c->own_quant = own && quant;
-    c->lds_scene_bytes = (size_t)s.n_wnodes * 64 + (own ? b.own_tree.tripos.size() : b.tripos.size()) * 16;
+    c->lds_scene_bytes = (size_t)s.n_wnodes * 64 + walk_tris * 48;
     c->have_scene = true;
     c->st.leaves_used = own ? 2u : 1u;
     c->st.leaf_tris_used = own ? b.own_tree.max_leaf_tris : b.max_leaf_tris;
+    c->st.tree_builder_used = b.builder_used();
+    b.info(&c->img);
     c->st.upload_copy_ms = ms_since(t_copy);
     c->st.upload_tree_ms = b.tree_ms;
     c->st.upload_ms = prep->build_ms + ms_since(t_start);
@@ -788,6 +890,7 @@ int ptmi_upload_scene(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt, const
     int rc = PTMI_OK;
     PtPrepared *p = pt_prepare_scene(c, tris, nt, mats, nm, nodes, nn, lights, nl, &rc);
     if (!p) return rc;
+    p->take_device_buffers = true;
     rc = pt_install_scene(c, p);
     pt_free_prepared(p);
     return rc;
@@ -1120,7 +1223,7 @@ int ptmi_reset_stats(ptmi_ctx *c) {
     std::memset(&c->st, 0, sizeof c->st);
     c->st.bvh_depth = c->bvh_depth;
     c->st.upload_ms = old.upload_ms; c->st.upload_tree_ms = old.upload_tree_ms; c->st.upload_copy_ms = old.upload_copy_ms;
-    c->st.leaves_used = old.leaves_used; c->st.leaf_tris_used = old.leaf_tris_used;
+    c->st.leaves_used = old.leaves_used; c->st.leaf_tris_used = old.leaf_tris_used; c->st.tree_builder_used = old.tree_builder_used;
     return PTMI_OK;
 }
 
@@ -1299,27 +1402,29 @@ int ptmi_debug_build_image(const ptmi_triangle *tris, uint32_t nt, const ptmi_bv
     Built b;
     int rc = build_image(&tmp, tris, nt, nodes, nn, b);
     if (rc) { g_create_err = tmp.err; return rc; }
-    const bool own = b.own, fast = own || !b.fast_wnodes.empty();
-    const std::vector<float4> &walk = own ? b.own_tree.wnodes : fast ? b.fast_wnodes : b.wnodes;
+    const bool own = b.own;
+    const std::vector<float4> &walk = b.walk();
     const std::vector<float4> &tp = own ? b.own_tree.tripos : b.tripos;
     const std::vector<uint4> &qn = own ? b.own_qnodes : b.qnodes;
-    info->leaves_used = own ? 2u : 1u;
-    info->n_wnodes = (uint32_t)(walk.size() / 4); info->n_tris = (uint32_t)(tp.size() / 3);
-    info->root_ref = own ? b.own_tree.root_ref : fast ? b.fast_root : b.root_ref;
-    info->depth = own ? b.own_tree.depth : fast ? b.fast_depth : b.depth;
-    info->n_leaves = own ? b.own_tree.n_leaves : 0u;
-    info->max_leaf_tris = own ? b.own_tree.max_leaf_tris : b.max_leaf_tris;
-    info->quantised = qn.empty() ? 0u : 1u;
-    for (int k = 0; k < 3; k++) {
-        info->root_min[k] = own ? b.own_tree.root_min[k] : b.root_min[k]; info->root_max[k] = own ? b.own_tree.root_max[k] : b.root_max[k];
-        info->q_origin[k] = b.q_origin[k]; info->q_scale[k] = b.q_scale[k];
-    }
-    info->pad = own ? b.own_tree.pad : 0.0f; info->safe_origin = own ? b.own_tree.safe_origin : 0.0f;
-    info->ref_depth = b.depth;
+    b.info(info);
     if (wnodes16 && !walk.empty()) std::memcpy(wnodes16, walk.data(), walk.size() * 16);
     if (qnodes8 && !qn.empty()) std::memcpy(qnodes8, qn.data(), qn.size() * 16);
     if (tripos12 && !tp.empty()) std::memcpy(tripos12, tp.data(), tp.size() * 16);
     if (leafbox8 && !b.leafbox.empty()) std::memcpy(leafbox8, b.leafbox.data(), b.leafbox.size() * 16);
+    return PTMI_OK;
+}
+
+int ptmi_debug_read_image(ptmi_ctx *c, ptmi_image_info *info, float *wnodes16, uint32_t *qnodes8, float *tripos12, float *leafbox8) {
+    if (!c || !info) return PTMI_E_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, sync_all(c));
+    *info = c->img;
+    if (!c->have_scene) return PTMI_OK;
+    const DevScene &s = c->sc;
+    if (wnodes16 && info->n_wnodes) HIP_TRY(c, hipMemcpy(wnodes16, s.wnodes, (size_t)info->n_wnodes * 64, hipMemcpyDeviceToHost));
+    if (qnodes8 && info->quantised) HIP_TRY(c, hipMemcpy(qnodes8, s.qnodes, (size_t)info->n_wnodes * 32, hipMemcpyDeviceToHost));
+    if (tripos12 && info->n_tris) HIP_TRY(c, hipMemcpy(tripos12, s.tripos, (size_t)info->n_tris * 48, hipMemcpyDeviceToHost));
+    if (leafbox8 && info->leaves_used == 2 && s.n_tris) HIP_TRY(c, hipMemcpy(leafbox8, s.tri_leafbox, (size_t)s.n_tris * 32, hipMemcpyDeviceToHost));
     return PTMI_OK;
 }
 

@@ -289,7 +289,7 @@ static napi_value stats_object(napi_env env, const ptmi_stats *s) {
     set_num(env, o, "framesPerBatchUsed", s->frames_per_batch_used);
     set_num(env, o, "leavesUsed", s->leaves_used); set_num(env, o, "leafTrisUsed", s->leaf_tris_used);
     set_num(env, o, "extendVariant", s->extend_variant); set_num(env, o, "shadowVariant", s->shadow_variant);
-    set_num(env, o, "verifyFailed", (double)s->verify_failed);
+    set_num(env, o, "verifyFailed", (double)s->verify_failed); set_num(env, o, "treeBuilderUsed", s->tree_builder_used);
     return o;
 }
 

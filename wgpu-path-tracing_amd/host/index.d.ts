@@ -28,7 +28,9 @@ export interface TraceOptions {
   perfMode?: 0 | 1;
   /** 0 / 1 / 2 (library default): run the shadow kernel on a second stream beside the next bounce */
   overlap?: 0 | 1 | 2;
-  /** read at loadModel: 0 (library default) / 1 the host builds the traversal hierarchy (SAH) / 2 the GPU does (linear BVH) */
+  /** read at loadModel: 0 (library default) / 1 the host builds the traversal hierarchy (SAH) / 2 the GPU does (leaves = 1: linear BVH;
+   *  leaves = 2: PLOC over the triangles for scenes above 4 096 triangles, the host below). Same results; stats.treeBuilderUsed
+   *  reports who built */
   treeBuilder?: 0 | 1 | 2;
   /** read at loadModel: 0 (library default = 2) / 1 triangles are tested in the uploaded BVH's own leaves / 2 in the library's own
    *  leaves (a SAH hierarchy over the triangles; the winner is verified against its reference leaf, results unchanged) */
@@ -41,6 +43,8 @@ export interface Stats {
   gpuMs: number; extendMs: number; shadeMs: number; shadowMs: number; bvhDepth: number; traversalUsed: number;
   shadowTraced: number; uploadMs: number; framesPerBatchUsed: number; leavesUsed: number; leafTrisUsed: number;
   extendVariant: number; shadowVariant: number; verifyFailed: number;
+  /** who built the walked hierarchy at the last loadModel: 1 the host, 2 the GPU, 0 none (the uploaded tree is walked as it is) */
+  treeBuilderUsed: number;
 }
 export class Renderer {
   /** `devices: [0, 1, ...]` renders on several GPUs of one node behind one Renderer (include/ptmi.h ptmi_multi_*: rows dealt out as

@@ -22,7 +22,7 @@ EXPORTS = [
     "ptmi_synchronize", "ptmi_read_output", "ptmi_write_output", "ptmi_output_device_ptr",
     "ptmi_bind_output_device", "ptmi_set_stream", "ptmi_blit", "ptmi_get_stats", "ptmi_reset_stats",
     "ptmi_debug_raygen", "ptmi_debug_intersect", "ptmi_debug_occluded", "ptmi_debug_math", "ptmi_debug_exact_math", "ptmi_get_size",
-    "ptmi_debug_image_stats", "ptmi_debug_build_image", "ptmi_throttle", "ptmi_multi_throttle",
+    "ptmi_debug_image_stats", "ptmi_debug_build_image", "ptmi_debug_read_image", "ptmi_throttle", "ptmi_multi_throttle",
     "ptmi_multi_create", "ptmi_multi_destroy", "ptmi_multi_last_error", "ptmi_multi_count", "ptmi_multi_context",
     "ptmi_multi_upload_scene", "ptmi_multi_upload_atlas", "ptmi_multi_resize", "ptmi_multi_set_options", "ptmi_multi_get_options",
     "ptmi_multi_dispatch", "ptmi_multi_gather", "ptmi_multi_synchronize", "ptmi_multi_read_output", "ptmi_multi_write_output",
@@ -62,7 +62,7 @@ class Stats(ctypes.Structure):
                 ("upload_ms", ctypes.c_double), ("upload_tree_ms", ctypes.c_double), ("upload_copy_ms", ctypes.c_double),
                 ("leaves_used", ctypes.c_uint32), ("leaf_tris_used", ctypes.c_uint32),
                 ("extend_variant", ctypes.c_uint32), ("shadow_variant", ctypes.c_uint32), ("verify_failed", ctypes.c_uint64),
-                ("reserved_stats", ctypes.c_uint32 * 2)]
+                ("tree_builder_used", ctypes.c_uint32), ("reserved_stats", ctypes.c_uint32 * 1)]
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("segments_by_bounce", "reserved_stats")}
@@ -104,6 +104,7 @@ def load():
         L.ptmi_get_size.argtypes = [vp, vp, vp]
         L.ptmi_debug_image_stats.argtypes = [vp, u32, vp, u32, vp]
         L.ptmi_debug_build_image.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp, vp, vp]
+        L.ptmi_debug_read_image.argtypes = [vp, vp, vp, vp, vp, vp]
         if L.ptmi_abi_version() != ABI_VERSION:
             raise PtmiError(-1, f"{LIB_PATH} has ABI {L.ptmi_abi_version()}, this binding expects {ABI_VERSION}: rebuild it")
         L.ptmi_get_stats.argtypes = [vp, vp]
@@ -184,6 +185,18 @@ def build_image(scene, leaves=0, leaf_tris=0, keep_reference_tree=0):
     return info, wn, qn, tp, lb
 
 
+def _read_image(L, h, n_triangles, ck):
+    """ptmi_debug_read_image on context handle h, whose last upload had n_triangles triangles (the rows of leafbox8)"""
+    info = ImageInfo()
+    ck(L.ptmi_debug_read_image(h, ctypes.byref(info), None, None, None, None))
+    wn = np.zeros((info.n_wnodes, 16), np.float32)
+    qn = np.zeros((info.n_wnodes, 8), np.uint32) if info.quantised else None
+    tp = np.zeros((info.n_tris, 12), np.float32)
+    lb = np.zeros((n_triangles, 8), np.float32) if info.leaves_used == 2 else None
+    ck(L.ptmi_debug_read_image(h, ctypes.byref(info), _p(wn), _p(qn), _p(tp), _p(lb)))
+    return info, wn, qn, tp, lb
+
+
 class Context:
     """One device context = the reference Renderer's GPU resources (bind group 0)."""
 
@@ -195,6 +208,7 @@ class Context:
             raise PtmiError(rc, self.L.ptmi_last_error(None).decode())
         self.h = h
         self.width = self.height = 0
+        self._uploaded_tris = 0
 
     def _ck(self, rc):
         if rc != 0:
@@ -220,6 +234,7 @@ class Context:
             assert a.dtype == dt and a.flags.c_contiguous
         self._ck(self.L.ptmi_upload_scene(self.h, _p(scene.tris), len(scene.tris), _p(scene.mats), len(scene.mats),
                                           _p(scene.nodes), len(scene.nodes), _p(scene.lights), len(scene.lights)))
+        self._uploaded_tris = len(scene.tris)
         a = scene.atlas
         if a is None:
             self._ck(self.L.ptmi_upload_atlas(self.h, None, 0, 0, 0))
@@ -293,6 +308,11 @@ class Context:
     def reset_stats(self):
         self._ck(self.L.ptmi_reset_stats(self.h))
 
+    def read_image(self):
+        """The traversal image the last upload_scene put on the device (include/ptmi.h: ptmi_debug_read_image), as build_image()
+        returns it: (info, wnodes, qnodes or None, tripos, leafbox or None)."""
+        return _read_image(self.L, self.h, self._uploaded_tris, self._ck)
+
     # -- per-stage entry points ------------------------------------------------
     def debug_raygen(self, camera, xs, ys, frames):
         xs, ys, frames = (np.ascontiguousarray(a, np.uint32) for a in (xs, ys, frames))
@@ -347,6 +367,7 @@ class MultiContext:
         self.h = h
         self.n = len(devices)
         self.width = self.height = 0
+        self._uploaded_tris = 0
 
     def _ck(self, rc):
         if rc != 0:
@@ -368,12 +389,22 @@ class MultiContext:
     def upload_scene(self, scene):
         self._ck(self.L.ptmi_multi_upload_scene(self.h, _p(scene.tris), len(scene.tris), _p(scene.mats), len(scene.mats),
                                                 _p(scene.nodes), len(scene.nodes), _p(scene.lights), len(scene.lights)))
+        self._uploaded_tris = len(scene.tris)
         a = scene.atlas
         if a is None:
             self._ck(self.L.ptmi_multi_upload_atlas(self.h, None, 0, 0, 0))
         else:
             fmt = ATLAS_RGBA16F if a.dtype == np.float16 else ATLAS_RGBA32F
             self._ck(self.L.ptmi_multi_upload_atlas(self.h, _p(a), a.shape[1], a.shape[0], fmt))
+
+    def read_image(self, i):
+        """Context.read_image of device i's context (ptmi_multi_context)"""
+        h = self.L.ptmi_multi_context(self.h, i)
+
+        def ck(rc):
+            if rc != 0:
+                raise PtmiError(rc, self.L.ptmi_last_error(h).decode())
+        return _read_image(self.L, h, self._uploaded_tris, ck)
 
     def resize(self, width, height):
         self._ck(self.L.ptmi_multi_resize(self.h, width, height))
