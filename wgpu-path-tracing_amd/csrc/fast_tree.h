@@ -54,11 +54,13 @@ bool pt_quantize_tree(const std::vector<PtFastLeaf> &leaves, const std::vector<f
 //            fma(bound, 1/d, -o/d) accepts every ray the exact box would (for origins within `safe_origin` of the coordinate origin)
 //   tripos   3 float4 per listed triangle in LEAF order: (v0, bits(ORIGINAL triangle index)), (e1, 0), (e2, 0); a leaf reference
 //            is PT_REF_LEAF | (count - 1) << 26 | position of its first triangle in this array
-struct PtOwnTree {
-    std::vector<float4> wnodes, tripos;
+struct PtOwnTreeHeader {               // what both builders report beside the buffers
     uint32_t root_ref = 0xFFFFFFFFu, depth = 0, n_leaves = 0, max_leaf_tris = 0;
     float root_min[3] = {0, 0, 0}, root_max[3] = {0, 0, 0};     // padded
     float pad = 0.0f, safe_origin = 0.0f;
+};
+struct PtOwnTree : PtOwnTreeHeader {
+    std::vector<float4> wnodes, tripos;
 };
 struct ptmi_triangle;
 // which: the original indices of the triangles to build over (those some reachable reference leaf lists), ascending.
@@ -70,13 +72,11 @@ bool pt_build_own_tree(const ptmi_triangle *tris, const std::vector<uint32_t> &w
 // buffers have the layouts of PtOwnTree::wnodes / tripos and of pt_quantize_nodes (qnodes: NULL when the scene has no quantised image);
 // pad, safe_origin and the root box equal the host build's bit for bit (they depend on the triangle set only). Synchronises the stream.
 // false: could not (a non-finite vertex, more than depth_limit levels, an allocation or HIP failure); nothing is left allocated.
-struct PtOwnTreeGpu {
+struct PtOwnTreeGpu : PtOwnTreeHeader {
     float4 *wnodes = nullptr, *tripos = nullptr;
     uint4 *qnodes = nullptr;
-    uint32_t n_wnodes = 0, n_tris = 0, root_ref = 0xFFFFFFFFu, depth = 0, n_leaves = 0, max_leaf_tris = 0, q_top = 0;
+    uint32_t n_wnodes = 0, n_tris = 0, q_top = 0;
     bool quantised = false;
-    float root_min[3] = {0, 0, 0}, root_max[3] = {0, 0, 0};
-    float pad = 0.0f, safe_origin = 0.0f;
     float q_origin[3] = {0, 0, 0}, q_scale[3] = {0, 0, 0};
     void release();                        // frees the device buffers (hipFree) and resets the fields
 };

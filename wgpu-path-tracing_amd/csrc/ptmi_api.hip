@@ -15,13 +15,27 @@
 #include <cstdio>
 #include <cstring>
 #include <deque>
+#include <memory>
 #include <string>
+#include <typeinfo>
 #include <utility>
 #include <vector>
 
 namespace {
 
 thread_local std::string g_create_err;
+
+// The device buffers of an uploaded scene, one entry each (the atlas is ptmi_upload_atlas's). The walked image's entries are absent when
+// the kernels walk the tree as uploaded: DevScene then points at the reference entries.
+enum SceneBuf {
+    kTris, kMats, kLights,
+    kRefWnodes, kRefTripos,            // the tree as uploaded; triangle images in original order
+    kWnodes, kTripos,                  // the walked image: a hierarchy rebuilt over the reference's leaves (nodes only), or own leaves
+    kQnodes, kLeafStream,              // its quantised nodes; the leaf stream (the reference's leaves only)
+    kLeafbox,                          // own leaves: per original triangle, the box of the reference leaf that lists it
+    kWnodes16, kRefWnodes16, kQnodes16,    // own leaves, small scenes: the two hierarchies and the quantised nodes with 16-bit references
+    kSceneBufs
+};
 
 struct EventPair { hipEvent_t a, b; int kind; };   // kind: 0 dispatch, 1 extend, 2 shade, 3 shadow, 4 raygen, 5 compaction, 6 accumulate
 constexpr size_t kMaxPendingEvents = 4096;        // a caller that never synchronises (a preview loop) must not grow the list without bound
@@ -54,18 +68,11 @@ struct ptmi_ctx {
     ptmi_options opt{};
 
     // scene (bindings 1, 2, 4, 5, 6)
-    void *d_tris = nullptr, *d_mats = nullptr, *d_lights = nullptr, *d_atlas = nullptr;
-    float4 *d_wnodes = nullptr, *d_tripos = nullptr, *d_fast_wnodes = nullptr;
-    float4 *d_own_tripos = nullptr, *d_leafbox = nullptr, *d_wnodes16 = nullptr, *d_ref_wnodes16 = nullptr;
-    uint4 *d_qnodes16 = nullptr;
-    DevScene *d_scene = nullptr;                       // sc in device memory (DevScene::self), rewritten whenever sc changes               // own leaves: leaf-ordered triangle images, per-triangle reference leaf boxes
-    uint4 *d_qnodes = nullptr; uint32_t *d_leaf_stream = nullptr;        // quantised image of the rebuilt hierarchy (global variant)
+    void *buf[kSceneBufs] = {};                        // indexed by SceneBuf (absent: NULL)
+    void *d_atlas = nullptr;
+    DevScene *d_scene = nullptr;                       // sc in device memory (DevScene::self), rewritten whenever sc changes
     DevScene sc{};
-    uint32_t bvh_depth = 0;
-    uint32_t own_depth = 0;                  // own leaves: levels of the library's hierarchy (the uploaded tree's: bvh_depth)
-    bool own_quant = false;                  // ... and whether it has a quantised image
     bool have_scene = false;
-    size_t lds_scene_bytes = 0;
     ptmi_image_info img{};                   // what the last upload put on the device (ptmi_debug_read_image)
 
     // output (binding 0)
@@ -87,10 +94,17 @@ namespace {
 constexpr int kStatsWords = 8 + 64;
 constexpr int kShadowCount = 72;          // slot of the shadow-queue length in ctx->counts (80 words)
 constexpr size_t kLdsMax = 160 * 1024;
-int fail(const ptmi_ctx *c, int code, const char *fmt, ...) {
+void vfail(std::string &err, const char *fmt, va_list ap) {
     char buf[512];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    if (c) c->err = buf; else g_create_err = buf;
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    err = buf;
+}
+int fail(std::string &err, int code, const char *fmt, ...) {
+    va_list ap; va_start(ap, fmt); vfail(err, fmt, ap); va_end(ap);
+    return code;
+}
+int fail(const ptmi_ctx *c, int code, const char *fmt, ...) {
+    va_list ap; va_start(ap, fmt); vfail(c ? c->err : g_create_err, fmt, ap); va_end(ap);
     return code;
 }
 #define HIP_TRY(c, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
@@ -219,63 +233,55 @@ int ensure_capacity(ptmi_ctx *c, Lane &ln, size_t n) {
 }
 
 // ---- scene validation and the traversal image ---------------------------------
-struct Built {
-    std::vector<float4> wnodes, tripos;      // reference-shaped image
-    std::vector<float4> fast_wnodes;         // SAH tree over the reference's leaves (empty: not applicable)
-    float root_min[3] = {0, 0, 0}, root_max[3] = {0, 0, 0};
-    uint32_t root_ref = PT_REF_NONE, depth = 0;
-    uint32_t fast_root = PT_REF_NONE, fast_depth = 0;
-    double tree_ms = 0.0;                    // time spent in pt_build_fast_tree
-    float tri_safe_dsum = 0.0f;              // DevScene::tri_safe_dsum
-    std::vector<uint4> qnodes; std::vector<uint32_t> leaf_stream;     // quantised image (empty: none)
-    float q_origin[3] = {0, 0, 0}, q_scale[3] = {0, 0, 0};
-    uint32_t q_top = 0;                      // quantised nodes numbered breadth-first at the front (LDS-resident in the kernel)
-    uint32_t max_leaf_tris = 0;
-    bool gpu_tree = false;                   // the rebuilt hierarchy came from the device (ptmi_options.tree_builder = 2)
-    // own leaves (ptmi_options.leaves = 2)
-    bool own = false;
-    PtOwnTree own_tree;
-    std::vector<uint4> own_qnodes;           // quantised nodes of own_tree (empty: a 16-bit grid does not resolve this scene)
-    std::vector<float4> leafbox;             // 2 float4 per triangle (original index): its reference leaf's box
-    std::vector<float4> own_wnodes16, ref_wnodes16;   // the two hierarchies with 16-bit child references (empty: the scene is too large for them)
-    std::vector<uint4> own_qnodes16;         // own_qnodes with 16-bit child references (empty: no quantised image, or too large)
-    uint32_t own_root16 = PT_REF_NONE, ref_root16 = PT_REF_NONE;
-    // tree_builder = 2 with own leaves: the own tree was built on device `dev_device` into own_dev (own_tree then holds its scalars
-    // only, own_qnodes stays empty), from d_tris, the device copy of the triangles the upload takes over
-    bool own_gpu = false;
-    PtOwnTreeGpu own_dev;
-    void *d_tris = nullptr;
-    int dev_device = -1;
+// One scene buffer as a preparation leaves it: absent, host bytes (a vector moved in, or the caller's blob), or a buffer on `device` that
+// the install takes over or copies.
+struct HeldBuf {
+    bool present = false;
+    std::shared_ptr<const void> keep;        // the vector `host` points into (none: the caller's blob)
+    const std::type_info *type = nullptr;    // ... and its type
+    const void *host = nullptr;
+    void *dev = nullptr;
+    int device = -1;
+    size_t bytes = 0;
+};
 
-    Built() = default;
+// The scene's buffers, and one header for the image the kernels walk.
+struct Built {
+    HeldBuf buf[kSceneBufs];
+    ptmi_image_info img{};                   // the walked image (ptmi_debug_read_image); ref_depth: levels of the tree as uploaded
+    uint32_t ref_root_ref = PT_REF_NONE;     // the root of the tree as uploaded
+    float ref_root_min[3] = {0, 0, 0}, ref_root_max[3] = {0, 0, 0};
+    uint32_t root_ref16 = PT_REF_NONE, ref_root_ref16 = PT_REF_NONE;     // the roots of kWnodes16 / kRefWnodes16
+    uint32_t q_top = 0;                      // quantised nodes numbered breadth-first at the front (LDS-resident in the kernel)
+    float tri_safe_dsum = 0.0f;              // DevScene::tri_safe_dsum
+    uint32_t tree_builder_used = 0;          // ptmi_stats.tree_builder_used
+    double tree_ms = 0.0;                    // time spent building and quantising the walked hierarchy
+
+    Built() { img.leaves_used = 1; img.root_ref = PT_REF_NONE; }
     Built(const Built &) = delete;
     Built &operator=(const Built &) = delete;
-    ~Built() { own_dev.release(); if (d_tris) (void)hipFree(d_tris); }
+    ~Built() { for (HeldBuf &e : buf) if (e.dev) (void)hipFree(e.dev); }
 
-    // the image the kernels walk: its wide nodes, triangle records and whether it has quantised nodes
-    const std::vector<float4> &walk() const { return own ? own_tree.wnodes : !fast_wnodes.empty() ? fast_wnodes : wnodes; }
-    size_t walk_nodes() const { return own_gpu ? own_dev.n_wnodes : walk().size() / 4; }
-    size_t walk_tris() const { return own_gpu ? own_dev.n_tris : (own ? own_tree.tripos.size() : tripos.size()) / 3; }
-    bool quantised() const { return own_gpu ? own_dev.quantised : !(own ? own_qnodes : qnodes).empty(); }
-    uint32_t builder_used() const { return own ? (own_gpu ? 2u : 1u) : !fast_wnodes.empty() ? (gpu_tree ? 2u : 1u) : 0u; }
-    void info(ptmi_image_info *out) const {
-        const bool fast = own || !fast_wnodes.empty();
-        std::memset(out, 0, sizeof *out);
-        out->leaves_used = own ? 2u : 1u;
-        out->n_wnodes = (uint32_t)walk_nodes(); out->n_tris = (uint32_t)walk_tris();
-        out->root_ref = own ? own_tree.root_ref : fast ? fast_root : root_ref;
-        out->depth = own ? own_tree.depth : fast ? fast_depth : depth;
-        out->n_leaves = own ? own_tree.n_leaves : 0u;
-        out->max_leaf_tris = own ? own_tree.max_leaf_tris : max_leaf_tris;
-        out->quantised = quantised() ? 1u : 0u;
-        for (int k = 0; k < 3; k++) {
-            out->root_min[k] = own ? own_tree.root_min[k] : root_min[k]; out->root_max[k] = own ? own_tree.root_max[k] : root_max[k];
-            out->q_origin[k] = q_origin[k]; out->q_scale[k] = q_scale[k];
-        }
-        out->pad = own ? own_tree.pad : 0.0f; out->safe_origin = own ? own_tree.safe_origin : 0.0f;
-        out->ref_depth = depth;
+    template <class T> void hold(int k, std::vector<T> &&v) {
+        auto p = std::make_shared<const std::vector<T>>(std::move(v));
+        buf[k].present = true; buf[k].host = p->data(); buf[k].bytes = p->size() * sizeof(T); buf[k].keep = std::move(p);
+        buf[k].type = &typeid(std::vector<T>);
+    }
+    void view(int k, const void *host, size_t bytes) { buf[k].present = true; buf[k].host = host; buf[k].bytes = bytes; }
+    void on_device(int k, void *dev, size_t bytes, int device) {
+        buf[k].present = true; buf[k].dev = dev; buf[k].bytes = bytes; buf[k].device = device;
+    }
+    template <class T> const std::vector<T> &vec(int k) const {       // an entry held on the host as a vector of T (else empty)
+        static const std::vector<T> none;
+        const HeldBuf &e = buf[k];
+        return e.type && *e.type == typeid(std::vector<T>) ? *static_cast<const std::vector<T> *>(e.keep.get()) : none;
     }
 };
+
+// kWnodes / kTripos as the kernels walk them, in a preparation's table or a context's: the reference's entry when no other image was built
+bool present(const HeldBuf &e) { return e.present; }
+bool present(const void *d) { return d != nullptr; }
+template <class E> const E &walked(const E *buf, SceneBuf k) { return present(buf[k]) ? buf[k] : buf[k == kWnodes ? kRefWnodes : kRefTripos]; }
 
 // a copy of a wide-node image whose child references fit 16 bits: an internal node's index, or 0x8000 | (count - 1) << 12 | first
 // triangle. false: some reference does not fit (more than 32 767 nodes, a leaf beyond triangle 4 095 or of more than 8 triangles)
@@ -314,56 +320,77 @@ uint32_t leaf_ref(const ptmi_bvh_node &n) {
     return PT_REF_LEAF | ((n.triangle_count - 1u) << PT_LEAF_OFF_BITS) | n.triangle_offset;
 }
 
-// The own tree on c's device (own_tree_gpu.hip) from a device copy of the triangles, made first and kept in b for the upload to take over.
-// false: not built (the caller builds on the host); b then holds no device-built image.
-bool own_tree_on_device(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt, const std::vector<uint32_t> &which, uint32_t k_max,
-                        uint32_t limit, Built &b) {
-    if (!b.d_tris) {
-        const size_t bytes = (size_t)nt * sizeof(ptmi_triangle);
-        if (hipMalloc(&b.d_tris, bytes) != hipSuccess) { b.d_tris = nullptr; (void)hipGetLastError(); return false; }
-        if (hipMemcpy(b.d_tris, tris, bytes, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(b.d_tris); b.d_tris = nullptr; (void)hipGetLastError(); return false;
-        }
-        b.dev_device = c->device;
-    }
-    PtOwnTreeGpu &g = b.own_dev;
-    if (!pt_build_own_tree_gpu(static_cast<const ptmi_triangle *>(b.d_tris), which, k_max, limit, c->stream, g)) return false;
-    PtOwnTree &t = b.own_tree;
-    t = PtOwnTree();
-    t.root_ref = g.root_ref; t.depth = g.depth; t.n_leaves = g.n_leaves; t.max_leaf_tris = g.max_leaf_tris;
-    t.pad = g.pad; t.safe_origin = g.safe_origin;
-    for (int k = 0; k < 3; k++) { t.root_min[k] = g.root_min[k]; t.root_max[k] = g.root_max[k]; }
-    if (g.quantised) {
-        b.q_top = g.q_top;
-        for (int k = 0; k < 3; k++) { b.q_origin[k] = g.q_origin[k]; b.q_scale[k] = g.q_scale[k]; }
-    }
-    if (nt <= 4096u) {                                  // small scenes: the 16-bit copies, made on the host from a read-back
-        std::vector<float4> w((size_t)g.n_wnodes * 4);
-        std::vector<uint4> q(g.quantised ? (size_t)g.n_wnodes * 2 : 0);
-        bool ok = hipMemcpy(w.data(), g.wnodes, w.size() * 16, hipMemcpyDeviceToHost) == hipSuccess;
-        ok = ok && (q.empty() || hipMemcpy(q.data(), g.qnodes, q.size() * 16, hipMemcpyDeviceToHost) == hipSuccess);
-        if (!ok) { (void)hipGetLastError(); g.release(); return false; }
-        if (!compact_refs(w, t.root_ref, b.own_wnodes16, b.own_root16) || !compact_refs(b.wnodes, b.root_ref, b.ref_wnodes16, b.ref_root16)) {
-            b.own_wnodes16.clear(); b.ref_wnodes16.clear();
-        }
-        if (!q.empty() && !b.own_wnodes16.empty()) {
-            b.own_qnodes16 = q;
-            for (uint4 &x : b.own_qnodes16) if (!compact_ref(x.w, x.w)) { b.own_qnodes16.clear(); break; }
-        }
-    }
-    return true;
+// The own tree on `device` (own_tree_gpu.hip) from a device copy of the triangles, made first and kept as b's kTris for the upload to
+// take over. false: not built (the caller builds on the host).
+bool own_tree_on_device(hipStream_t stream, int device, const ptmi_triangle *tris, uint32_t nt, const std::vector<uint32_t> &which,
+                        uint32_t k_max, uint32_t limit, Built &b, PtOwnTreeGpu &g) {
+    const size_t bytes = (size_t)nt * sizeof(ptmi_triangle);
+    void *d_tris = nullptr;
+    if (hipMalloc(&d_tris, bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (hipMemcpy(d_tris, tris, bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_tris); (void)hipGetLastError(); return false; }
+    b.on_device(kTris, d_tris, bytes, device);
+    return pt_build_own_tree_gpu(static_cast<const ptmi_triangle *>(d_tris), which, k_max, limit, stream, g);
 }
 
-int build_image(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt, const ptmi_bvh_node *nodes, uint32_t nn, Built &b) {
-    if (nt == 0 || nn == 0) return PTMI_OK;                       // empty scene: every ray misses
-    if (nt > PT_LEAF_OFF_MASK) return fail(c, PTMI_E_UNSUPPORTED, "more than %u triangles", PT_LEAF_OFF_MASK);
+// Own leaves, after whichever builder ran (on_device: g on `device`, else t): the walked image and its header, the quantised nodes (the
+// device builder made its own) and, for scenes of up to 4 096 triangles, both hierarchies and the quantised nodes once more with 16-bit
+// child references (the device builder only runs on larger scenes).
+void own_image(Built &b, bool on_device, int device, PtOwnTreeGpu &g, PtOwnTree &t, uint32_t nt, const std::vector<float4> &ref_wnodes,
+               std::vector<float4> &&leafbox) {
+    ptmi_image_info &h = b.img;
+    const PtOwnTreeHeader &o = on_device ? static_cast<const PtOwnTreeHeader &>(g) : t;
+    h.leaves_used = 2u; h.root_ref = o.root_ref; h.depth = o.depth; h.n_leaves = o.n_leaves; h.max_leaf_tris = o.max_leaf_tris;
+    for (int k = 0; k < 3; k++) { h.root_min[k] = o.root_min[k]; h.root_max[k] = o.root_max[k]; }
+    h.pad = o.pad; h.safe_origin = o.safe_origin;
+    b.tree_builder_used = on_device ? 2u : 1u;
+    b.hold(kLeafbox, std::move(leafbox));
+    if (on_device) {
+        h.n_wnodes = g.n_wnodes; h.n_tris = g.n_tris; h.quantised = g.quantised ? 1u : 0u; b.q_top = g.q_top;
+        for (int k = 0; k < 3; k++) { h.q_origin[k] = g.q_origin[k]; h.q_scale[k] = g.q_scale[k]; }
+        b.on_device(kWnodes, g.wnodes, (size_t)g.n_wnodes * 64, device);
+        b.on_device(kTripos, g.tripos, (size_t)g.n_tris * 48, device);
+        if (g.quantised) b.on_device(kQnodes, g.qnodes, (size_t)g.n_wnodes * 32, device);
+        g.wnodes = nullptr; g.tripos = nullptr; g.qnodes = nullptr;
+        return;
+    }
+    std::vector<uint4> q;
+    float qo[3], qs[3];
+    if (pt_quantize_nodes(t.wnodes, q, qo, qs, PT_QCACHE_NODES, b.q_top))
+        for (int k = 0; k < 3; k++) { h.q_origin[k] = qo[k]; h.q_scale[k] = qs[k]; }
+    else q.clear();
+    std::vector<float4> w16, r16;
+    uint32_t root16, ref_root16;
+    if (nt <= 4096u && !t.wnodes.empty() && compact_refs(t.wnodes, t.root_ref, w16, root16) && compact_refs(ref_wnodes, b.ref_root_ref, r16, ref_root16)) {
+        b.root_ref16 = root16; b.ref_root_ref16 = ref_root16;
+        if (!q.empty()) {                              // (the quantised nodes are renumbered: node 0 stays the root)
+            std::vector<uint4> q16 = q;
+            bool ok = true;
+            for (uint4 &x : q16) if (!(ok = compact_ref(x.w, x.w))) break;
+            if (ok) b.hold(kQnodes16, std::move(q16));
+        }
+        b.hold(kWnodes16, std::move(w16)); b.hold(kRefWnodes16, std::move(r16));
+    }
+    h.n_wnodes = (uint32_t)(t.wnodes.size() / 4); h.n_tris = (uint32_t)(t.tripos.size() / 3); h.quantised = q.empty() ? 0u : 1u;
+    b.hold(kWnodes, std::move(t.wnodes)); b.hold(kTripos, std::move(t.tripos));
+    if (!q.empty()) b.hold(kQnodes, std::move(q));
+}
+
+// The traversal image of a scene under `opt`. tree_builder = 2 builds on `device` through `stream` (none: the host-only debug entry
+// points build on the host). err: why a scene is refused.
+int build_image(const ptmi_options &opt, hipStream_t stream, int device, const ptmi_triangle *tris, uint32_t nt,
+                const ptmi_bvh_node *nodes, uint32_t nn, Built &b, std::string &err) {
+    if (nt == 0 || nn == 0) {                                      // empty scene: every ray misses
+        b.hold(kRefWnodes, std::vector<float4>()); b.hold(kRefTripos, std::vector<float4>());
+        return PTMI_OK;
+    }
+    if (nt > PT_LEAF_OFF_MASK) return fail(err, PTMI_E_UNSUPPORTED, "more than %u triangles", PT_LEAF_OFF_MASK);
     // leaf <=> triangleCount > 0 (pt.wgsl:271)
     auto check_leaf = [&](uint32_t i) -> int {
         const ptmi_bvh_node &n = nodes[i];
         if (n.triangle_count > PT_LEAF_MAX_TRIS)
-            return fail(c, PTMI_E_UNSUPPORTED, "BVH leaf %u holds %u triangles (limit %u)", i, n.triangle_count, PT_LEAF_MAX_TRIS);
+            return fail(err, PTMI_E_UNSUPPORTED, "BVH leaf %u holds %u triangles (limit %u)", i, n.triangle_count, PT_LEAF_MAX_TRIS);
         if ((uint64_t)n.triangle_offset + n.triangle_count > nt)
-            return fail(c, PTMI_E_INVALID, "BVH leaf %u references triangles [%u,+%u) beyond %u", i, n.triangle_offset, n.triangle_count, nt);
+            return fail(err, PTMI_E_INVALID, "BVH leaf %u references triangles [%u,+%u) beyond %u", i, n.triangle_offset, n.triangle_count, nt);
         return PTMI_OK;
     };
     std::vector<uint32_t> wide_of(nn, PT_REF_NONE);
@@ -372,15 +399,15 @@ int build_image(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt, const ptmi_
     std::vector<Item> stack;
     // pass 1: preorder (left first) numbering of the internal nodes
     stack.push_back({0u, 1u});
-    uint32_t n_wide = 0;
+    uint32_t n_wide = 0, depth = 0, max_leaf_tris = 0;
     uint64_t next_offset = 0;               // leaves must come in ascending triangle order along the left-first DFS (below)
     while (!stack.empty()) {
         Item it = stack.back(); stack.pop_back();
-        if (it.node >= nn) return fail(c, PTMI_E_INVALID, "BVH child index %u out of range (%u nodes)", it.node, nn);
-        if (seen[it.node]) return fail(c, PTMI_E_INVALID, "BVH node %u is reachable twice", it.node);
+        if (it.node >= nn) return fail(err, PTMI_E_INVALID, "BVH child index %u out of range (%u nodes)", it.node, nn);
+        if (seen[it.node]) return fail(err, PTMI_E_INVALID, "BVH node %u is reachable twice", it.node);
         seen[it.node] = 1;
-        b.depth = std::max(b.depth, it.depth);
-        if (it.depth > 62) return fail(c, PTMI_E_UNSUPPORTED, "BVH deeper than 62 levels (the reference's own traversal stack holds 64 entries, pt.wgsl:249)");
+        depth = std::max(depth, it.depth);
+        if (it.depth > 62) return fail(err, PTMI_E_UNSUPPORTED, "BVH deeper than 62 levels (the reference's own traversal stack holds 64 entries, pt.wgsl:249)");
         const ptmi_bvh_node &n = nodes[it.node];
         if (n.triangle_count > 0) {
             int rc = check_leaf(it.node); if (rc) return rc;
@@ -388,22 +415,22 @@ int build_image(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt, const ptmi_
             // order and break ties by the lowest triangle index. The two agree iff leaf ranges ascend along that DFS —
             // true of every tree bvh.ts builds (children split one contiguous range, left = lower part, bvh.ts:114-127).
             if (n.triangle_offset < next_offset)
-                return fail(c, PTMI_E_UNSUPPORTED, "BVH leaf %u starts at triangle %u but an earlier leaf of the left-first DFS ends at %llu: "
+                return fail(err, PTMI_E_UNSUPPORTED, "BVH leaf %u starts at triangle %u but an earlier leaf of the left-first DFS ends at %llu: "
                             "leaf ranges must ascend in DFS order (as bvh.ts builds them)", it.node, n.triangle_offset, (unsigned long long)next_offset);
             next_offset = (uint64_t)n.triangle_offset + n.triangle_count;
-            b.max_leaf_tris = std::max(b.max_leaf_tris, n.triangle_count);
+            max_leaf_tris = std::max(max_leaf_tris, n.triangle_count);
             continue;
         }
         wide_of[it.node] = n_wide++;
         stack.push_back({n.right, it.depth + 1});
         stack.push_back({n.left, it.depth + 1});
     }
-    b.wnodes.assign((size_t)n_wide * 4, make_float4(0, 0, 0, 0));
+    std::vector<float4> wnodes((size_t)n_wide * 4, make_float4(0, 0, 0, 0));
     auto ref_of = [&](uint32_t i) { return nodes[i].triangle_count > 0 ? leaf_ref(nodes[i]) : wide_of[i]; };
     for (uint32_t i = 0; i < nn; i++) {
         if (wide_of[i] == PT_REF_NONE) continue;
         const ptmi_bvh_node &L = nodes[nodes[i].left], &R = nodes[nodes[i].right];
-        float4 *w = &b.wnodes[(size_t)wide_of[i] * 4];
+        float4 *w = &wnodes[(size_t)wide_of[i] * 4];
         w[0] = make_float4(L.aabb_min[0], L.aabb_min[1], L.aabb_min[2], L.aabb_max[0]);
         w[1] = make_float4(L.aabb_max[1], L.aabb_max[2], R.aabb_min[0], R.aabb_min[1]);
         w[2] = make_float4(R.aabb_min[2], R.aabb_max[0], R.aabb_max[1], R.aabb_max[2]);
@@ -411,8 +438,12 @@ int build_image(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt, const ptmi_
         float fl, fr; std::memcpy(&fl, &lr, 4); std::memcpy(&fr, &rr, 4);
         w[3] = make_float4(fl, fr, 0.0f, 0.0f);
     }
-    for (int k = 0; k < 3; k++) { b.root_min[k] = nodes[0].aabb_min[k]; b.root_max[k] = nodes[0].aabb_max[k]; }
-    b.root_ref = ref_of(0);
+    for (int k = 0; k < 3; k++) { b.ref_root_min[k] = nodes[0].aabb_min[k]; b.ref_root_max[k] = nodes[0].aabb_max[k]; }
+    b.ref_root_ref = ref_of(0);
+    // the header of the tree as uploaded: the image the kernels walk unless a hierarchy is built below
+    ptmi_image_info &h = b.img;
+    h.n_wnodes = n_wide; h.n_tris = nt; h.root_ref = b.ref_root_ref; h.depth = h.ref_depth = depth; h.max_leaf_tris = max_leaf_tris;
+    for (int k = 0; k < 3; k++) { h.root_min[k] = b.ref_root_min[k]; h.root_max[k] = b.ref_root_max[k]; }
     // Nested tree (each node box contains its children's, all finite)? Then rebuild the hierarchy over the
     // reference's leaves (fast_tree.hip explains why the results cannot change).
     bool nested = n_wide > 0;
@@ -432,76 +463,64 @@ int build_image(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt, const ptmi_
                     nested = nested && nodes[ch].aabb_min[k] >= n.aabb_min[k] && nodes[ch].aabb_max[k] <= n.aabb_max[k];
         }
     }
-    const uint32_t leaves_mode = c->opt.leaves ? c->opt.leaves : (uint32_t)PT_LEAVES_DEFAULT;
-    if (nested && leaves_mode == 2u && !c->opt.keep_reference_tree) {
+    const uint32_t leaves_mode = opt.leaves ? opt.leaves : (uint32_t)PT_LEAVES_DEFAULT;
+    bool own = false;
+    if (nested && leaves_mode == 2u && !opt.keep_reference_tree) {
         // The library's own leaves (fast_tree.h). What the reference's semantics need from the uploaded tree is kept beside them: the
         // tree itself (slow rays walk it) and, per triangle, the box of the leaf that lists it (the winner's verification).
         const auto t0 = std::chrono::steady_clock::now();
         std::vector<uint32_t> which;
         which.reserve(nt);
-        b.leafbox.assign((size_t)nt * 2, make_float4(0, 0, 0, 0));
+        std::vector<float4> leafbox((size_t)nt * 2, make_float4(0, 0, 0, 0));
         for (const PtFastLeaf &l : leaves) {            // (leaf ranges ascend and do not overlap: checked above)
             const uint32_t first = l.ref & PT_LEAF_OFF_MASK;
             for (uint32_t k = 0; k < l.weight; k++) {
                 which.push_back(first + k);
-                b.leafbox[2 * (size_t)(first + k)] = make_float4(l.mn[0], l.mn[1], l.mn[2], 0.0f);
-                b.leafbox[2 * (size_t)(first + k) + 1] = make_float4(l.mx[0], l.mx[1], l.mx[2], 0.0f);
+                leafbox[2 * (size_t)(first + k)] = make_float4(l.mn[0], l.mn[1], l.mn[2], 0.0f);
+                leafbox[2 * (size_t)(first + k) + 1] = make_float4(l.mx[0], l.mx[1], l.mx[2], 0.0f);
             }
         }
         std::sort(which.begin(), which.end());
-        const uint32_t k_max = c->opt.leaf_tris ? c->opt.leaf_tris : (uint32_t)PT_LEAF_TRIS_DEFAULT;
+        const uint32_t k_max = opt.leaf_tris ? opt.leaf_tris : (uint32_t)PT_LEAF_TRIS_DEFAULT;
         // small scenes: at most 14 levels, so that a lane's whole node stack fits the 15 LDS entries of two workgroups per CU
         const uint32_t limit = which.size() <= 2048 ? 14u : 60u;
         // tree_builder = 2: on the device for scenes above 4 096 triangles. Smaller scenes keep the host builder (a few ms): they get the
         // 16-bit images, and which of the LDS variants fits them turns on a few tens of nodes (cornell_spheres: the host tree has 2 038,
         // within the 2 046 of the quantised 16-bit variant; the device tree 2 109). Also on the host: without a device (the host-only
         // debug entry points) and when the device build fails
-        if (c->opt.tree_builder == 2u && c->stream && nt > 4096u && which.size() > 2048u)
-            b.own_gpu = own_tree_on_device(c, tris, nt, which, k_max, limit, b);
-        b.own = b.own_gpu || pt_build_own_tree(tris, which, k_max, limit, b.own_tree);
-        if (b.own_gpu) {
-            // the device build made the quantised nodes and the 16-bit copies
-        } else if (b.own && nt <= 4096u) {                     // small scenes: both hierarchies once more with 16-bit child references
-            if (!compact_refs(b.own_tree.wnodes, b.own_tree.root_ref, b.own_wnodes16, b.own_root16) ||
-                !compact_refs(b.wnodes, b.root_ref, b.ref_wnodes16, b.ref_root16)) { b.own_wnodes16.clear(); b.ref_wnodes16.clear(); }
-        }
-        if (b.own && !b.own_gpu) {
-            float qo[3], qs[3];
-            if (pt_quantize_nodes(b.own_tree.wnodes, b.own_qnodes, qo, qs, PT_QCACHE_NODES, b.q_top))
-                for (int k = 0; k < 3; k++) { b.q_origin[k] = qo[k]; b.q_scale[k] = qs[k]; }
-            else b.own_qnodes.clear();
-            if (!b.own_qnodes.empty() && !b.own_wnodes16.empty()) {     // (the quantised nodes are renumbered: node 0 stays the root)
-                b.own_qnodes16 = b.own_qnodes;
-                for (uint4 &q : b.own_qnodes16) if (!compact_ref(q.w, q.w)) { b.own_qnodes16.clear(); break; }
-            }
-        } else if (!b.own) {
-            b.leafbox.clear();
-        }
+        PtOwnTreeGpu g;
+        PtOwnTree t;
+        const bool on_device = opt.tree_builder == 2u && stream && nt > 4096u && which.size() > 2048u &&
+                               own_tree_on_device(stream, device, tris, nt, which, k_max, limit, b, g);
+        own = on_device || pt_build_own_tree(tris, which, k_max, limit, t);
+        if (own) own_image(b, on_device, device, g, t, nt, wnodes, std::move(leafbox));
         b.tree_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
-    if (nested && leaves.size() >= 2 && !c->opt.keep_reference_tree && !b.own) {
+    std::vector<float4> fast;                   // a hierarchy rebuilt over the reference's leaves
+    if (nested && leaves.size() >= 2 && !opt.keep_reference_tree && !own) {
         const auto t0 = std::chrono::steady_clock::now();
         // tree_builder = 2: on the device (gpu_tree.hip); the host builder when that is not wanted, not possible (ptmi_debug_image_stats
         // has no device) or refused
-        bool built = false;
-        if (c->opt.tree_builder == 2u && c->stream) built = pt_build_fast_tree_gpu(leaves, b.fast_wnodes, b.fast_root, b.fast_depth, c->stream);
-        b.gpu_tree = built;
-        if (!built) pt_build_fast_tree(leaves, b.fast_wnodes, b.fast_root, b.fast_depth);
+        uint32_t root = PT_REF_NONE, fast_depth = 0;
+        const bool on_device = opt.tree_builder == 2u && stream && pt_build_fast_tree_gpu(leaves, fast, root, fast_depth, stream);
+        if (!on_device) pt_build_fast_tree(leaves, fast, root, fast_depth);
+        h.n_wnodes = (uint32_t)(fast.size() / 4); h.root_ref = root; h.depth = fast_depth;
+        b.tree_builder_used = on_device ? 2u : 1u;
         b.tree_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     // triangle images: v0, e1 = v1 - v0, e2 = v2 - v0 (pt.wgsl:128-129; one IEEE subtraction each)
-    b.tripos.resize((size_t)nt * 3);
+    std::vector<float4> tripos((size_t)nt * 3);
     for (uint32_t i = 0; i < nt; i++) {
         const ptmi_triangle &t = tris[i];
-        b.tripos[3 * (size_t)i + 0] = make_float4(t.v0[0], t.v0[1], t.v0[2], 0.0f);
-        b.tripos[3 * (size_t)i + 1] = make_float4(t.v1[0] - t.v0[0], t.v1[1] - t.v0[1], t.v1[2] - t.v0[2], 0.0f);
-        b.tripos[3 * (size_t)i + 2] = make_float4(t.v2[0] - t.v0[0], t.v2[1] - t.v0[1], t.v2[2] - t.v0[2], 0.0f);
+        tripos[3 * (size_t)i + 0] = make_float4(t.v0[0], t.v0[1], t.v0[2], 0.0f);
+        tripos[3 * (size_t)i + 1] = make_float4(t.v1[0] - t.v0[0], t.v1[1] - t.v0[1], t.v1[2] - t.v0[2], 0.0f);
+        tripos[3 * (size_t)i + 2] = make_float4(t.v2[0] - t.v0[0], t.v2[1] - t.v0[1], t.v2[2] - t.v0[2], 0.0f);
     }
     {   // longest edge squared, in double; NaN / inf edges give 0 (no ray is "bounded" then)
         double emax2 = 0.0; bool finite = true;
-        for (size_t k = 0; k < b.tripos.size(); k++) {
+        for (size_t k = 0; k < tripos.size(); k++) {
             if (k % 3 == 0) continue;
-            const float4 &e = b.tripos[k];
+            const float4 &e = tripos[k];
             const double l2 = (double)e.x * e.x + (double)e.y * e.y + (double)e.z * e.z;
             if (!(l2 <= 1.7e308)) finite = false; else if (l2 > emax2) emax2 = l2;
         }
@@ -510,20 +529,29 @@ int build_image(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt, const ptmi_
     }
     {
         const auto t0 = std::chrono::steady_clock::now();
-        if (!b.fast_wnodes.empty() && !pt_quantize_tree(leaves, b.fast_wnodes, b.tripos, b.qnodes, b.leaf_stream, b.q_origin, b.q_scale,
-                                                         PT_QCACHE_NODES, b.q_top)) {
-            b.qnodes.clear(); b.leaf_stream.clear();
+        std::vector<uint4> q;
+        std::vector<uint32_t> leaf_stream;
+        if (!fast.empty() && pt_quantize_tree(leaves, fast, tripos, q, leaf_stream, h.q_origin, h.q_scale, PT_QCACHE_NODES, b.q_top)) {
+            h.quantised = 1u;
+            b.hold(kQnodes, std::move(q)); b.hold(kLeafStream, std::move(leaf_stream));
         }
         b.tree_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
+    if (!fast.empty()) b.hold(kWnodes, std::move(fast));
+    b.hold(kRefWnodes, std::move(wnodes)); b.hold(kRefTripos, std::move(tripos));
     return PTMI_OK;
 }
+
+// bytes of the walked image in LDS (nodes and triangle images)
+size_t lds_scene_bytes(const ptmi_ctx *c) { return (size_t)c->img.n_wnodes * 64 + (size_t)c->img.n_tris * 48; }
+// ptmi_stats.bvh_depth: levels of the uploaded tree, or of the hierarchy rebuilt over its leaves where that is deeper
+uint32_t stats_depth(const ptmi_ctx *c) { return c->img.leaves_used == 2u ? c->img.ref_depth : std::max(c->img.depth, c->img.ref_depth); }
 
 // Sizes `variant` (pt_variant) on the uploaded scene with `wgs` workgroups per CU: the per-lane stack, whether it spills, the LDS it
 // launches with. False: it does not fit, or the scene has no image in its node format.
 bool size_variant(const ptmi_ctx *c, int variant, int wgs, TraverseConfig &cfg) {
     const PtVariant &r = pt_variant(variant);
-    const uint32_t depth = c->sc.own ? std::max(c->own_depth, c->bvh_depth) : c->bvh_depth;   // slow rays walk the uploaded tree on the same stacks
+    const uint32_t depth = std::max(c->img.depth, c->img.ref_depth);    // slow rays walk the uploaded tree on the same stacks
     int entries = 0;
     bool ok = true;
     switch (r.stack) {
@@ -541,7 +569,7 @@ bool size_variant(const ptmi_ctx *c, int variant, int wgs, TraverseConfig &cfg) 
         break;
     }
     }
-    ok = ok && (!pt_quantised(r) || c->own_quant) && (r.nodes != PT_NODES_EXACT16 || c->sc.wnodes16 != nullptr);
+    ok = ok && (!pt_quantised(r) || (c->sc.own && c->img.quantised)) && (r.nodes != PT_NODES_EXACT16 || c->sc.wnodes16 != nullptr);
     cfg.variant = variant; cfg.wgs_per_cu = wgs; cfg.stack_entries = entries;
     cfg.wants_spill = pt_spills(r, wgs) ? 1 : 0;
     cfg.quantized = pt_quantised(r) ? 1 : 0;
@@ -553,7 +581,7 @@ bool size_variant(const ptmi_ctx *c, int variant, int wgs, TraverseConfig &cfg) 
 // PTMI_OWN_SHADOW (a code as ptmi_stats reports it, pt_variant_code: 102 = PT_VARIANT_OWN_LDS16_NODES, two workgroups per CU) override
 // the choice of the own-leaf variants where it fits — for same-box A/Bs, not for users.
 TraverseConfig traverse_config(const ptmi_ctx *c, bool closest_hit) {
-    const bool own = c->sc.own, big = c->lds_scene_bytes > ((size_t)4 << 20);       // big: beyond an XCD's L2
+    const bool own = c->sc.own, big = lds_scene_bytes(c) > ((size_t)4 << 20);       // big: beyond an XCD's L2
     const int traversal = c->opt.traversal;
     TraverseConfig cfg{};
     cfg.cull = c->opt.cull ? 1 : 0;
@@ -564,7 +592,7 @@ TraverseConfig traverse_config(const ptmi_ctx *c, bool closest_hit) {
     const bool mem_quant = traversal == PTMI_TRAVERSAL_GLOBAL || (traversal == PTMI_TRAVERSAL_AUTO && big);
     auto from_memory = [&]() {
         if (!own) { pick(PT_VARIANT_GLOBAL, 1); cfg.quantized = mem_quant; cfg.wgs_per_cu = 2; }  // (2: the code leaves = 1 has always reported)
-        else pick(c->own_quant && mem_quant ? PT_VARIANT_OWN_QGLOBAL : PT_VARIANT_OWN_GLOBAL, 1);
+        else pick(c->img.quantised && mem_quant ? PT_VARIANT_OWN_QGLOBAL : PT_VARIANT_OWN_GLOBAL, 1);
         return cfg;
     };
     if (traversal == PTMI_TRAVERSAL_GLOBAL || traversal == PTMI_TRAVERSAL_GLOBAL_EXACT) return from_memory();
@@ -723,9 +751,8 @@ int ptmi_destroy(ptmi_ctx *c) {
         for (hipEvent_t e : {ln.ev_ready, ln.ev_shadow[0], ln.ev_shadow[1]}) if (e) (void)hipEventDestroy(e);
         if (ln.side) (void)hipStreamDestroy(ln.side);
     }
-    dfree(c->d_tris); dfree(c->d_mats); dfree(c->d_lights); dfree(c->d_atlas); dfree(c->d_wnodes); dfree(c->d_tripos);
-    dfree(c->d_fast_wnodes); dfree(c->d_qnodes); dfree(c->d_leaf_stream); dfree(c->d_own_tripos); dfree(c->d_leafbox); dfree(c->d_wnodes16); dfree(c->d_ref_wnodes16);
-    dfree(c->d_qnodes16);
+    for (void *&p : c->buf) dfree(p);
+    dfree(c->d_atlas);
     dfree(c->d_out_own); dfree(c->d_stats); dfree(c->d_scene); dfree(c->d_blit_f32); dfree(c->d_blit_u8);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -737,11 +764,9 @@ int ptmi_destroy(ptmi_ctx *c) {
 // A scene prepared on the host (validation + traversal image: everything of an upload that does not depend on the device), and the
 // caller's blobs it was made from. ptmi_upload_scene = prepare + install; ptmi_multi_upload_scene prepares ONCE and installs on N devices.
 struct PtPrepared {
-    Built b;
-    const ptmi_triangle *tris; uint32_t nt; const ptmi_material *mats; uint32_t nm;
-    const ptmi_light *lights; uint32_t nl;
+    Built b;                                 // the triangles, materials and lights included
+    uint32_t nt, nm, nl;
     double build_ms;
-    ptmi_options opt;                        // what it was built under (leaves, leaf_tris, keep_reference_tree, tree_builder)
     bool take_device_buffers = false;        // the one install may take b's device buffers instead of copying them (single device)
 };
 
@@ -760,11 +785,13 @@ PtPrepared *pt_prepare_scene(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt
     }
     const auto t_start = std::chrono::steady_clock::now();
     PtPrepared *p = new PtPrepared();
-    int rc = build_image(c, tris, nt, nodes, nn, p->b);
+    int rc = build_image(c->opt, c->stream, c->device, tris, nt, nodes, nn, p->b, c->err);
     if (rc) { delete p; return bad(rc); }
-    p->tris = tris; p->nt = nt; p->mats = mats; p->nm = nm; p->lights = lights; p->nl = nl;
+    if (!p->b.buf[kTris].present) p->b.view(kTris, tris, (size_t)nt * sizeof(ptmi_triangle));     // (else the device copy)
+    p->b.view(kMats, mats, (size_t)nm * sizeof(ptmi_material));
+    p->b.view(kLights, lights, (size_t)nl * sizeof(ptmi_light));
+    p->nt = nt; p->nm = nm; p->nl = nl;
     p->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-    p->opt = c->opt;
     *rc_out = PTMI_OK;
     return p;
 }
@@ -777,106 +804,63 @@ int pt_install_scene(ptmi_ctx *c, PtPrepared *prep) {
     auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
     const auto t_start = clk::now();
     Built &b = prep->b;
-    const ptmi_triangle *tris = prep->tris; const uint32_t nt = prep->nt;
-    const ptmi_material *mats = prep->mats; const uint32_t nm = prep->nm;
-    const ptmi_light *lights = prep->lights; const uint32_t nl = prep->nl;
-    // Allocate and fill the new buffers first; the context keeps its previous scene until all of them exist.
+    // Allocate and fill the new buffers first; the context keeps its previous scene until all of them exist. An empty buffer gets 16
+    // zeroed bytes. Buffers the preparation made on a device are taken over (the one install on that device) or copied.
     const auto t_copy = clk::now();
-    void *n_tris = nullptr, *n_mats = nullptr, *n_lights = nullptr;
-    float4 *n_wnodes = nullptr, *n_tripos = nullptr, *n_fast = nullptr, *n_own_tripos = nullptr, *n_leafbox = nullptr;
-    float4 *n_w16 = nullptr, *n_r16 = nullptr;
-    const bool has16 = b.own && !b.own_wnodes16.empty();
-    uint4 *n_qnodes = nullptr, *n_q16 = nullptr; uint32_t *n_stream = nullptr;
-    const bool own = b.own, dev = b.own_gpu;
-    const bool hasq16 = has16 && !b.own_qnodes16.empty();
-    const std::vector<uint4> &qn = own ? b.own_qnodes : b.qnodes;
-    const bool quant = b.quantised();
-    auto up = [&](void **dst, const void *src, size_t bytes) -> hipError_t {
-        if (bytes == 0) { hipError_t e = hipMalloc(dst, 16); if (e != hipSuccess) return e; return hipMemset(*dst, 0, 16); }
-        hipError_t e = hipMalloc(dst, bytes); if (e != hipSuccess) return e;
-        return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-    };
-    // buffers the preparation made on a device: taken over (one install on that device), or copied device to device
-    const bool take = prep->take_device_buffers && b.dev_device == c->device;
-    auto from_dev = [&](void **dst, void *src, size_t bytes, auto &&release) -> hipError_t {
-        if (take) { *dst = src; release(); return hipSuccess; }
-        hipError_t e = hipMalloc(dst, bytes ? bytes : 16); if (e != hipSuccess) return e;
-        return b.dev_device == c->device ? hipMemcpy(*dst, src, bytes, hipMemcpyDeviceToDevice)
-                                         : hipMemcpyPeer(*dst, c->device, src, b.dev_device, bytes);
-    };
-    // n_fast: the hierarchy the regular rays walk when it is not the uploaded one — rebuilt over the reference's leaves, or the own tree
-    const std::vector<float4> &walk = own ? b.own_tree.wnodes : b.fast_wnodes;
-    const bool fast = own || !b.fast_wnodes.empty();
-    hipError_t e = b.d_tris ? from_dev(&n_tris, b.d_tris, (size_t)nt * sizeof(ptmi_triangle), [&] { b.d_tris = nullptr; })
-                            : up(&n_tris, tris, (size_t)nt * sizeof(ptmi_triangle));
-    if (e == hipSuccess) e = up(&n_mats, mats, (size_t)nm * sizeof(ptmi_material));
-    if (e == hipSuccess) e = up(&n_lights, lights, (size_t)nl * sizeof(ptmi_light));
-    if (e == hipSuccess) e = up(reinterpret_cast<void **>(&n_wnodes), b.wnodes.data(), b.wnodes.size() * 16);
-    if (e == hipSuccess) e = up(reinterpret_cast<void **>(&n_tripos), b.tripos.data(), b.tripos.size() * 16);
-    const size_t walk_nodes = b.walk_nodes(), walk_tris = b.walk_tris();
-    if (dev) {
-        if (e == hipSuccess) e = from_dev(reinterpret_cast<void **>(&n_fast), b.own_dev.wnodes, walk_nodes * 64, [&] { b.own_dev.wnodes = nullptr; });
-        if (e == hipSuccess) e = from_dev(reinterpret_cast<void **>(&n_own_tripos), b.own_dev.tripos, walk_tris * 48, [&] { b.own_dev.tripos = nullptr; });
-        if (e == hipSuccess && quant) e = from_dev(reinterpret_cast<void **>(&n_qnodes), b.own_dev.qnodes, walk_nodes * 32, [&] { b.own_dev.qnodes = nullptr; });
+    void *n[kSceneBufs] = {};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < kSceneBufs && e == hipSuccess; k++) {
+        HeldBuf &h = b.buf[k];
+        if (!h.present) continue;
+        if (h.dev && prep->take_device_buffers && h.device == c->device) { n[k] = h.dev; h.dev = nullptr; continue; }
+        e = hipMalloc(&n[k], h.bytes ? h.bytes : 16);
+        if (e != hipSuccess) break;
+        if (h.dev) e = h.device == c->device ? hipMemcpy(n[k], h.dev, h.bytes, hipMemcpyDeviceToDevice)
+                                             : hipMemcpyPeer(n[k], c->device, h.dev, h.device, h.bytes);
+        else e = h.bytes ? hipMemcpy(n[k], h.host, h.bytes, hipMemcpyHostToDevice) : hipMemset(n[k], 0, 16);
     }
-    if (e == hipSuccess && fast && !dev) e = up(reinterpret_cast<void **>(&n_fast), walk.data(), walk.size() * 16);
-    if (e == hipSuccess && own && !dev) e = up(reinterpret_cast<void **>(&n_own_tripos), b.own_tree.tripos.data(), b.own_tree.tripos.size() * 16);
-    if (e == hipSuccess && own) e = up(reinterpret_cast<void **>(&n_leafbox), b.leafbox.data(), b.leafbox.size() * 16);
-    if (e == hipSuccess && has16) e = up(reinterpret_cast<void **>(&n_w16), b.own_wnodes16.data(), b.own_wnodes16.size() * 16);
-    if (e == hipSuccess && has16) e = up(reinterpret_cast<void **>(&n_r16), b.ref_wnodes16.data(), b.ref_wnodes16.size() * 16);
-    if (e == hipSuccess && quant && !dev) e = up(reinterpret_cast<void **>(&n_qnodes), qn.data(), qn.size() * 16);
-    if (e == hipSuccess && hasq16) e = up(reinterpret_cast<void **>(&n_q16), b.own_qnodes16.data(), b.own_qnodes16.size() * 16);
-    if (e == hipSuccess && quant && !own) e = up(reinterpret_cast<void **>(&n_stream), b.leaf_stream.data(), b.leaf_stream.size() * 4);
     if (e != hipSuccess) {
-        dfree(n_tris); dfree(n_mats); dfree(n_lights); dfree(n_wnodes); dfree(n_tripos); dfree(n_fast); dfree(n_qnodes); dfree(n_stream);
-        dfree(n_own_tripos); dfree(n_leafbox); dfree(n_w16); dfree(n_r16); dfree(n_q16);
+        for (void *&p : n) dfree(p);
         return fail(c, PTMI_E_HIP, "scene upload failed: %s (the previous scene, if any, is still in place)", hipGetErrorString(e));
     }
     HIP_TRY(c, sync_all(c));                  // nothing in flight reads the old buffers any more
-    dfree(c->d_tris); dfree(c->d_mats); dfree(c->d_lights); dfree(c->d_wnodes); dfree(c->d_tripos); dfree(c->d_fast_wnodes);
-    dfree(c->d_qnodes); dfree(c->d_leaf_stream); dfree(c->d_own_tripos); dfree(c->d_leafbox); dfree(c->d_wnodes16); dfree(c->d_ref_wnodes16);
-    c->d_wnodes16 = n_w16; c->d_ref_wnodes16 = n_r16;
-    dfree(c->d_qnodes16); c->d_qnodes16 = n_q16;
-    c->d_qnodes = n_qnodes; c->d_leaf_stream = n_stream;
-    c->d_tris = n_tris; c->d_mats = n_mats; c->d_lights = n_lights;
-    c->d_wnodes = n_wnodes; c->d_tripos = n_tripos; c->d_fast_wnodes = n_fast;
-    c->d_own_tripos = n_own_tripos; c->d_leafbox = n_leafbox;
+    for (int k = 0; k < kSceneBufs; k++) { dfree(c->buf[k]); c->buf[k] = n[k]; }
+    void *const *d = c->buf;
+    const ptmi_image_info &h = b.img;
+    const bool own = h.leaves_used == 2u;
     DevScene &s = c->sc;
-    s.tris = static_cast<const ptmi_triangle *>(c->d_tris); s.n_tris = nt;
-    s.mats = static_cast<const ptmi_material *>(c->d_mats); s.n_mats = nm;
-    s.lights = static_cast<const ptmi_light *>(c->d_lights); s.n_lights = nl;
-    s.ref_wnodes = c->d_wnodes; s.ref_root_ref = b.root_ref; s.has_fast = fast ? 1u : 0u;
-    s.wnodes = fast ? c->d_fast_wnodes : c->d_wnodes;
-    s.n_wnodes = (uint32_t)(fast ? walk_nodes : b.wnodes.size() / 4);
-    s.tripos = own ? c->d_own_tripos : c->d_tripos;
-    s.ref_tripos = c->d_tripos;
-    s.qnodes = c->d_qnodes; s.leaf_stream = c->d_leaf_stream;
-    for (int k = 0; k < 3; k++) { s.q_origin[k] = b.q_origin[k]; s.q_scale[k] = b.q_scale[k]; }
+    s.tris = static_cast<const ptmi_triangle *>(d[kTris]); s.n_tris = prep->nt;
+    s.mats = static_cast<const ptmi_material *>(d[kMats]); s.n_mats = prep->nm;
+    s.lights = static_cast<const ptmi_light *>(d[kLights]); s.n_lights = prep->nl;
+    s.ref_wnodes = static_cast<const float4 *>(d[kRefWnodes]); s.ref_root_ref = b.ref_root_ref; s.has_fast = d[kWnodes] ? 1u : 0u;
+    s.wnodes = static_cast<const float4 *>(walked(d, kWnodes));
+    s.n_wnodes = h.n_wnodes;
+    s.tripos = static_cast<const float4 *>(walked(d, kTripos));
+    s.ref_tripos = static_cast<const float4 *>(d[kRefTripos]);
+    s.qnodes = static_cast<const uint4 *>(d[kQnodes]); s.leaf_stream = static_cast<const uint32_t *>(d[kLeafStream]);
+    for (int k = 0; k < 3; k++) { s.q_origin[k] = h.q_origin[k]; s.q_scale[k] = h.q_scale[k]; }
     s.q_cached = b.q_top;
     s.tri_safe_dsum = b.tri_safe_dsum;
     for (int k = 0; k < 3; k++) {
-        s.ref_root_min[k] = b.root_min[k]; s.ref_root_max[k] = b.root_max[k];
-        s.root_min[k] = own ? b.own_tree.root_min[k] : b.root_min[k]; s.root_max[k] = own ? b.own_tree.root_max[k] : b.root_max[k];
+        s.ref_root_min[k] = b.ref_root_min[k]; s.ref_root_max[k] = b.ref_root_max[k];
+        s.root_min[k] = h.root_min[k]; s.root_max[k] = h.root_max[k];
     }
-    s.root_ref = own ? b.own_tree.root_ref : fast ? b.fast_root : b.root_ref;
+    s.root_ref = h.root_ref;
     s.own = own ? 1u : 0u;
-    s.n_own_tris = own ? (uint32_t)walk_tris : 0u;
-    s.tri_leafbox = c->d_leafbox;
-    s.wnodes16 = c->d_wnodes16; s.ref_wnodes16 = c->d_ref_wnodes16; s.qnodes16 = c->d_qnodes16;
-    s.root_ref16 = has16 ? b.own_root16 : PT_REF_NONE; s.ref_root_ref16 = has16 ? b.ref_root16 : PT_REF_NONE;
-    s.safe_origin = own ? b.own_tree.safe_origin : 0.0f;
+    s.n_own_tris = own ? h.n_tris : 0u;
+    s.tri_leafbox = static_cast<const float4 *>(d[kLeafbox]);
+    s.wnodes16 = static_cast<const float4 *>(d[kWnodes16]); s.ref_wnodes16 = static_cast<const float4 *>(d[kRefWnodes16]);
+    s.qnodes16 = static_cast<const uint4 *>(d[kQnodes16]);
+    s.root_ref16 = b.root_ref16; s.ref_root_ref16 = b.ref_root_ref16;
+    s.safe_origin = h.safe_origin;
     s.verify_stat = c->d_stats + 4;
     s.self = c->d_scene;
     HIP_TRY(c, hipMemcpy(c->d_scene, &c->sc, sizeof(DevScene), hipMemcpyHostToDevice));
-    c->bvh_depth = std::max(b.depth, b.fast_depth);           // stacks must hold either tree (irregular rays use the uploaded one)
-    c->own_depth = own ? b.own_tree.depth : 0u;
-    c->own_quant = own && quant;
-    c->lds_scene_bytes = (size_t)s.n_wnodes * 64 + walk_tris * 48;
+    c->img = h;
     c->have_scene = true;
-    c->st.leaves_used = own ? 2u : 1u;
-    c->st.leaf_tris_used = own ? b.own_tree.max_leaf_tris : b.max_leaf_tris;
-    c->st.tree_builder_used = b.builder_used();
-    b.info(&c->img);
+    c->st.leaves_used = h.leaves_used;
+    c->st.leaf_tris_used = h.max_leaf_tris;
+    c->st.tree_builder_used = b.tree_builder_used;
     c->st.upload_copy_ms = ms_since(t_copy);
     c->st.upload_tree_ms = b.tree_ms;
     c->st.upload_ms = prep->build_ms + ms_since(t_start);
@@ -1023,7 +1007,7 @@ int ptmi_dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames) {
     if (npix * F > 0xFFFFFF00ull) return fail(c, PTMI_E_UNSUPPORTED, "batch of %llu paths exceeds 2^32", (unsigned long long)(npix * F));
     const TraverseConfig cfg0 = traverse_config(c, true), cfg_shadow0 = traverse_config(c, false);
     if (c->opt.traversal == PTMI_TRAVERSAL_LDS && pt_variant(cfg0.variant).where != PT_LDS_ALL)
-        return fail(c, PTMI_E_UNSUPPORTED, "scene needs %zu B of LDS plus the stack; it does not fit in %zu B", c->lds_scene_bytes, kLdsMax);
+        return fail(c, PTMI_E_UNSUPPORTED, "scene needs %zu B of LDS plus the stack; it does not fit in %zu B", lds_scene_bytes(c), kLdsMax);
     for (;;) {
         rc = ensure_capacity(c, ln, (size_t)(npix * F));
         if (rc == PTMI_OK) break;
@@ -1208,7 +1192,7 @@ int ptmi_get_stats(ptmi_ctx *c, ptmi_stats *out) {
     c->st.segments = h[0]; c->st.shadow_rays = h[1] - h[3]; c->st.shadow_traced = h[2] - h[3];      // h[3]: records of emissive hits
     for (int i = 0; i < 64; i++) c->st.segments_by_bounce[i] = h[8 + i];
     c->st.verify_failed = h[4];
-    c->st.bvh_depth = c->bvh_depth;
+    c->st.bvh_depth = stats_depth(c);
     *out = c->st;
     return PTMI_OK;
 }
@@ -1221,7 +1205,7 @@ int ptmi_reset_stats(ptmi_ctx *c) {
     HIP_TRY(c, hipMemset(c->d_stats, 0, kStatsWords * sizeof(unsigned long long)));
     const ptmi_stats old = c->st;
     std::memset(&c->st, 0, sizeof c->st);
-    c->st.bvh_depth = c->bvh_depth;
+    c->st.bvh_depth = stats_depth(c);
     c->st.upload_ms = old.upload_ms; c->st.upload_tree_ms = old.upload_tree_ms; c->st.upload_copy_ms = old.upload_copy_ms;
     c->st.leaves_used = old.leaves_used; c->st.leaf_tris_used = old.leaf_tris_used; c->st.tree_builder_used = old.tree_builder_used;
     return PTMI_OK;
@@ -1320,15 +1304,19 @@ int ptmi_debug_occluded(ptmi_ctx *c, uint32_t n, const float *o3, const float *d
 int ptmi_debug_image_stats(const ptmi_triangle *tris, uint32_t nt, const ptmi_bvh_node *nodes, uint32_t nn, double out[8]) {
     if (!out || (nt && !tris) || (nn && !nodes)) return PTMI_E_INVALID;
     for (int i = 0; i < 8; i++) out[i] = 0.0;
-    ptmi_ctx tmp;                                   // host-only: never touches a device
-    default_options(tmp.opt);
-    tmp.opt.leaves = 1;                             // the image over the reference's leaves (ptmi_debug_build_image: the own one)
+    ptmi_options opt;
+    default_options(opt);
+    opt.leaves = 1;                                 // the image over the reference's leaves (ptmi_debug_build_image: the own one)
     Built b;
-    int rc = build_image(&tmp, tris, nt, nodes, nn, b);
-    if (rc) { g_create_err = tmp.err; return rc; }
-    out[0] = (double)(b.fast_wnodes.size() / 4); out[2] = (double)b.fast_depth;
-    out[3] = (double)(b.qnodes.size() / 2); out[4] = (double)b.leaf_stream.size();
-    if (b.qnodes.empty()) return PTMI_OK;
+    int rc = build_image(opt, nullptr, -1, tris, nt, nodes, nn, b, g_create_err);     // host-only: never touches a device
+    if (rc) return rc;
+    const std::vector<float4> &fast_wnodes = b.vec<float4>(kWnodes), &tripos = b.vec<float4>(kRefTripos);
+    const std::vector<uint4> &qnodes = b.vec<uint4>(kQnodes);
+    const std::vector<uint32_t> &leaf_stream = b.vec<uint32_t>(kLeafStream);
+    const float *q_origin = b.img.q_origin, *q_scale = b.img.q_scale;
+    out[0] = (double)(fast_wnodes.size() / 4); out[2] = fast_wnodes.empty() ? 0.0 : (double)b.img.depth;
+    out[3] = (double)(qnodes.size() / 2); out[4] = (double)leaf_stream.size();
+    if (qnodes.empty()) return PTMI_OK;
     // every quantised child box, decoded with the kernel's own fmaf, must contain the exact child box it stands for
     double viol = 0.0, infl = 0.0; size_t boxes = 0, leaves = 0, bad_hdr = 0;
     auto area = [](const float *lo, const float *hi) {
@@ -1342,19 +1330,19 @@ int ptmi_debug_image_stats(const ptmi_triangle *tris, uint32_t nt, const ptmi_bv
     while (!todo.empty()) {
         const uint32_t i = todo.back().first, qi = todo.back().second;
         todo.pop_back();
-        if ((size_t)qi * 2 + 1 >= b.qnodes.size() || (size_t)i * 4 + 3 >= b.fast_wnodes.size()) { bad_hdr++; continue; }
+        if ((size_t)qi * 2 + 1 >= qnodes.size() || (size_t)i * 4 + 3 >= fast_wnodes.size()) { bad_hdr++; continue; }
         visited++;
-        const float4 *w = &b.fast_wnodes[(size_t)i * 4];
+        const float4 *w = &fast_wnodes[(size_t)i * 4];
         const float lo[2][3] = {{w[0].x, w[0].y, w[0].z}, {w[1].z, w[1].w, w[2].x}};
         const float hi[2][3] = {{w[0].w, w[1].x, w[1].y}, {w[2].y, w[2].z, w[2].w}};
         uint32_t refs[2]; std::memcpy(&refs[0], &w[3].x, 4); std::memcpy(&refs[1], &w[3].y, 4);
         for (int ch = 0; ch < 2; ch++) {
-            const uint4 q = b.qnodes[(size_t)qi * 2 + ch];
+            const uint4 q = qnodes[(size_t)qi * 2 + ch];
             const uint32_t pl[6] = {q.x & 0xFFFFu, q.x >> 16, q.y & 0xFFFFu, q.y >> 16, q.z & 0xFFFFu, q.z >> 16};   // lo.xyz, hi.xyz
             float dlo[3], dhi[3];
             for (int k = 0; k < 3; k++) {
-                dlo[k] = std::fmaf(b.q_scale[k], (float)pl[k], b.q_origin[k]);
-                dhi[k] = std::fmaf(b.q_scale[k], (float)pl[3 + k], b.q_origin[k]);
+                dlo[k] = std::fmaf(q_scale[k], (float)pl[k], q_origin[k]);
+                dhi[k] = std::fmaf(q_scale[k], (float)pl[3 + k], q_origin[k]);
                 if (!(dlo[k] <= lo[ch][k]) || !(dhi[k] >= hi[ch][k])) viol += 1.0;
             }
             const double a0 = area(lo[ch], hi[ch]);
@@ -1362,14 +1350,14 @@ int ptmi_debug_image_stats(const ptmi_triangle *tris, uint32_t nt, const ptmi_bv
             if (refs[ch] & PT_REF_LEAF) {
                 leaves++;
                 if (!(q.w & PT_REF_LEAF)) { bad_hdr++; continue; }
-                const uint32_t *h = &b.leaf_stream[q.w & ~PT_REF_LEAF];
+                const uint32_t *h = &leaf_stream[q.w & ~PT_REF_LEAF];
                 float hl[3], hh[3]; std::memcpy(hl, h, 12); std::memcpy(hh, h + 4, 12);
                 const uint32_t first = refs[ch] & PT_LEAF_OFF_MASK, cnt = ((refs[ch] >> PT_LEAF_OFF_BITS) & (PT_LEAF_MAX_TRIS - 1u)) + 1u;
                 bool ok = h[3] == first && h[7] == cnt;
                 for (int k = 0; k < 3; k++) ok = ok && hl[k] == lo[ch][k] && hh[k] == hi[ch][k];
                 for (uint32_t t = 0; t < cnt && ok; t++)
                     for (int j = 0; j < 3; j++) {
-                        const float4 &v = b.tripos[3 * (size_t)(first + t) + j];
+                        const float4 &v = tripos[3 * (size_t)(first + t) + j];
                         float g[3]; std::memcpy(g, h + 8 + 9 * t + 3 * j, 12);
                         ok = ok && std::memcmp(&g[0], &v.x, 4) == 0 && std::memcmp(&g[1], &v.y, 4) == 0 && std::memcmp(&g[2], &v.z, 4) == 0;
                     }
@@ -1377,8 +1365,8 @@ int ptmi_debug_image_stats(const ptmi_triangle *tris, uint32_t nt, const ptmi_bv
             } else if (q.w & PT_REF_LEAF) bad_hdr++;
             else {
                 // an inner box is the exact union of its two children's boxes (what makes any topology equivalent, §3.2)
-                if ((size_t)refs[ch] * 4 + 3 < b.fast_wnodes.size()) {
-                    const float4 *cw = &b.fast_wnodes[(size_t)refs[ch] * 4];
+                if ((size_t)refs[ch] * 4 + 3 < fast_wnodes.size()) {
+                    const float4 *cw = &fast_wnodes[(size_t)refs[ch] * 4];
                     const float clo[3] = {std::min(cw[0].x, cw[1].z), std::min(cw[0].y, cw[1].w), std::min(cw[0].z, cw[2].x)};
                     const float chi[3] = {std::max(cw[0].w, cw[2].y), std::max(cw[1].x, cw[2].z), std::max(cw[1].y, cw[2].w)};
                     for (int k = 0; k < 3; k++) if (clo[k] != lo[ch][k] || chi[k] != hi[ch][k]) { bad_hdr++; break; }
@@ -1387,7 +1375,7 @@ int ptmi_debug_image_stats(const ptmi_triangle *tris, uint32_t nt, const ptmi_bv
             }
         }
     }
-    if (visited != b.qnodes.size() / 2) bad_hdr++;          // every node reached exactly once (a tree: no node can be reached twice)
+    if (visited != qnodes.size() / 2) bad_hdr++;          // every node reached exactly once (a tree: no node can be reached twice)
     out[1] = (double)leaves; out[5] = viol; out[6] = boxes ? infl / (double)boxes : 0.0; out[7] = (double)bad_hdr;
     return PTMI_OK;
 }
@@ -1396,21 +1384,16 @@ int ptmi_debug_build_image(const ptmi_triangle *tris, uint32_t nt, const ptmi_bv
                            ptmi_image_info *info, float *wnodes16, uint32_t *qnodes8, float *tripos12, float *leafbox8) {
     if (!info || (nt && !tris) || (nn && !nodes)) return PTMI_E_INVALID;
     std::memset(info, 0, sizeof *info);
-    ptmi_ctx tmp;                                   // host-only: never touches a device
-    default_options(tmp.opt);
-    if (opt) { tmp.opt.leaves = opt->leaves; tmp.opt.leaf_tris = opt->leaf_tris; tmp.opt.keep_reference_tree = opt->keep_reference_tree; }
+    ptmi_options o;
+    default_options(o);
+    if (opt) { o.leaves = opt->leaves; o.leaf_tris = opt->leaf_tris; o.keep_reference_tree = opt->keep_reference_tree; }
     Built b;
-    int rc = build_image(&tmp, tris, nt, nodes, nn, b);
-    if (rc) { g_create_err = tmp.err; return rc; }
-    const bool own = b.own;
-    const std::vector<float4> &walk = b.walk();
-    const std::vector<float4> &tp = own ? b.own_tree.tripos : b.tripos;
-    const std::vector<uint4> &qn = own ? b.own_qnodes : b.qnodes;
-    b.info(info);
-    if (wnodes16 && !walk.empty()) std::memcpy(wnodes16, walk.data(), walk.size() * 16);
-    if (qnodes8 && !qn.empty()) std::memcpy(qnodes8, qn.data(), qn.size() * 16);
-    if (tripos12 && !tp.empty()) std::memcpy(tripos12, tp.data(), tp.size() * 16);
-    if (leafbox8 && !b.leafbox.empty()) std::memcpy(leafbox8, b.leafbox.data(), b.leafbox.size() * 16);
+    int rc = build_image(o, nullptr, -1, tris, nt, nodes, nn, b, g_create_err);       // host-only: never touches a device
+    if (rc) return rc;
+    *info = b.img;
+    const struct { const HeldBuf &from; void *to; } out[] = {
+        {walked(b.buf, kWnodes), wnodes16}, {b.buf[kQnodes], qnodes8}, {walked(b.buf, kTripos), tripos12}, {b.buf[kLeafbox], leafbox8}};
+    for (const auto &x : out) if (x.to && x.from.bytes) std::memcpy(x.to, x.from.host, x.from.bytes);
     return PTMI_OK;
 }
 
@@ -1420,11 +1403,13 @@ int ptmi_debug_read_image(ptmi_ctx *c, ptmi_image_info *info, float *wnodes16, u
     HIP_TRY(c, sync_all(c));
     *info = c->img;
     if (!c->have_scene) return PTMI_OK;
-    const DevScene &s = c->sc;
-    if (wnodes16 && info->n_wnodes) HIP_TRY(c, hipMemcpy(wnodes16, s.wnodes, (size_t)info->n_wnodes * 64, hipMemcpyDeviceToHost));
-    if (qnodes8 && info->quantised) HIP_TRY(c, hipMemcpy(qnodes8, s.qnodes, (size_t)info->n_wnodes * 32, hipMemcpyDeviceToHost));
-    if (tripos12 && info->n_tris) HIP_TRY(c, hipMemcpy(tripos12, s.tripos, (size_t)info->n_tris * 48, hipMemcpyDeviceToHost));
-    if (leafbox8 && info->leaves_used == 2 && s.n_tris) HIP_TRY(c, hipMemcpy(leafbox8, s.tri_leafbox, (size_t)s.n_tris * 32, hipMemcpyDeviceToHost));
+    void *const *d = c->buf;
+    const struct { const void *from; void *to; size_t bytes; } out[] = {
+        {walked(d, kWnodes), wnodes16, (size_t)info->n_wnodes * 64},
+        {d[kQnodes], qnodes8, info->quantised ? (size_t)info->n_wnodes * 32 : 0},
+        {walked(d, kTripos), tripos12, (size_t)info->n_tris * 48},
+        {d[kLeafbox], leafbox8, info->leaves_used == 2 ? (size_t)c->sc.n_tris * 32 : 0}};
+    for (const auto &x : out) if (x.to && x.bytes) HIP_TRY(c, hipMemcpy(x.to, x.from, x.bytes, hipMemcpyDeviceToHost));
     return PTMI_OK;
 }
 
