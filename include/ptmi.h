@@ -194,6 +194,32 @@ int ptmi_bind_output_device(ptmi_ctx *ctx, void *device_ptr, size_t bytes);
 /* Order this context's work on a caller-owned hipStream_t (NULL = the context's own). */
 int ptmi_set_stream(ptmi_ctx *ctx, void *hip_stream);
 
+/* ---- first-hit planes ("AOVs": the guides a denoiser takes, depth for compositing, ids for picking) -------------------
+ * Off by default. While a plane is on, every dispatch also folds, per pixel and in the same frame order as the output buffer, what
+ * each frame's camera ray found at its first hit. Each plane is width*height entries, index y*width+x, like the output buffer:
+ *   PTMI_AOV_ALBEDO  float4: xyz = the hit's albedo (base colour x albedo-map texel, what the BSDF sees), w = coverage (1 hit, 0 miss)
+ *   PTMI_AOV_NORMAL  float4: xyz = the hit's world-space shading normal (after the normal map; not flipped toward the viewer),
+ *                            w = t, the distance from the camera ray's origin (on the lens with depth of field), 0 on a miss
+ *   PTMI_AOV_ID      uint32 x 2: the triangle (index as uploaded) and its material_index, of the LAST frame folded in;
+ *                            0xFFFFFFFF twice on a miss. Not averaged.
+ * ALBEDO and NORMAL follow the output buffer's fold exactly, without its clamp: frame 0 overwrites, frame f > 0 mixes with weight
+ * 1 / (f + 1). A mean of unit normals is not of unit length: normalise it before use. A plane turned on after accumulation has
+ * started (frame_index > 0) mixes with zeros until the next frame-0 dispatch, as the output buffer would. The radiance is the same
+ * bits with the planes on or off. Only the rows this context renders (tile_y0 / tile_y1, tile_parts) are written; the others keep
+ * their contents. The contexts of a ptmi_multi may enable planes, but nothing gathers them: each then holds only its own strips.
+ * Cost while on: 32 bytes of device memory per path of a batch (the automatic batch size counts it) and one more pass per batch. */
+enum { PTMI_AOV_ALBEDO = 1u, PTMI_AOV_NORMAL = 2u, PTMI_AOV_ID = 4u };
+/* mask: any combination of PTMI_AOV_* (0 = none, the default; other bits PTMI_E_INVALID). A plane turned on is allocated and
+ * zero-filled, planes already on keep their contents, a plane turned off is freed. ptmi_resize re-allocates the enabled planes,
+ * zero-filled. A failed call leaves the previous mask and planes in place. Synchronises. */
+int ptmi_set_aovs(ptmi_ctx *ctx, uint32_t mask);
+int ptmi_get_aovs(const ptmi_ctx *ctx, uint32_t *mask);
+/* which: exactly one PTMI_AOV_* bit; n_bytes: width*height*16 (width*height*8 for PTMI_AOV_ID), else PTMI_E_INVALID. A plane that
+ * is off (or before ptmi_resize) gives PTMI_E_STATE. Synchronises. */
+int ptmi_read_aov(ptmi_ctx *ctx, uint32_t which, void *dst, size_t n_bytes);
+/* the plane's device address for zero-copy consumers (a denoiser on the same device); NULL when that plane is off */
+void *ptmi_aov_device_ptr(ptmi_ctx *ctx, uint32_t which);
+
 /* ---- presentation (the reference's blit pass, src/shader/blit.wgsl:43-155; renderer.ts:434-449) ---- */
 /* Tone-maps the output buffer (exposure 2^1, AgX, gamma 1/2.2) into a width*height canvas, row 0 = top.
  * dst_rgba_f32 (n_floats must be width*height*4, alpha 1) and/or dst_rgba8 (n_bytes must be width*height*4);

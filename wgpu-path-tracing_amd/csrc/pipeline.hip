@@ -210,6 +210,38 @@ __global__ __launch_bounds__(BLOCK) void k_accumulate(DevBand band, uint32_t fra
     }
 }
 
+// The first-hit planes (ptmi_set_aovs) from the records `shade` wrote at bounce 0 (rec[2p], rec[2p + 1] for path p; shade.hip):
+// albedo = (albedo.rgb, coverage) and normal = (normal.xyz, t) follow the fold of k_accumulate without its clamp; ids = (triangle,
+// its material) of the batch's last frame.
+__global__ __launch_bounds__(BLOCK) void k_accumulate_aov(DevBand band, uint32_t frame0, uint32_t n_frames, const float4 *__restrict__ rec,
+                                                          const ptmi_triangle *__restrict__ tris, uint32_t n_tris,
+                                                          float4 *__restrict__ albedo, float4 *__restrict__ normal, uint2 *__restrict__ ids) {
+    const uint32_t npix = band.rows * band.width;
+    for (uint32_t pix = blockIdx.x * BLOCK + threadIdx.x; pix < npix; pix += gridDim.x * BLOCK) {
+        const size_t oi = (size_t)band.row_of(pix / band.width) * band.width + pix % band.width;
+        float4 a = albedo ? albedo[oi] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        float4 n = normal ? normal[oi] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        uint32_t tri = 0xFFFFFFFFu;
+        for (uint32_t k = 0; k < n_frames; k++) {
+            const size_t li = (size_t)k * npix + pix;
+            const float4 ra = ld_stream(&rec[2 * li]), rn = ld_stream(&rec[2 * li + 1]);
+            tri = __float_as_uint(rn.w);
+            float4 xa = make_float4(ra.x, ra.y, ra.z, tri != 0xFFFFFFFFu ? 1.0f : 0.0f);
+            float4 xn = make_float4(rn.x, rn.y, rn.z, ra.w);
+            const uint32_t frame = frame0 + k;
+            if (frame > 0u) {
+                const float t = 1.0f / (float)(frame + 1u);
+                xa = make_float4(mix1(a.x, xa.x, t), mix1(a.y, xa.y, t), mix1(a.z, xa.z, t), mix1(a.w, xa.w, t));
+                xn = make_float4(mix1(n.x, xn.x, t), mix1(n.y, xn.y, t), mix1(n.z, xn.z, t), mix1(n.w, xn.w, t));
+            }
+            a = xa; n = xn;
+        }
+        if (albedo) albedo[oi] = a;
+        if (normal) normal[oi] = n;
+        if (ids) ids[oi] = make_uint2(tri, tri < n_tris ? tris[tri].material_index : 0xFFFFFFFFu);
+    }
+}
+
 // ---- multi-GPU gather (ptmi_multi_gather): a device's rows (DevBand: the strips part, part + parts, ...) <-> one contiguous
 // buffer of band.rows x width float4, local row l of the buffer = frame row band.row_of(l)
 __global__ __launch_bounds__(BLOCK) void k_pack_rows(DevBand band, const float4 *__restrict__ frame, float4 *__restrict__ packed) {
@@ -351,6 +383,11 @@ void pt_launch_compact(hipStream_t s, int tiles, const uint32_t *queue, const ui
 void pt_launch_accumulate(hipStream_t s, int blocks, DevBand band, uint32_t frame0, uint32_t n_frames,
                           const float *L, uint32_t l_stride, float4 *out) {
     hipLaunchKernelGGL(k_accumulate, dim3(blocks), dim3(BLOCK), 0, s, band, frame0, n_frames, L, l_stride, out);
+}
+void pt_launch_accumulate_aov(hipStream_t s, int blocks, DevBand band, uint32_t frame0, uint32_t n_frames, const float4 *rec,
+                              const ptmi_triangle *tris, uint32_t n_tris, float4 *albedo, float4 *normal, uint2 *ids) {
+    hipLaunchKernelGGL(k_accumulate_aov, dim3(blocks), dim3(BLOCK), 0, s, band, frame0, n_frames, rec, tris, n_tris, albedo, normal,
+                       ids);
 }
 void pt_launch_pack_rows(hipStream_t s, int blocks, DevBand band, const float4 *frame, float4 *packed) {
     hipLaunchKernelGGL(k_pack_rows, dim3(blocks), dim3(BLOCK), 0, s, band, frame, packed);

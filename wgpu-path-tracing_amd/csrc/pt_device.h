@@ -206,10 +206,11 @@ void pt_launch_shadow_own(hipStream_t s, int blocks, const TraverseConfig &cfg, 
                           DevShadow sh, const uint32_t *shadow_queue, const uint32_t *count, uint8_t *occluded_out);
 void pt_launch_shade(hipStream_t s, int blocks, const DevScene &sc, DevPaths p, const uint32_t *queue,
                      const uint32_t *count, const float2 *hits, DevShadow sh, uint64_t *alive_mask,
-                     uint64_t *shadow_mask, ShadeParams sp);
+                     uint64_t *shadow_mask, ShadeParams sp, float4 *aov = nullptr);
 void pt_launch_shade_fast(hipStream_t s, int blocks, const DevScene &sc, DevPaths p, const uint32_t *queue,
                           const uint32_t *count, const float2 *hits, DevShadow sh, uint64_t *alive_mask,
-                          uint64_t *shadow_mask, ShadeParams sp);      // perf mode: shade.hip built with fast division / sqrt
+                          uint64_t *shadow_mask, ShadeParams sp, float4 *aov = nullptr);   // perf mode: shade.hip built with fast division / sqrt
+// (aov, bounce 0 only: 2 float4 per path of first-hit record, see shade.hip k_shade; NULL: none written)
 // ordered stream compaction of the survivors: masks -> next queue + its count, plus statistics
 // (tiles = ceil(capacity / pt_compact_tile_slots()) + 1: one workgroup per tile of ballot words)
 uint32_t pt_compact_tile_slots(void);
@@ -219,6 +220,10 @@ void pt_launch_compact(hipStream_t s, int tiles, const uint32_t *queue, const ui
                        unsigned long long *stats, uint32_t bounce, int do_scatter);
 void pt_launch_accumulate(hipStream_t s, int blocks, DevBand band, uint32_t frame0, uint32_t n_frames,
                           const float *L, uint32_t l_stride, float4 *out);
+// the first-hit planes (ptmi_set_aovs) from the batch's bounce-0 records, frames in ascending order like pt_launch_accumulate;
+// a NULL plane is not written
+void pt_launch_accumulate_aov(hipStream_t s, int blocks, DevBand band, uint32_t frame0, uint32_t n_frames, const float4 *rec,
+                              const ptmi_triangle *tris, uint32_t n_tris, float4 *albedo, float4 *normal, uint2 *ids);
 void pt_launch_blit(hipStream_t s, int blocks, uint32_t W, uint32_t H, const float4 *color, float4 *out_f32,
                     uint32_t *out_rgba8);
 // a device's rows of the frame <-> a contiguous buffer (ptmi_multi_gather)

@@ -57,6 +57,7 @@ struct Lane {
     uint8_t *d_occ = nullptr;
     hipStream_t side = nullptr;           // `shadow` of bounce b beside the kernels of bounce b + 1
     hipEvent_t ev_ready = nullptr, ev_shadow[2] = {nullptr, nullptr};
+    float4 *aov = nullptr;                // first-hit records of bounce 0, 32 B per path (k_shade<true>); only while AOV planes are on
 };
 
 struct ptmi_ctx {
@@ -78,6 +79,10 @@ struct ptmi_ctx {
     // output (binding 0)
     uint32_t W = 0, H = 0;
     float4 *d_out_own = nullptr, *d_out = nullptr;
+    // first-hit planes (ptmi_set_aovs): W x H each, present while their bit is set and the output buffer exists
+    uint32_t aov_mask = 0;
+    float4 *d_aov_albedo = nullptr, *d_aov_normal = nullptr;
+    uint2 *d_aov_id = nullptr;
 
     unsigned long long *d_stats = nullptr;
     float4 *d_blit_f32 = nullptr; uint32_t *d_blit_u8 = nullptr; size_t blit_px = 0;   // canvas staging of ptmi_blit, kept between calls
@@ -188,6 +193,7 @@ void free_batch(Lane &ln) {
     dfree(ln.hits);
     for (int k = 0; k < 2; k++) { dfree(ln.sh[k].SO); ln.sh[k].SD = nullptr; ln.sh[k].SC = nullptr; dfree(ln.sq[k]); }
     dfree(ln.queue[0]); dfree(ln.queue[1]); dfree(ln.alive); dfree(ln.shadowm); dfree(ln.word_off); dfree(ln.d_occ);
+    dfree(ln.aov);
     ln.cap = 0;
 }
 
@@ -201,9 +207,12 @@ hipError_t sync_all(ptmi_ctx *c) {
 
 // bytes of device memory a path of a batch takes in ensure_capacity (state 56 + hit 8 + 2 x (record 44 + index 4) + 2 queues + masks)
 constexpr size_t kBytesPerPath = 16 + 16 + 8 + 16 + 8 + 2 * (16 + 16 + sizeof(rgb_sc) + 4) + 2 * 4 + 1 + 1;
+constexpr size_t kAovBytesPerPath = 32;   // ... and, while AOV planes are on, its first-hit record (Lane::aov)
+size_t bytes_per_path(bool aov) { return kBytesPerPath + (aov ? kAovBytesPerPath : 0); }
 
 int ensure_capacity(ptmi_ctx *c, Lane &ln, size_t n) {
-    if (n <= ln.cap) return PTMI_OK;
+    const bool aov = c->aov_mask != 0;
+    if (n <= ln.cap && (!aov || ln.aov)) return PTMI_OK;
     HIP_TRY(c, sync_all(c));
     free_batch(ln);
     size_t cap = (n + 1023) & ~(size_t)1023;
@@ -227,6 +236,7 @@ int ensure_capacity(ptmi_ctx *c, Lane &ln, size_t n) {
     ALLOC(ln.alive, words * 8); ALLOC(ln.shadowm, words * 8); ln.mask_words = words;
     ALLOC(ln.word_off, 2 * tiles * 4);
     ALLOC(ln.d_occ, cap);
+    if (aov) ALLOC(ln.aov, cap * kAovBytesPerPath);
 #undef ALLOC
     ln.cap = cap;
     return PTMI_OK;
@@ -636,6 +646,43 @@ bool walks_memory_quantised(const TraverseConfig &cfg) {
     return cfg.quantized && pt_variant(cfg.variant).where == PT_FROM_MEMORY;
 }
 
+constexpr uint32_t kAovAll = PTMI_AOV_ALBEDO | PTMI_AOV_NORMAL | PTMI_AOV_ID;
+size_t aov_elem_bytes(uint32_t which) { return which == PTMI_AOV_ID ? 8 : 16; }
+void **aov_plane(ptmi_ctx *c, uint32_t which) {
+    switch (which) {
+    case PTMI_AOV_ALBEDO: return reinterpret_cast<void **>(&c->d_aov_albedo);
+    case PTMI_AOV_NORMAL: return reinterpret_cast<void **>(&c->d_aov_normal);
+    case PTMI_AOV_ID: return reinterpret_cast<void **>(&c->d_aov_id);
+    default: return nullptr;
+    }
+}
+
+// Makes the planes of `mask` exist at the output buffer's size and frees the others. New planes are zero-filled; with `fresh` (a resize)
+// every plane is. Everything is allocated before anything is freed: a failed call leaves the planes as they were.
+int alloc_aov_planes(ptmi_ctx *c, uint32_t mask, bool fresh) {
+    const size_t npix = (size_t)c->W * c->H;
+    void *n[3] = {};
+    const uint32_t bits[3] = {PTMI_AOV_ALBEDO, PTMI_AOV_NORMAL, PTMI_AOV_ID};
+    for (int k = 0; k < 3; k++) {
+        if (!(mask & bits[k]) || npix == 0 || (*aov_plane(c, bits[k]) && !fresh)) continue;
+        const size_t bytes = npix * aov_elem_bytes(bits[k]);
+        hipError_t e = hipMalloc(&n[k], bytes);
+        if (e == hipSuccess) e = hipMemset(n[k], 0, bytes);
+        if (e != hipSuccess) {
+            for (void *&p : n) dfree(p);
+            (void)hipGetLastError();
+            return fail(c, PTMI_E_HIP, "allocation of a %zu-byte AOV plane failed: %s (the AOV planes are as they were)", bytes,
+                        hipGetErrorString(e));
+        }
+    }
+    for (int k = 0; k < 3; k++) {
+        void **p = aov_plane(c, bits[k]);
+        if (n[k]) { dfree(*p); *p = n[k]; }
+        else if (!(mask & bits[k])) dfree(*p);
+    }
+    return PTMI_OK;
+}
+
 int check_ready(ptmi_ctx *c, bool need_output) {
     if (!c) return PTMI_E_INVALID;
     if (!c->have_scene) return fail(c, PTMI_E_STATE, "no scene uploaded (ptmi_upload_scene)");
@@ -753,7 +800,7 @@ int ptmi_destroy(ptmi_ctx *c) {
     }
     for (void *&p : c->buf) dfree(p);
     dfree(c->d_atlas);
-    dfree(c->d_out_own); dfree(c->d_stats); dfree(c->d_scene); dfree(c->d_blit_f32); dfree(c->d_blit_u8);
+    dfree(c->d_out_own); dfree(c->d_aov_albedo); dfree(c->d_aov_normal); dfree(c->d_aov_id); dfree(c->d_stats); dfree(c->d_scene); dfree(c->d_blit_f32); dfree(c->d_blit_u8);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
     return PTMI_OK;
@@ -942,7 +989,7 @@ int ptmi_resize(ptmi_ctx *c, uint32_t w, uint32_t h) {
     HIP_TRY(c, hipMalloc(&c->d_out_own, bytes));
     HIP_TRY(c, hipMemset(c->d_out_own, 0, bytes));
     c->d_out = c->d_out_own; c->W = w; c->H = h;
-    return PTMI_OK;
+    return alloc_aov_planes(c, c->aov_mask, true);
 }
 
 int ptmi_set_options(ptmi_ctx *c, const ptmi_options *o) {
@@ -992,9 +1039,9 @@ int ptmi_dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames) {
         // Room = free memory + what this context already holds, less a tenth for the rest (spill areas, blit staging).
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const uint64_t held = (uint64_t)ln.cap * kBytesPerPath;
+            const uint64_t held = (uint64_t)ln.cap * bytes_per_path(ln.aov != nullptr);
             const uint64_t room = (uint64_t)((double)(free_b + held) * 0.9);
-            F = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(F, room / (npix * kBytesPerPath)));
+            F = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(F, room / (npix * bytes_per_path(c->aov_mask != 0))));
         }
     }
     F = std::min(F, n_frames);
@@ -1042,6 +1089,7 @@ int ptmi_dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames) {
         if (cfg_shadow.wants_spill && !cfg_shadow.spill) cfg_shadow.spill = ln.d_spill_side;
         ln.paths.l_stride = c->st.radiance_stride_bytes / 4u;
         const DevPaths bp = ln.paths;
+        float4 *const aov_rec = c->aov_mask ? ln.aov : nullptr;         // written by shade(0), read by the fold after the last bounce
         for (uint32_t f0 = 0; f0 < n_frames; f0 += F) {
             const uint32_t fb = std::min(F, n_frames - f0);
             const uint32_t frame0 = cam->frame_index + f0;
@@ -1056,7 +1104,8 @@ int ptmi_dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames) {
                 if (side && b >= 2) HIP_TRY(c, hipStreamWaitEvent(ms, ln.ev_shadow[par], 0));      // its records are read
                 { Timed t(c, 2, t3, ms);
                   (c->opt.perf_mode ? pt_launch_shade_fast : pt_launch_shade)(
-                      ms, shade_blocks, c->sc, bp, q, &ln.counts[b], ln.hits, ln.sh[par], ln.alive, ln.shadowm, shp); }
+                      ms, shade_blocks, c->sc, bp, q, &ln.counts[b], ln.hits, ln.sh[par], ln.alive, ln.shadowm, shp,
+                      b == 0 ? aov_rec : nullptr); }
                 { Timed t(c, 5, t3, ms);
                   pt_launch_compact(ms, tiles, q, &ln.counts[b], ln.alive, nee ? ln.shadowm : nullptr,
                                     ln.word_off, ln.queue[cur ^ 1], &ln.counts[b + 1], ln.sq[par], &ln.counts[kShadowCount + par],
@@ -1079,7 +1128,11 @@ int ptmi_dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames) {
                 HIP_TRY(c, hipStreamWaitEvent(ms, ln.ev_shadow[(maxb - 1) & 1u], 0));
                 if (maxb >= 2) HIP_TRY(c, hipStreamWaitEvent(ms, ln.ev_shadow[maxb & 1u], 0));
             }
-            { Timed t(c, 6, t3, ms); pt_launch_accumulate(ms, blocks, band, frame0, fb, bp.L, bp.l_stride, c->d_out); }
+            { Timed t(c, 6, t3, ms);
+              pt_launch_accumulate(ms, blocks, band, frame0, fb, bp.L, bp.l_stride, c->d_out);
+              if (aov_rec)
+                  pt_launch_accumulate_aov(ms, blocks, band, frame0, fb, aov_rec, c->sc.tris, c->sc.n_tris, c->d_aov_albedo,
+                                           c->d_aov_normal, c->d_aov_id); }
         }
     }
     HIP_TRY(c, hipGetLastError());
@@ -1180,6 +1233,46 @@ int ptmi_get_size(const ptmi_ctx *c, uint32_t *w, uint32_t *h) {
     if (!c || !w || !h) return PTMI_E_INVALID;
     *w = c->W; *h = c->H;
     return PTMI_OK;
+}
+
+int ptmi_set_aovs(ptmi_ctx *c, uint32_t mask) {
+    if (!c) return PTMI_E_INVALID;
+    if (mask & ~kAovAll) return fail(c, PTMI_E_INVALID, "unknown AOV bits 0x%x", mask & ~kAovAll);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, sync_all(c));                     // nothing in flight writes a plane or a record that goes
+    const int rc = alloc_aov_planes(c, mask, false);
+    if (rc) return rc;
+    c->aov_mask = mask;
+    if (!mask) dfree(c->lane.aov);               // the records live only while a plane is on (ensure_capacity makes them)
+    return PTMI_OK;
+}
+
+int ptmi_get_aovs(const ptmi_ctx *c, uint32_t *mask) {
+    if (!c || !mask) return PTMI_E_INVALID;
+    *mask = c->aov_mask;
+    return PTMI_OK;
+}
+
+int ptmi_read_aov(ptmi_ctx *c, uint32_t which, void *dst, size_t n_bytes) {
+    if (!c) return PTMI_E_INVALID;
+    void **plane = aov_plane(c, which);
+    if (!plane) return fail(c, PTMI_E_INVALID, "which = 0x%x is not one PTMI_AOV_* plane", which);
+    if (!dst) return fail(c, PTMI_E_INVALID, "dst is NULL");
+    if (!(c->aov_mask & which)) return fail(c, PTMI_E_STATE, "AOV plane 0x%x is off (ptmi_set_aovs)", which);
+    if (!*plane) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
+    const size_t bytes = (size_t)c->W * c->H * aov_elem_bytes(which);
+    if (n_bytes != bytes) return fail(c, PTMI_E_INVALID, "expected %zu bytes, got %zu", bytes, n_bytes);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, sync_all(c));
+    drain_events(c);
+    HIP_TRY(c, hipMemcpy(dst, *plane, bytes, hipMemcpyDeviceToHost));
+    return PTMI_OK;
+}
+
+void *ptmi_aov_device_ptr(ptmi_ctx *c, uint32_t which) {
+    if (!c) return nullptr;
+    void **plane = aov_plane(c, which);
+    return plane && (c->aov_mask & which) ? *plane : nullptr;
 }
 
 int ptmi_get_stats(ptmi_ctx *c, ptmi_stats *out) {

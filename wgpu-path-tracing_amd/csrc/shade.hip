@@ -284,11 +284,17 @@ constexpr int SBLOCK = 256;
 #define PT_SHADE_ATTR
 #endif
 
+// AOV: the instantiation launched for bounce 0 while first-hit planes are enabled (ptmi_set_aovs). It also writes the path's first-hit
+// record, 32 B at slot i (the bounce-0 queue is the identity: slot i is path i), from the HitInfo the bounce builds anyway:
+// aov[2i] = (albedo.rgb, t), aov[2i + 1] = (normal.xyz, bits(triangle)); a miss writes zeros and triangle 0xFFFFFFFF.
+// The other instantiation never reads `aov` and is the bounce kernel as it was.
+template <bool AOV>
 __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, DevPaths P, const uint32_t *__restrict__ queue,
                                                   const uint32_t *__restrict__ count_ptr,
                                                   const float2 *__restrict__ hits, DevShadow S,
                                                   uint64_t *__restrict__ alive_mask,
-                                                  uint64_t *__restrict__ shadow_mask, ShadeParams sp) {
+                                                  uint64_t *__restrict__ shadow_mask, ShadeParams sp,
+                                                  float4 *__restrict__ aov) {
     const uint32_t count = *count_ptr;
     uint32_t n_skipped = 0, n_emitted = 0;  // lane 0 of each wave: one atomic per wave at the end
     for (uint32_t base = blockIdx.x * SBLOCK; base < count; base += gridDim.x * SBLOCK) {
@@ -305,6 +311,10 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                 v3 thr = mk3(1.0f, 1.0f, 1.0f);                                      // pt.wgsl:639; raygen stores no throughput
                 if (sp.bounce != 0u) { const float2 c2 = ld_stream(&P.C[q]); thr = mk3(d4.w, c2.x, c2.y); }
                 const HitInfo hit = make_hitinfo(sc, ro, rd, h2.x, __float_as_uint(h2.y));
+                if (AOV) {
+                    st_stream(&aov[2 * (size_t)i], make_float4(hit.albedo.x, hit.albedo.y, hit.albedo.z, hit.t));
+                    st_stream(&aov[2 * (size_t)i + 1], make_float4(hit.normal.x, hit.normal.y, hit.normal.z, h2.y));
+                }
                 if (hit.emission.x > 0.0f || hit.emission.y > 0.0f || hit.emission.z > 0.0f) {   // pt.wgsl:652-658
                     float att = rcp1(1.0f + hit.t * hit.t);
                     float k = hit.emissive_strength;
@@ -363,6 +373,9 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                         }
                     }
                 }
+            } else if (AOV) {                                                 // bounce 0 only: a camera ray that misses
+                st_stream(&aov[2 * (size_t)i], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+                st_stream(&aov[2 * (size_t)i + 1], make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu)));
             } else if (sp.bounce != 0u) {
                 // pt.wgsl:646-648: a miss adds `throughput * vec3f(0.0)` — nothing while the throughput is finite (x + +-0 = x, and
                 // the radiance is never -0), NaN in every component whose throughput is infinite or NaN (degenerate materials
@@ -408,9 +421,13 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
 #endif
 void PT_LAUNCH_SHADE(hipStream_t s, int blocks, const DevScene &sc, DevPaths p, const uint32_t *queue,
                      const uint32_t *count, const float2 *hits, DevShadow sh, uint64_t *alive_mask,
-                     uint64_t *shadow_mask, ShadeParams sp) {
-    hipLaunchKernelGGL(k_shade, dim3(blocks), dim3(SBLOCK), 0, s, sc, p, queue, count, hits, sh, alive_mask,
-                       shadow_mask, sp);
+                     uint64_t *shadow_mask, ShadeParams sp, float4 *aov) {
+    if (aov)
+        hipLaunchKernelGGL(k_shade<true>, dim3(blocks), dim3(SBLOCK), 0, s, sc, p, queue, count, hits, sh, alive_mask,
+                           shadow_mask, sp, aov);
+    else
+        hipLaunchKernelGGL(k_shade<false>, dim3(blocks), dim3(SBLOCK), 0, s, sc, p, queue, count, hits, sh, alive_mask,
+                           shadow_mask, sp, aov);
 }
 
 #ifndef PT_SHADE_FAST

@@ -236,6 +236,34 @@ static napi_value js_read_output(napi_env env, napi_callback_info info) {
     return argv[1];
 }
 
+/* setAovs(ctx, mask): PTMI_AOV_* bits */
+static napi_value js_set_aovs(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return NULL;
+    ptmi_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    uint32_t mask = 0;
+    napi_get_value_uint32(env, argv[1], &mask);
+    int rc = ptmi_set_aovs(ctx, mask);
+    if (rc) return throw_ptmi(env, ctx, rc, "ptmi_set_aovs");
+    return NULL;
+}
+
+/* readAov(ctx, which, dst typed array of width*height*16 (or *8 for PTMI_AOV_ID) bytes) */
+static napi_value js_read_aov(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return NULL;
+    ptmi_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    uint32_t which = 0;
+    napi_get_value_uint32(env, argv[1], &which);
+    void *p; size_t n;
+    if (!get_bytes(env, argv[2], &p, &n)) return NULL;
+    int rc = ptmi_read_aov(ctx, which, p, n);
+    if (rc) return throw_ptmi(env, ctx, rc, "ptmi_read_aov");
+    return argv[2];
+}
+
 static napi_value js_write_output(napi_env env, napi_callback_info info) {
     napi_value argv[2];
     if (!get_args(env, info, 2, argv)) return NULL;
@@ -607,7 +635,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"abiVersion", js_abi_version}, {"create", js_create}, {"destroy", js_destroy},
         {"uploadScene", js_upload_scene}, {"uploadAtlas", js_upload_atlas}, {"resize", js_resize},
         {"setOptions", js_set_options}, {"dispatch", js_dispatch}, {"synchronize", js_synchronize}, {"throttle", js_throttle}, {"multiThrottle", js_multi_throttle},
-        {"readOutput", js_read_output}, {"writeOutput", js_write_output}, {"blit", js_blit}, {"getStats", js_get_stats},
+        {"readOutput", js_read_output}, {"writeOutput", js_write_output}, {"setAovs", js_set_aovs}, {"readAov", js_read_aov}, {"blit", js_blit}, {"getStats", js_get_stats},
         {"resetStats", js_reset_stats}, {"buildBvh", js_build_bvh}, {"emissiveLights", js_emissive_lights},
         {"multiCreate", js_multi_create}, {"multiDestroy", js_multi_destroy}, {"multiUploadScene", js_multi_upload_scene},
         {"multiUploadAtlas", js_multi_upload_atlas}, {"multiResize", js_multi_resize}, {"multiSetOptions", js_multi_set_options},

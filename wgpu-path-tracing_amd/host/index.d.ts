@@ -64,6 +64,13 @@ export class Renderer {
   moveCamera(forward: number, right: number, up: number): void;
   rotateCamera(yaw: number, pitch: number): void;
   readOutput(): Float32Array;
+  /** first-hit planes (include/ptmi.h ptmi_set_aovs); throws with several devices */
+  setAovs(names: Array<'albedo' | 'normal' | 'id'>): void;
+  /** width*height entries, index y*width+x: 'albedo' / 'normal' 4 floats each, 'id' 2 uint32 (triangle, material) */
+  readAov(name: 'albedo' | 'normal'): Float32Array;
+  readAov(name: 'id'): Uint32Array;
+  /** canvas pixel (row 0 = top): what the last frame hit there, or null on a miss; needs the 'id' plane */
+  pick(x: number, y: number): { triangle: number; material: number; depth: number | null } | null;
   /** blit pass (blit.wgsl): tone-mapped RGBA8 canvas, row 0 = top */
   blit(): Uint8Array;
   setOptions(o: TraceOptions): void;

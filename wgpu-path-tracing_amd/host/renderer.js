@@ -224,6 +224,43 @@ Renderer.prototype.blit = function () {
   return out;
 };
 
+/** First-hit planes (include/ptmi.h ptmi_set_aovs): names of the planes to keep from now on, any of 'albedo', 'normal', 'id';
+ *  [] turns them all off. One device only: nothing gathers the planes of several. */
+var AOVS = { albedo: 1, normal: 2, id: 4 };
+function aovBit(name) {
+  if (!Object.prototype.hasOwnProperty.call(AOVS, name)) throw new Error('unknown AOV plane "' + name + '" (albedo, normal, id)');
+  return AOVS[name];
+}
+Renderer.prototype.setAovs = function (names) {
+  if (this.api.multi) throw new Error('setAovs: AOV planes are not supported with several devices');
+  var mask = 0;
+  (names || []).forEach(function (n) { mask |= aovBit(n); });
+  this.addon.setAovs(this.ctx, mask);
+  this.aovMask = mask;
+};
+/** A plane as width*height entries, index y*width+x like readOutput: 'albedo' / 'normal' a Float32Array of 4 per pixel
+ *  ((albedo, coverage) / (normal, depth)), 'id' a Uint32Array of 2 (triangle, material; 0xFFFFFFFF on a miss). Synchronises. */
+Renderer.prototype.readAov = function (name) {
+  var bit = aovBit(name);
+  var n = this.width * this.height;
+  var out = bit === 4 ? new Uint32Array(n * 2) : new Float32Array(n * 4);
+  this.addon.readAov(this.ctx, bit, out);
+  return out;
+};
+/** What is under canvas pixel (x, y), row 0 = top like blit(): {triangle, material, depth} of the last frame traced, or null
+ *  on a miss. Needs the 'id' plane; depth (the mean first-hit distance) comes from the 'normal' plane when that is on, else null. */
+Renderer.prototype.pick = function (x, y) {
+  if (!((this.aovMask || 0) & 4)) throw new Error("pick: turn the 'id' plane on first (setAovs)");
+  x = Math.floor(x); y = Math.floor(y);
+  if (x < 0 || y < 0 || x >= this.width || y >= this.height) return null;
+  var i = (this.height - 1 - y) * this.width + x;           // the planes' row 0 is the image bottom
+  var ids = this.readAov('id');
+  if (ids[2 * i] === 0xFFFFFFFF) return null;
+  var depth = null;
+  if (this.aovMask & 2) depth = this.readAov('normal')[4 * i + 3];
+  return { triangle: ids[2 * i], material: ids[2 * i + 1], depth: depth };
+};
+
 Renderer.prototype.setOptions = function (o) { this.api.setOptions(this.ctx, o); };
 Renderer.prototype.getStats = function () { return this.api.getStats(this.ctx); };
 /** several devices: assemble the frame on the first one now (readOutput / blit do it themselves) */

@@ -27,8 +27,12 @@ EXPORTS = [
     "ptmi_multi_upload_scene", "ptmi_multi_upload_atlas", "ptmi_multi_resize", "ptmi_multi_set_options", "ptmi_multi_get_options",
     "ptmi_multi_dispatch", "ptmi_multi_gather", "ptmi_multi_synchronize", "ptmi_multi_read_output", "ptmi_multi_write_output",
     "ptmi_multi_blit", "ptmi_multi_get_stats", "ptmi_multi_reset_stats", "ptmi_multi_gather_ms",
+    "ptmi_set_aovs", "ptmi_get_aovs", "ptmi_read_aov", "ptmi_aov_device_ptr",
 ]
 MULTI_LOOPBACK = 1
+# first-hit planes (include/ptmi.h ptmi_set_aovs): name -> (bit, numpy dtype, channels)
+AOV_ALBEDO, AOV_NORMAL, AOV_ID = 1, 2, 4
+AOVS = {"albedo": (AOV_ALBEDO, np.float32, 4), "normal": (AOV_NORMAL, np.float32, 4), "id": (AOV_ID, np.uint32, 2)}
 ABI_VERSION = 4
 
 
@@ -135,6 +139,11 @@ def load():
         L.ptmi_multi_blit.argtypes = [vp, vp, sz, vp, sz]
         L.ptmi_multi_get_stats.argtypes = [vp, vp]
         L.ptmi_multi_gather_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
+        L.ptmi_set_aovs.argtypes = [vp, u32]
+        L.ptmi_get_aovs.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32)]
+        L.ptmi_read_aov.argtypes = [vp, u32, vp, sz]
+        L.ptmi_aov_device_ptr.restype = vp
+        L.ptmi_aov_device_ptr.argtypes = [vp, u32]
         _lib = L
     return _lib
 
@@ -195,6 +204,12 @@ def _read_image(L, h, n_triangles, ck):
     lb = np.zeros((n_triangles, 8), np.float32) if info.leaves_used == 2 else None
     ck(L.ptmi_debug_read_image(h, ctypes.byref(info), _p(wn), _p(qn), _p(tp), _p(lb)))
     return info, wn, qn, tp, lb
+
+
+def _aov(name):
+    if name not in AOVS:
+        raise ValueError(f"unknown AOV plane {name!r}: one of {sorted(AOVS)}")
+    return AOVS[name]
 
 
 class Context:
@@ -307,6 +322,30 @@ class Context:
 
     def reset_stats(self):
         self._ck(self.L.ptmi_reset_stats(self.h))
+
+    # -- first-hit planes (include/ptmi.h ptmi_set_aovs) ----------------------------
+    def set_aovs(self, *planes):
+        """set_aovs('albedo', 'normal', 'id') or set_aovs(mask); set_aovs() turns every plane off"""
+        mask = 0
+        for p in planes:
+            mask |= int(p) if not isinstance(p, str) else _aov(p)[0]
+        self._ck(self.L.ptmi_set_aovs(self.h, mask))
+
+    def aovs(self):
+        """the names of the planes that are on"""
+        m = ctypes.c_uint32(0)
+        self._ck(self.L.ptmi_get_aovs(self.h, ctypes.byref(m)))
+        return tuple(n for n, (bit, _, _) in AOVS.items() if m.value & bit)
+
+    def read_aov(self, name):
+        """(H, W, 4) float32 for 'albedo' / 'normal', (H, W, 2) uint32 (triangle, material) for 'id'"""
+        bit, dt, ch = _aov(name)
+        out = np.empty((self.height, self.width, ch), dt)
+        self._ck(self.L.ptmi_read_aov(self.h, bit, _p(out), out.nbytes))
+        return out
+
+    def aov_device_ptr(self, name):
+        return self.L.ptmi_aov_device_ptr(self.h, _aov(name)[0])
 
     def read_image(self):
         """The traversal image the last upload_scene put on the device (include/ptmi.h: ptmi_debug_read_image), as build_image()
