@@ -55,6 +55,19 @@ def test_addon_loads_and_fails_loudly_without_gpu():
     assert out == "CREATED" or ("ptmi_create failed" in out and "no CPU backend" in out), out
 
 
+def test_addon_rejects_anything_but_a_handle():
+    """Every export that takes a handle throws a TypeError for a value that is not one, before any library call: no GPU needed."""
+    _build_addon()
+    js = ("var a=require(%r);var noHandle={abiVersion:1,create:1,multiCreate:1,buildBvh:1,emissiveLights:1};var res={};"
+          "Object.keys(a).filter(function(k){return !noHandle[k]}).forEach(function(k){res[k]=[{},1,null,undefined].map(function(v){"
+          "try{a[k](v,null,null,null,null);return 'no error'}catch(e){return e instanceof TypeError?e.message:String(e)}})});"
+          "console.log(JSON.stringify(res))" % os.path.join(HOST, "addon", "ptmi_napi.node"))
+    res = json.loads(subprocess.check_output([NODE, "-e", js], text=True))
+    assert {"destroy", "dispatch", "blit", "gather", "setAovs", "resetStats"} <= set(res), sorted(res)
+    for name, msgs in res.items():
+        assert all("expected a ptmi handle" in m for m in msgs), (name, msgs)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("batch", [1, 4])
 def test_node_render_matches_oracle(tmp_path, oracle, batch):
@@ -94,7 +107,8 @@ def test_node_blit_png(tmp_path, oracle):
 @pytest.mark.gpu
 def test_node_blit_rejects_a_buffer_of_the_wrong_size(tmp_path):
     """addon.blit writes width*height*4 bytes: a short array, or one kept from before resize(), must raise a RangeError
-    in JS instead of reaching the library (which would write past the end of the V8 buffer)."""
+    in JS instead of reaching the library (which would write past the end of the V8 buffer). A handle kept past destroy()
+    is a TypeError, for blit and for a second destroy."""
     _build_addon()
     sc = scenes.make("cornell")
     scene_io.save_ptscene(sc, str(tmp_path / "c.ptscene"))
@@ -103,7 +117,9 @@ def test_node_blit_rejects_a_buffer_of_the_wrong_size(tmp_path):
           "[new Uint8Array(10),new Uint8Array(16*8*4+4)].forEach(function(b){try{r.addon.blit(r.ctx,b);res.push('no error')}"
           "catch(e){res.push(e instanceof RangeError?'RangeError':String(e))}});"
           "r.resize(32,8);try{r.addon.blit(r.ctx,ok);res.push('no error')}catch(e){res.push(e instanceof RangeError?'RangeError':String(e))}"
-          "res.push(r.blit().length);console.log(JSON.stringify(res));r.destroy();})"
+          "res.push(r.blit().length);var c=r.ctx;r.destroy();[function(){r.addon.blit(c,ok)},function(){r.addon.destroy(c)}]"
+          ".forEach(function(f){try{f();res.push('no error')}catch(e){res.push(e instanceof TypeError?'TypeError':String(e))}});"
+          "console.log(JSON.stringify(res));})"
           % (os.path.join(HOST, "renderer.js"), str(tmp_path / "c.ptscene")))
     out = json.loads(subprocess.check_output([NODE, "-e", js], text=True).strip().splitlines()[-1])
-    assert out == [16 * 8 * 4, "RangeError", "RangeError", "RangeError", 32 * 8 * 4]
+    assert out == [16 * 8 * 4, "RangeError", "RangeError", "RangeError", 32 * 8 * 4, "TypeError", "TypeError"]

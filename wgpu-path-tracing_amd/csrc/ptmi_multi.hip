@@ -96,6 +96,15 @@ int mfail(const ptmi_multi *m, int code, const char *fmt, ...) {
 int cfail(const ptmi_multi *m, int i, int rc, const char *what) {
     return mfail(m, rc, "%s on device %d (ordinal %d): %s", what, i, m->dev[i], ptmi_last_error(m->ctx[i]));
 }
+// fn(ctx, args...) on every device's context in turn; the first failure is reported through cfail and ends the loop
+template <class Fn, class... Args>
+int each_ctx(const ptmi_multi *m, const char *what, Fn fn, const Args &...args) {
+    for (size_t i = 0; i < m->ctx.size(); i++) {
+        int rc = fn(m->ctx[i], args...);
+        if (rc) return cfail(m, (int)i, rc, what);
+    }
+    return PTMI_OK;
+}
 #define MHIP(m, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
     return mfail((m), PTMI_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 #define MNCCL(m, expr) do { ncclResult_t r_ = (expr); if (r_ != ncclSuccess) \
@@ -257,19 +266,13 @@ int ptmi_multi_upload_atlas(ptmi_multi *m, const void *texels, uint32_t w, uint3
         char why[128];
         if (pt_atlas_bytes(w, h, fmt, &bytes, why, sizeof why) != PTMI_OK) return mfail(m, PTMI_E_INVALID, "%s", why);
     }
-    for (size_t i = 0; i < m->ctx.size(); i++) {
-        int rc = ptmi_upload_atlas(m->ctx[i], texels, w, h, fmt);
-        if (rc) return cfail(m, (int)i, rc, "ptmi_upload_atlas");
-    }
-    return PTMI_OK;
+    return each_ctx(m, "ptmi_upload_atlas", ptmi_upload_atlas, texels, w, h, fmt);
 }
 
 int ptmi_multi_resize(ptmi_multi *m, uint32_t w, uint32_t h) {
     if (!m) return PTMI_E_INVALID;
-    for (size_t i = 0; i < m->ctx.size(); i++) {
-        int rc = ptmi_resize(m->ctx[i], w, h);
-        if (rc) return cfail(m, (int)i, rc, "ptmi_resize");
-    }
+    int rc = each_ctx(m, "ptmi_resize", ptmi_resize, w, h);
+    if (rc) return rc;
     m->W = w; m->H = h;
     m->dispatched = m->gathered = 0;
     return configure(m);
@@ -389,11 +392,7 @@ int ptmi_multi_gather(ptmi_multi *m) {
 
 int ptmi_multi_synchronize(ptmi_multi *m) {
     if (!m) return PTMI_E_INVALID;
-    for (size_t i = 0; i < m->ctx.size(); i++) {
-        int rc = ptmi_synchronize(m->ctx[i]);
-        if (rc) return cfail(m, (int)i, rc, "ptmi_synchronize");
-    }
-    return PTMI_OK;
+    return each_ctx(m, "ptmi_synchronize", ptmi_synchronize);
 }
 
 int ptmi_multi_throttle(ptmi_multi *m, uint32_t max_in_flight, uint32_t *in_flight) {
@@ -420,10 +419,8 @@ int ptmi_multi_read_output(ptmi_multi *m, float *dst, size_t n_floats) {
 
 int ptmi_multi_write_output(ptmi_multi *m, const float *src, size_t n_floats) {
     if (!m || !src) return PTMI_E_INVALID;
-    for (size_t i = 0; i < m->ctx.size(); i++) {
-        int rc = ptmi_write_output(m->ctx[i], src, n_floats);
-        if (rc) return cfail(m, (int)i, rc, "ptmi_write_output");
-    }
+    int rc = each_ctx(m, "ptmi_write_output", ptmi_write_output, src, n_floats);
+    if (rc) return rc;
     m->dispatched = m->gathered = 0;          // every device holds the whole frame again: the rows may be dealt out anew
     return PTMI_OK;
 }
@@ -460,11 +457,7 @@ int ptmi_multi_get_stats(ptmi_multi *m, ptmi_stats *out) {
 
 int ptmi_multi_reset_stats(ptmi_multi *m) {
     if (!m) return PTMI_E_INVALID;
-    for (size_t i = 0; i < m->ctx.size(); i++) {
-        int rc = ptmi_reset_stats(m->ctx[i]);
-        if (rc) return cfail(m, (int)i, rc, "ptmi_reset_stats");
-    }
-    return PTMI_OK;
+    return each_ctx(m, "ptmi_reset_stats", ptmi_reset_stats);
 }
 
 int ptmi_multi_gather_ms(ptmi_multi *m, double *ms) {

@@ -1,10 +1,12 @@
 /*
  * ptmi_napi.c — thin N-API (Node >= 12, N-API 4) addon over the C ABI of include/ptmi.h.
  *
- * One JS function per C function; scene / camera blobs travel as ArrayBuffers (or typed-array
- * views) in the exact WGSL layouts the reference writes with device.queue.writeBuffer
- * (src/renderer/renderer.ts:242-355, :403-413). A non-zero ptmi status becomes a JS Error
- * carrying ptmi_last_error(). No rendering logic lives here.
+ * One JS function per operation, for both handle types: create(device) and multiCreate([ordinal, ...], flags) return a
+ * handle, and every other function calls ptmi_X or ptmi_multi_X by the kind of handle it is given. Scene / camera blobs
+ * travel as ArrayBuffers (or typed-array views) in the exact WGSL layouts the reference writes with
+ * device.queue.writeBuffer (src/renderer/renderer.ts:242-355, :403-413). A non-zero ptmi status becomes a JS Error
+ * "<C function> failed (<rc>): <ptmi_last_error or ptmi_multi_last_error>"; anything but a live handle is a TypeError
+ * before any library call. No rendering logic lives here.
  *
  * build: oracle-free, see Makefile next to this file
  *   gcc -shared -fPIC -I/usr/include/node -I../../../include ptmi_napi.c -L../../lib -lptmi
@@ -13,6 +15,7 @@
 #include <node_api.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "ptmi.h"
@@ -26,9 +29,27 @@
         }                                                                         \
     } while (0)
 
-static napi_value throw_ptmi(napi_env env, ptmi_ctx *ctx, int rc, const char *what) {
-    char buf[640];
-    snprintf(buf, sizeof buf, "%s failed (%d): %s", what, rc, ptmi_last_error(ctx));
+/* What a JS handle points at: which library type, and the library object (NULL once destroy() has run). The kinds are
+ * unlikely bit patterns, so that get_handle can tell this record from another addon's external. */
+enum { KIND_CTX = 0x70746d31, KIND_MULTI = 0x70746d4e };
+typedef struct {
+    uint32_t kind;
+    union { void *p; ptmi_ctx *ctx; ptmi_multi *m; };
+} handle;
+
+/* ptmi_<fn>(ctx, ...) or ptmi_multi_<fn>(m, ...), by the handle's kind */
+#define RUN(h, fn, ...) ((h)->kind == KIND_MULTI ? ptmi_multi_##fn((h)->m, ##__VA_ARGS__) : ptmi_##fn((h)->ctx, ##__VA_ARGS__))
+/* RUN, and a non-zero status throws, naming the function that ran */
+#define CALL(env, h, fn, ...)                                                                                   \
+    do {                                                                                                        \
+        int rc_ = RUN(h, fn, ##__VA_ARGS__);                                                                    \
+        if (rc_) return throw_ptmi((env), (h), rc_, (h)->kind == KIND_MULTI ? "ptmi_multi_" #fn : "ptmi_" #fn); \
+    } while (0)
+
+static napi_value throw_ptmi(napi_env env, const handle *h, int rc, const char *what) {
+    char buf[768];
+    snprintf(buf, sizeof buf, "%s failed (%d): %s", what, rc,
+             h->kind == KIND_MULTI ? ptmi_multi_last_error(h->m) : ptmi_last_error(h->ctx));
     napi_throw_error(env, "PTMI", buf);
     return NULL;
 }
@@ -42,13 +63,36 @@ static int get_args(napi_env env, napi_callback_info info, size_t want, napi_val
     return 1;
 }
 
-static ptmi_ctx *get_ctx(napi_env env, napi_value v) {
-    void *p = NULL;
-    if (napi_get_value_external(env, v, &p) != napi_ok || !p) {
-        napi_throw_type_error(env, NULL, "expected a ptmi context handle");
+/* the finalizer frees the record only: the library object lives until destroy() */
+static void free_handle(napi_env env, void *data, void *hint) {
+    (void)env; (void)hint;
+    free(data);
+}
+
+static napi_value new_handle(napi_env env, uint32_t kind, void *p) {
+    handle *h = malloc(sizeof *h);
+    napi_value ext;
+    if (!h) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    h->kind = kind; h->p = p;
+    if (napi_create_external(env, h, free_handle, NULL, &ext) != napi_ok) {
+        free(h);
+        napi_throw_error(env, NULL, "N-API call failed: napi_create_external");
         return NULL;
     }
-    return (ptmi_ctx *)p;
+    return ext;
+}
+
+/* the call's arguments, and the live handle in the first; NULL after throwing a TypeError */
+static handle *get_handle(napi_env env, napi_callback_info info, size_t want, napi_value *argv) {
+    void *p = NULL;
+    handle *h = NULL;
+    if (!get_args(env, info, want, argv)) return NULL;
+    if (napi_get_value_external(env, argv[0], &p) == napi_ok) h = p;
+    if (!h || (h->kind != KIND_CTX && h->kind != KIND_MULTI) || !h->p) {
+        napi_throw_type_error(env, NULL, "expected a ptmi handle from create() or multiCreate() that has not been destroyed");
+        return NULL;
+    }
+    return h;
 }
 
 /* ArrayBuffer or TypedArray/DataView -> (pointer, byte length); null/undefined -> (NULL, 0) */
@@ -88,274 +132,8 @@ static napi_value js_create(napi_env env, napi_callback_info info) {
     NAPI_OK(env, napi_get_value_int32(env, argv[0], &dev));
     ptmi_ctx *ctx = NULL;
     int rc = ptmi_create(dev, &ctx);
-    if (rc) return throw_ptmi(env, NULL, rc, "ptmi_create");
-    napi_value ext;
-    NAPI_OK(env, napi_create_external(env, ctx, NULL, NULL, &ext));
-    return ext;
-}
-
-static napi_value js_destroy(napi_env env, napi_callback_info info) {
-    napi_value argv[1];
-    if (!get_args(env, info, 1, argv)) return NULL;
-    ptmi_ctx *ctx = get_ctx(env, argv[0]);
-    if (!ctx) return NULL;
-    ptmi_destroy(ctx);
-    return NULL;
-}
-
-static napi_value js_upload_scene(napi_env env, napi_callback_info info) {
-    napi_value argv[5];
-    if (!get_args(env, info, 5, argv)) return NULL;
-    ptmi_ctx *ctx = get_ctx(env, argv[0]);
-    if (!ctx) return NULL;
-    void *p[4]; size_t n[4];
-    static const size_t stride[4] = {sizeof(ptmi_triangle), sizeof(ptmi_material), sizeof(ptmi_bvh_node), sizeof(ptmi_light)};
-    for (int i = 0; i < 4; i++) {
-        if (!get_bytes(env, argv[1 + i], &p[i], &n[i])) return NULL;
-        if (n[i] % stride[i]) { napi_throw_range_error(env, NULL, "blob length is not a multiple of its element size"); return NULL; }
-    }
-    int rc = ptmi_upload_scene(ctx, (const ptmi_triangle *)p[0], (uint32_t)(n[0] / stride[0]),
-                               (const ptmi_material *)p[1], (uint32_t)(n[1] / stride[1]),
-                               (const ptmi_bvh_node *)p[2], (uint32_t)(n[2] / stride[2]),
-                               (const ptmi_light *)p[3], (uint32_t)(n[3] / stride[3]));
-    if (rc) return throw_ptmi(env, ctx, rc, "ptmi_upload_scene");
-    return NULL;
-}
-
-static napi_value js_upload_atlas(napi_env env, napi_callback_info info) {
-    napi_value argv[5];
-    if (!get_args(env, info, 5, argv)) return NULL;
-    ptmi_ctx *ctx = get_ctx(env, argv[0]);
-    if (!ctx) return NULL;
-    void *p; size_t n; uint32_t w = 0, h = 0; int32_t fmt = 0;
-    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
-    napi_get_value_uint32(env, argv[2], &w); napi_get_value_uint32(env, argv[3], &h); napi_get_value_int32(env, argv[4], &fmt);
-    if (p && n < (size_t)w * h * (fmt == PTMI_ATLAS_RGBA16F ? 8 : 16)) { napi_throw_range_error(env, NULL, "atlas buffer too small"); return NULL; }
-    int rc = ptmi_upload_atlas(ctx, p, w, h, fmt);
-    if (rc) return throw_ptmi(env, ctx, rc, "ptmi_upload_atlas");
-    return NULL;
-}
-
-static napi_value js_resize(napi_env env, napi_callback_info info) {
-    napi_value argv[3];
-    if (!get_args(env, info, 3, argv)) return NULL;
-    ptmi_ctx *ctx = get_ctx(env, argv[0]);
-    if (!ctx) return NULL;
-    uint32_t w = 0, h = 0;
-    napi_get_value_uint32(env, argv[1], &w); napi_get_value_uint32(env, argv[2], &h);
-    int rc = ptmi_resize(ctx, w, h);
-    if (rc) return throw_ptmi(env, ctx, rc, "ptmi_resize");
-    return NULL;
-}
-
-/* JS option names -> ptmi_options (unset properties keep their current values) */
-static void read_options(napi_env env, napi_value obj, ptmi_options *o) {
-    o->max_bounces = get_u32_prop(env, obj, "maxBounces", o->max_bounces);
-    o->do_mis = get_u32_prop(env, obj, "doMis", o->do_mis);
-    o->tile_y0 = get_u32_prop(env, obj, "tileY0", o->tile_y0);
-    o->tile_y1 = get_u32_prop(env, obj, "tileY1", o->tile_y1);
-    o->frames_per_batch = get_u32_prop(env, obj, "framesPerBatch", o->frames_per_batch);
-    o->traversal = get_u32_prop(env, obj, "traversal", o->traversal);
-    o->cull = get_u32_prop(env, obj, "cull", o->cull);
-    o->timing = get_u32_prop(env, obj, "timing", o->timing);
-    o->keep_reference_tree = get_u32_prop(env, obj, "keepReferenceTree", o->keep_reference_tree);
-    o->tile_parts = get_u32_prop(env, obj, "tileParts", o->tile_parts);
-    o->tile_part = get_u32_prop(env, obj, "tilePart", o->tile_part);
-    o->tile_strip = get_u32_prop(env, obj, "tileStrip", o->tile_strip);
-    o->perf_mode = get_u32_prop(env, obj, "perfMode", o->perf_mode);
-    o->overlap = get_u32_prop(env, obj, "overlap", o->overlap);
-    o->tree_builder = get_u32_prop(env, obj, "treeBuilder", o->tree_builder);
-    o->leaves = get_u32_prop(env, obj, "leaves", o->leaves);
-    o->leaf_tris = get_u32_prop(env, obj, "leafTris", o->leaf_tris);
-}
-
-static napi_value js_set_options(napi_env env, napi_callback_info info) {
-    napi_value argv[2];
-    if (!get_args(env, info, 2, argv)) return NULL;
-    ptmi_ctx *ctx = get_ctx(env, argv[0]);
-    if (!ctx) return NULL;
-    ptmi_options o;
-    ptmi_get_options(ctx, &o);
-    read_options(env, argv[1], &o);
-    int rc = ptmi_set_options(ctx, &o);
-    if (rc) return throw_ptmi(env, ctx, rc, "ptmi_set_options");
-    return NULL;
-}
-
-static napi_value js_dispatch(napi_env env, napi_callback_info info) {
-    napi_value argv[3];
-    if (!get_args(env, info, 3, argv)) return NULL;
-    ptmi_ctx *ctx = get_ctx(env, argv[0]);
-    if (!ctx) return NULL;
-    void *p; size_t n; uint32_t frames = 1;
-    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
-    if (!p || n != sizeof(ptmi_camera)) { napi_throw_range_error(env, NULL, "camera blob must be 96 bytes"); return NULL; }
-    napi_get_value_uint32(env, argv[2], &frames);
-    ptmi_camera cam;
-    memcpy(&cam, p, sizeof cam);
-    int rc = ptmi_dispatch(ctx, &cam, frames);
-    if (rc) return throw_ptmi(env, ctx, rc, "ptmi_dispatch");
-    return NULL;
-}
-
-static napi_value js_synchronize(napi_env env, napi_callback_info info) {
-    napi_value argv[1];
-    if (!get_args(env, info, 1, argv)) return NULL;
-    ptmi_ctx *ctx = get_ctx(env, argv[0]);
-    if (!ctx) return NULL;
-    int rc = ptmi_synchronize(ctx);
-    if (rc) return throw_ptmi(env, ctx, rc, "ptmi_synchronize");
-    return NULL;
-}
-
-/* throttle(ctx, maxInFlight) -> dispatches still in flight (blocks until at most maxInFlight are) */
-static napi_value js_throttle(napi_env env, napi_callback_info info) {
-    napi_value argv[2];
-    if (!get_args(env, info, 2, argv)) return NULL;
-    ptmi_ctx *ctx = get_ctx(env, argv[0]);
-    if (!ctx) return NULL;
-    uint32_t max = 0, n = 0;
-    napi_get_value_uint32(env, argv[1], &max);
-    int rc = ptmi_throttle(ctx, max, &n);
-    if (rc) return throw_ptmi(env, ctx, rc, "ptmi_throttle");
-    napi_value v;
-    NAPI_OK(env, napi_create_uint32(env, n, &v));
-    return v;
-}
-
-/* readOutput(ctx, Float32Array dst) */
-static napi_value js_read_output(napi_env env, napi_callback_info info) {
-    napi_value argv[2];
-    if (!get_args(env, info, 2, argv)) return NULL;
-    ptmi_ctx *ctx = get_ctx(env, argv[0]);
-    if (!ctx) return NULL;
-    void *p; size_t n;
-    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
-    int rc = ptmi_read_output(ctx, (float *)p, n / 4);
-    if (rc) return throw_ptmi(env, ctx, rc, "ptmi_read_output");
-    return argv[1];
-}
-
-/* setAovs(ctx, mask): PTMI_AOV_* bits */
-static napi_value js_set_aovs(napi_env env, napi_callback_info info) {
-    napi_value argv[2];
-    if (!get_args(env, info, 2, argv)) return NULL;
-    ptmi_ctx *ctx = get_ctx(env, argv[0]);
-    if (!ctx) return NULL;
-    uint32_t mask = 0;
-    napi_get_value_uint32(env, argv[1], &mask);
-    int rc = ptmi_set_aovs(ctx, mask);
-    if (rc) return throw_ptmi(env, ctx, rc, "ptmi_set_aovs");
-    return NULL;
-}
-
-/* readAov(ctx, which, dst typed array of width*height*16 (or *8 for PTMI_AOV_ID) bytes) */
-static napi_value js_read_aov(napi_env env, napi_callback_info info) {
-    napi_value argv[3];
-    if (!get_args(env, info, 3, argv)) return NULL;
-    ptmi_ctx *ctx = get_ctx(env, argv[0]);
-    if (!ctx) return NULL;
-    uint32_t which = 0;
-    napi_get_value_uint32(env, argv[1], &which);
-    void *p; size_t n;
-    if (!get_bytes(env, argv[2], &p, &n)) return NULL;
-    int rc = ptmi_read_aov(ctx, which, p, n);
-    if (rc) return throw_ptmi(env, ctx, rc, "ptmi_read_aov");
-    return argv[2];
-}
-
-static napi_value js_write_output(napi_env env, napi_callback_info info) {
-    napi_value argv[2];
-    if (!get_args(env, info, 2, argv)) return NULL;
-    ptmi_ctx *ctx = get_ctx(env, argv[0]);
-    if (!ctx) return NULL;
-    void *p; size_t n;
-    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
-    int rc = ptmi_write_output(ctx, (const float *)p, n / 4);
-    if (rc) return throw_ptmi(env, ctx, rc, "ptmi_write_output");
-    return NULL;
-}
-
-/* blit(ctx, Uint8Array dstRgba8) — the reference's blit pass (blit.wgsl) into an 8-bit canvas, row 0 = top */
-static napi_value js_blit(napi_env env, napi_callback_info info) {
-    napi_value argv[2];
-    if (!get_args(env, info, 2, argv)) return NULL;
-    ptmi_ctx *ctx = get_ctx(env, argv[0]);
-    if (!ctx) return NULL;
-    void *p; size_t n;
-    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
-    if (!p) { napi_throw_type_error(env, NULL, "expected a Uint8Array of width*height*4 bytes"); return NULL; }
-    /* the library writes width*height*4 bytes: a short (or stale, after resize()) array must not reach it */
-    uint32_t w = 0, h = 0;
-    int rc = ptmi_get_size(ctx, &w, &h);
-    if (rc) return throw_ptmi(env, ctx, rc, "ptmi_get_size");
-    if (n != (size_t)w * h * 4) {
-        char msg[128];
-        snprintf(msg, sizeof msg, "blit: expected a Uint8Array of %zu bytes (%ux%ux4), got %zu", (size_t)w * h * 4, w, h, n);
-        napi_throw_range_error(env, NULL, msg);
-        return NULL;
-    }
-    rc = ptmi_blit(ctx, NULL, 0, (uint8_t *)p, n);
-    if (rc) return throw_ptmi(env, ctx, rc, "ptmi_blit");
-    return argv[1];
-}
-
-static void set_num(napi_env env, napi_value obj, const char *k, double v) {
-    napi_value n;
-    if (napi_create_double(env, v, &n) == napi_ok) napi_set_named_property(env, obj, k, n);
-}
-
-static napi_value stats_object(napi_env env, const ptmi_stats *s) {
-    napi_value o;
-    NAPI_OK(env, napi_create_object(env, &o));
-    set_num(env, o, "paths", (double)s->paths); set_num(env, o, "segments", (double)s->segments);
-    set_num(env, o, "shadowRays", (double)s->shadow_rays); set_num(env, o, "frames", (double)s->frames);
-    set_num(env, o, "dispatches", (double)s->dispatches); set_num(env, o, "gpuMs", s->gpu_ms);
-    set_num(env, o, "extendMs", s->extend_ms); set_num(env, o, "shadeMs", s->shade_ms); set_num(env, o, "shadowMs", s->shadow_ms);
-    set_num(env, o, "shadowTraced", (double)s->shadow_traced); set_num(env, o, "uploadMs", s->upload_ms);
-    set_num(env, o, "bvhDepth", s->bvh_depth); set_num(env, o, "traversalUsed", s->traversal_used);
-    set_num(env, o, "framesPerBatchUsed", s->frames_per_batch_used);
-    set_num(env, o, "leavesUsed", s->leaves_used); set_num(env, o, "leafTrisUsed", s->leaf_tris_used);
-    set_num(env, o, "extendVariant", s->extend_variant); set_num(env, o, "shadowVariant", s->shadow_variant);
-    set_num(env, o, "verifyFailed", (double)s->verify_failed); set_num(env, o, "treeBuilderUsed", s->tree_builder_used);
-    return o;
-}
-
-static napi_value js_get_stats(napi_env env, napi_callback_info info) {
-    napi_value argv[1];
-    if (!get_args(env, info, 1, argv)) return NULL;
-    ptmi_ctx *ctx = get_ctx(env, argv[0]);
-    if (!ctx) return NULL;
-    ptmi_stats s;
-    int rc = ptmi_get_stats(ctx, &s);
-    if (rc) return throw_ptmi(env, ctx, rc, "ptmi_get_stats");
-    return stats_object(env, &s);
-}
-
-static napi_value js_reset_stats(napi_env env, napi_callback_info info) {
-    napi_value argv[1];
-    if (!get_args(env, info, 1, argv)) return NULL;
-    ptmi_ctx *ctx = get_ctx(env, argv[0]);
-    if (!ctx) return NULL;
-    ptmi_reset_stats(ctx);
-    return NULL;
-}
-
-
-/* ---- several devices behind one handle (include/ptmi.h ptmi_multi_*): the same calls, one per JS function ---- */
-static napi_value throw_multi(napi_env env, ptmi_multi *m, int rc, const char *what) {
-    char buf[768];
-    snprintf(buf, sizeof buf, "%s failed (%d): %s", what, rc, ptmi_multi_last_error(m));
-    napi_throw_error(env, "PTMI", buf);
-    return NULL;
-}
-static ptmi_multi *get_multi(napi_env env, napi_value v) {
-    void *p = NULL;
-    if (napi_get_value_external(env, v, &p) != napi_ok || !p) {
-        napi_throw_type_error(env, NULL, "expected a ptmi multi-device handle");
-        return NULL;
-    }
-    return (ptmi_multi *)p;
+    if (rc) return throw_ptmi(env, &(handle){.kind = KIND_CTX}, rc, "ptmi_create");
+    return new_handle(env, KIND_CTX, ctx);
 }
 
 /* multiCreate([ordinal, ...], flags) */
@@ -378,191 +156,254 @@ static napi_value js_multi_create(napi_env env, napi_callback_info info) {
     napi_get_value_uint32(env, argv[1], &flags);
     ptmi_multi *m = NULL;
     int rc = ptmi_multi_create((int)n, dev, flags, &m);
-    if (rc) return throw_multi(env, NULL, rc, "ptmi_multi_create");
-    napi_value ext;
-    NAPI_OK(env, napi_create_external(env, m, NULL, NULL, &ext));
-    return ext;
+    if (rc) return throw_ptmi(env, &(handle){.kind = KIND_MULTI}, rc, "ptmi_multi_create");
+    return new_handle(env, KIND_MULTI, m);
 }
 
-static napi_value js_multi_destroy(napi_env env, napi_callback_info info) {
+static napi_value js_destroy(napi_env env, napi_callback_info info) {
     napi_value argv[1];
-    if (!get_args(env, info, 1, argv)) return NULL;
-    ptmi_multi *m = get_multi(env, argv[0]);
-    if (m) ptmi_multi_destroy(m);
+    handle *h = get_handle(env, info, 1, argv);
+    if (!h) return NULL;
+    (void)RUN(h, destroy);
+    h->p = NULL;
     return NULL;
 }
 
-static napi_value js_multi_upload_scene(napi_env env, napi_callback_info info) {
+static napi_value js_upload_scene(napi_env env, napi_callback_info info) {
     napi_value argv[5];
-    if (!get_args(env, info, 5, argv)) return NULL;
-    ptmi_multi *m = get_multi(env, argv[0]);
-    if (!m) return NULL;
+    handle *h = get_handle(env, info, 5, argv);
+    if (!h) return NULL;
     void *p[4]; size_t n[4];
     static const size_t stride[4] = {sizeof(ptmi_triangle), sizeof(ptmi_material), sizeof(ptmi_bvh_node), sizeof(ptmi_light)};
     for (int i = 0; i < 4; i++) {
         if (!get_bytes(env, argv[1 + i], &p[i], &n[i])) return NULL;
         if (n[i] % stride[i]) { napi_throw_range_error(env, NULL, "blob length is not a multiple of its element size"); return NULL; }
     }
-    int rc = ptmi_multi_upload_scene(m, (const ptmi_triangle *)p[0], (uint32_t)(n[0] / stride[0]),
-                                     (const ptmi_material *)p[1], (uint32_t)(n[1] / stride[1]),
-                                     (const ptmi_bvh_node *)p[2], (uint32_t)(n[2] / stride[2]),
-                                     (const ptmi_light *)p[3], (uint32_t)(n[3] / stride[3]));
-    if (rc) return throw_multi(env, m, rc, "ptmi_multi_upload_scene");
+    CALL(env, h, upload_scene, (const ptmi_triangle *)p[0], (uint32_t)(n[0] / stride[0]),
+         (const ptmi_material *)p[1], (uint32_t)(n[1] / stride[1]),
+         (const ptmi_bvh_node *)p[2], (uint32_t)(n[2] / stride[2]),
+         (const ptmi_light *)p[3], (uint32_t)(n[3] / stride[3]));
     return NULL;
 }
 
-static napi_value js_multi_upload_atlas(napi_env env, napi_callback_info info) {
+static napi_value js_upload_atlas(napi_env env, napi_callback_info info) {
     napi_value argv[5];
-    if (!get_args(env, info, 5, argv)) return NULL;
-    ptmi_multi *m = get_multi(env, argv[0]);
-    if (!m) return NULL;
-    void *p; size_t n; uint32_t w = 0, h = 0; int32_t fmt = 0;
+    handle *h = get_handle(env, info, 5, argv);
+    if (!h) return NULL;
+    void *p; size_t n; uint32_t w = 0, hh = 0; int32_t fmt = 0;
     if (!get_bytes(env, argv[1], &p, &n)) return NULL;
-    napi_get_value_uint32(env, argv[2], &w); napi_get_value_uint32(env, argv[3], &h); napi_get_value_int32(env, argv[4], &fmt);
-    if (p && n < (size_t)w * h * (fmt == PTMI_ATLAS_RGBA16F ? 8 : 16)) { napi_throw_range_error(env, NULL, "atlas buffer too small"); return NULL; }
-    int rc = ptmi_multi_upload_atlas(m, p, w, h, fmt);
-    if (rc) return throw_multi(env, m, rc, "ptmi_multi_upload_atlas");
+    napi_get_value_uint32(env, argv[2], &w); napi_get_value_uint32(env, argv[3], &hh); napi_get_value_int32(env, argv[4], &fmt);
+    if (p && n < (size_t)w * hh * (fmt == PTMI_ATLAS_RGBA16F ? 8 : 16)) { napi_throw_range_error(env, NULL, "atlas buffer too small"); return NULL; }
+    CALL(env, h, upload_atlas, p, w, hh, fmt);
     return NULL;
 }
 
-static napi_value js_multi_resize(napi_env env, napi_callback_info info) {
+static napi_value js_resize(napi_env env, napi_callback_info info) {
     napi_value argv[3];
-    if (!get_args(env, info, 3, argv)) return NULL;
-    ptmi_multi *m = get_multi(env, argv[0]);
-    if (!m) return NULL;
-    uint32_t w = 0, h = 0;
-    napi_get_value_uint32(env, argv[1], &w); napi_get_value_uint32(env, argv[2], &h);
-    int rc = ptmi_multi_resize(m, w, h);
-    if (rc) return throw_multi(env, m, rc, "ptmi_multi_resize");
+    handle *h = get_handle(env, info, 3, argv);
+    if (!h) return NULL;
+    uint32_t w = 0, hh = 0;
+    napi_get_value_uint32(env, argv[1], &w); napi_get_value_uint32(env, argv[2], &hh);
+    CALL(env, h, resize, w, hh);
     return NULL;
 }
 
-static napi_value js_multi_set_options(napi_env env, napi_callback_info info) {
+/* setOptions(h, {maxBounces, doMis, ...}): JS option names -> ptmi_options; unset properties keep their current values */
+static napi_value js_set_options(napi_env env, napi_callback_info info) {
     napi_value argv[2];
-    if (!get_args(env, info, 2, argv)) return NULL;
-    ptmi_multi *m = get_multi(env, argv[0]);
-    if (!m) return NULL;
+    handle *h = get_handle(env, info, 2, argv);
+    if (!h) return NULL;
     ptmi_options o;
-    ptmi_multi_get_options(m, &o);
-    o.tile_parts = 0; o.tile_part = 0; o.tile_strip = 0;            /* dealt out by the library unless tileStrip says otherwise */
-    read_options(env, argv[1], &o);
-    int rc = ptmi_multi_set_options(m, &o);
-    if (rc) return throw_multi(env, m, rc, "ptmi_multi_set_options");
+    (void)RUN(h, get_options, &o);
+    /* several devices: the library deals out the rows, unless tileStrip says otherwise */
+    if (h->kind == KIND_MULTI) { o.tile_parts = 0; o.tile_part = 0; o.tile_strip = 0; }
+    napi_value js = argv[1];
+    o.max_bounces = get_u32_prop(env, js, "maxBounces", o.max_bounces);
+    o.do_mis = get_u32_prop(env, js, "doMis", o.do_mis);
+    o.tile_y0 = get_u32_prop(env, js, "tileY0", o.tile_y0);
+    o.tile_y1 = get_u32_prop(env, js, "tileY1", o.tile_y1);
+    o.frames_per_batch = get_u32_prop(env, js, "framesPerBatch", o.frames_per_batch);
+    o.traversal = get_u32_prop(env, js, "traversal", o.traversal);
+    o.cull = get_u32_prop(env, js, "cull", o.cull);
+    o.timing = get_u32_prop(env, js, "timing", o.timing);
+    o.keep_reference_tree = get_u32_prop(env, js, "keepReferenceTree", o.keep_reference_tree);
+    o.tile_parts = get_u32_prop(env, js, "tileParts", o.tile_parts);
+    o.tile_part = get_u32_prop(env, js, "tilePart", o.tile_part);
+    o.tile_strip = get_u32_prop(env, js, "tileStrip", o.tile_strip);
+    o.perf_mode = get_u32_prop(env, js, "perfMode", o.perf_mode);
+    o.overlap = get_u32_prop(env, js, "overlap", o.overlap);
+    o.tree_builder = get_u32_prop(env, js, "treeBuilder", o.tree_builder);
+    o.leaves = get_u32_prop(env, js, "leaves", o.leaves);
+    o.leaf_tris = get_u32_prop(env, js, "leafTris", o.leaf_tris);
+    CALL(env, h, set_options, &o);
     return NULL;
 }
 
-static napi_value js_multi_dispatch(napi_env env, napi_callback_info info) {
+static napi_value js_dispatch(napi_env env, napi_callback_info info) {
     napi_value argv[3];
-    if (!get_args(env, info, 3, argv)) return NULL;
-    ptmi_multi *m = get_multi(env, argv[0]);
-    if (!m) return NULL;
+    handle *h = get_handle(env, info, 3, argv);
+    if (!h) return NULL;
     void *p; size_t n; uint32_t frames = 1;
     if (!get_bytes(env, argv[1], &p, &n)) return NULL;
     if (!p || n != sizeof(ptmi_camera)) { napi_throw_range_error(env, NULL, "camera blob must be 96 bytes"); return NULL; }
     napi_get_value_uint32(env, argv[2], &frames);
     ptmi_camera cam;
     memcpy(&cam, p, sizeof cam);
-    int rc = ptmi_multi_dispatch(m, &cam, frames);
-    if (rc) return throw_multi(env, m, rc, "ptmi_multi_dispatch");
+    CALL(env, h, dispatch, &cam, frames);
     return NULL;
 }
 
-static napi_value js_multi_gather(napi_env env, napi_callback_info info) {
+/* gather(h): several devices assemble the frame on the first; one device has nothing to do */
+static napi_value js_gather(napi_env env, napi_callback_info info) {
     napi_value argv[1];
-    if (!get_args(env, info, 1, argv)) return NULL;
-    ptmi_multi *m = get_multi(env, argv[0]);
-    if (!m) return NULL;
-    int rc = ptmi_multi_gather(m);
-    if (rc) return throw_multi(env, m, rc, "ptmi_multi_gather");
+    handle *h = get_handle(env, info, 1, argv);
+    if (!h) return NULL;
+    int rc = h->kind == KIND_MULTI ? ptmi_multi_gather(h->m) : PTMI_OK;
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_multi_gather");
     return NULL;
 }
 
-static napi_value js_multi_synchronize(napi_env env, napi_callback_info info) {
+static napi_value js_synchronize(napi_env env, napi_callback_info info) {
     napi_value argv[1];
-    if (!get_args(env, info, 1, argv)) return NULL;
-    ptmi_multi *m = get_multi(env, argv[0]);
-    if (!m) return NULL;
-    int rc = ptmi_multi_synchronize(m);
-    if (rc) return throw_multi(env, m, rc, "ptmi_multi_synchronize");
+    handle *h = get_handle(env, info, 1, argv);
+    if (!h) return NULL;
+    CALL(env, h, synchronize);
     return NULL;
 }
 
-static napi_value js_multi_throttle(napi_env env, napi_callback_info info) {
+/* throttle(h, maxInFlight) -> dispatches still in flight (blocks until at most maxInFlight are) */
+static napi_value js_throttle(napi_env env, napi_callback_info info) {
     napi_value argv[2];
-    if (!get_args(env, info, 2, argv)) return NULL;
-    ptmi_multi *m = get_multi(env, argv[0]);
-    if (!m) return NULL;
+    handle *h = get_handle(env, info, 2, argv);
+    if (!h) return NULL;
     uint32_t max = 0, n = 0;
     napi_get_value_uint32(env, argv[1], &max);
-    int rc = ptmi_multi_throttle(m, max, &n);
-    if (rc) return throw_multi(env, m, rc, "ptmi_multi_throttle");
+    CALL(env, h, throttle, max, &n);
     napi_value v;
     NAPI_OK(env, napi_create_uint32(env, n, &v));
     return v;
 }
 
-static napi_value js_multi_read_output(napi_env env, napi_callback_info info) {
+/* readOutput(h, Float32Array dst) */
+static napi_value js_read_output(napi_env env, napi_callback_info info) {
     napi_value argv[2];
-    if (!get_args(env, info, 2, argv)) return NULL;
-    ptmi_multi *m = get_multi(env, argv[0]);
-    if (!m) return NULL;
+    handle *h = get_handle(env, info, 2, argv);
+    if (!h) return NULL;
     void *p; size_t n;
     if (!get_bytes(env, argv[1], &p, &n)) return NULL;
-    int rc = ptmi_multi_read_output(m, (float *)p, n / 4);
-    if (rc) return throw_multi(env, m, rc, "ptmi_multi_read_output");
+    CALL(env, h, read_output, (float *)p, n / 4);
     return argv[1];
 }
 
-static napi_value js_multi_write_output(napi_env env, napi_callback_info info) {
+static napi_value js_write_output(napi_env env, napi_callback_info info) {
     napi_value argv[2];
-    if (!get_args(env, info, 2, argv)) return NULL;
-    ptmi_multi *m = get_multi(env, argv[0]);
-    if (!m) return NULL;
+    handle *h = get_handle(env, info, 2, argv);
+    if (!h) return NULL;
     void *p; size_t n;
     if (!get_bytes(env, argv[1], &p, &n)) return NULL;
-    int rc = ptmi_multi_write_output(m, (const float *)p, n / 4);
-    if (rc) return throw_multi(env, m, rc, "ptmi_multi_write_output");
+    CALL(env, h, write_output, (const float *)p, n / 4);
     return NULL;
 }
 
-static napi_value js_multi_blit(napi_env env, napi_callback_info info) {
+/* get_handle for the AOV calls, which take one device's handle: nothing gathers the planes of several */
+static handle *get_single_handle(napi_env env, napi_callback_info info, size_t want, napi_value *argv, const char *what) {
+    handle *h = get_handle(env, info, want, argv);
+    if (h && h->kind == KIND_MULTI) {
+        char msg[128];
+        snprintf(msg, sizeof msg, "%s: AOV planes are not supported with several devices", what);
+        napi_throw_error(env, NULL, msg);
+        return NULL;
+    }
+    return h;
+}
+
+/* setAovs(h, mask): PTMI_AOV_* bits */
+static napi_value js_set_aovs(napi_env env, napi_callback_info info) {
     napi_value argv[2];
-    if (!get_args(env, info, 2, argv)) return NULL;
-    ptmi_multi *m = get_multi(env, argv[0]);
-    if (!m) return NULL;
+    handle *h = get_single_handle(env, info, 2, argv, "setAovs");
+    if (!h) return NULL;
+    uint32_t mask = 0;
+    napi_get_value_uint32(env, argv[1], &mask);
+    int rc = ptmi_set_aovs(h->ctx, mask);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_set_aovs");
+    return NULL;
+}
+
+/* readAov(h, which, dst typed array of width*height*16 (or *8 for PTMI_AOV_ID) bytes) */
+static napi_value js_read_aov(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    handle *h = get_single_handle(env, info, 3, argv, "readAov");
+    if (!h) return NULL;
+    uint32_t which = 0;
+    napi_get_value_uint32(env, argv[1], &which);
+    void *p; size_t n;
+    if (!get_bytes(env, argv[2], &p, &n)) return NULL;
+    int rc = ptmi_read_aov(h->ctx, which, p, n);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_read_aov");
+    return argv[2];
+}
+
+/* blit(h, Uint8Array dstRgba8) — the reference's blit pass (blit.wgsl) into an 8-bit canvas, row 0 = top */
+static napi_value js_blit(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    handle *h = get_handle(env, info, 2, argv);
+    if (!h) return NULL;
     void *p; size_t n;
     if (!get_bytes(env, argv[1], &p, &n)) return NULL;
     if (!p) { napi_throw_type_error(env, NULL, "expected a Uint8Array of width*height*4 bytes"); return NULL; }
-    uint32_t w = 0, h = 0;
-    int rc = ptmi_get_size(ptmi_multi_context(m, 0), &w, &h);
-    if (rc) return throw_multi(env, m, rc, "ptmi_get_size");
-    if (n != (size_t)w * h * 4) { napi_throw_range_error(env, NULL, "blit: the Uint8Array is not width*height*4 bytes"); return NULL; }
-    rc = ptmi_multi_blit(m, NULL, 0, (uint8_t *)p, n);
-    if (rc) return throw_multi(env, m, rc, "ptmi_multi_blit");
+    /* the library writes width*height*4 bytes: a short (or stale, after resize()) array must not reach it. Several devices
+     * blit on the first, whose size is the frame's. */
+    uint32_t w = 0, hh = 0;
+    int rc = ptmi_get_size(h->kind == KIND_MULTI ? ptmi_multi_context(h->m, 0) : h->ctx, &w, &hh);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_get_size");
+    if (n != (size_t)w * hh * 4) {
+        char msg[128];
+        snprintf(msg, sizeof msg, "blit: expected a Uint8Array of %zu bytes (%ux%ux4), got %zu", (size_t)w * hh * 4, w, hh, n);
+        napi_throw_range_error(env, NULL, msg);
+        return NULL;
+    }
+    CALL(env, h, blit, NULL, 0, (uint8_t *)p, n);
     return argv[1];
 }
 
-static napi_value js_multi_get_stats(napi_env env, napi_callback_info info) {
+static void set_num(napi_env env, napi_value obj, const char *k, double v) {
+    napi_value n;
+    if (napi_create_double(env, v, &n) == napi_ok) napi_set_named_property(env, obj, k, n);
+}
+
+/* getStats(h); several devices add gatherMs (once a gather has been timed) and devices */
+static napi_value js_get_stats(napi_env env, napi_callback_info info) {
     napi_value argv[1];
-    if (!get_args(env, info, 1, argv)) return NULL;
-    ptmi_multi *m = get_multi(env, argv[0]);
-    if (!m) return NULL;
+    handle *h = get_handle(env, info, 1, argv);
+    if (!h) return NULL;
     ptmi_stats s;
-    int rc = ptmi_multi_get_stats(m, &s);
-    if (rc) return throw_multi(env, m, rc, "ptmi_multi_get_stats");
-    napi_value o = stats_object(env, &s);
-    if (!o) return NULL;
-    double ms = -1.0;
-    if (ptmi_multi_gather_ms(m, &ms) == 0) set_num(env, o, "gatherMs", ms);
-    set_num(env, o, "devices", ptmi_multi_count(m));
+    CALL(env, h, get_stats, &s);
+    napi_value o;
+    NAPI_OK(env, napi_create_object(env, &o));
+    set_num(env, o, "paths", (double)s.paths); set_num(env, o, "segments", (double)s.segments);
+    set_num(env, o, "shadowRays", (double)s.shadow_rays); set_num(env, o, "frames", (double)s.frames);
+    set_num(env, o, "dispatches", (double)s.dispatches); set_num(env, o, "gpuMs", s.gpu_ms);
+    set_num(env, o, "extendMs", s.extend_ms); set_num(env, o, "shadeMs", s.shade_ms); set_num(env, o, "shadowMs", s.shadow_ms);
+    set_num(env, o, "shadowTraced", (double)s.shadow_traced); set_num(env, o, "uploadMs", s.upload_ms);
+    set_num(env, o, "bvhDepth", s.bvh_depth); set_num(env, o, "traversalUsed", s.traversal_used);
+    set_num(env, o, "framesPerBatchUsed", s.frames_per_batch_used);
+    set_num(env, o, "leavesUsed", s.leaves_used); set_num(env, o, "leafTrisUsed", s.leaf_tris_used);
+    set_num(env, o, "extendVariant", s.extend_variant); set_num(env, o, "shadowVariant", s.shadow_variant);
+    set_num(env, o, "verifyFailed", (double)s.verify_failed); set_num(env, o, "treeBuilderUsed", s.tree_builder_used);
+    if (h->kind == KIND_MULTI) {
+        double ms = -1.0;
+        if (ptmi_multi_gather_ms(h->m, &ms) == 0) set_num(env, o, "gatherMs", ms);
+        set_num(env, o, "devices", ptmi_multi_count(h->m));
+    }
     return o;
 }
 
-static napi_value js_multi_reset_stats(napi_env env, napi_callback_info info) {
+/* resetStats(h): the status is not reported */
+static napi_value js_reset_stats(napi_env env, napi_callback_info info) {
     napi_value argv[1];
-    if (!get_args(env, info, 1, argv)) return NULL;
-    ptmi_multi *m = get_multi(env, argv[0]);
-    if (m) ptmi_multi_reset_stats(m);
+    handle *h = get_handle(env, info, 1, argv);
+    if (!h) return NULL;
+    (void)RUN(h, reset_stats);
     return NULL;
 }
 
@@ -632,16 +473,12 @@ static napi_value js_abi_version(napi_env env, napi_callback_info info) {
 
 static napi_value init(napi_env env, napi_value exports) {
     static const struct { const char *name; napi_callback fn; } fns[] = {
-        {"abiVersion", js_abi_version}, {"create", js_create}, {"destroy", js_destroy},
-        {"uploadScene", js_upload_scene}, {"uploadAtlas", js_upload_atlas}, {"resize", js_resize},
-        {"setOptions", js_set_options}, {"dispatch", js_dispatch}, {"synchronize", js_synchronize}, {"throttle", js_throttle}, {"multiThrottle", js_multi_throttle},
-        {"readOutput", js_read_output}, {"writeOutput", js_write_output}, {"setAovs", js_set_aovs}, {"readAov", js_read_aov}, {"blit", js_blit}, {"getStats", js_get_stats},
-        {"resetStats", js_reset_stats}, {"buildBvh", js_build_bvh}, {"emissiveLights", js_emissive_lights},
-        {"multiCreate", js_multi_create}, {"multiDestroy", js_multi_destroy}, {"multiUploadScene", js_multi_upload_scene},
-        {"multiUploadAtlas", js_multi_upload_atlas}, {"multiResize", js_multi_resize}, {"multiSetOptions", js_multi_set_options},
-        {"multiDispatch", js_multi_dispatch}, {"multiGather", js_multi_gather}, {"multiSynchronize", js_multi_synchronize},
-        {"multiReadOutput", js_multi_read_output}, {"multiWriteOutput", js_multi_write_output}, {"multiBlit", js_multi_blit},
-        {"multiGetStats", js_multi_get_stats}, {"multiResetStats", js_multi_reset_stats},
+        {"abiVersion", js_abi_version}, {"create", js_create}, {"multiCreate", js_multi_create}, {"destroy", js_destroy},
+        {"uploadScene", js_upload_scene}, {"uploadAtlas", js_upload_atlas}, {"resize", js_resize}, {"setOptions", js_set_options},
+        {"dispatch", js_dispatch}, {"gather", js_gather}, {"synchronize", js_synchronize}, {"throttle", js_throttle},
+        {"readOutput", js_read_output}, {"writeOutput", js_write_output}, {"setAovs", js_set_aovs}, {"readAov", js_read_aov},
+        {"blit", js_blit}, {"getStats", js_get_stats}, {"resetStats", js_reset_stats},
+        {"buildBvh", js_build_bvh}, {"emissiveLights", js_emissive_lights},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

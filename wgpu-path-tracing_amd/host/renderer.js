@@ -33,24 +33,13 @@ function loadAddon() {
 
 var MAX_FRAMES = -1;                       // renderer.ts:16
 
-// the addon's single-device and multi-device entry points under one set of names
-function deviceApi(addon, devices, loopback) {
-  if (!devices) return { multi: false, create: function (d) { return addon.create(d); }, destroy: addon.destroy,
-    uploadScene: addon.uploadScene, uploadAtlas: addon.uploadAtlas, resize: addon.resize, setOptions: addon.setOptions,
-    dispatch: addon.dispatch, synchronize: addon.synchronize, throttle: addon.throttle, readOutput: addon.readOutput,
-    writeOutput: addon.writeOutput, blit: addon.blit, getStats: addon.getStats, gather: function () {} };
-  return { multi: true, create: function () { return addon.multiCreate(devices, loopback ? 1 : 0); }, destroy: addon.multiDestroy,
-    uploadScene: addon.multiUploadScene, uploadAtlas: addon.multiUploadAtlas, resize: addon.multiResize,
-    setOptions: addon.multiSetOptions, dispatch: addon.multiDispatch, synchronize: addon.multiSynchronize,
-    throttle: addon.multiThrottle, readOutput: addon.multiReadOutput, writeOutput: addon.multiWriteOutput, blit: addon.multiBlit,
-    getStats: addon.multiGetStats, gather: addon.multiGather };
-}
-
 function Renderer(options) {
   options = options || {};
   this.addon = loadAddon();
-  this.api = deviceApi(this.addon, options.devices, options.loopback);
-  this.ctx = this.api.create(options.device || 0);     // throws without a gfx950 device: there is no CPU path
+  this.api = this.addon;                                // the same functions under the name callers poll, e.g. api.throttle(ctx, n)
+  this.multi = !!options.devices;
+  // throws without a gfx950 device: there is no CPU path
+  this.ctx = this.multi ? this.addon.multiCreate(options.devices, options.loopback ? 1 : 0) : this.addon.create(options.device || 0);
   this.gatherEvery = options.gatherEvery || 0;          // several devices: assemble the frame every so many frames (0: when it is read)
   this.sinceGather = 0;
   this.maxFramesPerTick = options.maxFramesPerTick || 64;
@@ -64,8 +53,8 @@ function Renderer(options) {
   this.sceneLoaded = false;
   this.cameraBytes = new ArrayBuffer(pack.CAMERA_SIZE);
   this.setupCamera();
-  this.api.resize(this.ctx, this.width, this.height);
-  if (options.options) this.api.setOptions(this.ctx, options.options);
+  this.addon.resize(this.ctx, this.width, this.height);
+  if (options.options) this.addon.setOptions(this.ctx, options.options);
 }
 
 /** renderer.ts:136-150 */
@@ -99,9 +88,9 @@ Renderer.prototype.loadModel = function (model, atlas) {
     } else {
       blobs = pack.packScene(model);
     }
-    self.api.uploadScene(self.ctx, blobs.triangles, blobs.materials, blobs.bvhNodes, blobs.lights);
-    if (atlas) self.api.uploadAtlas(self.ctx, atlas.data, atlas.width, atlas.height, atlas.format || 1);
-    else self.api.uploadAtlas(self.ctx, null, 0, 0, 0);
+    self.addon.uploadScene(self.ctx, blobs.triangles, blobs.materials, blobs.bvhNodes, blobs.lights);
+    if (atlas) self.addon.uploadAtlas(self.ctx, atlas.data, atlas.width, atlas.height, atlas.format || 1);
+    else self.addon.uploadAtlas(self.ctx, null, 0, 0, 0);
     self.sceneLoaded = true;
     self.resetOutputBuffer(false);
     resolve();
@@ -126,11 +115,11 @@ Renderer.prototype.updateCamera = function () {
 Renderer.prototype.renderFrame = function (frames) {
   frames = frames || 1;
   this.updateCamera();
-  this.api.dispatch(this.ctx, this.cameraBytes, frames);
+  this.addon.dispatch(this.ctx, this.cameraBytes, frames);
   this.frameIndex += frames;
-  if (this.api.multi && this.gatherEvery > 0) {
+  if (this.multi && this.gatherEvery > 0) {
     this.sinceGather += frames;
-    if (this.sinceGather >= this.gatherEvery) { this.api.gather(this.ctx); this.sinceGather = 0; }
+    if (this.sinceGather >= this.gatherEvery) { this.addon.gather(this.ctx); this.sinceGather = 0; }
   }
 };
 
@@ -142,7 +131,7 @@ Renderer.prototype.start = function () {
     // Back-pressure without blocking the event loop (the reference's requestAnimationFrame loop never blocks: input events keep
     // flowing): POLL how many dispatches are unfinished and come back on the next turn of the loop while more than one is — at
     // most two in flight with the one a tick enqueues. A turn that only waits is not a tick: no update task runs.
-    if (self.sceneLoaded && self.api.throttle(self.ctx, 0xFFFFFFFF) > 1) {
+    if (self.sceneLoaded && self.addon.throttle(self.ctx, 0xFFFFFFFF) > 1) {
       self.throttledTurns = (self.throttledTurns || 0) + 1;
       if (self.timer !== null) self.timer = setImmediate(animate);
       return;
@@ -170,7 +159,7 @@ Renderer.prototype.stop = function () {
 /** renderer.ts:482-494 */
 Renderer.prototype.destroy = function () {
   this.stop();
-  if (this.ctx) { this.api.destroy(this.ctx); this.ctx = null; }
+  if (this.ctx) { this.addon.destroy(this.ctx); this.ctx = null; }
 };
 
 /** renderer.ts:496-510 */
@@ -180,7 +169,7 @@ Renderer.prototype.resize = function (width, height) {
   this.camera.width = width; this.camera.height = height;
   this.frameIndex = 0;
   this.framesPerTick = 1;
-  this.api.resize(this.ctx, width, height);
+  this.addon.resize(this.ctx, width, height);
 };
 
 /** renderer.ts:152-170 */
@@ -213,14 +202,14 @@ Renderer.prototype.rotateCamera = function (yaw, pitch) {
 /** Output buffer (binding 0): width*height float4, row 0 = image bottom. Synchronises. */
 Renderer.prototype.readOutput = function () {
   var out = new Float32Array(this.width * this.height * 4);
-  this.api.readOutput(this.ctx, out);
+  this.addon.readOutput(this.ctx, out);
   return out;
 };
 
 /** The reference's blit pass (renderer.ts:434-449, blit.wgsl): tone-mapped 8-bit canvas, row 0 = top. */
 Renderer.prototype.blit = function () {
   var out = new Uint8Array(this.width * this.height * 4);
-  this.api.blit(this.ctx, out);
+  this.addon.blit(this.ctx, out);
   return out;
 };
 
@@ -232,7 +221,7 @@ function aovBit(name) {
   return AOVS[name];
 }
 Renderer.prototype.setAovs = function (names) {
-  if (this.api.multi) throw new Error('setAovs: AOV planes are not supported with several devices');
+  if (this.multi) throw new Error('setAovs: AOV planes are not supported with several devices');
   var mask = 0;
   (names || []).forEach(function (n) { mask |= aovBit(n); });
   this.addon.setAovs(this.ctx, mask);
@@ -261,11 +250,11 @@ Renderer.prototype.pick = function (x, y) {
   return { triangle: ids[2 * i], material: ids[2 * i + 1], depth: depth };
 };
 
-Renderer.prototype.setOptions = function (o) { this.api.setOptions(this.ctx, o); };
-Renderer.prototype.getStats = function () { return this.api.getStats(this.ctx); };
+Renderer.prototype.setOptions = function (o) { this.addon.setOptions(this.ctx, o); };
+Renderer.prototype.getStats = function () { return this.addon.getStats(this.ctx); };
 /** several devices: assemble the frame on the first one now (readOutput / blit do it themselves) */
-Renderer.prototype.gather = function () { this.api.gather(this.ctx); this.sinceGather = 0; };
-Renderer.prototype.synchronize = function () { this.api.synchronize(this.ctx); };
+Renderer.prototype.gather = function () { this.addon.gather(this.ctx); this.sinceGather = 0; };
+Renderer.prototype.synchronize = function () { this.addon.synchronize(this.ctx); };
 
 /** renderer.ts:513-558 without the canvas: create, load, (optionally) start; options.input (an event source,
  *  see controller.js) gets a Controller whose update runs every frame, like renderer.ts:554-555 */

@@ -3,7 +3,9 @@
 No fallback: if the library or a gfx950 device is missing, `Context()` raises.
 """
 import ctypes
+import functools
 import os
+import types
 
 import numpy as np
 
@@ -74,6 +76,16 @@ class Stats(ctypes.Structure):
         return d
 
 
+# the calls both handle types have, with the same arguments after the handle: ptmi_X(ctx, ...) and ptmi_multi_X(m, ...)
+_SHARED = {
+    "destroy": [], "last_error": [], "synchronize": [], "reset_stats": [], "resize": [ctypes.c_uint32, ctypes.c_uint32],
+    "upload_scene": [ctypes.c_void_p, ctypes.c_uint32] * 4,
+    "upload_atlas": [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int],
+    "set_options": [ctypes.c_void_p], "get_options": [ctypes.c_void_p], "dispatch": [ctypes.c_void_p, ctypes.c_uint32],
+    "throttle": [ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)], "read_output": [ctypes.c_void_p, ctypes.c_size_t],
+    "write_output": [ctypes.c_void_p, ctypes.c_size_t], "blit": [ctypes.c_void_p, ctypes.c_size_t] * 2,
+    "get_stats": [ctypes.c_void_p],
+}
 _lib = None
 
 
@@ -84,60 +96,34 @@ def load():
         if not os.path.exists(LIB_PATH):
             raise PtmiError(-2, f"{LIB_PATH} is missing: build it with `python __graft_entry__.py build`")
         L = ctypes.CDLL(LIB_PATH)
-        L.ptmi_last_error.restype = ctypes.c_char_p
-        L.ptmi_last_error.argtypes = [ctypes.c_void_p]
-        L.ptmi_output_device_ptr.restype = ctypes.c_void_p
-        L.ptmi_output_device_ptr.argtypes = [ctypes.c_void_p]
-        L.ptmi_create.argtypes = [ctypes.c_int, ctypes.c_void_p]
         for name in EXPORTS:
             getattr(L, name)
+        if L.ptmi_abi_version() != ABI_VERSION:
+            raise PtmiError(-1, f"{LIB_PATH} has ABI {L.ptmi_abi_version()}, this binding expects {ABI_VERSION}: rebuild it")
         vp, u32, sz = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_size_t
-        L.ptmi_destroy.argtypes = [vp]
-        L.ptmi_upload_scene.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, u32]
-        L.ptmi_upload_atlas.argtypes = [vp, vp, u32, u32, ctypes.c_int]
-        L.ptmi_resize.argtypes = [vp, u32, u32]
-        L.ptmi_set_options.argtypes = [vp, vp]
-        L.ptmi_get_options.argtypes = [vp, vp]
-        L.ptmi_dispatch.argtypes = [vp, vp, u32]
-        L.ptmi_synchronize.argtypes = [vp]
-        L.ptmi_read_output.argtypes = [vp, vp, sz]
-        L.ptmi_write_output.argtypes = [vp, vp, sz]
+        for prefix in ("ptmi_", "ptmi_multi_"):
+            for name, args in _SHARED.items():
+                getattr(L, prefix + name).argtypes = [vp] + args
+        L.ptmi_last_error.restype = L.ptmi_multi_last_error.restype = ctypes.c_char_p
+        L.ptmi_create.argtypes = [ctypes.c_int, vp]
+        L.ptmi_output_device_ptr.restype = vp
+        L.ptmi_output_device_ptr.argtypes = [vp]
         L.ptmi_bind_output_device.argtypes = [vp, vp, sz]
         L.ptmi_set_stream.argtypes = [vp, vp]
-        L.ptmi_blit.argtypes = [vp, vp, sz, vp, sz]
         L.ptmi_get_size.argtypes = [vp, vp, vp]
         L.ptmi_debug_image_stats.argtypes = [vp, u32, vp, u32, vp]
         L.ptmi_debug_build_image.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp, vp, vp]
         L.ptmi_debug_read_image.argtypes = [vp, vp, vp, vp, vp, vp]
-        if L.ptmi_abi_version() != ABI_VERSION:
-            raise PtmiError(-1, f"{LIB_PATH} has ABI {L.ptmi_abi_version()}, this binding expects {ABI_VERSION}: rebuild it")
-        L.ptmi_get_stats.argtypes = [vp, vp]
-        L.ptmi_reset_stats.argtypes = [vp]
         L.ptmi_debug_raygen.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp, vp]
         L.ptmi_debug_intersect.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
         L.ptmi_debug_occluded.argtypes = [vp, u32, vp, vp, vp, vp]
         L.ptmi_debug_math.argtypes = [vp, ctypes.c_int, u32, vp, vp, vp, vp]
         L.ptmi_debug_exact_math.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
-        L.ptmi_throttle.argtypes = [vp, u32, ctypes.POINTER(ctypes.c_uint32)]
-        L.ptmi_multi_throttle.argtypes = [vp, u32, ctypes.POINTER(ctypes.c_uint32)]
-        L.ptmi_multi_last_error.restype = ctypes.c_char_p
-        L.ptmi_multi_last_error.argtypes = [vp]
-        L.ptmi_multi_context.restype = vp
-        L.ptmi_multi_context.argtypes = [vp, ctypes.c_int]
         L.ptmi_multi_create.argtypes = [ctypes.c_int, vp, u32, vp]
         L.ptmi_multi_count.argtypes = [vp]
-        for name in ("destroy", "gather", "synchronize", "reset_stats"):
-            getattr(L, "ptmi_multi_" + name).argtypes = [vp]
-        L.ptmi_multi_upload_scene.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, u32]
-        L.ptmi_multi_upload_atlas.argtypes = [vp, vp, u32, u32, ctypes.c_int]
-        L.ptmi_multi_resize.argtypes = [vp, u32, u32]
-        L.ptmi_multi_set_options.argtypes = [vp, vp]
-        L.ptmi_multi_get_options.argtypes = [vp, vp]
-        L.ptmi_multi_dispatch.argtypes = [vp, vp, u32]
-        L.ptmi_multi_read_output.argtypes = [vp, vp, sz]
-        L.ptmi_multi_write_output.argtypes = [vp, vp, sz]
-        L.ptmi_multi_blit.argtypes = [vp, vp, sz, vp, sz]
-        L.ptmi_multi_get_stats.argtypes = [vp, vp]
+        L.ptmi_multi_context.restype = vp
+        L.ptmi_multi_context.argtypes = [vp, ctypes.c_int]
+        L.ptmi_multi_gather.argtypes = [vp]
         L.ptmi_multi_gather_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
         L.ptmi_set_aovs.argtypes = [vp, u32]
         L.ptmi_get_aovs.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32)]
@@ -212,26 +198,34 @@ def _aov(name):
     return AOVS[name]
 
 
-class Context:
-    """One device context = the reference Renderer's GPU resources (bind group 0)."""
+class _Handle:
+    """What Context and MultiContext share. self._c holds the calls both C handle types have (_SHARED), bound once by the
+    class's prefix: self._c.resize is ptmi_resize for a Context and ptmi_multi_resize for a MultiContext."""
 
-    def __init__(self, device=0):
+    _prefix = None
+
+    def __init__(self, *create_args):
         self.L = load()
+        c = self._c
         h = ctypes.c_void_p()
-        rc = self.L.ptmi_create(device, ctypes.byref(h))
+        rc = getattr(self.L, self._prefix + "create")(*create_args, ctypes.byref(h))
         if rc != 0:
-            raise PtmiError(rc, self.L.ptmi_last_error(None).decode())
+            raise PtmiError(rc, c.last_error(None).decode())
         self.h = h
         self.width = self.height = 0
         self._uploaded_tris = 0
 
+    @functools.cached_property
+    def _c(self):
+        return types.SimpleNamespace(**{name: getattr(self.L, self._prefix + name) for name in _SHARED})
+
     def _ck(self, rc):
         if rc != 0:
-            raise PtmiError(rc, self.L.ptmi_last_error(self.h).decode())
+            raise PtmiError(rc, self._c.last_error(self.h).decode())
 
     def close(self):
         if getattr(self, "h", None):
-            self.L.ptmi_destroy(self.h)
+            self._c.destroy(self.h)
             self.h = None
 
     __del__ = close
@@ -247,57 +241,77 @@ class Context:
         for a, dt in ((scene.tris, layout.TRIANGLE), (scene.mats, layout.MATERIAL),
                       (scene.nodes, layout.BVH_NODE), (scene.lights, layout.LIGHT)):
             assert a.dtype == dt and a.flags.c_contiguous
-        self._ck(self.L.ptmi_upload_scene(self.h, _p(scene.tris), len(scene.tris), _p(scene.mats), len(scene.mats),
-                                          _p(scene.nodes), len(scene.nodes), _p(scene.lights), len(scene.lights)))
+        self._ck(self._c.upload_scene(self.h, _p(scene.tris), len(scene.tris), _p(scene.mats), len(scene.mats),
+                                      _p(scene.nodes), len(scene.nodes), _p(scene.lights), len(scene.lights)))
         self._uploaded_tris = len(scene.tris)
         a = scene.atlas
         if a is None:
-            self._ck(self.L.ptmi_upload_atlas(self.h, None, 0, 0, 0))
+            self._ck(self._c.upload_atlas(self.h, None, 0, 0, 0))
         else:
             assert a.ndim == 3 and a.shape[2] == 4 and a.flags.c_contiguous
             fmt = ATLAS_RGBA16F if a.dtype == np.float16 else ATLAS_RGBA32F
-            self._ck(self.L.ptmi_upload_atlas(self.h, _p(a), a.shape[1], a.shape[0], fmt))
+            self._ck(self._c.upload_atlas(self.h, _p(a), a.shape[1], a.shape[0], fmt))
 
     def resize(self, width, height):
-        self._ck(self.L.ptmi_resize(self.h, width, height))
+        self._ck(self._c.resize(self.h, width, height))
         self.width, self.height = width, height
 
+    def _before_set_options(self, o, kw):
+        """set_options starts from the current options o, adjusted here before the keywords kw are applied"""
+
     def set_options(self, **kw):
-        o = Options()
-        self._ck(self.L.ptmi_get_options(self.h, ctypes.byref(o)))
+        o = self.options()
+        self._before_set_options(o, kw)
         for k, v in kw.items():
             if not hasattr(o, k):
                 raise TypeError(f"unknown option {k}")
             setattr(o, k, int(v))
-        self._ck(self.L.ptmi_set_options(self.h, ctypes.byref(o)))
+        self._ck(self._c.set_options(self.h, ctypes.byref(o)))
 
     def options(self):
         o = Options()
-        self._ck(self.L.ptmi_get_options(self.h, ctypes.byref(o)))
+        self._ck(self._c.get_options(self.h, ctypes.byref(o)))
         return o
 
     # -- the compute pass ------------------------------------------------------
     def dispatch(self, camera, n_frames=1):
         assert camera.dtype == layout.CAMERA
-        self._ck(self.L.ptmi_dispatch(self.h, _p(camera), n_frames))
+        self._ck(self._c.dispatch(self.h, _p(camera), n_frames))
 
     def synchronize(self):
-        self._ck(self.L.ptmi_synchronize(self.h))
+        self._ck(self._c.synchronize(self.h))
 
     def throttle(self, max_in_flight=0xFFFFFFFF):
         """Blocks until at most max_in_flight dispatches are unfinished (default: only polls); returns how many are."""
         n = ctypes.c_uint32(0)
-        self._ck(self.L.ptmi_throttle(self.h, max_in_flight, ctypes.byref(n)))
+        self._ck(self._c.throttle(self.h, max_in_flight, ctypes.byref(n)))
         return int(n.value)
 
     def read_output(self):
         out = np.empty((self.height, self.width, 4), np.float32)
-        self._ck(self.L.ptmi_read_output(self.h, _p(out), out.size))
+        self._ck(self._c.read_output(self.h, _p(out), out.size))
         return out
 
     def write_output(self, arr):
         arr = np.ascontiguousarray(arr, np.float32)
-        self._ck(self.L.ptmi_write_output(self.h, _p(arr), arr.size))
+        self._ck(self._c.write_output(self.h, _p(arr), arr.size))
+
+    def stats(self):
+        s = Stats()
+        self._ck(self._c.get_stats(self.h, ctypes.byref(s)))
+        return s
+
+    def reset_stats(self):
+        self._ck(self._c.reset_stats(self.h))
+
+
+class Context(_Handle):
+    """One device context = the reference Renderer's GPU resources (bind group 0)."""
+
+    _prefix = "ptmi_"
+
+    def __init__(self, device=0):
+        super().__init__(device)
 
     def output_device_ptr(self):
         return self.L.ptmi_output_device_ptr(self.h)
@@ -314,14 +328,6 @@ class Context:
         b = np.empty((self.height, self.width, 4), np.uint8) if want_rgba8 else None
         self._ck(self.L.ptmi_blit(self.h, _p(f), 0 if f is None else f.size, _p(b), 0 if b is None else b.size))
         return f, b
-
-    def stats(self):
-        s = Stats()
-        self._ck(self.L.ptmi_get_stats(self.h, ctypes.byref(s)))
-        return s
-
-    def reset_stats(self):
-        self._ck(self.L.ptmi_reset_stats(self.h))
 
     # -- first-hit planes (include/ptmi.h ptmi_set_aovs) ----------------------------
     def set_aovs(self, *planes):
@@ -391,50 +397,22 @@ class Context:
         return int(n.value), int(first.value)
 
 
-class MultiContext:
+class MultiContext(_Handle):
     """Several devices of one node behind one handle (include/ptmi.h ptmi_multi_*): the frame's rows are dealt out as
     interleaved strips, every device accumulates its own, gather() assembles the frame on the first device through RCCL.
     loopback=True replaces the collective with device-to-device copies, so that one device can stand in for several."""
 
+    _prefix = "ptmi_multi_"
+
     def __init__(self, devices, loopback=False):
-        self.L = load()
-        devs = (ctypes.c_int * len(devices))(*devices)
-        h = ctypes.c_void_p()
-        rc = self.L.ptmi_multi_create(len(devices), devs, MULTI_LOOPBACK if loopback else 0, ctypes.byref(h))
-        if rc != 0:
-            raise PtmiError(rc, self.L.ptmi_multi_last_error(None).decode())
-        self.h = h
+        super().__init__(len(devices), (ctypes.c_int * len(devices))(*devices), MULTI_LOOPBACK if loopback else 0)
         self.n = len(devices)
-        self.width = self.height = 0
-        self._uploaded_tris = 0
 
-    def _ck(self, rc):
-        if rc != 0:
-            raise PtmiError(rc, self.L.ptmi_multi_last_error(self.h).decode())
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.ptmi_multi_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def upload_scene(self, scene):
-        self._ck(self.L.ptmi_multi_upload_scene(self.h, _p(scene.tris), len(scene.tris), _p(scene.mats), len(scene.mats),
-                                                _p(scene.nodes), len(scene.nodes), _p(scene.lights), len(scene.lights)))
-        self._uploaded_tris = len(scene.tris)
-        a = scene.atlas
-        if a is None:
-            self._ck(self.L.ptmi_multi_upload_atlas(self.h, None, 0, 0, 0))
-        else:
-            fmt = ATLAS_RGBA16F if a.dtype == np.float16 else ATLAS_RGBA32F
-            self._ck(self.L.ptmi_multi_upload_atlas(self.h, _p(a), a.shape[1], a.shape[0], fmt))
+    def _before_set_options(self, o, kw):
+        """the library deals out the rows: no tile of the caller's, and the automatic strip height unless kw names one"""
+        o.tile_parts = o.tile_part = 0
+        if "tile_strip" not in kw:
+            o.tile_strip = 0
 
     def read_image(self, i):
         """Context.read_image of device i's context (ptmi_multi_context)"""
@@ -445,58 +423,13 @@ class MultiContext:
                 raise PtmiError(rc, self.L.ptmi_last_error(h).decode())
         return _read_image(self.L, h, self._uploaded_tris, ck)
 
-    def resize(self, width, height):
-        self._ck(self.L.ptmi_multi_resize(self.h, width, height))
-        self.width, self.height = width, height
-
-    def set_options(self, **kw):
-        o = Options()
-        self._ck(self.L.ptmi_multi_get_options(self.h, ctypes.byref(o)))
-        o.tile_parts = o.tile_part = 0
-        if "tile_strip" not in kw:
-            o.tile_strip = 0
-        for k, v in kw.items():
-            if not hasattr(o, k):
-                raise TypeError(f"unknown option {k}")
-            setattr(o, k, int(v))
-        self._ck(self.L.ptmi_multi_set_options(self.h, ctypes.byref(o)))
-
-    def options(self):
-        o = Options()
-        self._ck(self.L.ptmi_multi_get_options(self.h, ctypes.byref(o)))
-        return o
-
-    def dispatch(self, camera, n_frames=1):
-        assert camera.dtype == layout.CAMERA
-        self._ck(self.L.ptmi_multi_dispatch(self.h, _p(camera), n_frames))
-
     def gather(self):
         self._ck(self.L.ptmi_multi_gather(self.h))
-
-    def synchronize(self):
-        self._ck(self.L.ptmi_multi_synchronize(self.h))
-
-    def read_output(self):
-        out = np.empty((self.height, self.width, 4), np.float32)
-        self._ck(self.L.ptmi_multi_read_output(self.h, _p(out), out.size))
-        return out
-
-    def write_output(self, arr):
-        arr = np.ascontiguousarray(arr, np.float32)
-        self._ck(self.L.ptmi_multi_write_output(self.h, _p(arr), arr.size))
 
     def blit(self):
         b = np.empty((self.height, self.width, 4), np.uint8)
         self._ck(self.L.ptmi_multi_blit(self.h, None, 0, _p(b), b.size))
         return b
-
-    def stats(self):
-        s = Stats()
-        self._ck(self.L.ptmi_multi_get_stats(self.h, ctypes.byref(s)))
-        return s
-
-    def reset_stats(self):
-        self._ck(self.L.ptmi_multi_reset_stats(self.h))
 
     def gather_ms(self):
         ms = ctypes.c_double(-1.0)
