@@ -220,6 +220,48 @@ int ptmi_read_aov(ptmi_ctx *ctx, uint32_t which, void *dst, size_t n_bytes);
 /* the plane's device address for zero-copy consumers (a denoiser on the same device); NULL when that plane is off */
 void *ptmi_aov_device_ptr(ptmi_ctx *ctx, uint32_t which);
 
+/* ---- sample moments and the denoiser (an SVGF-style a-trous filter over the first-hit planes) -------------------------------
+ * The sample-moments plane is off by default. While on, every dispatch also folds per pixel, in the output buffer's frame order and
+ * with its fold rule (frame 0 overwrites, frame f > 0 mixes with weight 1 / (f + 1)), a float4:
+ *   x = mean of l, y = mean of l^2, z = frames folded (frame + 1 of the last one), w = 0,
+ * with l = 0.2126 r + 0.7152 g + 0.0722 b of exactly the clamped per-frame radiance the output buffer folds. The variance of the
+ * mean is then max(0, y - x^2) / max(z, 1). The radiance keeps its bits with the plane on. Its life cycle is an AOV plane's: turning
+ * it on allocates it zero-filled (a plane turned on after accumulation has started mixes with those zeros until the next frame-0
+ * dispatch), ptmi_resize re-allocates it zero-filled, only the rows this context renders are written, a failed call keeps the
+ * previous state. It is not a PTMI_AOV_* bit. Cost while on: one more pass per batch, no per-path memory. */
+/* on: 0 or 1 (else PTMI_E_INVALID). Synchronises. */
+int ptmi_set_moments(ptmi_ctx *ctx, uint32_t on);
+int ptmi_get_moments(const ptmi_ctx *ctx, uint32_t *on);
+/* n_floats: width*height*4, else PTMI_E_INVALID; the plane off (or before ptmi_resize): PTMI_E_STATE. Synchronises. */
+int ptmi_read_moments(ptmi_ctx *ctx, float *dst, size_t n_floats);
+/* NULL while the plane is off */
+void *ptmi_moments_device_ptr(ptmi_ctx *ctx);
+
+/* ptmi_denoise filters the whole width x height output buffer with an edge-avoiding a-trous wavelet (Dammertz et al. 2010) whose
+ * colour weight is scaled by the moments plane's variance (Schied et al. 2017, spatial part only), guided by the NORMAL plane
+ * (normal and depth) and, when demodulating, the ALBEDO plane. It needs the NORMAL and the moments planes on (else PTMI_E_STATE)
+ * and writes a context-owned width*height float4 plane, (rgb, 0) in the output buffer's layout; the output buffer and the other
+ * planes are not written. It is not on the parity path: its contract is a tolerance against tests/denoise_ref.py. The variance
+ * estimate shrinks as frames accumulate, so the filter backs off as the image converges. Over a ptmi_multi, each context holds only
+ * its own strips of the planes: nothing gathers them, and a context's denoise sees only its own rows. */
+typedef struct ptmi_denoise_params {
+    uint32_t iterations;   /* a-trous passes, step 2^i pixels for pass i; 1..10; 0 -> 5 */
+    uint32_t demodulate;   /* 0: on iff the ALBEDO plane is on; 1: never; 2: always (ALBEDO off -> PTMI_E_STATE) */
+    float    phi_color;    /* luminance edge-stopping, in standard deviations; 0 -> 4 */
+    float    phi_normal;   /* exponent on the normals' dot product; 0 -> 128 */
+    float    phi_depth;    /* depth edge-stopping, in units of the local depth gradient; 0 -> 1 */
+    uint32_t reserved[3];  /* must be 0 */
+} ptmi_denoise_params;
+/* params NULL: the defaults. A negative or non-finite phi, iterations > 10, an unknown demodulate, a non-zero reserved word or (with
+ * dst_rgba) n_floats != width*height*4: PTMI_E_INVALID; before ptmi_resize: PTMI_E_STATE. dst_rgba NULL: asynchronous on the
+ * context's stream (read the result through ptmi_denoised_device_ptr after ptmi_synchronize); else synchronises and copies the
+ * width*height float4 result out. */
+int ptmi_denoise(ptmi_ctx *ctx, const ptmi_denoise_params *params, float *dst_rgba, size_t n_floats);
+/* the denoised plane's device address; NULL before the first ptmi_denoise since the last ptmi_resize */
+void *ptmi_denoised_device_ptr(ptmi_ctx *ctx);
+/* ptmi_blit's contract, on the denoised plane (PTMI_E_STATE before the first ptmi_denoise since the last ptmi_resize) */
+int ptmi_blit_denoised(ptmi_ctx *ctx, float *dst_rgba_f32, size_t n_floats, uint8_t *dst_rgba8, size_t n_bytes);
+
 /* ---- presentation (the reference's blit pass, src/shader/blit.wgsl:43-155; renderer.ts:434-449) ---- */
 /* Tone-maps the output buffer (exposure 2^1, AgX, gamma 1/2.2) into a width*height canvas, row 0 = top.
  * dst_rgba_f32 (n_floats must be width*height*4, alpha 1) and/or dst_rgba8 (n_bytes must be width*height*4);

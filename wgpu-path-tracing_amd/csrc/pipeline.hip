@@ -242,6 +242,34 @@ __global__ __launch_bounds__(BLOCK) void k_accumulate_aov(DevBand band, uint32_t
     }
 }
 
+// The sample-moments plane (ptmi_set_moments) from the same clamped per-frame radiance k_accumulate folds: per pixel
+// (mean of l, mean of l^2, frames folded, 0) with l = 0.2126 r + 0.7152 g + 0.0722 b (left to right, no FMA), the means following
+// the output buffer's fold (frame 0 overwrites, frame f > 0 mixes with weight 1 / (f + 1)).
+__global__ __launch_bounds__(BLOCK) void k_accumulate_moments(DevBand band, uint32_t frame0, uint32_t n_frames,
+                                                              const float *__restrict__ L, uint32_t l_stride,
+                                                              float4 *__restrict__ mom) {
+    const uint32_t npix = band.rows * band.width;
+    for (uint32_t pix = blockIdx.x * BLOCK + threadIdx.x; pix < npix; pix += gridDim.x * BLOCK) {
+        const size_t oi = (size_t)band.row_of(pix / band.width) * band.width + pix % band.width;
+        float4 acc = mom[oi];
+        for (uint32_t k = 0; k < n_frames; k++) {
+            const size_t li = (size_t)k * npix + pix;
+            rgb_sc l;
+            if (l_stride == 4u) { const float4 v = reinterpret_cast<const float4 *>(L)[li]; l = rgb_sc{v.x, v.y, v.z}; }
+            else l = reinterpret_cast<const rgb_sc *>(L)[li];
+            const float lum = 0.2126f * min1(l.x, 2.5f) + 0.7152f * min1(l.y, 2.5f) + 0.0722f * min1(l.z, 2.5f);
+            float m1 = lum, m2 = lum * lum;
+            const uint32_t frame = frame0 + k;
+            if (frame > 0u) {
+                const float t = 1.0f / (float)(frame + 1u);
+                m1 = mix1(acc.x, m1, t); m2 = mix1(acc.y, m2, t);
+            }
+            acc = make_float4(m1, m2, (float)(frame + 1u), 0.0f);
+        }
+        mom[oi] = acc;
+    }
+}
+
 // ---- multi-GPU gather (ptmi_multi_gather): a device's rows (DevBand: the strips part, part + parts, ...) <-> one contiguous
 // buffer of band.rows x width float4, local row l of the buffer = frame row band.row_of(l)
 __global__ __launch_bounds__(BLOCK) void k_pack_rows(DevBand band, const float4 *__restrict__ frame, float4 *__restrict__ packed) {
@@ -388,6 +416,10 @@ void pt_launch_accumulate_aov(hipStream_t s, int blocks, DevBand band, uint32_t 
                               const ptmi_triangle *tris, uint32_t n_tris, float4 *albedo, float4 *normal, uint2 *ids) {
     hipLaunchKernelGGL(k_accumulate_aov, dim3(blocks), dim3(BLOCK), 0, s, band, frame0, n_frames, rec, tris, n_tris, albedo, normal,
                        ids);
+}
+void pt_launch_accumulate_moments(hipStream_t s, int blocks, DevBand band, uint32_t frame0, uint32_t n_frames, const float *L,
+                                  uint32_t l_stride, float4 *mom) {
+    hipLaunchKernelGGL(k_accumulate_moments, dim3(blocks), dim3(BLOCK), 0, s, band, frame0, n_frames, L, l_stride, mom);
 }
 void pt_launch_pack_rows(hipStream_t s, int blocks, DevBand band, const float4 *frame, float4 *packed) {
     hipLaunchKernelGGL(k_pack_rows, dim3(blocks), dim3(BLOCK), 0, s, band, frame, packed);

@@ -224,6 +224,17 @@ void pt_launch_accumulate(hipStream_t s, int blocks, DevBand band, uint32_t fram
 // a NULL plane is not written
 void pt_launch_accumulate_aov(hipStream_t s, int blocks, DevBand band, uint32_t frame0, uint32_t n_frames, const float4 *rec,
                               const ptmi_triangle *tris, uint32_t n_tris, float4 *albedo, float4 *normal, uint2 *ids);
+// the sample-moments plane (ptmi_set_moments) from the batch's per-path radiance, frames in ascending order like pt_launch_accumulate
+void pt_launch_accumulate_moments(hipStream_t s, int blocks, DevBand band, uint32_t frame0, uint32_t n_frames, const float *L,
+                                  uint32_t l_stride, float4 *mom);
+// the denoiser (denoise.hip, ptmi_denoise): a prepass into guide / grad / cv, then `iterations` a-trous passes ping-ponging between
+// cv and tmp, the last remodulating into out. albedo NULL: no demodulation. cv is overwritten.
+struct DenoiseArgs {
+    uint32_t W, H, iterations;
+    float phi_color, phi_normal, phi_depth;
+};
+void pt_launch_denoise(hipStream_t s, const DenoiseArgs &a, const float4 *radiance, const float4 *normal, const float4 *albedo,
+                       const float4 *moments, float4 *guide, float *grad, float4 *cv, float4 *tmp, float4 *out);
 void pt_launch_blit(hipStream_t s, int blocks, uint32_t W, uint32_t H, const float4 *color, float4 *out_f32,
                     uint32_t *out_rgba8);
 // a device's rows of the frame <-> a contiguous buffer (ptmi_multi_gather)

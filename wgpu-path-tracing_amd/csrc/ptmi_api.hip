@@ -83,6 +83,13 @@ struct ptmi_ctx {
     uint32_t aov_mask = 0;
     float4 *d_aov_albedo = nullptr, *d_aov_normal = nullptr;
     uint2 *d_aov_id = nullptr;
+    // sample-moments plane (ptmi_set_moments): W x H float4, present while on and the output buffer exists
+    bool moments_on = false;
+    float4 *d_moments = nullptr;
+    // the denoiser's planes (ptmi_denoise), W x H each, made by its first call after a resize: guide (unit normal, depth), depth
+    // gradient, two ping-pong colour + variance planes, and the result
+    float4 *d_dn_guide = nullptr, *d_dn_a = nullptr, *d_dn_b = nullptr, *d_dn_out = nullptr;
+    float *d_dn_grad = nullptr;
 
     unsigned long long *d_stats = nullptr;
     float4 *d_blit_f32 = nullptr; uint32_t *d_blit_u8 = nullptr; size_t blit_px = 0;   // canvas staging of ptmi_blit, kept between calls
@@ -683,6 +690,26 @@ int alloc_aov_planes(ptmi_ctx *c, uint32_t mask, bool fresh) {
     return PTMI_OK;
 }
 
+// The sample-moments plane at the output buffer's size, zero-filled; nothing is changed if that fails.
+int alloc_moments(ptmi_ctx *c) {
+    const size_t bytes = (size_t)c->W * c->H * 16;
+    if (bytes == 0) return PTMI_OK;
+    void *p = nullptr;
+    hipError_t e = hipMalloc(&p, bytes);
+    if (e == hipSuccess) e = hipMemset(p, 0, bytes);
+    if (e != hipSuccess) {
+        dfree(p);
+        (void)hipGetLastError();
+        return fail(c, PTMI_E_HIP, "allocation of the %zu-byte moments plane failed: %s", bytes, hipGetErrorString(e));
+    }
+    c->d_moments = static_cast<float4 *>(p);
+    return PTMI_OK;
+}
+
+void free_denoise(ptmi_ctx *c) {
+    dfree(c->d_dn_guide); dfree(c->d_dn_grad); dfree(c->d_dn_a); dfree(c->d_dn_b); dfree(c->d_dn_out);
+}
+
 int check_ready(ptmi_ctx *c, bool need_output) {
     if (!c) return PTMI_E_INVALID;
     if (!c->have_scene) return fail(c, PTMI_E_STATE, "no scene uploaded (ptmi_upload_scene)");
@@ -801,6 +828,7 @@ int ptmi_destroy(ptmi_ctx *c) {
     for (void *&p : c->buf) dfree(p);
     dfree(c->d_atlas);
     dfree(c->d_out_own); dfree(c->d_aov_albedo); dfree(c->d_aov_normal); dfree(c->d_aov_id); dfree(c->d_stats); dfree(c->d_scene); dfree(c->d_blit_f32); dfree(c->d_blit_u8);
+    dfree(c->d_moments); free_denoise(c);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
     return PTMI_OK;
@@ -989,7 +1017,11 @@ int ptmi_resize(ptmi_ctx *c, uint32_t w, uint32_t h) {
     HIP_TRY(c, hipMalloc(&c->d_out_own, bytes));
     HIP_TRY(c, hipMemset(c->d_out_own, 0, bytes));
     c->d_out = c->d_out_own; c->W = w; c->H = h;
-    return alloc_aov_planes(c, c->aov_mask, true);
+    free_denoise(c);
+    dfree(c->d_moments);                         // never left at the old size
+    int rc = alloc_aov_planes(c, c->aov_mask, true);
+    if (rc == PTMI_OK && c->moments_on) rc = alloc_moments(c);
+    return rc;
 }
 
 int ptmi_set_options(ptmi_ctx *c, const ptmi_options *o) {
@@ -1132,7 +1164,8 @@ int ptmi_dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames) {
               pt_launch_accumulate(ms, blocks, band, frame0, fb, bp.L, bp.l_stride, c->d_out);
               if (aov_rec)
                   pt_launch_accumulate_aov(ms, blocks, band, frame0, fb, aov_rec, c->sc.tris, c->sc.n_tris, c->d_aov_albedo,
-                                           c->d_aov_normal, c->d_aov_id); }
+                                           c->d_aov_normal, c->d_aov_id);
+              if (c->d_moments) pt_launch_accumulate_moments(ms, blocks, band, frame0, fb, bp.L, bp.l_stride, c->d_moments); }
         }
     }
     HIP_TRY(c, hipGetLastError());
@@ -1206,9 +1239,9 @@ int ptmi_set_stream(ptmi_ctx *c, void *s) {
     return PTMI_OK;
 }
 
-int ptmi_blit(ptmi_ctx *c, float *dst_f32, size_t n_floats, uint8_t *dst_rgba8, size_t n_bytes) {
-    if (!c) return PTMI_E_INVALID;
-    if (!c->d_out) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
+namespace {
+// ptmi_blit's contract for any W x H float4 plane of the context
+int blit_plane(ptmi_ctx *c, const float4 *src, float *dst_f32, size_t n_floats, uint8_t *dst_rgba8, size_t n_bytes) {
     if (!dst_f32 && !dst_rgba8) return PTMI_OK;
     const size_t n = (size_t)c->W * c->H;
     if (dst_f32 && n_floats != n * 4) return fail(c, PTMI_E_INVALID, "float canvas: expected %zu floats, got %zu", n * 4, n_floats);
@@ -1221,12 +1254,19 @@ int ptmi_blit(ptmi_ctx *c, float *dst_f32, size_t n_floats, uint8_t *dst_rgba8, 
     if (dst_f32 && !c->d_blit_f32) HIP_TRY(c, hipMalloc(&c->d_blit_f32, n * 16));
     if (dst_rgba8 && !c->d_blit_u8) HIP_TRY(c, hipMalloc(&c->d_blit_u8, n * 4));
     c->blit_px = n;
-    pt_launch_blit(c->stream, c->n_cu * 8, c->W, c->H, c->d_out, dst_f32 ? c->d_blit_f32 : nullptr, dst_rgba8 ? c->d_blit_u8 : nullptr);
+    pt_launch_blit(c->stream, c->n_cu * 8, c->W, c->H, src, dst_f32 ? c->d_blit_f32 : nullptr, dst_rgba8 ? c->d_blit_u8 : nullptr);
     HIP_TRY(c, sync_all(c));
     drain_events(c);
     if (dst_f32) HIP_TRY(c, hipMemcpy(dst_f32, c->d_blit_f32, n * 16, hipMemcpyDeviceToHost));
     if (dst_rgba8) HIP_TRY(c, hipMemcpy(dst_rgba8, c->d_blit_u8, n * 4, hipMemcpyDeviceToHost));
     return PTMI_OK;
+}
+}  // namespace
+
+int ptmi_blit(ptmi_ctx *c, float *dst_f32, size_t n_floats, uint8_t *dst_rgba8, size_t n_bytes) {
+    if (!c) return PTMI_E_INVALID;
+    if (!c->d_out) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
+    return blit_plane(c, c->d_out, dst_f32, n_floats, dst_rgba8, n_bytes);
 }
 
 int ptmi_get_size(const ptmi_ctx *c, uint32_t *w, uint32_t *h) {
@@ -1273,6 +1313,101 @@ void *ptmi_aov_device_ptr(ptmi_ctx *c, uint32_t which) {
     if (!c) return nullptr;
     void **plane = aov_plane(c, which);
     return plane && (c->aov_mask & which) ? *plane : nullptr;
+}
+
+int ptmi_set_moments(ptmi_ctx *c, uint32_t on) {
+    if (!c) return PTMI_E_INVALID;
+    if (on > 1u) return fail(c, PTMI_E_INVALID, "on = %u is not 0 or 1", on);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, sync_all(c));                     // nothing in flight writes a plane that goes
+    if (on && !c->d_moments) {
+        const int rc = alloc_moments(c);
+        if (rc) return rc;
+    }
+    if (!on) dfree(c->d_moments);
+    c->moments_on = on != 0;
+    return PTMI_OK;
+}
+
+int ptmi_get_moments(const ptmi_ctx *c, uint32_t *on) {
+    if (!c || !on) return PTMI_E_INVALID;
+    *on = c->moments_on ? 1u : 0u;
+    return PTMI_OK;
+}
+
+int ptmi_read_moments(ptmi_ctx *c, float *dst, size_t n_floats) {
+    if (!c) return PTMI_E_INVALID;
+    if (!dst) return fail(c, PTMI_E_INVALID, "dst is NULL");
+    if (!c->moments_on) return fail(c, PTMI_E_STATE, "the moments plane is off (ptmi_set_moments)");
+    if (!c->d_moments) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
+    const size_t n = (size_t)c->W * c->H * 4;
+    if (n_floats != n) return fail(c, PTMI_E_INVALID, "expected %zu floats, got %zu", n, n_floats);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, sync_all(c));
+    drain_events(c);
+    HIP_TRY(c, hipMemcpy(dst, c->d_moments, n * 4, hipMemcpyDeviceToHost));
+    return PTMI_OK;
+}
+
+void *ptmi_moments_device_ptr(ptmi_ctx *c) { return c && c->moments_on ? c->d_moments : nullptr; }
+
+int ptmi_denoise(ptmi_ctx *c, const ptmi_denoise_params *p, float *dst_rgba, size_t n_floats) {
+    if (!c) return PTMI_E_INVALID;
+    const ptmi_denoise_params zero = {};
+    const ptmi_denoise_params &q = p ? *p : zero;
+    if (q.iterations > 10u) return fail(c, PTMI_E_INVALID, "iterations = %u is above 10", q.iterations);
+    if (q.demodulate > 2u) return fail(c, PTMI_E_INVALID, "unknown demodulate %u", q.demodulate);
+    if (q.reserved[0] || q.reserved[1] || q.reserved[2]) return fail(c, PTMI_E_INVALID, "a reserved word is not zero");
+    const float phis[3] = {q.phi_color, q.phi_normal, q.phi_depth};
+    for (float f : phis)
+        if (!std::isfinite(f) || f < 0.0f) return fail(c, PTMI_E_INVALID, "phi %g is negative or not finite", (double)f);
+    if (!c->d_out) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
+    const size_t npix = (size_t)c->W * c->H;
+    if (dst_rgba && n_floats != npix * 4) return fail(c, PTMI_E_INVALID, "expected %zu floats, got %zu", npix * 4, n_floats);
+    if (!(c->aov_mask & PTMI_AOV_NORMAL) || !c->d_aov_normal)
+        return fail(c, PTMI_E_STATE, "the denoiser needs the NORMAL plane (ptmi_set_aovs)");
+    if (!c->d_moments) return fail(c, PTMI_E_STATE, "the denoiser needs the moments plane (ptmi_set_moments)");
+    const bool have_albedo = (c->aov_mask & PTMI_AOV_ALBEDO) && c->d_aov_albedo;
+    if (q.demodulate == 2u && !have_albedo) return fail(c, PTMI_E_STATE, "demodulate = 2 needs the ALBEDO plane (ptmi_set_aovs)");
+    const bool demod = q.demodulate == 2u || (q.demodulate == 0u && have_albedo);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->d_dn_out) {                          // all five or none
+        float4 *g = nullptr, *a = nullptr, *b = nullptr, *o = nullptr;
+        float *gr = nullptr;
+        hipError_t e = hipMalloc(&g, npix * 16);
+        if (e == hipSuccess) e = hipMalloc(&gr, npix * 4);
+        if (e == hipSuccess) e = hipMalloc(&a, npix * 16);
+        if (e == hipSuccess) e = hipMalloc(&b, npix * 16);
+        if (e == hipSuccess) e = hipMalloc(&o, npix * 16);
+        if (e != hipSuccess) {
+            dfree(g); dfree(gr); dfree(a); dfree(b); dfree(o);
+            (void)hipGetLastError();
+            return fail(c, PTMI_E_HIP, "allocation of the denoiser's planes (%zu bytes) failed: %s", npix * 68, hipGetErrorString(e));
+        }
+        c->d_dn_guide = g; c->d_dn_grad = gr; c->d_dn_a = a; c->d_dn_b = b; c->d_dn_out = o;
+    }
+    DenoiseArgs da;
+    da.W = c->W; da.H = c->H;
+    da.iterations = q.iterations ? q.iterations : 5u;
+    da.phi_color = q.phi_color > 0.0f ? q.phi_color : 4.0f;
+    da.phi_normal = q.phi_normal > 0.0f ? q.phi_normal : 128.0f;
+    da.phi_depth = q.phi_depth > 0.0f ? q.phi_depth : 1.0f;
+    pt_launch_denoise(c->stream, da, c->d_out, c->d_aov_normal, demod ? c->d_aov_albedo : nullptr, c->d_moments, c->d_dn_guide,
+                      c->d_dn_grad, c->d_dn_a, c->d_dn_b, c->d_dn_out);
+    HIP_TRY(c, hipGetLastError());
+    if (!dst_rgba) return PTMI_OK;
+    HIP_TRY(c, sync_all(c));
+    drain_events(c);
+    HIP_TRY(c, hipMemcpy(dst_rgba, c->d_dn_out, npix * 16, hipMemcpyDeviceToHost));
+    return PTMI_OK;
+}
+
+void *ptmi_denoised_device_ptr(ptmi_ctx *c) { return c ? c->d_dn_out : nullptr; }
+
+int ptmi_blit_denoised(ptmi_ctx *c, float *dst_f32, size_t n_floats, uint8_t *dst_rgba8, size_t n_bytes) {
+    if (!c) return PTMI_E_INVALID;
+    if (!c->d_dn_out) return fail(c, PTMI_E_STATE, "nothing denoised since the last resize (ptmi_denoise)");
+    return blit_plane(c, c->d_dn_out, dst_f32, n_floats, dst_rgba8, n_bytes);
 }
 
 int ptmi_get_stats(ptmi_ctx *c, ptmi_stats *out) {

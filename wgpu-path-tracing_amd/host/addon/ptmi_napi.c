@@ -305,12 +305,12 @@ static napi_value js_write_output(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
-/* get_handle for the AOV calls, which take one device's handle: nothing gathers the planes of several */
+/* get_handle for the AOV, moments and denoiser calls, which take one device's handle: nothing gathers the planes of several */
 static handle *get_single_handle(napi_env env, napi_callback_info info, size_t want, napi_value *argv, const char *what) {
     handle *h = get_handle(env, info, want, argv);
     if (h && h->kind == KIND_MULTI) {
         char msg[128];
-        snprintf(msg, sizeof msg, "%s: AOV planes are not supported with several devices", what);
+        snprintf(msg, sizeof msg, "%s: AOV planes, moments and the denoiser are not supported with several devices", what);
         napi_throw_error(env, NULL, msg);
         return NULL;
     }
@@ -363,6 +363,84 @@ static napi_value js_blit(napi_env env, napi_callback_info info) {
         return NULL;
     }
     CALL(env, h, blit, NULL, 0, (uint8_t *)p, n);
+    return argv[1];
+}
+
+/* the canvas-sized typed array a call writes: width*height*4 elements of elem_bytes each, else a RangeError (a short or stale
+ * array, after resize(), must not reach the library) */
+static int check_canvas(napi_env env, handle *h, const char *what, const char *type, size_t elem_bytes, void *p, size_t n) {
+    if (!p) {
+        char msg[128];
+        snprintf(msg, sizeof msg, "%s: expected a %s of width*height*4 elements", what, type);
+        napi_throw_type_error(env, NULL, msg);
+        return 0;
+    }
+    uint32_t w = 0, hh = 0;
+    int rc = ptmi_get_size(h->ctx, &w, &hh);
+    if (rc) { throw_ptmi(env, h, rc, "ptmi_get_size"); return 0; }
+    if (n != (size_t)w * hh * 4 * elem_bytes) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "%s: expected a %s of %zu bytes (%ux%ux4), got %zu", what, type, (size_t)w * hh * 4 * elem_bytes, w,
+                 hh, n);
+        napi_throw_range_error(env, NULL, msg);
+        return 0;
+    }
+    return 1;
+}
+
+static float get_f32_prop(napi_env env, napi_value obj, const char *name, float dflt) {
+    napi_value v; bool has = false; double out = dflt;
+    if (napi_has_named_property(env, obj, name, &has) == napi_ok && has &&
+        napi_get_named_property(env, obj, name, &v) == napi_ok)
+        napi_get_value_double(env, v, &out);
+    return (float)out;
+}
+
+/* setMoments(h, on) */
+static napi_value js_set_moments(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    handle *h = get_single_handle(env, info, 2, argv, "setMoments");
+    if (!h) return NULL;
+    bool on = false;
+    napi_get_value_bool(env, argv[1], &on);
+    int rc = ptmi_set_moments(h->ctx, on ? 1u : 0u);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_set_moments");
+    return NULL;
+}
+
+/* denoise(h, {iterations, demodulate, phiColor, phiNormal, phiDepth} or null, Float32Array dst of width*height*4) */
+static napi_value js_denoise(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    handle *h = get_single_handle(env, info, 3, argv, "denoise");
+    if (!h) return NULL;
+    ptmi_denoise_params prm;
+    memset(&prm, 0, sizeof prm);
+    napi_valuetype t;
+    if (napi_typeof(env, argv[1], &t) == napi_ok && t == napi_object) {
+        prm.iterations = get_u32_prop(env, argv[1], "iterations", 0);
+        prm.demodulate = get_u32_prop(env, argv[1], "demodulate", 0);
+        prm.phi_color = get_f32_prop(env, argv[1], "phiColor", 0.0f);
+        prm.phi_normal = get_f32_prop(env, argv[1], "phiNormal", 0.0f);
+        prm.phi_depth = get_f32_prop(env, argv[1], "phiDepth", 0.0f);
+    }
+    void *p; size_t n;
+    if (!get_bytes(env, argv[2], &p, &n)) return NULL;
+    if (!check_canvas(env, h, "denoise", "Float32Array", 4, p, n)) return NULL;
+    int rc = ptmi_denoise(h->ctx, &prm, (float *)p, n / 4);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_denoise");
+    return argv[2];
+}
+
+/* blitDenoised(h, Uint8Array dstRgba8): blit() of the last denoise() result */
+static napi_value js_blit_denoised(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    handle *h = get_single_handle(env, info, 2, argv, "blitDenoised");
+    if (!h) return NULL;
+    void *p; size_t n;
+    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
+    if (!check_canvas(env, h, "blitDenoised", "Uint8Array", 1, p, n)) return NULL;
+    int rc = ptmi_blit_denoised(h->ctx, NULL, 0, (uint8_t *)p, n);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_blit_denoised");
     return argv[1];
 }
 
@@ -478,6 +556,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"dispatch", js_dispatch}, {"gather", js_gather}, {"synchronize", js_synchronize}, {"throttle", js_throttle},
         {"readOutput", js_read_output}, {"writeOutput", js_write_output}, {"setAovs", js_set_aovs}, {"readAov", js_read_aov},
         {"blit", js_blit}, {"getStats", js_get_stats}, {"resetStats", js_reset_stats},
+        {"setMoments", js_set_moments}, {"denoise", js_denoise}, {"blitDenoised", js_blit_denoised},
         {"buildBvh", js_build_bvh}, {"emissiveLights", js_emissive_lights},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

@@ -73,8 +73,18 @@ export class Renderer {
   pick(x: number, y: number): { triangle: number; material: number; depth: number | null } | null;
   /** blit pass (blit.wgsl): tone-mapped RGBA8 canvas, row 0 = top */
   blit(): Uint8Array;
+  /** the denoiser's planes (normal, albedo, sample moments) on or off together; an 'id' plane stays; throws with several devices */
+  setDenoise(on: boolean): void;
+  /** the denoised output buffer (include/ptmi.h ptmi_denoise): width*height float4 (rgb, 0), row 0 = image bottom */
+  denoise(params?: DenoiseParams): Float32Array;
+  /** blit pass of the last denoise() result: tone-mapped RGBA8 canvas, row 0 = top */
+  blitDenoised(): Uint8Array;
   setOptions(o: TraceOptions): void;
   getStats(): Stats;
+}
+/** 0 or absent: the default (include/ptmi.h ptmi_denoise_params) */
+export interface DenoiseParams {
+  iterations?: number; demodulate?: 0 | 1 | 2; phiColor?: number; phiNormal?: number; phiDepth?: number;
 }
 export function setupRenderer(options?: { device?: number; width?: number; height?: number; model?: string; autoStart?: boolean; options?: TraceOptions; input?: InputSource }): Promise<Renderer>;
 export const pack: {

@@ -4,9 +4,10 @@
  * render_cli.js — drives the Renderer the way the reference's frame loop does
  * (renderer.ts:415-454: one dispatch per frame, frameIndex++), headless:
  *   node render_cli.js <scene.ptscene> <out.f32> [--width W --height H --frames N --bounces B --mis 0|1
- *                       --aperture A --focus F --batch K --png out.png]
- * --batch K traces K frames per dispatch instead of one. Writes W*H*4 float32 (the output buffer)
- * and prints one JSON line with the statistics.
+ *                       --aperture A --focus F --batch K --png out.png --denoise]
+ * --batch K traces K frames per dispatch instead of one. --denoise keeps the denoiser's planes and makes --png the tone-mapped
+ * denoised image (include/ptmi.h ptmi_denoise, default parameters). Writes W*H*4 float32 (the output buffer, raw also with
+ * --denoise) and prints one JSON line with the statistics.
  */
 var fs = require('fs');
 var host = require('./renderer');
@@ -19,10 +20,12 @@ function arg(name, dflt) {
 var scenePath = process.argv[2], outPath = process.argv[3];
 if (!scenePath || !outPath) { console.error('usage: render_cli.js scene.ptscene out.f32 [options]'); process.exit(2); }
 var W = arg('width', 256), H = arg('height', 256), frames = arg('frames', 16), batch = arg('batch', 1);
+var denoise = process.argv.indexOf('--denoise') >= 0;
 
 var r = new host.Renderer({ width: W, height: H, options: { maxBounces: arg('bounces', 8), doMis: arg('mis', 1) } });
 r.camera.aperture = arg('aperture', r.camera.aperture);
 r.camera.focusDistance = arg('focus', r.camera.focusDistance);
+if (denoise) r.setDenoise(true);
 r.loadModel(scenePath).then(function () {
   var t0 = Date.now();
   while (r.frameIndex < frames) r.renderFrame(Math.min(batch, frames - r.frameIndex));
@@ -30,7 +33,11 @@ r.loadModel(scenePath).then(function () {
   var ms = Date.now() - t0;
   fs.writeFileSync(outPath, Buffer.from(out.buffer));
   var pi = process.argv.indexOf('--png');
-  if (pi >= 0) fs.writeFileSync(process.argv[pi + 1], require('./png').encodePNG(r.blit(), W, H));
+  if (pi >= 0) {
+    var img;
+    if (denoise) { r.denoise(); img = r.blitDenoised(); } else img = r.blit();
+    fs.writeFileSync(process.argv[pi + 1], require('./png').encodePNG(img, W, H));
+  }
   var st = r.getStats();
   st.wallMs = ms; st.width = W; st.height = H; st.frames = frames;
   console.log(JSON.stringify(st));

@@ -250,6 +250,33 @@ Renderer.prototype.pick = function (x, y) {
   return { triangle: ids[2 * i], material: ids[2 * i + 1], depth: depth };
 };
 
+/** The denoiser's inputs (include/ptmi.h ptmi_denoise): on turns the 'normal' and 'albedo' planes and the sample-moments plane on,
+ *  off turns the three off; an 'id' plane that is on stays on. Like setAovs, planes turned on mid-accumulation mix with zeros
+ *  until the next frame 0. One device only. */
+Renderer.prototype.setDenoise = function (on) {
+  if (this.multi) throw new Error('setDenoise: the denoiser is not supported with several devices');
+  var mask = ((this.aovMask || 0) & 4) | (on ? 3 : 0);
+  this.addon.setAovs(this.ctx, mask);
+  this.aovMask = mask;
+  this.addon.setMoments(this.ctx, !!on);
+  this.denoiseOn = !!on;
+};
+/** The denoised output buffer: width*height float4 (rgb, 0), row 0 = image bottom like readOutput. params (all optional, 0 = the
+ *  default): {iterations, demodulate, phiColor, phiNormal, phiDepth}. Needs setDenoise(true). Synchronises. */
+Renderer.prototype.denoise = function (params) {
+  if (this.multi) throw new Error('denoise: the denoiser is not supported with several devices');
+  var out = new Float32Array(this.width * this.height * 4);
+  this.addon.denoise(this.ctx, params || null, out);
+  return out;
+};
+/** blit() of the last denoise() result: tone-mapped 8-bit canvas, row 0 = top */
+Renderer.prototype.blitDenoised = function () {
+  if (this.multi) throw new Error('blitDenoised: the denoiser is not supported with several devices');
+  var out = new Uint8Array(this.width * this.height * 4);
+  this.addon.blitDenoised(this.ctx, out);
+  return out;
+};
+
 Renderer.prototype.setOptions = function (o) { this.addon.setOptions(this.ctx, o); };
 Renderer.prototype.getStats = function () { return this.addon.getStats(this.ctx); };
 /** several devices: assemble the frame on the first one now (readOutput / blit do it themselves) */

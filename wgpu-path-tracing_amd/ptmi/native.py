@@ -30,6 +30,8 @@ EXPORTS = [
     "ptmi_multi_dispatch", "ptmi_multi_gather", "ptmi_multi_synchronize", "ptmi_multi_read_output", "ptmi_multi_write_output",
     "ptmi_multi_blit", "ptmi_multi_get_stats", "ptmi_multi_reset_stats", "ptmi_multi_gather_ms",
     "ptmi_set_aovs", "ptmi_get_aovs", "ptmi_read_aov", "ptmi_aov_device_ptr",
+    "ptmi_set_moments", "ptmi_get_moments", "ptmi_read_moments", "ptmi_moments_device_ptr",
+    "ptmi_denoise", "ptmi_denoised_device_ptr", "ptmi_blit_denoised",
 ]
 MULTI_LOOPBACK = 1
 # first-hit planes (include/ptmi.h ptmi_set_aovs): name -> (bit, numpy dtype, channels)
@@ -53,6 +55,11 @@ class Options(ctypes.Structure):
                 ("perf_mode", ctypes.c_uint32), ("reserved_a", ctypes.c_uint32), ("overlap", ctypes.c_uint32),
                 ("reserved_b", ctypes.c_uint32 * 4), ("tree_builder", ctypes.c_uint32),
                 ("leaves", ctypes.c_uint32), ("leaf_tris", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 1)]
+
+
+class DenoiseParams(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_uint32), ("demodulate", ctypes.c_uint32), ("phi_color", ctypes.c_float),
+                ("phi_normal", ctypes.c_float), ("phi_depth", ctypes.c_float), ("reserved", ctypes.c_uint32 * 3)]
 
 
 class Stats(ctypes.Structure):
@@ -130,6 +137,15 @@ def load():
         L.ptmi_read_aov.argtypes = [vp, u32, vp, sz]
         L.ptmi_aov_device_ptr.restype = vp
         L.ptmi_aov_device_ptr.argtypes = [vp, u32]
+        L.ptmi_set_moments.argtypes = [vp, u32]
+        L.ptmi_get_moments.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32)]
+        L.ptmi_read_moments.argtypes = [vp, vp, sz]
+        L.ptmi_moments_device_ptr.restype = vp
+        L.ptmi_moments_device_ptr.argtypes = [vp]
+        L.ptmi_denoise.argtypes = [vp, vp, vp, sz]
+        L.ptmi_denoised_device_ptr.restype = vp
+        L.ptmi_denoised_device_ptr.argtypes = [vp]
+        L.ptmi_blit_denoised.argtypes = [vp, vp, sz, vp, sz]
         _lib = L
     return _lib
 
@@ -352,6 +368,43 @@ class Context(_Handle):
 
     def aov_device_ptr(self, name):
         return self.L.ptmi_aov_device_ptr(self.h, _aov(name)[0])
+
+    # -- sample moments and the denoiser (include/ptmi.h ptmi_set_moments, ptmi_denoise) ----------------------
+    def set_moments(self, on=True):
+        self._ck(self.L.ptmi_set_moments(self.h, int(on)))
+
+    def moments(self):
+        """whether the sample-moments plane is on"""
+        m = ctypes.c_uint32(0)
+        self._ck(self.L.ptmi_get_moments(self.h, ctypes.byref(m)))
+        return bool(m.value)
+
+    def read_moments(self):
+        """(H, W, 4) float32: mean luminance, mean squared luminance, frames folded, 0"""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._ck(self.L.ptmi_read_moments(self.h, _p(out), out.size))
+        return out
+
+    def moments_device_ptr(self):
+        return self.L.ptmi_moments_device_ptr(self.h)
+
+    def denoise(self, iterations=0, demodulate=0, phi_color=0.0, phi_normal=0.0, phi_depth=0.0, reserved=(0, 0, 0), dst=True):
+        """the denoised output buffer, (H, W, 4) float32 with w = 0; 0 picks a parameter's default (include/ptmi.h).
+        dst=False: only queue it on the context's stream (denoised_device_ptr, blit_denoised) and return None."""
+        prm = DenoiseParams(iterations, demodulate, phi_color, phi_normal, phi_depth, (ctypes.c_uint32 * 3)(*reserved))
+        out = np.empty((self.height, self.width, 4), np.float32) if dst else None
+        self._ck(self.L.ptmi_denoise(self.h, ctypes.byref(prm), _p(out), 0 if out is None else out.size))
+        return out
+
+    def denoised_device_ptr(self):
+        return self.L.ptmi_denoised_device_ptr(self.h)
+
+    def blit_denoised(self, want_f32=True, want_rgba8=True):
+        """blit() of the denoised plane: (canvas float RGBA or None, canvas uint8 RGBA or None), row 0 = top"""
+        f = np.empty((self.height, self.width, 4), np.float32) if want_f32 else None
+        b = np.empty((self.height, self.width, 4), np.uint8) if want_rgba8 else None
+        self._ck(self.L.ptmi_blit_denoised(self.h, _p(f), 0 if f is None else f.size, _p(b), 0 if b is None else b.size))
+        return f, b
 
     def read_image(self):
         """The traversal image the last upload_scene put on the device (include/ptmi.h: ptmi_debug_read_image), as build_image()
