@@ -79,7 +79,9 @@ __global__ __launch_bounds__(BLOCK) void k_raygen_list(ptmi_camera cam, uint32_t
 //                 wave walks its 64 words: word j's mask and base offset are read from lane j,
 //                 lane L keeps slot 64*w+L iff bit L is set, at base + popcount(bits below L).
 // The next queue is therefore the surviving path ids in unchanged (ascending) order, and its
-// length lands in next_count — no host round trip.
+// length lands in next_count — no host round trip. The shadow half lists record positions instead:
+// `shade` packs the records of each wave's 64 slots at the front of those slots (shade.hip), so
+// the bit below-rank of word w is the record at 64 w + rank.
 // Measured on config 1 (Msamples/s, same box): 256 words per tile 8 898, 512: 9 133, 1024: 9 160 — with 133 M slots a launch
 // of 8 100 four-wave workgroups costs more than the prefix over fewer, larger tiles.
 #ifndef PT_TILE_WORDS
@@ -116,6 +118,7 @@ __global__ __launch_bounds__(TILE_WORDS) void k_tile_sums(const uint32_t *__rest
     }
 }
 
+template <bool PACKED>
 PT_DEV void scatter_tile(uint32_t tile, const uint32_t *__restrict__ count_ptr, const uint32_t *__restrict__ queue,
                          const uint64_t *__restrict__ alive, const uint32_t *__restrict__ tile_sums,
                          uint32_t *__restrict__ next_queue, uint32_t *__restrict__ next_count) {
@@ -161,7 +164,7 @@ PT_DEV void scatter_tile(uint32_t tile, const uint32_t *__restrict__ count_ptr, 
         if ((jm >> lane) & 1ull) {
             const uint32_t below = (uint32_t)__popcll(jm & ((1ull << lane) - 1ull));
             const uint32_t slot = (w0 + j) * 64u + lane;
-            next_queue[jbase + below] = queue ? queue[slot] : slot;
+            next_queue[jbase + below] = PACKED ? (w0 + j) * 64u + below : queue ? queue[slot] : slot;
         }
     }
 }
@@ -172,18 +175,39 @@ __global__ __launch_bounds__(TILE_WORDS) void k_scatter(const uint32_t *__restri
                                                         const uint32_t *__restrict__ tile_sums,
                                                         uint32_t *__restrict__ next_queue,
                                                         uint32_t *__restrict__ next_count) {
-    scatter_tile(blockIdx.x, count_ptr, queue, alive, tile_sums, next_queue, next_count);
+    scatter_tile<false>(blockIdx.x, count_ptr, queue, alive, tile_sums, next_queue, next_count);
+}
+__global__ __launch_bounds__(TILE_WORDS) void k_scatter_packed(const uint32_t *__restrict__ count_ptr,
+                                                               const uint64_t *__restrict__ shadow,
+                                                               const uint32_t *__restrict__ shadow_sums,
+                                                               uint32_t *__restrict__ shadow_queue,
+                                                               uint32_t *__restrict__ shadow_count) {
+    scatter_tile<true>(blockIdx.x, count_ptr, nullptr, shadow, shadow_sums, shadow_queue, shadow_count);
 }
 // both compactions of a bounce in one launch: workgroups [0, tiles) compact the survivors into the next queue,
-// [tiles, 2 tiles) the emitted records into the shadow index list
+// [tiles, 2 tiles) the emitted records into the shadow index list (record positions, see above)
 __global__ __launch_bounds__(TILE_WORDS) void k_scatter2(uint32_t tiles, const uint32_t *__restrict__ count_ptr,
                                                          const uint32_t *__restrict__ queue,
                                                          const uint64_t *__restrict__ alive, const uint64_t *__restrict__ shadow,
                                                          const uint32_t *__restrict__ tile_sums, const uint32_t *__restrict__ shadow_sums,
                                                          uint32_t *__restrict__ next_queue, uint32_t *__restrict__ next_count,
                                                          uint32_t *__restrict__ shadow_queue, uint32_t *__restrict__ shadow_count) {
-    if (blockIdx.x < tiles) scatter_tile(blockIdx.x, count_ptr, queue, alive, tile_sums, next_queue, next_count);
-    else scatter_tile(blockIdx.x - tiles, count_ptr, nullptr, shadow, shadow_sums, shadow_queue, shadow_count);
+    if (blockIdx.x < tiles) scatter_tile<false>(blockIdx.x, count_ptr, queue, alive, tile_sums, next_queue, next_count);
+    else scatter_tile<true>(blockIdx.x - tiles, count_ptr, nullptr, shadow, shadow_sums, shadow_queue, shadow_count);
+}
+
+// The repack, once per batch after the compaction of the first bounce that plays roulette (ptmi_api.hip): queue entry j (path id q)
+// -> to.O / D / C[j] = from.O / D / C[q], pid[j] = q. Every entry is independent: one gather per lane, many in flight.
+__global__ __launch_bounds__(BLOCK) void k_repack(const uint32_t *__restrict__ count_ptr, const uint32_t *__restrict__ queue,
+                                                  DevPaths from, DevPaths to, uint32_t *__restrict__ pid) {
+    const uint32_t n = *count_ptr;
+    for (uint32_t j = blockIdx.x * BLOCK + threadIdx.x; j < n; j += gridDim.x * BLOCK) {
+        const uint32_t q = queue[j];
+        const float4 o = ld_stream(&from.O[q]), d = ld_stream(&from.D[q]);
+        const float2 c = ld_stream(&from.C[q]);
+        st_stream(&to.O[j], o); st_stream(&to.D[j], d); st_stream(&to.C[j], c);
+        pid[j] = q;
+    }
 }
 
 // pt.wgsl:751-761 for the batch's frames in ascending order
@@ -404,9 +428,13 @@ void pt_launch_compact(hipStream_t s, int tiles, const uint32_t *queue, const ui
     if (do_scatter)
         hipLaunchKernelGGL(k_scatter, dim3(tiles), dim3(TILE_WORDS), 0, s, count, queue, alive_mask, tile_sums,
                            next_queue, next_count);
-    if (shadow_mask)    // slots (not path ids) of the emitted shadow records, ascending
-        hipLaunchKernelGGL(k_scatter, dim3(tiles), dim3(TILE_WORDS), 0, s, count, (const uint32_t *)nullptr,
-                           shadow_mask, shadow_sums, shadow_queue, shadow_count);
+    if (shadow_mask)    // positions (not path ids) of the emitted shadow records, ascending
+        hipLaunchKernelGGL(k_scatter_packed, dim3(tiles), dim3(TILE_WORDS), 0, s, count, shadow_mask, shadow_sums, shadow_queue,
+                           shadow_count);
+}
+void pt_launch_repack(hipStream_t s, int blocks, const uint32_t *count, const uint32_t *queue, DevPaths from, DevPaths to,
+                      uint32_t *pid) {
+    hipLaunchKernelGGL(k_repack, dim3(blocks), dim3(BLOCK), 0, s, count, queue, from, to, pid);
 }
 void pt_launch_accumulate(hipStream_t s, int blocks, DevBand band, uint32_t frame0, uint32_t n_frames,
                           const float *L, uint32_t l_stride, float4 *out) {

@@ -64,7 +64,7 @@ struct DevScene {
     const DevScene *self;       // this description in device memory (the own-leaf kernels read it from there, not from kernel arguments)
 };
 
-// ---- path state: 56 B per path, four streams indexed by path id ----
+// ---- path state: 56 B per path, four streams indexed by path id (O / D / C: by queue slot after the repack, ShadeParams) ----
 //   O = (origin.xyz, bits(rng state))   D = (direction.xyz, throughput.x)      the two float4 `extend` reads
 //   C = (throughput.y, throughput.z)    L = (radiance.xyz, 0)
 // Radiance L and the contribution SC of a shadow record have three lanes and are stored as three floats.
@@ -88,7 +88,7 @@ struct DevPaths {
     }
 };
 // hit record, 8 B per queue slot: (t, bits(triangle index)); t = -1 on a miss. `shade` rebuilds (u, v) from the triangle.
-// shadow record, 44 B per queue slot:
+// shadow record, 44 B per queue slot (`shade` packs a wave's records at the front of its 64 slots):
 //   SO = (origin.xyz, dist or -1 for directional)  SD = (wi.xyz, bits(path id))
 //   SC = throughput * directLight .xyz (12-byte stride)   added to L[path] when unoccluded
 // One allocation per bounce parity: SO at the base, SD `cap` float4 further, SC after both (the shadow kernel carries only the
@@ -106,6 +106,12 @@ struct DevBand {
     }
 };
 
+// Russian roulette (pt.wgsl:699-705) from this bounce on. The first such bounce is also where the batch's path state is repacked:
+// after its compaction, O / D / C of the survivors are gathered into tail arrays at their queue positions (pt_launch_repack), and
+// from the next bounce on the state stays at the slot the queue names, its path id beside it (ShadeParams::pid).
+PT_HD bool pt_plays_roulette(uint32_t bounce) { return bounce > 2u; }
+inline uint32_t pt_repack_bounce() { uint32_t b = 0; while (!pt_plays_roulette(b)) b++; return b; }
+
 struct ShadeParams {
     uint32_t bounce, max_bounces, do_mis;
     unsigned long long *stats;          // [1] += next-event samples counted but not traced (zero contribution)
@@ -113,6 +119,7 @@ struct ShadeParams {
                                         //    that `shadow` adds like an unoccluded light sample — all additions to L then happen in
                                         //    that one kernel, in bounce order, and `shadow` can run beside the next bounce's kernels.
                                         //    stats[3] += such records (they are not shadow rays)
+    const uint32_t *pid;                // path id of a state slot after the repack (NULL: the slot is the path id)
 };
 
 enum { PT_VARIANT_GLOBAL = 1, PT_VARIANT_LDS = 2, PT_VARIANT_LDS_NODES = 3,
@@ -199,7 +206,7 @@ void pt_launch_extend_own(hipStream_t s, int blocks, const TraverseConfig &cfg, 
                           const uint32_t *queue, const uint32_t *count, float2 *hits);        // traverse_own.hip
 // (u, v) of n hit records, rebuilt the way `shade` does it (debug entry point of the parity tests)
 void pt_launch_hit_uv(hipStream_t s, uint32_t n, const DevScene &sc, DevPaths p, const float2 *hits, float2 *uv);
-// shadow_queue: slots of the shadow records to trace (NULL = slots 0..count-1), count = their number
+// shadow_queue: positions of the shadow records to trace (NULL = slots 0..count-1), count = their number
 void pt_launch_shadow(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &sc, DevPaths p,
                       DevShadow sh, const uint32_t *shadow_queue, const uint32_t *count, uint8_t *occluded_out);
 void pt_launch_shadow_own(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &sc, DevPaths p,
@@ -214,6 +221,9 @@ void pt_launch_shade_fast(hipStream_t s, int blocks, const DevScene &sc, DevPath
 // ordered stream compaction of the survivors: masks -> next queue + its count, plus statistics
 // (tiles = ceil(capacity / pt_compact_tile_slots()) + 1: one workgroup per tile of ballot words)
 uint32_t pt_compact_tile_slots(void);
+// the repack: queue entry j (path id q, j < *count) -> to.O / D / C[j] = from.O / D / C[q], pid[j] = q
+void pt_launch_repack(hipStream_t s, int blocks, const uint32_t *count, const uint32_t *queue, DevPaths from, DevPaths to,
+                      uint32_t *pid);
 void pt_launch_compact(hipStream_t s, int tiles, const uint32_t *queue, const uint32_t *count,
                        const uint64_t *alive_mask, const uint64_t *shadow_mask, uint32_t *tile_sums,
                        uint32_t *next_queue, uint32_t *next_count, uint32_t *shadow_queue, uint32_t *shadow_count,

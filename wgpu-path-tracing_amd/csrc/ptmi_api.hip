@@ -49,6 +49,8 @@ struct Lane {
     float2 *hits = nullptr;
     DevShadow sh[2]{};                                 // shadow records, double-buffered by bounce parity (overlap)
     uint32_t *queue[2] = {nullptr, nullptr}, *sq[2] = {nullptr, nullptr};
+    DevPaths tail{};                                   // O / D / C by queue slot from the bounce after the repack (L unused)
+    uint32_t *pid = nullptr;                           // ... and the path id of each such slot
     uint64_t *alive = nullptr, *shadowm = nullptr;
     size_t mask_words = 0;
     uint32_t *word_off = nullptr, *counts = nullptr;
@@ -199,6 +201,7 @@ void free_batch(Lane &ln) {
     dfree(ln.paths.O); dfree(ln.paths.D); dfree(ln.paths.C); dfree(ln.paths.L);
     dfree(ln.hits);
     for (int k = 0; k < 2; k++) { dfree(ln.sh[k].SO); ln.sh[k].SD = nullptr; ln.sh[k].SC = nullptr; dfree(ln.sq[k]); }
+    dfree(ln.tail.O); dfree(ln.tail.D); dfree(ln.tail.C); dfree(ln.pid);
     dfree(ln.queue[0]); dfree(ln.queue[1]); dfree(ln.alive); dfree(ln.shadowm); dfree(ln.word_off); dfree(ln.d_occ);
     dfree(ln.aov);
     ln.cap = 0;
@@ -212,8 +215,12 @@ hipError_t sync_all(ptmi_ctx *c) {
     return e;
 }
 
-// bytes of device memory a path of a batch takes in ensure_capacity (state 56 + hit 8 + 2 x (record 44 + index 4) + 2 queues + masks)
-constexpr size_t kBytesPerPath = 16 + 16 + 8 + 16 + 8 + 2 * (16 + 16 + sizeof(rgb_sc) + 4) + 2 * 4 + 1 + 1;
+// bytes of device memory a path of a batch takes in ensure_capacity (state 56 + hit 8 + 2 x (record 44 + index 4) + tail state 40 and
+// path id 4, sized for every path surviving roulette + 2 queues + masks)
+constexpr size_t kBytesPerPath = 16 + 16 + 8 + 16 + 8 + 2 * (16 + 16 + sizeof(rgb_sc) + 4) + (16 + 16 + 8 + 4) + 2 * 4 + 1 + 1;
+#ifndef PT_REPACK
+#define PT_REPACK 1          /* A/B switch: 0 leaves the path state at the path id for every bounce (no tail arrays in use) */
+#endif
 constexpr size_t kAovBytesPerPath = 32;   // ... and, while AOV planes are on, its first-hit record (Lane::aov)
 size_t bytes_per_path(bool aov) { return kBytesPerPath + (aov ? kAovBytesPerPath : 0); }
 
@@ -239,6 +246,7 @@ int ensure_capacity(ptmi_ctx *c, Lane &ln, size_t n) {
         ln.sh[k].SD = ln.sh[k].SO + cap; ln.sh[k].SC = reinterpret_cast<rgb_sc *>(ln.sh[k].SO + 2 * cap); ln.sh[k].cap = (uint32_t)cap;
         ALLOC(ln.sq[k], cap * 4);
     }
+    ALLOC(ln.tail.O, cap * 16); ALLOC(ln.tail.D, cap * 16); ALLOC(ln.tail.C, cap * 8); ALLOC(ln.pid, cap * 4);
     ALLOC(ln.queue[0], cap * 4); ALLOC(ln.queue[1], cap * 4);
     ALLOC(ln.alive, words * 8); ALLOC(ln.shadowm, words * 8); ln.mask_words = words;
     ALLOC(ln.word_off, 2 * tiles * 4);
@@ -1121,6 +1129,13 @@ int ptmi_dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames) {
         if (cfg_shadow.wants_spill && !cfg_shadow.spill) cfg_shadow.spill = ln.d_spill_side;
         ln.paths.l_stride = c->st.radiance_stride_bytes / 4u;
         const DevPaths bp = ln.paths;
+        // Once per batch, after the compaction of the first bounce that plays roulette, the survivors' O / D / C are gathered into the
+        // tail arrays at their queue positions: from then on a few percent of the paths are alive, and state left at the path id costs
+        // them a line per lane in each stream. From the next bounce on, extend and shade find the state at the slot the queue names
+        // and shade writes it back there; the radiance and the records keep the path id (ln.pid).
+        const uint32_t rb = PT_REPACK ? pt_repack_bounce() : 0xFFFFFFFEu;
+        DevPaths tp = ln.tail;
+        tp.L = bp.L; tp.l_stride = bp.l_stride;
         float4 *const aov_rec = c->aov_mask ? ln.aov : nullptr;         // written by shade(0), read by the fold after the last bounce
         for (uint32_t f0 = 0; f0 < n_frames; f0 += F) {
             const uint32_t fb = std::min(F, n_frames - f0);
@@ -1128,20 +1143,23 @@ int ptmi_dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames) {
             { Timed t(c, 4, t3, ms); pt_launch_raygen(ms, blocks, *cam, band, frame0, fb, bp, &ln.counts[0]); }
             int cur = 0;
             for (uint32_t b = 0; b < maxb; b++) {
-                const uint32_t *q = b == 0 ? nullptr : ln.queue[cur];      // bounce 0: slot i holds path i
+                const bool tail = b > rb;                                   // the state is in the tail arrays
+                const uint32_t *q = b == 0 || b == rb + 1 ? nullptr : ln.queue[cur];   // bounce 0 / after the repack: slot i holds path / state i
+                const DevPaths sp = tail ? tp : bp;
                 const int par = side ? (int)(b & 1u) : 0;
-                const ShadeParams shp{b, maxb, c->opt.do_mis, c->d_stats, side ? 1u : 0u};
-                { Timed t(c, 1, t2, ms); (c->sc.own ? pt_launch_extend_own : pt_launch_extend)(ms, blocks, cfg, c->sc, bp, q, &ln.counts[b], ln.hits); }
+                const ShadeParams shp{b, maxb, c->opt.do_mis, c->d_stats, side ? 1u : 0u, tail ? ln.pid : nullptr};
+                { Timed t(c, 1, t2, ms); (c->sc.own ? pt_launch_extend_own : pt_launch_extend)(ms, blocks, cfg, c->sc, sp, q, &ln.counts[b], ln.hits); }
                 const bool last = b + 1 == maxb;
                 if (side && b >= 2) HIP_TRY(c, hipStreamWaitEvent(ms, ln.ev_shadow[par], 0));      // its records are read
                 { Timed t(c, 2, t3, ms);
                   (c->opt.perf_mode ? pt_launch_shade_fast : pt_launch_shade)(
-                      ms, shade_blocks, c->sc, bp, q, &ln.counts[b], ln.hits, ln.sh[par], ln.alive, ln.shadowm, shp,
+                      ms, shade_blocks, c->sc, sp, q, &ln.counts[b], ln.hits, ln.sh[par], ln.alive, ln.shadowm, shp,
                       b == 0 ? aov_rec : nullptr); }
                 { Timed t(c, 5, t3, ms);
                   pt_launch_compact(ms, tiles, q, &ln.counts[b], ln.alive, nee ? ln.shadowm : nullptr,
                                     ln.word_off, ln.queue[cur ^ 1], &ln.counts[b + 1], ln.sq[par], &ln.counts[kShadowCount + par],
-                                    c->d_stats, b, last ? 0 : 1); }
+                                    c->d_stats, b, last ? 0 : 1);
+                  if (b == rb && !last) pt_launch_repack(ms, blocks, &ln.counts[b + 1], ln.queue[cur ^ 1], bp, tp, ln.pid); }
                 if (side) {
                     HIP_TRY(c, hipEventRecord(ln.ev_ready, ms));
                     HIP_TRY(c, hipStreamWaitEvent(ss, ln.ev_ready, 0));

@@ -288,6 +288,12 @@ constexpr int SBLOCK = 256;
 // record, 32 B at slot i (the bounce-0 queue is the identity: slot i is path i), from the HitInfo the bounce builds anyway:
 // aov[2i] = (albedo.rgb, t), aov[2i + 1] = (normal.xyz, bits(triangle)); a miss writes zeros and triangle 0xFFFFFFFF.
 // The other instantiation never reads `aov` and is the bounce kernel as it was.
+//
+// Shadow records (next-event samples, and with emit_records the records of emissive hits and non-finite misses) are held in
+// registers until the wave's ballot and then packed at the front of the wave's 64 slots: the lane with `rank` records below it
+// writes record 64 * (i / 64) + rank. Slot order is kept (the compaction lists positions in that order, pipeline.hip), and the
+// lines `shadow` reads are the filled ones: where 59 % of the slots leave a record (Cornell, MIS), the records left at their own
+// slots put a record in nearly every line of all three streams.
 template <bool AOV>
 __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, DevPaths P, const uint32_t *__restrict__ queue,
                                                   const uint32_t *__restrict__ count_ptr,
@@ -296,16 +302,19 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                                                   uint64_t *__restrict__ shadow_mask, ShadeParams sp,
                                                   float4 *__restrict__ aov) {
     const uint32_t count = *count_ptr;
+    const uint32_t lane = threadIdx.x & 63u;
     uint32_t n_skipped = 0, n_emitted = 0;  // lane 0 of each wave: one atomic per wave at the end
     for (uint32_t base = blockIdx.x * SBLOCK; base < count; base += gridDim.x * SBLOCK) {
         const uint32_t i = base + threadIdx.x;
         bool alive = false, shadow = false, skipped = false, emitted = false;
+        float4 rec_o = make_float4(0.0f, 0.0f, 0.0f, -2.0f), rec_d = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // the record (SO, SD, SC)
+        rgb_sc rec_c{0.0f, 0.0f, 0.0f};
         if (i < count) {
             const uint32_t q = queue ? queue[i] : i;                         // where this ray's state is
             const float2 h2 = ld_stream(&hits[i]);
             if (!(h2.x < 0.0f)) {                                            // pt.wgsl:646: miss adds zero
                 const float4 o4 = ld_stream(&P.O[q]), d4 = ld_stream(&P.D[q]);
-                const uint32_t p = q;                                            // the path id: where its radiance is
+                const uint32_t p = sp.pid ? sp.pid[q] : q;                       // the path id: where its radiance is
                 uint32_t rng = __float_as_uint(o4.w);
                 const v3 ro = xyz(o4), rd = xyz(d4);
                 v3 thr = mk3(1.0f, 1.0f, 1.0f);                                      // pt.wgsl:639; raygen stores no throughput
@@ -320,9 +329,8 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                     float k = hit.emissive_strength;
                     const v3 e = mk3(thr.x * hit.emission.x * k * att, thr.y * hit.emission.y * k * att, thr.z * hit.emission.z * k * att);
                     if (sp.emit_records) {          // the path ends here: its last addition to L, made by `shadow` in bounce order
-                        st_stream(&S.SO[i], make_float4(0.0f, 0.0f, 0.0f, -2.0f));
-                        st_stream(&S.SD[i], make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(p)));
-                        S.SC[i] = rgb_sc{e.x, e.y, e.z};
+                        rec_d.w = __uint_as_float(p);                                 // rec_o = (0, 0, 0, -2)
+                        rec_c = rgb_sc{e.x, e.y, e.z};
                         shadow = true; emitted = true;
                     } else {
                         const rgb_sc l = P.ldL(p);
@@ -343,9 +351,9 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                             // in the statistics like the reference's traversal but neither recorded nor traced.
                             if ((contrib.x != 0.0f) | (contrib.y != 0.0f) | (contrib.z != 0.0f)) {
                                 v3 so = madd3(ls.wi, PT_EPS, hit.position);
-                                st_stream(&S.SO[i], make_float4(so.x, so.y, so.z, ls.dist));
-                                st_stream(&S.SD[i], make_float4(ls.wi.x, ls.wi.y, ls.wi.z, __uint_as_float(p)));
-                                S.SC[i] = rgb_sc{contrib.x, contrib.y, contrib.z};
+                                rec_o = make_float4(so.x, so.y, so.z, ls.dist);
+                                rec_d = make_float4(ls.wi.x, ls.wi.y, ls.wi.z, __uint_as_float(p));
+                                rec_c = rgb_sc{contrib.x, contrib.y, contrib.z};
                                 shadow = true;
                             } else {
                                 skipped = true;
@@ -361,7 +369,7 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                         v3 nd = normalize3(dir);
                         thr = mul3(thr, vdiv3(mk3(ev.x, ev.y, ev.z), max1(ev.w, PT_EPS)));   // pt.wgsl:696
                         alive = true;
-                        if (sp.bounce > 2u) {                                 // pt.wgsl:699-705
+                        if (pt_plays_roulette(sp.bounce)) {                   // pt.wgsl:699-705
                             float pr = max1(max1(thr.x, thr.y), thr.z);
                             if (rng_f(rng) > pr) alive = false;
                             else thr = vdiv3(thr, pr);
@@ -383,12 +391,11 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                 const float tx = reinterpret_cast<const float *>(&P.D[q])[3];
                 const float2 c2 = ld_stream(&P.C[q]);
                 if (!(__builtin_isfinite(tx) & __builtin_isfinite(c2.x) & __builtin_isfinite(c2.y))) {
-                    const uint32_t p = q;
+                    const uint32_t p = sp.pid ? sp.pid[q] : q;
                     const v3 e = mk3(tx * 0.0f, c2.x * 0.0f, c2.y * 0.0f);
                     if (sp.emit_records) {
-                        st_stream(&S.SO[i], make_float4(0.0f, 0.0f, 0.0f, -2.0f));
-                        st_stream(&S.SD[i], make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(p)));
-                        S.SC[i] = rgb_sc{e.x, e.y, e.z};
+                        rec_d.w = __uint_as_float(p);                                 // rec_o = (0, 0, 0, -2)
+                        rec_c = rgb_sc{e.x, e.y, e.z};
                         shadow = true; emitted = true;
                     } else {
                         const rgb_sc l = P.ldL(p);
@@ -398,7 +405,13 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
             }
         }
         const uint64_t am = __ballot(alive), sm = __ballot(shadow), zm = __ballot(skipped), em = __ballot(emitted);
-        if ((threadIdx.x & 63u) == 0u && i < count) {
+        if (shadow) {
+            const uint32_t r = (i & ~63u) + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull));
+            st_stream(&S.SO[r], rec_o);
+            st_stream(&S.SD[r], rec_d);
+            S.SC[r] = rec_c;
+        }
+        if (lane == 0u && i < count) {
             alive_mask[i >> 6] = am;
             shadow_mask[i >> 6] = sm;
             n_skipped += (uint32_t)__popcll(zm);
