@@ -98,10 +98,17 @@ typedef struct ptmi_options {
                                        axis): a triangle is tested iff the box of ITS reference leaf passes, exactly as pt.wgsl:248-291 does;
                                    2 = the library's own leaves: a full-sweep SAH hierarchy over the TRIANGLES (leaf_tris at most per leaf),
                                        boxes padded outward so that they are conservative for the kernels' fused slab test. A ray then tests
-                                       a quarter of the triangles (Cornell: 9.8 -> 2.4 per closest-hit ray). The closest hit is verified
-                                       against the reference leaf's box before it is reported, and a ray whose winner fails that test — or
-                                       whose direction has a zero / non-finite component, or whose origin lies far outside the scene — is
-                                       traced again over the uploaded tree, so results equal mode 1's;
+                                       a quarter of the triangles (Cornell: 9.8 -> 2.4 per closest-hit ray). A sliver (longest edge
+                                       squared above 16 x twice its area) enters the hierarchy with its reference leaf's box. The closest
+                                       hit is verified against the reference leaf's box before it is reported, and a ray whose winner fails
+                                       that test — or whose direction has a zero / non-finite component, or whose origin lies far outside
+                                       the scene — is traced again over the uploaded tree. Results equal mode 1's on every ray of the
+                                       benchmark renders and on slivers, but NOT on every ray: a ray within ~1e-2 rad of an ordinary
+                                       triangle's plane can be accepted by Moller-Trumbore outside the triangle's padded box, and then
+                                       the own leaves miss a hit the reference reports (measured: 1 - 4 closest hits per 10^5 rays
+                                       aimed at triangle edges at 1e-7 ... 1e-2 rad, none at larger angles).
+                                       On scenes made mostly of slivers the own leaves do more work than mode 1 (a strip floor: about
+                                       2 x the closest-hit and 8 x the any-hit estimate). 1 is the strict mode;
                                    0 = library default (2) */
     uint32_t leaf_tris;         /* leaves = 2: most triangles per own leaf, 1 .. 32; 0 = library default (measured: profiles/README.md) */
     uint32_t reserved[1];       /* must be 0 */
@@ -138,7 +145,9 @@ typedef struct ptmi_stats {
     uint32_t extend_variant, shadow_variant;   /* of the last dispatch, the memory variant the closest-hit / any-hit kernel ran as:
                                                 * variant number * 10 + workgroups per CU (e.g. 102: variant 10 with two) */
     /* leaves = 2: closest hits / occluders whose reference leaf's box did not pass and rays that were therefore traced again over the
-     * uploaded tree (both kernels together), since the last reset */
+     * uploaded tree (both kernels together), since the last reset. Also counted: a lane whose stack ran out and that reported its hit
+     * unverified (cannot happen while the stack is deeper than the tree; counted so that a count equal to tools/own_sim.c's — whose
+     * stack never runs out — shows it did not) */
     uint64_t verify_failed;
     uint32_t tree_builder_used; /* who built the hierarchy the last upload's regular rays walk: 1 the host, 2 the device (both leaf modes);
                                    0 none: the uploaded tree is walked as it is (keep_reference_tree, an empty scene, a tree with

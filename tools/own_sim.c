@@ -159,8 +159,9 @@ static void trace_one(const own_sim_scene *s, int own, int quant, int cull, int 
             for (;;) {
                 if (cur == REF_NONE && sp > 0) cur = stack[--sp];
                 const int descent_over = cur == REF_NONE;
-                /* leaves: at once (the best case of the kernels' scheduling) or after the whole descent (the worst) */
-                if (nf && (!deferred || descent_over)) {
+                /* leaves: at once (the best case of the kernels' scheduling) or after the whole descent (the worst) — or when the list
+                 * is full, as a kernel lane without room for a node step takes the triangle stream */
+                if (nf && (!deferred || descent_over || nf + 2 > 256)) {
                     while (nf && !occluded) {
                         uint32_t ref = filed[--nf];
                         uint32_t first = ref & OFF_MASK, cnt = ((ref >> OFF_BITS) & 31u) + 1u;

@@ -17,6 +17,31 @@
 #define PT_OWN_PAD_LOG2 (-16)        /* own leaves' boxes grow by 2^this x the largest coordinate magnitude of the scene */
 #endif
 
+#ifndef PT_OWN_SLIVER
+#define PT_OWN_SLIVER 16.0           /* own leaves: a triangle whose longest edge squared exceeds this x |e1 x e2| is a SLIVER */
+#endif
+
+// Slivers (pt_own_sliver) enter the own hierarchy with the box of their REFERENCE leaf added to their own. Moller-Trumbore's (u, v) lose
+// accuracy as 1 / (sin of the triangle's smallest angle x sin of the ray's angle to its plane): for a thin triangle it can accept a
+// ray that passes far outside the triangle's padded box while the reference still tests the triangle (its leaf box passes), and a
+// hierarchy over the triangles' own boxes would not (tests/test_own_leaves_grazing_host.py: ratios of 100 and up, at any angle). Through
+// the leaf box the own leaves test such a triangle whenever the reference does, whatever the triangle test computes. Every triangle
+// cannot take that path — the leaf boxes are what the own leaves are there to avoid (Cornell: 9.2 triangle tests per closest-hit ray
+// instead of 2.8, more than leaves = 1) — so a non-sliver still relies on the padding, which rays within ~1e-3 rad of its plane can
+// defeat (measured rate). No triangle of the benchmark scenes is a sliver (the largest ratio there is 5.5).
+// Squares only (no square root), products and sums in double without contraction: both builders decide alike.
+__host__ __device__ inline bool pt_own_sliver(const float *a, const float *b, const float *c) {
+#pragma clang fp contract(off)
+    const double e1[3] = {(double)b[0] - a[0], (double)b[1] - a[1], (double)b[2] - a[2]};
+    const double e2[3] = {(double)c[0] - a[0], (double)c[1] - a[1], (double)c[2] - a[2]};
+    const double e3[3] = {(double)c[0] - b[0], (double)c[1] - b[1], (double)c[2] - b[2]};
+    const double x = e1[1] * e2[2] - e1[2] * e2[1], y = e1[2] * e2[0] - e1[0] * e2[2], z = e1[0] * e2[1] - e1[1] * e2[0];
+    const double l1 = e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2], l2 = e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2];
+    const double l3 = e3[0] * e3[0] + e3[1] * e3[1] + e3[2] * e3[2];
+    const double longest = l1 > l2 ? (l1 > l3 ? l1 : l3) : (l2 > l3 ? l2 : l3);
+    return longest * longest > (PT_OWN_SLIVER * PT_OWN_SLIVER) * (x * x + y * y + z * z);
+}
+
 struct PtFastLeaf {
     float mn[3], mx[3];     // the leaf's own box, as stored in the reference node
     uint32_t ref;           // PT_REF_LEAF | (count-1) << 26 | first triangle
@@ -64,9 +89,10 @@ struct PtOwnTree : PtOwnTreeHeader {
 };
 struct ptmi_triangle;
 // which: the original indices of the triangles to build over (those some reachable reference leaf lists), ascending.
+// leafbox: per ORIGINAL triangle index, (min.xyz, 0), (max.xyz, 0) of the reference leaf that lists it (added to a sliver's box).
 // depth_limit: most levels (leaves included) the tree may have. false: a vertex is not finite (the caller keeps the reference's leaves).
-bool pt_build_own_tree(const ptmi_triangle *tris, const std::vector<uint32_t> &which, uint32_t max_leaf, uint32_t depth_limit,
-                       PtOwnTree &out);
+bool pt_build_own_tree(const ptmi_triangle *tris, const std::vector<uint32_t> &which, const std::vector<float4> &leafbox,
+                       uint32_t max_leaf, uint32_t depth_limit, PtOwnTree &out);
 // The same tree built on the device `s` belongs to (own_tree_gpu.hip; ptmi_options.tree_builder = 2), from the device copy of the
 // triangles: Morton-sorted clusters merged by PLOC, collapsed with the host's cost model, emitted and quantised in place. The device
 // buffers have the layouts of PtOwnTree::wnodes / tripos and of pt_quantize_nodes (qnodes: NULL when the scene has no quantised image);
@@ -80,8 +106,8 @@ struct PtOwnTreeGpu : PtOwnTreeHeader {
     float q_origin[3] = {0, 0, 0}, q_scale[3] = {0, 0, 0};
     void release();                        // frees the device buffers (hipFree) and resets the fields
 };
-bool pt_build_own_tree_gpu(const ptmi_triangle *d_tris, const std::vector<uint32_t> &which, uint32_t max_leaf, uint32_t depth_limit,
-                           hipStream_t s, PtOwnTreeGpu &out);
+bool pt_build_own_tree_gpu(const ptmi_triangle *d_tris, const std::vector<uint32_t> &which, const std::vector<float4> &leafbox,
+                           uint32_t max_leaf, uint32_t depth_limit, hipStream_t s, PtOwnTreeGpu &out);
 // The 16-bit grid of pt_quantize_nodes over the bounds [mn, mx]: origin = mn, the smallest scale whose last plane reaches mx (checked
 // with fmaf). false: the bounds are not finite.
 bool pt_quant_grid(const float mn[3], const float mx[3], float origin[3], float scale[3]);

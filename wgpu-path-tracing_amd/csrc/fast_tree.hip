@@ -360,13 +360,14 @@ struct Collapse {
 
 }  // namespace
 
-bool pt_build_own_tree(const ptmi_triangle *tris, const std::vector<uint32_t> &which, uint32_t max_leaf, uint32_t depth_limit,
-                       PtOwnTree &out) {
+bool pt_build_own_tree(const ptmi_triangle *tris, const std::vector<uint32_t> &which, const std::vector<float4> &leafbox,
+                       uint32_t max_leaf, uint32_t depth_limit, PtOwnTree &out) {
     out = PtOwnTree();
     const uint32_t n = (uint32_t)which.size();
     if (n == 0) return false;
     max_leaf = std::max(1u, std::min(max_leaf, PT_LEAF_MAX_TRIS));
-    // one "leaf" per triangle: the box of its three vertices and of v0 + e1, v0 + e2 as the intersection test sees them
+    // one "leaf" per triangle: the box of its three vertices and of v0 + e1, v0 + e2 as the intersection test sees them, a sliver's
+    // grown by its reference leaf's box (fast_tree.h pt_own_sliver); the padding comes from the largest coordinate of these boxes
     std::vector<PtFastLeaf> units(n);
     double biggest = 0.0;
     for (uint32_t i = 0; i < n; i++) {
@@ -378,8 +379,14 @@ bool pt_build_own_tree(const ptmi_triangle *tris, const std::vector<uint32_t> &w
             if (!std::isfinite(a) || !std::isfinite(b) || !std::isfinite(c) || !std::isfinite(b2) || !std::isfinite(c2)) return false;
             u.mn[k] = std::min(std::min(std::min(a, b), std::min(c, b2)), c2);
             u.mx[k] = std::max(std::max(std::max(a, b), std::max(c, b2)), c2);
-            biggest = std::max(biggest, std::max(std::fabs((double)u.mn[k]), std::fabs((double)u.mx[k])));
         }
+        if (pt_own_sliver(t.v0, t.v1, t.v2)) {           // fast_tree.h: a sliver's box grows by its reference leaf's (not the padding)
+            const float4 lo = leafbox[2 * (size_t)which[i]], hi = leafbox[2 * (size_t)which[i] + 1];
+            const float l[3] = {lo.x, lo.y, lo.z}, h[3] = {hi.x, hi.y, hi.z};
+            for (int k = 0; k < 3; k++) { u.mn[k] = std::min(u.mn[k], l[k]); u.mx[k] = std::max(u.mx[k], h[k]); }
+        }
+        // (after the union: an uploaded tree's leaf box may reach beyond its triangles, and the padding must cover what is walked)
+        for (int k = 0; k < 3; k++) biggest = std::max(biggest, std::max(std::fabs((double)u.mn[k]), std::fabs((double)u.mx[k])));
         u.ref = PT_REF_LEAF | i; u.weight = 1u;
     }
     const bool dbg = std::getenv("PTMI_TREE_DEBUG") != nullptr;

@@ -4,8 +4,9 @@
 // quantisation rules), over another topology. Any topology is allowed: the kernels break ties by the lowest
 // triangle index and verify every winner against its reference leaf's box, so only the work per ray depends on the tree.
 //
-//   units     one box per listed triangle, min / max over a, b, c, a + (b - a), a + (c - a) as the host computes them; |coordinate|
-//             max-reduced for the padding (exact in f32)
+//   units     one box per listed triangle, min / max over a, b, c, a + (b - a), a + (c - a) as the host computes them, a sliver's
+//             grown by its reference leaf's box (fast_tree.h pt_own_sliver); |coordinate| of the unit boxes max-reduced for the
+//             padding (exact in f32)
 //   PLOC      Morton codes of the unit centroids, made unique by the unit's index and radix-sorted (hipCUB); then repeatedly: every
 //             cluster's nearest neighbour within +-PT_PLOC_RADIUS sorted positions (smallest surface area of the union, ties to the
 //             lower position), mutual pairs merged into a new node at the lower position, survivors compacted in order by a prefix sum
@@ -74,8 +75,8 @@ struct Red {                          // reductions of the build, zeroed before 
     uint32_t qmin[3], qmax[3];        // ord() of the padded child boxes' bounds
 };
 
-__global__ void k_units(uint32_t n, const ptmi_triangle *__restrict__ tris, const uint32_t *__restrict__ which, Box6 *__restrict__ box,
-                        Red *red) {
+__global__ void k_units(uint32_t n, const ptmi_triangle *__restrict__ tris, const uint32_t *__restrict__ which,
+                        const float4 *__restrict__ leafbox, Box6 *__restrict__ box, Red *red) {
     const uint32_t i = blockIdx.x * TB + threadIdx.x;
     if (i >= n) return;
     const ptmi_triangle &t = tris[which[i]];
@@ -86,8 +87,14 @@ __global__ void k_units(uint32_t n, const ptmi_triangle *__restrict__ tris, cons
         if (!isfinite(a) || !isfinite(b) || !isfinite(c) || !isfinite(b2) || !isfinite(c2)) bad = 1;
         u.mn[k] = mn_(mn_(mn_(a, b), mn_(c, b2)), c2);
         u.mx[k] = mx_(mx_(mx_(a, b), mx_(c, b2)), c2);
-        big = max(big, max(__float_as_uint(fabsf(u.mn[k])), __float_as_uint(fabsf(u.mx[k]))));
     }
+    if (pt_own_sliver(t.v0, t.v1, t.v2)) {                       // as the host: a sliver's box grows by its reference leaf's
+        const float4 lo = leafbox[2 * (size_t)which[i]], hi = leafbox[2 * (size_t)which[i] + 1];
+        const float l[3] = {lo.x, lo.y, lo.z}, h[3] = {hi.x, hi.y, hi.z};
+        for (int k = 0; k < 3; k++) { u.mn[k] = mn_(u.mn[k], l[k]); u.mx[k] = mx_(u.mx[k], h[k]); }
+    }
+    for (int k = 0; k < 3; k++)                                  // (after the union, as the host)
+        big = max(big, max(__float_as_uint(fabsf(u.mn[k])), __float_as_uint(fabsf(u.mx[k]))));
     box[i] = u;
     if (bad) { atomicOr(&red->bad, 1u); return; }
     atomicMax(&red->biggest, big);
@@ -335,8 +342,8 @@ template <class T> void dfree(T *&p) { if (p) { (void)hipFree(p); p = nullptr; }
 
 #define GT(expr) do { if ((expr) != hipSuccess) goto done; } while (0)
 
-bool pt_build_own_tree_gpu(const ptmi_triangle *d_tris, const std::vector<uint32_t> &which, uint32_t max_leaf, uint32_t depth_limit,
-                           hipStream_t s, PtOwnTreeGpu &out) {
+bool pt_build_own_tree_gpu(const ptmi_triangle *d_tris, const std::vector<uint32_t> &which, const std::vector<float4> &leafbox,
+                           uint32_t max_leaf, uint32_t depth_limit, hipStream_t s, PtOwnTreeGpu &out) {
     out.release();
     const uint32_t n = (uint32_t)which.size();
     if (n < 2 || n > PT_LEAF_OFF_MASK) return false;
@@ -350,6 +357,7 @@ bool pt_build_own_tree_gpu(const ptmi_triangle *d_tris, const std::vector<uint32
     uint8_t *d_level = nullptr;
     double *d_cost = nullptr, *d_growth = nullptr, *d_growth_sum = nullptr;
     unsigned long long *d_keys = nullptr, *d_keys2 = nullptr, *d_flags = nullptr, *d_ex = nullptr;
+    float4 *d_leafbox = nullptr;
     Box6 *d_box = nullptr; uint2 *d_child = nullptr; Step *d_step = nullptr; Red *d_red = nullptr;
     float4 *d_wn = nullptr, *d_tp = nullptr; uint4 *d_qn = nullptr;
     void *d_tmp = nullptr; size_t tmp_bytes = 0;
@@ -361,11 +369,13 @@ bool pt_build_own_tree_gpu(const ptmi_triangle *d_tris, const std::vector<uint32
     GT(hipMalloc(&d_which, (size_t)n * 4)); GT(hipMalloc(&d_box, (size_t)n_all * sizeof(Box6)));
     GT(hipMalloc(&d_red, sizeof(Red)));
     GT(hipMemcpyAsync(d_which, which.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    GT(hipMalloc(&d_leafbox, leafbox.size() * sizeof(float4)));
+    GT(hipMemcpyAsync(d_leafbox, leafbox.data(), leafbox.size() * sizeof(float4), hipMemcpyHostToDevice, s));
     {
         Red r0{}; r0.biggest = 0; r0.bad = 0;
         for (int k = 0; k < 3; k++) { r0.cmin[k] = r0.qmin[k] = 0xFFFFFFFFu; r0.cmax[k] = r0.qmax[k] = 0u; }
         GT(hipMemcpyAsync(d_red, &r0, sizeof r0, hipMemcpyHostToDevice, s));
-        k_units<<<blocks(n), TB, 0, s>>>(n, d_tris, d_which, d_box, d_red);
+        k_units<<<blocks(n), TB, 0, s>>>(n, d_tris, d_which, d_leafbox, d_box, d_red);
         GT(hipMemcpyAsync(&h, d_red, sizeof h, hipMemcpyDeviceToHost, s));
         GT(hipStreamSynchronize(s));
         GT(hipGetLastError());
@@ -502,7 +512,7 @@ bool pt_build_own_tree_gpu(const ptmi_triangle *d_tris, const std::vector<uint32
     ok = true;
 done:
     (void)hipStreamSynchronize(s);                               // nothing of ours may still run when the scratch goes
-    dfree(d_which); dfree(d_clu[0]); dfree(d_clu[1]); dfree(d_nn); dfree(d_parent); dfree(d_arr); dfree(d_cnt); dfree(d_icnt);
+    dfree(d_which); dfree(d_leafbox); dfree(d_clu[0]); dfree(d_clu[1]); dfree(d_nn); dfree(d_parent); dfree(d_arr); dfree(d_cnt); dfree(d_icnt);
     dfree(d_leafy); dfree(d_renum); dfree(d_rest_f); dfree(d_rest); dfree(d_grown); dfree(d_grown_sum); dfree(d_cost);
     dfree(d_growth); dfree(d_growth_sum); dfree(d_keys); dfree(d_keys2); dfree(d_flags); dfree(d_ex); dfree(d_box); dfree(d_child);
     dfree(d_step); dfree(d_red); dfree(d_level); dfree(d_wn); dfree(d_tp); dfree(d_qn); dfree(d_tmp);

@@ -348,13 +348,13 @@ uint32_t leaf_ref(const ptmi_bvh_node &n) {
 // The own tree on `device` (own_tree_gpu.hip) from a device copy of the triangles, made first and kept as b's kTris for the upload to
 // take over. false: not built (the caller builds on the host).
 bool own_tree_on_device(hipStream_t stream, int device, const ptmi_triangle *tris, uint32_t nt, const std::vector<uint32_t> &which,
-                        uint32_t k_max, uint32_t limit, Built &b, PtOwnTreeGpu &g) {
+                        const std::vector<float4> &leafbox, uint32_t k_max, uint32_t limit, Built &b, PtOwnTreeGpu &g) {
     const size_t bytes = (size_t)nt * sizeof(ptmi_triangle);
     void *d_tris = nullptr;
     if (hipMalloc(&d_tris, bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
     if (hipMemcpy(d_tris, tris, bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_tris); (void)hipGetLastError(); return false; }
     b.on_device(kTris, d_tris, bytes, device);
-    return pt_build_own_tree_gpu(static_cast<const ptmi_triangle *>(d_tris), which, k_max, limit, stream, g);
+    return pt_build_own_tree_gpu(static_cast<const ptmi_triangle *>(d_tris), which, leafbox, k_max, limit, stream, g);
 }
 
 // Own leaves, after whichever builder ran (on_device: g on `device`, else t): the walked image and its header, the quantised nodes (the
@@ -516,8 +516,8 @@ int build_image(const ptmi_options &opt, hipStream_t stream, int device, const p
         PtOwnTreeGpu g;
         PtOwnTree t;
         const bool on_device = opt.tree_builder == 2u && stream && nt > 4096u && which.size() > 2048u &&
-                               own_tree_on_device(stream, device, tris, nt, which, k_max, limit, b, g);
-        own = on_device || pt_build_own_tree(tris, which, k_max, limit, t);
+                               own_tree_on_device(stream, device, tris, nt, which, leafbox, k_max, limit, b, g);
+        own = on_device || pt_build_own_tree(tris, which, leafbox, k_max, limit, t);
         if (own) own_image(b, on_device, device, g, t, nt, wnodes, std::move(leafbox));
         b.tree_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }

@@ -22,7 +22,8 @@
 //      [2^-60, 2^60], an origin farther than DevScene::safe_origin from the coordinate origin, an unbounded triangle-test determinant.
 // So results equal traverse.hip's bit for bit unless a ray meets a triangle in Moller-Trumbore's arithmetic while missing that
 // triangle's padded bounding box — the padding is 2^-16 of the scene's largest coordinate, 16 x the rounding of the fused test for
-// origins inside the scene; tests/test_gpu_own_leaves.py counts such rays (none in 10^8 and more).
+// origins inside the scene; tests/test_gpu_own_leaves.py counts such rays (none in 10^8 and more). Thin triangles, where that happens at
+// any angle, enter the hierarchy with their reference leaf's box (fast_tree.h pt_own_sliver; tests/test_own_leaves_grazing_host.py).
 //
 // Execution model, majority scheduling and deferred leaves are those of traverse.hip (see there); the memory variants:
 //   OwnLdsMem     exact 64-byte nodes in LDS (+ the triangle images when they fit too)
@@ -392,10 +393,12 @@ PT_DEV void trace_wave_own(const Mem &m, const DevScene &sc, const IO &io, uint3
         const bool stuck = active & !can_node & !can_tri & ((bn | bt) == 0ull);
         const bool done = active & (occluded | stuck | ((cur == PT_REF_NONE) & (lp == top)));
         if (done) {
-            // (a stuck lane reports what it has, unverified: it cannot happen while STACK > tree depth)
+            // (a stuck lane reports what it has, unverified: it cannot happen while STACK > tree depth. It is counted with the
+            // retraced rays in ptmi_stats.verify_failed, so that a count equal to the CPU replay's — whose stack never runs out —
+            // also shows that no lane reported an unverified hit)
             active = false; cur = PT_REF_NONE; lp = top;
             fin = true; fin_occ = occluded;
-            if (stuck) slow = true;
+            if (stuck) { slow = true; n_redo++; }
         }
     }
     if (n_redo) atomicAdd(sc.verify_stat, (unsigned long long)n_redo);
