@@ -115,13 +115,13 @@ typedef struct ptmi_options {
 } ptmi_options;
 
 typedef struct ptmi_stats {
-    uint64_t paths;             /* (pixel, frame) samples traced since the last reset */
+    uint64_t paths;             /* (pixel, frame) samples traced since the last reset (adaptive dispatches: those of the listed pixels) */
     uint64_t segments;          /* path segments = bounce-loop iterations reaching sceneIntersect (pt.wgsl:643-644) */
     uint64_t shadow_rays;       /* shadow traversals of the reference (pt.wgsl:392/421/463). Those whose contribution is
                                    exactly zero (light behind the surface) are counted here but not traced: they cannot
                                    change the radiance */
-    uint64_t dispatches;        /* ptmi_dispatch calls */
-    uint64_t frames;            /* frames traced */
+    uint64_t dispatches;        /* ptmi_dispatch and ptmi_dispatch_adaptive calls */
+    uint64_t frames;            /* frames traced by ptmi_dispatch */
     uint64_t segments_by_bounce[64];
     double   gpu_ms;            /* device time of all dispatches (HIP events on the context's stream) */
     double   extend_ms;         /* ... of the closest-hit traversal kernel only, and its launch count */
@@ -270,6 +270,55 @@ int ptmi_denoise(ptmi_ctx *ctx, const ptmi_denoise_params *params, float *dst_rg
 void *ptmi_denoised_device_ptr(ptmi_ctx *ctx);
 /* ptmi_blit's contract, on the denoised plane (PTMI_E_STATE before the first ptmi_denoise since the last ptmi_resize) */
 int ptmi_blit_denoised(ptmi_ctx *ctx, float *dst_rgba_f32, size_t n_floats, uint8_t *dst_rgba8, size_t n_bytes);
+
+/* ---- adaptive sampling: further frames only for the pixels that have not converged ---------------------------------------------
+ * ptmi_dispatch traces every pixel of the context's rows for every frame. ptmi_dispatch_adaptive lets every pixel be at its own
+ * frame index: the per-pixel sample count is the moments plane's z (ptmi_set_moments(1) is required, else PTMI_E_STATE), and since
+ * the RNG is seeded per (x, y, frame) and every fold is per pixel in frame order, a pixel that has received its frames 0 .. n-1
+ * holds, bit for bit, what an n-frame ptmi_dispatch leaves at that pixel - in the output buffer, the first-hit planes and the moments
+ * plane - whatever its neighbours received.
+ * One call = `rounds` rounds, each entirely on the device. A round
+ *   1. selects. With (m1, m2, n) = moments.xyz of a pixel, all in float32, evaluated left to right, no FMA, no square root, no
+ *      transcendental, and max(a, b) = (a < b ? b : a):
+ *        var = max(m2 - m1 * m1, 0), e = threshold * max(m1, floor), bound = e * e * n;
+ *      a pixel is NOISY iff n < min_frames, or n < max_frames and NOT var <= bound (so a NaN moment stays noisy until max_frames).
+ *      With neighbourhood = 1 a pixel is ACTIVE iff its own n < max_frames and it or one of its 8 neighbours inside the context's
+ *      rows and the image is noisy; with neighbourhood = 0 active = noisy;
+ *   2. lists the active pixels in ascending order (the segment statistics are not touched);
+ *   3. traces, for every active pixel, its frames n .. n + step - 1 through the bounce loop of ptmi_dispatch (`step` is split into
+ *      sub-batches by options.frames_per_batch or by memory like any dispatch; the list is fixed before the first sub-batch), and
+ *   4. folds them, frames ascending, with the arithmetic of ptmi_dispatch's folds; n grows by step.
+ * A pixel is selected or not as a whole, so its count may pass max_frames by less than step. The counts are exact in float up to 2^24.
+ * Deciding from the samples being averaged biases the mean: min_frames and neighbourhood exist to bound that.
+ * camera.frame_index == 0 restarts: the first round treats every count of the context's rows as 0, so frame 0 overwrites; any other
+ * value continues from the plane and is otherwise unused. ptmi_dispatch followed by ptmi_dispatch_adaptive is defined (the uniform
+ * fold keeps z true). A plain ptmi_dispatch after adaptive rounds folds every pixel with the camera's frame index as it always has,
+ * whatever the pixels' own counts: that is the caller's business. Asynchronous, like ptmi_dispatch.
+ * ptmi_stats after one call: paths grows by the samples actually traced (counted on the device, read where ptmi_get_stats
+ * synchronises), frames by nothing, dispatches by one. ptmi_multi has no such call. */
+typedef struct ptmi_adaptive_params {
+    float    threshold;      /* relative standard error of the pixel's mean luminance; > 0 */
+    float    floor;          /* luminance under which the error is taken relative to `floor`; 0 -> 1 (an absolute error below luminance 1) */
+    uint32_t min_frames;     /* every pixel gets at least this many; 0 -> 16 */
+    uint32_t max_frames;     /* and at most this many (plus less than step); 0 -> 4096; <= 2^24 */
+    uint32_t step;           /* frames an active pixel receives per round; 0 -> 16 */
+    uint32_t neighbourhood;  /* 0 / 1 */
+    uint32_t reserved[2];    /* must be 0 */
+} ptmi_adaptive_params;      /* 32 bytes */
+/* a struct tag only (no typedef): the call below has the same name, so write `struct ptmi_adaptive_status` */
+struct ptmi_adaptive_status {
+    uint64_t active;         /* pixels the last round's list held (0 before the first round since ptmi_resize or ptmi_set_moments) */
+    uint64_t samples;        /* sum of the per-pixel counts over the context's rows */
+    uint32_t min_count, max_count;   /* smallest / largest count in the context's rows */
+    uint32_t rounds;         /* rounds since the last restart, ptmi_resize or change of ptmi_set_moments */
+    uint32_t reserved;
+};                           /* 32 bytes */
+/* PTMI_E_STATE: no scene, no output buffer, or the moments plane off. PTMI_E_INVALID: params or camera NULL, a camera of another
+ * size, threshold not > 0 (NaN included), floor negative or not finite, a non-zero reserved word, neighbourhood > 1,
+ * min_frames > max_frames (after the defaults), max_frames > 2^24, step > 2^16. rounds = 0 does nothing. */
+int ptmi_dispatch_adaptive(ptmi_ctx *ctx, const ptmi_camera *camera, const ptmi_adaptive_params *params, uint32_t rounds);
+/* Synchronises. PTMI_E_STATE while the moments plane is off or before ptmi_resize. */
+int ptmi_adaptive_status(ptmi_ctx *ctx, struct ptmi_adaptive_status *out);
 
 /* ---- presentation (the reference's blit pass, src/shader/blit.wgsl:43-155; renderer.ts:434-449) ---- */
 /* Tone-maps the output buffer (exposure 2^1, AgX, gamma 1/2.2) into a width*height canvas, row 0 = top.

@@ -294,6 +294,197 @@ __global__ __launch_bounds__(BLOCK) void k_accumulate_moments(DevBand band, uint
     }
 }
 
+// ---- adaptive sampling (ptmi_dispatch_adaptive; the rule is stated in include/ptmi.h) ------------------------------------------
+// Every pixel is at its own frame index: the moments plane's .z. A round selects the pixels that still get frames (k_ad_select:
+// one ballot word per 64 band pixels), lists them in ascending order with the scatter above (k_ad_tile_sums / k_ad_scatter: the
+// tile totals without k_tile_sums's segment statistics), and raygen and the three folds then walk that list: path
+// k * n_active + j is frame n(list[j]) + k of pixel list[j]. A list entry is a band-local pixel index (local row * width + x).
+PT_DEV float ad_max(float a, float b) { return a < b ? b : a; }       // a NaN in `a` stays
+PT_DEV bool ad_noisy(float4 m, const ptmi_adaptive_params &ap) {
+    const float n = m.z;
+    if (n < (float)ap.min_frames) return true;
+    if (!(n < (float)ap.max_frames)) return false;
+    const float var = ad_max(m.y - m.x * m.x, 0.0f);
+    const float e = ap.threshold * ad_max(m.x, ap.floor);
+    const float bound = e * e * n;
+    return !(var <= bound);
+}
+PT_DEV bool band_has_row(const DevBand &band, uint32_t y) {
+    if (y < band.y0 || y >= band.y1) return false;
+    return band.parts <= 1u || ((y - band.y0) / band.strip) % band.parts == band.part;
+}
+
+// restart: the band's pixels are back at frame 0 (the folds overwrite at frame 0, so only the count has to go)
+__global__ __launch_bounds__(BLOCK) void k_ad_restart(DevBand band, float4 *__restrict__ mom) {
+    const uint32_t npix = band.rows * band.width;
+    for (uint32_t pix = blockIdx.x * BLOCK + threadIdx.x; pix < npix; pix += gridDim.x * BLOCK)
+        mom[(size_t)band.row_of(pix / band.width) * band.width + pix % band.width].z = 0.0f;
+}
+
+// ctl[0] = band pixels (the `count` of the list build). Whole waves stay in the loop so that the ballot sees all 64 lanes.
+__global__ __launch_bounds__(BLOCK) void k_ad_select(DevBand band, ptmi_adaptive_params ap, const float4 *__restrict__ mom,
+                                                     uint64_t *__restrict__ ballot, uint32_t *__restrict__ ctl) {
+    const uint32_t npix = band.rows * band.width;
+    if (blockIdx.x == 0 && threadIdx.x == 0) ctl[0] = npix;
+    const uint32_t padded = (npix + 63u) & ~63u;
+    for (uint32_t pix = blockIdx.x * BLOCK + threadIdx.x; pix < padded; pix += gridDim.x * BLOCK) {
+        bool active = false;
+        if (pix < npix) {
+            const uint32_t y = band.row_of(pix / band.width), x = pix % band.width;
+            const float4 m = mom[(size_t)y * band.width + x];
+            active = ad_noisy(m, ap);
+            if (ap.neighbourhood && !active && m.z < (float)ap.max_frames) {
+                for (int dy = -1; dy <= 1 && !active; dy++) {
+                    const uint32_t ny = y + (uint32_t)dy;                   // y = 0, dy = -1 wraps and fails has_row
+                    if (!band_has_row(band, ny)) continue;
+                    for (int dx = -1; dx <= 1; dx++) {
+                        const uint32_t nx = x + (uint32_t)dx;
+                        if (nx >= band.width || (dx == 0 && dy == 0)) continue;
+                        if (ad_noisy(mom[(size_t)ny * band.width + nx], ap)) { active = true; break; }
+                    }
+                }
+            }
+        }
+        const uint64_t word = __ballot(active);
+        if ((threadIdx.x & 63u) == 0u) ballot[pix >> 6] = word;
+    }
+}
+
+__global__ __launch_bounds__(TILE_WORDS) void k_ad_tile_sums(const uint32_t *__restrict__ count_ptr, const uint64_t *__restrict__ ballot,
+                                                             uint32_t *__restrict__ tile_sums) {
+    __shared__ uint32_t wsum[TILE_WAVES];
+    const uint32_t nwords = (*count_ptr + 63u) >> 6;
+    const uint32_t w = blockIdx.x * TILE_WORDS + threadIdx.x;
+    uint32_t c = w < nwords ? (uint32_t)__popcll(ballot[w]) : 0u;
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
+    if ((threadIdx.x & 63u) == 0u) wsum[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (int i = 0; i < TILE_WAVES; i++) t += wsum[i];
+        tile_sums[blockIdx.x] = t;
+    }
+}
+__global__ __launch_bounds__(TILE_WORDS) void k_ad_scatter(const uint32_t *__restrict__ count_ptr, const uint64_t *__restrict__ ballot,
+                                                           const uint32_t *__restrict__ tile_sums, uint32_t *__restrict__ list,
+                                                           uint32_t *__restrict__ n_active) {
+    scatter_tile<false>(blockIdx.x, count_ptr, nullptr, ballot, tile_sums, list, n_active);
+}
+
+// k_raygen over the list; traced[0] += the paths of this batch (ptmi_stats.paths)
+__global__ __launch_bounds__(BLOCK) void k_ad_raygen(ptmi_camera cam, DevBand band, const uint32_t *__restrict__ list,
+                                                     const uint32_t *__restrict__ n_active, uint32_t n_frames,
+                                                     const float4 *__restrict__ mom, DevPaths P, uint32_t *__restrict__ count_out,
+                                                     unsigned long long *__restrict__ traced) {
+    const uint32_t na = *n_active;
+    const uint32_t total = na * n_frames;
+    if (blockIdx.x == 0 && threadIdx.x == 0) { *count_out = total; atomicAdd(&traced[0], (unsigned long long)total); }
+    for (uint32_t p = blockIdx.x * BLOCK + threadIdx.x; p < total; p += gridDim.x * BLOCK) {
+        const uint32_t k = p / na, pix = list[p - k * na];
+        const uint32_t y = band.row_of(pix / band.width), x = pix % band.width;
+        const uint32_t frame = (uint32_t)mom[(size_t)y * band.width + x].z + k;
+        v3 o, d; uint32_t rng;
+        camera_ray(cam, x, y, frame, o, d, rng);
+        init_path(P, p, o, d, rng);
+    }
+}
+
+// k_accumulate, k_accumulate_aov, k_accumulate_moments over the list: each pixel from its own frame index (mom.z, which the moments
+// fold, launched last, moves on)
+__global__ __launch_bounds__(BLOCK) void k_ad_accumulate(DevBand band, const uint32_t *__restrict__ list, const uint32_t *__restrict__ n_active,
+                                                         uint32_t n_frames, const float4 *__restrict__ mom, const float *__restrict__ L,
+                                                         uint32_t l_stride, float4 *__restrict__ out) {
+    const uint32_t na = *n_active;
+    for (uint32_t j = blockIdx.x * BLOCK + threadIdx.x; j < na; j += gridDim.x * BLOCK) {
+        const uint32_t pix = list[j];
+        const size_t oi = (size_t)band.row_of(pix / band.width) * band.width + pix % band.width;
+        const uint32_t frame0 = (uint32_t)mom[oi].z;
+        float4 acc = out[oi];
+        for (uint32_t k = 0; k < n_frames; k++) {
+            const size_t li = (size_t)k * na + j;
+            rgb_sc l;
+            if (l_stride == 4u) { const float4 v = reinterpret_cast<const float4 *>(L)[li]; l = rgb_sc{v.x, v.y, v.z}; }
+            else l = reinterpret_cast<const rgb_sc *>(L)[li];
+            float cx = min1(l.x, 2.5f), cy = min1(l.y, 2.5f), cz = min1(l.z, 2.5f);
+            const uint32_t frame = frame0 + k;
+            if (frame > 0u) {
+                const float t = 1.0f / (float)(frame + 1u);
+                cx = mix1(acc.x, cx, t); cy = mix1(acc.y, cy, t); cz = mix1(acc.z, cz, t);
+            }
+            acc = make_float4(cx, cy, cz, 0.0f);
+        }
+        out[oi] = acc;
+    }
+}
+__global__ __launch_bounds__(BLOCK) void k_ad_accumulate_aov(DevBand band, const uint32_t *__restrict__ list, const uint32_t *__restrict__ n_active,
+                                                             uint32_t n_frames, const float4 *__restrict__ mom, const float4 *__restrict__ rec,
+                                                             const ptmi_triangle *__restrict__ tris, uint32_t n_tris,
+                                                             float4 *__restrict__ albedo, float4 *__restrict__ normal, uint2 *__restrict__ ids) {
+    const uint32_t na = *n_active;
+    for (uint32_t j = blockIdx.x * BLOCK + threadIdx.x; j < na; j += gridDim.x * BLOCK) {
+        const uint32_t pix = list[j];
+        const size_t oi = (size_t)band.row_of(pix / band.width) * band.width + pix % band.width;
+        const uint32_t frame0 = (uint32_t)mom[oi].z;
+        float4 a = albedo ? albedo[oi] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        float4 n = normal ? normal[oi] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        uint32_t tri = 0xFFFFFFFFu;
+        for (uint32_t k = 0; k < n_frames; k++) {
+            const size_t li = (size_t)k * na + j;
+            const float4 ra = ld_stream(&rec[2 * li]), rn = ld_stream(&rec[2 * li + 1]);
+            tri = __float_as_uint(rn.w);
+            float4 xa = make_float4(ra.x, ra.y, ra.z, tri != 0xFFFFFFFFu ? 1.0f : 0.0f);
+            float4 xn = make_float4(rn.x, rn.y, rn.z, ra.w);
+            const uint32_t frame = frame0 + k;
+            if (frame > 0u) {
+                const float t = 1.0f / (float)(frame + 1u);
+                xa = make_float4(mix1(a.x, xa.x, t), mix1(a.y, xa.y, t), mix1(a.z, xa.z, t), mix1(a.w, xa.w, t));
+                xn = make_float4(mix1(n.x, xn.x, t), mix1(n.y, xn.y, t), mix1(n.z, xn.z, t), mix1(n.w, xn.w, t));
+            }
+            a = xa; n = xn;
+        }
+        if (albedo) albedo[oi] = a;
+        if (normal) normal[oi] = n;
+        if (ids) ids[oi] = make_uint2(tri, tri < n_tris ? tris[tri].material_index : 0xFFFFFFFFu);
+    }
+}
+__global__ __launch_bounds__(BLOCK) void k_ad_accumulate_moments(DevBand band, const uint32_t *__restrict__ list,
+                                                                 const uint32_t *__restrict__ n_active, uint32_t n_frames,
+                                                                 const float *__restrict__ L, uint32_t l_stride, float4 *__restrict__ mom) {
+    const uint32_t na = *n_active;
+    for (uint32_t j = blockIdx.x * BLOCK + threadIdx.x; j < na; j += gridDim.x * BLOCK) {
+        const uint32_t pix = list[j];
+        const size_t oi = (size_t)band.row_of(pix / band.width) * band.width + pix % band.width;
+        float4 acc = mom[oi];
+        const uint32_t frame0 = (uint32_t)acc.z;
+        for (uint32_t k = 0; k < n_frames; k++) {
+            const size_t li = (size_t)k * na + j;
+            rgb_sc l;
+            if (l_stride == 4u) { const float4 v = reinterpret_cast<const float4 *>(L)[li]; l = rgb_sc{v.x, v.y, v.z}; }
+            else l = reinterpret_cast<const rgb_sc *>(L)[li];
+            const float lum = 0.2126f * min1(l.x, 2.5f) + 0.7152f * min1(l.y, 2.5f) + 0.0722f * min1(l.z, 2.5f);
+            float m1 = lum, m2 = lum * lum;
+            const uint32_t frame = frame0 + k;
+            if (frame > 0u) {
+                const float t = 1.0f / (float)(frame + 1u);
+                m1 = mix1(acc.x, m1, t); m2 = mix1(acc.y, m2, t);
+            }
+            acc = make_float4(m1, m2, (float)(frame + 1u), 0.0f);
+        }
+        mom[oi] = acc;
+    }
+}
+
+// ptmi_adaptive_status: acc[1] += the band's counts, acc[2] / acc[3] = their minimum / maximum (the caller presets 0, ~0, 0)
+__global__ __launch_bounds__(BLOCK) void k_ad_status(DevBand band, const float4 *__restrict__ mom, unsigned long long *__restrict__ acc) {
+    const uint32_t npix = band.rows * band.width;
+    unsigned long long sum = 0, lo = ~0ull, hi = 0;
+    for (uint32_t pix = blockIdx.x * BLOCK + threadIdx.x; pix < npix; pix += gridDim.x * BLOCK) {
+        const unsigned long long n = (uint32_t)mom[(size_t)band.row_of(pix / band.width) * band.width + pix % band.width].z;
+        sum += n; lo = n < lo ? n : lo; hi = n > hi ? n : hi;
+    }
+    if (lo != ~0ull) { atomicAdd(&acc[1], sum); atomicMin(&acc[2], lo); atomicMax(&acc[3], hi); }
+}
+
 // ---- multi-GPU gather (ptmi_multi_gather): a device's rows (DevBand: the strips part, part + parts, ...) <-> one contiguous
 // buffer of band.rows x width float4, local row l of the buffer = frame row band.row_of(l)
 __global__ __launch_bounds__(BLOCK) void k_pack_rows(DevBand band, const float4 *__restrict__ frame, float4 *__restrict__ packed) {
@@ -449,6 +640,39 @@ void pt_launch_accumulate_moments(hipStream_t s, int blocks, DevBand band, uint3
                                   uint32_t l_stride, float4 *mom) {
     hipLaunchKernelGGL(k_accumulate_moments, dim3(blocks), dim3(BLOCK), 0, s, band, frame0, n_frames, L, l_stride, mom);
 }
+void pt_launch_adaptive_restart(hipStream_t s, int blocks, DevBand band, float4 *mom) {
+    hipLaunchKernelGGL(k_ad_restart, dim3(blocks), dim3(BLOCK), 0, s, band, mom);
+}
+void pt_launch_adaptive_list(hipStream_t s, int blocks, DevBand band, const ptmi_adaptive_params &ap, const float4 *mom, DevAdaptive ad) {
+    const uint32_t npix = band.rows * band.width;
+    const int tiles = (int)(((npix + 63u) / 64u + TILE_WORDS - 1) / TILE_WORDS);
+    hipLaunchKernelGGL(k_ad_select, dim3(blocks), dim3(BLOCK), 0, s, band, ap, mom, ad.ballot, ad.ctl);
+    hipLaunchKernelGGL(k_ad_tile_sums, dim3(tiles), dim3(TILE_WORDS), 0, s, &ad.ctl[0], ad.ballot, ad.tile_sums);
+    hipLaunchKernelGGL(k_ad_scatter, dim3(tiles), dim3(TILE_WORDS), 0, s, &ad.ctl[0], ad.ballot, ad.tile_sums, ad.list, &ad.ctl[1]);
+}
+void pt_launch_adaptive_raygen(hipStream_t s, int blocks, const ptmi_camera &cam, DevBand band, DevAdaptive ad, uint32_t n_frames,
+                               const float4 *mom, DevPaths p, uint32_t *count_out) {
+    hipLaunchKernelGGL(k_ad_raygen, dim3(blocks), dim3(BLOCK), 0, s, cam, band, ad.list, &ad.ctl[1], n_frames, mom, p, count_out, ad.acc);
+}
+void pt_launch_adaptive_accumulate(hipStream_t s, int blocks, DevBand band, DevAdaptive ad, uint32_t n_frames, const float4 *mom,
+                                   const float *L, uint32_t l_stride, float4 *out) {
+    hipLaunchKernelGGL(k_ad_accumulate, dim3(blocks), dim3(BLOCK), 0, s, band, ad.list, &ad.ctl[1], n_frames, mom, L, l_stride, out);
+}
+void pt_launch_adaptive_accumulate_aov(hipStream_t s, int blocks, DevBand band, DevAdaptive ad, uint32_t n_frames, const float4 *mom,
+                                       const float4 *rec, const ptmi_triangle *tris, uint32_t n_tris, float4 *albedo, float4 *normal,
+                                       uint2 *ids) {
+    hipLaunchKernelGGL(k_ad_accumulate_aov, dim3(blocks), dim3(BLOCK), 0, s, band, ad.list, &ad.ctl[1], n_frames, mom, rec, tris, n_tris,
+                       albedo, normal, ids);
+}
+void pt_launch_adaptive_accumulate_moments(hipStream_t s, int blocks, DevBand band, DevAdaptive ad, uint32_t n_frames, const float *L,
+                                           uint32_t l_stride, float4 *mom) {
+    hipLaunchKernelGGL(k_ad_accumulate_moments, dim3(blocks), dim3(BLOCK), 0, s, band, ad.list, &ad.ctl[1], n_frames, L, l_stride, mom);
+}
+void pt_launch_adaptive_status(hipStream_t s, int blocks, DevBand band, const float4 *mom, DevAdaptive ad) {
+    hipLaunchKernelGGL(k_ad_status, dim3(blocks), dim3(BLOCK), 0, s, band, mom, ad.acc);
+}
+// tile totals the list build of `npix` pixels needs (DevAdaptive::tile_sums)
+uint32_t pt_adaptive_tiles(uint32_t npix) { return ((npix + 63u) / 64u + TILE_WORDS - 1) / TILE_WORDS; }
 void pt_launch_pack_rows(hipStream_t s, int blocks, DevBand band, const float4 *frame, float4 *packed) {
     hipLaunchKernelGGL(k_pack_rows, dim3(blocks), dim3(BLOCK), 0, s, band, frame, packed);
 }

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "ptmi_layout.h"
+#include "ptmi.h"
 
 #define PT_HD __host__ __device__ inline
 
@@ -237,6 +238,30 @@ void pt_launch_accumulate_aov(hipStream_t s, int blocks, DevBand band, uint32_t 
 // the sample-moments plane (ptmi_set_moments) from the batch's per-path radiance, frames in ascending order like pt_launch_accumulate
 void pt_launch_accumulate_moments(hipStream_t s, int blocks, DevBand band, uint32_t frame0, uint32_t n_frames, const float *L,
                                   uint32_t l_stride, float4 *mom);
+// adaptive sampling (ptmi_dispatch_adaptive; kernels in pipeline.hip): the context's buffers of a round
+struct DevAdaptive {
+    uint64_t *ballot;             // one word per 64 band pixels: bit set = the pixel gets frames this round
+    uint32_t *list;               // ... as the ascending list of band-local pixel indices
+    uint32_t *tile_sums;          // pt_adaptive_tiles(band pixels) words
+    uint32_t *ctl;                // [0] band pixels, [1] length of the list
+    unsigned long long *acc;      // [0] paths traced by adaptive dispatches; [1] sum, [2] min, [3] max of the counts (status)
+};
+uint32_t pt_adaptive_tiles(uint32_t npix);
+void pt_launch_adaptive_restart(hipStream_t s, int blocks, DevBand band, float4 *mom);          // every count of the band back to 0
+// select + list build: ad.ballot, ad.list, ad.ctl of this round from the moments plane
+void pt_launch_adaptive_list(hipStream_t s, int blocks, DevBand band, const ptmi_adaptive_params &ap, const float4 *mom, DevAdaptive ad);
+// path k * n_active + j = frame mom.z + k of pixel list[j], k < n_frames; *count_out = n_active * n_frames
+void pt_launch_adaptive_raygen(hipStream_t s, int blocks, const ptmi_camera &cam, DevBand band, DevAdaptive ad, uint32_t n_frames,
+                               const float4 *mom, DevPaths p, uint32_t *count_out);
+// the three folds over the list, each pixel from its own frame index mom.z; the moments fold goes last (it moves mom.z on)
+void pt_launch_adaptive_accumulate(hipStream_t s, int blocks, DevBand band, DevAdaptive ad, uint32_t n_frames, const float4 *mom,
+                                   const float *L, uint32_t l_stride, float4 *out);
+void pt_launch_adaptive_accumulate_aov(hipStream_t s, int blocks, DevBand band, DevAdaptive ad, uint32_t n_frames, const float4 *mom,
+                                       const float4 *rec, const ptmi_triangle *tris, uint32_t n_tris, float4 *albedo, float4 *normal,
+                                       uint2 *ids);
+void pt_launch_adaptive_accumulate_moments(hipStream_t s, int blocks, DevBand band, DevAdaptive ad, uint32_t n_frames, const float *L,
+                                           uint32_t l_stride, float4 *mom);
+void pt_launch_adaptive_status(hipStream_t s, int blocks, DevBand band, const float4 *mom, DevAdaptive ad);
 // the denoiser (denoise.hip, ptmi_denoise): a prepass into guide / grad / cv, then `iterations` a-trous passes ping-ponging between
 // cv and tmp, the last remodulating into out. albedo NULL: no demodulation. cv is overwritten.
 struct DenoiseArgs {

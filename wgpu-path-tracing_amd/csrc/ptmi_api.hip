@@ -88,6 +88,11 @@ struct ptmi_ctx {
     // sample-moments plane (ptmi_set_moments): W x H float4, present while on and the output buffer exists
     bool moments_on = false;
     float4 *d_moments = nullptr;
+    // adaptive sampling (ptmi_dispatch_adaptive): ballot words, pixel list and tile totals sized for ad_px pixels (made by the first
+    // adaptive dispatch after a resize), control words and counters for the context's life
+    DevAdaptive ad{};
+    size_t ad_px = 0;
+    uint32_t ad_rounds = 0;                            // rounds since the last restart
     // the denoiser's planes (ptmi_denoise), W x H each, made by its first call after a resize: guide (unit normal, depth), depth
     // gradient, two ping-pong colour + variance planes, and the result
     float4 *d_dn_guide = nullptr, *d_dn_a = nullptr, *d_dn_b = nullptr, *d_dn_out = nullptr;
@@ -718,6 +723,43 @@ void free_denoise(ptmi_ctx *c) {
     dfree(c->d_dn_guide); dfree(c->d_dn_grad); dfree(c->d_dn_a); dfree(c->d_dn_b); dfree(c->d_dn_out);
 }
 
+void free_adaptive_planes(ptmi_ctx *c) {
+    dfree(c->ad.ballot); dfree(c->ad.list); dfree(c->ad.tile_sums);
+    c->ad_px = 0;
+}
+// the control words live for the context's life (ptmi_get_stats reads acc[0]) ...
+int ensure_adaptive_words(ptmi_ctx *c) {
+    if (!c->ad.ctl) {
+        HIP_TRY(c, hipMalloc(&c->ad.ctl, 4 * sizeof(uint32_t)));
+        HIP_TRY(c, hipMemset(c->ad.ctl, 0, 4 * sizeof(uint32_t)));
+    }
+    if (!c->ad.acc) {
+        HIP_TRY(c, hipMalloc(&c->ad.acc, 4 * sizeof(unsigned long long)));
+        HIP_TRY(c, hipMemset(c->ad.acc, 0, 4 * sizeof(unsigned long long)));
+    }
+    return PTMI_OK;
+}
+// ... the planes follow the output buffer's size and are made by the first adaptive dispatch that needs them
+int ensure_adaptive(ptmi_ctx *c) {
+    const int rc = ensure_adaptive_words(c);
+    if (rc) return rc;
+    const size_t px = (size_t)c->W * c->H;
+    if (c->ad_px == px && c->ad.list) return PTMI_OK;
+    HIP_TRY(c, sync_all(c));
+    free_adaptive_planes(c);
+    HIP_TRY(c, hipMalloc(&c->ad.ballot, (px / 64 + 1) * 8));
+    HIP_TRY(c, hipMalloc(&c->ad.list, px * 4));
+    HIP_TRY(c, hipMalloc(&c->ad.tile_sums, (size_t)pt_adaptive_tiles((uint32_t)px) * 4));
+    c->ad_px = px;
+    return PTMI_OK;
+}
+// a fresh moments plane (ptmi_resize, ptmi_set_moments): no round has listed anything in it
+int reset_adaptive_rounds(ptmi_ctx *c) {
+    if (c->ad.ctl) HIP_TRY(c, hipMemset(c->ad.ctl, 0, 4 * sizeof(uint32_t)));
+    c->ad_rounds = 0;
+    return PTMI_OK;
+}
+
 int check_ready(ptmi_ctx *c, bool need_output) {
     if (!c) return PTMI_E_INVALID;
     if (!c->have_scene) return fail(c, PTMI_E_STATE, "no scene uploaded (ptmi_upload_scene)");
@@ -837,6 +879,7 @@ int ptmi_destroy(ptmi_ctx *c) {
     dfree(c->d_atlas);
     dfree(c->d_out_own); dfree(c->d_aov_albedo); dfree(c->d_aov_normal); dfree(c->d_aov_id); dfree(c->d_stats); dfree(c->d_scene); dfree(c->d_blit_f32); dfree(c->d_blit_u8);
     dfree(c->d_moments); free_denoise(c);
+    free_adaptive_planes(c); dfree(c->ad.ctl); dfree(c->ad.acc);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
     return PTMI_OK;
@@ -1026,6 +1069,8 @@ int ptmi_resize(ptmi_ctx *c, uint32_t w, uint32_t h) {
     HIP_TRY(c, hipMemset(c->d_out_own, 0, bytes));
     c->d_out = c->d_out_own; c->W = w; c->H = h;
     free_denoise(c);
+    free_adaptive_planes(c);
+    if (int rc_ = reset_adaptive_rounds(c)) return rc_;
     dfree(c->d_moments);                         // never left at the old size
     int rc = alloc_aov_planes(c, c->aov_mask, true);
     if (rc == PTMI_OK && c->moments_on) rc = alloc_moments(c);
@@ -1055,14 +1100,22 @@ int ptmi_get_options(const ptmi_ctx *c, ptmi_options *o) {
     *o = c->opt; return PTMI_OK;
 }
 
-int ptmi_dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames) {
+}  // extern "C"
+
+namespace {
+
+// ptmi_dispatch (ap NULL: n_frames frames of every pixel of the band, from cam->frame_index) and ptmi_dispatch_adaptive (ap: `rounds`
+// rounds of ap->step frames for the listed pixels, each from its own count). Both run the same bounce loop per batch; they differ in
+// the raygen in front of it and the folds behind it.
+int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_adaptive_params *ap, uint32_t rounds) {
     int rc = check_ready(c, true);
     if (rc) return rc;
     if (!cam) return fail(c, PTMI_E_INVALID, "camera is NULL");
     if (cam->width != c->W || cam->height != c->H)
         return fail(c, PTMI_E_INVALID, "camera says %ux%u but the output buffer is %ux%u", cam->width, cam->height, c->W, c->H);
-    if (n_frames == 0) return PTMI_OK;
+    if (n_frames == 0 || (ap && rounds == 0)) return PTMI_OK;
     HIP_TRY(c, hipSetDevice(c->device));
+    if (ap && (rc = ensure_adaptive(c))) return rc;
     const DevBand band = pt_band_of(c->opt, c->W, c->H);
     if (band.y0 >= band.y1) return fail(c, PTMI_E_INVALID, "tile rows [%u,%u) outside the %u-row frame", band.y0, band.y1, c->H);
     if (band.rows == 0) return PTMI_OK;                         // more parts than strips: nothing to render here
@@ -1137,10 +1190,12 @@ int ptmi_dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames) {
         DevPaths tp = ln.tail;
         tp.L = bp.L; tp.l_stride = bp.l_stride;
         float4 *const aov_rec = c->aov_mask ? ln.aov : nullptr;         // written by shade(0), read by the fold after the last bounce
-        for (uint32_t f0 = 0; f0 < n_frames; f0 += F) {
-            const uint32_t fb = std::min(F, n_frames - f0);
-            const uint32_t frame0 = cam->frame_index + f0;
-            { Timed t(c, 4, t3, ms); pt_launch_raygen(ms, blocks, *cam, band, frame0, fb, bp, &ln.counts[0]); }
+        if (ap && cam->frame_index == 0u) { pt_launch_adaptive_restart(ms, blocks, band, c->d_moments); c->ad_rounds = 0; }
+        // a batch: fb frames of every pixel from frame0 on, or (ap) of every listed pixel from its own count on
+        auto batch = [&](uint32_t frame0, uint32_t fb) -> int {
+            { Timed t(c, 4, t3, ms);
+              if (ap) pt_launch_adaptive_raygen(ms, blocks, *cam, band, c->ad, fb, c->d_moments, bp, &ln.counts[0]);
+              else pt_launch_raygen(ms, blocks, *cam, band, frame0, fb, bp, &ln.counts[0]); }
             int cur = 0;
             for (uint32_t b = 0; b < maxb; b++) {
                 const bool tail = b > rb;                                   // the state is in the tail arrays
@@ -1178,12 +1233,32 @@ int ptmi_dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames) {
                 HIP_TRY(c, hipStreamWaitEvent(ms, ln.ev_shadow[(maxb - 1) & 1u], 0));
                 if (maxb >= 2) HIP_TRY(c, hipStreamWaitEvent(ms, ln.ev_shadow[maxb & 1u], 0));
             }
-            { Timed t(c, 6, t3, ms);
-              pt_launch_accumulate(ms, blocks, band, frame0, fb, bp.L, bp.l_stride, c->d_out);
-              if (aov_rec)
-                  pt_launch_accumulate_aov(ms, blocks, band, frame0, fb, aov_rec, c->sc.tris, c->sc.n_tris, c->d_aov_albedo,
-                                           c->d_aov_normal, c->d_aov_id);
-              if (c->d_moments) pt_launch_accumulate_moments(ms, blocks, band, frame0, fb, bp.L, bp.l_stride, c->d_moments); }
+            Timed t(c, 6, t3, ms);
+            if (ap) {                                                   // the moments fold last: the other two read the counts from it
+                pt_launch_adaptive_accumulate(ms, blocks, band, c->ad, fb, c->d_moments, bp.L, bp.l_stride, c->d_out);
+                if (aov_rec)
+                    pt_launch_adaptive_accumulate_aov(ms, blocks, band, c->ad, fb, c->d_moments, aov_rec, c->sc.tris, c->sc.n_tris,
+                                                      c->d_aov_albedo, c->d_aov_normal, c->d_aov_id);
+                pt_launch_adaptive_accumulate_moments(ms, blocks, band, c->ad, fb, bp.L, bp.l_stride, c->d_moments);
+                return PTMI_OK;
+            }
+            pt_launch_accumulate(ms, blocks, band, frame0, fb, bp.L, bp.l_stride, c->d_out);
+            if (aov_rec)
+                pt_launch_accumulate_aov(ms, blocks, band, frame0, fb, aov_rec, c->sc.tris, c->sc.n_tris, c->d_aov_albedo,
+                                         c->d_aov_normal, c->d_aov_id);
+            if (c->d_moments) pt_launch_accumulate_moments(ms, blocks, band, frame0, fb, bp.L, bp.l_stride, c->d_moments);
+            return PTMI_OK;
+        };
+        if (ap) {
+            for (uint32_t r = 0; r < rounds; r++) {
+                pt_launch_adaptive_list(ms, blocks, band, *ap, c->d_moments, c->ad);
+                for (uint32_t f0 = 0; f0 < n_frames; f0 += F)
+                    if ((rc = batch(0u, std::min(F, n_frames - f0)))) return rc;
+            }
+            c->ad_rounds += rounds;
+        } else {
+            for (uint32_t f0 = 0; f0 < n_frames; f0 += F)
+                if ((rc = batch(cam->frame_index + f0, std::min(F, n_frames - f0)))) return rc;
         }
     }
     HIP_TRY(c, hipGetLastError());
@@ -1193,9 +1268,64 @@ int ptmi_dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames) {
         c->in_flight.push_back(done);
         if (c->in_flight.size() > kMaxDispatchesInFlight) HIP_TRY(c, throttle(c, kMaxDispatchesInFlight));
     }
-    c->st.paths += npix * n_frames;
-    c->st.frames += n_frames;
+    if (!ap) { c->st.paths += npix * n_frames; c->st.frames += n_frames; }      // adaptive: counted on the device (DevAdaptive::acc)
     c->st.dispatches += 1;
+    return PTMI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ptmi_dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames) { return dispatch(c, cam, n_frames, nullptr, 0); }
+
+int ptmi_dispatch_adaptive(ptmi_ctx *c, const ptmi_camera *cam, const ptmi_adaptive_params *params, uint32_t rounds) {
+    if (!c) return PTMI_E_INVALID;
+    if (!params) return fail(c, PTMI_E_INVALID, "params is NULL");
+    ptmi_adaptive_params ap = *params;
+    if (!(ap.threshold > 0.0f)) return fail(c, PTMI_E_INVALID, "threshold %g is not > 0", (double)ap.threshold);
+    if (!(ap.floor >= 0.0f) || std::isinf(ap.floor)) return fail(c, PTMI_E_INVALID, "floor %g is negative or not finite", (double)ap.floor);
+    if (ap.reserved[0] || ap.reserved[1]) return fail(c, PTMI_E_INVALID, "a reserved word of ptmi_adaptive_params is not zero");
+    if (ap.neighbourhood > 1u) return fail(c, PTMI_E_INVALID, "neighbourhood %u is not 0 or 1", ap.neighbourhood);
+    if (ap.floor == 0.0f) ap.floor = 1.0f;
+    if (ap.min_frames == 0u) ap.min_frames = 16u;
+    if (ap.max_frames == 0u) ap.max_frames = 4096u;
+    if (ap.step == 0u) ap.step = 16u;
+    if (ap.max_frames > (1u << 24)) return fail(c, PTMI_E_INVALID, "max_frames %u above 2^24", ap.max_frames);
+    if (ap.min_frames > ap.max_frames) return fail(c, PTMI_E_INVALID, "min_frames %u above max_frames %u", ap.min_frames, ap.max_frames);
+    if (ap.step > (1u << 16)) return fail(c, PTMI_E_INVALID, "step %u above 2^16", ap.step);
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    if (!c->moments_on || !c->d_moments) return fail(c, PTMI_E_STATE, "adaptive sampling needs the moments plane (ptmi_set_moments)");
+    return dispatch(c, cam, ap.step, &ap, rounds);
+}
+
+int ptmi_adaptive_status(ptmi_ctx *c, struct ptmi_adaptive_status *out) {
+    if (!c || !out) return PTMI_E_INVALID;
+    if (!c->moments_on) return fail(c, PTMI_E_STATE, "the moments plane is off (ptmi_set_moments)");
+    if (!c->d_moments) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = ensure_adaptive_words(c);
+    if (rc) return rc;
+    std::memset(out, 0, sizeof *out);
+    const DevBand band = pt_band_of(c->opt, c->W, c->H);
+    const unsigned long long preset[3] = {0ull, ~0ull, 0ull};
+    unsigned long long acc[3] = {0ull, 0ull, 0ull};
+    uint32_t ctl[2] = {0u, 0u};
+    HIP_TRY(c, sync_all(c));
+    drain_events(c);
+    if (band.y0 < band.y1 && band.rows) {
+        HIP_TRY(c, hipMemcpyAsync(&c->ad.acc[1], preset, sizeof preset, hipMemcpyHostToDevice, c->stream));
+        pt_launch_adaptive_status(c->stream, c->n_cu * 8, band, c->d_moments, c->ad);
+        HIP_TRY(c, hipMemcpyAsync(acc, &c->ad.acc[1], sizeof acc, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipMemcpyAsync(ctl, c->ad.ctl, sizeof ctl, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    out->active = ctl[1];
+    out->samples = acc[0];
+    out->min_count = acc[1] == ~0ull ? 0u : (uint32_t)acc[1];
+    out->max_count = (uint32_t)acc[2];
+    out->rounds = c->ad_rounds;
     return PTMI_OK;
 }
 
@@ -1343,6 +1473,7 @@ int ptmi_set_moments(ptmi_ctx *c, uint32_t on) {
         if (rc) return rc;
     }
     if (!on) dfree(c->d_moments);
+    if ((on != 0) != c->moments_on) { const int rc = reset_adaptive_rounds(c); if (rc) return rc; }
     c->moments_on = on != 0;
     return PTMI_OK;
 }
@@ -1440,6 +1571,11 @@ int ptmi_get_stats(ptmi_ctx *c, ptmi_stats *out) {
     c->st.verify_failed = h[4];
     c->st.bvh_depth = stats_depth(c);
     *out = c->st;
+    if (c->ad.acc) {                                  // the samples adaptive dispatches traced
+        unsigned long long traced = 0;
+        HIP_TRY(c, hipMemcpy(&traced, c->ad.acc, sizeof traced, hipMemcpyDeviceToHost));
+        out->paths += traced;
+    }
     return PTMI_OK;
 }
 
@@ -1449,6 +1585,7 @@ int ptmi_reset_stats(ptmi_ctx *c) {
     HIP_TRY(c, sync_all(c));
     drain_events(c);
     HIP_TRY(c, hipMemset(c->d_stats, 0, kStatsWords * sizeof(unsigned long long)));
+    if (c->ad.acc) HIP_TRY(c, hipMemset(c->ad.acc, 0, sizeof(unsigned long long)));
     const ptmi_stats old = c->st;
     std::memset(&c->st, 0, sizeof c->st);
     c->st.bvh_depth = stats_depth(c);

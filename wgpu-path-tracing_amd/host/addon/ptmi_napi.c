@@ -431,6 +431,64 @@ static napi_value js_denoise(napi_env env, napi_callback_info info) {
     return argv[2];
 }
 
+static void set_num(napi_env env, napi_value obj, const char *k, double v);
+
+/* dispatchAdaptive(h, cameraBytes, {threshold, floor, minFrames, maxFrames, step, neighbourhood}, rounds): ptmi_dispatch_adaptive */
+static napi_value js_dispatch_adaptive(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    handle *h = get_single_handle(env, info, 4, argv, "dispatchAdaptive");
+    if (!h) return NULL;
+    void *p; size_t n; uint32_t rounds = 1;
+    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
+    if (!p || n != sizeof(ptmi_camera)) { napi_throw_range_error(env, NULL, "camera blob must be 96 bytes"); return NULL; }
+    ptmi_adaptive_params prm;
+    memset(&prm, 0, sizeof prm);
+    napi_valuetype t;
+    if (napi_typeof(env, argv[2], &t) == napi_ok && t == napi_object) {
+        prm.threshold = get_f32_prop(env, argv[2], "threshold", 0.0f);
+        prm.floor = get_f32_prop(env, argv[2], "floor", 0.0f);
+        prm.min_frames = get_u32_prop(env, argv[2], "minFrames", 0);
+        prm.max_frames = get_u32_prop(env, argv[2], "maxFrames", 0);
+        prm.step = get_u32_prop(env, argv[2], "step", 0);
+        prm.neighbourhood = get_u32_prop(env, argv[2], "neighbourhood", 0);
+    }
+    napi_get_value_uint32(env, argv[3], &rounds);
+    ptmi_camera cam;
+    memcpy(&cam, p, sizeof cam);
+    int rc = ptmi_dispatch_adaptive(h->ctx, &cam, &prm, rounds);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_dispatch_adaptive");
+    return NULL;
+}
+
+/* adaptiveStatus(h) -> {active, samples, minCount, maxCount, rounds}; synchronises */
+static napi_value js_adaptive_status(napi_env env, napi_callback_info info) {
+    napi_value argv[1];
+    handle *h = get_single_handle(env, info, 1, argv, "adaptiveStatus");
+    if (!h) return NULL;
+    struct ptmi_adaptive_status s;
+    int rc = ptmi_adaptive_status(h->ctx, &s);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_adaptive_status");
+    napi_value o;
+    NAPI_OK(env, napi_create_object(env, &o));
+    set_num(env, o, "active", (double)s.active); set_num(env, o, "samples", (double)s.samples);
+    set_num(env, o, "minCount", (double)s.min_count); set_num(env, o, "maxCount", (double)s.max_count);
+    set_num(env, o, "rounds", (double)s.rounds);
+    return o;
+}
+
+/* readMoments(h, Float32Array dst of width*height*4): the sample-moments plane */
+static napi_value js_read_moments(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    handle *h = get_single_handle(env, info, 2, argv, "readMoments");
+    if (!h) return NULL;
+    void *p; size_t n;
+    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
+    if (!check_canvas(env, h, "readMoments", "Float32Array", 4, p, n)) return NULL;
+    int rc = ptmi_read_moments(h->ctx, (float *)p, n / 4);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_read_moments");
+    return argv[1];
+}
+
 /* blitDenoised(h, Uint8Array dstRgba8): blit() of the last denoise() result */
 static napi_value js_blit_denoised(napi_env env, napi_callback_info info) {
     napi_value argv[2];
@@ -557,6 +615,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"readOutput", js_read_output}, {"writeOutput", js_write_output}, {"setAovs", js_set_aovs}, {"readAov", js_read_aov},
         {"blit", js_blit}, {"getStats", js_get_stats}, {"resetStats", js_reset_stats},
         {"setMoments", js_set_moments}, {"denoise", js_denoise}, {"blitDenoised", js_blit_denoised},
+        {"dispatchAdaptive", js_dispatch_adaptive}, {"adaptiveStatus", js_adaptive_status}, {"readMoments", js_read_moments},
         {"buildBvh", js_build_bvh}, {"emissiveLights", js_emissive_lights},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

@@ -55,7 +55,7 @@ export class Renderer {
    *  device through RCCL and with several contexts on one device (`loopback: true`); more than one device over RCCL has never run —
    *  no machine this was built on has two GPUs. */
   constructor(options?: { device?: number; devices?: number[]; loopback?: boolean; gatherEvery?: number; maxFramesPerTick?: number;
-                          width?: number; height?: number; options?: TraceOptions });
+                          width?: number; height?: number; options?: TraceOptions; adaptive?: AdaptiveParams });
   camera: CameraCPU;
   addOnUpdate(callback: (deltaTime: number) => void): void;
   loadModel(model: string | SceneData | { blobs: SceneBlobs; atlas?: Atlas | null }, atlas?: Atlas): Promise<void>;
@@ -78,12 +78,24 @@ export class Renderer {
   blit(): Uint8Array;
   /** the denoiser's planes (normal, albedo, sample moments) on or off together; an 'id' plane stays; throws with several devices */
   setDenoise(on: boolean): void;
+  /** adaptive sampling on (params) or off (null): the frame loop then issues adaptive rounds and stops re-arming when a round lists
+   *  no pixel; turns the sample-moments plane on; throws with several devices */
+  setAdaptive(params: AdaptiveParams | null): void;
+  /** `rounds` adaptive rounds now (frameIndex 0 restarts) */
+  renderAdaptive(rounds?: number): void;
+  adaptiveStatus(): { active: number; samples: number; minCount: number; maxCount: number; rounds: number };
+  /** per-pixel sample counts (the moments plane's z), width*height, row 0 = image bottom */
+  sampleCounts(): Float32Array;
   /** the denoised output buffer (include/ptmi.h ptmi_denoise): width*height float4 (rgb, 0), row 0 = image bottom */
   denoise(params?: DenoiseParams): Float32Array;
   /** blit pass of the last denoise() result: tone-mapped RGBA8 canvas, row 0 = top */
   blitDenoised(): Uint8Array;
   setOptions(o: TraceOptions): void;
   getStats(): Stats;
+}
+/** 0 or absent: the default (include/ptmi.h ptmi_adaptive_params); threshold is required and > 0 */
+export interface AdaptiveParams {
+  threshold: number; floor?: number; minFrames?: number; maxFrames?: number; step?: number; neighbourhood?: 0 | 1;
 }
 /** 0 or absent: the default (include/ptmi.h ptmi_denoise_params) */
 export interface DenoiseParams {

@@ -4,9 +4,12 @@
  * render_cli.js — drives the Renderer the way the reference's frame loop does
  * (renderer.ts:415-454: one dispatch per frame, frameIndex++), headless:
  *   node render_cli.js <scene.ptscene> <out.f32> [--width W --height H --frames N --bounces B --mis 0|1
- *                       --aperture A --focus F --batch K --png out.png --denoise]
+ *                       --aperture A --focus F --batch K --png out.png --denoise
+ *                       --adaptive THRESHOLD --max-frames N --rounds R]
  * --batch K traces K frames per dispatch instead of one. --denoise keeps the denoiser's planes and makes --png the tone-mapped
- * denoised image (include/ptmi.h ptmi_denoise, default parameters). Writes W*H*4 float32 (the output buffer, raw also with
+ * denoised image (include/ptmi.h ptmi_denoise, default parameters). --adaptive renders to a noise level instead of --frames
+ * (include/ptmi.h ptmi_dispatch_adaptive): rounds until none lists a pixel, or --rounds R of them; the JSON line then also holds
+ * adaptive: { samples, minCount, maxCount, rounds }. Writes W*H*4 float32 (the output buffer, raw also with
  * --denoise) and prints one JSON line with the statistics.
  */
 var fs = require('fs');
@@ -21,6 +24,7 @@ var scenePath = process.argv[2], outPath = process.argv[3];
 if (!scenePath || !outPath) { console.error('usage: render_cli.js scene.ptscene out.f32 [options]'); process.exit(2); }
 var W = arg('width', 256), H = arg('height', 256), frames = arg('frames', 16), batch = arg('batch', 1);
 var denoise = process.argv.indexOf('--denoise') >= 0;
+var adaptive = process.argv.indexOf('--adaptive') >= 0 ? { threshold: arg('adaptive', 0), maxFrames: arg('max-frames', 0) } : null;
 
 var r = new host.Renderer({ width: W, height: H, options: { maxBounces: arg('bounces', 8), doMis: arg('mis', 1) } });
 r.camera.aperture = arg('aperture', r.camera.aperture);
@@ -28,7 +32,15 @@ r.camera.focusDistance = arg('focus', r.camera.focusDistance);
 if (denoise) r.setDenoise(true);
 r.loadModel(scenePath).then(function () {
   var t0 = Date.now();
-  while (r.frameIndex < frames) r.renderFrame(Math.min(batch, frames - r.frameIndex));
+  var status = null;
+  if (adaptive) {
+    r.setAdaptive(adaptive);
+    var rounds = arg('rounds', 0);
+    if (rounds > 0) r.renderAdaptive(rounds);
+    else do { r.renderAdaptive(1); } while (r.adaptiveStatus().active > 0);
+    status = r.adaptiveStatus();
+  } else
+    while (r.frameIndex < frames) r.renderFrame(Math.min(batch, frames - r.frameIndex));
   var out = r.readOutput();
   var ms = Date.now() - t0;
   fs.writeFileSync(outPath, Buffer.from(out.buffer));
@@ -40,6 +52,8 @@ r.loadModel(scenePath).then(function () {
   }
   var st = r.getStats();
   st.wallMs = ms; st.width = W; st.height = H; st.frames = frames;
+  if (status) st.frames = 0;                // no uniform frames: the counts are per pixel
+  if (status) st.adaptive = { samples: status.samples, minCount: status.minCount, maxCount: status.maxCount, rounds: status.rounds };
   console.log(JSON.stringify(st));
   r.destroy();
 }).catch(function (e) { console.error(String(e && e.stack || e)); process.exit(1); });

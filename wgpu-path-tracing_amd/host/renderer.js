@@ -55,6 +55,9 @@ function Renderer(options) {
   this.setupCamera();
   this.addon.resize(this.ctx, this.width, this.height);
   if (options.options) this.addon.setOptions(this.ctx, options.options);
+  this.adaptive = null;
+  this.adaptiveActive = -1;                 // pixels the last adaptive round listed (-1: none issued since the last reset)
+  if (options.adaptive) this.setAdaptive(options.adaptive);
 }
 
 /** renderer.ts:136-150 */
@@ -102,6 +105,8 @@ Renderer.prototype.resetOutputBuffer = function (restart) {
   this.frameIndex = 0;
   this.camera.frameIndex = 0;
   this.framesPerTick = 1;                   // the picture changed: back to one frame per tick, for the shortest latency
+  this.adaptiveActive = -1;
+  this.adaptivePending = false;
   if (restart !== false && this.timer === null && this.sceneLoaded) this.start();
 };
 
@@ -141,7 +146,16 @@ Renderer.prototype.start = function () {
     self.lastTime = now;
     for (var i = 0; i < self.onUpdateTasks.length; i++) self.onUpdateTasks[i](dt);      // may move the camera: framesPerTick = 1
     if (self.timer === null) return;        // an update task stopped the loop
-    if (MAX_FRAMES === -1 || self.frameIndex < MAX_FRAMES) {
+    if (self.adaptive) {
+      // adaptive: one round in flight. Whether anything is left is read once the throttle's poll says that round has finished (the
+      // status call then finds the device idle), so a turn of the loop never waits for a round; until then it only re-arms.
+      if (self.adaptivePending && self.addon.throttle(self.ctx, 0xFFFFFFFF) === 0) {
+        self.adaptiveActive = self.adaptiveStatus().active;
+        self.adaptivePending = false;
+      }
+      if (self.adaptiveActive === 0) { self.timer = null; return; }      // converged: no re-arming until the picture changes
+      if (!self.adaptivePending) { self.renderAdaptive(1); self.adaptivePending = true; }
+    } else if (MAX_FRAMES === -1 || self.frameIndex < MAX_FRAMES) {
       var n = self.framesPerTick;
       if (MAX_FRAMES !== -1) n = Math.min(n, MAX_FRAMES - self.frameIndex);
       self.renderFrame(n);
@@ -258,7 +272,7 @@ Renderer.prototype.setDenoise = function (on) {
   var mask = ((this.aovMask || 0) & 4) | (on ? 3 : 0);
   this.addon.setAovs(this.ctx, mask);
   this.aovMask = mask;
-  this.addon.setMoments(this.ctx, !!on);
+  if (on || !this.adaptive) this.addon.setMoments(this.ctx, !!on);      // adaptive sampling keeps the moments plane it counts in
   this.denoiseOn = !!on;
 };
 /** The denoised output buffer: width*height float4 (rgb, 0), row 0 = image bottom like readOutput. params (all optional, 0 = the
@@ -274,6 +288,37 @@ Renderer.prototype.blitDenoised = function () {
   if (this.multi) throw new Error('blitDenoised: the denoiser is not supported with several devices');
   var out = new Uint8Array(this.width * this.height * 4);
   this.addon.blitDenoised(this.ctx, out);
+  return out;
+};
+
+/** Adaptive sampling (include/ptmi.h ptmi_dispatch_adaptive): params = { threshold, floor, minFrames, maxFrames, step,
+ *  neighbourhood } (0 or absent: the default; threshold has none), or null to go back to uniform frames. Turns the sample-moments
+ *  plane on. While set, the frame loop issues adaptive rounds and stops re-arming once a round lists no pixel. */
+Renderer.prototype.setAdaptive = function (params) {
+  if (this.multi) throw new Error('setAdaptive: adaptive sampling is not supported with several devices');
+  if (params) {
+    if (!(params.threshold > 0)) throw new RangeError('setAdaptive: threshold must be > 0');
+    if (!this.denoiseOn && !this.adaptive) this.addon.setMoments(this.ctx, true);
+  } else if (this.adaptive && !this.denoiseOn) this.addon.setMoments(this.ctx, false);
+  this.adaptive = params || null;
+  this.resetOutputBuffer(false);
+};
+/** `rounds` adaptive rounds; frameIndex counts rounds here (0 restarts, like a first frame) */
+Renderer.prototype.renderAdaptive = function (rounds) {
+  if (!this.adaptive) throw new Error('renderAdaptive: setAdaptive first');
+  rounds = rounds || 1;
+  this.updateCamera();
+  this.addon.dispatchAdaptive(this.ctx, this.cameraBytes, this.adaptive, rounds);
+  this.frameIndex += rounds;
+};
+/** { active, samples, minCount, maxCount, rounds } (include/ptmi.h ptmi_adaptive_status); synchronises */
+Renderer.prototype.adaptiveStatus = function () { return this.addon.adaptiveStatus(this.ctx); };
+/** per-pixel sample counts (the moments plane's z): width*height floats, row 0 = image bottom like readOutput */
+Renderer.prototype.sampleCounts = function () {
+  if (this.multi) throw new Error('sampleCounts: the moments plane is not supported with several devices');
+  var m = this.addon.readMoments(this.ctx, new Float32Array(this.width * this.height * 4));
+  var out = new Float32Array(this.width * this.height);
+  for (var i = 0; i < out.length; i++) out[i] = m[4 * i + 2];
   return out;
 };
 

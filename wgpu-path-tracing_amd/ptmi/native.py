@@ -32,6 +32,7 @@ EXPORTS = [
     "ptmi_set_aovs", "ptmi_get_aovs", "ptmi_read_aov", "ptmi_aov_device_ptr",
     "ptmi_set_moments", "ptmi_get_moments", "ptmi_read_moments", "ptmi_moments_device_ptr",
     "ptmi_denoise", "ptmi_denoised_device_ptr", "ptmi_blit_denoised",
+    "ptmi_dispatch_adaptive", "ptmi_adaptive_status",
 ]
 MULTI_LOOPBACK = 1
 # first-hit planes (include/ptmi.h ptmi_set_aovs): name -> (bit, numpy dtype, channels)
@@ -60,6 +61,21 @@ class Options(ctypes.Structure):
 class DenoiseParams(ctypes.Structure):
     _fields_ = [("iterations", ctypes.c_uint32), ("demodulate", ctypes.c_uint32), ("phi_color", ctypes.c_float),
                 ("phi_normal", ctypes.c_float), ("phi_depth", ctypes.c_float), ("reserved", ctypes.c_uint32 * 3)]
+
+
+class AdaptiveParams(ctypes.Structure):
+    """ptmi_adaptive_params; 0 picks a field's default (include/ptmi.h), threshold has none"""
+    _fields_ = [("threshold", ctypes.c_float), ("floor", ctypes.c_float), ("min_frames", ctypes.c_uint32),
+                ("max_frames", ctypes.c_uint32), ("step", ctypes.c_uint32), ("neighbourhood", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 2)]
+
+
+class AdaptiveStatus(ctypes.Structure):
+    _fields_ = [("active", ctypes.c_uint64), ("samples", ctypes.c_uint64), ("min_count", ctypes.c_uint32),
+                ("max_count", ctypes.c_uint32), ("rounds", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
 class Stats(ctypes.Structure):
@@ -146,6 +162,8 @@ def load():
         L.ptmi_denoised_device_ptr.restype = vp
         L.ptmi_denoised_device_ptr.argtypes = [vp]
         L.ptmi_blit_denoised.argtypes = [vp, vp, sz, vp, sz]
+        L.ptmi_dispatch_adaptive.argtypes = [vp, vp, vp, u32]
+        L.ptmi_adaptive_status.argtypes = [vp, vp]
         _lib = L
     return _lib
 
@@ -405,6 +423,20 @@ class Context(_Handle):
         b = np.empty((self.height, self.width, 4), np.uint8) if want_rgba8 else None
         self._ck(self.L.ptmi_blit_denoised(self.h, _p(f), 0 if f is None else f.size, _p(b), 0 if b is None else b.size))
         return f, b
+
+    # -- adaptive sampling (include/ptmi.h ptmi_dispatch_adaptive) ---------------------------------------------
+    def dispatch_adaptive(self, camera, rounds=1, threshold=0.0, floor=0.0, min_frames=0, max_frames=0, step=0, neighbourhood=0,
+                          reserved=(0, 0)):
+        """`rounds` rounds of `step` further frames for the pixels the rule of include/ptmi.h selects; needs set_moments().
+        camera frame_index 0 restarts, any other value continues from the per-pixel counts."""
+        assert camera.dtype == layout.CAMERA
+        prm = AdaptiveParams(threshold, floor, min_frames, max_frames, step, neighbourhood, (ctypes.c_uint32 * 2)(*reserved))
+        self._ck(self.L.ptmi_dispatch_adaptive(self.h, _p(camera), ctypes.byref(prm), rounds))
+
+    def adaptive_status(self):
+        st = AdaptiveStatus()
+        self._ck(self.L.ptmi_adaptive_status(self.h, ctypes.byref(st)))
+        return st
 
     def read_image(self):
         """The traversal image the last upload_scene put on the device (include/ptmi.h: ptmi_debug_read_image), as build_image()
