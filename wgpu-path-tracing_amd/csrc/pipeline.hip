@@ -47,18 +47,39 @@ PT_DEV void init_path(DevPaths P, uint32_t p, v3 o, v3 d, uint32_t rng) {
 
 // path id = frame_in_batch * band_pixels + local_row * width + x (local rows: DevBand::row_of). The bounce-0 queue is the identity and is
 // not materialised: extend / shade / compact take a null queue as "slot i holds path i".
-__global__ __launch_bounds__(BLOCK) void k_raygen(ptmi_camera cam, DevBand band, uint32_t frame0, uint32_t n_frames,
-                                                  DevPaths P, uint32_t *__restrict__ count_out) {
-    const uint32_t npix = band.rows * band.width;
-    const uint32_t total = npix * n_frames;
+//
+// The pixels a batch walks (DevPixels), as the kernels see them. Ray generation and the three folds are written once over a source that
+// answers: how many entries, the band-local pixel of entry j, the first frame of the pixel at frame index oi. The kernel picks the source.
+struct DensePixels {                    // every pixel of the band, all from frame0
+    DevBand band; uint32_t frame0;
+    PT_DEV uint32_t entries() const { return band.rows * band.width; }
+    PT_DEV uint32_t pixel(uint32_t j) const { return j; }
+    PT_DEV uint32_t first_frame(size_t) const { return frame0; }
+};
+struct ListedPixels {                   // the *n_active pixels of the list, each from its own count mom[oi].z
+    DevBand band; const uint32_t *list, *n_active; const float4 *mom;
+    PT_DEV uint32_t entries() const { return *n_active; }
+    PT_DEV uint32_t pixel(uint32_t j) const { return list[j]; }
+    PT_DEV uint32_t first_frame(size_t oi) const { return (uint32_t)mom[oi].z; }
+};
+
+template <class Pixels>
+PT_DEV void raygen(const ptmi_camera &cam, const Pixels &px, uint32_t n_frames, DevPaths P, uint32_t *__restrict__ count_out) {
+    const DevBand &band = px.band;
+    const uint32_t n = px.entries();
+    const uint32_t total = n * n_frames;
     if (blockIdx.x == 0 && threadIdx.x == 0) *count_out = total;
     for (uint32_t p = blockIdx.x * BLOCK + threadIdx.x; p < total; p += gridDim.x * BLOCK) {
-        uint32_t k = p / npix, pix = p - k * npix;
-        uint32_t y = band.row_of(pix / band.width), x = pix % band.width;
+        const uint32_t k = p / n, pix = px.pixel(p - k * n);
+        const uint32_t y = band.row_of(pix / band.width), x = pix % band.width;
         v3 o, d; uint32_t rng;
-        camera_ray(cam, x, y, frame0 + k, o, d, rng);
+        camera_ray(cam, x, y, px.first_frame((size_t)y * band.width + x) + k, o, d, rng);
         init_path(P, p, o, d, rng);
     }
+}
+__global__ __launch_bounds__(BLOCK) void k_raygen(ptmi_camera cam, DevBand band, uint32_t frame0, uint32_t n_frames,
+                                                  DevPaths P, uint32_t *__restrict__ count_out) {
+    raygen(cam, DensePixels{band, frame0}, n_frames, P, count_out);
 }
 
 __global__ __launch_bounds__(BLOCK) void k_raygen_list(ptmi_camera cam, uint32_t n, const uint32_t *xs,
@@ -210,94 +231,107 @@ __global__ __launch_bounds__(BLOCK) void k_repack(const uint32_t *__restrict__ c
     }
 }
 
+// pt.wgsl:751-761: one step of the running mean on N channels. Frame 0 overwrites, frame f > 0 mixes with weight 1 / (f + 1).
+template <int N>
+PT_DEV void fold(float (&acc)[N], const float (&x)[N], uint32_t frame) {
+    if (frame > 0u) {
+        const float t = 1.0f / (float)(frame + 1u);
+        for (int i = 0; i < N; i++) acc[i] = mix1(acc[i], x[i], t);
+    } else {
+        for (int i = 0; i < N; i++) acc[i] = x[i];
+    }
+}
+// radiance of path p (12- or 16-byte stride, DevPaths::l_stride) under the 2.5 clamp of pt.wgsl:752
+PT_DEV rgb_sc ld_clamped(const float *__restrict__ L, uint32_t l_stride, size_t p) {
+    rgb_sc l;
+    if (l_stride == 4u) { const float4 v = reinterpret_cast<const float4 *>(L)[p]; l = rgb_sc{v.x, v.y, v.z}; }
+    else l = reinterpret_cast<const rgb_sc *>(L)[p];
+    return rgb_sc{min1(l.x, 2.5f), min1(l.y, 2.5f), min1(l.z, 2.5f)};
+}
+
 // pt.wgsl:751-761 for the batch's frames in ascending order
-__global__ __launch_bounds__(BLOCK) void k_accumulate(DevBand band, uint32_t frame0, uint32_t n_frames,
-                                                      const float *__restrict__ L, uint32_t l_stride, float4 *__restrict__ out) {
-    const uint32_t npix = band.rows * band.width;
-    for (uint32_t pix = blockIdx.x * BLOCK + threadIdx.x; pix < npix; pix += gridDim.x * BLOCK) {
-        const size_t oi = (size_t)band.row_of(pix / band.width) * band.width + pix % band.width;
-        float4 acc = out[oi];
+template <class Pixels>
+PT_DEV void fold_radiance(const Pixels &px, uint32_t n_frames, const float *__restrict__ L, uint32_t l_stride, float4 *__restrict__ out) {
+    const uint32_t n = px.entries();
+    for (uint32_t j = blockIdx.x * BLOCK + threadIdx.x; j < n; j += gridDim.x * BLOCK) {
+        const size_t oi = px.band.frame_pixel(px.pixel(j));
+        const uint32_t frame0 = px.first_frame(oi);
+        const float4 o = out[oi];
+        float acc[3] = {o.x, o.y, o.z};
         for (uint32_t k = 0; k < n_frames; k++) {
-            const size_t li = (size_t)k * npix + pix;
-            rgb_sc l;
-            if (l_stride == 4u) { const float4 v = reinterpret_cast<const float4 *>(L)[li]; l = rgb_sc{v.x, v.y, v.z}; }
-            else l = reinterpret_cast<const rgb_sc *>(L)[li];
-            float cx = min1(l.x, 2.5f), cy = min1(l.y, 2.5f), cz = min1(l.z, 2.5f);
-            uint32_t frame = frame0 + k;
-            if (frame > 0u) {
-                float t = 1.0f / (float)(frame + 1u);
-                cx = mix1(acc.x, cx, t); cy = mix1(acc.y, cy, t); cz = mix1(acc.z, cz, t);
-            }
-            acc = make_float4(cx, cy, cz, 0.0f);
+            const rgb_sc c = ld_clamped(L, l_stride, (size_t)k * n + j);
+            fold(acc, {c.x, c.y, c.z}, frame0 + k);
         }
-        out[oi] = acc;
+        out[oi] = n_frames ? make_float4(acc[0], acc[1], acc[2], 0.0f) : o;
     }
 }
 
 // The first-hit planes (ptmi_set_aovs) from the records `shade` wrote at bounce 0 (rec[2p], rec[2p + 1] for path p; shade.hip):
-// albedo = (albedo.rgb, coverage) and normal = (normal.xyz, t) follow the fold of k_accumulate without its clamp; ids = (triangle,
+// albedo = (albedo.rgb, coverage) and normal = (normal.xyz, t) follow the fold of the radiance without its clamp; ids = (triangle,
 // its material) of the batch's last frame.
-__global__ __launch_bounds__(BLOCK) void k_accumulate_aov(DevBand band, uint32_t frame0, uint32_t n_frames, const float4 *__restrict__ rec,
-                                                          const ptmi_triangle *__restrict__ tris, uint32_t n_tris,
-                                                          float4 *__restrict__ albedo, float4 *__restrict__ normal, uint2 *__restrict__ ids) {
-    const uint32_t npix = band.rows * band.width;
-    for (uint32_t pix = blockIdx.x * BLOCK + threadIdx.x; pix < npix; pix += gridDim.x * BLOCK) {
-        const size_t oi = (size_t)band.row_of(pix / band.width) * band.width + pix % band.width;
-        float4 a = albedo ? albedo[oi] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        float4 n = normal ? normal[oi] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+template <class Pixels>
+PT_DEV void fold_aov(const Pixels &px, uint32_t n_frames, const float4 *__restrict__ rec, const ptmi_triangle *__restrict__ tris,
+                     uint32_t n_tris, float4 *__restrict__ albedo, float4 *__restrict__ normal, uint2 *__restrict__ ids) {
+    const uint32_t n = px.entries();
+    for (uint32_t j = blockIdx.x * BLOCK + threadIdx.x; j < n; j += gridDim.x * BLOCK) {
+        const size_t oi = px.band.frame_pixel(px.pixel(j));
+        const uint32_t frame0 = px.first_frame(oi);
+        const float4 a = albedo ? albedo[oi] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        const float4 nm = normal ? normal[oi] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        float acc[8] = {a.x, a.y, a.z, a.w, nm.x, nm.y, nm.z, nm.w};
         uint32_t tri = 0xFFFFFFFFu;
         for (uint32_t k = 0; k < n_frames; k++) {
-            const size_t li = (size_t)k * npix + pix;
+            const size_t li = (size_t)k * n + j;
             const float4 ra = ld_stream(&rec[2 * li]), rn = ld_stream(&rec[2 * li + 1]);
             tri = __float_as_uint(rn.w);
-            float4 xa = make_float4(ra.x, ra.y, ra.z, tri != 0xFFFFFFFFu ? 1.0f : 0.0f);
-            float4 xn = make_float4(rn.x, rn.y, rn.z, ra.w);
-            const uint32_t frame = frame0 + k;
-            if (frame > 0u) {
-                const float t = 1.0f / (float)(frame + 1u);
-                xa = make_float4(mix1(a.x, xa.x, t), mix1(a.y, xa.y, t), mix1(a.z, xa.z, t), mix1(a.w, xa.w, t));
-                xn = make_float4(mix1(n.x, xn.x, t), mix1(n.y, xn.y, t), mix1(n.z, xn.z, t), mix1(n.w, xn.w, t));
-            }
-            a = xa; n = xn;
+            fold(acc, {ra.x, ra.y, ra.z, tri != 0xFFFFFFFFu ? 1.0f : 0.0f, rn.x, rn.y, rn.z, ra.w}, frame0 + k);
         }
-        if (albedo) albedo[oi] = a;
-        if (normal) normal[oi] = n;
+        if (albedo) albedo[oi] = make_float4(acc[0], acc[1], acc[2], acc[3]);
+        if (normal) normal[oi] = make_float4(acc[4], acc[5], acc[6], acc[7]);
         if (ids) ids[oi] = make_uint2(tri, tri < n_tris ? tris[tri].material_index : 0xFFFFFFFFu);
     }
 }
 
-// The sample-moments plane (ptmi_set_moments) from the same clamped per-frame radiance k_accumulate folds: per pixel
+// The sample-moments plane (ptmi_set_moments) from the same clamped per-frame radiance fold_radiance folds: per pixel
 // (mean of l, mean of l^2, frames folded, 0) with l = 0.2126 r + 0.7152 g + 0.0722 b (left to right, no FMA), the means following
-// the output buffer's fold (frame 0 overwrites, frame f > 0 mixes with weight 1 / (f + 1)).
+// the output buffer's fold. `mom` carries no __restrict__: a listed source reads its frame index from the same plane.
+template <class Pixels>
+PT_DEV void fold_moments(const Pixels &px, uint32_t n_frames, const float *__restrict__ L, uint32_t l_stride, float4 *mom) {
+    const uint32_t n = px.entries();
+    for (uint32_t j = blockIdx.x * BLOCK + threadIdx.x; j < n; j += gridDim.x * BLOCK) {
+        const size_t oi = px.band.frame_pixel(px.pixel(j));
+        const float4 m = mom[oi];
+        const uint32_t frame0 = px.first_frame(oi);
+        float acc[2] = {m.x, m.y};
+        for (uint32_t k = 0; k < n_frames; k++) {
+            const rgb_sc c = ld_clamped(L, l_stride, (size_t)k * n + j);
+            const float lum = 0.2126f * c.x + 0.7152f * c.y + 0.0722f * c.z;
+            fold(acc, {lum, lum * lum}, frame0 + k);
+        }
+        mom[oi] = n_frames ? make_float4(acc[0], acc[1], (float)(frame0 + n_frames), 0.0f) : m;
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_accumulate(DevBand band, uint32_t frame0, uint32_t n_frames,
+                                                      const float *__restrict__ L, uint32_t l_stride, float4 *__restrict__ out) {
+    fold_radiance(DensePixels{band, frame0}, n_frames, L, l_stride, out);
+}
+__global__ __launch_bounds__(BLOCK) void k_accumulate_aov(DevBand band, uint32_t frame0, uint32_t n_frames, const float4 *__restrict__ rec,
+                                                          const ptmi_triangle *__restrict__ tris, uint32_t n_tris,
+                                                          float4 *__restrict__ albedo, float4 *__restrict__ normal, uint2 *__restrict__ ids) {
+    fold_aov(DensePixels{band, frame0}, n_frames, rec, tris, n_tris, albedo, normal, ids);
+}
 __global__ __launch_bounds__(BLOCK) void k_accumulate_moments(DevBand band, uint32_t frame0, uint32_t n_frames,
                                                               const float *__restrict__ L, uint32_t l_stride,
                                                               float4 *__restrict__ mom) {
-    const uint32_t npix = band.rows * band.width;
-    for (uint32_t pix = blockIdx.x * BLOCK + threadIdx.x; pix < npix; pix += gridDim.x * BLOCK) {
-        const size_t oi = (size_t)band.row_of(pix / band.width) * band.width + pix % band.width;
-        float4 acc = mom[oi];
-        for (uint32_t k = 0; k < n_frames; k++) {
-            const size_t li = (size_t)k * npix + pix;
-            rgb_sc l;
-            if (l_stride == 4u) { const float4 v = reinterpret_cast<const float4 *>(L)[li]; l = rgb_sc{v.x, v.y, v.z}; }
-            else l = reinterpret_cast<const rgb_sc *>(L)[li];
-            const float lum = 0.2126f * min1(l.x, 2.5f) + 0.7152f * min1(l.y, 2.5f) + 0.0722f * min1(l.z, 2.5f);
-            float m1 = lum, m2 = lum * lum;
-            const uint32_t frame = frame0 + k;
-            if (frame > 0u) {
-                const float t = 1.0f / (float)(frame + 1u);
-                m1 = mix1(acc.x, m1, t); m2 = mix1(acc.y, m2, t);
-            }
-            acc = make_float4(m1, m2, (float)(frame + 1u), 0.0f);
-        }
-        mom[oi] = acc;
-    }
+    fold_moments(DensePixels{band, frame0}, n_frames, L, l_stride, mom);
 }
 
 // ---- adaptive sampling (ptmi_dispatch_adaptive; the rule is stated in include/ptmi.h) ------------------------------------------
 // Every pixel is at its own frame index: the moments plane's .z. A round selects the pixels that still get frames (k_ad_select:
 // one ballot word per 64 band pixels), lists them in ascending order with the scatter above (k_ad_tile_sums / k_ad_scatter: the
-// tile totals without k_tile_sums's segment statistics), and raygen and the three folds then walk that list: path
+// tile totals without k_tile_sums's segment statistics), and raygen and the three folds then walk that list (ListedPixels, the
+// same bodies as the plain dispatch): path
 // k * n_active + j is frame n(list[j]) + k of pixel list[j]. A list entry is a band-local pixel index (local row * width + x).
 PT_DEV float ad_max(float a, float b) { return a < b ? b : a; }       // a NaN in `a` stays
 PT_DEV bool ad_noisy(float4 m, const ptmi_adaptive_params &ap) {
@@ -318,7 +352,7 @@ PT_DEV bool band_has_row(const DevBand &band, uint32_t y) {
 __global__ __launch_bounds__(BLOCK) void k_ad_restart(DevBand band, float4 *__restrict__ mom) {
     const uint32_t npix = band.rows * band.width;
     for (uint32_t pix = blockIdx.x * BLOCK + threadIdx.x; pix < npix; pix += gridDim.x * BLOCK)
-        mom[(size_t)band.row_of(pix / band.width) * band.width + pix % band.width].z = 0.0f;
+        mom[band.frame_pixel(pix)].z = 0.0f;
 }
 
 // ctl[0] = band pixels (the `count` of the list build). Whole waves stay in the loop so that the ballot sees all 64 lanes.
@@ -371,107 +405,30 @@ __global__ __launch_bounds__(TILE_WORDS) void k_ad_scatter(const uint32_t *__res
     scatter_tile<false>(blockIdx.x, count_ptr, nullptr, ballot, tile_sums, list, n_active);
 }
 
-// k_raygen over the list; traced[0] += the paths of this batch (ptmi_stats.paths)
+// k_raygen and the three folds over the list: each pixel from its own frame index (mom.z, which the moments fold, launched last,
+// moves on). traced[0] += the paths of this batch (ptmi_stats.paths).
 __global__ __launch_bounds__(BLOCK) void k_ad_raygen(ptmi_camera cam, DevBand band, const uint32_t *__restrict__ list,
                                                      const uint32_t *__restrict__ n_active, uint32_t n_frames,
                                                      const float4 *__restrict__ mom, DevPaths P, uint32_t *__restrict__ count_out,
                                                      unsigned long long *__restrict__ traced) {
-    const uint32_t na = *n_active;
-    const uint32_t total = na * n_frames;
-    if (blockIdx.x == 0 && threadIdx.x == 0) { *count_out = total; atomicAdd(&traced[0], (unsigned long long)total); }
-    for (uint32_t p = blockIdx.x * BLOCK + threadIdx.x; p < total; p += gridDim.x * BLOCK) {
-        const uint32_t k = p / na, pix = list[p - k * na];
-        const uint32_t y = band.row_of(pix / band.width), x = pix % band.width;
-        const uint32_t frame = (uint32_t)mom[(size_t)y * band.width + x].z + k;
-        v3 o, d; uint32_t rng;
-        camera_ray(cam, x, y, frame, o, d, rng);
-        init_path(P, p, o, d, rng);
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&traced[0], (unsigned long long)(*n_active * n_frames));
+    raygen(cam, ListedPixels{band, list, n_active, mom}, n_frames, P, count_out);
 }
-
-// k_accumulate, k_accumulate_aov, k_accumulate_moments over the list: each pixel from its own frame index (mom.z, which the moments
-// fold, launched last, moves on)
 __global__ __launch_bounds__(BLOCK) void k_ad_accumulate(DevBand band, const uint32_t *__restrict__ list, const uint32_t *__restrict__ n_active,
                                                          uint32_t n_frames, const float4 *__restrict__ mom, const float *__restrict__ L,
                                                          uint32_t l_stride, float4 *__restrict__ out) {
-    const uint32_t na = *n_active;
-    for (uint32_t j = blockIdx.x * BLOCK + threadIdx.x; j < na; j += gridDim.x * BLOCK) {
-        const uint32_t pix = list[j];
-        const size_t oi = (size_t)band.row_of(pix / band.width) * band.width + pix % band.width;
-        const uint32_t frame0 = (uint32_t)mom[oi].z;
-        float4 acc = out[oi];
-        for (uint32_t k = 0; k < n_frames; k++) {
-            const size_t li = (size_t)k * na + j;
-            rgb_sc l;
-            if (l_stride == 4u) { const float4 v = reinterpret_cast<const float4 *>(L)[li]; l = rgb_sc{v.x, v.y, v.z}; }
-            else l = reinterpret_cast<const rgb_sc *>(L)[li];
-            float cx = min1(l.x, 2.5f), cy = min1(l.y, 2.5f), cz = min1(l.z, 2.5f);
-            const uint32_t frame = frame0 + k;
-            if (frame > 0u) {
-                const float t = 1.0f / (float)(frame + 1u);
-                cx = mix1(acc.x, cx, t); cy = mix1(acc.y, cy, t); cz = mix1(acc.z, cz, t);
-            }
-            acc = make_float4(cx, cy, cz, 0.0f);
-        }
-        out[oi] = acc;
-    }
+    fold_radiance(ListedPixels{band, list, n_active, mom}, n_frames, L, l_stride, out);
 }
 __global__ __launch_bounds__(BLOCK) void k_ad_accumulate_aov(DevBand band, const uint32_t *__restrict__ list, const uint32_t *__restrict__ n_active,
                                                              uint32_t n_frames, const float4 *__restrict__ mom, const float4 *__restrict__ rec,
                                                              const ptmi_triangle *__restrict__ tris, uint32_t n_tris,
                                                              float4 *__restrict__ albedo, float4 *__restrict__ normal, uint2 *__restrict__ ids) {
-    const uint32_t na = *n_active;
-    for (uint32_t j = blockIdx.x * BLOCK + threadIdx.x; j < na; j += gridDim.x * BLOCK) {
-        const uint32_t pix = list[j];
-        const size_t oi = (size_t)band.row_of(pix / band.width) * band.width + pix % band.width;
-        const uint32_t frame0 = (uint32_t)mom[oi].z;
-        float4 a = albedo ? albedo[oi] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        float4 n = normal ? normal[oi] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        uint32_t tri = 0xFFFFFFFFu;
-        for (uint32_t k = 0; k < n_frames; k++) {
-            const size_t li = (size_t)k * na + j;
-            const float4 ra = ld_stream(&rec[2 * li]), rn = ld_stream(&rec[2 * li + 1]);
-            tri = __float_as_uint(rn.w);
-            float4 xa = make_float4(ra.x, ra.y, ra.z, tri != 0xFFFFFFFFu ? 1.0f : 0.0f);
-            float4 xn = make_float4(rn.x, rn.y, rn.z, ra.w);
-            const uint32_t frame = frame0 + k;
-            if (frame > 0u) {
-                const float t = 1.0f / (float)(frame + 1u);
-                xa = make_float4(mix1(a.x, xa.x, t), mix1(a.y, xa.y, t), mix1(a.z, xa.z, t), mix1(a.w, xa.w, t));
-                xn = make_float4(mix1(n.x, xn.x, t), mix1(n.y, xn.y, t), mix1(n.z, xn.z, t), mix1(n.w, xn.w, t));
-            }
-            a = xa; n = xn;
-        }
-        if (albedo) albedo[oi] = a;
-        if (normal) normal[oi] = n;
-        if (ids) ids[oi] = make_uint2(tri, tri < n_tris ? tris[tri].material_index : 0xFFFFFFFFu);
-    }
+    fold_aov(ListedPixels{band, list, n_active, mom}, n_frames, rec, tris, n_tris, albedo, normal, ids);
 }
 __global__ __launch_bounds__(BLOCK) void k_ad_accumulate_moments(DevBand band, const uint32_t *__restrict__ list,
                                                                  const uint32_t *__restrict__ n_active, uint32_t n_frames,
                                                                  const float *__restrict__ L, uint32_t l_stride, float4 *__restrict__ mom) {
-    const uint32_t na = *n_active;
-    for (uint32_t j = blockIdx.x * BLOCK + threadIdx.x; j < na; j += gridDim.x * BLOCK) {
-        const uint32_t pix = list[j];
-        const size_t oi = (size_t)band.row_of(pix / band.width) * band.width + pix % band.width;
-        float4 acc = mom[oi];
-        const uint32_t frame0 = (uint32_t)acc.z;
-        for (uint32_t k = 0; k < n_frames; k++) {
-            const size_t li = (size_t)k * na + j;
-            rgb_sc l;
-            if (l_stride == 4u) { const float4 v = reinterpret_cast<const float4 *>(L)[li]; l = rgb_sc{v.x, v.y, v.z}; }
-            else l = reinterpret_cast<const rgb_sc *>(L)[li];
-            const float lum = 0.2126f * min1(l.x, 2.5f) + 0.7152f * min1(l.y, 2.5f) + 0.0722f * min1(l.z, 2.5f);
-            float m1 = lum, m2 = lum * lum;
-            const uint32_t frame = frame0 + k;
-            if (frame > 0u) {
-                const float t = 1.0f / (float)(frame + 1u);
-                m1 = mix1(acc.x, m1, t); m2 = mix1(acc.y, m2, t);
-            }
-            acc = make_float4(m1, m2, (float)(frame + 1u), 0.0f);
-        }
-        mom[oi] = acc;
-    }
+    fold_moments(ListedPixels{band, list, n_active, mom}, n_frames, L, l_stride, mom);
 }
 
 // ptmi_adaptive_status: acc[1] += the band's counts, acc[2] / acc[3] = their minimum / maximum (the caller presets 0, ~0, 0)
@@ -479,7 +436,7 @@ __global__ __launch_bounds__(BLOCK) void k_ad_status(DevBand band, const float4 
     const uint32_t npix = band.rows * band.width;
     unsigned long long sum = 0, lo = ~0ull, hi = 0;
     for (uint32_t pix = blockIdx.x * BLOCK + threadIdx.x; pix < npix; pix += gridDim.x * BLOCK) {
-        const unsigned long long n = (uint32_t)mom[(size_t)band.row_of(pix / band.width) * band.width + pix % band.width].z;
+        const unsigned long long n = (uint32_t)mom[band.frame_pixel(pix)].z;
         sum += n; lo = n < lo ? n : lo; hi = n > hi ? n : hi;
     }
     if (lo != ~0ull) { atomicAdd(&acc[1], sum); atomicMin(&acc[2], lo); atomicMax(&acc[3], hi); }
@@ -490,12 +447,12 @@ __global__ __launch_bounds__(BLOCK) void k_ad_status(DevBand band, const float4 
 __global__ __launch_bounds__(BLOCK) void k_pack_rows(DevBand band, const float4 *__restrict__ frame, float4 *__restrict__ packed) {
     const uint32_t n = band.rows * band.width;
     for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK)
-        packed[i] = frame[(size_t)band.row_of(i / band.width) * band.width + i % band.width];
+        packed[i] = frame[band.frame_pixel(i)];
 }
 __global__ __launch_bounds__(BLOCK) void k_unpack_rows(DevBand band, const float4 *__restrict__ packed, float4 *__restrict__ frame) {
     const uint32_t n = band.rows * band.width;
     for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK)
-        frame[(size_t)band.row_of(i / band.width) * band.width + i % band.width] = packed[i];
+        frame[band.frame_pixel(i)] = packed[i];
 }
 
 // ---- presentation: src/shader/blit.wgsl:43-155 (exposure 2^1, AgX, look, EOTF, gamma 1/2.2) -------------
@@ -594,9 +551,12 @@ __global__ void k_exact_math(int which, unsigned long long *out) {
 void pt_launch_exact_math(hipStream_t s, int which, unsigned long long *out) {
     hipLaunchKernelGGL(k_exact_math, dim3(256 * 16), dim3(256), 0, s, which, out);
 }
-void pt_launch_raygen(hipStream_t s, int blocks, const ptmi_camera &cam, DevBand band, uint32_t frame0,
-                      uint32_t n_frames, DevPaths p, uint32_t *count_out) {
-    hipLaunchKernelGGL(k_raygen, dim3(blocks), dim3(BLOCK), 0, s, cam, band, frame0, n_frames, p, count_out);
+void pt_launch_raygen(hipStream_t s, int blocks, const ptmi_camera &cam, DevPixels px, uint32_t n_frames, DevPaths p,
+                      uint32_t *count_out) {
+    if (px.list)
+        hipLaunchKernelGGL(k_ad_raygen, dim3(blocks), dim3(BLOCK), 0, s, cam, px.band, px.list, px.n_active, n_frames, px.mom, p, count_out,
+                           px.traced);
+    else hipLaunchKernelGGL(k_raygen, dim3(blocks), dim3(BLOCK), 0, s, cam, px.band, px.frame0, n_frames, p, count_out);
 }
 void pt_launch_raygen_list(hipStream_t s, const ptmi_camera &cam, uint32_t n, const uint32_t *xs,
                            const uint32_t *ys, const uint32_t *frames, DevPaths p) {
@@ -627,18 +587,25 @@ void pt_launch_repack(hipStream_t s, int blocks, const uint32_t *count, const ui
                       uint32_t *pid) {
     hipLaunchKernelGGL(k_repack, dim3(blocks), dim3(BLOCK), 0, s, count, queue, from, to, pid);
 }
-void pt_launch_accumulate(hipStream_t s, int blocks, DevBand band, uint32_t frame0, uint32_t n_frames,
-                          const float *L, uint32_t l_stride, float4 *out) {
-    hipLaunchKernelGGL(k_accumulate, dim3(blocks), dim3(BLOCK), 0, s, band, frame0, n_frames, L, l_stride, out);
+void pt_launch_accumulate(hipStream_t s, int blocks, DevPixels px, uint32_t n_frames, const float *L, uint32_t l_stride, float4 *out) {
+    if (px.list)
+        hipLaunchKernelGGL(k_ad_accumulate, dim3(blocks), dim3(BLOCK), 0, s, px.band, px.list, px.n_active, n_frames, px.mom, L, l_stride, out);
+    else hipLaunchKernelGGL(k_accumulate, dim3(blocks), dim3(BLOCK), 0, s, px.band, px.frame0, n_frames, L, l_stride, out);
 }
-void pt_launch_accumulate_aov(hipStream_t s, int blocks, DevBand band, uint32_t frame0, uint32_t n_frames, const float4 *rec,
+void pt_launch_accumulate_aov(hipStream_t s, int blocks, DevPixels px, uint32_t n_frames, const float4 *rec,
                               const ptmi_triangle *tris, uint32_t n_tris, float4 *albedo, float4 *normal, uint2 *ids) {
-    hipLaunchKernelGGL(k_accumulate_aov, dim3(blocks), dim3(BLOCK), 0, s, band, frame0, n_frames, rec, tris, n_tris, albedo, normal,
-                       ids);
+    if (px.list)
+        hipLaunchKernelGGL(k_ad_accumulate_aov, dim3(blocks), dim3(BLOCK), 0, s, px.band, px.list, px.n_active, n_frames, px.mom, rec, tris,
+                           n_tris, albedo, normal, ids);
+    else
+        hipLaunchKernelGGL(k_accumulate_aov, dim3(blocks), dim3(BLOCK), 0, s, px.band, px.frame0, n_frames, rec, tris, n_tris, albedo, normal,
+                           ids);
 }
-void pt_launch_accumulate_moments(hipStream_t s, int blocks, DevBand band, uint32_t frame0, uint32_t n_frames, const float *L,
-                                  uint32_t l_stride, float4 *mom) {
-    hipLaunchKernelGGL(k_accumulate_moments, dim3(blocks), dim3(BLOCK), 0, s, band, frame0, n_frames, L, l_stride, mom);
+void pt_launch_accumulate_moments(hipStream_t s, int blocks, DevPixels px, uint32_t n_frames, const float *L, uint32_t l_stride,
+                                  float4 *mom) {
+    if (px.list)
+        hipLaunchKernelGGL(k_ad_accumulate_moments, dim3(blocks), dim3(BLOCK), 0, s, px.band, px.list, px.n_active, n_frames, L, l_stride, mom);
+    else hipLaunchKernelGGL(k_accumulate_moments, dim3(blocks), dim3(BLOCK), 0, s, px.band, px.frame0, n_frames, L, l_stride, mom);
 }
 void pt_launch_adaptive_restart(hipStream_t s, int blocks, DevBand band, float4 *mom) {
     hipLaunchKernelGGL(k_ad_restart, dim3(blocks), dim3(BLOCK), 0, s, band, mom);
@@ -649,24 +616,6 @@ void pt_launch_adaptive_list(hipStream_t s, int blocks, DevBand band, const ptmi
     hipLaunchKernelGGL(k_ad_select, dim3(blocks), dim3(BLOCK), 0, s, band, ap, mom, ad.ballot, ad.ctl);
     hipLaunchKernelGGL(k_ad_tile_sums, dim3(tiles), dim3(TILE_WORDS), 0, s, &ad.ctl[0], ad.ballot, ad.tile_sums);
     hipLaunchKernelGGL(k_ad_scatter, dim3(tiles), dim3(TILE_WORDS), 0, s, &ad.ctl[0], ad.ballot, ad.tile_sums, ad.list, &ad.ctl[1]);
-}
-void pt_launch_adaptive_raygen(hipStream_t s, int blocks, const ptmi_camera &cam, DevBand band, DevAdaptive ad, uint32_t n_frames,
-                               const float4 *mom, DevPaths p, uint32_t *count_out) {
-    hipLaunchKernelGGL(k_ad_raygen, dim3(blocks), dim3(BLOCK), 0, s, cam, band, ad.list, &ad.ctl[1], n_frames, mom, p, count_out, ad.acc);
-}
-void pt_launch_adaptive_accumulate(hipStream_t s, int blocks, DevBand band, DevAdaptive ad, uint32_t n_frames, const float4 *mom,
-                                   const float *L, uint32_t l_stride, float4 *out) {
-    hipLaunchKernelGGL(k_ad_accumulate, dim3(blocks), dim3(BLOCK), 0, s, band, ad.list, &ad.ctl[1], n_frames, mom, L, l_stride, out);
-}
-void pt_launch_adaptive_accumulate_aov(hipStream_t s, int blocks, DevBand band, DevAdaptive ad, uint32_t n_frames, const float4 *mom,
-                                       const float4 *rec, const ptmi_triangle *tris, uint32_t n_tris, float4 *albedo, float4 *normal,
-                                       uint2 *ids) {
-    hipLaunchKernelGGL(k_ad_accumulate_aov, dim3(blocks), dim3(BLOCK), 0, s, band, ad.list, &ad.ctl[1], n_frames, mom, rec, tris, n_tris,
-                       albedo, normal, ids);
-}
-void pt_launch_adaptive_accumulate_moments(hipStream_t s, int blocks, DevBand band, DevAdaptive ad, uint32_t n_frames, const float *L,
-                                           uint32_t l_stride, float4 *mom) {
-    hipLaunchKernelGGL(k_ad_accumulate_moments, dim3(blocks), dim3(BLOCK), 0, s, band, ad.list, &ad.ctl[1], n_frames, L, l_stride, mom);
 }
 void pt_launch_adaptive_status(hipStream_t s, int blocks, DevBand band, const float4 *mom, DevAdaptive ad) {
     hipLaunchKernelGGL(k_ad_status, dim3(blocks), dim3(BLOCK), 0, s, band, mom, ad.acc);

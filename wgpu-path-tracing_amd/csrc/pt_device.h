@@ -105,6 +105,8 @@ struct DevBand {
         if (parts <= 1u) return y0 + l;
         return y0 + ((l / strip) * parts + part) * strip + l % strip;
     }
+    // band-local pixel (local row * width + x) -> its index in the width x height frame
+    PT_HD size_t frame_pixel(uint32_t pix) const { return (size_t)row_of(pix / width) * width + pix % width; }
 };
 
 // Russian roulette (pt.wgsl:699-705) from this bounce on. The first such bounce is also where the batch's path state is repacked:
@@ -197,8 +199,17 @@ inline uint32_t pt_variant_code(const TraverseConfig &cfg) { return (uint32_t)cf
 size_t pt_spill_bytes(int blocks);
 
 // ---- launchers (each enqueues on `s`; grids are persistent, sized by the caller) ----
-void pt_launch_raygen(hipStream_t s, int blocks, const ptmi_camera &cam, DevBand band, uint32_t frame0,
-                      uint32_t n_frames, DevPaths p, uint32_t *count_out);
+// The pixels a batch walks, in ray generation and the three folds: every pixel of the band from frame `frame0` on (list == NULL:
+// plain dispatch), or the *n_active band-local pixels of `list`, each from its own frame index mom[pixel].z (adaptive dispatch).
+// n_frames frames of each: path k * entries + j is frame k of entry j.
+struct DevPixels {
+    DevBand band; uint32_t frame0;
+    const uint32_t *list, *n_active; const float4 *mom;
+    unsigned long long *traced;         // listed: [0] += the batch's paths (a plain dispatch counts its paths on the host)
+};
+// *count_out = entries * n_frames
+void pt_launch_raygen(hipStream_t s, int blocks, const ptmi_camera &cam, DevPixels px, uint32_t n_frames, DevPaths p,
+                      uint32_t *count_out);
 void pt_launch_raygen_list(hipStream_t s, const ptmi_camera &cam, uint32_t n, const uint32_t *xs,
                            const uint32_t *ys, const uint32_t *frames, DevPaths p);
 void pt_launch_extend(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &sc, DevPaths p,
@@ -229,15 +240,15 @@ void pt_launch_compact(hipStream_t s, int tiles, const uint32_t *queue, const ui
                        const uint64_t *alive_mask, const uint64_t *shadow_mask, uint32_t *tile_sums,
                        uint32_t *next_queue, uint32_t *next_count, uint32_t *shadow_queue, uint32_t *shadow_count,
                        unsigned long long *stats, uint32_t bounce, int do_scatter);
-void pt_launch_accumulate(hipStream_t s, int blocks, DevBand band, uint32_t frame0, uint32_t n_frames,
-                          const float *L, uint32_t l_stride, float4 *out);
-// the first-hit planes (ptmi_set_aovs) from the batch's bounce-0 records, frames in ascending order like pt_launch_accumulate;
-// a NULL plane is not written
-void pt_launch_accumulate_aov(hipStream_t s, int blocks, DevBand band, uint32_t frame0, uint32_t n_frames, const float4 *rec,
+// the three folds of a batch over its pixels (DevPixels), each pixel's frames in ascending order. Listed pixels read their frame index
+// from mom.z, which the moments fold moves on: it goes last.
+void pt_launch_accumulate(hipStream_t s, int blocks, DevPixels px, uint32_t n_frames, const float *L, uint32_t l_stride, float4 *out);
+// the first-hit planes (ptmi_set_aovs) from the batch's bounce-0 records; a NULL plane is not written
+void pt_launch_accumulate_aov(hipStream_t s, int blocks, DevPixels px, uint32_t n_frames, const float4 *rec,
                               const ptmi_triangle *tris, uint32_t n_tris, float4 *albedo, float4 *normal, uint2 *ids);
-// the sample-moments plane (ptmi_set_moments) from the batch's per-path radiance, frames in ascending order like pt_launch_accumulate
-void pt_launch_accumulate_moments(hipStream_t s, int blocks, DevBand band, uint32_t frame0, uint32_t n_frames, const float *L,
-                                  uint32_t l_stride, float4 *mom);
+// the sample-moments plane (ptmi_set_moments) from the batch's per-path radiance; listed pixels: mom is px.mom
+void pt_launch_accumulate_moments(hipStream_t s, int blocks, DevPixels px, uint32_t n_frames, const float *L, uint32_t l_stride,
+                                  float4 *mom);
 // adaptive sampling (ptmi_dispatch_adaptive; kernels in pipeline.hip): the context's buffers of a round
 struct DevAdaptive {
     uint64_t *ballot;             // one word per 64 band pixels: bit set = the pixel gets frames this round
@@ -250,17 +261,7 @@ uint32_t pt_adaptive_tiles(uint32_t npix);
 void pt_launch_adaptive_restart(hipStream_t s, int blocks, DevBand band, float4 *mom);          // every count of the band back to 0
 // select + list build: ad.ballot, ad.list, ad.ctl of this round from the moments plane
 void pt_launch_adaptive_list(hipStream_t s, int blocks, DevBand band, const ptmi_adaptive_params &ap, const float4 *mom, DevAdaptive ad);
-// path k * n_active + j = frame mom.z + k of pixel list[j], k < n_frames; *count_out = n_active * n_frames
-void pt_launch_adaptive_raygen(hipStream_t s, int blocks, const ptmi_camera &cam, DevBand band, DevAdaptive ad, uint32_t n_frames,
-                               const float4 *mom, DevPaths p, uint32_t *count_out);
-// the three folds over the list, each pixel from its own frame index mom.z; the moments fold goes last (it moves mom.z on)
-void pt_launch_adaptive_accumulate(hipStream_t s, int blocks, DevBand band, DevAdaptive ad, uint32_t n_frames, const float4 *mom,
-                                   const float *L, uint32_t l_stride, float4 *out);
-void pt_launch_adaptive_accumulate_aov(hipStream_t s, int blocks, DevBand band, DevAdaptive ad, uint32_t n_frames, const float4 *mom,
-                                       const float4 *rec, const ptmi_triangle *tris, uint32_t n_tris, float4 *albedo, float4 *normal,
-                                       uint2 *ids);
-void pt_launch_adaptive_accumulate_moments(hipStream_t s, int blocks, DevBand band, DevAdaptive ad, uint32_t n_frames, const float *L,
-                                           uint32_t l_stride, float4 *mom);
+// (ray generation and the folds of a round: pt_launch_raygen / pt_launch_accumulate* with the list as their DevPixels)
 void pt_launch_adaptive_status(hipStream_t s, int blocks, DevBand band, const float4 *mom, DevAdaptive ad);
 // the denoiser (denoise.hip, ptmi_denoise): a prepass into guide / grad / cv, then `iterations` a-trous passes ping-ponging between
 // cv and tmp, the last remodulating into out. albedo NULL: no demodulation. cv is overwritten.

@@ -1193,9 +1193,9 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         if (ap && cam->frame_index == 0u) { pt_launch_adaptive_restart(ms, blocks, band, c->d_moments); c->ad_rounds = 0; }
         // a batch: fb frames of every pixel from frame0 on, or (ap) of every listed pixel from its own count on
         auto batch = [&](uint32_t frame0, uint32_t fb) -> int {
-            { Timed t(c, 4, t3, ms);
-              if (ap) pt_launch_adaptive_raygen(ms, blocks, *cam, band, c->ad, fb, c->d_moments, bp, &ln.counts[0]);
-              else pt_launch_raygen(ms, blocks, *cam, band, frame0, fb, bp, &ln.counts[0]); }
+            const DevPixels px = ap ? DevPixels{band, 0u, c->ad.list, &c->ad.ctl[1], c->d_moments, c->ad.acc}
+                                    : DevPixels{band, frame0, nullptr, nullptr, nullptr, nullptr};
+            { Timed t(c, 4, t3, ms); pt_launch_raygen(ms, blocks, *cam, px, fb, bp, &ln.counts[0]); }
             int cur = 0;
             for (uint32_t b = 0; b < maxb; b++) {
                 const bool tail = b > rb;                                   // the state is in the tail arrays
@@ -1234,19 +1234,13 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
                 if (maxb >= 2) HIP_TRY(c, hipStreamWaitEvent(ms, ln.ev_shadow[maxb & 1u], 0));
             }
             Timed t(c, 6, t3, ms);
-            if (ap) {                                                   // the moments fold last: the other two read the counts from it
-                pt_launch_adaptive_accumulate(ms, blocks, band, c->ad, fb, c->d_moments, bp.L, bp.l_stride, c->d_out);
-                if (aov_rec)
-                    pt_launch_adaptive_accumulate_aov(ms, blocks, band, c->ad, fb, c->d_moments, aov_rec, c->sc.tris, c->sc.n_tris,
-                                                      c->d_aov_albedo, c->d_aov_normal, c->d_aov_id);
-                pt_launch_adaptive_accumulate_moments(ms, blocks, band, c->ad, fb, bp.L, bp.l_stride, c->d_moments);
-                return PTMI_OK;
-            }
-            pt_launch_accumulate(ms, blocks, band, frame0, fb, bp.L, bp.l_stride, c->d_out);
+            pt_launch_accumulate(ms, blocks, px, fb, bp.L, bp.l_stride, c->d_out);
             if (aov_rec)
-                pt_launch_accumulate_aov(ms, blocks, band, frame0, fb, aov_rec, c->sc.tris, c->sc.n_tris, c->d_aov_albedo,
-                                         c->d_aov_normal, c->d_aov_id);
-            if (c->d_moments) pt_launch_accumulate_moments(ms, blocks, band, frame0, fb, bp.L, bp.l_stride, c->d_moments);
+                pt_launch_accumulate_aov(ms, blocks, px, fb, aov_rec, c->sc.tris, c->sc.n_tris, c->d_aov_albedo, c->d_aov_normal,
+                                         c->d_aov_id);
+            // the moments fold goes last: it moves mom.z on, where the other two read the listed pixels' counts. An adaptive dispatch
+            // always has the plane (it is refused without); a plain one folds it only while it is on.
+            if (ap || c->d_moments) pt_launch_accumulate_moments(ms, blocks, px, fb, bp.L, bp.l_stride, c->d_moments);
             return PTMI_OK;
         };
         if (ap) {
