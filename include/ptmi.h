@@ -150,8 +150,8 @@ typedef struct ptmi_stats {
      * stack never runs out — shows it did not) */
     uint64_t verify_failed;
     uint32_t tree_builder_used; /* who built the hierarchy the last upload's regular rays walk: 1 the host, 2 the device (both leaf modes);
-                                   0 none: the uploaded tree is walked as it is (keep_reference_tree, an empty scene, a tree with
-                                   non-finite boxes) */
+                                   0 none: the uploaded tree is walked as it is (keep_reference_tree, an empty scene, a tree whose
+                                   root is a leaf — there is no hierarchy over a single leaf —, a tree with non-finite boxes) */
     uint32_t reserved_stats[1];
 } ptmi_stats;
 
