@@ -854,14 +854,37 @@ uint64_t pto_render_tap(const pto_scene *s, const ptmi_camera *cam, uint32_t n_f
     return n;
 }
 
+/* one path of pixel (x, y) at `frame`: what pto_trace_path and pto_trace_paths both report */
+static v3 trace_one(const pto_scene *s, const ptmi_camera *cam, uint32_t x, uint32_t y, uint32_t frame, const pto_options *opt,
+                    counters_t *c, float *log16, int *n_log) {
+    uint32_t rng;
+    ray_t r = camera_ray(cam, x, y, frame, &rng);
+    return trace(s, &rng, r, opt ? opt->max_bounces : 8u, opt ? (int)opt->do_mis : 1, c, log16, n_log);
+}
+
 int pto_trace_path(const pto_scene *s, const ptmi_camera *cam, uint32_t x, uint32_t y,
                    uint32_t frame, const pto_options *opt, float *radiance3, float *log16) {
     counters_t c; memset(&c, 0, sizeof c);
-    uint32_t rng; int nl = 0;
-    ray_t r = camera_ray(cam, x, y, frame, &rng);
-    v3 col = trace(s, &rng, r, opt ? opt->max_bounces : 8u, opt ? (int)opt->do_mis : 1, &c, log16, &nl);
+    int nl = 0;
+    v3 col = trace_one(s, cam, x, y, frame, opt, &c, log16, &nl);
     radiance3[0] = col.x; radiance3[1] = col.y; radiance3[2] = col.z;
     return nl;
+}
+
+int pto_trace_paths(const pto_scene *s, const ptmi_camera *cam, uint64_t n, const uint32_t *xs, const uint32_t *ys,
+                    const uint32_t *frames, const pto_options *opt, float *radiance3, uint32_t *segments) {
+    int nthreads = 1;
+#ifdef _OPENMP
+    nthreads = (opt && opt->threads) ? (int)opt->threads : omp_get_max_threads();
+#endif
+#pragma omp parallel for schedule(dynamic, 256) num_threads(nthreads)
+    for (int64_t i = 0; i < (int64_t)n; i++) {
+        counters_t c; memset(&c, 0, sizeof c);
+        v3 col = trace_one(s, cam, xs[i], ys[i], frames[i], opt, &c, NULL, NULL);
+        radiance3[3 * i] = col.x; radiance3[3 * i + 1] = col.y; radiance3[3 * i + 2] = col.z;
+        if (segments) segments[i] = (uint32_t)c.segments;
+    }
+    return 0;
 }
 
 /* Analysis aid (not a parity function): work counters of an ordered two-box descent with the

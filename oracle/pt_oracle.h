@@ -107,6 +107,12 @@ uint64_t pto_render_tap(const pto_scene *s, const ptmi_camera *cam, uint32_t n_f
 int pto_trace_path(const pto_scene *s, const ptmi_camera *cam, uint32_t x, uint32_t y,
                    uint32_t frame, const pto_options *opt, float *radiance3, float *log16);
 
+/* pto_trace_path for n (x, y, frame) triples at once, threaded like pto_render (opt->threads; 0: all): radiance3[3 i ..] = the
+ * unclamped result of path i, segments[i] (may be NULL) = the segments it traced = its log records with alive = 1. Both entry
+ * points trace through one function. */
+int pto_trace_paths(const pto_scene *s, const ptmi_camera *cam, uint64_t n, const uint32_t *xs, const uint32_t *ys,
+                    const uint32_t *frames, const pto_options *opt, float *radiance3, uint32_t *segments);
+
 /* blit.wgsl:43-155 (presentation pass; tolerance-compared). rgba/out: W*H*4 floats, out row 0 = canvas top. */
 void pto_blit(const float *rgba, uint32_t W, uint32_t H, float *out_rgba);
 

@@ -11,6 +11,9 @@ mix(a, b, t) = fma(b, t, a * (1 - t)), the FMA emulated in float64 as tests/deno
           and the image is noisy) (neighbourhood 1).
   run     keeps an image, a moments plane (hence the counts) and what the device counters would say; the per-path radiance of a
           (pixel, frame) comes from Oracle.trace_path, which agrees with the kernels bit for bit.
+  run_planes  the same rule over whole planes, for frames too large for run's loop over pixels: select, then one Oracle.trace_paths
+          call per round and frame offset for all listed pixels, then fold_listed. tests/test_adaptive_host.py holds the two equal
+          bit for bit; run stays as the statement of the rule.
 """
 import numpy as np
 
@@ -85,7 +88,7 @@ def select(moments, params, rows=None):
 
 
 def _mix(a, b, t):
-    t = f32(t)
+    t = np.asarray(t, np.float32)
     p = np.asarray(a, np.float32) * (f32(1) - t)
     return (np.asarray(b, np.float32).astype(np.float64) * np.float64(t) + p.astype(np.float64)).astype(np.float32)
 
@@ -137,6 +140,48 @@ def run(oracle, scene, cam, params, rounds, rows=None, state=None, restart=True,
                 st.segments += int((log[:, 15] == 1).sum())          # the last record (alive = 0) is no segment
             st.image[y, x] = (rgb[0], rgb[1], rgb[2], 0)
             st.moments[y, x] = mom
+        st.paths += st.active[-1] * p["step"]
+        st.rounds += 1
+    return st
+
+
+def fold_listed(rgb, mom, L, frame):
+    """fold_pixel for n pixels at once: rgb (n, 3), mom (n, 4), per-path radiance L (n, 3), each pixel at its own frame (n,)"""
+    frame = np.asarray(frame, np.uint32)
+    c = np.fmin(np.asarray(L, np.float32), f32(2.5))
+    l = f32(0.2126) * c[:, 0] + f32(0.7152) * c[:, 1] + f32(0.0722) * c[:, 2]
+    m = np.stack([l, l * l], axis=1).astype(np.float32)
+    t = (f32(1) / (frame + np.uint32(1)).astype(np.float32))[:, None]
+    later = (frame > 0)[:, None]
+    with np.errstate(invalid="ignore", over="ignore"):
+        c = np.where(later, _mix(rgb, c, t), c).astype(np.float32)
+        m = np.where(later, _mix(mom[:, :2], m, t), m).astype(np.float32)
+    out = np.zeros((len(frame), 4), np.float32)
+    out[:, :2], out[:, 2] = m, (frame + np.uint32(1)).astype(np.float32)
+    return c, out
+
+
+def run_planes(oracle, scene, cam, params, rounds, rows=None, state=None, restart=True, max_bounces=8, do_mis=1):
+    """run(), with the listed pixels of a round traced and folded together (same arguments, same State, bit for bit)"""
+    p = resolve(params)
+    W, H = int(cam["width"]), int(cam["height"])
+    st = State(H, W) if state is None else state
+    inside = rows_mask(H, rows)
+    if restart:
+        st.moments[inside, :, 2] = 0
+        st.rounds = 0
+    for _ in range(rounds):
+        act = select(st.moments, p, inside)
+        st.active.append(int(act.sum()))
+        ys, xs = np.nonzero(act)
+        rgb, mom = st.image[ys, xs, :3], st.moments[ys, xs]
+        n0 = mom[:, 2].astype(np.uint32)
+        for k in range(p["step"] if len(ys) else 0):
+            L, seg = oracle.trace_paths(scene, cam, xs, ys, n0 + np.uint32(k), max_bounces=max_bounces, do_mis=do_mis)
+            rgb, mom = fold_listed(rgb, mom, L, n0 + np.uint32(k))
+            st.segments += int(seg.sum(dtype=np.uint64))
+        st.image[ys, xs, :3], st.image[ys, xs, 3] = rgb, 0
+        st.moments[ys, xs] = mom
         st.paths += st.active[-1] * p["step"]
         st.rounds += 1
     return st

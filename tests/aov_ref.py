@@ -60,15 +60,19 @@ def _mapped_normal(tri_rec, u, v, n_i, texel):
     return _unit(Tn * m[0] + Bn * m[1] + n_i * m[2])
 
 
-def samples(oracle, scene, cam, frame):
-    """One frame's first hits for every pixel, row-major (index y * W + x). Returns a dict of arrays:
+def samples(oracle, scene, cam, frame, rows=None):
+    """One frame's first hits for every pixel, row-major (index y * W + x), or with `rows` (ascending row numbers) for the pixels of
+    those rows only, row after row (index i * W + x for rows[i]: the texel candidates are a Python loop per pixel, and a large frame is
+    sampled by rows). Returns a dict of arrays:
     albedo (n, 3) f32 (first candidate), normal (n, 3) f64, t (n,) f32 (0 on a miss), tri, mat (n,) u32, hit (n,) bool,
     albedo_exact / normal_exact (n,) bool: one texel decides the value, normal_mapped (n,) bool: a normal map bent it."""
     W, H = int(cam["width"]), int(cam["height"])
-    ys, xs = np.divmod(np.arange(W * H, dtype=np.uint32), np.uint32(W))
-    o, d, _ = oracle.raygen(cam, xs, ys, np.full(W * H, frame, np.uint32))
+    rows = np.arange(H, dtype=np.uint32) if rows is None else np.asarray(rows, np.uint32)
+    assert rows.ndim == 1 and (rows < H).all()
+    ys, xs = np.repeat(rows, W), np.tile(np.arange(W, dtype=np.uint32), len(rows))
+    n = len(ys)
+    o, d, _ = oracle.raygen(cam, xs, ys, np.full(n, frame, np.uint32))
     t, tri, u, v, _ = oracle.intersect(scene, o, d)
-    n = W * H
     hit = ~(t < 0)
     out = dict(albedo=np.zeros((n, 3), np.float32), normal=np.zeros((n, 3), np.float64),
                t=np.where(hit, t, np.float32(0)).astype(np.float32), tri=np.where(hit, tri, MISS).astype(np.uint32),

@@ -153,6 +153,22 @@ class Oracle:
         n = self.L.pto_trace_path(ctypes.byref(s), _ptr(cam), x, y, frame, ctypes.byref(opt), _ptr(rad), _ptr(log))
         return rad, log[:n]
 
+    def trace_paths(self, scene, cam, xs, ys, frames, max_bounces=8, do_mis=1, threads=0):
+        """trace_path for arrays of (x, y, frame): per-path radiance (n, 3) float32 (unclamped) and segment count (n,) uint32 (the
+        records of trace_path's log with alive = 1), threaded like render"""
+        xs, ys, frames = (np.ascontiguousarray(a, np.uint32).ravel() for a in (xs, ys, frames))
+        n = len(xs)
+        assert len(ys) == n and len(frames) == n
+        rad, seg = np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
+        opt = PtoOptions(max_bounces, do_mis, 0, 0, threads)
+        s = self.scene_struct(scene)
+        fn = self.L.pto_trace_paths
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * 6
+        rc = fn(ctypes.byref(s), _ptr(cam), n, _ptr(xs), _ptr(ys), _ptr(frames), ctypes.byref(opt), _ptr(rad), _ptr(seg))
+        assert rc == 0
+        return rad, seg
+
     # -- probes ----------------------------------------------------------------
     def eval_bsdf(self, albedo, rough, metal, trans, ior, n, v, l, front=True):
         a, n, v, l = (np.ascontiguousarray(q, np.float32) for q in (albedo, n, v, l))

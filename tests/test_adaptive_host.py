@@ -1,11 +1,13 @@
 """Adaptive sampling without a GPU (include/ptmi.h ptmi_dispatch_adaptive): the ABI surface, the selection rule of
-tests/adaptive_ref.py on synthetic planes, the model against the oracle's plain renders, and its quality at equal budget."""
+tests/adaptive_ref.py on synthetic planes, the model against the oracle's plain renders, its quality at equal budget, and the model's
+whole-plane form (run_planes over Oracle.trace_paths) against its per-pixel statement (run over Oracle.trace_path)."""
 import ctypes
 import os
 import re
 import subprocess
 
 import numpy as np
+import pytest
 
 import adaptive_ref
 
@@ -175,3 +177,63 @@ def test_quality_at_equal_budget(oracle, scene_factory):
     print("samples", total, "uniform frames", -(-total // (W * H)), "mse adaptive", mse(st.image), "uniform", mse(uni),
           "gain", mse(uni) / mse(st.image))
     assert mse(st.image) * K < mse(uni), (mse(st.image), mse(uni))
+
+
+# the cases tests/test_gpu_adaptive.py compares with the GPU at 24 x 20 (its P and ROUNDS), here through both forms of the model
+P_GPU = dict(threshold=0.35, floor=0.05, min_frames=4, max_frames=64, step=4, neighbourhood=1)
+BANDS = [None, dict(tile_y0=5, tile_y1=14), dict(tile_parts=3, tile_part=1, tile_strip=2),
+         dict(tile_y0=2, tile_y1=19, tile_parts=2, tile_part=0, tile_strip=3)]
+
+
+def _same_state(a, b, rows=None):
+    assert np.array_equal(a.image.view(np.uint32), b.image.view(np.uint32))
+    assert np.array_equal(a.moments.view(np.uint32), b.moments.view(np.uint32))
+    assert a.active == b.active and a.paths == b.paths and a.segments == b.segments and a.rounds == b.rounds
+    assert adaptive_ref.status(a, rows) == adaptive_ref.status(b, rows)
+
+
+@pytest.mark.parametrize("name", ["cornell", "feature_box"])
+@pytest.mark.parametrize("neighbourhood", [0, 1])
+@pytest.mark.parametrize("band", range(len(BANDS)))
+def test_run_planes_equals_run(oracle, scene_factory, name, neighbourhood, band):
+    from ptmi import layout
+    sc = scene_factory(name)
+    W, H = 24, 20
+    cam = layout.make_camera(W, H)
+    p = dict(P_GPU, neighbourhood=neighbourhood)
+    t = BANDS[band]
+    rows = None if t is None else adaptive_ref.band_rows(H, t.get("tile_y0", 0), t.get("tile_y1", 0), t.get("tile_parts", 1),
+                                                         t.get("tile_part", 0), t.get("tile_strip", 1))
+    a = adaptive_ref.run(oracle, sc, cam, p, 6, rows=rows)
+    b = adaptive_ref.run_planes(oracle, sc, cam, p, 6, rows=rows)
+    assert len(set(a.active)) > 1 and 0 < a.active[-1] < a.active[0]          # rounds with lists of their own
+    _same_state(a, b, rows)
+    # continued without a restart, from a state of the other form's making
+    a2 = adaptive_ref.run(oracle, sc, cam, p, 2, rows=rows, state=a, restart=False)
+    b2 = adaptive_ref.run_planes(oracle, sc, cam, p, 2, rows=rows, state=b, restart=False)
+    _same_state(a2, b2, rows)
+
+
+@pytest.mark.parametrize("name,dof", [("cornell", False), ("feature_box", True)])
+def test_trace_paths_equals_trace_path(oracle, scene_factory, name, dof):
+    from ptmi import layout
+    sc = scene_factory(name)
+    W, H = 257, 131
+    cam = layout.make_camera(W, H, aperture=0.05, focus_distance=2.5) if dof else layout.make_camera(W, H)
+    rng = np.random.default_rng(20 + dof)
+    n = 3000
+    xs, ys = rng.integers(0, W, n, dtype=np.uint32), rng.integers(0, H, n, dtype=np.uint32)
+    frames = rng.integers(0, 5000, n, dtype=np.uint32)
+    for mb, mis in ((8, 1), (3, 0)):
+        L, seg = oracle.trace_paths(sc, cam, xs, ys, frames, max_bounces=mb, do_mis=mis)
+        assert L.shape == (n, 3) and seg.shape == (n,)
+        for i in range(n):
+            r, log = oracle.trace_path(sc, cam, int(xs[i]), int(ys[i]), int(frames[i]), max_bounces=mb, do_mis=mis)
+            assert np.array_equal(r.view(np.uint32), L[i].view(np.uint32)), i
+            assert int((log[:, 15] == 1).sum()) == seg[i], i
+        assert 1 <= seg.min() and seg.max() <= mb and len(np.unique(seg)) > 1
+        # one thread or all: the same paths
+        L1, seg1 = oracle.trace_paths(sc, cam, xs, ys, frames, max_bounces=mb, do_mis=mis, threads=1)
+        assert np.array_equal(L1.view(np.uint32), L.view(np.uint32)) and np.array_equal(seg1, seg)
+    L0, seg0 = oracle.trace_paths(sc, cam, xs[:0], ys[:0], frames[:0])
+    assert L0.shape == (0, 3) and seg0.shape == (0,)

@@ -54,16 +54,17 @@ def run(ctx, cam, dispatches, f0=0):
     return ctx.read_output()
 
 
-def per_path(oracle, sc, cam, frames):
+def per_path_rows(oracle, sc, cam, frames, rows=None, **opt):
+    """denoise_ref.fold_moments's input from Oracle.trace_paths: per frame the (n, 3) per-path radiance of every pixel of `rows`
+    (ascending row numbers; None: the whole frame), row after row"""
     W, H = int(cam["width"]), int(cam["height"])
-    out = []
-    for f in frames:
-        L = np.zeros((W * H, 3), np.float32)
-        for y in range(H):
-            for x in range(W):
-                L[y * W + x] = oracle.trace_path(sc, cam, x, y, f)[0]
-        out.append(L)
-    return out
+    rows = np.arange(H, dtype=np.uint32) if rows is None else np.asarray(rows, np.uint32)
+    ys, xs = np.repeat(rows, W), np.tile(np.arange(W, dtype=np.uint32), len(rows))
+    return [oracle.trace_paths(sc, cam, xs, ys, np.full(len(ys), f, np.uint32), **opt)[0] for f in frames]
+
+
+def per_path(oracle, sc, cam, frames):
+    return per_path_rows(oracle, sc, cam, frames)
 
 
 def err(fn, *a, **kw):
