@@ -173,7 +173,8 @@ int ptmi_upload_scene(ptmi_ctx *ctx,
 /* Binding 6. texels: width*height RGBA, row-major, texel (0,0) first. NULL/0 removes the atlas. An unknown format or a
  * width*height*texel size that does not fit in size_t gives PTMI_E_INVALID; a call that fails leaves the current atlas in place. */
 int ptmi_upload_atlas(ptmi_ctx *ctx, const void *texels, uint32_t width, uint32_t height, int format);
-/* Binding 0: (re)allocates the width*height*16-byte output buffer, zero-filled (renderer.ts:272-279, :496-510). */
+/* Binding 0: (re)allocates the width*height*16-byte output buffer, zero-filled (renderer.ts:272-279, :496-510). A failed call
+ * leaves the previous state in place: the size, every plane with its contents, and the output binding. */
 int ptmi_resize(ptmi_ctx *ctx, uint32_t width, uint32_t height);
 int ptmi_set_options(ptmi_ctx *ctx, const ptmi_options *opt);
 int ptmi_get_options(const ptmi_ctx *ctx, ptmi_options *opt);

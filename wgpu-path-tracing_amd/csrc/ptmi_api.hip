@@ -37,6 +37,30 @@ enum SceneBuf {
     kSceneBufs
 };
 
+// The per-pixel buffers that follow the output size, one entry each (kFrame below: what each takes and when it is made).
+enum FramePlane {
+    kOut,                                          // the context's own output buffer (binding 0)
+    kAovAlbedo, kAovNormal, kAovId,                // first-hit planes (ptmi_set_aovs), in the order of the PTMI_AOV_* bits
+    kMoments,                                      // sample moments (ptmi_set_moments)
+    kDnGuide, kDnGrad, kDnA, kDnB, kDnOut,         // the denoiser's: guide (unit normal, depth), depth gradient, two ping-pong colour +
+                                                   // variance planes, the result
+    kAdBallot, kAdList, kAdTileSums,               // adaptive sampling: ballot words, pixel list, tile totals
+    kBlitF32, kBlitU8,                             // canvas staging of ptmi_blit
+    kFramePlanes
+};
+
+// The per-path arrays of a batch, one entry each (kLaneBytes below: what each takes per path), in the order they are allocated.
+enum LaneBuf {
+    kPathO, kPathD, kPathC, kPathL,                // path state; L has room for either stride
+    kHits,
+    kShadow0, kShadowIdx0, kShadow1, kShadowIdx1,  // shadow records (SO, SD, SC in one block) and their index arrays, by bounce parity
+    kTailO, kTailD, kTailC, kPid,                  // state by queue slot after the repack, and the path id of each such slot
+    kQueue0, kQueue1,
+    kOcc,                                          // occlusion bytes (ptmi_debug_occluded)
+    kAovRec,                                       // first-hit records of bounce 0 (k_shade<true>); only while AOV planes are on
+    kLaneBufs
+};
+
 struct EventPair { hipEvent_t a, b; int kind; };   // kind: 0 dispatch, 1 extend, 2 shade, 3 shadow, 4 raygen, 5 compaction, 6 accumulate
 constexpr size_t kMaxPendingEvents = 4096;        // a caller that never synchronises (a preview loop) must not grow the list without bound
 
@@ -45,6 +69,7 @@ constexpr size_t kMaxPendingEvents = 4096;        // a caller that never synchro
 // The buffers of the wavefront batch in flight, and the second stream that lets `shadow` run beside the next bounce.
 struct Lane {
     size_t cap = 0;
+    void *buf[kLaneBufs] = {};                         // indexed by LaneBuf; the typed members below are views of it (lane_views)
     DevPaths paths{};
     float2 *hits = nullptr;
     DevShadow sh[2]{};                                 // shadow records, double-buffered by bounce parity (overlap)
@@ -80,26 +105,16 @@ struct ptmi_ctx {
 
     // output (binding 0)
     uint32_t W = 0, H = 0;
-    float4 *d_out_own = nullptr, *d_out = nullptr;
-    // first-hit planes (ptmi_set_aovs): W x H each, present while their bit is set and the output buffer exists
-    uint32_t aov_mask = 0;
-    float4 *d_aov_albedo = nullptr, *d_aov_normal = nullptr;
-    uint2 *d_aov_id = nullptr;
-    // sample-moments plane (ptmi_set_moments): W x H float4, present while on and the output buffer exists
-    bool moments_on = false;
-    float4 *d_moments = nullptr;
-    // adaptive sampling (ptmi_dispatch_adaptive): ballot words, pixel list and tile totals sized for ad_px pixels (made by the first
-    // adaptive dispatch after a resize), control words and counters for the context's life
+    void *plane[kFramePlanes] = {};                    // indexed by FramePlane, W x H pixels each (absent: NULL)
+    float4 *d_out = nullptr;                           // what dispatches write: plane[kOut] or the caller's buffer (ptmi_bind_output_device)
+    uint32_t aov_mask = 0;                             // ptmi_set_aovs: a plane is present while its bit is set and the output buffer exists
+    bool moments_on = false;                           // ptmi_set_moments: likewise
+    // adaptive sampling (ptmi_dispatch_adaptive): ballot, list and tile_sums are views of the planes; the control words and counters
+    // live for the context's life
     DevAdaptive ad{};
-    size_t ad_px = 0;
     uint32_t ad_rounds = 0;                            // rounds since the last restart
-    // the denoiser's planes (ptmi_denoise), W x H each, made by its first call after a resize: guide (unit normal, depth), depth
-    // gradient, two ping-pong colour + variance planes, and the result
-    float4 *d_dn_guide = nullptr, *d_dn_a = nullptr, *d_dn_b = nullptr, *d_dn_out = nullptr;
-    float *d_dn_grad = nullptr;
 
     unsigned long long *d_stats = nullptr;
-    float4 *d_blit_f32 = nullptr; uint32_t *d_blit_u8 = nullptr; size_t blit_px = 0;   // canvas staging of ptmi_blit, kept between calls
 
     // statistics
     ptmi_stats st{};
@@ -130,6 +145,9 @@ int fail(const ptmi_ctx *c, int code, const char *fmt, ...) {
     return fail((c), PTMI_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
 template <class T> void dfree(T *&p) { if (p) { (void)hipFree(p); p = nullptr; } }
+// device scratch of one call (the ptmi_debug_*math entry points), freed on every way out of it
+template <class T> struct Scratch { T *p = nullptr; ~Scratch() { if (p) (void)hipFree(p); } };
+template <class T> void view(T *&p, void *b) { p = static_cast<T *>(b); }      // a typed member that stands for an entry of a buffer table
 
 void default_options(ptmi_options &o) {
     std::memset(&o, 0, sizeof o);
@@ -202,14 +220,45 @@ struct Timed {
     }
 };
 
+// what a path of a batch takes in each of the lane's per-path arrays, in bytes
+constexpr size_t kLaneBytes[kLaneBufs] = {
+    16, 16, 8, 16,                                 // kPathO .. kPathL
+    8,                                             // kHits
+    16 + 16 + sizeof(rgb_sc), 4, 16 + 16 + sizeof(rgb_sc), 4,      // kShadow0, kShadowIdx0, kShadow1, kShadowIdx1
+    16, 16, 8, 4,                                  // kTailO .. kPid
+    4, 4,                                          // kQueue0, kQueue1
+    1,                                             // kOcc
+    32,                                            // kAovRec
+};
+// bytes of device memory a path of a batch takes in ensure_capacity: the per-path arrays and one byte for the two masks (2 x 8 B per 64
+// paths). The automatic batch size and its out-of-memory retry (ptmi_dispatch) rely on it.
+constexpr size_t bytes_per_path(bool aov) {
+    size_t n = 1;
+    for (int k = 0; k < kLaneBufs; k++) if (k != kAovRec || aov) n += kLaneBytes[k];
+    return n;
+}
+static_assert(bytes_per_path(false) == 214 && bytes_per_path(true) == 246, "the automatic frames_per_batch moves with these");
+
+// the typed members that kernels receive, as views of Lane::buf
+void lane_views(Lane &ln) {
+    auto at = [&](int k, auto *&p) { view(p, ln.buf[k]); };
+    at(kPathO, ln.paths.O); at(kPathD, ln.paths.D); at(kPathC, ln.paths.C); at(kPathL, ln.paths.L);
+    at(kHits, ln.hits);
+    for (int k = 0; k < 2; k++) {
+        DevShadow &sh = ln.sh[k];
+        at(k ? kShadow1 : kShadow0, sh.SO); at(k ? kShadowIdx1 : kShadowIdx0, ln.sq[k]); at(k ? kQueue1 : kQueue0, ln.queue[k]);
+        sh.SD = sh.SO ? sh.SO + ln.cap : nullptr; sh.SC = sh.SO ? reinterpret_cast<rgb_sc *>(sh.SO + 2 * ln.cap) : nullptr;
+        sh.cap = (uint32_t)ln.cap;
+    }
+    at(kTailO, ln.tail.O); at(kTailD, ln.tail.D); at(kTailC, ln.tail.C); at(kPid, ln.pid);
+    at(kOcc, ln.d_occ); at(kAovRec, ln.aov);
+}
+
 void free_batch(Lane &ln) {
-    dfree(ln.paths.O); dfree(ln.paths.D); dfree(ln.paths.C); dfree(ln.paths.L);
-    dfree(ln.hits);
-    for (int k = 0; k < 2; k++) { dfree(ln.sh[k].SO); ln.sh[k].SD = nullptr; ln.sh[k].SC = nullptr; dfree(ln.sq[k]); }
-    dfree(ln.tail.O); dfree(ln.tail.D); dfree(ln.tail.C); dfree(ln.pid);
-    dfree(ln.queue[0]); dfree(ln.queue[1]); dfree(ln.alive); dfree(ln.shadowm); dfree(ln.word_off); dfree(ln.d_occ);
-    dfree(ln.aov);
+    for (void *&p : ln.buf) dfree(p);
+    dfree(ln.alive); dfree(ln.shadowm); dfree(ln.word_off);
     ln.cap = 0;
+    lane_views(ln);
 }
 
 // everything the library has in flight, on every stream it owns
@@ -220,45 +269,37 @@ hipError_t sync_all(ptmi_ctx *c) {
     return e;
 }
 
-// bytes of device memory a path of a batch takes in ensure_capacity (state 56 + hit 8 + 2 x (record 44 + index 4) + tail state 40 and
-// path id 4, sized for every path surviving roulette + 2 queues + masks)
-constexpr size_t kBytesPerPath = 16 + 16 + 8 + 16 + 8 + 2 * (16 + 16 + sizeof(rgb_sc) + 4) + (16 + 16 + 8 + 4) + 2 * 4 + 1 + 1;
 #ifndef PT_REPACK
 #define PT_REPACK 1          /* A/B switch: 0 leaves the path state at the path id for every bounce (no tail arrays in use) */
 #endif
-constexpr size_t kAovBytesPerPath = 32;   // ... and, while AOV planes are on, its first-hit record (Lane::aov)
-size_t bytes_per_path(bool aov) { return kBytesPerPath + (aov ? kAovBytesPerPath : 0); }
 
 int ensure_capacity(ptmi_ctx *c, Lane &ln, size_t n) {
     const bool aov = c->aov_mask != 0;
     if (n <= ln.cap && (!aov || ln.aov)) return PTMI_OK;
     HIP_TRY(c, sync_all(c));
     free_batch(ln);
-    size_t cap = (n + 1023) & ~(size_t)1023;
-    size_t words = cap / 64 + 1;
-    size_t tiles = cap / pt_compact_tile_slots() + 2;
+    const size_t cap = (n + 1023) & ~(size_t)1023;
+    const size_t words = cap / 64 + 1;
+    const size_t tiles = cap / pt_compact_tile_slots() + 2;
     c->alloc_oom = false;
-    // a failed allocation leaves the lane empty (not half-built) and the runtime's sticky error cleared; ptmi_dispatch retries
-    // with a smaller batch when it chose the size itself
-#define ALLOC(ptr, bytes) do { hipError_t e_ = hipMalloc(&(ptr), (bytes)); if (e_ != hipSuccess) { \
-        c->alloc_oom = e_ == hipErrorOutOfMemory; free_batch(ln); (void)hipGetLastError(); \
-        return fail(c, PTMI_E_HIP, "hipMalloc of %zu bytes for a batch of %zu paths failed: %s", (size_t)(bytes), cap, hipGetErrorString(e_)); } } while (0)
-    ALLOC(ln.paths.O, cap * 16); ALLOC(ln.paths.D, cap * 16);
-    ALLOC(ln.paths.C, cap * 8); ALLOC(ln.paths.L, cap * 16);      // room for either stride
-    ALLOC(ln.hits, cap * 8);
-    for (int k = 0; k < 2; k++) {
-        ALLOC(ln.sh[k].SO, cap * (16 + 16 + sizeof(rgb_sc)));
-        ln.sh[k].SD = ln.sh[k].SO + cap; ln.sh[k].SC = reinterpret_cast<rgb_sc *>(ln.sh[k].SO + 2 * cap); ln.sh[k].cap = (uint32_t)cap;
-        ALLOC(ln.sq[k], cap * 4);
+    hipError_t e = hipSuccess;
+    size_t bytes = 0;
+    for (int k = 0; k < kLaneBufs && e == hipSuccess; k++)
+        if (k != kAovRec || aov) e = hipMalloc(&ln.buf[k], bytes = cap * kLaneBytes[k]);
+    if (e == hipSuccess) e = hipMalloc(&ln.alive, bytes = words * 8);
+    if (e == hipSuccess) e = hipMalloc(&ln.shadowm, bytes = words * 8);
+    if (e == hipSuccess) e = hipMalloc(&ln.word_off, bytes = 2 * tiles * 4);
+    if (e != hipSuccess) {
+        // a failed allocation leaves the lane empty (not half-built) and the runtime's sticky error cleared; ptmi_dispatch retries
+        // with a smaller batch when it chose the size itself
+        c->alloc_oom = e == hipErrorOutOfMemory;
+        free_batch(ln);
+        (void)hipGetLastError();
+        return fail(c, PTMI_E_HIP, "hipMalloc of %zu bytes for a batch of %zu paths failed: %s", bytes, cap, hipGetErrorString(e));
     }
-    ALLOC(ln.tail.O, cap * 16); ALLOC(ln.tail.D, cap * 16); ALLOC(ln.tail.C, cap * 8); ALLOC(ln.pid, cap * 4);
-    ALLOC(ln.queue[0], cap * 4); ALLOC(ln.queue[1], cap * 4);
-    ALLOC(ln.alive, words * 8); ALLOC(ln.shadowm, words * 8); ln.mask_words = words;
-    ALLOC(ln.word_off, 2 * tiles * 4);
-    ALLOC(ln.d_occ, cap);
-    if (aov) ALLOC(ln.aov, cap * kAovBytesPerPath);
-#undef ALLOC
+    ln.mask_words = words;
     ln.cap = cap;
+    lane_views(ln);
     return PTMI_OK;
 }
 
@@ -667,68 +708,87 @@ bool walks_memory_quantised(const TraverseConfig &cfg) {
 }
 
 constexpr uint32_t kAovAll = PTMI_AOV_ALBEDO | PTMI_AOV_NORMAL | PTMI_AOV_ID;
-size_t aov_elem_bytes(uint32_t which) { return which == PTMI_AOV_ID ? 8 : 16; }
-void **aov_plane(ptmi_ctx *c, uint32_t which) {
-    switch (which) {
-    case PTMI_AOV_ALBEDO: return reinterpret_cast<void **>(&c->d_aov_albedo);
-    case PTMI_AOV_NORMAL: return reinterpret_cast<void **>(&c->d_aov_normal);
-    case PTMI_AOV_ID: return reinterpret_cast<void **>(&c->d_aov_id);
-    default: return nullptr;
-    }
+
+// One row per FramePlane: its size for px pixels, whether it is zero-filled when made, and when it is made: with the frame (ptmi_resize
+// and the call that turns it on), or by the first call that needs it since the last resize.
+enum PlaneGroup { kWithFrame, kByDenoise, kByAdaptive, kByBlit };
+template <size_t K> size_t per_pixel(size_t px) { return px * K; }
+size_t ballot_bytes(size_t px) { return (px / 64 + 1) * 8; }
+size_t tile_sum_bytes(size_t px) { return (size_t)pt_adaptive_tiles((uint32_t)px) * 4; }
+const struct { const char *name; size_t (*bytes)(size_t px); bool zeroed; PlaneGroup group; } kFrame[kFramePlanes] = {
+    {"output", per_pixel<PTMI_OUTPUT_STRIDE>, true, kWithFrame},
+    {"albedo", per_pixel<16>, true, kWithFrame}, {"normal", per_pixel<16>, true, kWithFrame}, {"id", per_pixel<8>, true, kWithFrame},
+    {"moments", per_pixel<16>, true, kWithFrame},
+    {"denoiser guide", per_pixel<16>, false, kByDenoise}, {"denoiser gradient", per_pixel<4>, false, kByDenoise},
+    {"denoiser ping", per_pixel<16>, false, kByDenoise}, {"denoiser pong", per_pixel<16>, false, kByDenoise},
+    {"denoised", per_pixel<16>, false, kByDenoise},
+    {"adaptive ballot", ballot_bytes, false, kByAdaptive}, {"adaptive list", per_pixel<4>, false, kByAdaptive},
+    {"adaptive tile sums", tile_sum_bytes, false, kByAdaptive},
+    {"float canvas", per_pixel<16>, false, kByBlit}, {"8-bit canvas", per_pixel<4>, false, kByBlit},
+};
+// sets of planes: a bit per FramePlane
+constexpr uint32_t kAllPlanes = (1u << kFramePlanes) - 1u;
+constexpr uint32_t bit(FramePlane k) { return 1u << k; }
+static_assert(PTMI_AOV_ALBEDO << kAovAlbedo == bit(kAovAlbedo) && PTMI_AOV_NORMAL << kAovAlbedo == bit(kAovNormal) &&
+              PTMI_AOV_ID << kAovAlbedo == bit(kAovId), "an AOV mask, shifted, is its set of planes");
+uint32_t group_set(PlaneGroup g) {
+    uint32_t set = 0;
+    for (int k = 0; k < kFramePlanes; k++) if (kFrame[k].group == g) set |= 1u << k;
+    return set;
+}
+// the planes that exist whenever the output buffer does: the output, the AOV planes of the mask, the moments plane while on
+uint32_t frame_set(const ptmi_ctx *c) { return bit(kOut) | c->aov_mask << kAovAlbedo | (c->moments_on ? bit(kMoments) : 0u); }
+// which: one PTMI_AOV_* bit (else kFramePlanes)
+FramePlane aov_plane_of(uint32_t which) {
+    return which == PTMI_AOV_ALBEDO ? kAovAlbedo : which == PTMI_AOV_NORMAL ? kAovNormal : which == PTMI_AOV_ID ? kAovId : kFramePlanes;
+}
+template <class T> T *plane_as(const ptmi_ctx *c, FramePlane k) { return static_cast<T *>(c->plane[k]); }
+void view_planes(ptmi_ctx *c) {
+    view(c->ad.ballot, c->plane[kAdBallot]); view(c->ad.list, c->plane[kAdList]); view(c->ad.tile_sums, c->plane[kAdTileSums]);
 }
 
-// Makes the planes of `mask` exist at the output buffer's size and frees the others. New planes are zero-filled; with `fresh` (a resize)
-// every plane is. Everything is allocated before anything is freed: a failed call leaves the planes as they were.
-int alloc_aov_planes(ptmi_ctx *c, uint32_t mask, bool fresh) {
-    const size_t npix = (size_t)c->W * c->H;
-    void *n[3] = {};
-    const uint32_t bits[3] = {PTMI_AOV_ALBEDO, PTMI_AOV_NORMAL, PTMI_AOV_ID};
-    for (int k = 0; k < 3; k++) {
-        if (!(mask & bits[k]) || npix == 0 || (*aov_plane(c, bits[k]) && !fresh)) continue;
-        const size_t bytes = npix * aov_elem_bytes(bits[k]);
+// Makes every plane of `set` that `into` (the context's table, or an empty one for fresh planes) lacks, for px pixels, all or nothing:
+// on failure what was made is freed, the runtime's sticky error cleared, and `into` and the context are as they were. Nothing is freed
+// or overwritten, so nothing in flight is disturbed. Before ptmi_resize (px = 0) there is nothing to make.
+int make_planes(ptmi_ctx *c, uint32_t set, size_t px, void **into) {
+    void *n[kFramePlanes] = {};
+    for (int k = 0; k < kFramePlanes && px; k++) {
+        if (!(set & 1u << k) || into[k]) continue;
+        const size_t bytes = kFrame[k].bytes(px);
         hipError_t e = hipMalloc(&n[k], bytes);
-        if (e == hipSuccess) e = hipMemset(n[k], 0, bytes);
+        if (e == hipSuccess && kFrame[k].zeroed) e = hipMemset(n[k], 0, bytes);
         if (e != hipSuccess) {
             for (void *&p : n) dfree(p);
             (void)hipGetLastError();
-            return fail(c, PTMI_E_HIP, "allocation of a %zu-byte AOV plane failed: %s (the AOV planes are as they were)", bytes,
+            return fail(c, PTMI_E_HIP, "allocation of the %zu-byte %s plane failed: %s (the planes are as they were)", bytes, kFrame[k].name,
                         hipGetErrorString(e));
         }
     }
-    for (int k = 0; k < 3; k++) {
-        void **p = aov_plane(c, bits[k]);
-        if (n[k]) { dfree(*p); *p = n[k]; }
-        else if (!(mask & bits[k])) dfree(*p);
-    }
+    for (int k = 0; k < kFramePlanes; k++) if (n[k]) into[k] = n[k];
+    view_planes(c);
     return PTMI_OK;
 }
 
-// The sample-moments plane at the output buffer's size, zero-filled; nothing is changed if that fails.
-int alloc_moments(ptmi_ctx *c) {
-    const size_t bytes = (size_t)c->W * c->H * 16;
-    if (bytes == 0) return PTMI_OK;
-    void *p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e == hipSuccess) e = hipMemset(p, 0, bytes);
-    if (e != hipSuccess) {
-        dfree(p);
-        (void)hipGetLastError();
-        return fail(c, PTMI_E_HIP, "allocation of the %zu-byte moments plane failed: %s", bytes, hipGetErrorString(e));
-    }
-    c->d_moments = static_cast<float4 *>(p);
+// Frees the context's planes of `set` (the caller has synchronised where one may be in use).
+void drop_planes(ptmi_ctx *c, uint32_t set) {
+    for (int k = 0; k < kFramePlanes; k++) if (set & 1u << k) dfree(c->plane[k]);
+    view_planes(c);
+}
+
+// Copies a whole plane to the host once everything in flight has finished. src: the plane, or the buffer bound in its place. n: the
+// caller's count of `unit`-byte elements (4: floats, 1: bytes), which must be the plane's.
+int read_plane(ptmi_ctx *c, FramePlane k, const void *src, void *dst, size_t n, size_t unit) {
+    const size_t bytes = kFrame[k].bytes((size_t)c->W * c->H);
+    if (n * unit != bytes) return fail(c, PTMI_E_INVALID, "expected %zu %s, got %zu", bytes / unit, unit == 4 ? "floats" : "bytes", n);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, sync_all(c));
+    drain_events(c);
+    HIP_TRY(c, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
     return PTMI_OK;
 }
 
-void free_denoise(ptmi_ctx *c) {
-    dfree(c->d_dn_guide); dfree(c->d_dn_grad); dfree(c->d_dn_a); dfree(c->d_dn_b); dfree(c->d_dn_out);
-}
-
-void free_adaptive_planes(ptmi_ctx *c) {
-    dfree(c->ad.ballot); dfree(c->ad.list); dfree(c->ad.tile_sums);
-    c->ad_px = 0;
-}
-// the control words live for the context's life (ptmi_get_stats reads acc[0]) ...
-int ensure_adaptive_words(ptmi_ctx *c) {
+// the control words live for the context's life (ptmi_get_stats reads acc[0]); the planes follow the output buffer's size
+int adaptive_words(ptmi_ctx *c) {
     if (!c->ad.ctl) {
         HIP_TRY(c, hipMalloc(&c->ad.ctl, 4 * sizeof(uint32_t)));
         HIP_TRY(c, hipMemset(c->ad.ctl, 0, 4 * sizeof(uint32_t)));
@@ -737,20 +797,6 @@ int ensure_adaptive_words(ptmi_ctx *c) {
         HIP_TRY(c, hipMalloc(&c->ad.acc, 4 * sizeof(unsigned long long)));
         HIP_TRY(c, hipMemset(c->ad.acc, 0, 4 * sizeof(unsigned long long)));
     }
-    return PTMI_OK;
-}
-// ... the planes follow the output buffer's size and are made by the first adaptive dispatch that needs them
-int ensure_adaptive(ptmi_ctx *c) {
-    const int rc = ensure_adaptive_words(c);
-    if (rc) return rc;
-    const size_t px = (size_t)c->W * c->H;
-    if (c->ad_px == px && c->ad.list) return PTMI_OK;
-    HIP_TRY(c, sync_all(c));
-    free_adaptive_planes(c);
-    HIP_TRY(c, hipMalloc(&c->ad.ballot, (px / 64 + 1) * 8));
-    HIP_TRY(c, hipMalloc(&c->ad.list, px * 4));
-    HIP_TRY(c, hipMalloc(&c->ad.tile_sums, (size_t)pt_adaptive_tiles((uint32_t)px) * 4));
-    c->ad_px = px;
     return PTMI_OK;
 }
 // a fresh moments plane (ptmi_resize, ptmi_set_moments): no round has listed anything in it
@@ -877,9 +923,8 @@ int ptmi_destroy(ptmi_ctx *c) {
     }
     for (void *&p : c->buf) dfree(p);
     dfree(c->d_atlas);
-    dfree(c->d_out_own); dfree(c->d_aov_albedo); dfree(c->d_aov_normal); dfree(c->d_aov_id); dfree(c->d_stats); dfree(c->d_scene); dfree(c->d_blit_f32); dfree(c->d_blit_u8);
-    dfree(c->d_moments); free_denoise(c);
-    free_adaptive_planes(c); dfree(c->ad.ctl); dfree(c->ad.acc);
+    drop_planes(c, kAllPlanes);
+    dfree(c->d_stats); dfree(c->d_scene); dfree(c->ad.ctl); dfree(c->ad.acc);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
     return PTMI_OK;
@@ -1058,23 +1103,25 @@ int ptmi_upload_atlas(ptmi_ctx *c, const void *texels, uint32_t w, uint32_t h, i
     return PTMI_OK;
 }
 
+// The planes of the new size are made before anything of the old size goes, so a failed call leaves the context as it was; for the
+// length of the call both exist, at most 72 B per pixel of the new size (output, three AOV planes, moments), small beside a batch.
 int ptmi_resize(ptmi_ctx *c, uint32_t w, uint32_t h) {
     if (!c) return PTMI_E_INVALID;
     if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 28)) return fail(c, PTMI_E_INVALID, "bad size %ux%u", w, h);
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, sync_all(c));
-    dfree(c->d_out_own);
-    size_t bytes = (size_t)w * h * PTMI_OUTPUT_STRIDE;
-    HIP_TRY(c, hipMalloc(&c->d_out_own, bytes));
-    HIP_TRY(c, hipMemset(c->d_out_own, 0, bytes));
-    c->d_out = c->d_out_own; c->W = w; c->H = h;
-    free_denoise(c);
-    free_adaptive_planes(c);
-    if (int rc_ = reset_adaptive_rounds(c)) return rc_;
-    dfree(c->d_moments);                         // never left at the old size
-    int rc = alloc_aov_planes(c, c->aov_mask, true);
-    if (rc == PTMI_OK && c->moments_on) rc = alloc_moments(c);
-    return rc;
+    void *fresh[kFramePlanes] = {};
+    const int rc = make_planes(c, frame_set(c), (size_t)w * h, fresh);
+    if (rc) return rc;
+    const hipError_t e = sync_all(c);                 // nothing in flight uses the old planes any more
+    if (e != hipSuccess) {
+        for (void *&p : fresh) dfree(p);
+        return fail(c, PTMI_E_HIP, "sync_all failed: %s", hipGetErrorString(e));
+    }
+    drop_planes(c, kAllPlanes);                       // the denoiser's, the adaptive and the blit planes come back at their first use
+    std::copy(fresh, fresh + kFramePlanes, c->plane);
+    c->W = w; c->H = h;
+    c->d_out = plane_as<float4>(c, kOut);
+    return reset_adaptive_rounds(c);
 }
 
 int ptmi_set_options(ptmi_ctx *c, const ptmi_options *o) {
@@ -1115,7 +1162,7 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         return fail(c, PTMI_E_INVALID, "camera says %ux%u but the output buffer is %ux%u", cam->width, cam->height, c->W, c->H);
     if (n_frames == 0 || (ap && rounds == 0)) return PTMI_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (ap && (rc = ensure_adaptive(c))) return rc;
+    if (ap && ((rc = adaptive_words(c)) || (rc = make_planes(c, group_set(kByAdaptive), (size_t)c->W * c->H, c->plane)))) return rc;
     const DevBand band = pt_band_of(c->opt, c->W, c->H);
     if (band.y0 >= band.y1) return fail(c, PTMI_E_INVALID, "tile rows [%u,%u) outside the %u-row frame", band.y0, band.y1, c->H);
     if (band.rows == 0) return PTMI_OK;                         // more parts than strips: nothing to render here
@@ -1190,10 +1237,11 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         DevPaths tp = ln.tail;
         tp.L = bp.L; tp.l_stride = bp.l_stride;
         float4 *const aov_rec = c->aov_mask ? ln.aov : nullptr;         // written by shade(0), read by the fold after the last bounce
-        if (ap && cam->frame_index == 0u) { pt_launch_adaptive_restart(ms, blocks, band, c->d_moments); c->ad_rounds = 0; }
+        float4 *const mom = plane_as<float4>(c, kMoments);
+        if (ap && cam->frame_index == 0u) { pt_launch_adaptive_restart(ms, blocks, band, mom); c->ad_rounds = 0; }
         // a batch: fb frames of every pixel from frame0 on, or (ap) of every listed pixel from its own count on
         auto batch = [&](uint32_t frame0, uint32_t fb) -> int {
-            const DevPixels px = ap ? DevPixels{band, 0u, c->ad.list, &c->ad.ctl[1], c->d_moments, c->ad.acc}
+            const DevPixels px = ap ? DevPixels{band, 0u, c->ad.list, &c->ad.ctl[1], mom, c->ad.acc}
                                     : DevPixels{band, frame0, nullptr, nullptr, nullptr, nullptr};
             { Timed t(c, 4, t3, ms); pt_launch_raygen(ms, blocks, *cam, px, fb, bp, &ln.counts[0]); }
             int cur = 0;
@@ -1236,16 +1284,16 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
             Timed t(c, 6, t3, ms);
             pt_launch_accumulate(ms, blocks, px, fb, bp.L, bp.l_stride, c->d_out);
             if (aov_rec)
-                pt_launch_accumulate_aov(ms, blocks, px, fb, aov_rec, c->sc.tris, c->sc.n_tris, c->d_aov_albedo, c->d_aov_normal,
-                                         c->d_aov_id);
+                pt_launch_accumulate_aov(ms, blocks, px, fb, aov_rec, c->sc.tris, c->sc.n_tris, plane_as<float4>(c, kAovAlbedo),
+                                         plane_as<float4>(c, kAovNormal), plane_as<uint2>(c, kAovId));
             // the moments fold goes last: it moves mom.z on, where the other two read the listed pixels' counts. An adaptive dispatch
             // always has the plane (it is refused without); a plain one folds it only while it is on.
-            if (ap || c->d_moments) pt_launch_accumulate_moments(ms, blocks, px, fb, bp.L, bp.l_stride, c->d_moments);
+            if (ap || mom) pt_launch_accumulate_moments(ms, blocks, px, fb, bp.L, bp.l_stride, mom);
             return PTMI_OK;
         };
         if (ap) {
             for (uint32_t r = 0; r < rounds; r++) {
-                pt_launch_adaptive_list(ms, blocks, band, *ap, c->d_moments, c->ad);
+                pt_launch_adaptive_list(ms, blocks, band, *ap, mom, c->ad);
                 for (uint32_t f0 = 0; f0 < n_frames; f0 += F)
                     if ((rc = batch(0u, std::min(F, n_frames - f0)))) return rc;
             }
@@ -1290,16 +1338,16 @@ int ptmi_dispatch_adaptive(ptmi_ctx *c, const ptmi_camera *cam, const ptmi_adapt
     if (ap.step > (1u << 16)) return fail(c, PTMI_E_INVALID, "step %u above 2^16", ap.step);
     int rc = check_ready(c, true);
     if (rc) return rc;
-    if (!c->moments_on || !c->d_moments) return fail(c, PTMI_E_STATE, "adaptive sampling needs the moments plane (ptmi_set_moments)");
+    if (!c->moments_on || !c->plane[kMoments]) return fail(c, PTMI_E_STATE, "adaptive sampling needs the moments plane (ptmi_set_moments)");
     return dispatch(c, cam, ap.step, &ap, rounds);
 }
 
 int ptmi_adaptive_status(ptmi_ctx *c, struct ptmi_adaptive_status *out) {
     if (!c || !out) return PTMI_E_INVALID;
     if (!c->moments_on) return fail(c, PTMI_E_STATE, "the moments plane is off (ptmi_set_moments)");
-    if (!c->d_moments) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
+    if (!c->plane[kMoments]) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = ensure_adaptive_words(c);
+    int rc = adaptive_words(c);
     if (rc) return rc;
     std::memset(out, 0, sizeof *out);
     const DevBand band = pt_band_of(c->opt, c->W, c->H);
@@ -1310,7 +1358,7 @@ int ptmi_adaptive_status(ptmi_ctx *c, struct ptmi_adaptive_status *out) {
     drain_events(c);
     if (band.y0 < band.y1 && band.rows) {
         HIP_TRY(c, hipMemcpyAsync(&c->ad.acc[1], preset, sizeof preset, hipMemcpyHostToDevice, c->stream));
-        pt_launch_adaptive_status(c->stream, c->n_cu * 8, band, c->d_moments, c->ad);
+        pt_launch_adaptive_status(c->stream, c->n_cu * 8, band, plane_as<float4>(c, kMoments), c->ad);
         HIP_TRY(c, hipMemcpyAsync(acc, &c->ad.acc[1], sizeof acc, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(c, hipMemcpyAsync(ctl, c->ad.ctl, sizeof ctl, hipMemcpyDeviceToHost, c->stream));
@@ -1343,12 +1391,7 @@ int ptmi_synchronize(ptmi_ctx *c) {
 int ptmi_read_output(ptmi_ctx *c, float *dst, size_t n_floats) {
     if (!c || !dst) return PTMI_E_INVALID;
     if (!c->d_out) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
-    if (n_floats != (size_t)c->W * c->H * 4) return fail(c, PTMI_E_INVALID, "expected %zu floats, got %zu", (size_t)c->W * c->H * 4, n_floats);
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, sync_all(c));
-    drain_events(c);
-    HIP_TRY(c, hipMemcpy(dst, c->d_out, n_floats * 4, hipMemcpyDeviceToHost));
-    return PTMI_OK;
+    return read_plane(c, kOut, c->d_out, dst, n_floats, 4);
 }
 
 int ptmi_write_output(ptmi_ctx *c, const float *src, size_t n_floats) {
@@ -1366,7 +1409,7 @@ void *ptmi_output_device_ptr(ptmi_ctx *c) { return c ? c->d_out : nullptr; }
 int ptmi_bind_output_device(ptmi_ctx *c, void *p, size_t bytes) {
     if (!c) return PTMI_E_INVALID;
     if (c->W == 0) return fail(c, PTMI_E_STATE, "call ptmi_resize first");
-    if (!p) { c->d_out = c->d_out_own; return PTMI_OK; }
+    if (!p) { c->d_out = plane_as<float4>(c, kOut); return PTMI_OK; }
     if (bytes < (size_t)c->W * c->H * PTMI_OUTPUT_STRIDE) return fail(c, PTMI_E_INVALID, "buffer of %zu bytes is too small", bytes);
     if (reinterpret_cast<uintptr_t>(p) & 15u) return fail(c, PTMI_E_INVALID, "buffer must be 16-byte aligned");
     c->d_out = static_cast<float4 *>(p);
@@ -1382,25 +1425,19 @@ int ptmi_set_stream(ptmi_ctx *c, void *s) {
 }
 
 namespace {
-// ptmi_blit's contract for any W x H float4 plane of the context
-int blit_plane(ptmi_ctx *c, const float4 *src, float *dst_f32, size_t n_floats, uint8_t *dst_rgba8, size_t n_bytes) {
+// ptmi_blit's contract for any W x H float4 plane of the context; the staging planes are kept between calls
+int blit_from(ptmi_ctx *c, const float4 *src, float *dst_f32, size_t n_floats, uint8_t *dst_rgba8, size_t n_bytes) {
     if (!dst_f32 && !dst_rgba8) return PTMI_OK;
     const size_t n = (size_t)c->W * c->H;
     if (dst_f32 && n_floats != n * 4) return fail(c, PTMI_E_INVALID, "float canvas: expected %zu floats, got %zu", n * 4, n_floats);
     if (dst_rgba8 && n_bytes != n * 4) return fail(c, PTMI_E_INVALID, "8-bit canvas: expected %zu bytes, got %zu", n * 4, n_bytes);
     HIP_TRY(c, hipSetDevice(c->device));
-    if (c->blit_px != n) {                                       // staging buffers live in the context (one pair per size)
-        HIP_TRY(c, sync_all(c));
-        dfree(c->d_blit_f32); dfree(c->d_blit_u8); c->blit_px = 0;
-    }
-    if (dst_f32 && !c->d_blit_f32) HIP_TRY(c, hipMalloc(&c->d_blit_f32, n * 16));
-    if (dst_rgba8 && !c->d_blit_u8) HIP_TRY(c, hipMalloc(&c->d_blit_u8, n * 4));
-    c->blit_px = n;
-    pt_launch_blit(c->stream, c->n_cu * 8, c->W, c->H, src, dst_f32 ? c->d_blit_f32 : nullptr, dst_rgba8 ? c->d_blit_u8 : nullptr);
-    HIP_TRY(c, sync_all(c));
-    drain_events(c);
-    if (dst_f32) HIP_TRY(c, hipMemcpy(dst_f32, c->d_blit_f32, n * 16, hipMemcpyDeviceToHost));
-    if (dst_rgba8) HIP_TRY(c, hipMemcpy(dst_rgba8, c->d_blit_u8, n * 4, hipMemcpyDeviceToHost));
+    int rc = make_planes(c, (dst_f32 ? bit(kBlitF32) : 0u) | (dst_rgba8 ? bit(kBlitU8) : 0u), n, c->plane);
+    if (rc) return rc;
+    pt_launch_blit(c->stream, c->n_cu * 8, c->W, c->H, src, dst_f32 ? plane_as<float4>(c, kBlitF32) : nullptr,
+                   dst_rgba8 ? plane_as<uint32_t>(c, kBlitU8) : nullptr);
+    if (dst_f32 && (rc = read_plane(c, kBlitF32, c->plane[kBlitF32], dst_f32, n_floats, 4))) return rc;
+    if (dst_rgba8 && (rc = read_plane(c, kBlitU8, c->plane[kBlitU8], dst_rgba8, n_bytes, 1))) return rc;
     return PTMI_OK;
 }
 }  // namespace
@@ -1408,7 +1445,7 @@ int blit_plane(ptmi_ctx *c, const float4 *src, float *dst_f32, size_t n_floats, 
 int ptmi_blit(ptmi_ctx *c, float *dst_f32, size_t n_floats, uint8_t *dst_rgba8, size_t n_bytes) {
     if (!c) return PTMI_E_INVALID;
     if (!c->d_out) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
-    return blit_plane(c, c->d_out, dst_f32, n_floats, dst_rgba8, n_bytes);
+    return blit_from(c, c->d_out, dst_f32, n_floats, dst_rgba8, n_bytes);
 }
 
 int ptmi_get_size(const ptmi_ctx *c, uint32_t *w, uint32_t *h) {
@@ -1422,10 +1459,11 @@ int ptmi_set_aovs(ptmi_ctx *c, uint32_t mask) {
     if (mask & ~kAovAll) return fail(c, PTMI_E_INVALID, "unknown AOV bits 0x%x", mask & ~kAovAll);
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, sync_all(c));                     // nothing in flight writes a plane or a record that goes
-    const int rc = alloc_aov_planes(c, mask, false);
+    const int rc = make_planes(c, mask << kAovAlbedo, (size_t)c->W * c->H, c->plane);    // planes already on keep their contents
     if (rc) return rc;
+    drop_planes(c, (kAovAll & ~mask) << kAovAlbedo);
     c->aov_mask = mask;
-    if (!mask) dfree(c->lane.aov);               // the records live only while a plane is on (ensure_capacity makes them)
+    if (!mask) { dfree(c->lane.buf[kAovRec]); lane_views(c->lane); }      // the records live only while a plane is on (ensure_capacity makes them)
     return PTMI_OK;
 }
 
@@ -1437,24 +1475,18 @@ int ptmi_get_aovs(const ptmi_ctx *c, uint32_t *mask) {
 
 int ptmi_read_aov(ptmi_ctx *c, uint32_t which, void *dst, size_t n_bytes) {
     if (!c) return PTMI_E_INVALID;
-    void **plane = aov_plane(c, which);
-    if (!plane) return fail(c, PTMI_E_INVALID, "which = 0x%x is not one PTMI_AOV_* plane", which);
+    const FramePlane k = aov_plane_of(which);
+    if (k == kFramePlanes) return fail(c, PTMI_E_INVALID, "which = 0x%x is not one PTMI_AOV_* plane", which);
     if (!dst) return fail(c, PTMI_E_INVALID, "dst is NULL");
     if (!(c->aov_mask & which)) return fail(c, PTMI_E_STATE, "AOV plane 0x%x is off (ptmi_set_aovs)", which);
-    if (!*plane) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
-    const size_t bytes = (size_t)c->W * c->H * aov_elem_bytes(which);
-    if (n_bytes != bytes) return fail(c, PTMI_E_INVALID, "expected %zu bytes, got %zu", bytes, n_bytes);
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, sync_all(c));
-    drain_events(c);
-    HIP_TRY(c, hipMemcpy(dst, *plane, bytes, hipMemcpyDeviceToHost));
-    return PTMI_OK;
+    if (!c->plane[k]) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
+    return read_plane(c, k, c->plane[k], dst, n_bytes, 1);
 }
 
 void *ptmi_aov_device_ptr(ptmi_ctx *c, uint32_t which) {
     if (!c) return nullptr;
-    void **plane = aov_plane(c, which);
-    return plane && (c->aov_mask & which) ? *plane : nullptr;
+    const FramePlane k = aov_plane_of(which);
+    return k != kFramePlanes && (c->aov_mask & which) ? c->plane[k] : nullptr;
 }
 
 int ptmi_set_moments(ptmi_ctx *c, uint32_t on) {
@@ -1462,11 +1494,10 @@ int ptmi_set_moments(ptmi_ctx *c, uint32_t on) {
     if (on > 1u) return fail(c, PTMI_E_INVALID, "on = %u is not 0 or 1", on);
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, sync_all(c));                     // nothing in flight writes a plane that goes
-    if (on && !c->d_moments) {
-        const int rc = alloc_moments(c);
+    if (on) {
+        const int rc = make_planes(c, bit(kMoments), (size_t)c->W * c->H, c->plane);
         if (rc) return rc;
-    }
-    if (!on) dfree(c->d_moments);
+    } else drop_planes(c, bit(kMoments));
     if ((on != 0) != c->moments_on) { const int rc = reset_adaptive_rounds(c); if (rc) return rc; }
     c->moments_on = on != 0;
     return PTMI_OK;
@@ -1482,17 +1513,11 @@ int ptmi_read_moments(ptmi_ctx *c, float *dst, size_t n_floats) {
     if (!c) return PTMI_E_INVALID;
     if (!dst) return fail(c, PTMI_E_INVALID, "dst is NULL");
     if (!c->moments_on) return fail(c, PTMI_E_STATE, "the moments plane is off (ptmi_set_moments)");
-    if (!c->d_moments) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
-    const size_t n = (size_t)c->W * c->H * 4;
-    if (n_floats != n) return fail(c, PTMI_E_INVALID, "expected %zu floats, got %zu", n, n_floats);
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, sync_all(c));
-    drain_events(c);
-    HIP_TRY(c, hipMemcpy(dst, c->d_moments, n * 4, hipMemcpyDeviceToHost));
-    return PTMI_OK;
+    if (!c->plane[kMoments]) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
+    return read_plane(c, kMoments, c->plane[kMoments], dst, n_floats, 4);
 }
 
-void *ptmi_moments_device_ptr(ptmi_ctx *c) { return c && c->moments_on ? c->d_moments : nullptr; }
+void *ptmi_moments_device_ptr(ptmi_ctx *c) { return c && c->moments_on ? c->plane[kMoments] : nullptr; }
 
 int ptmi_denoise(ptmi_ctx *c, const ptmi_denoise_params *p, float *dst_rgba, size_t n_floats) {
     if (!c) return PTMI_E_INVALID;
@@ -1507,50 +1532,34 @@ int ptmi_denoise(ptmi_ctx *c, const ptmi_denoise_params *p, float *dst_rgba, siz
     if (!c->d_out) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
     const size_t npix = (size_t)c->W * c->H;
     if (dst_rgba && n_floats != npix * 4) return fail(c, PTMI_E_INVALID, "expected %zu floats, got %zu", npix * 4, n_floats);
-    if (!(c->aov_mask & PTMI_AOV_NORMAL) || !c->d_aov_normal)
+    if (!(c->aov_mask & PTMI_AOV_NORMAL) || !c->plane[kAovNormal])
         return fail(c, PTMI_E_STATE, "the denoiser needs the NORMAL plane (ptmi_set_aovs)");
-    if (!c->d_moments) return fail(c, PTMI_E_STATE, "the denoiser needs the moments plane (ptmi_set_moments)");
-    const bool have_albedo = (c->aov_mask & PTMI_AOV_ALBEDO) && c->d_aov_albedo;
+    if (!c->plane[kMoments]) return fail(c, PTMI_E_STATE, "the denoiser needs the moments plane (ptmi_set_moments)");
+    const bool have_albedo = (c->aov_mask & PTMI_AOV_ALBEDO) && c->plane[kAovAlbedo];
     if (q.demodulate == 2u && !have_albedo) return fail(c, PTMI_E_STATE, "demodulate = 2 needs the ALBEDO plane (ptmi_set_aovs)");
     const bool demod = q.demodulate == 2u || (q.demodulate == 0u && have_albedo);
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->d_dn_out) {                          // all five or none
-        float4 *g = nullptr, *a = nullptr, *b = nullptr, *o = nullptr;
-        float *gr = nullptr;
-        hipError_t e = hipMalloc(&g, npix * 16);
-        if (e == hipSuccess) e = hipMalloc(&gr, npix * 4);
-        if (e == hipSuccess) e = hipMalloc(&a, npix * 16);
-        if (e == hipSuccess) e = hipMalloc(&b, npix * 16);
-        if (e == hipSuccess) e = hipMalloc(&o, npix * 16);
-        if (e != hipSuccess) {
-            dfree(g); dfree(gr); dfree(a); dfree(b); dfree(o);
-            (void)hipGetLastError();
-            return fail(c, PTMI_E_HIP, "allocation of the denoiser's planes (%zu bytes) failed: %s", npix * 68, hipGetErrorString(e));
-        }
-        c->d_dn_guide = g; c->d_dn_grad = gr; c->d_dn_a = a; c->d_dn_b = b; c->d_dn_out = o;
-    }
+    const int rc = make_planes(c, group_set(kByDenoise), npix, c->plane);
+    if (rc) return rc;
     DenoiseArgs da;
     da.W = c->W; da.H = c->H;
     da.iterations = q.iterations ? q.iterations : 5u;
     da.phi_color = q.phi_color > 0.0f ? q.phi_color : 4.0f;
     da.phi_normal = q.phi_normal > 0.0f ? q.phi_normal : 128.0f;
     da.phi_depth = q.phi_depth > 0.0f ? q.phi_depth : 1.0f;
-    pt_launch_denoise(c->stream, da, c->d_out, c->d_aov_normal, demod ? c->d_aov_albedo : nullptr, c->d_moments, c->d_dn_guide,
-                      c->d_dn_grad, c->d_dn_a, c->d_dn_b, c->d_dn_out);
+    pt_launch_denoise(c->stream, da, c->d_out, plane_as<float4>(c, kAovNormal), demod ? plane_as<float4>(c, kAovAlbedo) : nullptr,
+                      plane_as<float4>(c, kMoments), plane_as<float4>(c, kDnGuide), plane_as<float>(c, kDnGrad), plane_as<float4>(c, kDnA),
+                      plane_as<float4>(c, kDnB), plane_as<float4>(c, kDnOut));
     HIP_TRY(c, hipGetLastError());
-    if (!dst_rgba) return PTMI_OK;
-    HIP_TRY(c, sync_all(c));
-    drain_events(c);
-    HIP_TRY(c, hipMemcpy(dst_rgba, c->d_dn_out, npix * 16, hipMemcpyDeviceToHost));
-    return PTMI_OK;
+    return dst_rgba ? read_plane(c, kDnOut, c->plane[kDnOut], dst_rgba, n_floats, 4) : PTMI_OK;
 }
 
-void *ptmi_denoised_device_ptr(ptmi_ctx *c) { return c ? c->d_dn_out : nullptr; }
+void *ptmi_denoised_device_ptr(ptmi_ctx *c) { return c ? c->plane[kDnOut] : nullptr; }
 
 int ptmi_blit_denoised(ptmi_ctx *c, float *dst_f32, size_t n_floats, uint8_t *dst_rgba8, size_t n_bytes) {
     if (!c) return PTMI_E_INVALID;
-    if (!c->d_dn_out) return fail(c, PTMI_E_STATE, "nothing denoised since the last resize (ptmi_denoise)");
-    return blit_plane(c, c->d_dn_out, dst_f32, n_floats, dst_rgba8, n_bytes);
+    if (!c->plane[kDnOut]) return fail(c, PTMI_E_STATE, "nothing denoised since the last resize (ptmi_denoise)");
+    return blit_from(c, plane_as<float4>(c, kDnOut), dst_f32, n_floats, dst_rgba8, n_bytes);
 }
 
 int ptmi_get_stats(ptmi_ctx *c, ptmi_stats *out) {
@@ -1794,29 +1803,28 @@ int ptmi_debug_math(ptmi_ctx *c, int op, uint32_t n, const float *a, const float
     if (!c || !a || !out) return PTMI_E_INVALID;
     if (n == 0) return PTMI_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    float *da = nullptr, *db = nullptr, *dc = nullptr, *dout = nullptr;
+    Scratch<float> da, db, dc, dout;
     size_t bytes = (size_t)n * 4;
-    HIP_TRY(c, hipMalloc(&da, bytes)); HIP_TRY(c, hipMalloc(&dout, bytes));
-    HIP_TRY(c, hipMemcpy(da, a, bytes, hipMemcpyHostToDevice));
-    if (b) { HIP_TRY(c, hipMalloc(&db, bytes)); HIP_TRY(c, hipMemcpy(db, b, bytes, hipMemcpyHostToDevice)); }
-    if (cc) { HIP_TRY(c, hipMalloc(&dc, bytes)); HIP_TRY(c, hipMemcpy(dc, cc, bytes, hipMemcpyHostToDevice)); }
-    pt_launch_math(c->stream, op, n, da, db, dc, dout);
+    HIP_TRY(c, hipMalloc(&da.p, bytes)); HIP_TRY(c, hipMalloc(&dout.p, bytes));
+    HIP_TRY(c, hipMemcpy(da.p, a, bytes, hipMemcpyHostToDevice));
+    if (b) { HIP_TRY(c, hipMalloc(&db.p, bytes)); HIP_TRY(c, hipMemcpy(db.p, b, bytes, hipMemcpyHostToDevice)); }
+    if (cc) { HIP_TRY(c, hipMalloc(&dc.p, bytes)); HIP_TRY(c, hipMemcpy(dc.p, cc, bytes, hipMemcpyHostToDevice)); }
+    pt_launch_math(c->stream, op, n, da.p, db.p, dc.p, dout.p);
     HIP_TRY(c, sync_all(c));
-    HIP_TRY(c, hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
-    dfree(da); dfree(db); dfree(dc); dfree(dout);
+    HIP_TRY(c, hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
     return PTMI_OK;
 }
 
 int ptmi_debug_exact_math(ptmi_ctx *c, int which, uint64_t *n_different, uint32_t *first_different) {
     if (!c || !n_different || which < 0 || which > 2) return PTMI_E_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
-    unsigned long long *d = nullptr, h[2] = {0ull, ~0ull};
-    HIP_TRY(c, hipMalloc(&d, sizeof h));
-    HIP_TRY(c, hipMemcpy(d, h, sizeof h, hipMemcpyHostToDevice));
-    pt_launch_exact_math(c->stream, which, d);
+    Scratch<unsigned long long> d;
+    unsigned long long h[2] = {0ull, ~0ull};
+    HIP_TRY(c, hipMalloc(&d.p, sizeof h));
+    HIP_TRY(c, hipMemcpy(d.p, h, sizeof h, hipMemcpyHostToDevice));
+    pt_launch_exact_math(c->stream, which, d.p);
     HIP_TRY(c, sync_all(c));
-    HIP_TRY(c, hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost));
-    dfree(d);
+    HIP_TRY(c, hipMemcpy(h, d.p, sizeof h, hipMemcpyDeviceToHost));
     *n_different = h[0];
     if (first_different) *first_different = (uint32_t)h[1];
     return PTMI_OK;
