@@ -233,7 +233,22 @@ typedef struct {
     uint64_t segments, shadow_rays, nodes_visited, tris_tested, closest_hits;
     uint32_t max_stack;
     ray_tap_t *tap;
+    uint64_t *cen;          /* branch census (pto_render_census): cen[event * 64 + bounce], this thread's own; NULL elsewhere */
+    uint32_t b;             /* the bounce being traced, min(bounce, 63) */
 } counters_t;
+
+/* ------------------------------------------------------------------------- */
+/* branch census — pto_census_event in pt_oracle.h                             */
+/* ------------------------------------------------------------------------- */
+#define CEN(c, ev) do { if ((c)->cen) (c)->cen[(ev) * PTO_CENSUS_BOUNCES + (c)->b]++; } while (0)
+/* the range tests of rcp1 / sqrt1 / normalize3 in csrc/pt_math.h: outside them (or NaN) the kernels take the IEEE expansion.
+ * The oracle only classifies the operand; its own arithmetic is the same IEEE operation either way. */
+static inline int out_of_rcp_range(float x) { float a = fabsf(x); return !(a >= 0x1p-100f && a <= 0x1p100f); }
+static inline int out_of_sqrt_range(float x) { return !(x >= 0x1p-100f && x <= 0x1p100f); }
+#define CS_RCP(c, ev, x)  do { if ((c)->cen && out_of_rcp_range(x)) CEN(c, ev); } while (0)
+#define CS_SQRT(c, ev, x) do { if ((c)->cen && out_of_sqrt_range(x)) CEN(c, ev); } while (0)
+#define CS_NORM(c, ev, a) do { if ((c)->cen) { v3 a_ = (a); if (out_of_sqrt_range(dot3(a_, a_))) CEN(c, ev); } } while (0)
+static inline int finite3(v3 a) { return isfinite(a.x) && isfinite(a.y) && isfinite(a.z); }
 
 /* ------------------------------------------------------------------------- */
 /* textures — pt.wgsl:112-120                                                 */
@@ -354,7 +369,7 @@ static void tap_shadow(counters_t *c, float dist) {
 }
 
 /* rayTriangleIntersect, pt.wgsl:159-226, for the winning triangle only */
-static hitinfo_t make_hitinfo(const pto_scene *s, ray_t r, hit_t h) {
+static hitinfo_t make_hitinfo(const pto_scene *s, ray_t r, hit_t h, counters_t *c) {
     hitinfo_t hi;
     memset(&hi, 0, sizeof hi);
     hi.t = h.t;
@@ -365,7 +380,9 @@ static hitinfo_t make_hitinfo(const pto_scene *s, ray_t r, hit_t h) {
     v3 e1 = sub3(ld3(T->v1), v0), e2 = sub3(ld3(T->v2), v0);
     hi.position = madd3(r.d, h.t, r.o);                                      /* :159 */
     float w = 1.0f - u - v;                                                  /* :162 */
+    CS_NORM(c, PTO_CS_GEO_NORMAL, cross3(e1, e2));
     v3 geo_n = normalize3(cross3(e1, e2));                                   /* :165 */
+    CS_NORM(c, PTO_CS_VERTEX_NORMAL, lincomb3(ld3(T->n0), w, ld3(T->n1), u, ld3(T->n2), v));
     v3 n_i = normalize3(lincomb3(ld3(T->n0), w, ld3(T->n1), u, ld3(T->n2), v)); /* :168-172 */
     hi.uvx = fma_(T->uv2[0], v, fma_(T->uv1[0], u, T->uv0[0] * w));          /* :192 */
     hi.uvy = fma_(T->uv2[1], v, fma_(T->uv1[1], u, T->uv0[1] * w));
@@ -373,6 +390,7 @@ static hitinfo_t make_hitinfo(const pto_scene *s, ray_t r, hit_t h) {
     hi.is_front = dot3(geo_n, r.d) < 0.0f;                                   /* :196 */
     ptmi_material zero_m; memset(&zero_m, 0, sizeof zero_m);
     const ptmi_material *m = hi.material_index < s->n_mats ? &s->mats[hi.material_index] : &zero_m; /* :200 */
+    if (m == &zero_m) CEN(c, PTO_EV_MATERIAL_OUT_OF_RANGE);
     v4 one = { 1.0f, 1.0f, 1.0f, 1.0f };
     v4 alb = texture_color(s, &m->albedo_map, hi.uvx, hi.uvy, one);          /* :203 */
     hi.albedo = V3(alb.x * m->base_color[0], alb.y * m->base_color[1], alb.z * m->base_color[2]);
@@ -380,7 +398,9 @@ static hitinfo_t make_hitinfo(const pto_scene *s, ray_t r, hit_t h) {
     v4 pbr = texture_color(s, &m->pbr_map, hi.uvx, hi.uvy, one);             /* :206 */
     hi.metallic = pbr.z * m->metallic;                                       /* :207 */
     hi.roughness = max1(pbr.y * m->roughness, 0.04f);                        /* :208 */
+    if (!(pbr.y * m->roughness >= 0.04f)) CEN(c, PTO_EV_ROUGHNESS_CLAMPED);
     hi.transmission = m->transmission;
+    if (hi.transmission > 0.0f && hi.transmission < 1.0f) CEN(c, PTO_EV_TRANSMISSION_FRACTIONAL);
     hi.ior = m->ior;
     v4 em = texture_color(s, &m->emissive_map, hi.uvx, hi.uvy, one);         /* :211 */
     hi.emission = V3(em.x * m->emission[0], em.y * m->emission[1], em.z * m->emission[2]);
@@ -391,26 +411,34 @@ static hitinfo_t make_hitinfo(const pto_scene *s, ray_t r, hit_t h) {
         /* tangent frame, :176-189 (the bitangent of :183 is never used) */
         float du1x = T->uv1[0] - T->uv0[0], du1y = T->uv1[1] - T->uv0[1];
         float du2x = T->uv2[0] - T->uv0[0], du2y = T->uv2[1] - T->uv0[1];
+        CEN(c, PTO_EV_NORMAL_MAP);
+        if (fma_(du1x, du2y, -(du1y * du2x)) == 0.0f) CEN(c, PTO_EV_NORMAL_MAP_ZERO_DET);
+        CS_RCP(c, PTO_CS_UV_DET, fma_(du1x, du2y, -(du1y * du2x)));
         float rr = 1.0f / fma_(du1x, du2y, -(du1y * du2x));                  /* :181 */
         v3 tg = V3(fma_(e1.x, du2y, -(e2.x * du1y)) * rr,
                    fma_(e1.y, du2y, -(e2.y * du1y)) * rr,
                    fma_(e1.z, du2y, -(e2.z * du1y)) * rr);
+        CS_NORM(c, PTO_CS_TANGENT, tg);
         tg = normalize3(tg);                                                 /* :182 */
         v3 N = n_i;
+        CS_NORM(c, PTO_CS_TANGENT_ORTHO, madd3(N, -dot3(N, tg), tg));
         v3 Tn = normalize3(madd3(N, -dot3(N, tg), tg));                      /* :187 */
+        CS_NORM(c, PTO_CS_BITANGENT, cross3(N, Tn));
         v3 Bn = normalize3(cross3(N, Tn));                                   /* :188 */
         float tx = nm.x * 2.0f - 1.0f, ty = nm.y * 2.0f - 1.0f, tz = nm.z * 2.0f - 1.0f; /* :219 */
+        CS_NORM(c, PTO_CS_MAPPED_NORMAL, lincomb3(Tn, tx, Bn, ty, N, tz));
         hi.normal = normalize3(lincomb3(Tn, tx, Bn, ty, N, tz));             /* :222 */
     } else {
         hi.normal = n_i;                                                     /* :225 */
     }
+    if (hi.normal.x != hi.normal.x || hi.normal.y != hi.normal.y || hi.normal.z != hi.normal.z) CEN(c, PTO_EV_NAN_NORMAL);
     return hi;
 }
 
 static hitinfo_t scene_intersect(const pto_scene *s, ray_t r, counters_t *c, hit_t *raw) { /* :294-296 */
     hit_t h = traverse(s, r, c);
     if (raw) *raw = h;
-    return make_hitinfo(s, r, h);
+    return make_hitinfo(s, r, h, c);
 }
 
 /* ------------------------------------------------------------------------- */
@@ -454,21 +482,25 @@ static float reflectance(float cos_theta, float eta) {              /* :616-620 
     return r0 + (1.0f - r0) * pow5(1.0f - cos_theta);
 }
 /* constructTBN, :624-634: columns T, B, N */
-static void construct_tbn(v3 N, v3 *To, v3 *Bo) {
+static void construct_tbn(v3 N, v3 *To, v3 *Bo, counters_t *c) {
     v3 T = V3(1.0f, 0.0f, 0.0f);
-    if (fabsf(N.x) > 0.9f) T = V3(0.0f, 1.0f, 0.0f);
+    if (fabsf(N.x) > 0.9f) { T = V3(0.0f, 1.0f, 0.0f); CEN(c, PTO_EV_TBN_NX_ABOVE_0P9); }
+    CS_NORM(c, PTO_CS_TBN_B, cross3(N, T));
     v3 B = normalize3(cross3(N, T));
+    CS_NORM(c, PTO_CS_TBN_T, cross3(B, N));
     T = normalize3(cross3(B, N));
     *To = T; *Bo = B;
 }
-static v3 sample_ggx_normal(uint32_t *rng, v3 normal, float roughness) {  /* :348-364 */
+static v3 sample_ggx_normal(uint32_t *rng, v3 normal, float roughness, counters_t *c) {  /* :348-364 */
     float r1 = rng_f(rng), r2 = rng_f(rng);
     float a = roughness * roughness;
     float phi = (2.0f * PT_PI) * r1;
     float cos_t = sqrtf((1.0f - r2) / (1.0f + (a * a - 1.0f) * r2));
+    CS_SQRT(c, PTO_CS_GGX_SIN, 1.0f - cos_t * cos_t);
     float sin_t = sqrtf(1.0f - cos_t * cos_t);
     float sp, cp; sincos1(phi, &sp, &cp);
-    v3 T, B; construct_tbn(normal, &T, &B);
+    v3 T, B; construct_tbn(normal, &T, &B, c);
+    CS_NORM(c, PTO_CS_GGX_NORMAL, lincomb3(T, sin_t * cp, B, sin_t * sp, normal, cos_t));
     return normalize3(lincomb3(T, sin_t * cp, B, sin_t * sp, normal, cos_t));
 }
 static float power_heuristic(float nf, float fpdf, float ng, float gpdf) {  /* :492-496 */
@@ -476,35 +508,50 @@ static float power_heuristic(float nf, float fpdf, float ng, float gpdf) {  /* :
     return (f * f) / (f * f + g * g);
 }
 /* sampleBSDF, :498-546 (direction is returned un-normalised, as there) */
-static v3 sample_bsdf(uint32_t *rng, const hitinfo_t *h, ray_t cur, int front) {
+static v3 sample_bsdf(uint32_t *rng, const hitinfo_t *h, ray_t cur, int front, counters_t *c) {
     v3 Vv = neg3(normalize3(cur.d));                                /* :500 */
     float diffuse_p = (1.0f - h->metallic) * (1.0f - h->transmission);
     float specular_p = h->metallic;
     float r = rng_f(rng);                                           /* :508 */
     if (r < diffuse_p) {
+        CEN(c, PTO_EV_LOBE_DIFFUSE);
         v3 l = random_cosine_direction(rng);
-        v3 T, B; construct_tbn(h->normal, &T, &B);
+        v3 T, B; construct_tbn(h->normal, &T, &B, c);
         return lincomb3(T, l.x, B, l.y, h->normal, l.z);            /* :514 */
     } else if (r < diffuse_p + specular_p) {
+        CEN(c, PTO_EV_LOBE_SPECULAR);
         float rough = max1(h->roughness, 0.04f);
-        v3 N = sample_ggx_normal(rng, h->normal, rough);
+        v3 N = sample_ggx_normal(rng, h->normal, rough, c);
         return reflect3(neg3(Vv), N);                               /* :520 */
     } else {
+        CEN(c, front ? PTO_EV_LOBE_TRANSMIT_FRONT : PTO_EV_LOBE_TRANSMIT_BACK);
+        if (front) CS_RCP(c, PTO_CS_SAMPLE_IOR, h->ior);
         float eta = front ? 1.0f / h->ior : h->ior;                 /* :524 */
         float rough = max1(h->roughness, 0.04f);
-        v3 N = sample_ggx_normal(rng, h->normal, rough);
+        v3 N = sample_ggx_normal(rng, h->normal, rough, c);
         if (!front) N = neg3(N);                                    /* :528 */
         float cos_t = dot3(N, Vv);
+        CS_SQRT(c, PTO_CS_SAMPLE_SIN, 1.0f - cos_t * cos_t);
         float sin_t = sqrtf(1.0f - cos_t * cos_t);
         int cannot_refract = eta * sin_t > 1.0f;
         float F = reflectance(fabsf(cos_t), eta);
-        if (cannot_refract || (rng_f(rng) < F))                     /* :538 short-circuit */
+        if (cannot_refract) { CEN(c, PTO_EV_TOTAL_INTERNAL_REFLECTION); return reflect3(neg3(Vv), N); }
+        if (rng_f(rng) < F) {                                       /* :538 short-circuit */
+            CEN(c, PTO_EV_FRESNEL_REFLECTION);
             return reflect3(neg3(Vv), N);
+        }
+        CEN(c, PTO_EV_REFRACTION);
+        if (c->cen) {                                               /* what refract3 is about to test */
+            float dn = dot3(N, neg3(Vv)), k = 1.0f - (eta * eta) * (1.0f - dn * dn);
+            if (k < 0.0f) CEN(c, PTO_EV_REFRACT_K_NEGATIVE);
+            else CS_SQRT(c, PTO_CS_REFRACT_K, k);
+        }
         return refract3(neg3(Vv), N, eta);                          /* :543 */
     }
 }
 /* evalBSDF, :548-614: returns (f*cos, pdf) */
-static v4 eval_bsdf(const hitinfo_t *h, v3 normal, v3 Vv, v3 L, int front) {
+static v4 eval_bsdf(const hitinfo_t *h, v3 normal, v3 Vv, v3 L, int front, counters_t *c) {
+    CS_NORM(c, PTO_CS_EVAL_HALF, add3(Vv, L));
     v3 H = normalize3(add3(Vv, L));
     float ndl = max1(dot3(normal, L), 0.0f);
     float ndv = max1(dot3(normal, Vv), 0.0f);
@@ -522,6 +569,7 @@ static v4 eval_bsdf(const hitinfo_t *h, v3 normal, v3 Vv, v3 L, int front) {
     v3 bsdf = V3(0.0f, 0.0f, 0.0f);
     float pdf = 0.0f;
     if (h->transmission > 0.0f) {                                            /* :581-594 */
+        if (front) CS_RCP(c, PTO_CS_EVAL_IOR, h->ior);
         float eta = front ? 1.0f / h->ior : h->ior;
         float cos_t = dot3(normal, Vv);
         float Ft = reflectance(fabsf(cos_t), eta);
@@ -542,7 +590,10 @@ static v4 eval_bsdf(const hitinfo_t *h, v3 normal, v3 Vv, v3 L, int front) {
 /* ------------------------------------------------------------------------- */
 /* light sampling — pt.wgsl:374-489                                            */
 /* ------------------------------------------------------------------------- */
-typedef struct { v3 intensity; uint32_t light_type; v3 wi; float pdf; } light_sample_t;
+/* traced: the reference shoots this sample's shadow ray. occluded is set only under the census (c->cen), which evaluates an
+ * occluded sample as if it were not — what `shade` computes before `shadow` knows the answer — beside the result: trace()
+ * never adds such a sample. Without the census an occluded sample returns at once with pdf = 0, as the reference does. */
+typedef struct { v3 intensity; uint32_t light_type; v3 wi; float pdf; int traced, occluded; } light_sample_t;
 
 static light_sample_t sample_light(const pto_scene *s, uint32_t *rng, v3 hit_pos, counters_t *c) {
     light_sample_t ls;
@@ -552,30 +603,39 @@ static light_sample_t sample_light(const pto_scene *s, uint32_t *rng, v3 hit_pos
     ls.light_type = lt->light_type;
     float inv_n = 1.0f / (float)nl;
     if (lt->light_type == PTMI_LIGHT_DIRECTIONAL) {                   /* :385-406 */
+        CEN(c, PTO_EV_NEE_DIRECTIONAL);
+        CS_NORM(c, PTO_CS_LIGHT_DIRECTION, neg3(ld3(lt->position)));
         v3 wi = normalize3(neg3(ld3(lt->position)));
         ray_t sr = { madd3(wi, PT_EPS, hit_pos), wi };
         c->shadow_rays++;
         hit_t sh = traverse(s, sr, c);
         tap_shadow(c, -1.0f);
-        if (sh.t > 0.0f) { ls.wi = wi; ls.pdf = 0.0f; return ls; }
+        ls.traced = 1;
+        if (sh.t > 0.0f) { ls.wi = wi; ls.pdf = 0.0f; if (!c->cen) return ls; ls.occluded = 1; }
         ls.intensity = scale3(ld3(lt->color), lt->intensity);
         ls.wi = wi;
         ls.pdf = inv_n * 1000.0f;
     } else if (lt->light_type == PTMI_LIGHT_POINT) {                  /* :407-438 */
+        CEN(c, PTO_EV_NEE_POINT);
         v3 to_l = sub3(ld3(lt->position), hit_pos);
+        CS_SQRT(c, PTO_CS_POINT_DISTANCE, dot3(to_l, to_l));
         float dist = length3(to_l);
-        if (dist > 100.0f) return ls;
+        if (dist > 100.0f) { CEN(c, PTO_EV_POINT_LIGHT_BEYOND_100); return ls; }
+        CS_RCP(c, PTO_CS_POINT_RCP_DISTANCE, dist);
         v3 wi = vdiv3(to_l, dist);
         ray_t sr = { madd3(wi, PT_EPS, hit_pos), wi };
         c->shadow_rays++;
         hit_t sh = traverse(s, sr, c);
         tap_shadow(c, dist);
-        if (sh.t > 0.0f && sh.t < dist - PT_EPS * 2.0f) { ls.wi = wi; ls.pdf = 0.0f; return ls; }
+        ls.traced = 1;
+        if (sh.t > 0.0f && sh.t < dist - PT_EPS * 2.0f) { ls.wi = wi; ls.pdf = 0.0f; if (!c->cen) return ls; ls.occluded = 1; }
+        CS_RCP(c, PTO_CS_POINT_ATTENUATION, dist * dist);
         float att = 1.0f / (dist * dist);
         ls.intensity = scale3(scale3(ld3(lt->color), lt->intensity), att);
         ls.wi = wi;
         ls.pdf = inv_n * 10000.0f;
     } else if (lt->light_type == PTMI_LIGHT_EMISSIVE) {               /* :439-486 */
+        CEN(c, PTO_EV_NEE_EMISSIVE);
         ptmi_triangle zero_t; memset(&zero_t, 0, sizeof zero_t);
         const ptmi_triangle *T = lt->triangle_index < s->n_tris ? &s->tris[lt->triangle_index] : &zero_t;
         float r1 = rng_f(rng), r2 = rng_f(rng);
@@ -584,17 +644,23 @@ static light_sample_t sample_light(const pto_scene *s, uint32_t *rng, v3 hit_pos
         float v = r2 * sq;
         float w = 1.0f - u - v;
         v3 lp = lincomb3(ld3(T->v0), w, ld3(T->v1), u, ld3(T->v2), v);
+        CS_NORM(c, PTO_CS_LIGHT_NORMAL, lincomb3(ld3(T->n0), w, ld3(T->n1), u, ld3(T->n2), v));
         v3 n = normalize3(lincomb3(ld3(T->n0), w, ld3(T->n1), u, ld3(T->n2), v));
         v3 to_l = sub3(lp, hit_pos);
+        CS_SQRT(c, PTO_CS_EMISSIVE_DISTANCE, dot3(to_l, to_l));
         float dist = length3(to_l);
+        CS_RCP(c, PTO_CS_EMISSIVE_RCP_DISTANCE, dist);
         v3 wi = vdiv3(to_l, dist);
         ray_t sr = { madd3(wi, PT_EPS, hit_pos), wi };
         c->shadow_rays++;
         hit_t sh = traverse(s, sr, c);
         tap_shadow(c, dist);
-        if (sh.t > 0.0f && sh.t < dist - PT_EPS * 2.0f) { ls.wi = wi; ls.pdf = 0.0f; return ls; }
+        ls.traced = 1;
+        if (sh.t > 0.0f && sh.t < dist - PT_EPS * 2.0f) { ls.wi = wi; ls.pdf = 0.0f; if (!c->cen) return ls; ls.occluded = 1; }
         v3 e1 = sub3(ld3(T->v1), ld3(T->v0)), e2 = sub3(ld3(T->v2), ld3(T->v0));
+        CS_SQRT(c, PTO_CS_LIGHT_AREA, dot3(cross3(e1, e2), cross3(e1, e2)));
         float area = length3(cross3(e1, e2)) * 0.5f;
+        CS_RCP(c, PTO_CS_LIGHT_RCP_AREA, area);
         float cos_t = fabsf(dot3(n, neg3(wi)));
         ls.pdf = (inv_n * (1.0f / area)) * (dist * dist / max1(cos_t, PT_EPS));   /* :481 */
         ls.intensity = scale3(ld3(lt->color), lt->intensity);
@@ -614,6 +680,8 @@ static v3 trace(const pto_scene *s, uint32_t *rng, ray_t ray, uint32_t max_bounc
     for (uint32_t bounce = 0; bounce < max_bounces; bounce++) {
         hit_t raw;
         c->segments++;
+        c->b = bounce < PTO_CENSUS_BOUNCES ? bounce : PTO_CENSUS_BOUNCES - 1u;
+        CEN(c, PTO_EV_SEGMENT);
         hitinfo_t hit = scene_intersect(s, cur, c, &raw);                    /* :644 */
         if (log16) {
             float *L = log16 + 16 * nl++;
@@ -624,11 +692,14 @@ static v3 trace(const pto_scene *s, uint32_t *rng, ray_t ray, uint32_t max_bounc
         if (hit.t < 0.0f) {                                                  /* :646-649 */
             /* `result += throughput * vec3f(0.0)`: nothing for a finite throughput, NaN in every component whose
              * throughput is infinite or NaN (found by oracle/pt_literal.c, round 3; the kernels follow: shade.hip) */
+            CEN(c, finite3(thr) ? PTO_EV_MISS_FINITE : PTO_EV_MISS_NONFINITE);
             res = add3(res, mul3(thr, V3(0.0f, 0.0f, 0.0f)));
             break;
         }
         c->closest_hits++;
         if (hit.emission.x > 0.0f || hit.emission.y > 0.0f || hit.emission.z > 0.0f) {  /* :652 */
+            CEN(c, finite3(thr) ? PTO_EV_EMISSIVE_FINITE : PTO_EV_EMISSIVE_NONFINITE);
+            CS_RCP(c, PTO_CS_EMISSIVE_ATTENUATION, 1.0f + hit.t * hit.t);
             float att = 1.0f / (1.0f + hit.t * hit.t);
             float k = hit.emissive_strength;
             res = V3(res.x + thr.x * hit.emission.x * k * att,
@@ -642,24 +713,39 @@ static v3 trace(const pto_scene *s, uint32_t *rng, ray_t ray, uint32_t max_bounc
             light_sample_t ls = sample_light(s, rng, hit.position, c);
             if (ls.pdf > 0.0f) {
                 v3 Vv = neg3(normalize3(cur.d));
-                v4 ev = eval_bsdf(&hit, hit.normal, Vv, ls.wi, hit.is_front);
+                v4 ev = eval_bsdf(&hit, hit.normal, Vv, ls.wi, hit.is_front, c);
                 float wmis = power_heuristic(1.0f, ls.pdf, 1.0f, ev.w);
+                CS_RCP(c, PTO_CS_DIRECT_PDF, max1(ls.pdf, PT_EPS));
                 v3 direct = vdiv3(scale3(mul3(ls.intensity, V3(ev.x, ev.y, ev.z)), wmis),
                                   max1(ls.pdf, PT_EPS));                     /* :674 */
-                res = add3(res, mul3(thr, direct));                          /* :675 */
+                if (c->cen) {                /* what `shade` decides before the shadow ray is traced (shade.hip) */
+                    v3 contrib = mul3(thr, direct);
+                    if (contrib.x != 0.0f || contrib.y != 0.0f || contrib.z != 0.0f) CEN(c, PTO_EV_WOULD_LEAVE_RECORD);
+                    else CEN(c, PTO_EV_CONTRIBUTION_ZERO);
+                    if (!finite3(contrib)) CEN(c, PTO_EV_CONTRIBUTION_NONFINITE);
+                }
+                if (!ls.occluded) res = add3(res, mul3(thr, direct));        /* :675 */
+            } else if (ls.traced) {
+                CEN(c, PTO_EV_SAMPLE_PDF_NOT_POSITIVE);
             }
+        } else if (do_mis && s->n_lights > 0u) {
+            CEN(c, hit.transmission != 0.0f ? PTO_EV_NEE_SKIPPED_TRANSMISSION : PTO_EV_NEE_SKIPPED_BACK_FACE);
         }
-        v3 dir = sample_bsdf(rng, &hit, cur, hit.is_front);                  /* :680 */
-        v4 ev = eval_bsdf(&hit, hit.normal, neg3(normalize3(cur.d)), dir, hit.is_front);
+        v3 dir = sample_bsdf(rng, &hit, cur, hit.is_front, c);               /* :680 */
+        v4 ev = eval_bsdf(&hit, hit.normal, neg3(normalize3(cur.d)), dir, hit.is_front, c);
         if (ev.w <= 0.0f) break;                                             /* :685 (dead) */
         cur.o = madd3(dir, PT_EPS, hit.position);                            /* :691 */
+        CS_NORM(c, PTO_CS_NEXT_DIRECTION, dir);
         cur.d = normalize3(dir);                                             /* :692 */
         thr = mul3(thr, vdiv3(V3(ev.x, ev.y, ev.z), max1(ev.w, PT_EPS)));    /* :696 */
         if (bounce > 2u) {                                                   /* :699-705 */
             float p = max1(max1(thr.x, thr.y), thr.z);
-            if (rng_f(rng) > p) break;
+            if (rng_f(rng) > p) { CEN(c, PTO_EV_ROULETTE_KILL); break; }
+            CEN(c, PTO_EV_ROULETTE_SURVIVAL);
+            CS_RCP(c, PTO_CS_ROULETTE, p);
             thr = vdiv3(thr, p);
         }
+        if (bounce + 1u == max_bounces) CEN(c, PTO_EV_BOUNCE_LIMIT_END);
     }
     if (log16) {
         float *L = log16 + 16 * nl++;
@@ -769,8 +855,10 @@ static double now_s(void) {
 #endif
 }
 
-int pto_render(const pto_scene *s, const ptmi_camera *cam, uint32_t n_frames,
-               const pto_options *opt, float *out, pto_stats *st) {
+/* pto_render and pto_render_census: one frame loop, one trace(). census (NULL for pto_render): PTO_EV_COUNT x 64 totals; each thread
+ * counts into a table of its own (counters_t.cen) and adds it under the lock at the end. */
+static int render_impl(const pto_scene *s, const ptmi_camera *cam, uint32_t n_frames,
+                       const pto_options *opt, float *out, pto_stats *st, uint64_t *census) {
     uint32_t W = cam->width, H = cam->height;
     uint32_t y0 = opt ? opt->y0 : 0u, y1 = (opt && opt->y1) ? opt->y1 : H;
     uint32_t maxb = opt ? opt->max_bounces : 8u;
@@ -786,6 +874,7 @@ int pto_render(const pto_scene *s, const ptmi_camera *cam, uint32_t n_frames,
 #pragma omp parallel num_threads(nthreads)
     {
         counters_t c; memset(&c, 0, sizeof c);
+        if (census) c.cen = (uint64_t *)calloc((size_t)PTO_EV_COUNT * PTO_CENSUS_BOUNCES, sizeof(uint64_t));
 #pragma omp for schedule(dynamic, 1)
         for (int64_t y = y0; y < (int64_t)y1; y++) {
             for (uint32_t x = 0; x < W; x++) {
@@ -810,7 +899,9 @@ int pto_render(const pto_scene *s, const ptmi_camera *cam, uint32_t n_frames,
             tot.nodes_visited += c.nodes_visited; tot.tris_tested += c.tris_tested;
             tot.closest_hits += c.closest_hits;
             if (c.max_stack > tot.max_stack) tot.max_stack = c.max_stack;
+            if (c.cen) for (size_t i = 0; i < (size_t)PTO_EV_COUNT * PTO_CENSUS_BOUNCES; i++) census[i] += c.cen[i];
         }
+        free(c.cen);
     }
     if (st) {
         add_counters(st, &tot);
@@ -820,6 +911,25 @@ int pto_render(const pto_scene *s, const ptmi_camera *cam, uint32_t n_frames,
     }
     return 0;
 }
+
+int pto_render(const pto_scene *s, const ptmi_camera *cam, uint32_t n_frames,
+               const pto_options *opt, float *out, pto_stats *st) {
+    return render_impl(s, cam, n_frames, opt, out, st, NULL);
+}
+int pto_render_census(const pto_scene *s, const ptmi_camera *cam, uint32_t n_frames,
+                      const pto_options *opt, float *out, pto_stats *st, uint64_t *census) {
+    if (!census) return -1;
+    memset(census, 0, sizeof(uint64_t) * PTO_EV_COUNT * PTO_CENSUS_BOUNCES);
+    return render_impl(s, cam, n_frames, opt, out, st, census);
+}
+
+static const char *const census_names[PTO_EV_COUNT] = {
+#define X(id, name) name,
+    PTO_CENSUS_EVENTS(X)
+#undef X
+};
+int pto_census_event_count(void) { return PTO_EV_COUNT; }
+const char *pto_census_event_name(int ev) { return ev >= 0 && ev < PTO_EV_COUNT ? census_names[ev] : NULL; }
 
 /* Every ray a render traces, with the traversal's result: rec9[9 i ..] = o.xyz, d.xyz, dist (0: closest-hit ray; < 0: shadow ray to
  * a directional light; > 0: shadow ray, the light's distance), t (-1: miss), tri (bits). Rows [y0, y1) x n_frames; at most max_rays
@@ -1021,7 +1131,8 @@ void pto_eval_bsdf(const float albedo[3], float roughness, float metallic, float
     hitinfo_t h; memset(&h, 0, sizeof h);
     h.albedo = ld3(albedo); h.roughness = roughness; h.metallic = metallic;
     h.transmission = transmission; h.ior = ior; h.normal = ld3(n);
-    v4 r = eval_bsdf(&h, ld3(n), ld3(v), ld3(l), front);
+    counters_t c; memset(&c, 0, sizeof c);
+    v4 r = eval_bsdf(&h, ld3(n), ld3(v), ld3(l), front, &c);
     out4[0] = r.x; out4[1] = r.y; out4[2] = r.z; out4[3] = r.w;
 }
 float pto_distribution_ggx(const float n[3], const float h[3], float roughness) {
@@ -1035,6 +1146,7 @@ void pto_cosine_direction(uint32_t *state_io, float out3[3]) {
     out3[0] = d.x; out3[1] = d.y; out3[2] = d.z;
 }
 void pto_sample_ggx_normal(uint32_t *state_io, const float n[3], float roughness, float out3[3]) {
-    v3 d = sample_ggx_normal(state_io, ld3(n), roughness);
+    counters_t c; memset(&c, 0, sizeof c);
+    v3 d = sample_ggx_normal(state_io, ld3(n), roughness, &c);
     out3[0] = d.x; out3[1] = d.y; out3[2] = d.z;
 }

@@ -91,6 +91,96 @@ int pto_occluded(const pto_scene *s, uint32_t n, const float *o3, const float *d
 int pto_render(const pto_scene *s, const ptmi_camera *cam, uint32_t n_frames,
                const pto_options *opt, float *out_rgba, pto_stats *st);
 
+/* The branch census: pto_render with a table census[event * PTO_CENSUS_BOUNCES + bounce] of how often each event of the bounce
+ * loop happened at each bounce (bounces from 63 on share the last column, like ptmi_stats.segments_by_bounce). Same trace(),
+ * same image bits, same pto_stats as pto_render.
+ *
+ * "would_leave_record", "contribution_zero", "contribution_nonfinite" and "sample_pdf_not_positive" describe a next-event
+ * sample as the `shade` kernel sees it, before the shadow ray is traced: its pdf and contribution as if unoccluded. For that the
+ * census evaluates an occluded sample too, beside the result (it is never added). From the table follow three figures the
+ * GPU reports: segments_by_bounce[b] = segment[b]; shadow_rays = sum of nee_* minus point_light_beyond_100;
+ * shadow_traced = sum of would_leave_record.
+ *
+ * The cs_* events are the call sites in `shade` of the short reciprocal / square root / normalize (csrc/pt_math.h rcp1, sqrt1,
+ * normalize3): counted when the operand is outside [2^-100, 2^100] or NaN, where the kernel takes the IEEE expansion. Sites
+ * whose operand cannot leave the range are not listed: normalize of the ray direction (unit length, or the ray has missed),
+ * 1 / n_lights, / pi, / max(4 NdotV NdotL, 1e-6), / max(pdf, 1e-6) of the BSDF sample, and the square roots of uniform draws
+ * (zero for one RNG word in 2^32). */
+#define PTO_CENSUS_BOUNCES 64
+#define PTO_CENSUS_EVENTS(X) \
+    X(PTO_EV_SEGMENT, "segment") \
+    X(PTO_EV_MISS_FINITE, "miss_finite") \
+    X(PTO_EV_MISS_NONFINITE, "miss_nonfinite") \
+    X(PTO_EV_EMISSIVE_FINITE, "emissive_finite") \
+    X(PTO_EV_EMISSIVE_NONFINITE, "emissive_nonfinite") \
+    X(PTO_EV_NEE_DIRECTIONAL, "nee_directional") \
+    X(PTO_EV_NEE_POINT, "nee_point") \
+    X(PTO_EV_NEE_EMISSIVE, "nee_emissive") \
+    X(PTO_EV_POINT_LIGHT_BEYOND_100, "point_light_beyond_100") \
+    X(PTO_EV_WOULD_LEAVE_RECORD, "would_leave_record") \
+    X(PTO_EV_CONTRIBUTION_ZERO, "contribution_zero") \
+    X(PTO_EV_SAMPLE_PDF_NOT_POSITIVE, "sample_pdf_not_positive") \
+    X(PTO_EV_CONTRIBUTION_NONFINITE, "contribution_nonfinite") \
+    X(PTO_EV_NEE_SKIPPED_BACK_FACE, "nee_skipped_back_face") \
+    X(PTO_EV_NEE_SKIPPED_TRANSMISSION, "nee_skipped_transmission") \
+    X(PTO_EV_LOBE_DIFFUSE, "lobe_diffuse") \
+    X(PTO_EV_LOBE_SPECULAR, "lobe_specular") \
+    X(PTO_EV_LOBE_TRANSMIT_FRONT, "lobe_transmit_front") \
+    X(PTO_EV_LOBE_TRANSMIT_BACK, "lobe_transmit_back") \
+    X(PTO_EV_TOTAL_INTERNAL_REFLECTION, "total_internal_reflection") \
+    X(PTO_EV_FRESNEL_REFLECTION, "fresnel_reflection") \
+    X(PTO_EV_REFRACTION, "refraction") \
+    X(PTO_EV_REFRACT_K_NEGATIVE, "refract_k_negative") \
+    X(PTO_EV_NORMAL_MAP, "normal_map") \
+    X(PTO_EV_NORMAL_MAP_ZERO_DET, "normal_map_zero_det") \
+    X(PTO_EV_TBN_NX_ABOVE_0P9, "tbn_nx_above_0p9") \
+    X(PTO_EV_NAN_NORMAL, "nan_normal") \
+    X(PTO_EV_MATERIAL_OUT_OF_RANGE, "material_out_of_range") \
+    X(PTO_EV_TRANSMISSION_FRACTIONAL, "transmission_fractional") \
+    X(PTO_EV_ROUGHNESS_CLAMPED, "roughness_clamped") \
+    X(PTO_EV_ROULETTE_KILL, "roulette_kill") \
+    X(PTO_EV_ROULETTE_SURVIVAL, "roulette_survival") \
+    X(PTO_EV_BOUNCE_LIMIT_END, "bounce_limit_end") \
+    X(PTO_CS_GEO_NORMAL, "cs_geo_normal") \
+    X(PTO_CS_VERTEX_NORMAL, "cs_vertex_normal") \
+    X(PTO_CS_UV_DET, "cs_uv_det") \
+    X(PTO_CS_TANGENT, "cs_tangent") \
+    X(PTO_CS_TANGENT_ORTHO, "cs_tangent_ortho") \
+    X(PTO_CS_BITANGENT, "cs_bitangent") \
+    X(PTO_CS_MAPPED_NORMAL, "cs_mapped_normal") \
+    X(PTO_CS_EMISSIVE_ATTENUATION, "cs_emissive_attenuation") \
+    X(PTO_CS_LIGHT_DIRECTION, "cs_light_direction") \
+    X(PTO_CS_POINT_DISTANCE, "cs_point_distance") \
+    X(PTO_CS_POINT_RCP_DISTANCE, "cs_point_rcp_distance") \
+    X(PTO_CS_POINT_ATTENUATION, "cs_point_attenuation") \
+    X(PTO_CS_LIGHT_NORMAL, "cs_light_normal") \
+    X(PTO_CS_EMISSIVE_DISTANCE, "cs_emissive_distance") \
+    X(PTO_CS_EMISSIVE_RCP_DISTANCE, "cs_emissive_rcp_distance") \
+    X(PTO_CS_LIGHT_AREA, "cs_light_area") \
+    X(PTO_CS_LIGHT_RCP_AREA, "cs_light_rcp_area") \
+    X(PTO_CS_EVAL_HALF, "cs_eval_half") \
+    X(PTO_CS_EVAL_IOR, "cs_eval_ior") \
+    X(PTO_CS_DIRECT_PDF, "cs_direct_pdf") \
+    X(PTO_CS_TBN_B, "cs_tbn_b") \
+    X(PTO_CS_TBN_T, "cs_tbn_t") \
+    X(PTO_CS_GGX_SIN, "cs_ggx_sin") \
+    X(PTO_CS_GGX_NORMAL, "cs_ggx_normal") \
+    X(PTO_CS_SAMPLE_IOR, "cs_sample_ior") \
+    X(PTO_CS_SAMPLE_SIN, "cs_sample_sin") \
+    X(PTO_CS_REFRACT_K, "cs_refract_k") \
+    X(PTO_CS_NEXT_DIRECTION, "cs_next_direction") \
+    X(PTO_CS_ROULETTE, "cs_roulette")
+typedef enum pto_census_event {
+#define PTO_X_(id, name) id,
+    PTO_CENSUS_EVENTS(PTO_X_)
+#undef PTO_X_
+    PTO_EV_COUNT
+} pto_census_event;
+int pto_render_census(const pto_scene *s, const ptmi_camera *cam, uint32_t n_frames,
+                      const pto_options *opt, float *out_rgba, pto_stats *st, uint64_t *census);
+int pto_census_event_count(void);
+const char *pto_census_event_name(int ev);
+
 /* Every ray a render traces, with the traversal's result (for tools that replay real rays through another traversal):
  * rec9[9 i ..] = o.xyz, d.xyz, dist (0: closest-hit ray; < 0: shadow ray to a directional light; > 0: shadow ray, the light's
  * distance), t (-1: miss), tri (bits). Rows [opt->y0, opt->y1) x n_frames; at most max_rays are stored, in no particular order;

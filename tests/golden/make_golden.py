@@ -8,6 +8,9 @@ versions must reproduce them) and fixed targets for the HIP path. Each file hold
 complete inputs (scene blobs, camera, rays) next to the expected outputs.
 
     python tests/golden/make_golden.py [fixture names]
+
+shade_census.json (fixture name "shade_census") holds the oracle's branch census of the gauntlet renders and of the renders the
+GPU parity tests compare: tests/test_shade_census_host.py.
 """
 import os
 import sys
@@ -26,14 +29,26 @@ CASES = [  # name, scene, W, H, frames, bounces, mis, aperture
     ("cornell_64x48_4spp_mis", "cornell", 64, 48, 4, 8, 1, 0.001),
     ("cornell_64x64_4spp_b4_nomis", "cornell", 64, 64, 4, 4, 0, 0.001),      # BASELINE configs[0] shape, reduced
     ("feature_box_48x48_3spp", "feature_box", 48, 48, 3, 8, 1, 0.05),
-    ("random_soup3_48x48_3spp", "random_soup:3", 48, 48, 3, 8, 1, 0.02),        # degenerate triangles, zero normals, all lobes
+    ("random_soup3_48x48_3spp", "random_soup:3", 48, 48, 3, 8, 1, 0.02),        # degenerate triangles, zero normals, three lobes
     ("deep_chain_32x32_2spp", "deep_chain", 32, 32, 2, 4, 1, 0.0),              # 58-level BVH (spilling node stacks)
 ]
+
+
+def write_shade_census(orc):
+    import json
+    import test_shade_census_host as T
+    tables = T.census_tables(orc)
+    with open(T.GOLDEN, "w") as f:
+        f.write("{\n" + ",\n".join(json.dumps(k) + ": " + json.dumps(v, separators=(",", ":")) for k, v in sorted(tables.items()))
+                + "\n}\n")
+    print("shade_census", len(tables), "renders")
 
 
 def main():
     orc = Oracle(strict=False)
     only = set(sys.argv[1:])                  # optional: names of the fixtures to (re)write; default all
+    if not only or "shade_census" in only:
+        write_shade_census(orc)
     for name, sname, W, H, frames, bounces, mis, ap in CASES:
         if only and name not in only:
             continue

@@ -138,6 +138,30 @@ class Oracle:
         assert rc == 0
         return out, st
 
+    def census_events(self):
+        """the names of the census events, in table order (oracle/pt_oracle.h PTO_CENSUS_EVENTS)"""
+        self.L.pto_census_event_name.restype = ctypes.c_char_p
+        self.L.pto_census_event_name.argtypes = [ctypes.c_int]
+        return [self.L.pto_census_event_name(i).decode() for i in range(self.L.pto_census_event_count())]
+
+    def render_census(self, scene, cam, n_frames, max_bounces=8, do_mis=1, out=None, y0=0, y1=0, threads=0):
+        """render() plus the branch census: (out, stats, {event name: (64,) uint64 occurrences per bounce})"""
+        W, H = int(cam["width"]), int(cam["height"])
+        if out is None:
+            out = np.zeros((H, W, 4), np.float32)
+        assert out.dtype == np.float32 and out.shape == (H, W, 4) and out.flags.c_contiguous
+        names = self.census_events()
+        table = np.zeros((len(names), 64), np.uint64)
+        opt = PtoOptions(max_bounces, do_mis, y0, y1, threads)
+        st = PtoStats()
+        s = self.scene_struct(scene)
+        fn = self.L.pto_render_census
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 4
+        rc = fn(ctypes.byref(s), _ptr(cam), n_frames, ctypes.byref(opt), _ptr(out), ctypes.byref(st), _ptr(table))
+        assert rc == 0
+        return out, st, dict(zip(names, table))
+
     def blit(self, rgba):
         rgba = np.ascontiguousarray(rgba, np.float32)
         H, W = rgba.shape[:2]
