@@ -152,7 +152,9 @@ typedef struct ptmi_stats {
     uint32_t tree_builder_used; /* who built the hierarchy the last upload's regular rays walk: 1 the host, 2 the device (both leaf modes);
                                    0 none: the uploaded tree is walked as it is (keep_reference_tree, an empty scene, a tree whose
                                    root is a leaf — there is no hierarchy over a single leaf —, a tree with non-finite boxes) */
-    uint32_t reserved_stats[1];
+    uint32_t shade_tables;      /* of the last dispatch (was reserved): bits 0-23 the bytes of LDS a workgroup of `shade` may fill with the
+                                   scene's materials, lights and light triangles; bit 28 set: the materials were served from LDS, bit 29: the
+                                   lights and their triangles (a table that does not fit is read from memory; same results either way) */
 } ptmi_stats;
 
 /* ---- lifetime ----------------------------------------------------------- */

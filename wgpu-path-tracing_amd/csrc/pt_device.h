@@ -63,7 +63,28 @@ struct DevScene {
     const uint4 *qnodes16;      // qnodes with the same 16-bit references (NULL: none)
     unsigned long long *verify_stat;    // += rays whose winner failed its reference leaf's box and were traced again
     const DevScene *self;       // this description in device memory (the own-leaf kernels read it from there, not from kernel arguments)
+    const float4 *shade_tab;    // the shade tables (below): what `shade` stages into LDS
 };
+
+// ---- shade tables: the records `shade` reads per hit that are the same for the whole scene, in one blob built at upload ----
+// In float4 (16 B) units, all raw copies of the uploaded bytes:
+//   [0, 8 (n_mats + 1))         the materials, 8 each, then one material of zeros: what a material index >= n_mats reads
+//   [.., + 3 n_lights)          the lights, 3 each
+//   [.., + 8 n_lights)          per light, at the light's own index, the triangle an emissive light names (zeros for the other types
+//                               and for a triangle index >= n_tris), so that it is found without reading triangle_index first
+// k_shade copies the materials, the lights (with their triangles) or both into LDS when they fit PT_SHADE_LDS_BUDGET and reads them
+// from there; a table that does not fit is read from DevScene::mats / lights / tris as before (pt_shade_stage: chosen per launch).
+#define PT_SHADE_LDS_BUDGET 16384u      /* bytes of LDS per 256-thread workgroup of k_shade */
+enum { PT_STAGE_MATS = 1, PT_STAGE_LIGHTS = 2 };
+PT_HD size_t pt_tab_mats_q(uint32_t n_mats) { return ((size_t)n_mats + 1u) * 8u; }
+PT_HD size_t pt_tab_lights_q(uint32_t n_lights) { return (size_t)n_lights * 11u; }
+// which tables a launch stages: both if they fit together, else the materials (every hit reads one) if they fit, else the lights
+PT_HD int pt_shade_stage(uint32_t n_mats, uint32_t n_lights) {
+    const size_t m = pt_tab_mats_q(n_mats) * 16u, l = pt_tab_lights_q(n_lights) * 16u;
+    if (m + l <= PT_SHADE_LDS_BUDGET) return PT_STAGE_MATS | (n_lights ? PT_STAGE_LIGHTS : 0);
+    if (m <= PT_SHADE_LDS_BUDGET) return PT_STAGE_MATS;
+    return l <= PT_SHADE_LDS_BUDGET && n_lights ? PT_STAGE_LIGHTS : 0;
+}
 
 // ---- path state: 56 B per path, four streams indexed by path id (O / D / C: by queue slot after the repack, ShadeParams) ----
 //   O = (origin.xyz, bits(rng state))   D = (direction.xyz, throughput.x)      the two float4 `extend` reads

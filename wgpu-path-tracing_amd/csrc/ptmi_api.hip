@@ -34,6 +34,7 @@ enum SceneBuf {
     kQnodes, kLeafStream,              // its quantised nodes; the leaf stream (the reference's leaves only)
     kLeafbox,                          // own leaves: per original triangle, the box of the reference leaf that lists it
     kWnodes16, kRefWnodes16, kQnodes16,    // own leaves, small scenes: the two hierarchies and the quantised nodes with 16-bit references
+    kShadeTab,                         // the shade tables: materials, lights and the lights' triangles in one blob (pt_device.h)
     kSceneBufs
 };
 
@@ -941,6 +942,21 @@ struct PtPrepared {
     bool take_device_buffers = false;        // the one install may take b's device buffers instead of copying them (single device)
 };
 
+// The shade tables of a scene (pt_device.h): raw copies of the uploaded records, in the order k_shade stages them.
+static std::vector<float4> shade_tables(const ptmi_triangle *tris, uint32_t nt, const ptmi_material *mats, uint32_t nm,
+                                        const ptmi_light *lights, uint32_t nl) {
+    std::vector<float4> tab(pt_tab_mats_q(nm) + pt_tab_lights_q(nl), make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    char *at = reinterpret_cast<char *>(tab.data());
+    if (nm) std::memcpy(at, mats, (size_t)nm * sizeof(ptmi_material));
+    at += pt_tab_mats_q(nm) * sizeof(float4);                                   // (behind the materials: the material of zeros)
+    if (nl) std::memcpy(at, lights, (size_t)nl * sizeof(ptmi_light));
+    at += (size_t)nl * sizeof(ptmi_light);
+    for (uint32_t i = 0; i < nl; i++)
+        if (lights[i].light_type == PTMI_LIGHT_EMISSIVE && lights[i].triangle_index < nt)
+            std::memcpy(at + (size_t)i * sizeof(ptmi_triangle), &tris[lights[i].triangle_index], sizeof(ptmi_triangle));
+    return tab;
+}
+
 PtPrepared *pt_prepare_scene(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt, const ptmi_material *mats, uint32_t nm,
                              const ptmi_bvh_node *nodes, uint32_t nn, const ptmi_light *lights, uint32_t nl, int *rc_out) {
     auto bad = [&](int rc) -> PtPrepared * { *rc_out = rc; return nullptr; };
@@ -961,6 +977,7 @@ PtPrepared *pt_prepare_scene(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt
     if (!p->b.buf[kTris].present) p->b.view(kTris, tris, (size_t)nt * sizeof(ptmi_triangle));     // (else the device copy)
     p->b.view(kMats, mats, (size_t)nm * sizeof(ptmi_material));
     p->b.view(kLights, lights, (size_t)nl * sizeof(ptmi_light));
+    p->b.hold(kShadeTab, shade_tables(tris, nt, mats, nm, lights, nl));
     p->nt = nt; p->nm = nm; p->nl = nl;
     p->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     *rc_out = PTMI_OK;
@@ -1026,6 +1043,7 @@ int pt_install_scene(ptmi_ctx *c, PtPrepared *prep) {
     s.safe_origin = h.safe_origin;
     s.verify_stat = c->d_stats + 4;
     s.self = c->d_scene;
+    s.shade_tab = static_cast<const float4 *>(d[kShadeTab]);
     HIP_TRY(c, hipMemcpy(c->d_scene, &c->sc, sizeof(DevScene), hipMemcpyHostToDevice));
     c->img = h;
     c->have_scene = true;
@@ -1210,6 +1228,7 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
     c->st.shadow_variant = pt_variant_code(cfg_shadow0);
     c->st.frames_per_batch_used = F;
     c->st.radiance_stride_bytes = (walks_memory_quantised(cfg0) || walks_memory_quantised(cfg_shadow0)) ? 16u : 12u;
+    c->st.shade_tables = PT_SHADE_LDS_BUDGET | ((uint32_t)pt_shade_stage(c->sc.n_mats, c->sc.n_lights) << 28);
     const int blocks = c->n_cu * 8;
 #ifndef PT_SHADE_WGS_PER_CU
 #define PT_SHADE_WGS_PER_CU 16

@@ -24,6 +24,42 @@ struct HitInfo {                       // pt.wgsl:86-101 (fields the bounce loop
 
 PT_DEV v3 ld3(const float *p) { return mk3(p[0], p[1], p[2]); }
 
+// Where a bounce gets its material, its light and the light's triangle (pt_device.h, shade tables). STAGE names the tables k_shade
+// copied into LDS (PT_STAGE_*): those are read from there through address-space-qualified pointers, as the
+// traversal kernels read theirs (a generic pointer would make them FLAT loads, which take the texture-address path the copy exists to
+// avoid); the others come from memory as they always did. Either way the same bytes arrive, the zeros of the out-of-range rules included.
+typedef float f4v __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(3))) f4v *lds_f4p;
+// a record of Q quads: copied as a whole, so that the compiler reads the fields the bounce uses in the widths that suit them (whole
+// quads held in registers would keep the records' padding words live)
+template <class R, int Q> PT_DEV R lds_record(lds_f4p p) {
+    static_assert(sizeof(R) == Q * 16, "a record of Q quads");
+    R r;
+    __builtin_memcpy(&r, p, sizeof r);
+    return r;
+}
+template <int STAGE> struct ShadeTabs {
+    lds_f4p mats, lights, ltris;                // the staged tables (a table that is not staged: never read)
+    PT_DEV ptmi_material material(const DevScene &sc, uint32_t mi) const {
+        if (STAGE & PT_STAGE_MATS) return lds_record<ptmi_material, 8>(mats + 8u * min(mi, sc.n_mats));   // record n_mats is the zeros
+        ptmi_material m;
+        if (mi < sc.n_mats) m = sc.mats[mi];
+        else __builtin_memset(&m, 0, sizeof m);
+        return m;
+    }
+    PT_DEV ptmi_light light(const DevScene &sc, uint32_t li) const {
+        if (STAGE & PT_STAGE_LIGHTS) return lds_record<ptmi_light, 3>(lights + 3u * li);
+        return sc.lights[li];
+    }
+    PT_DEV ptmi_triangle light_triangle(const DevScene &sc, uint32_t li, uint32_t triangle_index) const {
+        if (STAGE & PT_STAGE_LIGHTS) return lds_record<ptmi_triangle, 8>(ltris + 8u * li);
+        ptmi_triangle T;
+        if (triangle_index < sc.n_tris) T = sc.tris[triangle_index];
+        else __builtin_memset(&T, 0, sizeof T);
+        return T;
+    }
+};
+
 PT_DEV v4 atlas_load(const DevScene &sc, uint32_t x, uint32_t y) {
     v4 r; r.x = r.y = r.z = r.w = 0.0f;
     if (sc.atlas_fmt == 0u || x >= sc.atlas_w || y >= sc.atlas_h) return r;      // out of bounds reads zero
@@ -53,7 +89,8 @@ PT_DEV v4 texture_color(const DevScene &sc, const ptmi_atlas_rect &tx, float uvx
 // rayTriangleIntersect, pt.wgsl:159-226, for the closest hit only. The hit record carries (t, triangle); the barycentric
 // (u, v) are the ones `extend` computed when it accepted the hit — recomputed here by the same tri_test on the same
 // operands (e1, e2 are the same single IEEE subtractions the traversal image was built with, ptmi_api.hip).
-PT_DEV HitInfo make_hitinfo(const DevScene &sc, v3 ro, v3 rd, float t, uint32_t tri) {
+template <int STAGE>
+PT_DEV HitInfo make_hitinfo(const DevScene &sc, const ShadeTabs<STAGE> &tabs, v3 ro, v3 rd, float t, uint32_t tri) {
     HitInfo hi;
     const ptmi_triangle &T = sc.tris[tri];
     // the whole triangle record is requested before the first use: the range tests of the short reciprocal / square root below
@@ -74,9 +111,7 @@ PT_DEV HitInfo make_hitinfo(const DevScene &sc, v3 ro, v3 rd, float t, uint32_t 
     float uvx = fma1(u2x, v, fma1(u1x, u, u0x * w));
     float uvy = fma1(u2y, v, fma1(u1y, u, u0y * w));
     hi.is_front = dot3(geo_n, rd) < 0.0f;
-    ptmi_material m;
-    if (mi < sc.n_mats) m = sc.mats[mi];
-    else __builtin_memset(&m, 0, sizeof m);
+    const ptmi_material m = tabs.material(sc, mi);
     v4 one; one.x = one.y = one.z = one.w = 1.0f;
     v4 alb = texture_color(sc, m.albedo_map, uvx, uvy, one);
     hi.albedo = mk3(alb.x * m.base_color[0], alb.y * m.base_color[1], alb.z * m.base_color[2]);
@@ -226,11 +261,13 @@ struct LightSample { v3 intensity; v3 wi; float pdf; float dist; bool traced; };
 
 // sampleLight, pt.wgsl:374-489, without its traversal: the occlusion test is the
 // `shadow` kernel's; pdf = 0 means "no record" (the :413-415 early-out).
-PT_DEV LightSample sample_light(const DevScene &sc, uint32_t &rng, v3 hit_pos) {
+template <int STAGE>
+PT_DEV LightSample sample_light(const DevScene &sc, const ShadeTabs<STAGE> &tabs, uint32_t &rng, v3 hit_pos) {
     LightSample ls;
     ls.intensity = mk3(0.0f, 0.0f, 0.0f); ls.wi = mk3(0.0f, 0.0f, 0.0f); ls.pdf = 0.0f; ls.dist = -1.0f; ls.traced = false;
     const uint32_t nl = sc.n_lights;
-    const ptmi_light lt = sc.lights[rng_int(rng, 0u, nl - 1u)];
+    const uint32_t li = rng_int(rng, 0u, nl - 1u);
+    const ptmi_light lt = tabs.light(sc, li);
     const float inv_n = rcp1((float)nl);
     if (lt.light_type == PTMI_LIGHT_DIRECTIONAL) {
         ls.wi = normalize3(neg3(ld3(lt.position)));
@@ -249,9 +286,7 @@ PT_DEV LightSample sample_light(const DevScene &sc, uint32_t &rng, v3 hit_pos) {
         ls.dist = dist;
         ls.traced = true;
     } else if (lt.light_type == PTMI_LIGHT_EMISSIVE) {
-        ptmi_triangle T;
-        if (lt.triangle_index < sc.n_tris) T = sc.tris[lt.triangle_index];
-        else __builtin_memset(&T, 0, sizeof T);
+        const ptmi_triangle T = tabs.light_triangle(sc, li, lt.triangle_index);
         float r1 = rng_f(rng), r2 = rng_f(rng);
         float sq = sqrt1(r1);
         float u = 1.0f - sq;
@@ -294,15 +329,29 @@ constexpr int SBLOCK = 256;
 // writes record 64 * (i / 64) + rank. Slot order is kept (the compaction lists positions in that order, pipeline.hip), and the
 // lines `shadow` reads are the filled ones: where 59 % of the slots leave a record (Cornell, MIS), the records left at their own
 // slots put a record in nearly every line of all three streams.
-template <bool AOV>
+//
+// STAGE (PT_STAGE_*, chosen per launch by pt_shade_stage): the shade tables the workgroup copies into LDS before its first segment. On
+// the scenes measured every lane of every bounce fetched its material, its light and the light's triangle from a handful of records
+// through its own vector loads, three dependent rounds behind the hit's triangle; from LDS they cost ds_reads on another unit.
+template <bool AOV, int STAGE>
 __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, DevPaths P, const uint32_t *__restrict__ queue,
                                                   const uint32_t *__restrict__ count_ptr,
                                                   const float2 *__restrict__ hits, DevShadow S,
                                                   uint64_t *__restrict__ alive_mask,
                                                   uint64_t *__restrict__ shadow_mask, ShadeParams sp,
                                                   float4 *__restrict__ aov) {
+    extern __shared__ float4 smem[];
     const uint32_t count = *count_ptr;
     const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t mats_q = (STAGE & PT_STAGE_MATS) ? (uint32_t)pt_tab_mats_q(sc.n_mats) : 0u;          // staged quads of each table
+    const uint32_t lights_q = (STAGE & PT_STAGE_LIGHTS) ? (uint32_t)pt_tab_lights_q(sc.n_lights) : 0u;
+    if (STAGE) {
+        const float4 *src = sc.shade_tab + ((STAGE & PT_STAGE_MATS) ? 0u : pt_tab_mats_q(sc.n_mats));
+        for (uint32_t k = threadIdx.x; k < mats_q + lights_q; k += SBLOCK) smem[k] = src[k];
+        __syncthreads();
+    }
+    const lds_f4p lds_lights = (lds_f4p)smem + mats_q;
+    const ShadeTabs<STAGE> tabs{(lds_f4p)smem, lds_lights, lds_lights + 3u * sc.n_lights};
     uint32_t n_skipped = 0, n_emitted = 0;  // lane 0 of each wave: one atomic per wave at the end
     for (uint32_t base = blockIdx.x * SBLOCK; base < count; base += gridDim.x * SBLOCK) {
         const uint32_t i = base + threadIdx.x;
@@ -319,7 +368,7 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                 const v3 ro = xyz(o4), rd = xyz(d4);
                 v3 thr = mk3(1.0f, 1.0f, 1.0f);                                      // pt.wgsl:639; raygen stores no throughput
                 if (sp.bounce != 0u) { const float2 c2 = ld_stream(&P.C[q]); thr = mk3(d4.w, c2.x, c2.y); }
-                const HitInfo hit = make_hitinfo(sc, ro, rd, h2.x, __float_as_uint(h2.y));
+                const HitInfo hit = make_hitinfo(sc, tabs, ro, rd, h2.x, __float_as_uint(h2.y));
                 if (AOV) {
                     st_stream(&aov[2 * (size_t)i], make_float4(hit.albedo.x, hit.albedo.y, hit.albedo.z, hit.t));
                     st_stream(&aov[2 * (size_t)i + 1], make_float4(hit.normal.x, hit.normal.y, hit.normal.z, h2.y));
@@ -338,7 +387,7 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                     }
                 } else {
                     if (sp.do_mis && sc.n_lights > 0u && hit.transmission == 0.0f && hit.is_front) {   // pt.wgsl:661
-                        LightSample ls = sample_light(sc, rng, hit.position);
+                        LightSample ls = sample_light(sc, tabs, rng, hit.position);
                         if (ls.pdf > 0.0f) {
                             v3 V = neg3(normalize3(rd));
                             v4 ev = eval_bsdf(hit, hit.normal, V, ls.wi, hit.is_front);
@@ -432,15 +481,28 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
 #else
 #define PT_LAUNCH_SHADE pt_launch_shade
 #endif
+namespace {
+template <bool AOV, int STAGE>
+void launch_shade(hipStream_t s, int blocks, const DevScene &sc, DevPaths p, const uint32_t *queue, const uint32_t *count,
+                  const float2 *hits, DevShadow sh, uint64_t *alive_mask, uint64_t *shadow_mask, ShadeParams sp, float4 *aov) {
+    const size_t lds = (((STAGE & PT_STAGE_MATS) ? pt_tab_mats_q(sc.n_mats) : 0) + ((STAGE & PT_STAGE_LIGHTS) ? pt_tab_lights_q(sc.n_lights) : 0)) * 16;
+    hipLaunchKernelGGL((k_shade<AOV, STAGE>), dim3(blocks), dim3(SBLOCK), lds, s, sc, p, queue, count, hits, sh, alive_mask,
+                       shadow_mask, sp, aov);
+}
+}  // namespace
+// the tables each launch stages: pt_shade_stage of the scene's counts (what fits PT_SHADE_LDS_BUDGET), for both instantiations
 void PT_LAUNCH_SHADE(hipStream_t s, int blocks, const DevScene &sc, DevPaths p, const uint32_t *queue,
                      const uint32_t *count, const float2 *hits, DevShadow sh, uint64_t *alive_mask,
                      uint64_t *shadow_mask, ShadeParams sp, float4 *aov) {
-    if (aov)
-        hipLaunchKernelGGL(k_shade<true>, dim3(blocks), dim3(SBLOCK), 0, s, sc, p, queue, count, hits, sh, alive_mask,
-                           shadow_mask, sp, aov);
-    else
-        hipLaunchKernelGGL(k_shade<false>, dim3(blocks), dim3(SBLOCK), 0, s, sc, p, queue, count, hits, sh, alive_mask,
-                           shadow_mask, sp, aov);
+#define PT_SHADE_CASE(STAGE)                                                                                              \
+    case STAGE:                                                                                                           \
+        (aov ? launch_shade<true, STAGE> : launch_shade<false, STAGE>)(s, blocks, sc, p, queue, count, hits, sh, alive_mask, \
+                                                                       shadow_mask, sp, aov);                             \
+        break;
+    switch (pt_shade_stage(sc.n_mats, sc.n_lights)) {
+        PT_SHADE_CASE(0) PT_SHADE_CASE(PT_STAGE_MATS) PT_SHADE_CASE(PT_STAGE_LIGHTS) PT_SHADE_CASE(PT_STAGE_MATS | PT_STAGE_LIGHTS)
+    }
+#undef PT_SHADE_CASE
 }
 
 #ifndef PT_SHADE_FAST
