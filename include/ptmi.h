@@ -323,6 +323,55 @@ int ptmi_dispatch_adaptive(ptmi_ctx *ctx, const ptmi_camera *camera, const ptmi_
 /* Synchronises. PTMI_E_STATE while the moments plane is off or before ptmi_resize. */
 int ptmi_adaptive_status(ptmi_ctx *ctx, struct ptmi_adaptive_status *out);
 
+/* ---- reprojection: carry the accumulated samples across a camera move (the temporal half of Schied et al. 2017) -------------------
+ * A frame-0 dispatch after a camera move throws away every sample. ptmi_reproject instead rewrites the output buffer, the moments
+ * plane (per-pixel counts included) and the first-hit planes for the camera `to` from what they hold for the camera `from`, so that
+ * ptmi_dispatch_adaptive(to, frame_index != 0) continues every pixel from the count it is left with: a pixel that shows a surface
+ * the old view had seen keeps (a bilinear blend of) its history, a disoccluded pixel is at count 0 and is overwritten by its frame 0.
+ * It needs the NORMAL plane (its w is the mean first-hit distance) and the moments plane (else PTMI_E_STATE); ALBEDO and ID are
+ * carried while on. A post-process like the denoiser: not on the parity path, nothing else changes behaviour unless it is called.
+ * The pass, over the pixels of the context's rows (tile_y0 / tile_y1, tile_parts); rows of other contexts are neither read nor written:
+ *   1. snapshot: device-to-device copies of the output buffer (the caller's, when one is bound), moments, NORMAL and, while on,
+ *      ALBEDO and ID into context-owned history planes (made by the first call since ptmi_resize, all or nothing). The live planes
+ *      are then rewritten in place.
+ *   2. the centre ray of every pixel under `to`: the camera ray of ptmi_dispatch with the jitter replaced by (0.5, 0.5), no lens
+ *      sample and no RNG (aperture is ignored): origin = to.position (ptmi_debug_center_rays returns them).
+ *   3. their closest hits (t, tri), by the traversal kernel of ptmi_dispatch, as ptmi_debug_intersect runs it.
+ *   4. per pixel, all in float32, left to right, no FMA, with the correctly rounded / and sqrt, and dot(a, b) = a.x*b.x + a.y*b.y + a.z*b.z:
+ *      MISS (tri == 0xFFFFFFFF): every live plane of the pixel becomes zero, the ids 0xFFFFFFFF twice, the count 0. Else
+ *        P = o + t d (per component: multiply, then add), v = P - from.position, zf = dot(v, from.forward), dist = sqrt(dot(v, v)),
+ *        th = tan(from.fov * 0.5f) (the kernels' tan: ptmi_debug_math op 11);
+ *        !(zf > 0): DISOCCLUDED. Else sx = dot(v, from.right) / (zf * th * from.aspect), sy = dot(v, from.up) / (zf * th) (from's basis
+ *        is taken as orthonormal), fx = (sx + 1) * 0.5f * W - 0.5f, fy = (sy + 1) * 0.5f * H - 0.5f; fx or fy not finite: DISOCCLUDED.
+ *        x0 = floor(fx), ax = fx - x0, y0 = floor(fy), ay = fy - y0. The four taps (x0 + i, y0 + j) are visited in the order
+ *        (0,0), (1,0), (0,1), (1,1) with weight w = (i ? ax : 1 - ax) * (j ? ay : 1 - ay). A tap q is VALID iff it lies inside the
+ *        image and in a row of this context, its snapshot count n_q = moments.z >= 1, its snapshot depth t_q = normal.w > 0,
+ *        |t_q - dist| <= depth_tolerance * dist, every snapshot float read for it (output xyz, moments xyz, normal xyzw, albedo xyzw
+ *        while on) is finite, and - when ids are compared - its snapshot material id equals triangles[tri].material_index.
+ *        sw = the sum of the valid weights in tap order. No valid tap, or !(sw > 0): DISOCCLUDED: the planes are zeroed as for a
+ *        miss, ids = (tri, material), count 0. Else CARRIED: output xyz, moments xy, albedo xyzw and normal xyz each become
+ *        (sum over the valid taps, in tap order, of w * value) / sw; normal.w = t, ids = (tri, material), output.w = moments.w = 0,
+ *        count = min(min over the valid taps of n_q, max_history) with min(a, b) = a < b ? a : b (an integer, as its inputs are).
+ * After the call the planes are what a render with per-pixel counts leaves. Caveat: with from == to and max_history below a pixel's
+ * count, the pixel traces seeds again that it has already used (frames count .. are those of its earlier samples): reprojection is
+ * for a camera that moved. There is no ptmi_multi counterpart: each context of a ptmi_multi holds only its own strips, and a
+ * reprojected sample would have to come from another device's. */
+typedef struct ptmi_reproject_params {
+    uint32_t max_history;      /* a carried count is capped here; 0 -> 32; <= 2^24 */
+    float    depth_tolerance;  /* relative: a tap is rejected when |t_tap - dist| > depth_tolerance * dist; 0 -> 0.02 */
+    uint32_t match_ids;        /* 0: compare material ids iff the ID plane is on; 1: never; 2: always (ID off -> PTMI_E_STATE) */
+    uint32_t reserved[5];      /* must be 0 */
+} ptmi_reproject_params;       /* 32 bytes */
+/* of the last ptmi_reproject, over the context's rows: carried + disoccluded + missed = their pixels; samples = the sum of the new
+ * counts (all zero before the first call). A struct tag only, like ptmi_adaptive_status */
+struct ptmi_reproject_status { uint64_t carried, disoccluded, missed, samples; };   /* 32 bytes */
+/* Asynchronous on the context's stream. params NULL: the defaults. PTMI_E_STATE: no scene, no output buffer, the NORMAL or the
+ * moments plane off, match_ids = 2 with the ID plane off. PTMI_E_INVALID: from or to NULL, a camera of another size than the
+ * context's, depth_tolerance negative or not finite, max_history > 2^24, match_ids > 2, a non-zero reserved word. A failed call
+ * writes nothing. */
+int ptmi_reproject(ptmi_ctx *ctx, const ptmi_camera *from, const ptmi_camera *to, const ptmi_reproject_params *params);
+int ptmi_reproject_status(ptmi_ctx *ctx, struct ptmi_reproject_status *out);    /* synchronises */
+
 /* ---- presentation (the reference's blit pass, src/shader/blit.wgsl:43-155; renderer.ts:434-449) ---- */
 /* Tone-maps the output buffer (exposure 2^1, AgX, gamma 1/2.2) into a width*height canvas, row 0 = top.
  * dst_rgba_f32 (n_floats must be width*height*4, alpha 1) and/or dst_rgba8 (n_bytes must be width*height*4);
@@ -401,6 +450,9 @@ int ptmi_reset_stats(ptmi_ctx *ctx);
 /* raygen kernel (pt.wgsl:714-750) for explicit (x, y, frame) triples. o3/d3: n*3 floats. */
 int ptmi_debug_raygen(ptmi_ctx *ctx, const ptmi_camera *camera, uint32_t n, const uint32_t *xs,
                       const uint32_t *ys, const uint32_t *frames, float *o3, float *d3, uint32_t *rng);
+/* the centre rays ptmi_reproject traces for `camera` (step 2 there), for the n = width*height pixels of the context's size, index
+ * y*width+x. o3/d3: n*3 floats each, n_floats_each must be n*3 (else, or with a camera of another size: PTMI_E_INVALID). */
+int ptmi_debug_center_rays(ptmi_ctx *ctx, const ptmi_camera *camera, float *o3, float *d3, size_t n_floats_each);
 /* extend kernel (pt.wgsl:248-296) on caller rays: t = -1 / tri = 0xFFFFFFFF on miss. */
 int ptmi_debug_intersect(ptmi_ctx *ctx, uint32_t n, const float *o3, const float *d3,
                          float *t, uint32_t *tri, float *u, float *v);

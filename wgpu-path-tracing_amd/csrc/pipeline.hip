@@ -10,22 +10,28 @@ namespace {
 
 constexpr int BLOCK = 256;
 
-// pt.wgsl:719-750
-PT_DEV void camera_ray(const ptmi_camera &cam, uint32_t x, uint32_t y, uint32_t frame, v3 &org, v3 &dir,
-                       uint32_t &rng) {
-    rng = rng_seed(x, y, frame);
-    float jx = rng_f(rng), jy = rng_f(rng);
-    float px = (float)x + jx, py = (float)y + jy;
+// pt.wgsl:721-733: the pinhole direction through the point (px, py) of the image plane, in pixels
+PT_DEV v3 camera_dir(const ptmi_camera &cam, float px, float py) {
     float uvx = (px / (float)cam.width) * 2.0f - 1.0f;
     float uvy = (py / (float)cam.height) * 2.0f - 1.0f;
     float th = tan1(cam.fov * 0.5f);
     v3 fw = mk3(cam.forward[0], cam.forward[1], cam.forward[2]);
     v3 rt = mk3(cam.right[0], cam.right[1], cam.right[2]);
     v3 up = mk3(cam.up[0], cam.up[1], cam.up[2]);
-    v3 pos = mk3(cam.position[0], cam.position[1], cam.position[2]);
     v3 a = scale3(scale3(scale3(rt, uvx), th), cam.aspect);
     v3 b = scale3(scale3(up, uvy), th);
-    dir = normalize3(add3(add3(fw, a), b));
+    return normalize3(add3(add3(fw, a), b));
+}
+
+// pt.wgsl:719-750
+PT_DEV void camera_ray(const ptmi_camera &cam, uint32_t x, uint32_t y, uint32_t frame, v3 &org, v3 &dir,
+                       uint32_t &rng) {
+    rng = rng_seed(x, y, frame);
+    float jx = rng_f(rng), jy = rng_f(rng);
+    v3 rt = mk3(cam.right[0], cam.right[1], cam.right[2]);
+    v3 up = mk3(cam.up[0], cam.up[1], cam.up[2]);
+    v3 pos = mk3(cam.position[0], cam.position[1], cam.position[2]);
+    dir = camera_dir(cam, (float)x + jx, (float)y + jy);
     org = pos;
     if (cam.aperture > 0.0f) {
         v3 focal = madd3(dir, cam.focus_distance, pos);
@@ -80,6 +86,18 @@ PT_DEV void raygen(const ptmi_camera &cam, const Pixels &px, uint32_t n_frames, 
 __global__ __launch_bounds__(BLOCK) void k_raygen(ptmi_camera cam, DevBand band, uint32_t frame0, uint32_t n_frames,
                                                   DevPaths P, uint32_t *__restrict__ count_out) {
     raygen(cam, DensePixels{band, frame0}, n_frames, P, count_out);
+}
+
+// ptmi_reproject's centre rays: camera_ray with the jitter replaced by (0.5, 0.5), no lens sample, no RNG. Path p is the band-local pixel p.
+__global__ __launch_bounds__(BLOCK) void k_center_rays(ptmi_camera cam, DevBand band, DevPaths P, uint32_t *__restrict__ count_out) {
+    const uint32_t total = band.rows * band.width;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *count_out = total;
+    for (uint32_t p = blockIdx.x * BLOCK + threadIdx.x; p < total; p += gridDim.x * BLOCK) {
+        const uint32_t y = band.row_of(p / band.width), x = p % band.width;
+        const v3 d = camera_dir(cam, (float)x + 0.5f, (float)y + 0.5f);
+        P.O[p] = make_float4(cam.position[0], cam.position[1], cam.position[2], 0.0f);
+        P.D[p] = make_float4(d.x, d.y, d.z, 0.0f);
+    }
 }
 
 __global__ __launch_bounds__(BLOCK) void k_raygen_list(ptmi_camera cam, uint32_t n, const uint32_t *xs,
@@ -343,10 +361,6 @@ PT_DEV bool ad_noisy(float4 m, const ptmi_adaptive_params &ap) {
     const float bound = e * e * n;
     return !(var <= bound);
 }
-PT_DEV bool band_has_row(const DevBand &band, uint32_t y) {
-    if (y < band.y0 || y >= band.y1) return false;
-    return band.parts <= 1u || ((y - band.y0) / band.strip) % band.parts == band.part;
-}
 
 // restart: the band's pixels are back at frame 0 (the folds overwrite at frame 0, so only the count has to go)
 __global__ __launch_bounds__(BLOCK) void k_ad_restart(DevBand band, float4 *__restrict__ mom) {
@@ -370,7 +384,7 @@ __global__ __launch_bounds__(BLOCK) void k_ad_select(DevBand band, ptmi_adaptive
             if (ap.neighbourhood && !active && m.z < (float)ap.max_frames) {
                 for (int dy = -1; dy <= 1 && !active; dy++) {
                     const uint32_t ny = y + (uint32_t)dy;                   // y = 0, dy = -1 wraps and fails has_row
-                    if (!band_has_row(band, ny)) continue;
+                    if (!band.has_row(ny)) continue;
                     for (int dx = -1; dx <= 1; dx++) {
                         const uint32_t nx = x + (uint32_t)dx;
                         if (nx >= band.width || (dx == 0 && dy == 0)) continue;
@@ -557,6 +571,9 @@ void pt_launch_raygen(hipStream_t s, int blocks, const ptmi_camera &cam, DevPixe
         hipLaunchKernelGGL(k_ad_raygen, dim3(blocks), dim3(BLOCK), 0, s, cam, px.band, px.list, px.n_active, n_frames, px.mom, p, count_out,
                            px.traced);
     else hipLaunchKernelGGL(k_raygen, dim3(blocks), dim3(BLOCK), 0, s, cam, px.band, px.frame0, n_frames, p, count_out);
+}
+void pt_launch_center_rays(hipStream_t s, int blocks, const ptmi_camera &cam, DevBand band, DevPaths p, uint32_t *count_out) {
+    hipLaunchKernelGGL(k_center_rays, dim3(blocks), dim3(BLOCK), 0, s, cam, band, p, count_out);
 }
 void pt_launch_raygen_list(hipStream_t s, const ptmi_camera &cam, uint32_t n, const uint32_t *xs,
                            const uint32_t *ys, const uint32_t *frames, DevPaths p) {

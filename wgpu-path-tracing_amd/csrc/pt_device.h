@@ -126,6 +126,11 @@ struct DevBand {
         if (parts <= 1u) return y0 + l;
         return y0 + ((l / strip) * parts + part) * strip + l % strip;
     }
+    // whether frame row y is one of the band's
+    PT_HD bool has_row(uint32_t y) const {
+        if (y < y0 || y >= y1) return false;
+        return parts <= 1u || ((y - y0) / strip) % parts == part;
+    }
     // band-local pixel (local row * width + x) -> its index in the width x height frame
     PT_HD size_t frame_pixel(uint32_t pix) const { return (size_t)row_of(pix / width) * width + pix % width; }
 };
@@ -292,6 +297,21 @@ struct DenoiseArgs {
 };
 void pt_launch_denoise(hipStream_t s, const DenoiseArgs &a, const float4 *radiance, const float4 *normal, const float4 *albedo,
                        const float4 *moments, float4 *guide, float *grad, float4 *cv, float4 *tmp, float4 *out);
+// reprojection (reproject.hip, ptmi_reproject; the contract is stated in include/ptmi.h). The centre rays of the band's pixels under
+// `cam` go to p.O / p.D at the band-local pixel index, *count_out = their number: what `extend` then traces with a null queue.
+void pt_launch_center_rays(hipStream_t s, int blocks, const ptmi_camera &cam, DevBand band, DevPaths p, uint32_t *count_out);
+struct ReprojectArgs {
+    ptmi_camera from;
+    DevBand band;
+    uint32_t max_history, match_ids;    // match_ids: 0 / 1, resolved
+    float depth_tolerance;
+    const float4 *O, *D; const float2 *hits;            // the centre rays of `to` and their closest hits, by band-local pixel
+    const ptmi_triangle *tris; uint32_t n_tris;
+    const float4 *h_out, *h_mom, *h_normal, *h_albedo; const uint2 *h_ids;   // the snapshot (albedo / ids NULL: that plane is off)
+    float4 *out, *mom, *normal, *albedo; uint2 *ids;    // the live planes, rewritten
+    unsigned long long *status;                         // += carried, disoccluded, missed, samples
+};
+void pt_launch_reproject(hipStream_t s, const ReprojectArgs &a);
 void pt_launch_blit(hipStream_t s, int blocks, uint32_t W, uint32_t H, const float4 *color, float4 *out_f32,
                     uint32_t *out_rgba8);
 // a device's rows of the frame <-> a contiguous buffer (ptmi_multi_gather)

@@ -46,6 +46,7 @@ enum FramePlane {
     kDnGuide, kDnGrad, kDnA, kDnB, kDnOut,         // the denoiser's: guide (unit normal, depth), depth gradient, two ping-pong colour +
                                                    // variance planes, the result
     kAdBallot, kAdList, kAdTileSums,               // adaptive sampling: ballot words, pixel list, tile totals
+    kRpOut, kRpMoments, kRpNormal, kRpAlbedo, kRpId,   // reprojection: the snapshot of the output, moments and first-hit planes
     kBlitF32, kBlitU8,                             // canvas staging of ptmi_blit
     kFramePlanes
 };
@@ -114,6 +115,7 @@ struct ptmi_ctx {
     // live for the context's life
     DevAdaptive ad{};
     uint32_t ad_rounds = 0;                            // rounds since the last restart
+    unsigned long long *d_reproject = nullptr;         // ptmi_reproject_status: the four counters of the last ptmi_reproject (made by the first)
 
     unsigned long long *d_stats = nullptr;
 
@@ -712,7 +714,7 @@ constexpr uint32_t kAovAll = PTMI_AOV_ALBEDO | PTMI_AOV_NORMAL | PTMI_AOV_ID;
 
 // One row per FramePlane: its size for px pixels, whether it is zero-filled when made, and when it is made: with the frame (ptmi_resize
 // and the call that turns it on), or by the first call that needs it since the last resize.
-enum PlaneGroup { kWithFrame, kByDenoise, kByAdaptive, kByBlit };
+enum PlaneGroup { kWithFrame, kByDenoise, kByAdaptive, kByReproject, kByBlit };
 template <size_t K> size_t per_pixel(size_t px) { return px * K; }
 size_t ballot_bytes(size_t px) { return (px / 64 + 1) * 8; }
 size_t tile_sum_bytes(size_t px) { return (size_t)pt_adaptive_tiles((uint32_t)px) * 4; }
@@ -725,6 +727,9 @@ const struct { const char *name; size_t (*bytes)(size_t px); bool zeroed; PlaneG
     {"denoised", per_pixel<16>, false, kByDenoise},
     {"adaptive ballot", ballot_bytes, false, kByAdaptive}, {"adaptive list", per_pixel<4>, false, kByAdaptive},
     {"adaptive tile sums", tile_sum_bytes, false, kByAdaptive},
+    {"output history", per_pixel<PTMI_OUTPUT_STRIDE>, false, kByReproject}, {"moments history", per_pixel<16>, false, kByReproject},
+    {"normal history", per_pixel<16>, false, kByReproject}, {"albedo history", per_pixel<16>, false, kByReproject},
+    {"id history", per_pixel<8>, false, kByReproject},
     {"float canvas", per_pixel<16>, false, kByBlit}, {"8-bit canvas", per_pixel<4>, false, kByBlit},
 };
 // sets of planes: a bit per FramePlane
@@ -925,7 +930,7 @@ int ptmi_destroy(ptmi_ctx *c) {
     for (void *&p : c->buf) dfree(p);
     dfree(c->d_atlas);
     drop_planes(c, kAllPlanes);
-    dfree(c->d_stats); dfree(c->d_scene); dfree(c->ad.ctl); dfree(c->ad.acc);
+    dfree(c->d_stats); dfree(c->d_scene); dfree(c->ad.ctl); dfree(c->ad.acc); dfree(c->d_reproject);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
     return PTMI_OK;
@@ -1135,7 +1140,7 @@ int ptmi_resize(ptmi_ctx *c, uint32_t w, uint32_t h) {
         for (void *&p : fresh) dfree(p);
         return fail(c, PTMI_E_HIP, "sync_all failed: %s", hipGetErrorString(e));
     }
-    drop_planes(c, kAllPlanes);                       // the denoiser's, the adaptive and the blit planes come back at their first use
+    drop_planes(c, kAllPlanes);                       // the denoiser's, the adaptive, the history and the blit planes come back at their first use
     std::copy(fresh, fresh + kFramePlanes, c->plane);
     c->W = w; c->H = h;
     c->d_out = plane_as<float4>(c, kOut);
@@ -1390,6 +1395,85 @@ int ptmi_adaptive_status(ptmi_ctx *c, struct ptmi_adaptive_status *out) {
     return PTMI_OK;
 }
 
+// The snapshot is a copy of whole planes (rows of other contexts travel along and are never read); the centre rays and their hits use
+// the batch arrays of a dispatch, like the per-stage entry points. Everything that can fail comes before the first write.
+int ptmi_reproject(ptmi_ctx *c, const ptmi_camera *from, const ptmi_camera *to, const ptmi_reproject_params *params) {
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    if (!from || !to) return fail(c, PTMI_E_INVALID, "a camera is NULL");
+    for (const ptmi_camera *cam : {from, to})
+        if (cam->width != c->W || cam->height != c->H)
+            return fail(c, PTMI_E_INVALID, "a camera says %ux%u but the output buffer is %ux%u", cam->width, cam->height, c->W, c->H);
+    const ptmi_reproject_params zero = {};
+    const ptmi_reproject_params &q = params ? *params : zero;
+    if (!std::isfinite(q.depth_tolerance) || q.depth_tolerance < 0.0f)
+        return fail(c, PTMI_E_INVALID, "depth_tolerance %g is negative or not finite", (double)q.depth_tolerance);
+    if (q.max_history > (1u << 24)) return fail(c, PTMI_E_INVALID, "max_history %u above 2^24", q.max_history);
+    if (q.match_ids > 2u) return fail(c, PTMI_E_INVALID, "unknown match_ids %u", q.match_ids);
+    for (uint32_t r : q.reserved) if (r) return fail(c, PTMI_E_INVALID, "a reserved word of ptmi_reproject_params is not zero");
+    if (!(c->aov_mask & PTMI_AOV_NORMAL) || !c->plane[kAovNormal])
+        return fail(c, PTMI_E_STATE, "reprojection needs the NORMAL plane (ptmi_set_aovs)");
+    if (!c->moments_on || !c->plane[kMoments]) return fail(c, PTMI_E_STATE, "reprojection needs the moments plane (ptmi_set_moments)");
+    const bool have_albedo = (c->aov_mask & PTMI_AOV_ALBEDO) && c->plane[kAovAlbedo];
+    const bool have_ids = (c->aov_mask & PTMI_AOV_ID) && c->plane[kAovId];
+    if (q.match_ids == 2u && !have_ids) return fail(c, PTMI_E_STATE, "match_ids = 2 needs the ID plane (ptmi_set_aovs)");
+    const DevBand band = pt_band_of(c->opt, c->W, c->H);
+    if (band.y0 >= band.y1) return fail(c, PTMI_E_INVALID, "tile rows [%u,%u) outside the %u-row frame", band.y0, band.y1, c->H);
+    if ((band.rows + 3u) / 4u > 65535u) return fail(c, PTMI_E_UNSUPPORTED, "more than 262140 rows");
+    const TraverseConfig cfg0 = traverse_config(c, true);
+    if (c->opt.traversal == PTMI_TRAVERSAL_LDS && pt_variant(cfg0.variant).where != PT_LDS_ALL)
+        return fail(c, PTMI_E_UNSUPPORTED, "scene does not fit in LDS");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t npix = (size_t)c->W * c->H;
+    const uint32_t history = bit(kRpOut) | bit(kRpMoments) | bit(kRpNormal) | (have_albedo ? bit(kRpAlbedo) : 0u) | (have_ids ? bit(kRpId) : 0u);
+    if ((rc = make_planes(c, history, npix, c->plane))) return rc;
+    if (!c->d_reproject) HIP_TRY(c, hipMalloc(&c->d_reproject, 4 * sizeof(unsigned long long)));
+    Lane &ln = c->lane;
+    if (band.rows && (rc = ensure_capacity(c, ln, (size_t)band.rows * band.width))) return rc;
+    if (cfg0.wants_spill && !ln.d_spill) HIP_TRY(c, hipMalloc(&ln.d_spill, pt_spill_bytes(c->n_cu * 8)));
+    const hipStream_t s = c->stream;
+    HIP_TRY(c, hipMemsetAsync(c->d_reproject, 0, 4 * sizeof(unsigned long long), s));
+    if (band.rows == 0) return PTMI_OK;                         // more parts than strips: no pixel of this context's
+    const struct { FramePlane to; const void *from; bool on; } copies[] = {
+        {kRpOut, c->d_out, true}, {kRpMoments, c->plane[kMoments], true}, {kRpNormal, c->plane[kAovNormal], true},
+        {kRpAlbedo, c->plane[kAovAlbedo], have_albedo}, {kRpId, c->plane[kAovId], have_ids}};
+    for (const auto &cp : copies)
+        if (cp.on) HIP_TRY(c, hipMemcpyAsync(c->plane[cp.to], cp.from, kFrame[cp.to].bytes(npix), hipMemcpyDeviceToDevice, s));
+    TraverseConfig cfg = cfg0;
+    cfg.spill = ln.d_spill;
+    const int blocks = c->n_cu * 8;
+    pt_launch_center_rays(s, blocks, *to, band, ln.paths, &ln.counts[0]);
+    (c->sc.own ? pt_launch_extend_own : pt_launch_extend)(s, blocks, cfg, c->sc, ln.paths, nullptr, &ln.counts[0], ln.hits);
+    ReprojectArgs a{};
+    a.from = *from; a.band = band;
+    a.max_history = q.max_history ? q.max_history : 32u;
+    a.depth_tolerance = q.depth_tolerance > 0.0f ? q.depth_tolerance : 0.02f;
+    a.match_ids = q.match_ids == 2u || (q.match_ids == 0u && have_ids) ? 1u : 0u;
+    a.O = ln.paths.O; a.D = ln.paths.D; a.hits = ln.hits;
+    a.tris = c->sc.tris; a.n_tris = c->sc.n_tris;
+    a.h_out = plane_as<float4>(c, kRpOut); a.h_mom = plane_as<float4>(c, kRpMoments); a.h_normal = plane_as<float4>(c, kRpNormal);
+    a.h_albedo = have_albedo ? plane_as<float4>(c, kRpAlbedo) : nullptr; a.h_ids = have_ids ? plane_as<uint2>(c, kRpId) : nullptr;
+    a.out = c->d_out; a.mom = plane_as<float4>(c, kMoments); a.normal = plane_as<float4>(c, kAovNormal);
+    a.albedo = have_albedo ? plane_as<float4>(c, kAovAlbedo) : nullptr; a.ids = have_ids ? plane_as<uint2>(c, kAovId) : nullptr;
+    a.status = c->d_reproject;
+    pt_launch_reproject(s, a);
+    HIP_TRY(c, hipGetLastError());
+    return PTMI_OK;
+}
+
+int ptmi_reproject_status(ptmi_ctx *c, struct ptmi_reproject_status *out) {
+    if (!c || !out) return PTMI_E_INVALID;
+    std::memset(out, 0, sizeof *out);
+    if (!c->d_reproject) return PTMI_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, sync_all(c));
+    drain_events(c);
+    unsigned long long h[4];
+    HIP_TRY(c, hipMemcpy(h, c->d_reproject, sizeof h, hipMemcpyDeviceToHost));
+    out->carried = h[0]; out->disoccluded = h[1]; out->missed = h[2]; out->samples = h[3];
+    return PTMI_OK;
+}
+
 int ptmi_throttle(ptmi_ctx *c, uint32_t max_in_flight, uint32_t *in_flight) {
     if (!c) return PTMI_E_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1639,6 +1723,32 @@ int ptmi_debug_raygen(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n, const uin
         o3[3 * i] = o[i].x; o3[3 * i + 1] = o[i].y; o3[3 * i + 2] = o[i].z;
         d3[3 * i] = d[i].x; d3[3 * i + 1] = d[i].y; d3[3 * i + 2] = d[i].z;
         if (rng) std::memcpy(&rng[i], &o[i].w, 4);
+    }
+    return PTMI_OK;
+}
+
+int ptmi_debug_center_rays(ptmi_ctx *c, const ptmi_camera *cam, float *o3, float *d3, size_t n_floats_each) {
+    if (!c) return PTMI_E_INVALID;
+    if (!cam || !o3 || !d3) return fail(c, PTMI_E_INVALID, "NULL argument");
+    if (c->W == 0 || c->H == 0) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
+    if (cam->width != c->W || cam->height != c->H)
+        return fail(c, PTMI_E_INVALID, "camera says %ux%u but the output buffer is %ux%u", cam->width, cam->height, c->W, c->H);
+    const size_t n = (size_t)c->W * c->H;
+    if (n_floats_each != n * 3) return fail(c, PTMI_E_INVALID, "expected %zu floats each, got %zu", n * 3, n_floats_each);
+    HIP_TRY(c, hipSetDevice(c->device));
+    Lane &ln = c->lane;                              // the per-stage entry points run on the context's stream
+    HIP_TRY(c, sync_all(c));
+    int rc = ensure_capacity(c, ln, n);
+    if (rc) return rc;
+    const DevBand whole{c->W, c->H, 0u, c->H, 1u, 1u, 0u, c->H};
+    pt_launch_center_rays(c->stream, c->n_cu * 8, *cam, whole, ln.paths, &ln.counts[0]);
+    std::vector<float4> o(n), d(n);
+    HIP_TRY(c, hipMemcpyAsync(o.data(), ln.paths.O, n * 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d.data(), ln.paths.D, n * 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, sync_all(c));
+    for (size_t i = 0; i < n; i++) {
+        o3[3 * i] = o[i].x; o3[3 * i + 1] = o[i].y; o3[3 * i + 2] = o[i].z;
+        d3[3 * i] = d[i].x; d3[3 * i + 1] = d[i].y; d3[3 * i + 2] = d[i].z;
     }
     return PTMI_OK;
 }

@@ -476,6 +476,46 @@ static napi_value js_adaptive_status(napi_env env, napi_callback_info info) {
     return o;
 }
 
+/* reproject(h, fromCameraBytes, toCameraBytes, {maxHistory, depthTolerance, matchIds} or null): ptmi_reproject */
+static napi_value js_reproject(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    handle *h = get_single_handle(env, info, 4, argv, "reproject");
+    if (!h) return NULL;
+    ptmi_camera cams[2];
+    for (int k = 0; k < 2; k++) {
+        void *p; size_t n;
+        if (!get_bytes(env, argv[1 + k], &p, &n)) return NULL;
+        if (!p || n != sizeof(ptmi_camera)) { napi_throw_range_error(env, NULL, "camera blob must be 96 bytes"); return NULL; }
+        memcpy(&cams[k], p, sizeof cams[k]);
+    }
+    ptmi_reproject_params prm;
+    memset(&prm, 0, sizeof prm);
+    napi_valuetype t;
+    if (napi_typeof(env, argv[3], &t) == napi_ok && t == napi_object) {
+        prm.max_history = get_u32_prop(env, argv[3], "maxHistory", 0);
+        prm.depth_tolerance = get_f32_prop(env, argv[3], "depthTolerance", 0.0f);
+        prm.match_ids = get_u32_prop(env, argv[3], "matchIds", 0);
+    }
+    int rc = ptmi_reproject(h->ctx, &cams[0], &cams[1], &prm);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_reproject");
+    return NULL;
+}
+
+/* reprojectStatus(h) -> {carried, disoccluded, missed, samples} of the last reproject(); synchronises */
+static napi_value js_reproject_status(napi_env env, napi_callback_info info) {
+    napi_value argv[1];
+    handle *h = get_single_handle(env, info, 1, argv, "reprojectStatus");
+    if (!h) return NULL;
+    struct ptmi_reproject_status s;
+    int rc = ptmi_reproject_status(h->ctx, &s);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_reproject_status");
+    napi_value o;
+    NAPI_OK(env, napi_create_object(env, &o));
+    set_num(env, o, "carried", (double)s.carried); set_num(env, o, "disoccluded", (double)s.disoccluded);
+    set_num(env, o, "missed", (double)s.missed); set_num(env, o, "samples", (double)s.samples);
+    return o;
+}
+
 /* readMoments(h, Float32Array dst of width*height*4): the sample-moments plane */
 static napi_value js_read_moments(napi_env env, napi_callback_info info) {
     napi_value argv[2];
@@ -616,6 +656,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"blit", js_blit}, {"getStats", js_get_stats}, {"resetStats", js_reset_stats},
         {"setMoments", js_set_moments}, {"denoise", js_denoise}, {"blitDenoised", js_blit_denoised},
         {"dispatchAdaptive", js_dispatch_adaptive}, {"adaptiveStatus", js_adaptive_status}, {"readMoments", js_read_moments},
+        {"reproject", js_reproject}, {"reprojectStatus", js_reproject_status},
         {"buildBvh", js_build_bvh}, {"emissiveLights", js_emissive_lights},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

@@ -84,6 +84,12 @@ export class Renderer {
   /** `rounds` adaptive rounds now (frameIndex 0 restarts) */
   renderAdaptive(rounds?: number): void;
   adaptiveStatus(): { active: number; samples: number; minCount: number; maxCount: number; rounds: number };
+  /** reprojection on (params, {} for the defaults) or off (null): while on and adaptive sampling is set, a camera change no longer
+   *  restarts the accumulation: the next adaptive round is preceded by reproject(previous camera, current camera) and continues
+   *  from the per-pixel counts that leaves (include/ptmi.h ptmi_reproject). Turns the 'normal' plane on; throws with several devices */
+  setReproject(params: ReprojectParams | null): void;
+  /** of the last reprojection (include/ptmi.h ptmi_reproject_status); synchronises */
+  reprojectStatus(): { carried: number; disoccluded: number; missed: number; samples: number };
   /** per-pixel sample counts (the moments plane's z), width*height, row 0 = image bottom */
   sampleCounts(): Float32Array;
   /** the denoised output buffer (include/ptmi.h ptmi_denoise): width*height float4 (rgb, 0), row 0 = image bottom */
@@ -97,6 +103,8 @@ export class Renderer {
 export interface AdaptiveParams {
   threshold: number; floor?: number; minFrames?: number; maxFrames?: number; step?: number; neighbourhood?: 0 | 1;
 }
+/** 0 or absent: the default (include/ptmi.h ptmi_reproject_params) */
+export interface ReprojectParams { maxHistory?: number; depthTolerance?: number; matchIds?: 0 | 1 | 2 }
 /** 0 or absent: the default (include/ptmi.h ptmi_denoise_params) */
 export interface DenoiseParams {
   iterations?: number; demodulate?: 0 | 1 | 2; phiColor?: number; phiNormal?: number; phiDepth?: number;

@@ -57,6 +57,9 @@ function Renderer(options) {
   if (options.options) this.addon.setOptions(this.ctx, options.options);
   this.adaptive = null;
   this.adaptiveActive = -1;                 // pixels the last adaptive round listed (-1: none issued since the last reset)
+  this.reproject = null;                    // setReproject: the parameters, while camera changes carry the accumulated samples over
+  this.accumulatedUnder = null;             // the camera bytes of the last adaptive round: what the planes were accumulated under
+  this.reprojectFrom = null;                // ... kept here while a camera change waits for the next round to reproject
   if (options.adaptive) this.setAdaptive(options.adaptive);
 }
 
@@ -100,9 +103,11 @@ Renderer.prototype.loadModel = function (model, atlas) {
   });
 };
 
-/** renderer.ts:357-366 */
-Renderer.prototype.resetOutputBuffer = function (restart) {
-  this.frameIndex = 0;
+/** renderer.ts:357-366. cameraMoved: the reset follows a camera change and nothing else; with setReproject and adaptive rounds
+ *  accumulated, the samples then stay, for the next round to reproject from the camera they were accumulated under. */
+Renderer.prototype.resetOutputBuffer = function (restart, cameraMoved) {
+  this.reprojectFrom = cameraMoved && this.reproject && this.adaptive && this.frameIndex > 0 ? this.accumulatedUnder : null;
+  if (!this.reprojectFrom) this.frameIndex = 0;
   this.camera.frameIndex = 0;
   this.framesPerTick = 1;                   // the picture changed: back to one frame per tick, for the shortest latency
   this.adaptiveActive = -1;
@@ -181,6 +186,7 @@ Renderer.prototype.resize = function (width, height) {
   this.width = width; this.height = height;
   this.camera.aspect = width / height;
   this.camera.width = width; this.camera.height = height;
+  this.reprojectFrom = null;                // the planes of the new size are empty
   this.frameIndex = 0;
   this.framesPerTick = 1;
   this.addon.resize(this.ctx, width, height);
@@ -190,7 +196,7 @@ Renderer.prototype.resize = function (width, height) {
 Renderer.prototype.moveCamera = function (forward, right, up) {
   var c = this.camera;
   for (var k = 0; k < 3; k++) c.position[k] += right * c.right[k] + forward * c.forward[k] + up * c.up[k];
-  this.resetOutputBuffer();
+  this.resetOutputBuffer(undefined, true);
 };
 
 function normalize(v) { var l = Math.sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); return [v[0] / l, v[1] / l, v[2] / l]; }
@@ -210,7 +216,7 @@ Renderer.prototype.rotateCamera = function (yaw, pitch) {
   c.forward = normalize([cy * v1[0] + sy * v1[2], v1[1], -sy * v1[0] + cy * v1[2]]);
   c.right = normalize(cross(c.forward, [0, 1, 0]));
   c.up = normalize(cross(c.right, c.forward));
-  this.resetOutputBuffer();
+  this.resetOutputBuffer(undefined, true);
 };
 
 /** Output buffer (binding 0): width*height float4, row 0 = image bottom. Synchronises. */
@@ -269,7 +275,7 @@ Renderer.prototype.pick = function (x, y) {
  *  until the next frame 0. One device only. */
 Renderer.prototype.setDenoise = function (on) {
   if (this.multi) throw new Error('setDenoise: the denoiser is not supported with several devices');
-  var mask = ((this.aovMask || 0) & 4) | (on ? 3 : 0);
+  var mask = ((this.aovMask || 0) & 4) | (on ? 3 : 0) | (this.reproject ? 2 : 0);      // reprojection keeps the 'normal' plane it reads
   this.addon.setAovs(this.ctx, mask);
   this.aovMask = mask;
   if (on || !this.adaptive) this.addon.setMoments(this.ctx, !!on);      // adaptive sampling keeps the moments plane it counts in
@@ -308,9 +314,30 @@ Renderer.prototype.renderAdaptive = function (rounds) {
   if (!this.adaptive) throw new Error('renderAdaptive: setAdaptive first');
   rounds = rounds || 1;
   this.updateCamera();
+  if (this.reprojectFrom) {                 // the camera moved since the last round: carry the samples over, then continue
+    this.addon.reproject(this.ctx, this.reprojectFrom, this.cameraBytes, this.reproject);
+    this.reprojectFrom = null;
+  }
   this.addon.dispatchAdaptive(this.ctx, this.cameraBytes, this.adaptive, rounds);
+  this.accumulatedUnder = this.reproject ? this.cameraBytes.slice(0) : null;
   this.frameIndex += rounds;
 };
+/** Reprojection (include/ptmi.h ptmi_reproject): params = { maxHistory, depthTolerance, matchIds } (0 or absent: the default; {} for
+ *  all defaults), or null to go back to restarting on every camera change. While set and adaptive sampling is on, moveCamera /
+ *  rotateCamera keep the accumulated samples: the next adaptive round is preceded by reproject(previous camera, current camera) and
+ *  continues from the per-pixel counts that leaves. Turns the 'normal' plane on (the pass reads its depth); it stays on afterwards. */
+Renderer.prototype.setReproject = function (params) {
+  if (this.multi) throw new Error('setReproject: reprojection is not supported with several devices');
+  if (params && !((this.aovMask || 0) & 2)) {
+    this.addon.setAovs(this.ctx, (this.aovMask || 0) | 2);
+    this.aovMask = (this.aovMask || 0) | 2;
+    this.resetOutputBuffer(false);          // a plane turned on mid-accumulation holds zeros until the next frame 0
+  }
+  this.reproject = params || null;
+  if (!params && this.reprojectFrom) this.resetOutputBuffer(false);    // a pending camera change restarts after all
+};
+/** { carried, disoccluded, missed, samples } of the last reprojection (include/ptmi.h ptmi_reproject_status); synchronises */
+Renderer.prototype.reprojectStatus = function () { return this.addon.reprojectStatus(this.ctx); };
 /** { active, samples, minCount, maxCount, rounds } (include/ptmi.h ptmi_adaptive_status); synchronises */
 Renderer.prototype.adaptiveStatus = function () { return this.addon.adaptiveStatus(this.ctx); };
 /** per-pixel sample counts (the moments plane's z): width*height floats, row 0 = image bottom like readOutput */

@@ -33,6 +33,7 @@ EXPORTS = [
     "ptmi_set_moments", "ptmi_get_moments", "ptmi_read_moments", "ptmi_moments_device_ptr",
     "ptmi_denoise", "ptmi_denoised_device_ptr", "ptmi_blit_denoised",
     "ptmi_dispatch_adaptive", "ptmi_adaptive_status",
+    "ptmi_reproject", "ptmi_reproject_status", "ptmi_debug_center_rays",
 ]
 MULTI_LOOPBACK = 1
 # first-hit planes (include/ptmi.h ptmi_set_aovs): name -> (bit, numpy dtype, channels)
@@ -76,6 +77,20 @@ class AdaptiveStatus(ctypes.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+class ReprojectParams(ctypes.Structure):
+    """ptmi_reproject_params; 0 picks a field's default (include/ptmi.h)"""
+    _fields_ = [("max_history", ctypes.c_uint32), ("depth_tolerance", ctypes.c_float), ("match_ids", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 5)]
+
+
+class ReprojectStatus(ctypes.Structure):
+    _fields_ = [("carried", ctypes.c_uint64), ("disoccluded", ctypes.c_uint64), ("missed", ctypes.c_uint64),
+                ("samples", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
 class Stats(ctypes.Structure):
@@ -164,6 +179,9 @@ def load():
         L.ptmi_blit_denoised.argtypes = [vp, vp, sz, vp, sz]
         L.ptmi_dispatch_adaptive.argtypes = [vp, vp, vp, u32]
         L.ptmi_adaptive_status.argtypes = [vp, vp]
+        L.ptmi_reproject.argtypes = [vp, vp, vp, vp]
+        L.ptmi_reproject_status.argtypes = [vp, vp]
+        L.ptmi_debug_center_rays.argtypes = [vp, vp, vp, vp, sz]
         _lib = L
     return _lib
 
@@ -437,6 +455,26 @@ class Context(_Handle):
         st = AdaptiveStatus()
         self._ck(self.L.ptmi_adaptive_status(self.h, ctypes.byref(st)))
         return st
+
+    # -- reprojection (include/ptmi.h ptmi_reproject) -----------------------------------------------------------
+    def reproject(self, from_cam, to_cam, max_history=0, depth_tolerance=0.0, match_ids=0, reserved=(0, 0, 0, 0, 0)):
+        """rewrites the output buffer, the moments plane and the first-hit planes for to_cam from what they hold for from_cam; needs
+        the 'normal' plane and set_moments(). 0 picks a parameter's default. Asynchronous."""
+        assert from_cam.dtype == layout.CAMERA and to_cam.dtype == layout.CAMERA
+        prm = ReprojectParams(max_history, depth_tolerance, match_ids, (ctypes.c_uint32 * 5)(*reserved))
+        self._ck(self.L.ptmi_reproject(self.h, _p(from_cam), _p(to_cam), ctypes.byref(prm)))
+
+    def reproject_status(self):
+        st = ReprojectStatus()
+        self._ck(self.L.ptmi_reproject_status(self.h, ctypes.byref(st)))
+        return st
+
+    def debug_center_rays(self, camera):
+        """the centre rays reproject() traces for `camera`: origins and directions, (H * W, 3) float32 each, index y * W + x"""
+        n = self.width * self.height
+        o, d = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+        self._ck(self.L.ptmi_debug_center_rays(self.h, _p(camera), _p(o), _p(d), o.size))
+        return o, d
 
     def read_image(self):
         """The traversal image the last upload_scene put on the device (include/ptmi.h: ptmi_debug_read_image), as build_image()
