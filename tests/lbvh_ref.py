@@ -7,7 +7,7 @@ sorted unique keys is unique, inner boxes are exact minima / maxima, the host re
 compiled without contraction or fast-math, so numpy's float32 arithmetic restates its float32 arithmetic operation for operation.
 
 What is restated from the code, and what is deliberately done another way:
-  leaves   as build_image (csrc/ptmi_api.hip) collects them: the reachable reference nodes with triangle_count > 0 in node-array order
+  leaves   as build_image (csrc/scene_image.hip) collects them: the reachable reference nodes with triangle_count > 0 in node-array order
   keys     the host prologue of pt_build_fast_tree_gpu and k_morton, same float32 operations in the same order; the 10 -> 30 bit spread
            is a bit-by-bit loop here, not the multiply-and-mask of expand10
   tree     NOT Karras' per-node search: top-down, a range of sorted keys splits where the highest bit in which its first and last key
@@ -21,7 +21,7 @@ import numpy as np
 from ptmi import layout, scene_host, scenes
 
 # csrc/pt_device.h, copied by value: PT_REF_LEAF, PT_LEAF_OFF_BITS, PT_LEAF_MAX_TRIS (a leaf reference is
-# PT_REF_LEAF | (count - 1) << PT_LEAF_OFF_BITS | first triangle: leaf_ref, csrc/ptmi_api.hip)
+# PT_REF_LEAF | (count - 1) << PT_LEAF_OFF_BITS | first triangle: leaf_ref, csrc/scene_image.hip)
 REF_LEAF = 0x80000000
 LEAF_OFF_BITS = 26
 LEAF_MAX_TRIS = 32

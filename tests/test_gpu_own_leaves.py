@@ -36,7 +36,7 @@ def own_ctx(gpu_ctx):
 
 def force(kind, code):
     """PTMI_OWN_EXTEND / PTMI_OWN_SHADOW = variant + 10 for two workgroups per CU, 20 for the compact-reference variant
-    (csrc/ptmi_api.hip own_config)"""
+    (csrc/traverse_pick.hip traverse_config)"""
     os.environ["PTMI_OWN_EXTEND" if kind == "extend" else "PTMI_OWN_SHADOW"] = {102: "20", 112: "21"}.get(code) or str(code // 10 + (10 if code % 10 == 2 else 0))
 
 

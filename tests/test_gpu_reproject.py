@@ -186,7 +186,12 @@ def test_everything_disoccluded_then_a_round_equals_a_fresh_render(ctx, scene_fa
     to = MOVES["sideways"]
     fresh = rendered(ctx, sc, cam=to, frames=4)
     rendered(ctx, sc)
+    ran = ctx.stats()
+    ctx.set_options(traversal=native.TRAVERSAL_GLOBAL_EXACT)        # the centre rays are traced by another variant than the dispatch ran
     ctx.reproject(away(BASE), to)
+    ctx.set_options(traversal=native.TRAVERSAL_AUTO)
+    after = ctx.stats()                                              # ... and the statistics still name the dispatch's
+    assert (after.extend_variant, after.shadow_variant) == (ran.extend_variant, ran.shadow_variant) and ran.extend_variant // 10 not in (1, 9)
     st = ctx.reproject_status().as_dict()
     assert st["carried"] == 0 and st["samples"] == 0 and st["disoccluded"] > 0 and st["missed"] > 0
     assert st["disoccluded"] + st["missed"] == W * H

@@ -1,0 +1,422 @@
+// dispatch.hip — the wavefront dispatch loop behind ptmi_dispatch and ptmi_dispatch_adaptive, ptmi_reproject, and what they leave for
+// later calls to pick up: event pairs that become the timing statistics, and the dispatches in flight that ptmi_throttle bounds.
+//
+// Replaces the reference's dispatch (src/renderer/renderer.ts: updateCamera + dispatch :403-431).
+#include "ptmi_ctx.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <utility>
+#include <vector>
+
+namespace {
+
+constexpr size_t kMaxPendingEvents = 4096;        // a caller that never synchronises (a preview loop) must not grow the list without bound
+constexpr size_t kMaxDispatchesInFlight = 256;     // a caller that never throttles or synchronises still cannot queue without bound
+constexpr int kShadowCount = 72;          // slot of the shadow-queue length in ctx->counts (80 words)
+
+// the statistics an event pair of each kind adds to: its time, and where there is one its launch count
+const struct { double ptmi_stats::*ms; uint64_t ptmi_stats::*launches; } kEventStat[kEventKinds] = {
+    {&ptmi_stats::gpu_ms, nullptr},                                  // kDispatch
+    {&ptmi_stats::extend_ms, &ptmi_stats::extend_launches},          // kExtend
+    {&ptmi_stats::shade_ms, &ptmi_stats::shade_launches},            // kShade
+    {&ptmi_stats::shadow_ms, &ptmi_stats::shadow_launches},          // kShadow
+    {&ptmi_stats::raygen_ms, nullptr},                               // kRaygen
+    {&ptmi_stats::compact_ms, nullptr},                              // kCompact
+    {&ptmi_stats::accumulate_ms, nullptr},                           // kAccumulate
+};
+
+hipEvent_t get_event(ptmi_ctx *c) {
+    if (!c->event_pool.empty()) { hipEvent_t e = c->event_pool.back(); c->event_pool.pop_back(); return e; }
+    hipEvent_t e = nullptr; (void)hipEventCreate(&e); return e;
+}
+
+}  // namespace
+
+PT_HOST {
+
+// resolve finished event pairs into the statistics (stream must be synchronised)
+void drain_events(ptmi_ctx *c) {
+    for (auto &p : c->pending) {
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
+            c->st.*kEventStat[p.kind].ms += ms;
+            if (kEventStat[p.kind].launches) (c->st.*kEventStat[p.kind].launches)++;
+        }
+        c->event_pool.push_back(p.a); c->event_pool.push_back(p.b);
+    }
+    c->pending.clear();
+}
+
+// wait for everything in flight, then resolve its event pairs: what a call does before it reads what dispatches wrote
+hipError_t quiesce(ptmi_ctx *c) {
+    const hipError_t e = sync_all(c);
+    if (e == hipSuccess) drain_events(c);
+    return e;
+}
+
+}  // namespace pt_host
+
+namespace {
+
+// without a synchronisation: resolve the pairs at the front of the list whose closing event has completed
+void drain_completed_events(ptmi_ctx *c) {
+    size_t n = 0;
+    while (n < c->pending.size() && hipEventQuery(c->pending[n].b) == hipSuccess) n++;
+    if (n == 0) return;
+    std::vector<EventPair> rest(c->pending.begin() + n, c->pending.end());
+    c->pending.resize(n);
+    drain_events(c);
+    c->pending = std::move(rest);
+}
+
+// drop the finished dispatches from the front of the list, then wait for the oldest ones until at most `max` are left
+hipError_t throttle(ptmi_ctx *c, size_t max) {
+    while (!c->in_flight.empty() && hipEventQuery(c->in_flight.front()) == hipSuccess) {
+        c->event_pool.push_back(c->in_flight.front()); c->in_flight.pop_front();
+    }
+    (void)hipGetLastError();                          // hipErrorNotReady of the query is not an error
+    while (c->in_flight.size() > max) {
+        hipError_t e = hipEventSynchronize(c->in_flight.front());
+        if (e != hipSuccess) return e;
+        c->event_pool.push_back(c->in_flight.front()); c->in_flight.pop_front();
+    }
+    return hipSuccess;
+}
+
+struct Timed {
+    ptmi_ctx *c; hipEvent_t a = nullptr, b = nullptr; EventKind kind; bool on;
+    hipStream_t st;
+    Timed(ptmi_ctx *c_, EventKind kind_, bool on_, hipStream_t st_ = nullptr) : c(c_), kind(kind_), on(on_), st(st_ ? st_ : c_->stream) {
+        if (on) { a = get_event(c); b = get_event(c); (void)hipEventRecord(a, st); }
+    }
+    ~Timed() {
+        if (!on) return;
+        (void)hipEventRecord(b, st);
+        c->pending.push_back({a, b, kind});
+        if (c->pending.size() > kMaxPendingEvents) drain_completed_events(c);
+    }
+};
+
+// the control words live for the context's life (ptmi_get_stats reads acc[0]); the planes follow the output buffer's size
+int adaptive_words(ptmi_ctx *c) {
+    if (!c->ad.ctl) {
+        HIP_TRY(c, hipMalloc(&c->ad.ctl, 4 * sizeof(uint32_t)));
+        HIP_TRY(c, hipMemset(c->ad.ctl, 0, 4 * sizeof(uint32_t)));
+    }
+    if (!c->ad.acc) {
+        HIP_TRY(c, hipMalloc(&c->ad.acc, 4 * sizeof(unsigned long long)));
+        HIP_TRY(c, hipMemset(c->ad.acc, 0, 4 * sizeof(unsigned long long)));
+    }
+    return PTMI_OK;
+}
+
+#ifndef PT_REPACK
+#define PT_REPACK 1          /* A/B switch: 0 leaves the path state at the path id for every bounce (no tail arrays in use) */
+#endif
+
+// ptmi_dispatch (ap NULL: n_frames frames of every pixel of the band, from cam->frame_index) and ptmi_dispatch_adaptive (ap: `rounds`
+// rounds of ap->step frames for the listed pixels, each from its own count). Both run the same bounce loop per batch; they differ in
+// the raygen in front of it and the folds behind it.
+int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_adaptive_params *ap, uint32_t rounds) {
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    if (!cam) return fail(c, PTMI_E_INVALID, "camera is NULL");
+    if (cam->width != c->W || cam->height != c->H)
+        return fail(c, PTMI_E_INVALID, "camera says %ux%u but the output buffer is %ux%u", cam->width, cam->height, c->W, c->H);
+    if (n_frames == 0 || (ap && rounds == 0)) return PTMI_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (ap && ((rc = adaptive_words(c)) || (rc = make_planes(c, group_set(kByAdaptive), (size_t)c->W * c->H, c->plane)))) return rc;
+    const DevBand band = pt_band_of(c->opt, c->W, c->H);
+    if (band.y0 >= band.y1) return fail(c, PTMI_E_INVALID, "tile rows [%u,%u) outside the %u-row frame", band.y0, band.y1, c->H);
+    if (band.rows == 0) return PTMI_OK;                         // more parts than strips: nothing to render here
+    const uint64_t npix = (uint64_t)band.rows * band.width;
+    uint32_t F = c->opt.frames_per_batch;
+    // ~128 Mi paths, ~23 GB of state: the last bounces' small queues cost a fixed ~3 ms per batch, so fewer, larger batches
+    // (measured at 1080p, Msamples/s: 32 frames 8 920, 64 frames 9 150 - 9 275, 128 frames 9 270 - 9 310)
+    const bool auto_F = F == 0;
+    Lane &ln = c->lane;
+    if (auto_F) {
+        F = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(64, (128ull << 20) / npix));
+        // ... but never more than the device has room for: several contexts may share one device (ranks rehearsed on one GPU, a
+        // Node host beside another process), and eight ranks of one node each size their batch by what THEIR device has free.
+        // Room = free memory + what this context already holds, less a tenth for the rest (spill areas, blit staging).
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            const uint64_t held = (uint64_t)ln.cap * bytes_per_path(ln.aov != nullptr);
+            const uint64_t room = (uint64_t)((double)(free_b + held) * 0.9);
+            F = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(F, room / (npix * bytes_per_path(c->aov_mask != 0))));
+        }
+    }
+    F = std::min(F, n_frames);
+    const bool nee = c->opt.do_mis && c->sc.n_lights > 0;
+    // overlap: `shadow` of bounce b on a side stream, beside extend / shade of bounce b + 1. It is then the only kernel that
+    // adds to L (emissive hits leave a record too, ShadeParams::emit_records), bounce after bounce on one stream, so every
+    // path's sum is formed in the same order as without it. Record buffers alternate by bounce parity; shade(b) waits for
+    // shadow(b - 2), the end of the batch for the last one.
+    const bool side = nee && c->opt.overlap != 0;
+    if (npix * F > 0xFFFFFF00ull) return fail(c, PTMI_E_UNSUPPORTED, "batch of %llu paths exceeds 2^32", (unsigned long long)(npix * F));
+    TraverseConfig cfg, cfg_shadow;
+    if ((rc = traverse_pick(c, true, cfg)) || (rc = traverse_pick(c, false, cfg_shadow))) return rc;      // refused before anything is made
+    for (;;) {
+        rc = ensure_capacity(c, ln, (size_t)(npix * F));
+        if (rc == PTMI_OK) break;
+        // out of device memory with a batch size the library chose: halve it and try again (hipMemGetInfo is a snapshot; another
+        // context may have allocated since). A size the caller asked for fails loudly.
+        if (!auto_F || !c->alloc_oom || F <= 1) return rc;
+        F = (F + 1) / 2;
+    }
+    if ((rc = traverse_arm(c, true, kSpillMain, cfg, true)) || (rc = traverse_arm(c, false, side ? kSpillSide : kSpillAfterExtend, cfg_shadow, true)))
+        return rc;
+    c->st.traversal_used = pt_variant(cfg.variant).where == PT_FROM_MEMORY ? PTMI_TRAVERSAL_GLOBAL : PTMI_TRAVERSAL_LDS;
+    c->st.frames_per_batch_used = F;
+    c->st.radiance_stride_bytes = (walks_memory_quantised(cfg) || walks_memory_quantised(cfg_shadow)) ? 16u : 12u;
+    c->st.shade_tables = PT_SHADE_LDS_BUDGET | ((uint32_t)pt_shade_stage(c->sc.n_mats, c->sc.n_lights) << 28);
+    const int blocks = c->n_cu * 8;
+#ifndef PT_SHADE_WGS_PER_CU
+#define PT_SHADE_WGS_PER_CU 16
+#endif
+    // 256-thread workgroups of the grid-stride shade kernel. Config 1, five interleaved runs each (Msamples/s): 8 per CU 9 247,
+    // 16: 9 362, 32: 9 303, 64: 8 929 (run-to-run +-130); config 3 +-0.
+    const int shade_blocks = c->n_cu * PT_SHADE_WGS_PER_CU;
+    const uint32_t maxb = c->opt.max_bounces;
+    const bool t1 = c->opt.timing >= 1, t2 = c->opt.timing >= 2, t3 = c->opt.timing >= 3;
+    {
+        Timed td(c, kDispatch, t1);
+        const hipStream_t ms = c->stream;                                         // the bounce loop's stream
+        const hipStream_t ss = side ? ln.side : ms;                               // ... and the shadow kernels'
+        const int tiles = (int)(ln.cap / pt_compact_tile_slots() + 1);
+        ln.paths.l_stride = c->st.radiance_stride_bytes / 4u;
+        const DevPaths bp = ln.paths;
+        // Once per batch, after the compaction of the first bounce that plays roulette, the survivors' O / D / C are gathered into the
+        // tail arrays at their queue positions: from then on a few percent of the paths are alive, and state left at the path id costs
+        // them a line per lane in each stream. From the next bounce on, extend and shade find the state at the slot the queue names
+        // and shade writes it back there; the radiance and the records keep the path id (ln.pid).
+        const uint32_t rb = PT_REPACK ? pt_repack_bounce() : 0xFFFFFFFEu;
+        DevPaths tp = ln.tail;
+        tp.L = bp.L; tp.l_stride = bp.l_stride;
+        float4 *const aov_rec = c->aov_mask ? ln.aov : nullptr;         // written by shade(0), read by the fold after the last bounce
+        float4 *const mom = plane_as<float4>(c, kMoments);
+        if (ap && cam->frame_index == 0u) { pt_launch_adaptive_restart(ms, blocks, band, mom); c->ad_rounds = 0; }
+        // a batch: fb frames of every pixel from frame0 on, or (ap) of every listed pixel from its own count on
+        auto batch = [&](uint32_t frame0, uint32_t fb) -> int {
+            const DevPixels px = ap ? DevPixels{band, 0u, c->ad.list, &c->ad.ctl[1], mom, c->ad.acc}
+                                    : DevPixels{band, frame0, nullptr, nullptr, nullptr, nullptr};
+            { Timed t(c, kRaygen, t3, ms); pt_launch_raygen(ms, blocks, *cam, px, fb, bp, &ln.counts[0]); }
+            int cur = 0;
+            for (uint32_t b = 0; b < maxb; b++) {
+                const bool tail = b > rb;                                   // the state is in the tail arrays
+                const uint32_t *q = b == 0 || b == rb + 1 ? nullptr : ln.queue[cur];   // bounce 0 / after the repack: slot i holds path / state i
+                const DevPaths sp = tail ? tp : bp;
+                const int par = side ? (int)(b & 1u) : 0;
+                const ShadeParams shp{b, maxb, c->opt.do_mis, c->d_stats, side ? 1u : 0u, tail ? ln.pid : nullptr};
+                { Timed t(c, kExtend, t2, ms); launch_extend(c, ms, cfg, sp, q, &ln.counts[b], ln.hits); }
+                const bool last = b + 1 == maxb;
+                if (side && b >= 2) HIP_TRY(c, hipStreamWaitEvent(ms, ln.ev_shadow[par], 0));      // its records are read
+                { Timed t(c, kShade, t3, ms);
+                  (c->opt.perf_mode ? pt_launch_shade_fast : pt_launch_shade)(
+                      ms, shade_blocks, c->sc, sp, q, &ln.counts[b], ln.hits, ln.sh[par], ln.alive, ln.shadowm, shp,
+                      b == 0 ? aov_rec : nullptr); }
+                { Timed t(c, kCompact, t3, ms);
+                  pt_launch_compact(ms, tiles, q, &ln.counts[b], ln.alive, nee ? ln.shadowm : nullptr,
+                                    ln.word_off, ln.queue[cur ^ 1], &ln.counts[b + 1], ln.sq[par], &ln.counts[kShadowCount + par],
+                                    c->d_stats, b, last ? 0 : 1);
+                  if (b == rb && !last) pt_launch_repack(ms, blocks, &ln.counts[b + 1], ln.queue[cur ^ 1], bp, tp, ln.pid); }
+                if (side) {
+                    HIP_TRY(c, hipEventRecord(ln.ev_ready, ms));
+                    HIP_TRY(c, hipStreamWaitEvent(ss, ln.ev_ready, 0));
+                    { Timed t(c, kShadow, t3, ss); launch_shadow(c, ss, cfg_shadow, bp, ln.sh[par], ln.sq[par], &ln.counts[kShadowCount + par], nullptr); }
+                    HIP_TRY(c, hipEventRecord(ln.ev_shadow[par], ss));
+                } else if (nee) {
+                    Timed t(c, kShadow, t3, ms);
+                    launch_shadow(c, ms, cfg_shadow, bp, ln.sh[0], ln.sq[0], &ln.counts[kShadowCount], nullptr);
+                }
+                cur ^= 1;
+            }
+            // all additions to L are in before it is folded
+            if (side) {
+                HIP_TRY(c, hipStreamWaitEvent(ms, ln.ev_shadow[(maxb - 1) & 1u], 0));
+                if (maxb >= 2) HIP_TRY(c, hipStreamWaitEvent(ms, ln.ev_shadow[maxb & 1u], 0));
+            }
+            Timed t(c, kAccumulate, t3, ms);
+            pt_launch_accumulate(ms, blocks, px, fb, bp.L, bp.l_stride, c->d_out);
+            if (aov_rec)
+                pt_launch_accumulate_aov(ms, blocks, px, fb, aov_rec, c->sc.tris, c->sc.n_tris, plane_as<float4>(c, kAovAlbedo),
+                                         plane_as<float4>(c, kAovNormal), plane_as<uint2>(c, kAovId));
+            // the moments fold goes last: it moves mom.z on, where the other two read the listed pixels' counts. An adaptive dispatch
+            // always has the plane (it is refused without); a plain one folds it only while it is on.
+            if (ap || mom) pt_launch_accumulate_moments(ms, blocks, px, fb, bp.L, bp.l_stride, mom);
+            return PTMI_OK;
+        };
+        if (ap) {
+            for (uint32_t r = 0; r < rounds; r++) {
+                pt_launch_adaptive_list(ms, blocks, band, *ap, mom, c->ad);
+                for (uint32_t f0 = 0; f0 < n_frames; f0 += F)
+                    if ((rc = batch(0u, std::min(F, n_frames - f0)))) return rc;
+            }
+            c->ad_rounds += rounds;
+        } else {
+            for (uint32_t f0 = 0; f0 < n_frames; f0 += F)
+                if ((rc = batch(cam->frame_index + f0, std::min(F, n_frames - f0)))) return rc;
+        }
+    }
+    HIP_TRY(c, hipGetLastError());
+    {   // the end of this dispatch on the context's stream (the fold of its last batch): what ptmi_throttle waits for
+        hipEvent_t done = get_event(c);
+        HIP_TRY(c, hipEventRecord(done, c->stream));
+        c->in_flight.push_back(done);
+        if (c->in_flight.size() > kMaxDispatchesInFlight) HIP_TRY(c, throttle(c, kMaxDispatchesInFlight));
+    }
+    if (!ap) { c->st.paths += npix * n_frames; c->st.frames += n_frames; }      // adaptive: counted on the device (DevAdaptive::acc)
+    c->st.dispatches += 1;
+    return PTMI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ptmi_dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames) { return dispatch(c, cam, n_frames, nullptr, 0); }
+
+int ptmi_dispatch_adaptive(ptmi_ctx *c, const ptmi_camera *cam, const ptmi_adaptive_params *params, uint32_t rounds) {
+    if (!c) return PTMI_E_INVALID;
+    if (!params) return fail(c, PTMI_E_INVALID, "params is NULL");
+    ptmi_adaptive_params ap = *params;
+    if (!(ap.threshold > 0.0f)) return fail(c, PTMI_E_INVALID, "threshold %g is not > 0", (double)ap.threshold);
+    if (!(ap.floor >= 0.0f) || std::isinf(ap.floor)) return fail(c, PTMI_E_INVALID, "floor %g is negative or not finite", (double)ap.floor);
+    if (ap.reserved[0] || ap.reserved[1]) return fail(c, PTMI_E_INVALID, "a reserved word of ptmi_adaptive_params is not zero");
+    if (ap.neighbourhood > 1u) return fail(c, PTMI_E_INVALID, "neighbourhood %u is not 0 or 1", ap.neighbourhood);
+    if (ap.floor == 0.0f) ap.floor = 1.0f;
+    if (ap.min_frames == 0u) ap.min_frames = 16u;
+    if (ap.max_frames == 0u) ap.max_frames = 4096u;
+    if (ap.step == 0u) ap.step = 16u;
+    if (ap.max_frames > (1u << 24)) return fail(c, PTMI_E_INVALID, "max_frames %u above 2^24", ap.max_frames);
+    if (ap.min_frames > ap.max_frames) return fail(c, PTMI_E_INVALID, "min_frames %u above max_frames %u", ap.min_frames, ap.max_frames);
+    if (ap.step > (1u << 16)) return fail(c, PTMI_E_INVALID, "step %u above 2^16", ap.step);
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    if (!c->moments_on || !c->plane[kMoments]) return fail(c, PTMI_E_STATE, "adaptive sampling needs the moments plane (ptmi_set_moments)");
+    return dispatch(c, cam, ap.step, &ap, rounds);
+}
+
+int ptmi_adaptive_status(ptmi_ctx *c, struct ptmi_adaptive_status *out) {
+    if (!c || !out) return PTMI_E_INVALID;
+    if (!c->moments_on) return fail(c, PTMI_E_STATE, "the moments plane is off (ptmi_set_moments)");
+    if (!c->plane[kMoments]) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = adaptive_words(c);
+    if (rc) return rc;
+    std::memset(out, 0, sizeof *out);
+    const DevBand band = pt_band_of(c->opt, c->W, c->H);
+    const unsigned long long preset[3] = {0ull, ~0ull, 0ull};
+    unsigned long long acc[3] = {0ull, 0ull, 0ull};
+    uint32_t ctl[2] = {0u, 0u};
+    HIP_TRY(c, quiesce(c));
+    if (band.y0 < band.y1 && band.rows) {
+        HIP_TRY(c, hipMemcpyAsync(&c->ad.acc[1], preset, sizeof preset, hipMemcpyHostToDevice, c->stream));
+        pt_launch_adaptive_status(c->stream, c->n_cu * 8, band, plane_as<float4>(c, kMoments), c->ad);
+        HIP_TRY(c, hipMemcpyAsync(acc, &c->ad.acc[1], sizeof acc, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipMemcpyAsync(ctl, c->ad.ctl, sizeof ctl, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    out->active = ctl[1];
+    out->samples = acc[0];
+    out->min_count = acc[1] == ~0ull ? 0u : (uint32_t)acc[1];
+    out->max_count = (uint32_t)acc[2];
+    out->rounds = c->ad_rounds;
+    return PTMI_OK;
+}
+
+// The snapshot is a copy of whole planes (rows of other contexts travel along and are never read); the centre rays and their hits use
+// the batch arrays of a dispatch, like the per-stage entry points. Everything that can fail comes before the first write.
+int ptmi_reproject(ptmi_ctx *c, const ptmi_camera *from, const ptmi_camera *to, const ptmi_reproject_params *params) {
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    if (!from || !to) return fail(c, PTMI_E_INVALID, "a camera is NULL");
+    for (const ptmi_camera *cam : {from, to})
+        if (cam->width != c->W || cam->height != c->H)
+            return fail(c, PTMI_E_INVALID, "a camera says %ux%u but the output buffer is %ux%u", cam->width, cam->height, c->W, c->H);
+    const ptmi_reproject_params zero = {};
+    const ptmi_reproject_params &q = params ? *params : zero;
+    if (!std::isfinite(q.depth_tolerance) || q.depth_tolerance < 0.0f)
+        return fail(c, PTMI_E_INVALID, "depth_tolerance %g is negative or not finite", (double)q.depth_tolerance);
+    if (q.max_history > (1u << 24)) return fail(c, PTMI_E_INVALID, "max_history %u above 2^24", q.max_history);
+    if (q.match_ids > 2u) return fail(c, PTMI_E_INVALID, "unknown match_ids %u", q.match_ids);
+    for (uint32_t r : q.reserved) if (r) return fail(c, PTMI_E_INVALID, "a reserved word of ptmi_reproject_params is not zero");
+    if (!(c->aov_mask & PTMI_AOV_NORMAL) || !c->plane[kAovNormal])
+        return fail(c, PTMI_E_STATE, "reprojection needs the NORMAL plane (ptmi_set_aovs)");
+    if (!c->moments_on || !c->plane[kMoments]) return fail(c, PTMI_E_STATE, "reprojection needs the moments plane (ptmi_set_moments)");
+    const bool have_albedo = (c->aov_mask & PTMI_AOV_ALBEDO) && c->plane[kAovAlbedo];
+    const bool have_ids = (c->aov_mask & PTMI_AOV_ID) && c->plane[kAovId];
+    if (q.match_ids == 2u && !have_ids) return fail(c, PTMI_E_STATE, "match_ids = 2 needs the ID plane (ptmi_set_aovs)");
+    const DevBand band = pt_band_of(c->opt, c->W, c->H);
+    if (band.y0 >= band.y1) return fail(c, PTMI_E_INVALID, "tile rows [%u,%u) outside the %u-row frame", band.y0, band.y1, c->H);
+    if ((band.rows + 3u) / 4u > 65535u) return fail(c, PTMI_E_UNSUPPORTED, "more than 262140 rows");
+    TraverseConfig cfg;
+    if ((rc = traverse_pick(c, true, cfg))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t npix = (size_t)c->W * c->H;
+    const uint32_t history = bit(kRpOut) | bit(kRpMoments) | bit(kRpNormal) | (have_albedo ? bit(kRpAlbedo) : 0u) | (have_ids ? bit(kRpId) : 0u);
+    if ((rc = make_planes(c, history, npix, c->plane))) return rc;
+    if (!c->d_reproject) HIP_TRY(c, hipMalloc(&c->d_reproject, 4 * sizeof(unsigned long long)));
+    Lane &ln = c->lane;
+    if (band.rows && (rc = ensure_capacity(c, ln, (size_t)band.rows * band.width))) return rc;
+    if ((rc = traverse_arm(c, true, kSpillMain, cfg, false))) return rc;      // (the statistics keep the variants of the last dispatch)
+    const hipStream_t s = c->stream;
+    HIP_TRY(c, hipMemsetAsync(c->d_reproject, 0, 4 * sizeof(unsigned long long), s));
+    if (band.rows == 0) return PTMI_OK;                         // more parts than strips: no pixel of this context's
+    const struct { FramePlane to; const void *from; bool on; } copies[] = {
+        {kRpOut, c->d_out, true}, {kRpMoments, c->plane[kMoments], true}, {kRpNormal, c->plane[kAovNormal], true},
+        {kRpAlbedo, c->plane[kAovAlbedo], have_albedo}, {kRpId, c->plane[kAovId], have_ids}};
+    for (const auto &cp : copies)
+        if (cp.on) HIP_TRY(c, hipMemcpyAsync(c->plane[cp.to], cp.from, plane_bytes(cp.to, npix), hipMemcpyDeviceToDevice, s));
+    const int blocks = c->n_cu * 8;
+    pt_launch_center_rays(s, blocks, *to, band, ln.paths, &ln.counts[0]);
+    launch_extend(c, s, cfg, ln.paths, nullptr, &ln.counts[0], ln.hits);
+    ReprojectArgs a{};
+    a.from = *from; a.band = band;
+    a.max_history = q.max_history ? q.max_history : 32u;
+    a.depth_tolerance = q.depth_tolerance > 0.0f ? q.depth_tolerance : 0.02f;
+    a.match_ids = q.match_ids == 2u || (q.match_ids == 0u && have_ids) ? 1u : 0u;
+    a.O = ln.paths.O; a.D = ln.paths.D; a.hits = ln.hits;
+    a.tris = c->sc.tris; a.n_tris = c->sc.n_tris;
+    a.h_out = plane_as<float4>(c, kRpOut); a.h_mom = plane_as<float4>(c, kRpMoments); a.h_normal = plane_as<float4>(c, kRpNormal);
+    a.h_albedo = have_albedo ? plane_as<float4>(c, kRpAlbedo) : nullptr; a.h_ids = have_ids ? plane_as<uint2>(c, kRpId) : nullptr;
+    a.out = c->d_out; a.mom = plane_as<float4>(c, kMoments); a.normal = plane_as<float4>(c, kAovNormal);
+    a.albedo = have_albedo ? plane_as<float4>(c, kAovAlbedo) : nullptr; a.ids = have_ids ? plane_as<uint2>(c, kAovId) : nullptr;
+    a.status = c->d_reproject;
+    pt_launch_reproject(s, a);
+    HIP_TRY(c, hipGetLastError());
+    return PTMI_OK;
+}
+
+int ptmi_reproject_status(ptmi_ctx *c, struct ptmi_reproject_status *out) {
+    if (!c || !out) return PTMI_E_INVALID;
+    std::memset(out, 0, sizeof *out);
+    if (!c->d_reproject) return PTMI_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, quiesce(c));
+    unsigned long long h[4];
+    HIP_TRY(c, hipMemcpy(h, c->d_reproject, sizeof h, hipMemcpyDeviceToHost));
+    out->carried = h[0]; out->disoccluded = h[1]; out->missed = h[2]; out->samples = h[3];
+    return PTMI_OK;
+}
+
+int ptmi_throttle(ptmi_ctx *c, uint32_t max_in_flight, uint32_t *in_flight) {
+    if (!c) return PTMI_E_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, throttle(c, max_in_flight));
+    if (in_flight) *in_flight = (uint32_t)c->in_flight.size();
+    return PTMI_OK;
+}
+
+int ptmi_synchronize(ptmi_ctx *c) {
+    if (!c) return PTMI_E_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, quiesce(c));
+    HIP_TRY(c, throttle(c, 0));
+    return PTMI_OK;
+}
+
+}  // extern "C"

@@ -235,7 +235,7 @@ __global__ __launch_bounds__(TILE_WORDS) void k_scatter2(uint32_t tiles, const u
     else scatter_tile<true>(blockIdx.x - tiles, count_ptr, nullptr, shadow, shadow_sums, shadow_queue, shadow_count);
 }
 
-// The repack, once per batch after the compaction of the first bounce that plays roulette (ptmi_api.hip): queue entry j (path id q)
+// The repack, once per batch after the compaction of the first bounce that plays roulette (dispatch.hip): queue entry j (path id q)
 // -> to.O / D / C[j] = from.O / D / C[q], pid[j] = q. Every entry is independent: one gather per lane, many in flight.
 __global__ __launch_bounds__(BLOCK) void k_repack(const uint32_t *__restrict__ count_ptr, const uint32_t *__restrict__ queue,
                                                   DevPaths from, DevPaths to, uint32_t *__restrict__ pid) {

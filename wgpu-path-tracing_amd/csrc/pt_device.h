@@ -160,7 +160,7 @@ enum { PT_VARIANT_GLOBAL = 1, PT_VARIANT_LDS = 2, PT_VARIANT_LDS_NODES = 3,
                                                 // 8 - 15 16-bit entries per lane (what the nodes leave of 80 KB), the node stack spills
        PT_VARIANT_COUNT };
 
-// What each traversal variant is: one row per PT_VARIANT_* (pt_variant), the one place selection (ptmi_api.hip traverse_config) and
+// What each traversal variant is: one row per PT_VARIANT_* (pt_variant), the one place selection (traverse_pick.hip traverse_config) and
 // the launches read it from.
 enum PtNodes {                  // node format
     PT_NODES_EXACT,             // 64-B wide nodes (PT_VARIANT_GLOBAL: or the quantised image, TraverseConfig::quantized)
@@ -320,20 +320,6 @@ void pt_launch_unpack_rows(hipStream_t s, int blocks, DevBand band, const float4
 // the rows DevBand describes for a context with these options on a width x height frame (rows = 0: none)
 struct ptmi_options;
 DevBand pt_band_of(const ptmi_options &opt, uint32_t width, uint32_t height);
-// what ptmi_multi.hip needs from a context (ptmi_api.hip)
-struct ptmi_ctx;
-struct PtPrepared;               // a scene prepared on the host: validation + traversal image (ptmi_api.hip)
-PtPrepared *pt_prepare_scene(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt, const ptmi_material *mats, uint32_t nm,
-                             const ptmi_bvh_node *nodes, uint32_t nn, const ptmi_light *lights, uint32_t nl, int *rc_out);
-int pt_install_scene(ptmi_ctx *c, PtPrepared *p);            // allocates and copies on c's device; c keeps its old scene on failure
-void pt_free_prepared(PtPrepared *p);
-// bytes of a width x height atlas of `format` (ptmi_upload_atlas); PTMI_E_INVALID, with the reason in `why`, for an unknown
-// format or a size that does not fit in size_t
-int pt_atlas_bytes(uint32_t width, uint32_t height, int format, size_t *bytes, char *why, size_t why_len);
-hipStream_t pt_ctx_stream(ptmi_ctx *c);
-float4 *pt_ctx_output(ptmi_ctx *c);
-int pt_ctx_device(const ptmi_ctx *c);
-int pt_ctx_cus(const ptmi_ctx *c);
 void pt_launch_exact_math(hipStream_t s, int which, unsigned long long *out);
 void pt_launch_math(hipStream_t s, int op, uint32_t n, const float *a, const float *b, const float *c, float *out);
 

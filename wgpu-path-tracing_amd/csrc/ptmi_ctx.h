@@ -1,0 +1,187 @@
+// ptmi_ctx.h — the context behind the C ABI of include/ptmi.h, and what the files that implement it share. Host code only; internal.
+//   ptmi_api.hip       the context and its options, the frame planes, the batch arrays, output, statistics
+//   scene_image.hip    scene validation, the traversal image, ptmi_upload_scene
+//   traverse_pick.hip  which variant a traversal kernel runs as, and the launch of one
+//   dispatch.hip       the wavefront dispatch loop, adaptive sampling, reprojection, event timing
+//   debug_stages.hip   the per-stage debug entry points
+#pragma once
+#include "ptmi.h"
+#include "pt_device.h"
+
+#include <cstddef>
+#include <cstdint>
+#include <deque>
+#include <string>
+#include <vector>
+
+// what ptmi_multi.hip needs from a context
+struct ptmi_ctx;
+struct PtPrepared;               // a scene prepared on the host: validation + traversal image (scene_image.hip)
+PtPrepared *pt_prepare_scene(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt, const ptmi_material *mats, uint32_t nm,
+                             const ptmi_bvh_node *nodes, uint32_t nn, const ptmi_light *lights, uint32_t nl, int *rc_out);
+int pt_install_scene(ptmi_ctx *c, PtPrepared *p);            // allocates and copies on c's device; c keeps its old scene on failure
+void pt_free_prepared(PtPrepared *p);
+// bytes of a width x height atlas of `format` (ptmi_upload_atlas); PTMI_E_INVALID, with the reason in `why`, for an unknown
+// format or a size that does not fit in size_t
+int pt_atlas_bytes(uint32_t width, uint32_t height, int format, size_t *bytes, char *why, size_t why_len);
+hipStream_t pt_ctx_stream(ptmi_ctx *c);
+float4 *pt_ctx_output(ptmi_ctx *c);
+int pt_ctx_device(const ptmi_ctx *c);
+int pt_ctx_cus(const ptmi_ctx *c);
+
+// What follows is shared by the five files above only: hidden, so that the library exports the C ABI and the pt_* names and no helper.
+// (A definition takes the visibility of the namespace block it stands in, so every block of pt_host is opened with PT_HOST.)
+#define PT_HOST namespace pt_host __attribute__((visibility("hidden")))
+PT_HOST {
+// The device buffers of an uploaded scene, one entry each (the atlas is ptmi_upload_atlas's). The walked image's entries are absent when
+// the kernels walk the tree as uploaded: DevScene then points at the reference entries.
+enum SceneBuf {
+    kTris, kMats, kLights,
+    kRefWnodes, kRefTripos,            // the tree as uploaded; triangle images in original order
+    kWnodes, kTripos,                  // the walked image: a hierarchy rebuilt over the reference's leaves (nodes only), or own leaves
+    kQnodes, kLeafStream,              // its quantised nodes; the leaf stream (the reference's leaves only)
+    kLeafbox,                          // own leaves: per original triangle, the box of the reference leaf that lists it
+    kWnodes16, kRefWnodes16, kQnodes16,    // own leaves, small scenes: the two hierarchies and the quantised nodes with 16-bit references
+    kShadeTab,                         // the shade tables: materials, lights and the lights' triangles in one blob (pt_device.h)
+    kSceneBufs
+};
+
+// The per-pixel buffers that follow the output size, one entry each (ptmi_api.hip kFrame: what each takes and when it is made).
+enum FramePlane {
+    kOut,                                          // the context's own output buffer (binding 0)
+    kAovAlbedo, kAovNormal, kAovId,                // first-hit planes (ptmi_set_aovs), in the order of the PTMI_AOV_* bits
+    kMoments,                                      // sample moments (ptmi_set_moments)
+    kDnGuide, kDnGrad, kDnA, kDnB, kDnOut,         // the denoiser's: guide (unit normal, depth), depth gradient, two ping-pong colour +
+                                                   // variance planes, the result
+    kAdBallot, kAdList, kAdTileSums,               // adaptive sampling: ballot words, pixel list, tile totals
+    kRpOut, kRpMoments, kRpNormal, kRpAlbedo, kRpId,   // reprojection: the snapshot of the output, moments and first-hit planes
+    kBlitF32, kBlitU8,                             // canvas staging of ptmi_blit
+    kFramePlanes
+};
+
+// The per-path arrays of a batch, one entry each (ptmi_api.hip kLaneBytes: what each takes per path), in the order they are allocated.
+enum LaneBuf {
+    kPathO, kPathD, kPathC, kPathL,                // path state; L has room for either stride
+    kHits,
+    kShadow0, kShadowIdx0, kShadow1, kShadowIdx1,  // shadow records (SO, SD, SC in one block) and their index arrays, by bounce parity
+    kTailO, kTailD, kTailC, kPid,                  // state by queue slot after the repack, and the path id of each such slot
+    kQueue0, kQueue1,
+    kOcc,                                          // occlusion bytes (ptmi_debug_occluded)
+    kAovRec,                                       // first-hit records of bounce 0 (k_shade<true>); only while AOV planes are on
+    kLaneBufs
+};
+
+// A timed stretch of a stream: the two events around it and the statistic it adds to (dispatch.hip kEventStat).
+enum EventKind { kDispatch, kExtend, kShade, kShadow, kRaygen, kCompact, kAccumulate, kEventKinds };
+struct EventPair { hipEvent_t a, b; EventKind kind; };
+
+}  // namespace pt_host
+using namespace pt_host;
+
+// The buffers of the wavefront batch in flight, and the second stream that lets `shadow` run beside the next bounce.
+struct Lane {
+    size_t cap = 0;
+    void *buf[kLaneBufs] = {};                         // indexed by LaneBuf; the typed members below are views of it (lane_views)
+    DevPaths paths{};
+    float2 *hits = nullptr;
+    DevShadow sh[2]{};                                 // shadow records, double-buffered by bounce parity (overlap)
+    uint32_t *queue[2] = {nullptr, nullptr}, *sq[2] = {nullptr, nullptr};
+    DevPaths tail{};                                   // O / D / C by queue slot from the bounce after the repack (L unused)
+    uint32_t *pid = nullptr;                           // ... and the path id of each such slot
+    uint64_t *alive = nullptr, *shadowm = nullptr;
+    size_t mask_words = 0;
+    uint32_t *word_off = nullptr, *counts = nullptr;
+    uint32_t *d_spill = nullptr;          // node-stack overflow of the global traversal variant (128 MiB on 256 CUs; first use)
+    uint32_t *d_spill_side = nullptr;     // ... of the `shadow` kernel when it runs beside `extend`
+    uint8_t *d_occ = nullptr;
+    hipStream_t side = nullptr;           // `shadow` of bounce b beside the kernels of bounce b + 1
+    hipEvent_t ev_ready = nullptr, ev_shadow[2] = {nullptr, nullptr};
+    float4 *aov = nullptr;                // first-hit records of bounce 0, 32 B per path (k_shade<true>); only while AOV planes are on
+};
+
+struct ptmi_ctx {
+    int device = 0, n_cu = 256;
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    Lane lane;
+    mutable std::string err;
+    bool alloc_oom = false;                            // the last failed batch allocation ran out of device memory
+    ptmi_options opt{};
+
+    // scene (bindings 1, 2, 4, 5, 6)
+    void *buf[kSceneBufs] = {};                        // indexed by SceneBuf (absent: NULL)
+    void *d_atlas = nullptr;
+    DevScene *d_scene = nullptr;                       // sc in device memory (DevScene::self), rewritten whenever sc changes
+    DevScene sc{};
+    bool have_scene = false;
+    ptmi_image_info img{};                   // what the last upload put on the device (ptmi_debug_read_image)
+
+    // output (binding 0)
+    uint32_t W = 0, H = 0;
+    void *plane[kFramePlanes] = {};                    // indexed by FramePlane, W x H pixels each (absent: NULL)
+    float4 *d_out = nullptr;                           // what dispatches write: plane[kOut] or the caller's buffer (ptmi_bind_output_device)
+    uint32_t aov_mask = 0;                             // ptmi_set_aovs: a plane is present while its bit is set and the output buffer exists
+    bool moments_on = false;                           // ptmi_set_moments: likewise
+    // adaptive sampling (ptmi_dispatch_adaptive): ballot, list and tile_sums are views of the planes; the control words and counters
+    // live for the context's life
+    DevAdaptive ad{};
+    uint32_t ad_rounds = 0;                            // rounds since the last restart
+    unsigned long long *d_reproject = nullptr;         // ptmi_reproject_status: the four counters of the last ptmi_reproject (made by the first)
+
+    unsigned long long *d_stats = nullptr;
+
+    // statistics
+    ptmi_stats st{};
+    std::vector<EventPair> pending;
+    std::vector<hipEvent_t> event_pool;
+    std::deque<hipEvent_t> in_flight;                  // one event per ptmi_dispatch, recorded behind its last kernel (ptmi_throttle)
+};
+
+PT_HOST {
+
+extern thread_local std::string g_create_err;      // the error of a call that has no context (ptmi_last_error(NULL))
+int fail(std::string &err, int code, const char *fmt, ...);
+int fail(const ptmi_ctx *c, int code, const char *fmt, ...);
+#define HIP_TRY(c, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
+    return fail((c), PTMI_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+
+template <class T> void dfree(T *&p) { if (p) { (void)hipFree(p); p = nullptr; } }
+// device scratch of one call (the ptmi_debug_*math entry points), freed on every way out of it
+template <class T> struct Scratch { T *p = nullptr; ~Scratch() { if (p) (void)hipFree(p); } };
+template <class T> void view(T *&p, void *b) { p = static_cast<T *>(b); }      // a typed member that stands for an entry of a buffer table
+template <class T> T *plane_as(const ptmi_ctx *c, FramePlane k) { return static_cast<T *>(c->plane[k]); }
+
+// ptmi_api.hip
+void default_options(ptmi_options &o);
+hipError_t sync_all(ptmi_ctx *c);
+size_t bytes_per_path(bool aov);
+int ensure_capacity(ptmi_ctx *c, Lane &ln, size_t n);
+enum PlaneGroup { kWithFrame, kByDenoise, kByAdaptive, kByReproject, kByBlit };     // when a plane is made (the kFrame table)
+constexpr uint32_t bit(FramePlane k) { return 1u << k; }                            // sets of planes: a bit per FramePlane
+uint32_t group_set(PlaneGroup g);
+size_t plane_bytes(FramePlane k, size_t px);                                        // what plane k takes for px pixels
+int make_planes(ptmi_ctx *c, uint32_t set, size_t px, void **into);
+int check_ready(ptmi_ctx *c, bool need_output);
+
+// dispatch.hip
+void drain_events(ptmi_ctx *c);
+hipError_t quiesce(ptmi_ctx *c);
+
+// traverse_pick.hip
+bool walks_memory_quantised(const TraverseConfig &cfg);
+// A traced launch in two steps, for the callers that have work between them (traverse_ready: both, for those that have none).
+// traverse_pick chooses the variant of the extend (closest_hit) or the any-hit kernel and touches no device; PTMI_E_UNSUPPORTED: the
+// option is PTMI_TRAVERSAL_LDS and the scene does not fit (extend only: the any-hit kernel is never refused).
+// traverse_arm makes the spill area on first use, sets cfg.spill and (record) writes ptmi_stats.extend_variant / shadow_variant.
+// Kernels that run at the same time need a spill area each, so every kernel has the lane's d_spill (kSpillMain) except the any-hit
+// kernel of a dispatch: that one makes d_spill_side, and uses it beside `extend` on the side stream (kSpillSide); on the main stream
+// (kSpillAfterExtend) it uses d_spill where extend's variant has made one, else d_spill_side.
+enum SpillArea { kSpillMain, kSpillSide, kSpillAfterExtend };
+int traverse_pick(const ptmi_ctx *c, bool closest_hit, TraverseConfig &cfg);
+int traverse_arm(ptmi_ctx *c, bool closest_hit, SpillArea area, TraverseConfig &cfg, bool record);
+int traverse_ready(ptmi_ctx *c, bool closest_hit, TraverseConfig &cfg);            // pick, then arm with d_spill, recorded
+// the launch of either kernel on c->n_cu * 8 workgroups: the own-leaf launcher or the reference-leaf one, by the uploaded scene
+void launch_extend(ptmi_ctx *c, hipStream_t s, const TraverseConfig &cfg, DevPaths p, const uint32_t *queue, const uint32_t *count,
+                   float2 *hits);
+void launch_shadow(ptmi_ctx *c, hipStream_t s, const TraverseConfig &cfg, DevPaths p, DevShadow sh, const uint32_t *shadow_queue,
+                   const uint32_t *count, uint8_t *occluded_out);
+}  // namespace pt_host

@@ -12,8 +12,7 @@
 // Equal counts per rank are what ncclGather takes, so every device sends rows_max x width float4 (the last round of strips may
 // leave some devices a strip short; the padding is never unpacked). RCCL is loaded with dlopen when the first handle is
 // created: a process that renders on one device never maps it.
-#include "ptmi.h"
-#include "pt_device.h"
+#include "ptmi_ctx.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>

@@ -88,7 +88,7 @@ PT_DEV v4 texture_color(const DevScene &sc, const ptmi_atlas_rect &tx, float uvx
 
 // rayTriangleIntersect, pt.wgsl:159-226, for the closest hit only. The hit record carries (t, triangle); the barycentric
 // (u, v) are the ones `extend` computed when it accepted the hit — recomputed here by the same tri_test on the same
-// operands (e1, e2 are the same single IEEE subtractions the traversal image was built with, ptmi_api.hip).
+// operands (e1, e2 are the same single IEEE subtractions the traversal image was built with, scene_image.hip).
 template <int STAGE>
 PT_DEV HitInfo make_hitinfo(const DevScene &sc, const ShadeTabs<STAGE> &tabs, v3 ro, v3 rd, float t, uint32_t tri) {
     HitInfo hi;

@@ -364,7 +364,7 @@ __global__ __launch_bounds__(GBLOCK) void k_trace_global(DevScene sc, IO io, con
 //              workgroups fit a CU (8 waves per SIMD instead of 4)
 // Measured on Cornell 1080p: closest-hit rays run 14 % faster from the node cache (they are
 // issue-bound and gain from the second workgroup), shadow rays 7 % slower (they test fewer boxes per
-// triangle and miss the LDS-resident triangles); ptmi_api picks per kernel.
+// triangle and miss the LDS-resident triangles); traverse_pick.hip picks per kernel.
 constexpr int LBLOCK = 1024;
 
 template <int MODE, bool CULL, int STACK, bool TRIS_IN_LDS, bool SPILL, class IO>
@@ -398,7 +398,7 @@ void launch_global(hipStream_t s, int cus, const DevScene &sc, const IO &io, con
     hipLaunchKernelGGL((k_trace_global<MODE, CULL, 16, QUANT, IO>), dim3(per_cu * cus), dim3(GBLOCK), 0, s, sc, io, count, spill);
 }
 
-// the config -> the kernel it names; sizes come from the config (ptmi_api.hip traverse_config)
+// the config -> the kernel it names; sizes come from the config (traverse_pick.hip traverse_config)
 template <int MODE, bool CULL, class IO>
 void launch(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &sc, const IO &io, const uint32_t *count) {
     const int cus = blocks / 8 > 0 ? blocks / 8 : 1;

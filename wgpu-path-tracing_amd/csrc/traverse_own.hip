@@ -492,7 +492,7 @@ void launch_own_global(hipStream_t s, int cus, const DevScene *sc, const IO &io,
     hipLaunchKernelGGL((k_own_global<MODE, CULL, QUANT, IO>), dim3(per_cu * cus), dim3(GBLOCK), 0, s, sc, io, count, spill);
 }
 
-// the config -> the kernel it names; sizes come from the config (ptmi_api.hip traverse_config)
+// the config -> the kernel it names; sizes come from the config (traverse_pick.hip traverse_config)
 template <int MODE, bool CULL, class IO>
 void launch_own(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &hsc, const IO &io, const uint32_t *count) {
     const int cus = blocks / 8 > 0 ? blocks / 8 : 1;
