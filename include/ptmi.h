@@ -372,6 +372,45 @@ struct ptmi_reproject_status { uint64_t carried, disoccluded, missed, samples; }
 int ptmi_reproject(ptmi_ctx *ctx, const ptmi_camera *from, const ptmi_camera *to, const ptmi_reproject_params *params);
 int ptmi_reproject_status(ptmi_ctx *ctx, struct ptmi_reproject_status *out);    /* synchronises */
 
+/* ---- environment lighting: an HDR sky behind every miss, importance-sampled ------------------
+ * Without an environment a ray that leaves the scene adds throughput * 0 (pt.wgsl:646-648) and nothing changes: every result keeps
+ * its bits. With one, a ray of bounce b that misses adds throughput * (W_b * Le(d)) where an emissive hit's addition goes, the camera
+ * ray included (W_0 = 1); the first-hit planes of a miss stay zeros / 0xFFFFFFFF.
+ * The map is equirectangular, width x height RGBA texels in either atlas format (alpha is ignored), row 0 at the +Y pole, texel (0,0)
+ * first. LOOKUP of a unit direction d: phi = atan2(d.z, d.x) - rotation, u = phi / 2pi + 0.5 wrapped into [0, 1),
+ * v = acos(clamp(d.y, -1, 1)) / pi, texel (min(floor(u W), W - 1), min(floor(v H), H - 1)), nearest, unfiltered;
+ * Le = texel.rgb * intensity, one float32 multiply per channel. atan2 and acos are the device's own: which texel a direction within
+ * rounding of a texel border reads is outside the bit-exact arithmetic contract, like ptmi_blit.
+ * DISTRIBUTION, built on the host at upload in double precision: w_t = lum(rgb_t) * (cos(theta_top) - cos(theta_bottom)) of the
+ * texel's row, lum = 0.2126 r + 0.7152 g + 0.0722 b; P_t = w_t / sum(w); a Vose alias table (prob: float, alias: uint32) over the
+ * N = W * H texels; c_t = float(P_t * N / (2 pi^2)) beside the texel's rgb. pdf(d) = c_t / max(sqrt(max(0, 1 - d.y^2)), 1e-6) is the
+ * solid-angle density of "texel t with probability P_t, then uniform in (u, v) inside it". A map whose sum(w) is 0 (all black) is
+ * looked up but never sampled.
+ * SAMPLING (next-event estimation, do_mis = 1): while a map is in place and sampled it is light number n_lights: sampleLight draws
+ * its index from 0 .. n_lights and every light's pdf takes 1 / (n_lights + 1). Chosen, it draws r1 .. r4: k = min(floor(r1 N), N - 1),
+ * t = r2 < prob[k] ? k : alias[k], u = (t mod W + r3) / W, v = (t / W + r4) / H, theta = v pi, phi = (u - 0.5) 2pi + rotation,
+ * d = (sin theta cos phi, cos theta, sin theta sin phi) with the kernels' sin / cos (ptmi_debug_math ops 5, 6), density
+ * c_t / max(sin theta, 1e-6), radiance the texel's: a directional shadow record (any hit occludes), weighted like every light sample.
+ * The bounce ray of a vertex that ran next-event estimation with a sampled map carries W = powerHeuristic(1, bsdf pdf, 1,
+ * pdf(direction) / (n_lights + 1)) for the bounce that may miss; every other ray carries 1 (do_mis = 0, a transmissive hit, a back
+ * face, sample = 1). */
+typedef struct ptmi_environment {
+    float    intensity;   /* radiance scale; 0 -> 1; negative / non-finite: PTMI_E_INVALID */
+    float    rotation;    /* radians about +Y, added to the azimuth; must be finite (kept as its remainder by 2 pi, in [-pi, pi]) */
+    uint32_t sample;      /* 0: next-event samples include the sky (default); 1: lookup only (misses see it, NEE never picks it) */
+    uint32_t reserved[5]; /* must be 0 */
+} ptmi_environment;       /* 32 bytes */
+/* texels NULL or width / height 0: removes the environment. params NULL: the defaults. PTMI_E_INVALID: an unknown format, a size that
+ * does not fit (more than 2^28 texels included), a texel whose r, g or b is negative or not finite, bad params. A call that fails
+ * leaves the current environment in place. Synchronises. */
+int ptmi_upload_environment(ptmi_ctx *ctx, const void *texels, uint32_t width, uint32_t height, int format,
+                            const ptmi_environment *params);
+/* intensity / rotation / sample of the map in place, without a re-upload. PTMI_E_STATE: none is in place. Synchronises. */
+int ptmi_set_environment(ptmi_ctx *ctx, const ptmi_environment *params);
+/* width = height = 0: none in place. sampled: 1 iff next-event estimation picks it (sample = 0 and sum(w) > 0). A struct tag only. */
+struct ptmi_environment_status { uint32_t width, height, sampled, reserved; double weight_sum; };   /* 24 bytes */
+int ptmi_environment_status(ptmi_ctx *ctx, struct ptmi_environment_status *out);
+
 /* ---- presentation (the reference's blit pass, src/shader/blit.wgsl:43-155; renderer.ts:434-449) ---- */
 /* Tone-maps the output buffer (exposure 2^1, AgX, gamma 1/2.2) into a width*height canvas, row 0 = top.
  * dst_rgba_f32 (n_floats must be width*height*4, alpha 1) and/or dst_rgba8 (n_bytes must be width*height*4);
@@ -416,6 +455,10 @@ int ptmi_multi_upload_scene(ptmi_multi *m,
                             const ptmi_light *lights, uint32_t n_lights);
 int ptmi_multi_upload_atlas(ptmi_multi *m, const void *texels, uint32_t width, uint32_t height, int format);
 int ptmi_multi_resize(ptmi_multi *m, uint32_t width, uint32_t height);
+/* ptmi_upload_environment / ptmi_set_environment on every device (replicated, like the atlas; checked once before any device changes) */
+int ptmi_multi_upload_environment(ptmi_multi *m, const void *texels, uint32_t width, uint32_t height, int format,
+                                  const ptmi_environment *params);
+int ptmi_multi_set_environment(ptmi_multi *m, const ptmi_environment *params);
 /* Options for every device. tile_parts / tile_part are set by the library (device i renders the strips i, i + N, ...);
  * tile_strip = 0 picks the strip height: 4 rows, or the largest smaller height that makes the frame a whole number of rounds
  * (3840x2160 over 8 devices: 3), so that all devices get equal shares; tile_y0 / tile_y1 must be 0. */
@@ -494,6 +537,18 @@ int ptmi_debug_read_image(ptmi_ctx *ctx, ptmi_image_info *info, float *wnodes16,
  *      7 pow5(a), 8 f32(u32 bits of a), 9 u32(a) as bits, 10 a - trunc(a), 11 tan(a), 12 1/a (the kernels' short form) */
 int ptmi_debug_math(ptmi_ctx *ctx, int op, uint32_t n, const float *a, const float *b,
                     const float *c, float *out);
+/* The environment map (ptmi_upload_environment), probed with the functions the renders run. Both synchronise; PTMI_E_STATE: no map.
+ * lookup: n unit directions d3 (n*3 floats) -> out4[4i .. 4i+3] = (Le.rgb, pdf) of direction i.
+ * sample: the sampling routine on caller-supplied uniforms r4[4i .. 4i+3] = r1 .. r4 in place of RNG draws (PTMI_E_STATE also when
+ * the map is not sampled) -> d3 the direction, out4 = (Le.rgb, density), texel[i] the texel picked. d3 / out4 / texel may be NULL. */
+int ptmi_debug_env_lookup(ptmi_ctx *ctx, uint32_t n, const float *d3, float *out4);
+int ptmi_debug_env_sample(ptmi_ctx *ctx, uint32_t n, const float *r4, float *d3, float *out4, uint32_t *texel);
+/* Host-only (no context, no device): the tables ptmi_upload_environment would build for these texels. c_out: width*height floats
+ * (c_t); prob_out / alias_out: width*height entries of the alias table; *weight_sum = sum(w). Each may be NULL. An all-black map gives
+ * weight_sum 0, every c_t and prob 0 and alias[k] = k: such a map is never sampled. Errors as ptmi_upload_environment's, with the
+ * message under ptmi_last_error(NULL). */
+int ptmi_debug_env_table(const void *texels, uint32_t width, uint32_t height, int format, float *c_out, float *prob_out,
+                         uint32_t *alias_out, double *weight_sum);
 /* The kernels compute 1/x and sqrt(x) with short instruction sequences where the operand's magnitude is within
  * [2^-100, 2^100] and with the compiler's IEEE expansions elsewhere (csrc/pt_math.h). This runs both over ALL 2^32 float bit
  * patterns on the device and reports how many inputs give different bits (two NaNs count as equal) and the smallest such

@@ -144,13 +144,14 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         // Room = free memory + what this context already holds, less a tenth for the rest (spill areas, blit staging).
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const uint64_t held = (uint64_t)ln.cap * bytes_per_path(ln.aov != nullptr);
+            const uint64_t held = (uint64_t)ln.cap * bytes_per_path(ln.aov != nullptr, ln.paths.W != nullptr);
             const uint64_t room = (uint64_t)((double)(free_b + held) * 0.9);
-            F = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(F, room / (npix * bytes_per_path(c->aov_mask != 0))));
+            F = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(F, room / (npix * bytes_per_path(c->aov_mask != 0, c->sc.env.sampled != 0))));
         }
     }
     F = std::min(F, n_frames);
-    const bool nee = c->opt.do_mis && c->sc.n_lights > 0;
+    const bool env_w = c->sc.env.sampled != 0;                  // a sampled environment is one more light, and bounce rays carry its weight
+    const bool nee = c->opt.do_mis && (c->sc.n_lights > 0 || env_w);
     // overlap: `shadow` of bounce b on a side stream, beside extend / shade of bounce b + 1. It is then the only kernel that
     // adds to L (emissive hits leave a record too, ShadeParams::emit_records), bounce after bounce on one stream, so every
     // path's sum is formed in the same order as without it. Record buffers alternate by bounce parity; shade(b) waits for
@@ -188,7 +189,8 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         const hipStream_t ss = side ? ln.side : ms;                               // ... and the shadow kernels'
         const int tiles = (int)(ln.cap / pt_compact_tile_slots() + 1);
         ln.paths.l_stride = c->st.radiance_stride_bytes / 4u;
-        const DevPaths bp = ln.paths;
+        DevPaths bp = ln.paths;
+        if (!env_w) bp.W = nullptr;                             // (the arrays of an earlier, sampled environment may still be there)
         // Once per batch, after the compaction of the first bounce that plays roulette, the survivors' O / D / C are gathered into the
         // tail arrays at their queue positions: from then on a few percent of the paths are alive, and state left at the path id costs
         // them a line per lane in each stream. From the next bounce on, extend and shade find the state at the slot the queue names
@@ -196,6 +198,7 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         const uint32_t rb = PT_REPACK ? pt_repack_bounce() : 0xFFFFFFFEu;
         DevPaths tp = ln.tail;
         tp.L = bp.L; tp.l_stride = bp.l_stride;
+        if (!env_w) tp.W = nullptr;
         float4 *const aov_rec = c->aov_mask ? ln.aov : nullptr;         // written by shade(0), read by the fold after the last bounce
         float4 *const mom = plane_as<float4>(c, kMoments);
         if (ap && cam->frame_index == 0u) { pt_launch_adaptive_restart(ms, blocks, band, mom); c->ad_rounds = 0; }

@@ -245,6 +245,7 @@ __global__ __launch_bounds__(BLOCK) void k_repack(const uint32_t *__restrict__ c
         const float4 o = ld_stream(&from.O[q]), d = ld_stream(&from.D[q]);
         const float2 c = ld_stream(&from.C[q]);
         st_stream(&to.O[j], o); st_stream(&to.D[j], d); st_stream(&to.C[j], c);
+        if (from.W) to.W[j] = from.W[q];
         pid[j] = q;
     }
 }

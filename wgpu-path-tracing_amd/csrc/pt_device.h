@@ -24,6 +24,15 @@
 #define PT_LEAF_OFF_BITS 26u
 #define PT_LEAF_OFF_MASK ((1u << PT_LEAF_OFF_BITS) - 1u)
 
+// The environment map (ptmi_upload_environment; pt_env.h has the functions that read it). tab NULL: none uploaded.
+struct DevEnv {
+    const float4 *tab;          // per texel (r, g, b, c): the radiance and c = P_t N / (2 pi^2), the texel's density over (u, v)
+    const uint2 *alias;         // per entry (bits(prob), alias): the alias table over the w * h texels (NULL: never sampled)
+    uint32_t w, h;
+    uint32_t sampled;           // 1: next-event estimation picks it as light number n_lights, and bounce rays carry an MIS weight
+    float intensity, rotation;  // radiance scale; radians about +Y added to the azimuth
+};
+
 struct DevScene;
 struct DevScene {
     const ptmi_triangle *tris;  uint32_t n_tris;
@@ -64,6 +73,7 @@ struct DevScene {
     unsigned long long *verify_stat;    // += rays whose winner failed its reference leaf's box and were traced again
     const DevScene *self;       // this description in device memory (the own-leaf kernels read it from there, not from kernel arguments)
     const float4 *shade_tab;    // the shade tables (below): what `shade` stages into LDS
+    DevEnv env;                 // the environment map behind every miss (tab NULL: none, a miss adds throughput * 0)
 };
 
 // ---- shade tables: the records `shade` reads per hit that are the same for the whole scene, in one blob built at upload ----
@@ -89,6 +99,7 @@ PT_HD int pt_shade_stage(uint32_t n_mats, uint32_t n_lights) {
 // ---- path state: 56 B per path, four streams indexed by path id (O / D / C: by queue slot after the repack, ShadeParams) ----
 //   O = (origin.xyz, bits(rng state))   D = (direction.xyz, throughput.x)      the two float4 `extend` reads
 //   C = (throughput.y, throughput.z)    L = (radiance.xyz, 0)
+// and, only while a sampled environment is in place, W: the MIS weight of the environment's radiance should this ray miss (4 B).
 // Radiance L and the contribution SC of a shadow record have three lanes and are stored as three floats.
 // SC (read and written in queue-slot order) sits at 12-byte stride. L is read-modify-written by path id, scattered, and its
 // stride is chosen per dispatch (DevPaths::l_stride, in floats): 3 where the scene lives in LDS, 4 where the traversal
@@ -98,6 +109,7 @@ PT_HD int pt_shade_stage(uint32_t n_mats, uint32_t n_lights) {
 struct rgb_sc { float x, y, z; };
 struct DevPaths {
     float4 *O, *D; float2 *C; float *L; uint32_t l_stride = 3;
+    float *W = nullptr;         // NULL while no environment is sampled (a miss then takes the weight 1)
     // stride 4 means whole 16-byte accesses (a 12-byte access is issued as two requests: with stride 4 and 12-byte accesses
     // raygen's store of L takes 1.9 instead of 1.1 ms per 64 spp, and config 3 loses the same 5 % as with stride 3)
     __device__ __forceinline__ rgb_sc ldL(uint32_t p) const {
@@ -259,7 +271,7 @@ void pt_launch_shade_fast(hipStream_t s, int blocks, const DevScene &sc, DevPath
 // ordered stream compaction of the survivors: masks -> next queue + its count, plus statistics
 // (tiles = ceil(capacity / pt_compact_tile_slots()) + 1: one workgroup per tile of ballot words)
 uint32_t pt_compact_tile_slots(void);
-// the repack: queue entry j (path id q, j < *count) -> to.O / D / C[j] = from.O / D / C[q], pid[j] = q
+// the repack: queue entry j (path id q, j < *count) -> to.O / D / C[j] = from.O / D / C[q] (W too, where there is one), pid[j] = q
 void pt_launch_repack(hipStream_t s, int blocks, const uint32_t *count, const uint32_t *queue, DevPaths from, DevPaths to,
                       uint32_t *pid);
 void pt_launch_compact(hipStream_t s, int tiles, const uint32_t *queue, const uint32_t *count,

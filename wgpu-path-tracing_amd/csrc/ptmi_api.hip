@@ -28,15 +28,19 @@ constexpr size_t kLaneBytes[kLaneBufs] = {
     4, 4,                                          // kQueue0, kQueue1
     1,                                             // kOcc
     32,                                            // kAovRec
+    4, 4,                                          // kPathW, kTailW
 };
 // bytes of device memory a path of a batch takes in ensure_capacity: the per-path arrays and one byte for the two masks (2 x 8 B per 64
 // paths). The automatic batch size and its out-of-memory retry (ptmi_dispatch) rely on it.
-constexpr size_t lane_bytes_per_path(bool aov) {
+// the arrays that exist only while something is on: the first-hit records (aov), the environment's weights (env_w)
+constexpr bool lane_buf_wanted(int k, bool aov, bool env_w) { return k == kAovRec ? aov : k == kPathW || k == kTailW ? env_w : true; }
+constexpr size_t lane_bytes_per_path(bool aov, bool env_w) {
     size_t n = 1;
-    for (int k = 0; k < kLaneBufs; k++) if (k != kAovRec || aov) n += kLaneBytes[k];
+    for (int k = 0; k < kLaneBufs; k++) if (lane_buf_wanted(k, aov, env_w)) n += kLaneBytes[k];
     return n;
 }
-static_assert(lane_bytes_per_path(false) == 214 && lane_bytes_per_path(true) == 246, "the automatic frames_per_batch moves with these");
+static_assert(lane_bytes_per_path(false, false) == 214 && lane_bytes_per_path(true, false) == 246 && lane_bytes_per_path(false, true) == 222,
+              "the automatic frames_per_batch moves with these");
 
 // the typed members that kernels receive, as views of Lane::buf
 void lane_views(Lane &ln) {
@@ -51,6 +55,7 @@ void lane_views(Lane &ln) {
     }
     at(kTailO, ln.tail.O); at(kTailD, ln.tail.D); at(kTailC, ln.tail.C); at(kPid, ln.pid);
     at(kOcc, ln.d_occ); at(kAovRec, ln.aov);
+    at(kPathW, ln.paths.W); at(kTailW, ln.tail.W);
 }
 
 void free_batch(Lane &ln) {
@@ -150,11 +155,11 @@ hipError_t sync_all(ptmi_ctx *c) {
     return e;
 }
 
-size_t bytes_per_path(bool aov) { return lane_bytes_per_path(aov); }
+size_t bytes_per_path(bool aov, bool env_w) { return lane_bytes_per_path(aov, env_w); }
 
 int ensure_capacity(ptmi_ctx *c, Lane &ln, size_t n) {
-    const bool aov = c->aov_mask != 0;
-    if (n <= ln.cap && (!aov || ln.aov)) return PTMI_OK;
+    const bool aov = c->aov_mask != 0, env_w = c->sc.env.sampled != 0;
+    if (n <= ln.cap && (!aov || ln.aov) && (!env_w || ln.paths.W)) return PTMI_OK;
     HIP_TRY(c, sync_all(c));
     free_batch(ln);
     const size_t cap = (n + 1023) & ~(size_t)1023;
@@ -164,7 +169,7 @@ int ensure_capacity(ptmi_ctx *c, Lane &ln, size_t n) {
     hipError_t e = hipSuccess;
     size_t bytes = 0;
     for (int k = 0; k < kLaneBufs && e == hipSuccess; k++)
-        if (k != kAovRec || aov) e = hipMalloc(&ln.buf[k], bytes = cap * kLaneBytes[k]);
+        if (lane_buf_wanted(k, aov, env_w)) e = hipMalloc(&ln.buf[k], bytes = cap * kLaneBytes[k]);
     if (e == hipSuccess) e = hipMalloc(&ln.alive, bytes = words * 8);
     if (e == hipSuccess) e = hipMalloc(&ln.shadowm, bytes = words * 8);
     if (e == hipSuccess) e = hipMalloc(&ln.word_off, bytes = 2 * tiles * 4);
@@ -315,7 +320,7 @@ int ptmi_destroy(ptmi_ctx *c) {
         if (ln.side) (void)hipStreamDestroy(ln.side);
     }
     for (void *&p : c->buf) dfree(p);
-    dfree(c->d_atlas);
+    dfree(c->d_atlas); dfree(c->d_env); dfree(c->d_env_alias);
     drop_planes(c, kAllPlanes);
     dfree(c->d_stats); dfree(c->d_scene); dfree(c->ad.ctl); dfree(c->ad.acc); dfree(c->d_reproject);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);

@@ -4,6 +4,7 @@
 //   traverse_pick.hip  which variant a traversal kernel runs as, and the launch of one
 //   dispatch.hip       the wavefront dispatch loop, adaptive sampling, reprojection, event timing
 //   debug_stages.hip   the per-stage debug entry points
+//   environment.hip    the environment map: its tables, upload and removal, its debug entry points
 #pragma once
 #include "ptmi.h"
 #include "pt_device.h"
@@ -29,7 +30,7 @@ float4 *pt_ctx_output(ptmi_ctx *c);
 int pt_ctx_device(const ptmi_ctx *c);
 int pt_ctx_cus(const ptmi_ctx *c);
 
-// What follows is shared by the five files above only: hidden, so that the library exports the C ABI and the pt_* names and no helper.
+// What follows is shared by the six files above only: hidden, so that the library exports the C ABI and the pt_* names and no helper.
 // (A definition takes the visibility of the namespace block it stands in, so every block of pt_host is opened with PT_HOST.)
 #define PT_HOST namespace pt_host __attribute__((visibility("hidden")))
 PT_HOST {
@@ -68,6 +69,8 @@ enum LaneBuf {
     kQueue0, kQueue1,
     kOcc,                                          // occlusion bytes (ptmi_debug_occluded)
     kAovRec,                                       // first-hit records of bounce 0 (k_shade<true>); only while AOV planes are on
+    kPathW, kTailW,                                // the environment's MIS weight of a bounce ray, by path and (after the repack) by queue
+                                                   // slot; only while a sampled environment is in place
     kLaneBufs
 };
 
@@ -110,6 +113,9 @@ struct ptmi_ctx {
     // scene (bindings 1, 2, 4, 5, 6)
     void *buf[kSceneBufs] = {};                        // indexed by SceneBuf (absent: NULL)
     void *d_atlas = nullptr;
+    void *d_env = nullptr, *d_env_alias = nullptr;     // the environment map's texel and alias tables (DevScene::env points at them)
+    double env_weight_sum = 0.0;                       // sum of the map's sampling weights (0: all black, never sampled)
+    bool env_lookup_only = false;                      // ptmi_environment.sample = 1
     DevScene *d_scene = nullptr;                       // sc in device memory (DevScene::self), rewritten whenever sc changes
     DevScene sc{};
     bool have_scene = false;
@@ -153,7 +159,7 @@ template <class T> T *plane_as(const ptmi_ctx *c, FramePlane k) { return static_
 // ptmi_api.hip
 void default_options(ptmi_options &o);
 hipError_t sync_all(ptmi_ctx *c);
-size_t bytes_per_path(bool aov);
+size_t bytes_per_path(bool aov, bool env_w);
 int ensure_capacity(ptmi_ctx *c, Lane &ln, size_t n);
 enum PlaneGroup { kWithFrame, kByDenoise, kByAdaptive, kByReproject, kByBlit };     // when a plane is made (the kFrame table)
 constexpr uint32_t bit(FramePlane k) { return 1u << k; }                            // sets of planes: a bit per FramePlane

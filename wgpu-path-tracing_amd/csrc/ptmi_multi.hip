@@ -268,6 +268,20 @@ int ptmi_multi_upload_atlas(ptmi_multi *m, const void *texels, uint32_t w, uint3
     return each_ctx(m, "ptmi_upload_atlas", ptmi_upload_atlas, texels, w, h, fmt);
 }
 
+int ptmi_multi_upload_environment(ptmi_multi *m, const void *texels, uint32_t w, uint32_t h, int fmt, const ptmi_environment *params) {
+    if (!m) return PTMI_E_INVALID;
+    if (texels && w != 0 && h != 0) {       // checked once, before any device changes: a rejected map leaves every shard's in place
+        const int rc = ptmi_debug_env_table(texels, w, h, fmt, nullptr, nullptr, nullptr, nullptr);
+        if (rc) return mfail(m, rc, "%s", ptmi_last_error(nullptr));
+    }
+    return each_ctx(m, "ptmi_upload_environment", ptmi_upload_environment, texels, w, h, fmt, params);
+}
+
+int ptmi_multi_set_environment(ptmi_multi *m, const ptmi_environment *params) {
+    if (!m) return PTMI_E_INVALID;
+    return each_ctx(m, "ptmi_set_environment", ptmi_set_environment, params);
+}
+
 int ptmi_multi_resize(ptmi_multi *m, uint32_t w, uint32_t h) {
     if (!m) return PTMI_E_INVALID;
     int rc = each_ctx(m, "ptmi_resize", ptmi_resize, w, h);

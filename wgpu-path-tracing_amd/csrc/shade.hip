@@ -10,6 +10,7 @@
 // each (64 paths -> one u64 word) for the ordered compaction kernel.
 #include "pt_device.h"
 #include "pt_math.h"
+#include "pt_env.h"
 
 namespace {
 
@@ -261,14 +262,29 @@ struct LightSample { v3 intensity; v3 wi; float pdf; float dist; bool traced; };
 
 // sampleLight, pt.wgsl:374-489, without its traversal: the occlusion test is the
 // `shadow` kernel's; pdf = 0 means "no record" (the :413-415 early-out).
-template <int STAGE>
-PT_DEV LightSample sample_light(const DevScene &sc, const ShadeTabs<STAGE> &tabs, uint32_t &rng, v3 hit_pos) {
+// ENV: a sampled environment is light number n_lights — one more light to pick from, for every light's 1 / n. Picked, it takes four
+// draws (pt_env.h env_sample) and leaves a directional sample: any hit occludes. inv_n goes back to the caller for the MIS weight of
+// the bounce ray (k_shade).
+template <int STAGE, bool ENV>
+PT_DEV LightSample sample_light(const DevScene &sc, const ShadeTabs<STAGE> &tabs, uint32_t &rng, v3 hit_pos, float &inv_n_out) {
     LightSample ls;
     ls.intensity = mk3(0.0f, 0.0f, 0.0f); ls.wi = mk3(0.0f, 0.0f, 0.0f); ls.pdf = 0.0f; ls.dist = -1.0f; ls.traced = false;
-    const uint32_t nl = sc.n_lights;
+    const uint32_t nl = ENV ? sc.n_lights + sc.env.sampled : sc.n_lights;
     const uint32_t li = rng_int(rng, 0u, nl - 1u);
+    if (ENV && li == sc.n_lights) {
+        const float inv_n = rcp1((float)nl);
+        inv_n_out = inv_n;
+        const float r1 = rng_f(rng), r2 = rng_f(rng), r3 = rng_f(rng), r4 = rng_f(rng);
+        uint32_t texel;
+        const EnvSample es = env_sample(sc.env, r1, r2, r3, r4, ls.wi, texel);
+        ls.intensity = es.le;
+        ls.pdf = es.pdf * inv_n;
+        ls.traced = true;
+        return ls;
+    }
     const ptmi_light lt = tabs.light(sc, li);
     const float inv_n = rcp1((float)nl);
+    if (ENV) inv_n_out = inv_n;
     if (lt.light_type == PTMI_LIGHT_DIRECTIONAL) {
         ls.wi = normalize3(neg3(ld3(lt.position)));
         ls.intensity = scale3(ld3(lt.color), lt.intensity);
@@ -333,7 +349,12 @@ constexpr int SBLOCK = 256;
 // STAGE (PT_STAGE_*, chosen per launch by pt_shade_stage): the shade tables the workgroup copies into LDS before its first segment. On
 // the scenes measured every lane of every bounce fetched its material, its light and the light's triangle from a handful of records
 // through its own vector loads, three dependent rounds behind the hit's triangle; from LDS they cost ds_reads on another unit.
-template <bool AOV, int STAGE>
+//
+// ENV: the instantiations launched while an environment map is in place (DevScene::env). A ray that misses — a camera
+// ray too — adds throughput * (W * Le(direction)) where an emissive hit's addition goes; while the map is sampled it is one more light
+// for next-event estimation, and the bounce ray carries W, the power-heuristic weight of its own density against the environment's at
+// its direction, in P.W for the bounce that may miss. Without ENV the kernel is the one it was: no branch of it reads the map.
+template <bool AOV, int STAGE, bool ENV>
 __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, DevPaths P, const uint32_t *__restrict__ queue,
                                                   const uint32_t *__restrict__ count_ptr,
                                                   const float2 *__restrict__ hits, DevShadow S,
@@ -386,8 +407,10 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                         P.stL(p, l.x + e.x, l.y + e.y, l.z + e.z);
                     }
                 } else {
-                    if (sp.do_mis && sc.n_lights > 0u && hit.transmission == 0.0f && hit.is_front) {   // pt.wgsl:661
-                        LightSample ls = sample_light(sc, tabs, rng, hit.position);
+                    float inv_n = 0.0f;                                       // ENV: set where next-event estimation ran
+                    const bool have_light = ENV ? sc.n_lights + sc.env.sampled > 0u : sc.n_lights > 0u;
+                    if (sp.do_mis && have_light && hit.transmission == 0.0f && hit.is_front) {   // pt.wgsl:661
+                        LightSample ls = sample_light<STAGE, ENV>(sc, tabs, rng, hit.position, inv_n);
                         if (ls.pdf > 0.0f) {
                             v3 V = neg3(normalize3(rd));
                             v4 ev = eval_bsdf(hit, hit.normal, V, ls.wi, hit.is_front);
@@ -427,7 +450,42 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                             st_stream(&P.O[q], make_float4(no.x, no.y, no.z, __uint_as_float(rng)));
                             st_stream(&P.D[q], make_float4(nd.x, nd.y, nd.z, thr.x));
                             st_stream(&P.C[q], make_float2(thr.y, thr.z));
+                            if (ENV && P.W) {
+                                // what the environment's radiance weighs if this ray misses: where this vertex's next-event sample
+                                // could have picked the same direction, the power heuristic of the two densities; else 1
+                                float w = 1.0f;
+                                if (inv_n != 0.0f) w = power_heuristic(1.0f, ev.w, 1.0f, env_lookup(sc.env, nd).pdf * inv_n);
+                                P.W[q] = w;
+                            }
                         }
+                    }
+                }
+            } else if (ENV) {                                                 // a miss sees the environment, the camera ray too
+                if (AOV) {
+                    st_stream(&aov[2 * (size_t)i], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+                    st_stream(&aov[2 * (size_t)i + 1], make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu)));
+                }
+                const float4 d4 = ld_stream(&P.D[q]);
+                v3 thr = mk3(1.0f, 1.0f, 1.0f);
+                float w = 1.0f;
+                if (sp.bounce != 0u) {
+                    const float2 c2 = ld_stream(&P.C[q]);
+                    thr = mk3(d4.w, c2.x, c2.y);
+                    if (P.W) w = P.W[q];
+                }
+                const v3 le = env_lookup(sc.env, xyz(d4)).le;
+                const v3 e = mk3(thr.x * (w * le.x), thr.y * (w * le.y), thr.z * (w * le.z));
+                // a zero leaves the radiance as it is (x + 0 = x): nothing to add, as without a map; a throughput that is not finite
+                // gives NaN or infinity and is added, as without a map
+                if ((e.x != 0.0f) | (e.y != 0.0f) | (e.z != 0.0f)) {
+                    const uint32_t p = sp.pid ? sp.pid[q] : q;
+                    if (sp.emit_records) {
+                        rec_d.w = __uint_as_float(p);                                 // rec_o = (0, 0, 0, -2)
+                        rec_c = rgb_sc{e.x, e.y, e.z};
+                        shadow = true; emitted = true;
+                    } else {
+                        const rgb_sc l = P.ldL(p);
+                        P.stL(p, l.x + e.x, l.y + e.y, l.z + e.z);
                     }
                 }
             } else if (AOV) {                                                 // bounce 0 only: a camera ray that misses
@@ -482,22 +540,24 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
 #define PT_LAUNCH_SHADE pt_launch_shade
 #endif
 namespace {
-template <bool AOV, int STAGE>
+template <bool AOV, int STAGE, bool ENV>
 void launch_shade(hipStream_t s, int blocks, const DevScene &sc, DevPaths p, const uint32_t *queue, const uint32_t *count,
                   const float2 *hits, DevShadow sh, uint64_t *alive_mask, uint64_t *shadow_mask, ShadeParams sp, float4 *aov) {
     const size_t lds = (((STAGE & PT_STAGE_MATS) ? pt_tab_mats_q(sc.n_mats) : 0) + ((STAGE & PT_STAGE_LIGHTS) ? pt_tab_lights_q(sc.n_lights) : 0)) * 16;
-    hipLaunchKernelGGL((k_shade<AOV, STAGE>), dim3(blocks), dim3(SBLOCK), lds, s, sc, p, queue, count, hits, sh, alive_mask,
+    hipLaunchKernelGGL((k_shade<AOV, STAGE, ENV>), dim3(blocks), dim3(SBLOCK), lds, s, sc, p, queue, count, hits, sh, alive_mask,
                        shadow_mask, sp, aov);
 }
 }  // namespace
-// the tables each launch stages: pt_shade_stage of the scene's counts (what fits PT_SHADE_LDS_BUDGET), for both instantiations
+// the tables each launch stages: pt_shade_stage of the scene's counts (what fits PT_SHADE_LDS_BUDGET), for every instantiation; ENV
+// while an environment map is in place
 void PT_LAUNCH_SHADE(hipStream_t s, int blocks, const DevScene &sc, DevPaths p, const uint32_t *queue,
                      const uint32_t *count, const float2 *hits, DevShadow sh, uint64_t *alive_mask,
                      uint64_t *shadow_mask, ShadeParams sp, float4 *aov) {
 #define PT_SHADE_CASE(STAGE)                                                                                              \
     case STAGE:                                                                                                           \
-        (aov ? launch_shade<true, STAGE> : launch_shade<false, STAGE>)(s, blocks, sc, p, queue, count, hits, sh, alive_mask, \
-                                                                       shadow_mask, sp, aov);                             \
+        (sc.env.tab ? (aov ? launch_shade<true, STAGE, true> : launch_shade<false, STAGE, true>)                          \
+                    : (aov ? launch_shade<true, STAGE, false> : launch_shade<false, STAGE, false>))(                      \
+            s, blocks, sc, p, queue, count, hits, sh, alive_mask, shadow_mask, sp, aov);                                  \
         break;
     switch (pt_shade_stage(sc.n_mats, sc.n_lights)) {
         PT_SHADE_CASE(0) PT_SHADE_CASE(PT_STAGE_MATS) PT_SHADE_CASE(PT_STAGE_LIGHTS) PT_SHADE_CASE(PT_STAGE_MATS | PT_STAGE_LIGHTS)

@@ -198,6 +198,26 @@ static napi_value js_upload_atlas(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* uploadEnvironment(handle, float32 RGBA texels | null, width, height, {intensity, rotation (radians), sample}) */
+static napi_value js_upload_environment(napi_env env, napi_callback_info info) {
+    napi_value argv[5], v;
+    handle *h = get_handle(env, info, 5, argv);
+    if (!h) return NULL;
+    void *p; size_t n; uint32_t w = 0, hh = 0; double d;
+    ptmi_environment prm = {0};
+    napi_valuetype t;
+    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
+    napi_get_value_uint32(env, argv[2], &w); napi_get_value_uint32(env, argv[3], &hh);
+    if (napi_typeof(env, argv[4], &t) == napi_ok && t == napi_object) {
+        if (napi_get_named_property(env, argv[4], "intensity", &v) == napi_ok && napi_get_value_double(env, v, &d) == napi_ok) prm.intensity = (float)d;
+        if (napi_get_named_property(env, argv[4], "rotation", &v) == napi_ok && napi_get_value_double(env, v, &d) == napi_ok) prm.rotation = (float)d;
+        prm.sample = get_u32_prop(env, argv[4], "sample", 0);
+    }
+    if (p && n / 16 / (w ? w : 1) < hh) { napi_throw_range_error(env, NULL, "environment buffer too small"); return NULL; }
+    CALL(env, h, upload_environment, p, w, hh, PTMI_ATLAS_RGBA32F, &prm);
+    return NULL;
+}
+
 static napi_value js_resize(napi_env env, napi_callback_info info) {
     napi_value argv[3];
     handle *h = get_handle(env, info, 3, argv);
@@ -650,7 +670,7 @@ static napi_value js_abi_version(napi_env env, napi_callback_info info) {
 static napi_value init(napi_env env, napi_value exports) {
     static const struct { const char *name; napi_callback fn; } fns[] = {
         {"abiVersion", js_abi_version}, {"create", js_create}, {"multiCreate", js_multi_create}, {"destroy", js_destroy},
-        {"uploadScene", js_upload_scene}, {"uploadAtlas", js_upload_atlas}, {"resize", js_resize}, {"setOptions", js_set_options},
+        {"uploadScene", js_upload_scene}, {"uploadAtlas", js_upload_atlas}, {"uploadEnvironment", js_upload_environment}, {"resize", js_resize}, {"setOptions", js_set_options},
         {"dispatch", js_dispatch}, {"gather", js_gather}, {"synchronize", js_synchronize}, {"throttle", js_throttle},
         {"readOutput", js_read_output}, {"writeOutput", js_write_output}, {"setAovs", js_set_aovs}, {"readAov", js_read_aov},
         {"blit", js_blit}, {"getStats", js_get_stats}, {"resetStats", js_reset_stats},

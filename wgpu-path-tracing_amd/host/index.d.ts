@@ -59,6 +59,9 @@ export class Renderer {
   camera: CameraCPU;
   addOnUpdate(callback: (deltaTime: number) => void): void;
   loadModel(model: string | SceneData | { blobs: SceneBlobs; atlas?: Atlas | null }, atlas?: Atlas): Promise<void>;
+  /** the environment map behind every miss: float32 RGBA texels, equirectangular, row 0 at the +Y pole; null removes it.
+   *  Restarts accumulation. */
+  setEnvironment(texels: Float32Array | null, width?: number, height?: number, opts?: EnvironmentOptions): void;
   renderFrame(frames?: number): void;
   start(): void;
   stop(): void;
@@ -115,6 +118,16 @@ export const pack: {
   packBVH(n: BVHNode[]): ArrayBuffer; packLights(l: LightCPU[]): ArrayBuffer;
   packCamera(c: CameraCPU, out?: ArrayBuffer): ArrayBuffer; packScene(s: SceneData): SceneBlobs;
 };
+export interface EnvironmentOptions {
+  /** radiance scale; 0 / undefined: 1 */
+  intensity?: number;
+  /** radians about +Y, added to the azimuth */
+  rotation?: number;
+  /** 0 (default): next-event estimation samples the map; 1: misses look it up, nothing samples it */
+  sample?: 0 | 1;
+}
+/** hdr_decode.js — a Radiance .hdr (RGBE) file as float32 RGBA texels, row 0 on top; throws on a malformed or truncated file */
+export function decodeHDR(bytes: Uint8Array | ArrayBuffer): { width: number; height: number; data: Float32Array };
 export function readSceneFile(path: string): { blobs: SceneBlobs; atlas: Atlas | null };
 /** atlas.js — src/renderer/atlas.ts (PackedAtlas): the canvas as RGBA8 and as rgba16float texels, rects per material */
 export interface PackedAtlas {

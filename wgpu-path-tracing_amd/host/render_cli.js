@@ -5,11 +5,14 @@
  * (renderer.ts:415-454: one dispatch per frame, frameIndex++), headless:
  *   node render_cli.js <scene.ptscene> <out.f32> [--width W --height H --frames N --bounces B --mis 0|1
  *                       --aperture A --focus F --batch K --png out.png --denoise
- *                       --adaptive THRESHOLD --max-frames N --rounds R]
+ *                       --adaptive THRESHOLD --max-frames N --rounds R
+ *                       --env file.hdr --env-intensity X --env-rotation DEGREES --env-sample 0|1]
  * --batch K traces K frames per dispatch instead of one. --denoise keeps the denoiser's planes and makes --png the tone-mapped
  * denoised image (include/ptmi.h ptmi_denoise, default parameters). --adaptive renders to a noise level instead of --frames
  * (include/ptmi.h ptmi_dispatch_adaptive): rounds until none lists a pixel, or --rounds R of them; the JSON line then also holds
- * adaptive: { samples, minCount, maxCount, rounds }. Writes W*H*4 float32 (the output buffer, raw also with
+ * adaptive: { samples, minCount, maxCount, rounds }. --env lights the scene with a Radiance .hdr environment map (hdr_decode.js;
+ * include/ptmi.h ptmi_upload_environment): equirectangular, scaled by --env-intensity, turned by --env-rotation degrees about +Y;
+ * --env-sample 1 only looks it up. Writes W*H*4 float32 (the output buffer, raw also with
  * --denoise) and prints one JSON line with the statistics.
  */
 var fs = require('fs');
@@ -30,7 +33,13 @@ var r = new host.Renderer({ width: W, height: H, options: { maxBounces: arg('bou
 r.camera.aperture = arg('aperture', r.camera.aperture);
 r.camera.focusDistance = arg('focus', r.camera.focusDistance);
 if (denoise) r.setDenoise(true);
+var envAt = process.argv.indexOf('--env');
 r.loadModel(scenePath).then(function () {
+  if (envAt >= 0) {
+    var env = require('./hdr_decode').decodeHDR(fs.readFileSync(process.argv[envAt + 1]));
+    r.setEnvironment(env.data, env.width, env.height,
+                     { intensity: arg('env-intensity', 1), rotation: arg('env-rotation', 0) * Math.PI / 180, sample: arg('env-sample', 0) });
+  }
   var t0 = Date.now();
   var status = null;
   if (adaptive) {

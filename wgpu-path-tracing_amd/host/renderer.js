@@ -182,6 +182,19 @@ Renderer.prototype.destroy = function () {
 };
 
 /** renderer.ts:496-510 */
+/**
+ * The environment map behind every miss (include/ptmi.h ptmi_upload_environment): float32 RGBA texels, equirectangular, row 0 at the
+ * +Y pole. opts: { intensity (0 / undefined: 1), rotation (radians about +Y), sample (0: next-event estimation samples it, 1: lookup
+ * only) }. texels null removes it. Accumulation restarts: the picture under another sky is another picture.
+ */
+Renderer.prototype.setEnvironment = function (texels, width, height, opts) {
+  opts = opts || {};
+  if (texels && !(texels instanceof Float32Array)) throw new TypeError('setEnvironment: texels must be a Float32Array of RGBA');
+  this.addon.uploadEnvironment(this.ctx, texels || null, texels ? width : 0, texels ? height : 0,
+                               { intensity: opts.intensity || 0, rotation: opts.rotation || 0, sample: opts.sample ? 1 : 0 });
+  this.frameIndex = 0;
+};
+
 Renderer.prototype.resize = function (width, height) {
   this.width = width; this.height = height;
   this.camera.aspect = width / height;
@@ -369,5 +382,5 @@ function setupRenderer(options) {
 }
 
 module.exports = { Renderer: Renderer, setupRenderer: setupRenderer, pack: pack, readSceneFile: sceneFile.readSceneFile,
-  atlas: require('./atlas'), decodePNG: require('./png_decode').decodePNG,
+  atlas: require('./atlas'), decodePNG: require('./png_decode').decodePNG, decodeHDR: require('./hdr_decode').decodeHDR,
   decodeJPEG: require('./jpeg_decode').decodeJPEG, Controller: require('./controller').Controller };

@@ -34,6 +34,8 @@ EXPORTS = [
     "ptmi_denoise", "ptmi_denoised_device_ptr", "ptmi_blit_denoised",
     "ptmi_dispatch_adaptive", "ptmi_adaptive_status",
     "ptmi_reproject", "ptmi_reproject_status", "ptmi_debug_center_rays",
+    "ptmi_upload_environment", "ptmi_set_environment", "ptmi_environment_status", "ptmi_multi_upload_environment",
+    "ptmi_multi_set_environment", "ptmi_debug_env_lookup", "ptmi_debug_env_sample", "ptmi_debug_env_table",
 ]
 MULTI_LOOPBACK = 1
 # first-hit planes (include/ptmi.h ptmi_set_aovs): name -> (bit, numpy dtype, channels)
@@ -93,6 +95,20 @@ class ReprojectStatus(ctypes.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class Environment(ctypes.Structure):
+    """ptmi_environment; intensity 0 picks 1 (include/ptmi.h)"""
+    _fields_ = [("intensity", ctypes.c_float), ("rotation", ctypes.c_float), ("sample", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 5)]
+
+
+class EnvironmentStatus(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("sampled", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("weight_sum", ctypes.c_double)]
+
+    def as_dict(self):
+        return {"width": int(self.width), "height": int(self.height), "sampled": int(self.sampled), "weight_sum": float(self.weight_sum)}
+
+
 class Stats(ctypes.Structure):
     _fields_ = [("paths", ctypes.c_uint64), ("segments", ctypes.c_uint64), ("shadow_rays", ctypes.c_uint64),
                 ("dispatches", ctypes.c_uint64), ("frames", ctypes.c_uint64),
@@ -123,6 +139,8 @@ _SHARED = {
     "throttle": [ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)], "read_output": [ctypes.c_void_p, ctypes.c_size_t],
     "write_output": [ctypes.c_void_p, ctypes.c_size_t], "blit": [ctypes.c_void_p, ctypes.c_size_t] * 2,
     "get_stats": [ctypes.c_void_p],
+    "upload_environment": [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p],
+    "set_environment": [ctypes.c_void_p],
 }
 _lib = None
 
@@ -182,6 +200,10 @@ def load():
         L.ptmi_reproject.argtypes = [vp, vp, vp, vp]
         L.ptmi_reproject_status.argtypes = [vp, vp]
         L.ptmi_debug_center_rays.argtypes = [vp, vp, vp, vp, sz]
+        L.ptmi_environment_status.argtypes = [vp, vp]
+        L.ptmi_debug_env_lookup.argtypes = [vp, u32, vp, vp]
+        L.ptmi_debug_env_sample.argtypes = [vp, u32, vp, vp, vp, vp]
+        L.ptmi_debug_env_table.argtypes = [vp, u32, u32, ctypes.c_int, vp, vp, vp, ctypes.POINTER(ctypes.c_double)]
         _lib = L
     return _lib
 
@@ -200,6 +222,31 @@ def image_stats(scene):
     keys = ("wide_nodes", "leaves", "depth", "quantised_nodes", "stream_dwords", "containment_violations",
             "mean_area_growth", "stream_mismatches")
     return dict(zip(keys, list(out)))
+
+
+def _env_texels(texels):
+    """(texels as a contiguous (H, W, 4) float16 / float32 array, its PTMI_ATLAS_* format)"""
+    a = np.ascontiguousarray(texels)
+    if a.dtype not in (np.float16, np.float32):
+        a = a.astype(np.float32)
+    assert a.ndim == 3 and a.shape[2] == 4, "an environment is (H, W, 4) RGBA texels"
+    return a, ATLAS_RGBA16F if a.dtype == np.float16 else ATLAS_RGBA32F
+
+
+def env_table(texels, fmt=None, width=None, height=None):
+    """Host-only: the tables upload_environment would build (include/ptmi.h: ptmi_debug_env_table):
+    (c [H, W] f32, prob [H * W] f32, alias [H * W] u32, weight_sum). fmt / width / height override what the array says (for tests)."""
+    L = load()
+    a, f = _env_texels(texels)
+    h, w = a.shape[:2]
+    w, h, f = (w if width is None else width), (h if height is None else height), (f if fmt is None else fmt)
+    n = a.shape[0] * a.shape[1]
+    c, prob, alias = np.zeros(a.shape[:2], np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint32)
+    ws = ctypes.c_double(0.0)
+    rc = L.ptmi_debug_env_table(_p(a), w, h, f, _p(c), _p(prob), _p(alias), ctypes.byref(ws))
+    if rc != 0:
+        raise PtmiError(rc, L.ptmi_last_error(None).decode())
+    return c, prob, alias, ws.value
 
 
 class ImageInfo(ctypes.Structure):
@@ -303,6 +350,21 @@ class _Handle:
             assert a.ndim == 3 and a.shape[2] == 4 and a.flags.c_contiguous
             fmt = ATLAS_RGBA16F if a.dtype == np.float16 else ATLAS_RGBA32F
             self._ck(self._c.upload_atlas(self.h, _p(a), a.shape[1], a.shape[0], fmt))
+
+    def upload_environment(self, texels, intensity=0.0, rotation=0.0, sample=0, reserved=(0, 0, 0, 0, 0)):
+        """The environment map behind every miss (include/ptmi.h ptmi_upload_environment): (H, W, 4) float16 / float32 texels,
+        equirectangular, row 0 at the +Y pole. texels None removes it."""
+        if texels is None:
+            self._ck(self._c.upload_environment(self.h, None, 0, 0, 0, None))
+            return
+        a, fmt = _env_texels(texels)
+        prm = Environment(intensity, rotation, sample, (ctypes.c_uint32 * 5)(*reserved))
+        self._ck(self._c.upload_environment(self.h, _p(a), a.shape[1], a.shape[0], fmt, ctypes.byref(prm)))
+
+    def set_environment(self, intensity=0.0, rotation=0.0, sample=0, reserved=(0, 0, 0, 0, 0)):
+        """intensity / rotation / sample of the map in place, without a re-upload"""
+        prm = Environment(intensity, rotation, sample, (ctypes.c_uint32 * 5)(*reserved))
+        self._ck(self._c.set_environment(self.h, ctypes.byref(prm)))
 
     def resize(self, width, height):
         self._ck(self._c.resize(self.h, width, height))
@@ -475,6 +537,26 @@ class Context(_Handle):
         o, d = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
         self._ck(self.L.ptmi_debug_center_rays(self.h, _p(camera), _p(o), _p(d), o.size))
         return o, d
+
+    # -- environment lighting (include/ptmi.h ptmi_upload_environment) ------------------------------------------
+    def environment_status(self):
+        st = EnvironmentStatus()
+        self._ck(self.L.ptmi_environment_status(self.h, ctypes.byref(st)))
+        return st
+
+    def debug_env_lookup(self, d):
+        """(Le.rgb, pdf) of each unit direction, (n, 4) float32"""
+        d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        out = np.zeros((len(d), 4), np.float32)
+        self._ck(self.L.ptmi_debug_env_lookup(self.h, len(d), _p(d), _p(out)))
+        return out
+
+    def debug_env_sample(self, r):
+        """the kernels' environment sampling on the uniforms r (n, 4): (directions (n, 3), (Le.rgb, density) (n, 4), texels (n,))"""
+        r = np.ascontiguousarray(r, np.float32).reshape(-1, 4)
+        d, out, tex = np.zeros((len(r), 3), np.float32), np.zeros((len(r), 4), np.float32), np.zeros(len(r), np.uint32)
+        self._ck(self.L.ptmi_debug_env_sample(self.h, len(r), _p(r), _p(d), _p(out), _p(tex)))
+        return d, out, tex
 
     def read_image(self):
         """The traversal image the last upload_scene put on the device (include/ptmi.h: ptmi_debug_read_image), as build_image()

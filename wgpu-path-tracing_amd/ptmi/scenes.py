@@ -513,6 +513,35 @@ def texture_edges(atlas_shape=(67, 29), fmt="f16"):
                    info={"atlas_shape": (W, H), "fmt": fmt, "probe_materials": sorted(m_probe.values())})
 
 
+def sky(w, h, kind="disc"):
+    """A procedural equirectangular environment map (native upload_environment): (h, w, 4) float32 RGBA, row 0 at the +Y pole, alpha 1.
+    kind: 'constant' — (0.3, 0.2, 0.1) everywhere; 'gradient' — a vertical gradient from a blue zenith over a pale horizon to a dark
+    ground; 'disc' — the gradient plus one small bright disc (a sun 35 degrees above the horizon, about 6 degrees across)."""
+    out = np.ones((h, w, 4), np.float32)
+    if kind == "constant":
+        out[..., :3] = (0.3, 0.2, 0.1)
+        return out
+    if kind not in ("gradient", "disc"):
+        raise ValueError(f"unknown sky kind {kind!r}: constant, gradient or disc")
+    theta = (np.arange(h) + 0.5) / h * np.pi
+    up = np.cos(theta)                                        # +1 at the zenith, -1 at the nadir
+    zenith, horizon, ground = np.array((0.15, 0.3, 0.8)), np.array((0.8, 0.8, 0.75)), np.array((0.12, 0.1, 0.08))
+    t = np.clip(up, 0.0, 1.0)[:, None] ** 0.5
+    rows = np.where(up[:, None] >= 0.0, horizon * (1.0 - t) + zenith * t, ground)
+    out[..., :3] = rows[:, None, :]
+    if kind == "disc":
+        phi = ((np.arange(w) + 0.5) / w - 0.5) * 2.0 * np.pi
+        d = np.stack([np.sin(theta)[:, None] * np.cos(phi)[None, :], np.broadcast_to(up[:, None], (h, w)),
+                      np.sin(theta)[:, None] * np.sin(phi)[None, :]], -1)
+        el, az = np.radians(35.0), np.radians(40.0)
+        sun = np.array((np.cos(el) * np.cos(az), np.sin(el), np.cos(el) * np.sin(az)))
+        inside = d @ sun >= np.cos(np.radians(3.0))
+        if not inside.any():                                  # a map too coarse for the disc: the texel that holds its centre
+            inside[np.unravel_index(np.argmax(d @ sun), inside.shape)] = True
+        out[inside, :3] = (60.0, 55.0, 45.0)
+    return out
+
+
 SCENES = {"cornell": cornell, "cornell_glass": lambda: cornell(glass=True), "cornell_enclosed": cornell_enclosed,
           "cornell_spheres": cornell_spheres, "grid_1m": grid_1m, "feature_box": feature_box, "deep_chain": deep_chain,
           "texture_edges": texture_edges, "texture_edges_f32": lambda: texture_edges(fmt="f32")}
