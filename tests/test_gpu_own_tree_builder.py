@@ -234,6 +234,79 @@ def test_device_image_is_sound_and_shares_the_host_padding(ctx, name, k):
     assert same_arrays(img[4], host[4])
 
 
+def requantised_words(info, wn):
+    """The three plane words of both children of every wide node [n, 2, 3], from the rule itself: on each axis the LARGEST plane
+    number whose plane fma(scale, k, origin), in float32, is <= the box's lower bound, and the SMALLEST whose plane is >= its upper
+    bound (an axis of scale 0 has plane 0 only). The double-precision quotient is a first guess that is then moved either way."""
+    qo = np.array(info.q_origin[:], np.float32); qs = np.array(info.q_scale[:], np.float32)
+    lo = np.stack([wn[:, 0:3], wn[:, 6:9]], axis=1)
+    hi = np.stack([wn[:, 3:6], wn[:, 9:12]], axis=1)
+
+    def plane(k):
+        return fmaf(qs, k.astype(np.float32), qo)
+
+    def search(v, below):
+        x = (v.astype(np.float64) - qo) / np.where(qs > 0, qs, np.float32(1)).astype(np.float64)
+        k = np.clip(np.floor(x) if below else np.ceil(x), 0, 65535).astype(np.int64)
+        for _ in range(16):
+            if below:
+                down = (k > 0) & (plane(k) > v)
+                up = ~down & (k < 65535) & (plane(np.minimum(k + 1, 65535)) <= v)
+            else:
+                up = (k < 65535) & (plane(k) < v)
+                down = ~up & (k > 0) & (plane(np.maximum(k - 1, 0)) >= v)
+            if not (down | up).any():
+                break
+            k = k - down + up
+        else:
+            raise AssertionError("the plane search did not settle")
+        return np.where(qs > 0, k, 0).astype(np.uint32)
+
+    ql, qh = search(lo, True), search(hi, False)
+    return np.stack([ql[..., 0] | (ql[..., 1] << 16), ql[..., 2] | (qh[..., 0] << 16), qh[..., 1] | (qh[..., 2] << 16)], axis=-1)
+
+
+def quantised_numbers(wn, qn):
+    """perm[i]: the quantised node that stands for wide node i, by the child references of both arrays walked together from the
+    roots; asserts that they describe one tree (leaf references equal, every node of either array reached exactly once)."""
+    u = wn.view(np.uint32)
+    perm = np.full(len(wn), -1, np.int64)
+    taken = np.zeros(len(qn), bool)
+    todo = [(0, 0)]
+    while todo:
+        i, qi = todo.pop()
+        assert perm[i] < 0 and not taken[qi]
+        perm[i] = qi; taken[qi] = True
+        for side in (0, 1):
+            r, q = int(u[i, 12 + side]), int(qn[qi, 4 * side + 3])
+            if r & REF_LEAF:
+                assert q == r
+            else:
+                assert not (q & REF_LEAF) and r < len(wn) and q < len(qn)
+                todo.append((r, q))
+    assert (perm >= 0).all() and taken.all()
+    return perm
+
+
+@pytest.mark.parametrize("k", [1, 2, 4])
+def test_device_planes_are_the_shared_definitions(ctx, k):
+    """The device builder's quantised nodes are pinned to the one definition (csrc/wide_node.h), not merely to soundness: its own
+    wide nodes, quantised again here on the grid it reports, give its plane words bit for bit. grid48 is the smallest scene the
+    device builder accepts. Its renumbering is not recomputed, only checked to be a renumbering of the same tree.
+
+    (The rule asks for the nearest plane. The library stops one plane short of it where that plane rounds onto the bound itself while
+    the double-precision quotient stays below the integer — 40 to 100 words of cornell_spheres' host images, none of this scene's:
+    every bound of either builder's tree here is a padded triangle coordinate, and the host image at leaf_tris = 1, which holds every
+    triangle's box as a child, meets the rule throughout.)"""
+    sc = scene("grid48")
+    assert upload(ctx, sc, 2, leaf_tris=k).tree_builder_used == 2
+    info, wn, qn, _, _ = ctx.read_image()
+    assert info.quantised == 1 and qn is not None and len(qn) == len(wn) == info.n_wnodes
+    perm = quantised_numbers(wn, qn)
+    got = qn[perm].reshape(len(wn), 2, 4)[..., 0:3]
+    assert np.array_equal(got, requantised_words(info, wn))
+
+
 # -- 4. the build is deterministic --------------------------------------------------------------------------------------------------
 def test_device_build_is_deterministic(ctx):
     sc = scene("grid96")

@@ -1,4 +1,5 @@
-// fast_tree.h — host-side rebuild of the traversal hierarchy over the reference's leaves (see fast_tree.hip).
+// fast_tree.h — the hierarchies built at upload and their quantised images: the FAST tree over the reference's leaves and the OWN tree
+// over the triangles (host: fast_tree.hip; device: gpu_tree.hip, own_tree_gpu.hip), and the two quantisers (quantise.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -58,10 +59,10 @@ void pt_build_fast_tree(const std::vector<PtFastLeaf> &leaves, std::vector<float
 bool pt_build_fast_tree_gpu(const std::vector<PtFastLeaf> &leaves, std::vector<float4> &wnodes, uint32_t &root_ref, uint32_t &depth,
                             hipStream_t s);
 
-// Quantised image of that hierarchy for the global traversal variant (layout: traverse.hip, QuantMem).
+// Quantised image of that hierarchy for the global traversal variant (quantise.hip; layout: traverse.hip, QuantMem).
 //   qnodes      2 uint4 per wide node: child boxes as 16-bit plane numbers on the grid origin + k * scale, rounded outward
-//               (verified with the same fmaf the kernel evaluates), child references (leaf: PT_REF_LEAF | dword offset into
-//               `stream`)
+//               (wide_node.h pt_quantise_child: verified with the same fmaf the kernel evaluates), child references (leaf:
+//               PT_REF_LEAF | dword offset into `stream`)
 //   stream      per leaf: exact box (the reference node's), first triangle, count, then v0, e1, e2 of each triangle (9 dwords)
 // tripos: 3 float4 per triangle (v0, e1, e2), indexed by triangle. Returns false when the hierarchy cannot be quantised
 // (non-finite boxes, a stream beyond 2^31 dwords); the caller then keeps the exact image.
@@ -108,7 +109,7 @@ struct PtOwnTreeGpu : PtOwnTreeHeader {
 };
 bool pt_build_own_tree_gpu(const ptmi_triangle *d_tris, const std::vector<uint32_t> &which, const std::vector<float4> &leafbox,
                            uint32_t max_leaf, uint32_t depth_limit, hipStream_t s, PtOwnTreeGpu &out);
-// The 16-bit grid of pt_quantize_nodes over the bounds [mn, mx]: origin = mn, the smallest scale whose last plane reaches mx (checked
+// The 16-bit grid of both quantisers and of the device builder over the bounds [mn, mx]: origin = mn, the smallest scale whose last plane reaches mx (checked
 // with fmaf). false: the bounds are not finite.
 bool pt_quant_grid(const float mn[3], const float mx[3], float origin[3], float scale[3]);
 // Quantised nodes of any wide-node hierarchy whose leaf references are to stay as they are (own leaves): 2 uint4 per node as in

@@ -1,6 +1,11 @@
-// fast_tree.hip — host code: a traversal hierarchy rebuilt over the REFERENCE's leaves.
+// fast_tree.hip — host code: the hierarchies the kernels walk instead of the tree as uploaded.
+//   Builder, rotations   the top-down SAH build and the bottom-up rotation passes, shared by both hierarchies
+//   pt_build_fast_tree   the FAST tree: a hierarchy rebuilt over the REFERENCE's leaves (ptmi_options.leaves = 1)
+//   pt_build_own_tree    the OWN tree: a hierarchy over the triangles themselves, collapsed into the library's own leaves and padded
+//                        (ptmi_options.leaves = 2; fast_tree.h)
+// Their quantised images are made in quantise.hip.
 //
-// Why this is allowed: the reference tests a triangle iff the slab predicate of
+// Why rebuilding over the reference's leaves is allowed: the reference tests a triangle iff the slab predicate of
 // pt.wgsl:234-245 passes for every box on the path from the root to the triangle's leaf. With the
 // contract's slab arithmetic, (bound - o) * (1/d) followed by min/max, the predicate is monotone under
 // box containment for every "regular" ray (all three 1/d finite and non-zero): a larger box yields a
@@ -16,6 +21,7 @@
 // component) keep walking the reference's own tree (traverse.hip).
 #include "fast_tree.h"
 #include "pt_device.h"
+#include "wide_node.h"
 #include <limits>
 
 #include <algorithm>
@@ -151,12 +157,7 @@ struct Builder {
             lref = build(s, pos, d + 1, me + 1, lb);
             rref = build(pos, e, d + 1, me + (pos - s), rb);
         }
-        float fl, fr; std::memcpy(&fl, &lref, 4); std::memcpy(&fr, &rref, 4);
-        float4 *w = &out[(size_t)me * 4];
-        w[0] = make_float4(lb.mn[0], lb.mn[1], lb.mn[2], lb.mx[0]);
-        w[1] = make_float4(lb.mx[1], lb.mx[2], rb.mn[0], rb.mn[1]);
-        w[2] = make_float4(rb.mn[2], rb.mx[0], rb.mx[1], rb.mx[2]);
-        w[3] = make_float4(fl, fr, 0.0f, 0.0f);
+        pt_wide_pack(&out[(size_t)me * 4], lb.mn, lb.mx, lref, rb.mn, rb.mx, rref);
         box = lb; box.grow(rb);
         return me;
     }
@@ -180,20 +181,13 @@ uint32_t depth_of(const WideView &v, uint32_t n);
 struct WideView {
     std::vector<float4> &w;
     static bool leaf(uint32_t ref) { return (ref & PT_REF_LEAF) != 0u; }
-    uint32_t ref(uint32_t n, int side) const { uint32_t r; std::memcpy(&r, side ? &w[(size_t)n * 4 + 3].y : &w[(size_t)n * 4 + 3].x, 4); return r; }
-    void set_ref(uint32_t n, int side, uint32_t r) { std::memcpy(side ? &w[(size_t)n * 4 + 3].y : &w[(size_t)n * 4 + 3].x, &r, 4); }
+    uint32_t ref(uint32_t n, int side) const { return pt_wide_ref(&w[(size_t)n * 4], side); }
+    void set_ref(uint32_t n, int side, uint32_t r) { pt_wide_set_ref(&w[(size_t)n * 4], side, r); }
     Box box(uint32_t n, int side) const {
-        const float4 *q = &w[(size_t)n * 4];
-        Box b;
-        if (side == 0) { b.mn[0] = q[0].x; b.mn[1] = q[0].y; b.mn[2] = q[0].z; b.mx[0] = q[0].w; b.mx[1] = q[1].x; b.mx[2] = q[1].y; }
-        else { b.mn[0] = q[1].z; b.mn[1] = q[1].w; b.mn[2] = q[2].x; b.mx[0] = q[2].y; b.mx[1] = q[2].z; b.mx[2] = q[2].w; }
-        return b;
+        const PtWideChild c = pt_wide_child(&w[(size_t)n * 4], side);
+        return Box{{c.lo[0], c.lo[1], c.lo[2]}, {c.hi[0], c.hi[1], c.hi[2]}};
     }
-    void set_box(uint32_t n, int side, const Box &b) {
-        float4 *q = &w[(size_t)n * 4];
-        if (side == 0) { q[0] = make_float4(b.mn[0], b.mn[1], b.mn[2], b.mx[0]); q[1].x = b.mx[1]; q[1].y = b.mx[2]; }
-        else { q[1].z = b.mn[0]; q[1].w = b.mn[1]; q[2] = make_float4(b.mn[2], b.mx[0], b.mx[1], b.mx[2]); }
-    }
+    void set_box(uint32_t n, int side, const Box &b) { pt_wide_set_box(&w[(size_t)n * 4], side, b.mn, b.mx); }
 };
 
 // one bottom-up pass over the subtree of n (at `level`, the root at 1); returns the subtree's height in levels (a leaf = 1) and
@@ -455,13 +449,10 @@ bool pt_build_own_tree(const ptmi_triangle *tris, const std::vector<uint32_t> &w
             float4 *w = &out.wnodes[(size_t)new_of[r] * 4];
             const float4 *q = &per_tri[(size_t)r * 4];
             w[0] = q[0]; w[1] = q[1]; w[2] = q[2];
-            uint32_t refs[2];
-            for (int side = 0; side < 2; side++) {
+            for (int side = 0; side < 2; side++) {           // (the two spare words stay zero)
                 const uint32_t c = v.ref(r, side);
-                refs[side] = is_leaf(c) ? leaf_of(c) : new_of[c];
+                pt_wide_set_ref(w, side, is_leaf(c) ? leaf_of(c) : new_of[c]);
             }
-            float fl, fr; std::memcpy(&fl, &refs[0], 4); std::memcpy(&fr, &refs[1], 4);
-            w[3] = make_float4(fl, fr, 0.0f, 0.0f);
             const uint32_t a = v.ref(r, 0), b = v.ref(r, 1);
             if (!is_leaf(b)) st.push_back(b);
             if (!is_leaf(a)) st.push_back(a);
@@ -495,240 +486,5 @@ bool pt_build_own_tree(const ptmi_triangle *tris, const std::vector<uint32_t> &w
                           n, out.wnodes.size() / 4, out.n_leaves, out.depth, ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, now()));
     out.pad = pad;
     out.safe_origin = (float)std::min(8.0 * biggest, 3.0e38);      // the rounding of the fused tests stays below a quarter of the padding up to here
-    return true;
-}
-
-// ---- quantised image ------------------------------------------------------------------------------------------------
-bool pt_quantize_tree(const std::vector<PtFastLeaf> &leaves, const std::vector<float4> &wnodes, const std::vector<float4> &tripos,
-                      std::vector<uint4> &qnodes, std::vector<uint32_t> &stream, float origin[3], float scale[3],
-                      uint32_t top_nodes, uint32_t &n_top) {
-    qnodes.clear(); stream.clear(); n_top = 0;
-    const size_t n_nodes = wnodes.size() / 4;
-    if (n_nodes == 0 || leaves.empty()) return false;
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    size_t n_tri_refs = 0;
-    for (const PtFastLeaf &l : leaves) {
-        for (int k = 0; k < 3; k++) {
-            if (!std::isfinite(l.mn[k]) || !std::isfinite(l.mx[k]) || l.mn[k] > l.mx[k]) return false;
-            mn[k] = std::min(mn[k], l.mn[k]); mx[k] = std::max(mx[k], l.mx[k]);
-        }
-        n_tri_refs += l.weight;
-    }
-    if (leaves.size() * 8 + n_tri_refs * 9 >= (1ull << 31)) return false;
-    for (int k = 0; k < 3; k++) {
-        origin[k] = mn[k];
-        const double ext = (double)mx[k] - (double)mn[k];
-        float s = (float)(ext / 65535.0);
-        if (!std::isfinite(s)) return false;
-        if (ext > 0.0) {
-            if (!(s > 0.0f)) s = std::numeric_limits<float>::denorm_min();
-            int guard = 0;
-            while (std::fmaf(s, 65535.0f, origin[k]) < mx[k] && guard++ < 64) s = std::nextafterf(s, INFINITY);   // the last plane reaches the far side
-            if (std::fmaf(s, 65535.0f, origin[k]) < mx[k]) return false;
-        }
-        scale[k] = s;
-    }
-    auto plane_lo = [&](int k, float v) -> uint32_t {         // largest plane number whose plane is <= v
-        if (!(scale[k] > 0.0f)) return 0u;
-        double q = std::floor(((double)v - (double)origin[k]) / (double)scale[k]);
-        uint32_t u = q <= 0.0 ? 0u : q >= 65535.0 ? 65535u : (uint32_t)q;
-        while (u > 0u && std::fmaf(scale[k], (float)u, origin[k]) > v) u--;
-        return u;
-    };
-    auto plane_hi = [&](int k, float v) -> uint32_t {         // smallest plane number whose plane is >= v
-        if (!(scale[k] > 0.0f)) return 0u;
-        double q = std::ceil(((double)v - (double)origin[k]) / (double)scale[k]);
-        uint32_t u = q <= 0.0 ? 0u : q >= 65535.0 ? 65535u : (uint32_t)q;
-        while (u < 65535u && std::fmaf(scale[k], (float)u, origin[k]) < v) u++;
-        return u;
-    };
-    // the leaf stream, in the order the leaves hang off the preorder nodes (neighbours in the tree are neighbours in memory).
-    // Pass 1 assigns every leaf child its place (sequential, two words per node); pass 2 fills nodes and stream in parallel.
-    const size_t n_tris = tripos.size() / 3;
-    std::vector<uint32_t> leaf_of_first(n_tris, 0xFFFFFFFFu);         // a leaf is identified by its first triangle
-    for (size_t i = 0; i < leaves.size(); i++) {
-        const uint32_t first = leaves[i].ref & PT_LEAF_OFF_MASK;
-        if (first >= n_tris) return false;
-        leaf_of_first[first] = (uint32_t)i;
-    }
-    std::vector<uint32_t> child_off(n_nodes * 2, 0u);
-    size_t total = 0;
-    for (size_t i = 0; i < n_nodes; i++) {
-        uint32_t refs[2]; std::memcpy(&refs[0], &wnodes[i * 4 + 3].x, 4); std::memcpy(&refs[1], &wnodes[i * 4 + 3].y, 4);
-        for (int c = 0; c < 2; c++)
-            if (refs[c] & PT_REF_LEAF) {
-                child_off[i * 2 + c] = (uint32_t)total;
-                total += 8 + 9 * (size_t)(((refs[c] >> PT_LEAF_OFF_BITS) & (PT_LEAF_MAX_TRIS - 1u)) + 1u);
-            }
-    }
-    if (total >= (1ull << 31)) return false;
-    stream.assign(total, 0u);
-    qnodes.resize(n_nodes * 2);
-    // new numbers: the top of the tree breadth-first (root first), then everything else in preorder
-    std::vector<uint32_t> renum(n_nodes, 0xFFFFFFFFu);
-    {
-        std::vector<uint32_t> bfs; bfs.reserve(top_nodes);
-        bfs.push_back(0u);
-        for (size_t h = 0; h < bfs.size() && bfs.size() < top_nodes; h++) {
-            uint32_t refs[2]; std::memcpy(&refs[0], &wnodes[(size_t)bfs[h] * 4 + 3].x, 4); std::memcpy(&refs[1], &wnodes[(size_t)bfs[h] * 4 + 3].y, 4);
-            for (int c = 0; c < 2 && bfs.size() < top_nodes; c++)
-                if (!(refs[c] & PT_REF_LEAF)) bfs.push_back(refs[c]);
-        }
-        for (size_t k = 0; k < bfs.size(); k++) renum[bfs[k]] = (uint32_t)k;
-        n_top = (uint32_t)bfs.size();
-        uint32_t next = n_top;
-        for (size_t i = 0; i < n_nodes; i++) if (renum[i] == 0xFFFFFFFFu) renum[i] = next++;
-    }
-    auto area = [](const float *l, const float *h) {
-        const double x = (double)h[0] - l[0], y = (double)h[1] - l[1], z = (double)h[2] - l[2];
-        return 2.0 * (x * y + y * z + z * x);
-    };
-    auto fill = [&](size_t i0, size_t i1, double &growth, size_t &grown, bool &ok) {
-        for (size_t i = i0; i < i1; i++) {
-            const float4 *w = &wnodes[i * 4];
-            const float lo[2][3] = {{w[0].x, w[0].y, w[0].z}, {w[1].z, w[1].w, w[2].x}};
-            const float hi[2][3] = {{w[0].w, w[1].x, w[1].y}, {w[2].y, w[2].z, w[2].w}};
-            uint32_t refs[2]; std::memcpy(&refs[0], &w[3].x, 4); std::memcpy(&refs[1], &w[3].y, 4);
-            for (int c = 0; c < 2; c++) {
-                uint32_t ql[3], qh[3];
-                for (int k = 0; k < 3; k++) { ql[k] = plane_lo(k, lo[c][k]); qh[k] = plane_hi(k, hi[c][k]); }
-                uint32_t ref = refs[c];
-                if (ref & PT_REF_LEAF) {
-                    const uint32_t first = ref & PT_LEAF_OFF_MASK, cnt = ((ref >> PT_LEAF_OFF_BITS) & (PT_LEAF_MAX_TRIS - 1u)) + 1u;
-                    const uint32_t li = first < n_tris ? leaf_of_first[first] : 0xFFFFFFFFu;
-                    if (li == 0xFFFFFFFFu || leaves[li].ref != ref || (size_t)first + cnt > n_tris) { ok = false; continue; }
-                    const PtFastLeaf &l = leaves[li];
-                    uint32_t *h = &stream[child_off[i * 2 + c]];
-                    std::memcpy(h, l.mn, 12); h[3] = first; std::memcpy(h + 4, l.mx, 12); h[7] = cnt;
-                    for (uint32_t t = 0; t < cnt; t++)
-                        for (int j = 0; j < 3; j++) std::memcpy(h + 8 + 9 * t + 3 * j, &tripos[3 * (size_t)(first + t) + j], 12);
-                    ref = PT_REF_LEAF | child_off[i * 2 + c];
-                } else {
-                    ref = renum[ref];
-                }
-                qnodes[(size_t)renum[i] * 2 + c] = make_uint4(ql[0] | (ql[1] << 16), ql[2] | (qh[0] << 16), qh[1] | (qh[2] << 16), ref);
-                float dl[3], dh[3];
-                for (int k = 0; k < 3; k++) { dl[k] = std::fmaf(scale[k], (float)ql[k], origin[k]); dh[k] = std::fmaf(scale[k], (float)qh[k], origin[k]); }
-                const double a0 = area(lo[c], hi[c]);
-                if (a0 > 0.0) { growth += std::min(area(dl, dh) / a0 - 1.0, 1e6); grown++; }
-            }
-        }
-    };
-    const unsigned hw = std::thread::hardware_concurrency();
-    const size_t n_thr = n_nodes < 65536 ? 1 : std::min<size_t>(16, hw ? hw : 1);
-    std::vector<double> g(n_thr, 0.0); std::vector<size_t> gn(n_thr, 0); std::vector<char> oks(n_thr, 1);
-    {
-        std::vector<std::thread> pool;
-        for (size_t t = 1; t < n_thr; t++)
-            pool.emplace_back([&, t] { bool ok = true; fill(n_nodes * t / n_thr, n_nodes * (t + 1) / n_thr, g[t], gn[t], ok); oks[t] = ok; });
-        bool ok = true; fill(0, n_nodes / n_thr, g[0], gn[0], ok); oks[0] = ok;
-        for (auto &th : pool) th.join();
-    }
-    double growth = 0.0; size_t grown = 0;       // mean relative growth of the child boxes' surface area
-    for (size_t t = 0; t < n_thr; t++) { growth += g[t]; grown += gn[t]; if (!oks[t]) { qnodes.clear(); stream.clear(); return false; } }
-    // One grid for the whole scene suits scenes whose boxes are not many orders of magnitude smaller than the scene.
-    // Where they are (a chain of boxes shrinking geometrically), the rounded boxes would admit far more rays than the exact
-    // ones: same results, much more work. Such scenes keep the exact image.
-    if (grown && growth / (double)grown > 0.25) { qnodes.clear(); stream.clear(); return false; }
-    return true;
-}
-
-bool pt_quant_grid(const float mn[3], const float mx[3], float origin[3], float scale[3]) {
-    for (int k = 0; k < 3; k++) {
-        origin[k] = mn[k];
-        const double ext = (double)mx[k] - (double)mn[k];
-        float s = (float)(ext / 65535.0);
-        if (!std::isfinite(s)) return false;
-        if (ext > 0.0) {
-            if (!(s > 0.0f)) s = std::numeric_limits<float>::denorm_min();
-            int guard = 0;
-            while (std::fmaf(s, 65535.0f, origin[k]) < mx[k] && guard++ < 64) s = std::nextafterf(s, INFINITY);
-            if (std::fmaf(s, 65535.0f, origin[k]) < mx[k]) return false;
-        }
-        scale[k] = s;
-    }
-    return true;
-}
-
-bool pt_quantize_nodes(const std::vector<float4> &wnodes, std::vector<uint4> &qnodes, float origin[3], float scale[3],
-                       uint32_t top_nodes, uint32_t &n_top) {
-    qnodes.clear(); n_top = 0;
-    const size_t n_nodes = wnodes.size() / 4;
-    if (n_nodes == 0) return false;
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (size_t i = 0; i < n_nodes; i++) {
-        const float4 *w = &wnodes[i * 4];
-        const float lo[2][3] = {{w[0].x, w[0].y, w[0].z}, {w[1].z, w[1].w, w[2].x}};
-        const float hi[2][3] = {{w[0].w, w[1].x, w[1].y}, {w[2].y, w[2].z, w[2].w}};
-        for (int c = 0; c < 2; c++)
-            for (int k = 0; k < 3; k++) {
-                if (!std::isfinite(lo[c][k]) || !std::isfinite(hi[c][k]) || lo[c][k] > hi[c][k]) return false;
-                mn[k] = std::min(mn[k], lo[c][k]); mx[k] = std::max(mx[k], hi[c][k]);
-            }
-    }
-    if (!pt_quant_grid(mn, mx, origin, scale)) return false;
-    auto plane_lo = [&](int k, float v) -> uint32_t {
-        if (!(scale[k] > 0.0f)) return 0u;
-        double q = std::floor(((double)v - (double)origin[k]) / (double)scale[k]);
-        uint32_t u = q <= 0.0 ? 0u : q >= 65535.0 ? 65535u : (uint32_t)q;
-        while (u > 0u && std::fmaf(scale[k], (float)u, origin[k]) > v) u--;
-        return u;
-    };
-    auto plane_hi = [&](int k, float v) -> uint32_t {
-        if (!(scale[k] > 0.0f)) return 0u;
-        double q = std::ceil(((double)v - (double)origin[k]) / (double)scale[k]);
-        uint32_t u = q <= 0.0 ? 0u : q >= 65535.0 ? 65535u : (uint32_t)q;
-        while (u < 65535u && std::fmaf(scale[k], (float)u, origin[k]) < v) u++;
-        return u;
-    };
-    std::vector<uint32_t> renum(n_nodes, 0xFFFFFFFFu);
-    {
-        std::vector<uint32_t> bfs; bfs.reserve(top_nodes);
-        bfs.push_back(0u);
-        for (size_t h = 0; h < bfs.size() && bfs.size() < top_nodes; h++) {
-            uint32_t refs[2]; std::memcpy(&refs[0], &wnodes[(size_t)bfs[h] * 4 + 3].x, 4); std::memcpy(&refs[1], &wnodes[(size_t)bfs[h] * 4 + 3].y, 4);
-            for (int c = 0; c < 2 && bfs.size() < top_nodes; c++)
-                if (!(refs[c] & PT_REF_LEAF)) bfs.push_back(refs[c]);
-        }
-        for (size_t k = 0; k < bfs.size(); k++) renum[bfs[k]] = (uint32_t)k;
-        n_top = (uint32_t)bfs.size();
-        uint32_t next = n_top;
-        for (size_t i = 0; i < n_nodes; i++) if (renum[i] == 0xFFFFFFFFu) renum[i] = next++;
-    }
-    qnodes.resize(n_nodes * 2);
-    auto fill = [&](size_t i0, size_t i1, double &growth, size_t &grown) {
-        for (size_t i = i0; i < i1; i++) {
-            const float4 *w = &wnodes[i * 4];
-            const float lo[2][3] = {{w[0].x, w[0].y, w[0].z}, {w[1].z, w[1].w, w[2].x}};
-            const float hi[2][3] = {{w[0].w, w[1].x, w[1].y}, {w[2].y, w[2].z, w[2].w}};
-            uint32_t refs[2]; std::memcpy(&refs[0], &w[3].x, 4); std::memcpy(&refs[1], &w[3].y, 4);
-            for (int c = 0; c < 2; c++) {
-                uint32_t ql[3], qh[3];
-                float dl[3], dh[3];
-                for (int k = 0; k < 3; k++) {
-                    ql[k] = plane_lo(k, lo[c][k]); qh[k] = plane_hi(k, hi[c][k]);
-                    dl[k] = std::fmaf(scale[k], (float)ql[k], origin[k]); dh[k] = std::fmaf(scale[k], (float)qh[k], origin[k]);
-                }
-                const uint32_t ref = (refs[c] & PT_REF_LEAF) ? refs[c] : renum[refs[c]];
-                qnodes[(size_t)renum[i] * 2 + c] = make_uint4(ql[0] | (ql[1] << 16), ql[2] | (qh[0] << 16), qh[1] | (qh[2] << 16), ref);
-                const double ax = (double)hi[c][0] - lo[c][0], ay = (double)hi[c][1] - lo[c][1], az = (double)hi[c][2] - lo[c][2];
-                const double a0 = 2.0 * (ax * ay + ay * az + az * ax);
-                const double bx = (double)dh[0] - dl[0], by = (double)dh[1] - dl[1], bz = (double)dh[2] - dl[2];
-                if (a0 > 0.0) { growth += std::min(2.0 * (bx * by + by * bz + bz * bx) / a0 - 1.0, 1e6); grown++; }
-            }
-        }
-    };
-    const unsigned hw = std::thread::hardware_concurrency();
-    const size_t n_thr = n_nodes < 65536 ? 1 : std::min<size_t>(16, hw ? hw : 1);
-    std::vector<double> g(n_thr, 0.0); std::vector<size_t> gn(n_thr, 0);
-    {
-        std::vector<std::thread> pool;
-        for (size_t t = 1; t < n_thr; t++) pool.emplace_back([&, t] { fill(n_nodes * t / n_thr, n_nodes * (t + 1) / n_thr, g[t], gn[t]); });
-        fill(0, n_nodes / n_thr, g[0], gn[0]);
-        for (auto &th : pool) th.join();
-    }
-    double growth = 0.0; size_t grown = 0;
-    for (size_t t = 0; t < n_thr; t++) { growth += g[t]; grown += gn[t]; }
-    if (grown && growth / (double)grown > 0.25) { qnodes.clear(); return false; }       // a 16-bit grid is too coarse for this scene's boxes
     return true;
 }

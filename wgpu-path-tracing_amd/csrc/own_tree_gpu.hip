@@ -1,8 +1,9 @@
 // own_tree_gpu.hip — the library's OWN-leaf hierarchy (ptmi_options.leaves = 2) built on the device (ptmi_options.tree_builder = 2).
 //
-// It produces what pt_build_own_tree + pt_quantize_nodes produce on the host (fast_tree.h: the same layouts, the same padding, the same
-// quantisation rules), over another topology. Any topology is allowed: the kernels break ties by the lowest
-// triangle index and verify every winner against its reference leaf's box, so only the work per ray depends on the tree.
+// It produces what pt_build_own_tree + pt_quantize_nodes produce on the host (fast_tree.hip, quantise.hip: the same layouts, the same
+// padding, and the quantisation of wide_node.h itself), over another topology. Any topology is allowed: the
+// kernels break ties by the lowest triangle index and verify every winner against its reference leaf's box, so only the work per ray
+// depends on the tree.
 //
 //   units     one box per listed triangle, min / max over a, b, c, a + (b - a), a + (c - a) as the host computes them, a sliver's
 //             grown by its reference leaf's box (fast_tree.h pt_own_sliver); |coordinate| of the unit boxes max-reduced for the
@@ -18,14 +19,15 @@
 //   emit      every node walks up to the root summing the offsets its ancestors stored for it: its preorder number among the
 //             surviving inner nodes, its first position in leaf order, its level. Inner nodes write their wide node (child boxes
 //             padded outward exactly as the host pads them), units write their triangle (v0, bits(original index)), e1, e2
-//   quantise  the host's grid (pt_quant_grid) from the min / max of the padded boxes; the top PT_QCACHE_NODES nodes breadth-first
-//             at the front, the others in preorder; planes rounded outward and checked with the kernel's own fmaf
+//   quantise  the host's grid (quantise.hip pt_quant_grid) from the min / max of the padded boxes; the top PT_QCACHE_NODES nodes
+//             breadth-first at the front, the others in preorder; every child through the host's own wide_node.h pt_quantise_child
 //
 // Every step is deterministic: the same scene gives the same bytes on every run and every device. Scratch is sized from the scene and
 // freed on every path; any failure returns false and the caller builds on the host.
 #include "fast_tree.h"
 #include "pt_device.h"
 #include "ptmi_layout.h"
+#include "wide_node.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -263,11 +265,7 @@ __global__ void k_emit(uint32_t n_all, uint32_t n, uint32_t root, float pad, con
         }
     }
     atomicMax(&red->depth, lvl + 1u);                            // the children sit one level down
-    float4 *w = wn + 4 * (size_t)pre;
-    w[0] = make_float4(b[0].mn[0], b[0].mn[1], b[0].mn[2], b[0].mx[0]);
-    w[1] = make_float4(b[0].mx[1], b[0].mx[2], b[1].mn[0], b[1].mn[1]);
-    w[2] = make_float4(b[1].mn[2], b[1].mx[0], b[1].mx[1], b[1].mx[2]);
-    w[3] = make_float4(__uint_as_float(ref[0]), __uint_as_float(ref[1]), 0.0f, 0.0f);
+    pt_wide_pack(wn + 4 * (size_t)pre, b[0].mn, b[0].mx, ref[0], b[1].mn, b[1].mx, ref[1]);
 }
 
 // the top `top` nodes breadth-first from the root (one thread: a few hundred steps)
@@ -276,8 +274,8 @@ __global__ void k_top(const float4 *__restrict__ wn, uint32_t top, uint32_t *__r
     uint32_t len = 0;
     bfs[len++] = 0u;
     for (uint32_t h = 0; h < len && len < top; h++) {
-        const float4 r = wn[4 * (size_t)bfs[h] + 3];
-        const uint32_t refs[2] = {__float_as_uint(r.x), __float_as_uint(r.y)};
+        const float4 *w = wn + 4 * (size_t)bfs[h];
+        const uint32_t refs[2] = {pt_wide_ref(w, 0), pt_wide_ref(w, 1)};
         for (int c = 0; c < 2 && len < top; c++)
             if (!(refs[c] & PT_REF_LEAF)) bfs[len++] = refs[c];
     }
@@ -290,48 +288,21 @@ __global__ void k_rest_flags(uint32_t m, const uint32_t *__restrict__ renum, uin
     if (i < m) flags[i] = renum[i] == PT_REF_NONE ? 1u : 0u;
 }
 
-struct Grid { float origin[3], scale[3]; };
-
-__device__ __forceinline__ uint32_t plane_lo(const Grid &g, int k, float v) {     // fast_tree.hip pt_quantize_nodes
-    if (!(g.scale[k] > 0.0f)) return 0u;
-    const double q = floor(((double)v - (double)g.origin[k]) / (double)g.scale[k]);
-    uint32_t u = q <= 0.0 ? 0u : q >= 65535.0 ? 65535u : (uint32_t)q;
-    while (u > 0u && fmaf(g.scale[k], (float)u, g.origin[k]) > v) u--;
-    return u;
-}
-__device__ __forceinline__ uint32_t plane_hi(const Grid &g, int k, float v) {
-    if (!(g.scale[k] > 0.0f)) return 0u;
-    const double q = ceil(((double)v - (double)g.origin[k]) / (double)g.scale[k]);
-    uint32_t u = q <= 0.0 ? 0u : q >= 65535.0 ? 65535u : (uint32_t)q;
-    while (u < 65535u && fmaf(g.scale[k], (float)u, g.origin[k]) < v) u++;
-    return u;
-}
-
-__global__ void k_quantise(uint32_t m, Grid g, const float4 *__restrict__ wn, const uint32_t *__restrict__ renum,
+// every child of every node through the host's quantisation (wide_node.h); the nodes' new numbers from k_top and the scan
+__global__ void k_quantise(uint32_t m, PtQuantGrid g, const float4 *__restrict__ wn, const uint32_t *__restrict__ renum,
                            const uint32_t *__restrict__ rest, const Red *red, uint4 *__restrict__ qn, double *__restrict__ growth,
                            uint32_t *__restrict__ grown) {
     const uint32_t i = blockIdx.x * TB + threadIdx.x;
     if (i >= m) return;
     const uint32_t n_top = red->n_top;
     auto number = [&](uint32_t j) { const uint32_t r = renum[j]; return r != PT_REF_NONE ? r : n_top + rest[j]; };
-    const float4 *w = wn + 4 * (size_t)i;
-    const float lo[2][3] = {{w[0].x, w[0].y, w[0].z}, {w[1].z, w[1].w, w[2].x}};
-    const float hi[2][3] = {{w[0].w, w[1].x, w[1].y}, {w[2].y, w[2].z, w[2].w}};
-    const uint32_t refs[2] = {__float_as_uint(w[3].x), __float_as_uint(w[3].y)};
     const uint32_t me = number(i);
     double gsum = 0.0; uint32_t gn = 0;
     for (int c = 0; c < 2; c++) {
-        uint32_t ql[3], qh[3]; float dl[3], dh[3];
-        for (int k = 0; k < 3; k++) {
-            ql[k] = plane_lo(g, k, lo[c][k]); qh[k] = plane_hi(g, k, hi[c][k]);
-            dl[k] = fmaf(g.scale[k], (float)ql[k], g.origin[k]); dh[k] = fmaf(g.scale[k], (float)qh[k], g.origin[k]);
-        }
-        const uint32_t ref = (refs[c] & PT_REF_LEAF) ? refs[c] : number(refs[c]);
-        qn[(size_t)me * 2 + c] = make_uint4(ql[0] | (ql[1] << 16), ql[2] | (qh[0] << 16), qh[1] | (qh[2] << 16), ref);
-        const double ax = (double)hi[c][0] - lo[c][0], ay = (double)hi[c][1] - lo[c][1], az = (double)hi[c][2] - lo[c][2];
-        const double a0 = 2.0 * (ax * ay + ay * az + az * ax);
-        const double bx = (double)dh[0] - dl[0], by = (double)dh[1] - dl[1], bz = (double)dh[2] - dl[2];
-        if (a0 > 0.0) { gsum += fmin(2.0 * (bx * by + by * bz + bz * bx) / a0 - 1.0, 1e6); gn++; }
+        const PtWideChild ch = pt_wide_child(wn + 4 * (size_t)i, c);
+        const PtQuantChild q = pt_quantise_child(g, ch.lo, ch.hi, (ch.ref & PT_REF_LEAF) ? ch.ref : number(ch.ref));
+        qn[(size_t)me * 2 + c] = q.q;
+        if (q.grown) { gsum += q.growth; gn++; }
     }
     growth[i] = gsum; grown[i] = gn;
 }
@@ -481,7 +452,7 @@ bool pt_build_own_tree_gpu(const ptmi_triangle *d_tris, const std::vector<uint32
     {
         float mn[3], mx[3];
         for (int k = 0; k < 3; k++) { mn[k] = unord_f(h.qmin[k]); mx[k] = unord_f(h.qmax[k]); }
-        Grid g;
+        PtQuantGrid g;
         if (pt_quant_grid(mn, mx, g.origin, g.scale)) {
             GT(hipMalloc(&d_qn, (size_t)n_inner * 32)); GT(hipMalloc(&d_renum, (size_t)n_inner * 4));
             GT(hipMalloc(&d_rest_f, (size_t)n_inner * 4)); GT(hipMalloc(&d_rest, (size_t)n_inner * 4));

@@ -1,9 +1,11 @@
 // scene_image.hip — an uploaded scene: validation of the caller's BVH, the traversal image the kernels walk (the tree as uploaded, a
-// hierarchy rebuilt over its leaves, or the library's own leaves: fast_tree.h), and its installation on a device.
+// hierarchy rebuilt over its leaves, or the library's own leaves: fast_tree.h; quantised: quantise.hip), and its installation on a
+// device.
 //
 // Replaces the reference's scene buffers (src/renderer/renderer.ts: createBuffers :242-355).
 #include "ptmi_ctx.h"
 #include "fast_tree.h"
+#include "wide_node.h"
 
 #include <algorithm>
 #include <chrono>
@@ -80,15 +82,14 @@ bool compact_ref(uint32_t r, uint32_t &o) {
     return true;
 }
 bool compact_refs(const std::vector<float4> &w, uint32_t root, std::vector<float4> &out, uint32_t &root16) {
-    auto conv = compact_ref;
     out = w;
-    if (root == PT_REF_NONE || !conv(root, root16)) return false;
-    for (size_t i = 0; i < w.size() / 4; i++) {
-        uint32_t l, r, l16, r16;
-        std::memcpy(&l, &w[i * 4 + 3].x, 4); std::memcpy(&r, &w[i * 4 + 3].y, 4);
-        if (!conv(l, l16) || !conv(r, r16)) return false;
-        std::memcpy(&out[i * 4 + 3].x, &l16, 4); std::memcpy(&out[i * 4 + 3].y, &r16, 4);
-    }
+    if (root == PT_REF_NONE || !compact_ref(root, root16)) return false;
+    for (size_t i = 0; i < w.size() / 4; i++)
+        for (int side = 0; side < 2; side++) {
+            uint32_t r16;
+            if (!compact_ref(pt_wide_ref(&w[i * 4], side), r16)) return false;
+            pt_wide_set_ref(&out[i * 4], side, r16);
+        }
     return true;
 }
 
@@ -213,13 +214,8 @@ int build_image(const ptmi_options &opt, hipStream_t stream, int device, const p
     for (uint32_t i = 0; i < nn; i++) {
         if (wide_of[i] == PT_REF_NONE) continue;
         const ptmi_bvh_node &L = nodes[nodes[i].left], &R = nodes[nodes[i].right];
-        float4 *w = &wnodes[(size_t)wide_of[i] * 4];
-        w[0] = make_float4(L.aabb_min[0], L.aabb_min[1], L.aabb_min[2], L.aabb_max[0]);
-        w[1] = make_float4(L.aabb_max[1], L.aabb_max[2], R.aabb_min[0], R.aabb_min[1]);
-        w[2] = make_float4(R.aabb_min[2], R.aabb_max[0], R.aabb_max[1], R.aabb_max[2]);
-        uint32_t lr = ref_of(nodes[i].left), rr = ref_of(nodes[i].right);
-        float fl, fr; std::memcpy(&fl, &lr, 4); std::memcpy(&fr, &rr, 4);
-        w[3] = make_float4(fl, fr, 0.0f, 0.0f);
+        pt_wide_pack(&wnodes[(size_t)wide_of[i] * 4], L.aabb_min, L.aabb_max, ref_of(nodes[i].left), R.aabb_min, R.aabb_max,
+                     ref_of(nodes[i].right));
     }
     for (int k = 0; k < 3; k++) { b.ref_root_min[k] = nodes[0].aabb_min[k]; b.ref_root_max[k] = nodes[0].aabb_max[k]; }
     b.ref_root_ref = ref_of(0);

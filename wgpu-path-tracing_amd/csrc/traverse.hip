@@ -63,7 +63,7 @@ struct LdsMem {
     }
 };
 
-// QUANTISED variant (large scenes, walked from global memory; fast_tree.hip::pt_quantize_tree builds the image):
+// QUANTISED variant (large scenes, walked from global memory; quantise.hip pt_quantize_tree builds the image):
 //   node, 32 B = 2 x uint4: per child three words of 16-bit plane numbers (lo.x | lo.y << 16, lo.z | hi.x << 16,
 //         hi.y | hi.z << 16) and its reference; plane k on axis a is fma(scale[a], k, origin[a]) — the child's exact box
 //         rounded OUTWARD to that grid. A box that contains a leaf's box passes whenever the leaf's own box passes (the

@@ -100,7 +100,7 @@ struct OwnGlobalMem {
         glb_f4p p = tg + 3u * (size_t)i; a = as_f4(p[0]); b = as_f4(p[1]); c = as_f4(p[2]);
     }
 };
-// Quantised nodes (fast_tree.hip pt_quantize_nodes): per child three words of 16-bit plane numbers (lo.x | lo.y << 16,
+// Quantised nodes (quantise.hip pt_quantize_nodes): per child three words of 16-bit plane numbers (lo.x | lo.y << 16,
 // lo.z | hi.x << 16, hi.y | hi.z << 16) and its reference; plane k on axis a stands at origin[a] + k * scale[a], the padded box rounded
 // OUTWARD to that grid. The test never forms that position: t = fma(k, scale / d, (origin - o) / d), one instruction per plane after
 // the conversion of k. Its rounding (<= 2^-22 of scene extent + origin distance, in position terms) is far inside the padding.
