@@ -72,7 +72,7 @@ int ptmi_debug_center_rays(ptmi_ctx *c, const ptmi_camera *cam, float *o3, float
     if (rc) return rc;
     Lane &ln = c->lane;
     const DevBand whole{c->W, c->H, 0u, c->H, 1u, 1u, 0u, c->H};
-    pt_launch_center_rays(c->stream, c->n_cu * 8, *cam, whole, ln.paths, &ln.counts[0]);
+    pt_launch_center_rays(c->stream, c->n_cu * 8, *cam, whole, ln.paths, &c->d_control[kCwQueue]);
     std::vector<float4> o(n), d(n);
     HIP_TRY(c, hipMemcpyAsync(o.data(), ln.paths.O, n * 16, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(d.data(), ln.paths.D, n * 16, hipMemcpyDeviceToHost, c->stream));
@@ -91,10 +91,10 @@ int ptmi_debug_intersect(ptmi_ctx *c, uint32_t n, const float *o3, const float *
     Lane &ln = c->lane;
     rc = upload_rays(c, n, o3, d3, nullptr, ln.paths.O, ln.paths.D);
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(&ln.counts[0], &n, 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&c->d_control[kCwQueue], &n, 4, hipMemcpyHostToDevice, c->stream));
     TraverseConfig cfg;
     if ((rc = traverse_ready(c, true, cfg))) return rc;
-    launch_extend(c, c->stream, cfg, ln.paths, nullptr, &ln.counts[0], ln.hits);
+    launch_extend(c, c->stream, cfg, ln.paths, nullptr, &c->d_control[kCwQueue], ln.hits);
     // (u, v) are not part of the hit record: rebuilt exactly as `shade` rebuilds them (into the C stream, unused here)
     pt_launch_hit_uv(c->stream, n, c->sc, ln.paths, ln.hits, ln.paths.C);
     std::vector<float2> h(n), uv(n);
@@ -122,10 +122,10 @@ int ptmi_debug_occluded(ptmi_ctx *c, uint32_t n, const float *o3, const float *d
         rc = upload_rays(c, n, o3, d3, dn.data(), ln.sh[0].SO, ln.sh[0].SD);
     }
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(&ln.counts[0], &n, 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&c->d_control[kCwQueue], &n, 4, hipMemcpyHostToDevice, c->stream));
     TraverseConfig cfg;
     if ((rc = traverse_ready(c, false, cfg))) return rc;
-    launch_shadow(c, c->stream, cfg, ln.paths, ln.sh[0], nullptr, &ln.counts[0], ln.d_occ);
+    launch_shadow(c, c->stream, cfg, ln.paths, ln.sh[0], nullptr, &c->d_control[kCwQueue], ln.d_occ);
     HIP_TRY(c, hipMemcpyAsync(occ, ln.d_occ, n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, sync_all(c));
     HIP_TRY(c, hipGetLastError());

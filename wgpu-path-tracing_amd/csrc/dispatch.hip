@@ -14,7 +14,6 @@ namespace {
 
 constexpr size_t kMaxPendingEvents = 4096;        // a caller that never synchronises (a preview loop) must not grow the list without bound
 constexpr size_t kMaxDispatchesInFlight = 256;     // a caller that never throttles or synchronises still cannot queue without bound
-constexpr int kShadowCount = 72;          // slot of the shadow-queue length in ctx->counts (80 words)
 
 // the statistics an event pair of each kind adds to: its time, and where there is one its launch count
 const struct { double ptmi_stats::*ms; uint64_t ptmi_stats::*launches; } kEventStat[kEventKinds] = {
@@ -99,19 +98,6 @@ struct Timed {
     }
 };
 
-// the control words live for the context's life (ptmi_get_stats reads acc[0]); the planes follow the output buffer's size
-int adaptive_words(ptmi_ctx *c) {
-    if (!c->ad.ctl) {
-        HIP_TRY(c, hipMalloc(&c->ad.ctl, 4 * sizeof(uint32_t)));
-        HIP_TRY(c, hipMemset(c->ad.ctl, 0, 4 * sizeof(uint32_t)));
-    }
-    if (!c->ad.acc) {
-        HIP_TRY(c, hipMalloc(&c->ad.acc, 4 * sizeof(unsigned long long)));
-        HIP_TRY(c, hipMemset(c->ad.acc, 0, 4 * sizeof(unsigned long long)));
-    }
-    return PTMI_OK;
-}
-
 #ifndef PT_REPACK
 #define PT_REPACK 1          /* A/B switch: 0 leaves the path state at the path id for every bounce (no tail arrays in use) */
 #endif
@@ -127,7 +113,7 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         return fail(c, PTMI_E_INVALID, "camera says %ux%u but the output buffer is %ux%u", cam->width, cam->height, c->W, c->H);
     if (n_frames == 0 || (ap && rounds == 0)) return PTMI_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (ap && ((rc = adaptive_words(c)) || (rc = make_planes(c, group_set(kByAdaptive), (size_t)c->W * c->H, c->plane)))) return rc;
+    if (ap && (rc = make_planes(c, group_set(kByAdaptive), (size_t)c->W * c->H, c->plane))) return rc;
     const DevBand band = pt_band_of(c->opt, c->W, c->H);
     if (band.y0 >= band.y1) return fail(c, PTMI_E_INVALID, "tile rows [%u,%u) outside the %u-row frame", band.y0, band.y1, c->H);
     if (band.rows == 0) return PTMI_OK;                         // more parts than strips: nothing to render here
@@ -201,39 +187,41 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         if (!env_w) tp.W = nullptr;
         float4 *const aov_rec = c->aov_mask ? ln.aov : nullptr;         // written by shade(0), read by the fold after the last bounce
         float4 *const mom = plane_as<float4>(c, kMoments);
+        unsigned long long *const ct = c->d_counters;
+        uint32_t *const qlen = &c->d_control[kCwQueue], *const slen = &c->d_control[kCwShadow];    // queue lengths by bounce; shadow, by parity
         if (ap && cam->frame_index == 0u) { pt_launch_adaptive_restart(ms, blocks, band, mom); c->ad_rounds = 0; }
         // a batch: fb frames of every pixel from frame0 on, or (ap) of every listed pixel from its own count on
         auto batch = [&](uint32_t frame0, uint32_t fb) -> int {
-            const DevPixels px = ap ? DevPixels{band, 0u, c->ad.list, &c->ad.ctl[1], mom, c->ad.acc}
+            const DevPixels px = ap ? DevPixels{band, 0u, c->ad.list, &c->d_control[kCwAdActive], mom, &ct[kCtAdTraced]}
                                     : DevPixels{band, frame0, nullptr, nullptr, nullptr, nullptr};
-            { Timed t(c, kRaygen, t3, ms); pt_launch_raygen(ms, blocks, *cam, px, fb, bp, &ln.counts[0]); }
+            { Timed t(c, kRaygen, t3, ms); pt_launch_raygen(ms, blocks, *cam, px, fb, bp, &qlen[0]); }
             int cur = 0;
             for (uint32_t b = 0; b < maxb; b++) {
                 const bool tail = b > rb;                                   // the state is in the tail arrays
                 const uint32_t *q = b == 0 || b == rb + 1 ? nullptr : ln.queue[cur];   // bounce 0 / after the repack: slot i holds path / state i
                 const DevPaths sp = tail ? tp : bp;
                 const int par = side ? (int)(b & 1u) : 0;
-                const ShadeParams shp{b, maxb, c->opt.do_mis, c->d_stats, side ? 1u : 0u, tail ? ln.pid : nullptr};
-                { Timed t(c, kExtend, t2, ms); launch_extend(c, ms, cfg, sp, q, &ln.counts[b], ln.hits); }
+                const ShadeParams shp{b, maxb, c->opt.do_mis, ct, side ? 1u : 0u, tail ? ln.pid : nullptr};
+                { Timed t(c, kExtend, t2, ms); launch_extend(c, ms, cfg, sp, q, &qlen[b], ln.hits); }
                 const bool last = b + 1 == maxb;
                 if (side && b >= 2) HIP_TRY(c, hipStreamWaitEvent(ms, ln.ev_shadow[par], 0));      // its records are read
                 { Timed t(c, kShade, t3, ms);
                   (c->opt.perf_mode ? pt_launch_shade_fast : pt_launch_shade)(
-                      ms, shade_blocks, c->sc, sp, q, &ln.counts[b], ln.hits, ln.sh[par], ln.alive, ln.shadowm, shp,
+                      ms, shade_blocks, c->sc, sp, q, &qlen[b], ln.hits, ln.sh[par], ln.alive, ln.shadowm, shp,
                       b == 0 ? aov_rec : nullptr); }
                 { Timed t(c, kCompact, t3, ms);
-                  pt_launch_compact(ms, tiles, q, &ln.counts[b], ln.alive, nee ? ln.shadowm : nullptr,
-                                    ln.word_off, ln.queue[cur ^ 1], &ln.counts[b + 1], ln.sq[par], &ln.counts[kShadowCount + par],
-                                    c->d_stats, b, last ? 0 : 1);
-                  if (b == rb && !last) pt_launch_repack(ms, blocks, &ln.counts[b + 1], ln.queue[cur ^ 1], bp, tp, ln.pid); }
+                  pt_launch_compact(ms, tiles, q, &qlen[b], ln.alive, nee ? ln.shadowm : nullptr,
+                                    ln.word_off, ln.queue[cur ^ 1], &qlen[b + 1], ln.sq[par], &slen[par],
+                                    ct, b, last ? 0 : 1);
+                  if (b == rb && !last) pt_launch_repack(ms, blocks, &qlen[b + 1], ln.queue[cur ^ 1], bp, tp, ln.pid); }
                 if (side) {
                     HIP_TRY(c, hipEventRecord(ln.ev_ready, ms));
                     HIP_TRY(c, hipStreamWaitEvent(ss, ln.ev_ready, 0));
-                    { Timed t(c, kShadow, t3, ss); launch_shadow(c, ss, cfg_shadow, bp, ln.sh[par], ln.sq[par], &ln.counts[kShadowCount + par], nullptr); }
+                    { Timed t(c, kShadow, t3, ss); launch_shadow(c, ss, cfg_shadow, bp, ln.sh[par], ln.sq[par], &slen[par], nullptr); }
                     HIP_TRY(c, hipEventRecord(ln.ev_shadow[par], ss));
                 } else if (nee) {
                     Timed t(c, kShadow, t3, ms);
-                    launch_shadow(c, ms, cfg_shadow, bp, ln.sh[0], ln.sq[0], &ln.counts[kShadowCount], nullptr);
+                    launch_shadow(c, ms, cfg_shadow, bp, ln.sh[0], ln.sq[0], &slen[0], nullptr);
                 }
                 cur ^= 1;
             }
@@ -271,7 +259,7 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         c->in_flight.push_back(done);
         if (c->in_flight.size() > kMaxDispatchesInFlight) HIP_TRY(c, throttle(c, kMaxDispatchesInFlight));
     }
-    if (!ap) { c->st.paths += npix * n_frames; c->st.frames += n_frames; }      // adaptive: counted on the device (DevAdaptive::acc)
+    if (!ap) { c->st.paths += npix * n_frames; c->st.frames += n_frames; }      // adaptive: counted on the device (kCtAdTraced)
     c->st.dispatches += 1;
     return PTMI_OK;
 }
@@ -308,25 +296,23 @@ int ptmi_adaptive_status(ptmi_ctx *c, struct ptmi_adaptive_status *out) {
     if (!c->moments_on) return fail(c, PTMI_E_STATE, "the moments plane is off (ptmi_set_moments)");
     if (!c->plane[kMoments]) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = adaptive_words(c);
-    if (rc) return rc;
     std::memset(out, 0, sizeof *out);
     const DevBand band = pt_band_of(c->opt, c->W, c->H);
     const unsigned long long preset[3] = {0ull, ~0ull, 0ull};
-    unsigned long long acc[3] = {0ull, 0ull, 0ull};
-    uint32_t ctl[2] = {0u, 0u};
+    unsigned long long sum_min_max[3] = {0ull, 0ull, 0ull};
+    uint32_t active = 0u;
     HIP_TRY(c, quiesce(c));
     if (band.y0 < band.y1 && band.rows) {
-        HIP_TRY(c, hipMemcpyAsync(&c->ad.acc[1], preset, sizeof preset, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(&c->d_counters[kCtAdSum], preset, sizeof preset, hipMemcpyHostToDevice, c->stream));
         pt_launch_adaptive_status(c->stream, c->n_cu * 8, band, plane_as<float4>(c, kMoments), c->ad);
-        HIP_TRY(c, hipMemcpyAsync(acc, &c->ad.acc[1], sizeof acc, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(sum_min_max, &c->d_counters[kCtAdSum], sizeof sum_min_max, hipMemcpyDeviceToHost, c->stream));
     }
-    HIP_TRY(c, hipMemcpyAsync(ctl, c->ad.ctl, sizeof ctl, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&active, &c->d_control[kCwAdActive], sizeof active, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    out->active = ctl[1];
-    out->samples = acc[0];
-    out->min_count = acc[1] == ~0ull ? 0u : (uint32_t)acc[1];
-    out->max_count = (uint32_t)acc[2];
+    out->active = active;
+    out->samples = sum_min_max[0];
+    out->min_count = sum_min_max[1] == ~0ull ? 0u : (uint32_t)sum_min_max[1];
+    out->max_count = (uint32_t)sum_min_max[2];
     out->rounds = c->ad_rounds;
     return PTMI_OK;
 }
@@ -362,12 +348,11 @@ int ptmi_reproject(ptmi_ctx *c, const ptmi_camera *from, const ptmi_camera *to, 
     const size_t npix = (size_t)c->W * c->H;
     const uint32_t history = bit(kRpOut) | bit(kRpMoments) | bit(kRpNormal) | (have_albedo ? bit(kRpAlbedo) : 0u) | (have_ids ? bit(kRpId) : 0u);
     if ((rc = make_planes(c, history, npix, c->plane))) return rc;
-    if (!c->d_reproject) HIP_TRY(c, hipMalloc(&c->d_reproject, 4 * sizeof(unsigned long long)));
     Lane &ln = c->lane;
     if (band.rows && (rc = ensure_capacity(c, ln, (size_t)band.rows * band.width))) return rc;
     if ((rc = traverse_arm(c, true, kSpillMain, cfg, false))) return rc;      // (the statistics keep the variants of the last dispatch)
     const hipStream_t s = c->stream;
-    HIP_TRY(c, hipMemsetAsync(c->d_reproject, 0, 4 * sizeof(unsigned long long), s));
+    HIP_TRY(c, hipMemsetAsync(&c->d_counters[kCtRpCarried], 0, 4 * sizeof(unsigned long long), s));
     if (band.rows == 0) return PTMI_OK;                         // more parts than strips: no pixel of this context's
     const struct { FramePlane to; const void *from; bool on; } copies[] = {
         {kRpOut, c->d_out, true}, {kRpMoments, c->plane[kMoments], true}, {kRpNormal, c->plane[kAovNormal], true},
@@ -375,8 +360,8 @@ int ptmi_reproject(ptmi_ctx *c, const ptmi_camera *from, const ptmi_camera *to, 
     for (const auto &cp : copies)
         if (cp.on) HIP_TRY(c, hipMemcpyAsync(c->plane[cp.to], cp.from, plane_bytes(cp.to, npix), hipMemcpyDeviceToDevice, s));
     const int blocks = c->n_cu * 8;
-    pt_launch_center_rays(s, blocks, *to, band, ln.paths, &ln.counts[0]);
-    launch_extend(c, s, cfg, ln.paths, nullptr, &ln.counts[0], ln.hits);
+    pt_launch_center_rays(s, blocks, *to, band, ln.paths, &c->d_control[kCwQueue]);
+    launch_extend(c, s, cfg, ln.paths, nullptr, &c->d_control[kCwQueue], ln.hits);
     ReprojectArgs a{};
     a.from = *from; a.band = band;
     a.max_history = q.max_history ? q.max_history : 32u;
@@ -388,7 +373,7 @@ int ptmi_reproject(ptmi_ctx *c, const ptmi_camera *from, const ptmi_camera *to, 
     a.h_albedo = have_albedo ? plane_as<float4>(c, kRpAlbedo) : nullptr; a.h_ids = have_ids ? plane_as<uint2>(c, kRpId) : nullptr;
     a.out = c->d_out; a.mom = plane_as<float4>(c, kMoments); a.normal = plane_as<float4>(c, kAovNormal);
     a.albedo = have_albedo ? plane_as<float4>(c, kAovAlbedo) : nullptr; a.ids = have_ids ? plane_as<uint2>(c, kAovId) : nullptr;
-    a.status = c->d_reproject;
+    a.status = c->d_counters;
     pt_launch_reproject(s, a);
     HIP_TRY(c, hipGetLastError());
     return PTMI_OK;
@@ -397,12 +382,13 @@ int ptmi_reproject(ptmi_ctx *c, const ptmi_camera *from, const ptmi_camera *to, 
 int ptmi_reproject_status(ptmi_ctx *c, struct ptmi_reproject_status *out) {
     if (!c || !out) return PTMI_E_INVALID;
     std::memset(out, 0, sizeof *out);
-    if (!c->d_reproject) return PTMI_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, quiesce(c));
     unsigned long long h[4];
-    HIP_TRY(c, hipMemcpy(h, c->d_reproject, sizeof h, hipMemcpyDeviceToHost));
-    out->carried = h[0]; out->disoccluded = h[1]; out->missed = h[2]; out->samples = h[3];
+    HIP_TRY(c, hipMemcpy(h, &c->d_counters[kCtRpCarried], sizeof h, hipMemcpyDeviceToHost));
+    const auto word = [&](CounterWord w) { return h[w - kCtRpCarried]; };
+    out->carried = word(kCtRpCarried); out->disoccluded = word(kCtRpDisoccluded);
+    out->missed = word(kCtRpMissed); out->samples = word(kCtRpSamples);
     return PTMI_OK;
 }
 

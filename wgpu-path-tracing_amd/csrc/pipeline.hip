@@ -139,7 +139,7 @@ __global__ __launch_bounds__(TILE_WORDS) void k_tile_sums(const uint32_t *__rest
     const uint32_t count = *count_ptr;
     const uint32_t nwords = (count + 63u) >> 6;
     if (blockIdx.x == 0 && threadIdx.x == 0) {          // atomics: two batches may be in flight on two lanes
-        atomicAdd(&stats[0], (unsigned long long)count); atomicAdd(&stats[8 + bounce], (unsigned long long)count);
+        atomicAdd(&stats[kCtSegments], (unsigned long long)count); atomicAdd(&stats[kCtByBounce + bounce], (unsigned long long)count);
     }
     if (blockIdx.x * TILE_WORDS >= nwords) return;
     const uint32_t w = blockIdx.x * TILE_WORDS + threadIdx.x;
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(TILE_WORDS) void k_tile_sums(const uint32_t *__rest
         for (int i = 0; i < TILE_WAVES; i++) { t += wsum[i]; ts += wssum[i]; }
         tile_sums[blockIdx.x] = t;
         shadow_tile_sums[blockIdx.x] = ts;
-        if (ts) { atomicAdd(&stats[1], (unsigned long long)ts); atomicAdd(&stats[2], (unsigned long long)ts); }   // shadow rays, and those traced (integers: order-free)
+        if (ts) { atomicAdd(&stats[kCtShadowRays], (unsigned long long)ts); atomicAdd(&stats[kCtShadowTraced], (unsigned long long)ts); }   // shadow rays, and those traced (integers: order-free)
     }
 }
 
@@ -370,11 +370,11 @@ __global__ __launch_bounds__(BLOCK) void k_ad_restart(DevBand band, float4 *__re
         mom[band.frame_pixel(pix)].z = 0.0f;
 }
 
-// ctl[0] = band pixels (the `count` of the list build). Whole waves stay in the loop so that the ballot sees all 64 lanes.
+// control[kCwAdPixels] = band pixels (the `count` of the list build). Whole waves stay in the loop so that the ballot sees all 64 lanes.
 __global__ __launch_bounds__(BLOCK) void k_ad_select(DevBand band, ptmi_adaptive_params ap, const float4 *__restrict__ mom,
-                                                     uint64_t *__restrict__ ballot, uint32_t *__restrict__ ctl) {
+                                                     uint64_t *__restrict__ ballot, uint32_t *__restrict__ control) {
     const uint32_t npix = band.rows * band.width;
-    if (blockIdx.x == 0 && threadIdx.x == 0) ctl[0] = npix;
+    if (blockIdx.x == 0 && threadIdx.x == 0) control[kCwAdPixels] = npix;
     const uint32_t padded = (npix + 63u) & ~63u;
     for (uint32_t pix = blockIdx.x * BLOCK + threadIdx.x; pix < padded; pix += gridDim.x * BLOCK) {
         bool active = false;
@@ -421,12 +421,12 @@ __global__ __launch_bounds__(TILE_WORDS) void k_ad_scatter(const uint32_t *__res
 }
 
 // k_raygen and the three folds over the list: each pixel from its own frame index (mom.z, which the moments fold, launched last,
-// moves on). traced[0] += the paths of this batch (ptmi_stats.paths).
+// moves on). *traced += the paths of this batch (ptmi_stats.paths).
 __global__ __launch_bounds__(BLOCK) void k_ad_raygen(ptmi_camera cam, DevBand band, const uint32_t *__restrict__ list,
                                                      const uint32_t *__restrict__ n_active, uint32_t n_frames,
                                                      const float4 *__restrict__ mom, DevPaths P, uint32_t *__restrict__ count_out,
                                                      unsigned long long *__restrict__ traced) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&traced[0], (unsigned long long)(*n_active * n_frames));
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(traced, (unsigned long long)(*n_active * n_frames));
     raygen(cam, ListedPixels{band, list, n_active, mom}, n_frames, P, count_out);
 }
 __global__ __launch_bounds__(BLOCK) void k_ad_accumulate(DevBand band, const uint32_t *__restrict__ list, const uint32_t *__restrict__ n_active,
@@ -446,15 +446,17 @@ __global__ __launch_bounds__(BLOCK) void k_ad_accumulate_moments(DevBand band, c
     fold_moments(ListedPixels{band, list, n_active, mom}, n_frames, L, l_stride, mom);
 }
 
-// ptmi_adaptive_status: acc[1] += the band's counts, acc[2] / acc[3] = their minimum / maximum (the caller presets 0, ~0, 0)
-__global__ __launch_bounds__(BLOCK) void k_ad_status(DevBand band, const float4 *__restrict__ mom, unsigned long long *__restrict__ acc) {
+// ptmi_adaptive_status: counters[kCtAdSum] += the band's counts, [kCtAdMin] / [kCtAdMax] = their minimum / maximum (the caller presets
+// 0, ~0, 0)
+__global__ __launch_bounds__(BLOCK) void k_ad_status(DevBand band, const float4 *__restrict__ mom,
+                                                     unsigned long long *__restrict__ counters) {
     const uint32_t npix = band.rows * band.width;
     unsigned long long sum = 0, lo = ~0ull, hi = 0;
     for (uint32_t pix = blockIdx.x * BLOCK + threadIdx.x; pix < npix; pix += gridDim.x * BLOCK) {
         const unsigned long long n = (uint32_t)mom[band.frame_pixel(pix)].z;
         sum += n; lo = n < lo ? n : lo; hi = n > hi ? n : hi;
     }
-    if (lo != ~0ull) { atomicAdd(&acc[1], sum); atomicMin(&acc[2], lo); atomicMax(&acc[3], hi); }
+    if (lo != ~0ull) { atomicAdd(&counters[kCtAdSum], sum); atomicMin(&counters[kCtAdMin], lo); atomicMax(&counters[kCtAdMax], hi); }
 }
 
 // ---- multi-GPU gather (ptmi_multi_gather): a device's rows (DevBand: the strips part, part + parts, ...) <-> one contiguous
@@ -631,12 +633,12 @@ void pt_launch_adaptive_restart(hipStream_t s, int blocks, DevBand band, float4 
 void pt_launch_adaptive_list(hipStream_t s, int blocks, DevBand band, const ptmi_adaptive_params &ap, const float4 *mom, DevAdaptive ad) {
     const uint32_t npix = band.rows * band.width;
     const int tiles = (int)(((npix + 63u) / 64u + TILE_WORDS - 1) / TILE_WORDS);
-    hipLaunchKernelGGL(k_ad_select, dim3(blocks), dim3(BLOCK), 0, s, band, ap, mom, ad.ballot, ad.ctl);
-    hipLaunchKernelGGL(k_ad_tile_sums, dim3(tiles), dim3(TILE_WORDS), 0, s, &ad.ctl[0], ad.ballot, ad.tile_sums);
-    hipLaunchKernelGGL(k_ad_scatter, dim3(tiles), dim3(TILE_WORDS), 0, s, &ad.ctl[0], ad.ballot, ad.tile_sums, ad.list, &ad.ctl[1]);
+    hipLaunchKernelGGL(k_ad_select, dim3(blocks), dim3(BLOCK), 0, s, band, ap, mom, ad.ballot, ad.control);
+    hipLaunchKernelGGL(k_ad_tile_sums, dim3(tiles), dim3(TILE_WORDS), 0, s, &ad.control[kCwAdPixels], ad.ballot, ad.tile_sums);
+    hipLaunchKernelGGL(k_ad_scatter, dim3(tiles), dim3(TILE_WORDS), 0, s, &ad.control[kCwAdPixels], ad.ballot, ad.tile_sums, ad.list, &ad.control[kCwAdActive]);
 }
 void pt_launch_adaptive_status(hipStream_t s, int blocks, DevBand band, const float4 *mom, DevAdaptive ad) {
-    hipLaunchKernelGGL(k_ad_status, dim3(blocks), dim3(BLOCK), 0, s, band, mom, ad.acc);
+    hipLaunchKernelGGL(k_ad_status, dim3(blocks), dim3(BLOCK), 0, s, band, mom, ad.counters);
 }
 // tile totals the list build of `npix` pixels needs (DevAdaptive::tile_sums)
 uint32_t pt_adaptive_tiles(uint32_t npix) { return ((npix + 63u) / 64u + TILE_WORDS - 1) / TILE_WORDS; }

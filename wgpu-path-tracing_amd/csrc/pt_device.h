@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <initializer_list>
 #include "ptmi_layout.h"
 #include "ptmi.h"
 
@@ -70,7 +71,7 @@ struct DevScene {
     const float4 *wnodes16, *ref_wnodes16;
     uint32_t root_ref16, ref_root_ref16;
     const uint4 *qnodes16;      // qnodes with the same 16-bit references (NULL: none)
-    unsigned long long *verify_stat;    // += rays whose winner failed its reference leaf's box and were traced again
+    unsigned long long *verify_stat;    // the word kCtVerifyFailed: += rays whose winner failed its reference leaf's box and were traced again
     const DevScene *self;       // this description in device memory (the own-leaf kernels read it from there, not from kernel arguments)
     const float4 *shade_tab;    // the shade tables (below): what `shade` stages into LDS
     DevEnv env;                 // the environment map behind every miss (tab NULL: none, a miss adds throughput * 0)
@@ -153,13 +154,63 @@ struct DevBand {
 PT_HD bool pt_plays_roulette(uint32_t bounce) { return bounce > 2u; }
 inline uint32_t pt_repack_bounce() { uint32_t b = 0; while (!pt_plays_roulette(b)) b++; return b; }
 
+// ---- counter and control words: the two small blocks of a context that kernels and host code share by word ----
+// Both are made and zeroed by ptmi_create and live as long as the context. Kernels get the block's base (ShadeParams::stats,
+// DevAdaptive::counters / control, ReprojectArgs::status) or the address of one word (DevScene::verify_stat, queue lengths).
+constexpr int kMaxBounces = 64;         // ptmi_options.max_bounces' upper limit (ptmi_set_options)
+// u64 counters, added to with atomics. [kCtSegments, kCtDispatchEnd) is what ptmi_reset_stats zeroes.
+enum CounterWord {
+    kCtSegments,                        // path segments (k_tile_sums: the queue length of every bounce)
+    kCtShadowRays,                      // records `shade` left (k_tile_sums) + next-event samples counted but not traced (k_shade)
+    kCtShadowTraced,                    // records `shade` left
+    kCtEmitRecords,                     // ... of which records of emissive hits: no shadow rays, ptmi_get_stats takes them off both
+    kCtVerifyFailed,                    // own leaves: rays traced again (DevScene::verify_stat)
+    kCtAdTraced,                        // paths of adaptive dispatches (ptmi_stats.paths)
+    kCtByBounce,                        // kMaxBounces words: segments of bounce b
+    kCtDispatchEnd = kCtByBounce + kMaxBounces,
+    kCtAdSum = kCtDispatchEnd, kCtAdMin, kCtAdMax,                      // ptmi_adaptive_status: the band's counts (preset 0, ~0, 0 per call)
+    kCtRpCarried, kCtRpDisoccluded, kCtRpMissed, kCtRpSamples,          // ptmi_reproject_status: the last ptmi_reproject
+    kCounterWords
+};
+// u32 control words: lengths that one kernel writes and the next reads
+enum ControlWord {
+    kCwQueue,                           // kMaxBounces + 1 words: the queue length of bounce b (the last bounce writes that of the next)
+    kCwShadow = kCwQueue + kMaxBounces + 1,     // 2 words: the shadow queue's length, by bounce parity (overlap)
+    kCwAdPixels = kCwShadow + 2,        // adaptive round: the band's pixels
+    kCwAdActive,                        // ... and how many of them the round lists
+    kControlWords
+};
+// no two names share a word: every name or run of words starts where the one before it ends, and the last ends the block
+constexpr bool pt_words_disjoint(std::initializer_list<int> first_then_length, int total) {
+    int at = 0;
+    for (const int *p = first_then_length.begin(); p != first_then_length.end(); p += 2) {
+        if (p[0] != at) return false;
+        at += p[1];
+    }
+    return at == total;
+}
+static_assert(pt_words_disjoint({kCtSegments, 1, kCtShadowRays, 1, kCtShadowTraced, 1, kCtEmitRecords, 1, kCtVerifyFailed, 1, kCtAdTraced, 1,
+                                 kCtByBounce, kMaxBounces, kCtAdSum, 1, kCtAdMin, 1, kCtAdMax, 1,
+                                 kCtRpCarried, 1, kCtRpDisoccluded, 1, kCtRpMissed, 1, kCtRpSamples, 1}, kCounterWords),
+              "a counter word has two names, or none");
+static_assert(pt_words_disjoint({kCwQueue, kMaxBounces + 1, kCwShadow, 2, kCwAdPixels, 1, kCwAdActive, 1}, kControlWords),
+              "a control word has two names, or none");
+static_assert(kCtDispatchEnd - kCtByBounce == 64 && sizeof(ptmi_stats::segments_by_bounce) == 64 * sizeof(uint64_t),
+              "a word per bounce up to max_bounces' limit, as ptmi_stats reports them");
+static_assert(kCwShadow - kCwQueue == 64 + 1, "bounce b reads queue length b and writes b + 1, for b < 64");
+static_assert(kCtAdTraced < kCtDispatchEnd && kCtAdSum >= kCtDispatchEnd && kCtRpCarried >= kCtDispatchEnd,
+              "ptmi_reset_stats zeroes the dispatch statistics and the adaptive traced count, nothing else");
+static_assert(kCtAdMin == kCtAdSum + 1 && kCtAdMax == kCtAdSum + 2, "ptmi_adaptive_status presets and reads the three with one copy each");
+static_assert(kCtRpDisoccluded == kCtRpCarried + 1 && kCtRpMissed == kCtRpCarried + 2 && kCtRpSamples == kCtRpCarried + 3,
+              "ptmi_reproject zeroes the four with one memset, ptmi_reproject_status reads them with one copy");
+
 struct ShadeParams {
     uint32_t bounce, max_bounces, do_mis;
-    unsigned long long *stats;          // [1] += next-event samples counted but not traced (zero contribution)
+    unsigned long long *stats;          // the counter block: [kCtShadowRays] += next-event samples counted but not traced (zero contribution)
     uint32_t emit_records;              // 1: an emissive hit does not add to L here; it leaves a record (SO.w = -2: nothing to trace)
                                         //    that `shadow` adds like an unoccluded light sample — all additions to L then happen in
                                         //    that one kernel, in bounce order, and `shadow` can run beside the next bounce's kernels.
-                                        //    stats[3] += such records (they are not shadow rays)
+                                        //    stats[kCtEmitRecords] += such records (they are not shadow rays)
     const uint32_t *pid;                // path id of a state slot after the repack (NULL: the slot is the path id)
 };
 
@@ -243,7 +294,7 @@ size_t pt_spill_bytes(int blocks);
 struct DevPixels {
     DevBand band; uint32_t frame0;
     const uint32_t *list, *n_active; const float4 *mom;
-    unsigned long long *traced;         // listed: [0] += the batch's paths (a plain dispatch counts its paths on the host)
+    unsigned long long *traced;         // listed: the word kCtAdTraced, += the batch's paths (a plain dispatch counts its paths on the host)
 };
 // *count_out = entries * n_frames
 void pt_launch_raygen(hipStream_t s, int blocks, const ptmi_camera &cam, DevPixels px, uint32_t n_frames, DevPaths p,
@@ -292,12 +343,12 @@ struct DevAdaptive {
     uint64_t *ballot;             // one word per 64 band pixels: bit set = the pixel gets frames this round
     uint32_t *list;               // ... as the ascending list of band-local pixel indices
     uint32_t *tile_sums;          // pt_adaptive_tiles(band pixels) words
-    uint32_t *ctl;                // [0] band pixels, [1] length of the list
-    unsigned long long *acc;      // [0] paths traced by adaptive dispatches; [1] sum, [2] min, [3] max of the counts (status)
+    uint32_t *control;            // the context's control block: kCwAdPixels, kCwAdActive (the length of the list)
+    unsigned long long *counters; // the context's counter block: kCtAdTraced, and kCtAdSum / Min / Max of the counts (status)
 };
 uint32_t pt_adaptive_tiles(uint32_t npix);
 void pt_launch_adaptive_restart(hipStream_t s, int blocks, DevBand band, float4 *mom);          // every count of the band back to 0
-// select + list build: ad.ballot, ad.list, ad.ctl of this round from the moments plane
+// select + list build: ad.ballot, ad.list and the two control words of this round from the moments plane
 void pt_launch_adaptive_list(hipStream_t s, int blocks, DevBand band, const ptmi_adaptive_params &ap, const float4 *mom, DevAdaptive ad);
 // (ray generation and the folds of a round: pt_launch_raygen / pt_launch_accumulate* with the list as their DevPixels)
 void pt_launch_adaptive_status(hipStream_t s, int blocks, DevBand band, const float4 *mom, DevAdaptive ad);
@@ -321,7 +372,7 @@ struct ReprojectArgs {
     const ptmi_triangle *tris; uint32_t n_tris;
     const float4 *h_out, *h_mom, *h_normal, *h_albedo; const uint2 *h_ids;   // the snapshot (albedo / ids NULL: that plane is off)
     float4 *out, *mom, *normal, *albedo; uint2 *ids;    // the live planes, rewritten
-    unsigned long long *status;                         // += carried, disoccluded, missed, samples
+    unsigned long long *status;                         // the counter block: kCtRpCarried, ...Disoccluded, ...Missed, ...Samples +=
 };
 void pt_launch_reproject(hipStream_t s, const ReprojectArgs &a);
 void pt_launch_blit(hipStream_t s, int blocks, uint32_t W, uint32_t H, const float4 *color, float4 *out_f32,

@@ -12,7 +12,6 @@
 
 namespace {
 
-constexpr int kStatsWords = 8 + 64;
 void vfail(std::string &err, const char *fmt, va_list ap) {
     char buf[512];
     vsnprintf(buf, sizeof buf, fmt, ap);
@@ -122,7 +121,8 @@ int read_plane(ptmi_ctx *c, FramePlane k, const void *src, void *dst, size_t n, 
 
 // a fresh moments plane (ptmi_resize, ptmi_set_moments): no round has listed anything in it
 int reset_adaptive_rounds(ptmi_ctx *c) {
-    if (c->ad.ctl) HIP_TRY(c, hipMemset(c->ad.ctl, 0, 4 * sizeof(uint32_t)));
+    static_assert(kCwAdActive == kCwAdPixels + 1, "the round's two words, zeroed as one");
+    HIP_TRY(c, hipMemset(&c->d_control[kCwAdPixels], 0, 2 * sizeof(uint32_t)));
     c->ad_rounds = 0;
     return PTMI_OK;
 }
@@ -293,14 +293,16 @@ int ptmi_create(int device_ordinal, ptmi_ctx **out) {
 #endif
         for (hipEvent_t *e : {&ln.ev_ready, &ln.ev_shadow[0], &ln.ev_shadow[1]})
             ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipMalloc(&ln.counts, 80 * sizeof(uint32_t)) == hipSuccess;
         if (!ok) { ptmi_destroy(c); return fail(nullptr, PTMI_E_HIP, "stream / event creation failed"); }
     }
-    if (hipMalloc(&c->d_stats, kStatsWords * sizeof(unsigned long long)) != hipSuccess ||
+    if (hipMalloc(&c->d_counters, kCounterWords * sizeof(unsigned long long)) != hipSuccess ||
+        hipMalloc(&c->d_control, kControlWords * sizeof(uint32_t)) != hipSuccess ||
         hipMalloc(&c->d_scene, sizeof(DevScene)) != hipSuccess || hipMemset(c->d_scene, 0, sizeof(DevScene)) != hipSuccess ||
-        hipMemset(c->d_stats, 0, kStatsWords * sizeof(unsigned long long)) != hipSuccess) {
+        hipMemset(c->d_counters, 0, kCounterWords * sizeof(unsigned long long)) != hipSuccess ||
+        hipMemset(c->d_control, 0, kControlWords * sizeof(uint32_t)) != hipSuccess) {
         ptmi_destroy(c); return fail(nullptr, PTMI_E_HIP, "device allocation failed");
     }
+    c->ad.control = c->d_control; c->ad.counters = c->d_counters;
     *out = c;
     return PTMI_OK;
 }
@@ -315,14 +317,14 @@ int ptmi_destroy(ptmi_ctx *c) {
     {
         Lane &ln = c->lane;
         free_batch(ln);
-        dfree(ln.counts); dfree(ln.d_spill); dfree(ln.d_spill_side);
+        dfree(ln.d_spill); dfree(ln.d_spill_side);
         for (hipEvent_t e : {ln.ev_ready, ln.ev_shadow[0], ln.ev_shadow[1]}) if (e) (void)hipEventDestroy(e);
         if (ln.side) (void)hipStreamDestroy(ln.side);
     }
     for (void *&p : c->buf) dfree(p);
     dfree(c->d_atlas); dfree(c->d_env); dfree(c->d_env_alias);
     drop_planes(c, kAllPlanes);
-    dfree(c->d_stats); dfree(c->d_scene); dfree(c->ad.ctl); dfree(c->ad.acc); dfree(c->d_reproject);
+    dfree(c->d_counters); dfree(c->d_control); dfree(c->d_scene);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
     return PTMI_OK;
@@ -403,7 +405,7 @@ int ptmi_resize(ptmi_ctx *c, uint32_t w, uint32_t h) {
 
 int ptmi_set_options(ptmi_ctx *c, const ptmi_options *o) {
     if (!c || !o) return PTMI_E_INVALID;
-    if (o->max_bounces < 1 || o->max_bounces > 64) return fail(c, PTMI_E_INVALID, "max_bounces %u not in 1..64", o->max_bounces);
+    if (o->max_bounces < 1 || o->max_bounces > kMaxBounces) return fail(c, PTMI_E_INVALID, "max_bounces %u not in 1..64", o->max_bounces);
     if (o->traversal > PTMI_TRAVERSAL_GLOBAL_EXACT) return fail(c, PTMI_E_INVALID, "unknown traversal mode %u", o->traversal);
     if (o->tile_y1 != 0 && o->tile_y0 >= o->tile_y1) return fail(c, PTMI_E_INVALID, "empty tile rows [%u,%u)", o->tile_y0, o->tile_y1);
     if (o->tile_parts > 1 && o->tile_part >= o->tile_parts)
@@ -605,18 +607,15 @@ int ptmi_get_stats(ptmi_ctx *c, ptmi_stats *out) {
     if (!c || !out) return PTMI_E_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, quiesce(c));
-    unsigned long long h[kStatsWords];
-    HIP_TRY(c, hipMemcpy(h, c->d_stats, sizeof h, hipMemcpyDeviceToHost));
-    c->st.segments = h[0]; c->st.shadow_rays = h[1] - h[3]; c->st.shadow_traced = h[2] - h[3];      // h[3]: records of emissive hits
-    for (int i = 0; i < 64; i++) c->st.segments_by_bounce[i] = h[8 + i];
-    c->st.verify_failed = h[4];
+    unsigned long long h[kCtDispatchEnd];
+    HIP_TRY(c, hipMemcpy(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
+    c->st.segments = h[kCtSegments];
+    c->st.shadow_rays = h[kCtShadowRays] - h[kCtEmitRecords]; c->st.shadow_traced = h[kCtShadowTraced] - h[kCtEmitRecords];
+    for (int i = 0; i < kMaxBounces; i++) c->st.segments_by_bounce[i] = h[kCtByBounce + i];
+    c->st.verify_failed = h[kCtVerifyFailed];
     c->st.bvh_depth = stats_depth(c);
     *out = c->st;
-    if (c->ad.acc) {                                  // the samples adaptive dispatches traced
-        unsigned long long traced = 0;
-        HIP_TRY(c, hipMemcpy(&traced, c->ad.acc, sizeof traced, hipMemcpyDeviceToHost));
-        out->paths += traced;
-    }
+    out->paths += h[kCtAdTraced];                     // the samples adaptive dispatches traced: in the returned copy only
     return PTMI_OK;
 }
 
@@ -624,8 +623,7 @@ int ptmi_reset_stats(ptmi_ctx *c) {
     if (!c) return PTMI_E_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, quiesce(c));
-    HIP_TRY(c, hipMemset(c->d_stats, 0, kStatsWords * sizeof(unsigned long long)));
-    if (c->ad.acc) HIP_TRY(c, hipMemset(c->ad.acc, 0, sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemset(c->d_counters, 0, kCtDispatchEnd * sizeof(unsigned long long)));      // not the status words of the last calls
     const ptmi_stats old = c->st;
     std::memset(&c->st, 0, sizeof c->st);
     c->st.bvh_depth = stats_depth(c);

@@ -93,7 +93,7 @@ struct Lane {
     uint32_t *pid = nullptr;                           // ... and the path id of each such slot
     uint64_t *alive = nullptr, *shadowm = nullptr;
     size_t mask_words = 0;
-    uint32_t *word_off = nullptr, *counts = nullptr;
+    uint32_t *word_off = nullptr;
     uint32_t *d_spill = nullptr;          // node-stack overflow of the global traversal variant (128 MiB on 256 CUs; first use)
     uint32_t *d_spill_side = nullptr;     // ... of the `shadow` kernel when it runs beside `extend`
     uint8_t *d_occ = nullptr;
@@ -127,13 +127,12 @@ struct ptmi_ctx {
     float4 *d_out = nullptr;                           // what dispatches write: plane[kOut] or the caller's buffer (ptmi_bind_output_device)
     uint32_t aov_mask = 0;                             // ptmi_set_aovs: a plane is present while its bit is set and the output buffer exists
     bool moments_on = false;                           // ptmi_set_moments: likewise
-    // adaptive sampling (ptmi_dispatch_adaptive): ballot, list and tile_sums are views of the planes; the control words and counters
-    // live for the context's life
+    // the counter and control words (pt_device.h CounterWord, ControlWord): made and zeroed by ptmi_create
+    unsigned long long *d_counters = nullptr;          // kCounterWords
+    uint32_t *d_control = nullptr;                     // kControlWords
+    // adaptive sampling (ptmi_dispatch_adaptive): ballot, list and tile_sums are views of the planes, control and counters of the two blocks
     DevAdaptive ad{};
     uint32_t ad_rounds = 0;                            // rounds since the last restart
-    unsigned long long *d_reproject = nullptr;         // ptmi_reproject_status: the four counters of the last ptmi_reproject (made by the first)
-
-    unsigned long long *d_stats = nullptr;
 
     // statistics
     ptmi_stats st{};

@@ -109,10 +109,10 @@ __global__ __launch_bounds__(RX * RY) void k_reproject(ReprojectArgs a) {
     uint32_t samples = (uint32_t)count;              // at most 2^24 each, 64 lanes
     for (int off = 32; off > 0; off >>= 1) samples += __shfl_down(samples, off);
     if ((threadIdx.x & 63u) == 0u) {
-        if (n_carried) atomicAdd(&a.status[0], n_carried);
-        if (n_dis) atomicAdd(&a.status[1], n_dis);
-        if (n_missed) atomicAdd(&a.status[2], n_missed);
-        if (samples) atomicAdd(&a.status[3], (unsigned long long)samples);
+        if (n_carried) atomicAdd(&a.status[kCtRpCarried], n_carried);
+        if (n_dis) atomicAdd(&a.status[kCtRpDisoccluded], n_dis);
+        if (n_missed) atomicAdd(&a.status[kCtRpMissed], n_missed);
+        if (samples) atomicAdd(&a.status[kCtRpSamples], (unsigned long long)samples);
     }
 }
 

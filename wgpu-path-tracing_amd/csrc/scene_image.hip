@@ -431,7 +431,7 @@ int pt_install_scene(ptmi_ctx *c, PtPrepared *prep) {
     s.qnodes16 = static_cast<const uint4 *>(d[kQnodes16]);
     s.root_ref16 = b.root_ref16; s.ref_root_ref16 = b.ref_root_ref16;
     s.safe_origin = h.safe_origin;
-    s.verify_stat = c->d_stats + 4;
+    s.verify_stat = &c->d_counters[kCtVerifyFailed];
     s.self = c->d_scene;
     s.shade_tab = static_cast<const float4 *>(d[kShadeTab]);
     HIP_TRY(c, hipMemcpy(c->d_scene, &c->sc, sizeof(DevScene), hipMemcpyHostToDevice));

@@ -326,6 +326,7 @@ PT_DEV LightSample sample_light(const DevScene &sc, const ShadeTabs<STAGE> &tabs
 }
 
 constexpr int SBLOCK = 256;
+
 #ifndef PT_SHADE_WAVES
 #define PT_SHADE_WAVES 0           /* > 0: waves per SIMD asked of the register allocator (94 VGPRs = 5 waves by itself) */
 #endif
@@ -334,6 +335,32 @@ constexpr int SBLOCK = 256;
 #else
 #define PT_SHADE_ATTR
 #endif
+
+// What the three ways a path ends in k_shade share, and what its two kinds of miss share. (terminal_add reports the record it left
+// instead of setting the lane's votes through references: a bool behind a reference stays a byte through the ballots.)
+// A path's last addition to L: an emissive hit, a miss under an environment, a miss with a throughput that is not finite. With
+// emit_records the lane leaves a record with nothing to trace (rec_o stays (0, 0, 0, -2)) that `shadow` adds in bounce order, and the
+// caller votes `shadow` and `emitted`; else the addition is made here.
+PT_DEV bool terminal_add(const DevPaths &P, uint32_t emit_records, uint32_t p, v3 e, float4 &rec_d, rgb_sc &rec_c) {
+    if (emit_records) {
+        rec_d.w = __uint_as_float(p);
+        rec_c = rgb_sc{e.x, e.y, e.z};
+        return true;
+    }
+    const rgb_sc l = P.ldL(p);
+    P.stL(p, l.x + e.x, l.y + e.y, l.z + e.z);
+    return false;
+}
+// the first-hit record of a camera ray that misses: zeros and triangle 0xFFFFFFFF
+PT_DEV void aov_miss(float4 *__restrict__ aov, uint32_t i) {
+    st_stream(&aov[2 * (size_t)i], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    st_stream(&aov[2 * (size_t)i + 1], make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu)));
+}
+// the throughput a bounce > 0 starts with: (D.w, C.xy) of its state slot, D being loaded already (raygen stores none: a camera ray's is 1)
+PT_DEV v3 stored_throughput(const DevPaths &P, uint32_t q, float4 d4) {
+    const float2 c2 = ld_stream(&P.C[q]);
+    return mk3(d4.w, c2.x, c2.y);
+}
 
 // AOV: the instantiation launched for bounce 0 while first-hit planes are enabled (ptmi_set_aovs). It also writes the path's first-hit
 // record, 32 B at slot i (the bounce-0 queue is the identity: slot i is path i), from the HitInfo the bounce builds anyway:
@@ -388,7 +415,7 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                 uint32_t rng = __float_as_uint(o4.w);
                 const v3 ro = xyz(o4), rd = xyz(d4);
                 v3 thr = mk3(1.0f, 1.0f, 1.0f);                                      // pt.wgsl:639; raygen stores no throughput
-                if (sp.bounce != 0u) { const float2 c2 = ld_stream(&P.C[q]); thr = mk3(d4.w, c2.x, c2.y); }
+                if (sp.bounce != 0u) thr = stored_throughput(P, q, d4);
                 const HitInfo hit = make_hitinfo(sc, tabs, ro, rd, h2.x, __float_as_uint(h2.y));
                 if (AOV) {
                     st_stream(&aov[2 * (size_t)i], make_float4(hit.albedo.x, hit.albedo.y, hit.albedo.z, hit.t));
@@ -398,14 +425,7 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                     float att = rcp1(1.0f + hit.t * hit.t);
                     float k = hit.emissive_strength;
                     const v3 e = mk3(thr.x * hit.emission.x * k * att, thr.y * hit.emission.y * k * att, thr.z * hit.emission.z * k * att);
-                    if (sp.emit_records) {          // the path ends here: its last addition to L, made by `shadow` in bounce order
-                        rec_d.w = __uint_as_float(p);                                 // rec_o = (0, 0, 0, -2)
-                        rec_c = rgb_sc{e.x, e.y, e.z};
-                        shadow = true; emitted = true;
-                    } else {
-                        const rgb_sc l = P.ldL(p);
-                        P.stL(p, l.x + e.x, l.y + e.y, l.z + e.z);
-                    }
+                    if (terminal_add(P, sp.emit_records, p, e, rec_d, rec_c)) { shadow = true; emitted = true; }   // the path ends here
                 } else {
                     float inv_n = 0.0f;                                       // ENV: set where next-event estimation ran
                     const bool have_light = ENV ? sc.n_lights + sc.env.sampled > 0u : sc.n_lights > 0u;
@@ -462,15 +482,13 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                 }
             } else if (ENV) {                                                 // a miss sees the environment, the camera ray too
                 if (AOV) {
-                    st_stream(&aov[2 * (size_t)i], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-                    st_stream(&aov[2 * (size_t)i + 1], make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu)));
+                    aov_miss(aov, i);
                 }
                 const float4 d4 = ld_stream(&P.D[q]);
                 v3 thr = mk3(1.0f, 1.0f, 1.0f);
                 float w = 1.0f;
                 if (sp.bounce != 0u) {
-                    const float2 c2 = ld_stream(&P.C[q]);
-                    thr = mk3(d4.w, c2.x, c2.y);
+                    thr = stored_throughput(P, q, d4);
                     if (P.W) w = P.W[q];
                 }
                 const v3 le = env_lookup(sc.env, xyz(d4)).le;
@@ -479,18 +497,10 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                 // gives NaN or infinity and is added, as without a map
                 if ((e.x != 0.0f) | (e.y != 0.0f) | (e.z != 0.0f)) {
                     const uint32_t p = sp.pid ? sp.pid[q] : q;
-                    if (sp.emit_records) {
-                        rec_d.w = __uint_as_float(p);                                 // rec_o = (0, 0, 0, -2)
-                        rec_c = rgb_sc{e.x, e.y, e.z};
-                        shadow = true; emitted = true;
-                    } else {
-                        const rgb_sc l = P.ldL(p);
-                        P.stL(p, l.x + e.x, l.y + e.y, l.z + e.z);
-                    }
+                    if (terminal_add(P, sp.emit_records, p, e, rec_d, rec_c)) { shadow = true; emitted = true; }
                 }
             } else if (AOV) {                                                 // bounce 0 only: a camera ray that misses
-                st_stream(&aov[2 * (size_t)i], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-                st_stream(&aov[2 * (size_t)i + 1], make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu)));
+                aov_miss(aov, i);
             } else if (sp.bounce != 0u) {
                 // pt.wgsl:646-648: a miss adds `throughput * vec3f(0.0)` — nothing while the throughput is finite (x + +-0 = x, and
                 // the radiance is never -0), NaN in every component whose throughput is infinite or NaN (degenerate materials
@@ -500,14 +510,7 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                 if (!(__builtin_isfinite(tx) & __builtin_isfinite(c2.x) & __builtin_isfinite(c2.y))) {
                     const uint32_t p = sp.pid ? sp.pid[q] : q;
                     const v3 e = mk3(tx * 0.0f, c2.x * 0.0f, c2.y * 0.0f);
-                    if (sp.emit_records) {
-                        rec_d.w = __uint_as_float(p);                                 // rec_o = (0, 0, 0, -2)
-                        rec_c = rgb_sc{e.x, e.y, e.z};
-                        shadow = true; emitted = true;
-                    } else {
-                        const rgb_sc l = P.ldL(p);
-                        P.stL(p, l.x + e.x, l.y + e.y, l.z + e.z);
-                    }
+                    if (terminal_add(P, sp.emit_records, p, e, rec_d, rec_c)) { shadow = true; emitted = true; }
                 }
             }
         }
@@ -525,8 +528,8 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
             n_emitted += (uint32_t)__popcll(em);
         }
     }
-    if (n_skipped) atomicAdd(&sp.stats[1], (unsigned long long)n_skipped);
-    if (n_emitted) atomicAdd(&sp.stats[3], (unsigned long long)n_emitted);
+    if (n_skipped) atomicAdd(&sp.stats[kCtShadowRays], (unsigned long long)n_skipped);
+    if (n_emitted) atomicAdd(&sp.stats[kCtEmitRecords], (unsigned long long)n_emitted);
 }
 
 }  // namespace
