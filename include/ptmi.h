@@ -218,7 +218,8 @@ int ptmi_set_stream(ptmi_ctx *ctx, void *hip_stream);
  * 1 / (f + 1). A mean of unit normals is not of unit length: normalise it before use. A plane turned on after accumulation has
  * started (frame_index > 0) mixes with zeros until the next frame-0 dispatch, as the output buffer would. The radiance is the same
  * bits with the planes on or off. Only the rows this context renders (tile_y0 / tile_y1, tile_parts) are written; the others keep
- * their contents. The contexts of a ptmi_multi may enable planes, but nothing gathers them: each then holds only its own strips.
+ * their contents. Over a ptmi_multi, ptmi_multi_set_aovs turns the planes on on every device, each holds its own strips, and
+ * ptmi_multi_gather_planes / ptmi_multi_read_aov assemble them on device 0.
  * Cost while on: 32 bytes of device memory per path of a batch (the automatic batch size counts it) and one more pass per batch. */
 enum { PTMI_AOV_ALBEDO = 1u, PTMI_AOV_NORMAL = 2u, PTMI_AOV_ID = 4u };
 /* mask: any combination of PTMI_AOV_* (0 = none, the default; other bits PTMI_E_INVALID). A plane turned on is allocated and
@@ -254,8 +255,9 @@ void *ptmi_moments_device_ptr(ptmi_ctx *ctx);
  * (normal and depth) and, when demodulating, the ALBEDO plane. It needs the NORMAL and the moments planes on (else PTMI_E_STATE)
  * and writes a context-owned width*height float4 plane, (rgb, 0) in the output buffer's layout; the output buffer and the other
  * planes are not written. It is not on the parity path: its contract is a tolerance against tests/denoise_ref.py. The variance
- * estimate shrinks as frames accumulate, so the filter backs off as the image converges. Over a ptmi_multi, each context holds only
- * its own strips of the planes: nothing gathers them, and a context's denoise sees only its own rows. */
+ * estimate shrinks as frames accumulate, so the filter backs off as the image converges. Over a ptmi_multi, ptmi_multi_denoise first
+ * gathers the planes the filter reads onto device 0 and then runs it there on the whole frame (a context's own ptmi_denoise sees only
+ * the rows it holds). */
 typedef struct ptmi_denoise_params {
     uint32_t iterations;   /* a-trous passes, step 2^i pixels for pass i; 1..10; 0 -> 5 */
     uint32_t demodulate;   /* 0: on iff the ALBEDO plane is on; 1: never; 2: always (ALBEDO off -> PTMI_E_STATE) */
@@ -298,7 +300,8 @@ int ptmi_blit_denoised(ptmi_ctx *ctx, float *dst_rgba_f32, size_t n_floats, uint
  * fold keeps z true). A plain ptmi_dispatch after adaptive rounds folds every pixel with the camera's frame index as it always has,
  * whatever the pixels' own counts: that is the caller's business. Asynchronous, like ptmi_dispatch.
  * ptmi_stats after one call: paths grows by the samples actually traced (counted on the device, read where ptmi_get_stats
- * synchronises), frames by nothing, dispatches by one. ptmi_multi has no such call. */
+ * synchronises), frames by nothing, dispatches by one. ptmi_multi_dispatch_adaptive is the call over several devices: there the
+ * neighbours of rule 1 are those inside the image, whichever device holds their row. */
 typedef struct ptmi_adaptive_params {
     float    threshold;      /* relative standard error of the pixel's mean luminance; > 0 */
     float    floor;          /* luminance under which the error is taken relative to `floor`; 0 -> 1 (an absolute error below luminance 1) */
@@ -354,8 +357,8 @@ int ptmi_adaptive_status(ptmi_ctx *ctx, struct ptmi_adaptive_status *out);
  *        count = min(min over the valid taps of n_q, max_history) with min(a, b) = a < b ? a : b (an integer, as its inputs are).
  * After the call the planes are what a render with per-pixel counts leaves. Caveat: with from == to and max_history below a pixel's
  * count, the pixel traces seeds again that it has already used (frames count .. are those of its earlier samples): reprojection is
- * for a camera that moved. There is no ptmi_multi counterpart: each context of a ptmi_multi holds only its own strips, and a
- * reprojected sample would have to come from another device's. */
+ * for a camera that moved. There is no ptmi_multi counterpart: each context of a ptmi_multi holds only its own strips, a reprojected
+ * sample would have to come from another device's, and the planes gather of ptmi_multi assembles frames on device 0 only. */
 typedef struct ptmi_reproject_params {
     uint32_t max_history;      /* a carried count is capped here; 0 -> 32; <= 2^24 */
     float    depth_tolerance;  /* relative: a tap is rejected when |t_tap - dist| > depth_tolerance * dist; 0 -> 0.02 */
@@ -441,6 +444,11 @@ enum {
     PTMI_MULTI_LOOPBACK = 1u    /* device-to-device copies in place of the collective: lets ONE device stand in for several (the same
                                    ordinal may then be listed more than once) — for tests of the packing on a one-GPU box; RCCL is not loaded */
 };
+/* ptmi_multi_gather_planes: with the PTMI_AOV_* bits, what to assemble on device 0 */
+enum {
+    PTMI_MULTI_PLANE_MOMENTS = 0x100u,   /* the sample-moments plane */
+    PTMI_MULTI_PLANE_OUTPUT = 0x200u     /* the output buffer (what ptmi_multi_gather assembles) */
+};
 /* ordinals: n_devices HIP device ordinals (NULL = 0 .. n_devices-1); the first one is the root that ends up with the frame. */
 int ptmi_multi_create(int n_devices, const int *ordinals, uint32_t flags, ptmi_multi **out);
 int ptmi_multi_destroy(ptmi_multi *m);
@@ -483,7 +491,44 @@ int ptmi_multi_get_stats(ptmi_multi *m, ptmi_stats *out);
 int ptmi_multi_reset_stats(ptmi_multi *m);
 /* time of the last ptmi_multi_gather on device 0's stream — from the moment every device has rendered its rows: pack + collective +
  * unpack, not the wait for the slowest device — in ms (-1 before the first; synchronises) */
-int ptmi_multi_gather_ms(ptmi_multi *m, double *ms);
+int ptmi_multi_gather_ms(ptmi_multi *m, double *ms);          /* ... or ptmi_multi_gather_planes, whichever ran last */
+
+/* ---- first-hit planes, moments, adaptive rounds and the denoiser over several devices ---------------------------------------------
+ * ptmi_set_aovs / ptmi_set_moments on every device. The argument is checked once, before any device changes; a device that fails
+ * leaves the devices already changed back at the earlier mask (the contents of a plane that had been turned off are gone). */
+int ptmi_multi_set_aovs(ptmi_multi *m, uint32_t mask);
+int ptmi_multi_get_aovs(const ptmi_multi *m, uint32_t *mask);
+int ptmi_multi_set_moments(ptmi_multi *m, uint32_t on);
+int ptmi_multi_get_moments(const ptmi_multi *m, uint32_t *on);
+/* Assembles the named planes in device 0's own planes, ordered after every device's work so far. Asynchronous, like ptmi_multi_gather.
+ * planes: any combination of PTMI_AOV_*, PTMI_MULTI_PLANE_MOMENTS and PTMI_MULTI_PLANE_OUTPUT. An unknown bit: PTMI_E_INVALID; a bit
+ * of a plane that is off: PTMI_E_STATE; 0 does nothing. ONE pass whatever the set: one pack kernel per device writes its rows of every
+ * named plane into one contiguous share (plane after plane, rows_max x width entries each, 16 bytes an entry, 8 for PTMI_AOV_ID; every
+ * device sends the largest share's size, the padding is never unpacked), one grouped ncclGather (loopback: one copy per device) moves
+ * the shares, one unpack kernel on device 0 scatters them by row. Device 0's rows are in place already; rows of planes that are not
+ * named are not touched. The buffers are sized for the planes that are on and remade when that set, the size or the strip height
+ * changes: with everything on 72 bytes per pixel arrive on device 0.
+ * STATUS: as for ptmi_multi_gather: N = 1 through RCCL and N = 2 .. 8 in loopback are tested bit for bit; the N > 1 RCCL leg of this
+ * gather HAS NEVER RUN. */
+int ptmi_multi_gather_planes(ptmi_multi *m, uint32_t planes);
+/* gather the plane if device 0 does not hold it whole + synchronise + ptmi_read_aov / ptmi_read_moments of device 0's plane */
+int ptmi_multi_read_aov(ptmi_multi *m, uint32_t which, void *dst, size_t n_bytes);
+int ptmi_multi_read_moments(ptmi_multi *m, float *dst, size_t n_floats);
+/* ptmi_dispatch_adaptive over every device's strips: afterwards every plane of every pixel holds, bit for bit, what
+ * ptmi_dispatch_adaptive on ONE device with the same parameters leaves there (a pixel's frames are seeded per (x, y, frame) and folded
+ * per pixel: the devices only have to take the same selection). Validation and error codes are ptmi_dispatch_adaptive's, checked on
+ * every device before anything is enqueued. neighbourhood = 0: every device runs all rounds on its own rows. neighbourhood = 1: per
+ * round, without a host synchronisation, every device writes the NOISY flag of each pixel of its rows (one byte), the flags go to every
+ * device (ncclAllGather; loopback: copies ordered by events), and every device selects over its own rows from the whole-frame flags.
+ * Asynchronous. STATUS: N = 1 through RCCL and loopback are tested; the N > 1 ncclAllGather HAS NEVER RUN. */
+int ptmi_multi_dispatch_adaptive(ptmi_multi *m, const ptmi_camera *camera, const ptmi_adaptive_params *params, uint32_t rounds);
+/* active and samples summed over the devices, min_count / max_count over the devices that have rows, rounds device 0's. Synchronises. */
+int ptmi_multi_adaptive_status(ptmi_multi *m, struct ptmi_adaptive_status *out);
+/* Gathers what device 0 does not hold whole of the output buffer, NORMAL, the moments plane and (when demodulating) ALBEDO, then
+ * ptmi_denoise / ptmi_blit_denoised on device 0's context: the single-device planes and kernels, hence its result bit for bit.
+ * The NORMAL or the moments plane off: PTMI_E_STATE; otherwise ptmi_denoise's errors. */
+int ptmi_multi_denoise(ptmi_multi *m, const ptmi_denoise_params *params, float *dst_rgba, size_t n_floats);
+int ptmi_multi_blit_denoised(ptmi_multi *m, float *dst_rgba_f32, size_t n_floats, uint8_t *dst_rgba8, size_t n_bytes);
 
 /* ---- statistics ----------------------------------------------------------- */
 int ptmi_get_stats(ptmi_ctx *ctx, ptmi_stats *out);           /* synchronises */

@@ -105,7 +105,10 @@ struct Timed {
 // ptmi_dispatch (ap NULL: n_frames frames of every pixel of the band, from cam->frame_index) and ptmi_dispatch_adaptive (ap: `rounds`
 // rounds of ap->step frames for the listed pixels, each from its own count). Both run the same bounce loop per batch; they differ in
 // the raygen in front of it and the folds behind it.
-int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_adaptive_params *ap, uint32_t rounds) {
+// map (with ap; ptmi_multi_dispatch_adaptive): the round selects from the whole-frame flag map and never restarts (pt_adaptive_flags
+// has); count_call = false: a further round of one call, which ptmi_stats.dispatches has already counted.
+int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_adaptive_params *ap, uint32_t rounds,
+             const DevFlagMap *map = nullptr, bool count_call = true) {
     int rc = check_ready(c, true);
     if (rc) return rc;
     if (!cam) return fail(c, PTMI_E_INVALID, "camera is NULL");
@@ -189,7 +192,7 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         float4 *const mom = plane_as<float4>(c, kMoments);
         unsigned long long *const ct = c->d_counters;
         uint32_t *const qlen = &c->d_control[kCwQueue], *const slen = &c->d_control[kCwShadow];    // queue lengths by bounce; shadow, by parity
-        if (ap && cam->frame_index == 0u) { pt_launch_adaptive_restart(ms, blocks, band, mom); c->ad_rounds = 0; }
+        if (ap && !map && cam->frame_index == 0u) { pt_launch_adaptive_restart(ms, blocks, band, mom); c->ad_rounds = 0; }
         // a batch: fb frames of every pixel from frame0 on, or (ap) of every listed pixel from its own count on
         auto batch = [&](uint32_t frame0, uint32_t fb) -> int {
             const DevPixels px = ap ? DevPixels{band, 0u, c->ad.list, &c->d_control[kCwAdActive], mom, &ct[kCtAdTraced]}
@@ -242,7 +245,8 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         };
         if (ap) {
             for (uint32_t r = 0; r < rounds; r++) {
-                pt_launch_adaptive_list(ms, blocks, band, *ap, mom, c->ad);
+                if (map) pt_launch_adaptive_list_map(ms, blocks, band, *ap, mom, *map, c->ad);
+                else pt_launch_adaptive_list(ms, blocks, band, *ap, mom, c->ad);
                 for (uint32_t f0 = 0; f0 < n_frames; f0 += F)
                     if ((rc = batch(0u, std::min(F, n_frames - f0)))) return rc;
             }
@@ -260,17 +264,13 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         if (c->in_flight.size() > kMaxDispatchesInFlight) HIP_TRY(c, throttle(c, kMaxDispatchesInFlight));
     }
     if (!ap) { c->st.paths += npix * n_frames; c->st.frames += n_frames; }      // adaptive: counted on the device (kCtAdTraced)
-    c->st.dispatches += 1;
+    if (count_call) c->st.dispatches += 1;
     return PTMI_OK;
 }
 
 }  // namespace
 
-extern "C" {
-
-int ptmi_dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames) { return dispatch(c, cam, n_frames, nullptr, 0); }
-
-int ptmi_dispatch_adaptive(ptmi_ctx *c, const ptmi_camera *cam, const ptmi_adaptive_params *params, uint32_t rounds) {
+int pt_adaptive_check(ptmi_ctx *c, const ptmi_camera *cam, const ptmi_adaptive_params *params, ptmi_adaptive_params *out) {
     if (!c) return PTMI_E_INVALID;
     if (!params) return fail(c, PTMI_E_INVALID, "params is NULL");
     ptmi_adaptive_params ap = *params;
@@ -288,6 +288,41 @@ int ptmi_dispatch_adaptive(ptmi_ctx *c, const ptmi_camera *cam, const ptmi_adapt
     int rc = check_ready(c, true);
     if (rc) return rc;
     if (!c->moments_on || !c->plane[kMoments]) return fail(c, PTMI_E_STATE, "adaptive sampling needs the moments plane (ptmi_set_moments)");
+    if (!cam) return fail(c, PTMI_E_INVALID, "camera is NULL");
+    if (cam->width != c->W || cam->height != c->H)
+        return fail(c, PTMI_E_INVALID, "camera says %ux%u but the output buffer is %ux%u", cam->width, cam->height, c->W, c->H);
+    *out = ap;
+    return PTMI_OK;
+}
+
+int pt_adaptive_flags(ptmi_ctx *c, const ptmi_adaptive_params *ap, bool restart, uint8_t **share_out) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = make_planes(c, group_set(kByAdaptive), (size_t)c->W * c->H, c->plane);
+    if (rc) return rc;
+    *share_out = plane_as<uint8_t>(c, kAdFlags);
+    const DevBand band = pt_band_of(c->opt, c->W, c->H);
+    if (band.y0 >= band.y1 || band.rows == 0) return PTMI_OK;           // more parts than strips: no pixel of this context's
+    float4 *const mom = plane_as<float4>(c, kMoments);
+    if (restart) { pt_launch_adaptive_restart(c->stream, c->n_cu * 8, band, mom); c->ad_rounds = 0; }
+    pt_launch_adaptive_flags(c->stream, c->n_cu * 8, band, *ap, mom, *share_out);
+    HIP_TRY(c, hipGetLastError());
+    return PTMI_OK;
+}
+
+int pt_adaptive_round(ptmi_ctx *c, const ptmi_camera *cam, const ptmi_adaptive_params *ap, const uint8_t *map, uint32_t share_px,
+                      bool count_call) {
+    const DevFlagMap fm{map, share_px, c->W, std::max(1u, c->opt.tile_strip), std::max(1u, c->opt.tile_parts)};
+    return dispatch(c, cam, ap->step, ap, 1, &fm, count_call);
+}
+
+extern "C" {
+
+int ptmi_dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames) { return dispatch(c, cam, n_frames, nullptr, 0); }
+
+int ptmi_dispatch_adaptive(ptmi_ctx *c, const ptmi_camera *cam, const ptmi_adaptive_params *params, uint32_t rounds) {
+    ptmi_adaptive_params ap;
+    const int rc = pt_adaptive_check(c, cam, params, &ap);
+    if (rc) return rc;
     return dispatch(c, cam, ap.step, &ap, rounds);
 }
 

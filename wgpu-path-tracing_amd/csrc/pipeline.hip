@@ -371,8 +371,11 @@ __global__ __launch_bounds__(BLOCK) void k_ad_restart(DevBand band, float4 *__re
 }
 
 // control[kCwAdPixels] = band pixels (the `count` of the list build). Whole waves stay in the loop so that the ballot sees all 64 lanes.
-__global__ __launch_bounds__(BLOCK) void k_ad_select(DevBand band, ptmi_adaptive_params ap, const float4 *__restrict__ mom,
-                                                     uint64_t *__restrict__ ballot, uint32_t *__restrict__ control) {
+// MAP: the neighbourhood is looked up in the whole-frame flag map (rounds over several devices: a neighbour's row may be another
+// device's); else in the band's own moments, and only inside the band's rows.
+template <bool MAP>
+PT_DEV void ad_select(DevBand band, ptmi_adaptive_params ap, const float4 *__restrict__ mom, DevFlagMap fm,
+                      uint64_t *__restrict__ ballot, uint32_t *__restrict__ control) {
     const uint32_t npix = band.rows * band.width;
     if (blockIdx.x == 0 && threadIdx.x == 0) control[kCwAdPixels] = npix;
     const uint32_t padded = (npix + 63u) & ~63u;
@@ -381,15 +384,30 @@ __global__ __launch_bounds__(BLOCK) void k_ad_select(DevBand band, ptmi_adaptive
         if (pix < npix) {
             const uint32_t y = band.row_of(pix / band.width), x = pix % band.width;
             const float4 m = mom[(size_t)y * band.width + x];
-            active = ad_noisy(m, ap);
-            if (ap.neighbourhood && !active && m.z < (float)ap.max_frames) {
-                for (int dy = -1; dy <= 1 && !active; dy++) {
-                    const uint32_t ny = y + (uint32_t)dy;                   // y = 0, dy = -1 wraps and fails has_row
-                    if (!band.has_row(ny)) continue;
-                    for (int dx = -1; dx <= 1; dx++) {
-                        const uint32_t nx = x + (uint32_t)dx;
-                        if (nx >= band.width || (dx == 0 && dy == 0)) continue;
-                        if (ad_noisy(mom[(size_t)ny * band.width + nx], ap)) { active = true; break; }
+            if constexpr (MAP) {
+                // a flagged pixel has n < max_frames itself (ad_noisy), so "it or a neighbour is flagged, and its own n < max_frames"
+                if (m.z < (float)ap.max_frames) {
+                    for (int dy = -1; dy <= 1 && !active; dy++) {
+                        const uint32_t ny = y + (uint32_t)dy;               // y = 0, dy = -1 wraps and fails the test
+                        if (ny >= band.height) continue;
+                        for (int dx = -1; dx <= 1; dx++) {
+                            const uint32_t nx = x + (uint32_t)dx;
+                            if (nx >= band.width) continue;
+                            if (fm.at(nx, ny)) { active = true; break; }
+                        }
+                    }
+                }
+            } else {
+                active = ad_noisy(m, ap);
+                if (ap.neighbourhood && !active && m.z < (float)ap.max_frames) {
+                    for (int dy = -1; dy <= 1 && !active; dy++) {
+                        const uint32_t ny = y + (uint32_t)dy;                   // y = 0, dy = -1 wraps and fails has_row
+                        if (!band.has_row(ny)) continue;
+                        for (int dx = -1; dx <= 1; dx++) {
+                            const uint32_t nx = x + (uint32_t)dx;
+                            if (nx >= band.width || (dx == 0 && dy == 0)) continue;
+                            if (ad_noisy(mom[(size_t)ny * band.width + nx], ap)) { active = true; break; }
+                        }
                     }
                 }
             }
@@ -397,6 +415,21 @@ __global__ __launch_bounds__(BLOCK) void k_ad_select(DevBand band, ptmi_adaptive
         const uint64_t word = __ballot(active);
         if ((threadIdx.x & 63u) == 0u) ballot[pix >> 6] = word;
     }
+}
+__global__ __launch_bounds__(BLOCK) void k_ad_select(DevBand band, ptmi_adaptive_params ap, const float4 *__restrict__ mom,
+                                                     uint64_t *__restrict__ ballot, uint32_t *__restrict__ control) {
+    ad_select<false>(band, ap, mom, DevFlagMap{}, ballot, control);
+}
+__global__ __launch_bounds__(BLOCK) void k_ad_select_map(DevBand band, ptmi_adaptive_params ap, const float4 *__restrict__ mom,
+                                                         DevFlagMap fm, uint64_t *__restrict__ ballot, uint32_t *__restrict__ control) {
+    ad_select<true>(band, ap, mom, fm, ballot, control);
+}
+// the NOISY flag of every pixel of the band, by band-local pixel: a device's share of the whole-frame map (DevFlagMap)
+__global__ __launch_bounds__(BLOCK) void k_ad_flags(DevBand band, ptmi_adaptive_params ap, const float4 *__restrict__ mom,
+                                                    uint8_t *__restrict__ flags) {
+    const uint32_t npix = band.rows * band.width;
+    for (uint32_t pix = blockIdx.x * BLOCK + threadIdx.x; pix < npix; pix += gridDim.x * BLOCK)
+        flags[pix] = ad_noisy(mom[band.frame_pixel(pix)], ap) ? 1u : 0u;
 }
 
 __global__ __launch_bounds__(TILE_WORDS) void k_ad_tile_sums(const uint32_t *__restrict__ count_ptr, const uint64_t *__restrict__ ballot,
@@ -470,6 +503,62 @@ __global__ __launch_bounds__(BLOCK) void k_unpack_rows(DevBand band, const float
     const uint32_t n = band.rows * band.width;
     for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK)
         frame[band.frame_pixel(i)] = packed[i];
+}
+
+// ---- multi-GPU gather of several planes at once (ptmi_multi_gather_planes): the share layout is DevPlaneSet's. Every lane moves 16 bytes
+// per access: a float4 entry, or two 8-byte ids (an odd width leaves id pairs that straddle rows or sit at odd frame indices: those
+// frames move their ids 8 bytes at a time). No LDS: a copy has no reuse.
+__global__ __launch_bounds__(BLOCK) void k_pack_planes(DevBand band, DevPlaneSet set, float4 *__restrict__ share) {
+    const uint32_t n = band.rows * band.width, stride = gridDim.x * BLOCK;
+    for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride) {
+        const size_t fp = band.frame_pixel(i);
+        for (uint32_t p = 0; p < set.n4; p++) share[(size_t)p * set.share_px + i] = set.f4[p][fp];
+    }
+    if (!set.ids) return;
+    uint2 *const sid = reinterpret_cast<uint2 *>(share + (size_t)set.n4 * set.share_px);
+    if ((band.width & 1u) == 0u) {           // pairs (2k, 2k + 1) share a row and start at an even frame index: both sides 16-byte aligned
+        for (uint32_t k = blockIdx.x * BLOCK + threadIdx.x; k < n / 2u; k += stride)
+            reinterpret_cast<uint4 *>(sid)[k] = *reinterpret_cast<const uint4 *>(set.ids + band.frame_pixel(2u * k));
+    } else {
+        for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride) sid[i] = set.ids[band.frame_pixel(i)];
+    }
+}
+// one pass over the frame: pixel (x, y) of part r's rows comes from share r, local row (strip number / parts) * strip + y % strip
+__global__ __launch_bounds__(BLOCK) void k_unpack_planes(DevBand band, DevPlaneSet set, const float4 *__restrict__ recv, uint32_t share_f4,
+                                                         uint32_t skip) {
+    const uint32_t W = band.width, n = W * band.height, stride = gridDim.x * BLOCK;
+    // (row, x) -> the share's entry; part = 0xFFFFFFFF for a row that is skipped
+    auto source = [&](uint32_t y, uint32_t x, uint32_t &part) -> size_t {
+        const uint32_t s = y / band.strip;
+        part = band.parts > 1u ? s % band.parts : 0u;
+        const uint32_t l = band.parts > 1u ? (s / band.parts) * band.strip + y % band.strip : y;
+        return (size_t)l * W + x;
+    };
+    for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride) {
+        uint32_t part;
+        const size_t e = source(i / W, i % W, part);
+        if (part == skip) continue;
+        const float4 *const sh = recv + (size_t)part * share_f4;
+        for (uint32_t p = 0; p < set.n4; p++) set.f4[p][i] = sh[(size_t)p * set.share_px + e];
+    }
+    if (!set.ids) return;
+    if ((W & 1u) == 0u) {
+        for (uint32_t k = blockIdx.x * BLOCK + threadIdx.x; k < n / 2u; k += stride) {
+            uint32_t part;
+            const size_t e = source(2u * k / W, 2u * k % W, part);
+            if (part == skip) continue;
+            const uint2 *const sid = reinterpret_cast<const uint2 *>(recv + (size_t)part * share_f4 + (size_t)set.n4 * set.share_px);
+            *reinterpret_cast<uint4 *>(set.ids + 2u * k) = *reinterpret_cast<const uint4 *>(sid + e);
+        }
+    } else {
+        for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride) {
+            uint32_t part;
+            const size_t e = source(i / W, i % W, part);
+            if (part == skip) continue;
+            const uint2 *const sid = reinterpret_cast<const uint2 *>(recv + (size_t)part * share_f4 + (size_t)set.n4 * set.share_px);
+            set.ids[i] = sid[e];
+        }
+    }
 }
 
 // ---- presentation: src/shader/blit.wgsl:43-155 (exposure 2^1, AgX, look, EOTF, gamma 1/2.2) -------------
@@ -637,6 +726,17 @@ void pt_launch_adaptive_list(hipStream_t s, int blocks, DevBand band, const ptmi
     hipLaunchKernelGGL(k_ad_tile_sums, dim3(tiles), dim3(TILE_WORDS), 0, s, &ad.control[kCwAdPixels], ad.ballot, ad.tile_sums);
     hipLaunchKernelGGL(k_ad_scatter, dim3(tiles), dim3(TILE_WORDS), 0, s, &ad.control[kCwAdPixels], ad.ballot, ad.tile_sums, ad.list, &ad.control[kCwAdActive]);
 }
+void pt_launch_adaptive_flags(hipStream_t s, int blocks, DevBand band, const ptmi_adaptive_params &ap, const float4 *mom, uint8_t *flags) {
+    hipLaunchKernelGGL(k_ad_flags, dim3(blocks), dim3(BLOCK), 0, s, band, ap, mom, flags);
+}
+void pt_launch_adaptive_list_map(hipStream_t s, int blocks, DevBand band, const ptmi_adaptive_params &ap, const float4 *mom, DevFlagMap fm,
+                                 DevAdaptive ad) {
+    const uint32_t npix = band.rows * band.width;
+    const int tiles = (int)pt_adaptive_tiles(npix);
+    hipLaunchKernelGGL(k_ad_select_map, dim3(blocks), dim3(BLOCK), 0, s, band, ap, mom, fm, ad.ballot, ad.control);
+    hipLaunchKernelGGL(k_ad_tile_sums, dim3(tiles), dim3(TILE_WORDS), 0, s, &ad.control[kCwAdPixels], ad.ballot, ad.tile_sums);
+    hipLaunchKernelGGL(k_ad_scatter, dim3(tiles), dim3(TILE_WORDS), 0, s, &ad.control[kCwAdPixels], ad.ballot, ad.tile_sums, ad.list, &ad.control[kCwAdActive]);
+}
 void pt_launch_adaptive_status(hipStream_t s, int blocks, DevBand band, const float4 *mom, DevAdaptive ad) {
     hipLaunchKernelGGL(k_ad_status, dim3(blocks), dim3(BLOCK), 0, s, band, mom, ad.counters);
 }
@@ -647,6 +747,12 @@ void pt_launch_pack_rows(hipStream_t s, int blocks, DevBand band, const float4 *
 }
 void pt_launch_unpack_rows(hipStream_t s, int blocks, DevBand band, const float4 *packed, float4 *frame) {
     hipLaunchKernelGGL(k_unpack_rows, dim3(blocks), dim3(BLOCK), 0, s, band, packed, frame);
+}
+void pt_launch_pack_planes(hipStream_t s, int blocks, DevBand band, DevPlaneSet set, float4 *share) {
+    hipLaunchKernelGGL(k_pack_planes, dim3(blocks), dim3(BLOCK), 0, s, band, set, share);
+}
+void pt_launch_unpack_planes(hipStream_t s, int blocks, DevBand band, DevPlaneSet set, const float4 *recv, uint32_t skip) {
+    hipLaunchKernelGGL(k_unpack_planes, dim3(blocks), dim3(BLOCK), 0, s, band, set, recv, (uint32_t)(set.share_bytes() / 16u), skip);
 }
 void pt_launch_blit(hipStream_t s, int blocks, uint32_t W, uint32_t H, const float4 *color, float4 *out_f32,
                     uint32_t *out_rgba8) {

@@ -352,6 +352,23 @@ void pt_launch_adaptive_restart(hipStream_t s, int blocks, DevBand band, float4 
 void pt_launch_adaptive_list(hipStream_t s, int blocks, DevBand band, const ptmi_adaptive_params &ap, const float4 *mom, DevAdaptive ad);
 // (ray generation and the folds of a round: pt_launch_raygen / pt_launch_accumulate* with the list as their DevPixels)
 void pt_launch_adaptive_status(hipStream_t s, int blocks, DevBand band, const float4 *mom, DevAdaptive ad);
+// Adaptive rounds over several devices (ptmi_multi_dispatch_adaptive with neighbourhood = 1): the NOISY flag of every pixel of the frame,
+// one byte each, as the devices' shares one after the other. Share r holds the rows of part r (DevBand::row_of) of a frame dealt out
+// from row 0, local row l at share_px * r + l * width: a device writes its own share and receives the others'.
+struct DevFlagMap {
+    const uint8_t *map;
+    uint32_t share_px, width, strip, parts;
+    PT_HD uint8_t at(uint32_t x, uint32_t y) const {
+        if (parts <= 1u) return map[(size_t)y * width + x];
+        const uint32_t s = y / strip;
+        return map[(size_t)(s % parts) * share_px + (size_t)((s / parts) * strip + y % strip) * width + x];
+    }
+};
+// flags[band-local pixel] = the pixel is NOISY (the rule of k_ad_select, per pixel)
+void pt_launch_adaptive_flags(hipStream_t s, int blocks, DevBand band, const ptmi_adaptive_params &ap, const float4 *mom, uint8_t *flags);
+// pt_launch_adaptive_list with the neighbourhood looked up in the whole-frame map instead of the band's own moments
+void pt_launch_adaptive_list_map(hipStream_t s, int blocks, DevBand band, const ptmi_adaptive_params &ap, const float4 *mom, DevFlagMap fm,
+                                 DevAdaptive ad);
 // the denoiser (denoise.hip, ptmi_denoise): a prepass into guide / grad / cv, then `iterations` a-trous passes ping-ponging between
 // cv and tmp, the last remodulating into out. albedo NULL: no demodulation. cv is overwritten.
 struct DenoiseArgs {
@@ -380,6 +397,20 @@ void pt_launch_blit(hipStream_t s, int blocks, uint32_t W, uint32_t H, const flo
 // a device's rows of the frame <-> a contiguous buffer (ptmi_multi_gather)
 void pt_launch_pack_rows(hipStream_t s, int blocks, DevBand band, const float4 *frame, float4 *packed);
 void pt_launch_unpack_rows(hipStream_t s, int blocks, DevBand band, const float4 *packed, float4 *frame);
+// Several planes of a device's rows <-> one contiguous share (ptmi_multi_gather_planes). A share is laid out plane after plane, each
+// share_px = rows_max x width entries (the largest band's; a smaller band leaves padding that is never unpacked): first the n4 planes of
+// 16-byte entries in the order of f4[], then the 8-byte ids. A frame plane that is absent from the set is NULL / not counted.
+struct DevPlaneSet {
+    float4 *f4[4];
+    uint2 *ids;
+    uint32_t n4, share_px;
+    PT_HD size_t share_bytes() const { return ((size_t)share_px * (n4 * 16u + (ids ? 8u : 0u)) + 15u) & ~(size_t)15u; }
+};
+// band's rows of every plane of the set -> share
+void pt_launch_pack_planes(hipStream_t s, int blocks, DevBand band, DevPlaneSet set, float4 *share);
+// recv = `parts` shares, share_bytes apart, share r from the device of part r -> the frame planes of the set, every row of the frame
+// except those of part `skip` (0xFFFFFFFF: none). band: any device's (its part is not read).
+void pt_launch_unpack_planes(hipStream_t s, int blocks, DevBand band, DevPlaneSet set, const float4 *recv, uint32_t skip);
 // the rows DevBand describes for a context with these options on a width x height frame (rows = 0: none)
 struct ptmi_options;
 DevBand pt_band_of(const ptmi_options &opt, uint32_t width, uint32_t height);

@@ -82,7 +82,7 @@ const struct { const char *name; size_t (*bytes)(size_t px); bool zeroed; PlaneG
     {"denoiser ping", per_pixel<16>, false, kByDenoise}, {"denoiser pong", per_pixel<16>, false, kByDenoise},
     {"denoised", per_pixel<16>, false, kByDenoise},
     {"adaptive ballot", ballot_bytes, false, kByAdaptive}, {"adaptive list", per_pixel<4>, false, kByAdaptive},
-    {"adaptive tile sums", tile_sum_bytes, false, kByAdaptive},
+    {"adaptive tile sums", tile_sum_bytes, false, kByAdaptive}, {"adaptive flag share", per_pixel<1>, false, kByAdaptive},
     {"output history", per_pixel<PTMI_OUTPUT_STRIDE>, false, kByReproject}, {"moments history", per_pixel<16>, false, kByReproject},
     {"normal history", per_pixel<16>, false, kByReproject}, {"albedo history", per_pixel<16>, false, kByReproject},
     {"id history", per_pixel<8>, false, kByReproject},

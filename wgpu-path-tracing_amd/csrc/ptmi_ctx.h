@@ -29,6 +29,16 @@ hipStream_t pt_ctx_stream(ptmi_ctx *c);
 float4 *pt_ctx_output(ptmi_ctx *c);
 int pt_ctx_device(const ptmi_ctx *c);
 int pt_ctx_cus(const ptmi_ctx *c);
+// Adaptive rounds driven from outside, one at a time (ptmi_multi_dispatch_adaptive with neighbourhood = 1; dispatch.hip).
+// pt_adaptive_check: everything ptmi_dispatch_adaptive checks before it enqueues, with its error codes; *ap = the params with their defaults.
+int pt_adaptive_check(ptmi_ctx *c, const ptmi_camera *cam, const ptmi_adaptive_params *params, ptmi_adaptive_params *ap);
+// restart: the band's counts go back to 0 first. Then the NOISY flag of every pixel of c's rows is written to c's flag share
+// (*share_out: band-local pixel order, one byte each; DevFlagMap), on c's stream.
+int pt_adaptive_flags(ptmi_ctx *c, const ptmi_adaptive_params *ap, bool restart, uint8_t **share_out);
+// one round of ptmi_dispatch_adaptive with the selection taken from `map` (the shares of every device, device memory on c's device,
+// share_px entries each). count_call: this round is the first of its ptmi_multi_dispatch_adaptive call (ptmi_stats.dispatches).
+int pt_adaptive_round(ptmi_ctx *c, const ptmi_camera *cam, const ptmi_adaptive_params *ap, const uint8_t *map, uint32_t share_px,
+                      bool count_call);
 
 // What follows is shared by the six files above only: hidden, so that the library exports the C ABI and the pt_* names and no helper.
 // (A definition takes the visibility of the namespace block it stands in, so every block of pt_host is opened with PT_HOST.)
@@ -55,6 +65,7 @@ enum FramePlane {
     kDnGuide, kDnGrad, kDnA, kDnB, kDnOut,         // the denoiser's: guide (unit normal, depth), depth gradient, two ping-pong colour +
                                                    // variance planes, the result
     kAdBallot, kAdList, kAdTileSums,               // adaptive sampling: ballot words, pixel list, tile totals
+    kAdFlags,                                      // ... over several devices: this context's share of the whole-frame flag map
     kRpOut, kRpMoments, kRpNormal, kRpAlbedo, kRpId,   // reprojection: the snapshot of the output, moments and first-hit planes
     kBlitF32, kBlitU8,                             // canvas staging of ptmi_blit
     kFramePlanes

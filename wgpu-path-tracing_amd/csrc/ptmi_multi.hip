@@ -9,6 +9,11 @@
 //     ncclGather  (one group call, root = device 0; RCCL over xGMI)  on the same streams
 //     k_unpack_rows (device 0: buffer r -> the rows of device r)     on device 0's stream
 //
+// ptmi_multi_gather_planes does the same for any set of the first-hit planes, the moments plane and the output buffer in ONE pass:
+// k_pack_planes writes a device's rows of every named plane into one share (DevPlaneSet, pt_device.h), one grouped ncclGather moves the
+// shares, k_unpack_planes scatters all of them in one pass over the frame. Adaptive rounds with neighbourhood = 1 exchange one byte per
+// pixel per round (the NOISY flags) among all devices: ncclAllGather, or peer copies in loopback (ptmi_multi_dispatch_adaptive).
+//
 // Equal counts per rank are what ncclGather takes, so every device sends rows_max x width float4 (the last round of strips may
 // leave some devices a strip short; the padding is never unpacked). RCCL is loaded with dlopen when the first handle is
 // created: a process that renders on one device never maps it.
@@ -18,6 +23,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <functional>
 #include <thread>
 #include <cstdarg>
 #include <cstdio>
@@ -37,6 +43,7 @@ struct Rccl {
     ncclResult_t (*GroupStart)() = nullptr;
     ncclResult_t (*GroupEnd)() = nullptr;
     ncclResult_t (*Gather)(const void *, void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
+    ncclResult_t (*AllGather)(const void *, void *, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
     const char *(*GetErrorString)(ncclResult_t) = nullptr;
     std::string err;
     bool load() {
@@ -50,8 +57,9 @@ struct Rccl {
         GroupStart = reinterpret_cast<decltype(GroupStart)>(sym("ncclGroupStart"));
         GroupEnd = reinterpret_cast<decltype(GroupEnd)>(sym("ncclGroupEnd"));
         Gather = reinterpret_cast<decltype(Gather)>(sym("ncclGather"));
+        AllGather = reinterpret_cast<decltype(AllGather)>(sym("ncclAllGather"));
         GetErrorString = reinterpret_cast<decltype(GetErrorString)>(sym("ncclGetErrorString"));
-        if (!CommInitAll || !CommDestroy || !GroupStart || !GroupEnd || !Gather || !GetErrorString) {
+        if (!CommInitAll || !CommDestroy || !GroupStart || !GroupEnd || !Gather || !AllGather || !GetErrorString) {
             dlclose(lib); lib = nullptr; return false;
         }
         return true;
@@ -70,7 +78,15 @@ struct ptmi_multi {
     ptmi_options opt{};                                // as given by the caller (tile_strip 0 = automatic)
     uint32_t W = 0, H = 0, strip = kStripRows;
     size_t rows_max = 0;                               // rows of the largest share
-    size_t share_bytes = 0;                            // what every d_send[i] holds (d_recv: N of them): rows_max x W float4 when allocated
+    size_t share_bytes = 0;                            // what every d_send[i] holds (d_recv: N of them): rows_max x W entries of the output
+                                                       // and of every plane that is on (plane_set_of), when allocated
+    uint32_t aov_mask = 0;                             // ptmi_multi_set_aovs / _set_moments: what every device has on
+    bool moments_on = false;
+    std::vector<uint8_t *> d_flags;                    // per device: the whole-frame NOISY flags of an adaptive round, N shares of
+    size_t flags_bytes = 0;                            // rows_max x W bytes each (the device's own share is its context's kAdFlags plane)
+    std::vector<hipEvent_t> ev_flags;                  // loopback: device r's flag share is written / device r has copied every share
+    std::vector<hipEvent_t> ev_flags_copied;
+    std::vector<char> flags_copied_recorded;
     std::vector<float4 *> d_send;                      // per device: its packed rows
     float4 *d_recv = nullptr;                          // device 0: N shares
     std::vector<hipEvent_t> ev;                        // loopback: device r's share is packed
@@ -80,6 +96,7 @@ struct ptmi_multi {
     hipEvent_t g0 = nullptr, g1 = nullptr;             // around the last gather on device 0's stream
     bool gather_timed = false;
     uint64_t dispatched = 0, gathered = 0;             // dispatch calls so far / included in device 0's frame
+    uint64_t gathered_plane[4] = {0, 0, 0, 0};         // ... / included in device 0's ALBEDO, NORMAL, ID and moments plane (kind_of)
     mutable std::string err;
 };
 
@@ -125,14 +142,43 @@ ptmi_options options_of(const ptmi_multi *m, int i) {
     return o;
 }
 
+constexpr uint32_t kAovAll = PTMI_AOV_ALBEDO | PTMI_AOV_NORMAL | PTMI_AOV_ID;
+constexpr uint32_t kGatherAll = kAovAll | PTMI_MULTI_PLANE_MOMENTS | PTMI_MULTI_PLANE_OUTPUT;
+static_assert((kAovAll & (PTMI_MULTI_PLANE_MOMENTS | PTMI_MULTI_PLANE_OUTPUT)) == 0, "the gather bits extend the PTMI_AOV_* bits");
+// the planes whose staleness gathered_plane[] tracks (the output's is `gathered`)
+const struct { uint32_t bit; const char *name; } kPlaneKinds[4] = {
+    {PTMI_AOV_ALBEDO, "ALBEDO"}, {PTMI_AOV_NORMAL, "NORMAL"}, {PTMI_AOV_ID, "ID"}, {PTMI_MULTI_PLANE_MOMENTS, "moments"}};
+
+// what every device has: the output buffer, the AOV planes of the mask, the moments plane while on
+uint32_t planes_on(const ptmi_multi *m) { return PTMI_MULTI_PLANE_OUTPUT | m->aov_mask | (m->moments_on ? PTMI_MULTI_PLANE_MOMENTS : 0u); }
+// the share of device i for `planes` (all of them on): output, ALBEDO, NORMAL, moments, then the ids
+DevPlaneSet plane_set_of(const ptmi_multi *m, int i, uint32_t planes) {
+    ptmi_ctx *c = m->ctx[i];
+    DevPlaneSet set{};
+    if (planes & PTMI_MULTI_PLANE_OUTPUT) set.f4[set.n4++] = c->d_out;
+    if (planes & PTMI_AOV_ALBEDO) set.f4[set.n4++] = plane_as<float4>(c, kAovAlbedo);
+    if (planes & PTMI_AOV_NORMAL) set.f4[set.n4++] = plane_as<float4>(c, kAovNormal);
+    if (planes & PTMI_MULTI_PLANE_MOMENTS) set.f4[set.n4++] = plane_as<float4>(c, kMoments);
+    if (planes & PTMI_AOV_ID) set.ids = plane_as<uint2>(c, kAovId);
+    set.share_px = (uint32_t)(m->rows_max * m->W);
+    return set;
+}
+// bytes of a share of rows_max x W entries of `planes`, a multiple of 16 (DevPlaneSet::share_bytes, before there are pointers)
+size_t share_bytes_of(size_t rows_max, uint32_t W, uint32_t planes) {
+    const size_t per_px = 16u * (size_t)__builtin_popcount(planes & (kGatherAll & ~(uint32_t)PTMI_AOV_ID)) + ((planes & PTMI_AOV_ID) ? 8u : 0u);
+    return (rows_max * W * per_px + 15u) & ~(size_t)15u;
+}
+
 void free_buffers(ptmi_multi *m) {
     for (size_t i = 0; i < m->d_send.size(); i++)
         if (m->d_send[i]) { (void)hipSetDevice(m->dev[i]); (void)hipFree(m->d_send[i]); m->d_send[i] = nullptr; }
+    for (size_t i = 0; i < m->d_flags.size(); i++)
+        if (m->d_flags[i]) { (void)hipSetDevice(m->dev[i]); (void)hipFree(m->d_flags[i]); m->d_flags[i] = nullptr; }
     if (m->d_recv) { (void)hipSetDevice(m->dev[0]); (void)hipFree(m->d_recv); m->d_recv = nullptr; }
-    m->rows_max = 0; m->share_bytes = 0;
+    m->rows_max = 0; m->share_bytes = 0; m->flags_bytes = 0;
 }
 
-// options of every context + the gather's buffers for the current size and strip height
+// options of every context + the gathers' buffers for the current size, strip height and set of planes that are on
 int configure(ptmi_multi *m) {
     const int n = (int)m->ctx.size();
     m->strip = m->opt.tile_strip ? m->opt.tile_strip : auto_strip(m->H ? m->H : 1, (uint32_t)n);
@@ -141,15 +187,19 @@ int configure(ptmi_multi *m) {
         int rc = ptmi_set_options(m->ctx[i], &o);
         if (rc) return cfail(m, i, rc, "ptmi_set_options");
     }
-    if (m->W == 0 || n == 1) return PTMI_OK;
+    if (m->W == 0) return PTMI_OK;
     size_t rows_max = 0;
     for (int i = 0; i < n; i++) rows_max = std::max<size_t>(rows_max, pt_band_of(options_of(m, i), m->W, m->H).rows);
-    // the buffers are sized in BYTES (rows_max x W float4): a resize that keeps the height but widens the frame needs new ones
-    const size_t share = rows_max * m->W * sizeof(float4);
-    if (rows_max == m->rows_max && share == m->share_bytes && m->d_recv) return PTMI_OK;
+    // the buffers are sized in BYTES (rows_max x W entries of every plane that is on): a resize that keeps the height but widens the
+    // frame needs new ones, and so does a plane turned on. One device without RCCL gathers nothing and has none.
+    const bool wanted = n > 1 || !m->comm.empty();
+    const size_t share = share_bytes_of(rows_max, m->W, planes_on(m));
+    if (rows_max == m->rows_max && share == m->share_bytes && (m->d_recv || !wanted)) return PTMI_OK;
     int rc = ptmi_multi_synchronize(m);
     if (rc) return rc;
     free_buffers(m);
+    m->rows_max = rows_max;
+    if (!wanted) { m->share_bytes = share; return PTMI_OK; }
     for (int i = 0; i < n; i++) {
         MHIP(m, hipSetDevice(m->dev[i]));
         MHIP(m, hipMalloc(&m->d_send[i], std::max<size_t>(share, 16)));
@@ -157,8 +207,92 @@ int configure(ptmi_multi *m) {
     }
     MHIP(m, hipSetDevice(m->dev[0]));
     MHIP(m, hipMalloc(&m->d_recv, std::max<size_t>(share * n, 16)));
-    m->rows_max = rows_max; m->share_bytes = share;
+    m->share_bytes = share;
     std::fill(m->copied_recorded.begin(), m->copied_recorded.end(), 0);
+    std::fill(m->flags_copied_recorded.begin(), m->flags_copied_recorded.end(), 0);
+    return PTMI_OK;
+}
+
+// every count back to 0 (the frame is the same on every device again, or fresh). A plane that device 0 does not hold whole stays stale.
+void reset_counts(ptmi_multi *m, bool fresh) {
+    for (uint64_t &g : m->gathered_plane) g = fresh || g == m->dispatched ? 0 : ~0ull;
+    m->dispatched = m->gathered = 0;
+}
+
+// pack -> collective -> unpack of `planes` (all on, not 0, buffers in place) onto device 0; the body of both gathers
+int gather_set(ptmi_multi *m, uint32_t planes) {
+    const int n = (int)m->ctx.size();
+    hipStream_t s0 = pt_ctx_stream(m->ctx[0]);
+    // the timed region (ptmi_multi_gather_ms) starts when EVERY device has rendered its rows: pack, gather, unpack — not the wait for
+    // the slowest device, which is the dispatch's time
+    for (int i = 1; i < n; i++) {
+        MHIP(m, hipSetDevice(m->dev[i]));
+        MHIP(m, hipEventRecord(m->ev_done[i], pt_ctx_stream(m->ctx[i])));
+        MHIP(m, hipSetDevice(m->dev[0]));
+        MHIP(m, hipStreamWaitEvent(s0, m->ev_done[i], 0));
+    }
+    MHIP(m, hipSetDevice(m->dev[0]));
+    MHIP(m, hipEventRecord(m->g0, s0));
+    const DevPlaneSet set0 = plane_set_of(m, 0, planes);
+    const size_t share = set0.share_bytes();              // of this gather: at most m->share_bytes, what the buffers hold per device
+    if (share > m->share_bytes) return mfail(m, PTMI_E_STATE, "a share of %zu bytes does not fit the %zu-byte buffers", share, m->share_bytes);
+    for (int i = 0; i < n; i++) {
+        const DevBand band = pt_band_of(options_of(m, i), m->W, m->H);
+        MHIP(m, hipSetDevice(m->dev[i]));
+        // loopback: the previous gather's copy out of d_send[i] (on device 0's stream) must be done before it is packed again
+        if (m->comm.empty() && i > 0 && m->copied_recorded[i]) MHIP(m, hipStreamWaitEvent(pt_ctx_stream(m->ctx[i]), m->ev_copied[i], 0));
+        // (loopback: device 0's share is never read)
+        if (band.rows && (i > 0 || !m->comm.empty()))
+            pt_launch_pack_planes(pt_ctx_stream(m->ctx[i]), pt_ctx_cus(m->ctx[i]) * 8, band, plane_set_of(m, i, planes), m->d_send[i]);
+    }
+    if (!m->comm.empty()) {
+        MNCCL(m, g_rccl.GroupStart());
+        for (int i = 0; i < n; i++) {
+            ncclResult_t r = g_rccl.Gather(m->d_send[i], i == 0 ? m->d_recv : nullptr, share / 4, ncclFloat, 0, m->comm[i], pt_ctx_stream(m->ctx[i]));
+            if (r != ncclSuccess) { (void)g_rccl.GroupEnd(); return mfail(m, PTMI_E_HIP, "ncclGather (device %d) failed: %s", i, g_rccl.GetErrorString(r)); }
+        }
+        MNCCL(m, g_rccl.GroupEnd());
+    } else {
+        // loopback: device r's share is copied into slot r of device 0's receive buffer once it is packed
+        for (int i = 1; i < n; i++) {
+            MHIP(m, hipSetDevice(m->dev[i]));
+            MHIP(m, hipEventRecord(m->ev[i], pt_ctx_stream(m->ctx[i])));
+            MHIP(m, hipSetDevice(m->dev[0]));
+            MHIP(m, hipStreamWaitEvent(s0, m->ev[i], 0));
+            MHIP(m, hipMemcpyPeerAsync(reinterpret_cast<char *>(m->d_recv) + (size_t)i * share, m->dev[0], m->d_send[i], m->dev[i], share, s0));
+            MHIP(m, hipEventRecord(m->ev_copied[i], s0));
+            m->copied_recorded[i] = 1;
+        }
+    }
+    MHIP(m, hipSetDevice(m->dev[0]));
+    // device 0's own rows are already in place (RCCL delivers a copy of them into slot 0; the single-device case unpacks that copy, so
+    // that the planes really went through the collective)
+    pt_launch_unpack_planes(s0, pt_ctx_cus(m->ctx[0]) * 8, pt_band_of(options_of(m, 0), m->W, m->H), set0, m->d_recv, n > 1 ? 0u : 0xFFFFFFFFu);
+    MHIP(m, hipEventRecord(m->g1, s0));
+    MHIP(m, hipGetLastError());
+    m->gather_timed = true;
+    if (planes & PTMI_MULTI_PLANE_OUTPUT) m->gathered = m->dispatched;
+    for (int k = 0; k < 4; k++) if (planes & kPlaneKinds[k].bit) m->gathered_plane[k] = m->dispatched;
+    return PTMI_OK;
+}
+
+// of `planes` (all on), those device 0 does not hold whole
+uint32_t stale_of(const ptmi_multi *m, uint32_t planes) {
+    uint32_t stale = (planes & PTMI_MULTI_PLANE_OUTPUT) && m->gathered != m->dispatched ? PTMI_MULTI_PLANE_OUTPUT : 0u;
+    for (int k = 0; k < 4; k++) if ((planes & kPlaneKinds[k].bit) && m->gathered_plane[k] != m->dispatched) stale |= kPlaneKinds[k].bit;
+    return stale;
+}
+
+// fn(i) for every device, each from a thread of its own for the length of the call (ptmi_multi_dispatch says why); the first failure
+int each_threaded(ptmi_multi *m, const char *what, const std::function<int(size_t)> &fn) {
+    const size_t n = m->ctx.size();
+    std::vector<int> rcs(n, PTMI_OK);
+    std::vector<std::thread> pool;
+    pool.reserve(n - 1);
+    for (size_t i = 1; i < n; i++) pool.emplace_back([&, i] { rcs[i] = fn(i); });
+    rcs[0] = fn(0);
+    for (std::thread &t : pool) t.join();
+    for (size_t i = 0; i < n; i++) if (rcs[i]) return cfail(m, (int)i, rcs[i], what);
     return PTMI_OK;
 }
 
@@ -193,7 +327,7 @@ int ptmi_multi_create(int n, const int *ordinals, uint32_t flags, ptmi_multi **o
         }
         m->ctx.push_back(c);
     }
-    m->d_send.assign(n, nullptr);
+    m->d_send.assign(n, nullptr); m->d_flags.assign(n, nullptr);
     ptmi_get_options(m->ctx[0], &m->opt);
     m->opt.tile_strip = 0;
     if (!m->loopback && n >= 1) {
@@ -211,9 +345,12 @@ int ptmi_multi_create(int n, const int *ordinals, uint32_t flags, ptmi_multi **o
     }
     bool ok = true;
     m->ev.assign(n, nullptr); m->ev_copied.assign(n, nullptr); m->ev_done.assign(n, nullptr); m->copied_recorded.assign(n, 0);
+    m->ev_flags.assign(n, nullptr); m->ev_flags_copied.assign(n, nullptr); m->flags_copied_recorded.assign(n, 0);
     for (int i = 0; i < n && ok; i++) {
         ok = hipSetDevice(m->dev[i]) == hipSuccess && hipEventCreateWithFlags(&m->ev[i], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&m->ev_done[i], hipEventDisableTiming) == hipSuccess;
+             hipEventCreateWithFlags(&m->ev_done[i], hipEventDisableTiming) == hipSuccess &&
+             hipEventCreateWithFlags(&m->ev_flags[i], hipEventDisableTiming) == hipSuccess &&
+             hipEventCreateWithFlags(&m->ev_flags_copied[i], hipEventDisableTiming) == hipSuccess;
         ok = ok && hipSetDevice(m->dev[0]) == hipSuccess && hipEventCreateWithFlags(&m->ev_copied[i], hipEventDisableTiming) == hipSuccess;
     }
     ok = ok && hipSetDevice(m->dev[0]) == hipSuccess && hipEventCreate(&m->g0) == hipSuccess && hipEventCreate(&m->g1) == hipSuccess;
@@ -231,6 +368,9 @@ int ptmi_multi_destroy(ptmi_multi *m) {
     free_buffers(m);
     for (size_t i = 0; i < m->ev.size(); i++) if (m->ev[i]) { (void)hipSetDevice(m->dev[i]); (void)hipEventDestroy(m->ev[i]); }
     for (size_t i = 0; i < m->ev_done.size(); i++) if (m->ev_done[i]) { (void)hipSetDevice(m->dev[i]); (void)hipEventDestroy(m->ev_done[i]); }
+    for (size_t i = 0; i < m->ev_flags.size(); i++) if (m->ev_flags[i]) { (void)hipSetDevice(m->dev[i]); (void)hipEventDestroy(m->ev_flags[i]); }
+    for (size_t i = 0; i < m->ev_flags_copied.size(); i++)
+        if (m->ev_flags_copied[i]) { (void)hipSetDevice(m->dev[i]); (void)hipEventDestroy(m->ev_flags_copied[i]); }
     for (size_t i = 0; i < m->ev_copied.size(); i++) if (m->ev_copied[i]) { (void)hipSetDevice(m->dev[0]); (void)hipEventDestroy(m->ev_copied[i]); }
     if (m->g0) (void)hipEventDestroy(m->g0);
     if (m->g1) (void)hipEventDestroy(m->g1);
@@ -287,7 +427,7 @@ int ptmi_multi_resize(ptmi_multi *m, uint32_t w, uint32_t h) {
     int rc = each_ctx(m, "ptmi_resize", ptmi_resize, w, h);
     if (rc) return rc;
     m->W = w; m->H = h;
-    m->dispatched = m->gathered = 0;
+    reset_counts(m, true);                  // every plane of every device is zero-filled
     return configure(m);
 }
 
@@ -339,19 +479,8 @@ int ptmi_multi_gather(ptmi_multi *m) {
     const int n = (int)m->ctx.size();
     if (n == 1 && m->comm.empty()) { m->gathered = m->dispatched; return PTMI_OK; }
     if (m->W == 0) return mfail(m, PTMI_E_STATE, "no output buffer (ptmi_multi_resize)");
-    if (n == 1) {
-        // one device through RCCL: the degenerate gather of its whole frame onto itself, then copied back — the frame must come
-        // out of the collective unchanged (the N = 1 test of the RCCL leg on a one-GPU box)
-        const size_t frame_bytes = (size_t)m->W * m->H * sizeof(float4);
-        if (!m->d_recv || m->rows_max != m->H || m->share_bytes != frame_bytes) {
-            int rc = ptmi_multi_synchronize(m); if (rc) return rc;
-            free_buffers(m);
-            MHIP(m, hipSetDevice(m->dev[0]));
-            MHIP(m, hipMalloc(&m->d_send[0], frame_bytes));
-            MHIP(m, hipMalloc(&m->d_recv, frame_bytes));
-            m->rows_max = m->H; m->share_bytes = frame_bytes;
-        }
-    }
+    // (one device through RCCL: the degenerate gather of its whole frame onto itself, then copied back — the frame must come out of
+    // the collective unchanged: the N = 1 test of the RCCL leg on a one-GPU box. configure has sized the buffers for rows_max = H.)
     const size_t share_f4 = m->rows_max * m->W;
     hipStream_t s0 = pt_ctx_stream(m->ctx[0]);
     // the timed region (ptmi_multi_gather_ms) starts when EVERY device has rendered its rows: pack, gather, unpack — not the wait for
@@ -434,7 +563,7 @@ int ptmi_multi_write_output(ptmi_multi *m, const float *src, size_t n_floats) {
     if (!m || !src) return PTMI_E_INVALID;
     int rc = each_ctx(m, "ptmi_write_output", ptmi_write_output, src, n_floats);
     if (rc) return rc;
-    m->dispatched = m->gathered = 0;          // every device holds the whole frame again: the rows may be dealt out anew
+    reset_counts(m, false);                   // every device holds the whole frame again: the rows may be dealt out anew
     return PTMI_OK;
 }
 
@@ -445,6 +574,192 @@ int ptmi_multi_blit(ptmi_multi *m, float *dst_f32, size_t n_floats, uint8_t *dst
     if (rc) return rc;
     rc = ptmi_blit(m->ctx[0], dst_f32, n_floats, dst_rgba8, n_bytes);
     return rc ? cfail(m, 0, rc, "ptmi_blit") : PTMI_OK;
+}
+
+/* ---- planes, moments, adaptive rounds and the denoiser over the devices ---- */
+
+int ptmi_multi_set_aovs(ptmi_multi *m, uint32_t mask) {
+    if (!m) return PTMI_E_INVALID;
+    if (mask & ~kAovAll) return mfail(m, PTMI_E_INVALID, "unknown AOV bits 0x%x", mask & ~kAovAll);     // once, before any device changes
+    for (size_t i = 0; i < m->ctx.size(); i++) {
+        const int rc = ptmi_set_aovs(m->ctx[i], mask);
+        if (rc) {
+            cfail(m, (int)i, rc, "ptmi_set_aovs");
+            for (size_t j = 0; j < i; j++) (void)ptmi_set_aovs(m->ctx[j], m->aov_mask);      // the devices already changed go back
+            return rc;
+        }
+    }
+    // a plane turned on is zero on every device, device 0's copy included: nothing to gather
+    for (int k = 0; k < 3; k++) if (mask & ~m->aov_mask & kPlaneKinds[k].bit) m->gathered_plane[k] = m->dispatched;
+    m->aov_mask = mask;
+    return configure(m);
+}
+int ptmi_multi_get_aovs(const ptmi_multi *m, uint32_t *mask) {
+    if (!m || !mask) return PTMI_E_INVALID;
+    *mask = m->aov_mask;
+    return PTMI_OK;
+}
+int ptmi_multi_set_moments(ptmi_multi *m, uint32_t on) {
+    if (!m) return PTMI_E_INVALID;
+    if (on > 1u) return mfail(m, PTMI_E_INVALID, "on = %u is not 0 or 1", on);
+    for (size_t i = 0; i < m->ctx.size(); i++) {
+        const int rc = ptmi_set_moments(m->ctx[i], on);
+        if (rc) {
+            cfail(m, (int)i, rc, "ptmi_set_moments");
+            for (size_t j = 0; j < i; j++) (void)ptmi_set_moments(m->ctx[j], m->moments_on ? 1u : 0u);
+            return rc;
+        }
+    }
+    if (on && !m->moments_on) m->gathered_plane[3] = m->dispatched;
+    m->moments_on = on != 0;
+    return configure(m);
+}
+int ptmi_multi_get_moments(const ptmi_multi *m, uint32_t *on) {
+    if (!m || !on) return PTMI_E_INVALID;
+    *on = m->moments_on ? 1u : 0u;
+    return PTMI_OK;
+}
+
+int ptmi_multi_gather_planes(ptmi_multi *m, uint32_t planes) {
+    if (!m) return PTMI_E_INVALID;
+    if (planes & ~kGatherAll) return mfail(m, PTMI_E_INVALID, "unknown plane bits 0x%x", planes & ~kGatherAll);
+    if (planes & ~planes_on(m)) return mfail(m, PTMI_E_STATE, "plane bits 0x%x name planes that are off", planes & ~planes_on(m));
+    if (planes == 0) return PTMI_OK;
+    if (m->W == 0) return mfail(m, PTMI_E_STATE, "no output buffer (ptmi_multi_resize)");
+    if (m->ctx.size() == 1 && m->comm.empty()) {          // one device, no collective: its planes are the frame's
+        if (planes & PTMI_MULTI_PLANE_OUTPUT) m->gathered = m->dispatched;
+        for (int k = 0; k < 4; k++) if (planes & kPlaneKinds[k].bit) m->gathered_plane[k] = m->dispatched;
+        return PTMI_OK;
+    }
+    return gather_set(m, planes);
+}
+
+int ptmi_multi_read_aov(ptmi_multi *m, uint32_t which, void *dst, size_t n_bytes) {
+    if (!m) return PTMI_E_INVALID;
+    // (a `which` that is not one plane, or one that is off, is ptmi_read_aov's to refuse: nothing is gathered for it)
+    const uint32_t stale = stale_of(m, which & m->aov_mask);
+    if (stale && !(which & (which - 1u)) && dst) { int rc = ptmi_multi_gather_planes(m, stale); if (rc) return rc; }
+    int rc = ptmi_multi_synchronize(m);
+    if (rc) return rc;
+    rc = ptmi_read_aov(m->ctx[0], which, dst, n_bytes);
+    return rc ? cfail(m, 0, rc, "ptmi_read_aov") : PTMI_OK;
+}
+
+int ptmi_multi_read_moments(ptmi_multi *m, float *dst, size_t n_floats) {
+    if (!m) return PTMI_E_INVALID;
+    if (m->moments_on && dst && stale_of(m, PTMI_MULTI_PLANE_MOMENTS)) { int rc = ptmi_multi_gather_planes(m, PTMI_MULTI_PLANE_MOMENTS); if (rc) return rc; }
+    int rc = ptmi_multi_synchronize(m);
+    if (rc) return rc;
+    rc = ptmi_read_moments(m->ctx[0], dst, n_floats);
+    return rc ? cfail(m, 0, rc, "ptmi_read_moments") : PTMI_OK;
+}
+
+int ptmi_multi_denoise(ptmi_multi *m, const ptmi_denoise_params *params, float *dst_rgba, size_t n_floats) {
+    if (!m) return PTMI_E_INVALID;
+    if (!(m->aov_mask & PTMI_AOV_NORMAL)) return mfail(m, PTMI_E_STATE, "the denoiser needs the NORMAL plane (ptmi_multi_set_aovs)");
+    if (!m->moments_on) return mfail(m, PTMI_E_STATE, "the denoiser needs the moments plane (ptmi_multi_set_moments)");
+    const uint32_t demodulate = params ? params->demodulate : 0u;
+    uint32_t need = PTMI_MULTI_PLANE_OUTPUT | PTMI_AOV_NORMAL | PTMI_MULTI_PLANE_MOMENTS;
+    if ((demodulate == 0u || demodulate == 2u) && (m->aov_mask & PTMI_AOV_ALBEDO)) need |= PTMI_AOV_ALBEDO;
+    if (m->W != 0) {                                      // (before ptmi_multi_resize: ptmi_denoise's PTMI_E_STATE)
+        const uint32_t stale = stale_of(m, need);
+        if (stale) { int rc = ptmi_multi_gather_planes(m, stale); if (rc) return rc; }
+    }
+    // on device 0's stream, behind the unpack: the filter sees the whole frame
+    const int rc = ptmi_denoise(m->ctx[0], params, dst_rgba, n_floats);
+    return rc ? cfail(m, 0, rc, "ptmi_denoise") : PTMI_OK;
+}
+
+int ptmi_multi_blit_denoised(ptmi_multi *m, float *dst_f32, size_t n_floats, uint8_t *dst_rgba8, size_t n_bytes) {
+    if (!m) return PTMI_E_INVALID;
+    const int rc = ptmi_blit_denoised(m->ctx[0], dst_f32, n_floats, dst_rgba8, n_bytes);
+    return rc ? cfail(m, 0, rc, "ptmi_blit_denoised") : PTMI_OK;
+}
+
+int ptmi_multi_dispatch_adaptive(ptmi_multi *m, const ptmi_camera *cam, const ptmi_adaptive_params *params, uint32_t rounds) {
+    if (!m) return PTMI_E_INVALID;
+    const int n = (int)m->ctx.size();
+    ptmi_adaptive_params ap{};
+    for (int i = 0; i < n; i++) {                         // checked once, on every device, before anything is enqueued
+        const int rc = pt_adaptive_check(m->ctx[i], cam, params, &ap);
+        if (rc) return cfail(m, i, rc, "ptmi_dispatch_adaptive");
+    }
+    if (rounds == 0) return PTMI_OK;
+    if (ap.neighbourhood == 0u || (n == 1 && m->comm.empty())) {
+        // selection is per pixel (or one device has the whole frame): every device runs all rounds on its own rows
+        const int rc = each_threaded(m, "ptmi_dispatch_adaptive", [&](size_t i) { return ptmi_dispatch_adaptive(m->ctx[i], cam, params, rounds); });
+        if (rc) return rc;
+        m->dispatched++;
+        return PTMI_OK;
+    }
+    // neighbourhood = 1: a pixel's neighbours may be another device's, so every round exchanges the NOISY flags of the whole frame
+    const size_t share_px = m->rows_max * m->W, map_bytes = share_px * (size_t)n;
+    if (m->flags_bytes != map_bytes) {
+        for (int i = 0; i < n; i++) {
+            MHIP(m, hipSetDevice(m->dev[i]));
+            if (m->d_flags[i]) { MHIP(m, hipStreamSynchronize(pt_ctx_stream(m->ctx[i]))); MHIP(m, hipFree(m->d_flags[i])); m->d_flags[i] = nullptr; }
+            MHIP(m, hipMalloc(&m->d_flags[i], std::max<size_t>(map_bytes, 16)));
+        }
+        m->flags_bytes = map_bytes;
+        std::fill(m->flags_copied_recorded.begin(), m->flags_copied_recorded.end(), 0);
+    }
+    std::vector<uint8_t *> share(n, nullptr);
+    for (uint32_t r = 0; r < rounds; r++) {
+        for (int i = 0; i < n; i++) {
+            MHIP(m, hipSetDevice(m->dev[i]));
+            // loopback: every device has copied share i of the round before out of the plane it is written to again
+            if (m->comm.empty())
+                for (int d = 0; d < n; d++)
+                    if (d != i && m->flags_copied_recorded[d]) MHIP(m, hipStreamWaitEvent(pt_ctx_stream(m->ctx[i]), m->ev_flags_copied[d], 0));
+            const int rc = pt_adaptive_flags(m->ctx[i], &ap, r == 0 && cam->frame_index == 0u, &share[i]);
+            if (rc) return cfail(m, i, rc, "ptmi_dispatch_adaptive (flags)");
+            if (m->comm.empty()) MHIP(m, hipEventRecord(m->ev_flags[i], pt_ctx_stream(m->ctx[i])));
+        }
+        if (!m->comm.empty()) {
+            MNCCL(m, g_rccl.GroupStart());
+            for (int i = 0; i < n; i++) {
+                ncclResult_t e = g_rccl.AllGather(share[i], m->d_flags[i], share_px, ncclUint8, m->comm[i], pt_ctx_stream(m->ctx[i]));
+                if (e != ncclSuccess) { (void)g_rccl.GroupEnd(); return mfail(m, PTMI_E_HIP, "ncclAllGather (device %d) failed: %s", i, g_rccl.GetErrorString(e)); }
+            }
+            MNCCL(m, g_rccl.GroupEnd());
+        } else {
+            for (int d = 0; d < n; d++) {
+                MHIP(m, hipSetDevice(m->dev[d]));
+                hipStream_t sd = pt_ctx_stream(m->ctx[d]);
+                for (int i = 0; i < n; i++) {
+                    if (i != d) MHIP(m, hipStreamWaitEvent(sd, m->ev_flags[i], 0));
+                    MHIP(m, hipMemcpyPeerAsync(m->d_flags[d] + (size_t)i * share_px, m->dev[d], share[i], m->dev[i], share_px, sd));
+                }
+                MHIP(m, hipEventRecord(m->ev_flags_copied[d], sd));
+                m->flags_copied_recorded[d] = 1;
+            }
+        }
+        const int rc = each_threaded(m, "ptmi_dispatch_adaptive (round)", [&](size_t i) {
+            return pt_adaptive_round(m->ctx[i], cam, &ap, m->d_flags[i], (uint32_t)share_px, r == 0);
+        });
+        if (rc) return rc;
+    }
+    m->dispatched++;
+    return PTMI_OK;
+}
+
+int ptmi_multi_adaptive_status(ptmi_multi *m, struct ptmi_adaptive_status *out) {
+    if (!m || !out) return PTMI_E_INVALID;
+    struct ptmi_adaptive_status sum{};
+    bool first = true;
+    for (size_t i = 0; i < m->ctx.size(); i++) {
+        struct ptmi_adaptive_status s;
+        const int rc = ptmi_adaptive_status(m->ctx[i], &s);
+        if (rc) return cfail(m, (int)i, rc, "ptmi_adaptive_status");
+        if (i == 0) sum.rounds = s.rounds;
+        sum.active += s.active; sum.samples += s.samples;
+        if (pt_band_of(options_of(m, (int)i), m->W, m->H).rows == 0) continue;       // a device without rows has no counts
+        sum.min_count = first ? s.min_count : std::min(sum.min_count, s.min_count);
+        sum.max_count = first ? s.max_count : std::max(sum.max_count, s.max_count);
+        first = false;
+    }
+    *out = sum;
+    return PTMI_OK;
 }
 
 int ptmi_multi_get_stats(ptmi_multi *m, ptmi_stats *out) {

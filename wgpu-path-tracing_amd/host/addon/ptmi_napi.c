@@ -283,6 +283,18 @@ static napi_value js_gather(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* gatherPlanes(h, bits): PTMI_AOV_* | PTMI_MULTI_PLANE_*; several devices assemble those planes on the first in one pass */
+static napi_value js_gather_planes(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    handle *h = get_handle(env, info, 2, argv);
+    if (!h) return NULL;
+    uint32_t planes = 0;
+    napi_get_value_uint32(env, argv[1], &planes);
+    int rc = h->kind == KIND_MULTI ? ptmi_multi_gather_planes(h->m, planes) : PTMI_OK;
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_multi_gather_planes");
+    return NULL;
+}
+
 static napi_value js_synchronize(napi_env env, napi_callback_info info) {
     napi_value argv[1];
     handle *h = get_handle(env, info, 1, argv);
@@ -325,12 +337,12 @@ static napi_value js_write_output(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
-/* get_handle for the AOV, moments and denoiser calls, which take one device's handle: nothing gathers the planes of several */
+/* get_handle for the reprojection calls, which take one device's handle: ptmi_multi has no counterpart (include/ptmi.h) */
 static handle *get_single_handle(napi_env env, napi_callback_info info, size_t want, napi_value *argv, const char *what) {
     handle *h = get_handle(env, info, want, argv);
     if (h && h->kind == KIND_MULTI) {
         char msg[128];
-        snprintf(msg, sizeof msg, "%s: AOV planes, moments and the denoiser are not supported with several devices", what);
+        snprintf(msg, sizeof msg, "%s: reprojection is not supported with several devices", what);
         napi_throw_error(env, NULL, msg);
         return NULL;
     }
@@ -340,26 +352,24 @@ static handle *get_single_handle(napi_env env, napi_callback_info info, size_t w
 /* setAovs(h, mask): PTMI_AOV_* bits */
 static napi_value js_set_aovs(napi_env env, napi_callback_info info) {
     napi_value argv[2];
-    handle *h = get_single_handle(env, info, 2, argv, "setAovs");
+    handle *h = get_handle(env, info, 2, argv);
     if (!h) return NULL;
     uint32_t mask = 0;
     napi_get_value_uint32(env, argv[1], &mask);
-    int rc = ptmi_set_aovs(h->ctx, mask);
-    if (rc) return throw_ptmi(env, h, rc, "ptmi_set_aovs");
+    CALL(env, h, set_aovs, mask);
     return NULL;
 }
 
 /* readAov(h, which, dst typed array of width*height*16 (or *8 for PTMI_AOV_ID) bytes) */
 static napi_value js_read_aov(napi_env env, napi_callback_info info) {
     napi_value argv[3];
-    handle *h = get_single_handle(env, info, 3, argv, "readAov");
+    handle *h = get_handle(env, info, 3, argv);
     if (!h) return NULL;
     uint32_t which = 0;
     napi_get_value_uint32(env, argv[1], &which);
     void *p; size_t n;
     if (!get_bytes(env, argv[2], &p, &n)) return NULL;
-    int rc = ptmi_read_aov(h->ctx, which, p, n);
-    if (rc) return throw_ptmi(env, h, rc, "ptmi_read_aov");
+    CALL(env, h, read_aov, which, p, n);
     return argv[2];
 }
 
@@ -396,7 +406,7 @@ static int check_canvas(napi_env env, handle *h, const char *what, const char *t
         return 0;
     }
     uint32_t w = 0, hh = 0;
-    int rc = ptmi_get_size(h->ctx, &w, &hh);
+    int rc = ptmi_get_size(h->kind == KIND_MULTI ? ptmi_multi_context(h->m, 0) : h->ctx, &w, &hh);     /* several devices: the first's size is the frame's */
     if (rc) { throw_ptmi(env, h, rc, "ptmi_get_size"); return 0; }
     if (n != (size_t)w * hh * 4 * elem_bytes) {
         char msg[160];
@@ -419,19 +429,18 @@ static float get_f32_prop(napi_env env, napi_value obj, const char *name, float 
 /* setMoments(h, on) */
 static napi_value js_set_moments(napi_env env, napi_callback_info info) {
     napi_value argv[2];
-    handle *h = get_single_handle(env, info, 2, argv, "setMoments");
+    handle *h = get_handle(env, info, 2, argv);
     if (!h) return NULL;
     bool on = false;
     napi_get_value_bool(env, argv[1], &on);
-    int rc = ptmi_set_moments(h->ctx, on ? 1u : 0u);
-    if (rc) return throw_ptmi(env, h, rc, "ptmi_set_moments");
+    CALL(env, h, set_moments, on ? 1u : 0u);
     return NULL;
 }
 
 /* denoise(h, {iterations, demodulate, phiColor, phiNormal, phiDepth} or null, Float32Array dst of width*height*4) */
 static napi_value js_denoise(napi_env env, napi_callback_info info) {
     napi_value argv[3];
-    handle *h = get_single_handle(env, info, 3, argv, "denoise");
+    handle *h = get_handle(env, info, 3, argv);
     if (!h) return NULL;
     ptmi_denoise_params prm;
     memset(&prm, 0, sizeof prm);
@@ -446,8 +455,7 @@ static napi_value js_denoise(napi_env env, napi_callback_info info) {
     void *p; size_t n;
     if (!get_bytes(env, argv[2], &p, &n)) return NULL;
     if (!check_canvas(env, h, "denoise", "Float32Array", 4, p, n)) return NULL;
-    int rc = ptmi_denoise(h->ctx, &prm, (float *)p, n / 4);
-    if (rc) return throw_ptmi(env, h, rc, "ptmi_denoise");
+    CALL(env, h, denoise, &prm, (float *)p, n / 4);
     return argv[2];
 }
 
@@ -456,7 +464,7 @@ static void set_num(napi_env env, napi_value obj, const char *k, double v);
 /* dispatchAdaptive(h, cameraBytes, {threshold, floor, minFrames, maxFrames, step, neighbourhood}, rounds): ptmi_dispatch_adaptive */
 static napi_value js_dispatch_adaptive(napi_env env, napi_callback_info info) {
     napi_value argv[4];
-    handle *h = get_single_handle(env, info, 4, argv, "dispatchAdaptive");
+    handle *h = get_handle(env, info, 4, argv);
     if (!h) return NULL;
     void *p; size_t n; uint32_t rounds = 1;
     if (!get_bytes(env, argv[1], &p, &n)) return NULL;
@@ -475,19 +483,17 @@ static napi_value js_dispatch_adaptive(napi_env env, napi_callback_info info) {
     napi_get_value_uint32(env, argv[3], &rounds);
     ptmi_camera cam;
     memcpy(&cam, p, sizeof cam);
-    int rc = ptmi_dispatch_adaptive(h->ctx, &cam, &prm, rounds);
-    if (rc) return throw_ptmi(env, h, rc, "ptmi_dispatch_adaptive");
+    CALL(env, h, dispatch_adaptive, &cam, &prm, rounds);
     return NULL;
 }
 
 /* adaptiveStatus(h) -> {active, samples, minCount, maxCount, rounds}; synchronises */
 static napi_value js_adaptive_status(napi_env env, napi_callback_info info) {
     napi_value argv[1];
-    handle *h = get_single_handle(env, info, 1, argv, "adaptiveStatus");
+    handle *h = get_handle(env, info, 1, argv);
     if (!h) return NULL;
     struct ptmi_adaptive_status s;
-    int rc = ptmi_adaptive_status(h->ctx, &s);
-    if (rc) return throw_ptmi(env, h, rc, "ptmi_adaptive_status");
+    CALL(env, h, adaptive_status, &s);
     napi_value o;
     NAPI_OK(env, napi_create_object(env, &o));
     set_num(env, o, "active", (double)s.active); set_num(env, o, "samples", (double)s.samples);
@@ -539,26 +545,24 @@ static napi_value js_reproject_status(napi_env env, napi_callback_info info) {
 /* readMoments(h, Float32Array dst of width*height*4): the sample-moments plane */
 static napi_value js_read_moments(napi_env env, napi_callback_info info) {
     napi_value argv[2];
-    handle *h = get_single_handle(env, info, 2, argv, "readMoments");
+    handle *h = get_handle(env, info, 2, argv);
     if (!h) return NULL;
     void *p; size_t n;
     if (!get_bytes(env, argv[1], &p, &n)) return NULL;
     if (!check_canvas(env, h, "readMoments", "Float32Array", 4, p, n)) return NULL;
-    int rc = ptmi_read_moments(h->ctx, (float *)p, n / 4);
-    if (rc) return throw_ptmi(env, h, rc, "ptmi_read_moments");
+    CALL(env, h, read_moments, (float *)p, n / 4);
     return argv[1];
 }
 
 /* blitDenoised(h, Uint8Array dstRgba8): blit() of the last denoise() result */
 static napi_value js_blit_denoised(napi_env env, napi_callback_info info) {
     napi_value argv[2];
-    handle *h = get_single_handle(env, info, 2, argv, "blitDenoised");
+    handle *h = get_handle(env, info, 2, argv);
     if (!h) return NULL;
     void *p; size_t n;
     if (!get_bytes(env, argv[1], &p, &n)) return NULL;
     if (!check_canvas(env, h, "blitDenoised", "Uint8Array", 1, p, n)) return NULL;
-    int rc = ptmi_blit_denoised(h->ctx, NULL, 0, (uint8_t *)p, n);
-    if (rc) return throw_ptmi(env, h, rc, "ptmi_blit_denoised");
+    CALL(env, h, blit_denoised, NULL, 0, (uint8_t *)p, n);
     return argv[1];
 }
 
@@ -671,7 +675,7 @@ static napi_value init(napi_env env, napi_value exports) {
     static const struct { const char *name; napi_callback fn; } fns[] = {
         {"abiVersion", js_abi_version}, {"create", js_create}, {"multiCreate", js_multi_create}, {"destroy", js_destroy},
         {"uploadScene", js_upload_scene}, {"uploadAtlas", js_upload_atlas}, {"uploadEnvironment", js_upload_environment}, {"resize", js_resize}, {"setOptions", js_set_options},
-        {"dispatch", js_dispatch}, {"gather", js_gather}, {"synchronize", js_synchronize}, {"throttle", js_throttle},
+        {"dispatch", js_dispatch}, {"gather", js_gather}, {"gatherPlanes", js_gather_planes}, {"synchronize", js_synchronize}, {"throttle", js_throttle},
         {"readOutput", js_read_output}, {"writeOutput", js_write_output}, {"setAovs", js_set_aovs}, {"readAov", js_read_aov},
         {"blit", js_blit}, {"getStats", js_get_stats}, {"resetStats", js_reset_stats},
         {"setMoments", js_set_moments}, {"denoise", js_denoise}, {"blitDenoised", js_blit_denoised},

@@ -70,7 +70,7 @@ export class Renderer {
   moveCamera(forward: number, right: number, up: number): void;
   rotateCamera(yaw: number, pitch: number): void;
   readOutput(): Float32Array;
-  /** first-hit planes (include/ptmi.h ptmi_set_aovs); throws with several devices */
+  /** first-hit planes (include/ptmi.h ptmi_set_aovs); with several devices each keeps its strips and readAov assembles the plane */
   setAovs(names: Array<'albedo' | 'normal' | 'id'>): void;
   /** width*height entries, index y*width+x: 'albedo' / 'normal' 4 floats each, 'id' 2 uint32 (triangle, material) */
   readAov(name: 'albedo' | 'normal'): Float32Array;
@@ -79,10 +79,12 @@ export class Renderer {
   pick(x: number, y: number): { triangle: number; material: number; depth: number | null } | null;
   /** blit pass (blit.wgsl): tone-mapped RGBA8 canvas, row 0 = top */
   blit(): Uint8Array;
-  /** the denoiser's planes (normal, albedo, sample moments) on or off together; an 'id' plane stays; throws with several devices */
+  /** the denoiser's planes (normal, albedo, sample moments) on or off together; an 'id' plane stays; with several devices
+   *  denoise() gathers the planes onto the first device and filters the whole frame there */
   setDenoise(on: boolean): void;
   /** adaptive sampling on (params) or off (null): the frame loop then issues adaptive rounds and stops re-arming when a round lists
-   *  no pixel; turns the sample-moments plane on; throws with several devices */
+   *  no pixel; turns the sample-moments plane on. With several devices the rounds select as one device would (include/ptmi.h
+   *  ptmi_multi_dispatch_adaptive) */
   setAdaptive(params: AdaptiveParams | null): void;
   /** `rounds` adaptive rounds now (frameIndex 0 restarts) */
   renderAdaptive(rounds?: number): void;

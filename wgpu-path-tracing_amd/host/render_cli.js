@@ -6,14 +6,17 @@
  *   node render_cli.js <scene.ptscene> <out.f32> [--width W --height H --frames N --bounces B --mis 0|1
  *                       --aperture A --focus F --batch K --png out.png --denoise
  *                       --adaptive THRESHOLD --max-frames N --rounds R
- *                       --env file.hdr --env-intensity X --env-rotation DEGREES --env-sample 0|1]
+ *                       --env file.hdr --env-intensity X --env-rotation DEGREES --env-sample 0|1
+ *                       --devices 0,1,... --loopback --aov albedo|normal|id --aov-out plane.bin]
  * --batch K traces K frames per dispatch instead of one. --denoise keeps the denoiser's planes and makes --png the tone-mapped
  * denoised image (include/ptmi.h ptmi_denoise, default parameters). --adaptive renders to a noise level instead of --frames
  * (include/ptmi.h ptmi_dispatch_adaptive): rounds until none lists a pixel, or --rounds R of them; the JSON line then also holds
  * adaptive: { samples, minCount, maxCount, rounds }. --env lights the scene with a Radiance .hdr environment map (hdr_decode.js;
  * include/ptmi.h ptmi_upload_environment): equirectangular, scaled by --env-intensity, turned by --env-rotation degrees about +Y;
  * --env-sample 1 only looks it up. Writes W*H*4 float32 (the output buffer, raw also with
- * --denoise) and prints one JSON line with the statistics.
+ * --denoise) and prints one JSON line with the statistics. --devices renders on several GPUs behind one Renderer (include/ptmi.h
+ * ptmi_multi_*; --loopback lets one ordinal be listed more than once, for a one-GPU box); --adaptive, --denoise and --aov work with
+ * it. --aov keeps that first-hit plane and --aov-out writes it raw (float32 x 4 per pixel, uint32 x 2 for id).
  */
 var fs = require('fs');
 var host = require('./renderer');
@@ -29,10 +32,23 @@ var W = arg('width', 256), H = arg('height', 256), frames = arg('frames', 16), b
 var denoise = process.argv.indexOf('--denoise') >= 0;
 var adaptive = process.argv.indexOf('--adaptive') >= 0 ? { threshold: arg('adaptive', 0), maxFrames: arg('max-frames', 0) } : null;
 
-var r = new host.Renderer({ width: W, height: H, options: { maxBounces: arg('bounces', 8), doMis: arg('mis', 1) } });
+function textArg(name) {
+  var i = process.argv.indexOf('--' + name);
+  return i >= 0 ? process.argv[i + 1] : null;
+}
+var devices = textArg('devices') ? textArg('devices').split(',').map(Number) : null;
+var aov = textArg('aov');
+
+var r = new host.Renderer({ width: W, height: H, devices: devices || undefined, loopback: process.argv.indexOf('--loopback') >= 0,
+                            options: { maxBounces: arg('bounces', 8), doMis: arg('mis', 1) } });
 r.camera.aperture = arg('aperture', r.camera.aperture);
 r.camera.focusDistance = arg('focus', r.camera.focusDistance);
 if (denoise) r.setDenoise(true);
+if (aov) {                                 // beside the denoiser's planes, when those are on
+  var names = denoise ? ['normal', 'albedo'] : [];
+  if (names.indexOf(aov) < 0) names.push(aov);
+  r.setAovs(names);
+}
 var envAt = process.argv.indexOf('--env');
 r.loadModel(scenePath).then(function () {
   if (envAt >= 0) {
@@ -53,6 +69,7 @@ r.loadModel(scenePath).then(function () {
   var out = r.readOutput();
   var ms = Date.now() - t0;
   fs.writeFileSync(outPath, Buffer.from(out.buffer));
+  if (aov && textArg('aov-out')) { var plane = r.readAov(aov); fs.writeFileSync(textArg('aov-out'), Buffer.from(plane.buffer)); }
   var pi = process.argv.indexOf('--png');
   if (pi >= 0) {
     var img;

@@ -247,14 +247,13 @@ Renderer.prototype.blit = function () {
 };
 
 /** First-hit planes (include/ptmi.h ptmi_set_aovs): names of the planes to keep from now on, any of 'albedo', 'normal', 'id';
- *  [] turns them all off. One device only: nothing gathers the planes of several. */
+ *  [] turns them all off. With several devices every device keeps its own strips and readAov assembles the plane on the first. */
 var AOVS = { albedo: 1, normal: 2, id: 4 };
 function aovBit(name) {
   if (!Object.prototype.hasOwnProperty.call(AOVS, name)) throw new Error('unknown AOV plane "' + name + '" (albedo, normal, id)');
   return AOVS[name];
 }
 Renderer.prototype.setAovs = function (names) {
-  if (this.multi) throw new Error('setAovs: AOV planes are not supported with several devices');
   var mask = 0;
   (names || []).forEach(function (n) { mask |= aovBit(n); });
   this.addon.setAovs(this.ctx, mask);
@@ -285,9 +284,8 @@ Renderer.prototype.pick = function (x, y) {
 
 /** The denoiser's inputs (include/ptmi.h ptmi_denoise): on turns the 'normal' and 'albedo' planes and the sample-moments plane on,
  *  off turns the three off; an 'id' plane that is on stays on. Like setAovs, planes turned on mid-accumulation mix with zeros
- *  until the next frame 0. One device only. */
+ *  until the next frame 0. With several devices denoise() first gathers the planes the filter reads onto the first device. */
 Renderer.prototype.setDenoise = function (on) {
-  if (this.multi) throw new Error('setDenoise: the denoiser is not supported with several devices');
   var mask = ((this.aovMask || 0) & 4) | (on ? 3 : 0) | (this.reproject ? 2 : 0);      // reprojection keeps the 'normal' plane it reads
   this.addon.setAovs(this.ctx, mask);
   this.aovMask = mask;
@@ -297,14 +295,12 @@ Renderer.prototype.setDenoise = function (on) {
 /** The denoised output buffer: width*height float4 (rgb, 0), row 0 = image bottom like readOutput. params (all optional, 0 = the
  *  default): {iterations, demodulate, phiColor, phiNormal, phiDepth}. Needs setDenoise(true). Synchronises. */
 Renderer.prototype.denoise = function (params) {
-  if (this.multi) throw new Error('denoise: the denoiser is not supported with several devices');
   var out = new Float32Array(this.width * this.height * 4);
   this.addon.denoise(this.ctx, params || null, out);
   return out;
 };
 /** blit() of the last denoise() result: tone-mapped 8-bit canvas, row 0 = top */
 Renderer.prototype.blitDenoised = function () {
-  if (this.multi) throw new Error('blitDenoised: the denoiser is not supported with several devices');
   var out = new Uint8Array(this.width * this.height * 4);
   this.addon.blitDenoised(this.ctx, out);
   return out;
@@ -314,7 +310,6 @@ Renderer.prototype.blitDenoised = function () {
  *  neighbourhood } (0 or absent: the default; threshold has none), or null to go back to uniform frames. Turns the sample-moments
  *  plane on. While set, the frame loop issues adaptive rounds and stops re-arming once a round lists no pixel. */
 Renderer.prototype.setAdaptive = function (params) {
-  if (this.multi) throw new Error('setAdaptive: adaptive sampling is not supported with several devices');
   if (params) {
     if (!(params.threshold > 0)) throw new RangeError('setAdaptive: threshold must be > 0');
     if (!this.denoiseOn && !this.adaptive) this.addon.setMoments(this.ctx, true);
@@ -355,7 +350,6 @@ Renderer.prototype.reprojectStatus = function () { return this.addon.reprojectSt
 Renderer.prototype.adaptiveStatus = function () { return this.addon.adaptiveStatus(this.ctx); };
 /** per-pixel sample counts (the moments plane's z): width*height floats, row 0 = image bottom like readOutput */
 Renderer.prototype.sampleCounts = function () {
-  if (this.multi) throw new Error('sampleCounts: the moments plane is not supported with several devices');
   var m = this.addon.readMoments(this.ctx, new Float32Array(this.width * this.height * 4));
   var out = new Float32Array(this.width * this.height);
   for (var i = 0; i < out.length; i++) out[i] = m[4 * i + 2];

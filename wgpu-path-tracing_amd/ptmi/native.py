@@ -36,8 +36,12 @@ EXPORTS = [
     "ptmi_reproject", "ptmi_reproject_status", "ptmi_debug_center_rays",
     "ptmi_upload_environment", "ptmi_set_environment", "ptmi_environment_status", "ptmi_multi_upload_environment",
     "ptmi_multi_set_environment", "ptmi_debug_env_lookup", "ptmi_debug_env_sample", "ptmi_debug_env_table",
+    "ptmi_multi_set_aovs", "ptmi_multi_get_aovs", "ptmi_multi_set_moments", "ptmi_multi_get_moments", "ptmi_multi_gather_planes",
+    "ptmi_multi_read_aov", "ptmi_multi_read_moments", "ptmi_multi_dispatch_adaptive", "ptmi_multi_adaptive_status",
+    "ptmi_multi_denoise", "ptmi_multi_blit_denoised",
 ]
 MULTI_LOOPBACK = 1
+MULTI_PLANE_MOMENTS, MULTI_PLANE_OUTPUT = 0x100, 0x200      # gather_planes: with the AOV_* bits
 # first-hit planes (include/ptmi.h ptmi_set_aovs): name -> (bit, numpy dtype, channels)
 AOV_ALBEDO, AOV_NORMAL, AOV_ID = 1, 2, 4
 AOVS = {"albedo": (AOV_ALBEDO, np.float32, 4), "normal": (AOV_NORMAL, np.float32, 4), "id": (AOV_ID, np.uint32, 2)}
@@ -141,6 +145,10 @@ _SHARED = {
     "get_stats": [ctypes.c_void_p],
     "upload_environment": [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p],
     "set_environment": [ctypes.c_void_p],
+    "set_aovs": [ctypes.c_uint32], "get_aovs": [ctypes.POINTER(ctypes.c_uint32)], "read_aov": [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t],
+    "set_moments": [ctypes.c_uint32], "get_moments": [ctypes.POINTER(ctypes.c_uint32)], "read_moments": [ctypes.c_void_p, ctypes.c_size_t],
+    "denoise": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t], "blit_denoised": [ctypes.c_void_p, ctypes.c_size_t] * 2,
+    "dispatch_adaptive": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32], "adaptive_status": [ctypes.c_void_p],
 }
 _lib = None
 
@@ -181,22 +189,13 @@ def load():
         L.ptmi_multi_context.argtypes = [vp, ctypes.c_int]
         L.ptmi_multi_gather.argtypes = [vp]
         L.ptmi_multi_gather_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
-        L.ptmi_set_aovs.argtypes = [vp, u32]
-        L.ptmi_get_aovs.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32)]
-        L.ptmi_read_aov.argtypes = [vp, u32, vp, sz]
+        L.ptmi_multi_gather_planes.argtypes = [vp, u32]
         L.ptmi_aov_device_ptr.restype = vp
         L.ptmi_aov_device_ptr.argtypes = [vp, u32]
-        L.ptmi_set_moments.argtypes = [vp, u32]
-        L.ptmi_get_moments.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32)]
-        L.ptmi_read_moments.argtypes = [vp, vp, sz]
         L.ptmi_moments_device_ptr.restype = vp
         L.ptmi_moments_device_ptr.argtypes = [vp]
-        L.ptmi_denoise.argtypes = [vp, vp, vp, sz]
         L.ptmi_denoised_device_ptr.restype = vp
         L.ptmi_denoised_device_ptr.argtypes = [vp]
-        L.ptmi_blit_denoised.argtypes = [vp, vp, sz, vp, sz]
-        L.ptmi_dispatch_adaptive.argtypes = [vp, vp, vp, u32]
-        L.ptmi_adaptive_status.argtypes = [vp, vp]
         L.ptmi_reproject.argtypes = [vp, vp, vp, vp]
         L.ptmi_reproject_status.argtypes = [vp, vp]
         L.ptmi_debug_center_rays.argtypes = [vp, vp, vp, vp, sz]
@@ -418,6 +417,70 @@ class _Handle:
     def reset_stats(self):
         self._ck(self._c.reset_stats(self.h))
 
+    # -- first-hit planes (include/ptmi.h ptmi_set_aovs) ----------------------------
+    def set_aovs(self, *planes):
+        """set_aovs('albedo', 'normal', 'id') or set_aovs(mask); set_aovs() turns every plane off"""
+        mask = 0
+        for p in planes:
+            mask |= int(p) if not isinstance(p, str) else _aov(p)[0]
+        self._ck(self._c.set_aovs(self.h, mask))
+
+    def aovs(self):
+        """the names of the planes that are on"""
+        m = ctypes.c_uint32(0)
+        self._ck(self._c.get_aovs(self.h, ctypes.byref(m)))
+        return tuple(n for n, (bit, _, _) in AOVS.items() if m.value & bit)
+
+    def read_aov(self, name):
+        """(H, W, 4) float32 for 'albedo' / 'normal', (H, W, 2) uint32 (triangle, material) for 'id'"""
+        bit, dt, ch = _aov(name)
+        out = np.empty((self.height, self.width, ch), dt)
+        self._ck(self._c.read_aov(self.h, bit, _p(out), out.nbytes))
+        return out
+
+    # -- sample moments and the denoiser (include/ptmi.h ptmi_set_moments, ptmi_denoise) ----------------------
+    def set_moments(self, on=True):
+        self._ck(self._c.set_moments(self.h, int(on)))
+
+    def moments(self):
+        """whether the sample-moments plane is on"""
+        m = ctypes.c_uint32(0)
+        self._ck(self._c.get_moments(self.h, ctypes.byref(m)))
+        return bool(m.value)
+
+    def read_moments(self):
+        """(H, W, 4) float32: mean luminance, mean squared luminance, frames folded, 0"""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._ck(self._c.read_moments(self.h, _p(out), out.size))
+        return out
+
+    def denoise(self, iterations=0, demodulate=0, phi_color=0.0, phi_normal=0.0, phi_depth=0.0, reserved=(0, 0, 0), dst=True):
+        """the denoised output buffer, (H, W, 4) float32 with w = 0; 0 picks a parameter's default (include/ptmi.h).
+        dst=False: only queue it on the context's stream (denoised_device_ptr, blit_denoised) and return None."""
+        prm = DenoiseParams(iterations, demodulate, phi_color, phi_normal, phi_depth, (ctypes.c_uint32 * 3)(*reserved))
+        out = np.empty((self.height, self.width, 4), np.float32) if dst else None
+        self._ck(self._c.denoise(self.h, ctypes.byref(prm), _p(out), 0 if out is None else out.size))
+        return out
+
+    def blit_denoised(self, want_f32=True, want_rgba8=True):
+        """blit() of the denoised plane: (canvas float RGBA or None, canvas uint8 RGBA or None), row 0 = top"""
+        f = np.empty((self.height, self.width, 4), np.float32) if want_f32 else None
+        b = np.empty((self.height, self.width, 4), np.uint8) if want_rgba8 else None
+        self._ck(self._c.blit_denoised(self.h, _p(f), 0 if f is None else f.size, _p(b), 0 if b is None else b.size))
+        return f, b
+
+    # -- adaptive sampling (include/ptmi.h ptmi_dispatch_adaptive) ---------------------------------------------
+
+    def _dispatch_adaptive(self, camera, rounds, threshold, floor, min_frames, max_frames, step, neighbourhood, reserved):
+        assert camera.dtype == layout.CAMERA
+        prm = AdaptiveParams(threshold, floor, min_frames, max_frames, step, neighbourhood, (ctypes.c_uint32 * 2)(*reserved))
+        self._ck(self._c.dispatch_adaptive(self.h, _p(camera), ctypes.byref(prm), rounds))
+
+    def adaptive_status(self):
+        st = AdaptiveStatus()
+        self._ck(self._c.adaptive_status(self.h, ctypes.byref(st)))
+        return st
+
 
 class Context(_Handle):
     """One device context = the reference Renderer's GPU resources (bind group 0)."""
@@ -443,80 +506,21 @@ class Context(_Handle):
         self._ck(self.L.ptmi_blit(self.h, _p(f), 0 if f is None else f.size, _p(b), 0 if b is None else b.size))
         return f, b
 
-    # -- first-hit planes (include/ptmi.h ptmi_set_aovs) ----------------------------
-    def set_aovs(self, *planes):
-        """set_aovs('albedo', 'normal', 'id') or set_aovs(mask); set_aovs() turns every plane off"""
-        mask = 0
-        for p in planes:
-            mask |= int(p) if not isinstance(p, str) else _aov(p)[0]
-        self._ck(self.L.ptmi_set_aovs(self.h, mask))
-
-    def aovs(self):
-        """the names of the planes that are on"""
-        m = ctypes.c_uint32(0)
-        self._ck(self.L.ptmi_get_aovs(self.h, ctypes.byref(m)))
-        return tuple(n for n, (bit, _, _) in AOVS.items() if m.value & bit)
-
-    def read_aov(self, name):
-        """(H, W, 4) float32 for 'albedo' / 'normal', (H, W, 2) uint32 (triangle, material) for 'id'"""
-        bit, dt, ch = _aov(name)
-        out = np.empty((self.height, self.width, ch), dt)
-        self._ck(self.L.ptmi_read_aov(self.h, bit, _p(out), out.nbytes))
-        return out
-
+    # -- device addresses of the planes, and adaptive rounds on this context ---------------------------------
     def aov_device_ptr(self, name):
         return self.L.ptmi_aov_device_ptr(self.h, _aov(name)[0])
-
-    # -- sample moments and the denoiser (include/ptmi.h ptmi_set_moments, ptmi_denoise) ----------------------
-    def set_moments(self, on=True):
-        self._ck(self.L.ptmi_set_moments(self.h, int(on)))
-
-    def moments(self):
-        """whether the sample-moments plane is on"""
-        m = ctypes.c_uint32(0)
-        self._ck(self.L.ptmi_get_moments(self.h, ctypes.byref(m)))
-        return bool(m.value)
-
-    def read_moments(self):
-        """(H, W, 4) float32: mean luminance, mean squared luminance, frames folded, 0"""
-        out = np.empty((self.height, self.width, 4), np.float32)
-        self._ck(self.L.ptmi_read_moments(self.h, _p(out), out.size))
-        return out
 
     def moments_device_ptr(self):
         return self.L.ptmi_moments_device_ptr(self.h)
 
-    def denoise(self, iterations=0, demodulate=0, phi_color=0.0, phi_normal=0.0, phi_depth=0.0, reserved=(0, 0, 0), dst=True):
-        """the denoised output buffer, (H, W, 4) float32 with w = 0; 0 picks a parameter's default (include/ptmi.h).
-        dst=False: only queue it on the context's stream (denoised_device_ptr, blit_denoised) and return None."""
-        prm = DenoiseParams(iterations, demodulate, phi_color, phi_normal, phi_depth, (ctypes.c_uint32 * 3)(*reserved))
-        out = np.empty((self.height, self.width, 4), np.float32) if dst else None
-        self._ck(self.L.ptmi_denoise(self.h, ctypes.byref(prm), _p(out), 0 if out is None else out.size))
-        return out
-
     def denoised_device_ptr(self):
         return self.L.ptmi_denoised_device_ptr(self.h)
 
-    def blit_denoised(self, want_f32=True, want_rgba8=True):
-        """blit() of the denoised plane: (canvas float RGBA or None, canvas uint8 RGBA or None), row 0 = top"""
-        f = np.empty((self.height, self.width, 4), np.float32) if want_f32 else None
-        b = np.empty((self.height, self.width, 4), np.uint8) if want_rgba8 else None
-        self._ck(self.L.ptmi_blit_denoised(self.h, _p(f), 0 if f is None else f.size, _p(b), 0 if b is None else b.size))
-        return f, b
-
-    # -- adaptive sampling (include/ptmi.h ptmi_dispatch_adaptive) ---------------------------------------------
     def dispatch_adaptive(self, camera, rounds=1, threshold=0.0, floor=0.0, min_frames=0, max_frames=0, step=0, neighbourhood=0,
                           reserved=(0, 0)):
         """`rounds` rounds of `step` further frames for the pixels the rule of include/ptmi.h selects; needs set_moments().
         camera frame_index 0 restarts, any other value continues from the per-pixel counts."""
-        assert camera.dtype == layout.CAMERA
-        prm = AdaptiveParams(threshold, floor, min_frames, max_frames, step, neighbourhood, (ctypes.c_uint32 * 2)(*reserved))
-        self._ck(self.L.ptmi_dispatch_adaptive(self.h, _p(camera), ctypes.byref(prm), rounds))
-
-    def adaptive_status(self):
-        st = AdaptiveStatus()
-        self._ck(self.L.ptmi_adaptive_status(self.h, ctypes.byref(st)))
-        return st
+        self._dispatch_adaptive(camera, rounds, threshold, floor, min_frames, max_frames, step, neighbourhood, reserved)
 
     # -- reprojection (include/ptmi.h ptmi_reproject) -----------------------------------------------------------
     def reproject(self, from_cam, to_cam, max_history=0, depth_tolerance=0.0, match_ids=0, reserved=(0, 0, 0, 0, 0)):
@@ -630,6 +634,19 @@ class MultiContext(_Handle):
 
     def gather(self):
         self._ck(self.L.ptmi_multi_gather(self.h))
+
+    def gather_planes(self, *planes):
+        """assembles the named planes on the first device in one pass: 'albedo', 'normal', 'id', 'moments', 'output', or bit masks"""
+        mask = 0
+        for p in planes:
+            mask |= int(p) if not isinstance(p, str) else {"moments": MULTI_PLANE_MOMENTS, "output": MULTI_PLANE_OUTPUT}.get(p) or _aov(p)[0]
+        self._ck(self.L.ptmi_multi_gather_planes(self.h, mask))
+
+    def dispatch_adaptive_rounds(self, camera, rounds=1, threshold=0.0, floor=0.0, min_frames=0, max_frames=0, step=0, neighbourhood=0,
+                                 reserved=(0, 0)):
+        """Context.dispatch_adaptive over every device's strips (ptmi_multi_dispatch_adaptive): the same arguments, the same planes
+        afterwards. With neighbourhood=1 the devices exchange their pixels' flags every round."""
+        self._dispatch_adaptive(camera, rounds, threshold, floor, min_frames, max_frames, step, neighbourhood, reserved)
 
     def blit(self):
         b = np.empty((self.height, self.width, 4), np.uint8)
