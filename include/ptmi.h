@@ -414,6 +414,50 @@ int ptmi_set_environment(ptmi_ctx *ctx, const ptmi_environment *params);
 struct ptmi_environment_status { uint32_t width, height, sampled, reserved; double weight_sum; };   /* 24 bytes */
 int ptmi_environment_status(ptmi_ctx *ctx, struct ptmi_environment_status *out);
 
+/* ---- a homogeneous participating medium: scattering fog inside a box --------------------------
+ * Without a medium light travels through vacuum and nothing changes: the kernels launched are the ones of before and every result
+ * keeps its bits. With one, there is ONE homogeneous medium per context inside an axis-aligned box: a scalar (grey) extinction
+ * sigma_t, which keeps distance sampling exact for all three channels, a single-scattering albedo per channel, and the
+ * Henyey-Greenstein phase function of asymmetry g. Per PATH SEGMENT, in the shade kernel, with the ray (o, d) of the path state (d is
+ * the unit direction it holds) and t_hit the hit distance, or +inf on a miss:
+ * 1. INTERVAL. Per axis k: inv = 1 / d_k, t1 = (min_k - o_k) inv, t2 = (max_k - o_k) inv; near = max_k min(t1, t2),
+ *    far = min_k max(t1, t2), a = max(near, 0), b = min(far, t_hit), with fmin / fmax semantics (a NaN from 0 * inf drops out). If NOT
+ *    b > a the segment is handled exactly as without a medium and draws nothing extra. (A box with min == max on an axis has no such
+ *    segment, but for a ray that lies in that plane with a direction component of exactly 0 across it: both of its NaNs drop out.)
+ * 2. FREE FLIGHT. One draw r, before any other draw of the segment: s = -ln(1 - r) / sigma_t. The path SCATTERS iff a + s < b, at
+ *    x = o + (a + s) d; otherwise the surface hit or the miss is handled as without a medium, the throughput unchanged (distance
+ *    sampling and the transmittance cancel).
+ * 3. AT A SCATTER the throughput is multiplied by the albedo; all zero, the path ends. Otherwise next-event estimation runs when
+ *    do_mis is on and there is a light or a sampled sky: sampleLight at x, with the phase value
+ *    p = (1 - g^2) / (4 pi (1 + g^2 - 2 g cos)^1.5), cos = dot(d, wi), where evalBSDF's value and pdf stand (f = (p, p, p), pdf = p),
+ *    the same powerHeuristic and `direct` arithmetic (the reference's pdf constants of punctual lights included), times Tr (below); the
+ *    record is an ordinary shadow record from x, a zero contribution is counted and not recorded. The bounce direction takes two
+ *    draws xi1, xi2: cos = 1 - 2 xi1 for |g| < 1e-3, else (1 + g^2 - ((1 - g^2) / (1 - g + 2 g xi1))^2) / (2 g), clamped to [-1, 1];
+ *    sin = sqrt(max(0, 1 - cos^2)); phi = 2 pi xi2 with the kernels' sin / cos; the frame about d is Duff et al. 2017:
+ *    sg = copysign(1, d.z), A = -1 / (sg + d.z), B = d.x d.y A, T = (1 + sg d.x^2 A, sg B, -sg d.x), U = (B, sg + d.y^2 A, -d.y); the
+ *    direction is sin cos(phi) T + sin sin(phi) U + cos d, normalised. Its density is its phase value: the throughput takes no further
+ *    factor. Roulette as at a surface; a scatter is one bounce and one segment. Under a sampled sky the bounce ray carries
+ *    W = powerHeuristic(1, p, 1, pdf_env(direction) / (n_lights + 1)) where next-event estimation ran, else 1.
+ * 4. TRANSMITTANCE of every next-event sample, those from surfaces too (the one change to the surface branch while a medium is in
+ *    place): Tr(o, wi, dist) = exp(-sigma_t max(0, min(far, dist) - max(near, 0))) with near / far of the ray (o, wi), far alone for
+ *    directional and sky samples; it multiplies the contribution before the "exactly zero" test.
+ * 5. UNCHANGED: the additions of emissive hits and misses; the first-hit planes, which record the camera ray's SURFACE hit whether or
+ *    not the path scattered in front of it (every plane has the same bits with and without a medium); the moments plane; the fold.
+ * ln, exp and the free-flight comparison use the device's logf / expf: they are outside the bit-exact arithmetic contract, like the
+ * sky lookup and ptmi_blit, and the CPU oracle does not model the medium. A ray that starts at a scatter point outside the scene's
+ * bounds takes the own-leaf kernels' re-trace over the tree as uploaded: correct, and slower. */
+typedef struct ptmi_medium {
+    float    sigma_t;                 /* extinction per unit length; finite, > 0 */
+    float    albedo[3];               /* each in [0, 1] */
+    float    g;                       /* |g| <= 0.99 */
+    float    box_min[3], box_max[3];  /* finite, min <= max per axis; an axis with min == max makes a medium no ray traverses */
+    uint32_t reserved[5];             /* must be 0 */
+} ptmi_medium;                        /* 64 bytes */
+/* medium NULL removes it. A bad field: PTMI_E_INVALID, and the medium in place stays. Takes effect at the next dispatch. Synchronises. */
+int ptmi_set_medium(ptmi_ctx *ctx, const ptmi_medium *medium);
+/* *present = 1 and *out = the medium as it was set, or *present = 0 and *out zeroed. Either pointer may be NULL. */
+int ptmi_get_medium(const ptmi_ctx *ctx, ptmi_medium *out, uint32_t *present);
+
 /* ---- presentation (the reference's blit pass, src/shader/blit.wgsl:43-155; renderer.ts:434-449) ---- */
 /* Tone-maps the output buffer (exposure 2^1, AgX, gamma 1/2.2) into a width*height canvas, row 0 = top.
  * dst_rgba_f32 (n_floats must be width*height*4, alpha 1) and/or dst_rgba8 (n_bytes must be width*height*4);
@@ -467,6 +511,8 @@ int ptmi_multi_resize(ptmi_multi *m, uint32_t width, uint32_t height);
 int ptmi_multi_upload_environment(ptmi_multi *m, const void *texels, uint32_t width, uint32_t height, int format,
                                   const ptmi_environment *params);
 int ptmi_multi_set_environment(ptmi_multi *m, const ptmi_environment *params);
+/* ptmi_set_medium on every device (replicated; checked once before any device changes) */
+int ptmi_multi_set_medium(ptmi_multi *m, const ptmi_medium *medium);
 /* Options for every device. tile_parts / tile_part are set by the library (device i renders the strips i, i + N, ...);
  * tile_strip = 0 picks the strip height: 4 rows, or the largest smaller height that makes the frame a whole number of rounds
  * (3840x2160 over 8 devices: 3), so that all devices get equal shares; tile_y0 / tile_y1 must be 0. */
@@ -588,6 +634,14 @@ int ptmi_debug_math(ptmi_ctx *ctx, int op, uint32_t n, const float *a, const flo
  * the map is not sampled) -> d3 the direction, out4 = (Le.rgb, density), texel[i] the texel picked. d3 / out4 / texel may be NULL. */
 int ptmi_debug_env_lookup(ptmi_ctx *ctx, uint32_t n, const float *d3, float *out4);
 int ptmi_debug_env_sample(ptmi_ctx *ctx, uint32_t n, const float *r4, float *d3, float *out4, uint32_t *texel);
+/* The medium (ptmi_set_medium), probed with the functions the renders run. Both synchronise; PTMI_E_STATE: no medium in place.
+ * step: one path segment on caller-supplied uniforms r3[3i .. 3i+2] = (r, xi1, xi2) in place of RNG draws, for the ray (o3, d3) and
+ * the hit distance t_hit[i] (+inf: a miss) -> scattered[i] 0 / 1, x3 the scatter point, dir3 the sampled direction,
+ * out4 = (a, b, s, phase density of dir). Without an interval s, x3, dir3 and the density are 0; without a scatter x3, dir3 and the
+ * density are 0. tr: tr[i] = Tr(o3, wi3, dist[i]) (dist < 0: directional). Output pointers may be NULL. */
+int ptmi_debug_medium_step(ptmi_ctx *ctx, uint32_t n, const float *o3, const float *d3, const float *t_hit, const float *r3,
+                           uint32_t *scattered, float *x3, float *dir3, float *out4);
+int ptmi_debug_medium_tr(ptmi_ctx *ctx, uint32_t n, const float *o3, const float *wi3, const float *dist, float *tr);
 /* Host-only (no context, no device): the tables ptmi_upload_environment would build for these texels. c_out: width*height floats
  * (c_t); prob_out / alias_out: width*height entries of the alias table; *weight_sum = sum(w). Each may be NULL. An all-black map gives
  * weight_sum 0, every c_t and prob 0 and alias[k] = k: such a map is never sampled. Errors as ptmi_upload_environment's, with the

@@ -34,6 +34,14 @@ struct DevEnv {
     float intensity, rotation;  // radiance scale; radians about +Y added to the azimuth
 };
 
+// The participating medium (ptmi_set_medium; pt_medium.h has the functions that read it). on 0: none in place.
+struct DevMedium {
+    float sigma_t, g;           // extinction per unit length; Henyey-Greenstein asymmetry
+    float albedo[3];            // single-scattering albedo per channel
+    float box_min[3], box_max[3];
+    uint32_t on;
+};
+
 struct DevScene;
 struct DevScene {
     const ptmi_triangle *tris;  uint32_t n_tris;
@@ -75,6 +83,7 @@ struct DevScene {
     const DevScene *self;       // this description in device memory (the own-leaf kernels read it from there, not from kernel arguments)
     const float4 *shade_tab;    // the shade tables (below): what `shade` stages into LDS
     DevEnv env;                 // the environment map behind every miss (tab NULL: none, a miss adds throughput * 0)
+    DevMedium med;              // the homogeneous medium inside a box (on 0: none, every segment travels through vacuum)
 };
 
 // ---- shade tables: the records `shade` reads per hit that are the same for the whole scene, in one blob built at upload ----

@@ -5,6 +5,7 @@
 //   dispatch.hip       the wavefront dispatch loop, adaptive sampling, reprojection, event timing
 //   debug_stages.hip   the per-stage debug entry points
 //   environment.hip    the environment map: its tables, upload and removal, its debug entry points
+//   medium.hip         the participating medium: its checks, installation and removal, its debug entry points
 #pragma once
 #include "ptmi.h"
 #include "pt_device.h"
@@ -25,6 +26,8 @@ void pt_free_prepared(PtPrepared *p);
 // bytes of a width x height atlas of `format` (ptmi_upload_atlas); PTMI_E_INVALID, with the reason in `why`, for an unknown
 // format or a size that does not fit in size_t
 int pt_atlas_bytes(uint32_t width, uint32_t height, int format, size_t *bytes, char *why, size_t why_len);
+// the field checks of ptmi_set_medium (medium.hip): PTMI_E_INVALID with the reason in err; m NULL (removal) is fine
+int pt_check_medium(const ptmi_medium *m, std::string &err);
 hipStream_t pt_ctx_stream(ptmi_ctx *c);
 float4 *pt_ctx_output(ptmi_ctx *c);
 int pt_ctx_device(const ptmi_ctx *c);
@@ -40,7 +43,7 @@ int pt_adaptive_flags(ptmi_ctx *c, const ptmi_adaptive_params *ap, bool restart,
 int pt_adaptive_round(ptmi_ctx *c, const ptmi_camera *cam, const ptmi_adaptive_params *ap, const uint8_t *map, uint32_t share_px,
                       bool count_call);
 
-// What follows is shared by the six files above only: hidden, so that the library exports the C ABI and the pt_* names and no helper.
+// What follows is shared by the seven files above only: hidden, so that the library exports the C ABI and the pt_* names and no helper.
 // (A definition takes the visibility of the namespace block it stands in, so every block of pt_host is opened with PT_HOST.)
 #define PT_HOST namespace pt_host __attribute__((visibility("hidden")))
 PT_HOST {
@@ -127,6 +130,7 @@ struct ptmi_ctx {
     void *d_env = nullptr, *d_env_alias = nullptr;     // the environment map's texel and alias tables (DevScene::env points at them)
     double env_weight_sum = 0.0;                       // sum of the map's sampling weights (0: all black, never sampled)
     bool env_lookup_only = false;                      // ptmi_environment.sample = 1
+    ptmi_medium medium{};                              // the medium as the caller gave it (ptmi_get_medium); DevScene::med.on: in place
     DevScene *d_scene = nullptr;                       // sc in device memory (DevScene::self), rewritten whenever sc changes
     DevScene sc{};
     bool have_scene = false;

@@ -422,6 +422,14 @@ int ptmi_multi_set_environment(ptmi_multi *m, const ptmi_environment *params) {
     return each_ctx(m, "ptmi_set_environment", ptmi_set_environment, params);
 }
 
+int ptmi_multi_set_medium(ptmi_multi *m, const ptmi_medium *medium) {
+    if (!m) return PTMI_E_INVALID;
+    std::string why;                        // checked once, before any device changes: a rejected medium leaves every shard's in place
+    const int rc = pt_check_medium(medium, why);
+    if (rc) return mfail(m, rc, "%s", why.c_str());
+    return each_ctx(m, "ptmi_set_medium", ptmi_set_medium, medium);
+}
+
 int ptmi_multi_resize(ptmi_multi *m, uint32_t w, uint32_t h) {
     if (!m) return PTMI_E_INVALID;
     int rc = each_ctx(m, "ptmi_resize", ptmi_resize, w, h);

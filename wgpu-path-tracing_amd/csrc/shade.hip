@@ -11,6 +11,7 @@
 #include "pt_device.h"
 #include "pt_math.h"
 #include "pt_env.h"
+#include "pt_medium.h"
 
 namespace {
 
@@ -381,7 +382,14 @@ PT_DEV v3 stored_throughput(const DevPaths &P, uint32_t q, float4 d4) {
 // ray too — adds throughput * (W * Le(direction)) where an emissive hit's addition goes; while the map is sampled it is one more light
 // for next-event estimation, and the bounce ray carries W, the power-heuristic weight of its own density against the environment's at
 // its direction, in P.W for the bounce that may miss. Without ENV the kernel is the one it was: no branch of it reads the map.
-template <bool AOV, int STAGE, bool ENV>
+//
+// MED: the instantiations launched while a participating medium is in place (DevScene::med; DESIGN.md §11, pt_medium.h), with or
+// without ENV. A segment that crosses the box takes one draw for its free flight before any other; a collision in front of the hit (or
+// anywhere along a miss) makes the segment a SCATTER, decided before the hit's triangle and material are fetched and before the sky is
+// looked up: albedo, next-event estimation with the phase value where the BSDF's value and pdf stand, a direction sampled from the
+// phase function, roulette. Otherwise the segment is shaded as without a medium, except that every next-event sample's contribution
+// takes the transmittance towards its light. Without MED the kernel is the one it was: no branch of it reads the medium.
+template <bool AOV, int STAGE, bool ENV, bool MED>
 __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, DevPaths P, const uint32_t *__restrict__ queue,
                                                   const uint32_t *__restrict__ count_ptr,
                                                   const float2 *__restrict__ hits, DevShadow S,
@@ -409,10 +417,86 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
         if (i < count) {
             const uint32_t q = queue ? queue[i] : i;                         // where this ray's state is
             const float2 h2 = ld_stream(&hits[i]);
-            if (!(h2.x < 0.0f)) {                                            // pt.wgsl:646: miss adds zero
-                const float4 o4 = ld_stream(&P.O[q]), d4 = ld_stream(&P.D[q]);
+            bool scattered = false;
+            uint32_t med_rng = 0u;                                           // MED: the RNG state behind the free-flight draw, if one was taken
+            float4 med_o4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), med_d4 = med_o4;   // MED: the segment's O and D, loaded once for every branch
+            if (MED) {
+                med_o4 = ld_stream(&P.O[q]); med_d4 = ld_stream(&P.D[q]);
+                const float4 o4 = med_o4, d4 = med_d4;
+                const v3 ro = xyz(o4), rd = xyz(d4);
+                const bool is_hit = !(h2.x < 0.0f);
+                const MedInterval iv = med_interval(sc.med, ro, rd, is_hit ? h2.x : __builtin_inff());
+                med_rng = __float_as_uint(o4.w);
+                if (iv.b > iv.a) {
+                    const float t_sc = iv.a + med_free_flight(sc.med, rng_f(med_rng));
+                    scattered = t_sc < iv.b;
+                    if (scattered) {
+                        if (AOV) {                                           // the planes record the camera ray's surface hit all the same
+                            if (is_hit) {
+                                const HitInfo hit = make_hitinfo(sc, tabs, ro, rd, h2.x, __float_as_uint(h2.y));
+                                st_stream(&aov[2 * (size_t)i], make_float4(hit.albedo.x, hit.albedo.y, hit.albedo.z, hit.t));
+                                st_stream(&aov[2 * (size_t)i + 1], make_float4(hit.normal.x, hit.normal.y, hit.normal.z, h2.y));
+                            } else {
+                                aov_miss(aov, i);
+                            }
+                        }
+                        const uint32_t p = sp.pid ? sp.pid[q] : q;
+                        v3 thr = mk3(1.0f, 1.0f, 1.0f);
+                        if (sp.bounce != 0u) thr = stored_throughput(P, q, d4);
+                        thr = mul3(thr, ld3(sc.med.albedo));
+                        if ((thr.x != 0.0f) | (thr.y != 0.0f) | (thr.z != 0.0f)) {       // all zero: the path ends here
+                            const v3 x = madd3(rd, t_sc, ro);
+                            const float g = sc.med.g;
+                            float inv_n = 0.0f;
+                            const bool have_light = ENV ? sc.n_lights + sc.env.sampled > 0u : sc.n_lights > 0u;
+                            if (sp.do_mis && have_light) {
+                                LightSample ls = sample_light<STAGE, ENV>(sc, tabs, med_rng, x, inv_n);
+                                if (ls.pdf > 0.0f) {
+                                    const float ph = med_phase(g, dot3(rd, ls.wi));
+                                    float wmis = power_heuristic(1.0f, ls.pdf, 1.0f, ph);
+                                    v3 direct = vdiv3(scale3(scale3(ls.intensity, ph), wmis), max1(ls.pdf, PT_EPS));
+                                    v3 contrib = scale3(mul3(thr, direct), med_tr(sc.med, x, ls.wi, ls.dist));
+                                    if ((contrib.x != 0.0f) | (contrib.y != 0.0f) | (contrib.z != 0.0f)) {
+                                        rec_o = make_float4(x.x, x.y, x.z, ls.dist);
+                                        rec_d = make_float4(ls.wi.x, ls.wi.y, ls.wi.z, __uint_as_float(p));
+                                        rec_c = rgb_sc{contrib.x, contrib.y, contrib.z};
+                                        shadow = true;
+                                    } else {
+                                        skipped = true;
+                                    }
+                                } else if (ls.traced) {
+                                    skipped = true;
+                                }
+                            }
+                            const float xi1 = rng_f(med_rng), xi2 = rng_f(med_rng);
+                            float ct;
+                            const v3 nd = med_sample_phase(g, rd, xi1, xi2, ct);      // its density is its phase value: no factor
+                            alive = true;
+                            if (pt_plays_roulette(sp.bounce)) {
+                                float pr = max1(max1(thr.x, thr.y), thr.z);
+                                if (rng_f(med_rng) > pr) alive = false;
+                                else thr = vdiv3(thr, pr);
+                            }
+                            if (alive && sp.bounce + 1u < sp.max_bounces) {
+                                st_stream(&P.O[q], make_float4(x.x, x.y, x.z, __uint_as_float(med_rng)));
+                                st_stream(&P.D[q], make_float4(nd.x, nd.y, nd.z, thr.x));
+                                st_stream(&P.C[q], make_float2(thr.y, thr.z));
+                                if (ENV && P.W) {
+                                    float w = 1.0f;
+                                    if (inv_n != 0.0f) w = power_heuristic(1.0f, med_phase(g, ct), 1.0f, env_lookup(sc.env, nd).pdf * inv_n);
+                                    P.W[q] = w;
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+            if (MED && scattered) {
+                // handled above
+            } else if (!(h2.x < 0.0f)) {                                     // pt.wgsl:646: miss adds zero
+                const float4 o4 = MED ? med_o4 : ld_stream(&P.O[q]), d4 = MED ? med_d4 : ld_stream(&P.D[q]);
                 const uint32_t p = sp.pid ? sp.pid[q] : q;                       // the path id: where its radiance is
-                uint32_t rng = __float_as_uint(o4.w);
+                uint32_t rng = MED ? med_rng : __float_as_uint(o4.w);
                 const v3 ro = xyz(o4), rd = xyz(d4);
                 v3 thr = mk3(1.0f, 1.0f, 1.0f);                                      // pt.wgsl:639; raygen stores no throughput
                 if (sp.bounce != 0u) thr = stored_throughput(P, q, d4);
@@ -438,6 +522,7 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                             v3 direct = vdiv3(scale3(mul3(ls.intensity, mk3(ev.x, ev.y, ev.z)), wmis),
                                               max1(ls.pdf, PT_EPS));          // pt.wgsl:674
                             v3 contrib = mul3(thr, direct);                   // pt.wgsl:675, added by `shadow`
+                            if (MED) contrib = scale3(contrib, med_tr(sc.med, hit.position, ls.wi, ls.dist));
                             // A contribution of exactly zero (the light is behind the surface: NdotL = 0) leaves the
                             // radiance unchanged whatever the shadow ray finds (x + 0 = x), so that ray is counted
                             // in the statistics like the reference's traversal but neither recorded nor traced.
@@ -484,7 +569,7 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                 if (AOV) {
                     aov_miss(aov, i);
                 }
-                const float4 d4 = ld_stream(&P.D[q]);
+                const float4 d4 = MED ? med_d4 : ld_stream(&P.D[q]);
                 v3 thr = mk3(1.0f, 1.0f, 1.0f);
                 float w = 1.0f;
                 if (sp.bounce != 0u) {
@@ -543,29 +628,32 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
 #define PT_LAUNCH_SHADE pt_launch_shade
 #endif
 namespace {
-template <bool AOV, int STAGE, bool ENV>
+template <bool AOV, int STAGE, bool ENV, bool MED>
 void launch_shade(hipStream_t s, int blocks, const DevScene &sc, DevPaths p, const uint32_t *queue, const uint32_t *count,
                   const float2 *hits, DevShadow sh, uint64_t *alive_mask, uint64_t *shadow_mask, ShadeParams sp, float4 *aov) {
     const size_t lds = (((STAGE & PT_STAGE_MATS) ? pt_tab_mats_q(sc.n_mats) : 0) + ((STAGE & PT_STAGE_LIGHTS) ? pt_tab_lights_q(sc.n_lights) : 0)) * 16;
-    hipLaunchKernelGGL((k_shade<AOV, STAGE, ENV>), dim3(blocks), dim3(SBLOCK), lds, s, sc, p, queue, count, hits, sh, alive_mask,
+    hipLaunchKernelGGL((k_shade<AOV, STAGE, ENV, MED>), dim3(blocks), dim3(SBLOCK), lds, s, sc, p, queue, count, hits, sh, alive_mask,
                        shadow_mask, sp, aov);
 }
 }  // namespace
 // the tables each launch stages: pt_shade_stage of the scene's counts (what fits PT_SHADE_LDS_BUDGET), for every instantiation; ENV
-// while an environment map is in place
+// while an environment map is in place, MED while a medium is
 void PT_LAUNCH_SHADE(hipStream_t s, int blocks, const DevScene &sc, DevPaths p, const uint32_t *queue,
                      const uint32_t *count, const float2 *hits, DevShadow sh, uint64_t *alive_mask,
                      uint64_t *shadow_mask, ShadeParams sp, float4 *aov) {
+#define PT_SHADE_PICK(STAGE, MED)                                                                                         \
+    (sc.env.tab ? (aov ? launch_shade<true, STAGE, true, MED> : launch_shade<false, STAGE, true, MED>)                    \
+                : (aov ? launch_shade<true, STAGE, false, MED> : launch_shade<false, STAGE, false, MED>))
 #define PT_SHADE_CASE(STAGE)                                                                                              \
     case STAGE:                                                                                                           \
-        (sc.env.tab ? (aov ? launch_shade<true, STAGE, true> : launch_shade<false, STAGE, true>)                          \
-                    : (aov ? launch_shade<true, STAGE, false> : launch_shade<false, STAGE, false>))(                      \
+        (sc.med.on ? PT_SHADE_PICK(STAGE, true) : PT_SHADE_PICK(STAGE, false))(                                           \
             s, blocks, sc, p, queue, count, hits, sh, alive_mask, shadow_mask, sp, aov);                                  \
         break;
     switch (pt_shade_stage(sc.n_mats, sc.n_lights)) {
         PT_SHADE_CASE(0) PT_SHADE_CASE(PT_STAGE_MATS) PT_SHADE_CASE(PT_STAGE_LIGHTS) PT_SHADE_CASE(PT_STAGE_MATS | PT_STAGE_LIGHTS)
     }
 #undef PT_SHADE_CASE
+#undef PT_SHADE_PICK
 }
 
 #ifndef PT_SHADE_FAST

@@ -218,6 +218,46 @@ static napi_value js_upload_environment(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* a number property of obj into *out; 0 when it is absent or not a number */
+static int get_float_prop(napi_env env, napi_value obj, const char *name, float *out) {
+    napi_value v; double d;
+    if (napi_get_named_property(env, obj, name, &v) != napi_ok || napi_get_value_double(env, v, &d) != napi_ok) return 0;
+    *out = (float)d;
+    return 1;
+}
+/* an array property of three numbers */
+static int get_float3_prop(napi_env env, napi_value obj, const char *name, float out[3]) {
+    napi_value arr, v; double d;
+    if (napi_get_named_property(env, obj, name, &arr) != napi_ok) return 0;
+    for (uint32_t k = 0; k < 3; k++) {
+        if (napi_get_element(env, arr, k, &v) != napi_ok || napi_get_value_double(env, v, &d) != napi_ok) return 0;
+        out[k] = (float)d;
+    }
+    return 1;
+}
+
+/* setMedium(handle, {sigmaT, albedo: [r, g, b], g, min: [x, y, z], max: [x, y, z]} | null): ptmi_set_medium; null removes it */
+static napi_value js_set_medium(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    handle *h = get_handle(env, info, 2, argv);
+    if (!h) return NULL;
+    napi_valuetype t = napi_undefined;
+    if (napi_typeof(env, argv[1], &t) != napi_ok) t = napi_undefined;
+    if (t == napi_null || t == napi_undefined) {
+        CALL(env, h, set_medium, NULL);
+        return NULL;
+    }
+    ptmi_medium m = {0};
+    if (t != napi_object || !get_float_prop(env, argv[1], "sigmaT", &m.sigma_t) || !get_float3_prop(env, argv[1], "albedo", m.albedo) ||
+        !get_float_prop(env, argv[1], "g", &m.g) || !get_float3_prop(env, argv[1], "min", m.box_min) ||
+        !get_float3_prop(env, argv[1], "max", m.box_max)) {
+        napi_throw_type_error(env, NULL, "setMedium: expected {sigmaT, albedo: [3], g, min: [3], max: [3]} or null");
+        return NULL;
+    }
+    CALL(env, h, set_medium, &m);
+    return NULL;
+}
+
 static napi_value js_resize(napi_env env, napi_callback_info info) {
     napi_value argv[3];
     handle *h = get_handle(env, info, 3, argv);
@@ -674,7 +714,7 @@ static napi_value js_abi_version(napi_env env, napi_callback_info info) {
 static napi_value init(napi_env env, napi_value exports) {
     static const struct { const char *name; napi_callback fn; } fns[] = {
         {"abiVersion", js_abi_version}, {"create", js_create}, {"multiCreate", js_multi_create}, {"destroy", js_destroy},
-        {"uploadScene", js_upload_scene}, {"uploadAtlas", js_upload_atlas}, {"uploadEnvironment", js_upload_environment}, {"resize", js_resize}, {"setOptions", js_set_options},
+        {"uploadScene", js_upload_scene}, {"uploadAtlas", js_upload_atlas}, {"uploadEnvironment", js_upload_environment}, {"setMedium", js_set_medium}, {"resize", js_resize}, {"setOptions", js_set_options},
         {"dispatch", js_dispatch}, {"gather", js_gather}, {"gatherPlanes", js_gather_planes}, {"synchronize", js_synchronize}, {"throttle", js_throttle},
         {"readOutput", js_read_output}, {"writeOutput", js_write_output}, {"setAovs", js_set_aovs}, {"readAov", js_read_aov},
         {"blit", js_blit}, {"getStats", js_get_stats}, {"resetStats", js_reset_stats},

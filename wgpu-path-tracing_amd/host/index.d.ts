@@ -62,6 +62,8 @@ export class Renderer {
   /** the environment map behind every miss: float32 RGBA texels, equirectangular, row 0 at the +Y pole; null removes it.
    *  Restarts accumulation. */
   setEnvironment(texels: Float32Array | null, width?: number, height?: number, opts?: EnvironmentOptions): void;
+  /** one homogeneous scattering medium (fog) inside an axis-aligned box; null removes it. Restarts accumulation. */
+  setMedium(medium: MediumOptions | null): void;
   renderFrame(frames?: number): void;
   start(): void;
   stop(): void;
@@ -120,6 +122,16 @@ export const pack: {
   packBVH(n: BVHNode[]): ArrayBuffer; packLights(l: LightCPU[]): ArrayBuffer;
   packCamera(c: CameraCPU, out?: ArrayBuffer): ArrayBuffer; packScene(s: SceneData): SceneBlobs;
 };
+export interface MediumOptions {
+  /** extinction per unit length; finite, > 0 */
+  sigmaT: number;
+  /** single-scattering albedo, a number or [r, g, b], each in [0, 1]; default 1 */
+  albedo?: number | [number, number, number];
+  /** Henyey-Greenstein asymmetry, |g| <= 0.99; default 0 */
+  g?: number;
+  /** the medium's box, or 'scene': the root box of the scene loaded last */
+  bounds: { min: [number, number, number]; max: [number, number, number] } | 'scene';
+}
 export interface EnvironmentOptions {
   /** radiance scale; 0 / undefined: 1 */
   intensity?: number;

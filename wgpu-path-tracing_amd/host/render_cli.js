@@ -7,13 +7,15 @@
  *                       --aperture A --focus F --batch K --png out.png --denoise
  *                       --adaptive THRESHOLD --max-frames N --rounds R
  *                       --env file.hdr --env-intensity X --env-rotation DEGREES --env-sample 0|1
+ *                       --fog sigma_t[,albedo[,g]]
  *                       --devices 0,1,... --loopback --aov albedo|normal|id --aov-out plane.bin]
  * --batch K traces K frames per dispatch instead of one. --denoise keeps the denoiser's planes and makes --png the tone-mapped
  * denoised image (include/ptmi.h ptmi_denoise, default parameters). --adaptive renders to a noise level instead of --frames
  * (include/ptmi.h ptmi_dispatch_adaptive): rounds until none lists a pixel, or --rounds R of them; the JSON line then also holds
  * adaptive: { samples, minCount, maxCount, rounds }. --env lights the scene with a Radiance .hdr environment map (hdr_decode.js;
  * include/ptmi.h ptmi_upload_environment): equirectangular, scaled by --env-intensity, turned by --env-rotation degrees about +Y;
- * --env-sample 1 only looks it up. Writes W*H*4 float32 (the output buffer, raw also with
+ * --env-sample 1 only looks it up. --fog fills the scene's box with a homogeneous scattering medium (include/ptmi.h ptmi_set_medium):
+ * extinction sigma_t per unit length, single-scattering albedo (default 1) and Henyey-Greenstein asymmetry g (default 0). Writes W*H*4 float32 (the output buffer, raw also with
  * --denoise) and prints one JSON line with the statistics. --devices renders on several GPUs behind one Renderer (include/ptmi.h
  * ptmi_multi_*; --loopback lets one ordinal be listed more than once, for a one-GPU box); --adaptive, --denoise and --aov work with
  * it. --aov keeps that first-hit plane and --aov-out writes it raw (float32 x 4 per pixel, uint32 x 2 for id).
@@ -55,6 +57,10 @@ r.loadModel(scenePath).then(function () {
     var env = require('./hdr_decode').decodeHDR(fs.readFileSync(process.argv[envAt + 1]));
     r.setEnvironment(env.data, env.width, env.height,
                      { intensity: arg('env-intensity', 1), rotation: arg('env-rotation', 0) * Math.PI / 180, sample: arg('env-sample', 0) });
+  }
+  if (textArg('fog')) {
+    var fog = textArg('fog').split(',').map(Number);
+    r.setMedium({ sigmaT: fog[0], albedo: fog.length > 1 ? fog[1] : 1, g: fog.length > 2 ? fog[2] : 0, bounds: 'scene' });
   }
   var t0 = Date.now();
   var status = null;

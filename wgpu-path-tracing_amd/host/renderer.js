@@ -95,6 +95,7 @@ Renderer.prototype.loadModel = function (model, atlas) {
       blobs = pack.packScene(model);
     }
     self.addon.uploadScene(self.ctx, blobs.triangles, blobs.materials, blobs.bvhNodes, blobs.lights);
+    self.sceneBounds = rootBox(blobs.bvhNodes);       // setMedium({ bounds: 'scene' })
     if (atlas) self.addon.uploadAtlas(self.ctx, atlas.data, atlas.width, atlas.height, atlas.format || 1);
     else self.addon.uploadAtlas(self.ctx, null, 0, 0, 0);
     self.sceneLoaded = true;
@@ -102,6 +103,15 @@ Renderer.prototype.loadModel = function (model, atlas) {
     resolve();
   });
 };
+
+/** the box of the hierarchy's root, node 0 of the 48-byte nodes (min.xyz, pad, max.xyz, pad, ...); null without nodes */
+function rootBox(bvhNodes) {
+  var bytes = bvhNodes && (bvhNodes.byteLength || 0);
+  if (!bytes || bytes < 32) return null;
+  var f = bvhNodes instanceof ArrayBuffer ? new Float32Array(bvhNodes, 0, 8)
+                                          : new Float32Array(bvhNodes.buffer, bvhNodes.byteOffset, 8);
+  return { min: [f[0], f[1], f[2]], max: [f[4], f[5], f[6]] };
+}
 
 /** renderer.ts:357-366. cameraMoved: the reset follows a camera change and nothing else; with setReproject and adaptive rounds
  *  accumulated, the samples then stay, for the next round to reproject from the camera they were accumulated under. */
@@ -192,6 +202,28 @@ Renderer.prototype.setEnvironment = function (texels, width, height, opts) {
   if (texels && !(texels instanceof Float32Array)) throw new TypeError('setEnvironment: texels must be a Float32Array of RGBA');
   this.addon.uploadEnvironment(this.ctx, texels || null, texels ? width : 0, texels ? height : 0,
                                { intensity: opts.intensity || 0, rotation: opts.rotation || 0, sample: opts.sample ? 1 : 0 });
+  this.frameIndex = 0;
+};
+
+/**
+ * One homogeneous scattering medium inside an axis-aligned box (include/ptmi.h ptmi_set_medium): { sigmaT (extinction per unit
+ * length), albedo (a number or [r, g, b], default 1), g (Henyey-Greenstein asymmetry, default 0), bounds ({ min: [x, y, z],
+ * max: [x, y, z] }, or 'scene': the root box of the scene loaded last) }. null removes it. Accumulation restarts.
+ */
+Renderer.prototype.setMedium = function (medium) {
+  if (!medium) {
+    this.addon.setMedium(this.ctx, null);
+  } else {
+    var bounds = medium.bounds;
+    if (bounds === 'scene') {
+      if (!this.sceneBounds) throw new Error("setMedium: bounds 'scene' needs a loaded scene with a hierarchy");
+      bounds = this.sceneBounds;
+    }
+    if (!bounds || !bounds.min || !bounds.max) throw new TypeError("setMedium: bounds must be { min, max } or 'scene'");
+    var a = medium.albedo === undefined ? 1 : medium.albedo;
+    this.addon.setMedium(this.ctx, { sigmaT: medium.sigmaT, albedo: typeof a === 'number' ? [a, a, a] : a, g: medium.g || 0,
+                                     min: bounds.min, max: bounds.max });
+  }
   this.frameIndex = 0;
 };
 

@@ -39,6 +39,7 @@ EXPORTS = [
     "ptmi_multi_set_aovs", "ptmi_multi_get_aovs", "ptmi_multi_set_moments", "ptmi_multi_get_moments", "ptmi_multi_gather_planes",
     "ptmi_multi_read_aov", "ptmi_multi_read_moments", "ptmi_multi_dispatch_adaptive", "ptmi_multi_adaptive_status",
     "ptmi_multi_denoise", "ptmi_multi_blit_denoised",
+    "ptmi_set_medium", "ptmi_get_medium", "ptmi_multi_set_medium", "ptmi_debug_medium_step", "ptmi_debug_medium_tr",
 ]
 MULTI_LOOPBACK = 1
 MULTI_PLANE_MOMENTS, MULTI_PLANE_OUTPUT = 0x100, 0x200      # gather_planes: with the AOV_* bits
@@ -113,6 +114,16 @@ class EnvironmentStatus(ctypes.Structure):
         return {"width": int(self.width), "height": int(self.height), "sampled": int(self.sampled), "weight_sum": float(self.weight_sum)}
 
 
+class Medium(ctypes.Structure):
+    """ptmi_medium: one homogeneous medium inside an axis-aligned box (include/ptmi.h)"""
+    _fields_ = [("sigma_t", ctypes.c_float), ("albedo", ctypes.c_float * 3), ("g", ctypes.c_float),
+                ("box_min", ctypes.c_float * 3), ("box_max", ctypes.c_float * 3), ("reserved", ctypes.c_uint32 * 5)]
+
+    def as_dict(self):
+        return {"sigma_t": float(self.sigma_t), "albedo": tuple(self.albedo), "g": float(self.g),
+                "box": (tuple(self.box_min), tuple(self.box_max))}
+
+
 class Stats(ctypes.Structure):
     _fields_ = [("paths", ctypes.c_uint64), ("segments", ctypes.c_uint64), ("shadow_rays", ctypes.c_uint64),
                 ("dispatches", ctypes.c_uint64), ("frames", ctypes.c_uint64),
@@ -145,6 +156,7 @@ _SHARED = {
     "get_stats": [ctypes.c_void_p],
     "upload_environment": [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p],
     "set_environment": [ctypes.c_void_p],
+    "set_medium": [ctypes.c_void_p],
     "set_aovs": [ctypes.c_uint32], "get_aovs": [ctypes.POINTER(ctypes.c_uint32)], "read_aov": [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t],
     "set_moments": [ctypes.c_uint32], "get_moments": [ctypes.POINTER(ctypes.c_uint32)], "read_moments": [ctypes.c_void_p, ctypes.c_size_t],
     "denoise": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t], "blit_denoised": [ctypes.c_void_p, ctypes.c_size_t] * 2,
@@ -203,6 +215,9 @@ def load():
         L.ptmi_debug_env_lookup.argtypes = [vp, u32, vp, vp]
         L.ptmi_debug_env_sample.argtypes = [vp, u32, vp, vp, vp, vp]
         L.ptmi_debug_env_table.argtypes = [vp, u32, u32, ctypes.c_int, vp, vp, vp, ctypes.POINTER(ctypes.c_double)]
+        L.ptmi_get_medium.argtypes = [vp, vp, ctypes.POINTER(u32)]
+        L.ptmi_debug_medium_step.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.ptmi_debug_medium_tr.argtypes = [vp, u32, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -364,6 +379,18 @@ class _Handle:
         """intensity / rotation / sample of the map in place, without a re-upload"""
         prm = Environment(intensity, rotation, sample, (ctypes.c_uint32 * 5)(*reserved))
         self._ck(self._c.set_environment(self.h, ctypes.byref(prm)))
+
+    def set_medium(self, sigma_t=None, albedo=(1.0, 1.0, 1.0), g=0.0, box=None, reserved=(0, 0, 0, 0, 0)):
+        """One homogeneous scattering medium inside the axis-aligned box (min, max) (include/ptmi.h ptmi_set_medium): extinction
+        sigma_t per unit length, single-scattering albedo per channel (a scalar: all three), Henyey-Greenstein asymmetry g.
+        sigma_t None removes it."""
+        if sigma_t is None:
+            self._ck(self._c.set_medium(self.h, None))
+            return
+        alb = np.broadcast_to(np.asarray(albedo, np.float32), (3,))
+        f3 = ctypes.c_float * 3
+        m = Medium(sigma_t, f3(*alb), g, f3(*box[0]), f3(*box[1]), (ctypes.c_uint32 * 5)(*reserved))
+        self._ck(self._c.set_medium(self.h, ctypes.byref(m)))
 
     def resize(self, width, height):
         self._ck(self._c.resize(self.h, width, height))
@@ -561,6 +588,33 @@ class Context(_Handle):
         d, out, tex = np.zeros((len(r), 3), np.float32), np.zeros((len(r), 4), np.float32), np.zeros(len(r), np.uint32)
         self._ck(self.L.ptmi_debug_env_sample(self.h, len(r), _p(r), _p(d), _p(out), _p(tex)))
         return d, out, tex
+
+    # -- the participating medium (include/ptmi.h ptmi_set_medium) ----------------------------------------------------
+    def get_medium(self):
+        """the medium in place as a Medium, or None"""
+        m, present = Medium(), ctypes.c_uint32(0)
+        self._ck(self.L.ptmi_get_medium(self.h, ctypes.byref(m), ctypes.byref(present)))
+        return m if present.value else None
+
+    def debug_medium_step(self, o, d, t_hit, r):
+        """one path segment of the medium in place on the uniforms r (n, 3) = (r, xi1, xi2) for the rays (o, d) and hit distances t_hit
+        (inf: a miss): (scattered (n,) bool, x (n, 3), direction (n, 3), (a, b, s, phase density) (n, 4))"""
+        o, d = np.ascontiguousarray(o, np.float32).reshape(-1, 3), np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        t_hit, r = np.ascontiguousarray(t_hit, np.float32).reshape(-1), np.ascontiguousarray(r, np.float32).reshape(-1, 3)
+        n = len(o)
+        assert len(d) == n and len(t_hit) == n and len(r) == n
+        sc, x, dr, out = np.zeros(n, np.uint32), np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros((n, 4), np.float32)
+        self._ck(self.L.ptmi_debug_medium_step(self.h, n, _p(o), _p(d), _p(t_hit), _p(r), _p(sc), _p(x), _p(dr), _p(out)))
+        return sc != 0, x, dr, out
+
+    def debug_medium_tr(self, o, wi, dist):
+        """the transmittance a next-event sample from o towards wi, dist away (< 0: directional), takes: (n,) float32"""
+        o, wi = np.ascontiguousarray(o, np.float32).reshape(-1, 3), np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
+        dist = np.ascontiguousarray(dist, np.float32).reshape(-1)
+        assert len(wi) == len(o) and len(dist) == len(o)
+        tr = np.zeros(len(o), np.float32)
+        self._ck(self.L.ptmi_debug_medium_tr(self.h, len(o), _p(o), _p(wi), _p(dist), _p(tr)))
+        return tr
 
     def read_image(self):
         """The traversal image the last upload_scene put on the device (include/ptmi.h: ptmi_debug_read_image), as build_image()
