@@ -424,6 +424,7 @@ int ptmi_environment_status(ptmi_ctx *ctx, struct ptmi_environment_status *out);
  *    far = min_k max(t1, t2), a = max(near, 0), b = min(far, t_hit), with fmin / fmax semantics (a NaN from 0 * inf drops out). If NOT
  *    b > a the segment is handled exactly as without a medium and draws nothing extra. (A box with min == max on an axis has no such
  *    segment, but for a ray that lies in that plane with a direction component of exactly 0 across it: both of its NaNs drop out.)
+ *    A ray whose t1 and t2 are NaN on all three axes, the NaN origin or direction of a degenerate path, has no interval: b = a.
  * 2. FREE FLIGHT. One draw r, before any other draw of the segment: s = -ln(1 - r) / sigma_t. The path SCATTERS iff a + s < b, at
  *    x = o + (a + s) d; otherwise the surface hit or the miss is handled as without a medium, the throughput unchanged (distance
  *    sampling and the transmittance cancel).
@@ -444,8 +445,9 @@ int ptmi_environment_status(ptmi_ctx *ctx, struct ptmi_environment_status *out);
  * 5. UNCHANGED: the additions of emissive hits and misses; the first-hit planes, which record the camera ray's SURFACE hit whether or
  *    not the path scattered in front of it (every plane has the same bits with and without a medium); the moments plane; the fold.
  * ln, exp and the free-flight comparison use the device's logf / expf: they are outside the bit-exact arithmetic contract, like the
- * sky lookup and ptmi_blit, and the CPU oracle does not model the medium. A ray that starts at a scatter point outside the scene's
- * bounds takes the own-leaf kernels' re-trace over the tree as uploaded: correct, and slower. */
+ * sky lookup and ptmi_blit; the CPU oracle models the medium with the C library's (oracle/pt_oracle.h pto_extras). A ray that
+ * starts at a scatter point outside the scene's bounds takes the own-leaf kernels' re-trace over the tree as uploaded: correct, and
+ * slower. */
 typedef struct ptmi_medium {
     float    sigma_t;                 /* extinction per unit length; finite, > 0 */
     float    albedo[3];               /* each in [0, 1] */

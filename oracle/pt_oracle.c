@@ -235,7 +235,13 @@ typedef struct {
     ray_tap_t *tap;
     uint64_t *cen;          /* branch census (pto_render_census): cen[event * 64 + bounce], this thread's own; NULL elsewhere */
     uint32_t b;             /* the bounce being traced, min(bounce, 63) */
+    float border;           /* extras: the smallest distance of a sky lookup from a texel border, in texels (reset per path by the caller) */
+    uint32_t sig;           /* a hash of the path's discrete decisions (SIG below; reset per path by the caller) */
 } counters_t;
+/* Every decision of a path that is not arithmetic — the triangle hit, interval and scatter, the light picked, occlusion, the lobe,
+ * reflection or refraction, roulette, the sky texel read — goes into one word per path: two runs whose words are equal took the
+ * same branches, and differ by rounding alone (pto_render_ext's `branches`). */
+#define SIG(c, v) ((c)->sig = ((c)->sig ^ (uint32_t)(v)) * 0x01000193u)
 
 /* ------------------------------------------------------------------------- */
 /* branch census — pto_census_event in pt_oracle.h                             */
@@ -435,12 +441,6 @@ static hitinfo_t make_hitinfo(const pto_scene *s, ray_t r, hit_t h, counters_t *
     return hi;
 }
 
-static hitinfo_t scene_intersect(const pto_scene *s, ray_t r, counters_t *c, hit_t *raw) { /* :294-296 */
-    hit_t h = traverse(s, r, c);
-    if (raw) *raw = h;
-    return make_hitinfo(s, r, h, c);
-}
-
 /* ------------------------------------------------------------------------- */
 /* sampling and BSDF — pt.wgsl:299-364, :492-634                               */
 /* ------------------------------------------------------------------------- */
@@ -514,12 +514,12 @@ static v3 sample_bsdf(uint32_t *rng, const hitinfo_t *h, ray_t cur, int front, c
     float specular_p = h->metallic;
     float r = rng_f(rng);                                           /* :508 */
     if (r < diffuse_p) {
-        CEN(c, PTO_EV_LOBE_DIFFUSE);
+        CEN(c, PTO_EV_LOBE_DIFFUSE); SIG(c, 0x10BE0);
         v3 l = random_cosine_direction(rng);
         v3 T, B; construct_tbn(h->normal, &T, &B, c);
         return lincomb3(T, l.x, B, l.y, h->normal, l.z);            /* :514 */
     } else if (r < diffuse_p + specular_p) {
-        CEN(c, PTO_EV_LOBE_SPECULAR);
+        CEN(c, PTO_EV_LOBE_SPECULAR); SIG(c, 0x10BE1);
         float rough = max1(h->roughness, 0.04f);
         v3 N = sample_ggx_normal(rng, h->normal, rough, c);
         return reflect3(neg3(Vv), N);                               /* :520 */
@@ -535,12 +535,12 @@ static v3 sample_bsdf(uint32_t *rng, const hitinfo_t *h, ray_t cur, int front, c
         float sin_t = sqrtf(1.0f - cos_t * cos_t);
         int cannot_refract = eta * sin_t > 1.0f;
         float F = reflectance(fabsf(cos_t), eta);
-        if (cannot_refract) { CEN(c, PTO_EV_TOTAL_INTERNAL_REFLECTION); return reflect3(neg3(Vv), N); }
+        if (cannot_refract) { CEN(c, PTO_EV_TOTAL_INTERNAL_REFLECTION); SIG(c, 0x10BE2); return reflect3(neg3(Vv), N); }
         if (rng_f(rng) < F) {                                       /* :538 short-circuit */
-            CEN(c, PTO_EV_FRESNEL_REFLECTION);
+            CEN(c, PTO_EV_FRESNEL_REFLECTION); SIG(c, 0x10BE3);
             return reflect3(neg3(Vv), N);
         }
-        CEN(c, PTO_EV_REFRACTION);
+        CEN(c, PTO_EV_REFRACTION); SIG(c, 0x10BE4);
         if (c->cen) {                                               /* what refract3 is about to test */
             float dn = dot3(N, neg3(Vv)), k = 1.0f - (eta * eta) * (1.0f - dn * dn);
             if (k < 0.0f) CEN(c, PTO_EV_REFRACT_K_NEGATIVE);
@@ -593,49 +593,183 @@ static v4 eval_bsdf(const hitinfo_t *h, v3 normal, v3 Vv, v3 L, int front, count
 /* traced: the reference shoots this sample's shadow ray. occluded is set only under the census (c->cen), which evaluates an
  * occluded sample as if it were not — what `shade` computes before `shadow` knows the answer — beside the result: trace()
  * never adds such a sample. Without the census an occluded sample returns at once with pdf = 0, as the reference does. */
-typedef struct { v3 intensity; uint32_t light_type; v3 wi; float pdf; int traced, occluded; } light_sample_t;
+typedef struct { v3 intensity; uint32_t light_type; v3 wi; float pdf; float dist; int traced, occluded; } light_sample_t;
 
-static light_sample_t sample_light(const pto_scene *s, uint32_t *rng, v3 hit_pos, counters_t *c) {
+/* ------------------------------------------------------------------------- */
+/* extras — the environment and the medium of include/ptmi.h (pto_extras)     */
+/* ------------------------------------------------------------------------- */
+/* Statement by statement csrc/pt_env.h and csrc/pt_medium.h. Outside the arithmetic contract there: logf, expf, atan2f, acosf (the
+ * device's are 1 - 2 ulp; libm's here); each of their results is moved by ex->ulp_nudge float32 steps, 0 for the reference. */
+#define PT_TWO_PI  6.28318530718f
+#define PT_FOUR_PI 12.5663706144f
+static inline int env_on(const pto_extras *ex) { return ex && ex->env_texels; }
+static inline int env_sampled(const pto_extras *ex) { return env_on(ex) && ex->env_sampled; }
+static inline int med_on(const pto_extras *ex) { return ex && ex->med_on; }
+static inline float nudge(float x, int n) {
+    for (; n > 0; n--) x = nextafterf(x, INFINITY);
+    for (; n < 0; n++) x = nextafterf(x, -INFINITY);
+    return x;
+}
+static inline uint32_t min_u(uint32_t a, uint32_t b) { return a < b ? a : b; }
+typedef struct { v3 le; float pdf; } env_sample_t;
+/* pt_env.h env_texel; the lookup's distance from a texel border goes to c->border */
+static uint32_t env_texel(const pto_extras *ex, v3 d, counters_t *c) {
+    float phi = nudge(atan2f(d.z, d.x), ex->ulp_nudge) - ex->env_rotation;
+    float u = phi / PT_TWO_PI + 0.5f;
+    u -= floorf(u);
+    float v = nudge(acosf(min1(max1(d.y, -1.0f), 1.0f)), ex->ulp_nudge) / PT_PI;
+    float uw = u * (float)ex->env_w, vh = v * (float)ex->env_h;
+    float bd = min1(fabsf(uw - rintf(uw)), fabsf(vh - rintf(vh)));
+    if (bd < c->border) c->border = bd;
+    uint32_t x = min_u(f2u(uw), ex->env_w - 1u), y = min_u(f2u(vh), ex->env_h - 1u);
+    SIG(c, 0x7E0000u + y * ex->env_w + x);
+    return y * ex->env_w + x;
+}
+static inline v3 env_radiance(const pto_extras *ex, const float *t) {
+    return V3(t[0] * ex->env_intensity, t[1] * ex->env_intensity, t[2] * ex->env_intensity);
+}
+static inline float env_pdf_of(float cc, float dy) {
+    return cc / max1(sqrtf(max1(0.0f, __builtin_fmaf(-dy, dy, 1.0f))), PT_EPS);
+}
+static env_sample_t env_lookup(const pto_extras *ex, v3 d, counters_t *c) {
+    const float *t = ex->env_texels + 4 * (size_t)env_texel(ex, d, c);
+    env_sample_t r = { env_radiance(ex, t), env_pdf_of(t[3], d.y) };
+    return r;
+}
+/* pt_env.h env_sample */
+static env_sample_t env_sample(const pto_extras *ex, float r1, float r2, float r3, float r4, v3 *d, uint32_t *texel) {
+    uint32_t n = ex->env_w * ex->env_h;
+    uint32_t k = min_u(f2u(r1 * (float)n), n - 1u);
+    uint32_t t = r2 < ex->env_prob[k] ? k : ex->env_alias[k];
+    uint32_t ty = t / ex->env_w, tx = t - ty * ex->env_w;
+    float u = ((float)tx + r3) / (float)ex->env_w, v = ((float)ty + r4) / (float)ex->env_h;
+    float theta = v * PT_PI, phi = __builtin_fmaf(u - 0.5f, PT_TWO_PI, ex->env_rotation);
+    float st, ct, sp, cp;
+    sincos1(theta, &st, &ct);
+    sincos1(phi, &sp, &cp);
+    *d = V3(st * cp, ct, st * sp);
+    *texel = t;
+    const float *q = ex->env_texels + 4 * (size_t)t;
+    env_sample_t r = { env_radiance(ex, q), q[3] / max1(st, PT_EPS) };
+    return r;
+}
+typedef struct { float near, far, a, b; } med_interval_t;
+/* pt_medium.h med_interval */
+static med_interval_t med_interval(const pto_extras *ex, v3 o, v3 d, float t_hit) {
+    float ix = 1.0f / d.x, iy = 1.0f / d.y, iz = 1.0f / d.z;
+    float x1 = (ex->box_min[0] - o.x) * ix, x2 = (ex->box_max[0] - o.x) * ix;
+    float y1 = (ex->box_min[1] - o.y) * iy, y2 = (ex->box_max[1] - o.y) * iy;
+    float z1 = (ex->box_min[2] - o.z) * iz, z2 = (ex->box_max[2] - o.z) * iz;
+    med_interval_t r;
+    r.near = max1(max1(min1(x1, x2), min1(y1, y2)), min1(z1, z2));
+    r.far = min1(min1(max1(x1, x2), max1(y1, y2)), max1(z1, z2));
+    r.a = max1(r.near, 0.0f);
+    r.b = r.far == r.far ? min1(r.far, t_hit) : r.a;     /* NaN on every axis (a degenerate path): no interval */
+    return r;
+}
+static float med_free_flight(const pto_extras *ex, float r) { return -nudge(logf(1.0f - r), ex->ulp_nudge) / ex->sigma_t; }
+static float med_tr(const pto_extras *ex, v3 o, v3 wi, float dist) {
+    med_interval_t iv = med_interval(ex, o, wi, INFINITY);
+    float end = dist < 0.0f ? iv.far : min1(iv.far, dist);
+    return nudge(expf(-ex->sigma_t * max1(0.0f, end - iv.a)), ex->ulp_nudge);
+}
+static float med_phase(float g, float cos_t) {
+    float g2 = g * g;
+    float k = 1.0f + g2 - 2.0f * g * cos_t;
+    return (1.0f - g2) / (PT_FOUR_PI * (k * sqrtf(k)));
+}
+static v3 med_sample_phase(float g, v3 d, float xi1, float xi2, float *cos_out) {
+    float ct;
+    if (fabsf(g) < 1e-3f) {
+        ct = 1.0f - 2.0f * xi1;
+    } else {
+        float g2 = g * g;
+        float q = (1.0f - g2) / (1.0f - g + 2.0f * g * xi1);
+        ct = (1.0f + g2 - q * q) / (2.0f * g);
+    }
+    ct = min1(max1(ct, -1.0f), 1.0f);
+    float st = sqrtf(max1(0.0f, 1.0f - ct * ct));
+    float sp, cp; sincos1((2.0f * PT_PI) * xi2, &sp, &cp);
+    float sg = copysignf(1.0f, d.z);
+    float A = -1.0f / (sg + d.z);
+    float B = d.x * d.y * A;
+    v3 T = V3(1.0f + sg * d.x * d.x * A, sg * B, -sg * d.x);
+    v3 U = V3(B, sg + d.y * d.y * A, -d.y);
+    *cos_out = ct;
+    return normalize3(lincomb3(T, st * cp, U, st * sp, d, ct));
+}
+
+/* ex (NULL: none): a sampled environment is light number n_lights, one more to pick from, for every light's 1 / n (shade.hip
+ * sample_light<.., ENV>). scatter: the sample is taken at a scatter point of the medium: the shadow ray starts at hit_pos itself
+ * and the census counts the med_nee_* events. inv_n_out: 1 / n, for the weight of the bounce ray. */
+static light_sample_t sample_light(const pto_scene *s, const pto_extras *ex, int scatter, uint32_t *rng, v3 hit_pos, counters_t *c,
+                                   float *inv_n_out) {
     light_sample_t ls;
     memset(&ls, 0, sizeof ls);
-    uint32_t nl = s->n_lights;                       /* caller guarantees nl > 0 */
-    const ptmi_light *lt = &s->lights[rng_int(rng, 0u, nl - 1u)];    /* :375 */
-    ls.light_type = lt->light_type;
+    ls.dist = -1.0f;
+#define SHADOW_ORIGIN(wi) (scatter ? hit_pos : madd3(wi, PT_EPS, hit_pos))
+    uint32_t nl = s->n_lights + (env_sampled(ex) ? 1u : 0u);        /* caller guarantees nl > 0 */
+    uint32_t li = rng_int(rng, 0u, nl - 1u);                         /* :375 */
     float inv_n = 1.0f / (float)nl;
-    if (lt->light_type == PTMI_LIGHT_DIRECTIONAL) {                   /* :385-406 */
-        CEN(c, PTO_EV_NEE_DIRECTIONAL);
-        CS_NORM(c, PTO_CS_LIGHT_DIRECTION, neg3(ld3(lt->position)));
-        v3 wi = normalize3(neg3(ld3(lt->position)));
-        ray_t sr = { madd3(wi, PT_EPS, hit_pos), wi };
+    *inv_n_out = inv_n;
+    SIG(c, 0x1100u + li);
+    if (li == s->n_lights) {                                         /* the environment: four draws, a directional sample */
+        CEN(c, scatter ? PTO_EV_MED_NEE_ENV : PTO_EV_NEE_ENV);
+        float r1 = rng_f(rng), r2 = rng_f(rng), r3 = rng_f(rng), r4 = rng_f(rng);
+        v3 wi; uint32_t texel;
+        env_sample_t es = env_sample(ex, r1, r2, r3, r4, &wi, &texel);
+        ray_t sr = { SHADOW_ORIGIN(wi), wi };
         c->shadow_rays++;
         hit_t sh = traverse(s, sr, c);
         tap_shadow(c, -1.0f);
         ls.traced = 1;
+        ls.light_type = 0xFFFFFFFFu;
+        ls.wi = wi;
+        SIG(c, sh.t > 0.0f);
+        if (sh.t > 0.0f) { ls.pdf = 0.0f; if (!c->cen) return ls; ls.occluded = 1; }
+        ls.intensity = es.le;
+        ls.pdf = es.pdf * inv_n;
+        return ls;
+    }
+    const ptmi_light *lt = &s->lights[li];
+    ls.light_type = lt->light_type;
+    if (lt->light_type == PTMI_LIGHT_DIRECTIONAL) {                   /* :385-406 */
+        CEN(c, scatter ? PTO_EV_MED_NEE_DIRECTIONAL : PTO_EV_NEE_DIRECTIONAL);
+        CS_NORM(c, PTO_CS_LIGHT_DIRECTION, neg3(ld3(lt->position)));
+        v3 wi = normalize3(neg3(ld3(lt->position)));
+        ray_t sr = { SHADOW_ORIGIN(wi), wi };
+        c->shadow_rays++;
+        hit_t sh = traverse(s, sr, c);
+        tap_shadow(c, -1.0f);
+        ls.traced = 1;
+        SIG(c, sh.t > 0.0f);
         if (sh.t > 0.0f) { ls.wi = wi; ls.pdf = 0.0f; if (!c->cen) return ls; ls.occluded = 1; }
         ls.intensity = scale3(ld3(lt->color), lt->intensity);
         ls.wi = wi;
         ls.pdf = inv_n * 1000.0f;
     } else if (lt->light_type == PTMI_LIGHT_POINT) {                  /* :407-438 */
-        CEN(c, PTO_EV_NEE_POINT);
+        CEN(c, scatter ? PTO_EV_MED_NEE_POINT : PTO_EV_NEE_POINT);
         v3 to_l = sub3(ld3(lt->position), hit_pos);
         CS_SQRT(c, PTO_CS_POINT_DISTANCE, dot3(to_l, to_l));
         float dist = length3(to_l);
-        if (dist > 100.0f) { CEN(c, PTO_EV_POINT_LIGHT_BEYOND_100); return ls; }
+        if (dist > 100.0f) { CEN(c, PTO_EV_POINT_LIGHT_BEYOND_100); SIG(c, 0xB100); return ls; }
         CS_RCP(c, PTO_CS_POINT_RCP_DISTANCE, dist);
         v3 wi = vdiv3(to_l, dist);
-        ray_t sr = { madd3(wi, PT_EPS, hit_pos), wi };
+        ray_t sr = { SHADOW_ORIGIN(wi), wi };
         c->shadow_rays++;
         hit_t sh = traverse(s, sr, c);
         tap_shadow(c, dist);
         ls.traced = 1;
+        SIG(c, sh.t > 0.0f && sh.t < dist - PT_EPS * 2.0f);
         if (sh.t > 0.0f && sh.t < dist - PT_EPS * 2.0f) { ls.wi = wi; ls.pdf = 0.0f; if (!c->cen) return ls; ls.occluded = 1; }
         CS_RCP(c, PTO_CS_POINT_ATTENUATION, dist * dist);
         float att = 1.0f / (dist * dist);
         ls.intensity = scale3(scale3(ld3(lt->color), lt->intensity), att);
         ls.wi = wi;
         ls.pdf = inv_n * 10000.0f;
+        ls.dist = dist;
     } else if (lt->light_type == PTMI_LIGHT_EMISSIVE) {               /* :439-486 */
-        CEN(c, PTO_EV_NEE_EMISSIVE);
+        CEN(c, scatter ? PTO_EV_MED_NEE_EMISSIVE : PTO_EV_NEE_EMISSIVE);
         ptmi_triangle zero_t; memset(&zero_t, 0, sizeof zero_t);
         const ptmi_triangle *T = lt->triangle_index < s->n_tris ? &s->tris[lt->triangle_index] : &zero_t;
         float r1 = rng_f(rng), r2 = rng_f(rng);
@@ -651,11 +785,12 @@ static light_sample_t sample_light(const pto_scene *s, uint32_t *rng, v3 hit_pos
         float dist = length3(to_l);
         CS_RCP(c, PTO_CS_EMISSIVE_RCP_DISTANCE, dist);
         v3 wi = vdiv3(to_l, dist);
-        ray_t sr = { madd3(wi, PT_EPS, hit_pos), wi };
+        ray_t sr = { SHADOW_ORIGIN(wi), wi };
         c->shadow_rays++;
         hit_t sh = traverse(s, sr, c);
         tap_shadow(c, dist);
         ls.traced = 1;
+        SIG(c, sh.t > 0.0f && sh.t < dist - PT_EPS * 2.0f);
         if (sh.t > 0.0f && sh.t < dist - PT_EPS * 2.0f) { ls.wi = wi; ls.pdf = 0.0f; if (!c->cen) return ls; ls.occluded = 1; }
         v3 e1 = sub3(ld3(T->v1), ld3(T->v0)), e2 = sub3(ld3(T->v2), ld3(T->v0));
         CS_SQRT(c, PTO_CS_LIGHT_AREA, dot3(cross3(e1, e2), cross3(e1, e2)));
@@ -665,31 +800,114 @@ static light_sample_t sample_light(const pto_scene *s, uint32_t *rng, v3 hit_pos
         ls.pdf = (inv_n * (1.0f / area)) * (dist * dist / max1(cos_t, PT_EPS));   /* :481 */
         ls.intensity = scale3(ld3(lt->color), lt->intensity);
         ls.wi = wi;
+        ls.dist = dist;
     }
     return ls;
+#undef SHADOW_ORIGIN
 }
 
 /* ------------------------------------------------------------------------- */
 /* trace — pt.wgsl:638-709                                                     */
 /* ------------------------------------------------------------------------- */
-static v3 trace(const pto_scene *s, uint32_t *rng, ray_t ray, uint32_t max_bounces, int do_mis,
+static v3 trace(const pto_scene *s, const pto_extras *ex, uint32_t *rng, ray_t ray, uint32_t max_bounces, int do_mis,
                 counters_t *c, float *log16, int *n_log) {
     v3 thr = V3(1.0f, 1.0f, 1.0f), res = V3(0.0f, 0.0f, 0.0f);
     ray_t cur = ray;
     int nl = 0;
+    /* extras (shade.hip k_shade<.., ENV, MED>): whether next-event estimation has a light, and the weight the environment's radiance
+     * takes if this segment misses: 1 for the camera ray and while the map is not sampled, else what the vertex behind it left */
+    const int have_light = s->n_lights + (env_sampled(ex) ? 1u : 0u) > 0u;
+    float W = 1.0f;
     for (uint32_t bounce = 0; bounce < max_bounces; bounce++) {
         hit_t raw;
         c->segments++;
         c->b = bounce < PTO_CENSUS_BOUNCES ? bounce : PTO_CENSUS_BOUNCES - 1u;
         CEN(c, PTO_EV_SEGMENT);
-        hitinfo_t hit = scene_intersect(s, cur, c, &raw);                    /* :644 */
+        raw = traverse(s, cur, c);                                           /* :644 (the shading state follows below) */
+        SIG(c, raw.tri);
         if (log16) {
             float *L = log16 + 16 * nl++;
             L[0] = cur.o.x; L[1] = cur.o.y; L[2] = cur.o.z; L[3] = cur.d.x; L[4] = cur.d.y; L[5] = cur.d.z;
             L[6] = thr.x; L[7] = thr.y; L[8] = thr.z; L[9] = res.x; L[10] = res.y; L[11] = res.z;
             memcpy(&L[12], rng, 4); L[13] = raw.t; memcpy(&L[14], &raw.tri, 4); L[15] = 1.0f;
         }
+        if (med_on(ex)) {
+            /* The medium first (shade.hip): one draw for the free flight iff the segment has an interval inside the box; a collision
+             * in front of the hit, or anywhere along a miss, makes the segment a scatter. The draw stays taken either way. */
+            const int is_hit = !(raw.t < 0.0f);
+            const med_interval_t iv = med_interval(ex, cur.o, cur.d, is_hit ? raw.t : INFINITY);
+            int scattered = 0;
+            float t_sc = 0.0f;
+            if (iv.b > iv.a) {
+                t_sc = iv.a + med_free_flight(ex, rng_f(rng));
+                scattered = t_sc < iv.b;
+                if (!scattered) CEN(c, PTO_EV_MED_INTERVAL_NO_SCATTER);
+                SIG(c, scattered ? 0x5C0002u : 0x5C0001u);
+            } else {
+                CEN(c, PTO_EV_MED_NO_INTERVAL);
+                SIG(c, 0x5C0000u);
+            }
+            if (scattered) {
+                CEN(c, is_hit ? PTO_EV_MED_SCATTER_BEFORE_HIT : PTO_EV_MED_SCATTER_ON_MISS);
+                if (is_hit) c->closest_hits++;
+                thr = mul3(thr, ld3(ex->albedo));
+                if (!(thr.x != 0.0f || thr.y != 0.0f || thr.z != 0.0f)) { CEN(c, PTO_EV_MED_SCATTER_THROUGHPUT_ZERO); SIG(c, 0x7E80u); break; }
+                const v3 x = madd3(cur.d, t_sc, cur.o);
+                const float g = ex->g;
+                float inv_n = 0.0f;
+                if (do_mis && have_light) {
+                    light_sample_t ls = sample_light(s, ex, 1, rng, x, c, &inv_n);
+                    if (ls.pdf > 0.0f) {
+                        const float ph = med_phase(g, dot3(cur.d, ls.wi));
+                        float wmis = power_heuristic(1.0f, ls.pdf, 1.0f, ph);
+                        v3 direct = vdiv3(scale3(scale3(ls.intensity, ph), wmis), max1(ls.pdf, PT_EPS));
+                        v3 contrib = scale3(mul3(thr, direct), med_tr(ex, x, ls.wi, ls.dist));
+                        if (contrib.x != 0.0f || contrib.y != 0.0f || contrib.z != 0.0f) CEN(c, PTO_EV_MED_WOULD_LEAVE_RECORD);
+                        else CEN(c, PTO_EV_MED_CONTRIBUTION_ZERO);
+                        SIG(c, 0xC0 | (contrib.x != 0.0f || contrib.y != 0.0f || contrib.z != 0.0f));
+                        if (!ls.occluded) res = add3(res, contrib);
+                    } else if (ls.traced) {
+                        CEN(c, PTO_EV_MED_SAMPLE_PDF_NOT_POSITIVE);
+                        SIG(c, 0xC2);
+                    }
+                }
+                const float xi1 = rng_f(rng), xi2 = rng_f(rng);
+                float ct;
+                const v3 nd = med_sample_phase(g, cur.d, xi1, xi2, &ct);     /* its density is its phase value: no factor */
+                if (bounce > 2u) {
+                    float p = max1(max1(thr.x, thr.y), thr.z);
+                    if (rng_f(rng) > p) { CEN(c, PTO_EV_MED_ROULETTE_KILL); SIG(c, 0xD1E); break; }
+                    CEN(c, PTO_EV_MED_ROULETTE_SURVIVAL);
+                    thr = vdiv3(thr, p);
+                }
+                if (bounce + 1u == max_bounces) { CEN(c, PTO_EV_MED_BOUNCE_LIMIT_END); break; }
+                cur.o = x;
+                cur.d = nd;
+                if (env_sampled(ex)) {
+                    W = 1.0f;
+                    if (inv_n != 0.0f) {
+                        CEN(c, PTO_EV_ENV_WEIGHT_AT_SCATTER);
+                        W = power_heuristic(1.0f, med_phase(g, ct), 1.0f, env_lookup(ex, nd, c).pdf * inv_n);
+                    }
+                }
+                continue;
+            }
+        }
+        hitinfo_t hit = make_hitinfo(s, cur, raw, c);
         if (hit.t < 0.0f) {                                                  /* :646-649 */
+            if (env_on(ex)) {
+                /* a miss sees the environment, the camera ray too: throughput * (W * Le); an exact zero adds nothing */
+                const v3 le = env_lookup(ex, cur.d, c).le;
+                const v3 e = V3(thr.x * (W * le.x), thr.y * (W * le.y), thr.z * (W * le.z));
+                SIG(c, 0xE0 | (e.x != 0.0f || e.y != 0.0f || e.z != 0.0f));
+                if (e.x != 0.0f || e.y != 0.0f || e.z != 0.0f) {
+                    CEN(c, W != 1.0f ? PTO_EV_MISS_SKY_WEIGHTED : PTO_EV_MISS_SKY_UNWEIGHTED);
+                    res = add3(res, e);
+                } else {
+                    CEN(c, PTO_EV_MISS_SKY_ZERO);
+                }
+                break;
+            }
             /* `result += throughput * vec3f(0.0)`: nothing for a finite throughput, NaN in every component whose
              * throughput is infinite or NaN (found by oracle/pt_literal.c, round 3; the kernels follow: shade.hip) */
             CEN(c, finite3(thr) ? PTO_EV_MISS_FINITE : PTO_EV_MISS_NONFINITE);
@@ -697,6 +915,7 @@ static v3 trace(const pto_scene *s, uint32_t *rng, ray_t ray, uint32_t max_bounc
             break;
         }
         c->closest_hits++;
+        SIG(c, 0xF0 | (hit.is_front ? 1 : 0));
         if (hit.emission.x > 0.0f || hit.emission.y > 0.0f || hit.emission.z > 0.0f) {  /* :652 */
             CEN(c, finite3(thr) ? PTO_EV_EMISSIVE_FINITE : PTO_EV_EMISSIVE_NONFINITE);
             CS_RCP(c, PTO_CS_EMISSIVE_ATTENUATION, 1.0f + hit.t * hit.t);
@@ -709,8 +928,9 @@ static v3 trace(const pto_scene *s, uint32_t *rng, ray_t ray, uint32_t max_bounc
         }
         /* :661. A scene without lights cannot be bound in the reference (WebGPU
          * rejects a zero-sized storage buffer); here it simply has no NEE. */
-        if (do_mis && s->n_lights > 0u && hit.transmission == 0.0f && hit.is_front) {
-            light_sample_t ls = sample_light(s, rng, hit.position, c);
+        float inv_n = 0.0f;                                                  /* extras: set where next-event estimation ran */
+        if (do_mis && have_light && hit.transmission == 0.0f && hit.is_front) {
+            light_sample_t ls = sample_light(s, ex, 0, rng, hit.position, c, &inv_n);
             if (ls.pdf > 0.0f) {
                 v3 Vv = neg3(normalize3(cur.d));
                 v4 ev = eval_bsdf(&hit, hit.normal, Vv, ls.wi, hit.is_front, c);
@@ -718,34 +938,50 @@ static v3 trace(const pto_scene *s, uint32_t *rng, ray_t ray, uint32_t max_bounc
                 CS_RCP(c, PTO_CS_DIRECT_PDF, max1(ls.pdf, PT_EPS));
                 v3 direct = vdiv3(scale3(mul3(ls.intensity, V3(ev.x, ev.y, ev.z)), wmis),
                                   max1(ls.pdf, PT_EPS));                     /* :674 */
+                v3 contrib = mul3(thr, direct);
+                if (med_on(ex)) {                /* the transmittance towards the light, before `shade`'s test for an exact zero */
+                    const float tr = med_tr(ex, hit.position, ls.wi, ls.dist);
+                    CEN(c, tr < 1.0f ? PTO_EV_SURFACE_NEE_TR_BELOW_ONE : PTO_EV_SURFACE_NEE_TR_ONE);
+                    contrib = scale3(contrib, tr);
+                }
+                SIG(c, 0xC0 | (contrib.x != 0.0f || contrib.y != 0.0f || contrib.z != 0.0f));
                 if (c->cen) {                /* what `shade` decides before the shadow ray is traced (shade.hip) */
-                    v3 contrib = mul3(thr, direct);
                     if (contrib.x != 0.0f || contrib.y != 0.0f || contrib.z != 0.0f) CEN(c, PTO_EV_WOULD_LEAVE_RECORD);
                     else CEN(c, PTO_EV_CONTRIBUTION_ZERO);
                     if (!finite3(contrib)) CEN(c, PTO_EV_CONTRIBUTION_NONFINITE);
                 }
-                if (!ls.occluded) res = add3(res, mul3(thr, direct));        /* :675 */
+                if (!ls.occluded) res = add3(res, contrib);                  /* :675 */
             } else if (ls.traced) {
                 CEN(c, PTO_EV_SAMPLE_PDF_NOT_POSITIVE);
+                SIG(c, 0xC2);
             }
-        } else if (do_mis && s->n_lights > 0u) {
+        } else if (do_mis && have_light) {
             CEN(c, hit.transmission != 0.0f ? PTO_EV_NEE_SKIPPED_TRANSMISSION : PTO_EV_NEE_SKIPPED_BACK_FACE);
         }
         v3 dir = sample_bsdf(rng, &hit, cur, hit.is_front, c);               /* :680 */
         v4 ev = eval_bsdf(&hit, hit.normal, neg3(normalize3(cur.d)), dir, hit.is_front, c);
-        if (ev.w <= 0.0f) break;                                             /* :685 (dead) */
+        if (ev.w <= 0.0f) { SIG(c, 0xDEAD); break; }                         /* :685 (dead) */
         cur.o = madd3(dir, PT_EPS, hit.position);                            /* :691 */
         CS_NORM(c, PTO_CS_NEXT_DIRECTION, dir);
         cur.d = normalize3(dir);                                             /* :692 */
         thr = mul3(thr, vdiv3(V3(ev.x, ev.y, ev.z), max1(ev.w, PT_EPS)));    /* :696 */
         if (bounce > 2u) {                                                   /* :699-705 */
             float p = max1(max1(thr.x, thr.y), thr.z);
-            if (rng_f(rng) > p) { CEN(c, PTO_EV_ROULETTE_KILL); break; }
+            if (rng_f(rng) > p) { CEN(c, PTO_EV_ROULETTE_KILL); SIG(c, 0xD1E); break; }
             CEN(c, PTO_EV_ROULETTE_SURVIVAL);
             CS_RCP(c, PTO_CS_ROULETTE, p);
             thr = vdiv3(thr, p);
         }
         if (bounce + 1u == max_bounces) CEN(c, PTO_EV_BOUNCE_LIMIT_END);
+        else if (env_sampled(ex)) {
+            /* what the environment's radiance weighs if this ray misses: where this vertex's next-event sample could have picked
+             * the same direction, the power heuristic of the two densities; else 1 */
+            W = 1.0f;
+            if (inv_n != 0.0f) {
+                CEN(c, PTO_EV_ENV_WEIGHT_AT_SURFACE);
+                W = power_heuristic(1.0f, ev.w, 1.0f, env_lookup(ex, cur.d, c).pdf * inv_n);
+            }
+        }
     }
     if (log16) {
         float *L = log16 + 16 * nl++;
@@ -857,8 +1093,8 @@ static double now_s(void) {
 
 /* pto_render and pto_render_census: one frame loop, one trace(). census (NULL for pto_render): PTO_EV_COUNT x 64 totals; each thread
  * counts into a table of its own (counters_t.cen) and adds it under the lock at the end. */
-static int render_impl(const pto_scene *s, const ptmi_camera *cam, uint32_t n_frames,
-                       const pto_options *opt, float *out, pto_stats *st, uint64_t *census) {
+static int render_impl(const pto_scene *s, const ptmi_camera *cam, uint32_t n_frames, const pto_options *opt,
+                       const pto_extras *ex, float *out, float *border, uint32_t *branches, pto_stats *st, uint64_t *census) {
     uint32_t W = cam->width, H = cam->height;
     uint32_t y0 = opt ? opt->y0 : 0u, y1 = (opt && opt->y1) ? opt->y1 : H;
     uint32_t maxb = opt ? opt->max_bounces : 8u;
@@ -879,11 +1115,16 @@ static int render_impl(const pto_scene *s, const ptmi_camera *cam, uint32_t n_fr
         for (int64_t y = y0; y < (int64_t)y1; y++) {
             for (uint32_t x = 0; x < W; x++) {
                 float *px = out + ((size_t)y * W + x) * 4;                   /* :753 */
+                float near_border = INFINITY;
+                uint32_t pixel_sig = 0u;
                 for (uint32_t k = 0; k < n_frames; k++) {
                     uint32_t frame = cam->frame_index + k;
                     uint32_t rng;
                     ray_t r = camera_ray(cam, x, (uint32_t)y, frame, &rng);
-                    v3 col = trace(s, &rng, r, maxb, do_mis, &c, NULL, NULL);
+                    c.border = INFINITY; c.sig = 0u;
+                    v3 col = trace(s, ex, &rng, r, maxb, do_mis, &c, NULL, NULL);
+                    near_border = min1(near_border, c.border);
+                    pixel_sig = pixel_sig * 31u + c.sig;
                     col = V3(min1(col.x, 2.5f), min1(col.y, 2.5f), min1(col.z, 2.5f));  /* :751 */
                     if (frame > 0u) {                                        /* :754-759 */
                         float t = 1.0f / (float)(frame + 1u);
@@ -891,6 +1132,8 @@ static int render_impl(const pto_scene *s, const ptmi_camera *cam, uint32_t n_fr
                     }
                     px[0] = col.x; px[1] = col.y; px[2] = col.z; px[3] = 0.0f;   /* :761 */
                 }
+                if (border) border[(size_t)y * W + x] = near_border;
+                if (branches) branches[(size_t)y * W + x] = pixel_sig;
             }
         }
 #pragma omp critical
@@ -914,13 +1157,23 @@ static int render_impl(const pto_scene *s, const ptmi_camera *cam, uint32_t n_fr
 
 int pto_render(const pto_scene *s, const ptmi_camera *cam, uint32_t n_frames,
                const pto_options *opt, float *out, pto_stats *st) {
-    return render_impl(s, cam, n_frames, opt, out, st, NULL);
+    return render_impl(s, cam, n_frames, opt, NULL, out, NULL, NULL, st, NULL);
+}
+int pto_render_ext(const pto_scene *s, const ptmi_camera *cam, uint32_t n_frames, const pto_options *opt, const pto_extras *ex,
+                   float *out, float *border, uint32_t *branches, pto_stats *st) {
+    return render_impl(s, cam, n_frames, opt, ex, out, border, branches, st, NULL);
 }
 int pto_render_census(const pto_scene *s, const ptmi_camera *cam, uint32_t n_frames,
                       const pto_options *opt, float *out, pto_stats *st, uint64_t *census) {
     if (!census) return -1;
     memset(census, 0, sizeof(uint64_t) * PTO_EV_COUNT * PTO_CENSUS_BOUNCES);
-    return render_impl(s, cam, n_frames, opt, out, st, census);
+    return render_impl(s, cam, n_frames, opt, NULL, out, NULL, NULL, st, census);
+}
+int pto_render_census_ext(const pto_scene *s, const ptmi_camera *cam, uint32_t n_frames, const pto_options *opt, const pto_extras *ex,
+                          float *out, float *border, uint32_t *branches, pto_stats *st, uint64_t *census) {
+    if (!census) return -1;
+    memset(census, 0, sizeof(uint64_t) * PTO_EV_COUNT * PTO_CENSUS_BOUNCES);
+    return render_impl(s, cam, n_frames, opt, ex, out, border, branches, st, census);
 }
 
 static const char *const census_names[PTO_EV_COUNT] = {
@@ -958,7 +1211,7 @@ uint64_t pto_render_tap(const pto_scene *s, const ptmi_camera *cam, uint32_t n_f
                 for (uint32_t k = 0; k < n_frames; k++) {
                     uint32_t rng;
                     ray_t r = camera_ray(cam, x, (uint32_t)y, cam->frame_index + k, &rng);
-                    (void)trace(s, &rng, r, maxb, do_mis, &c, NULL, NULL);
+                    (void)trace(s, NULL, &rng, r, maxb, do_mis, &c, NULL, NULL);
                 }
     }
     return n;
@@ -966,23 +1219,29 @@ uint64_t pto_render_tap(const pto_scene *s, const ptmi_camera *cam, uint32_t n_f
 
 /* one path of pixel (x, y) at `frame`: what pto_trace_path and pto_trace_paths both report */
 static v3 trace_one(const pto_scene *s, const ptmi_camera *cam, uint32_t x, uint32_t y, uint32_t frame, const pto_options *opt,
-                    counters_t *c, float *log16, int *n_log) {
+                    const pto_extras *ex, counters_t *c, float *log16, int *n_log) {
     uint32_t rng;
     ray_t r = camera_ray(cam, x, y, frame, &rng);
-    return trace(s, &rng, r, opt ? opt->max_bounces : 8u, opt ? (int)opt->do_mis : 1, c, log16, n_log);
+    c->border = INFINITY; c->sig = 0u;
+    return trace(s, ex, &rng, r, opt ? opt->max_bounces : 8u, opt ? (int)opt->do_mis : 1, c, log16, n_log);
 }
 
-int pto_trace_path(const pto_scene *s, const ptmi_camera *cam, uint32_t x, uint32_t y,
-                   uint32_t frame, const pto_options *opt, float *radiance3, float *log16) {
+int pto_trace_path_ext(const pto_scene *s, const ptmi_camera *cam, uint32_t x, uint32_t y, uint32_t frame, const pto_options *opt,
+                       const pto_extras *ex, float *radiance3, float *log16) {
     counters_t c; memset(&c, 0, sizeof c);
     int nl = 0;
-    v3 col = trace_one(s, cam, x, y, frame, opt, &c, log16, &nl);
+    v3 col = trace_one(s, cam, x, y, frame, opt, ex, &c, log16, &nl);
     radiance3[0] = col.x; radiance3[1] = col.y; radiance3[2] = col.z;
     return nl;
 }
+int pto_trace_path(const pto_scene *s, const ptmi_camera *cam, uint32_t x, uint32_t y,
+                   uint32_t frame, const pto_options *opt, float *radiance3, float *log16) {
+    return pto_trace_path_ext(s, cam, x, y, frame, opt, NULL, radiance3, log16);
+}
 
-int pto_trace_paths(const pto_scene *s, const ptmi_camera *cam, uint64_t n, const uint32_t *xs, const uint32_t *ys,
-                    const uint32_t *frames, const pto_options *opt, float *radiance3, uint32_t *segments) {
+int pto_trace_paths_ext(const pto_scene *s, const ptmi_camera *cam, uint64_t n, const uint32_t *xs, const uint32_t *ys,
+                        const uint32_t *frames, const pto_options *opt, const pto_extras *ex, float *radiance3, uint32_t *segments,
+                        float *border, uint32_t *branches) {
     int nthreads = 1;
 #ifdef _OPENMP
     nthreads = (opt && opt->threads) ? (int)opt->threads : omp_get_max_threads();
@@ -990,9 +1249,55 @@ int pto_trace_paths(const pto_scene *s, const ptmi_camera *cam, uint64_t n, cons
 #pragma omp parallel for schedule(dynamic, 256) num_threads(nthreads)
     for (int64_t i = 0; i < (int64_t)n; i++) {
         counters_t c; memset(&c, 0, sizeof c);
-        v3 col = trace_one(s, cam, xs[i], ys[i], frames[i], opt, &c, NULL, NULL);
+        v3 col = trace_one(s, cam, xs[i], ys[i], frames[i], opt, ex, &c, NULL, NULL);
         radiance3[3 * i] = col.x; radiance3[3 * i + 1] = col.y; radiance3[3 * i + 2] = col.z;
         if (segments) segments[i] = (uint32_t)c.segments;
+        if (border) border[i] = c.border;
+        if (branches) branches[i] = c.sig;
+    }
+    return 0;
+}
+int pto_trace_paths(const pto_scene *s, const ptmi_camera *cam, uint64_t n, const uint32_t *xs, const uint32_t *ys,
+                    const uint32_t *frames, const pto_options *opt, float *radiance3, uint32_t *segments) {
+    return pto_trace_paths_ext(s, cam, n, xs, ys, frames, opt, NULL, radiance3, segments, NULL, NULL);
+}
+
+/* the extras' functions on given inputs (pt_oracle.h pto_ext_probe) */
+int pto_ext_probe(const pto_extras *ex, int op, uint32_t n, const float *in, float *out) {
+    counters_t c; memset(&c, 0, sizeof c);
+    if (!ex) return -1;
+    if ((op == PTO_PROBE_ENV_SAMPLE && !(env_on(ex) && ex->env_prob && ex->env_alias)) || (op == PTO_PROBE_ENV_LOOKUP && !env_on(ex))) return -1;
+    for (uint32_t i = 0; i < n; i++) {
+        const float *a = in + 8 * (size_t)i;
+        float *o = out + 8 * (size_t)i;
+        memset(o, 0, 8 * sizeof(float));
+        switch (op) {
+        case PTO_PROBE_MED_STEP: {          /* in: o, d, t_hit, r; out: a, b, s (0 without an interval), scattered, the scatter point */
+            med_interval_t iv = med_interval(ex, ld3(a), ld3(a + 3), a[6]);
+            o[0] = iv.a; o[1] = iv.b;
+            if (iv.b > iv.a) {
+                o[2] = med_free_flight(ex, a[7]);
+                const float t_sc = iv.a + o[2];
+                if (t_sc < iv.b) { v3 x = madd3(ld3(a + 3), t_sc, ld3(a)); o[3] = 1.0f; o[4] = x.x; o[5] = x.y; o[6] = x.z; }
+            }
+            break; }
+        case PTO_PROBE_MED_TR: o[0] = med_tr(ex, ld3(a), ld3(a + 3), a[6]); break;      /* in: o, wi, dist */
+        case PTO_PROBE_MED_PHASE: {         /* in: d, xi1, xi2; out: direction, sampled cosine, its phase value */
+            float ct; v3 nd = med_sample_phase(ex->g, ld3(a), a[3], a[4], &ct);
+            o[0] = nd.x; o[1] = nd.y; o[2] = nd.z; o[3] = ct; o[4] = med_phase(ex->g, ct);
+            break; }
+        case PTO_PROBE_ENV_SAMPLE: {        /* in: r1..r4; out: direction, radiance, density, texel (bits) */
+            v3 d; uint32_t t; env_sample_t es = env_sample(ex, a[0], a[1], a[2], a[3], &d, &t);
+            o[0] = d.x; o[1] = d.y; o[2] = d.z; o[3] = es.le.x; o[4] = es.le.y; o[5] = es.le.z; o[6] = es.pdf; memcpy(&o[7], &t, 4);
+            break; }
+        case PTO_PROBE_ENV_LOOKUP: {        /* in: d; out: radiance, density, texel (bits), distance from a texel border */
+            c.border = INFINITY;
+            v3 d = ld3(a); uint32_t t = env_texel(ex, d, &c);
+            env_sample_t es = env_lookup(ex, d, &c);
+            o[0] = es.le.x; o[1] = es.le.y; o[2] = es.le.z; o[3] = es.pdf; memcpy(&o[4], &t, 4); o[5] = c.border;
+            break; }
+        default: return -1;
+        }
     }
     return 0;
 }

@@ -2,7 +2,8 @@
  * pt_oracle.h — CPU oracle for the path-tracing hot path (TEST INFRASTRUCTURE).
  *
  * A scalar f32 restatement of the reference's compute shader
- * (reference: src/shader/pt.wgsl + src/shader/random.wgsl). It is the checker
+ * (reference: src/shader/pt.wgsl + src/shader/random.wgsl), plus, as optional extras the reference does not have (pto_extras
+ * below), the environment map and the participating medium of include/ptmi.h as the kernels implement them. It is the checker
  * the HIP path is compared against and the timed CPU baseline of bench.py.
  * It is NOT part of the product: nothing under wgpu-path-tracing_amd/ links,
  * loads or calls it. Only tests/, __graft_entry__.smoke() and bench.py's
@@ -141,6 +142,29 @@ int pto_render(const pto_scene *s, const ptmi_camera *cam, uint32_t n_frames,
     X(PTO_EV_ROULETTE_KILL, "roulette_kill") \
     X(PTO_EV_ROULETTE_SURVIVAL, "roulette_survival") \
     X(PTO_EV_BOUNCE_LIMIT_END, "bounce_limit_end") \
+    X(PTO_EV_MED_NO_INTERVAL, "med_no_interval") \
+    X(PTO_EV_MED_INTERVAL_NO_SCATTER, "med_interval_no_scatter") \
+    X(PTO_EV_MED_SCATTER_BEFORE_HIT, "med_scatter_before_hit") \
+    X(PTO_EV_MED_SCATTER_ON_MISS, "med_scatter_on_miss") \
+    X(PTO_EV_MED_SCATTER_THROUGHPUT_ZERO, "med_scatter_throughput_zero") \
+    X(PTO_EV_MED_NEE_DIRECTIONAL, "med_nee_directional") \
+    X(PTO_EV_MED_NEE_POINT, "med_nee_point") \
+    X(PTO_EV_MED_NEE_EMISSIVE, "med_nee_emissive") \
+    X(PTO_EV_MED_NEE_ENV, "med_nee_env") \
+    X(PTO_EV_MED_CONTRIBUTION_ZERO, "med_contribution_zero") \
+    X(PTO_EV_MED_SAMPLE_PDF_NOT_POSITIVE, "med_sample_pdf_not_positive") \
+    X(PTO_EV_MED_WOULD_LEAVE_RECORD, "med_would_leave_record") \
+    X(PTO_EV_MED_ROULETTE_KILL, "med_roulette_kill") \
+    X(PTO_EV_MED_ROULETTE_SURVIVAL, "med_roulette_survival") \
+    X(PTO_EV_MED_BOUNCE_LIMIT_END, "med_bounce_limit_end") \
+    X(PTO_EV_SURFACE_NEE_TR_BELOW_ONE, "surface_nee_tr_below_one") \
+    X(PTO_EV_SURFACE_NEE_TR_ONE, "surface_nee_tr_one") \
+    X(PTO_EV_NEE_ENV, "nee_env") \
+    X(PTO_EV_MISS_SKY_WEIGHTED, "miss_sky_weighted") \
+    X(PTO_EV_MISS_SKY_UNWEIGHTED, "miss_sky_unweighted") \
+    X(PTO_EV_MISS_SKY_ZERO, "miss_sky_zero") \
+    X(PTO_EV_ENV_WEIGHT_AT_SURFACE, "env_weight_at_surface") \
+    X(PTO_EV_ENV_WEIGHT_AT_SCATTER, "env_weight_at_scatter") \
     X(PTO_CS_GEO_NORMAL, "cs_geo_normal") \
     X(PTO_CS_VERTEX_NORMAL, "cs_vertex_normal") \
     X(PTO_CS_UV_DET, "cs_uv_det") \
@@ -180,6 +204,62 @@ int pto_render_census(const pto_scene *s, const ptmi_camera *cam, uint32_t n_fra
                       const pto_options *opt, float *out_rgba, pto_stats *st, uint64_t *census);
 int pto_census_event_count(void);
 const char *pto_census_event_name(int ev);
+
+/* ---- extras: the environment map and the participating medium ------------------------------------------------------------------
+ * NOT a restatement of the reference, which has no sky and no fog: they restate include/ptmi.h §environment and §medium as the
+ * `shade` kernel implements them (csrc/shade.hip k_shade<.., ENV, MED>, csrc/pt_env.h, csrc/pt_medium.h), statement by statement,
+ * inside the same trace() as everything above. With ex = NULL, or neither part present, every *_ext entry point is its plain
+ * namesake bit for bit, census included. Inside the arithmetic contract: everything but logf, expf (free flight, transmittance)
+ * and atan2f, acosf (the sky lookup), which are libm's here and the device library's there, 1 - 2 ulp apart.
+ *
+ * Environment (env_texels != NULL): texels (r, g, b, c) per texel, row 0 at the +Y pole, c the texel's density over (u, v); the
+ * alias table (prob, alias) per entry. The tables are inputs (ptmi_debug_env_table builds them; intensity and rotation as
+ * ptmi_upload_environment resolves them: intensity not 0, |rotation| <= pi). env_sampled: 1 = it is light number n_lights for
+ * next-event estimation and bounce rays carry an MIS weight; 0 = looked up only.
+ * Medium (med_on != 0): ptmi_medium's fields.
+ * ulp_nudge: every result of logf, expf, atan2f and acosf inside the extras is moved by this many float32 steps (0: the reference);
+ * for measuring what a 1 - 2 ulp library may change, nothing else.
+ *
+ * border (may be NULL), per pixel (renders, the smallest over the pixel's frames) or per path: the smallest distance of any sky
+ * lookup of the path, at a miss or for a bounce ray's weight, from a texel border, in texels (of u w and v h); +inf without a
+ * lookup. Which texel a direction that close to a border reads is the device's atan2f / acosf's to decide.
+ *
+ * branches (may be NULL), per pixel (over its frames) or per path: one word hashed from every decision of the path that is not
+ * arithmetic: the triangle each segment hit, interval and scatter, the light picked, whether its sample was occluded, dropped or
+ * left a record, the lobe, reflection or refraction, roulette, the sky texel read. Two runs (two values of ulp_nudge) with equal
+ * words took the same branches and differ by rounding alone; with different words some path went another way.
+ *
+ * Census: the med_*, surface_nee_tr_*, nee_env, miss_sky_* and env_weight_* events are counted only with extras present. A scatter
+ * counts `segment` and the med_* events and none of the surface's; under a map a miss counts miss_sky_* instead of miss_*finite;
+ * would_leave_record / contribution_zero at a surface are taken after the transmittance, as `shade` takes them. The GPU's figures:
+ * shadow_rays = sum of nee_* and med_nee_* minus point_light_beyond_100; shadow_traced = would_leave_record + med_would_leave_record. */
+typedef struct pto_extras {
+    const float *env_texels; const float *env_prob; const uint32_t *env_alias;
+    uint32_t env_w, env_h, env_sampled;
+    float env_intensity, env_rotation;
+    uint32_t med_on;
+    float sigma_t, albedo[3], g, box_min[3], box_max[3];
+    int32_t ulp_nudge;
+} pto_extras;
+int pto_render_ext(const pto_scene *s, const ptmi_camera *cam, uint32_t n_frames, const pto_options *opt, const pto_extras *ex,
+                   float *out_rgba, float *border, uint32_t *branches, pto_stats *st);
+int pto_render_census_ext(const pto_scene *s, const ptmi_camera *cam, uint32_t n_frames, const pto_options *opt, const pto_extras *ex,
+                          float *out_rgba, float *border, uint32_t *branches, pto_stats *st, uint64_t *census);
+/* pto_trace_path / pto_trace_paths with extras. A scatter's log record is a segment's like any other: its hit t and triangle are
+ * what the traversal found behind the scatter point. */
+int pto_trace_path_ext(const pto_scene *s, const ptmi_camera *cam, uint32_t x, uint32_t y, uint32_t frame, const pto_options *opt,
+                       const pto_extras *ex, float *radiance3, float *log16);
+int pto_trace_paths_ext(const pto_scene *s, const ptmi_camera *cam, uint64_t n, const uint32_t *xs, const uint32_t *ys,
+                        const uint32_t *frames, const pto_options *opt, const pto_extras *ex, float *radiance3, uint32_t *segments,
+                        float *border, uint32_t *branches);
+/* The extras' functions on n inputs of 8 floats each, 8 floats out each (unused ones zero):
+ *   MED_STEP   in o.xyz, d.xyz, t_hit, r     out a, b, s (free flight; 0 without an interval), scattered (0 / 1), scatter point.xyz
+ *   MED_TR     in o.xyz, wi.xyz, dist        out Tr
+ *   MED_PHASE  in d.xyz, xi1, xi2            out direction.xyz, sampled cosine, its phase value
+ *   ENV_SAMPLE in r1, r2, r3, r4             out direction.xyz, radiance.rgb, density, texel (bits)
+ *   ENV_LOOKUP in d.xyz                      out radiance.rgb, density, texel (bits), distance from a texel border */
+enum { PTO_PROBE_MED_STEP = 0, PTO_PROBE_MED_TR = 1, PTO_PROBE_MED_PHASE = 2, PTO_PROBE_ENV_SAMPLE = 3, PTO_PROBE_ENV_LOOKUP = 4 };
+int pto_ext_probe(const pto_extras *ex, int op, uint32_t n, const float *in, float *out);
 
 /* Every ray a render traces, with the traversal's result (for tools that replay real rays through another traversal):
  * rec9[9 i ..] = o.xyz, d.xyz, dist (0: closest-hit ray; < 0: shadow ray to a directional light; > 0: shadow ray, the light's

@@ -3,6 +3,9 @@ sampling weights and probabilities, c_t, the lookup of a direction and the sampl
 import numpy as np
 
 EPS = 1e-6
+# A direction whose u W or v H lies this close to a whole number, in texels, may read either texel: which one is the device's atan2f /
+# acosf's to decide (outside the arithmetic contract). Tests set such lookups aside.
+BORDER_BAND = 1e-4
 
 
 def weights(texels):

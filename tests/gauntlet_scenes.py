@@ -155,6 +155,121 @@ def gauntlet_lights():
 SCENES = {"gauntlet_materials": gauntlet_materials, "gauntlet_lights": gauntlet_lights}
 
 
+# ---- the fog / sky gauntlet: the branches of `shade`'s ENV and MED instantiations (tests/test_oracle_extras_host.py holds the coverage
+# condition, tests/test_gpu_shade_extras.py compares these renders with the oracle's extras) ----
+def gauntlet_fog():
+    """The room with openings in the back wall and the ceiling (misses at every bounce, the camera ray's too), well-behaved materials
+    (no roughness below 0.3 on an opaque surface: a rounding of the scatter point must stay a rounding of the radiance), a glass box
+    inside the fog, an emissive patch, a point and a directional light (the API's two punctual kinds; with the emissive triangles
+    every kind of light record), a point light of intensity 0 (a sample whose contribution is exactly zero) and an emissive
+    triangle at 1e31 that is never hit (its area overflows: a sample whose pdf is NaN)."""
+    M = scenes._material
+    mats = [
+        M((0.9, 0.9, 0.9)),                                                      # 0 bright wall: paths live long
+        M((0.8, 0.8, 0.8), emission=(1.0, 0.9, 0.8), strength=3.0),              # 1 lights
+        M((0.9, 0.85, 0.8), metallic=0.6, roughness=0.35),                       # 2
+        M((0.95, 1.0, 0.95), roughness=0.3, transmission=1.0, ior=1.5),          # 3 glass
+        M((0.85, 0.3, 0.3), roughness=0.6),                                      # 4
+    ]
+    variants = [(0, "keep", "keep")] * 3 + [(2, "keep", "keep"), (4, "keep", "keep")]
+    parts = _patch_room(variants, 4, holes={(0, 1, 1), (0, 2, 1), (0, 1, 2), (0, 2, 2), (5, 0, 3), (5, 1, 3), (5, 3, 0), (1, 0, 3)})
+    parts.append(scenes._quad((-0.3, 1.999, -0.3), (0.3, 1.999, -0.3), (0.3, 1.999, 0.3), (-0.3, 1.999, 0.3), (0, -1, 0), 1))
+    parts.append(scenes._box((-0.25, 0.45, -0.3), (0.45, 0.7, 0.45), 3))        # inside the fog box
+    parts.append(scenes._box((0.75, 0.3, 0.7), (0.3, 0.6, 0.3), 2))             # outside it
+    far = scenes._tri_array(np.array([[(1e31, 1e31, -1e31), (1.00001e31, 1e31, -1e31), (1e31, 1.00001e31, -1e31)]], np.float32),
+                            np.zeros((1, 3, 3), np.float32), np.zeros((1, 3, 2), np.float32), 1)
+    parts.append(far)
+    punctual = np.zeros(3, layout.LIGHT)
+    for k, (pos, typ, inten) in enumerate([((0.3, 1.5, 0.2), layout.LIGHT_POINT, 1.2), ((0.3, -1.0, 0.25), layout.LIGHT_DIRECTIONAL, 0.8),
+                                           ((-0.5, 1.0, 0.6), layout.LIGHT_POINT, 0.0)]):
+        punctual[k]["position"], punctual[k]["light_type"] = pos, typ
+        punctual[k]["color"], punctual[k]["intensity"] = (1.0, 0.95, 0.9), inten
+    return _finish("gauntlet_fog", parts, mats, punctual)
+
+
+FOG_BOX = ((-0.7, 0.0, -1.25), (0.65, 1.45, 0.5))         # a part of the room, and a little beyond the back wall's opening
+FOG_CAMERA_INSIDE = dict(position=(0.1, 0.95, 0.3), forward=(0.0, 0.0, -1.0), fov=1.9)      # CAMERA stands outside it
+FOG_SKY_INTENSITY, FOG_SKY_ROTATION = 0.5, 0.7
+
+
+def fog_sky(W=16, H=8):
+    """a small non-uniform map: every texel its own radiance, a quarter of them black (never sampled; a miss that adds nothing), two bright"""
+    rng = np.random.default_rng(29)
+    t = np.ones((H, W, 4), np.float32)
+    t[..., :3] = rng.random((H, W, 3), np.float32) * 1.5 + 0.05
+    t[rng.random((H, W)) < 0.25, :3] = 0.0
+    t[1, 5, :3], t[2, 12, :3] = (9.0, 8.0, 7.0), (4.0, 5.0, 6.0)
+    return t
+
+
+# feature states: what is in place (sky: None / "lookup" / "sampled"; fog: None or the medium), and where the camera stands
+_FOG = dict(sigma_t=1.6, albedo=(0.9, 0.0, 0.8), g=0.4, box=FOG_BOX)
+FOG_STATES = {
+    "sky_lookup": dict(sky="lookup", fog=None, camera=CAMERA),
+    "sky_sampled": dict(sky="sampled", fog=None, camera=CAMERA),
+    "fog": dict(sky=None, fog=_FOG, camera=CAMERA),
+    "fog_sky_sampled": dict(sky="sampled", fog=_FOG, camera=FOG_CAMERA_INSIDE),
+    "fog_black": dict(sky="lookup", fog=dict(_FOG, albedo=(0.0, 0.0, 0.0)), camera=FOG_CAMERA_INSIDE),   # every scatter ends its path
+}
+FOG_GPU_STATES = ["sky_lookup", "sky_sampled", "fog", "fog_sky_sampled"]
+# Fewer than FRAMES, for the shares of pixels the comparisons set aside, which must stay under 1 %: with 8 frames 1.1 % (sky sampled) of the
+# pixels have a lookup within env_ref.BORDER_BAND of a texel border — a sampled sky is looked up at every vertex for the bounce ray's
+# weight —, and with 4 frames 1.0 % (fog and sky, 8 bounces) have a path that takes another branch when logf / expf / atan2f / acosf move by
+# 2 ulp; 2 frames give 0.3 % and 0.5 % (tests/test_oracle_extras_host.py prints and holds both)
+FOG_FRAMES = 2
+
+
+def fog_camera(state, width=SIZE[0], height=SIZE[1]):
+    return layout.make_camera(width, height, **FOG_STATES[state]["camera"])
+
+
+def fog_env(state, env_table):
+    """the environment of a state as Oracle.extras takes it (env_table: native.env_table), or None"""
+    kind = FOG_STATES[state]["sky"]
+    if kind is None:
+        return None
+    t = fog_sky()
+    c, prob, alias, _ = env_table(t)
+    return dict(texels=t, c=c, prob=prob, alias=alias, intensity=FOG_SKY_INTENSITY, rotation=FOG_SKY_ROTATION, sampled=int(kind == "sampled"))
+
+
+def fog_gpu_cases():
+    """Option sets of tests/test_gpu_shade_extras.py, the same for every state: bounce limits 1, at the repack bounce (no roulette
+    yet), one and two above it (roulette on the last bounce; one bounce from the repacked arrays) and 8; both sides of emit_records;
+    both traversal picks; the bounce-0 instantiation with planes; one frame and many per batch; a row range ending in a partial wave."""
+    rb = repack_bounce()
+    auto, glob = 0, 1
+    c = lambda mb, overlap, trav, planes, fpb, tile=False: dict(max_bounces=mb, overlap=overlap, traversal=trav, planes=planes,
+                                                               frames_per_batch=fpb, tile=tile)
+    return [c(1, 0, auto, False, 0), c(1, 2, glob, True, 1), c(rb, 2, auto, True, 0), c(rb, 0, glob, False, 1),
+            c(rb + 1, 0, auto, True, 1), c(rb + 2, 2, glob, False, 1), c(8, 2, glob, False, 0), c(8, 0, auto, True, 1),
+            c(8, 2, auto, False, 0, tile=True)]
+
+
+def fog_oracle_renders():
+    return sorted({(c["max_bounces"], c["tile"]) for c in fog_gpu_cases()})
+
+
+def render_fog(oracle, scene, state, env_table, max_bounces, tile, threads=0, ulp_nudge=0, frames=None, do_mis=1):
+    """(image, stats, border, census) of one state's render through the oracle's extras"""
+    if tile:
+        cam, (y0, y1) = fog_camera(state, TILE_CASE["width"], TILE_CASE["height"]), TILE_CASE["rows"]
+    else:
+        cam, (y0, y1) = fog_camera(state), (0, 0)
+    ex = oracle.extras(fog_env(state, env_table), FOG_STATES[state]["fog"], ulp_nudge)
+    return oracle.render_census_ext(scene, cam, FOG_FRAMES if frames is None else frames, ex, max_bounces=max_bounces, do_mis=do_mis,
+                                    y0=y0, y1=y1, threads=threads)
+
+
+def gpu_figures_ext(census, max_bounces):
+    """gpu_figures with the extras' events: samples at scatter points and of the environment are shadow rays like any other"""
+    nee = sum(census[k] for k in ("nee_directional", "nee_point", "nee_emissive", "nee_env", "med_nee_directional", "med_nee_point",
+                                  "med_nee_emissive", "med_nee_env"))
+    return dict(segments_by_bounce=[int(v) for v in census["segment"][:min(max_bounces, 64)]],
+                shadow_rays=int(nee.sum() - census["point_light_beyond_100"].sum()),
+                shadow_traced=int(census["would_leave_record"].sum() + census["med_would_leave_record"].sum()))
+
+
 # ---- the renders of tests/test_gpu_shade_census.py; the coverage condition of tests/test_shade_census_host.py is over their union ----
 def repack_bounce():
     """the first bounce that plays Russian roulette (pt.wgsl:699 `bounce > 2`; csrc/pt_device.h pt_repack_bounce): from the next
@@ -211,3 +326,35 @@ def gpu_figures(census, max_bounces):
     return dict(segments_by_bounce=[int(v) for v in census["segment"][:min(max_bounces, 64)]],
                 shadow_rays=int(nee.sum() - census["point_light_beyond_100"].sum()),
                 shadow_traced=int(census["would_leave_record"].sum()))
+
+
+# ---- what the device's logf / expf / atan2f / acosf, 1 - 2 ulp from libm's, may change in a render with fog: measured on the oracle ----
+NUDGES = (-2, -1, 1, 2)
+FLIP_FROM = 1e-2          # no pixel whose paths all kept their branches comes within a factor 100 of this deviation
+
+
+def pixel_deviation(img, ref):
+    """(H, W): per pixel the largest |img - ref| / max(|ref|, 1) of the three channels (medium_ref.deviation's scale)"""
+    a, r = np.asarray(img)[..., :3].astype(np.float64), np.asarray(ref)[..., :3].astype(np.float64)
+    assert np.isfinite(a).all() and np.isfinite(r).all()
+    return (np.abs(a - r) / np.maximum(np.abs(r), 1.0)).max(axis=-1)
+
+
+def rendered_rows(tile):
+    return slice(*TILE_CASE["rows"]) if tile else slice(None)
+
+
+def nudge_study(oracle, scene, state, env_table, max_bounces, tile, threads=0):
+    """One render of a fog state with ulp_nudge 0 (the reference) and with every value of NUDGES: dict(ref, stats, border, census of the
+    reference; dev (H, W): the largest deviation of any variant; flips: the pixels where a path of some variant took another branch
+    than the reference's, by the oracle's hash of a path's decisions (pto_render_ext's `branches`), whatever that did to the pixel;
+    drift: the largest deviation of the others, which is rounding)"""
+    ref, st, border, cen = render_fog(oracle, scene, state, env_table, max_bounces, tile, threads)
+    branches = oracle.last_branches
+    dev, flips = np.zeros(ref.shape[:2]), np.zeros(ref.shape[:2], bool)
+    for k in NUDGES:
+        img = render_fog(oracle, scene, state, env_table, max_bounces, tile, threads, ulp_nudge=k)[0]
+        dev = np.maximum(dev, pixel_deviation(img, ref))
+        flips |= oracle.last_branches != branches
+    ref.setflags(write=False)
+    return dict(ref=ref, stats=st, border=border, census=cen, dev=dev, flips=flips, drift=float(dev[~flips].max()))

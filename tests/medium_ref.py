@@ -19,7 +19,7 @@ class Medium:
 
 
 def interval(m, o, d, t_hit, dtype=np.float64):
-    """(near, far, a, b) per ray; fmin / fmax drop the NaN of 0 * inf. No interval: NOT b > a."""
+    """(near, far, a, b) per ray; fmin / fmax drop the NaN of 0 * inf. No interval: NOT b > a; a ray that is NaN on every axis has none."""
     o, d, t_hit = np.asarray(o, np.float32).astype(dtype), np.asarray(d, np.float32).astype(dtype), np.asarray(t_hit, np.float32).astype(dtype)
     lo, hi = m.box_min.astype(dtype), m.box_max.astype(dtype)
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -27,7 +27,8 @@ def interval(m, o, d, t_hit, dtype=np.float64):
         t1, t2 = (lo - o) * inv, (hi - o) * inv
     near = np.fmax(np.fmax(np.fmin(t1, t2)[:, 0], np.fmin(t1, t2)[:, 1]), np.fmin(t1, t2)[:, 2])
     far = np.fmin(np.fmin(np.fmax(t1, t2)[:, 0], np.fmax(t1, t2)[:, 1]), np.fmax(t1, t2)[:, 2])
-    return near, far, np.fmax(near, dtype(0.0)), np.fmin(far, t_hit)
+    a = np.fmax(near, dtype(0.0))
+    return near, far, a, np.where(np.isnan(far), a, np.fmin(far, t_hit))
 
 
 def free_flight(m, r, dtype=np.float64):
@@ -111,6 +112,14 @@ PROBE_SEED = 5
 # each times 4, which leaves room for the device's logf / expf being 1 - 2 ulp and for its fused multiply-adds.
 MEASURED_GEOM, MEASURED_DIR, MEASURED_PDF = 7.86e-7, 3.50e-5, 2.28e-6
 TOL_GEOM, TOL_DIR, TOL_PDF = 4.0 * MEASURED_GEOM, 4.0 * MEASURED_DIR, 4.0 * MEASURED_PDF
+# A whole render in fog against the CPU oracle's (tests/test_gpu_shade_extras.py): the largest deviation of a pixel, |difference| /
+# max(|value|, 1) per channel, between the oracle's renders of the fog / sky gauntlet (tests/gauntlet_scenes.py: the two states with fog, every
+# bounce limit of fog_gpu_cases, FOG_FRAMES frames) with every result of logf / expf / atan2f / acosf moved by -2 .. 2 float32 steps and
+# the render with none moved, over the pixels none of whose paths took another branch for it (the oracle's hash of a path's decisions
+# tells; those pixels, some 20 of 3 072 a render, deviate by anything from 1e-9 to 0.08). tests/test_oracle_extras_host.py measures it
+# again without a GPU and holds the constant to it. Times 4.
+MEASURED_SHADE = 7.52e-6
+TOL_SHADE = 4.0 * MEASURED_SHADE
 
 
 def unit(v):

@@ -36,6 +36,17 @@ class PtoStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class PtoExtras(ctypes.Structure):
+    _fields_ = [("env_texels", ctypes.c_void_p), ("env_prob", ctypes.c_void_p), ("env_alias", ctypes.c_void_p),
+                ("env_w", ctypes.c_uint32), ("env_h", ctypes.c_uint32), ("env_sampled", ctypes.c_uint32),
+                ("env_intensity", ctypes.c_float), ("env_rotation", ctypes.c_float),
+                ("med_on", ctypes.c_uint32), ("sigma_t", ctypes.c_float), ("albedo", ctypes.c_float * 3), ("g", ctypes.c_float),
+                ("box_min", ctypes.c_float * 3), ("box_max", ctypes.c_float * 3), ("ulp_nudge", ctypes.c_int32)]
+
+
+PROBE_MED_STEP, PROBE_MED_TR, PROBE_MED_PHASE, PROBE_ENV_SAMPLE, PROBE_ENV_LOOKUP = range(5)
+
+
 def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
 
@@ -192,6 +203,96 @@ class Oracle:
         rc = fn(ctypes.byref(s), _ptr(cam), n, _ptr(xs), _ptr(ys), _ptr(frames), ctypes.byref(opt), _ptr(rad), _ptr(seg))
         assert rc == 0
         return rad, seg
+
+    # -- extras: the environment and the medium (oracle/pt_oracle.h pto_extras) ---------------------------------------------
+    @staticmethod
+    def extras(env=None, medium=None, ulp_nudge=0):
+        """pto_extras, and the arrays it points into (keep both alive for the call).
+        env: dict(texels (H, W, 4) float32 with alpha, c (H, W), prob, alias — the last three from native.env_table —, intensity,
+        rotation, sampled) or None; medium: dict(sigma_t, albedo, g, box=(min, max)) (what native.Context.set_medium takes) or None."""
+        ex, keep = PtoExtras(), []
+        if env is not None:
+            t = np.ascontiguousarray(env["texels"], np.float32).copy()
+            t[..., 3] = np.asarray(env["c"], np.float32)
+            prob, alias = np.ascontiguousarray(env["prob"], np.float32), np.ascontiguousarray(env["alias"], np.uint32)
+            assert t.ndim == 3 and t.shape[2] == 4 and len(prob) == len(alias) == t.shape[0] * t.shape[1]
+            rot, inten = float(env.get("rotation", 0.0)), float(env.get("intensity", 1.0))
+            assert abs(rot) <= np.pi and inten > 0.0          # as ptmi_upload_environment resolves them
+            keep += [t, prob, alias]
+            ex.env_texels, ex.env_prob, ex.env_alias = _ptr(t), _ptr(prob), _ptr(alias)
+            ex.env_h, ex.env_w, ex.env_sampled = t.shape[0], t.shape[1], int(env.get("sampled", 1))
+            ex.env_intensity, ex.env_rotation = inten, rot
+        if medium is not None:
+            f3 = ctypes.c_float * 3
+            ex.med_on, ex.sigma_t, ex.g = 1, medium["sigma_t"], medium.get("g", 0.0)
+            ex.albedo = f3(*np.broadcast_to(np.asarray(medium.get("albedo", 1.0), np.float32), (3,)))
+            ex.box_min, ex.box_max = f3(*medium["box"][0]), f3(*medium["box"][1])
+        ex.ulp_nudge = int(ulp_nudge)
+        return ex, keep
+
+    def render_ext(self, scene, cam, n_frames, extras=None, max_bounces=8, do_mis=1, out=None, y0=0, y1=0, threads=0, census=False):
+        """render() / render_census() with extras (from Oracle.extras; None: none): (out, stats, border[, census]); border (H, W)
+        float32 = per pixel the smallest distance of a sky lookup from a texel border, in texels (inf: no lookup). The per-pixel
+        hash of the decisions its paths took (pto_render_ext's branches) is left in self.last_branches, (H, W) uint32."""
+        W, H = int(cam["width"]), int(cam["height"])
+        if out is None:
+            out = np.zeros((H, W, 4), np.float32)
+        assert out.dtype == np.float32 and out.shape == (H, W, 4) and out.flags.c_contiguous
+        border = np.full((H, W), np.inf, np.float32)
+        self.last_branches = branches = np.zeros((H, W), np.uint32)
+        opt, st, s = PtoOptions(max_bounces, do_mis, y0, y1, threads), PtoStats(), self.scene_struct(scene)
+        ex = ctypes.byref(extras[0]) if extras is not None else None
+        if not census:
+            fn = self.L.pto_render_ext
+            fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 6
+            assert fn(ctypes.byref(s), _ptr(cam), n_frames, ctypes.byref(opt), ex, _ptr(out), _ptr(border), _ptr(branches), ctypes.byref(st)) == 0
+            return out, st, border
+        names = self.census_events()
+        table = np.zeros((len(names), 64), np.uint64)
+        fn = self.L.pto_render_census_ext
+        fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 7
+        assert fn(ctypes.byref(s), _ptr(cam), n_frames, ctypes.byref(opt), ex, _ptr(out), _ptr(border), _ptr(branches), ctypes.byref(st),
+                  _ptr(table)) == 0
+        return out, st, border, dict(zip(names, table))
+
+    def render_census_ext(self, scene, cam, n_frames, extras=None, **kw):
+        return self.render_ext(scene, cam, n_frames, extras, census=True, **kw)
+
+    def trace_path_ext(self, scene, cam, x, y, frame, extras=None, max_bounces=8, do_mis=1):
+        opt = PtoOptions(max_bounces, do_mis, 0, 0, 1)
+        rad, log = np.zeros(3, np.float32), np.zeros((max_bounces + 1, 16), np.float32)
+        s = self.scene_struct(scene)
+        fn = self.L.pto_trace_path_ext
+        fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_uint32] * 3 + [ctypes.c_void_p] * 4
+        n = fn(ctypes.byref(s), _ptr(cam), x, y, frame, ctypes.byref(opt), ctypes.byref(extras[0]) if extras is not None else None,
+               _ptr(rad), _ptr(log))
+        return rad, log[:n]
+
+    def trace_paths_ext(self, scene, cam, xs, ys, frames, extras=None, max_bounces=8, do_mis=1, threads=0):
+        """trace_paths with extras: (radiance (n, 3) unclamped, segments (n,), border (n,): the path's smallest distance of a sky
+        lookup from a texel border, in texels); the paths' decision hashes are left in self.last_branches, (n,) uint32"""
+        xs, ys, frames = (np.ascontiguousarray(a, np.uint32).ravel() for a in (xs, ys, frames))
+        n = len(xs)
+        assert len(ys) == n and len(frames) == n
+        rad, seg, border = np.zeros((n, 3), np.float32), np.zeros(n, np.uint32), np.zeros(n, np.float32)
+        self.last_branches = branches = np.zeros(n, np.uint32)
+        opt, s = PtoOptions(max_bounces, do_mis, 0, 0, threads), self.scene_struct(scene)
+        fn = self.L.pto_trace_paths_ext
+        fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * 9
+        assert fn(ctypes.byref(s), _ptr(cam), n, _ptr(xs), _ptr(ys), _ptr(frames), ctypes.byref(opt),
+                  ctypes.byref(extras[0]) if extras is not None else None, _ptr(rad), _ptr(seg), _ptr(border), _ptr(branches)) == 0
+        return rad, seg, border
+
+    def ext_probe(self, extras, op, inputs):
+        """pto_ext_probe: inputs (n, <= 8) float32, padded with zeros; returns (n, 8) float32"""
+        a = np.asarray(inputs, np.float32)
+        inp = np.zeros((len(a), 8), np.float32)
+        inp[:, :a.shape[1]] = a
+        out = np.zeros((len(a), 8), np.float32)
+        fn = self.L.pto_ext_probe
+        fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+        assert fn(ctypes.byref(extras[0]), op, len(a), _ptr(inp), _ptr(out)) == 0
+        return out
 
     # -- probes ----------------------------------------------------------------
     def eval_bsdf(self, albedo, rough, metal, trans, ior, n, v, l, front=True):

@@ -217,7 +217,7 @@ def test_camera_sees_the_sky(ctx):
     ys, xs = np.divmod(np.arange(FW * FH), FW)
     _, d, _ = ctx.debug_raygen(cam, xs, ys, np.zeros(FW * FH))
     _, le, _, uW, vH = env_ref.lookup(t, d, 0.5, 0.7)
-    near = (np.abs(uW - np.round(uW)) < 1e-4) | (np.abs(vH - np.round(vH)) < 1e-4)
+    near = (np.abs(uW - np.round(uW)) < env_ref.BORDER_BAND) | (np.abs(vH - np.round(vH)) < env_ref.BORDER_BAND)
     assert near.mean() <= 0.01
     want = np.minimum(le, np.float32(2.5))                    # the fold's clamp of a sample (pt.wgsl:752): the disc is brighter
     assert same(got.reshape(-1, 4)[~near, :3], want[~near])
@@ -397,6 +397,6 @@ def test_one_bounce_shows_the_sky_only_where_the_camera_ray_misses(ctx):
     assert same(lit[~miss], dark[~miss]) and not dark[miss, :3].any()
     assert same(sampled[miss], lit[miss]) and not same(sampled[~miss], dark[~miss])
     _, le, _, uW, vH = env_ref.lookup(t, d, 0.05, 0.7)
-    near = (np.abs(uW - np.round(uW)) < 1e-4) | (np.abs(vH - np.round(vH)) < 1e-4)
+    near = (np.abs(uW - np.round(uW)) < env_ref.BORDER_BAND) | (np.abs(vH - np.round(vH)) < env_ref.BORDER_BAND)
     keep = miss & ~near
     assert same(lit[keep, :3], np.minimum(le[keep], np.float32(2.5)))

@@ -4,8 +4,9 @@ tests say which those are, on the CPU alone:
   * coverage: the gauntlet renders (tests/gauntlet_scenes.py; the GPU test compares exactly these) reach every event in every
     bounce class at least 16 times, but for the cells listed as impossible;
   * equivalence: the census changes nothing render() returns;
-  * golden: the tables of the gauntlet renders and of the ordinary parity renders are pinned (tests/golden/shade_census.json), so
-    a change of the oracle's control flow shows."""
+  * golden: the tables of the gauntlet renders, of the fog / sky gauntlet's (the oracle's extras; their coverage condition is in
+    tests/test_oracle_extras_host.py) and of the ordinary parity renders are pinned (tests/golden/shade_census.json), so a change
+    of the oracle's control flow shows."""
 import json
 import os
 
@@ -13,7 +14,7 @@ import numpy as np
 import pytest
 
 import gauntlet_scenes as G
-from ptmi import layout, scenes
+from ptmi import layout, native, scenes
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "shade_census.json")
 MIN_COUNT = 16
@@ -33,6 +34,11 @@ EXEMPT = {
     ("refract_k_negative", "C"): "k < 0 is the total-internal-reflection test, taken first",
     ("refract_k_negative", "D"): "k < 0 is the total-internal-reflection test, taken first",
 }
+
+
+def extras_events(names):
+    """the census events of pto_extras (oracle/pt_oracle.h), a contiguous run of the table"""
+    return names[names.index("med_no_interval"):names.index("env_weight_at_scatter") + 1]
 
 
 def classes(row):
@@ -58,6 +64,11 @@ def test_gauntlet_reaches_every_branch_in_every_bounce_class(oracle, gauntlet):
     for _, _, cen in gauntlet.values():
         for n in names:
             total[n] += cen[n].astype(np.int64)
+    # the events of the oracle's extras (the sky and the fog) are counted only with extras in place: never here; their own coverage
+    # condition, over the fog / sky gauntlet, is in tests/test_oracle_extras_host.py
+    extras = extras_events(names)
+    assert len(extras) == 23 and not any(total[n].any() for n in extras)
+    names = [n for n in names if n not in extras]
     assert {e for e, _ in EXEMPT} <= set(names)
     short = []
     for n in names:
@@ -117,6 +128,11 @@ def census_tables(oracle):
         sc = make()
         for mb, tile in G.oracle_renders():
             tables["%s-b%d%s" % (name, mb, "-rows" if tile else "")] = rows(G.render_census(oracle, sc, mb, tile)[2])
+    fog = G.gauntlet_fog()                                       # the fog / sky gauntlet through the oracle's extras, every state
+    for state in G.FOG_STATES:
+        for mb, tile in G.fog_oracle_renders():
+            cen = G.render_fog(oracle, fog, state, native.env_table, mb, tile)[3]
+            tables["gauntlet_fog-%s-b%d%s" % (state, mb, "-rows" if tile else "")] = rows(cen)
     for key, make, cam, frames in parity_renders():
         tables[key] = rows(oracle.render_census(make(), cam, frames, max_bounces=8)[2])
     return tables

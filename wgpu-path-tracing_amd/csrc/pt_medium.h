@@ -15,7 +15,9 @@
 struct MedInterval { float near, far, a, b; };      // the ray is inside the box for t in [near, far]; the segment for t in (a, b)
 
 // The slab test of the box per axis with fmin / fmax (v_min_f32 / v_max_f32: a NaN from 0 * inf gives the other operand).
-// t_hit: the segment's end, +inf on a miss. No interval: NOT b > a.
+// t_hit: the segment's end, +inf on a miss. No interval: NOT b > a. A ray whose slab distances are NaN on all three axes (the NaN origin or
+// direction of a degenerate path; far is NaN only then) would leave the fmin / fmax as inside the medium from 0 to t_hit, wherever the
+// box is: it has no interval.
 PT_DEV MedInterval med_interval(const DevMedium &m, v3 o, v3 d, float t_hit) {
     const float ix = rcp1(d.x), iy = rcp1(d.y), iz = rcp1(d.z);
     const float x1 = (m.box_min[0] - o.x) * ix, x2 = (m.box_max[0] - o.x) * ix;
@@ -25,7 +27,7 @@ PT_DEV MedInterval med_interval(const DevMedium &m, v3 o, v3 d, float t_hit) {
     r.near = max1(max1(min1(x1, x2), min1(y1, y2)), min1(z1, z2));
     r.far = min1(min1(max1(x1, x2), max1(y1, y2)), max1(z1, z2));
     r.a = max1(r.near, 0.0f);
-    r.b = min1(r.far, t_hit);
+    r.b = r.far == r.far ? min1(r.far, t_hit) : r.a;
     return r;
 }
 // the distance to the next collision from one uniform in [0, 1]: r = 1 gives +inf (no collision), r = 0 gives 0
