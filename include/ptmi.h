@@ -460,6 +460,41 @@ int ptmi_set_medium(ptmi_ctx *ctx, const ptmi_medium *medium);
 /* *present = 1 and *out = the medium as it was set, or *present = 0 and *out zeroed. Either pointer may be NULL. */
 int ptmi_get_medium(const ptmi_ctx *ctx, ptmi_medium *out, uint32_t *present);
 
+/* ---- a density grid for the medium: smoke, a cloud, a mist that thins with height -------------
+ * nx * ny * nz float32 multipliers rho in [0, 1], stretched over the medium's box: the local extinction is sigma_t * rho(x), so the
+ * medium's sigma_t is the majorant by construction. Albedo, g and the box stay those of ptmi_medium. Without a grid nothing changes: the
+ * kernels launched and every result are those of the homogeneous medium.
+ * LAYOUT: x fastest, cell (i, j, k) is entry (k * ny + j) * nx + i and covers box_min + (i .. i + 1) / nx * extent on x, likewise y, z.
+ * LOOKUP at p, float32 in the order written, a plain '/', no fused step (under the arithmetic contract):
+ *    u_k = (p_k - min_k) / (max_k - min_k) * n_k.  filter 0 (nearest): i_k = clamp(int(floor(u_k)), 0, n_k - 1).
+ *    filter 1 (trilinear over cell centres): v_k = u_k - 0.5, i0 = floor(v_k), f_k = v_k - i0, taps i0 and i0 + 1 each clamped to
+ *    [0, n_k - 1], interpolated along x, then y, then z, each as a * (1 - f) + b * f. A NaN coordinate reads index 0 on that axis.
+ * DELTA TRACKING replaces the free-flight draw (step 2 above) on a segment with an interval (a, b), b > a:
+ *    t = a;  repeat:  r = draw;  t += -ln(1 - r) / sigma_t;  if NOT t < b: no scatter, stop
+ *                     rho = lookup(o + t d);  r' = draw (always);  if r' < rho: SCATTER at t, stop
+ *    All tracking draws of a segment come before any other draw of it; the RNG state behind them is handed on as the state behind the
+ *    single draw is. A scatter is handled as above (step 3), a segment without one keeps its throughput.
+ * RATIO TRACKING replaces Tr (step 4) where Tr is evaluated (the sample's pdf > 0), with near / far / end as there:
+ *    T = 1, t = max(near, 0);  repeat:  r = draw;  t += -ln(1 - r) / sigma_t;  stop if NOT t < end;  T *= 1 - lookup(o + t wi);
+ *    stop if T == 0.  Its draws come after sampleLight's and before any later draw of the vertex. T multiplies the contribution before
+ *    the "exactly zero" test.
+ * TERMINATION: a grid is accepted only while sigma_t * |box diagonal| <= 256 (at most 256 expected tentative collisions a segment);
+ * both loops stop after 65 536 iterations, a guard nothing should reach: a delta-tracking segment then ends its path, a ratio-tracking
+ * sample gives T = 0. The tracking decisions are outside the bit-exact arithmetic contract, like the free-flight draw they replace. */
+typedef struct ptmi_medium_grid {
+    uint32_t filter;                  /* 0 nearest, 1 trilinear */
+    uint32_t reserved[7];             /* must be 0 */
+} ptmi_medium_grid;                   /* 32 bytes */
+/* rho NULL or a zero dimension removes the grid: the medium is homogeneous again (without a medium: nothing to do, PTMI_OK). Otherwise
+ * PTMI_E_STATE: no medium in place. PTMI_E_INVALID: a value that is not finite or outside [0, 1], filter > 1, a non-zero reserved word,
+ * a dimension above 1024. PTMI_E_UNSUPPORTED: the optical-depth limit. A failed call leaves the grid in place. params NULL: nearest.
+ * ptmi_set_medium with a new medium keeps the grid, stretched over the new box; it checks the optical-depth limit again
+ * (PTMI_E_UNSUPPORTED leaves everything as it was). ptmi_set_medium(NULL) removes the medium and the grid. Synchronises. */
+int ptmi_upload_medium_density(ptmi_ctx *ctx, const float *rho, uint32_t nx, uint32_t ny, uint32_t nz, const ptmi_medium_grid *params);
+/* nx = ny = nz = 0: none in place. rho_mean: the mean over the cells. A struct tag only. */
+struct ptmi_medium_grid_status { uint32_t nx, ny, nz, filter; float rho_min, rho_max; double rho_mean; };   /* 32 bytes */
+int ptmi_medium_grid_status(ptmi_ctx *ctx, struct ptmi_medium_grid_status *out);
+
 /* ---- presentation (the reference's blit pass, src/shader/blit.wgsl:43-155; renderer.ts:434-449) ---- */
 /* Tone-maps the output buffer (exposure 2^1, AgX, gamma 1/2.2) into a width*height canvas, row 0 = top.
  * dst_rgba_f32 (n_floats must be width*height*4, alpha 1) and/or dst_rgba8 (n_bytes must be width*height*4);
@@ -515,6 +550,9 @@ int ptmi_multi_upload_environment(ptmi_multi *m, const void *texels, uint32_t wi
 int ptmi_multi_set_environment(ptmi_multi *m, const ptmi_environment *params);
 /* ptmi_set_medium on every device (replicated; checked once before any device changes) */
 int ptmi_multi_set_medium(ptmi_multi *m, const ptmi_medium *medium);
+/* ptmi_upload_medium_density on every device (replicated; checked once before any device changes) */
+int ptmi_multi_upload_medium_density(ptmi_multi *m, const float *rho, uint32_t nx, uint32_t ny, uint32_t nz,
+                                     const ptmi_medium_grid *params);
 /* Options for every device. tile_parts / tile_part are set by the library (device i renders the strips i, i + N, ...);
  * tile_strip = 0 picks the strip height: 4 rows, or the largest smaller height that makes the frame a whole number of rounds
  * (3840x2160 over 8 devices: 3), so that all devices get equal shares; tile_y0 / tile_y1 must be 0. */
@@ -644,6 +682,22 @@ int ptmi_debug_env_sample(ptmi_ctx *ctx, uint32_t n, const float *r4, float *d3,
 int ptmi_debug_medium_step(ptmi_ctx *ctx, uint32_t n, const float *o3, const float *d3, const float *t_hit, const float *r3,
                            uint32_t *scattered, float *x3, float *dir3, float *out4);
 int ptmi_debug_medium_tr(ptmi_ctx *ctx, uint32_t n, const float *o3, const float *wi3, const float *dist, float *tr);
+/* The density grid (ptmi_upload_medium_density), probed with the functions the renders run. Both synchronise; PTMI_E_STATE: no grid.
+ * density: rho_out[i] = the lookup at point p3[3i .. 3i+2].
+ * track: ray i is (o3, d3) and draws from the kernel RNG state rng_in[i] (the number of draws is open, so no list of uniforms serves).
+ * mode 0: delta tracking of the segment ending at t_end[i] (+inf: a miss), on its interval as ptmi_debug_medium_step computes it
+ * (without one: nothing is drawn) -> scattered[i] 0 / 1, t_out the scatter distance, value_out rho at the scatter point (both 0
+ * without a scatter). mode 1: ratio tracking towards dist = t_end[i] (< 0: directional) -> scattered 0, t_out the segment's `end`,
+ * value_out = T. Both: steps_out the tentative collisions, rng_out the RNG state afterwards. Output pointers may be NULL. */
+int ptmi_debug_medium_density(ptmi_ctx *ctx, uint32_t n, const float *p3, float *rho_out);
+int ptmi_debug_medium_track(ptmi_ctx *ctx, uint32_t n, const float *o3, const float *d3, const float *t_end, const uint32_t *rng_in,
+                            uint32_t mode, uint32_t *scattered, float *t_out, float *value_out, uint32_t *steps_out, uint32_t *rng_out);
+/* Host-only (no context, no device): the checks ptmi_upload_medium_density would run for this grid on this medium, with its error
+ * codes (PTMI_E_INVALID also for rho NULL, a zero dimension or a medium that ptmi_set_medium would refuse) and the message under
+ * ptmi_last_error(NULL). medium NULL: the grid's own checks alone, without the optical-depth limit. *out (may be NULL) = what
+ * ptmi_medium_grid_status would report after the upload. */
+int ptmi_debug_medium_grid_check(const ptmi_medium *medium, const float *rho, uint32_t nx, uint32_t ny, uint32_t nz,
+                                 const ptmi_medium_grid *params, struct ptmi_medium_grid_status *out);
 /* Host-only (no context, no device): the tables ptmi_upload_environment would build for these texels. c_out: width*height floats
  * (c_t); prob_out / alias_out: width*height entries of the alias table; *weight_sum = sum(w). Each may be NULL. An all-black map gives
  * weight_sum 0, every c_t and prob 0 and alias[k] = k: such a map is never sampled. Errors as ptmi_upload_environment's, with the

@@ -56,14 +56,25 @@ int pt_check_medium(const ptmi_medium *m, std::string &err) {
     for (uint32_t r : m->reserved) if (r) return fail(err, PTMI_E_INVALID, "a reserved word of ptmi_medium is not zero");
     return PTMI_OK;
 }
+// a density grid needs sigma_t * |box diagonal| <= PT_MED_MAX_DEPTH (pt_medium.h): the bound on its tracking loops
+int pt_check_medium_depth(const ptmi_medium *m, std::string &err) {
+    double d2 = 0.0;
+    for (int k = 0; k < 3; k++) { const double e = (double)m->box_max[k] - (double)m->box_min[k]; d2 += e * e; }
+    const double depth = (double)m->sigma_t * std::sqrt(d2);
+    if (!(depth <= PT_MED_MAX_DEPTH))
+        return fail(err, PTMI_E_UNSUPPORTED, "sigma_t * |box diagonal| = %g exceeds %g, the limit of a medium with a density grid", depth,
+                    PT_MED_MAX_DEPTH);
+    return PTMI_OK;
+}
 
 extern "C" {
 
 // Checked before anything changes: a failed call leaves the medium, the context's DevScene and the device copy of that as they were.
 int ptmi_set_medium(ptmi_ctx *c, const ptmi_medium *m) {
     if (!c) return PTMI_E_INVALID;
-    const int rc = pt_check_medium(m, c->err);
+    int rc = pt_check_medium(m, c->err);
     if (rc) return rc;
+    if (m && c->sc.med.grid && (rc = pt_check_medium_depth(m, c->err))) return rc;     // the grid stays, stretched over the new box
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, sync_all(c));                                // nothing in flight reads the device copy any more
     DevMedium d{};
@@ -71,13 +82,19 @@ int ptmi_set_medium(ptmi_ctx *c, const ptmi_medium *m) {
         d.sigma_t = m->sigma_t; d.g = m->g;
         for (int k = 0; k < 3; k++) { d.albedo[k] = m->albedo[k]; d.box_min[k] = m->box_min[k]; d.box_max[k] = m->box_max[k]; }
         d.on = 1u;
+        d.grid = c->sc.med.grid; d.filter = c->sc.med.filter;
+        d.nx = c->sc.med.nx; d.ny = c->sc.med.ny; d.nz = c->sc.med.nz;
     }
     DevScene next = c->sc;
     next.med = d;
     HIP_TRY(c, hipMemcpy(c->d_scene, &next, sizeof(DevScene), hipMemcpyHostToDevice));
     c->sc = next;
     if (m) c->medium = *m;
-    else std::memset(&c->medium, 0, sizeof c->medium);
+    else {                                                  // the grid goes with its medium
+        std::memset(&c->medium, 0, sizeof c->medium);
+        dfree(c->d_med_grid);
+        c->med_grid = {};
+    }
     return PTMI_OK;
 }
 

@@ -40,6 +40,11 @@ struct DevMedium {
     float albedo[3];            // single-scattering albedo per channel
     float box_min[3], box_max[3];
     uint32_t on;
+    // the density grid (ptmi_upload_medium_density; grid NULL: none, the medium is homogeneous): nx * ny * nz multipliers in [0, 1] of
+    // sigma_t stretched over the box, x fastest; filter 0 nearest, 1 trilinear over cell centres
+    uint32_t filter;
+    const float *grid;
+    uint32_t nx, ny, nz;
 };
 
 struct DevScene;
@@ -83,7 +88,7 @@ struct DevScene {
     const DevScene *self;       // this description in device memory (the own-leaf kernels read it from there, not from kernel arguments)
     const float4 *shade_tab;    // the shade tables (below): what `shade` stages into LDS
     DevEnv env;                 // the environment map behind every miss (tab NULL: none, a miss adds throughput * 0)
-    DevMedium med;              // the homogeneous medium inside a box (on 0: none, every segment travels through vacuum)
+    DevMedium med;              // the medium inside a box (on 0: none, every segment travels through vacuum), with or without a density grid
 };
 
 // ---- shade tables: the records `shade` reads per hit that are the same for the whole scene, in one blob built at upload ----

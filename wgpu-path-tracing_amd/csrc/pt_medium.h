@@ -1,5 +1,6 @@
-// pt_medium.h — the homogeneous participating medium on the device: the interval a ray spends inside the box, free-flight sampling,
-// transmittance, the Henyey-Greenstein phase value and its sampling (include/ptmi.h ptmi_set_medium).
+// pt_medium.h — the participating medium on the device: the interval a ray spends inside the box, free-flight sampling,
+// transmittance, the Henyey-Greenstein phase value and its sampling (include/ptmi.h ptmi_set_medium); and, while a
+// density grid is in place, the grid lookup with delta and ratio tracking (ptmi_upload_medium_density).
 // Included by shade.hip (both builds) and by medium.hip, whose debug kernels call the same functions the renders run.
 //
 // Arithmetic: ln and exp are the device's logf / expf, so the free-flight distance, the scatter decision within rounding of the
@@ -11,6 +12,8 @@
 #include "pt_math.h"
 
 #define PT_FOUR_PI 12.5663706144f
+// k_shade's MED axis: which medium code an instantiation contains
+enum { PT_MED_NONE = 0, PT_MED_HOMOGENEOUS = 1, PT_MED_GRID = 2 };
 
 struct MedInterval { float near, far, a, b; };      // the ray is inside the box for t in [near, far]; the segment for t in (a, b)
 
@@ -65,4 +68,83 @@ PT_DEV v3 med_sample_phase(float g, v3 d, float xi1, float xi2, float &cos_out) 
     const v3 U = mk3(B, sg + d.y * d.y * A, -d.y);
     cos_out = ct;
     return normalize3(lincomb3(T, st * cp, U, st * sp, d, ct));
+}
+
+// ---- the density grid: sigma_t * rho(x), rho in [0, 1], so that sigma_t is the majorant everywhere ------------------------------------
+// The lookup is under the arithmetic contract: float32 in the order written, the quotient a plain '/', no fused step (the contract
+// build compiles with contraction off). The tracking decisions are outside it, like the free-flight draw they replace.
+//
+// Both tracking loops stop after PT_MED_TRACK_CAP iterations: a delta-tracking segment then ends its path, a ratio-tracking sample
+// gives T = 0. The cap is a guard for a shared machine and nothing a render or a test may reach: a grid is accepted only while
+// sigma_t * |box diagonal| <= PT_MED_MAX_DEPTH, which bounds the expected number of tentative collisions of a segment by 256 and makes
+// 65 536 of them an event of probability below e^-60000.
+#define PT_MED_TRACK_CAP 65536u
+#define PT_MED_MAX_DEPTH 256.0
+enum { PT_TRACK_PASSED = 0, PT_TRACK_SCATTERED = 1, PT_TRACK_CAPPED = 2 };
+
+// a cell index from a floored coordinate: clamped to [0, n - 1]; NaN gives 0 (v_max_f32 returns the other operand)
+PT_DEV uint32_t med_cell(float f, uint32_t n) { return (uint32_t)min1(max1(f, 0.0f), (float)(n - 1u)); }
+PT_DEV float med_grid_coord(float p, float lo, float hi, uint32_t n) { return (p - lo) / (hi - lo) * (float)n; }
+// rho at p. Cell (i, j, k) is entry (k * ny + j) * nx + i and covers box_min + (i .. i + 1) / nx * extent on x, likewise on y and z.
+// filter 0: the cell that holds p. filter 1: trilinear over the cell centres, the taps clamped at the faces, along x, then y, then z.
+PT_DEV float med_density(const DevMedium &m, v3 p) {
+    const float ux = med_grid_coord(p.x, m.box_min[0], m.box_max[0], m.nx);
+    const float uy = med_grid_coord(p.y, m.box_min[1], m.box_max[1], m.ny);
+    const float uz = med_grid_coord(p.z, m.box_min[2], m.box_max[2], m.nz);
+    const float *__restrict__ g = m.grid;
+    if (m.filter == 0u) {
+        const uint32_t i = med_cell(__builtin_floorf(ux), m.nx), j = med_cell(__builtin_floorf(uy), m.ny), k = med_cell(__builtin_floorf(uz), m.nz);
+        return g[(k * m.ny + j) * m.nx + i];
+    }
+    const float vx = ux - 0.5f, vy = uy - 0.5f, vz = uz - 0.5f;
+    const float bx = __builtin_floorf(vx), by = __builtin_floorf(vy), bz = __builtin_floorf(vz);
+    const float fx = vx - bx, fy = vy - by, fz = vz - bz;
+    const uint32_t i0 = med_cell(bx, m.nx), i1 = med_cell(bx + 1.0f, m.nx);
+    const uint32_t j0 = med_cell(by, m.ny), j1 = med_cell(by + 1.0f, m.ny);
+    const uint32_t k0 = med_cell(bz, m.nz), k1 = med_cell(bz + 1.0f, m.nz);
+    const uint32_t r00 = (k0 * m.ny + j0) * m.nx, r10 = (k0 * m.ny + j1) * m.nx;
+    const uint32_t r01 = (k1 * m.ny + j0) * m.nx, r11 = (k1 * m.ny + j1) * m.nx;
+    const float c000 = g[r00 + i0], c100 = g[r00 + i1], c010 = g[r10 + i0], c110 = g[r10 + i1];
+    const float c001 = g[r01 + i0], c101 = g[r01 + i1], c011 = g[r11 + i0], c111 = g[r11 + i1];
+    const float gx = 1.0f - fx, gy = 1.0f - fy, gz = 1.0f - fz;
+    const float c00 = c000 * gx + c100 * fx, c10 = c010 * gx + c110 * fx;
+    const float c01 = c001 * gx + c101 * fx, c11 = c011 * gx + c111 * fx;
+    const float c0 = c00 * gy + c10 * fy, c1 = c01 * gy + c11 * fy;
+    return c0 * gz + c1 * fz;
+}
+// Delta (Woodcock) tracking of the segment (a, b) of the ray (o, d), b > a: tentative collisions at the majorant's rate, each real with
+// probability rho. Two draws per tentative collision, the second also where rho is 0 or 1; the last free flight takes one.
+// PT_TRACK_SCATTERED: at t_out. steps: the tentative collisions (lookups).
+PT_DEV int med_delta_track(const DevMedium &m, v3 o, v3 d, float a, float b, uint32_t &rng, float &t_out, uint32_t &steps) {
+    float t = a;
+    t_out = 0.0f; steps = 0u;
+    for (uint32_t k = 0u; k < PT_MED_TRACK_CAP; k++) {
+        t += med_free_flight(m, rng_f(rng));
+        if (!(t < b)) return PT_TRACK_PASSED;
+        steps++;
+        const float rho = med_density(m, madd3(d, t, o));
+        if (rng_f(rng) < rho) { t_out = t; return PT_TRACK_SCATTERED; }
+    }
+    return PT_TRACK_CAPPED;
+}
+// Ratio tracking of a next-event sample from o towards wi, dist away (dist < 0: directional or sky, to the box's far side): the
+// product of 1 - rho over the tentative collisions of (max(near, 0), end), near / far / end as med_tr has them. One draw per tentative
+// collision and one for the flight that leaves the segment (also where the segment is empty). A product of exactly 0 stops the loop.
+PT_DEV float med_ratio_track(const DevMedium &m, v3 o, v3 wi, float dist, uint32_t &rng, uint32_t &steps, float &end_out) {
+    const MedInterval iv = med_interval(m, o, wi, __builtin_inff());
+    const float end = dist < 0.0f ? iv.far : min1(iv.far, dist);
+    float t = iv.a, T = 1.0f;
+    end_out = end; steps = 0u;
+    for (uint32_t k = 0u; k < PT_MED_TRACK_CAP; k++) {
+        t += med_free_flight(m, rng_f(rng));
+        if (!(t < end)) return T;
+        steps++;
+        T *= 1.0f - med_density(m, madd3(wi, t, o));
+        if (T == 0.0f) return T;
+    }
+    return 0.0f;
+}
+PT_DEV float med_ratio_track(const DevMedium &m, v3 o, v3 wi, float dist, uint32_t &rng) {
+    uint32_t steps; float end;
+    return med_ratio_track(m, o, wi, dist, rng, steps, end);
 }

@@ -322,7 +322,7 @@ int ptmi_destroy(ptmi_ctx *c) {
         if (ln.side) (void)hipStreamDestroy(ln.side);
     }
     for (void *&p : c->buf) dfree(p);
-    dfree(c->d_atlas); dfree(c->d_env); dfree(c->d_env_alias);
+    dfree(c->d_atlas); dfree(c->d_env); dfree(c->d_env_alias); dfree(c->d_med_grid);
     drop_planes(c, kAllPlanes);
     dfree(c->d_counters); dfree(c->d_control); dfree(c->d_scene);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);

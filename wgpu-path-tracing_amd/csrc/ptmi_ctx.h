@@ -6,6 +6,7 @@
 //   debug_stages.hip   the per-stage debug entry points
 //   environment.hip    the environment map: its tables, upload and removal, its debug entry points
 //   medium.hip         the participating medium: its checks, installation and removal, its debug entry points
+//   medium_grid.hip    the medium's density grid: its checks, upload and removal, its debug entry points
 #pragma once
 #include "ptmi.h"
 #include "pt_device.h"
@@ -28,6 +29,15 @@ void pt_free_prepared(PtPrepared *p);
 int pt_atlas_bytes(uint32_t width, uint32_t height, int format, size_t *bytes, char *why, size_t why_len);
 // the field checks of ptmi_set_medium (medium.hip): PTMI_E_INVALID with the reason in err; m NULL (removal) is fine
 int pt_check_medium(const ptmi_medium *m, std::string &err);
+// the optical-depth limit of a medium that carries a density grid (medium.hip): PTMI_E_UNSUPPORTED with the reason in err
+int pt_check_medium_depth(const ptmi_medium *m, std::string &err);
+// the argument checks of ptmi_upload_medium_density (medium_grid.hip), without a context: PTMI_E_INVALID with the reason in err;
+// *st (may be NULL) = what ptmi_medium_grid_status reports for these values. Not called for a removal (rho NULL or a zero dimension).
+int pt_check_medium_density(const float *rho, uint32_t nx, uint32_t ny, uint32_t nz, const ptmi_medium_grid *params,
+                            struct ptmi_medium_grid_status *st, std::string &err);
+// the medium of a context as it was set (NULL: none in place), and whether it carries a grid
+const ptmi_medium *pt_ctx_medium(const ptmi_ctx *c);
+bool pt_ctx_has_medium_grid(const ptmi_ctx *c);
 hipStream_t pt_ctx_stream(ptmi_ctx *c);
 float4 *pt_ctx_output(ptmi_ctx *c);
 int pt_ctx_device(const ptmi_ctx *c);
@@ -43,7 +53,7 @@ int pt_adaptive_flags(ptmi_ctx *c, const ptmi_adaptive_params *ap, bool restart,
 int pt_adaptive_round(ptmi_ctx *c, const ptmi_camera *cam, const ptmi_adaptive_params *ap, const uint8_t *map, uint32_t share_px,
                       bool count_call);
 
-// What follows is shared by the seven files above only: hidden, so that the library exports the C ABI and the pt_* names and no helper.
+// What follows is shared by the files above only: hidden, so that the library exports the C ABI and the pt_* names and no helper.
 // (A definition takes the visibility of the namespace block it stands in, so every block of pt_host is opened with PT_HOST.)
 #define PT_HOST namespace pt_host __attribute__((visibility("hidden")))
 PT_HOST {
@@ -131,6 +141,8 @@ struct ptmi_ctx {
     double env_weight_sum = 0.0;                       // sum of the map's sampling weights (0: all black, never sampled)
     bool env_lookup_only = false;                      // ptmi_environment.sample = 1
     ptmi_medium medium{};                              // the medium as the caller gave it (ptmi_get_medium); DevScene::med.on: in place
+    float *d_med_grid = nullptr;                       // the medium's density grid (DevScene::med.grid points at it; NULL: homogeneous)
+    struct ptmi_medium_grid_status med_grid{};                // ... as ptmi_medium_grid_status reports it
     DevScene *d_scene = nullptr;                       // sc in device memory (DevScene::self), rewritten whenever sc changes
     DevScene sc{};
     bool have_scene = false;

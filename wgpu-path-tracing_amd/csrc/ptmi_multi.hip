@@ -425,9 +425,23 @@ int ptmi_multi_set_environment(ptmi_multi *m, const ptmi_environment *params) {
 int ptmi_multi_set_medium(ptmi_multi *m, const ptmi_medium *medium) {
     if (!m) return PTMI_E_INVALID;
     std::string why;                        // checked once, before any device changes: a rejected medium leaves every shard's in place
-    const int rc = pt_check_medium(medium, why);
+    int rc = pt_check_medium(medium, why);
     if (rc) return mfail(m, rc, "%s", why.c_str());
+    if (medium && pt_ctx_has_medium_grid(m->ctx[0]) && (rc = pt_check_medium_depth(medium, why))) return mfail(m, rc, "%s", why.c_str());
     return each_ctx(m, "ptmi_set_medium", ptmi_set_medium, medium);
+}
+
+int ptmi_multi_upload_medium_density(ptmi_multi *m, const float *rho, uint32_t nx, uint32_t ny, uint32_t nz, const ptmi_medium_grid *params) {
+    if (!m) return PTMI_E_INVALID;
+    if (rho && nx != 0 && ny != 0 && nz != 0) {     // checked once, before any device changes: a rejected grid leaves every shard's in place
+        std::string why;
+        const ptmi_medium *med = pt_ctx_medium(m->ctx[0]);
+        if (!med) return mfail(m, PTMI_E_STATE, "no medium in place (ptmi_set_medium)");
+        int rc = pt_check_medium_density(rho, nx, ny, nz, params, nullptr, why);
+        if (!rc) rc = pt_check_medium_depth(med, why);
+        if (rc) return mfail(m, rc, "%s", why.c_str());
+    }
+    return each_ctx(m, "ptmi_upload_medium_density", ptmi_upload_medium_density, rho, nx, ny, nz, params);
 }
 
 int ptmi_multi_resize(ptmi_multi *m, uint32_t w, uint32_t h) {

@@ -389,7 +389,11 @@ PT_DEV v3 stored_throughput(const DevPaths &P, uint32_t q, float4 d4) {
 // looked up: albedo, next-event estimation with the phase value where the BSDF's value and pdf stand, a direction sampled from the
 // phase function, roulette. Otherwise the segment is shaded as without a medium, except that every next-event sample's contribution
 // takes the transmittance towards its light. Without MED the kernel is the one it was: no branch of it reads the medium.
-template <bool AOV, int STAGE, bool ENV, bool MED>
+// MED is PT_MED_HOMOGENEOUS for that medium and PT_MED_GRID while a density grid is in place (ptmi_upload_medium_density; DESIGN.md
+// §12): the one free-flight draw becomes delta tracking against the majorant sigma_t and the transmittance becomes ratio tracking,
+// both with draws from the path's RNG (pt_medium.h); everything around them is the same code. The instantiations without a grid
+// contain none of it.
+template <bool AOV, int STAGE, bool ENV, int MED>
 __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, DevPaths P, const uint32_t *__restrict__ queue,
                                                   const uint32_t *__restrict__ count_ptr,
                                                   const float2 *__restrict__ hits, DevShadow S,
@@ -428,8 +432,17 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                 const MedInterval iv = med_interval(sc.med, ro, rd, is_hit ? h2.x : __builtin_inff());
                 med_rng = __float_as_uint(o4.w);
                 if (iv.b > iv.a) {
-                    const float t_sc = iv.a + med_free_flight(sc.med, rng_f(med_rng));
-                    scattered = t_sc < iv.b;
+                    float t_sc;
+                    bool capped = false;                                     // GRID: the tracking loop reached its cap, the path ends
+                    if (MED == PT_MED_GRID) {
+                        uint32_t steps;
+                        const int how = med_delta_track(sc.med, ro, rd, iv.a, iv.b, med_rng, t_sc, steps);
+                        scattered = how != PT_TRACK_PASSED;
+                        capped = how == PT_TRACK_CAPPED;
+                    } else {
+                        t_sc = iv.a + med_free_flight(sc.med, rng_f(med_rng));
+                        scattered = t_sc < iv.b;
+                    }
                     if (scattered) {
                         if (AOV) {                                           // the planes record the camera ray's surface hit all the same
                             if (is_hit) {
@@ -444,7 +457,8 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                         v3 thr = mk3(1.0f, 1.0f, 1.0f);
                         if (sp.bounce != 0u) thr = stored_throughput(P, q, d4);
                         thr = mul3(thr, ld3(sc.med.albedo));
-                        if ((thr.x != 0.0f) | (thr.y != 0.0f) | (thr.z != 0.0f)) {       // all zero: the path ends here
+                        if (!(MED == PT_MED_GRID && capped) &&
+                            ((thr.x != 0.0f) | (thr.y != 0.0f) | (thr.z != 0.0f))) {     // all zero: the path ends here
                             const v3 x = madd3(rd, t_sc, ro);
                             const float g = sc.med.g;
                             float inv_n = 0.0f;
@@ -455,7 +469,8 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                                     const float ph = med_phase(g, dot3(rd, ls.wi));
                                     float wmis = power_heuristic(1.0f, ls.pdf, 1.0f, ph);
                                     v3 direct = vdiv3(scale3(scale3(ls.intensity, ph), wmis), max1(ls.pdf, PT_EPS));
-                                    v3 contrib = scale3(mul3(thr, direct), med_tr(sc.med, x, ls.wi, ls.dist));
+                                    v3 contrib = MED == PT_MED_GRID ? scale3(mul3(thr, direct), med_ratio_track(sc.med, x, ls.wi, ls.dist, med_rng))
+                                                                    : scale3(mul3(thr, direct), med_tr(sc.med, x, ls.wi, ls.dist));
                                     if ((contrib.x != 0.0f) | (contrib.y != 0.0f) | (contrib.z != 0.0f)) {
                                         rec_o = make_float4(x.x, x.y, x.z, ls.dist);
                                         rec_d = make_float4(ls.wi.x, ls.wi.y, ls.wi.z, __uint_as_float(p));
@@ -522,7 +537,8 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                             v3 direct = vdiv3(scale3(mul3(ls.intensity, mk3(ev.x, ev.y, ev.z)), wmis),
                                               max1(ls.pdf, PT_EPS));          // pt.wgsl:674
                             v3 contrib = mul3(thr, direct);                   // pt.wgsl:675, added by `shadow`
-                            if (MED) contrib = scale3(contrib, med_tr(sc.med, hit.position, ls.wi, ls.dist));
+                            if (MED == PT_MED_GRID) contrib = scale3(contrib, med_ratio_track(sc.med, hit.position, ls.wi, ls.dist, rng));
+                            else if (MED) contrib = scale3(contrib, med_tr(sc.med, hit.position, ls.wi, ls.dist));
                             // A contribution of exactly zero (the light is behind the surface: NdotL = 0) leaves the
                             // radiance unchanged whatever the shadow ray finds (x + 0 = x), so that ray is counted
                             // in the statistics like the reference's traversal but neither recorded nor traced.
@@ -628,7 +644,7 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
 #define PT_LAUNCH_SHADE pt_launch_shade
 #endif
 namespace {
-template <bool AOV, int STAGE, bool ENV, bool MED>
+template <bool AOV, int STAGE, bool ENV, int MED>
 void launch_shade(hipStream_t s, int blocks, const DevScene &sc, DevPaths p, const uint32_t *queue, const uint32_t *count,
                   const float2 *hits, DevShadow sh, uint64_t *alive_mask, uint64_t *shadow_mask, ShadeParams sp, float4 *aov) {
     const size_t lds = (((STAGE & PT_STAGE_MATS) ? pt_tab_mats_q(sc.n_mats) : 0) + ((STAGE & PT_STAGE_LIGHTS) ? pt_tab_lights_q(sc.n_lights) : 0)) * 16;
@@ -637,7 +653,7 @@ void launch_shade(hipStream_t s, int blocks, const DevScene &sc, DevPaths p, con
 }
 }  // namespace
 // the tables each launch stages: pt_shade_stage of the scene's counts (what fits PT_SHADE_LDS_BUDGET), for every instantiation; ENV
-// while an environment map is in place, MED while a medium is
+// while an environment map is in place, MED by the medium in place and its grid
 void PT_LAUNCH_SHADE(hipStream_t s, int blocks, const DevScene &sc, DevPaths p, const uint32_t *queue,
                      const uint32_t *count, const float2 *hits, DevShadow sh, uint64_t *alive_mask,
                      uint64_t *shadow_mask, ShadeParams sp, float4 *aov) {
@@ -646,7 +662,8 @@ void PT_LAUNCH_SHADE(hipStream_t s, int blocks, const DevScene &sc, DevPaths p, 
                 : (aov ? launch_shade<true, STAGE, false, MED> : launch_shade<false, STAGE, false, MED>))
 #define PT_SHADE_CASE(STAGE)                                                                                              \
     case STAGE:                                                                                                           \
-        (sc.med.on ? PT_SHADE_PICK(STAGE, true) : PT_SHADE_PICK(STAGE, false))(                                           \
+        (!sc.med.on ? PT_SHADE_PICK(STAGE, PT_MED_NONE)                                                                   \
+                    : sc.med.grid ? PT_SHADE_PICK(STAGE, PT_MED_GRID) : PT_SHADE_PICK(STAGE, PT_MED_HOMOGENEOUS))(        \
             s, blocks, sc, p, queue, count, hits, sh, alive_mask, shadow_mask, sp, aov);                                  \
         break;
     switch (pt_shade_stage(sc.n_mats, sc.n_lights)) {

@@ -258,6 +258,29 @@ static napi_value js_set_medium(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* uploadMediumDensity(handle, Float32Array | null, [nx, ny, nz], filter): ptmi_upload_medium_density; null or a zero dimension removes the grid */
+static napi_value js_upload_medium_density(napi_env env, napi_callback_info info) {
+    napi_value argv[4], v;
+    handle *h = get_handle(env, info, 4, argv);
+    if (!h) return NULL;
+    void *p; size_t n; uint32_t dim[3] = {0, 0, 0};
+    ptmi_medium_grid prm = {0};
+    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
+    for (uint32_t k = 0; p && k < 3; k++)
+        if (napi_get_element(env, argv[2], k, &v) != napi_ok || napi_get_value_uint32(env, v, &dim[k]) != napi_ok) {
+            napi_throw_type_error(env, NULL, "uploadMediumDensity: expected the dimensions [nx, ny, nz]");
+            return NULL;
+        }
+    napi_get_value_uint32(env, argv[3], &prm.filter);
+    /* (dimensions above the limit are the library's to refuse: only what it would read is checked here) */
+    if (p && dim[0] <= 1024 && dim[1] <= 1024 && dim[2] <= 1024 && n / 4 < (size_t)dim[0] * dim[1] * dim[2]) {
+        napi_throw_range_error(env, NULL, "density buffer too small");
+        return NULL;
+    }
+    CALL(env, h, upload_medium_density, (const float *)p, dim[0], dim[1], dim[2], &prm);
+    return NULL;
+}
+
 static napi_value js_resize(napi_env env, napi_callback_info info) {
     napi_value argv[3];
     handle *h = get_handle(env, info, 3, argv);
@@ -714,7 +737,7 @@ static napi_value js_abi_version(napi_env env, napi_callback_info info) {
 static napi_value init(napi_env env, napi_value exports) {
     static const struct { const char *name; napi_callback fn; } fns[] = {
         {"abiVersion", js_abi_version}, {"create", js_create}, {"multiCreate", js_multi_create}, {"destroy", js_destroy},
-        {"uploadScene", js_upload_scene}, {"uploadAtlas", js_upload_atlas}, {"uploadEnvironment", js_upload_environment}, {"setMedium", js_set_medium}, {"resize", js_resize}, {"setOptions", js_set_options},
+        {"uploadScene", js_upload_scene}, {"uploadAtlas", js_upload_atlas}, {"uploadEnvironment", js_upload_environment}, {"setMedium", js_set_medium}, {"uploadMediumDensity", js_upload_medium_density}, {"resize", js_resize}, {"setOptions", js_set_options},
         {"dispatch", js_dispatch}, {"gather", js_gather}, {"gatherPlanes", js_gather_planes}, {"synchronize", js_synchronize}, {"throttle", js_throttle},
         {"readOutput", js_read_output}, {"writeOutput", js_write_output}, {"setAovs", js_set_aovs}, {"readAov", js_read_aov},
         {"blit", js_blit}, {"getStats", js_get_stats}, {"resetStats", js_reset_stats},

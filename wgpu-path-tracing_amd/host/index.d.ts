@@ -64,6 +64,9 @@ export class Renderer {
   setEnvironment(texels: Float32Array | null, width?: number, height?: number, opts?: EnvironmentOptions): void;
   /** one homogeneous scattering medium (fog) inside an axis-aligned box; null removes it. Restarts accumulation. */
   setMedium(medium: MediumOptions | null): void;
+  /** a density grid for the medium in place: nx * ny * nz multipliers of its sigmaT, x fastest, stretched over its box; null removes
+   *  it. Needs setMedium first. A refused grid throws and leaves the grid and the medium in place. Restarts accumulation. */
+  setMediumDensity(rho: Float32Array | null, dims?: [number, number, number], opts?: MediumDensityOptions): void;
   renderFrame(frames?: number): void;
   start(): void;
   stop(): void;
@@ -131,6 +134,13 @@ export interface MediumOptions {
   g?: number;
   /** the medium's box, or 'scene': the root box of the scene loaded last */
   bounds: { min: [number, number, number]; max: [number, number, number] } | 'scene';
+}
+export interface MediumDensityOptions {
+  /** 'nearest' (default): the cell that holds the point; 'linear': trilinear over the cell centres */
+  filter?: 'nearest' | 'linear';
+  /** false (default): the values must lie in [0, 1]. true: any non-negative densities; they are divided by their maximum and the
+   *  medium's sigmaT is multiplied by it */
+  normalise?: boolean;
 }
 export interface EnvironmentOptions {
   /** radiance scale; 0 / undefined: 1 */

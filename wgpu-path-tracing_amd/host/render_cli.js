@@ -7,7 +7,7 @@
  *                       --aperture A --focus F --batch K --png out.png --denoise
  *                       --adaptive THRESHOLD --max-frames N --rounds R
  *                       --env file.hdr --env-intensity X --env-rotation DEGREES --env-sample 0|1
- *                       --fog sigma_t[,albedo[,g]]
+ *                       --fog sigma_t[,albedo[,g]] --fog-density file.f32 --fog-grid nx,ny,nz --fog-filter nearest|linear
  *                       --devices 0,1,... --loopback --aov albedo|normal|id --aov-out plane.bin]
  * --batch K traces K frames per dispatch instead of one. --denoise keeps the denoiser's planes and makes --png the tone-mapped
  * denoised image (include/ptmi.h ptmi_denoise, default parameters). --adaptive renders to a noise level instead of --frames
@@ -15,7 +15,10 @@
  * adaptive: { samples, minCount, maxCount, rounds }. --env lights the scene with a Radiance .hdr environment map (hdr_decode.js;
  * include/ptmi.h ptmi_upload_environment): equirectangular, scaled by --env-intensity, turned by --env-rotation degrees about +Y;
  * --env-sample 1 only looks it up. --fog fills the scene's box with a homogeneous scattering medium (include/ptmi.h ptmi_set_medium):
- * extinction sigma_t per unit length, single-scattering albedo (default 1) and Henyey-Greenstein asymmetry g (default 0). Writes W*H*4 float32 (the output buffer, raw also with
+ * extinction sigma_t per unit length, single-scattering albedo (default 1) and Henyey-Greenstein asymmetry g (default 0); --fog-density gives it a density grid
+ * (ptmi_upload_medium_density): a raw file of nx * ny * nz float32 values, x fastest, looked up per cell or with --fog-filter linear. Values in [0, 1]
+ * are taken as they are, as multipliers of sigma_t; a file that holds larger ones is divided by its maximum (sigma_t is then the
+ * extinction at its densest cell). Writes W*H*4 float32 (the output buffer, raw also with
  * --denoise) and prints one JSON line with the statistics. --devices renders on several GPUs behind one Renderer (include/ptmi.h
  * ptmi_multi_*; --loopback lets one ordinal be listed more than once, for a one-GPU box); --adaptive, --denoise and --aov work with
  * it. --aov keeps that first-hit plane and --aov-out writes it raw (float32 x 4 per pixel, uint32 x 2 for id).
@@ -61,6 +64,19 @@ r.loadModel(scenePath).then(function () {
   if (textArg('fog')) {
     var fog = textArg('fog').split(',').map(Number);
     r.setMedium({ sigmaT: fog[0], albedo: fog.length > 1 ? fog[1] : 1, g: fog.length > 2 ? fog[2] : 0, bounds: 'scene' });
+  }
+  if (textArg('fog-density')) {
+    if (!textArg('fog') || !textArg('fog-grid')) throw new Error('--fog-density needs --fog and --fog-grid nx,ny,nz');
+    var dims = textArg('fog-grid').split(',').map(Number);
+    var raw = fs.readFileSync(textArg('fog-density'));
+    if (dims.length !== 3 || raw.length !== dims[0] * dims[1] * dims[2] * 4) throw new Error('--fog-density: the file is not nx * ny * nz float32 values');
+    var rho = new Float32Array(raw.buffer.slice(raw.byteOffset, raw.byteOffset + raw.length));
+    var peak = 0;
+    for (var k = 0; k < rho.length; k++) peak = Math.max(peak, rho[k]);
+    // multipliers in [0, 1] are taken as they are; larger densities are divided by their maximum, with sigma_t left as given: the file
+    // then says where the fog is, --fog how thick it is at its thickest
+    if (peak > 1) for (var q = 0; q < rho.length; q++) rho[q] /= peak;
+    r.setMediumDensity(rho, dims, { filter: textArg('fog-filter') || 'nearest' });
   }
   var t0 = Date.now();
   var status = null;

@@ -213,6 +213,8 @@ Renderer.prototype.setEnvironment = function (texels, width, height, opts) {
 Renderer.prototype.setMedium = function (medium) {
   if (!medium) {
     this.addon.setMedium(this.ctx, null);
+    this.mediumSet = null;                  // (the library drops the density grid with its medium)
+    this.densityScale = 1;
   } else {
     var bounds = medium.bounds;
     if (bounds === 'scene') {
@@ -221,8 +223,82 @@ Renderer.prototype.setMedium = function (medium) {
     }
     if (!bounds || !bounds.min || !bounds.max) throw new TypeError("setMedium: bounds must be { min, max } or 'scene'");
     var a = medium.albedo === undefined ? 1 : medium.albedo;
-    this.addon.setMedium(this.ctx, { sigmaT: medium.sigmaT, albedo: typeof a === 'number' ? [a, a, a] : a, g: medium.g || 0,
-                                     min: bounds.min, max: bounds.max });
+    var m = { sigmaT: medium.sigmaT, albedo: typeof a === 'number' ? [a, a, a] : a, g: medium.g || 0, min: bounds.min, max: bounds.max };
+    var scale = this.densityScale || 1;     // a normalised density grid in place: its maximum stays in sigma_t
+    this.addon.setMedium(this.ctx, scale === 1 ? m : Object.assign({}, m, { sigmaT: m.sigmaT * scale }));
+    this.mediumSet = m;
+  }
+  this.frameIndex = 0;
+};
+
+/** why ptmi_upload_medium_density would refuse rho over dims on medium m with sigmaT times scale (include/ptmi.h), or null */
+function refusal(rho, dims, m, scale) {
+  var n = 1;
+  for (var k = 0; k < 3; k++) {
+    if (!(dims[k] >= 1 && dims[k] <= 1024) || dims[k] !== Math.floor(dims[k])) return 'dimension ' + dims[k] + ' is not an integer in 1 .. 1024';
+    n *= dims[k];
+  }
+  if (rho.length < n) return 'the array holds ' + rho.length + ' values, the grid ' + n;
+  for (var i = 0; i < n; i++) if (!(rho[i] >= 0 && rho[i] <= 1)) return 'density ' + rho[i] + ' at entry ' + i + ' is not within [0, 1]';
+  var sigma = Math.fround(m.sigmaT * scale), d2 = 0;
+  if (!(sigma > 0 && isFinite(sigma))) return 'sigmaT ' + sigma + ' is not finite and > 0';
+  for (var a = 0; a < 3; a++) { var e = Math.fround(m.max[a]) - Math.fround(m.min[a]); d2 += e * e; }
+  if (!(sigma * Math.sqrt(d2) <= 256)) return 'sigmaT * |box diagonal| = ' + sigma * Math.sqrt(d2) + ' exceeds 256, the limit of a medium with a density grid';
+  return null;
+}
+
+/**
+ * A density grid for the medium in place (include/ptmi.h ptmi_upload_medium_density): a Float32Array of nx * ny * nz multipliers of
+ * the medium's sigmaT, x fastest, stretched over its box; dims = [nx, ny, nz]; opts: { filter ('nearest', the default, or 'linear'),
+ * normalise (false: the values must lie in [0, 1]; true: any non-negative densities: they are divided by their maximum, and the
+ * medium's sigmaT is multiplied by it, so that sigmaT * rho stays what the array says) }. rho null removes the grid, and the medium is
+ * homogeneous with the sigmaT it was set with. Needs setMedium first. A refused grid throws and leaves the grid and the medium in place,
+ * also where `normalise` would have changed sigmaT. Accumulation restarts.
+ */
+Renderer.prototype.setMediumDensity = function (rho, dims, opts) {
+  opts = opts || {};
+  var self = this;
+  function rescale(scale) {                 // sigmaT of the medium as it was set, times scale
+    if (scale !== (self.densityScale || 1)) {
+      self.addon.setMedium(self.ctx, Object.assign({}, self.mediumSet, { sigmaT: self.mediumSet.sigmaT * scale }));
+      self.densityScale = scale;
+    }
+  }
+  if (!rho) {
+    this.addon.uploadMediumDensity(this.ctx, null, [0, 0, 0], 0);
+    if (this.mediumSet) rescale(1);
+  } else {
+    if (!(rho instanceof Float32Array)) throw new TypeError('setMediumDensity: rho must be a Float32Array');
+    if (!dims || dims.length !== 3) throw new TypeError('setMediumDensity: dims must be [nx, ny, nz]');
+    if (!this.mediumSet) throw new Error('setMediumDensity: needs a medium in place (setMedium)');
+    if (opts.filter !== undefined && opts.filter !== 'nearest' && opts.filter !== 'linear') throw new TypeError("setMediumDensity: filter must be 'nearest' or 'linear'");
+    var scale = 1;
+    if (opts.normalise) {
+      var max = 0;
+      for (var i = 0; i < rho.length; i++) {
+        if (!(rho[i] >= 0 && isFinite(rho[i]))) throw new RangeError('setMediumDensity: density ' + rho[i] + ' at entry ' + i + ' is not finite and >= 0');
+        if (rho[i] > max) max = rho[i];
+      }
+      if (max > 0) {
+        scale = max;
+        var scaled = new Float32Array(rho.length);
+        for (var j = 0; j < rho.length; j++) scaled[j] = Math.min(rho[j] / max, 1);
+        rho = scaled;
+      }
+    }
+    var filter = opts.filter === 'linear' ? 1 : 0;
+    if (scale === (this.densityScale || 1)) {
+      this.addon.uploadMediumDensity(this.ctx, rho, [dims[0], dims[1], dims[2]], filter);       // a refused grid leaves the one in place
+    } else {
+      // Another scale: the grid in place was normalised for the old one, so it has to go before sigmaT changes. What the library would
+      // refuse is therefore refused here first, before anything changes: like a failed ptmi_upload_medium_density, a throw leaves
+      // the grid and the medium in place.
+      var why = refusal(rho, dims, this.mediumSet, scale);
+      if (why) throw new RangeError('setMediumDensity: ' + why);
+      this.addon.uploadMediumDensity(this.ctx, null, [0, 0, 0], 0);
+      rescale(scale);
+      this.addon.uploadMediumDensity(this.ctx, rho, [dims[0], dims[1], dims[2]], filter);
+    }
   }
   this.frameIndex = 0;
 };

@@ -40,6 +40,8 @@ EXPORTS = [
     "ptmi_multi_read_aov", "ptmi_multi_read_moments", "ptmi_multi_dispatch_adaptive", "ptmi_multi_adaptive_status",
     "ptmi_multi_denoise", "ptmi_multi_blit_denoised",
     "ptmi_set_medium", "ptmi_get_medium", "ptmi_multi_set_medium", "ptmi_debug_medium_step", "ptmi_debug_medium_tr",
+    "ptmi_upload_medium_density", "ptmi_medium_grid_status", "ptmi_multi_upload_medium_density", "ptmi_debug_medium_density",
+    "ptmi_debug_medium_track", "ptmi_debug_medium_grid_check",
 ]
 MULTI_LOOPBACK = 1
 MULTI_PLANE_MOMENTS, MULTI_PLANE_OUTPUT = 0x100, 0x200      # gather_planes: with the AOV_* bits
@@ -124,6 +126,23 @@ class Medium(ctypes.Structure):
                 "box": (tuple(self.box_min), tuple(self.box_max))}
 
 
+class MediumGrid(ctypes.Structure):
+    """ptmi_medium_grid: how the medium's density grid is looked up (include/ptmi.h)"""
+    _fields_ = [("filter", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 7)]
+
+
+class MediumGridStatus(ctypes.Structure):
+    _fields_ = [("nx", ctypes.c_uint32), ("ny", ctypes.c_uint32), ("nz", ctypes.c_uint32), ("filter", ctypes.c_uint32),
+                ("rho_min", ctypes.c_float), ("rho_max", ctypes.c_float), ("rho_mean", ctypes.c_double)]
+
+    def as_dict(self):
+        return {"dims": (int(self.nx), int(self.ny), int(self.nz)), "filter": int(self.filter), "rho_min": float(self.rho_min),
+                "rho_max": float(self.rho_max), "rho_mean": float(self.rho_mean)}
+
+
+FILTER_NEAREST, FILTER_LINEAR = 0, 1
+
+
 class Stats(ctypes.Structure):
     _fields_ = [("paths", ctypes.c_uint64), ("segments", ctypes.c_uint64), ("shadow_rays", ctypes.c_uint64),
                 ("dispatches", ctypes.c_uint64), ("frames", ctypes.c_uint64),
@@ -157,6 +176,7 @@ _SHARED = {
     "upload_environment": [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p],
     "set_environment": [ctypes.c_void_p],
     "set_medium": [ctypes.c_void_p],
+    "upload_medium_density": [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p],
     "set_aovs": [ctypes.c_uint32], "get_aovs": [ctypes.POINTER(ctypes.c_uint32)], "read_aov": [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t],
     "set_moments": [ctypes.c_uint32], "get_moments": [ctypes.POINTER(ctypes.c_uint32)], "read_moments": [ctypes.c_void_p, ctypes.c_size_t],
     "denoise": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t], "blit_denoised": [ctypes.c_void_p, ctypes.c_size_t] * 2,
@@ -218,6 +238,10 @@ def load():
         L.ptmi_get_medium.argtypes = [vp, vp, ctypes.POINTER(u32)]
         L.ptmi_debug_medium_step.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.ptmi_debug_medium_tr.argtypes = [vp, u32, vp, vp, vp, vp]
+        L.ptmi_medium_grid_status.argtypes = [vp, vp]
+        L.ptmi_debug_medium_density.argtypes = [vp, u32, vp, vp]
+        L.ptmi_debug_medium_grid_check.argtypes = [vp, vp, u32, u32, u32, vp, vp]
+        L.ptmi_debug_medium_track.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -261,6 +285,28 @@ def env_table(texels, fmt=None, width=None, height=None):
     if rc != 0:
         raise PtmiError(rc, L.ptmi_last_error(None).decode())
     return c, prob, alias, ws.value
+
+
+def medium_grid_check(rho, filter=FILTER_NEAREST, dims=None, reserved=(0, 0, 0, 0, 0, 0, 0), medium=None):
+    """Host-only: the checks upload_medium_density would run (include/ptmi.h: ptmi_debug_medium_grid_check) for the grid rho, shape
+    (nz, ny, nx), on the medium given as set_medium's keywords (None: without the optical-depth limit); the MediumGridStatus the
+    upload would leave, or PtmiError. dims = (nx, ny, nz) overrides what the array's shape says."""
+    L = load()
+    a = np.ascontiguousarray(rho, np.float32)
+    if dims is None:
+        dims = a.shape[::-1]
+    prm = MediumGrid(filter, (ctypes.c_uint32 * 7)(*reserved))
+    m = None
+    if medium is not None:
+        f3 = ctypes.c_float * 3
+        alb = np.broadcast_to(np.asarray(medium.get("albedo", 1.0), np.float32), (3,))
+        m = ctypes.byref(Medium(medium["sigma_t"], f3(*alb), medium.get("g", 0.0), f3(*medium["box"][0]), f3(*medium["box"][1]),
+                                (ctypes.c_uint32 * 5)()))
+    st = MediumGridStatus()
+    rc = L.ptmi_debug_medium_grid_check(m, _p(a), dims[0], dims[1], dims[2], ctypes.byref(prm), ctypes.byref(st))
+    if rc != 0:
+        raise PtmiError(rc, L.ptmi_last_error(None).decode())
+    return st
 
 
 class ImageInfo(ctypes.Structure):
@@ -391,6 +437,20 @@ class _Handle:
         f3 = ctypes.c_float * 3
         m = Medium(sigma_t, f3(*alb), g, f3(*box[0]), f3(*box[1]), (ctypes.c_uint32 * 5)(*reserved))
         self._ck(self._c.set_medium(self.h, ctypes.byref(m)))
+
+    def upload_medium_density(self, rho, filter=FILTER_NEAREST, dims=None, reserved=(0, 0, 0, 0, 0, 0, 0)):
+        """A density grid for the medium in place (include/ptmi.h ptmi_upload_medium_density): float32 multipliers in [0, 1] of its
+        sigma_t as an array of shape (nz, ny, nx), x fastest, stretched over its box; filter 0 nearest, 1 trilinear. rho None removes
+        the grid. dims = (nx, ny, nz) overrides what the array's shape says."""
+        if rho is None:
+            self._ck(self._c.upload_medium_density(self.h, None, 0, 0, 0, None))
+            return
+        a = np.ascontiguousarray(rho, np.float32)
+        if dims is None:
+            assert a.ndim == 3, "a density grid is an array of shape (nz, ny, nx)"
+            dims = a.shape[::-1]
+        prm = MediumGrid(filter, (ctypes.c_uint32 * 7)(*reserved))
+        self._ck(self._c.upload_medium_density(self.h, _p(a), dims[0], dims[1], dims[2], ctypes.byref(prm)))
 
     def resize(self, width, height):
         self._ck(self._c.resize(self.h, width, height))
@@ -615,6 +675,32 @@ class Context(_Handle):
         tr = np.zeros(len(o), np.float32)
         self._ck(self.L.ptmi_debug_medium_tr(self.h, len(o), _p(o), _p(wi), _p(dist), _p(tr)))
         return tr
+
+    # -- the medium's density grid (include/ptmi.h ptmi_upload_medium_density) ---------------------------------------------
+    def medium_grid_status(self):
+        st = MediumGridStatus()
+        self._ck(self.L.ptmi_medium_grid_status(self.h, ctypes.byref(st)))
+        return st
+
+    def debug_medium_density(self, p):
+        """the grid lookup at the points p (n, 3): (n,) float32"""
+        p = np.ascontiguousarray(p, np.float32).reshape(-1, 3)
+        rho = np.zeros(len(p), np.float32)
+        self._ck(self.L.ptmi_debug_medium_density(self.h, len(p), _p(p), _p(rho)))
+        return rho
+
+    def debug_medium_track(self, o, d, t_end, rng, mode):
+        """mode 0: delta tracking of the rays (o, d) up to t_end (inf: a miss); mode 1: ratio tracking towards dist = t_end (< 0:
+        directional); each ray draws from its kernel RNG state rng[i]. (scattered (n,) bool, t (n,), value (n,), tentative collisions (n,)
+        uint32, RNG states afterwards (n,) uint32): t, value = scatter distance and rho there (mode 0), the segment's end and T (mode 1)"""
+        o, d = np.ascontiguousarray(o, np.float32).reshape(-1, 3), np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        t_end, rng = np.ascontiguousarray(t_end, np.float32).reshape(-1), np.ascontiguousarray(rng, np.uint32).reshape(-1)
+        n = len(o)
+        assert len(d) == n and len(t_end) == n and len(rng) == n
+        sc, steps, after = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        t, v = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        self._ck(self.L.ptmi_debug_medium_track(self.h, n, _p(o), _p(d), _p(t_end), _p(rng), mode, _p(sc), _p(t), _p(v), _p(steps), _p(after)))
+        return sc != 0, t, v, steps, after
 
     def read_image(self):
         """The traversal image the last upload_scene put on the device (include/ptmi.h: ptmi_debug_read_image), as build_image()
