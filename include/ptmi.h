@@ -616,6 +616,44 @@ int ptmi_multi_adaptive_status(ptmi_multi *m, struct ptmi_adaptive_status *out);
 int ptmi_multi_denoise(ptmi_multi *m, const ptmi_denoise_params *params, float *dst_rgba, size_t n_floats);
 int ptmi_multi_blit_denoised(ptmi_multi *m, float *dst_rgba_f32, size_t n_floats, uint8_t *dst_rgba8, size_t n_bytes);
 
+/* ---- editing a loaded scene in place -----------------------------------------------------------
+ * Each call copies the records [first, first + count) over the loaded scene's, waits for the work in flight as an upload does, and is
+ * synchronous. The output buffer and every plane are left alone: the caller restarts accumulation, as after any scene change. The
+ * topology never changes: the node array, the leaf ranges, the triangle order and the length of every table stay as uploaded.
+ * ptmi_update_triangles brings everything an upload derives from vertex positions to the values an upload of the edited triangles with
+ * the uploaded tree's boxes refitted (leaf box = min / max over its triangles' vertices, inner box = union of its children) would
+ * make, on the device: the triangle images, the light triangles of the shade tables, the boxes of the tree as uploaded and of the
+ * walked hierarchy (own leaves: unit boxes, slivers, padding, the 16-bit grid and the quantised nodes), the root boxes and the image
+ * header (ptmi_debug_read_image). Renders and the per-stage entry points give the bits of that fresh upload. With leaves = 1 the
+ * quantised nodes and the leaf stream are dropped at the first update and the exact nodes are walked (quantised_kept = 0).
+ * PTMI_E_INVALID: no scene, a range beyond the uploaded count, count > 0 with a NULL pointer, a vertex that is not finite (own leaves:
+ * or whose edge arithmetic a + (b - a) is not). PTMI_E_UNSUPPORTED: the uploaded tree was not nested and finite (it is walked as
+ * uploaded and its boxes mean what the caller made them mean). A refused call leaves the context unchanged. count = 0 is fine.
+ * ptmi_update_materials / ptmi_update_lights rewrite the records and their copies in the shade tables (an emissive light's triangle
+ * included); lights are checked as at upload (PTMI_E_INVALID: an unknown type, triangle_index >= n_triangles). Neither touches a tree. */
+int ptmi_update_triangles(ptmi_ctx *ctx, uint32_t first, uint32_t count, const ptmi_triangle *triangles);
+int ptmi_update_materials(ptmi_ctx *ctx, uint32_t first, uint32_t count, const ptmi_material *materials);
+int ptmi_update_lights(ptmi_ctx *ctx, uint32_t first, uint32_t count, const ptmi_light *lights);
+/* A refitted tree degrades as geometry moves. cost = the sum over every child box stored in the walked hierarchy of its surface area,
+ * divided by the root box's: cost_built when the plan was made (before the first refit), cost_now after the last update. The host
+ * decides from the ratio when to call ptmi_upload_scene again; the library never rebuilds on its own. Before the first update after an
+ * upload everything is zero. A struct tag only. */
+struct ptmi_scene_update_status {
+    uint32_t updates;         /* ptmi_update_triangles calls since the last upload */
+    uint32_t quantised_kept;  /* 1: the walked image still has its quantised nodes */
+    double   plan_ms;         /* one-time preparation at the first update after an upload (levels, numbering, scratch) */
+    double   refit_ms;        /* wall time of the last ptmi_update_triangles */
+    double   cost_built, cost_now;
+    float    root_min[3], root_max[3];   /* the refitted root box of the tree as uploaded */
+    uint32_t reserved[4];
+};                            /* 80 bytes */
+int ptmi_scene_update_status(ptmi_ctx *ctx, struct ptmi_scene_update_status *out);
+/* the three updates on every device; the status of device 0 */
+int ptmi_multi_update_triangles(ptmi_multi *m, uint32_t first, uint32_t count, const ptmi_triangle *triangles);
+int ptmi_multi_update_materials(ptmi_multi *m, uint32_t first, uint32_t count, const ptmi_material *materials);
+int ptmi_multi_update_lights(ptmi_multi *m, uint32_t first, uint32_t count, const ptmi_light *lights);
+int ptmi_multi_scene_update_status(ptmi_multi *m, struct ptmi_scene_update_status *out);
+
 /* ---- statistics ----------------------------------------------------------- */
 int ptmi_get_stats(ptmi_ctx *ctx, ptmi_stats *out);           /* synchronises */
 int ptmi_reset_stats(ptmi_ctx *ctx);

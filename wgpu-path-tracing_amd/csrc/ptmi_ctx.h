@@ -7,6 +7,7 @@
 //   environment.hip    the environment map: its tables, upload and removal, its debug entry points
 //   medium.hip         the participating medium: its checks, installation and removal, its debug entry points
 //   medium_grid.hip    the medium's density grid: its checks, upload and removal, its debug entry points
+//   scene_update.hip   edits of a loaded scene in place: ptmi_update_triangles (the refit on the device), _materials, _lights
 #pragma once
 #include "ptmi.h"
 #include "pt_device.h"
@@ -67,6 +68,11 @@ enum SceneBuf {
     kLeafbox,                          // own leaves: per original triangle, the box of the reference leaf that lists it
     kWnodes16, kRefWnodes16, kQnodes16,    // own leaves, small scenes: the two hierarchies and the quantised nodes with 16-bit references
     kShadeTab,                         // the shade tables: materials, lights and the lights' triangles in one blob (pt_device.h)
+    // the plan of ptmi_update_triangles (scene_update.hip), made at the first update after an upload and gone with the next upload:
+    kPlanRefOrder, kPlanOrder,         // the nodes of kRefWnodes / kWnodes by height above their deepest leaf, lowest first
+    kPlanQnum,                         // per node of kWnodes, its number in kQnodes
+    kPlanUnits, kPlanExact,            // own leaves: the unit box of every listed triangle (leaf order); both exact child boxes per node
+    kPlanWords,                        // the reduction words of one update and the partial sums of the cost
     kSceneBufs
 };
 
@@ -147,6 +153,13 @@ struct ptmi_ctx {
     DevScene sc{};
     bool have_scene = false;
     ptmi_image_info img{};                   // what the last upload put on the device (ptmi_debug_read_image)
+    uint32_t n_ref_wnodes = 0;               // wide nodes of the tree as uploaded (kRefWnodes)
+    bool tree_nested = false;                // the uploaded tree was nested and finite: a hierarchy could be built over it
+    // ptmi_update_triangles since the last upload (scene_update.hip): the level lists of the plan (level l of a list: entries
+    // [off[l], off[l + 1])) and what ptmi_scene_update_status reports
+    bool upd_planned = false;
+    std::vector<uint32_t> upd_ref_off, upd_off;
+    struct ptmi_scene_update_status upd{};
 
     // output (binding 0)
     uint32_t W = 0, H = 0;

@@ -444,6 +444,26 @@ int ptmi_multi_upload_medium_density(ptmi_multi *m, const float *rho, uint32_t n
     return each_ctx(m, "ptmi_upload_medium_density", ptmi_upload_medium_density, rho, nx, ny, nz, params);
 }
 
+// The edits of a loaded scene on every device (scene_update.hip). Every device holds the same scene under the same options and checks
+// before it changes anything, so a refused call is refused by the first device and leaves them all as they were.
+int ptmi_multi_update_triangles(ptmi_multi *m, uint32_t first, uint32_t count, const ptmi_triangle *tris) {
+    if (!m) return PTMI_E_INVALID;
+    return each_ctx(m, "ptmi_update_triangles", ptmi_update_triangles, first, count, tris);
+}
+int ptmi_multi_update_materials(ptmi_multi *m, uint32_t first, uint32_t count, const ptmi_material *mats) {
+    if (!m) return PTMI_E_INVALID;
+    return each_ctx(m, "ptmi_update_materials", ptmi_update_materials, first, count, mats);
+}
+int ptmi_multi_update_lights(ptmi_multi *m, uint32_t first, uint32_t count, const ptmi_light *lights) {
+    if (!m) return PTMI_E_INVALID;
+    return each_ctx(m, "ptmi_update_lights", ptmi_update_lights, first, count, lights);
+}
+int ptmi_multi_scene_update_status(ptmi_multi *m, struct ptmi_scene_update_status *out) {
+    if (!m || !out) return PTMI_E_INVALID;
+    const int rc = ptmi_scene_update_status(m->ctx[0], out);
+    return rc ? cfail(m, 0, rc, "ptmi_scene_update_status") : PTMI_OK;
+}
+
 int ptmi_multi_resize(ptmi_multi *m, uint32_t w, uint32_t h) {
     if (!m) return PTMI_E_INVALID;
     int rc = each_ctx(m, "ptmi_resize", ptmi_resize, w, h);

@@ -40,6 +40,7 @@ struct Built {
     uint32_t q_top = 0;                      // quantised nodes numbered breadth-first at the front (LDS-resident in the kernel)
     float tri_safe_dsum = 0.0f;              // DevScene::tri_safe_dsum
     uint32_t tree_builder_used = 0;          // ptmi_stats.tree_builder_used
+    bool nested = false;                     // the uploaded tree is nested and finite (ptmi_update_triangles refits only such a tree)
     double tree_ms = 0.0;                    // time spent building and quantising the walked hierarchy
 
     Built() { img.leaves_used = 1; img.root_ref = PT_REF_NONE; }
@@ -242,6 +243,7 @@ int build_image(const ptmi_options &opt, hipStream_t stream, int device, const p
                     nested = nested && nodes[ch].aabb_min[k] >= n.aabb_min[k] && nodes[ch].aabb_max[k] <= n.aabb_max[k];
         }
     }
+    b.nested = nested;
     const uint32_t leaves_mode = opt.leaves ? opt.leaves : (uint32_t)PT_LEAVES_DEFAULT;
     bool own = false;
     if (nested && leaves_mode == 2u && !opt.keep_reference_tree) {
@@ -437,6 +439,8 @@ int pt_install_scene(ptmi_ctx *c, PtPrepared *prep) {
     HIP_TRY(c, hipMemcpy(c->d_scene, &c->sc, sizeof(DevScene), hipMemcpyHostToDevice));
     c->img = h;
     c->have_scene = true;
+    c->n_ref_wnodes = (uint32_t)(b.buf[kRefWnodes].bytes / 64); c->tree_nested = b.nested;
+    c->upd_planned = false; c->upd_ref_off.clear(); c->upd_off.clear(); c->upd = {};
     c->st.leaves_used = h.leaves_used;
     c->st.leaf_tris_used = h.max_leaf_tris;
     c->st.tree_builder_used = b.tree_builder_used;

@@ -281,6 +281,50 @@ static napi_value js_upload_medium_density(napi_env env, napi_callback_info info
     return NULL;
 }
 
+/* updateTriangles / updateMaterials / updateLights(handle, first, blob): ptmi_update_*; the blob holds whole records in the upload's layout */
+#define JS_UPDATE(name, fn, type)                                                                                              \
+    static napi_value name(napi_env env, napi_callback_info info) {                                                            \
+        napi_value argv[3];                                                                                                    \
+        handle *h = get_handle(env, info, 3, argv);                                                                            \
+        if (!h) return NULL;                                                                                                   \
+        void *p; size_t n; uint32_t first = 0;                                                                                 \
+        NAPI_OK(env, napi_get_value_uint32(env, argv[1], &first));                                                             \
+        if (!get_bytes(env, argv[2], &p, &n)) return NULL;                                                                     \
+        if (n % sizeof(type)) { napi_throw_range_error(env, NULL, "blob length is not a multiple of its element size"); return NULL; } \
+        CALL(env, h, fn, first, (uint32_t)(n / sizeof(type)), (const type *)p);                                                \
+        return NULL;                                                                                                           \
+    }
+JS_UPDATE(js_update_triangles, update_triangles, ptmi_triangle)
+JS_UPDATE(js_update_materials, update_materials, ptmi_material)
+JS_UPDATE(js_update_lights, update_lights, ptmi_light)
+
+/* sceneUpdateStatus(handle) -> {updates, quantisedKept, planMs, refitMs, costBuilt, costNow, rootMin: [3], rootMax: [3]} */
+static napi_value js_scene_update_status(napi_env env, napi_callback_info info) {
+    napi_value argv[1], out, v, arr[2];
+    handle *h = get_handle(env, info, 1, argv);
+    if (!h) return NULL;
+    struct ptmi_scene_update_status st;
+    CALL(env, h, scene_update_status, &st);
+    NAPI_OK(env, napi_create_object(env, &out));
+    const struct { const char *name; double value; } num[] = {
+        {"updates", st.updates}, {"quantisedKept", st.quantised_kept}, {"planMs", st.plan_ms}, {"refitMs", st.refit_ms},
+        {"costBuilt", st.cost_built}, {"costNow", st.cost_now}};
+    for (size_t i = 0; i < sizeof num / sizeof num[0]; i++) {
+        NAPI_OK(env, napi_create_double(env, num[i].value, &v));
+        NAPI_OK(env, napi_set_named_property(env, out, num[i].name, v));
+    }
+    for (int side = 0; side < 2; side++) {
+        NAPI_OK(env, napi_create_array_with_length(env, 3, &arr[side]));
+        for (uint32_t k = 0; k < 3; k++) {
+            NAPI_OK(env, napi_create_double(env, side ? st.root_max[k] : st.root_min[k], &v));
+            NAPI_OK(env, napi_set_element(env, arr[side], k, v));
+        }
+    }
+    NAPI_OK(env, napi_set_named_property(env, out, "rootMin", arr[0]));
+    NAPI_OK(env, napi_set_named_property(env, out, "rootMax", arr[1]));
+    return out;
+}
+
 static napi_value js_resize(napi_env env, napi_callback_info info) {
     napi_value argv[3];
     handle *h = get_handle(env, info, 3, argv);
@@ -737,7 +781,9 @@ static napi_value js_abi_version(napi_env env, napi_callback_info info) {
 static napi_value init(napi_env env, napi_value exports) {
     static const struct { const char *name; napi_callback fn; } fns[] = {
         {"abiVersion", js_abi_version}, {"create", js_create}, {"multiCreate", js_multi_create}, {"destroy", js_destroy},
-        {"uploadScene", js_upload_scene}, {"uploadAtlas", js_upload_atlas}, {"uploadEnvironment", js_upload_environment}, {"setMedium", js_set_medium}, {"uploadMediumDensity", js_upload_medium_density}, {"resize", js_resize}, {"setOptions", js_set_options},
+        {"uploadScene", js_upload_scene}, {"uploadAtlas", js_upload_atlas}, {"uploadEnvironment", js_upload_environment}, {"setMedium", js_set_medium}, {"uploadMediumDensity", js_upload_medium_density},
+        {"updateTriangles", js_update_triangles}, {"updateMaterials", js_update_materials}, {"updateLights", js_update_lights}, {"sceneUpdateStatus", js_scene_update_status},
+        {"resize", js_resize}, {"setOptions", js_set_options},
         {"dispatch", js_dispatch}, {"gather", js_gather}, {"gatherPlanes", js_gather_planes}, {"synchronize", js_synchronize}, {"throttle", js_throttle},
         {"readOutput", js_read_output}, {"writeOutput", js_write_output}, {"setAovs", js_set_aovs}, {"readAov", js_read_aov},
         {"blit", js_blit}, {"getStats", js_get_stats}, {"resetStats", js_reset_stats},

@@ -67,6 +67,14 @@ export class Renderer {
   /** a density grid for the medium in place: nx * ny * nz multipliers of its sigmaT, x fastest, stretched over its box; null removes
    *  it. Needs setMedium first. A refused grid throws and leaves the grid and the medium in place. Restarts accumulation. */
   setMediumDensity(rho: Float32Array | null, dims?: [number, number, number], opts?: MediumDensityOptions): void;
+  /** writes whole records (the upload's layout) over the loaded scene's from record `first` on and refits the trees on the device;
+   *  the topology stays. Refreshes sceneBounds and restarts accumulation. A refused edit throws and changes nothing. */
+  updateTriangles(first: number, blob: ArrayBuffer | ArrayBufferView): void;
+  updateMaterials(first: number, blob: ArrayBuffer | ArrayBufferView): void;
+  updateLights(first: number, blob: ArrayBuffer | ArrayBufferView): void;
+  sceneUpdateStatus(): SceneUpdateStatus;
+  /** the root box of the loaded scene's hierarchy (null without one); follows updateTriangles */
+  sceneBounds: { min: number[]; max: number[] } | null;
   renderFrame(frames?: number): void;
   start(): void;
   stop(): void;
@@ -134,6 +142,14 @@ export interface MediumOptions {
   g?: number;
   /** the medium's box, or 'scene': the root box of the scene loaded last */
   bounds: { min: [number, number, number]; max: [number, number, number] } | 'scene';
+}
+/** ptmi_scene_update_status: the triangle updates since the scene was loaded */
+export interface SceneUpdateStatus {
+  updates: number; quantisedKept: number; planMs: number; refitMs: number;
+  /** sum of the walked tree's child-box areas over the root box's area: when the plan was made, and now */
+  costBuilt: number; costNow: number;
+  /** the refitted root box of the tree as uploaded */
+  rootMin: number[]; rootMax: number[];
 }
 export interface MediumDensityOptions {
   /** 'nearest' (default): the cell that holds the point; 'linear': trilinear over the cell centres */

@@ -231,6 +231,35 @@ Renderer.prototype.setMedium = function (medium) {
   this.frameIndex = 0;
 };
 
+/**
+ * Edits of the loaded scene in place (include/ptmi.h ptmi_update_triangles / _materials / _lights): `blob` holds whole records in the
+ * layout loadModel uploads (an ArrayBuffer or a typed array), written over the scene's from record `first` on. The topology stays:
+ * same counts, same triangle order. updateTriangles refits the trees on the device and refreshes sceneBounds (what
+ * setMedium({ bounds: 'scene' }) reads) from the refitted root box; sceneUpdateStatus().costNow / costBuilt says how far the refitted
+ * tree has degraded, for the host to decide when to loadModel again. Accumulation restarts. A refused edit throws and changes nothing.
+ */
+Renderer.prototype.updateTriangles = function (first, blob) {
+  if (!this.sceneLoaded) throw new Error('updateTriangles: needs a loaded scene (loadModel)');
+  this.addon.updateTriangles(this.ctx, first, blob);
+  var st = this.addon.sceneUpdateStatus(this.ctx);
+  if (this.sceneBounds) this.sceneBounds = { min: st.rootMin, max: st.rootMax };
+  this.frameIndex = 0;
+};
+Renderer.prototype.updateMaterials = function (first, blob) {
+  if (!this.sceneLoaded) throw new Error('updateMaterials: needs a loaded scene (loadModel)');
+  this.addon.updateMaterials(this.ctx, first, blob);
+  this.frameIndex = 0;
+};
+Renderer.prototype.updateLights = function (first, blob) {
+  if (!this.sceneLoaded) throw new Error('updateLights: needs a loaded scene (loadModel)');
+  this.addon.updateLights(this.ctx, first, blob);
+  this.frameIndex = 0;
+};
+/** { updates, quantisedKept, planMs, refitMs, costBuilt, costNow, rootMin, rootMax } of the triangle updates since loadModel */
+Renderer.prototype.sceneUpdateStatus = function () {
+  return this.addon.sceneUpdateStatus(this.ctx);
+};
+
 /** why ptmi_upload_medium_density would refuse rho over dims on medium m with sigmaT times scale (include/ptmi.h), or null */
 function refusal(rho, dims, m, scale) {
   var n = 1;

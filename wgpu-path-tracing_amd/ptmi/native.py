@@ -42,6 +42,8 @@ EXPORTS = [
     "ptmi_set_medium", "ptmi_get_medium", "ptmi_multi_set_medium", "ptmi_debug_medium_step", "ptmi_debug_medium_tr",
     "ptmi_upload_medium_density", "ptmi_medium_grid_status", "ptmi_multi_upload_medium_density", "ptmi_debug_medium_density",
     "ptmi_debug_medium_track", "ptmi_debug_medium_grid_check",
+    "ptmi_update_triangles", "ptmi_update_materials", "ptmi_update_lights", "ptmi_scene_update_status",
+    "ptmi_multi_update_triangles", "ptmi_multi_update_materials", "ptmi_multi_update_lights", "ptmi_multi_scene_update_status",
 ]
 MULTI_LOOPBACK = 1
 MULTI_PLANE_MOMENTS, MULTI_PLANE_OUTPUT = 0x100, 0x200      # gather_planes: with the AOV_* bits
@@ -143,6 +145,18 @@ class MediumGridStatus(ctypes.Structure):
 FILTER_NEAREST, FILTER_LINEAR = 0, 1
 
 
+class SceneUpdateStatus(ctypes.Structure):
+    """struct ptmi_scene_update_status: the triangle updates since the last upload (include/ptmi.h)"""
+    _fields_ = [("updates", ctypes.c_uint32), ("quantised_kept", ctypes.c_uint32), ("plan_ms", ctypes.c_double),
+                ("refit_ms", ctypes.c_double), ("cost_built", ctypes.c_double), ("cost_now", ctypes.c_double),
+                ("root_min", ctypes.c_float * 3), ("root_max", ctypes.c_float * 3), ("reserved", ctypes.c_uint32 * 4)]
+
+    def as_dict(self):
+        return {"updates": int(self.updates), "quantised_kept": int(self.quantised_kept), "plan_ms": float(self.plan_ms),
+                "refit_ms": float(self.refit_ms), "cost_built": float(self.cost_built), "cost_now": float(self.cost_now),
+                "root_box": (tuple(self.root_min), tuple(self.root_max))}
+
+
 class Stats(ctypes.Structure):
     _fields_ = [("paths", ctypes.c_uint64), ("segments", ctypes.c_uint64), ("shadow_rays", ctypes.c_uint64),
                 ("dispatches", ctypes.c_uint64), ("frames", ctypes.c_uint64),
@@ -181,6 +195,10 @@ _SHARED = {
     "set_moments": [ctypes.c_uint32], "get_moments": [ctypes.POINTER(ctypes.c_uint32)], "read_moments": [ctypes.c_void_p, ctypes.c_size_t],
     "denoise": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t], "blit_denoised": [ctypes.c_void_p, ctypes.c_size_t] * 2,
     "dispatch_adaptive": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32], "adaptive_status": [ctypes.c_void_p],
+    "update_triangles": [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p],
+    "update_materials": [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p],
+    "update_lights": [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p],
+    "scene_update_status": [ctypes.c_void_p],
 }
 _lib = None
 
@@ -410,6 +428,28 @@ class _Handle:
             assert a.ndim == 3 and a.shape[2] == 4 and a.flags.c_contiguous
             fmt = ATLAS_RGBA16F if a.dtype == np.float16 else ATLAS_RGBA32F
             self._ck(self._c.upload_atlas(self.h, _p(a), a.shape[1], a.shape[0], fmt))
+
+    # -- edits of the loaded scene in place (include/ptmi.h ptmi_update_triangles) ------------------------------------
+    def _update(self, call, first, records, dtype):
+        records = np.ascontiguousarray(records)
+        assert records.dtype == dtype
+        self._ck(call(self.h, first, len(records), _p(records) if len(records) else None))
+
+    def update_triangles(self, first, tris):
+        """writes the TRIANGLE records tris over the loaded scene's from index `first` on and refits the trees on the device; the
+        caller restarts accumulation"""
+        self._update(self._c.update_triangles, first, tris, layout.TRIANGLE)
+
+    def update_materials(self, first, mats):
+        self._update(self._c.update_materials, first, mats, layout.MATERIAL)
+
+    def update_lights(self, first, lights):
+        self._update(self._c.update_lights, first, lights, layout.LIGHT)
+
+    def scene_update_status(self):
+        st = SceneUpdateStatus()
+        self._ck(self._c.scene_update_status(self.h, ctypes.byref(st)))
+        return st
 
     def upload_environment(self, texels, intensity=0.0, rotation=0.0, sample=0, reserved=(0, 0, 0, 0, 0)):
         """The environment map behind every miss (include/ptmi.h ptmi_upload_environment): (H, W, 4) float16 / float32 texels,
