@@ -654,6 +654,40 @@ int ptmi_multi_update_materials(ptmi_multi *m, uint32_t first, uint32_t count, c
 int ptmi_multi_update_lights(ptmi_multi *m, uint32_t first, uint32_t count, const ptmi_light *lights);
 int ptmi_multi_scene_update_status(ptmi_multi *m, struct ptmi_scene_update_status *out);
 
+/* ---- alpha cutouts ---------------------------------------------------------------------------
+ * A per-material cutoff table for the loaded scene, one float per uploaded material. cutoff = 0: the material is opaque (the state of
+ * every material without a table). cutoff > 0: a hit on the material is NOT THERE where the alpha of its albedo map's texel at the hit
+ * is below the cutoff (alpha < cutoff, glTF's alphaMode MASK; a material without an albedo map has alpha 1). A ray that meets such a
+ * hole goes on in the same direction past it with nothing else changed: no bounce counted, no RNG draw, no throughput change, no
+ * roulette step. This holds for path segments and for the shadow rays of next-event estimation; `shade` sees the first hit that is
+ * there, at its true distance along the ray, and the first-hit planes and ptmi_reproject see that surface too. The alpha is the atlas
+ * texel's fourth channel, which nothing else reads.
+ * Inactive (no table, or a table without a positive entry): every call issues the launches and gives the bits it gives without this
+ * feature. Active: each bounce runs a resolve loop after `extend` and traces its shadow rays as closest-hit rays through a second loop
+ * (the reference's own rule for shadow rays), on the one-stream schedule whatever ptmi_options.overlap says (the stored option is left
+ * alone); a table whose holes no ray meets gives the bits of a render without it. max_layers bounds the holes one ray may pass per
+ * segment: a path ray still on a hole after that many takes the hit as opaque, a shadow ray is occluded, and both are counted.
+ * LIMITS: alphaMode BLEND stays opaque; a light sample aimed at an emissive triangle ignores that triangle's own cutout; the medium's
+ * box is not cut by holes; no overlap while active.
+ * cutoff NULL or n_materials 0 removes the table. PTMI_E_INVALID: no scene, n_materials different from the uploaded count, an entry
+ * that is negative or not finite, max_layers > 32, a non-zero reserved word; a failed call leaves the previous table in place. The call
+ * waits for the work in flight, as ptmi_set_medium does, and leaves the output and the planes alone. ptmi_upload_scene removes the
+ * table (it belongs to that scene's materials); ptmi_upload_atlas and the ptmi_update_* calls leave it alone. */
+typedef struct ptmi_alpha_params {
+    uint32_t max_layers;      /* holes one ray may pass per segment, 1..32; 0 = default (4) */
+    uint32_t reserved[3];     /* must be 0 */
+} ptmi_alpha_params;          /* 16 bytes */
+/* passes: holes passed; exhausted: rays still on a hole after max_layers — all four since ptmi_reset_stats. A struct tag only. */
+struct ptmi_alpha_status {
+    uint32_t present, n_materials, n_cutout, max_layers;      /* a table is in place; its length, positive entries and limit */
+    uint64_t path_passes, path_exhausted, shadow_passes, shadow_exhausted;
+};                            /* 48 bytes */
+int ptmi_set_alpha_cutoff(ptmi_ctx *ctx, const float *cutoff, uint32_t n_materials, const ptmi_alpha_params *params /* NULL: defaults */);
+int ptmi_alpha_status(ptmi_ctx *ctx, struct ptmi_alpha_status *out);      /* synchronises */
+/* the table on every device, checked once before any device changes; the counters summed over the devices, the rest device 0's */
+int ptmi_multi_set_alpha_cutoff(ptmi_multi *m, const float *cutoff, uint32_t n_materials, const ptmi_alpha_params *params);
+int ptmi_multi_alpha_status(ptmi_multi *m, struct ptmi_alpha_status *out);
+
 /* ---- statistics ----------------------------------------------------------- */
 int ptmi_get_stats(ptmi_ctx *ctx, ptmi_stats *out);           /* synchronises */
 int ptmi_reset_stats(ptmi_ctx *ctx);
@@ -665,14 +699,23 @@ int ptmi_debug_raygen(ptmi_ctx *ctx, const ptmi_camera *camera, uint32_t n, cons
 /* the centre rays ptmi_reproject traces for `camera` (step 2 there), for the n = width*height pixels of the context's size, index
  * y*width+x. o3/d3: n*3 floats each, n_floats_each must be n*3 (else, or with a camera of another size: PTMI_E_INVALID). */
 int ptmi_debug_center_rays(ptmi_ctx *ctx, const ptmi_camera *camera, float *o3, float *d3, size_t n_floats_each);
-/* extend kernel (pt.wgsl:248-296) on caller rays: t = -1 / tri = 0xFFFFFFFF on miss. */
+/* extend kernel (pt.wgsl:248-296) on caller rays: t = -1 / tri = 0xFFFFFFFF on miss. Raw: an alpha cutoff table is not consulted. */
 int ptmi_debug_intersect(ptmi_ctx *ctx, uint32_t n, const float *o3, const float *d3,
                          float *t, uint32_t *tri, float *u, float *v);
 /* shadow kernel predicate (pt.wgsl:394/423/465); dist[i] < 0 = directional light (any hit occludes). Every negative value
  * means that: the library normalises them to -1 before the kernel sees them (inside a dispatch, -2 marks the record of an
- * emissive hit, which is added without a traversal — never a value a caller can inject here). */
+ * emissive hit, which is added without a traversal — never a value a caller can inject here). Raw: an alpha cutoff table is not
+ * consulted. */
 int ptmi_debug_occluded(ptmi_ctx *ctx, uint32_t n, const float *o3, const float *d3,
                         const float *dist, uint8_t *occluded);
+/* The two loops of an active alpha cutoff table on caller rays, the very loops the renders run (PTMI_E_STATE without a table that has
+ * a positive entry). intersect: `extend`, then the path loop -> the first hit that is there, t measured along the caller's ray (-1 /
+ * 0xFFFFFFFF: a miss). occluded: the shadow stage of a bounce with the verdict written out instead of added; dist as for
+ * ptmi_debug_occluded. layers[i]: the holes ray i passed, or max_layers + 1 for a ray still on a hole after max_layers (its hit is
+ * reported as it stands / it is occluded). */
+int ptmi_debug_alpha_intersect(ptmi_ctx *ctx, uint32_t n, const float *o3, const float *d3, float *t, uint32_t *tri, uint32_t *layers);
+int ptmi_debug_alpha_occluded(ptmi_ctx *ctx, uint32_t n, const float *o3, const float *d3, const float *dist, uint8_t *occluded,
+                              uint32_t *layers);
 /* Host-only (no context, no device): builds the traversal image ptmi_upload_scene would build and reports on it.
  * out[0] wide nodes of the rebuilt hierarchy (0: the tree is walked as uploaded), [1] leaves, [2] its depth,
  * [3] quantised nodes (0: none), [4] dwords of the leaf stream, [5] quantised child boxes that do NOT contain the exact

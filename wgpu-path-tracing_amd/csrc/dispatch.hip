@@ -133,9 +133,9 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         // Room = free memory + what this context already holds, less a tenth for the rest (spill areas, blit staging).
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const uint64_t held = (uint64_t)ln.cap * bytes_per_path(ln.aov != nullptr, ln.paths.W != nullptr);
+            const uint64_t held = (uint64_t)ln.cap * bytes_per_path(ln.aov != nullptr, ln.paths.W != nullptr, ln.alpha.RO != nullptr);
             const uint64_t room = (uint64_t)((double)(free_b + held) * 0.9);
-            F = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(F, room / (npix * bytes_per_path(c->aov_mask != 0, c->sc.env.sampled != 0))));
+            F = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(F, room / (npix * bytes_per_path(c->aov_mask != 0, c->sc.env.sampled != 0, alpha_active(c)))));
         }
     }
     F = std::min(F, n_frames);
@@ -145,7 +145,10 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
     // adds to L (emissive hits leave a record too, ShadeParams::emit_records), bounce after bounce on one stream, so every
     // path's sum is formed in the same order as without it. Record buffers alternate by bounce parity; shade(b) waits for
     // shadow(b - 2), the end of the batch for the last one.
-    const bool side = nee && c->opt.overlap != 0;
+    // While an alpha cutoff table is active (alpha.hip) the shadow stage is `extend` plus a resolve loop on the bounce loop's stream,
+    // sharing its scratch arrays with the path loop: the one-stream schedule, whatever the option says.
+    const bool alpha = alpha_active(c);
+    const bool side = nee && c->opt.overlap != 0 && !alpha;
     if (npix * F > 0xFFFFFF00ull) return fail(c, PTMI_E_UNSUPPORTED, "batch of %llu paths exceeds 2^32", (unsigned long long)(npix * F));
     TraverseConfig cfg, cfg_shadow;
     if ((rc = traverse_pick(c, true, cfg)) || (rc = traverse_pick(c, false, cfg_shadow))) return rc;      // refused before anything is made
@@ -205,7 +208,8 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
                 const DevPaths sp = tail ? tp : bp;
                 const int par = side ? (int)(b & 1u) : 0;
                 const ShadeParams shp{b, maxb, c->opt.do_mis, ct, side ? 1u : 0u, tail ? ln.pid : nullptr};
-                { Timed t(c, kExtend, t2, ms); launch_extend(c, ms, cfg, sp, q, &qlen[b], ln.hits); }
+                { Timed t(c, kExtend, t2, ms); launch_extend(c, ms, cfg, sp, q, &qlen[b], ln.hits);
+                  if (alpha) alpha_resolve_paths(c, ms, cfg, sp, q, &qlen[b], ln.hits, nullptr); }
                 const bool last = b + 1 == maxb;
                 if (side && b >= 2) HIP_TRY(c, hipStreamWaitEvent(ms, ln.ev_shadow[par], 0));      // its records are read
                 { Timed t(c, kShade, t3, ms);
@@ -224,7 +228,8 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
                     HIP_TRY(c, hipEventRecord(ln.ev_shadow[par], ss));
                 } else if (nee) {
                     Timed t(c, kShadow, t3, ms);
-                    launch_shadow(c, ms, cfg_shadow, bp, ln.sh[0], ln.sq[0], &slen[0], nullptr);
+                    if (alpha) alpha_shadow_stage(c, ms, cfg, bp, ln.sh[0], ln.sq[0], &slen[0], ln.hits, nullptr, nullptr);   // (shade is done with the hits)
+                    else launch_shadow(c, ms, cfg_shadow, bp, ln.sh[0], ln.sq[0], &slen[0], nullptr);
                 }
                 cur ^= 1;
             }
@@ -397,6 +402,8 @@ int ptmi_reproject(ptmi_ctx *c, const ptmi_camera *from, const ptmi_camera *to, 
     const int blocks = c->n_cu * 8;
     pt_launch_center_rays(s, blocks, *to, band, ln.paths, &c->d_control[kCwQueue]);
     launch_extend(c, s, cfg, ln.paths, nullptr, &c->d_control[kCwQueue], ln.hits);
+    // the first surface that is there, as the first-hit planes recorded it: without this every pixel seen through a hole is disoccluded
+    if (alpha_active(c)) alpha_resolve_paths(c, s, cfg, ln.paths, nullptr, &c->d_control[kCwQueue], ln.hits, nullptr);
     ReprojectArgs a{};
     a.from = *from; a.band = band;
     a.max_history = q.max_history ? q.max_history : 32u;

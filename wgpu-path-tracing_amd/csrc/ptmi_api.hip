@@ -28,19 +28,27 @@ constexpr size_t kLaneBytes[kLaneBufs] = {
     1,                                             // kOcc
     32,                                            // kAovRec
     4, 4,                                          // kPathW, kTailW
+    16, 16, 4, 4, 8,                               // kAlphaO, kAlphaD, kAlphaList0, kAlphaList1, kAlphaHits
 };
 // bytes of device memory a path of a batch takes in ensure_capacity: the per-path arrays and one byte for the two masks (2 x 8 B per 64
 // paths). The automatic batch size and its out-of-memory retry (ptmi_dispatch) rely on it.
-// the arrays that exist only while something is on: the first-hit records (aov), the environment's weights (env_w)
-constexpr bool lane_buf_wanted(int k, bool aov, bool env_w) { return k == kAovRec ? aov : k == kPathW || k == kTailW ? env_w : true; }
-constexpr size_t lane_bytes_per_path(bool aov, bool env_w) {
+// the arrays that exist only while something is on: the first-hit records (aov), the environment's weights (env_w), the alpha resolve
+// loops' arrays (alpha)
+constexpr bool lane_buf_wanted(int k, bool aov, bool env_w, bool alpha) {
+    return k == kAovRec ? aov : k == kPathW || k == kTailW ? env_w : k >= kAlphaO && k <= kAlphaHits ? alpha : true;
+}
+constexpr size_t lane_bytes_per_path(bool aov, bool env_w, bool alpha) {
     size_t n = 1;
-    for (int k = 0; k < kLaneBufs; k++) if (lane_buf_wanted(k, aov, env_w)) n += kLaneBytes[k];
+    for (int k = 0; k < kLaneBufs; k++) if (lane_buf_wanted(k, aov, env_w, alpha)) n += kLaneBytes[k];
     return n;
 }
-static_assert(lane_bytes_per_path(false, false) == 214 && lane_bytes_per_path(true, false) == 246 && lane_bytes_per_path(false, true) == 222,
+static_assert(lane_bytes_per_path(false, false, false) == 214 && lane_bytes_per_path(true, false, false) == 246 &&
+              lane_bytes_per_path(false, true, false) == 222 && lane_bytes_per_path(false, false, true) == 262,
               "the automatic frames_per_batch moves with these");
 
+}  // namespace
+
+PT_HOST {
 // the typed members that kernels receive, as views of Lane::buf
 void lane_views(Lane &ln) {
     auto at = [&](int k, auto *&p) { view(p, ln.buf[k]); };
@@ -55,7 +63,12 @@ void lane_views(Lane &ln) {
     at(kTailO, ln.tail.O); at(kTailD, ln.tail.D); at(kTailC, ln.tail.C); at(kPid, ln.pid);
     at(kOcc, ln.d_occ); at(kAovRec, ln.aov);
     at(kPathW, ln.paths.W); at(kTailW, ln.tail.W);
+    at(kAlphaO, ln.alpha.RO); at(kAlphaD, ln.alpha.RD); at(kAlphaList0, ln.alpha.list[0]); at(kAlphaList1, ln.alpha.list[1]);
+    at(kAlphaHits, ln.alpha.hits);
 }
+}  // namespace pt_host
+
+namespace {
 
 void free_batch(Lane &ln) {
     for (void *&p : ln.buf) dfree(p);
@@ -155,11 +168,11 @@ hipError_t sync_all(ptmi_ctx *c) {
     return e;
 }
 
-size_t bytes_per_path(bool aov, bool env_w) { return lane_bytes_per_path(aov, env_w); }
+size_t bytes_per_path(bool aov, bool env_w, bool alpha) { return lane_bytes_per_path(aov, env_w, alpha); }
 
 int ensure_capacity(ptmi_ctx *c, Lane &ln, size_t n) {
-    const bool aov = c->aov_mask != 0, env_w = c->sc.env.sampled != 0;
-    if (n <= ln.cap && (!aov || ln.aov) && (!env_w || ln.paths.W)) return PTMI_OK;
+    const bool aov = c->aov_mask != 0, env_w = c->sc.env.sampled != 0, alpha = alpha_active(c);
+    if (n <= ln.cap && (!aov || ln.aov) && (!env_w || ln.paths.W) && (!alpha || ln.alpha.RO)) return PTMI_OK;
     HIP_TRY(c, sync_all(c));
     free_batch(ln);
     const size_t cap = (n + 1023) & ~(size_t)1023;
@@ -169,7 +182,7 @@ int ensure_capacity(ptmi_ctx *c, Lane &ln, size_t n) {
     hipError_t e = hipSuccess;
     size_t bytes = 0;
     for (int k = 0; k < kLaneBufs && e == hipSuccess; k++)
-        if (lane_buf_wanted(k, aov, env_w)) e = hipMalloc(&ln.buf[k], bytes = cap * kLaneBytes[k]);
+        if (lane_buf_wanted(k, aov, env_w, alpha)) e = hipMalloc(&ln.buf[k], bytes = cap * kLaneBytes[k]);
     if (e == hipSuccess) e = hipMalloc(&ln.alive, bytes = words * 8);
     if (e == hipSuccess) e = hipMalloc(&ln.shadowm, bytes = words * 8);
     if (e == hipSuccess) e = hipMalloc(&ln.word_off, bytes = 2 * tiles * 4);

@@ -8,6 +8,7 @@
 //   medium.hip         the participating medium: its checks, installation and removal, its debug entry points
 //   medium_grid.hip    the medium's density grid: its checks, upload and removal, its debug entry points
 //   scene_update.hip   edits of a loaded scene in place: ptmi_update_triangles (the refit on the device), _materials, _lights
+//   alpha.hip          alpha cutouts: the cutoff table, the two resolve loops between the existing kernels, their debug entry points
 #pragma once
 #include "ptmi.h"
 #include "pt_device.h"
@@ -39,6 +40,11 @@ int pt_check_medium_density(const float *rho, uint32_t nx, uint32_t ny, uint32_t
 // the medium of a context as it was set (NULL: none in place), and whether it carries a grid
 const ptmi_medium *pt_ctx_medium(const ptmi_ctx *c);
 bool pt_ctx_has_medium_grid(const ptmi_ctx *c);
+// the argument checks of ptmi_set_alpha_cutoff that need no context (alpha.hip): PTMI_E_INVALID with the reason in err; cutoff NULL
+// (removal) checks the params alone. And what its other checks compare with: whether c has a scene, and how many materials.
+int pt_check_alpha_cutoff(const float *cutoff, uint32_t n_materials, const ptmi_alpha_params *params, std::string &err);
+bool pt_ctx_has_scene(const ptmi_ctx *c);
+uint32_t pt_ctx_materials(const ptmi_ctx *c);
 hipStream_t pt_ctx_stream(ptmi_ctx *c);
 float4 *pt_ctx_output(ptmi_ctx *c);
 int pt_ctx_device(const ptmi_ctx *c);
@@ -73,6 +79,7 @@ enum SceneBuf {
     kPlanQnum,                         // per node of kWnodes, its number in kQnodes
     kPlanUnits, kPlanExact,            // own leaves: the unit box of every listed triangle (leaf order); both exact child boxes per node
     kPlanWords,                        // the reduction words of one update and the partial sums of the cost
+    kAlphaCutoff,                      // the per-material cutoff table of ptmi_set_alpha_cutoff (alpha.hip); gone with the next upload
     kSceneBufs
 };
 
@@ -101,6 +108,8 @@ enum LaneBuf {
     kAovRec,                                       // first-hit records of bounce 0 (k_shade<true>); only while AOV planes are on
     kPathW, kTailW,                                // the environment's MIS weight of a bounce ray, by path and (after the repack) by queue
                                                    // slot; only while a sampled environment is in place
+    kAlphaO, kAlphaD, kAlphaList0, kAlphaList1, kAlphaHits,   // alpha cutouts (pt_device.h DevAlpha): scratch rays, the two retry lists,
+                                                   // scratch hits; only while a cutoff table with a positive entry is in place
     kLaneBufs
 };
 
@@ -130,6 +139,7 @@ struct Lane {
     hipStream_t side = nullptr;           // `shadow` of bounce b beside the kernels of bounce b + 1
     hipEvent_t ev_ready = nullptr, ev_shadow[2] = {nullptr, nullptr};
     float4 *aov = nullptr;                // first-hit records of bounce 0, 32 B per path (k_shade<true>); only while AOV planes are on
+    DevAlpha alpha{};                     // the alpha resolve loops' arrays (RO NULL: none); cutoff, control, stats and max_layers are set per use
 };
 
 struct ptmi_ctx {
@@ -149,6 +159,9 @@ struct ptmi_ctx {
     ptmi_medium medium{};                              // the medium as the caller gave it (ptmi_get_medium); DevScene::med.on: in place
     float *d_med_grid = nullptr;                       // the medium's density grid (DevScene::med.grid points at it; NULL: homogeneous)
     struct ptmi_medium_grid_status med_grid{};                // ... as ptmi_medium_grid_status reports it
+    // alpha cutouts (ptmi_set_alpha_cutoff; alpha.hip): the table is buf[kAlphaCutoff], one float per material of the loaded scene
+    bool alpha_present = false;                        // a table is in place
+    uint32_t alpha_cutout = 0, alpha_layers = 0;       // its positive entries (0: inactive, no launch and no buffer differs); max_layers, resolved
     DevScene *d_scene = nullptr;                       // sc in device memory (DevScene::self), rewritten whenever sc changes
     DevScene sc{};
     bool have_scene = false;
@@ -198,7 +211,8 @@ template <class T> T *plane_as(const ptmi_ctx *c, FramePlane k) { return static_
 // ptmi_api.hip
 void default_options(ptmi_options &o);
 hipError_t sync_all(ptmi_ctx *c);
-size_t bytes_per_path(bool aov, bool env_w);
+size_t bytes_per_path(bool aov, bool env_w, bool alpha);
+void lane_views(Lane &ln);
 int ensure_capacity(ptmi_ctx *c, Lane &ln, size_t n);
 enum PlaneGroup { kWithFrame, kByDenoise, kByAdaptive, kByReproject, kByBlit };     // when a plane is made (the kFrame table)
 constexpr uint32_t bit(FramePlane k) { return 1u << k; }                            // sets of planes: a bit per FramePlane
@@ -210,6 +224,16 @@ int check_ready(ptmi_ctx *c, bool need_output);
 // dispatch.hip
 void drain_events(ptmi_ctx *c);
 hipError_t quiesce(ptmi_ctx *c);
+
+// alpha.hip. Active: a table with a positive entry is in place; only then do the loops run and the lane carry their arrays.
+inline bool alpha_active(const ptmi_ctx *c) { return c->alpha_cutout != 0u; }
+// the path loop on the *count hit records `extend` (variant cfg) has just written for the rays p.O / p.D at queue[i] (NULL: i), on stream s
+void alpha_resolve_paths(ptmi_ctx *c, hipStream_t s, const TraverseConfig &cfg, DevPaths p, const uint32_t *queue, const uint32_t *count,
+                         float2 *hits, uint32_t *layers_out);
+// the shadow stage of a bounce in place of the any-hit kernel: `extend` on the records, then the shadow loop. hits0: room for the first
+// trace's hits, one per queue entry (the bounce's hit array, which `shade` is done with)
+void alpha_shadow_stage(ptmi_ctx *c, hipStream_t s, const TraverseConfig &cfg, DevPaths p, DevShadow sh, const uint32_t *sq,
+                        const uint32_t *count, float2 *hits0, uint8_t *occ_out, uint32_t *layers_out);
 
 // traverse_pick.hip
 bool walks_memory_quantised(const TraverseConfig &cfg);

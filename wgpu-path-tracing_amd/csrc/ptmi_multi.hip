@@ -444,6 +444,34 @@ int ptmi_multi_upload_medium_density(ptmi_multi *m, const float *rho, uint32_t n
     return each_ctx(m, "ptmi_upload_medium_density", ptmi_upload_medium_density, rho, nx, ny, nz, params);
 }
 
+// The alpha cutoff table on every device (alpha.hip). Every device holds the same scene, so device 0's answers the checks that need one.
+int ptmi_multi_set_alpha_cutoff(ptmi_multi *m, const float *cutoff, uint32_t n_materials, const ptmi_alpha_params *params) {
+    if (!m) return PTMI_E_INVALID;
+    std::string why;                        // checked once, before any device changes: a rejected table leaves every shard's in place
+    if (!pt_ctx_has_scene(m->ctx[0])) return mfail(m, PTMI_E_INVALID, "no scene uploaded: the table belongs to a scene's materials");
+    const bool remove = !cutoff || n_materials == 0u;
+    const int rc = pt_check_alpha_cutoff(remove ? nullptr : cutoff, n_materials, params, why);
+    if (rc) return mfail(m, rc, "%s", why.c_str());
+    if (!remove && n_materials != pt_ctx_materials(m->ctx[0]))
+        return mfail(m, PTMI_E_INVALID, "n_materials %u is not the loaded scene's %u", n_materials, pt_ctx_materials(m->ctx[0]));
+    return each_ctx(m, "ptmi_set_alpha_cutoff", ptmi_set_alpha_cutoff, cutoff, n_materials, params);
+}
+
+int ptmi_multi_alpha_status(ptmi_multi *m, struct ptmi_alpha_status *out) {
+    if (!m || !out) return PTMI_E_INVALID;
+    for (int i = 0; i < (int)m->ctx.size(); i++) {
+        struct ptmi_alpha_status st;
+        const int rc = ptmi_alpha_status(m->ctx[i], &st);
+        if (rc) return cfail(m, i, rc, "ptmi_alpha_status");
+        if (i == 0) *out = st;
+        else {
+            out->path_passes += st.path_passes; out->path_exhausted += st.path_exhausted;
+            out->shadow_passes += st.shadow_passes; out->shadow_exhausted += st.shadow_exhausted;
+        }
+    }
+    return PTMI_OK;
+}
+
 // The edits of a loaded scene on every device (scene_update.hip). Every device holds the same scene under the same options and checks
 // before it changes anything, so a refused call is refused by the first device and leaves them all as they were.
 int ptmi_multi_update_triangles(ptmi_multi *m, uint32_t first, uint32_t count, const ptmi_triangle *tris) {

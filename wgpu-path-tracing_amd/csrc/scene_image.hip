@@ -441,6 +441,10 @@ int pt_install_scene(ptmi_ctx *c, PtPrepared *prep) {
     c->have_scene = true;
     c->n_ref_wnodes = (uint32_t)(b.buf[kRefWnodes].bytes / 64); c->tree_nested = b.nested;
     c->upd_planned = false; c->upd_ref_off.clear(); c->upd_off.clear(); c->upd = {};
+    // the alpha cutoff table belonged to the old scene's materials (its buffer went with the others above); the loops' arrays go too
+    c->alpha_present = false; c->alpha_cutout = c->alpha_layers = 0u;
+    for (int k = kAlphaO; k <= kAlphaHits; k++) dfree(c->lane.buf[k]);
+    lane_views(c->lane);
     c->st.leaves_used = h.leaves_used;
     c->st.leaf_tris_used = h.max_leaf_tris;
     c->st.tree_builder_used = b.tree_builder_used;

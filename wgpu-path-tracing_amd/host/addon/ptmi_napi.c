@@ -325,6 +325,39 @@ static napi_value js_scene_update_status(napi_env env, napi_callback_info info) 
     return out;
 }
 
+/* setAlphaCutoff(handle, Float32Array | null, maxLayers): ptmi_set_alpha_cutoff; one cutoff per uploaded material, null removes the table */
+static napi_value js_set_alpha_cutoff(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    handle *h = get_handle(env, info, 3, argv);
+    if (!h) return NULL;
+    void *p; size_t n;
+    ptmi_alpha_params prm = {0};
+    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
+    napi_get_value_uint32(env, argv[2], &prm.max_layers);
+    if (n % sizeof(float)) { napi_throw_range_error(env, NULL, "cutoff table is not whole floats"); return NULL; }
+    CALL(env, h, set_alpha_cutoff, (const float *)p, (uint32_t)(n / sizeof(float)), &prm);
+    return NULL;
+}
+
+/* alphaStatus(handle) -> {present, materials, cutout, maxLayers, pathPasses, pathExhausted, shadowPasses, shadowExhausted} */
+static napi_value js_alpha_status(napi_env env, napi_callback_info info) {
+    napi_value argv[1], out, v;
+    handle *h = get_handle(env, info, 1, argv);
+    if (!h) return NULL;
+    struct ptmi_alpha_status st;
+    CALL(env, h, alpha_status, &st);
+    NAPI_OK(env, napi_create_object(env, &out));
+    const struct { const char *name; double value; } num[] = {
+        {"present", st.present}, {"materials", st.n_materials}, {"cutout", st.n_cutout}, {"maxLayers", st.max_layers},
+        {"pathPasses", (double)st.path_passes}, {"pathExhausted", (double)st.path_exhausted},
+        {"shadowPasses", (double)st.shadow_passes}, {"shadowExhausted", (double)st.shadow_exhausted}};
+    for (size_t i = 0; i < sizeof num / sizeof num[0]; i++) {
+        NAPI_OK(env, napi_create_double(env, num[i].value, &v));
+        NAPI_OK(env, napi_set_named_property(env, out, num[i].name, v));
+    }
+    return out;
+}
+
 static napi_value js_resize(napi_env env, napi_callback_info info) {
     napi_value argv[3];
     handle *h = get_handle(env, info, 3, argv);
@@ -783,6 +816,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"abiVersion", js_abi_version}, {"create", js_create}, {"multiCreate", js_multi_create}, {"destroy", js_destroy},
         {"uploadScene", js_upload_scene}, {"uploadAtlas", js_upload_atlas}, {"uploadEnvironment", js_upload_environment}, {"setMedium", js_set_medium}, {"uploadMediumDensity", js_upload_medium_density},
         {"updateTriangles", js_update_triangles}, {"updateMaterials", js_update_materials}, {"updateLights", js_update_lights}, {"sceneUpdateStatus", js_scene_update_status},
+        {"setAlphaCutoff", js_set_alpha_cutoff}, {"alphaStatus", js_alpha_status},
         {"resize", js_resize}, {"setOptions", js_set_options},
         {"dispatch", js_dispatch}, {"gather", js_gather}, {"gatherPlanes", js_gather_planes}, {"synchronize", js_synchronize}, {"throttle", js_throttle},
         {"readOutput", js_read_output}, {"writeOutput", js_write_output}, {"setAovs", js_set_aovs}, {"readAov", js_read_aov},

@@ -95,8 +95,10 @@ function resample(img, dx, dy, dw, dh) {
 
 function halfUp(v) { return Math.min(255, Math.max(0, Math.floor(v + 0.5))); }
 
-/** atlas.ts:97-184: the size x size RGBA8 canvas */
-function buildCanvas(size, entries) {
+/** atlas.ts:97-184: the size x size RGBA8 canvas. keepAlpha (alpha cutouts, renderer.js alphaCutout): an albedo map's resampled
+ *  alpha stays in the canvas's alpha channel instead of being composited away; no other byte differs, and no kernel reads that
+ *  channel except for a material with a cutoff */
+function buildCanvas(size, entries, keepAlpha) {
   var canvas = new Uint8Array(size * size * 4);
   for (var p = 0; p < size * size; p++) canvas[p * 4 + 3] = 255;                // fillStyle 'black'
   function draw(info, texInfo, isAlbedo) {
@@ -117,6 +119,7 @@ function buildCanvas(size, entries) {
         if (x < 0 || y < 0 || x >= size || y >= size) continue;
         var d = (y * size + x) * 4;                                             // source-over on opaque black
         canvas[d] = halfUp(r); canvas[d + 1] = halfUp(g); canvas[d + 2] = halfUp(b);
+        if (keepAlpha && isAlbedo) canvas[d + 3] = halfUp(a);
       }
     }
   }
@@ -162,8 +165,9 @@ function canvasToHalf(rgba8) {
 /**
  * atlas.ts:33-75. gltf.materials carry resolved texture references ({texture: {source: {image}}}, as after
  * postProcessGLTF). Returns { texture: {width, height, rgba8, data (f16 bits), format: 1}, materials: Map }.
+ * opts.keepAlpha: see buildCanvas.
  */
-function packing(gltf) {
+function packing(gltf, opts) {
   var boxes = [], materials = new Map(), entries = [];
   (gltf.materials || []).forEach(function (m) {
     var pbr = m.pbrMetallicRoughness || {};
@@ -176,7 +180,7 @@ function packing(gltf) {
   });
   var packed = potpack(boxes);
   var size = Math.max(1, Math.pow(2, Math.ceil(Math.log2(Math.max(packed.w, packed.h)))));
-  var rgba8 = buildCanvas(size, entries);
+  var rgba8 = buildCanvas(size, entries, !!(opts && opts.keepAlpha));
   return {
     texture: { width: size, height: size, rgba8: rgba8, data: canvasToHalf(rgba8), format: 1 },
     materials: materials, packed: packed,

@@ -55,10 +55,20 @@ export class Renderer {
    *  device through RCCL and with several contexts on one device (`loopback: true`); more than one device over RCCL has never run —
    *  no machine this was built on has two GPUs. */
   constructor(options?: { device?: number; devices?: number[]; loopback?: boolean; gatherEvery?: number; maxFramesPerTick?: number;
-                          width?: number; height?: number; options?: TraceOptions; adaptive?: AdaptiveParams });
+                          width?: number; height?: number; options?: TraceOptions; adaptive?: AdaptiveParams;
+                          /** loadModel of a .glb keeps the alpha of albedo maps in the atlas and makes every alphaMode "MASK" material a
+                           *  cutout at its alphaCutoff (default 0.5); off (the default): the atlas bytes and everything else as without */
+                          alphaCutout?: boolean;
+                          /** ... with this maxLayers (0 / absent: the library's default, 4) */
+                          alphaLayers?: number });
   camera: CameraCPU;
   addOnUpdate(callback: (deltaTime: number) => void): void;
-  loadModel(model: string | SceneData | { blobs: SceneBlobs; atlas?: Atlas | null }, atlas?: Atlas): Promise<void>;
+  loadModel(model: string | SceneData | { blobs: SceneBlobs; atlas?: Atlas | null; alphaCutoff?: Float32Array }, atlas?: Atlas): Promise<void>;
+  /** alpha cutouts (include/ptmi.h ptmi_set_alpha_cutoff): one cutoff per material of the loaded scene, 0 opaque, > 0: a hit is absent
+   *  where the albedo map's alpha is below it; null removes the table, and so does loadModel. Restarts accumulation. */
+  setAlphaCutoff(cutoff: Float32Array | null, opts?: { maxLayers?: number }): void;
+  /** the table in place and what its loops counted since the statistics were reset; synchronises */
+  alphaStatus(): AlphaStatus;
   /** the environment map behind every miss: float32 RGBA texels, equirectangular, row 0 at the +Y pole; null removes it.
    *  Restarts accumulation. */
   setEnvironment(texels: Float32Array | null, width?: number, height?: number, opts?: EnvironmentOptions): void;
@@ -143,6 +153,11 @@ export interface MediumOptions {
   /** the medium's box, or 'scene': the root box of the scene loaded last */
   bounds: { min: [number, number, number]; max: [number, number, number] } | 'scene';
 }
+/** ptmi_alpha_status: passes = holes passed, exhausted = rays still on a hole after maxLayers */
+export interface AlphaStatus {
+  present: number; materials: number; cutout: number; maxLayers: number;
+  pathPasses: number; pathExhausted: number; shadowPasses: number; shadowExhausted: number;
+}
 /** ptmi_scene_update_status: the triangle updates since the scene was loaded */
 export interface SceneUpdateStatus {
   updates: number; quantisedKept: number; planMs: number; refitMs: number;
@@ -176,7 +191,8 @@ export interface PackedAtlas {
 }
 export const atlas: {
   potpack(boxes: { w: number; h: number; x?: number; y?: number }[]): { w: number; h: number; fill: number };
-  packing(gltf: { materials: object[] }): PackedAtlas;
+  /** keepAlpha: albedo maps keep their resampled alpha in the canvas's alpha channel (no other byte differs) */
+  packing(gltf: { materials: object[] }, opts?: { keepAlpha?: boolean }): PackedAtlas;
 };
 export function decodePNG(data: Uint8Array): { width: number; height: number; data: Uint8Array };
 /** jpeg_decode.js — sequential and progressive Huffman JPEG, bit-identical to libjpeg-turbo's default decode */

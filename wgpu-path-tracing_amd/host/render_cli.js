@@ -8,7 +8,8 @@
  *                       --adaptive THRESHOLD --max-frames N --rounds R
  *                       --env file.hdr --env-intensity X --env-rotation DEGREES --env-sample 0|1
  *                       --fog sigma_t[,albedo[,g]] --fog-density file.f32 --fog-grid nx,ny,nz --fog-filter nearest|linear
- *                       --devices 0,1,... --loopback --aov albedo|normal|id --aov-out plane.bin]
+ *                       --devices 0,1,... --loopback --aov albedo|normal|id --aov-out plane.bin
+ *                       --alpha-cutout --alpha-layers N]
  * --batch K traces K frames per dispatch instead of one. --denoise keeps the denoiser's planes and makes --png the tone-mapped
  * denoised image (include/ptmi.h ptmi_denoise, default parameters). --adaptive renders to a noise level instead of --frames
  * (include/ptmi.h ptmi_dispatch_adaptive): rounds until none lists a pixel, or --rounds R of them; the JSON line then also holds
@@ -22,6 +23,9 @@
  * --denoise) and prints one JSON line with the statistics. --devices renders on several GPUs behind one Renderer (include/ptmi.h
  * ptmi_multi_*; --loopback lets one ordinal be listed more than once, for a one-GPU box); --adaptive, --denoise and --aov work with
  * it. --aov keeps that first-hit plane and --aov-out writes it raw (float32 x 4 per pixel, uint32 x 2 for id).
+ * --alpha-cutout (a .glb scene): materials with alphaMode "MASK" become cutouts at their alphaCutoff (include/ptmi.h
+ * ptmi_set_alpha_cutoff): the atlas keeps the alpha of albedo maps, and paths and shadow rays pass where it is below the cutoff, through
+ * at most --alpha-layers N holes per segment (default: the library's, 4); the JSON line then also holds alpha: the table's status.
  */
 var fs = require('fs');
 var host = require('./renderer');
@@ -44,7 +48,9 @@ function textArg(name) {
 var devices = textArg('devices') ? textArg('devices').split(',').map(Number) : null;
 var aov = textArg('aov');
 
+var alphaCutout = process.argv.indexOf('--alpha-cutout') >= 0;
 var r = new host.Renderer({ width: W, height: H, devices: devices || undefined, loopback: process.argv.indexOf('--loopback') >= 0,
+                            alphaCutout: alphaCutout, alphaLayers: arg('alpha-layers', 0),
                             options: { maxBounces: arg('bounces', 8), doMis: arg('mis', 1) } });
 r.camera.aperture = arg('aperture', r.camera.aperture);
 r.camera.focusDistance = arg('focus', r.camera.focusDistance);
@@ -101,6 +107,7 @@ r.loadModel(scenePath).then(function () {
   var st = r.getStats();
   st.wallMs = ms; st.width = W; st.height = H; st.frames = frames;
   if (status) st.frames = 0;                // no uniform frames: the counts are per pixel
+  if (alphaCutout) st.alpha = r.alphaStatus();
   if (status) st.adaptive = { samples: status.samples, minCount: status.minCount, maxCount: status.maxCount, rounds: status.rounds };
   console.log(JSON.stringify(st));
   r.destroy();

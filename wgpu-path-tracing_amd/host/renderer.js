@@ -51,6 +51,8 @@ function Renderer(options) {
   this.timer = null;
   this.lastTime = 0;
   this.sceneLoaded = false;
+  this.alphaCutout = !!options.alphaCutout;             // loadModel of a .glb keeps albedo alpha and sets the MASK materials' cutoffs
+  this.alphaLayers = options.alphaLayers || 0;          // ... with this maxLayers (0: the library's default)
   this.cameraBytes = new ArrayBuffer(pack.CAMERA_SIZE);
   this.setupCamera();
   this.addon.resize(this.ctx, this.width, this.height);
@@ -82,15 +84,17 @@ Renderer.prototype.addOnUpdate = function (callback) { this.onUpdateTasks.push(c
 Renderer.prototype.loadModel = function (model, atlas) {
   var self = this;
   return new Promise(function (resolve) {
-    var blobs;
+    var blobs, cutoff = null;
     if (typeof model === 'string' && /\.glb$/i.test(model)) {
-      var prepared = require('./scene_prep').prepareScene(require('./gltf').loadGLB(model));
+      var prepared = require('./scene_prep').prepareScene(require('./gltf').loadGLB(model), { alphaCutout: self.alphaCutout });
       blobs = prepared.blobs; atlas = atlas || prepared.atlas; self.sceneInfo = prepared;
+      cutoff = prepared.alphaCutoff || null;
     } else if (typeof model === 'string') {
       var f = sceneFile.readSceneFile(model);
       blobs = f.blobs; atlas = atlas || f.atlas;
     } else if (model.blobs) {
       blobs = model.blobs; atlas = atlas || model.atlas;
+      if (self.alphaCutout) cutoff = model.alphaCutoff || null;         // what prepareScene({alphaCutout: true}) returned
     } else {
       blobs = pack.packScene(model);
     }
@@ -98,6 +102,8 @@ Renderer.prototype.loadModel = function (model, atlas) {
     self.sceneBounds = rootBox(blobs.bvhNodes);       // setMedium({ bounds: 'scene' })
     if (atlas) self.addon.uploadAtlas(self.ctx, atlas.data, atlas.width, atlas.height, atlas.format || 1);
     else self.addon.uploadAtlas(self.ctx, null, 0, 0, 0);
+    // (the upload removed any table: it belonged to the old scene's materials)
+    if (cutoff) self.addon.setAlphaCutoff(self.ctx, cutoff, self.alphaLayers);
     self.sceneLoaded = true;
     self.resetOutputBuffer(false);
     resolve();
@@ -259,6 +265,22 @@ Renderer.prototype.updateLights = function (first, blob) {
 Renderer.prototype.sceneUpdateStatus = function () {
   return this.addon.sceneUpdateStatus(this.ctx);
 };
+
+/**
+ * Alpha cutouts (include/ptmi.h ptmi_set_alpha_cutoff): a Float32Array with one cutoff per material of the loaded scene — 0 opaque,
+ * > 0: a hit is absent where the albedo map's alpha is below it (glTF alphaMode MASK) — or null to remove the table. opts:
+ * { maxLayers (holes one ray may pass per segment, 1 .. 32; 0 / absent: the default, 4) }. new Renderer({ alphaCutout: true }) does
+ * this on loadModel of a .glb from its materials' alphaMode / alphaCutoff. loadModel removes the table. Accumulation restarts.
+ */
+Renderer.prototype.setAlphaCutoff = function (cutoff, opts) {
+  if (cutoff && !(cutoff instanceof Float32Array)) throw new TypeError('setAlphaCutoff: cutoff must be a Float32Array or null');
+  if (cutoff && !this.sceneLoaded) throw new Error('setAlphaCutoff: needs a loaded scene (loadModel)');
+  this.addon.setAlphaCutoff(this.ctx, cutoff || null, (opts && opts.maxLayers) || 0);
+  this.frameIndex = 0;
+};
+/** { present, materials, cutout, maxLayers, pathPasses, pathExhausted, shadowPasses, shadowExhausted } (include/ptmi.h
+ *  ptmi_alpha_status): the table in place and what its loops counted since resetStats; synchronises */
+Renderer.prototype.alphaStatus = function () { return this.addon.alphaStatus(this.ctx); };
 
 /** why ptmi_upload_medium_density would refuse rho over dims on medium m with sigmaT times scale (include/ptmi.h), or null */
 function refusal(rho, dims, m, scale) {

@@ -107,10 +107,19 @@ function processNode(gltf, node, allTriangles, allMaterials, allLights, world, a
   }
 }
 
-/** loader.ts:20-40 + gpu.ts:67-150 -> { blobs, atlas, counts, bvhDepth } */
-function prepareScene(gltf) {
-  var packed = require('./atlas').packing(gltf);
-  var allTriangles = [], allMaterials = [], allLights = [];
+/** glTF's alpha rule for one material as a cutoff of the alpha table (include/ptmi.h ptmi_set_alpha_cutoff): alphaMode "MASK" cuts
+ *  at alphaCutoff (default 0.5); "OPAQUE", "BLEND" (a limit: it stays opaque) and a primitive without a material are 0 */
+function alphaCutoffOf(material) {
+  if (!material || material.alphaMode !== 'MASK') return 0;
+  return material.alphaCutoff === undefined || material.alphaCutoff === null ? 0.5 : material.alphaCutoff;
+}
+
+/** loader.ts:20-40 + gpu.ts:67-150 -> { blobs, atlas, counts, bvhDepth }. opts.alphaCutout: the atlas keeps the alpha of albedo maps
+ *  and the result carries alphaCutoff, a Float32Array with one cutoff per packed material (else: neither, and every byte as without) */
+function prepareScene(gltf, opts) {
+  var alphaCutout = !!(opts && opts.alphaCutout);
+  var packed = require('./atlas').packing(gltf, { keepAlpha: alphaCutout });
+  var allTriangles = [], allMaterials = [], allLights = [], allCutoffs = [];
   var parent = new Map();
   gltf.nodes.forEach(function (n) { (n.children || []).forEach(function (c) { parent.set(c, n); }); });
   var world = new Map();
@@ -120,7 +129,11 @@ function prepareScene(gltf) {
     while (parent.has(cur)) { cur = parent.get(cur); M.mul(extractNodeMatrix(cur), w, w); }
     world.set(node, w);
   });
-  gltf.nodes.forEach(function (node) { processNode(gltf, node, allTriangles, allMaterials, allLights, world.get(node), packed.materials); });
+  gltf.nodes.forEach(function (node) {
+    processNode(gltf, node, allTriangles, allMaterials, allLights, world.get(node), packed.materials);
+    // one material per primitive, in the order processNode packs them
+    if (alphaCutout && node.mesh) node.mesh.primitives.forEach(function (prim) { allCutoffs.push(alphaCutoffOf(prim.material)); });
+  });
 
   var triangles = pack.packTriangles(allTriangles);             // sorted in place by the BVH build
   var materials = pack.packMaterials(allMaterials);
@@ -129,6 +142,7 @@ function prepareScene(gltf) {
   var lights = a.emissiveLights(triangles, materials, pack.packLights(allLights));
   return {
     blobs: { triangles: triangles, materials: materials, bvhNodes: bvh.nodes, lights: lights },
+    alphaCutoff: alphaCutout ? new Float32Array(allCutoffs) : undefined,
     atlas: packed.texture,
     counts: { triangles: allTriangles.length, materials: allMaterials.length, bvhNodes: bvh.nodes.byteLength / pack.BVH_NODE_SIZE,
       lights: lights.byteLength / pack.LIGHT_SIZE, punctualLights: allLights.length },
@@ -136,4 +150,4 @@ function prepareScene(gltf) {
   };
 }
 
-module.exports = { prepareScene: prepareScene, extractNodeMatrix: extractNodeMatrix, buildMaterial: buildMaterial };
+module.exports = { prepareScene: prepareScene, extractNodeMatrix: extractNodeMatrix, buildMaterial: buildMaterial, alphaCutoffOf: alphaCutoffOf };

@@ -44,6 +44,8 @@ EXPORTS = [
     "ptmi_debug_medium_track", "ptmi_debug_medium_grid_check",
     "ptmi_update_triangles", "ptmi_update_materials", "ptmi_update_lights", "ptmi_scene_update_status",
     "ptmi_multi_update_triangles", "ptmi_multi_update_materials", "ptmi_multi_update_lights", "ptmi_multi_scene_update_status",
+    "ptmi_set_alpha_cutoff", "ptmi_alpha_status", "ptmi_multi_set_alpha_cutoff", "ptmi_multi_alpha_status",
+    "ptmi_debug_alpha_intersect", "ptmi_debug_alpha_occluded",
 ]
 MULTI_LOOPBACK = 1
 MULTI_PLANE_MOMENTS, MULTI_PLANE_OUTPUT = 0x100, 0x200      # gather_planes: with the AOV_* bits
@@ -157,6 +159,21 @@ class SceneUpdateStatus(ctypes.Structure):
                 "root_box": (tuple(self.root_min), tuple(self.root_max))}
 
 
+class AlphaParams(ctypes.Structure):
+    """ptmi_alpha_params; max_layers 0 picks the default (include/ptmi.h)"""
+    _fields_ = [("max_layers", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+class AlphaStatus(ctypes.Structure):
+    """struct ptmi_alpha_status: the cutoff table in place and what its loops counted since reset_stats (include/ptmi.h)"""
+    _fields_ = [("present", ctypes.c_uint32), ("n_materials", ctypes.c_uint32), ("n_cutout", ctypes.c_uint32),
+                ("max_layers", ctypes.c_uint32), ("path_passes", ctypes.c_uint64), ("path_exhausted", ctypes.c_uint64),
+                ("shadow_passes", ctypes.c_uint64), ("shadow_exhausted", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class Stats(ctypes.Structure):
     _fields_ = [("paths", ctypes.c_uint64), ("segments", ctypes.c_uint64), ("shadow_rays", ctypes.c_uint64),
                 ("dispatches", ctypes.c_uint64), ("frames", ctypes.c_uint64),
@@ -199,6 +216,7 @@ _SHARED = {
     "update_materials": [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p],
     "update_lights": [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p],
     "scene_update_status": [ctypes.c_void_p],
+    "set_alpha_cutoff": [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p], "alpha_status": [ctypes.c_void_p],
 }
 _lib = None
 
@@ -260,6 +278,8 @@ def load():
         L.ptmi_debug_medium_density.argtypes = [vp, u32, vp, vp]
         L.ptmi_debug_medium_grid_check.argtypes = [vp, vp, u32, u32, u32, vp, vp]
         L.ptmi_debug_medium_track.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+        L.ptmi_debug_alpha_intersect.argtypes = [vp, u32, vp, vp, vp, vp, vp]
+        L.ptmi_debug_alpha_occluded.argtypes = [vp, u32, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -449,6 +469,23 @@ class _Handle:
     def scene_update_status(self):
         st = SceneUpdateStatus()
         self._ck(self._c.scene_update_status(self.h, ctypes.byref(st)))
+        return st
+
+    # -- alpha cutouts (include/ptmi.h ptmi_set_alpha_cutoff) ---------------------------------------------------------
+    def set_alpha_cutoff(self, cutoff, max_layers=0, reserved=(0, 0, 0), n_materials=None):
+        """The per-material cutoff table of the loaded scene: one float per uploaded material, 0 = opaque, > 0 = a hit is absent
+        where the albedo map's alpha is below it. cutoff None removes the table. max_layers 0 picks the default; n_materials
+        overrides the array's length (for tests)."""
+        prm = AlphaParams(max_layers, (ctypes.c_uint32 * 3)(*reserved))
+        if cutoff is None:
+            self._ck(self._c.set_alpha_cutoff(self.h, None, 0, ctypes.byref(prm)))
+            return
+        a = np.ascontiguousarray(cutoff, np.float32).reshape(-1)
+        self._ck(self._c.set_alpha_cutoff(self.h, _p(a), len(a) if n_materials is None else n_materials, ctypes.byref(prm)))
+
+    def alpha_status(self):
+        st = AlphaStatus()
+        self._ck(self._c.alpha_status(self.h, ctypes.byref(st)))
         return st
 
     def upload_environment(self, texels, intensity=0.0, rotation=0.0, sample=0, reserved=(0, 0, 0, 0, 0)):
@@ -769,6 +806,22 @@ class Context(_Handle):
         occ = np.zeros(len(o), np.uint8)
         self._ck(self.L.ptmi_debug_occluded(self.h, len(o), _p(o), _p(d), _p(dist), _p(occ)))
         return occ
+
+    def debug_alpha_intersect(self, o, d):
+        """debug_intersect through the path loop of the active cutoff table: (t along the given ray, triangle, holes passed)"""
+        o, d = np.ascontiguousarray(o, np.float32), np.ascontiguousarray(d, np.float32)
+        n = len(o)
+        t, tri, layers = np.zeros(n, np.float32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        self._ck(self.L.ptmi_debug_alpha_intersect(self.h, n, _p(o), _p(d), _p(t), _p(tri), _p(layers)))
+        return t, tri, layers
+
+    def debug_alpha_occluded(self, o, d, dist):
+        """debug_occluded through the shadow loop of the active cutoff table: (occluded, holes passed)"""
+        o, d = np.ascontiguousarray(o, np.float32), np.ascontiguousarray(d, np.float32)
+        dist = np.ascontiguousarray(dist, np.float32)
+        occ, layers = np.zeros(len(o), np.uint8), np.zeros(len(o), np.uint32)
+        self._ck(self.L.ptmi_debug_alpha_occluded(self.h, len(o), _p(o), _p(d), _p(dist), _p(occ), _p(layers)))
+        return occ, layers
 
     def debug_math(self, op, a, b=None, c=None):
         a = np.ascontiguousarray(a, np.float32)

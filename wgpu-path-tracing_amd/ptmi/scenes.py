@@ -13,6 +13,8 @@ Scenes
                       textures incl. a normal map, point + directional + emissive lights)
   texture_edges()     the atlas lookup at its edges: non-square atlases (f16 or f32), rects at and
                       past the last row and column, f16 specials, an emissive-mapped probe wall
+  cornell_fence()     the enclosed Cornell box behind "fences" of 8 x 8 cells whose albedo texels carry a
+                      per-cell alpha: the scene of the alpha-cutout tests and of tools/alpha_cutout_cost.py
 """
 from dataclasses import dataclass, field
 
@@ -382,6 +384,54 @@ def cornell_enclosed():
     for k in ("n0", "n1", "n2"):
         room[k] = -room[k]                      # the room is seen from inside
     return _finish("cornell_enclosed", [base.tris, room], base.mats)
+
+
+FENCE_CELLS = 8
+
+
+def cornell_fence(alpha=None, z=(0.4,), offset=(0.0, 0.0, 0.0), drop=None, fmt="f16", furniture=True):
+    """The enclosed Cornell box with a point light inside it and, across the box between the camera and the back wall, one fence per
+    entry of z: the plane z = z[f] over the box's whole cross-section as an 8 x 8 grid of cells, two triangles per cell. Fence f has a
+    material of its own whose albedo map is an 8 x 8 rect of the atlas, and all three uvs of a cell's triangles sit at the centre of that
+    cell's own texel, so a lookup never lands on a neighbouring texel. The ceiling emitter and the point light are behind every fence.
+    alpha [f, row, column]: the alpha of each cell's texel (default 1; row 0 is the bottom row). drop [f, row, column]: cells whose
+    triangles are left out. offset: a translation of all geometry and of the point light (the camera is the caller's). fmt: the atlas
+    format, 'f16' or 'f32'. furniture=False leaves the two boxes and the sphere out (the material table stays). info: 'fence_materials', the material index of each fence; 'fence_rects', its albedo rect."""
+    nf, n = len(z), FENCE_CELLS
+    alpha = np.ones((nf, n, n), np.float32) if alpha is None else np.asarray(alpha, np.float32).reshape(nf, n, n)
+    drop = np.zeros((nf, n, n), bool) if drop is None else np.asarray(drop, bool).reshape(nf, n, n)
+    base = cornell()
+    room = _box((0.0, 2.0, 1.5), (8.0, 6.0, 9.0), 0)
+    for k in ("n0", "n1", "n2"):
+        room[k] = -room[k]
+    mats = list(base.mats)
+    parts = [base.tris if furniture else base.tris[base.tris["material_index"] < 4], room]
+    atlas = np.zeros((n, n * nf, 4), np.float32)
+    rects = []
+    for f in range(nf):
+        rects.append((n * f, 0, n, n))
+        atlas[:, n * f:n * (f + 1), :3] = (0.75, 0.6, 0.3)
+        atlas[:, n * f:n * (f + 1), 3] = alpha[f]
+        mats.append(_material((1.0, 1.0, 1.0), roughness=0.8, albedo_map=rects[f]))
+        xs, ys = np.linspace(-_ROOM_X, _ROOM_X, n + 1), np.linspace(0.0, _ROOM_Y, n + 1)
+        for j in range(n):
+            for i in range(n):
+                if drop[f, j, i]:
+                    continue
+                c = ((i + 0.5) / n, (j + 0.5) / n)
+                parts.append(_uv_quad((xs[i], ys[j], z[f]), (xs[i + 1], ys[j], z[f]), (xs[i + 1], ys[j + 1], z[f]), (xs[i], ys[j + 1], z[f]),
+                                      (0, 0, 1), len(mats) - 1, [c, c, c, c]))
+    punctual = np.zeros(1, layout.LIGHT)
+    punctual[0]["position"], punctual[0]["light_type"] = (0.3, 1.4, -0.4), layout.LIGHT_POINT
+    punctual[0]["color"], punctual[0]["intensity"] = (1.0, 0.9, 0.8), 2.0
+    tris = np.concatenate(parts)
+    off = np.asarray(offset, np.float32)
+    if off.any():
+        for k in ("v0", "v1", "v2"):
+            tris[k] = tris[k] + off
+        punctual[0]["position"] = punctual[0]["position"] + off
+    return _finish("cornell_fence", [tris], mats, punctual=punctual, atlas=np.ascontiguousarray(atlas.astype(np.float16 if fmt == "f16" else np.float32)),
+                   info={"fence_materials": list(range(len(base.mats), len(mats))), "fence_rects": rects})
 
 
 # f16 values texture_edges places at known texels: signed zeros, the smallest and largest subnormal, the largest finite value,
