@@ -375,6 +375,59 @@ struct ptmi_reproject_status { uint64_t carried, disoccluded, missed, samples; }
 int ptmi_reproject(ptmi_ctx *ctx, const ptmi_camera *from, const ptmi_camera *to, const ptmi_reproject_params *params);
 int ptmi_reproject_status(ptmi_ctx *ctx, struct ptmi_reproject_status *out);    /* synchronises */
 
+/* ---- motion: carry the samples across a geometry edit too ------------------------------------
+ * ptmi_reproject as stated above projects the new hit point into the old camera, which is the wrong place in the old image for a
+ * surface that ptmi_update_triangles has moved since the history was rendered. With motion on, the context keeps the vertex
+ * positions the history was rendered with (the previous positions: v0, v1, v2 as three float4 with w = 0, 48 bytes per uploaded
+ * triangle) and the range of triangles updated since (the dirty range), ptmi_reproject projects a hit on a moved triangle from where
+ * its point was, and the per-pixel screen motion is written to a plane: the guide temporal denoisers and upscalers ask for beside
+ * albedo, normal and depth. A post-process, off by default: while off every call issues the launches and gives the bits it gave
+ * before, and no buffer is allocated.
+ *   ptmi_set_motion(1) allocates the previous positions (filled from the triangles now on the device; with the other scene buffers)
+ *     and the motion plane (width*height float4, zero-filled; re-made zero-filled by ptmi_resize like an AOV plane), clears the dirty
+ *     range and sets epochs to 0. Allowed before an upload or a resize: the buffers then appear with the scene and the size. A failed
+ *     call leaves the previous state in place. ptmi_set_motion(0) frees both.
+ *   ptmi_upload_scene while on re-makes the previous positions from the new scene, clears the dirty range, epochs = 0.
+ *   ptmi_update_triangles while on does its work unchanged and widens the dirty range to the union with [first, first + count). The
+ *     previous positions are not touched: several updates between two commits accumulate against the same epoch.
+ *   ptmi_motion_commit copies the current v0, v1, v2 over the dirty range into the previous positions (one kernel), clears the range
+ *     and increments epochs. A host that restarts accumulation with a frame-0 dispatch after an edit calls it: the history is then
+ *     rendered with the current geometry. Asynchronous on the context's stream. PTMI_E_STATE while off.
+ *   ptmi_reproject while on runs its steps 1 to 3, recomputes (u, v) of the centre rays' resolved hits as ptmi_debug_intersect
+ *     reports them, runs step 4 with the moved rule, writes the motion plane for every pixel of the context's rows, and commits at
+ *     its end as ptmi_motion_commit does. A failed call writes nothing and commits nothing.
+ * The moved rule. A hit on triangle tri is MOVED iff tri lies in the dirty range AND at least one of the nine previous-position
+ * floats of tri differs in its bits from the current v0, v1, v2. A MOVED hit computes, with (u, v) as ptmi_debug_intersect reports
+ * them for that ray, in float32, left to right, no FMA, per component k:
+ *     e1_k = v1p_k - v0p_k,  e2_k = v2p_k - v0p_k,  Pprev_k = (v0p_k + u * e1_k) + v * e2_k      (v0p, v1p, v2p: the previous positions)
+ * and v = Pprev - from.position replaces v = P - from.position in step 4. Everything after it is unchanged: zf, dist, sx, sy, fx, fy,
+ * the four taps, the depth and id tests, the blends, the counts, and normal.w = t of the NEW hit. A hit that is not MOVED uses
+ * P = o + t d exactly as before: motion on with no edit gives the bits of motion off, pixel for pixel, and triangles outside the dirty
+ * range cost nothing extra (the range bounds are kernel arguments, so the test is uniform for most waves).
+ * The motion plane at a pixel (px, py) of the context's rows (integer coordinates as floats, row 0 at the bottom like the output
+ * buffer), from the fx, fy, dist its rule computed: x = fx - px, y = fy - py: where the surface was in `from`, in pixels, relative
+ * to the pixel; z = dist; w = 0 / 1 / 2 for CARRIED / DISOCCLUDED / MISSED. x = y = z = 0 on a miss, where !(zf > 0), or where fx or
+ * fy is not finite. Rows of other contexts are not written.
+ * Limits. The carried radiance and normals are the old ones: moved lighting, shadows cast by the moved object and rotated normals
+ * are stale until new frames dilute them; max_history is the bound, as in Schied et al. 2017. Topology changes are out of scope
+ * (ptmi_update_triangles never changes it; an upload restarts). With an alpha cutoff table active, (u, v) are those of the resolved
+ * hit on the caller's centre ray. There is no ptmi_multi counterpart, because reprojection has none. */
+int ptmi_set_motion(ptmi_ctx *ctx, uint32_t on);          /* 0 / 1, else PTMI_E_INVALID; synchronises */
+int ptmi_get_motion(const ptmi_ctx *ctx, uint32_t *on);
+int ptmi_motion_commit(ptmi_ctx *ctx);                    /* previous positions := current, over the dirty range */
+struct ptmi_motion_status {              /* 32 bytes; a struct tag only, like ptmi_reproject_status */
+    uint32_t on, epochs;                 /* commits since the last upload or ptmi_set_motion(1) */
+    uint32_t dirty_first, dirty_count;   /* union of the ranges updated since the last commit (0, 0: none) */
+    uint64_t moved, moved_carried;       /* pixels of the last ptmi_reproject that took the moved rule / of those, CARRIED */
+};
+int ptmi_motion_status(ptmi_ctx *ctx, struct ptmi_motion_status *out);   /* synchronises */
+/* n_floats: width*height*4, else PTMI_E_INVALID; motion off (or before ptmi_resize): PTMI_E_STATE. Synchronises. */
+int ptmi_read_motion(ptmi_ctx *ctx, float *dst, size_t n_floats);
+void *ptmi_motion_device_ptr(ptmi_ctx *ctx);                             /* NULL while off */
+/* per-stage: the previous positions of triangles [first, first+count): 9 floats each (v0, v1, v2). PTMI_E_STATE while off or
+ * without a scene; a range beyond the uploaded count: PTMI_E_INVALID. Synchronises. */
+int ptmi_debug_motion_prev(ptmi_ctx *ctx, uint32_t first, uint32_t count, float *v9);
+
 /* ---- environment lighting: an HDR sky behind every miss, importance-sampled ------------------
  * Without an environment a ray that leaves the scene adds throughput * 0 (pt.wgsl:646-648) and nothing changes: every result keeps
  * its bits. With one, a ray of bounce b that misses adds throughput * (W_b * Le(d)) where an emissive hit's addition goes, the camera

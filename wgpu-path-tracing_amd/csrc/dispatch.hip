@@ -392,7 +392,8 @@ int ptmi_reproject(ptmi_ctx *c, const ptmi_camera *from, const ptmi_camera *to, 
     if (band.rows && (rc = ensure_capacity(c, ln, (size_t)band.rows * band.width))) return rc;
     if ((rc = traverse_arm(c, true, kSpillMain, cfg, false))) return rc;      // (the statistics keep the variants of the last dispatch)
     const hipStream_t s = c->stream;
-    HIP_TRY(c, hipMemsetAsync(&c->d_counters[kCtRpCarried], 0, 4 * sizeof(unsigned long long), s));
+    static_assert(kCtRpMovedCarried == kCtRpCarried + 5, "the four words of the status and the two of the motion status, zeroed as one");
+    HIP_TRY(c, hipMemsetAsync(&c->d_counters[kCtRpCarried], 0, 6 * sizeof(unsigned long long), s));
     if (band.rows == 0) return PTMI_OK;                         // more parts than strips: no pixel of this context's
     const struct { FramePlane to; const void *from; bool on; } copies[] = {
         {kRpOut, c->d_out, true}, {kRpMoments, c->plane[kMoments], true}, {kRpNormal, c->plane[kAovNormal], true},
@@ -416,8 +417,17 @@ int ptmi_reproject(ptmi_ctx *c, const ptmi_camera *from, const ptmi_camera *to, 
     a.out = c->d_out; a.mom = plane_as<float4>(c, kMoments); a.normal = plane_as<float4>(c, kAovNormal);
     a.albedo = have_albedo ? plane_as<float4>(c, kAovAlbedo) : nullptr; a.ids = have_ids ? plane_as<uint2>(c, kAovId) : nullptr;
     a.status = c->d_counters;
+    const bool motion = c->motion_on && c->plane[kMotion] && c->buf[kMotionPrev];
+    if (motion) {
+        // (u, v) of the resolved hits on the centre rays, as ptmi_debug_intersect reports them, into the batch's C array
+        pt_launch_hit_uv(s, band.rows * band.width, c->sc, ln.paths, ln.hits, ln.paths.C);
+        a.prev = static_cast<const float4 *>(c->buf[kMotionPrev]); a.uv = ln.paths.C;
+        a.dirty_first = c->motion_dirty_first; a.dirty_end = c->motion_dirty_first + c->motion_dirty_count;
+        a.motion = plane_as<float4>(c, kMotion);
+    }
     pt_launch_reproject(s, a);
     HIP_TRY(c, hipGetLastError());
+    if (motion) return motion_commit(c);         // the history now holds the current geometry
     return PTMI_OK;
 }
 

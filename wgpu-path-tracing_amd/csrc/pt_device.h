@@ -186,6 +186,7 @@ enum CounterWord {
     kCtDispatchEnd = kCtByBounce + kMaxBounces,
     kCtAdSum = kCtDispatchEnd, kCtAdMin, kCtAdMax,                      // ptmi_adaptive_status: the band's counts (preset 0, ~0, 0 per call)
     kCtRpCarried, kCtRpDisoccluded, kCtRpMissed, kCtRpSamples,          // ptmi_reproject_status: the last ptmi_reproject
+    kCtRpMoved, kCtRpMovedCarried,      // ptmi_motion_status: its pixels that took the moved rule, and those of them that were carried
     kCounterWords
 };
 // u32 control words: lengths that one kernel writes and the next reads
@@ -209,7 +210,8 @@ constexpr bool pt_words_disjoint(std::initializer_list<int> first_then_length, i
 static_assert(pt_words_disjoint({kCtSegments, 1, kCtShadowRays, 1, kCtShadowTraced, 1, kCtEmitRecords, 1, kCtVerifyFailed, 1, kCtAdTraced, 1,
                                  kCtAlphaPathPasses, 1, kCtAlphaPathExhausted, 1, kCtAlphaShadowPasses, 1, kCtAlphaShadowExhausted, 1,
                                  kCtByBounce, kMaxBounces, kCtAdSum, 1, kCtAdMin, 1, kCtAdMax, 1,
-                                 kCtRpCarried, 1, kCtRpDisoccluded, 1, kCtRpMissed, 1, kCtRpSamples, 1}, kCounterWords),
+                                 kCtRpCarried, 1, kCtRpDisoccluded, 1, kCtRpMissed, 1, kCtRpSamples, 1,
+                                 kCtRpMoved, 1, kCtRpMovedCarried, 1}, kCounterWords),
               "a counter word has two names, or none");
 static_assert(pt_words_disjoint({kCwQueue, kMaxBounces + 1, kCwShadow, 2, kCwAdPixels, 1, kCwAdActive, 1, kCwAlpha, 3}, kControlWords),
               "a control word has two names, or none");
@@ -223,6 +225,8 @@ static_assert(kCtAlphaPathPasses > kCtSegments && kCtAlphaShadowExhausted == kCt
 static_assert(kCtAdMin == kCtAdSum + 1 && kCtAdMax == kCtAdSum + 2, "ptmi_adaptive_status presets and reads the three with one copy each");
 static_assert(kCtRpDisoccluded == kCtRpCarried + 1 && kCtRpMissed == kCtRpCarried + 2 && kCtRpSamples == kCtRpCarried + 3,
               "ptmi_reproject zeroes the four with one memset, ptmi_reproject_status reads them with one copy");
+static_assert(kCtRpMoved == kCtRpSamples + 1 && kCtRpMovedCarried == kCtRpMoved + 1,
+              "the two motion words follow the four: the same memset zeroes all six, ptmi_motion_status reads the two with one copy");
 
 struct ShadeParams {
     uint32_t bounce, max_bounces, do_mis;
@@ -436,8 +440,15 @@ struct ReprojectArgs {
     const float4 *h_out, *h_mom, *h_normal, *h_albedo; const uint2 *h_ids;   // the snapshot (albedo / ids NULL: that plane is off)
     float4 *out, *mom, *normal, *albedo; uint2 *ids;    // the live planes, rewritten
     unsigned long long *status;                         // the counter block: kCtRpCarried, ...Disoccluded, ...Missed, ...Samples +=
+    // motion (ptmi_set_motion; motion NULL: off, none of these is read and the kernel is the one without the moved rule)
+    const float4 *prev;                                 // the previous positions: (v0, v1, v2, w = 0) per triangle
+    const float2 *uv;                                   // (u, v) of the hits, by band-local pixel (pt_launch_hit_uv)
+    uint32_t dirty_first, dirty_end;                    // the triangles updated since the last commit: [dirty_first, dirty_end)
+    float4 *motion;                                     // the motion plane; status[kCtRpMoved], [kCtRpMovedCarried] +=
 };
 void pt_launch_reproject(hipStream_t s, const ReprojectArgs &a);
+// prev[3 i .. 3 i + 2] = (v0, v1, v2) of triangle i, w = 0, for first <= i < first + count (motion.hip: the commit, and the fill)
+void pt_launch_motion_commit(hipStream_t s, const ptmi_triangle *tris, uint32_t first, uint32_t count, float4 *prev);
 void pt_launch_blit(hipStream_t s, int blocks, uint32_t W, uint32_t H, const float4 *color, float4 *out_f32,
                     uint32_t *out_rgba8);
 // a device's rows of the frame <-> a contiguous buffer (ptmi_multi_gather)

@@ -100,13 +100,16 @@ const struct { const char *name; size_t (*bytes)(size_t px); bool zeroed; PlaneG
     {"normal history", per_pixel<16>, false, kByReproject}, {"albedo history", per_pixel<16>, false, kByReproject},
     {"id history", per_pixel<8>, false, kByReproject},
     {"float canvas", per_pixel<16>, false, kByBlit}, {"8-bit canvas", per_pixel<4>, false, kByBlit},
+    {"motion", per_pixel<16>, true, kWithFrame},
 };
 // sets of planes: a bit per FramePlane
 constexpr uint32_t kAllPlanes = (1u << kFramePlanes) - 1u;
 static_assert(PTMI_AOV_ALBEDO << kAovAlbedo == bit(kAovAlbedo) && PTMI_AOV_NORMAL << kAovAlbedo == bit(kAovNormal) &&
               PTMI_AOV_ID << kAovAlbedo == bit(kAovId), "an AOV mask, shifted, is its set of planes");
-// the planes that exist whenever the output buffer does: the output, the AOV planes of the mask, the moments plane while on
-uint32_t frame_set(const ptmi_ctx *c) { return bit(kOut) | c->aov_mask << kAovAlbedo | (c->moments_on ? bit(kMoments) : 0u); }
+// the planes that exist whenever the output buffer does: the output, the AOV planes of the mask, the moments and the motion plane while on
+uint32_t frame_set(const ptmi_ctx *c) {
+    return bit(kOut) | c->aov_mask << kAovAlbedo | (c->moments_on ? bit(kMoments) : 0u) | (c->motion_on ? bit(kMotion) : 0u);
+}
 // which: one PTMI_AOV_* bit (else kFramePlanes)
 FramePlane aov_plane_of(uint32_t which) {
     return which == PTMI_AOV_ALBEDO ? kAovAlbedo : which == PTMI_AOV_NORMAL ? kAovNormal : which == PTMI_AOV_ID ? kAovId : kFramePlanes;

@@ -9,6 +9,7 @@
 //   medium_grid.hip    the medium's density grid: its checks, upload and removal, its debug entry points
 //   scene_update.hip   edits of a loaded scene in place: ptmi_update_triangles (the refit on the device), _materials, _lights
 //   alpha.hip          alpha cutouts: the cutoff table, the two resolve loops between the existing kernels, their debug entry points
+//   motion.hip         reprojection across a geometry edit: the previous positions, their commit, the motion plane (ptmi_set_motion)
 #pragma once
 #include "ptmi.h"
 #include "pt_device.h"
@@ -80,6 +81,7 @@ enum SceneBuf {
     kPlanUnits, kPlanExact,            // own leaves: the unit box of every listed triangle (leaf order); both exact child boxes per node
     kPlanWords,                        // the reduction words of one update and the partial sums of the cost
     kAlphaCutoff,                      // the per-material cutoff table of ptmi_set_alpha_cutoff (alpha.hip); gone with the next upload
+    kMotionPrev,                       // the previous positions of ptmi_set_motion (motion.hip): 3 float4 per triangle; re-made by an upload
     kSceneBufs
 };
 
@@ -94,6 +96,7 @@ enum FramePlane {
     kAdFlags,                                      // ... over several devices: this context's share of the whole-frame flag map
     kRpOut, kRpMoments, kRpNormal, kRpAlbedo, kRpId,   // reprojection: the snapshot of the output, moments and first-hit planes
     kBlitF32, kBlitU8,                             // canvas staging of ptmi_blit
+    kMotion,                                       // the motion plane of ptmi_set_motion: where each pixel's surface was in `from`
     kFramePlanes
 };
 
@@ -174,6 +177,11 @@ struct ptmi_ctx {
     std::vector<uint32_t> upd_ref_off, upd_off;
     struct ptmi_scene_update_status upd{};
 
+    // motion (ptmi_set_motion; motion.hip): the previous positions are buf[kMotionPrev], the plane is plane[kMotion]
+    bool motion_on = false;
+    uint32_t motion_epochs = 0;                        // commits since the last upload or ptmi_set_motion(1)
+    uint32_t motion_dirty_first = 0, motion_dirty_count = 0;   // the union of the ranges updated since the last commit (0, 0: none)
+
     // output (binding 0)
     uint32_t W = 0, H = 0;
     void *plane[kFramePlanes] = {};                    // indexed by FramePlane, W x H pixels each (absent: NULL)
@@ -224,6 +232,15 @@ int check_ready(ptmi_ctx *c, bool need_output);
 // dispatch.hip
 void drain_events(ptmi_ctx *c);
 hipError_t quiesce(ptmi_ctx *c);
+
+// motion.hip
+// an upload or an update while motion is on: the previous positions filled from all of the device's triangles (dirty range and epochs
+// cleared), on c's stream; the union of the dirty range with [first, first + count)
+int motion_fill(ptmi_ctx *c);
+void motion_widen(ptmi_ctx *c, uint32_t first, uint32_t count);
+// copies the current positions over the dirty range, clears it and counts an epoch (ptmi_motion_commit; the end of ptmi_reproject)
+int motion_commit(ptmi_ctx *c);
+inline size_t motion_prev_bytes(uint32_t n_tris) { return n_tris ? (size_t)n_tris * 48u : 16u; }
 
 // alpha.hip. Active: a table with a positive entry is in place; only then do the loops run and the lane carry their arrays.
 inline bool alpha_active(const ptmi_ctx *c) { return c->alpha_cutout != 0u; }

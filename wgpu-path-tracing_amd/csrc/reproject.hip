@@ -6,6 +6,11 @@
 // One thread per pixel of the context's rows. The centre ray of the pixel under `to` and its closest hit (t, tri) are given (the
 // centre-ray kernel of pipeline.hip, then `extend`); the hit point is projected into `from`, and the four snapshot pixels around it
 // that show the same surface (depth within the tolerance, same material when ids are compared) and hold samples are blended.
+//
+// k_reproject<true> is the pass while ptmi_set_motion is on: a hit on a triangle that moved since the history was rendered is projected
+// from where its point was then (the hit's barycentrics on the previous positions), and every pixel writes the motion plane. The moved
+// test starts with the dirty range, two kernel arguments, so a wave whose hits all lie outside it reads nothing more than
+// k_reproject<false>, which is the kernel of a context with motion off, unchanged.
 #include "pt_device.h"
 #include "pt_math.h"
 
@@ -18,13 +23,19 @@ PT_DEV float dot_plain(float ax, float ay, float az, float bx, float by, float b
 
 enum { CARRIED = 0, DISOCCLUDED = 1, MISSED = 2 };
 
-__global__ __launch_bounds__(RX * RY) void k_reproject(ReprojectArgs a) {
+PT_DEV bool same_bits3(float4 p, const float *q) {
+    return __float_as_uint(p.x) == __float_as_uint(q[0]) && __float_as_uint(p.y) == __float_as_uint(q[1]) &&
+           __float_as_uint(p.z) == __float_as_uint(q[2]);
+}
+
+template <bool MOTION> __global__ __launch_bounds__(RX * RY) void k_reproject(ReprojectArgs a) {
     const DevBand &band = a.band;
     const uint32_t W = band.width, H = band.height;
     const uint32_t x = blockIdx.x * RX + threadIdx.x, l = blockIdx.y * RY + threadIdx.y;
     const bool in = x < W && l < band.rows;          // every lane stays for the wave reduction at the end
     int outcome = -1;
     float count = 0.0f;
+    bool moved = false;
     if (in) {
         const uint32_t p = l * W + x;
         const size_t oi = (size_t)band.row_of(l) * W + x;
@@ -32,6 +43,7 @@ __global__ __launch_bounds__(RX * RY) void k_reproject(ReprojectArgs a) {
         const uint32_t tri = __float_as_uint(hit.y);
         float4 o_out = make_float4(0.0f, 0.0f, 0.0f, 0.0f), o_mom = o_out, o_nrm = o_out, o_alb = o_out;
         uint2 o_ids = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
+        float m_x = 0.0f, m_y = 0.0f, m_z = 0.0f;                // the motion plane's x, y, z (MOTION only)
         outcome = MISSED;
         if (tri != 0xFFFFFFFFu) {
             outcome = DISOCCLUDED;
@@ -40,7 +52,19 @@ __global__ __launch_bounds__(RX * RY) void k_reproject(ReprojectArgs a) {
             o_ids = make_uint2(tri, mat);
             const float4 o = a.O[p], d = a.D[p];
             const ptmi_camera &cam = a.from;
-            const float Px = o.x + t * d.x, Py = o.y + t * d.y, Pz = o.z + t * d.z;
+            float Px = o.x + t * d.x, Py = o.y + t * d.y, Pz = o.z + t * d.z;
+            if (MOTION && tri >= a.dirty_first && tri < a.dirty_end && tri < a.n_tris) {
+                // MOVED: in the dirty range, and a previous position differs in its bits from the current one
+                const float4 p0 = a.prev[3u * (size_t)tri], p1 = a.prev[3u * (size_t)tri + 1u], p2 = a.prev[3u * (size_t)tri + 2u];
+                const ptmi_triangle &T = a.tris[tri];
+                moved = !(same_bits3(p0, T.v0) && same_bits3(p1, T.v1) && same_bits3(p2, T.v2));
+                if (moved) {
+                    const float2 uv = a.uv[p];
+                    Px = (p0.x + uv.x * (p1.x - p0.x)) + uv.y * (p2.x - p0.x);
+                    Py = (p0.y + uv.x * (p1.y - p0.y)) + uv.y * (p2.y - p0.y);
+                    Pz = (p0.z + uv.x * (p1.z - p0.z)) + uv.y * (p2.z - p0.z);
+                }
+            }
             const float vx = Px - cam.position[0], vy = Py - cam.position[1], vz = Pz - cam.position[2];
             const float zf = dot_plain(vx, vy, vz, cam.forward[0], cam.forward[1], cam.forward[2]);
             const float dist = sqrt1(dot_plain(vx, vy, vz, vx, vy, vz));
@@ -51,6 +75,7 @@ __global__ __launch_bounds__(RX * RY) void k_reproject(ReprojectArgs a) {
                 const float fx = (sx + 1.0f) * 0.5f * (float)W - 0.5f;
                 const float fy = (sy + 1.0f) * 0.5f * (float)H - 0.5f;
                 if (__builtin_isfinite(fx) && __builtin_isfinite(fy)) {
+                    if (MOTION) { m_x = fx - (float)x; m_y = fy - (float)band.row_of(l); m_z = dist; }
                     const float x0 = __builtin_floorf(fx), y0 = __builtin_floorf(fy);
                     const float ax = fx - x0, ay = fy - y0;
                     const float tol = a.depth_tolerance * dist;
@@ -102,6 +127,7 @@ __global__ __launch_bounds__(RX * RY) void k_reproject(ReprojectArgs a) {
         a.normal[oi] = o_nrm;
         if (a.albedo) a.albedo[oi] = o_alb;
         if (a.ids) a.ids[oi] = o_ids;
+        if (MOTION) a.motion[oi] = make_float4(m_x, m_y, m_z, (float)outcome);
     }
     // the counters: per wave, then one atomic each from its first lane (integers: order-free)
     const unsigned long long n_carried = __popcll(__ballot(outcome == CARRIED)), n_dis = __popcll(__ballot(outcome == DISOCCLUDED)),
@@ -114,11 +140,19 @@ __global__ __launch_bounds__(RX * RY) void k_reproject(ReprojectArgs a) {
         if (n_missed) atomicAdd(&a.status[kCtRpMissed], n_missed);
         if (samples) atomicAdd(&a.status[kCtRpSamples], (unsigned long long)samples);
     }
+    if (MOTION) {
+        const unsigned long long n_moved = __popcll(__ballot(moved)), n_moved_carried = __popcll(__ballot(moved && outcome == CARRIED));
+        if ((threadIdx.x & 63u) == 0u) {
+            if (n_moved) atomicAdd(&a.status[kCtRpMoved], n_moved);
+            if (n_moved_carried) atomicAdd(&a.status[kCtRpMovedCarried], n_moved_carried);
+        }
+    }
 }
 
 }  // namespace
 
 void pt_launch_reproject(hipStream_t s, const ReprojectArgs &a) {
     const dim3 grid((a.band.width + RX - 1) / RX, (a.band.rows + RY - 1) / RY), block(RX, RY);
-    hipLaunchKernelGGL(k_reproject, grid, block, 0, s, a);
+    if (a.motion) hipLaunchKernelGGL(k_reproject<true>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(k_reproject<false>, grid, block, 0, s, a);
 }

@@ -399,8 +399,14 @@ int pt_install_scene(ptmi_ctx *c, PtPrepared *prep) {
                                              : hipMemcpyPeer(n[k], c->device, h.dev, h.device, h.bytes);
         else e = h.bytes ? hipMemcpy(n[k], h.host, h.bytes, hipMemcpyHostToDevice) : hipMemset(n[k], 0, 16);
     }
+    // while motion is on (ptmi_set_motion) the previous positions are re-made for the new scene: filled below, from its triangles
+    if (e == hipSuccess && c->motion_on) {
+        e = hipMalloc(&n[kMotionPrev], motion_prev_bytes(prep->nt));
+        if (e == hipSuccess && !prep->nt) e = hipMemset(n[kMotionPrev], 0, motion_prev_bytes(0u));
+    }
     if (e != hipSuccess) {
         for (void *&p : n) dfree(p);
+        (void)hipGetLastError();
         return fail(c, PTMI_E_HIP, "scene upload failed: %s (the previous scene, if any, is still in place)", hipGetErrorString(e));
     }
     HIP_TRY(c, sync_all(c));                  // nothing in flight reads the old buffers any more
@@ -441,6 +447,11 @@ int pt_install_scene(ptmi_ctx *c, PtPrepared *prep) {
     c->have_scene = true;
     c->n_ref_wnodes = (uint32_t)(b.buf[kRefWnodes].bytes / 64); c->tree_nested = b.nested;
     c->upd_planned = false; c->upd_ref_off.clear(); c->upd_off.clear(); c->upd = {};
+    if (c->motion_on) {
+        const int rc = motion_fill(c);
+        if (rc) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
     // the alpha cutoff table belonged to the old scene's materials (its buffer went with the others above); the loops' arrays go too
     c->alpha_present = false; c->alpha_cutout = c->alpha_layers = 0u;
     for (int k = kAlphaO; k <= kAlphaHits; k++) dfree(c->lane.buf[k]);

@@ -469,6 +469,7 @@ int ptmi_update_triangles(ptmi_ctx *c, uint32_t first, uint32_t count, const ptm
     void *const *d = c->buf;
     Words *red = buf_as<Words>(c, kPlanWords);
     if (count) HIP_TRY(c, hipMemcpy(static_cast<ptmi_triangle *>(d[kTris]) + first, tris, (size_t)count * sizeof(ptmi_triangle), hipMemcpyHostToDevice));
+    motion_widen(c, first, count);                              // while motion is on: the previous positions stay, the dirty range grows
     {
         Words w0{};
         for (int k = 0; k < 3; k++) { w0.umin[k] = w0.qmin[k] = 0xFFFFFFFFu; w0.umax[k] = w0.qmax[k] = 0u; }

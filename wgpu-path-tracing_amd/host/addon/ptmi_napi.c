@@ -682,6 +682,73 @@ static napi_value js_reproject_status(napi_env env, napi_callback_info info) {
     return o;
 }
 
+/* setMotion(h, on): ptmi_set_motion. Like reprojection, one device's handle only */
+static napi_value js_set_motion(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    handle *h = get_single_handle(env, info, 2, argv, "setMotion");
+    if (!h) return NULL;
+    bool on = false;
+    napi_get_value_bool(env, argv[1], &on);
+    int rc = ptmi_set_motion(h->ctx, on ? 1u : 0u);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_set_motion");
+    return NULL;
+}
+
+/* motionCommit(h): ptmi_motion_commit */
+static napi_value js_motion_commit(napi_env env, napi_callback_info info) {
+    napi_value argv[1];
+    handle *h = get_single_handle(env, info, 1, argv, "motionCommit");
+    if (!h) return NULL;
+    int rc = ptmi_motion_commit(h->ctx);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_motion_commit");
+    return NULL;
+}
+
+/* motionStatus(h) -> {on, epochs, dirtyFirst, dirtyCount, moved, movedCarried}; synchronises */
+static napi_value js_motion_status(napi_env env, napi_callback_info info) {
+    napi_value argv[1];
+    handle *h = get_single_handle(env, info, 1, argv, "motionStatus");
+    if (!h) return NULL;
+    struct ptmi_motion_status s;
+    int rc = ptmi_motion_status(h->ctx, &s);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_motion_status");
+    napi_value o;
+    NAPI_OK(env, napi_create_object(env, &o));
+    set_num(env, o, "on", (double)s.on); set_num(env, o, "epochs", (double)s.epochs);
+    set_num(env, o, "dirtyFirst", (double)s.dirty_first); set_num(env, o, "dirtyCount", (double)s.dirty_count);
+    set_num(env, o, "moved", (double)s.moved); set_num(env, o, "movedCarried", (double)s.moved_carried);
+    return o;
+}
+
+/* readMotion(h, Float32Array dst of width*height*4): the motion plane */
+static napi_value js_read_motion(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    handle *h = get_single_handle(env, info, 2, argv, "readMotion");
+    if (!h) return NULL;
+    void *p; size_t n;
+    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
+    if (!check_canvas(env, h, "readMotion", "Float32Array", 4, p, n)) return NULL;
+    int rc = ptmi_read_motion(h->ctx, (float *)p, n / 4);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_read_motion");
+    return argv[1];
+}
+
+/* debugMotionPrev(h, first, count, Float32Array dst of count*9): the previous positions of triangles [first, first + count) */
+static napi_value js_debug_motion_prev(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    handle *h = get_single_handle(env, info, 4, argv, "debugMotionPrev");
+    if (!h) return NULL;
+    uint32_t first = 0, count = 0;
+    napi_get_value_uint32(env, argv[1], &first);
+    napi_get_value_uint32(env, argv[2], &count);
+    void *p; size_t n;
+    if (!get_bytes(env, argv[3], &p, &n)) return NULL;
+    if (n != (size_t)count * 9 * sizeof(float)) { napi_throw_range_error(env, NULL, "debugMotionPrev: expected count * 9 floats"); return NULL; }
+    int rc = ptmi_debug_motion_prev(h->ctx, first, count, (float *)p);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_debug_motion_prev");
+    return argv[3];
+}
+
 /* readMoments(h, Float32Array dst of width*height*4): the sample-moments plane */
 static napi_value js_read_moments(napi_env env, napi_callback_info info) {
     napi_value argv[2];
@@ -824,6 +891,8 @@ static napi_value init(napi_env env, napi_value exports) {
         {"setMoments", js_set_moments}, {"denoise", js_denoise}, {"blitDenoised", js_blit_denoised},
         {"dispatchAdaptive", js_dispatch_adaptive}, {"adaptiveStatus", js_adaptive_status}, {"readMoments", js_read_moments},
         {"reproject", js_reproject}, {"reprojectStatus", js_reproject_status},
+        {"setMotion", js_set_motion}, {"motionCommit", js_motion_commit}, {"motionStatus", js_motion_status}, {"readMotion", js_read_motion},
+        {"debugMotionPrev", js_debug_motion_prev},
         {"buildBvh", js_build_bvh}, {"emissiveLights", js_emissive_lights},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

@@ -118,6 +118,16 @@ export class Renderer {
   setReproject(params: ReprojectParams | null): void;
   /** of the last reprojection (include/ptmi.h ptmi_reproject_status); synchronises */
   reprojectStatus(): { carried: number; disoccluded: number; missed: number; samples: number };
+  /** motion on / off (include/ptmi.h ptmi_set_motion): while on, a reprojection follows the triangles updateTriangles moved, and with
+   *  setReproject and adaptive sampling set as well updateTriangles no longer restarts the accumulation: the next adaptive round is
+   *  preceded by a reprojection and continues from the per-pixel counts that leaves. Throws with several devices */
+  setMotion(on: boolean): void;
+  /** the motion plane, width*height float4, row 0 = image bottom: (x, y) where the pixel's surface was under the camera the last
+   *  reprojection came from, in pixels relative to the pixel; z its distance there; w 0 carried / 1 disoccluded / 2 missed.
+   *  Needs setMotion(true); synchronises */
+  readMotion(): Float32Array;
+  /** include/ptmi.h ptmi_motion_status; synchronises */
+  motionStatus(): { on: number; epochs: number; dirtyFirst: number; dirtyCount: number; moved: number; movedCarried: number };
   /** per-pixel sample counts (the moments plane's z), width*height, row 0 = image bottom */
   sampleCounts(): Float32Array;
   /** the denoised output buffer (include/ptmi.h ptmi_denoise): width*height float4 (rgb, 0), row 0 = image bottom */

@@ -62,6 +62,7 @@ function Renderer(options) {
   this.reproject = null;                    // setReproject: the parameters, while camera changes carry the accumulated samples over
   this.accumulatedUnder = null;             // the camera bytes of the last adaptive round: what the planes were accumulated under
   this.reprojectFrom = null;                // ... kept here while a camera change waits for the next round to reproject
+  this.motion = false;                      // setMotion: reprojection carries the samples across updateTriangles too
   if (options.adaptive) this.setAdaptive(options.adaptive);
 }
 
@@ -141,6 +142,7 @@ Renderer.prototype.updateCamera = function () {
 Renderer.prototype.renderFrame = function (frames) {
   frames = frames || 1;
   this.updateCamera();
+  if (this.motion && this.frameIndex === 0) this.addon.motionCommit(this.ctx);     // a restart: the history is rendered with the current geometry
   this.addon.dispatch(this.ctx, this.cameraBytes, frames);
   this.frameIndex += frames;
   if (this.multi && this.gatherEvery > 0) {
@@ -242,14 +244,21 @@ Renderer.prototype.setMedium = function (medium) {
  * layout loadModel uploads (an ArrayBuffer or a typed array), written over the scene's from record `first` on. The topology stays:
  * same counts, same triangle order. updateTriangles refits the trees on the device and refreshes sceneBounds (what
  * setMedium({ bounds: 'scene' }) reads) from the refitted root box; sceneUpdateStatus().costNow / costBuilt says how far the refitted
- * tree has degraded, for the host to decide when to loadModel again. Accumulation restarts. A refused edit throws and changes nothing.
+ * tree has degraded, for the host to decide when to loadModel again. Accumulation restarts, except after updateTriangles under
+ * setReproject, setMotion(true) and adaptive rounds, which continues (setMotion). A refused edit throws and changes nothing.
  */
 Renderer.prototype.updateTriangles = function (first, blob) {
   if (!this.sceneLoaded) throw new Error('updateTriangles: needs a loaded scene (loadModel)');
   this.addon.updateTriangles(this.ctx, first, blob);
   var st = this.addon.sceneUpdateStatus(this.ctx);
   if (this.sceneBounds) this.sceneBounds = { min: st.rootMin, max: st.rootMax };
-  this.frameIndex = 0;
+  if (this.motion && this.reproject && this.adaptive && this.frameIndex > 0 && this.accumulatedUnder) {
+    // setReproject and setMotion: the samples stay, and the next round is preceded by a reprojection from the camera they were
+    // accumulated under (the current one, unless a camera change is waiting too) that follows the moved triangles
+    if (!this.reprojectFrom) this.reprojectFrom = this.accumulatedUnder;
+    this.adaptiveActive = -1;
+    this.adaptivePending = false;
+  } else this.frameIndex = 0;
 };
 Renderer.prototype.updateMaterials = function (first, blob) {
   if (!this.sceneLoaded) throw new Error('updateMaterials: needs a loaded scene (loadModel)');
@@ -481,6 +490,7 @@ Renderer.prototype.renderAdaptive = function (rounds) {
   if (!this.adaptive) throw new Error('renderAdaptive: setAdaptive first');
   rounds = rounds || 1;
   this.updateCamera();
+  if (this.motion && this.frameIndex === 0) this.addon.motionCommit(this.ctx);     // a restart: the history is rendered with the current geometry
   if (this.reprojectFrom) {                 // the camera moved since the last round: carry the samples over, then continue
     this.addon.reproject(this.ctx, this.reprojectFrom, this.cameraBytes, this.reproject);
     this.reprojectFrom = null;
@@ -503,6 +513,24 @@ Renderer.prototype.setReproject = function (params) {
   this.reproject = params || null;
   if (!params && this.reprojectFrom) this.resetOutputBuffer(false);    // a pending camera change restarts after all
 };
+/** Motion (include/ptmi.h ptmi_set_motion): while on, the library keeps the vertex positions the history was rendered with, a
+ *  reprojection follows the triangles updateTriangles has moved since, and readMotion() returns the per-pixel screen motion. With
+ *  setReproject and adaptive sampling on as well, updateTriangles keeps the accumulated samples: the next adaptive round is preceded by
+ *  reproject(camera the samples were accumulated under, current camera) and continues from the counts that leaves. The carried
+ *  lighting is the old one until new frames dilute it (maxHistory bounds how long). */
+Renderer.prototype.setMotion = function (on) {
+  if (this.multi) throw new Error('setMotion: reprojection is not supported with several devices');
+  this.addon.setMotion(this.ctx, !!on);
+  this.motion = !!on;
+};
+/** The motion plane: width*height float4, row 0 = image bottom like readOutput. Per pixel (x, y): where its surface was under the camera
+ *  the last reprojection came from, in pixels relative to the pixel; z: its distance there; w: 0 carried, 1 disoccluded, 2 missed.
+ *  Needs setMotion(true). Synchronises. */
+Renderer.prototype.readMotion = function () {
+  return this.addon.readMotion(this.ctx, new Float32Array(this.width * this.height * 4));
+};
+/** { on, epochs, dirtyFirst, dirtyCount, moved, movedCarried } (include/ptmi.h ptmi_motion_status); synchronises */
+Renderer.prototype.motionStatus = function () { return this.addon.motionStatus(this.ctx); };
 /** { carried, disoccluded, missed, samples } of the last reprojection (include/ptmi.h ptmi_reproject_status); synchronises */
 Renderer.prototype.reprojectStatus = function () { return this.addon.reprojectStatus(this.ctx); };
 /** { active, samples, minCount, maxCount, rounds } (include/ptmi.h ptmi_adaptive_status); synchronises */

@@ -34,6 +34,8 @@ EXPORTS = [
     "ptmi_denoise", "ptmi_denoised_device_ptr", "ptmi_blit_denoised",
     "ptmi_dispatch_adaptive", "ptmi_adaptive_status",
     "ptmi_reproject", "ptmi_reproject_status", "ptmi_debug_center_rays",
+    "ptmi_set_motion", "ptmi_get_motion", "ptmi_motion_commit", "ptmi_motion_status", "ptmi_read_motion", "ptmi_motion_device_ptr",
+    "ptmi_debug_motion_prev",
     "ptmi_upload_environment", "ptmi_set_environment", "ptmi_environment_status", "ptmi_multi_upload_environment",
     "ptmi_multi_set_environment", "ptmi_debug_env_lookup", "ptmi_debug_env_sample", "ptmi_debug_env_table",
     "ptmi_multi_set_aovs", "ptmi_multi_get_aovs", "ptmi_multi_set_moments", "ptmi_multi_get_moments", "ptmi_multi_gather_planes",
@@ -101,6 +103,15 @@ class ReprojectParams(ctypes.Structure):
 class ReprojectStatus(ctypes.Structure):
     _fields_ = [("carried", ctypes.c_uint64), ("disoccluded", ctypes.c_uint64), ("missed", ctypes.c_uint64),
                 ("samples", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class MotionStatus(ctypes.Structure):
+    """ptmi_motion_status (include/ptmi.h ptmi_set_motion)"""
+    _fields_ = [("on", ctypes.c_uint32), ("epochs", ctypes.c_uint32), ("dirty_first", ctypes.c_uint32), ("dirty_count", ctypes.c_uint32),
+                ("moved", ctypes.c_uint64), ("moved_carried", ctypes.c_uint64)]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
@@ -267,6 +278,14 @@ def load():
         L.ptmi_reproject.argtypes = [vp, vp, vp, vp]
         L.ptmi_reproject_status.argtypes = [vp, vp]
         L.ptmi_debug_center_rays.argtypes = [vp, vp, vp, vp, sz]
+        L.ptmi_set_motion.argtypes = [vp, u32]
+        L.ptmi_get_motion.argtypes = [vp, vp]
+        L.ptmi_motion_commit.argtypes = [vp]
+        L.ptmi_motion_status.argtypes = [vp, vp]
+        L.ptmi_read_motion.argtypes = [vp, vp, sz]
+        L.ptmi_motion_device_ptr.restype = vp
+        L.ptmi_motion_device_ptr.argtypes = [vp]
+        L.ptmi_debug_motion_prev.argtypes = [vp, u32, u32, vp]
         L.ptmi_environment_status.argtypes = [vp, vp]
         L.ptmi_debug_env_lookup.argtypes = [vp, u32, vp, vp]
         L.ptmi_debug_env_sample.argtypes = [vp, u32, vp, vp, vp, vp]
@@ -705,6 +724,41 @@ class Context(_Handle):
         o, d = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
         self._ck(self.L.ptmi_debug_center_rays(self.h, _p(camera), _p(o), _p(d), o.size))
         return o, d
+
+    # -- motion: reprojection across a geometry edit (include/ptmi.h ptmi_set_motion) ---------------------------
+    def set_motion(self, on=True):
+        self._ck(self.L.ptmi_set_motion(self.h, int(on)))
+
+    def motion(self):
+        """whether motion is on"""
+        m = ctypes.c_uint32(0)
+        self._ck(self.L.ptmi_get_motion(self.h, ctypes.byref(m)))
+        return bool(m.value)
+
+    def motion_commit(self):
+        """previous positions := current, over the dirty range. Asynchronous."""
+        self._ck(self.L.ptmi_motion_commit(self.h))
+
+    def motion_status(self):
+        st = MotionStatus()
+        self._ck(self.L.ptmi_motion_status(self.h, ctypes.byref(st)))
+        return st
+
+    def read_motion(self, n_floats=None):
+        """(H, W, 4) float32: where the pixel's surface was under reproject()'s from_cam, in pixels relative to the pixel (x, y), its
+        distance there (z), and 0 / 1 / 2 for carried / disoccluded / missed. n_floats overrides the count passed (for tests)."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._ck(self.L.ptmi_read_motion(self.h, _p(out), out.size if n_floats is None else n_floats))
+        return out
+
+    def motion_device_ptr(self):
+        return self.L.ptmi_motion_device_ptr(self.h)
+
+    def debug_motion_prev(self, first, count):
+        """the previous positions of triangles [first, first + count): (count, 3, 3) float32, v0, v1, v2"""
+        out = np.zeros((count, 3, 3), np.float32)
+        self._ck(self.L.ptmi_debug_motion_prev(self.h, first, count, _p(out) if count else None))
+        return out
 
     # -- environment lighting (include/ptmi.h ptmi_upload_environment) ------------------------------------------
     def environment_status(self):
