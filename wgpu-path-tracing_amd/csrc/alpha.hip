@@ -9,6 +9,7 @@
 // k_alpha_shadow_resolve decides each record the way ShadowIO does.
 #include "ptmi_ctx.h"
 #include "pt_math.h"
+#include "pt_hit.h"
 #include "pt_texel.h"
 
 #include <cmath>
@@ -20,36 +21,29 @@ namespace {
 constexpr int ABLOCK = 256;
 constexpr uint32_t kDefaultLayers = 4u, kMaxLayers = 32u;
 
-PT_DEV v3 ld3(const float *p) { return mk3(p[0], p[1], p[2]); }
-
-// Whether the hit of the ray (ro, rd) on triangle `tri` is a hole: (u, v) by the tri_test `extend` accepted the hit with, on the same
-// operands (as k_hit_uv), the uv interpolated as make_hitinfo does, alpha = .w of the albedo map's texel (no map: 1).
+// Whether the hit of the ray (ro, rd) on triangle `tri` is a hole: the texture coordinates at the hit's (u, v) (pt_hit.h: the ones
+// `shade` looks its maps up with), alpha = .w of the albedo map's texel (no map: 1).
 PT_DEV bool alpha_hole(const DevScene &sc, const float *__restrict__ cutoff, uint32_t tri, v3 ro, v3 rd) {
     const ptmi_triangle &T = sc.tris[tri];
     const uint32_t mi = T.material_index;
     if (mi >= sc.n_mats) return false;                      // `shade` reads a material of zeros there: no map, alpha 1
     const float cut = cutoff[mi];
     if (!(cut > 0.0f)) return false;
-    const v3 v0 = ld3(T.v0);
     float u, v;
-    (void)tri_test(v0, sub3(ld3(T.v1), v0), sub3(ld3(T.v2), v0), ro, rd, u, v);
-    const float w = 1.0f - u - v;
-    const float uvx = fma1(T.uv2[0], v, fma1(T.uv1[0], u, T.uv0[0] * w));
-    const float uvy = fma1(T.uv2[1], v, fma1(T.uv1[1], u, T.uv0[1] * w));
+    (void)tri_hit(T, ro, rd, u, v);
+    const float uvx = hit_texcoord(T.uv0[0], T.uv1[0], T.uv2[0], u, v), uvy = hit_texcoord(T.uv0[1], T.uv1[1], T.uv2[1], u, v);
     v4 one; one.x = one.y = one.z = one.w = 1.0f;
     return texture_color(sc, sc.mats[mi].albedo_map, uvx, uvy, one).w < cut;
 }
 
 // The distance of the hit on `tri` along the ray (ro, rd) its segment STARTED with, for a ray that reached it past holes: the triangle
-// test `extend` would have run for it from there, on the same operands, so the ray reports the bits an unobstructed ray reports. The
+// test `extend` would have run for it from there (pt_hit.h), so the ray reports the bits an unobstructed ray reports. The
 // distance travelled plus the last leg carries the rounding of every scratch origin (an ulp of the coordinates: 15 PT_EPS at 200
 // units, enough to put a hit point under the floor it lies on); it stands in only where the test from the start rejects the hit, a
 // rounding apart at an edge.
 PT_DEV float alpha_hit_t(const DevScene &sc, uint32_t tri, v3 ro, v3 rd, float fallback) {
-    const ptmi_triangle &T = sc.tris[tri];
-    const v3 v0 = ld3(T.v0);
     float u, v;
-    const float t = tri_test(v0, sub3(ld3(T.v1), v0), sub3(ld3(T.v2), v0), ro, rd, u, v);
+    const float t = tri_hit(sc.tris[tri], ro, rd, u, v);
     return t > 0.0f ? t : fallback;
 }
 

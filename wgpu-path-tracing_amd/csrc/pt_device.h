@@ -355,7 +355,7 @@ void pt_launch_alpha_resolve(hipStream_t s, int blocks, const DevScene &sc, DevA
 // verdict INSTEAD of the addition, and the holes passed (max_layers + 1: still on a hole in the last round, occluded).
 void pt_launch_alpha_shadow_resolve(hipStream_t s, int blocks, const DevScene &sc, DevAlpha a, uint32_t round, DevPaths p, DevShadow sh,
                                     const uint32_t *sq, const uint32_t *count, const float2 *hits0, uint8_t *occ_out, uint32_t *layers_out);
-// (u, v) of n hit records, rebuilt the way `shade` does it (debug entry point of the parity tests)
+// (u, v) of n hit records, rebuilt the way `shade` does it (pt_hit.h; reproject.hip): for ptmi_debug_intersect and the motion-aware reprojection
 void pt_launch_hit_uv(hipStream_t s, uint32_t n, const DevScene &sc, DevPaths p, const float2 *hits, float2 *uv);
 // shadow_queue: positions of the shadow records to trace (NULL = slots 0..count-1), count = their number
 void pt_launch_shadow(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &sc, DevPaths p,

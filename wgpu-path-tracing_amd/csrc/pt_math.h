@@ -191,8 +191,8 @@ PT_DEV uint32_t f2u(float f) {
 // Moller-Trumbore, pt.wgsl:128-158; returns t (> 1e-6) or -1. Straight-line: the reference's four early returns
 // (:134, :143, :151, :157) are folded into one predicate with the same NaN behaviour (a NaN never
 // triggers an early return there, and fails the final t > EPSILON here as there). e1 = v1 - v0, e2 = v2 - v0.
-// Used by the traversal kernels for every candidate and by `shade` to rebuild (u, v) of the closest hit from its
-// triangle (the hit record carries only t and the triangle): same function, same operands, same bits.
+// Used by the traversal kernels for every candidate and, through pt_hit.h, by `shade` and the kernels beside it to rebuild (u, v)
+// of the closest hit from its triangle (the hit record carries only t and the triangle): same function, same operands, same bits.
 // BOUNDED: the caller knows |a| <= 2^100 for this ray and every triangle of the scene (traverse.hip: DevScene::tri_safe_dsum),
 // so the short reciprocal needs no range test — the triangle loop stays one basic block. Same bits either way.
 template <bool BOUNDED>

@@ -11,8 +11,11 @@
 // from where its point was then (the hit's barycentrics on the previous positions), and every pixel writes the motion plane. The moved
 // test starts with the dirty range, two kernel arguments, so a wave whose hits all lie outside it reads nothing more than
 // k_reproject<false>, which is the kernel of a context with motion off, unchanged.
+//
+// k_hit_uv writes the barycentrics that pass reads (ReprojectArgs::uv); ptmi_debug_intersect reports them too.
 #include "pt_device.h"
 #include "pt_math.h"
+#include "pt_hit.h"
 
 namespace {
 
@@ -149,7 +152,21 @@ template <bool MOTION> __global__ __launch_bounds__(RX * RY) void k_reproject(Re
     }
 }
 
+// (u, v) of every hit, which the 8-byte hit record does not carry (pt_hit.h); a miss gets (0, 0)
+__global__ void k_hit_uv(uint32_t n, DevScene sc, DevPaths P, const float2 *__restrict__ hits, float2 *__restrict__ uv) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float2 h = hits[i];
+    float u = 0.0f, v = 0.0f;
+    if (!(h.x < 0.0f)) (void)tri_hit(sc.tris[__float_as_uint(h.y)], xyz(P.O[i]), xyz(P.D[i]), u, v);
+    uv[i] = make_float2(u, v);
+}
+
 }  // namespace
+
+void pt_launch_hit_uv(hipStream_t s, uint32_t n, const DevScene &sc, DevPaths p, const float2 *hits, float2 *uv) {
+    hipLaunchKernelGGL(k_hit_uv, dim3((n + 255) / 256), dim3(256), 0, s, n, sc, p, hits, uv);
+}
 
 void pt_launch_reproject(hipStream_t s, const ReprojectArgs &a) {
     const dim3 grid((a.band.width + RX - 1) / RX, (a.band.rows + RY - 1) / RY), block(RX, RY);

@@ -10,6 +10,7 @@
 // each (64 paths -> one u64 word) for the ordered compaction kernel.
 #include "pt_device.h"
 #include "pt_math.h"
+#include "pt_hit.h"
 #include "pt_texel.h"
 #include "pt_env.h"
 #include "pt_medium.h"
@@ -24,8 +25,6 @@ struct HitInfo {                       // pt.wgsl:86-101 (fields the bounce loop
     v3 emission; float emissive_strength;
     bool is_front;
 };
-
-PT_DEV v3 ld3(const float *p) { return mk3(p[0], p[1], p[2]); }
 
 // Where a bounce gets its material, its light and the light's triangle (pt_device.h, shade tables). STAGE names the tables k_shade
 // copied into LDS (PT_STAGE_*): those are read from there through address-space-qualified pointers, as the
@@ -64,8 +63,7 @@ template <int STAGE> struct ShadeTabs {
 };
 
 // rayTriangleIntersect, pt.wgsl:159-226, for the closest hit only. The hit record carries (t, triangle); the barycentric
-// (u, v) are the ones `extend` computed when it accepted the hit — recomputed here by the same tri_test on the same
-// operands (e1, e2 are the same single IEEE subtractions the traversal image was built with, scene_image.hip).
+// (u, v) are the ones `extend` computed when it accepted the hit (pt_hit.h).
 template <int STAGE>
 PT_DEV HitInfo make_hitinfo(const DevScene &sc, const ShadeTabs<STAGE> &tabs, v3 ro, v3 rd, float t, uint32_t tri) {
     HitInfo hi;
@@ -76,17 +74,15 @@ PT_DEV HitInfo make_hitinfo(const DevScene &sc, const ShadeTabs<STAGE> &tabs, v3
     const v3 tn0 = ld3(T.n0), tn1 = ld3(T.n1), tn2 = ld3(T.n2);
     const float u0x = T.uv0[0], u0y = T.uv0[1], u1x = T.uv1[0], u1y = T.uv1[1], u2x = T.uv2[0], u2y = T.uv2[1];
     const uint32_t mi = T.material_index;
-    v3 v0 = tv0;
-    v3 e1 = sub3(tv1, v0), e2 = sub3(tv2, v0);
+    v3 e1, e2;
     float u, v;
-    (void)tri_test(v0, e1, e2, ro, rd, u, v);
+    (void)tri_hit(tv0, tv1, tv2, ro, rd, u, v, e1, e2);
     hi.t = t;
     hi.position = madd3(rd, t, ro);
     float w = 1.0f - u - v;
     v3 geo_n = normalize3(cross3(e1, e2));
     v3 n_i = normalize3(lincomb3(tn0, w, tn1, u, tn2, v));
-    float uvx = fma1(u2x, v, fma1(u1x, u, u0x * w));
-    float uvy = fma1(u2y, v, fma1(u1y, u, u0y * w));
+    const float uvx = hit_texcoord(u0x, u1x, u2x, u, v), uvy = hit_texcoord(u0y, u1y, u2y, u, v);
     hi.is_front = dot3(geo_n, rd) < 0.0f;
     const ptmi_material m = tabs.material(sc, mi);
     v4 one; one.x = one.y = one.z = one.w = 1.0f;
@@ -312,8 +308,10 @@ constexpr int SBLOCK = 256;
 #define PT_SHADE_ATTR
 #endif
 
-// What the three ways a path ends in k_shade share, and what its two kinds of miss share. (terminal_add reports the record it left
-// instead of setting the lane's votes through references: a bool behind a reference stays a byte through the ballots.)
+// ---- the steps both kinds of vertex take (the surface hit, the medium's scatter vertex) and both kinds of miss, each said once ----
+// A step reports a lane's votes as its return value, never through a reference: a bool behind a reference stays a byte through
+// the ballots.
+
 // A path's last addition to L: an emissive hit, a miss under an environment, a miss with a throughput that is not finite. With
 // emit_records the lane leaves a record with nothing to trace (rec_o stays (0, 0, 0, -2)) that `shadow` adds in bounce order, and the
 // caller votes `shadow` and `emitted`; else the addition is made here.
@@ -327,21 +325,68 @@ PT_DEV bool terminal_add(const DevPaths &P, uint32_t emit_records, uint32_t p, v
     P.stL(p, l.x + e.x, l.y + e.y, l.z + e.z);
     return false;
 }
-// the first-hit record of a camera ray that misses: zeros and triangle 0xFFFFFFFF
+// The first-hit record of camera ray i (AOV), 32 B at slot i (the bounce-0 queue is the identity: slot i is path i), from the
+// HitInfo the bounce builds anyway: aov[2i] = (albedo.rgb, t), aov[2i + 1] = (normal.xyz, bits(triangle)) ...
+PT_DEV void aov_hit(float4 *__restrict__ aov, uint32_t i, const HitInfo &hit, float tri_bits) {
+    st_stream(&aov[2 * (size_t)i], make_float4(hit.albedo.x, hit.albedo.y, hit.albedo.z, hit.t));
+    st_stream(&aov[2 * (size_t)i + 1], make_float4(hit.normal.x, hit.normal.y, hit.normal.z, tri_bits));
+}
+// ... and of a camera ray that misses: zeros and triangle 0xFFFFFFFF
 PT_DEV void aov_miss(float4 *__restrict__ aov, uint32_t i) {
     st_stream(&aov[2 * (size_t)i], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
     st_stream(&aov[2 * (size_t)i + 1], make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu)));
 }
-// the throughput a bounce > 0 starts with: (D.w, C.xy) of its state slot, D being loaded already (raygen stores none: a camera ray's is 1)
+// What the segment in state slot q starts with: its path id (where its radiance is; pid NULL: the slot is the path id) ...
+// (path_id and throughput_in take their word of ShadeParams by value: called with the struct by reference from the scatter vertex,
+// the kernels with a medium came out with other registers. continue_path takes the struct and does not have that effect.)
+PT_DEV uint32_t path_id(const uint32_t *pid, uint32_t q) { return pid ? pid[q] : q; }
+// ... and its throughput (pt.wgsl:639): (D.w, C.xy) of the slot for a bounce > 0, D being loaded already; raygen stores none, a
+// camera ray's is 1. (The environment miss calls stored_throughput itself: the weight in P.W is read under the same test, and with
+// the test in here that load leaves its branch and the kernels with an environment map take other registers.)
 PT_DEV v3 stored_throughput(const DevPaths &P, uint32_t q, float4 d4) {
     const float2 c2 = ld_stream(&P.C[q]);
     return mk3(d4.w, c2.x, c2.y);
 }
+PT_DEV v3 throughput_in(const DevPaths &P, uint32_t bounce, uint32_t q, float4 d4) {
+    v3 thr = mk3(1.0f, 1.0f, 1.0f);
+    if (bounce != 0u) thr = stored_throughput(P, q, d4);
+    return thr;
+}
+
+// How a vertex hands its path on: Russian roulette (pt.wgsl:699-705), then, unless this was the last bounce, the surviving path's
+// state into slot q: the ray (o, nd), the RNG state in O.w, the throughput in (D.w, C.xy). Returns whether the path survived.
+// ENV, while the map is sampled: the bounce ray carries in P.W what the environment's radiance weighs if this ray misses: where this
+// vertex's next-event sample could have picked the same direction (inv_n != 0: it ran, sample_light), the power heuristic of the
+// path's own density against the environment's at nd; else 1. own_pdf() is that density, asked for only there: the BSDF's pdf at a
+// surface, the phase value at a scatter vertex.
+// (Three things here are shaped by what the compiler in use makes of them, to keep the kernels without an environment map the code
+// they were before this was a function: alive is a flag and not an early return, rng is a reference though no caller reads it
+// afterwards, own_pdf is a callable and not a float. None of them is needed for correctness; with another compiler, or once those
+// kernels may change, a plain `float own_pdf`, `uint32_t rng` and early returns are the simpler form.)
+template <bool ENV, class OwnPdf>
+PT_DEV bool continue_path(const DevScene &sc, const DevPaths &P, const ShadeParams &sp, uint32_t q, uint32_t &rng, v3 o, v3 nd, v3 thr,
+                          OwnPdf own_pdf, float inv_n) {
+    bool alive = true;
+    if (pt_plays_roulette(sp.bounce)) {
+        float pr = max1(max1(thr.x, thr.y), thr.z);
+        if (rng_f(rng) > pr) alive = false;
+        else thr = vdiv3(thr, pr);
+    }
+    if (alive && sp.bounce + 1u < sp.max_bounces) {
+        st_stream(&P.O[q], make_float4(o.x, o.y, o.z, __uint_as_float(rng)));
+        st_stream(&P.D[q], make_float4(nd.x, nd.y, nd.z, thr.x));
+        st_stream(&P.C[q], make_float2(thr.y, thr.z));
+        if (ENV && P.W) {
+            float w = 1.0f;
+            if (inv_n != 0.0f) w = power_heuristic(1.0f, own_pdf(), 1.0f, env_lookup(sc.env, nd).pdf * inv_n);
+            P.W[q] = w;
+        }
+    }
+    return alive;
+}
 
 // AOV: the instantiation launched for bounce 0 while first-hit planes are enabled (ptmi_set_aovs). It also writes the path's first-hit
-// record, 32 B at slot i (the bounce-0 queue is the identity: slot i is path i), from the HitInfo the bounce builds anyway:
-// aov[2i] = (albedo.rgb, t), aov[2i + 1] = (normal.xyz, bits(triangle)); a miss writes zeros and triangle 0xFFFFFFFF.
-// The other instantiation never reads `aov` and is the bounce kernel as it was.
+// record (aov_hit, aov_miss). The other instantiation never reads `aov` and is the bounce kernel as it was.
 //
 // Shadow records (next-event samples, and with emit_records the records of emissive hits and non-finite misses) are held in
 // registers until the wave's ballot and then packed at the front of the wave's 64 slots: the lane with `rank` records below it
@@ -355,8 +400,8 @@ PT_DEV v3 stored_throughput(const DevPaths &P, uint32_t q, float4 d4) {
 //
 // ENV: the instantiations launched while an environment map is in place (DevScene::env). A ray that misses — a camera
 // ray too — adds throughput * (W * Le(direction)) where an emissive hit's addition goes; while the map is sampled it is one more light
-// for next-event estimation, and the bounce ray carries W, the power-heuristic weight of its own density against the environment's at
-// its direction, in P.W for the bounce that may miss. Without ENV the kernel is the one it was: no branch of it reads the map.
+// for next-event estimation (sample_light), and the bounce ray carries W in P.W for the bounce that may miss (continue_path).
+// Without ENV the kernel is the one it was: no branch of it reads the map.
 //
 // MED: the instantiations launched while a participating medium is in place (DevScene::med; DESIGN.md §11, pt_medium.h), with or
 // without ENV. A segment that crosses the box takes one draw for its free flight before any other; a collision in front of the hit (or
@@ -422,20 +467,20 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                         if (AOV) {                                           // the planes record the camera ray's surface hit all the same
                             if (is_hit) {
                                 const HitInfo hit = make_hitinfo(sc, tabs, ro, rd, h2.x, __float_as_uint(h2.y));
-                                st_stream(&aov[2 * (size_t)i], make_float4(hit.albedo.x, hit.albedo.y, hit.albedo.z, hit.t));
-                                st_stream(&aov[2 * (size_t)i + 1], make_float4(hit.normal.x, hit.normal.y, hit.normal.z, h2.y));
+                                aov_hit(aov, i, hit, h2.y);
                             } else {
                                 aov_miss(aov, i);
                             }
                         }
-                        const uint32_t p = sp.pid ? sp.pid[q] : q;
-                        v3 thr = mk3(1.0f, 1.0f, 1.0f);
-                        if (sp.bounce != 0u) thr = stored_throughput(P, q, d4);
-                        thr = mul3(thr, ld3(sc.med.albedo));
+                        const uint32_t p = path_id(sp.pid, q);
+                        v3 thr = mul3(throughput_in(P, sp.bounce, q, d4), ld3(sc.med.albedo));
                         if (!(MED == PT_MED_GRID && capped) &&
                             ((thr.x != 0.0f) | (thr.y != 0.0f) | (thr.z != 0.0f))) {     // all zero: the path ends here
                             const v3 x = madd3(rd, t_sc, ro);
                             const float g = sc.med.g;
+                            // Next-event estimation as at the surface hit below: the phase value where the BSDF's (f * cos, pdf) stand,
+                            // the record's origin x itself. (Still written out at both vertices: change one copy, change the other. A function
+                            // for it waits until the kernels that run without an environment map may change; profiles/README.md.)
                             float inv_n = 0.0f;
                             const bool have_light = ENV ? sc.n_lights + sc.env.sampled > 0u : sc.n_lights > 0u;
                             if (sp.do_mis && have_light) {
@@ -461,22 +506,7 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                             const float xi1 = rng_f(med_rng), xi2 = rng_f(med_rng);
                             float ct;
                             const v3 nd = med_sample_phase(g, rd, xi1, xi2, ct);      // its density is its phase value: no factor
-                            alive = true;
-                            if (pt_plays_roulette(sp.bounce)) {
-                                float pr = max1(max1(thr.x, thr.y), thr.z);
-                                if (rng_f(med_rng) > pr) alive = false;
-                                else thr = vdiv3(thr, pr);
-                            }
-                            if (alive && sp.bounce + 1u < sp.max_bounces) {
-                                st_stream(&P.O[q], make_float4(x.x, x.y, x.z, __uint_as_float(med_rng)));
-                                st_stream(&P.D[q], make_float4(nd.x, nd.y, nd.z, thr.x));
-                                st_stream(&P.C[q], make_float2(thr.y, thr.z));
-                                if (ENV && P.W) {
-                                    float w = 1.0f;
-                                    if (inv_n != 0.0f) w = power_heuristic(1.0f, med_phase(g, ct), 1.0f, env_lookup(sc.env, nd).pdf * inv_n);
-                                    P.W[q] = w;
-                                }
-                            }
+                            alive = continue_path<ENV>(sc, P, sp, q, med_rng, x, nd, thr, [=] { return med_phase(g, ct); }, inv_n);
                         }
                     }
                 }
@@ -485,16 +515,12 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                 // handled above
             } else if (!(h2.x < 0.0f)) {                                     // pt.wgsl:646: miss adds zero
                 const float4 o4 = MED ? med_o4 : ld_stream(&P.O[q]), d4 = MED ? med_d4 : ld_stream(&P.D[q]);
-                const uint32_t p = sp.pid ? sp.pid[q] : q;                       // the path id: where its radiance is
+                const uint32_t p = path_id(sp.pid, q);
                 uint32_t rng = MED ? med_rng : __float_as_uint(o4.w);
                 const v3 ro = xyz(o4), rd = xyz(d4);
-                v3 thr = mk3(1.0f, 1.0f, 1.0f);                                      // pt.wgsl:639; raygen stores no throughput
-                if (sp.bounce != 0u) thr = stored_throughput(P, q, d4);
+                v3 thr = throughput_in(P, sp.bounce, q, d4);
                 const HitInfo hit = make_hitinfo(sc, tabs, ro, rd, h2.x, __float_as_uint(h2.y));
-                if (AOV) {
-                    st_stream(&aov[2 * (size_t)i], make_float4(hit.albedo.x, hit.albedo.y, hit.albedo.z, hit.t));
-                    st_stream(&aov[2 * (size_t)i + 1], make_float4(hit.normal.x, hit.normal.y, hit.normal.z, h2.y));
-                }
+                if (AOV) aov_hit(aov, i, hit, h2.y);
                 if (hit.emission.x > 0.0f || hit.emission.y > 0.0f || hit.emission.z > 0.0f) {   // pt.wgsl:652-658
                     float att = rcp1(1.0f + hit.t * hit.t);
                     float k = hit.emissive_strength;
@@ -536,24 +562,7 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                         v3 no = madd3(dir, PT_EPS, hit.position);             // pt.wgsl:691
                         v3 nd = normalize3(dir);
                         thr = mul3(thr, vdiv3(mk3(ev.x, ev.y, ev.z), max1(ev.w, PT_EPS)));   // pt.wgsl:696
-                        alive = true;
-                        if (pt_plays_roulette(sp.bounce)) {                   // pt.wgsl:699-705
-                            float pr = max1(max1(thr.x, thr.y), thr.z);
-                            if (rng_f(rng) > pr) alive = false;
-                            else thr = vdiv3(thr, pr);
-                        }
-                        if (alive && sp.bounce + 1u < sp.max_bounces) {
-                            st_stream(&P.O[q], make_float4(no.x, no.y, no.z, __uint_as_float(rng)));
-                            st_stream(&P.D[q], make_float4(nd.x, nd.y, nd.z, thr.x));
-                            st_stream(&P.C[q], make_float2(thr.y, thr.z));
-                            if (ENV && P.W) {
-                                // what the environment's radiance weighs if this ray misses: where this vertex's next-event sample
-                                // could have picked the same direction, the power heuristic of the two densities; else 1
-                                float w = 1.0f;
-                                if (inv_n != 0.0f) w = power_heuristic(1.0f, ev.w, 1.0f, env_lookup(sc.env, nd).pdf * inv_n);
-                                P.W[q] = w;
-                            }
-                        }
+                        alive = continue_path<ENV>(sc, P, sp, q, rng, no, nd, thr, [=] { return ev.w; }, inv_n);
                     }
                 }
             } else if (ENV) {                                                 // a miss sees the environment, the camera ray too
@@ -572,7 +581,7 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                 // a zero leaves the radiance as it is (x + 0 = x): nothing to add, as without a map; a throughput that is not finite
                 // gives NaN or infinity and is added, as without a map
                 if ((e.x != 0.0f) | (e.y != 0.0f) | (e.z != 0.0f)) {
-                    const uint32_t p = sp.pid ? sp.pid[q] : q;
+                    const uint32_t p = path_id(sp.pid, q);
                     if (terminal_add(P, sp.emit_records, p, e, rec_d, rec_c)) { shadow = true; emitted = true; }
                 }
             } else if (AOV) {                                                 // bounce 0 only: a camera ray that misses
@@ -584,7 +593,7 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
                 const float tx = reinterpret_cast<const float *>(&P.D[q])[3];
                 const float2 c2 = ld_stream(&P.C[q]);
                 if (!(__builtin_isfinite(tx) & __builtin_isfinite(c2.x) & __builtin_isfinite(c2.y))) {
-                    const uint32_t p = sp.pid ? sp.pid[q] : q;
+                    const uint32_t p = path_id(sp.pid, q);
                     const v3 e = mk3(tx * 0.0f, c2.x * 0.0f, c2.y * 0.0f);
                     if (terminal_add(P, sp.emit_records, p, e, rec_d, rec_c)) { shadow = true; emitted = true; }
                 }
@@ -647,23 +656,3 @@ void PT_LAUNCH_SHADE(hipStream_t s, int blocks, const DevScene &sc, DevPaths p, 
 #undef PT_SHADE_CASE
 #undef PT_SHADE_PICK
 }
-
-#ifndef PT_SHADE_FAST
-namespace {
-__global__ void k_hit_uv(uint32_t n, DevScene sc, DevPaths P, const float2 *__restrict__ hits, float2 *__restrict__ uv) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float2 h = hits[i];
-    float u = 0.0f, v = 0.0f;
-    if (!(h.x < 0.0f)) {
-        const ptmi_triangle &T = sc.tris[__float_as_uint(h.y)];
-        const v3 v0 = ld3(T.v0);
-        (void)tri_test(v0, sub3(ld3(T.v1), v0), sub3(ld3(T.v2), v0), xyz(P.O[i]), xyz(P.D[i]), u, v);
-    }
-    uv[i] = make_float2(u, v);
-}
-}  // namespace
-void pt_launch_hit_uv(hipStream_t s, uint32_t n, const DevScene &sc, DevPaths p, const float2 *hits, float2 *uv) {
-    hipLaunchKernelGGL(k_hit_uv, dim3((n + 255) / 256), dim3(256), 0, s, n, sc, p, hits, uv);
-}
-#endif
