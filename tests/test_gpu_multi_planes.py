@@ -134,6 +134,34 @@ def test_a_subset_gathers_only_itself(ctx, scene_factory):
         assert_planes(planes_of(m), want, "the rest, gathered by the reads")
 
 
+@pytest.mark.parametrize("n,W,H,strip", [(3, 80, 50, 0), (5, 33, 4, 1)])      # the second: an odd width, and a device without rows
+def test_gather_assembles_the_output_and_nothing_else(ctx, scene_factory, n, W, H, strip):
+    """gather() is gather_planes("output"): device 0 then holds the whole output and, of every other plane, its own rows alone"""
+    sc = scene_factory("cornell")
+    uniform(single(ctx, sc, W, H), W, H)
+    want = planes_of(ctx)
+    with multi(n, sc, W, H, strip) as m:
+        uniform(m, W, H)
+        m.gather()
+        m.synchronize()
+        c0 = context_of(m, 0, W, H)
+        try:
+            own = shard.strip_rows(H, n, 0, m.options().tile_strip)
+            others = sorted(set(range(H)) - set(own))
+            assert others
+            assert_same_floats(c0.read_output(), want["output"], "the output after gather()")
+            for k in AOVS:
+                assert not c0.read_aov(k)[others].any(), f"{k} after gather()"
+            assert not c0.read_moments()[others].any(), "moments after gather()"
+        finally:
+            c0.h = None                                         # owned by the multi handle
+        assert m.gather_ms() >= 0.0
+        assert_planes(planes_of(m), want, "the rest, gathered by the reads")
+        m.gather()
+        m.gather_planes("output")
+        assert np.array_equal(bits(m.read_output()), bits(want["output"])), "the output, gathered again both ways"
+
+
 def test_resize_with_planes_on_reallocates_the_buffers(ctx, scene_factory):
     sc = scene_factory("cornell")
     with multi(3, sc, 16, 16) as m:

@@ -2,12 +2,12 @@
 """tools/multi_planes_time.py: what the fused planes gather (ptmi_multi_gather_planes, include/ptmi.h) costs beside the radiance
 gather, on a one-GPU box: N = 4 contexts on the one device (PTMI_MULTI_LOOPBACK), 1920x1080, every plane on. After a warm-up, REPEATS
 interleaved repeats of
-  (a) ptmi_multi_gather: the output buffer alone, one pack kernel per device, one copy per device, one unpack kernel per share -
-      the path of before, the yardstick;
-  (b) ptmi_multi_gather_planes of everything: output, ALBEDO, NORMAL, ID and moments, 72 bytes per pixel, one pack kernel per
-      device, one copy per device, ONE unpack kernel,
-each timed by the library's own events (ptmi_multi_gather_ms: pack + device copy + unpack). Both are pure copies, so (b)'s time per
-byte should not exceed (a)'s; the margin (b) gets is (a)'s own max / min spread over the repeats.
+  (a) ptmi_multi_gather: the output buffer alone, 16 bytes per pixel - the yardstick;
+  (b) ptmi_multi_gather_planes of everything: output, ALBEDO, NORMAL, ID and moments, 72 bytes per pixel,
+both through the one gather: one pack kernel per device but device 0, one copy per device, ONE unpack kernel (a library from before the
+two were merged, named by PTMI_LIB, runs (a) with a pack on device 0 too and one unpack kernel per share). Each is timed by the
+library's own events (ptmi_multi_gather_ms: pack + device copy + unpack). Both are pure copies, so (b)'s time per byte should not
+exceed (a)'s; the margin (b) gets is (a)'s own max / min spread over the repeats.
 Loopback times pack + device-to-device copy + unpack on ONE GPU: it says nothing about xGMI or RCCL."""
 import json
 import os

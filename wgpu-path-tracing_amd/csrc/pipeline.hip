@@ -492,22 +492,10 @@ __global__ __launch_bounds__(BLOCK) void k_ad_status(DevBand band, const float4 
     if (lo != ~0ull) { atomicAdd(&counters[kCtAdSum], sum); atomicMin(&counters[kCtAdMin], lo); atomicMax(&counters[kCtAdMax], hi); }
 }
 
-// ---- multi-GPU gather (ptmi_multi_gather): a device's rows (DevBand: the strips part, part + parts, ...) <-> one contiguous
-// buffer of band.rows x width float4, local row l of the buffer = frame row band.row_of(l)
-__global__ __launch_bounds__(BLOCK) void k_pack_rows(DevBand band, const float4 *__restrict__ frame, float4 *__restrict__ packed) {
-    const uint32_t n = band.rows * band.width;
-    for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK)
-        packed[i] = frame[band.frame_pixel(i)];
-}
-__global__ __launch_bounds__(BLOCK) void k_unpack_rows(DevBand band, const float4 *__restrict__ packed, float4 *__restrict__ frame) {
-    const uint32_t n = band.rows * band.width;
-    for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK)
-        frame[band.frame_pixel(i)] = packed[i];
-}
-
-// ---- multi-GPU gather of several planes at once (ptmi_multi_gather_planes): the share layout is DevPlaneSet's. Every lane moves 16 bytes
-// per access: a float4 entry, or two 8-byte ids (an odd width leaves id pairs that straddle rows or sit at odd frame indices: those
-// frames move their ids 8 bytes at a time). No LDS: a copy has no reuse.
+// ---- multi-GPU gather (ptmi_multi_gather, ptmi_multi_gather_planes): a device's rows (DevBand: the strips part, part + parts, ...) of
+// one or several planes <-> one contiguous share, local row l of the share = frame row band.row_of(l); the layout is DevPlaneSet's.
+// Every lane moves 16 bytes per access: a float4 entry, or two 8-byte ids (an odd width leaves id pairs that straddle rows or sit at
+// odd frame indices: those frames move their ids 8 bytes at a time). No LDS: a copy has no reuse.
 __global__ __launch_bounds__(BLOCK) void k_pack_planes(DevBand band, DevPlaneSet set, float4 *__restrict__ share) {
     const uint32_t n = band.rows * band.width, stride = gridDim.x * BLOCK;
     for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride) {
@@ -742,12 +730,6 @@ void pt_launch_adaptive_status(hipStream_t s, int blocks, DevBand band, const fl
 }
 // tile totals the list build of `npix` pixels needs (DevAdaptive::tile_sums)
 uint32_t pt_adaptive_tiles(uint32_t npix) { return ((npix + 63u) / 64u + TILE_WORDS - 1) / TILE_WORDS; }
-void pt_launch_pack_rows(hipStream_t s, int blocks, DevBand band, const float4 *frame, float4 *packed) {
-    hipLaunchKernelGGL(k_pack_rows, dim3(blocks), dim3(BLOCK), 0, s, band, frame, packed);
-}
-void pt_launch_unpack_rows(hipStream_t s, int blocks, DevBand band, const float4 *packed, float4 *frame) {
-    hipLaunchKernelGGL(k_unpack_rows, dim3(blocks), dim3(BLOCK), 0, s, band, packed, frame);
-}
 void pt_launch_pack_planes(hipStream_t s, int blocks, DevBand band, DevPlaneSet set, float4 *share) {
     hipLaunchKernelGGL(k_pack_planes, dim3(blocks), dim3(BLOCK), 0, s, band, set, share);
 }

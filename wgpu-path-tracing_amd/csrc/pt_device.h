@@ -451,12 +451,10 @@ void pt_launch_reproject(hipStream_t s, const ReprojectArgs &a);
 void pt_launch_motion_commit(hipStream_t s, const ptmi_triangle *tris, uint32_t first, uint32_t count, float4 *prev);
 void pt_launch_blit(hipStream_t s, int blocks, uint32_t W, uint32_t H, const float4 *color, float4 *out_f32,
                     uint32_t *out_rgba8);
-// a device's rows of the frame <-> a contiguous buffer (ptmi_multi_gather)
-void pt_launch_pack_rows(hipStream_t s, int blocks, DevBand band, const float4 *frame, float4 *packed);
-void pt_launch_unpack_rows(hipStream_t s, int blocks, DevBand band, const float4 *packed, float4 *frame);
-// Several planes of a device's rows <-> one contiguous share (ptmi_multi_gather_planes). A share is laid out plane after plane, each
-// share_px = rows_max x width entries (the largest band's; a smaller band leaves padding that is never unpacked): first the n4 planes of
-// 16-byte entries in the order of f4[], then the 8-byte ids. A frame plane that is absent from the set is NULL / not counted.
+// One or several planes of a device's rows <-> one contiguous share (ptmi_multi_gather, ptmi_multi_gather_planes). A share is laid out
+// plane after plane, each share_px = rows_max x width entries (the largest band's; a smaller band leaves padding that is never unpacked),
+// local row l = frame row band.row_of(l): first the n4 planes of 16-byte entries in the order of f4[], then the 8-byte ids. A frame plane
+// that is absent from the set is NULL / not counted.
 struct DevPlaneSet {
     float4 *f4[4];
     uint2 *ids;

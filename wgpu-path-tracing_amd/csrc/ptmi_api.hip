@@ -254,7 +254,6 @@ DevBand pt_band_of(const ptmi_options &opt, uint32_t W, uint32_t H) {
     return band;
 }
 hipStream_t pt_ctx_stream(ptmi_ctx *c) { return c->stream; }
-float4 *pt_ctx_output(ptmi_ctx *c) { return c->d_out; }
 int pt_ctx_device(const ptmi_ctx *c) { return c->device; }
 int pt_ctx_cus(const ptmi_ctx *c) { return c->n_cu; }
 

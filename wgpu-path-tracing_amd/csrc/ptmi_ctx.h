@@ -47,7 +47,6 @@ int pt_check_alpha_cutoff(const float *cutoff, uint32_t n_materials, const ptmi_
 bool pt_ctx_has_scene(const ptmi_ctx *c);
 uint32_t pt_ctx_materials(const ptmi_ctx *c);
 hipStream_t pt_ctx_stream(ptmi_ctx *c);
-float4 *pt_ctx_output(ptmi_ctx *c);
 int pt_ctx_device(const ptmi_ctx *c);
 int pt_ctx_cus(const ptmi_ctx *c);
 // Adaptive rounds driven from outside, one at a time (ptmi_multi_dispatch_adaptive with neighbourhood = 1; dispatch.hip).

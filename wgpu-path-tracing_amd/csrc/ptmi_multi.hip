@@ -3,18 +3,18 @@
 // The caller is the reference's frame loop (src/renderer/renderer.ts:415-454): one host thread driving one Renderer. Here the
 // Renderer owns N device contexts; the frame's rows are dealt out as interleaved strips (DevBand, pt_device.h), every device
 // traces and accumulates its own rows — pixels and RNG streams are independent (pt.wgsl:719, :753-761), so there is no
-// collective on the data path — and ptmi_multi_gather assembles the frame on device 0:
+// collective on the data path — and ONE gather (gather_set) assembles on device 0 any set of the output buffer, the first-hit planes
+// and the moments plane, in one pass:
 //
-//     k_pack_rows (each device: its rows -> one contiguous buffer)   on that device's stream
-//     ncclGather  (one group call, root = device 0; RCCL over xGMI)  on the same streams
-//     k_unpack_rows (device 0: buffer r -> the rows of device r)     on device 0's stream
+//     k_pack_planes (each device: its rows of every named plane -> one share; DevPlaneSet, pt_device.h)   on that device's stream
+//     ncclGather    (one group call, root = device 0; RCCL over xGMI; loopback: one peer copy per device)  on the same streams
+//     k_unpack_planes (device 0: one pass over the frame, row y from the share of the device that owns it) on device 0's stream
 //
-// ptmi_multi_gather_planes does the same for any set of the first-hit planes, the moments plane and the output buffer in ONE pass:
-// k_pack_planes writes a device's rows of every named plane into one share (DevPlaneSet, pt_device.h), one grouped ncclGather moves the
-// shares, k_unpack_planes scatters all of them in one pass over the frame. Adaptive rounds with neighbourhood = 1 exchange one byte per
-// pixel per round (the NOISY flags) among all devices: ncclAllGather, or peer copies in loopback (ptmi_multi_dispatch_adaptive).
+// ptmi_multi_gather_planes names the set; ptmi_multi_gather is the set of the output buffer alone. Adaptive rounds with neighbourhood = 1
+// exchange one byte per pixel per round (the NOISY flags) among all devices: ncclAllGather, or peer copies in loopback
+// (ptmi_multi_dispatch_adaptive).
 //
-// Equal counts per rank are what ncclGather takes, so every device sends rows_max x width float4 (the last round of strips may
+// Equal counts per rank are what ncclGather takes, so every device sends rows_max x width entries of each plane (the last round of strips may
 // leave some devices a strip short; the padding is never unpacked). RCCL is loaded with dlopen when the first handle is
 // created: a process that renders on one device never maps it.
 #include "ptmi_ctx.h"
@@ -70,29 +70,35 @@ constexpr uint32_t kStripRows = 4;      // measured on Cornell: every N-th 4-row
 
 }  // namespace
 
+// what the handle keeps for device r
+struct MultiDev {
+    ptmi_ctx *ctx = nullptr;
+    float4 *d_send = nullptr;                          // its packed rows
+    uint8_t *d_flags = nullptr;                        // the whole-frame NOISY flags of an adaptive round, N shares (ptmi_multi::flags_bytes)
+    // the events live on device r, ev_copied on device 0 (create_events / destroy_events)
+    hipEvent_t ev_done = nullptr;                      // its rendering is done (recorded on its stream when a gather starts)
+    hipEvent_t ev_packed = nullptr;                    // loopback: its share is packed
+    hipEvent_t ev_copied = nullptr;                    // loopback: its share has been copied out of d_send (recorded on device 0's stream)
+    hipEvent_t ev_flags = nullptr;                     // loopback: its flag share is written
+    hipEvent_t ev_flags_copied = nullptr;              // loopback: it has copied every flag share
+    bool copied_recorded = false, flags_copied_recorded = false;
+};
+
 struct ptmi_multi {
-    std::vector<ptmi_ctx *> ctx;
-    std::vector<int> dev;
+    std::vector<MultiDev> d;
+    std::vector<int> dev;                              // (dev and comm are arrays of their own: ncclCommInitAll takes them so)
     std::vector<ncclComm_t> comm;                      // empty: loopback copies
     bool loopback = false;
     ptmi_options opt{};                                // as given by the caller (tile_strip 0 = automatic)
     uint32_t W = 0, H = 0, strip = kStripRows;
     size_t rows_max = 0;                               // rows of the largest share
-    size_t share_bytes = 0;                            // what every d_send[i] holds (d_recv: N of them): rows_max x W entries of the output
+    size_t share_bytes = 0;                            // what every d_send holds (d_recv: N of them): rows_max x W entries of the output
                                                        // and of every plane that is on (plane_set_of), when allocated
     uint32_t aov_mask = 0;                             // ptmi_multi_set_aovs / _set_moments: what every device has on
     bool moments_on = false;
-    std::vector<uint8_t *> d_flags;                    // per device: the whole-frame NOISY flags of an adaptive round, N shares of
-    size_t flags_bytes = 0;                            // rows_max x W bytes each (the device's own share is its context's kAdFlags plane)
-    std::vector<hipEvent_t> ev_flags;                  // loopback: device r's flag share is written / device r has copied every share
-    std::vector<hipEvent_t> ev_flags_copied;
-    std::vector<char> flags_copied_recorded;
-    std::vector<float4 *> d_send;                      // per device: its packed rows
+    size_t flags_bytes = 0;                            // what every d_flags holds: N shares of rows_max x W bytes (a device's own share is
+                                                       // its context's kAdFlags plane)
     float4 *d_recv = nullptr;                          // device 0: N shares
-    std::vector<hipEvent_t> ev;                        // loopback: device r's share is packed
-    std::vector<hipEvent_t> ev_done;                   // device r's rendering is done (recorded on its stream when a gather starts)
-    std::vector<hipEvent_t> ev_copied;                 // loopback: device r's share has been copied out of d_send[r] (recorded on device 0's stream)
-    std::vector<char> copied_recorded;
     hipEvent_t g0 = nullptr, g1 = nullptr;             // around the last gather on device 0's stream
     bool gather_timed = false;
     uint64_t dispatched = 0, gathered = 0;             // dispatch calls so far / included in device 0's frame
@@ -110,13 +116,13 @@ int mfail(const ptmi_multi *m, int code, const char *fmt, ...) {
 }
 // a failed call on device i: carry its message
 int cfail(const ptmi_multi *m, int i, int rc, const char *what) {
-    return mfail(m, rc, "%s on device %d (ordinal %d): %s", what, i, m->dev[i], ptmi_last_error(m->ctx[i]));
+    return mfail(m, rc, "%s on device %d (ordinal %d): %s", what, i, m->dev[i], ptmi_last_error(m->d[i].ctx));
 }
 // fn(ctx, args...) on every device's context in turn; the first failure is reported through cfail and ends the loop
 template <class Fn, class... Args>
 int each_ctx(const ptmi_multi *m, const char *what, Fn fn, const Args &...args) {
-    for (size_t i = 0; i < m->ctx.size(); i++) {
-        int rc = fn(m->ctx[i], args...);
+    for (size_t i = 0; i < m->d.size(); i++) {
+        int rc = fn(m->d[i].ctx, args...);
         if (rc) return cfail(m, (int)i, rc, what);
     }
     return PTMI_OK;
@@ -136,7 +142,7 @@ uint32_t auto_strip(uint32_t H, uint32_t n) {
 
 ptmi_options options_of(const ptmi_multi *m, int i) {
     ptmi_options o = m->opt;
-    const uint32_t n = (uint32_t)m->ctx.size();
+    const uint32_t n = (uint32_t)m->d.size();
     o.tile_y0 = 0; o.tile_y1 = 0;
     o.tile_parts = n > 1 ? n : 0; o.tile_part = n > 1 ? (uint32_t)i : 0; o.tile_strip = m->strip;
     return o;
@@ -153,7 +159,7 @@ const struct { uint32_t bit; const char *name; } kPlaneKinds[4] = {
 uint32_t planes_on(const ptmi_multi *m) { return PTMI_MULTI_PLANE_OUTPUT | m->aov_mask | (m->moments_on ? PTMI_MULTI_PLANE_MOMENTS : 0u); }
 // the share of device i for `planes` (all of them on): output, ALBEDO, NORMAL, moments, then the ids
 DevPlaneSet plane_set_of(const ptmi_multi *m, int i, uint32_t planes) {
-    ptmi_ctx *c = m->ctx[i];
+    ptmi_ctx *c = m->d[i].ctx;
     DevPlaneSet set{};
     if (planes & PTMI_MULTI_PLANE_OUTPUT) set.f4[set.n4++] = c->d_out;
     if (planes & PTMI_AOV_ALBEDO) set.f4[set.n4++] = plane_as<float4>(c, kAovAlbedo);
@@ -170,21 +176,24 @@ size_t share_bytes_of(size_t rows_max, uint32_t W, uint32_t planes) {
 }
 
 void free_buffers(ptmi_multi *m) {
-    for (size_t i = 0; i < m->d_send.size(); i++)
-        if (m->d_send[i]) { (void)hipSetDevice(m->dev[i]); (void)hipFree(m->d_send[i]); m->d_send[i] = nullptr; }
-    for (size_t i = 0; i < m->d_flags.size(); i++)
-        if (m->d_flags[i]) { (void)hipSetDevice(m->dev[i]); (void)hipFree(m->d_flags[i]); m->d_flags[i] = nullptr; }
+    for (size_t i = 0; i < m->d.size(); i++) {
+        MultiDev &d = m->d[i];
+        (void)hipSetDevice(m->dev[i]);
+        if (d.d_send) { (void)hipFree(d.d_send); d.d_send = nullptr; }
+        if (d.d_flags) { (void)hipFree(d.d_flags); d.d_flags = nullptr; }
+        d.copied_recorded = d.flags_copied_recorded = false;      // nothing is being copied out of buffers that are gone
+    }
     if (m->d_recv) { (void)hipSetDevice(m->dev[0]); (void)hipFree(m->d_recv); m->d_recv = nullptr; }
     m->rows_max = 0; m->share_bytes = 0; m->flags_bytes = 0;
 }
 
 // options of every context + the gathers' buffers for the current size, strip height and set of planes that are on
 int configure(ptmi_multi *m) {
-    const int n = (int)m->ctx.size();
+    const int n = (int)m->d.size();
     m->strip = m->opt.tile_strip ? m->opt.tile_strip : auto_strip(m->H ? m->H : 1, (uint32_t)n);
     for (int i = 0; i < n; i++) {
         const ptmi_options o = options_of(m, i);
-        int rc = ptmi_set_options(m->ctx[i], &o);
+        int rc = ptmi_set_options(m->d[i].ctx, &o);
         if (rc) return cfail(m, i, rc, "ptmi_set_options");
     }
     if (m->W == 0) return PTMI_OK;
@@ -202,14 +211,12 @@ int configure(ptmi_multi *m) {
     if (!wanted) { m->share_bytes = share; return PTMI_OK; }
     for (int i = 0; i < n; i++) {
         MHIP(m, hipSetDevice(m->dev[i]));
-        MHIP(m, hipMalloc(&m->d_send[i], std::max<size_t>(share, 16)));
-        MHIP(m, hipMemset(m->d_send[i], 0, std::max<size_t>(share, 16)));
+        MHIP(m, hipMalloc(&m->d[i].d_send, std::max<size_t>(share, 16)));
+        MHIP(m, hipMemset(m->d[i].d_send, 0, std::max<size_t>(share, 16)));
     }
     MHIP(m, hipSetDevice(m->dev[0]));
     MHIP(m, hipMalloc(&m->d_recv, std::max<size_t>(share * n, 16)));
     m->share_bytes = share;
-    std::fill(m->copied_recorded.begin(), m->copied_recorded.end(), 0);
-    std::fill(m->flags_copied_recorded.begin(), m->flags_copied_recorded.end(), 0);
     return PTMI_OK;
 }
 
@@ -219,17 +226,23 @@ void reset_counts(ptmi_multi *m, bool fresh) {
     m->dispatched = m->gathered = 0;
 }
 
-// pack -> collective -> unpack of `planes` (all on, not 0, buffers in place) onto device 0; the body of both gathers
+// device 0 now holds `planes` whole
+void mark_gathered(ptmi_multi *m, uint32_t planes) {
+    if (planes & PTMI_MULTI_PLANE_OUTPUT) m->gathered = m->dispatched;
+    for (int k = 0; k < 4; k++) if (planes & kPlaneKinds[k].bit) m->gathered_plane[k] = m->dispatched;
+}
+
+// pack -> collective -> unpack of `planes` (all on, not 0, buffers in place) onto device 0: the one body of every gather
 int gather_set(ptmi_multi *m, uint32_t planes) {
-    const int n = (int)m->ctx.size();
-    hipStream_t s0 = pt_ctx_stream(m->ctx[0]);
+    const int n = (int)m->d.size();
+    hipStream_t s0 = pt_ctx_stream(m->d[0].ctx);
     // the timed region (ptmi_multi_gather_ms) starts when EVERY device has rendered its rows: pack, gather, unpack — not the wait for
     // the slowest device, which is the dispatch's time
     for (int i = 1; i < n; i++) {
         MHIP(m, hipSetDevice(m->dev[i]));
-        MHIP(m, hipEventRecord(m->ev_done[i], pt_ctx_stream(m->ctx[i])));
+        MHIP(m, hipEventRecord(m->d[i].ev_done, pt_ctx_stream(m->d[i].ctx)));
         MHIP(m, hipSetDevice(m->dev[0]));
-        MHIP(m, hipStreamWaitEvent(s0, m->ev_done[i], 0));
+        MHIP(m, hipStreamWaitEvent(s0, m->d[i].ev_done, 0));
     }
     MHIP(m, hipSetDevice(m->dev[0]));
     MHIP(m, hipEventRecord(m->g0, s0));
@@ -240,15 +253,15 @@ int gather_set(ptmi_multi *m, uint32_t planes) {
         const DevBand band = pt_band_of(options_of(m, i), m->W, m->H);
         MHIP(m, hipSetDevice(m->dev[i]));
         // loopback: the previous gather's copy out of d_send[i] (on device 0's stream) must be done before it is packed again
-        if (m->comm.empty() && i > 0 && m->copied_recorded[i]) MHIP(m, hipStreamWaitEvent(pt_ctx_stream(m->ctx[i]), m->ev_copied[i], 0));
+        if (m->comm.empty() && i > 0 && m->d[i].copied_recorded) MHIP(m, hipStreamWaitEvent(pt_ctx_stream(m->d[i].ctx), m->d[i].ev_copied, 0));
         // (loopback: device 0's share is never read)
         if (band.rows && (i > 0 || !m->comm.empty()))
-            pt_launch_pack_planes(pt_ctx_stream(m->ctx[i]), pt_ctx_cus(m->ctx[i]) * 8, band, plane_set_of(m, i, planes), m->d_send[i]);
+            pt_launch_pack_planes(pt_ctx_stream(m->d[i].ctx), pt_ctx_cus(m->d[i].ctx) * 8, band, plane_set_of(m, i, planes), m->d[i].d_send);
     }
     if (!m->comm.empty()) {
         MNCCL(m, g_rccl.GroupStart());
         for (int i = 0; i < n; i++) {
-            ncclResult_t r = g_rccl.Gather(m->d_send[i], i == 0 ? m->d_recv : nullptr, share / 4, ncclFloat, 0, m->comm[i], pt_ctx_stream(m->ctx[i]));
+            ncclResult_t r = g_rccl.Gather(m->d[i].d_send, i == 0 ? m->d_recv : nullptr, share / 4, ncclFloat, 0, m->comm[i], pt_ctx_stream(m->d[i].ctx));
             if (r != ncclSuccess) { (void)g_rccl.GroupEnd(); return mfail(m, PTMI_E_HIP, "ncclGather (device %d) failed: %s", i, g_rccl.GetErrorString(r)); }
         }
         MNCCL(m, g_rccl.GroupEnd());
@@ -256,23 +269,22 @@ int gather_set(ptmi_multi *m, uint32_t planes) {
         // loopback: device r's share is copied into slot r of device 0's receive buffer once it is packed
         for (int i = 1; i < n; i++) {
             MHIP(m, hipSetDevice(m->dev[i]));
-            MHIP(m, hipEventRecord(m->ev[i], pt_ctx_stream(m->ctx[i])));
+            MHIP(m, hipEventRecord(m->d[i].ev_packed, pt_ctx_stream(m->d[i].ctx)));
             MHIP(m, hipSetDevice(m->dev[0]));
-            MHIP(m, hipStreamWaitEvent(s0, m->ev[i], 0));
-            MHIP(m, hipMemcpyPeerAsync(reinterpret_cast<char *>(m->d_recv) + (size_t)i * share, m->dev[0], m->d_send[i], m->dev[i], share, s0));
-            MHIP(m, hipEventRecord(m->ev_copied[i], s0));
-            m->copied_recorded[i] = 1;
+            MHIP(m, hipStreamWaitEvent(s0, m->d[i].ev_packed, 0));
+            MHIP(m, hipMemcpyPeerAsync(reinterpret_cast<char *>(m->d_recv) + (size_t)i * share, m->dev[0], m->d[i].d_send, m->dev[i], share, s0));
+            MHIP(m, hipEventRecord(m->d[i].ev_copied, s0));
+            m->d[i].copied_recorded = true;
         }
     }
     MHIP(m, hipSetDevice(m->dev[0]));
-    // device 0's own rows are already in place (RCCL delivers a copy of them into slot 0; the single-device case unpacks that copy, so
-    // that the planes really went through the collective)
-    pt_launch_unpack_planes(s0, pt_ctx_cus(m->ctx[0]) * 8, pt_band_of(options_of(m, 0), m->W, m->H), set0, m->d_recv, n > 1 ? 0u : 0xFFFFFFFFu);
+    // device 0's own rows are already in place (RCCL delivers a copy of them into slot 0; one device through RCCL — the degenerate
+    // gather of its whole frame onto itself — unpacks that copy, so that the planes really went through the collective)
+    pt_launch_unpack_planes(s0, pt_ctx_cus(m->d[0].ctx) * 8, pt_band_of(options_of(m, 0), m->W, m->H), set0, m->d_recv, n > 1 ? 0u : 0xFFFFFFFFu);
     MHIP(m, hipEventRecord(m->g1, s0));
     MHIP(m, hipGetLastError());
     m->gather_timed = true;
-    if (planes & PTMI_MULTI_PLANE_OUTPUT) m->gathered = m->dispatched;
-    for (int k = 0; k < 4; k++) if (planes & kPlaneKinds[k].bit) m->gathered_plane[k] = m->dispatched;
+    mark_gathered(m, planes);
     return PTMI_OK;
 }
 
@@ -285,7 +297,7 @@ uint32_t stale_of(const ptmi_multi *m, uint32_t planes) {
 
 // fn(i) for every device, each from a thread of its own for the length of the call (ptmi_multi_dispatch says why); the first failure
 int each_threaded(ptmi_multi *m, const char *what, const std::function<int(size_t)> &fn) {
-    const size_t n = m->ctx.size();
+    const size_t n = m->d.size();
     std::vector<int> rcs(n, PTMI_OK);
     std::vector<std::thread> pool;
     pool.reserve(n - 1);
@@ -293,6 +305,35 @@ int each_threaded(ptmi_multi *m, const char *what, const std::function<int(size_
     rcs[0] = fn(0);
     for (std::thread &t : pool) t.join();
     for (size_t i = 0; i < n; i++) if (rcs[i]) return cfail(m, (int)i, rcs[i], what);
+    return PTMI_OK;
+}
+
+// the events of device i, each on the device whose stream records it: ev_copied on device 0, the others on device i
+bool create_events(ptmi_multi *m, int i) {
+    MultiDev &d = m->d[i];
+    if (hipSetDevice(m->dev[i]) != hipSuccess) return false;
+    for (hipEvent_t *e : {&d.ev_done, &d.ev_packed, &d.ev_flags, &d.ev_flags_copied})
+        if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return false;
+    return hipSetDevice(m->dev[0]) == hipSuccess && hipEventCreateWithFlags(&d.ev_copied, hipEventDisableTiming) == hipSuccess;
+}
+void destroy_events(ptmi_multi *m, int i) {
+    const MultiDev &d = m->d[i];
+    (void)hipSetDevice(m->dev[i]);
+    for (hipEvent_t e : {d.ev_done, d.ev_packed, d.ev_flags, d.ev_flags_copied}) if (e) (void)hipEventDestroy(e);
+    (void)hipSetDevice(m->dev[0]);
+    if (d.ev_copied) (void)hipEventDestroy(d.ev_copied);
+}
+
+// fn(ctx, value) on every device in turn; on the first failure, reported through cfail, the devices already changed get `before` back
+int each_ctx_or_back(ptmi_multi *m, const char *what, int (*fn)(ptmi_ctx *, uint32_t), uint32_t value, uint32_t before) {
+    for (size_t i = 0; i < m->d.size(); i++) {
+        const int rc = fn(m->d[i].ctx, value);
+        if (rc) {
+            cfail(m, (int)i, rc, what);
+            for (size_t j = 0; j < i; j++) (void)fn(m->d[j].ctx, before);
+            return rc;
+        }
+    }
     return PTMI_OK;
 }
 
@@ -325,10 +366,9 @@ int ptmi_multi_create(int n, const int *ordinals, uint32_t flags, ptmi_multi **o
             ptmi_multi_destroy(m);
             return rc;
         }
-        m->ctx.push_back(c);
+        m->d.push_back(MultiDev{c});
     }
-    m->d_send.assign(n, nullptr); m->d_flags.assign(n, nullptr);
-    ptmi_get_options(m->ctx[0], &m->opt);
+    ptmi_get_options(m->d[0].ctx, &m->opt);
     m->opt.tile_strip = 0;
     if (!m->loopback && n >= 1) {
         // one communicator per device, one process (ncclCommInitAll). A single device goes through RCCL too: its gather is the
@@ -344,15 +384,7 @@ int ptmi_multi_create(int n, const int *ordinals, uint32_t flags, ptmi_multi **o
         }
     }
     bool ok = true;
-    m->ev.assign(n, nullptr); m->ev_copied.assign(n, nullptr); m->ev_done.assign(n, nullptr); m->copied_recorded.assign(n, 0);
-    m->ev_flags.assign(n, nullptr); m->ev_flags_copied.assign(n, nullptr); m->flags_copied_recorded.assign(n, 0);
-    for (int i = 0; i < n && ok; i++) {
-        ok = hipSetDevice(m->dev[i]) == hipSuccess && hipEventCreateWithFlags(&m->ev[i], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&m->ev_done[i], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&m->ev_flags[i], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&m->ev_flags_copied[i], hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipSetDevice(m->dev[0]) == hipSuccess && hipEventCreateWithFlags(&m->ev_copied[i], hipEventDisableTiming) == hipSuccess;
-    }
+    for (int i = 0; i < n && ok; i++) ok = create_events(m, i);
     ok = ok && hipSetDevice(m->dev[0]) == hipSuccess && hipEventCreate(&m->g0) == hipSuccess && hipEventCreate(&m->g1) == hipSuccess;
     if (!ok) { mfail(nullptr, PTMI_E_HIP, "event creation failed"); ptmi_multi_destroy(m); return PTMI_E_HIP; }
     int rc = configure(m);
@@ -363,24 +395,19 @@ int ptmi_multi_create(int n, const int *ordinals, uint32_t flags, ptmi_multi **o
 
 int ptmi_multi_destroy(ptmi_multi *m) {
     if (!m) return PTMI_E_INVALID;
-    for (ptmi_ctx *c : m->ctx) (void)ptmi_synchronize(c);
+    for (const MultiDev &d : m->d) (void)ptmi_synchronize(d.ctx);
     for (ncclComm_t c : m->comm) if (c) (void)g_rccl.CommDestroy(c);
     free_buffers(m);
-    for (size_t i = 0; i < m->ev.size(); i++) if (m->ev[i]) { (void)hipSetDevice(m->dev[i]); (void)hipEventDestroy(m->ev[i]); }
-    for (size_t i = 0; i < m->ev_done.size(); i++) if (m->ev_done[i]) { (void)hipSetDevice(m->dev[i]); (void)hipEventDestroy(m->ev_done[i]); }
-    for (size_t i = 0; i < m->ev_flags.size(); i++) if (m->ev_flags[i]) { (void)hipSetDevice(m->dev[i]); (void)hipEventDestroy(m->ev_flags[i]); }
-    for (size_t i = 0; i < m->ev_flags_copied.size(); i++)
-        if (m->ev_flags_copied[i]) { (void)hipSetDevice(m->dev[i]); (void)hipEventDestroy(m->ev_flags_copied[i]); }
-    for (size_t i = 0; i < m->ev_copied.size(); i++) if (m->ev_copied[i]) { (void)hipSetDevice(m->dev[0]); (void)hipEventDestroy(m->ev_copied[i]); }
+    for (size_t i = 0; i < m->d.size(); i++) destroy_events(m, (int)i);       // (device 0 is current after the last)
     if (m->g0) (void)hipEventDestroy(m->g0);
     if (m->g1) (void)hipEventDestroy(m->g1);
-    for (ptmi_ctx *c : m->ctx) (void)ptmi_destroy(c);
+    for (const MultiDev &d : m->d) (void)ptmi_destroy(d.ctx);
     delete m;
     return PTMI_OK;
 }
 
-int ptmi_multi_count(const ptmi_multi *m) { return m ? (int)m->ctx.size() : 0; }
-ptmi_ctx *ptmi_multi_context(ptmi_multi *m, int i) { return (m && i >= 0 && i < (int)m->ctx.size()) ? m->ctx[i] : nullptr; }
+int ptmi_multi_count(const ptmi_multi *m) { return m ? (int)m->d.size() : 0; }
+ptmi_ctx *ptmi_multi_context(ptmi_multi *m, int i) { return (m && i >= 0 && i < (int)m->d.size()) ? m->d[i].ctx : nullptr; }
 
 int ptmi_multi_upload_scene(ptmi_multi *m, const ptmi_triangle *tris, uint32_t nt, const ptmi_material *mats, uint32_t nm,
                             const ptmi_bvh_node *nodes, uint32_t nn, const ptmi_light *lights, uint32_t nl) {
@@ -388,10 +415,10 @@ int ptmi_multi_upload_scene(ptmi_multi *m, const ptmi_triangle *tris, uint32_t n
     // validation, the hierarchy and its images are built ONCE on the host (under device 0's options: all devices share them) and copied
     // to every device — the 1 M-triangle scene costs one build, not N (round 3: N x 196 ms)
     int rc = PTMI_OK;
-    PtPrepared *p = pt_prepare_scene(m->ctx[0], tris, nt, mats, nm, nodes, nn, lights, nl, &rc);
+    PtPrepared *p = pt_prepare_scene(m->d[0].ctx, tris, nt, mats, nm, nodes, nn, lights, nl, &rc);
     if (!p) return cfail(m, 0, rc, "ptmi_upload_scene (prepare)");
-    for (size_t i = 0; i < m->ctx.size() && rc == PTMI_OK; i++) {
-        rc = pt_install_scene(m->ctx[i], p);
+    for (size_t i = 0; i < m->d.size() && rc == PTMI_OK; i++) {
+        rc = pt_install_scene(m->d[i].ctx, p);
         if (rc) rc = cfail(m, (int)i, rc, "ptmi_upload_scene (install)");
     }
     pt_free_prepared(p);
@@ -427,7 +454,7 @@ int ptmi_multi_set_medium(ptmi_multi *m, const ptmi_medium *medium) {
     std::string why;                        // checked once, before any device changes: a rejected medium leaves every shard's in place
     int rc = pt_check_medium(medium, why);
     if (rc) return mfail(m, rc, "%s", why.c_str());
-    if (medium && pt_ctx_has_medium_grid(m->ctx[0]) && (rc = pt_check_medium_depth(medium, why))) return mfail(m, rc, "%s", why.c_str());
+    if (medium && pt_ctx_has_medium_grid(m->d[0].ctx) && (rc = pt_check_medium_depth(medium, why))) return mfail(m, rc, "%s", why.c_str());
     return each_ctx(m, "ptmi_set_medium", ptmi_set_medium, medium);
 }
 
@@ -435,7 +462,7 @@ int ptmi_multi_upload_medium_density(ptmi_multi *m, const float *rho, uint32_t n
     if (!m) return PTMI_E_INVALID;
     if (rho && nx != 0 && ny != 0 && nz != 0) {     // checked once, before any device changes: a rejected grid leaves every shard's in place
         std::string why;
-        const ptmi_medium *med = pt_ctx_medium(m->ctx[0]);
+        const ptmi_medium *med = pt_ctx_medium(m->d[0].ctx);
         if (!med) return mfail(m, PTMI_E_STATE, "no medium in place (ptmi_set_medium)");
         int rc = pt_check_medium_density(rho, nx, ny, nz, params, nullptr, why);
         if (!rc) rc = pt_check_medium_depth(med, why);
@@ -448,20 +475,20 @@ int ptmi_multi_upload_medium_density(ptmi_multi *m, const float *rho, uint32_t n
 int ptmi_multi_set_alpha_cutoff(ptmi_multi *m, const float *cutoff, uint32_t n_materials, const ptmi_alpha_params *params) {
     if (!m) return PTMI_E_INVALID;
     std::string why;                        // checked once, before any device changes: a rejected table leaves every shard's in place
-    if (!pt_ctx_has_scene(m->ctx[0])) return mfail(m, PTMI_E_INVALID, "no scene uploaded: the table belongs to a scene's materials");
+    if (!pt_ctx_has_scene(m->d[0].ctx)) return mfail(m, PTMI_E_INVALID, "no scene uploaded: the table belongs to a scene's materials");
     const bool remove = !cutoff || n_materials == 0u;
     const int rc = pt_check_alpha_cutoff(remove ? nullptr : cutoff, n_materials, params, why);
     if (rc) return mfail(m, rc, "%s", why.c_str());
-    if (!remove && n_materials != pt_ctx_materials(m->ctx[0]))
-        return mfail(m, PTMI_E_INVALID, "n_materials %u is not the loaded scene's %u", n_materials, pt_ctx_materials(m->ctx[0]));
+    if (!remove && n_materials != pt_ctx_materials(m->d[0].ctx))
+        return mfail(m, PTMI_E_INVALID, "n_materials %u is not the loaded scene's %u", n_materials, pt_ctx_materials(m->d[0].ctx));
     return each_ctx(m, "ptmi_set_alpha_cutoff", ptmi_set_alpha_cutoff, cutoff, n_materials, params);
 }
 
 int ptmi_multi_alpha_status(ptmi_multi *m, struct ptmi_alpha_status *out) {
     if (!m || !out) return PTMI_E_INVALID;
-    for (int i = 0; i < (int)m->ctx.size(); i++) {
+    for (int i = 0; i < (int)m->d.size(); i++) {
         struct ptmi_alpha_status st;
-        const int rc = ptmi_alpha_status(m->ctx[i], &st);
+        const int rc = ptmi_alpha_status(m->d[i].ctx, &st);
         if (rc) return cfail(m, i, rc, "ptmi_alpha_status");
         if (i == 0) *out = st;
         else {
@@ -488,7 +515,7 @@ int ptmi_multi_update_lights(ptmi_multi *m, uint32_t first, uint32_t count, cons
 }
 int ptmi_multi_scene_update_status(ptmi_multi *m, struct ptmi_scene_update_status *out) {
     if (!m || !out) return PTMI_E_INVALID;
-    const int rc = ptmi_scene_update_status(m->ctx[0], out);
+    const int rc = ptmi_scene_update_status(m->d[0].ctx, out);
     return rc ? cfail(m, 0, rc, "ptmi_scene_update_status") : PTMI_OK;
 }
 
@@ -506,7 +533,7 @@ int ptmi_multi_set_options(ptmi_multi *m, const ptmi_options *o) {
     if (o->tile_y0 != 0 || o->tile_y1 != 0) return mfail(m, PTMI_E_INVALID, "tile_y0 / tile_y1 must be 0: the rows are dealt out by the library");
     // The strip height decides which device owns which rows: changing it while frames are being accumulated would hand rows that
     // hold k frames to a device whose copy of them holds none. It takes effect with the next ptmi_multi_resize / _write_output.
-    const uint32_t new_strip = o->tile_strip ? o->tile_strip : auto_strip(m->H ? m->H : 1, (uint32_t)m->ctx.size());
+    const uint32_t new_strip = o->tile_strip ? o->tile_strip : auto_strip(m->H ? m->H : 1, (uint32_t)m->d.size());
     if (m->dispatched != 0 && new_strip != m->strip)
         return mfail(m, PTMI_E_STATE, "tile_strip %u -> %u while %llu dispatches are accumulated: call ptmi_multi_resize or ptmi_multi_write_output first",
                      m->strip, new_strip, (unsigned long long)m->dispatched);
@@ -518,88 +545,28 @@ int ptmi_multi_set_options(ptmi_multi *m, const ptmi_options *o) {
 }
 int ptmi_multi_get_options(const ptmi_multi *m, ptmi_options *o) {
     if (!m || !o) return PTMI_E_INVALID;
-    *o = m->opt; o->tile_strip = m->strip; o->tile_parts = (uint32_t)m->ctx.size(); o->tile_part = 0;
+    *o = m->opt; o->tile_strip = m->strip; o->tile_parts = (uint32_t)m->d.size(); o->tile_part = 0;
     return PTMI_OK;
 }
 
 int ptmi_multi_dispatch(ptmi_multi *m, const ptmi_camera *cam, uint32_t n_frames) {
     if (!m) return PTMI_E_INVALID;
-    const size_t n = m->ctx.size();
     // One ptmi_dispatch of 64 frames is ~45 launches and ~110 event calls: 1.15 ms of host time (profiles/r04_multi.json). Enqueued
     // in turn from one thread, device i would start i x that after device 0 — 8 ms at N = 8 against 16 ms of device time per step of
     // configs[4] — so every device gets its own enqueuing thread for the call (contexts are independent: own device, own streams;
     // a context is still only ever touched by one thread at a time).
-    std::vector<int> rcs(n, PTMI_OK);
-    if (n > 1) {
-        std::vector<std::thread> pool;
-        pool.reserve(n - 1);
-        for (size_t i = 1; i < n; i++) pool.emplace_back([&, i] { rcs[i] = ptmi_dispatch(m->ctx[i], cam, n_frames); });
-        rcs[0] = ptmi_dispatch(m->ctx[0], cam, n_frames);
-        for (std::thread &t : pool) t.join();
-    } else {
-        rcs[0] = ptmi_dispatch(m->ctx[0], cam, n_frames);
-    }
-    for (size_t i = 0; i < n; i++) if (rcs[i]) return cfail(m, (int)i, rcs[i], "ptmi_dispatch");
+    const int rc = each_threaded(m, "ptmi_dispatch", [&](size_t i) { return ptmi_dispatch(m->d[i].ctx, cam, n_frames); });
+    if (rc) return rc;
     m->dispatched++;
     return PTMI_OK;
 }
 
+// the gather of the output buffer alone
 int ptmi_multi_gather(ptmi_multi *m) {
     if (!m) return PTMI_E_INVALID;
-    const int n = (int)m->ctx.size();
-    if (n == 1 && m->comm.empty()) { m->gathered = m->dispatched; return PTMI_OK; }
-    if (m->W == 0) return mfail(m, PTMI_E_STATE, "no output buffer (ptmi_multi_resize)");
-    // (one device through RCCL: the degenerate gather of its whole frame onto itself, then copied back — the frame must come out of
-    // the collective unchanged: the N = 1 test of the RCCL leg on a one-GPU box. configure has sized the buffers for rows_max = H.)
-    const size_t share_f4 = m->rows_max * m->W;
-    hipStream_t s0 = pt_ctx_stream(m->ctx[0]);
-    // the timed region (ptmi_multi_gather_ms) starts when EVERY device has rendered its rows: pack, gather, unpack — not the wait for
-    // the slowest device, which is the dispatch's time
-    for (int i = 1; i < n; i++) {
-        MHIP(m, hipSetDevice(m->dev[i]));
-        MHIP(m, hipEventRecord(m->ev_done[i], pt_ctx_stream(m->ctx[i])));
-        MHIP(m, hipSetDevice(m->dev[0]));
-        MHIP(m, hipStreamWaitEvent(s0, m->ev_done[i], 0));
-    }
-    MHIP(m, hipSetDevice(m->dev[0]));
-    MHIP(m, hipEventRecord(m->g0, s0));
-    std::vector<DevBand> bands(n);
-    for (int i = 0; i < n; i++) {
-        bands[i] = pt_band_of(options_of(m, i), m->W, m->H);
-        MHIP(m, hipSetDevice(m->dev[i]));
-        // loopback: the previous gather's copy out of d_send[i] (on device 0's stream) must be done before it is packed again
-        if (m->comm.empty() && i > 0 && m->copied_recorded[i]) MHIP(m, hipStreamWaitEvent(pt_ctx_stream(m->ctx[i]), m->ev_copied[i], 0));
-        if (bands[i].rows) pt_launch_pack_rows(pt_ctx_stream(m->ctx[i]), pt_ctx_cus(m->ctx[i]) * 8, bands[i], pt_ctx_output(m->ctx[i]), m->d_send[i]);
-    }
-    if (!m->comm.empty()) {
-        MNCCL(m, g_rccl.GroupStart());
-        for (int i = 0; i < n; i++) {
-            ncclResult_t r = g_rccl.Gather(m->d_send[i], i == 0 ? m->d_recv : nullptr, share_f4 * 4, ncclFloat, 0, m->comm[i], pt_ctx_stream(m->ctx[i]));
-            if (r != ncclSuccess) { (void)g_rccl.GroupEnd(); return mfail(m, PTMI_E_HIP, "ncclGather (device %d) failed: %s", i, g_rccl.GetErrorString(r)); }
-        }
-        MNCCL(m, g_rccl.GroupEnd());
-    } else {
-        // loopback: device r's share is copied into slot r of device 0's receive buffer once it is packed
-        for (int i = 1; i < n; i++) {
-            MHIP(m, hipSetDevice(m->dev[i]));
-            MHIP(m, hipEventRecord(m->ev[i], pt_ctx_stream(m->ctx[i])));
-            MHIP(m, hipSetDevice(m->dev[0]));
-            MHIP(m, hipStreamWaitEvent(s0, m->ev[i], 0));
-            MHIP(m, hipMemcpyPeerAsync(m->d_recv + (size_t)i * share_f4, m->dev[0], m->d_send[i], m->dev[i], share_f4 * sizeof(float4), s0));
-            MHIP(m, hipEventRecord(m->ev_copied[i], s0));
-            m->copied_recorded[i] = 1;
-        }
-    }
-    MHIP(m, hipSetDevice(m->dev[0]));
-    // device 0's own rows are already in place (RCCL delivers a copy of them into slot 0; the single-device case unpacks that
-    // copy, so that the frame really went through the collective)
-    for (int i = m->comm.empty() || n > 1 ? 1 : 0; i < n; i++)
-        if (bands[i].rows) pt_launch_unpack_rows(s0, pt_ctx_cus(m->ctx[0]) * 8, bands[i], m->d_recv + (size_t)i * share_f4, pt_ctx_output(m->ctx[0]));
-    MHIP(m, hipEventRecord(m->g1, s0));
-    MHIP(m, hipGetLastError());
-    m->gather_timed = true;
-    m->gathered = m->dispatched;
-    return PTMI_OK;
+    // one device without RCCL holds its frame whole, before any ptmi_multi_resize too (ptmi_multi_gather_planes asks for the size first)
+    if (m->d.size() == 1 && m->comm.empty()) { mark_gathered(m, PTMI_MULTI_PLANE_OUTPUT); return PTMI_OK; }
+    return ptmi_multi_gather_planes(m, PTMI_MULTI_PLANE_OUTPUT);
 }
 
 int ptmi_multi_synchronize(ptmi_multi *m) {
@@ -610,9 +577,9 @@ int ptmi_multi_synchronize(ptmi_multi *m) {
 int ptmi_multi_throttle(ptmi_multi *m, uint32_t max_in_flight, uint32_t *in_flight) {
     if (!m) return PTMI_E_INVALID;
     uint32_t worst = 0;
-    for (size_t i = 0; i < m->ctx.size(); i++) {
+    for (size_t i = 0; i < m->d.size(); i++) {
         uint32_t n = 0;
-        int rc = ptmi_throttle(m->ctx[i], max_in_flight, &n);
+        int rc = ptmi_throttle(m->d[i].ctx, max_in_flight, &n);
         if (rc) return cfail(m, (int)i, rc, "ptmi_throttle");
         worst = std::max(worst, n);
     }
@@ -625,7 +592,7 @@ int ptmi_multi_read_output(ptmi_multi *m, float *dst, size_t n_floats) {
     if (m->gathered != m->dispatched) { int rc = ptmi_multi_gather(m); if (rc) return rc; }
     int rc = ptmi_multi_synchronize(m);
     if (rc) return rc;
-    rc = ptmi_read_output(m->ctx[0], dst, n_floats);
+    rc = ptmi_read_output(m->d[0].ctx, dst, n_floats);
     return rc ? cfail(m, 0, rc, "ptmi_read_output") : PTMI_OK;
 }
 
@@ -642,7 +609,7 @@ int ptmi_multi_blit(ptmi_multi *m, float *dst_f32, size_t n_floats, uint8_t *dst
     if (m->gathered != m->dispatched) { int rc = ptmi_multi_gather(m); if (rc) return rc; }
     int rc = ptmi_multi_synchronize(m);
     if (rc) return rc;
-    rc = ptmi_blit(m->ctx[0], dst_f32, n_floats, dst_rgba8, n_bytes);
+    rc = ptmi_blit(m->d[0].ctx, dst_f32, n_floats, dst_rgba8, n_bytes);
     return rc ? cfail(m, 0, rc, "ptmi_blit") : PTMI_OK;
 }
 
@@ -651,14 +618,8 @@ int ptmi_multi_blit(ptmi_multi *m, float *dst_f32, size_t n_floats, uint8_t *dst
 int ptmi_multi_set_aovs(ptmi_multi *m, uint32_t mask) {
     if (!m) return PTMI_E_INVALID;
     if (mask & ~kAovAll) return mfail(m, PTMI_E_INVALID, "unknown AOV bits 0x%x", mask & ~kAovAll);     // once, before any device changes
-    for (size_t i = 0; i < m->ctx.size(); i++) {
-        const int rc = ptmi_set_aovs(m->ctx[i], mask);
-        if (rc) {
-            cfail(m, (int)i, rc, "ptmi_set_aovs");
-            for (size_t j = 0; j < i; j++) (void)ptmi_set_aovs(m->ctx[j], m->aov_mask);      // the devices already changed go back
-            return rc;
-        }
-    }
+    const int rc = each_ctx_or_back(m, "ptmi_set_aovs", ptmi_set_aovs, mask, m->aov_mask);
+    if (rc) return rc;
     // a plane turned on is zero on every device, device 0's copy included: nothing to gather
     for (int k = 0; k < 3; k++) if (mask & ~m->aov_mask & kPlaneKinds[k].bit) m->gathered_plane[k] = m->dispatched;
     m->aov_mask = mask;
@@ -672,14 +633,8 @@ int ptmi_multi_get_aovs(const ptmi_multi *m, uint32_t *mask) {
 int ptmi_multi_set_moments(ptmi_multi *m, uint32_t on) {
     if (!m) return PTMI_E_INVALID;
     if (on > 1u) return mfail(m, PTMI_E_INVALID, "on = %u is not 0 or 1", on);
-    for (size_t i = 0; i < m->ctx.size(); i++) {
-        const int rc = ptmi_set_moments(m->ctx[i], on);
-        if (rc) {
-            cfail(m, (int)i, rc, "ptmi_set_moments");
-            for (size_t j = 0; j < i; j++) (void)ptmi_set_moments(m->ctx[j], m->moments_on ? 1u : 0u);
-            return rc;
-        }
-    }
+    const int rc = each_ctx_or_back(m, "ptmi_set_moments", ptmi_set_moments, on, m->moments_on ? 1u : 0u);
+    if (rc) return rc;
     if (on && !m->moments_on) m->gathered_plane[3] = m->dispatched;
     m->moments_on = on != 0;
     return configure(m);
@@ -696,11 +651,7 @@ int ptmi_multi_gather_planes(ptmi_multi *m, uint32_t planes) {
     if (planes & ~planes_on(m)) return mfail(m, PTMI_E_STATE, "plane bits 0x%x name planes that are off", planes & ~planes_on(m));
     if (planes == 0) return PTMI_OK;
     if (m->W == 0) return mfail(m, PTMI_E_STATE, "no output buffer (ptmi_multi_resize)");
-    if (m->ctx.size() == 1 && m->comm.empty()) {          // one device, no collective: its planes are the frame's
-        if (planes & PTMI_MULTI_PLANE_OUTPUT) m->gathered = m->dispatched;
-        for (int k = 0; k < 4; k++) if (planes & kPlaneKinds[k].bit) m->gathered_plane[k] = m->dispatched;
-        return PTMI_OK;
-    }
+    if (m->d.size() == 1 && m->comm.empty()) { mark_gathered(m, planes); return PTMI_OK; }      // one device, no collective: its planes are the frame's
     return gather_set(m, planes);
 }
 
@@ -711,7 +662,7 @@ int ptmi_multi_read_aov(ptmi_multi *m, uint32_t which, void *dst, size_t n_bytes
     if (stale && !(which & (which - 1u)) && dst) { int rc = ptmi_multi_gather_planes(m, stale); if (rc) return rc; }
     int rc = ptmi_multi_synchronize(m);
     if (rc) return rc;
-    rc = ptmi_read_aov(m->ctx[0], which, dst, n_bytes);
+    rc = ptmi_read_aov(m->d[0].ctx, which, dst, n_bytes);
     return rc ? cfail(m, 0, rc, "ptmi_read_aov") : PTMI_OK;
 }
 
@@ -720,7 +671,7 @@ int ptmi_multi_read_moments(ptmi_multi *m, float *dst, size_t n_floats) {
     if (m->moments_on && dst && stale_of(m, PTMI_MULTI_PLANE_MOMENTS)) { int rc = ptmi_multi_gather_planes(m, PTMI_MULTI_PLANE_MOMENTS); if (rc) return rc; }
     int rc = ptmi_multi_synchronize(m);
     if (rc) return rc;
-    rc = ptmi_read_moments(m->ctx[0], dst, n_floats);
+    rc = ptmi_read_moments(m->d[0].ctx, dst, n_floats);
     return rc ? cfail(m, 0, rc, "ptmi_read_moments") : PTMI_OK;
 }
 
@@ -736,28 +687,28 @@ int ptmi_multi_denoise(ptmi_multi *m, const ptmi_denoise_params *params, float *
         if (stale) { int rc = ptmi_multi_gather_planes(m, stale); if (rc) return rc; }
     }
     // on device 0's stream, behind the unpack: the filter sees the whole frame
-    const int rc = ptmi_denoise(m->ctx[0], params, dst_rgba, n_floats);
+    const int rc = ptmi_denoise(m->d[0].ctx, params, dst_rgba, n_floats);
     return rc ? cfail(m, 0, rc, "ptmi_denoise") : PTMI_OK;
 }
 
 int ptmi_multi_blit_denoised(ptmi_multi *m, float *dst_f32, size_t n_floats, uint8_t *dst_rgba8, size_t n_bytes) {
     if (!m) return PTMI_E_INVALID;
-    const int rc = ptmi_blit_denoised(m->ctx[0], dst_f32, n_floats, dst_rgba8, n_bytes);
+    const int rc = ptmi_blit_denoised(m->d[0].ctx, dst_f32, n_floats, dst_rgba8, n_bytes);
     return rc ? cfail(m, 0, rc, "ptmi_blit_denoised") : PTMI_OK;
 }
 
 int ptmi_multi_dispatch_adaptive(ptmi_multi *m, const ptmi_camera *cam, const ptmi_adaptive_params *params, uint32_t rounds) {
     if (!m) return PTMI_E_INVALID;
-    const int n = (int)m->ctx.size();
+    const int n = (int)m->d.size();
     ptmi_adaptive_params ap{};
     for (int i = 0; i < n; i++) {                         // checked once, on every device, before anything is enqueued
-        const int rc = pt_adaptive_check(m->ctx[i], cam, params, &ap);
+        const int rc = pt_adaptive_check(m->d[i].ctx, cam, params, &ap);
         if (rc) return cfail(m, i, rc, "ptmi_dispatch_adaptive");
     }
     if (rounds == 0) return PTMI_OK;
     if (ap.neighbourhood == 0u || (n == 1 && m->comm.empty())) {
         // selection is per pixel (or one device has the whole frame): every device runs all rounds on its own rows
-        const int rc = each_threaded(m, "ptmi_dispatch_adaptive", [&](size_t i) { return ptmi_dispatch_adaptive(m->ctx[i], cam, params, rounds); });
+        const int rc = each_threaded(m, "ptmi_dispatch_adaptive", [&](size_t i) { return ptmi_dispatch_adaptive(m->d[i].ctx, cam, params, rounds); });
         if (rc) return rc;
         m->dispatched++;
         return PTMI_OK;
@@ -767,11 +718,12 @@ int ptmi_multi_dispatch_adaptive(ptmi_multi *m, const ptmi_camera *cam, const pt
     if (m->flags_bytes != map_bytes) {
         for (int i = 0; i < n; i++) {
             MHIP(m, hipSetDevice(m->dev[i]));
-            if (m->d_flags[i]) { MHIP(m, hipStreamSynchronize(pt_ctx_stream(m->ctx[i]))); MHIP(m, hipFree(m->d_flags[i])); m->d_flags[i] = nullptr; }
-            MHIP(m, hipMalloc(&m->d_flags[i], std::max<size_t>(map_bytes, 16)));
+            MultiDev &d = m->d[i];
+            if (d.d_flags) { MHIP(m, hipStreamSynchronize(pt_ctx_stream(d.ctx))); MHIP(m, hipFree(d.d_flags)); d.d_flags = nullptr; }
+            MHIP(m, hipMalloc(&d.d_flags, std::max<size_t>(map_bytes, 16)));
+            d.flags_copied_recorded = false;
         }
         m->flags_bytes = map_bytes;
-        std::fill(m->flags_copied_recorded.begin(), m->flags_copied_recorded.end(), 0);
     }
     std::vector<uint8_t *> share(n, nullptr);
     for (uint32_t r = 0; r < rounds; r++) {
@@ -780,32 +732,32 @@ int ptmi_multi_dispatch_adaptive(ptmi_multi *m, const ptmi_camera *cam, const pt
             // loopback: every device has copied share i of the round before out of the plane it is written to again
             if (m->comm.empty())
                 for (int d = 0; d < n; d++)
-                    if (d != i && m->flags_copied_recorded[d]) MHIP(m, hipStreamWaitEvent(pt_ctx_stream(m->ctx[i]), m->ev_flags_copied[d], 0));
-            const int rc = pt_adaptive_flags(m->ctx[i], &ap, r == 0 && cam->frame_index == 0u, &share[i]);
+                    if (d != i && m->d[d].flags_copied_recorded) MHIP(m, hipStreamWaitEvent(pt_ctx_stream(m->d[i].ctx), m->d[d].ev_flags_copied, 0));
+            const int rc = pt_adaptive_flags(m->d[i].ctx, &ap, r == 0 && cam->frame_index == 0u, &share[i]);
             if (rc) return cfail(m, i, rc, "ptmi_dispatch_adaptive (flags)");
-            if (m->comm.empty()) MHIP(m, hipEventRecord(m->ev_flags[i], pt_ctx_stream(m->ctx[i])));
+            if (m->comm.empty()) MHIP(m, hipEventRecord(m->d[i].ev_flags, pt_ctx_stream(m->d[i].ctx)));
         }
         if (!m->comm.empty()) {
             MNCCL(m, g_rccl.GroupStart());
             for (int i = 0; i < n; i++) {
-                ncclResult_t e = g_rccl.AllGather(share[i], m->d_flags[i], share_px, ncclUint8, m->comm[i], pt_ctx_stream(m->ctx[i]));
+                ncclResult_t e = g_rccl.AllGather(share[i], m->d[i].d_flags, share_px, ncclUint8, m->comm[i], pt_ctx_stream(m->d[i].ctx));
                 if (e != ncclSuccess) { (void)g_rccl.GroupEnd(); return mfail(m, PTMI_E_HIP, "ncclAllGather (device %d) failed: %s", i, g_rccl.GetErrorString(e)); }
             }
             MNCCL(m, g_rccl.GroupEnd());
         } else {
             for (int d = 0; d < n; d++) {
                 MHIP(m, hipSetDevice(m->dev[d]));
-                hipStream_t sd = pt_ctx_stream(m->ctx[d]);
+                hipStream_t sd = pt_ctx_stream(m->d[d].ctx);
                 for (int i = 0; i < n; i++) {
-                    if (i != d) MHIP(m, hipStreamWaitEvent(sd, m->ev_flags[i], 0));
-                    MHIP(m, hipMemcpyPeerAsync(m->d_flags[d] + (size_t)i * share_px, m->dev[d], share[i], m->dev[i], share_px, sd));
+                    if (i != d) MHIP(m, hipStreamWaitEvent(sd, m->d[i].ev_flags, 0));
+                    MHIP(m, hipMemcpyPeerAsync(m->d[d].d_flags + (size_t)i * share_px, m->dev[d], share[i], m->dev[i], share_px, sd));
                 }
-                MHIP(m, hipEventRecord(m->ev_flags_copied[d], sd));
-                m->flags_copied_recorded[d] = 1;
+                MHIP(m, hipEventRecord(m->d[d].ev_flags_copied, sd));
+                m->d[d].flags_copied_recorded = 1;
             }
         }
         const int rc = each_threaded(m, "ptmi_dispatch_adaptive (round)", [&](size_t i) {
-            return pt_adaptive_round(m->ctx[i], cam, &ap, m->d_flags[i], (uint32_t)share_px, r == 0);
+            return pt_adaptive_round(m->d[i].ctx, cam, &ap, m->d[i].d_flags, (uint32_t)share_px, r == 0);
         });
         if (rc) return rc;
     }
@@ -817,9 +769,9 @@ int ptmi_multi_adaptive_status(ptmi_multi *m, struct ptmi_adaptive_status *out) 
     if (!m || !out) return PTMI_E_INVALID;
     struct ptmi_adaptive_status sum{};
     bool first = true;
-    for (size_t i = 0; i < m->ctx.size(); i++) {
+    for (size_t i = 0; i < m->d.size(); i++) {
         struct ptmi_adaptive_status s;
-        const int rc = ptmi_adaptive_status(m->ctx[i], &s);
+        const int rc = ptmi_adaptive_status(m->d[i].ctx, &s);
         if (rc) return cfail(m, (int)i, rc, "ptmi_adaptive_status");
         if (i == 0) sum.rounds = s.rounds;
         sum.active += s.active; sum.samples += s.samples;
@@ -835,9 +787,9 @@ int ptmi_multi_adaptive_status(ptmi_multi *m, struct ptmi_adaptive_status *out) 
 int ptmi_multi_get_stats(ptmi_multi *m, ptmi_stats *out) {
     if (!m || !out) return PTMI_E_INVALID;
     ptmi_stats sum;
-    for (size_t i = 0; i < m->ctx.size(); i++) {
+    for (size_t i = 0; i < m->d.size(); i++) {
         ptmi_stats s;
-        int rc = ptmi_get_stats(m->ctx[i], &s);
+        int rc = ptmi_get_stats(m->d[i].ctx, &s);
         if (rc) return cfail(m, (int)i, rc, "ptmi_get_stats");
         if (i == 0) { sum = s; continue; }
         sum.paths += s.paths; sum.segments += s.segments; sum.shadow_rays += s.shadow_rays; sum.shadow_traced += s.shadow_traced;
