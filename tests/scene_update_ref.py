@@ -25,7 +25,7 @@ REF_NONE = 0xFFFFFFFF
 LEAF_OFF_BITS = 26
 LEAF_OFF_MASK = (1 << LEAF_OFF_BITS) - 1
 LEAF_MAX_TRIS = 32
-OWN_PAD_LOG2 = -16                    # csrc/fast_tree.h PT_OWN_PAD_LOG2
+OWN_PAD_LOG2 = -16                    # csrc/pt_box.h PT_OWN_PAD_LOG2
 OWN_SLIVER = 16.0                     # csrc/fast_tree.h PT_OWN_SLIVER
 F = np.float32
 D = np.float64

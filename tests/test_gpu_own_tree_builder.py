@@ -6,6 +6,8 @@ the padding to spare, the quantised planes holding the padded boxes), share with
 only (pad, safe origin, root box, leaf boxes) bit for bit, be the same bytes on every upload, replay on the CPU exactly as the
 reference traversal, cost about as much per ray as the host tree, and give the oracle's hits, shadow predicates and frames on the GPU."""
 import ctypes
+import hashlib
+import json
 import os
 import sys
 
@@ -322,6 +324,37 @@ def test_device_build_is_deterministic(ctx):
             got = m.read_image(i)
             assert info_bytes(got[0]) == info_bytes(a[0])
             assert all(same_arrays(x, y) for x, y in zip(got[1:], a[1:]))
+
+
+# -- 4b. the device image keeps its bits ----------------------------------------------------------------------------------------------
+# Nothing above pins the device tree's topology against a model, so its bytes are: tests/golden/own_tree_gpu_digests.json (written by
+# tests/golden/make_own_tree_gpu_digests.py) holds a SHA-256 of each array of read_image() for the smallest scenes the builder accepts.
+DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "own_tree_gpu_digests.json")
+DIGEST_CASES = [("grid48", 1), ("grid48", 2), ("grid48", 4), ("soup20k", 0)]          # (scene, leaf_tris)
+
+
+def digest_key(name, leaf_tris):
+    return f"{name}/leaf_tris={leaf_tris}"
+
+
+def device_image_digests(ctx, name, leaf_tris):
+    """(ptmi_stats of the upload, {array: SHA-256}) of the image the device builder makes"""
+    st = upload(ctx, scene(name), 2, leaf_tris=leaf_tris, leaves=2)
+    info, wn, qn, tp, lb = ctx.read_image()
+
+    def sha(a):
+        return None if a is None else hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+    return st, {"info": hashlib.sha256(info_bytes(info)).hexdigest(), "wnodes": sha(wn), "qnodes": sha(qn), "tripos": sha(tp), "leafbox": sha(lb)}
+
+
+@pytest.mark.parametrize("name,leaf_tris", DIGEST_CASES)
+def test_device_image_is_the_recorded_one(ctx, name, leaf_tris):
+    st, got = device_image_digests(ctx, name, leaf_tris)
+    assert st.tree_builder_used == 2                                    # a fallback to the host must not pass
+    with open(DIGESTS) as f:
+        want = json.load(f)
+    assert got == want[digest_key(name, leaf_tris)]
 
 
 # -- 5, 6. CPU replay of the device image: the reference traversal's results, and the work per ray ----------------------------------

@@ -14,10 +14,6 @@
 #ifndef PT_OWN_C_OPEN
 #define PT_OWN_C_OPEN 0.35           /* ... opening a leaf (its entry leaves the lane's list, the loop is set up, a share of a vote) */
 #endif
-#ifndef PT_OWN_PAD_LOG2
-#define PT_OWN_PAD_LOG2 (-16)        /* own leaves' boxes grow by 2^this x the largest coordinate magnitude of the scene */
-#endif
-
 #ifndef PT_OWN_SLIVER
 #define PT_OWN_SLIVER 16.0           /* own leaves: a triangle whose longest edge squared exceeds this x |e1 x e2| is a SLIVER */
 #endif

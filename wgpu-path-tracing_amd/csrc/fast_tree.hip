@@ -19,10 +19,8 @@
 // on the longest axis; a full-sweep SAH tree over the same leaves halves the boxes a Cornell ray
 // tests (25.7 -> 13.6 per ray, measured). Irregular rays (a zero, subnormal or non-finite direction
 // component) keep walking the reference's own tree (traverse.hip).
-#include "fast_tree.h"
+#include "pt_box.h"
 #include "pt_device.h"
-#include "wide_node.h"
-#include <limits>
 
 #include <algorithm>
 #include <cmath>
@@ -37,17 +35,13 @@
 
 namespace {
 
-struct Box {
-    float mn[3], mx[3];
-    void reset() { for (int k = 0; k < 3; k++) { mn[k] = INFINITY; mx[k] = -INFINITY; } }
-    void grow(const float *lo, const float *hi) {
-        for (int k = 0; k < 3; k++) { mn[k] = std::min(mn[k], lo[k]); mx[k] = std::max(mx[k], hi[k]); }
-    }
-    void grow(const Box &o) { grow(o.mn, o.mx); }
-    double area() const {
-        double dx = (double)mx[0] - mn[0], dy = (double)mx[1] - mn[1], dz = (double)mx[2] - mn[2];
-        return 2.0 * (dx * dy + dy * dz + dz * dx);
-    }
+struct Box : Box6 {                       // pt_box.h's box under the builder's verbs
+    Box() = default;
+    Box(const Box6 &b) : Box6(b) {}
+    void reset() { *this = pt_empty_box(); }
+    void grow(const float *lo, const float *hi) { *this = pt_unite(*this, lo, hi); }
+    void grow(const Box6 &o) { grow(o.mn, o.mx); }
+    double area() const { return pt_box_area(*this); }
 };
 
 struct Builder {
@@ -183,10 +177,7 @@ struct WideView {
     static bool leaf(uint32_t ref) { return (ref & PT_REF_LEAF) != 0u; }
     uint32_t ref(uint32_t n, int side) const { return pt_wide_ref(&w[(size_t)n * 4], side); }
     void set_ref(uint32_t n, int side, uint32_t r) { pt_wide_set_ref(&w[(size_t)n * 4], side, r); }
-    Box box(uint32_t n, int side) const {
-        const PtWideChild c = pt_wide_child(&w[(size_t)n * 4], side);
-        return Box{{c.lo[0], c.lo[1], c.lo[2]}, {c.hi[0], c.hi[1], c.hi[2]}};
-    }
+    Box box(uint32_t n, int side) const { return pt_child_box(&w[(size_t)n * 4], side); }
     void set_box(uint32_t n, int side, const Box &b) { pt_wide_set_box(&w[(size_t)n * 4], side, b.mn, b.mx); }
 };
 
@@ -360,27 +351,16 @@ bool pt_build_own_tree(const ptmi_triangle *tris, const std::vector<uint32_t> &w
     const uint32_t n = (uint32_t)which.size();
     if (n == 0) return false;
     max_leaf = std::max(1u, std::min(max_leaf, PT_LEAF_MAX_TRIS));
-    // one "leaf" per triangle: the box of its three vertices and of v0 + e1, v0 + e2 as the intersection test sees them, a sliver's
-    // grown by its reference leaf's box (fast_tree.h pt_own_sliver); the padding comes from the largest coordinate of these boxes
+    // one "leaf" per triangle: its unit box (pt_box.h pt_unit_box); the padding comes from the largest coordinate of these boxes
     std::vector<PtFastLeaf> units(n);
     double biggest = 0.0;
     for (uint32_t i = 0; i < n; i++) {
         const ptmi_triangle &t = tris[which[i]];
+        const PtUnitBox ub = pt_unit_box(t.v0, t.v1, t.v2, [&] { return pt_leafbox_row(leafbox.data(), which[i]); });
+        if (ub.bad) return false;
         PtFastLeaf &u = units[i];
-        for (int k = 0; k < 3; k++) {
-            const float a = t.v0[k], b = t.v1[k], c = t.v2[k];
-            const float b2 = a + (b - a), c2 = a + (c - a);
-            if (!std::isfinite(a) || !std::isfinite(b) || !std::isfinite(c) || !std::isfinite(b2) || !std::isfinite(c2)) return false;
-            u.mn[k] = std::min(std::min(std::min(a, b), std::min(c, b2)), c2);
-            u.mx[k] = std::max(std::max(std::max(a, b), std::max(c, b2)), c2);
-        }
-        if (pt_own_sliver(t.v0, t.v1, t.v2)) {           // fast_tree.h: a sliver's box grows by its reference leaf's (not the padding)
-            const float4 lo = leafbox[2 * (size_t)which[i]], hi = leafbox[2 * (size_t)which[i] + 1];
-            const float l[3] = {lo.x, lo.y, lo.z}, h[3] = {hi.x, hi.y, hi.z};
-            for (int k = 0; k < 3; k++) { u.mn[k] = std::min(u.mn[k], l[k]); u.mx[k] = std::max(u.mx[k], h[k]); }
-        }
-        // (after the union: an uploaded tree's leaf box may reach beyond its triangles, and the padding must cover what is walked)
-        for (int k = 0; k < 3; k++) biggest = std::max(biggest, std::max(std::fabs((double)u.mn[k]), std::fabs((double)u.mx[k])));
+        for (int k = 0; k < 3; k++) { u.mn[k] = ub.box.mn[k]; u.mx[k] = ub.box.mx[k]; }
+        biggest = std::max(biggest, (double)pt_bits_float(ub.biggest));
         u.ref = PT_REF_LEAF | i; u.weight = 1u;
     }
     const bool dbg = std::getenv("PTMI_TREE_DEBUG") != nullptr;
@@ -464,27 +444,19 @@ bool pt_build_own_tree(const ptmi_triangle *tris, const std::vector<uint32_t> &w
     }
     const auto t3 = now();
     // padding (see the header): every child box, and the root box the kernels test first
-    const float pad = std::max((float)std::ldexp(biggest, PT_OWN_PAD_LOG2 + (int)env_or("PTMI_OWN_PAD_EXTRA_LOG2", 0)), std::numeric_limits<float>::min());
-    if (!std::isfinite(pad)) return false;
-    auto lower = [&](float x) { const float y = x - pad; return y < x ? y : std::nextafterf(x, -INFINITY); };
-    auto upper = [&](float x) { const float y = x + pad; return y > x ? y : std::nextafterf(x, INFINITY); };
+    if (!pt_own_padding(biggest, out.pad, out.safe_origin, (int)env_or("PTMI_OWN_PAD_EXTRA_LOG2", 0))) return false;
     Box rb; rb.reset();
     if (out.root_ref & PT_REF_LEAF) { for (const PtFastLeaf &u : units) rb.grow(u.mn, u.mx); }
     else { WideView nv{out.wnodes}; rb = nv.box(0, 0); rb.grow(nv.box(0, 1)); }
-    for (int k = 0; k < 3; k++) { out.root_min[k] = lower(rb.mn[k]); out.root_max[k] = upper(rb.mx[k]); }
+    rb = pt_pad_box(rb, out.pad);
+    for (int k = 0; k < 3; k++) { out.root_min[k] = rb.mn[k]; out.root_max[k] = rb.mx[k]; }
     {
         WideView nv{out.wnodes};
         for (uint32_t i = 0; i < out.wnodes.size() / 4; i++)
-            for (int side = 0; side < 2; side++) {
-                Box b = nv.box(i, side);
-                for (int k = 0; k < 3; k++) { b.mn[k] = lower(b.mn[k]); b.mx[k] = upper(b.mx[k]); }
-                nv.set_box(i, side, b);
-            }
+            for (int side = 0; side < 2; side++) nv.set_box(i, side, pt_pad_box(nv.box(i, side), out.pad));
     }
     for (int k = 0; k < 3; k++) if (!std::isfinite(out.root_min[k]) || !std::isfinite(out.root_max[k])) return false;
     if (dbg) std::fprintf(stderr, "own tree: %u triangles -> %zu nodes, %u leaves, depth %u; hierarchy %.1f ms, collapse %.1f, emit + rotations %.1f, padding %.1f\n",
                           n, out.wnodes.size() / 4, out.n_leaves, out.depth, ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, now()));
-    out.pad = pad;
-    out.safe_origin = (float)std::min(8.0 * biggest, 3.0e38);      // the rounding of the fused tests stays below a quarter of the padding up to here
     return true;
 }

@@ -5,8 +5,7 @@
 // kernels break ties by the lowest triangle index and verify every winner against its reference leaf's box, so only the work per ray
 // depends on the tree.
 //
-//   units     one box per listed triangle, min / max over a, b, c, a + (b - a), a + (c - a) as the host computes them, a sliver's
-//             grown by its reference leaf's box (fast_tree.h pt_own_sliver); |coordinate| of the unit boxes max-reduced for the
+//   units     one box per listed triangle, the host's (pt_box.h pt_unit_box); |coordinate| of the unit boxes max-reduced for the
 //             padding (exact in f32)
 //   PLOC      Morton codes of the unit centroids, made unique by the unit's index and radix-sorted (hipCUB); then repeatedly: every
 //             cluster's nearest neighbour within +-PT_PLOC_RADIUS sorted positions (smallest surface area of the union, ties to the
@@ -18,23 +17,19 @@
 //             depend on the order of arrival
 //   emit      every node walks up to the root summing the offsets its ancestors stored for it: its preorder number among the
 //             surviving inner nodes, its first position in leaf order, its level. Inner nodes write their wide node (child boxes
-//             padded outward exactly as the host pads them), units write their triangle (v0, bits(original index)), e1, e2
+//             padded outward by the host's pt_box.h pt_pad_lower / pt_pad_upper), units write their triangle (v0, bits(original index)), e1, e2
 //   quantise  the host's grid (quantise.hip pt_quant_grid) from the min / max of the padded boxes; the top PT_QCACHE_NODES nodes
 //             breadth-first at the front, the others in preorder; every child through the host's own wide_node.h pt_quantise_child
 //
 // Every step is deterministic: the same scene gives the same bytes on every run and every device. Scratch is sized from the scene and
-// freed on every path; any failure returns false and the caller builds on the host.
-#include "fast_tree.h"
+// owned by the scope of one build (pt_dev_build.h DevScratch); any failure returns false and the caller builds on the host.
+#include "pt_box.h"
+#include "pt_dev_build.h"
 #include "pt_device.h"
 #include "ptmi_layout.h"
-#include "wide_node.h"
 
-#include <hipcub/hipcub.hpp>
-
-#include <cfloat>
 #include <chrono>
 #include <cmath>
-#include <cstring>
 #include <vector>
 
 #ifndef PT_PLOC_RADIUS
@@ -46,27 +41,6 @@ namespace {
 constexpr int TB = 256;
 constexpr int R = PT_PLOC_RADIUS;
 constexpr int kMaxPasses = 1024;     // PLOC passes before the build is refused (a backstop: real scenes take 40 - 70)
-
-struct Box6 { float mn[3], mx[3]; };
-
-// std::min / std::max exactly (the host's Box::grow): the first argument unless the second is strictly smaller / larger
-__device__ __forceinline__ float mn_(float a, float b) { return b < a ? b : a; }
-__device__ __forceinline__ float mx_(float a, float b) { return a < b ? b : a; }
-
-__device__ __forceinline__ Box6 unite(const Box6 &a, const Box6 &b) {
-    Box6 u;
-    for (int k = 0; k < 3; k++) { u.mn[k] = mn_(a.mn[k], b.mn[k]); u.mx[k] = mx_(a.mx[k], b.mx[k]); }
-    return u;
-}
-
-__device__ __forceinline__ double area(const Box6 &b) {          // fast_tree.hip Box::area
-    const double dx = (double)b.mx[0] - b.mn[0], dy = (double)b.mx[1] - b.mn[1], dz = (double)b.mx[2] - b.mn[2];
-    return 2.0 * (dx * dy + dy * dz + dz * dx);
-}
-
-// order-preserving float <-> uint (min / max reductions with integer atomics)
-__device__ __forceinline__ uint32_t ord(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-float unord_f(uint32_t u) { u = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u; float f; std::memcpy(&f, &u, 4); return f; }
 
 struct Red {                          // reductions of the build, zeroed before it
     uint32_t biggest;                 // bits of max |coordinate| over the unit boxes (non-negative floats order as integers)
@@ -82,48 +56,21 @@ __global__ void k_units(uint32_t n, const ptmi_triangle *__restrict__ tris, cons
     const uint32_t i = blockIdx.x * TB + threadIdx.x;
     if (i >= n) return;
     const ptmi_triangle &t = tris[which[i]];
-    Box6 u; uint32_t big = 0, bad = 0;
+    const PtUnitBox u = pt_unit_box(t.v0, t.v1, t.v2, [&] { return pt_leafbox_row(leafbox, which[i]); });
+    box[i] = u.box;
+    if (u.bad) { atomicOr(&red->bad, 1u); return; }
+    atomicMax(&red->biggest, u.biggest);
     for (int k = 0; k < 3; k++) {
-        const float a = t.v0[k], b = t.v1[k], c = t.v2[k];
-        const float b2 = a + (b - a), c2 = a + (c - a);
-        if (!isfinite(a) || !isfinite(b) || !isfinite(c) || !isfinite(b2) || !isfinite(c2)) bad = 1;
-        u.mn[k] = mn_(mn_(mn_(a, b), mn_(c, b2)), c2);
-        u.mx[k] = mx_(mx_(mx_(a, b), mx_(c, b2)), c2);
-    }
-    if (pt_own_sliver(t.v0, t.v1, t.v2)) {                       // as the host: a sliver's box grows by its reference leaf's
-        const float4 lo = leafbox[2 * (size_t)which[i]], hi = leafbox[2 * (size_t)which[i] + 1];
-        const float l[3] = {lo.x, lo.y, lo.z}, h[3] = {hi.x, hi.y, hi.z};
-        for (int k = 0; k < 3; k++) { u.mn[k] = mn_(u.mn[k], l[k]); u.mx[k] = mx_(u.mx[k], h[k]); }
-    }
-    for (int k = 0; k < 3; k++)                                  // (after the union, as the host)
-        big = max(big, max(__float_as_uint(fabsf(u.mn[k])), __float_as_uint(fabsf(u.mx[k]))));
-    box[i] = u;
-    if (bad) { atomicOr(&red->bad, 1u); return; }
-    atomicMax(&red->biggest, big);
-    for (int k = 0; k < 3; k++) {
-        const uint32_t c = ord(0.5f * u.mn[k] + 0.5f * u.mx[k]);
+        const uint32_t c = pt_ord(0.5f * u.box.mn[k] + 0.5f * u.box.mx[k]);
         atomicMin(&red->cmin[k], c); atomicMax(&red->cmax[k], c);
     }
-}
-
-__device__ __forceinline__ uint32_t expand10(uint32_t v) {          // 10 bits -> every third bit
-    v = (v * 0x00010001u) & 0xFF0000FFu;
-    v = (v * 0x00000101u) & 0x0F00F00Fu;
-    v = (v * 0x00000011u) & 0xC30C30C3u;
-    v = (v * 0x00000005u) & 0x49249249u;
-    return v;
 }
 
 __global__ void k_morton(uint32_t n, const Box6 *__restrict__ box, float3 lo, float3 inv, unsigned long long *__restrict__ keys) {
     const uint32_t i = blockIdx.x * TB + threadIdx.x;
     if (i >= n) return;
     const Box6 b = box[i];
-    const float cx = (0.5f * b.mn[0] + 0.5f * b.mx[0] - lo.x) * inv.x;
-    const float cy = (0.5f * b.mn[1] + 0.5f * b.mx[1] - lo.y) * inv.y;
-    const float cz = (0.5f * b.mn[2] + 0.5f * b.mx[2] - lo.z) * inv.z;
-    auto q = [](float v) { v = v * 1024.0f; v = v < 0.0f ? 0.0f : (v > 1023.0f ? 1023.0f : v); return (uint32_t)v; };
-    const uint32_t code = (expand10(q(cx)) << 2) | (expand10(q(cy)) << 1) | expand10(q(cz));
-    keys[i] = ((unsigned long long)code << 32) | i;
+    keys[i] = ((unsigned long long)pt_morton30(b.mn, b.mx, lo, inv) << 32) | i;
 }
 
 __global__ void k_first_clusters(uint32_t n, const unsigned long long *__restrict__ keys, uint32_t *__restrict__ clu) {
@@ -148,7 +95,7 @@ __global__ void __launch_bounds__(TB) k_nearest(uint32_t m, const uint32_t *__re
     const int j0 = max(0, i - R), j1 = min((int)m - 1, i + R);
     for (int j = j0; j <= j1; j++) {
         if (j == i) continue;
-        const double a = area(unite(me, s[j - base]));
+        const double a = pt_box_area(pt_unite(me, s[j - base]));
         if (a < best || bj < 0) { best = a; bj = j; }              // ascending j, strict <: ties go to the lower position
     }
     nn[i] = (uint32_t)bj;
@@ -178,7 +125,7 @@ __global__ void k_merge(uint32_t m, uint32_t n, uint32_t first_new, const uint32
         const uint32_t a = clu[i], b = clu[nn[i]];
         node = first_new + (uint32_t)(e >> 32);
         child[node - n] = make_uint2(a, b);
-        box[node] = unite(box[a], box[b]);
+        box[node] = pt_unite(box[a], box[b]);
         parent[a] = node; parent[b] = node;
         const uint32_t lv = 1u + max(a < n ? 1u : (uint32_t)level[a - n], b < n ? 1u : (uint32_t)level[b - n]);
         level[node - n] = (uint8_t)min(lv, 255u);                      // (the build is refused long before 255)
@@ -205,9 +152,9 @@ __global__ void k_collapse(uint32_t n, uint32_t max_leaf, double c_box, double c
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");           // the other child's stores are visible from here on
         const uint2 ch = child[node - n];
         const Box6 bl = box[ch.x], br = box[ch.y];
-        const double a = area(unite(bl, br));
+        const double a = pt_box_area(pt_unite(bl, br));
         const double lc = cost[ch.x], rc = cost[ch.y];
-        const double inner = c_box + (a > 0.0 ? (area(bl) * lc + area(br) * rc) / a : lc + rc);
+        const double inner = c_box + (a > 0.0 ? (pt_box_area(bl) * lc + pt_box_area(br) * rc) / a : lc + rc);
         const uint32_t k = cnt[ch.x] + cnt[ch.y];
         const double as_leaf = c_open + c_tri * (double)k;
         const bool lf = k <= max_leaf && as_leaf <= inner;
@@ -218,9 +165,6 @@ __global__ void k_collapse(uint32_t n, uint32_t max_leaf, double c_box, double c
         node = parent[node];
     }
 }
-
-__device__ __forceinline__ float lower(float x, float pad) { const float y = x - pad; return y < x ? y : nextafterf(x, -INFINITY); }
-__device__ __forceinline__ float upper(float x, float pad) { const float y = x + pad; return y > x ? y : nextafterf(x, INFINITY); }
 
 // one thread per node: walk to the root, then write what this node owns in the image
 __global__ void k_emit(uint32_t n_all, uint32_t n, uint32_t root, float pad, const ptmi_triangle *__restrict__ tris,
@@ -254,8 +198,8 @@ __global__ void k_emit(uint32_t n_all, uint32_t n, uint32_t root, float pad, con
     for (int s = 0; s < 2; s++) {
         const Box6 e = box[c[s]];
         for (int k = 0; k < 3; k++) {
-            b[s].mn[k] = lower(e.mn[k], pad); b[s].mx[k] = upper(e.mx[k], pad);
-            atomicMin(&red->qmin[k], ord(b[s].mn[k])); atomicMax(&red->qmax[k], ord(b[s].mx[k]));
+            b[s].mn[k] = pt_pad_lower(e.mn[k], pad); b[s].mx[k] = pt_pad_upper(e.mx[k], pad);
+            atomicMin(&red->qmin[k], pt_ord(b[s].mn[k])); atomicMax(&red->qmax[k], pt_ord(b[s].mx[k]));
         }
         if (leafy[c[s]]) {
             ref[s] = PT_REF_LEAF | ((cnt[c[s]] - 1u) << PT_LEAF_OFF_BITS) | ctri[s];
@@ -307,191 +251,163 @@ __global__ void k_quantise(uint32_t m, PtQuantGrid g, const float4 *__restrict__
     growth[i] = gsum; grown[i] = gn;
 }
 
-template <class T> void dfree(T *&p) { if (p) { (void)hipFree(p); p = nullptr; } }
-
-}  // namespace
-
-#define GT(expr) do { if ((expr) != hipSuccess) goto done; } while (0)
-
-bool pt_build_own_tree_gpu(const ptmi_triangle *d_tris, const std::vector<uint32_t> &which, const std::vector<float4> &leafbox,
-                           uint32_t max_leaf, uint32_t depth_limit, hipStream_t s, PtOwnTreeGpu &out) {
-    out.release();
+// the build itself; every allocation is mem's until the three buffers of `out` leave through keep(). The stream may still be busy on failure.
+bool build_own_tree(const ptmi_triangle *d_tris, const std::vector<uint32_t> &which, const std::vector<float4> &leafbox, uint32_t max_leaf,
+                    uint32_t depth_limit, hipStream_t s, DevScratch &mem, PtOwnTreeGpu &out) {
     const uint32_t n = (uint32_t)which.size();
     if (n < 2 || n > PT_LEAF_OFF_MASK) return false;
     max_leaf = std::max(1u, std::min(max_leaf, PT_LEAF_MAX_TRIS));
     const uint32_t n_all = 2 * n - 1;
     auto blocks = [](uint32_t k) { return dim3((k + TB - 1) / TB); };
-    bool ok = false;
-    uint32_t *d_which = nullptr, *d_clu[2] = {nullptr, nullptr}, *d_nn = nullptr, *d_parent = nullptr, *d_arr = nullptr;
-    uint32_t *d_cnt = nullptr, *d_icnt = nullptr, *d_leafy = nullptr, *d_renum = nullptr, *d_rest_f = nullptr, *d_rest = nullptr;
-    uint32_t *d_grown = nullptr, *d_grown_sum = nullptr;
-    uint8_t *d_level = nullptr;
-    double *d_cost = nullptr, *d_growth = nullptr, *d_growth_sum = nullptr;
-    unsigned long long *d_keys = nullptr, *d_keys2 = nullptr, *d_flags = nullptr, *d_ex = nullptr;
-    float4 *d_leafbox = nullptr;
-    Box6 *d_box = nullptr; uint2 *d_child = nullptr; Step *d_step = nullptr; Red *d_red = nullptr;
-    float4 *d_wn = nullptr, *d_tp = nullptr; uint4 *d_qn = nullptr;
-    void *d_tmp = nullptr; size_t tmp_bytes = 0;
-    Red h{};
-    uint32_t m = n, next = n, root = 0, n_inner = 0;
-    float pad = 0.0f;
-    double biggest = 0.0;
+    auto read = [&](void *to, const void *from, size_t bytes) { return hip_ok(hipMemcpyAsync(to, from, bytes, hipMemcpyDeviceToHost, s)); };
+    auto settled = [&] { return hip_ok(hipStreamSynchronize(s)) && hip_ok(hipGetLastError()); };
 
-    GT(hipMalloc(&d_which, (size_t)n * 4)); GT(hipMalloc(&d_box, (size_t)n_all * sizeof(Box6)));
-    GT(hipMalloc(&d_red, sizeof(Red)));
-    GT(hipMemcpyAsync(d_which, which.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-    GT(hipMalloc(&d_leafbox, leafbox.size() * sizeof(float4)));
-    GT(hipMemcpyAsync(d_leafbox, leafbox.data(), leafbox.size() * sizeof(float4), hipMemcpyHostToDevice, s));
-    {
-        Red r0{}; r0.biggest = 0; r0.bad = 0;
-        for (int k = 0; k < 3; k++) { r0.cmin[k] = r0.qmin[k] = 0xFFFFFFFFu; r0.cmax[k] = r0.qmax[k] = 0u; }
-        GT(hipMemcpyAsync(d_red, &r0, sizeof r0, hipMemcpyHostToDevice, s));
-        k_units<<<blocks(n), TB, 0, s>>>(n, d_tris, d_which, d_leafbox, d_box, d_red);
-        GT(hipMemcpyAsync(&h, d_red, sizeof h, hipMemcpyDeviceToHost, s));
-        GT(hipStreamSynchronize(s));
-        GT(hipGetLastError());
+    // units
+    uint32_t *d_which = mem.get<uint32_t>(n);
+    Box6 *d_box = mem.get<Box6>(n_all);
+    Red *d_red = mem.get<Red>(1);
+    float4 *d_leafbox = mem.get<float4>(leafbox.size());
+    if (mem.failed) return false;
+    Red h{};
+    for (int k = 0; k < 3; k++) { h.cmin[k] = h.qmin[k] = 0xFFFFFFFFu; h.cmax[k] = h.qmax[k] = 0u; }
+    if (!hip_ok(hipMemcpyAsync(d_which, which.data(), (size_t)n * 4, hipMemcpyHostToDevice, s)) ||
+        !hip_ok(hipMemcpyAsync(d_leafbox, leafbox.data(), leafbox.size() * sizeof(float4), hipMemcpyHostToDevice, s)) ||
+        !hip_ok(hipMemcpyAsync(d_red, &h, sizeof h, hipMemcpyHostToDevice, s))) return false;
+    k_units<<<blocks(n), TB, 0, s>>>(n, d_tris, d_which, d_leafbox, d_box, d_red);
+    if (!read(&h, d_red, sizeof h) || !settled()) return false;
+    if (h.bad) return false;                                     // a non-finite vertex: the host refuses it too
+    float pad, safe_origin;
+    if (!pt_own_padding((double)pt_bits_float(h.biggest), pad, safe_origin)) return false;
+
+    // Morton keys, sorted
+    float lo[3], inv[3];
+    for (int k = 0; k < 3; k++) { lo[k] = pt_unord_f(h.cmin[k]); inv[k] = pt_inv_extent(lo[k], pt_unord_f(h.cmax[k])); }
+    unsigned long long *d_keys = mem.get<unsigned long long>(n), *d_keys2 = mem.get<unsigned long long>(n);
+    if (mem.failed) return false;
+    k_morton<<<blocks(n), TB, 0, s>>>(n, d_box, make_float3(lo[0], lo[1], lo[2]), make_float3(inv[0], inv[1], inv[2]), d_keys);
+    size_t tmp_bytes = 0;
+    {   // one scratch for the sort, the per-pass scan and the final scan and reductions: the largest of them
+        unsigned long long *u64 = nullptr; uint32_t *u32 = nullptr; double *f64 = nullptr;
+        size_t need[5] = {0, 0, 0, 0, 0};
+        if (!hip_ok(pt_sort_keys_bytes(need[0], n, s)) ||
+            !hip_ok(hipcub::DeviceScan::ExclusiveSum(nullptr, need[1], u64, u64, (int)n + 1, s)) ||
+            !hip_ok(hipcub::DeviceScan::ExclusiveSum(nullptr, need[2], u32, u32, (int)n, s)) ||
+            !hip_ok(hipcub::DeviceReduce::Sum(nullptr, need[3], f64, f64, (int)n, s)) ||
+            !hip_ok(hipcub::DeviceReduce::Sum(nullptr, need[4], u32, u32, (int)n, s))) return false;
+        tmp_bytes = *std::max_element(need, need + 5);
     }
-    if (h.bad) goto done;                                        // a non-finite vertex: the host refuses it too
-    {
-        std::memcpy(&pad, &h.biggest, 4);
-        biggest = (double)pad;
-        pad = std::max((float)std::ldexp(biggest, PT_OWN_PAD_LOG2), FLT_MIN);
-        if (!std::isfinite(pad)) goto done;
-        float lo[3], inv[3];
-        for (int k = 0; k < 3; k++) {
-            lo[k] = unord_f(h.cmin[k]);
-            const float e = unord_f(h.cmax[k]) - lo[k];
-            inv[k] = (e > 0.0f && std::isfinite(1.0f / e)) ? 1.0f / e : 0.0f;
-        }
-        GT(hipMalloc(&d_keys, (size_t)n * 8)); GT(hipMalloc(&d_keys2, (size_t)n * 8));
-        k_morton<<<blocks(n), TB, 0, s>>>(n, d_box, make_float3(lo[0], lo[1], lo[2]), make_float3(inv[0], inv[1], inv[2]), d_keys);
-    }
-    {   // scratch for the sort, the per-pass scan and the final reductions: the largest of them
-        size_t a = 0, b = 0, c = 0, d = 0;
-        GT(hipcub::DeviceRadixSort::SortKeys(nullptr, a, d_keys, d_keys2, (int)n, 0, 62, s));
-        GT(hipcub::DeviceScan::ExclusiveSum(nullptr, b, d_flags, d_ex, (int)n + 1, s));
-        GT(hipcub::DeviceScan::ExclusiveSum(nullptr, c, d_rest_f, d_rest, (int)n, s));
-        GT(hipcub::DeviceReduce::Sum(nullptr, d, d_growth, d_growth_sum, (int)n, s));
-        tmp_bytes = std::max(std::max(a, b), std::max(c, d));
-        size_t d2 = 0;
-        GT(hipcub::DeviceReduce::Sum(nullptr, d2, d_grown, d_grown_sum, (int)n, s));
-        tmp_bytes = std::max(tmp_bytes, d2);
-        GT(hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 16));
-    }
-    GT(hipcub::DeviceRadixSort::SortKeys(d_tmp, tmp_bytes, d_keys, d_keys2, (int)n, 0, 62, s));
-    GT(hipMalloc(&d_clu[0], (size_t)n * 4)); GT(hipMalloc(&d_clu[1], (size_t)n * 4)); GT(hipMalloc(&d_nn, (size_t)n * 4));
-    GT(hipMalloc(&d_flags, (size_t)(n + 1) * 8)); GT(hipMalloc(&d_ex, (size_t)(n + 1) * 8));
-    GT(hipMalloc(&d_child, (size_t)(n - 1) * sizeof(uint2))); GT(hipMalloc(&d_parent, (size_t)n_all * 4));
-    GT(hipMemsetAsync(d_parent, 0xFF, (size_t)n_all * 4, s));
-    GT(hipMalloc(&d_level, (size_t)(n - 1)));
-    k_first_clusters<<<blocks(n), TB, 0, s>>>(n, d_keys2, d_clu[0]);
+    void *d_tmp = mem.get<char>(tmp_bytes ? tmp_bytes : 16);
+    if (!d_tmp || !hip_ok(pt_sort_keys(d_tmp, tmp_bytes, d_keys, d_keys2, n, s))) return false;
+
     // PLOC passes: each merges at least the globally closest pair. Collapsing takes at most max_leaf - 1 levels off a path, so a cluster
     // deeper than depth_limit + max_leaf - 1 levels can never give a tree within the limit: the build is refused as soon as one appears
     // (nested triangles along a line merge one pair per pass into a chain), before the passes and the emit walk grow with the depth.
     // The number of passes is capped as well (measured: 39 for 3 876 triangles, 62 for a million).
+    uint32_t *d_clu[2] = {mem.get<uint32_t>(n), mem.get<uint32_t>(n)}, *d_nn = mem.get<uint32_t>(n);
+    unsigned long long *d_flags = mem.get<unsigned long long>((size_t)n + 1), *d_ex = mem.get<unsigned long long>((size_t)n + 1);
+    uint2 *d_child = mem.get<uint2>(n - 1);
+    uint32_t *d_parent = mem.get<uint32_t>(n_all);
+    uint8_t *d_level = mem.get<uint8_t>(n - 1);
+    if (mem.failed || !hip_ok(hipMemsetAsync(d_parent, 0xFF, (size_t)n_all * 4, s))) return false;
+    k_first_clusters<<<blocks(n), TB, 0, s>>>(n, d_keys2, d_clu[0]);
+    uint32_t m = n, next = n;
     for (int cur = 0, pass = 0; m > 1; cur ^= 1, pass++) {
-        if (pass >= kMaxPasses) goto done;
+        if (pass >= kMaxPasses) return false;
         k_nearest<<<blocks(m), TB, 0, s>>>(m, d_clu[cur], d_box, d_nn);
         k_mark<<<blocks(m + 1), TB, 0, s>>>(m, d_nn, d_flags);
-        GT(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_flags, d_ex, (int)m + 1, s));
+        if (!hip_ok(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_flags, d_ex, (int)m + 1, s))) return false;
         k_merge<<<blocks(m), TB, 0, s>>>(m, n, next, d_clu[cur], d_nn, d_flags, d_ex, d_box, d_child, d_parent, d_level, d_clu[cur ^ 1],
                                          d_red);
         unsigned long long tot = 0;
         uint32_t deepest = 0;
-        GT(hipMemcpyAsync(&tot, d_ex + m, 8, hipMemcpyDeviceToHost, s));
-        GT(hipMemcpyAsync(&deepest, &d_red->ploc_depth, 4, hipMemcpyDeviceToHost, s));
-        GT(hipStreamSynchronize(s));
+        if (!read(&tot, d_ex + m, 8) || !read(&deepest, &d_red->ploc_depth, 4) || !hip_ok(hipStreamSynchronize(s))) return false;
         const uint32_t made = (uint32_t)(tot >> 32), left = (uint32_t)tot;
-        if (made == 0 || left + made != m) goto done;            // cannot happen (see the top); refuse rather than loop
-        if (deepest > depth_limit + max_leaf - 1u) goto done;   // too deep for any collapse: the host builds
+        if (made == 0 || left + made != m) return false;          // cannot happen (see the top); refuse rather than loop
+        if (deepest > depth_limit + max_leaf - 1u) return false; // too deep for any collapse: the host builds
         next += made; m = left;
     }
-    GT(hipGetLastError());
-    root = next - 1;
-    if (root != n_all - 1) goto done;
+    if (!hip_ok(hipGetLastError())) return false;
+    const uint32_t root = next - 1;
+    if (root != n_all - 1) return false;
+
     // collapse
-    GT(hipMalloc(&d_arr, (size_t)(n - 1) * 4)); GT(hipMalloc(&d_cnt, (size_t)n_all * 4)); GT(hipMalloc(&d_icnt, (size_t)n_all * 4));
-    GT(hipMalloc(&d_leafy, (size_t)n_all * 4)); GT(hipMalloc(&d_cost, (size_t)n_all * 8)); GT(hipMalloc(&d_step, (size_t)n_all * sizeof(Step)));
-    GT(hipMemsetAsync(d_arr, 0, (size_t)(n - 1) * 4, s));
+    uint32_t *d_arr = mem.get<uint32_t>(n - 1), *d_cnt = mem.get<uint32_t>(n_all), *d_icnt = mem.get<uint32_t>(n_all);
+    uint32_t *d_leafy = mem.get<uint32_t>(n_all);
+    double *d_cost = mem.get<double>(n_all);
+    Step *d_step = mem.get<Step>(n_all);
+    if (mem.failed || !hip_ok(hipMemsetAsync(d_arr, 0, (size_t)(n - 1) * 4, s))) return false;
     k_collapse<<<blocks(n), TB, 0, s>>>(n, max_leaf, PT_OWN_C_BOX, PT_OWN_C_TRI, PT_OWN_C_OPEN, d_box, d_child, d_parent, d_arr,
                                         d_cnt, d_icnt, d_cost, d_leafy, d_step);
-    {
-        uint32_t rl = 0;
-        GT(hipMemcpyAsync(&n_inner, d_icnt + root, 4, hipMemcpyDeviceToHost, s));
-        GT(hipMemcpyAsync(&rl, d_leafy + root, 4, hipMemcpyDeviceToHost, s));
-        GT(hipStreamSynchronize(s));
-        GT(hipGetLastError());
-        if (rl || n_inner == 0) goto done;                       // a single leaf (never above 32 triangles): the host's case
-    }
-    dfree(d_clu[0]); dfree(d_clu[1]); dfree(d_nn); dfree(d_flags); dfree(d_ex); dfree(d_arr); dfree(d_cost);
+    uint32_t n_inner = 0, root_leafy = 0;
+    if (!read(&n_inner, d_icnt + root, 4) || !read(&root_leafy, d_leafy + root, 4) || !settled()) return false;
+    if (root_leafy || n_inner == 0) return false;                // a single leaf (never above 32 triangles): the host's case
+    mem.drop(d_clu[0], d_clu[1], d_nn, d_flags, d_ex, d_arr, d_cost);
+
     // emit
-    GT(hipMalloc(&d_wn, (size_t)n_inner * 64)); GT(hipMalloc(&d_tp, (size_t)n * 48));
+    float4 *d_wn = mem.get<float4>(4 * (size_t)n_inner), *d_tp = mem.get<float4>(3 * (size_t)n);
+    if (mem.failed) return false;
     k_emit<<<blocks(n_all), TB, 0, s>>>(n_all, n, root, pad, d_tris, d_which, d_box, d_child, d_cnt, d_icnt, d_leafy, d_step, d_wn, d_tp, d_red);
-    {
-        Box6 rb;
-        GT(hipMemcpyAsync(&rb, d_box + root, sizeof rb, hipMemcpyDeviceToHost, s));
-        GT(hipMemcpyAsync(&h, d_red, sizeof h, hipMemcpyDeviceToHost, s));
-        GT(hipStreamSynchronize(s));
-        GT(hipGetLastError());
-        if (h.depth > depth_limit) goto done;
-        // padding and the root box exactly as the host derives them (fast_tree.hip pt_build_own_tree): they depend on the triangle set only
-        auto lower_h = [&](float x) { const float y = x - pad; return y < x ? y : std::nextafterf(x, -INFINITY); };
-        auto upper_h = [&](float x) { const float y = x + pad; return y > x ? y : std::nextafterf(x, INFINITY); };
-        for (int k = 0; k < 3; k++) {
-            out.root_min[k] = lower_h(rb.mn[k]); out.root_max[k] = upper_h(rb.mx[k]);
-            if (!std::isfinite(out.root_min[k]) || !std::isfinite(out.root_max[k])) goto done;
-        }
+    Box6 rb;
+    if (!read(&rb, d_box + root, sizeof rb) || !read(&h, d_red, sizeof h) || !settled()) return false;
+    if (h.depth > depth_limit) return false;
+    rb = pt_pad_box(rb, pad);                                    // the root box depends on the triangle set only: the host's, bit for bit
+    for (int k = 0; k < 3; k++) {
+        out.root_min[k] = rb.mn[k]; out.root_max[k] = rb.mx[k];
+        if (!std::isfinite(rb.mn[k]) || !std::isfinite(rb.mx[k])) return false;
     }
-    out.pad = pad;
-    out.safe_origin = (float)std::min(8.0 * biggest, 3.0e38);
+    out.pad = pad; out.safe_origin = safe_origin;
     out.root_ref = 0u; out.depth = h.depth; out.n_wnodes = n_inner; out.n_tris = n;
     out.n_leaves = n_inner + 1u; out.max_leaf_tris = h.max_leaf;
-    dfree(d_step); dfree(d_child); dfree(d_box); dfree(d_parent); dfree(d_cnt); dfree(d_icnt); dfree(d_leafy);
+    mem.drop(d_step, d_child, d_box, d_parent, d_cnt, d_icnt, d_leafy);
+
     // quantised nodes (none when the 16-bit grid is too coarse for the scene, as on the host)
     out.quantised = false;
-    {
-        float mn[3], mx[3];
-        for (int k = 0; k < 3; k++) { mn[k] = unord_f(h.qmin[k]); mx[k] = unord_f(h.qmax[k]); }
-        PtQuantGrid g;
-        if (pt_quant_grid(mn, mx, g.origin, g.scale)) {
-            GT(hipMalloc(&d_qn, (size_t)n_inner * 32)); GT(hipMalloc(&d_renum, (size_t)n_inner * 4));
-            GT(hipMalloc(&d_rest_f, (size_t)n_inner * 4)); GT(hipMalloc(&d_rest, (size_t)n_inner * 4));
-            GT(hipMalloc(&d_growth, (size_t)n_inner * 8)); GT(hipMalloc(&d_grown, (size_t)n_inner * 4));
-            GT(hipMalloc(&d_growth_sum, 8)); GT(hipMalloc(&d_grown_sum, 4));
-            GT(hipMemsetAsync(d_renum, 0xFF, (size_t)n_inner * 4, s));
-            k_top<<<1, 1, 0, s>>>(d_wn, std::min<uint32_t>(PT_QCACHE_NODES, n_inner), d_renum, d_red);
-            k_rest_flags<<<blocks(n_inner), TB, 0, s>>>(n_inner, d_renum, d_rest_f);
-            GT(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_rest_f, d_rest, (int)n_inner, s));
-            k_quantise<<<blocks(n_inner), TB, 0, s>>>(n_inner, g, d_wn, d_renum, d_rest, d_red, d_qn, d_growth, d_grown);
-            GT(hipcub::DeviceReduce::Sum(d_tmp, tmp_bytes, d_growth, d_growth_sum, (int)n_inner, s));
-            GT(hipcub::DeviceReduce::Sum(d_tmp, tmp_bytes, d_grown, d_grown_sum, (int)n_inner, s));
-            double growth = 0.0; uint32_t grown = 0;
-            GT(hipMemcpyAsync(&growth, d_growth_sum, 8, hipMemcpyDeviceToHost, s));
-            GT(hipMemcpyAsync(&grown, d_grown_sum, 4, hipMemcpyDeviceToHost, s));
-            GT(hipMemcpyAsync(&h, d_red, sizeof h, hipMemcpyDeviceToHost, s));
-            GT(hipStreamSynchronize(s));
-            GT(hipGetLastError());
-            if (!(grown && growth / (double)grown > 0.25)) {
-                out.quantised = true; out.q_top = h.n_top;
-                for (int k = 0; k < 3; k++) { out.q_origin[k] = g.origin[k]; out.q_scale[k] = g.scale[k]; }
-            }
+    uint4 *d_qn = nullptr;
+    float mn[3], mx[3];
+    for (int k = 0; k < 3; k++) { mn[k] = pt_unord_f(h.qmin[k]); mx[k] = pt_unord_f(h.qmax[k]); }
+    PtQuantGrid g;
+    if (pt_quant_grid(mn, mx, g.origin, g.scale)) {
+        d_qn = mem.get<uint4>(2 * (size_t)n_inner);
+        uint32_t *d_renum = mem.get<uint32_t>(n_inner), *d_rest_f = mem.get<uint32_t>(n_inner), *d_rest = mem.get<uint32_t>(n_inner);
+        double *d_growth = mem.get<double>(n_inner);
+        uint32_t *d_grown = mem.get<uint32_t>(n_inner);
+        double *d_growth_sum = mem.get<double>(1);
+        uint32_t *d_grown_sum = mem.get<uint32_t>(1);
+        if (mem.failed || !hip_ok(hipMemsetAsync(d_renum, 0xFF, (size_t)n_inner * 4, s))) return false;
+        k_top<<<1, 1, 0, s>>>(d_wn, std::min<uint32_t>(PT_QCACHE_NODES, n_inner), d_renum, d_red);
+        k_rest_flags<<<blocks(n_inner), TB, 0, s>>>(n_inner, d_renum, d_rest_f);
+        if (!hip_ok(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_rest_f, d_rest, (int)n_inner, s))) return false;
+        k_quantise<<<blocks(n_inner), TB, 0, s>>>(n_inner, g, d_wn, d_renum, d_rest, d_red, d_qn, d_growth, d_grown);
+        if (!hip_ok(hipcub::DeviceReduce::Sum(d_tmp, tmp_bytes, d_growth, d_growth_sum, (int)n_inner, s)) ||
+            !hip_ok(hipcub::DeviceReduce::Sum(d_tmp, tmp_bytes, d_grown, d_grown_sum, (int)n_inner, s))) return false;
+        double growth = 0.0; uint32_t grown = 0;
+        if (!read(&growth, d_growth_sum, 8) || !read(&grown, d_grown_sum, 4) || !read(&h, d_red, sizeof h) || !settled()) return false;
+        if (!(grown && growth / (double)grown > 0.25)) {
+            out.quantised = true; out.q_top = h.n_top;
+            for (int k = 0; k < 3; k++) { out.q_origin[k] = g.origin[k]; out.q_scale[k] = g.scale[k]; }
         }
     }
-    if (!out.quantised) dfree(d_qn);
-    out.wnodes = d_wn; out.tripos = d_tp; out.qnodes = d_qn;
-    d_wn = nullptr; d_tp = nullptr; d_qn = nullptr;
-    ok = true;
-done:
-    (void)hipStreamSynchronize(s);                               // nothing of ours may still run when the scratch goes
-    dfree(d_which); dfree(d_leafbox); dfree(d_clu[0]); dfree(d_clu[1]); dfree(d_nn); dfree(d_parent); dfree(d_arr); dfree(d_cnt); dfree(d_icnt);
-    dfree(d_leafy); dfree(d_renum); dfree(d_rest_f); dfree(d_rest); dfree(d_grown); dfree(d_grown_sum); dfree(d_cost);
-    dfree(d_growth); dfree(d_growth_sum); dfree(d_keys); dfree(d_keys2); dfree(d_flags); dfree(d_ex); dfree(d_box); dfree(d_child);
-    dfree(d_step); dfree(d_red); dfree(d_level); dfree(d_wn); dfree(d_tp); dfree(d_qn); dfree(d_tmp);
+    if (!out.quantised) { mem.drop(d_qn); d_qn = nullptr; }
+    out.wnodes = mem.keep(d_wn); out.tripos = mem.keep(d_tp); out.qnodes = mem.keep(d_qn);
+    return true;
+}
+
+}  // namespace
+
+bool pt_build_own_tree_gpu(const ptmi_triangle *d_tris, const std::vector<uint32_t> &which, const std::vector<float4> &leafbox,
+                           uint32_t max_leaf, uint32_t depth_limit, hipStream_t s, PtOwnTreeGpu &out) {
+    out.release();
+    bool ok;
+    {
+        DevScratch mem;
+        ok = build_own_tree(d_tris, which, leafbox, max_leaf, depth_limit, s, mem, out);
+        (void)hipStreamSynchronize(s);                           // nothing of ours may still run when the scratch goes
+    }
     if (!ok) { (void)hipGetLastError(); out.release(); }
     return ok;
 }
 
 void PtOwnTreeGpu::release() {
-    dfree(wnodes); dfree(tripos); dfree(qnodes);
+    (void)hipFree(wnodes); (void)hipFree(tripos); (void)hipFree(qnodes);
     *this = PtOwnTreeGpu();
 }

@@ -12,20 +12,18 @@
 //   uploaded  per height, one launch: a leaf child's box = min / max over its triangles' vertices, an inner child's = the union of that
 //             node's two stored boxes, written one launch earlier; a leaf child also writes its box to its triangles' rows of the leaf-box
 //             table. The hierarchy over the reference's leaves (leaves = 1) is refitted by the same kernel: its leaves are the same ranges.
-//   own       unit boxes as own_tree_gpu.hip k_units / fast_tree.hip compute them (slivers re-decided, grown by the NEW leaf box), the
+//   own       unit boxes as the builders compute them (pt_box.h pt_unit_box: slivers re-decided, grown by the NEW leaf box), the
 //             triangle images in leaf order, |coordinate| max-reduced for the padding; then per height: exact child boxes (kept
-//             unpadded in scratch for the parents), stored padded with the builders' lower / upper; the padded bounds min / max-reduced
+//             unpadded in scratch for the parents), stored padded with the builders' pt_pad_box; the padded bounds min / max-reduced
 //             for the 16-bit grid (quantise.hip pt_quant_grid), every child through wide_node.h pt_quantise_child, references kept
 //   cost      the surface areas of all stored child boxes, summed in a fixed order (per-thread strided sums, a tree per block, the
 //             blocks' partial sums added on the host in block order): the same update leaves the same number on every run
 // Every kernel of one launch reads only what earlier launches wrote: no hand-off inside a launch, nothing depends on dispatch order.
 // Minima and maxima are exact, so the results do not depend on the order of the unions either (which of -0 / +0 a tie returns is open).
 #include "ptmi_ctx.h"
-#include "fast_tree.h"
-#include "wide_node.h"
+#include "pt_box.h"
 
 #include <algorithm>
-#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -34,28 +32,6 @@ namespace {
 
 constexpr int TB = 256;
 constexpr int kCostBlocks = 256;         // partial sums of the cost (one double each)
-
-struct Box6 { float mn[3], mx[3]; };
-
-// std::min / std::max exactly (the builders' Box::grow): the first argument unless the second is strictly smaller / larger
-__host__ __device__ inline float mn_(float a, float b) { return b < a ? b : a; }
-__host__ __device__ inline float mx_(float a, float b) { return a < b ? b : a; }
-__host__ __device__ inline Box6 unite(const Box6 &a, const Box6 &b) {
-    Box6 u;
-    for (int k = 0; k < 3; k++) { u.mn[k] = mn_(a.mn[k], b.mn[k]); u.mx[k] = mx_(a.mx[k], b.mx[k]); }
-    return u;
-}
-__host__ __device__ inline Box6 child_box(const float4 *w, int side) {
-    const PtWideChild c = pt_wide_child(w, side);
-    return {{c.lo[0], c.lo[1], c.lo[2]}, {c.hi[0], c.hi[1], c.hi[2]}};
-}
-// the builders' padding (fast_tree.hip pt_build_own_tree, own_tree_gpu.hip)
-__host__ __device__ inline float lower(float x, float pad) { const float y = x - pad; return y < x ? y : nextafterf(x, -INFINITY); }
-__host__ __device__ inline float upper(float x, float pad) { const float y = x + pad; return y > x ? y : nextafterf(x, INFINITY); }
-
-// order-preserving float <-> uint (min / max reductions with integer atomics)
-__device__ __forceinline__ uint32_t ord(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-float unord_f(uint32_t u) { u = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u; float f; std::memcpy(&f, &u, 4); return f; }
 
 // The reduction words of one update, preset before it. Every thread of a wave takes part in the wave_* steps (no early return before them).
 struct Words {
@@ -126,13 +102,12 @@ __global__ void k_light_tris(uint32_t nl, const ptmi_light *__restrict__ lights,
 }
 
 __device__ __forceinline__ Box6 range_box(const ptmi_triangle *__restrict__ tris, uint32_t first, uint32_t cnt) {
-    Box6 b;
-    for (int k = 0; k < 3; k++) { b.mn[k] = INFINITY; b.mx[k] = -INFINITY; }
+    Box6 b = pt_empty_box();
     for (uint32_t t = first; t < first + cnt; t++) {
         const ptmi_triangle &tr = tris[t];
         for (int k = 0; k < 3; k++) {
-            b.mn[k] = mn_(mn_(mn_(b.mn[k], tr.v0[k]), tr.v1[k]), tr.v2[k]);
-            b.mx[k] = mx_(mx_(mx_(b.mx[k], tr.v0[k]), tr.v1[k]), tr.v2[k]);
+            b.mn[k] = pt_min(pt_min(pt_min(b.mn[k], tr.v0[k]), tr.v1[k]), tr.v2[k]);
+            b.mx[k] = pt_max(pt_max(pt_max(b.mx[k], tr.v0[k]), tr.v1[k]), tr.v2[k]);
         }
     }
     return b;
@@ -164,7 +139,7 @@ __global__ void __launch_bounds__(TB) k_refit_ranges(uint32_t m, const uint32_t 
         } else {
             if (ref >= n_nodes) continue;
             const float4 *c = w + 4 * (size_t)ref;                  // (a lower height: written by an earlier launch)
-            b = unite(child_box(c, 0), child_box(c, 1));
+            b = pt_unite(pt_child_box(c, 0), pt_child_box(c, 1));
         }
         pt_wide_set_box(me, side, b.mn, b.mx);
         if (w16) pt_wide_set_box(w16 + 4 * (size_t)i, side, b.mn, b.mx);
@@ -192,22 +167,10 @@ __global__ void __launch_bounds__(TB) k_units(uint32_t n, uint32_t n_tris, const
     const uint32_t orig = p < n ? __float_as_uint(tp[3 * (size_t)p].w) : PT_REF_NONE;
     if (orig < n_tris) {
         const ptmi_triangle &t = tris[orig];
-        Box6 u;
-        for (int k = 0; k < 3; k++) {
-            const float a = t.v0[k], b = t.v1[k], c = t.v2[k];
-            const float b2 = a + (b - a), c2 = a + (c - a);
-            u.mn[k] = mn_(mn_(mn_(a, b), mn_(c, b2)), c2);
-            u.mx[k] = mx_(mx_(mx_(a, b), mx_(c, b2)), c2);
-        }
-        if (pt_own_sliver(t.v0, t.v1, t.v2)) {                       // a sliver's box grows by its reference leaf's (fast_tree.h)
-            const float4 l = leafbox[2 * (size_t)orig], h = leafbox[2 * (size_t)orig + 1];
-            const float lb[3] = {l.x, l.y, l.z}, hb[3] = {h.x, h.y, h.z};
-            for (int k = 0; k < 3; k++) { u.mn[k] = mn_(u.mn[k], lb[k]); u.mx[k] = mx_(u.mx[k], hb[k]); }
-        }
-        for (int k = 0; k < 3; k++) {
-            big = max(big, max(__float_as_uint(fabsf(u.mn[k])), __float_as_uint(fabsf(u.mx[k]))));
-            lo[k] = ord(u.mn[k]); hi[k] = ord(u.mx[k]);
-        }
+        const PtUnitBox ub = pt_unit_box(t.v0, t.v1, t.v2, [&] { return pt_leafbox_row(leafbox, orig); });   // (the NEW leaf box)
+        const Box6 &u = ub.box;
+        big = ub.biggest;
+        for (int k = 0; k < 3; k++) { lo[k] = pt_ord(u.mn[k]); hi[k] = pt_ord(u.mx[k]); }
         unit[p] = u;
         tp[3 * (size_t)p + 0] = make_float4(t.v0[0], t.v0[1], t.v0[2], __uint_as_float(orig));
         tp[3 * (size_t)p + 1] = make_float4(t.v1[0] - t.v0[0], t.v1[1] - t.v0[1], t.v1[2] - t.v0[2], 0.0f);
@@ -236,16 +199,16 @@ __global__ void __launch_bounds__(TB) k_refit_own(uint32_t m, const uint32_t *__
                 const uint32_t first = leaf_first(ref), cnt = leaf_count(ref);
                 if ((uint64_t)first + cnt > n_units) continue;
                 b = unit[first];
-                for (uint32_t t = first + 1; t < first + cnt; t++) b = unite(b, unit[t]);
+                for (uint32_t t = first + 1; t < first + cnt; t++) b = pt_unite(b, unit[t]);
             } else {
                 if (ref >= n_nodes) continue;
-                b = unite(exact[2 * (size_t)ref], exact[2 * (size_t)ref + 1]);     // (a lower height: an earlier launch)
+                b = pt_unite(exact[2 * (size_t)ref], exact[2 * (size_t)ref + 1]);     // (a lower height: an earlier launch)
             }
             exact[2 * (size_t)i + side] = b;
             Box6 p;
             for (int a = 0; a < 3; a++) {
-                p.mn[a] = lower(b.mn[a], pad); p.mx[a] = upper(b.mx[a], pad);
-                lo[a] = min(lo[a], ord(p.mn[a])); hi[a] = max(hi[a], ord(p.mx[a]));
+                p.mn[a] = pt_pad_lower(b.mn[a], pad); p.mx[a] = pt_pad_upper(b.mx[a], pad);
+                lo[a] = min(lo[a], pt_ord(p.mn[a])); hi[a] = max(hi[a], pt_ord(p.mx[a]));
             }
             pt_wide_set_box(me, side, p.mn, p.mx);
             if (w16) pt_wide_set_box(w16 + 4 * (size_t)i, side, p.mn, p.mx);
@@ -500,13 +463,12 @@ int ptmi_update_triangles(ptmi_ctx *c, uint32_t first, uint32_t count, const ptm
         Words h;
         HIP_TRY(c, hipMemcpyAsync(&h, red, offsetof(Words, cost), hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipStreamSynchronize(st));
-        float biggest_f; std::memcpy(&biggest_f, &h.biggest, 4);
-        const double biggest = (double)biggest_f;
-        const float pad = std::max((float)std::ldexp(biggest, PT_OWN_PAD_LOG2), FLT_MIN);
-        img.pad = pad; img.safe_origin = next.safe_origin = (float)std::min(8.0 * biggest, 3.0e38);
+        float pad;
+        (void)pt_own_padding((double)pt_bits_float(h.biggest), pad, img.safe_origin);     // (finite: every vertex was checked above)
+        img.pad = pad; next.safe_origin = img.safe_origin;
         for (int k = 0; k < 3; k++) {
-            img.root_min[k] = next.root_min[k] = lower(unord_f(h.umin[k]), pad);
-            img.root_max[k] = next.root_max[k] = upper(unord_f(h.umax[k]), pad);
+            img.root_min[k] = next.root_min[k] = pt_pad_lower(pt_unord_f(h.umin[k]), pad);
+            img.root_max[k] = next.root_max[k] = pt_pad_upper(pt_unord_f(h.umax[k]), pad);
         }
         if (nw) {
             float4 *w = static_cast<float4 *>(d[kWnodes]), *w16 = static_cast<float4 *>(d[kWnodes16]);
@@ -520,7 +482,7 @@ int ptmi_update_triangles(ptmi_ctx *c, uint32_t first, uint32_t count, const ptm
                 HIP_TRY(c, hipMemcpyAsync(&h, red, offsetof(Words, cost), hipMemcpyDeviceToHost, st));
                 HIP_TRY(c, hipStreamSynchronize(st));
                 float mn[3], mx[3];
-                for (int k = 0; k < 3; k++) { mn[k] = unord_f(h.qmin[k]); mx[k] = unord_f(h.qmax[k]); }
+                for (int k = 0; k < 3; k++) { mn[k] = pt_unord_f(h.qmin[k]); mx[k] = pt_unord_f(h.qmax[k]); }
                 PtQuantGrid g;
                 if (pt_quant_grid(mn, mx, g.origin, g.scale)) {
                     k_requantise<<<blocks(nw), TB, 0, st>>>(nw, g, w, buf_as<uint32_t>(c, kPlanQnum), static_cast<uint4 *>(d[kQnodes]),
@@ -541,7 +503,7 @@ int ptmi_update_triangles(ptmi_ctx *c, uint32_t first, uint32_t count, const ptm
     HIP_TRY(c, hipMemcpyAsync(&h, red, offsetof(Words, cost), hipMemcpyDeviceToHost, st));
     if (c->n_ref_wnodes) HIP_TRY(c, hipMemcpyAsync(root, static_cast<float4 *>(d[kRefWnodes]) + 4 * (size_t)c->sc.ref_root_ref, sizeof root, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
-    const Box6 rb = c->n_ref_wnodes ? unite(child_box(root, 0), child_box(root, 1)) : h.leaf;
+    const Box6 rb = c->n_ref_wnodes ? pt_unite(pt_child_box(root, 0), pt_child_box(root, 1)) : h.leaf;
     for (int k = 0; k < 3; k++) { next.ref_root_min[k] = rb.mn[k]; next.ref_root_max[k] = rb.mx[k]; }
     if (!own)
         for (int k = 0; k < 3; k++) { img.root_min[k] = next.root_min[k] = rb.mn[k]; img.root_max[k] = next.root_max[k] = rb.mx[k]; }
