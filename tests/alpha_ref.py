@@ -6,12 +6,18 @@ The constants of the step: eps = max(PT_EPS, 2^-18 * max(|p.x|, |p.y|, |p.z|)) w
 fma(d, eps, p); the distance travelled grows by step = t + eps (travelled' = travelled + step). The distance a ray that passed holes
 reports for its last hit is the triangle test's t of that triangle from the ray's FIRST origin (what an unobstructed ray would report),
 and travelled + t of the last leg only where that test rejects the hit.
+
+Below the loops: the ghost scene (every hole triangle collapsed to a point, nothing else moved), the replay of the loops on every ray of
+the oracle's render of it, and the case table tests/test_alpha_replay_host.py and tests/test_gpu_alpha_per_sample.py share.
 """
+import dataclasses
+import types
+
 import numpy as np
 
 import texture_ref
-from ptmi import scenes
-from scene_update_ref import fmaf
+from ptmi import layout, scenes
+from scene_update_ref import fmaf, refit_nodes
 
 F = np.float32
 PT_EPS = F(1e-6)
@@ -203,3 +209,172 @@ def occluded(intersect, scene, cutoff, o, d, dist, max_layers=DEFAULT_LAYERS):
         travelled[nxt] = travelled[nxt] + st
         idx = nxt
     return occ, layers
+
+
+# ---- the ghost scene: a hole is an absent triangle, sample for sample ----------------------------------------------
+def ghost(scene, cutoff, at="v0"):
+    """(the ghost of `scene` under the table `cutoff`, the hole mask over its triangles): a copy with the same triangle order, nodes,
+    materials, lights and atlas in which every triangle whose albedo texel is below its material's cutoff is collapsed to the point
+    `at` (one of its own corners), so the triangle test rejects it (|a| < PT_EPS) while the old boxes still enclose it; light order and
+    triangle ids do not move. Asserts that every triangle of a cutout material reads one texel: the same verdict at its three corners
+    and at its centroid."""
+    cutoff = np.asarray(cutoff, F)
+    mi = scene.tris["material_index"].astype(np.int64)
+    cut = np.flatnonzero((mi < len(cutoff)) & (cutoff[np.minimum(mi, len(cutoff) - 1)] > 0))
+    third = F(1.0 / 3.0)
+    verdicts = [is_hole(scene, cutoff, cut, np.full(len(cut), u, F), np.full(len(cut), v, F))
+                for u, v in ((0, 0), (1, 0), (0, 1), (third, third))]
+    for k in verdicts[1:]:
+        assert np.array_equal(k, verdicts[0]), "a triangle of a cutout material reads more than one texel"
+    hole = np.zeros(len(scene.tris), bool)
+    hole[cut] = verdicts[0]
+    tris = scene.tris.copy()
+    point = scene.tris[at][hole].copy()
+    for k in ("v0", "v1", "v2"):
+        tris[k][hole] = point
+    return dataclasses.replace(scene, tris=tris), hole
+
+
+def replay(oracle, cut, cutoff, ghost, cam, frames, rows, max_bounces, do_mis, max_layers=DEFAULT_LAYERS):
+    """The model's two loops, over the oracle's closest-hit probe on the cutout scene `cut`, replayed on every ray the oracle's render
+    of the ghost scene traces (rows = (y0, y1); Oracle.render_tap in tracing order). A closest-hit ray disagrees when the bits of t or the
+    triangle differ from what the tap recorded for the ghost scene (two misses agree), a shadow ray when the verdict does. No kernel has
+    a part in any of it. Returns a namespace:
+      n_rays, n_closest, n_shadow       the rays replayed
+      disagreeing_closest / _shadow     how many disagree
+      path_passes, shadow_passes        holes passed: the sum of `layers` over the closest-hit / the shadow rays
+      through_holes                     rays that passed at least one hole
+      exhausted                         rays still on a hole after max_layers
+      shadow_lit                        shadow rays whose sample lies on the lit side of its surface, cos > 0: the ones `shade` leaves a
+                                        record for (a sample with ndl = 0 has contribution zero and is counted, not traced)
+      shadow_passes_lit                 the holes those passed: what ptmi_alpha_status.shadow_passes counts
+      shadow_grazing                    shadow rays with |cos| < 1e-5, whose side float64 and the kernels' float32 may see differently"""
+    y0, y1 = rows
+    W, H = int(cam["width"]), int(cam["height"])
+    n_paths = ((y1 or H) - y0) * W * frames
+    rec = oracle.render_tap(ghost, cam, frames, y0, y1, max(n_paths * (2 * max_bounces + 1), 1), max_bounces, do_mis, threads=1)
+    o, d, dist = rec[:, 0:3], rec[:, 3:6], rec[:, 6]
+    want_t, want_tri = rec[:, 7], np.ascontiguousarray(rec[:, 8]).view(np.uint32)
+    probe = lambda oo, dd: oracle.intersect(cut, oo, dd)[:4]
+    c, s = np.flatnonzero(dist == 0), np.flatnonzero(dist != 0)
+    t, tri, layers = resolve(probe, cut, cutoff, o[c], d[c], max_layers)
+    both_miss = (t < 0) & (want_t[c] < 0)
+    same = (np.ascontiguousarray(t).view(np.uint32) == np.ascontiguousarray(want_t[c]).view(np.uint32)) & (tri == want_tri[c])
+    occ, slayers = occluded(probe, cut, cutoff, o[s], d[s], dist[s], max_layers)
+    wt, ds = want_t[s], dist[s]
+    with np.errstate(invalid="ignore"):
+        want_occ = np.where(ds < 0, wt > 0, (wt > 0) & (wt < (ds - PT_EPS * F(2)).astype(F)))
+    # the side of its surface a light sample lies on: the shadow ray stands right behind the ray whose hit it starts from
+    cos = np.zeros(len(s))
+    if len(s):
+        assert s[0] > 0 and np.all(dist[s - 1] == 0) and np.all(want_t[s - 1] > 0)
+        pt, ptri, pu, pv = oracle.intersect(ghost, o[s - 1], d[s - 1])[:4]
+        assert np.array_equal(ptri, want_tri[s - 1])
+        T = ghost.tris[ptri.astype(np.int64)]
+        u, v = pu.astype(np.float64)[:, None], pv.astype(np.float64)[:, None]
+        w = (F(1) - pu - pv).astype(np.float64)[:, None]
+        n = T["n0"][:, :3] * w + T["n1"][:, :3] * u + T["n2"][:, :3] * v
+        n /= np.linalg.norm(n, axis=1, keepdims=True)
+        cos = (n * d[s].astype(np.float64)).sum(axis=1)
+    lit = cos > 0
+    return types.SimpleNamespace(
+        n_rays=len(rec), n_closest=len(c), n_shadow=len(s),
+        disagreeing_closest=int((~(same | both_miss)).sum()), disagreeing_shadow=int((occ.astype(bool) != want_occ).sum()),
+        path_passes=int(np.minimum(layers, max_layers).sum()), shadow_passes=int(np.minimum(slayers, max_layers).sum()),
+        through_holes=int((layers > 0).sum() + (slayers > 0).sum()),
+        exhausted=int((layers > max_layers).sum() + (slayers > max_layers).sum()),
+        shadow_lit=int(lit.sum()), shadow_passes_lit=int(np.minimum(slayers, max_layers)[lit].sum()),
+        shadow_grazing=int((np.abs(cos) < 1e-5).sum()))
+
+
+# ---- the cases of the per-sample comparison: tests/test_alpha_replay_host.py (the licence) and tests/test_gpu_alpha_per_sample.py -----
+STRIPES = (np.add.outer(np.arange(8), np.arange(8)) % 3 != 1)[None]        # holes: two cells of every three, in diagonal stripes
+SIZE, FRAMES = (96, 64), 8
+TILE = dict(width=100, height=64, rows=(5, 42))           # 37 rows of 100: the bounce-0 queue ends in a partial wave, whole or frame by frame
+FAR = dict(offset=(200.0, 200.0, 200.0), size=(64, 48), frames=4)
+FENCE_EDIT = dict(dz=-0.07, tilt=0.05)
+
+
+def case_scene(name, offset=(0.0, 0.0, 0.0)):
+    """(the cutout scene, its cutoff table, the number of fences) of the case scenes 'stripes' and 'checker2'"""
+    if name == "stripes":
+        return fence_scene(1.0 - STRIPES, z=(0.4,), offset=offset) + (1,)
+    assert name == "checker2"
+    return fence_scene(checker(2), z=(0.4, 0.3), offset=offset) + (2,)
+
+
+def case_camera(size=SIZE, offset=(0.0, 0.0, 0.0)):
+    return layout.make_camera(size[0], size[1], position=tuple(F((0.0, 1.0, 2.8)) + F(offset)))
+
+
+def edited_fence(scene, offset=(0.0, 0.0, 0.0)):
+    """the edit of the triangle-update tests: (the records of the whole scene with the fences moved by dz, tilted by tilt * x in z (x
+    from the scene's own offset) and u mirrored to 1 - u; the scene a fresh upload gets, those records with the nodes refitted over the
+    same topology)"""
+    moved = scene.tris.copy()
+    fence = np.isin(moved["material_index"], scene.info["fence_materials"])
+    for k in ("v0", "v1", "v2"):
+        v = moved[k][fence]
+        v[:, 2] = v[:, 2] + F(FENCE_EDIT["dz"]) + F(FENCE_EDIT["tilt"]) * (v[:, 0] - F(offset[0]))
+        moved[k][fence] = v
+    for k in ("uv0", "uv1", "uv2"):
+        uv = moved[k][fence]
+        uv[:, 0] = F(1) - uv[:, 0]
+        moved[k][fence] = uv
+    return moved, dataclasses.replace(scene, tris=moved, nodes=refit_nodes(scene.nodes, moved))
+
+
+_FACTORS = (("do_mis", (0, 1)), ("leaves", (1, 2)), ("traversal", (0, 1)), ("overlap", (0, 2)), ("frames_per_batch", (0, 1)),
+            ("planes", (False, True)), ("fence_layers", (False, True)))
+# Five settings of the seven two-valued factors and their complements, one pair per bounce limit: every value of every factor meets
+# every bounce limit, and, the columns of the last four rows being pairwise distinct, every pair of values of two factors occurs
+# (tests/test_alpha_replay_host.py checks both).
+_SETTINGS = ("0000000", "0101010", "0011001", "0110100", "0001111")
+
+
+def per_sample_cases(repack_bounce):
+    """Option sets of the per-sample comparison, the same for every scene: bounce limits 1, at the repack bounce, one and two above it
+    and 8; do_mis; both leaf kinds; both traversal picks; overlap 0 and 2; one frame and many per batch; planes and moments on and
+    off; max_layers at its default and equal to the number of fences (fence_layers); two row ranges of TILE."""
+    cases = []
+    for mb, bits in zip((1, repack_bounce, repack_bounce + 1, repack_bounce + 2, 8), _SETTINGS):
+        for flip in (0, 1):
+            c = dict(max_bounces=mb, tile=False)
+            c.update({k: vals[int(b) ^ flip] for (k, vals), b in zip(_FACTORS, bits)})
+            cases.append(c)
+    cases.append(dict(max_bounces=8, do_mis=1, leaves=2, traversal=0, overlap=2, frames_per_batch=0, planes=False, fence_layers=False, tile=True))
+    cases.append(dict(max_bounces=repack_bounce + 1, do_mis=0, leaves=1, traversal=1, overlap=0, frames_per_batch=1, planes=True,
+                      fence_layers=True, tile=True))
+    return cases
+
+
+def case_view(case, offset=(0.0, 0.0, 0.0)):
+    """(camera, (y0, y1)) of a case"""
+    if case["tile"]:
+        return case_camera((TILE["width"], TILE["height"]), offset), TILE["rows"]
+    return case_camera(SIZE, offset), (0, 0)
+
+
+_far = {}
+
+
+def far_scene():
+    """(cutout scene, cutoff, ghost, camera) of the stripes fence with everything offset by FAR['offset']"""
+    if "scene" not in _far:
+        cut, cutoff, _ = case_scene("stripes", FAR["offset"])
+        _far["scene"] = (cut, cutoff, ghost(cut, cutoff)[0], case_camera(FAR["size"], FAR["offset"]))
+    return _far["scene"]
+
+
+def far_rows_aside(oracle, do_mis, max_bounces=8):
+    """200 units out the triangle test leaks by itself: (the rows of the FAR render that hold a ray on which the replay disagrees, found
+    by tapping one row at a time: (H,) bool; the number of such rays). Computed once per do_mis."""
+    if do_mis not in _far:
+        cut, cutoff, gh, cam = far_scene()
+        bad = np.zeros(FAR["size"][1], np.int64)
+        for y in range(len(bad)):
+            r = replay(oracle, cut, cutoff, gh, cam, FAR["frames"], (y, y + 1), max_bounces, do_mis)
+            assert r.exhausted == 0
+            bad[y] = r.disagreeing_closest + r.disagreeing_shadow
+        _far[do_mis] = (bad > 0, int(bad.sum()))
+    return _far[do_mis]

@@ -149,6 +149,22 @@ class Oracle:
         assert rc == 0
         return out, st
 
+    def render_tap(self, scene, cam, frames, y0=0, y1=0, max_rays=1 << 22, max_bounces=8, do_mis=1, threads=0):
+        """Every ray the render of rows [y0, y1) (y1 = 0: to the last row) x `frames` frames traces, with the reference traversal's
+        result (pto_render_tap): (n, 9) float32 = o, d, dist (0: a closest-hit ray; < 0: a shadow ray to a directional light; > 0: a
+        shadow ray, the light's distance), t (-1: a miss), the triangle's bits. With threads = 1 the records stand in the order they
+        were traced: pixel by pixel, frame by frame, a path's rays one after the other, a shadow ray right behind the ray whose
+        hit it starts from; otherwise in no particular order."""
+        fn = self.L.pto_render_tap
+        fn.restype = ctypes.c_uint64
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
+        rec = np.zeros((max_rays, 9), np.float32)
+        opt = PtoOptions(max_bounces, do_mis, y0, y1, threads)
+        s = self.scene_struct(scene)
+        n = fn(ctypes.byref(s), _ptr(cam), frames, ctypes.byref(opt), _ptr(rec), max_rays)
+        assert n <= max_rays, "the render traced %d rays, more than the %d there was room for" % (n, max_rays)
+        return rec[:n]
+
     def census_events(self):
         """the names of the census events, in table order (oracle/pt_oracle.h PTO_CENSUS_EVENTS)"""
         self.L.pto_census_event_name.restype = ctypes.c_char_p
