@@ -689,7 +689,7 @@ int ptmi_update_materials(ptmi_ctx *ctx, uint32_t first, uint32_t count, const p
 int ptmi_update_lights(ptmi_ctx *ctx, uint32_t first, uint32_t count, const ptmi_light *lights);
 /* A refitted tree degrades as geometry moves. cost = the sum over every child box stored in the walked hierarchy of its surface area,
  * divided by the root box's: cost_built when the plan was made (before the first refit), cost_now after the last update. The host
- * decides from the ratio when to call ptmi_upload_scene again; the library never rebuilds on its own. Before the first update after an
+ * decides from the ratio when to call ptmi_rebuild_tree (below); the library never rebuilds on its own. Before the first update after an
  * upload everything is zero. A struct tag only. */
 struct ptmi_scene_update_status {
     uint32_t updates;         /* ptmi_update_triangles calls since the last upload */
@@ -706,6 +706,43 @@ int ptmi_multi_update_triangles(ptmi_multi *m, uint32_t first, uint32_t count, c
 int ptmi_multi_update_materials(ptmi_multi *m, uint32_t first, uint32_t count, const ptmi_material *materials);
 int ptmi_multi_update_lights(ptmi_multi *m, uint32_t first, uint32_t count, const ptmi_light *lights);
 int ptmi_multi_scene_update_status(ptmi_multi *m, struct ptmi_scene_update_status *out);
+
+/* ---- rebuilding the walked tree in place -------------------------------------------------------
+ * A refit keeps the topology, so the walked hierarchy degrades as geometry moves (ptmi_scene_update_status: cost_now / cost_built).
+ * ptmi_rebuild_tree builds the own-leaf hierarchy (leaves = 2) anew from what is on the device - the current triangles and the leaf
+ * boxes of the refitted uploaded tree - and swaps it in. Afterwards ptmi_debug_read_image returns the walked image a fresh
+ * ptmi_upload_scene of the current triangles, with the uploaded node array refitted as ptmi_update_triangles defines it, would build
+ * under the context's current options with leaves = 2, keep_reference_tree = 0 and tree_builder = params->builder: both builders are
+ * deterministic, so the same bytes (wide nodes, leaf-ordered triangle images, quantised nodes and grid, root box, pad / safe_origin,
+ * depth, n_leaves, max_leaf_tris, and the 16-bit copies of scenes of at most 4 096 triangles). Renders and the per-stage entry points
+ * give that upload's bits. Synchronous; waits for the work in flight as an update does. All-or-nothing: it builds into new buffers and
+ * swaps on success, and a failure leaves the context exactly as it was. Nothing else is touched: the triangle order, the triangles, the
+ * uploaded tree and its images, the leaf boxes, materials, lights, the shade tables, the atlas, the environment, the medium, the alpha
+ * table and its counters, the motion state, the output buffer and every plane. A rebuild without an edit is allowed; with the builder
+ * the upload used it reproduces the image byte for byte. The update plan is re-made for the new topology before the call returns:
+ * ptmi_scene_update_status then reports cost_built = cost_now = the new tree's cost, quantised_kept as the new image has it, plan_ms
+ * of the re-plan, and `updates` unchanged; ptmi_stats.tree_builder_used / leaf_tris_used follow the new image. On the device path
+ * (builder 2, scenes above 4 096 triangles) nothing per triangle crosses the bus; a device build that fails (allocation, more than 60
+ * levels, too many passes) falls back to the host builder as an upload does, and builder_used says 1.
+ * PTMI_E_INVALID: no scene, builder > 2, a non-zero reserved word. PTMI_E_UNSUPPORTED: the loaded image has no own leaves (leaves = 1,
+ * keep_reference_tree, a tree that is not nested, a single leaf, an empty scene; the message says which). ptmi_upload_scene zeroes
+ * the status. */
+typedef struct ptmi_rebuild_params {
+    uint32_t builder;      /* who builds, with ptmi_options.tree_builder's meaning: 1 the host, 2 the device where it applies
+                              (scenes above 4 096 triangles; smaller ones take the host builder); 0 -> 2 */
+    uint32_t reserved[7];  /* must be 0 */
+} ptmi_rebuild_params;     /* 32 bytes */
+struct ptmi_rebuild_status {          /* a struct tag only; 32 bytes */
+    uint32_t rebuilds;                /* since the last upload */
+    uint32_t builder_used;            /* 1 / 2 of the last rebuild (0: none yet) */
+    double   build_ms;                /* wall time of the last ptmi_rebuild_tree */
+    double   cost_before, cost_after; /* the walked hierarchy's cost (ptmi_scene_update_status's definition) around it */
+};
+int ptmi_rebuild_tree(ptmi_ctx *ctx, const ptmi_rebuild_params *params /* NULL: defaults */);
+int ptmi_rebuild_status(ptmi_ctx *ctx, struct ptmi_rebuild_status *out);
+/* on every device, checked once before any device changes; the status of device 0 */
+int ptmi_multi_rebuild_tree(ptmi_multi *m, const ptmi_rebuild_params *params);
+int ptmi_multi_rebuild_status(ptmi_multi *m, struct ptmi_rebuild_status *out);
 
 /* ---- alpha cutouts ---------------------------------------------------------------------------
  * A per-material cutoff table for the loaded scene, one float per uploaded material. cutoff = 0: the material is opaque (the state of

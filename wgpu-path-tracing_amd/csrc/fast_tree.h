@@ -105,6 +105,10 @@ struct PtOwnTreeGpu : PtOwnTreeHeader {
 };
 bool pt_build_own_tree_gpu(const ptmi_triangle *d_tris, const std::vector<uint32_t> &which, const std::vector<float4> &leafbox,
                            uint32_t max_leaf, uint32_t depth_limit, hipStream_t s, PtOwnTreeGpu &out);
+// ... with the unit list (n_units entries) and the leaf boxes in device memory as well (a rebuild has them there: scene_rebuild.hip); the
+// entry above copies its vectors to the device and calls this one. Nothing per triangle crosses the bus.
+bool pt_build_own_tree_gpu(const ptmi_triangle *d_tris, const uint32_t *d_which, uint32_t n_units, const float4 *d_leafbox,
+                           uint32_t max_leaf, uint32_t depth_limit, hipStream_t s, PtOwnTreeGpu &out);
 // The 16-bit grid of both quantisers and of the device builder over the bounds [mn, mx]: origin = mn, the smallest scale whose last plane reaches mx (checked
 // with fmaf). false: the bounds are not finite.
 bool pt_quant_grid(const float mn[3], const float mx[3], float origin[3], float scale[3]);

@@ -21,6 +21,8 @@
 //   quantise  the host's grid (quantise.hip pt_quant_grid) from the min / max of the padded boxes; the top PT_QCACHE_NODES nodes
 //             breadth-first at the front, the others in preorder; every child through the host's own wide_node.h pt_quantise_child
 //
+// The build reads the triangles, the unit list and the leaf boxes from device memory: an upload copies the latter two there first, a
+// rebuild (scene_rebuild.hip) has them there already. Both go through one body.
 // Every step is deterministic: the same scene gives the same bytes on every run and every device. Scratch is sized from the scene and
 // owned by the scope of one build (pt_dev_build.h DevScratch); any failure returns false and the caller builds on the host.
 #include "pt_box.h"
@@ -252,10 +254,9 @@ __global__ void k_quantise(uint32_t m, PtQuantGrid g, const float4 *__restrict__
 }
 
 // the build itself; every allocation is mem's until the three buffers of `out` leave through keep(). The stream may still be busy on failure.
-bool build_own_tree(const ptmi_triangle *d_tris, const std::vector<uint32_t> &which, const std::vector<float4> &leafbox, uint32_t max_leaf,
+bool build_own_tree(const ptmi_triangle *d_tris, const uint32_t *d_which, uint32_t n, const float4 *d_leafbox, uint32_t max_leaf,
                     uint32_t depth_limit, hipStream_t s, DevScratch &mem, PtOwnTreeGpu &out) {
-    const uint32_t n = (uint32_t)which.size();
-    if (n < 2 || n > PT_LEAF_OFF_MASK) return false;
+    if (n < 2 || n > PT_LEAF_OFF_MASK || !d_which || !d_leafbox) return false;
     max_leaf = std::max(1u, std::min(max_leaf, PT_LEAF_MAX_TRIS));
     const uint32_t n_all = 2 * n - 1;
     auto blocks = [](uint32_t k) { return dim3((k + TB - 1) / TB); };
@@ -263,16 +264,12 @@ bool build_own_tree(const ptmi_triangle *d_tris, const std::vector<uint32_t> &wh
     auto settled = [&] { return hip_ok(hipStreamSynchronize(s)) && hip_ok(hipGetLastError()); };
 
     // units
-    uint32_t *d_which = mem.get<uint32_t>(n);
     Box6 *d_box = mem.get<Box6>(n_all);
     Red *d_red = mem.get<Red>(1);
-    float4 *d_leafbox = mem.get<float4>(leafbox.size());
     if (mem.failed) return false;
     Red h{};
     for (int k = 0; k < 3; k++) { h.cmin[k] = h.qmin[k] = 0xFFFFFFFFu; h.cmax[k] = h.qmax[k] = 0u; }
-    if (!hip_ok(hipMemcpyAsync(d_which, which.data(), (size_t)n * 4, hipMemcpyHostToDevice, s)) ||
-        !hip_ok(hipMemcpyAsync(d_leafbox, leafbox.data(), leafbox.size() * sizeof(float4), hipMemcpyHostToDevice, s)) ||
-        !hip_ok(hipMemcpyAsync(d_red, &h, sizeof h, hipMemcpyHostToDevice, s))) return false;
+    if (!hip_ok(hipMemcpyAsync(d_red, &h, sizeof h, hipMemcpyHostToDevice, s))) return false;
     k_units<<<blocks(n), TB, 0, s>>>(n, d_tris, d_which, d_leafbox, d_box, d_red);
     if (!read(&h, d_red, sizeof h) || !settled()) return false;
     if (h.bad) return false;                                     // a non-finite vertex: the host refuses it too
@@ -394,17 +391,39 @@ bool build_own_tree(const ptmi_triangle *d_tris, const std::vector<uint32_t> &wh
 
 }  // namespace
 
-bool pt_build_own_tree_gpu(const ptmi_triangle *d_tris, const std::vector<uint32_t> &which, const std::vector<float4> &leafbox,
-                           uint32_t max_leaf, uint32_t depth_limit, hipStream_t s, PtOwnTreeGpu &out) {
+// one build in a scratch of its own: `build` takes every allocation from it (false: it could not build)
+template <class Build>
+static bool build_in_scope(hipStream_t s, PtOwnTreeGpu &out, Build &&build) {
     out.release();
     bool ok;
     {
         DevScratch mem;
-        ok = build_own_tree(d_tris, which, leafbox, max_leaf, depth_limit, s, mem, out);
+        ok = build(mem);
         (void)hipStreamSynchronize(s);                           // nothing of ours may still run when the scratch goes
     }
     if (!ok) { (void)hipGetLastError(); out.release(); }
     return ok;
+}
+
+bool pt_build_own_tree_gpu(const ptmi_triangle *d_tris, const uint32_t *d_which, uint32_t n_units, const float4 *d_leafbox,
+                           uint32_t max_leaf, uint32_t depth_limit, hipStream_t s, PtOwnTreeGpu &out) {
+    return build_in_scope(s, out, [&](DevScratch &mem) {
+        return build_own_tree(d_tris, d_which, n_units, d_leafbox, max_leaf, depth_limit, s, mem, out);
+    });
+}
+
+// an upload has the unit list and the leaf boxes on the host: copy, then the build above
+bool pt_build_own_tree_gpu(const ptmi_triangle *d_tris, const std::vector<uint32_t> &which, const std::vector<float4> &leafbox,
+                           uint32_t max_leaf, uint32_t depth_limit, hipStream_t s, PtOwnTreeGpu &out) {
+    return build_in_scope(s, out, [&](DevScratch &mem) {
+        const uint32_t n = (uint32_t)which.size();
+        uint32_t *d_which = mem.get<uint32_t>(n);
+        float4 *d_leafbox = mem.get<float4>(leafbox.size());
+        if (mem.failed || n < 2 ||
+            !hip_ok(hipMemcpyAsync(d_which, which.data(), (size_t)n * 4, hipMemcpyHostToDevice, s)) ||
+            !hip_ok(hipMemcpyAsync(d_leafbox, leafbox.data(), leafbox.size() * sizeof(float4), hipMemcpyHostToDevice, s))) return false;
+        return build_own_tree(d_tris, d_which, n, d_leafbox, max_leaf, depth_limit, s, mem, out);
+    });
 }
 
 void PtOwnTreeGpu::release() {

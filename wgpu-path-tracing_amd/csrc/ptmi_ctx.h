@@ -9,6 +9,7 @@
 //   medium_grid.hip    the medium's density grid: its checks, upload and removal, its debug entry points
 //   scene_update.hip   edits of a loaded scene in place: ptmi_update_triangles (the refit on the device), _materials, _lights
 //   alpha.hip          alpha cutouts: the cutoff table, the two resolve loops between the existing kernels, their debug entry points
+//   scene_rebuild.hip  the walked own-leaf tree rebuilt in place: the unit list on the device, the swap (ptmi_rebuild_tree)
 //   motion.hip         reprojection across a geometry edit: the previous positions, their commit, the motion plane (ptmi_set_motion)
 #pragma once
 #include "ptmi.h"
@@ -49,6 +50,8 @@ uint32_t pt_ctx_materials(const ptmi_ctx *c);
 hipStream_t pt_ctx_stream(ptmi_ctx *c);
 int pt_ctx_device(const ptmi_ctx *c);
 int pt_ctx_cus(const ptmi_ctx *c);
+// the argument and state checks of ptmi_rebuild_tree (scene_rebuild.hip), which change nothing: its error codes, the reason in err
+int pt_check_rebuild(const ptmi_ctx *c, const ptmi_rebuild_params *params, std::string &err);
 // Adaptive rounds driven from outside, one at a time (ptmi_multi_dispatch_adaptive with neighbourhood = 1; dispatch.hip).
 // pt_adaptive_check: everything ptmi_dispatch_adaptive checks before it enqueues, with its error codes; *ap = the params with their defaults.
 int pt_adaptive_check(ptmi_ctx *c, const ptmi_camera *cam, const ptmi_adaptive_params *params, ptmi_adaptive_params *ap);
@@ -74,7 +77,8 @@ enum SceneBuf {
     kLeafbox,                          // own leaves: per original triangle, the box of the reference leaf that lists it
     kWnodes16, kRefWnodes16, kQnodes16,    // own leaves, small scenes: the two hierarchies and the quantised nodes with 16-bit references
     kShadeTab,                         // the shade tables: materials, lights and the lights' triangles in one blob (pt_device.h)
-    // the plan of ptmi_update_triangles (scene_update.hip), made at the first update after an upload and gone with the next upload:
+    // the plan of ptmi_update_triangles (scene_update.hip), made at the first update after an upload, re-made by ptmi_rebuild_tree and
+    // gone with the next upload:
     kPlanRefOrder, kPlanOrder,         // the nodes of kRefWnodes / kWnodes by height above their deepest leaf, lowest first
     kPlanQnum,                         // per node of kWnodes, its number in kQnodes
     kPlanUnits, kPlanExact,            // own leaves: the unit box of every listed triangle (leaf order); both exact child boxes per node
@@ -167,7 +171,7 @@ struct ptmi_ctx {
     DevScene *d_scene = nullptr;                       // sc in device memory (DevScene::self), rewritten whenever sc changes
     DevScene sc{};
     bool have_scene = false;
-    ptmi_image_info img{};                   // what the last upload put on the device (ptmi_debug_read_image)
+    ptmi_image_info img{};                   // what the last upload (or rebuild) put on the device (ptmi_debug_read_image)
     uint32_t n_ref_wnodes = 0;               // wide nodes of the tree as uploaded (kRefWnodes)
     bool tree_nested = false;                // the uploaded tree was nested and finite: a hierarchy could be built over it
     // ptmi_update_triangles since the last upload (scene_update.hip): the level lists of the plan (level l of a list: entries
@@ -175,6 +179,7 @@ struct ptmi_ctx {
     bool upd_planned = false;
     std::vector<uint32_t> upd_ref_off, upd_off;
     struct ptmi_scene_update_status upd{};
+    struct ptmi_rebuild_status reb{};         // ptmi_rebuild_tree since the last upload (scene_rebuild.hip)
 
     // motion (ptmi_set_motion; motion.hip): the previous positions are buf[kMotionPrev], the plane is plane[kMotion]
     bool motion_on = false;
@@ -231,6 +236,27 @@ int check_ready(ptmi_ctx *c, bool need_output);
 // dispatch.hip
 void drain_events(ptmi_ctx *c);
 hipError_t quiesce(ptmi_ctx *c);
+
+// scene_update.hip: the plan of ptmi_update_triangles. make_plan reads the topology of both hierarchies as they stand and leaves the
+// context's scene alone (a failure leaves no plan behind; the caller drops what is left); walked_cost: the cost of the walked hierarchy
+// as it stands on the device (include/ptmi.h ptmi_scene_update_status), synchronises
+void drop_plan(ptmi_ctx *c);
+int make_plan(ptmi_ctx *c);
+int walked_cost(ptmi_ctx *c, double &cost);
+
+// scene_image.hip: the own-leaf image of the loaded scene built anew from what is on the device (ptmi_rebuild_tree), by the code an
+// upload builds it with. d_which: the unit list (n_units entries, device memory). buf: new device buffers for the entries a rebuild
+// replaces (kWnodes, kTripos, kQnodes and the three 16-bit copies; absent: NULL), owned here until the swap takes them.
+struct OwnRebuilt {
+    void *buf[kSceneBufs] = {};
+    ptmi_image_info img{};
+    uint32_t q_top = 0, root_ref16 = 0xFFFFFFFFu, ref_root_ref16 = 0xFFFFFFFFu, builder_used = 0;
+    OwnRebuilt() = default;
+    OwnRebuilt(const OwnRebuilt &) = delete;
+    OwnRebuilt &operator=(const OwnRebuilt &) = delete;
+    ~OwnRebuilt() { for (void *p : buf) if (p) (void)hipFree(p); }
+};
+int rebuild_own_image(ptmi_ctx *c, const ptmi_options &opt, const uint32_t *d_which, uint32_t n_units, OwnRebuilt &out);
 
 // motion.hip
 // an upload or an update while motion is on: the previous positions filled from all of the device's triangles (dirty range and epochs

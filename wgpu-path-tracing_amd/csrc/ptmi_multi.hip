@@ -519,6 +519,21 @@ int ptmi_multi_scene_update_status(ptmi_multi *m, struct ptmi_scene_update_statu
     return rc ? cfail(m, 0, rc, "ptmi_scene_update_status") : PTMI_OK;
 }
 
+// The walked tree rebuilt on every device (scene_rebuild.hip). Every device holds the same scene and both builders are deterministic, so
+// every device ends with the same image; the checks that refuse a call run once, on device 0's context, before any device changes.
+int ptmi_multi_rebuild_tree(ptmi_multi *m, const ptmi_rebuild_params *params) {
+    if (!m) return PTMI_E_INVALID;
+    std::string why;
+    const int rc = pt_check_rebuild(m->d[0].ctx, params, why);
+    if (rc) return mfail(m, rc, "%s", why.c_str());
+    return each_ctx(m, "ptmi_rebuild_tree", ptmi_rebuild_tree, params);
+}
+int ptmi_multi_rebuild_status(ptmi_multi *m, struct ptmi_rebuild_status *out) {
+    if (!m || !out) return PTMI_E_INVALID;
+    const int rc = ptmi_rebuild_status(m->d[0].ctx, out);
+    return rc ? cfail(m, 0, rc, "ptmi_rebuild_status") : PTMI_OK;
+}
+
 int ptmi_multi_resize(ptmi_multi *m, uint32_t w, uint32_t h) {
     if (!m) return PTMI_E_INVALID;
     int rc = each_ctx(m, "ptmi_resize", ptmi_resize, w, h);

@@ -120,15 +120,13 @@ bool own_tree_on_device(hipStream_t stream, int device, const ptmi_triangle *tri
 // Own leaves, after whichever builder ran (on_device: g on `device`, else t): the walked image and its header, the quantised nodes (the
 // device builder made its own) and, for scenes of up to 4 096 triangles, both hierarchies and the quantised nodes once more with 16-bit
 // child references (the device builder only runs on larger scenes).
-void own_image(Built &b, bool on_device, int device, PtOwnTreeGpu &g, PtOwnTree &t, uint32_t nt, const std::vector<float4> &ref_wnodes,
-               std::vector<float4> &&leafbox) {
+void own_image(Built &b, bool on_device, int device, PtOwnTreeGpu &g, PtOwnTree &t, uint32_t nt, const std::vector<float4> &ref_wnodes) {
     ptmi_image_info &h = b.img;
     const PtOwnTreeHeader &o = on_device ? static_cast<const PtOwnTreeHeader &>(g) : t;
     h.leaves_used = 2u; h.root_ref = o.root_ref; h.depth = o.depth; h.n_leaves = o.n_leaves; h.max_leaf_tris = o.max_leaf_tris;
     for (int k = 0; k < 3; k++) { h.root_min[k] = o.root_min[k]; h.root_max[k] = o.root_max[k]; }
     h.pad = o.pad; h.safe_origin = o.safe_origin;
     b.tree_builder_used = on_device ? 2u : 1u;
-    b.hold(kLeafbox, std::move(leafbox));
     if (on_device) {
         h.n_wnodes = g.n_wnodes; h.n_tris = g.n_tris; h.quantised = g.quantised ? 1u : 0u; b.q_top = g.q_top;
         for (int k = 0; k < 3; k++) { h.q_origin[k] = g.q_origin[k]; h.q_scale[k] = g.q_scale[k]; }
@@ -158,6 +156,38 @@ void own_image(Built &b, bool on_device, int device, PtOwnTreeGpu &g, PtOwnTree 
     h.n_wnodes = (uint32_t)(t.wnodes.size() / 4); h.n_tris = (uint32_t)(t.tripos.size() / 3); h.quantised = q.empty() ? 0u : 1u;
     b.hold(kWnodes, std::move(t.wnodes)); b.hold(kTripos, std::move(t.tripos));
     if (!q.empty()) b.hold(kQnodes, std::move(q));
+}
+
+// What the host builder of the own leaves reads: an upload has it at hand, a rebuild reads it back from the device only when it is needed.
+struct OwnHostInputs {
+    const ptmi_triangle *tris = nullptr;
+    const std::vector<uint32_t> *which = nullptr;        // the unit list: the triangles some reachable reference leaf lists, ascending
+    const std::vector<float4> *leafbox = nullptr;        // per original triangle, the box of the reference leaf that lists it
+    const std::vector<float4> *ref_wnodes = nullptr;     // the tree as uploaded (for its 16-bit copy)
+};
+
+// Own leaves over n_units of a scene's nt triangles under `opt`, into b: the one place that says which builder runs and with what limits,
+// for an upload (build_image) and a rebuild (rebuild_own_image) alike. device_build(k_max, limit, g): the device builder on the caller's
+// device inputs (false: not built); host_inputs(in): the host builder's inputs (false: they could not be had). have_device: there is
+// a stream to build on. false: no own leaves were built (b is as it was).
+template <class DeviceBuild, class HostInputs>
+bool own_leaves(const ptmi_options &opt, bool have_device, int device, uint32_t nt, uint32_t n_units, Built &b, DeviceBuild &&device_build,
+                HostInputs &&host_inputs) {
+    const uint32_t k_max = opt.leaf_tris ? opt.leaf_tris : (uint32_t)PT_LEAF_TRIS_DEFAULT;
+    // small scenes: at most 14 levels, so that a lane's whole node stack fits the 15 LDS entries of two workgroups per CU
+    const uint32_t limit = n_units <= 2048 ? 14u : 60u;
+    // tree_builder = 2: on the device for scenes above 4 096 triangles. Smaller scenes keep the host builder (a few ms): they get the
+    // 16-bit images, and which of the LDS variants fits them turns on a few tens of nodes (cornell_spheres: the host tree has 2 038,
+    // within the 2 046 of the quantised 16-bit variant; the device tree 2 109). Also on the host: without a device (the host-only
+    // debug entry points) and when the device build fails
+    PtOwnTreeGpu g;
+    PtOwnTree t;
+    const bool on_device = opt.tree_builder == 2u && have_device && nt > 4096u && n_units > 2048u && device_build(k_max, limit, g);
+    OwnHostInputs in;
+    static const std::vector<float4> none;
+    if (!on_device && !(host_inputs(in) && pt_build_own_tree(in.tris, *in.which, *in.leafbox, k_max, limit, t))) return false;
+    own_image(b, on_device, device, g, t, nt, in.ref_wnodes ? *in.ref_wnodes : none);
+    return true;
 }
 
 // The traversal image of a scene under `opt`. tree_builder = 2 builds on `device` through `stream` (none: the host-only debug entry
@@ -262,19 +292,12 @@ int build_image(const ptmi_options &opt, hipStream_t stream, int device, const p
             }
         }
         std::sort(which.begin(), which.end());
-        const uint32_t k_max = opt.leaf_tris ? opt.leaf_tris : (uint32_t)PT_LEAF_TRIS_DEFAULT;
-        // small scenes: at most 14 levels, so that a lane's whole node stack fits the 15 LDS entries of two workgroups per CU
-        const uint32_t limit = which.size() <= 2048 ? 14u : 60u;
-        // tree_builder = 2: on the device for scenes above 4 096 triangles. Smaller scenes keep the host builder (a few ms): they get the
-        // 16-bit images, and which of the LDS variants fits them turns on a few tens of nodes (cornell_spheres: the host tree has 2 038,
-        // within the 2 046 of the quantised 16-bit variant; the device tree 2 109). Also on the host: without a device (the host-only
-        // debug entry points) and when the device build fails
-        PtOwnTreeGpu g;
-        PtOwnTree t;
-        const bool on_device = opt.tree_builder == 2u && stream && nt > 4096u && which.size() > 2048u &&
-                               own_tree_on_device(stream, device, tris, nt, which, leafbox, k_max, limit, b, g);
-        own = on_device || pt_build_own_tree(tris, which, leafbox, k_max, limit, t);
-        if (own) own_image(b, on_device, device, g, t, nt, wnodes, std::move(leafbox));
+        own = own_leaves(opt, stream != nullptr, device, nt, (uint32_t)which.size(), b,
+                         [&](uint32_t k_max, uint32_t limit, PtOwnTreeGpu &g) {
+                             return own_tree_on_device(stream, device, tris, nt, which, leafbox, k_max, limit, b, g);
+                         },
+                         [&](OwnHostInputs &in) { in.tris = tris; in.which = &which; in.leafbox = &leafbox; in.ref_wnodes = &wnodes; return true; });
+        if (own) b.hold(kLeafbox, std::move(leafbox));
         b.tree_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     std::vector<float4> fast;                   // a hierarchy rebuilt over the reference's leaves
@@ -349,6 +372,17 @@ static std::vector<float4> shade_tables(const ptmi_triangle *tris, uint32_t nt, 
     return tab;
 }
 
+// One buffer of a preparation on c's device, in *out: taken over (`take`, and it is on that device), else allocated and copied. An empty
+// buffer gets 16 zeroed bytes.
+static hipError_t place(const ptmi_ctx *c, HeldBuf &h, bool take, void **out) {
+    if (h.dev && take && h.device == c->device) { *out = h.dev; h.dev = nullptr; return hipSuccess; }
+    hipError_t e = hipMalloc(out, h.bytes ? h.bytes : 16);
+    if (e != hipSuccess) return e;
+    if (h.dev) return h.device == c->device ? hipMemcpy(*out, h.dev, h.bytes, hipMemcpyDeviceToDevice)
+                                            : hipMemcpyPeer(*out, c->device, h.dev, h.device, h.bytes);
+    return h.bytes ? hipMemcpy(*out, h.host, h.bytes, hipMemcpyHostToDevice) : hipMemset(*out, 0, 16);
+}
+
 PtPrepared *pt_prepare_scene(ptmi_ctx *c, const ptmi_triangle *tris, uint32_t nt, const ptmi_material *mats, uint32_t nm,
                              const ptmi_bvh_node *nodes, uint32_t nn, const ptmi_light *lights, uint32_t nl, int *rc_out) {
     auto bad = [&](int rc) -> PtPrepared * { *rc_out = rc; return nullptr; };
@@ -390,14 +424,7 @@ int pt_install_scene(ptmi_ctx *c, PtPrepared *prep) {
     void *n[kSceneBufs] = {};
     hipError_t e = hipSuccess;
     for (int k = 0; k < kSceneBufs && e == hipSuccess; k++) {
-        HeldBuf &h = b.buf[k];
-        if (!h.present) continue;
-        if (h.dev && prep->take_device_buffers && h.device == c->device) { n[k] = h.dev; h.dev = nullptr; continue; }
-        e = hipMalloc(&n[k], h.bytes ? h.bytes : 16);
-        if (e != hipSuccess) break;
-        if (h.dev) e = h.device == c->device ? hipMemcpy(n[k], h.dev, h.bytes, hipMemcpyDeviceToDevice)
-                                             : hipMemcpyPeer(n[k], c->device, h.dev, h.device, h.bytes);
-        else e = h.bytes ? hipMemcpy(n[k], h.host, h.bytes, hipMemcpyHostToDevice) : hipMemset(n[k], 0, 16);
+        if (b.buf[k].present) e = place(c, b.buf[k], prep->take_device_buffers, &n[k]);
     }
     // while motion is on (ptmi_set_motion) the previous positions are re-made for the new scene: filled below, from its triangles
     if (e == hipSuccess && c->motion_on) {
@@ -446,7 +473,7 @@ int pt_install_scene(ptmi_ctx *c, PtPrepared *prep) {
     c->img = h;
     c->have_scene = true;
     c->n_ref_wnodes = (uint32_t)(b.buf[kRefWnodes].bytes / 64); c->tree_nested = b.nested;
-    c->upd_planned = false; c->upd_ref_off.clear(); c->upd_off.clear(); c->upd = {};
+    c->upd_planned = false; c->upd_ref_off.clear(); c->upd_off.clear(); c->upd = {}; c->reb = {};
     if (c->motion_on) {
         const int rc = motion_fill(c);
         if (rc) return rc;
@@ -462,6 +489,46 @@ int pt_install_scene(ptmi_ctx *c, PtPrepared *prep) {
     c->st.upload_copy_ms = ms_since(t_copy);
     c->st.upload_tree_ms = b.tree_ms;
     c->st.upload_ms = prep->build_ms + ms_since(t_start);
+    return PTMI_OK;
+}
+
+// ptmi_rebuild_tree's build (ptmi_ctx.h). The device builder reads the context's own buffers; the host builder's inputs are read back
+// (at most 512 KB for the scenes that always take it). Nothing of the context changes.
+int pt_host::rebuild_own_image(ptmi_ctx *c, const ptmi_options &opt, const uint32_t *d_which, uint32_t n_units, OwnRebuilt &out) {
+    const uint32_t nt = c->sc.n_tris;
+    void *const *d = c->buf;
+    Built b;
+    b.img = c->img;                                                  // (ref_depth stays; what follows is what build_image starts an own image from)
+    b.img.quantised = 0u;
+    for (int k = 0; k < 3; k++) b.img.q_origin[k] = b.img.q_scale[k] = 0.0f;
+    b.ref_root_ref = c->sc.ref_root_ref;
+    std::vector<ptmi_triangle> tris;
+    std::vector<uint32_t> which;
+    std::vector<float4> leafbox, ref_wnodes;
+    hipError_t e = hipSuccess;
+    auto fetch = [&](auto &v, size_t n, const void *from) {
+        v.resize(n);
+        if (n && e == hipSuccess) e = hipMemcpy(v.data(), from, n * sizeof(v[0]), hipMemcpyDeviceToHost);
+    };
+    const bool own = own_leaves(opt, true, c->device, nt, n_units, b,
+        [&](uint32_t k_max, uint32_t limit, PtOwnTreeGpu &g) {
+            return pt_build_own_tree_gpu(c->sc.tris, d_which, n_units, static_cast<const float4 *>(d[kLeafbox]), k_max, limit, c->stream, g);
+        },
+        [&](OwnHostInputs &in) {
+            fetch(tris, nt, d[kTris]); fetch(which, n_units, d_which); fetch(leafbox, (size_t)nt * 2, d[kLeafbox]);
+            fetch(ref_wnodes, (size_t)c->n_ref_wnodes * 4, d[kRefWnodes]);
+            in.tris = tris.data(); in.which = &which; in.leafbox = &leafbox; in.ref_wnodes = &ref_wnodes;
+            return e == hipSuccess;
+        });
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, PTMI_E_HIP, "reading the scene back for the host builder failed: %s", hipGetErrorString(e)); }
+    if (!own) return fail(c, PTMI_E_STATE, "the own-leaf builder refused the loaded triangles");      // (an update admits only finite ones)
+    for (SceneBuf k : {kWnodes, kTripos, kQnodes, kWnodes16, kRefWnodes16, kQnodes16})
+        if (b.buf[k].present && (e = place(c, b.buf[k], true, &out.buf[k])) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, PTMI_E_HIP, "placing the rebuilt image failed: %s", hipGetErrorString(e));
+        }
+    out.img = b.img; out.q_top = b.q_top; out.root_ref16 = b.root_ref16; out.ref_root_ref16 = b.ref_root_ref16;
+    out.builder_used = b.tree_builder_used;
     return PTMI_OK;
 }
 

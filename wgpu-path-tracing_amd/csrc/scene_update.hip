@@ -301,6 +301,21 @@ template <class T> int to_device(ptmi_ctx *c, SceneBuf k, const std::vector<T> &
 }
 template <class T> T *buf_as(const ptmi_ctx *c, SceneBuf k) { return static_cast<T *>(c->buf[k]); }
 
+// The reduction words, made on first use. Zeroed on the context's stream and waited for: that stream does not wait for the null stream,
+// so a plain hipMemset could land after the first k_cost had written its partial sums.
+int ensure_words(ptmi_ctx *c) {
+    if (c->buf[kPlanWords]) return PTMI_OK;
+    HIP_TRY(c, hipMalloc(&c->buf[kPlanWords], sizeof(Words)));
+    HIP_TRY(c, hipMemsetAsync(c->buf[kPlanWords], 0, sizeof(Words), c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PTMI_OK;
+}
+
+}  // namespace
+
+// the plan: shared with scene_rebuild.hip, which re-makes it for a new topology (ptmi_ctx.h)
+PT_HOST {
+
 void drop_plan(ptmi_ctx *c) {
     for (SceneBuf k : {kPlanRefOrder, kPlanOrder, kPlanQnum, kPlanUnits, kPlanExact, kPlanWords}) dfree(c->buf[k]);
     c->upd_planned = false; c->upd_ref_off.clear(); c->upd_off.clear();
@@ -311,6 +326,8 @@ int walked_cost(ptmi_ctx *c, double &cost) {
     cost = 0.0;
     const uint32_t m = c->sc.n_wnodes;
     if (m == 0) return PTMI_OK;
+    int rc = ensure_words(c);                                   // (before the first plan: scratch only, it is no part of a plan's state)
+    if (rc) return rc;
     Words *red = buf_as<Words>(c, kPlanWords);
     k_cost<<<kCostBlocks, TB, 0, c->stream>>>(m, c->sc.wnodes, red);
     HIP_TRY(c, hipGetLastError());
@@ -365,8 +382,7 @@ int make_plan(ptmi_ctx *c) {
         if (own) HIP_TRY(c, hipMalloc(&c->buf[kPlanExact], (size_t)n_walk * 2 * sizeof(Box6)));
     }
     if (own) HIP_TRY(c, hipMalloc(&c->buf[kPlanUnits], std::max<size_t>(16, (size_t)c->sc.n_own_tris * sizeof(Box6))));
-    HIP_TRY(c, hipMalloc(&c->buf[kPlanWords], sizeof(Words)));
-    HIP_TRY(c, hipMemset(c->buf[kPlanWords], 0, sizeof(Words)));
+    if ((rc = ensure_words(c))) return rc;
     c->upd = {};
     if ((rc = walked_cost(c, c->upd.cost_built))) return rc;
     c->upd.cost_now = c->upd.cost_built;
@@ -375,6 +391,10 @@ int make_plan(ptmi_ctx *c) {
     c->upd_planned = true;
     return PTMI_OK;
 }
+
+}  // namespace pt_host
+
+namespace {
 
 // one launch per height of a hierarchy over ranges of the original triangles
 int refit_ranges(ptmi_ctx *c, const std::vector<uint32_t> &off, SceneBuf order, uint32_t n_nodes, float4 *w, float4 *w16, float4 *leafbox) {

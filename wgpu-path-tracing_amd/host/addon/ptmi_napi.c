@@ -325,6 +325,35 @@ static napi_value js_scene_update_status(napi_env env, napi_callback_info info) 
     return out;
 }
 
+/* rebuildStatus(handle) -> {rebuilds, builderUsed, buildMs, costBefore, costAfter} */
+static napi_value js_rebuild_status(napi_env env, napi_callback_info info) {
+    napi_value argv[1], out, v;
+    handle *h = get_handle(env, info, 1, argv);
+    if (!h) return NULL;
+    struct ptmi_rebuild_status st;
+    CALL(env, h, rebuild_status, &st);
+    NAPI_OK(env, napi_create_object(env, &out));
+    const struct { const char *name; double value; } num[] = {
+        {"rebuilds", st.rebuilds}, {"builderUsed", st.builder_used}, {"buildMs", st.build_ms},
+        {"costBefore", st.cost_before}, {"costAfter", st.cost_after}};
+    for (size_t i = 0; i < sizeof num / sizeof num[0]; i++) {
+        NAPI_OK(env, napi_create_double(env, num[i].value, &v));
+        NAPI_OK(env, napi_set_named_property(env, out, num[i].name, v));
+    }
+    return out;
+}
+
+/* rebuildTree(handle, builder): ptmi_rebuild_tree; builder 0 picks the default */
+static napi_value js_rebuild_tree(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    handle *h = get_handle(env, info, 2, argv);
+    if (!h) return NULL;
+    ptmi_rebuild_params prm = {0};
+    napi_get_value_uint32(env, argv[1], &prm.builder);
+    CALL(env, h, rebuild_tree, &prm);
+    return NULL;
+}
+
 /* setAlphaCutoff(handle, Float32Array | null, maxLayers): ptmi_set_alpha_cutoff; one cutoff per uploaded material, null removes the table */
 static napi_value js_set_alpha_cutoff(napi_env env, napi_callback_info info) {
     napi_value argv[3];
@@ -883,6 +912,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"abiVersion", js_abi_version}, {"create", js_create}, {"multiCreate", js_multi_create}, {"destroy", js_destroy},
         {"uploadScene", js_upload_scene}, {"uploadAtlas", js_upload_atlas}, {"uploadEnvironment", js_upload_environment}, {"setMedium", js_set_medium}, {"uploadMediumDensity", js_upload_medium_density},
         {"updateTriangles", js_update_triangles}, {"updateMaterials", js_update_materials}, {"updateLights", js_update_lights}, {"sceneUpdateStatus", js_scene_update_status},
+        {"rebuildTree", js_rebuild_tree}, {"rebuildStatus", js_rebuild_status},
         {"setAlphaCutoff", js_set_alpha_cutoff}, {"alphaStatus", js_alpha_status},
         {"resize", js_resize}, {"setOptions", js_set_options},
         {"dispatch", js_dispatch}, {"gather", js_gather}, {"gatherPlanes", js_gather_planes}, {"synchronize", js_synchronize}, {"throttle", js_throttle},

@@ -60,7 +60,10 @@ export class Renderer {
                            *  cutout at its alphaCutoff (default 0.5); off (the default): the atlas bytes and everything else as without */
                           alphaCutout?: boolean;
                           /** ... with this maxLayers (0 / absent: the library's default, 4) */
-                          alphaLayers?: number });
+                          alphaLayers?: number;
+                          /** updateTriangles calls rebuildTree() when it leaves sceneUpdateStatus().costNow / costBuilt above this ratio.
+                           *  Off (0 / absent) by default; a rebuild was measured to pay from roughly 1.2 - 1.3 (README.md) */
+                          rebuildAbove?: number });
   camera: CameraCPU;
   addOnUpdate(callback: (deltaTime: number) => void): void;
   loadModel(model: string | SceneData | { blobs: SceneBlobs; atlas?: Atlas | null; alphaCutoff?: Float32Array }, atlas?: Atlas): Promise<void>;
@@ -83,6 +86,12 @@ export class Renderer {
   updateMaterials(first: number, blob: ArrayBuffer | ArrayBufferView): void;
   updateLights(first: number, blob: ArrayBuffer | ArrayBufferView): void;
   sceneUpdateStatus(): SceneUpdateStatus;
+  /** builds the walked own-leaf tree anew from the triangles as they stand on the device and swaps it in (include/ptmi.h
+   *  ptmi_rebuild_tree): the image a fresh loadModel of the edited scene would build, with the triangle order, the tables, the alpha
+   *  table, the motion state and every plane left alone. builder: 1 the host's, 2 (default) the device's where it applies. The hits
+   *  do not depend on the tree, so accumulation continues. Throws for an image without own leaves (leaves = 1, keepReferenceTree). */
+  rebuildTree(opts?: { builder?: 0 | 1 | 2 }): RebuildStatus;
+  rebuildStatus(): RebuildStatus;
   /** the root box of the loaded scene's hierarchy (null without one); follows updateTriangles */
   sceneBounds: { min: number[]; max: number[] } | null;
   renderFrame(frames?: number): void;
@@ -175,6 +184,15 @@ export interface SceneUpdateStatus {
   costBuilt: number; costNow: number;
   /** the refitted root box of the tree as uploaded */
   rootMin: number[]; rootMax: number[];
+}
+/** ptmi_rebuild_status: the rebuilds of the walked tree since the scene was loaded */
+export interface RebuildStatus {
+  rebuilds: number;
+  /** 1 the host, 2 the device built the last one (0: none yet) */
+  builderUsed: number;
+  buildMs: number;
+  /** the walked tree's cost (SceneUpdateStatus) around the last rebuild */
+  costBefore: number; costAfter: number;
 }
 export interface MediumDensityOptions {
   /** 'nearest' (default): the cell that holds the point; 'linear': trilinear over the cell centres */

@@ -62,6 +62,7 @@ function Renderer(options) {
   this.reproject = null;                    // setReproject: the parameters, while camera changes carry the accumulated samples over
   this.accumulatedUnder = null;             // the camera bytes of the last adaptive round: what the planes were accumulated under
   this.reprojectFrom = null;                // ... kept here while a camera change waits for the next round to reproject
+  this.rebuildAbove = options.rebuildAbove || 0;        // updateTriangles rebuilds the walked tree above this costNow / costBuilt (0: never)
   this.motion = false;                      // setMotion: reprojection carries the samples across updateTriangles too
   if (options.adaptive) this.setAdaptive(options.adaptive);
 }
@@ -244,7 +245,7 @@ Renderer.prototype.setMedium = function (medium) {
  * layout loadModel uploads (an ArrayBuffer or a typed array), written over the scene's from record `first` on. The topology stays:
  * same counts, same triangle order. updateTriangles refits the trees on the device and refreshes sceneBounds (what
  * setMedium({ bounds: 'scene' }) reads) from the refitted root box; sceneUpdateStatus().costNow / costBuilt says how far the refitted
- * tree has degraded, for the host to decide when to loadModel again. Accumulation restarts, except after updateTriangles under
+ * tree has degraded, for the host to decide when to rebuildTree (new Renderer({ rebuildAbove: ratio }) does so here). Accumulation restarts, except after updateTriangles under
  * setReproject, setMotion(true) and adaptive rounds, which continues (setMotion). A refused edit throws and changes nothing.
  */
 Renderer.prototype.updateTriangles = function (first, blob) {
@@ -259,6 +260,7 @@ Renderer.prototype.updateTriangles = function (first, blob) {
     this.adaptiveActive = -1;
     this.adaptivePending = false;
   } else this.frameIndex = 0;
+  if (this.rebuildAbove > 0 && st.costBuilt > 0 && st.costNow / st.costBuilt > this.rebuildAbove) this.rebuildTree();
 };
 Renderer.prototype.updateMaterials = function (first, blob) {
   if (!this.sceneLoaded) throw new Error('updateMaterials: needs a loaded scene (loadModel)');
@@ -273,6 +275,25 @@ Renderer.prototype.updateLights = function (first, blob) {
 /** { updates, quantisedKept, planMs, refitMs, costBuilt, costNow, rootMin, rootMax } of the triangle updates since loadModel */
 Renderer.prototype.sceneUpdateStatus = function () {
   return this.addon.sceneUpdateStatus(this.ctx);
+};
+
+/**
+ * The walked tree rebuilt in place (include/ptmi.h ptmi_rebuild_tree): a refit keeps the topology, so the tree degrades as geometry
+ * moves; this builds the own-leaf tree anew from the triangles as they stand on the device and swaps it in, leaving the triangle
+ * order, the tables, the alpha table, the motion state and every plane alone. opts: { builder (1 the host's, 2 / 0 / absent the
+ * device's where it applies) }. Any tree over the same triangles gives the same hits, so the accumulated samples stay valid and
+ * frameIndex is kept. Returns rebuildStatus(). new Renderer({ rebuildAbove: ratio }) calls this after an updateTriangles that leaves
+ * costNow / costBuilt above the ratio: off by default; a rebuild was measured to pay from roughly 1.2 - 1.3 (README.md). Throws for
+ * an image without own leaves (options.leaves = 1, keepReferenceTree).
+ */
+Renderer.prototype.rebuildTree = function (opts) {
+  if (!this.sceneLoaded) throw new Error('rebuildTree: needs a loaded scene (loadModel)');
+  this.addon.rebuildTree(this.ctx, (opts && opts.builder) || 0);
+  return this.addon.rebuildStatus(this.ctx);
+};
+/** { rebuilds, builderUsed, buildMs, costBefore, costAfter } of the rebuilds since loadModel */
+Renderer.prototype.rebuildStatus = function () {
+  return this.addon.rebuildStatus(this.ctx);
 };
 
 /**

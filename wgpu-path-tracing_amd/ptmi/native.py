@@ -46,6 +46,7 @@ EXPORTS = [
     "ptmi_debug_medium_track", "ptmi_debug_medium_grid_check",
     "ptmi_update_triangles", "ptmi_update_materials", "ptmi_update_lights", "ptmi_scene_update_status",
     "ptmi_multi_update_triangles", "ptmi_multi_update_materials", "ptmi_multi_update_lights", "ptmi_multi_scene_update_status",
+    "ptmi_rebuild_tree", "ptmi_rebuild_status", "ptmi_multi_rebuild_tree", "ptmi_multi_rebuild_status",
     "ptmi_set_alpha_cutoff", "ptmi_alpha_status", "ptmi_multi_set_alpha_cutoff", "ptmi_multi_alpha_status",
     "ptmi_debug_alpha_intersect", "ptmi_debug_alpha_occluded",
 ]
@@ -170,6 +171,21 @@ class SceneUpdateStatus(ctypes.Structure):
                 "root_box": (tuple(self.root_min), tuple(self.root_max))}
 
 
+class RebuildParams(ctypes.Structure):
+    """ptmi_rebuild_params; builder 0 picks the device builder where it applies (include/ptmi.h)"""
+    _fields_ = [("builder", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 7)]
+
+
+class RebuildStatus(ctypes.Structure):
+    """struct ptmi_rebuild_status: the rebuilds of the walked tree since the last upload (include/ptmi.h)"""
+    _fields_ = [("rebuilds", ctypes.c_uint32), ("builder_used", ctypes.c_uint32), ("build_ms", ctypes.c_double),
+                ("cost_before", ctypes.c_double), ("cost_after", ctypes.c_double)]
+
+    def as_dict(self):
+        return {"rebuilds": int(self.rebuilds), "builder_used": int(self.builder_used), "build_ms": float(self.build_ms),
+                "cost_before": float(self.cost_before), "cost_after": float(self.cost_after)}
+
+
 class AlphaParams(ctypes.Structure):
     """ptmi_alpha_params; max_layers 0 picks the default (include/ptmi.h)"""
     _fields_ = [("max_layers", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
@@ -227,6 +243,7 @@ _SHARED = {
     "update_materials": [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p],
     "update_lights": [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p],
     "scene_update_status": [ctypes.c_void_p],
+    "rebuild_tree": [ctypes.c_void_p], "rebuild_status": [ctypes.c_void_p],
     "set_alpha_cutoff": [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p], "alpha_status": [ctypes.c_void_p],
 }
 _lib = None
@@ -488,6 +505,20 @@ class _Handle:
     def scene_update_status(self):
         st = SceneUpdateStatus()
         self._ck(self._c.scene_update_status(self.h, ctypes.byref(st)))
+        return st
+
+    # -- the walked tree rebuilt in place (include/ptmi.h ptmi_rebuild_tree) --------------------------------------------
+    def rebuild_tree(self, builder=0, reserved=(0, 0, 0, 0, 0, 0, 0)):
+        """builds the walked own-leaf tree anew from the triangles as they stand on the device and swaps it in: the image a fresh
+        upload of the edited scene would build. builder 1: the host's, 2 (and 0): the device's where it applies. Returns the
+        RebuildStatus."""
+        prm = RebuildParams(builder, (ctypes.c_uint32 * 7)(*reserved))
+        self._ck(self._c.rebuild_tree(self.h, ctypes.byref(prm)))
+        return self.rebuild_status()
+
+    def rebuild_status(self):
+        st = RebuildStatus()
+        self._ck(self._c.rebuild_status(self.h, ctypes.byref(st)))
         return st
 
     # -- alpha cutouts (include/ptmi.h ptmi_set_alpha_cutoff) ---------------------------------------------------------
