@@ -744,6 +744,59 @@ int ptmi_rebuild_status(ptmi_ctx *ctx, struct ptmi_rebuild_status *out);
 int ptmi_multi_rebuild_tree(ptmi_multi *m, const ptmi_rebuild_params *params);
 int ptmi_multi_rebuild_status(ptmi_multi *m, struct ptmi_rebuild_status *out);
 
+/* ---- moving objects on the device: triangle groups ---------------------------------------------
+ * ptmi_set_triangle_groups tags every uploaded triangle with a group id (one uint32 per triangle, in uploaded order) and snapshots the
+ * REST POSE: v0, v1, v2, n0, n1, n2 of every triangle as they stand on the device now. Every group's matrix becomes "none" and
+ * `transforms` is zeroed. n_groups = the largest id + 1. group NULL or n_triangles 0 removes the table. PTMI_E_INVALID: no scene,
+ * n_triangles different from the uploaded count. PTMI_E_UNSUPPORTED: more than 65 536 groups. A failed call keeps the previous table.
+ * ptmi_upload_scene removes the table; ptmi_rebuild_tree, ptmi_update_materials and ptmi_update_lights leave it alone.
+ * ptmi_transform_groups sets the matrix of each group an op names. Transforms are ABSOLUTE, from the rest pose: every member
+ * triangle's live record becomes T(rest), so a host that composes matrices gets no drift. Groups that are not named keep their
+ * records (they are not rewritten). Per member triangle, in float32, in the order written, no FMA:
+ *   vertex p:  p'_k = ((m[4k] * p.x + m[4k+1] * p.y) + m[4k+2] * p.z) + m[4k+3]                                  k = x, y, z
+ *   normal n:  q_k = (nm[3k] * n.x + nm[3k+1] * n.y) + nm[3k+2] * n.z;  l2 = (q.x * q.x + q.y * q.y) + q.z * q.z;
+ *              n'_k = q_k / sqrt(l2) where l2 > 0 (both correctly rounded), else n' = q
+ * The uvs, material_index and the seven padding words keep their bits. Afterwards the call runs the refit of ptmi_update_triangles:
+ * the state is bit for bit what ptmi_update_triangles(0, n_triangles, the transformed records) leaves (triangle images, light triangles,
+ * both trees, root boxes, image header, quantised_kept, cost_now; ptmi_scene_update_status.updates grows by one), except that while
+ * motion is on the dirty range is widened to [lowest member, highest member] of the groups named only. n_ops = 0, or ops whose groups
+ * have no members, do what ptmi_update_triangles(0, 0, NULL) does. Point and directional lights are NOT moved: that is
+ * ptmi_update_lights' business (an emissive light follows its triangle, as after any triangle update).
+ * All-or-nothing. On the host: PTMI_E_STATE without a table; PTMI_E_INVALID for ops NULL with n_ops > 0, a matrix entry that is not
+ * finite, a non-zero reserved word, group >= n_groups, a group named twice; PTMI_E_UNSUPPORTED where ptmi_update_triangles gives it.
+ * On the device, before anything of the scene is written, a check pass applies ptmi_update_triangles' vertex checks to the
+ * transformed vertices (every component finite; own leaves: a + (b - a) and a + (d - a) finite too). On a failure the call returns
+ * PTMI_E_INVALID, first_bad holds the smallest offending triangle index and the context is otherwise unchanged; on success first_bad
+ * is 0xFFFFFFFF. ptmi_update_triangles while a table is in place re-bases: the records it writes become the rest pose of their
+ * triangles (the groups' matrices stay; they apply to the new rest pose at the next ptmi_transform_groups that names them).
+ * ptmi_normal_matrix (host only, no context): nm = the cofactor matrix of the upper 3 x 3 of m, each entry a*b - c*d in double in
+ * that order, rounded to float. It handles non-uniform scale; a mirror flips the normals with the winding. */
+typedef struct ptmi_group_transform {
+    uint32_t group;
+    uint32_t reserved0;      /* must be 0 */
+    float    m[12];          /* 3 x 4 affine, row-major: row k = m[4k .. 4k+3] */
+    float    nm[9];          /* 3 x 3 applied to the normals, row-major */
+    uint32_t reserved1;      /* must be 0 */
+} ptmi_group_transform;      /* 96 bytes */
+struct ptmi_transform_status {        /* a struct tag only; 32 bytes. Without a table every word is zero. */
+    uint32_t present, n_groups;       /* a table is in place; the largest id + 1 */
+    uint32_t transforms;              /* successful ptmi_transform_groups calls since the table was set */
+    uint32_t last_moved;              /* member triangles the last of them rewrote */
+    uint32_t first_bad, reserved;     /* the last call's check pass: the smallest offending triangle, 0xFFFFFFFF for none */
+    double   transform_ms;            /* wall time of the last successful ptmi_transform_groups, its refit included */
+};
+int ptmi_set_triangle_groups(ptmi_ctx *ctx, const uint32_t *group, uint32_t n_triangles);
+int ptmi_transform_groups(ptmi_ctx *ctx, const ptmi_group_transform *ops, uint32_t n_ops);
+void ptmi_normal_matrix(const float m[12], float nm[9]);
+int ptmi_transform_status(ptmi_ctx *ctx, struct ptmi_transform_status *out);
+/* the live records [first, first + count) as they stand on the device; synchronises. PTMI_E_INVALID: no scene, a range beyond the
+ * uploaded count, count > 0 with out NULL */
+int ptmi_debug_read_triangles(ptmi_ctx *ctx, uint32_t first, uint32_t count, ptmi_triangle *out);
+/* on every device, checked once before any device changes; the status of device 0 */
+int ptmi_multi_set_triangle_groups(ptmi_multi *m, const uint32_t *group, uint32_t n_triangles);
+int ptmi_multi_transform_groups(ptmi_multi *m, const ptmi_group_transform *ops, uint32_t n_ops);
+int ptmi_multi_transform_status(ptmi_multi *m, struct ptmi_transform_status *out);
+
 /* ---- alpha cutouts ---------------------------------------------------------------------------
  * A per-material cutoff table for the loaded scene, one float per uploaded material. cutoff = 0: the material is opaque (the state of
  * every material without a table). cutoff > 0: a hit on the material is NOT THERE where the alpha of its albedo map's texel at the hit

@@ -11,10 +11,12 @@
 //   alpha.hip          alpha cutouts: the cutoff table, the two resolve loops between the existing kernels, their debug entry points
 //   scene_rebuild.hip  the walked own-leaf tree rebuilt in place: the unit list on the device, the swap (ptmi_rebuild_tree)
 //   motion.hip         reprojection across a geometry edit: the previous positions, their commit, the motion plane (ptmi_set_motion)
+//   scene_transform.hip  triangle groups moved by matrix on the device: the table, the rest pose, the check and write passes
 #pragma once
 #include "ptmi.h"
 #include "pt_device.h"
 
+#include <chrono>
 #include <cstddef>
 #include <cstdint>
 #include <deque>
@@ -52,6 +54,10 @@ int pt_ctx_device(const ptmi_ctx *c);
 int pt_ctx_cus(const ptmi_ctx *c);
 // the argument and state checks of ptmi_rebuild_tree (scene_rebuild.hip), which change nothing: its error codes, the reason in err
 int pt_check_rebuild(const ptmi_ctx *c, const ptmi_rebuild_params *params, std::string &err);
+// the argument and state checks of ptmi_set_triangle_groups and ptmi_transform_groups that run on the host (scene_transform.hip), which
+// change nothing: their error codes, the reason in err. *n_groups_out (may be NULL): the largest id + 1.
+int pt_check_triangle_groups(const ptmi_ctx *c, const uint32_t *group, uint32_t n_triangles, uint32_t *n_groups_out, std::string &err);
+int pt_check_group_transforms(const ptmi_ctx *c, const ptmi_group_transform *ops, uint32_t n_ops, std::string &err);
 // Adaptive rounds driven from outside, one at a time (ptmi_multi_dispatch_adaptive with neighbourhood = 1; dispatch.hip).
 // pt_adaptive_check: everything ptmi_dispatch_adaptive checks before it enqueues, with its error codes; *ap = the params with their defaults.
 int pt_adaptive_check(ptmi_ctx *c, const ptmi_camera *cam, const ptmi_adaptive_params *params, ptmi_adaptive_params *ap);
@@ -85,6 +91,11 @@ enum SceneBuf {
     kPlanWords,                        // the reduction words of one update and the partial sums of the cost
     kAlphaCutoff,                      // the per-material cutoff table of ptmi_set_alpha_cutoff (alpha.hip); gone with the next upload
     kMotionPrev,                       // the previous positions of ptmi_set_motion (motion.hip): 3 float4 per triangle; re-made by an upload
+    // triangle groups (ptmi_set_triangle_groups; scene_transform.hip), gone with the next upload:
+    kGroupTab,                         // one group id per uploaded triangle
+    kGroupRest,                        // the rest pose: v0, v1, v2, n0, n1, n2 of every triangle, 6 float4 each
+    kGroupOps,                         // the op records of the ptmi_transform_groups call at hand (grown on demand)
+    kGroupMap,                         // 4 words (word 0: the smallest offending triangle of the check pass), then group -> op index
     kSceneBufs
 };
 
@@ -186,6 +197,15 @@ struct ptmi_ctx {
     uint32_t motion_epochs = 0;                        // commits since the last upload or ptmi_set_motion(1)
     uint32_t motion_dirty_first = 0, motion_dirty_count = 0;   // the union of the ranges updated since the last commit (0, 0: none)
 
+    // triangle groups (ptmi_set_triangle_groups; scene_transform.hip): the table is buf[kGroupTab], the rest pose buf[kGroupRest]
+    bool grp_present = false;
+    size_t grp_ops_cap = 0;                            // op records buf[kGroupOps] has room for
+    std::vector<uint32_t> grp_lo, grp_hi, grp_members; // per group: its lowest and highest member (lo > hi: none), how many it has
+    std::vector<uint32_t> grp_map;                     // the host's copy of buf[kGroupMap], all "not named" between calls
+    std::vector<uint8_t> grp_moved;                    // per group: a matrix is set (mats below holds it)
+    std::vector<ptmi_group_transform> grp_mats;        // per group: its current matrix
+    struct ptmi_transform_status tf{};                 // what ptmi_transform_status reports
+
     // output (binding 0)
     uint32_t W = 0, H = 0;
     void *plane[kFramePlanes] = {};                    // indexed by FramePlane, W x H pixels each (absent: NULL)
@@ -243,6 +263,18 @@ hipError_t quiesce(ptmi_ctx *c);
 void drop_plan(ptmi_ctx *c);
 int make_plan(ptmi_ctx *c);
 int walked_cost(ptmi_ctx *c, double &cost);
+// What ptmi_update_triangles and ptmi_transform_groups share around the write of the records. refit_begin: the tree must be one a refit
+// can serve (PTMI_E_UNSUPPORTED otherwise, nothing touched). refit_ready: waits for the work in flight and makes the plan at the first
+// edit after an upload. refit_written: everything behind the write - the triangle images, the light triangles, both trees, the root
+// boxes, the header, the cost and the status (updates grows by one; refit_ms counts from t0, when the entry point was entered).
+int refit_begin(ptmi_ctx *c);
+int refit_ready(ptmi_ctx *c);
+int refit_written(ptmi_ctx *c, std::chrono::steady_clock::time_point t0);
+
+// scene_transform.hip: the table goes with its scene (ptmi_upload_scene; the buffers have gone with the others); records
+// [first, first + count) that ptmi_update_triangles has just written become the rest pose of their triangles, on c's stream
+void groups_forget(ptmi_ctx *c);
+int groups_rebase(ptmi_ctx *c, uint32_t first, uint32_t count);
 
 // scene_image.hip: the own-leaf image of the loaded scene built anew from what is on the device (ptmi_rebuild_tree), by the code an
 // upload builds it with. d_which: the unit list (n_units entries, device memory). buf: new device buffers for the entries a rebuild

@@ -534,6 +534,29 @@ int ptmi_multi_rebuild_status(ptmi_multi *m, struct ptmi_rebuild_status *out) {
     return rc ? cfail(m, 0, rc, "ptmi_rebuild_status") : PTMI_OK;
 }
 
+// Triangle groups on every device (scene_transform.hip). The host-side checks run once, on device 0's context, before any device
+// changes; every device holds the same triangles and the same table, so the check pass on the device refuses on the first device or
+// on none.
+int ptmi_multi_set_triangle_groups(ptmi_multi *m, const uint32_t *group, uint32_t n_triangles) {
+    if (!m) return PTMI_E_INVALID;
+    std::string why;
+    const int rc = pt_check_triangle_groups(m->d[0].ctx, group, n_triangles, nullptr, why);
+    if (rc) return mfail(m, rc, "%s", why.c_str());
+    return each_ctx(m, "ptmi_set_triangle_groups", ptmi_set_triangle_groups, group, n_triangles);
+}
+int ptmi_multi_transform_groups(ptmi_multi *m, const ptmi_group_transform *ops, uint32_t n_ops) {
+    if (!m) return PTMI_E_INVALID;
+    std::string why;
+    const int rc = pt_check_group_transforms(m->d[0].ctx, ops, n_ops, why);
+    if (rc) return mfail(m, rc, "%s", why.c_str());
+    return each_ctx(m, "ptmi_transform_groups", ptmi_transform_groups, ops, n_ops);
+}
+int ptmi_multi_transform_status(ptmi_multi *m, struct ptmi_transform_status *out) {
+    if (!m || !out) return PTMI_E_INVALID;
+    const int rc = ptmi_transform_status(m->d[0].ctx, out);
+    return rc ? cfail(m, 0, rc, "ptmi_transform_status") : PTMI_OK;
+}
+
 int ptmi_multi_resize(ptmi_multi *m, uint32_t w, uint32_t h) {
     if (!m) return PTMI_E_INVALID;
     int rc = each_ctx(m, "ptmi_resize", ptmi_resize, w, h);

@@ -425,34 +425,31 @@ int refresh_light_tris(ptmi_ctx *c) {
 
 }  // namespace
 
-extern "C" {
+// the edit of the triangles in three steps around the write of the records: shared with scene_transform.hip (ptmi_ctx.h)
+PT_HOST {
 
-int ptmi_update_triangles(ptmi_ctx *c, uint32_t first, uint32_t count, const ptmi_triangle *tris) {
-    if (!c) return PTMI_E_INVALID;
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc = check_range(c, "triangles", first, count, c->sc.n_tris, tris);
-    if (rc) return rc;
+int refit_begin(ptmi_ctx *c) {
     if (c->n_ref_wnodes && !c->tree_nested)
         return fail(c, PTMI_E_UNSUPPORTED, "the uploaded tree is not nested and finite: it is walked as uploaded, and a refit would change what its boxes mean");
-    const bool own = c->sc.own != 0;
-    for (uint32_t i = 0; i < count; i++)
-        for (int k = 0; k < 3; k++) {
-            const float a = tris[i].v0[k], b = tris[i].v1[k], d = tris[i].v2[k];
-            if (!std::isfinite(a) || !std::isfinite(b) || !std::isfinite(d))
-                return fail(c, PTMI_E_INVALID, "triangle %u has a vertex that is not finite", first + i);
-            if (own && (!std::isfinite(a + (b - a)) || !std::isfinite(a + (d - a))))
-                return fail(c, PTMI_E_INVALID, "triangle %u: an edge is too long for float32 arithmetic", first + i);
-        }
+    return PTMI_OK;
+}
+
+int refit_ready(ptmi_ctx *c) {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, sync_all(c));                                    // nothing in flight reads the scene any more
+    int rc;
     if (!c->upd_planned && (rc = make_plan(c))) { drop_plan(c); return rc; }
+    return PTMI_OK;
+}
+
+int refit_written(ptmi_ctx *c, std::chrono::steady_clock::time_point t0) {
+    int rc;
+    const bool own = c->sc.own != 0;
     const uint32_t nt = c->sc.n_tris;
     if (nt == 0) { c->upd.updates++; return PTMI_OK; }
     hipStream_t st = c->stream;
     void *const *d = c->buf;
     Words *red = buf_as<Words>(c, kPlanWords);
-    if (count) HIP_TRY(c, hipMemcpy(static_cast<ptmi_triangle *>(d[kTris]) + first, tris, (size_t)count * sizeof(ptmi_triangle), hipMemcpyHostToDevice));
-    motion_widen(c, first, count);                              // while motion is on: the previous positions stay, the dirty range grows
     {
         Words w0{};
         for (int k = 0; k < 3; k++) { w0.umin[k] = w0.qmin[k] = 0xFFFFFFFFu; w0.umax[k] = w0.qmax[k] = 0u; }
@@ -545,6 +542,33 @@ int ptmi_update_triangles(ptmi_ctx *c, uint32_t first, uint32_t count, const ptm
     c->upd.updates++;
     c->upd.refit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return PTMI_OK;
+}
+
+}  // namespace pt_host
+
+extern "C" {
+
+int ptmi_update_triangles(ptmi_ctx *c, uint32_t first, uint32_t count, const ptmi_triangle *tris) {
+    if (!c) return PTMI_E_INVALID;
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = check_range(c, "triangles", first, count, c->sc.n_tris, tris);
+    if (rc || (rc = refit_begin(c))) return rc;
+    const bool own = c->sc.own != 0;
+    for (uint32_t i = 0; i < count; i++)
+        for (int k = 0; k < 3; k++) {
+            const float a = tris[i].v0[k], b = tris[i].v1[k], d = tris[i].v2[k];
+            if (!std::isfinite(a) || !std::isfinite(b) || !std::isfinite(d))
+                return fail(c, PTMI_E_INVALID, "triangle %u has a vertex that is not finite", first + i);
+            if (own && (!std::isfinite(a + (b - a)) || !std::isfinite(a + (d - a))))
+                return fail(c, PTMI_E_INVALID, "triangle %u: an edge is too long for float32 arithmetic", first + i);
+        }
+    if ((rc = refit_ready(c))) return rc;
+    if (count) {
+        HIP_TRY(c, hipMemcpy(static_cast<ptmi_triangle *>(c->buf[kTris]) + first, tris, (size_t)count * sizeof(ptmi_triangle), hipMemcpyHostToDevice));
+        motion_widen(c, first, count);                          // while motion is on: the previous positions stay, the dirty range grows
+        if ((rc = groups_rebase(c, first, count))) return rc;   // while a group table is in place: these records are their triangles' rest pose
+    }
+    return refit_written(c, t0);
 }
 
 int ptmi_update_materials(ptmi_ctx *c, uint32_t first, uint32_t count, const ptmi_material *mats) {

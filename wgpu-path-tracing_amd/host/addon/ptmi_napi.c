@@ -325,6 +325,63 @@ static napi_value js_scene_update_status(napi_env env, napi_callback_info info) 
     return out;
 }
 
+/* setTriangleGroups(handle, Uint32Array | null): ptmi_set_triangle_groups; one id per uploaded triangle, null removes the table */
+static napi_value js_set_triangle_groups(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    handle *h = get_handle(env, info, 2, argv);
+    if (!h) return NULL;
+    void *p; size_t n;
+    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
+    if (n % sizeof(uint32_t)) { napi_throw_range_error(env, NULL, "the group table is not whole uint32 words"); return NULL; }
+    CALL(env, h, set_triangle_groups, (const uint32_t *)p, (uint32_t)(n / sizeof(uint32_t)));
+    return NULL;
+}
+
+/* transformGroups(handle, blob): ptmi_transform_groups; the blob holds whole 96-byte ptmi_group_transform records */
+static napi_value js_transform_groups(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    handle *h = get_handle(env, info, 2, argv);
+    if (!h) return NULL;
+    void *p; size_t n;
+    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
+    if (n % sizeof(ptmi_group_transform)) { napi_throw_range_error(env, NULL, "blob length is not a multiple of 96 bytes"); return NULL; }
+    CALL(env, h, transform_groups, (const ptmi_group_transform *)p, (uint32_t)(n / sizeof(ptmi_group_transform)));
+    return NULL;
+}
+
+/* normalMatrix(handle, Float32Array(12) m, Float32Array(9) out): ptmi_normal_matrix. The library function needs no context; the handle
+ * is asked for like everywhere else, so that every export but the constructors takes one. */
+static napi_value js_normal_matrix(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    if (!get_handle(env, info, 3, argv)) return NULL;
+    void *m, *nm; size_t nm_bytes, m_bytes;
+    if (!get_bytes(env, argv[1], &m, &m_bytes) || !get_bytes(env, argv[2], &nm, &nm_bytes)) return NULL;
+    if (m_bytes != 12 * sizeof(float) || nm_bytes != 9 * sizeof(float)) {
+        napi_throw_range_error(env, NULL, "normalMatrix: expected a Float32Array(12) and a Float32Array(9)");
+        return NULL;
+    }
+    ptmi_normal_matrix((const float *)m, (float *)nm);
+    return NULL;
+}
+
+/* transformStatus(handle) -> {present, nGroups, transforms, lastMoved, firstBad, transformMs} */
+static napi_value js_transform_status(napi_env env, napi_callback_info info) {
+    napi_value argv[1], out, v;
+    handle *h = get_handle(env, info, 1, argv);
+    if (!h) return NULL;
+    struct ptmi_transform_status st;
+    CALL(env, h, transform_status, &st);
+    NAPI_OK(env, napi_create_object(env, &out));
+    const struct { const char *name; double value; } num[] = {
+        {"present", st.present}, {"nGroups", st.n_groups}, {"transforms", st.transforms}, {"lastMoved", st.last_moved},
+        {"firstBad", st.first_bad}, {"transformMs", st.transform_ms}};
+    for (size_t i = 0; i < sizeof num / sizeof num[0]; i++) {
+        NAPI_OK(env, napi_create_double(env, num[i].value, &v));
+        NAPI_OK(env, napi_set_named_property(env, out, num[i].name, v));
+    }
+    return out;
+}
+
 /* rebuildStatus(handle) -> {rebuilds, builderUsed, buildMs, costBefore, costAfter} */
 static napi_value js_rebuild_status(napi_env env, napi_callback_info info) {
     napi_value argv[1], out, v;
@@ -912,6 +969,8 @@ static napi_value init(napi_env env, napi_value exports) {
         {"abiVersion", js_abi_version}, {"create", js_create}, {"multiCreate", js_multi_create}, {"destroy", js_destroy},
         {"uploadScene", js_upload_scene}, {"uploadAtlas", js_upload_atlas}, {"uploadEnvironment", js_upload_environment}, {"setMedium", js_set_medium}, {"uploadMediumDensity", js_upload_medium_density},
         {"updateTriangles", js_update_triangles}, {"updateMaterials", js_update_materials}, {"updateLights", js_update_lights}, {"sceneUpdateStatus", js_scene_update_status},
+        {"setTriangleGroups", js_set_triangle_groups}, {"transformGroups", js_transform_groups}, {"transformStatus", js_transform_status},
+        {"normalMatrix", js_normal_matrix},
         {"rebuildTree", js_rebuild_tree}, {"rebuildStatus", js_rebuild_status},
         {"setAlphaCutoff", js_set_alpha_cutoff}, {"alphaStatus", js_alpha_status},
         {"resize", js_resize}, {"setOptions", js_set_options},

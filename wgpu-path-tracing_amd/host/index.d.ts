@@ -86,6 +86,15 @@ export class Renderer {
   updateMaterials(first: number, blob: ArrayBuffer | ArrayBufferView): void;
   updateLights(first: number, blob: ArrayBuffer | ArrayBufferView): void;
   sceneUpdateStatus(): SceneUpdateStatus;
+  /** tags every triangle of the loaded scene with a group id, in the uploaded order, and snapshots the rest pose (include/ptmi.h
+   *  ptmi_set_triangle_groups); null removes the table. loadModel of a .glb sets the node index of every triangle. */
+  setTriangleGroups(groups: Uint32Array | null): void;
+  /** sets the matrices of the groups named (ptmi_transform_groups): every member triangle becomes T(rest pose), absolute, and the
+   *  trees are refitted on the device. matrix: 12 numbers, a 3 x 4 row-major affine; normalMatrix: 9 numbers, derived through
+   *  ptmi_normal_matrix (the cofactors of the upper 3 x 3) when absent. What follows is what follows updateTriangles, rebuildAbove
+   *  included. A refused call throws and changes nothing. */
+  transformGroups(ops: Array<{ group: number; matrix: ArrayLike<number>; normalMatrix?: ArrayLike<number> }>): void;
+  transformStatus(): TransformStatus;
   /** builds the walked own-leaf tree anew from the triangles as they stand on the device and swaps it in (include/ptmi.h
    *  ptmi_rebuild_tree): the image a fresh loadModel of the edited scene would build, with the triangle order, the tables, the alpha
    *  table, the motion state and every plane left alone. builder: 1 the host's, 2 (default) the device's where it applies. The hits
@@ -176,6 +185,12 @@ export interface MediumOptions {
 export interface AlphaStatus {
   present: number; materials: number; cutout: number; maxLayers: number;
   pathPasses: number; pathExhausted: number; shadowPasses: number; shadowExhausted: number;
+}
+/** ptmi_transform_status: the group table in place and the transforms since it was set */
+export interface TransformStatus {
+  present: number; nGroups: number; transforms: number; lastMoved: number;
+  /** the last call's check pass: the smallest offending triangle, 0xFFFFFFFF for none */
+  firstBad: number; transformMs: number;
 }
 /** ptmi_scene_update_status: the triangle updates since the scene was loaded */
 export interface SceneUpdateStatus {

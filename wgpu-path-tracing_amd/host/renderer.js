@@ -86,16 +86,18 @@ Renderer.prototype.addOnUpdate = function (callback) { this.onUpdateTasks.push(c
 Renderer.prototype.loadModel = function (model, atlas) {
   var self = this;
   return new Promise(function (resolve) {
-    var blobs, cutoff = null;
+    var blobs, cutoff = null, groups = null;
     if (typeof model === 'string' && /\.glb$/i.test(model)) {
       var prepared = require('./scene_prep').prepareScene(require('./gltf').loadGLB(model), { alphaCutout: self.alphaCutout });
       blobs = prepared.blobs; atlas = atlas || prepared.atlas; self.sceneInfo = prepared;
       cutoff = prepared.alphaCutoff || null;
+      groups = prepared.triangleGroups || null;
     } else if (typeof model === 'string') {
       var f = sceneFile.readSceneFile(model);
       blobs = f.blobs; atlas = atlas || f.atlas;
     } else if (model.blobs) {
       blobs = model.blobs; atlas = atlas || model.atlas;
+      groups = model.triangleGroups || null;                            // what prepareScene returned: a triangle's glTF node
       if (self.alphaCutout) cutoff = model.alphaCutoff || null;         // what prepareScene({alphaCutout: true}) returned
     } else {
       blobs = pack.packScene(model);
@@ -106,6 +108,8 @@ Renderer.prototype.loadModel = function (model, atlas) {
     else self.addon.uploadAtlas(self.ctx, null, 0, 0, 0);
     // (the upload removed any table: it belonged to the old scene's materials)
     if (cutoff) self.addon.setAlphaCutoff(self.ctx, cutoff, self.alphaLayers);
+    // ... and any group table: a .glb's triangles are tagged with the node they came from (transformGroups moves a node by matrix)
+    if (groups && groups.length) self.addon.setTriangleGroups(self.ctx, groups);
     self.sceneLoaded = true;
     self.resetOutputBuffer(false);
     resolve();
@@ -251,6 +255,10 @@ Renderer.prototype.setMedium = function (medium) {
 Renderer.prototype.updateTriangles = function (first, blob) {
   if (!this.sceneLoaded) throw new Error('updateTriangles: needs a loaded scene (loadModel)');
   this.addon.updateTriangles(this.ctx, first, blob);
+  this._trianglesEdited();
+};
+/** what follows every edit of the triangles: the scene bounds, the accumulation, the rebuild above options.rebuildAbove */
+Renderer.prototype._trianglesEdited = function () {
   var st = this.addon.sceneUpdateStatus(this.ctx);
   if (this.sceneBounds) this.sceneBounds = { min: st.rootMin, max: st.rootMax };
   if (this.motion && this.reproject && this.adaptive && this.frameIndex > 0 && this.accumulatedUnder) {
@@ -271,6 +279,41 @@ Renderer.prototype.updateLights = function (first, blob) {
   if (!this.sceneLoaded) throw new Error('updateLights: needs a loaded scene (loadModel)');
   this.addon.updateLights(this.ctx, first, blob);
   this.frameIndex = 0;
+};
+/**
+ * Objects moved on the device (include/ptmi.h ptmi_set_triangle_groups / ptmi_transform_groups). setTriangleGroups tags every triangle
+ * of the loaded scene with a group id (a Uint32Array in the uploaded order; null removes the table) and snapshots the rest pose;
+ * loadModel of a .glb does it with the index of the node each triangle came from (scene.triangleGroups). transformGroups sets
+ * matrices: [{ group, matrix (12 numbers: a 3 x 4 row-major affine), normalMatrix? (9 numbers; derived through ptmi_normal_matrix
+ * when absent) }]. Transforms are absolute, from the rest pose; 96 bytes per group cross the bus. What follows is what follows
+ * updateTriangles: bounds, accumulation (kept under setMotion with setReproject and adaptive rounds), options.rebuildAbove.
+ * A refused call throws and changes nothing.
+ */
+Renderer.prototype.setTriangleGroups = function (groups) {
+  if (groups && !(groups instanceof Uint32Array)) throw new TypeError('setTriangleGroups: groups must be a Uint32Array or null');
+  if (!this.sceneLoaded) throw new Error('setTriangleGroups: needs a loaded scene (loadModel)');
+  this.addon.setTriangleGroups(this.ctx, groups || null);
+};
+Renderer.prototype.transformGroups = function (ops) {
+  if (!this.sceneLoaded) throw new Error('transformGroups: needs a loaded scene (loadModel)');
+  var blob = new ArrayBuffer(96 * ops.length), u32 = new Uint32Array(blob), f32 = new Float32Array(blob);
+  for (var i = 0; i < ops.length; i++) {
+    var op = ops[i], m = Float32Array.from(op.matrix), nm = new Float32Array(9);
+    if (m.length !== 12) throw new RangeError('transformGroups: matrix must hold 12 numbers (3 x 4, row-major)');
+    if (op.normalMatrix) {
+      if (op.normalMatrix.length !== 9) throw new RangeError('transformGroups: normalMatrix must hold 9 numbers');
+      nm.set(op.normalMatrix);
+    } else this.addon.normalMatrix(this.ctx, m, nm);
+    u32[24 * i] = op.group;
+    f32.set(m, 24 * i + 2);
+    f32.set(nm, 24 * i + 14);
+  }
+  this.addon.transformGroups(this.ctx, blob);
+  this._trianglesEdited();
+};
+/** { present, nGroups, transforms, lastMoved, firstBad, transformMs } of the group table in place */
+Renderer.prototype.transformStatus = function () {
+  return this.addon.transformStatus(this.ctx);
 };
 /** { updates, quantisedKept, planMs, refitMs, costBuilt, costNow, rootMin, rootMax } of the triangle updates since loadModel */
 Renderer.prototype.sceneUpdateStatus = function () {

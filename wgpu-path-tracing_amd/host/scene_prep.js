@@ -76,7 +76,7 @@ function buildTriangles(position, normal, uv, index) {
 }
 
 /** gpu.ts:194-299 */
-function processNode(gltf, node, allTriangles, allMaterials, allLights, world, atlas) {
+function processNode(gltf, node, allTriangles, allMaterials, allLights, world, atlas, nodeIndex) {
   var normalMat = M.transpose(M.inverse(world));
   if (node.light !== undefined) {
     var light = gltf.lights[node.light];
@@ -102,7 +102,7 @@ function processNode(gltf, node, allTriangles, allMaterials, allLights, world, a
       }
       var tris = buildTriangles(tp, tn, uv, prim.indices ? prim.indices.value : undefined);
       allMaterials.push(buildMaterial(prim.material, atlas));
-      tris.forEach(function (t) { t.materialIndex = allMaterials.length - 1; allTriangles.push(t); });
+      tris.forEach(function (t) { t.materialIndex = allMaterials.length - 1; t.group = nodeIndex; allTriangles.push(t); });
     });
   }
 }
@@ -114,7 +114,23 @@ function alphaCutoffOf(material) {
   return material.alphaCutoff === undefined || material.alphaCutoff === null ? 0.5 : material.alphaCutoff;
 }
 
-/** loader.ts:20-40 + gpu.ts:67-150 -> { blobs, atlas, counts, bvhDepth }. opts.alphaCutout: the atlas keeps the alpha of albedo maps
+/** Tags every packed triangle with its group in the padding word at byte 124 (_p6), for the BVH build to carry along: the builder
+ *  moves whole 128-byte records (csrc/scene/scene_prep.cpp: std::swap and assignment of ptmi_triangle values, one memcpy of whole
+ *  records per split), so the word arrives with its triangle. */
+function tagGroups(triangles, allTriangles) {
+  var u = new Uint32Array(triangles);
+  for (var i = 0; i < allTriangles.length; i++) u[i * 32 + 31] = allTriangles[i].group >>> 0;
+}
+/** ... and reads the tags back in the reordered order, zeroing the words again: the blob is then the bytes it is without tags */
+function untagGroups(triangles) {
+  var u = new Uint32Array(triangles), groups = new Uint32Array(u.length / 32);
+  for (var i = 0; i < groups.length; i++) { groups[i] = u[i * 32 + 31]; u[i * 32 + 31] = 0; }
+  return groups;
+}
+
+/** loader.ts:20-40 + gpu.ts:67-150 -> { blobs, atlas, counts, bvhDepth, triangleGroups, groupNames }: triangleGroups holds, per
+ *  triangle in the uploaded (reordered) order, the index of the glTF node it came from (Renderer.setTriangleGroups), groupNames
+ *  the nodes' names by that index (opts.triangleGroups === false: neither). opts.alphaCutout: the atlas keeps the alpha of albedo maps
  *  and the result carries alphaCutoff, a Float32Array with one cutoff per packed material (else: neither, and every byte as without) */
 function prepareScene(gltf, opts) {
   var alphaCutout = !!(opts && opts.alphaCutout);
@@ -129,8 +145,8 @@ function prepareScene(gltf, opts) {
     while (parent.has(cur)) { cur = parent.get(cur); M.mul(extractNodeMatrix(cur), w, w); }
     world.set(node, w);
   });
-  gltf.nodes.forEach(function (node) {
-    processNode(gltf, node, allTriangles, allMaterials, allLights, world.get(node), packed.materials);
+  gltf.nodes.forEach(function (node, nodeIndex) {
+    processNode(gltf, node, allTriangles, allMaterials, allLights, world.get(node), packed.materials, nodeIndex);
     // one material per primitive, in the order processNode packs them
     if (alphaCutout && node.mesh) node.mesh.primitives.forEach(function (prim) { allCutoffs.push(alphaCutoffOf(prim.material)); });
   });
@@ -138,11 +154,16 @@ function prepareScene(gltf, opts) {
   var triangles = pack.packTriangles(allTriangles);             // sorted in place by the BVH build
   var materials = pack.packMaterials(allMaterials);
   var a = addon();
+  var grouped = !(opts && opts.triangleGroups === false);       // false: no tags at all, and no table in the result
+  if (grouped) tagGroups(triangles, allTriangles);
   var bvh = a.buildBvh(triangles);
+  var triangleGroups = grouped ? untagGroups(triangles) : undefined;
   var lights = a.emissiveLights(triangles, materials, pack.packLights(allLights));
   return {
     blobs: { triangles: triangles, materials: materials, bvhNodes: bvh.nodes, lights: lights },
     alphaCutoff: alphaCutout ? new Float32Array(allCutoffs) : undefined,
+    triangleGroups: triangleGroups,
+    groupNames: grouped ? gltf.nodes.map(function (n, i) { return n.name || 'node' + i; }) : undefined,
     atlas: packed.texture,
     counts: { triangles: allTriangles.length, materials: allMaterials.length, bvhNodes: bvh.nodes.byteLength / pack.BVH_NODE_SIZE,
       lights: lights.byteLength / pack.LIGHT_SIZE, punctualLights: allLights.length },

@@ -49,6 +49,8 @@ EXPORTS = [
     "ptmi_rebuild_tree", "ptmi_rebuild_status", "ptmi_multi_rebuild_tree", "ptmi_multi_rebuild_status",
     "ptmi_set_alpha_cutoff", "ptmi_alpha_status", "ptmi_multi_set_alpha_cutoff", "ptmi_multi_alpha_status",
     "ptmi_debug_alpha_intersect", "ptmi_debug_alpha_occluded",
+    "ptmi_set_triangle_groups", "ptmi_transform_groups", "ptmi_transform_status", "ptmi_normal_matrix", "ptmi_debug_read_triangles",
+    "ptmi_multi_set_triangle_groups", "ptmi_multi_transform_groups", "ptmi_multi_transform_status",
 ]
 MULTI_LOOPBACK = 1
 MULTI_PLANE_MOMENTS, MULTI_PLANE_OUTPUT = 0x100, 0x200      # gather_planes: with the AOV_* bits
@@ -186,6 +188,26 @@ class RebuildStatus(ctypes.Structure):
                 "cost_before": float(self.cost_before), "cost_after": float(self.cost_after)}
 
 
+class GroupTransform(ctypes.Structure):
+    """ptmi_group_transform: the matrix of one triangle group (include/ptmi.h ptmi_transform_groups)"""
+    _fields_ = [("group", ctypes.c_uint32), ("reserved0", ctypes.c_uint32), ("m", ctypes.c_float * 12), ("nm", ctypes.c_float * 9),
+                ("reserved1", ctypes.c_uint32)]
+
+
+GROUP_TRANSFORM = np.dtype([("group", "<u4"), ("reserved0", "<u4"), ("m", "<f4", (12,)), ("nm", "<f4", (9,)), ("reserved1", "<u4")])
+
+
+class TransformStatus(ctypes.Structure):
+    """struct ptmi_transform_status: the group table in place and the transforms since it was set (include/ptmi.h)"""
+    _fields_ = [("present", ctypes.c_uint32), ("n_groups", ctypes.c_uint32), ("transforms", ctypes.c_uint32),
+                ("last_moved", ctypes.c_uint32), ("first_bad", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("transform_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {"present": int(self.present), "n_groups": int(self.n_groups), "transforms": int(self.transforms),
+                "last_moved": int(self.last_moved), "first_bad": int(self.first_bad), "transform_ms": float(self.transform_ms)}
+
+
 class AlphaParams(ctypes.Structure):
     """ptmi_alpha_params; max_layers 0 picks the default (include/ptmi.h)"""
     _fields_ = [("max_layers", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
@@ -245,6 +267,8 @@ _SHARED = {
     "scene_update_status": [ctypes.c_void_p],
     "rebuild_tree": [ctypes.c_void_p], "rebuild_status": [ctypes.c_void_p],
     "set_alpha_cutoff": [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p], "alpha_status": [ctypes.c_void_p],
+    "set_triangle_groups": [ctypes.c_void_p, ctypes.c_uint32], "transform_groups": [ctypes.c_void_p, ctypes.c_uint32],
+    "transform_status": [ctypes.c_void_p],
 }
 _lib = None
 
@@ -316,6 +340,9 @@ def load():
         L.ptmi_debug_medium_track.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
         L.ptmi_debug_alpha_intersect.argtypes = [vp, u32, vp, vp, vp, vp, vp]
         L.ptmi_debug_alpha_occluded.argtypes = [vp, u32, vp, vp, vp, vp, vp]
+        L.ptmi_normal_matrix.restype = None
+        L.ptmi_normal_matrix.argtypes = [vp, vp]
+        L.ptmi_debug_read_triangles.argtypes = [vp, u32, u32, vp]
         _lib = L
     return _lib
 
@@ -334,6 +361,28 @@ def image_stats(scene):
     keys = ("wide_nodes", "leaves", "depth", "quantised_nodes", "stream_dwords", "containment_violations",
             "mean_area_growth", "stream_mismatches")
     return dict(zip(keys, list(out)))
+
+
+def normal_matrix(m):
+    """Host-only: the 3 x 3 that goes with the 3 x 4 affine m for the normals (include/ptmi.h ptmi_normal_matrix): the cofactors of
+    its upper 3 x 3, as 9 float32, row-major."""
+    m = np.ascontiguousarray(m, np.float32).reshape(12)
+    nm = np.zeros(9, np.float32)
+    load().ptmi_normal_matrix(_p(m), _p(nm))
+    return nm
+
+
+def group_ops(ops):
+    """GROUP_TRANSFORM records from an array of them, or from (group, m[, nm]) tuples; nm None / absent derives it (normal_matrix)"""
+    if isinstance(ops, np.ndarray) and ops.dtype == GROUP_TRANSFORM:
+        return np.ascontiguousarray(ops)
+    out = np.zeros(len(ops), GROUP_TRANSFORM)
+    for i, op in enumerate(ops):
+        g, m, nm = (tuple(op) + (None,))[:3]
+        m = np.asarray(m, np.float32).reshape(12)
+        out[i]["group"], out[i]["m"] = g, m
+        out[i]["nm"] = normal_matrix(m) if nm is None else np.asarray(nm, np.float32).reshape(9)
+    return out
 
 
 def _env_texels(texels):
@@ -519,6 +568,31 @@ class _Handle:
     def rebuild_status(self):
         st = RebuildStatus()
         self._ck(self._c.rebuild_status(self.h, ctypes.byref(st)))
+        return st
+
+    # -- triangle groups moved by matrix on the device (include/ptmi.h ptmi_set_triangle_groups) ------------------------
+    def set_triangle_groups(self, groups, n_triangles=None):
+        """tags every uploaded triangle with a group id (uint32 per triangle, uploaded order) and snapshots the rest pose; None
+        removes the table. n_triangles overrides the array's length (for tests)."""
+        if groups is None:
+            self._ck(self._c.set_triangle_groups(self.h, None, 0))
+            return
+        g = np.ascontiguousarray(groups, np.uint32).reshape(-1)
+        self._ck(self._c.set_triangle_groups(self.h, _p(g), len(g) if n_triangles is None else n_triangles))
+
+    def transform_groups(self, ops, n_ops=None):
+        """sets the matrices of the groups named: every member triangle becomes T(rest pose), and the trees are refitted on the
+        device. ops: GROUP_TRANSFORM records, or (group, m[, nm]) tuples with m a 3 x 4 row-major affine (see group_ops). n_ops
+        overrides the count passed (for tests; ops None then passes NULL)."""
+        if ops is None:
+            self._ck(self._c.transform_groups(self.h, None, n_ops or 0))
+            return
+        rec = group_ops(ops)
+        self._ck(self._c.transform_groups(self.h, _p(rec) if len(rec) else None, len(rec) if n_ops is None else n_ops))
+
+    def transform_status(self):
+        st = TransformStatus()
+        self._ck(self._c.transform_status(self.h, ctypes.byref(st)))
         return st
 
     # -- alpha cutouts (include/ptmi.h ptmi_set_alpha_cutoff) ---------------------------------------------------------
@@ -864,6 +938,14 @@ class Context(_Handle):
         self._ck(self.L.ptmi_debug_medium_track(self.h, n, _p(o), _p(d), _p(t_end), _p(rng), mode, _p(sc), _p(t), _p(v), _p(steps), _p(after)))
         return sc != 0, t, v, steps, after
 
+    def read_triangles(self, first=0, count=None):
+        """the live TRIANGLE records [first, first + count) as they stand on the device (count None: to the end of the upload)"""
+        if count is None:
+            count = self._uploaded_tris - first
+        out = np.zeros(max(count, 0), layout.TRIANGLE)
+        self._ck(self.L.ptmi_debug_read_triangles(self.h, first, count, _p(out) if len(out) else None))
+        return out
+
     def read_image(self):
         """The traversal image the last upload_scene put on the device (include/ptmi.h: ptmi_debug_read_image), as build_image()
         returns it: (info, wnodes, qnodes or None, tripos, leafbox or None)."""
@@ -940,6 +1022,16 @@ class MultiContext(_Handle):
         o.tile_parts = o.tile_part = 0
         if "tile_strip" not in kw:
             o.tile_strip = 0
+
+    def read_triangles(self, i, first=0, count=None):
+        """Context.read_triangles of device i's context (ptmi_multi_context)"""
+        h = self.L.ptmi_multi_context(self.h, i)
+        count = self._uploaded_tris - first if count is None else count
+        out = np.zeros(max(count, 0), layout.TRIANGLE)
+        rc = self.L.ptmi_debug_read_triangles(h, first, count, _p(out) if len(out) else None)
+        if rc != 0:
+            raise PtmiError(rc, self.L.ptmi_last_error(h).decode())
+        return out
 
     def read_image(self, i):
         """Context.read_image of device i's context (ptmi_multi_context)"""
