@@ -122,8 +122,10 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
     if (band.rows == 0) return PTMI_OK;                         // more parts than strips: nothing to render here
     const uint64_t npix = (uint64_t)band.rows * band.width;
     uint32_t F = c->opt.frames_per_batch;
-    // ~128 Mi paths, ~23 GB of state: the last bounces' small queues cost a fixed ~3 ms per batch, so fewer, larger batches
-    // (measured at 1080p, Msamples/s: 32 frames 8 920, 64 frames 9 150 - 9 275, 128 frames 9 270 - 9 310)
+    // ~128 Mi paths, ~23 GB of state: the last bounces' small queues cost a fixed time per batch, so fewer, larger batches
+    // (measured at 1080p, Msamples/s: 32 frames 8 920, 64 frames 9 150 - 9 275, 128 frames 9 270 - 9 310, when that time was ~3 ms.
+    // About 1.2 ms of it, 0.15 ms per launch of `shade`, were the per-wave atomics of its statistics, which the compaction now sums:
+    // a launch of `shade` on a queue of no segments takes ~0.05 ms, not ~0.2; profiles/README.md, "Shade's statistics in the compaction")
     const bool auto_F = F == 0;
     Lane &ln = c->lane;
     if (auto_F) {
@@ -207,7 +209,7 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
                 const uint32_t *q = b == 0 || b == rb + 1 ? nullptr : ln.queue[cur];   // bounce 0 / after the repack: slot i holds path / state i
                 const DevPaths sp = tail ? tp : bp;
                 const int par = side ? (int)(b & 1u) : 0;
-                const ShadeParams shp{b, maxb, c->opt.do_mis, ct, side ? 1u : 0u, tail ? ln.pid : nullptr};
+                const ShadeParams shp{b, maxb, c->opt.do_mis, ln.counts, side ? 1u : 0u, tail ? ln.pid : nullptr};
                 { Timed t(c, kExtend, t2, ms); launch_extend(c, ms, cfg, sp, q, &qlen[b], ln.hits);
                   if (alpha) alpha_resolve_paths(c, ms, cfg, sp, q, &qlen[b], ln.hits, nullptr); }
                 const bool last = b + 1 == maxb;
@@ -217,7 +219,7 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
                       ms, shade_blocks, c->sc, sp, q, &qlen[b], ln.hits, ln.sh[par], ln.alive, ln.shadowm, shp,
                       b == 0 ? aov_rec : nullptr); }
                 { Timed t(c, kCompact, t3, ms);
-                  pt_launch_compact(ms, tiles, q, &qlen[b], ln.alive, nee ? ln.shadowm : nullptr,
+                  pt_launch_compact(ms, tiles, q, &qlen[b], ln.alive, nee ? ln.shadowm : nullptr, ln.counts,
                                     ln.word_off, ln.queue[cur ^ 1], &qlen[b + 1], ln.sq[par], &slen[par],
                                     ct, b, last ? 0 : 1);
                   if (b == rb && !last) pt_launch_repack(ms, blocks, &qlen[b + 1], ln.queue[cur ^ 1], bp, tp, ln.pid); }

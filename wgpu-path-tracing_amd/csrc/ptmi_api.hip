@@ -18,7 +18,8 @@ void vfail(std::string &err, const char *fmt, va_list ap) {
     err = buf;
 }
 
-// what a path of a batch takes in each of the lane's per-path arrays, in bytes
+// what an element of each of the lane's arrays takes, in bytes: a path of the batch in the per-path arrays, then a word per 64 paths,
+// then a compaction tile
 constexpr size_t kLaneBytes[kLaneBufs] = {
     16, 16, 8, 16,                                 // kPathO .. kPathL
     8,                                             // kHits
@@ -29,9 +30,16 @@ constexpr size_t kLaneBytes[kLaneBufs] = {
     32,                                            // kAovRec
     4, 4,                                          // kPathW, kTailW
     16, 16, 4, 4, 8,                               // kAlphaO, kAlphaD, kAlphaList0, kAlphaList1, kAlphaHits
+    8, 8, 4,                                       // kAliveMask, kShadowMask, kShadeCounts: per 64 paths
+    4 * 4,                                         // kTileSums: four totals per tile
 };
-// bytes of device memory a path of a batch takes in ensure_capacity: the per-path arrays and one byte for the two masks (2 x 8 B per 64
-// paths). The automatic batch size and its out-of-memory retry (ptmi_dispatch) rely on it.
+// elements of array k in a batch of `cap` paths
+size_t lane_elements(int k, size_t cap) {
+    return k < kLanePerPath ? cap : k == kTileSums ? cap / pt_compact_tile_slots() + 2 : cap / 64 + 1;
+}
+// bytes of device memory a path of a batch takes in ensure_capacity: the per-path arrays and one byte for the three arrays of words
+// (20 B per 64 paths; the tile totals are 16 B per 65 536). The automatic batch size and its out-of-memory retry (ptmi_dispatch)
+// rely on it.
 // the arrays that exist only while something is on: the first-hit records (aov), the environment's weights (env_w), the alpha resolve
 // loops' arrays (alpha)
 constexpr bool lane_buf_wanted(int k, bool aov, bool env_w, bool alpha) {
@@ -39,7 +47,7 @@ constexpr bool lane_buf_wanted(int k, bool aov, bool env_w, bool alpha) {
 }
 constexpr size_t lane_bytes_per_path(bool aov, bool env_w, bool alpha) {
     size_t n = 1;
-    for (int k = 0; k < kLaneBufs; k++) if (lane_buf_wanted(k, aov, env_w, alpha)) n += kLaneBytes[k];
+    for (int k = 0; k < kLanePerPath; k++) if (lane_buf_wanted(k, aov, env_w, alpha)) n += kLaneBytes[k];
     return n;
 }
 static_assert(lane_bytes_per_path(false, false, false) == 214 && lane_bytes_per_path(true, false, false) == 246 &&
@@ -65,6 +73,7 @@ void lane_views(Lane &ln) {
     at(kPathW, ln.paths.W); at(kTailW, ln.tail.W);
     at(kAlphaO, ln.alpha.RO); at(kAlphaD, ln.alpha.RD); at(kAlphaList0, ln.alpha.list[0]); at(kAlphaList1, ln.alpha.list[1]);
     at(kAlphaHits, ln.alpha.hits);
+    at(kAliveMask, ln.alive); at(kShadowMask, ln.shadowm); at(kShadeCounts, ln.counts); at(kTileSums, ln.word_off);
 }
 }  // namespace pt_host
 
@@ -72,7 +81,6 @@ namespace {
 
 void free_batch(Lane &ln) {
     for (void *&p : ln.buf) dfree(p);
-    dfree(ln.alive); dfree(ln.shadowm); dfree(ln.word_off);
     ln.cap = 0;
     lane_views(ln);
 }
@@ -179,16 +187,11 @@ int ensure_capacity(ptmi_ctx *c, Lane &ln, size_t n) {
     HIP_TRY(c, sync_all(c));
     free_batch(ln);
     const size_t cap = (n + 1023) & ~(size_t)1023;
-    const size_t words = cap / 64 + 1;
-    const size_t tiles = cap / pt_compact_tile_slots() + 2;
     c->alloc_oom = false;
     hipError_t e = hipSuccess;
     size_t bytes = 0;
     for (int k = 0; k < kLaneBufs && e == hipSuccess; k++)
-        if (lane_buf_wanted(k, aov, env_w, alpha)) e = hipMalloc(&ln.buf[k], bytes = cap * kLaneBytes[k]);
-    if (e == hipSuccess) e = hipMalloc(&ln.alive, bytes = words * 8);
-    if (e == hipSuccess) e = hipMalloc(&ln.shadowm, bytes = words * 8);
-    if (e == hipSuccess) e = hipMalloc(&ln.word_off, bytes = 2 * tiles * 4);
+        if (lane_buf_wanted(k, aov, env_w, alpha)) e = hipMalloc(&ln.buf[k], bytes = lane_elements(k, cap) * kLaneBytes[k]);
     if (e != hipSuccess) {
         // a failed allocation leaves the lane empty (not half-built) and the runtime's sticky error cleared; ptmi_dispatch retries
         // with a smaller batch when it chose the size itself
@@ -197,7 +200,6 @@ int ensure_capacity(ptmi_ctx *c, Lane &ln, size_t n) {
         (void)hipGetLastError();
         return fail(c, PTMI_E_HIP, "hipMalloc of %zu bytes for a batch of %zu paths failed: %s", bytes, cap, hipGetErrorString(e));
     }
-    ln.mask_words = words;
     ln.cap = cap;
     lane_views(ln);
     return PTMI_OK;

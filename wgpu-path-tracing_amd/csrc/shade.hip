@@ -432,7 +432,7 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
     }
     const lds_f4p lds_lights = (lds_f4p)smem + mats_q;
     const ShadeTabs<STAGE> tabs{(lds_f4p)smem, lds_lights, lds_lights + 3u * sc.n_lights};
-    uint32_t n_skipped = 0, n_emitted = 0;  // lane 0 of each wave: one atomic per wave at the end
+    uint32_t *__restrict__ const count_words = sp.counts;
     for (uint32_t base = blockIdx.x * SBLOCK; base < count; base += gridDim.x * SBLOCK) {
         const uint32_t i = base + threadIdx.x;
         bool alive = false, shadow = false, skipped = false, emitted = false;
@@ -609,12 +609,9 @@ __global__ __launch_bounds__(SBLOCK) PT_SHADE_ATTR void k_shade(DevScene sc, Dev
         if (lane == 0u && i < count) {
             alive_mask[i >> 6] = am;
             shadow_mask[i >> 6] = sm;
-            n_skipped += (uint32_t)__popcll(zm);
-            n_emitted += (uint32_t)__popcll(em);
+            count_words[i >> 6] = (uint32_t)__popcll(zm) | (uint32_t)__popcll(em) << 16;   // summed by the compaction (pipeline.hip)
         }
     }
-    if (n_skipped) atomicAdd(&sp.stats[kCtShadowRays], (unsigned long long)n_skipped);
-    if (n_emitted) atomicAdd(&sp.stats[kCtEmitRecords], (unsigned long long)n_emitted);
 }
 
 }  // namespace
