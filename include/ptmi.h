@@ -797,6 +797,56 @@ int ptmi_multi_set_triangle_groups(ptmi_multi *m, const uint32_t *group, uint32_
 int ptmi_multi_transform_groups(ptmi_multi *m, const ptmi_group_transform *ops, uint32_t n_ops);
 int ptmi_multi_transform_status(ptmi_multi *m, struct ptmi_transform_status *out);
 
+/* ---- skinned meshes on the device: linear-blend skinning ---------------------------------------
+ * ptmi_set_skin takes a LIST of skinned triangles (triangle[]: indices in uploaded order, strictly ascending) and three corner records
+ * per listed triangle (v0, v1, v2): four joint indices and four weights each. It snapshots the REST (bind) POSE of the listed
+ * triangles - v0, v1, v2, n0, n1, n2, 96 bytes each, as they stand on the device now - keeps the corner records on the device and zeroes
+ * `poses`. Triangles that are not listed cost nothing. triangle NULL or n_skinned 0 removes the skin. PTMI_E_INVALID: no scene, an
+ * index >= the uploaded count, a list that is not strictly ascending, corners NULL, a joint[k] >= n_joints (every slot, whatever its
+ * weight), a weight that is not finite, n_joints 0. PTMI_E_UNSUPPORTED: more than 65 536 joints. A failed call keeps the previous skin.
+ * ptmi_upload_scene removes the skin; ptmi_rebuild_tree, ptmi_update_materials and ptmi_update_lights leave it alone.
+ * ptmi_pose_skin takes a COMPLETE pose: n_joints must be the skin's, joints[i].group must be i and the reserved words 0 (a record
+ * array describes itself; a shuffled one is refused). Transforms are ABSOLUTE, from the rest pose. Per corner with the joints j0..j3
+ * and the weights w0..w3 of its record, in float32, in the order written, no FMA:
+ *   B.m[e]  = ((w0 * J[j0].m[e]  + w1 * J[j1].m[e])  + w2 * J[j2].m[e])  + w3 * J[j3].m[e]                          e = 0..11
+ *   B.nm[e] = ((w0 * J[j0].nm[e] + w1 * J[j1].nm[e]) + w2 * J[j2].nm[e]) + w3 * J[j3].nm[e]                         e = 0..8
+ *   vertex' = the vertex formula of ptmi_transform_groups with B.m;  normal' = its normal formula with B.nm
+ * All four slots are always evaluated: a zero weight is not skipped (so 0 * a matrix entry adds a signed zero, as written). This is
+ * glTF's blended-matrix form of linear-blend skinning. The blended cofactor matrix B.nm is the usual approximation of the cofactor
+ * matrix of the blend B.m (exact where one joint has all the weight). Weights are used as given: normalising them is the loader's
+ * job. The uvs, material_index and the seven padding words keep their bits; triangles that are not listed are not written.
+ * Afterwards the call runs the refit of ptmi_update_triangles: the state is bit for bit what ptmi_update_triangles(0, n_triangles,
+ * the skinned records) leaves and ptmi_scene_update_status.updates grows by one, except that while motion is on the dirty range is
+ * widened to [lowest listed, highest listed] only.
+ * All-or-nothing. On the host: PTMI_E_STATE without a skin; PTMI_E_INVALID for joints NULL, n_joints different from the skin's,
+ * group != i, a non-zero reserved word, a matrix entry that is not finite; PTMI_E_UNSUPPORTED where ptmi_update_triangles gives it.
+ * On the device, before anything of the scene is written, a check pass applies ptmi_update_triangles' vertex checks to the skinned
+ * vertices (as ptmi_transform_groups does): on a failure the call returns PTMI_E_INVALID, first_bad holds the smallest offending
+ * triangle index and the context is otherwise unchanged; on success first_bad is 0xFFFFFFFF.
+ * Interactions. ptmi_update_triangles while a skin is in place re-bases: the records it writes become the rest pose of the listed
+ * triangles inside its range (listed triangles outside it keep theirs). The skin and the triangle groups keep separate rest poses and
+ * neither call re-bases the other's: a triangle that is both listed and a member of a moved group takes the last writer's record.
+ * (The glTF loader never produces that overlap: glTF ignores a skinned mesh's node transform.) */
+typedef struct ptmi_skin_corner {
+    uint32_t joint[4];
+    float    weight[4];
+} ptmi_skin_corner;          /* 32 bytes */
+typedef ptmi_group_transform ptmi_joint_transform;   /* the same 96-byte record; `group` is the joint index */
+struct ptmi_skin_status {             /* a struct tag only; 32 bytes. Without a skin every word is zero. */
+    uint32_t present, n_joints;       /* a skin is in place; the joints it was set with */
+    uint32_t n_skinned;               /* listed triangles */
+    uint32_t poses;                   /* successful ptmi_pose_skin calls since the skin was set */
+    uint32_t first_bad, reserved;     /* the last call's check pass: the smallest offending triangle, 0xFFFFFFFF for none */
+    double   pose_ms;                 /* wall time of the last successful ptmi_pose_skin, its refit included */
+};
+int ptmi_set_skin(ptmi_ctx *ctx, const uint32_t *triangle, const ptmi_skin_corner *corners, uint32_t n_skinned, uint32_t n_joints);
+int ptmi_pose_skin(ptmi_ctx *ctx, const ptmi_joint_transform *joints, uint32_t n_joints);
+int ptmi_skin_status(ptmi_ctx *ctx, struct ptmi_skin_status *out);
+/* on every device, checked once before any device changes; the status of device 0 */
+int ptmi_multi_set_skin(ptmi_multi *m, const uint32_t *triangle, const ptmi_skin_corner *corners, uint32_t n_skinned, uint32_t n_joints);
+int ptmi_multi_pose_skin(ptmi_multi *m, const ptmi_joint_transform *joints, uint32_t n_joints);
+int ptmi_multi_skin_status(ptmi_multi *m, struct ptmi_skin_status *out);
+
 /* ---- alpha cutouts ---------------------------------------------------------------------------
  * A per-material cutoff table for the loaded scene, one float per uploaded material. cutoff = 0: the material is opaque (the state of
  * every material without a table). cutoff > 0: a hit on the material is NOT THERE where the alpha of its albedo map's texel at the hit

@@ -12,6 +12,7 @@
 //   scene_rebuild.hip  the walked own-leaf tree rebuilt in place: the unit list on the device, the swap (ptmi_rebuild_tree)
 //   motion.hip         reprojection across a geometry edit: the previous positions, their commit, the motion plane (ptmi_set_motion)
 //   scene_transform.hip  triangle groups moved by matrix on the device: the table, the rest pose, the check and write passes
+//   scene_skin.hip     skinned triangles posed on the device: the list, the corner records, the rest pose, the check and write passes
 #pragma once
 #include "ptmi.h"
 #include "pt_device.h"
@@ -58,6 +59,10 @@ int pt_check_rebuild(const ptmi_ctx *c, const ptmi_rebuild_params *params, std::
 // change nothing: their error codes, the reason in err. *n_groups_out (may be NULL): the largest id + 1.
 int pt_check_triangle_groups(const ptmi_ctx *c, const uint32_t *group, uint32_t n_triangles, uint32_t *n_groups_out, std::string &err);
 int pt_check_group_transforms(const ptmi_ctx *c, const ptmi_group_transform *ops, uint32_t n_ops, std::string &err);
+// likewise for ptmi_set_skin and ptmi_pose_skin (scene_skin.hip)
+int pt_check_skin(const ptmi_ctx *c, const uint32_t *triangle, const ptmi_skin_corner *corners, uint32_t n_skinned, uint32_t n_joints,
+                  std::string &err);
+int pt_check_skin_pose(const ptmi_ctx *c, const ptmi_joint_transform *joints, uint32_t n_joints, std::string &err);
 // Adaptive rounds driven from outside, one at a time (ptmi_multi_dispatch_adaptive with neighbourhood = 1; dispatch.hip).
 // pt_adaptive_check: everything ptmi_dispatch_adaptive checks before it enqueues, with its error codes; *ap = the params with their defaults.
 int pt_adaptive_check(ptmi_ctx *c, const ptmi_camera *cam, const ptmi_adaptive_params *params, ptmi_adaptive_params *ap);
@@ -96,6 +101,12 @@ enum SceneBuf {
     kGroupRest,                        // the rest pose: v0, v1, v2, n0, n1, n2 of every triangle, 6 float4 each
     kGroupOps,                         // the op records of the ptmi_transform_groups call at hand (grown on demand)
     kGroupMap,                         // 4 words (word 0: the smallest offending triangle of the check pass), then group -> op index
+    // the skin (ptmi_set_skin; scene_skin.hip), gone with the next upload; one entry of each per LISTED triangle, in list order:
+    kSkinList,                         // the listed triangles' indices, ascending
+    kSkinCorners,                      // their corner records: 3 ptmi_skin_corner = 6 float4 each
+    kSkinRest,                         // their rest pose: v0, v1, v2, n0, n1, n2, 6 float4 each
+    kSkinJoints,                       // 4 words (word 0: the smallest offending triangle of the check pass), then the joint records of the
+                                       // ptmi_pose_skin call at hand
     kSceneBufs
 };
 
@@ -212,6 +223,10 @@ struct ptmi_ctx {
     std::vector<ptmi_group_transform> grp_mats;        // per group: its current matrix
     struct ptmi_transform_status tf{};                 // what ptmi_transform_status reports
 
+    // the skin (ptmi_set_skin; scene_skin.hip): the list is buf[kSkinList], the corner records buf[kSkinCorners], the rest pose buf[kSkinRest]
+    std::vector<uint32_t> skin_list;                   // the host's copy of the list (empty: no skin), for the re-base of a range
+    struct ptmi_skin_status skin{};                    // what ptmi_skin_status reports
+
     // output (binding 0)
     uint32_t W = 0, H = 0;
     void *plane[kFramePlanes] = {};                    // indexed by FramePlane, W x H pixels each (absent: NULL)
@@ -269,7 +284,7 @@ hipError_t quiesce(ptmi_ctx *c);
 void drop_plan(ptmi_ctx *c);
 int make_plan(ptmi_ctx *c);
 int walked_cost(ptmi_ctx *c, double &cost);
-// What ptmi_update_triangles and ptmi_transform_groups share around the write of the records. refit_begin: the tree must be one a refit
+// What ptmi_update_triangles, ptmi_transform_groups and ptmi_pose_skin share around the write of the records. refit_begin: the tree must be one a refit
 // can serve (PTMI_E_UNSUPPORTED otherwise, nothing touched). refit_ready: waits for the work in flight and makes the plan at the first
 // edit after an upload. refit_written: everything behind the write - the triangle images, the light triangles, both trees, the root
 // boxes, the header, the cost and the status (updates grows by one; refit_ms counts from t0, when the entry point was entered).
@@ -281,6 +296,9 @@ int refit_written(ptmi_ctx *c, std::chrono::steady_clock::time_point t0);
 // [first, first + count) that ptmi_update_triangles has just written become the rest pose of their triangles, on c's stream
 void groups_forget(ptmi_ctx *c);
 int groups_rebase(ptmi_ctx *c, uint32_t first, uint32_t count);
+// scene_skin.hip: the same two for the skin; the re-base takes the listed triangles inside the range
+void skin_forget(ptmi_ctx *c);
+int skin_rebase(ptmi_ctx *c, uint32_t first, uint32_t count);
 
 // scene_image.hip: the own-leaf image of the loaded scene built anew from what is on the device (ptmi_rebuild_tree), by the code an
 // upload builds it with. d_which: the unit list (n_units entries, device memory). buf: new device buffers for the entries a rebuild

@@ -557,6 +557,27 @@ int ptmi_multi_transform_status(ptmi_multi *m, struct ptmi_transform_status *out
     return rc ? cfail(m, 0, rc, "ptmi_transform_status") : PTMI_OK;
 }
 
+// The skin on every device (scene_skin.hip), by the same rule as the groups: checked once on device 0's context.
+int ptmi_multi_set_skin(ptmi_multi *m, const uint32_t *triangle, const ptmi_skin_corner *corners, uint32_t n_skinned, uint32_t n_joints) {
+    if (!m) return PTMI_E_INVALID;
+    std::string why;
+    const int rc = pt_check_skin(m->d[0].ctx, triangle, corners, n_skinned, n_joints, why);
+    if (rc) return mfail(m, rc, "%s", why.c_str());
+    return each_ctx(m, "ptmi_set_skin", ptmi_set_skin, triangle, corners, n_skinned, n_joints);
+}
+int ptmi_multi_pose_skin(ptmi_multi *m, const ptmi_joint_transform *joints, uint32_t n_joints) {
+    if (!m) return PTMI_E_INVALID;
+    std::string why;
+    const int rc = pt_check_skin_pose(m->d[0].ctx, joints, n_joints, why);
+    if (rc) return mfail(m, rc, "%s", why.c_str());
+    return each_ctx(m, "ptmi_pose_skin", ptmi_pose_skin, joints, n_joints);
+}
+int ptmi_multi_skin_status(ptmi_multi *m, struct ptmi_skin_status *out) {
+    if (!m || !out) return PTMI_E_INVALID;
+    const int rc = ptmi_skin_status(m->d[0].ctx, out);
+    return rc ? cfail(m, 0, rc, "ptmi_skin_status") : PTMI_OK;
+}
+
 int ptmi_multi_resize(ptmi_multi *m, uint32_t w, uint32_t h) {
     if (!m) return PTMI_E_INVALID;
     int rc = each_ctx(m, "ptmi_resize", ptmi_resize, w, h);

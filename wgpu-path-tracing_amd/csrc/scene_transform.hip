@@ -18,6 +18,7 @@
 // -DPT_TRANSFORM_LANES=1 builds the layout this one was measured against instead (a lane per triangle, the same arithmetic through the
 // same functions): an A/B switch for tools/transform_cost.py, never the default. The numbers are in profiles/README.md.
 #include "ptmi_ctx.h"
+#include "pt_transform.h"   // transform_row, vertex_bad and the record constants, shared with scene_skin.hip
 
 #include <algorithm>
 #include <chrono>
@@ -37,15 +38,7 @@ constexpr uint32_t kChunk = 512u;            // op records per launch (LDS)
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kMaxGroups = 65536u;
 constexpr uint32_t kMapHead = 4u;            // words in front of the group -> op map; word 0: the check pass's smallest offender
-constexpr int kRestQ = 6;                    // float4 per triangle of the rest pose
-constexpr int kLiveQ = (int)(sizeof(ptmi_triangle) / sizeof(float4));
-static_assert(sizeof(ptmi_group_transform) == 96 && sizeof(ptmi_group_transform) % sizeof(float4) == 0, "an op record is 6 float4");
 static_assert(sizeof(struct ptmi_transform_status) == 32, "ptmi_transform_status is 32 bytes");
-constexpr int kOpQ = (int)(sizeof(ptmi_group_transform) / sizeof(float4));
-constexpr int kOpM = (int)(offsetof(ptmi_group_transform, m) / sizeof(float));
-constexpr int kOpNm = (int)(offsetof(ptmi_group_transform, nm) / sizeof(float));
-
-__device__ __forceinline__ bool finite1(float x) { return __builtin_fabsf(x) <= 3.402823466e38f; }
 
 // the rows [first, first + count) of the live records to the rest pose: a thread per float4
 __global__ void __launch_bounds__(TB) k_rest_snapshot(uint32_t first, uint32_t count, const float4 *__restrict__ live, float4 *__restrict__ rest) {
@@ -53,36 +46,6 @@ __global__ void __launch_bounds__(TB) k_rest_snapshot(uint32_t first, uint32_t c
     if (i >= (size_t)count * kRestQ) return;
     const size_t tri = first + i / kRestQ, q = i % kRestQ;
     rest[tri * kRestQ + q] = live[tri * kLiveQ + q];
-}
-
-// one float4 of the rest record through the op o (24 words): q < 3 a vertex, else a normal. The arithmetic of include/ptmi.h.
-__device__ __forceinline__ float4 transform_row(const float *o, uint32_t q, float4 p) {
-    float4 r;
-    if (q < 3u) {
-        const float *m = o + kOpM;
-        r.x = ((m[0] * p.x + m[1] * p.y) + m[2] * p.z) + m[3];
-        r.y = ((m[4] * p.x + m[5] * p.y) + m[6] * p.z) + m[7];
-        r.z = ((m[8] * p.x + m[9] * p.y) + m[10] * p.z) + m[11];
-    } else {
-        const float *nm = o + kOpNm;
-        const float qx = (nm[0] * p.x + nm[1] * p.y) + nm[2] * p.z;
-        const float qy = (nm[3] * p.x + nm[4] * p.y) + nm[5] * p.z;
-        const float qz = (nm[6] * p.x + nm[7] * p.y) + nm[8] * p.z;
-        const float l2 = (qx * qx + qy * qy) + qz * qz;
-        r.x = qx; r.y = qy; r.z = qz;
-        if (l2 > 0.0f) {
-            const float len = __builtin_sqrtf(l2);                  // correctly rounded, as '/' is (pt_math.h)
-            r.x = qx / len; r.y = qy / len; r.z = qz / len;
-        }
-    }
-    r.w = p.w;                                                       // the padding word keeps its bits
-    return r;
-}
-// scene_update.hip's checks on one transformed vertex b beside the first, a (b is a itself for the first)
-__device__ __forceinline__ bool vertex_bad(float4 a, float4 b, bool edge) {
-    bool bad = !finite1(b.x) || !finite1(b.y) || !finite1(b.z);
-    if (edge) bad = bad || !finite1(a.x + (b.x - a.x)) || !finite1(a.y + (b.y - a.y)) || !finite1(a.z + (b.z - a.z));
-    return bad;
 }
 
 // Triangles [tri_first, tri_end) against the ops [op_first, op_first + op_count) of the call. WRITE: the six float4 of named members

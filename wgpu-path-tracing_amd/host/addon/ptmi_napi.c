@@ -382,6 +382,55 @@ static napi_value js_transform_status(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* setSkin(handle, Uint32Array | null triangles, corners blob | null, nJoints): ptmi_set_skin; the blob holds three 32-byte
+ * ptmi_skin_corner records per listed triangle; null triangles remove the skin */
+static napi_value js_set_skin(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    handle *h = get_handle(env, info, 4, argv);
+    if (!h) return NULL;
+    void *t, *c; size_t tn, cn;
+    uint32_t n_joints = 0;
+    if (!get_bytes(env, argv[1], &t, &tn) || !get_bytes(env, argv[2], &c, &cn)) return NULL;
+    NAPI_OK(env, napi_get_value_uint32(env, argv[3], &n_joints));
+    if (tn % sizeof(uint32_t)) { napi_throw_range_error(env, NULL, "the triangle list is not whole uint32 words"); return NULL; }
+    if (c && cn != tn / sizeof(uint32_t) * 3 * sizeof(ptmi_skin_corner)) {
+        napi_throw_range_error(env, NULL, "the corner blob does not hold three 32-byte records per listed triangle");
+        return NULL;
+    }
+    CALL(env, h, set_skin, (const uint32_t *)t, (const ptmi_skin_corner *)c, (uint32_t)(tn / sizeof(uint32_t)), n_joints);
+    return NULL;
+}
+
+/* poseSkin(handle, blob): ptmi_pose_skin; the blob holds one 96-byte ptmi_joint_transform record per joint, in joint order */
+static napi_value js_pose_skin(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    handle *h = get_handle(env, info, 2, argv);
+    if (!h) return NULL;
+    void *p; size_t n;
+    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
+    if (n % sizeof(ptmi_joint_transform)) { napi_throw_range_error(env, NULL, "blob length is not a multiple of 96 bytes"); return NULL; }
+    CALL(env, h, pose_skin, (const ptmi_joint_transform *)p, (uint32_t)(n / sizeof(ptmi_joint_transform)));
+    return NULL;
+}
+
+/* skinStatus(handle) -> {present, nJoints, nSkinned, poses, firstBad, poseMs} */
+static napi_value js_skin_status(napi_env env, napi_callback_info info) {
+    napi_value argv[1], out, v;
+    handle *h = get_handle(env, info, 1, argv);
+    if (!h) return NULL;
+    struct ptmi_skin_status st;
+    CALL(env, h, skin_status, &st);
+    NAPI_OK(env, napi_create_object(env, &out));
+    const struct { const char *name; double value; } num[] = {
+        {"present", st.present}, {"nJoints", st.n_joints}, {"nSkinned", st.n_skinned}, {"poses", st.poses},
+        {"firstBad", st.first_bad}, {"poseMs", st.pose_ms}};
+    for (size_t i = 0; i < sizeof num / sizeof num[0]; i++) {
+        NAPI_OK(env, napi_create_double(env, num[i].value, &v));
+        NAPI_OK(env, napi_set_named_property(env, out, num[i].name, v));
+    }
+    return out;
+}
+
 /* rebuildStatus(handle) -> {rebuilds, builderUsed, buildMs, costBefore, costAfter} */
 static napi_value js_rebuild_status(napi_env env, napi_callback_info info) {
     napi_value argv[1], out, v;
@@ -971,6 +1020,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"updateTriangles", js_update_triangles}, {"updateMaterials", js_update_materials}, {"updateLights", js_update_lights}, {"sceneUpdateStatus", js_scene_update_status},
         {"setTriangleGroups", js_set_triangle_groups}, {"transformGroups", js_transform_groups}, {"transformStatus", js_transform_status},
         {"normalMatrix", js_normal_matrix},
+        {"setSkin", js_set_skin}, {"poseSkin", js_pose_skin}, {"skinStatus", js_skin_status},
         {"rebuildTree", js_rebuild_tree}, {"rebuildStatus", js_rebuild_status},
         {"setAlphaCutoff", js_set_alpha_cutoff}, {"alphaStatus", js_alpha_status},
         {"resize", js_resize}, {"setOptions", js_set_options},

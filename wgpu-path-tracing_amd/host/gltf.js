@@ -4,6 +4,10 @@
  * @loaders.gl/gltf's load + postProcessGLTF (src/renderer/loader.ts:13-17), reduced to the fields
  * src/renderer/gpu.ts reads: nodes (children, matrix | TRS, mesh, light), mesh primitives with
  * POSITION / NORMAL / TEXCOORD_0 / indices as typed arrays, materials, KHR_lights_punctual lights.
+ * Beyond the reference: skins ({ joints: node indices, inverseBindMatrices: Float32Array of 16 per joint, column-major, or
+ * undefined for identities }), a node's `skin` index, and animations ({ channels: [{ node, path, sampler }], samplers:
+ * [{ input, output, interpolation }] }); JOINTS_0 / WEIGHTS_0 come through the attribute reader like every other attribute
+ * (normalised integer weights are scaled to [0, 1]).
  * Images are decoded to RGBA8 ({width, height, data}; PNG and JPEG) and texture
  * references are resolved the way postProcessGLTF does (`material.normalTexture.texture.source.image`), which is
  * what src/renderer/atlas.ts:36-48 walks.
@@ -42,6 +46,11 @@ function readAccessor(json, bin, index) {
   var dv = new DataView(bin.buffer, base);
   var get = { 5120: 'getInt8', 5121: 'getUint8', 5122: 'getInt16', 5123: 'getUint16', 5125: 'getUint32', 5126: 'getFloat32' }[acc.componentType];
   for (var i = 0; i < acc.count; i++) for (var k = 0; k < n; k++) out[i * n + k] = dv[get](i * stride + k * esz, true);
+  if (acc.normalized && acc.componentType !== 5126) {               // normalised integers (WEIGHTS_0 may be): to [0, 1] / [-1, 1]
+    var top = { 5120: 127, 5121: 255, 5122: 32767, 5123: 65535 }[acc.componentType], f = new Float32Array(out.length);
+    for (var q = 0; q < out.length; q++) f[q] = Math.max(out[q] / top, -1);
+    out = f;
+  }
   return { value: out, size: n };
 }
 
@@ -98,13 +107,27 @@ function loadGLB(pathOrBuffer) {
   var nodes = (json.nodes || []).map(function (n) {
     var o = { name: n.name, matrix: n.matrix, translation: n.translation, rotation: n.rotation, scale: n.scale };
     if (n.mesh !== undefined) o.mesh = meshes[n.mesh];
+    if (n.skin !== undefined) o.skin = n.skin;
     if (n.extensions && n.extensions.KHR_lights_punctual) o.light = n.extensions.KHR_lights_punctual.light;
     return o;
   });
   (json.nodes || []).forEach(function (n, i) {
     if (n.children) nodes[i].children = n.children.map(function (c) { return nodes[c]; });
   });
-  return { nodes: nodes, meshes: meshes, materials: materials, textures: textures, images: images, lights: rootLights, json: json };
+  var skins = (json.skins || []).map(function (s) {
+    return { name: s.name, joints: s.joints.slice(), skeleton: s.skeleton,
+      inverseBindMatrices: s.inverseBindMatrices !== undefined ? readAccessor(json, bin, s.inverseBindMatrices).value : undefined };
+  });
+  var animations = (json.animations || []).map(function (a) {
+    return { name: a.name,
+      channels: a.channels.map(function (c) { return { node: c.target.node, path: c.target.path, sampler: c.sampler }; }),
+      samplers: a.samplers.map(function (s) {
+        return { input: readAccessor(json, bin, s.input).value, output: readAccessor(json, bin, s.output).value,
+          interpolation: s.interpolation || 'LINEAR' };
+      }) };
+  });
+  return { nodes: nodes, meshes: meshes, materials: materials, textures: textures, images: images, lights: rootLights,
+    skins: skins, animations: animations, json: json };
 }
 
 module.exports = { parseGLB: parseGLB, readAccessor: readAccessor, loadGLB: loadGLB };

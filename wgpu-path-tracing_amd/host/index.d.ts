@@ -95,6 +95,17 @@ export class Renderer {
    *  included. A refused call throws and changes nothing. */
   transformGroups(ops: Array<{ group: number; matrix: ArrayLike<number>; normalMatrix?: ArrayLike<number> }>): void;
   transformStatus(): TransformStatus;
+  /** lists the skinned triangles of the loaded scene (ascending indices in the uploaded order) with three 32-byte corner records each
+   *  ({ uint32 joint[4], float32 weight[4] }) for a skeleton of nJoints, and snapshots the rest pose (include/ptmi.h ptmi_set_skin);
+   *  null removes the skin. loadModel of a .glb with skins does it. */
+  setSkin(triangles: Uint32Array | null, corners: ArrayBuffer | ArrayBufferView | null, nJoints: number): void;
+  /** a complete pose, one entry per joint in joint order (ptmi_pose_skin): every listed triangle becomes the blend of its joints'
+   *  matrices applied to its rest pose, absolute, and the trees are refitted on the device. matrix: 12 numbers, a 3 x 4 row-major
+   *  affine; normalMatrix: 9 numbers, derived through ptmi_normal_matrix when absent. A refused call throws and changes nothing. */
+  poseSkin(joints: Array<{ matrix: ArrayLike<number>; normalMatrix?: ArrayLike<number> }>): void;
+  skinStatus(): SkinStatus;
+  /** poses the skin of the loaded .glb at t seconds of its animation (STEP and LINEAR samplers; CUBICSPLINE throws) */
+  poseAt(animationIndex: number, t: number): void;
   /** builds the walked own-leaf tree anew from the triangles as they stand on the device and swaps it in (include/ptmi.h
    *  ptmi_rebuild_tree): the image a fresh loadModel of the edited scene would build, with the triangle order, the tables, the alpha
    *  table, the motion state and every plane left alone. builder: 1 the host's, 2 (default) the device's where it applies. The hits
@@ -191,6 +202,12 @@ export interface TransformStatus {
   present: number; nGroups: number; transforms: number; lastMoved: number;
   /** the last call's check pass: the smallest offending triangle, 0xFFFFFFFF for none */
   firstBad: number; transformMs: number;
+}
+/** ptmi_skin_status: the skin in place and the poses since it was set */
+export interface SkinStatus {
+  present: number; nJoints: number; nSkinned: number; poses: number;
+  /** the last call's check pass: the smallest offending triangle, 0xFFFFFFFF for none */
+  firstBad: number; poseMs: number;
 }
 /** ptmi_scene_update_status: the triangle updates since the scene was loaded */
 export interface SceneUpdateStatus {

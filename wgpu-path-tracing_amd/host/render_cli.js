@@ -9,7 +9,7 @@
  *                       --env file.hdr --env-intensity X --env-rotation DEGREES --env-sample 0|1
  *                       --fog sigma_t[,albedo[,g]] --fog-density file.f32 --fog-grid nx,ny,nz --fog-filter nearest|linear
  *                       --devices 0,1,... --loopback --aov albedo|normal|id --aov-out plane.bin
- *                       --alpha-cutout --alpha-layers N]
+ *                       --alpha-cutout --alpha-layers N --animation N --time S]
  * --batch K traces K frames per dispatch instead of one. --denoise keeps the denoiser's planes and makes --png the tone-mapped
  * denoised image (include/ptmi.h ptmi_denoise, default parameters). --adaptive renders to a noise level instead of --frames
  * (include/ptmi.h ptmi_dispatch_adaptive): rounds until none lists a pixel, or --rounds R of them; the JSON line then also holds
@@ -26,6 +26,8 @@
  * --alpha-cutout (a .glb scene): materials with alphaMode "MASK" become cutouts at their alphaCutoff (include/ptmi.h
  * ptmi_set_alpha_cutoff): the atlas keeps the alpha of albedo maps, and paths and shadow rays pass where it is below the cutoff, through
  * at most --alpha-layers N holes per segment (default: the library's, 4); the JSON line then also holds alpha: the table's status.
+ * --animation N --time S (a .glb scene with a skin): renders one frame posed at S seconds (default 0) of the file's animation N
+ * (Renderer.poseAt; include/ptmi.h ptmi_pose_skin); the JSON line then also holds skin: the skin's status.
  */
 var fs = require('fs');
 var host = require('./renderer');
@@ -84,6 +86,7 @@ r.loadModel(scenePath).then(function () {
     if (peak > 1) for (var q = 0; q < rho.length; q++) rho[q] /= peak;
     r.setMediumDensity(rho, dims, { filter: textArg('fog-filter') || 'nearest' });
   }
+  if (textArg('animation') !== null) r.poseAt(arg('animation', 0), arg('time', 0));
   var t0 = Date.now();
   var status = null;
   if (adaptive) {
@@ -108,6 +111,7 @@ r.loadModel(scenePath).then(function () {
   st.wallMs = ms; st.width = W; st.height = H; st.frames = frames;
   if (status) st.frames = 0;                // no uniform frames: the counts are per pixel
   if (alphaCutout) st.alpha = r.alphaStatus();
+  if (textArg('animation') !== null) st.skin = r.skinStatus();
   if (status) st.adaptive = { samples: status.samples, minCount: status.minCount, maxCount: status.maxCount, rounds: status.rounds };
   console.log(JSON.stringify(st));
   r.destroy();

@@ -86,18 +86,22 @@ Renderer.prototype.addOnUpdate = function (callback) { this.onUpdateTasks.push(c
 Renderer.prototype.loadModel = function (model, atlas) {
   var self = this;
   return new Promise(function (resolve) {
-    var blobs, cutoff = null, groups = null;
+    var blobs, cutoff = null, groups = null, skin = null;
+    self.gltf = null; self.skins = null;
     if (typeof model === 'string' && /\.glb$/i.test(model)) {
-      var prepared = require('./scene_prep').prepareScene(require('./gltf').loadGLB(model), { alphaCutout: self.alphaCutout });
+      var gltf = require('./gltf').loadGLB(model);
+      var prepared = require('./scene_prep').prepareScene(gltf, { alphaCutout: self.alphaCutout });
       blobs = prepared.blobs; atlas = atlas || prepared.atlas; self.sceneInfo = prepared;
       cutoff = prepared.alphaCutoff || null;
       groups = prepared.triangleGroups || null;
+      if (prepared.skinTriangles) { skin = prepared; self.gltf = gltf; }
     } else if (typeof model === 'string') {
       var f = sceneFile.readSceneFile(model);
       blobs = f.blobs; atlas = atlas || f.atlas;
     } else if (model.blobs) {
       blobs = model.blobs; atlas = atlas || model.atlas;
       groups = model.triangleGroups || null;                            // what prepareScene returned: a triangle's glTF node
+      if (model.skinTriangles) { skin = model; self.gltf = model.gltf || null; }   // ... and its skinned triangles
       if (self.alphaCutout) cutoff = model.alphaCutoff || null;         // what prepareScene({alphaCutout: true}) returned
     } else {
       blobs = pack.packScene(model);
@@ -110,6 +114,11 @@ Renderer.prototype.loadModel = function (model, atlas) {
     if (cutoff) self.addon.setAlphaCutoff(self.ctx, cutoff, self.alphaLayers);
     // ... and any group table: a .glb's triangles are tagged with the node they came from (transformGroups moves a node by matrix)
     if (groups && groups.length) self.addon.setTriangleGroups(self.ctx, groups);
+    // ... and any skin: a .glb's skinned primitives are listed with their joints and weights (poseSkin / poseAt pose them)
+    if (skin && skin.skinTriangles.length) {
+      self.addon.setSkin(self.ctx, skin.skinTriangles, skin.skinCorners, skin.skinJoints);
+      self.skins = skin;
+    }
     self.sceneLoaded = true;
     self.resetOutputBuffer(false);
     resolve();
@@ -314,6 +323,50 @@ Renderer.prototype.transformGroups = function (ops) {
 /** { present, nGroups, transforms, lastMoved, firstBad, transformMs } of the group table in place */
 Renderer.prototype.transformStatus = function () {
   return this.addon.transformStatus(this.ctx);
+};
+/**
+ * Skinned meshes posed on the device (include/ptmi.h ptmi_set_skin / ptmi_pose_skin). setSkin lists the skinned triangles (a
+ * Uint32Array of ascending indices in the uploaded order; null removes the skin) with three 32-byte corner records each (corners: an
+ * ArrayBuffer of { uint32 joint[4], float32 weight[4] }) for a skeleton of nJoints, and snapshots the rest pose; loadModel of a .glb
+ * with skins does it (scene.skinTriangles / skinCorners). poseSkin takes a complete pose, one entry per joint in joint order:
+ * [{ matrix (12 numbers: a 3 x 4 row-major affine), normalMatrix? (9 numbers; derived through ptmi_normal_matrix when absent) }].
+ * Poses are absolute, from the rest pose; 96 bytes per joint cross the bus. What follows is what follows updateTriangles.
+ * A refused call throws and changes nothing.
+ */
+Renderer.prototype.setSkin = function (triangles, corners, nJoints) {
+  if (triangles && !(triangles instanceof Uint32Array)) throw new TypeError('setSkin: triangles must be a Uint32Array or null');
+  if (!this.sceneLoaded) throw new Error('setSkin: needs a loaded scene (loadModel)');
+  this.addon.setSkin(this.ctx, triangles || null, triangles ? corners : null, nJoints >>> 0);
+  this.skins = null;                                                   // (poseAt poses the skin loadModel set, not this one)
+};
+Renderer.prototype.poseSkin = function (joints) {
+  if (!this.sceneLoaded) throw new Error('poseSkin: needs a loaded scene (loadModel)');
+  var blob = new ArrayBuffer(96 * joints.length), u32 = new Uint32Array(blob), f32 = new Float32Array(blob);
+  for (var i = 0; i < joints.length; i++) {
+    var j = joints[i], m = Float32Array.from(j.matrix), nm = new Float32Array(9);
+    if (m.length !== 12) throw new RangeError('poseSkin: matrix must hold 12 numbers (3 x 4, row-major)');
+    if (j.normalMatrix) {
+      if (j.normalMatrix.length !== 9) throw new RangeError('poseSkin: normalMatrix must hold 9 numbers');
+      nm.set(j.normalMatrix);
+    } else this.addon.normalMatrix(this.ctx, m, nm);
+    u32[24 * i] = i;
+    f32.set(m, 24 * i + 2);
+    f32.set(nm, 24 * i + 14);
+  }
+  this.addon.poseSkin(this.ctx, blob);
+  this._trianglesEdited();
+};
+/** { present, nJoints, nSkinned, poses, firstBad, poseMs } of the skin in place */
+Renderer.prototype.skinStatus = function () {
+  return this.addon.skinStatus(this.ctx);
+};
+/** poses the skin of the loaded .glb at t seconds of its animation animationIndex: the animated local transforms (animation.js
+ *  sample: STEP and LINEAR), the node hierarchy composed in double, the joint matrices of scene_prep.skinPose, then poseSkin */
+Renderer.prototype.poseAt = function (animationIndex, t) {
+  if (!this.skins || !this.gltf) throw new Error('poseAt: needs a loaded .glb with a skin (loadModel)');
+  var animation = require('./animation');
+  var worlds = animation.worldMatrices(this.gltf, animation.sample(this.gltf, animationIndex, t));
+  this.poseSkin(require('./scene_prep').skinPose(this.skins, worlds));
 };
 /** { updates, quantisedKept, planMs, refitMs, costBuilt, costNow, rootMin, rootMax } of the triangle updates since loadModel */
 Renderer.prototype.sceneUpdateStatus = function () {

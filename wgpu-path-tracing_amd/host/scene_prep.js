@@ -76,7 +76,7 @@ function buildTriangles(position, normal, uv, index) {
 }
 
 /** gpu.ts:194-299 */
-function processNode(gltf, node, allTriangles, allMaterials, allLights, world, atlas, nodeIndex) {
+function processNode(gltf, node, allTriangles, allMaterials, allLights, world, atlas, nodeIndex, skinInstance) {
   var normalMat = M.transpose(M.inverse(world));
   if (node.light !== undefined) {
     var light = gltf.lights[node.light];
@@ -102,7 +102,18 @@ function processNode(gltf, node, allTriangles, allMaterials, allLights, world, a
       }
       var tris = buildTriangles(tp, tn, uv, prim.indices ? prim.indices.value : undefined);
       allMaterials.push(buildMaterial(prim.material, atlas));
-      tris.forEach(function (t) { t.materialIndex = allMaterials.length - 1; t.group = nodeIndex; allTriangles.push(t); });
+      // a skinned primitive is still placed by its node's world matrix (the uploaded bytes are what they are without skinning);
+      // its triangles remember their three vertices' JOINTS_0 / WEIGHTS_0 for the skin list
+      var skinned = skinInstance && prim.attributes.JOINTS_0 && prim.attributes.WEIGHTS_0 && prim.indices;
+      tris.forEach(function (t, k) {
+        t.materialIndex = allMaterials.length - 1; t.group = nodeIndex;
+        if (skinned) {
+          var ix = prim.indices.value;
+          t.skin = { instance: skinInstance, vertices: [ix[3 * k], ix[3 * k + 1], ix[3 * k + 2]],
+            joints: prim.attributes.JOINTS_0.value, weights: prim.attributes.WEIGHTS_0.value };
+        }
+        allTriangles.push(t);
+      });
     });
   }
 }
@@ -128,10 +139,65 @@ function untagGroups(triangles) {
   return groups;
 }
 
+/** The same ride for the skin: every triangle's PRE-SORT index in a second padding word (byte 92, _p5, behind n2), read back and
+ *  zeroed after the build. Only written when the file has a skinned primitive. */
+var PRESORT_WORD = 23;
+function tagPresort(triangles) {
+  var u = new Uint32Array(triangles);
+  for (var i = 0; i * 32 < u.length; i++) u[i * 32 + PRESORT_WORD] = i;
+}
+function untagPresort(triangles) {
+  var u = new Uint32Array(triangles), at = new Uint32Array(u.length / 32);
+  for (var i = 0; i < at.length; i++) { at[i] = u[i * 32 + PRESORT_WORD]; u[i * 32 + PRESORT_WORD] = 0; }
+  return at;
+}
+
+/** The skin list of a prepared scene (Renderer.setSkin): the uploaded indices of the skinned triangles, ascending, and three 32-byte
+ *  corner records each: the vertex's four JOINTS_0 offset by its skin instance's jointBase, and its WEIGHTS_0 normalised to sum 1 in
+ *  double and then rounded to float32 (a vertex whose weights sum to 0 keeps them). */
+function skinList(allTriangles, presort) {
+  var listed = [];
+  for (var i = 0; i < presort.length; i++) if (allTriangles[presort[i]].skin) listed.push(i);
+  var corners = new ArrayBuffer(96 * listed.length), u32 = new Uint32Array(corners), f32 = new Float32Array(corners);
+  listed.forEach(function (at, e) {
+    var s = allTriangles[presort[at]].skin;
+    for (var c = 0; c < 3; c++) {
+      var v = s.vertices[c], sum = 0, k;
+      for (k = 0; k < 4; k++) sum += s.weights[4 * v + k];
+      for (k = 0; k < 4; k++) {
+        u32[24 * e + 8 * c + k] = s.joints[4 * v + k] + s.instance.jointBase;
+        f32[24 * e + 8 * c + 4 + k] = sum > 0 ? s.weights[4 * v + k] / sum : s.weights[4 * v + k];
+      }
+    }
+  });
+  return { triangles: Uint32Array.from(listed), corners: corners };
+}
+
+/** The joint records of a pose (Renderer.poseSkin) from the world matrix of every node (animation.js worldMatrices: 16 numbers
+ *  each, column-major). The rest pose on the device is in world space, placed by the mesh node's world matrix, and glTF poses a
+ *  skinned vertex by its joints alone, so the device matrix of joint j is jointWorld_j . inverseBind_j . meshWorld^-1: composed in
+ *  double here, rounded to float32 where the records are packed. -> [{ matrix: 12 numbers, 3 x 4 row-major }] by device joint index */
+function skinPose(prepared, nodeWorldMatrices) {
+  var anim = require('./animation'), out = new Array(prepared.skinJoints);
+  prepared.skins.forEach(function (s) {
+    s.joints.forEach(function (node, k) {
+      var m = nodeWorldMatrices[node];
+      if (s.inverseBind) m = anim.mul4(m, Array.prototype.slice.call(s.inverseBind, 16 * k, 16 * k + 16));
+      m = anim.mul4(m, s.meshWorldInverse);
+      out[s.jointBase + k] = { matrix: [m[0], m[4], m[8], m[12], m[1], m[5], m[9], m[13], m[2], m[6], m[10], m[14]] };
+    });
+  });
+  return out;
+}
+
 /** loader.ts:20-40 + gpu.ts:67-150 -> { blobs, atlas, counts, bvhDepth, triangleGroups, groupNames }: triangleGroups holds, per
  *  triangle in the uploaded (reordered) order, the index of the glTF node it came from (Renderer.setTriangleGroups), groupNames
  *  the nodes' names by that index (opts.triangleGroups === false: neither). opts.alphaCutout: the atlas keeps the alpha of albedo maps
- *  and the result carries alphaCutoff, a Float32Array with one cutoff per packed material (else: neither, and every byte as without) */
+ *  and the result carries alphaCutoff, a Float32Array with one cutoff per packed material (else: neither, and every byte as without).
+ *  A file with skinned primitives (a node with `skin`, JOINTS_0 and WEIGHTS_0) also returns skinTriangles, skinCorners (skinList),
+ *  skinJoints (the joints of all skin instances together) and skins: per skinned node { node, skin, joints (node indices),
+ *  inverseBind, meshWorldInverse, jointBase } (opts.skins === false, or a file without skins: none of them, and every blob the
+ *  same bytes) */
 function prepareScene(gltf, opts) {
   var alphaCutout = !!(opts && opts.alphaCutout);
   var packed = require('./atlas').packing(gltf, { keepAlpha: alphaCutout });
@@ -145,8 +211,16 @@ function prepareScene(gltf, opts) {
     while (parent.has(cur)) { cur = parent.get(cur); M.mul(extractNodeMatrix(cur), w, w); }
     world.set(node, w);
   });
+  var skins = [], skinJoints = 0;
+  if (!(opts && opts.skins === false)) gltf.nodes.forEach(function (node, nodeIndex) {
+    var skin = node.skin !== undefined && node.mesh ? (gltf.skins || [])[node.skin] : undefined;
+    if (!skin) return;
+    skins[nodeIndex] = { node: nodeIndex, skin: node.skin, joints: skin.joints, inverseBind: skin.inverseBindMatrices,
+      meshWorldInverse: require('./animation').invert4(Array.from(world.get(node))), jointBase: skinJoints };
+    skinJoints += skin.joints.length;
+  });
   gltf.nodes.forEach(function (node, nodeIndex) {
-    processNode(gltf, node, allTriangles, allMaterials, allLights, world.get(node), packed.materials, nodeIndex);
+    processNode(gltf, node, allTriangles, allMaterials, allLights, world.get(node), packed.materials, nodeIndex, skins[nodeIndex]);
     // one material per primitive, in the order processNode packs them
     if (alphaCutout && node.mesh) node.mesh.primitives.forEach(function (prim) { allCutoffs.push(alphaCutoffOf(prim.material)); });
   });
@@ -156,14 +230,19 @@ function prepareScene(gltf, opts) {
   var a = addon();
   var grouped = !(opts && opts.triangleGroups === false);       // false: no tags at all, and no table in the result
   if (grouped) tagGroups(triangles, allTriangles);
+  var skinned = allTriangles.some(function (t) { return !!t.skin; });
+  if (skinned) tagPresort(triangles);
   var bvh = a.buildBvh(triangles);
   var triangleGroups = grouped ? untagGroups(triangles) : undefined;
+  var skin = skinned ? skinList(allTriangles, untagPresort(triangles)) : undefined;
   var lights = a.emissiveLights(triangles, materials, pack.packLights(allLights));
   return {
     blobs: { triangles: triangles, materials: materials, bvhNodes: bvh.nodes, lights: lights },
     alphaCutoff: alphaCutout ? new Float32Array(allCutoffs) : undefined,
     triangleGroups: triangleGroups,
     groupNames: grouped ? gltf.nodes.map(function (n, i) { return n.name || 'node' + i; }) : undefined,
+    skinTriangles: skin ? skin.triangles : undefined, skinCorners: skin ? skin.corners : undefined,
+    skinJoints: skin ? skinJoints : undefined, skins: skin ? skins.filter(Boolean) : undefined,
     atlas: packed.texture,
     counts: { triangles: allTriangles.length, materials: allMaterials.length, bvhNodes: bvh.nodes.byteLength / pack.BVH_NODE_SIZE,
       lights: lights.byteLength / pack.LIGHT_SIZE, punctualLights: allLights.length },
@@ -171,4 +250,4 @@ function prepareScene(gltf, opts) {
   };
 }
 
-module.exports = { prepareScene: prepareScene, extractNodeMatrix: extractNodeMatrix, buildMaterial: buildMaterial, alphaCutoffOf: alphaCutoffOf };
+module.exports = { prepareScene: prepareScene, skinPose: skinPose, extractNodeMatrix: extractNodeMatrix, buildMaterial: buildMaterial, alphaCutoffOf: alphaCutoffOf };

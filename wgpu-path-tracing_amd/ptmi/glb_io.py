@@ -63,10 +63,14 @@ def encode_png(pixels, color_type=6, filters=None, palette=None, trns=None, dept
     return b"\x89PNG\r\n\x1a\n" + body
 
 
-def write_glb(path, meshes, nodes, materials, lights=None, images=None, textures=None):
-    """meshes: list of dicts {positions (N,3), normals (N,3), uvs (N,2) or None, indices (M,), material or None};
-    nodes: list of dicts {mesh?, light?, translation?, rotation?, scale?, matrix?, children?};
-    images: list of encoded image files (bytes, PNG); textures: list of image indices (one glTF texture each)."""
+def write_glb(path, meshes, nodes, materials, lights=None, images=None, textures=None, skins=None, animations=None):
+    """meshes: list of dicts {positions (N,3), normals (N,3), uvs (N,2) or None, indices (M,), material or None,
+    joints (N,4) and weights (N,4) or absent: JOINTS_0 as uint16 and WEIGHTS_0 as float32};
+    nodes: list of dicts {mesh?, skin?, light?, translation?, rotation?, scale?, matrix?, children?};
+    images: list of encoded image files (bytes, PNG); textures: list of image indices (one glTF texture each);
+    skins: list of dicts {joints: node indices, inverseBindMatrices: (n,16) column-major or None};
+    animations: list of dicts {channels: [{node, path, sampler}], samplers: [{input: times, output: (k, width), interpolation}]}.
+    Without skins and animations the file is the bytes it always was."""
     bin_parts, views, accessors = [], [], []
 
     def add(arr, target, ctype, atype):
@@ -75,6 +79,8 @@ def write_glb(path, meshes, nodes, materials, lights=None, images=None, textures
         bin_parts.append(data + b"\0" * (-len(data) % 4))
         views.append({"buffer": 0, "byteOffset": off, "byteLength": len(data), "target": target})
         acc = {"bufferView": len(views) - 1, "componentType": ctype, "count": int(len(arr)), "type": atype}
+        if target is None:
+            del views[-1]["target"]
         if atype == "VEC3":
             a = np.asarray(arr, np.float64)
             acc["min"], acc["max"] = a.min(0).tolist(), a.max(0).tolist()
@@ -87,19 +93,47 @@ def write_glb(path, meshes, nodes, materials, lights=None, images=None, textures
                  "NORMAL": add(np.asarray(m["normals"], np.float32), 34962, 5126, "VEC3")}
         if m.get("uvs") is not None:
             attrs["TEXCOORD_0"] = add(np.asarray(m["uvs"], np.float32), 34962, 5126, "VEC2")
+        if m.get("joints") is not None:
+            attrs["JOINTS_0"] = add(np.asarray(m["joints"], np.uint16), 34962, 5123, "VEC4")
+            attrs["WEIGHTS_0"] = add(np.asarray(m["weights"], np.float32), 34962, 5126, "VEC4")
         prim = {"attributes": attrs, "indices": add(np.asarray(m["indices"], np.uint16), 34963, 5123, "SCALAR")}
         if m.get("material") is not None:
             prim["material"] = m["material"]
         jm.append({"primitives": [prim]})
     jn = []
     for n in nodes:
-        o = {k: n[k] for k in ("mesh", "translation", "rotation", "scale", "matrix", "children", "name") if k in n}
+        o = {k: n[k] for k in ("mesh", "skin", "translation", "rotation", "scale", "matrix", "children", "name") if k in n}
         if "light" in n:
             o["extensions"] = {"KHR_lights_punctual": {"light": n["light"]}}
         jn.append(o)
     doc = {"asset": {"version": "2.0"}, "scene": 0, "scenes": [{"nodes": list(range(len(nodes)))}], "nodes": jn,
            "meshes": jm, "materials": materials, "accessors": accessors, "bufferViews": views,
            "buffers": [{"byteLength": sum(len(b) for b in bin_parts)}]}
+    if skins:
+        doc["skins"] = []
+        for sk in skins:
+            o = {"joints": [int(j) for j in sk["joints"]]}
+            if sk.get("inverseBindMatrices") is not None:
+                o["inverseBindMatrices"] = add(np.asarray(sk["inverseBindMatrices"], np.float32).reshape(-1, 16), None, 5126, "MAT4")
+            doc["skins"].append(o)
+    if animations:
+        doc["animations"] = []
+        for an in animations:
+            samplers = []
+            for sm in an["samplers"]:
+                out = np.asarray(sm["output"], np.float32)
+                out = out.reshape(len(out), -1)
+                times = np.asarray(sm["input"], np.float32)
+                i = add(times, None, 5126, "SCALAR")
+                accessors[i]["min"], accessors[i]["max"] = [float(times.min())], [float(times.max())]
+                samplers.append({"input": i, "output": add(out, None, 5126, {3: "VEC3", 4: "VEC4"}[out.shape[1]]),
+                                 "interpolation": sm.get("interpolation", "LINEAR")})
+            doc["animations"].append({"samplers": samplers, "channels": [
+                {"sampler": int(c["sampler"]), "target": {"node": int(c["node"]), "path": c["path"]}} for c in an["channels"]]})
+        doc["accessors"], doc["bufferViews"] = accessors, views
+        doc["buffers"] = [{"byteLength": sum(len(b) for b in bin_parts)}]
+    if skins and not animations:
+        doc["buffers"] = [{"byteLength": sum(len(b) for b in bin_parts)}]
     if images:
         doc["images"] = []
         for data in images:

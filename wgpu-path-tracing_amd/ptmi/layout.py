@@ -39,9 +39,13 @@ CAMERA = np.dtype([
     ("aperture", F), ("focus_distance", F), ("_p3", U, 2),
 ])
 
+# ptmi_skin_corner (include/ptmi.h ptmi_set_skin): the four joints and weights of one triangle corner; three per listed triangle
+SKIN_CORNER = np.dtype([("joint", U, 4), ("weight", F, 4)])
+
 LIGHT_EMISSIVE, LIGHT_DIRECTIONAL, LIGHT_POINT = 0, 1, 2
 
 assert MATERIAL.itemsize == 128 and TRIANGLE.itemsize == 128
+assert SKIN_CORNER.itemsize == 32
 assert BVH_NODE.itemsize == 48 and LIGHT.itemsize == 48 and CAMERA.itemsize == 96
 assert MATERIAL.fields["albedo_map"][1] == 56 and MATERIAL.fields["emissive_map"][1] == 104
 assert TRIANGLE.fields["uv0"][1] == 96 and TRIANGLE.fields["material_index"][1] == 120

@@ -51,6 +51,7 @@ EXPORTS = [
     "ptmi_debug_alpha_intersect", "ptmi_debug_alpha_occluded",
     "ptmi_set_triangle_groups", "ptmi_transform_groups", "ptmi_transform_status", "ptmi_normal_matrix", "ptmi_debug_read_triangles",
     "ptmi_multi_set_triangle_groups", "ptmi_multi_transform_groups", "ptmi_multi_transform_status",
+    "ptmi_set_skin", "ptmi_pose_skin", "ptmi_skin_status", "ptmi_multi_set_skin", "ptmi_multi_pose_skin", "ptmi_multi_skin_status",
 ]
 MULTI_LOOPBACK = 1
 MULTI_PLANE_MOMENTS, MULTI_PLANE_OUTPUT = 0x100, 0x200      # gather_planes: with the AOV_* bits
@@ -208,6 +209,24 @@ class TransformStatus(ctypes.Structure):
                 "last_moved": int(self.last_moved), "first_bad": int(self.first_bad), "transform_ms": float(self.transform_ms)}
 
 
+class SkinCorner(ctypes.Structure):
+    """ptmi_skin_corner: the joints and weights of one corner of a skinned triangle (include/ptmi.h ptmi_set_skin)"""
+    _fields_ = [("joint", ctypes.c_uint32 * 4), ("weight", ctypes.c_float * 4)]
+
+
+JointTransform, JOINT_TRANSFORM = GroupTransform, GROUP_TRANSFORM      # ptmi_joint_transform: the same record, `group` is the joint
+
+
+class SkinStatus(ctypes.Structure):
+    """struct ptmi_skin_status: the skin in place and the poses since it was set (include/ptmi.h)"""
+    _fields_ = [("present", ctypes.c_uint32), ("n_joints", ctypes.c_uint32), ("n_skinned", ctypes.c_uint32), ("poses", ctypes.c_uint32),
+                ("first_bad", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("pose_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {"present": int(self.present), "n_joints": int(self.n_joints), "n_skinned": int(self.n_skinned), "poses": int(self.poses),
+                "first_bad": int(self.first_bad), "pose_ms": float(self.pose_ms)}
+
+
 class AlphaParams(ctypes.Structure):
     """ptmi_alpha_params; max_layers 0 picks the default (include/ptmi.h)"""
     _fields_ = [("max_layers", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
@@ -269,6 +288,8 @@ _SHARED = {
     "set_alpha_cutoff": [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p], "alpha_status": [ctypes.c_void_p],
     "set_triangle_groups": [ctypes.c_void_p, ctypes.c_uint32], "transform_groups": [ctypes.c_void_p, ctypes.c_uint32],
     "transform_status": [ctypes.c_void_p],
+    "set_skin": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32], "pose_skin": [ctypes.c_void_p, ctypes.c_uint32],
+    "skin_status": [ctypes.c_void_p],
 }
 _lib = None
 
@@ -383,6 +404,14 @@ def group_ops(ops):
         out[i]["group"], out[i]["m"] = g, m
         out[i]["nm"] = normal_matrix(m) if nm is None else np.asarray(nm, np.float32).reshape(9)
     return out
+
+
+def joint_ops(joints):
+    """JOINT_TRANSFORM records of a complete pose from an array of them, or from one (m, nm) pair per joint in joint order; nm None
+    derives it (normal_matrix). Record i names joint i."""
+    if isinstance(joints, np.ndarray) and joints.dtype == JOINT_TRANSFORM:
+        return np.ascontiguousarray(joints)
+    return group_ops([(i,) + tuple(j) for i, j in enumerate(joints)])
 
 
 def _env_texels(texels):
@@ -593,6 +622,36 @@ class _Handle:
     def transform_status(self):
         st = TransformStatus()
         self._ck(self._c.transform_status(self.h, ctypes.byref(st)))
+        return st
+
+    # -- skinned triangles posed on the device (include/ptmi.h ptmi_set_skin) --------------------------------------------
+    def set_skin(self, triangles, corners=None, n_joints=0, n_skinned=None):
+        """lists the skinned triangles (ascending uint32 indices, uploaded order) with three layout.SKIN_CORNER records each, for a
+        skeleton of n_joints, and snapshots their rest pose; triangles None removes the skin. corners None passes NULL and n_skinned
+        overrides the count passed (for tests)."""
+        if triangles is None:
+            self._ck(self._c.set_skin(self.h, None, None, 0, n_joints))
+            return
+        t = np.ascontiguousarray(triangles, np.uint32).reshape(-1)
+        q = None if corners is None else np.ascontiguousarray(corners, layout.SKIN_CORNER).reshape(-1)
+        if q is not None and len(q) != 3 * len(t):
+            raise ValueError(f"{len(q)} corner records for {len(t)} triangles: three each")
+        self._ck(self._c.set_skin(self.h, _p(t) if len(t) else None, None if q is None or not len(q) else _p(q),
+                                  len(t) if n_skinned is None else n_skinned, n_joints))
+
+    def pose_skin(self, joints, n_joints=None):
+        """poses the skin: every listed triangle becomes the blend of its joints' matrices applied to its rest pose, and the trees are
+        refitted on the device. joints: a complete pose, JOINT_TRANSFORM records or one (m, nm_or_None) pair per joint (see joint_ops).
+        n_joints overrides the count passed (for tests; joints None then passes NULL)."""
+        if joints is None:
+            self._ck(self._c.pose_skin(self.h, None, n_joints or 0))
+            return
+        rec = joint_ops(joints)
+        self._ck(self._c.pose_skin(self.h, _p(rec) if len(rec) else None, len(rec) if n_joints is None else n_joints))
+
+    def skin_status(self):
+        st = SkinStatus()
+        self._ck(self._c.skin_status(self.h, ctypes.byref(st)))
         return st
 
     # -- alpha cutouts (include/ptmi.h ptmi_set_alpha_cutoff) ---------------------------------------------------------
