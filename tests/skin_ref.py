@@ -48,6 +48,16 @@ def point_rows(M, p):
     return out
 
 
+def q_rows(NM, n):
+    """q = NM n alone, a matrix per row, as normal_rows computes it before it normalises (for transform_ref.normal_classes)"""
+    n = np.asarray(n, np.float32)
+    q = np.empty_like(n)
+    with np.errstate(all="ignore"):
+        for k in range(3):
+            q[:, k] = (NM[:, 3 * k] * n[:, 0] + NM[:, 3 * k + 1] * n[:, 1]) + NM[:, 3 * k + 2] * n[:, 2]
+    return q
+
+
 def normal_rows(NM, n):
     """transform_ref.normal with a matrix per row: NM (n, 9), n (n, 3)"""
     n = np.asarray(n, np.float32)
@@ -78,19 +88,30 @@ def skinned(tris, rest, listed, corners, joints):
     return out
 
 
-def first_bad(tris, rest, listed, corners, joints, own):
-    """the smallest listed triangle the check pass refuses (ptmi_update_triangles' vertex checks on the skinned vertices), or NONE"""
-    t = skinned(tris, rest, listed, corners, joints)
+def offenders(tris, rest, listed, corners, joints, own):
+    """every list ENTRY (position in `listed`) the check pass refuses (ptmi_update_triangles' vertex checks on the skinned vertices),
+    ascending; listed[offenders] are the triangles"""
+    listed = np.asarray(listed, np.int64)
+    t = skinned(tris, rest, listed, corners, joints)[listed]
     with np.errstate(all="ignore"):
         bad = ~(np.isfinite(t["v0"]).all(axis=1) & np.isfinite(t["v1"]).all(axis=1) & np.isfinite(t["v2"]).all(axis=1))
         if own:
             a = t["v0"]
             for f in ("v1", "v2"):
                 bad |= ~np.isfinite(a + (t[f] - a)).all(axis=1)
-    named = np.zeros(len(tris), bool)
-    named[np.asarray(listed, np.int64)] = True
-    bad &= named
-    return int(np.flatnonzero(bad)[0]) if bad.any() else NONE
+    return np.flatnonzero(bad)
+
+
+def first_bad(tris, rest, listed, corners, joints, own):
+    """the smallest listed triangle among offenders() (the list ascends: the first entry's), or NONE"""
+    bad = offenders(tris, rest, listed, corners, joints, own)
+    return int(np.asarray(listed, np.int64)[bad[0]]) if len(bad) else NONE
+
+
+def joint_raw(m, nm=None):
+    """joint() without the + 0: an (m, nm) pair as given or derived, negative zeros kept (a mirror's cofactors hold some)"""
+    m = np.asarray(m, np.float32).reshape(12)
+    return m.copy(), tref.normal_matrix(m) if nm is None else np.asarray(nm, np.float32).reshape(9).copy()
 
 
 def one_hot(joint_of_triangle):

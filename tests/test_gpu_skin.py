@@ -9,7 +9,8 @@ edited scene.
 The scenes are the smallest that cover: a list of 5 (no multiple of 8: a wave with three idle octets), a list of 1, a scattered third
 (332) and half (6 246: no multiple of 8 or of 64, many blocks, the last one ending in a partial wave), four non-zero weights per
 corner, the device builder above 4 096 triangles, and 600 joints, which take the instantiation that reads the joint records from
-global memory (above 512), every one of them referenced.
+global memory (above 512), every one of them referenced. Lists of more than one round of the grid, the joint counts 512 and 513, the
+magnitude classes of the normals and the weights as given are in tests/test_gpu_edit_edges.py.
 
 Every case fails without the feature: the binding has no set_skin."""
 import numpy as np

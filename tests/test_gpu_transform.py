@@ -10,6 +10,8 @@ render of the edited scene - pinned already by the scene-update suite; here it t
 The scenes are the smallest that cover: a triangle count that is no multiple of 8 or of 64 (996, 304, 402, 4, 5, 12 492), a group of
 one triangle, one group that is everything, members that straddle wave boundaries (a seeded random assignment scatters them), an empty
 group, the device builder above 4 096 triangles, and more ops than one launch holds in LDS (600 over a 600-group table on grid80).
+Scenes of more than one round of the grid, the op counts 512, 513 and 1 025 and the magnitude classes of the normals are in
+tests/test_gpu_edit_edges.py.
 
 Every case fails without the feature: the binding has no set_triangle_groups."""
 import dataclasses

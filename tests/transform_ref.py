@@ -58,6 +58,20 @@ def normal(nm, n):
     return out
 
 
+def normal_classes(q):
+    """which magnitude class of the normal formula each row of q = nm n (n, 3) falls to: a dict of boolean masks over the rows.
+    q_denormal: a component of q is a denormal; l2_zero: l2 underflows to 0 while q != 0 (q is stored unnormalised); l2_denormal:
+    l2 > 0 is a denormal; l2_large: l2 is finite and within a factor 256 of the largest float; l2_inf: l2 overflows with q finite
+    (the result is a signed zero)"""
+    q = np.asarray(q, np.float32)
+    tiny, big = np.finfo(np.float32).tiny, F32_MAX / np.float32(256.0)
+    with np.errstate(all="ignore"):
+        l2 = (q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1]) + q[:, 2] * q[:, 2]
+    return {"q_denormal": ((q != 0) & (np.abs(q) < tiny)).any(axis=1), "l2_zero": (l2 == 0) & (q != 0).any(axis=1),
+            "l2_denormal": (l2 > 0) & (l2 < tiny), "l2_large": np.isfinite(l2) & (l2 > big),
+            "l2_inf": np.isinf(l2) & np.isfinite(q).all(axis=1)}
+
+
 def transformed(tris, rest, groups, ops):
     """the live records after transform_groups(ops): members of a named group become T(rest), everything else keeps its bytes.
     ops: (group, m, nm) tuples, m 12 and nm 9 floats."""
@@ -74,8 +88,8 @@ def transformed(tris, rest, groups, ops):
     return out
 
 
-def first_bad(tris, rest, groups, ops, own):
-    """the smallest member triangle the check pass refuses (ptmi_update_triangles' vertex checks on the transformed vertices), or NONE"""
+def offenders(tris, rest, groups, ops, own):
+    """every member triangle the check pass refuses (ptmi_update_triangles' vertex checks on the transformed vertices), ascending"""
     t = transformed(tris, rest, groups, ops)
     named = np.isin(np.asarray(groups, np.uint32), [g for g, _, _ in ops])
     with np.errstate(all="ignore"):
@@ -85,7 +99,25 @@ def first_bad(tris, rest, groups, ops, own):
             for f in ("v1", "v2"):
                 bad |= ~np.isfinite(a + (t[f] - a)).all(axis=1)
     bad &= named
-    return int(np.flatnonzero(bad)[0]) if bad.any() else NONE
+    return np.flatnonzero(bad)
+
+
+def first_bad(tris, rest, groups, ops, own):
+    """the smallest of offenders(), or NONE"""
+    bad = offenders(tris, rest, groups, ops, own)
+    return int(bad[0]) if len(bad) else NONE
+
+
+def launch_ranges(groups, ops, chunk=512):
+    """the triangle range [first, end) each launch of a pass walks, as csrc/scene_transform.hip run_pass sets it: one launch per
+    chunk of `chunk` ops in call order, from the lowest member of the chunk's groups rounded down to a multiple of 8 to one past the
+    highest; None for a chunk whose groups have no member. A test uses it to say which block and round a triangle falls to."""
+    groups = np.asarray(groups, np.uint32)
+    out = []
+    for f in range(0, len(ops), chunk):
+        member = np.flatnonzero(np.isin(groups, [g for g, _, _ in ops[f:f + chunk]]))
+        out.append((int(member[0]) & ~7, int(member[-1]) + 1) if len(member) else None)
+    return out
 
 
 def affine(rot=None, scale=(1.0, 1.0, 1.0), shift=(0.0, 0.0, 0.0)):
