@@ -170,10 +170,26 @@ def test_transforms_are_absolute_from_the_rest_pose(ctx_a):
     assert second[groups == 3].tobytes() == first[groups == 3].tobytes()
     st = ctx_a.transform_status()
     assert st.transforms == 2 and st.last_moved == int((groups == 1).sum()) and ctx_a.scene_update_status().updates == 2
-    # no ops, and ops on nothing: what update_triangles(0, 0 records) does
+    # no ops: what update_triangles(0, 0 records) does
     ctx_a.transform_groups(records([]))
     assert ctx_a.read_triangles().tobytes() == second.tobytes()
     assert ctx_a.transform_status().transforms == 3 and ctx_a.transform_status().last_moved == 0 and ctx_a.scene_update_status().updates == 3
+    # ops on nothing: one op, and the group it names has no member (group 2 of the grouping "empty")
+    s = scene("feature_box")
+    groups = grouping(s, "empty")
+    assert not (groups == 2).any()
+    ctx_a.upload_scene(s)
+    ctx_a.set_triangle_groups(groups)
+    before, t0, u0 = ctx_a.read_triangles(), ctx_a.transform_status().transforms, ctx_a.scene_update_status().updates
+    ctx_a.transform_groups(records([ref.op(2, SCALE)]))
+    st = ctx_a.transform_status()
+    assert ctx_a.read_triangles().tobytes() == before.tobytes() == s.tris.tobytes()
+    assert (st.transforms, st.last_moved, st.first_bad) == (t0 + 1, 0, NONE) and ctx_a.scene_update_status().updates == u0 + 1
+    ga = int(groups[len(groups) // 2])
+    ctx_a.transform_groups(records([ref.op(ga, ROTATE)]))                # a real group after it still equals the model
+    assert ctx_a.read_triangles().tobytes() == ref.transformed(s.tris, ref.rest_of(s.tris), groups, [ref.op(ga, ROTATE)]).tobytes()
+    st = ctx_a.transform_status()
+    assert (st.transforms, st.last_moved, st.first_bad) == (t0 + 2, int((groups == ga).sum()), NONE)
 
 
 def test_update_triangles_rebases_the_rest_pose(ctx_a, ctx_b):

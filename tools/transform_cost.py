@@ -12,10 +12,10 @@ Per scene and share, in ONE process and in turn: 2 warm-up runs, then the median
   update_ms      ptmi_scene_update_status.refit_ms of update_triangles (its copy and refit included)
 with the wall time around each call beside it. Every run moves the group to another matrix, so no run finds its work done.
 
-The driver runs one worker process per layout of the kernel - the library as built (eight lanes per triangle) and, where
-lib/ab/libptmi_lpt.so exists (make -C wgpu-path-tracing_amd variant NAME=lpt EXTRA=-DPT_TRANSFORM_LANES=1), the lane-per-triangle
-build - each under its own `timeout`, one after the other, and stops at the first that fails. It writes --json (default
-profiles/transform_cost.json) and prints the first section of profiles/README.md for pasting.
+The driver runs one worker process per library - the one as built and, where lib/ab/libptmi_old.so exists (the parent commit's
+library, for a same-box comparison of a change to this path with its parent), that one - each under its own `timeout`, one after the
+other, and stops at the first that fails. It writes --json (default profiles/transform_cost.json) and prints the first section of
+profiles/README.md for pasting. (The lane-per-triangle layout the kernel was once measured against is in profiles/README.md.)
 
     python tools/transform_cost.py [--rounds 10] [--warmup 2] [--scenes grid_1m,cornell_spheres] [--json out.json] [--limit 480]
 """
@@ -33,7 +33,7 @@ PKG = os.path.join(ROOT, "wgpu-path-tracing_amd")
 sys.path.insert(0, PKG)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-LAYOUTS = {"eight_lanes": os.path.join(PKG, "lib", "libptmi.so"), "lane_per_triangle": os.path.join(PKG, "lib", "ab", "libptmi_lpt.so")}
+LAYOUTS = {"eight_lanes": os.path.join(PKG, "lib", "libptmi.so"), "parent": os.path.join(PKG, "lib", "ab", "libptmi_old.so")}
 
 
 def med(xs):

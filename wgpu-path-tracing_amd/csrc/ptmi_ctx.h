@@ -11,13 +11,15 @@
 //   alpha.hip          alpha cutouts: the cutoff table, the two resolve loops between the existing kernels, their debug entry points
 //   scene_rebuild.hip  the walked own-leaf tree rebuilt in place: the unit list on the device, the swap (ptmi_rebuild_tree)
 //   motion.hip         reprojection across a geometry edit: the previous positions, their commit, the motion plane (ptmi_set_motion)
-//   scene_transform.hip  triangle groups moved by matrix on the device: the table, the rest pose, the check and write passes
-//   scene_skin.hip     skinned triangles posed on the device: the list, the corner records, the rest pose, the check and write passes
+//   scene_pose.hip     what the two below share on the host: the check-then-write sequence of a pose, the rest-pose snapshot
+//   scene_transform.hip  triangle groups moved by matrix on the device: the table, the rest pose, the check and write kernel
+//   scene_skin.hip     skinned triangles posed on the device: the list, the corner records, the rest pose, the check and write kernel
 #pragma once
 #include "ptmi.h"
 #include "pt_device.h"
 
 #include <chrono>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <deque>
@@ -100,12 +102,12 @@ enum SceneBuf {
     kGroupTab,                         // one group id per uploaded triangle
     kGroupRest,                        // the rest pose: v0, v1, v2, n0, n1, n2 of every triangle, 6 float4 each
     kGroupOps,                         // the op records of the ptmi_transform_groups call at hand (grown on demand)
-    kGroupMap,                         // 4 words (word 0: the smallest offending triangle of the check pass), then group -> op index
+    kGroupMap,                         // the head with the check word (pt_transform.h kPoseHead), then group -> op index
     // the skin (ptmi_set_skin; scene_skin.hip), gone with the next upload; one entry of each per LISTED triangle, in list order:
     kSkinList,                         // the listed triangles' indices, ascending
     kSkinCorners,                      // their corner records: 3 ptmi_skin_corner = 6 float4 each
     kSkinRest,                         // their rest pose: v0, v1, v2, n0, n1, n2, 6 float4 each
-    kSkinJoints,                       // 4 words (word 0: the smallest offending triangle of the check pass), then the joint records of the
+    kSkinJoints,                       // the head with the check word (pt_transform.h kPoseHead), then the joint records of the
                                        // ptmi_pose_skin call at hand
     kSceneBufs
 };
@@ -284,13 +286,55 @@ hipError_t quiesce(ptmi_ctx *c);
 void drop_plan(ptmi_ctx *c);
 int make_plan(ptmi_ctx *c);
 int walked_cost(ptmi_ctx *c, double &cost);
-// What ptmi_update_triangles, ptmi_transform_groups and ptmi_pose_skin share around the write of the records. refit_begin: the tree must be one a refit
+// What ptmi_update_triangles and a refusable pose (pose_refusable below) share around the write of the records. refit_begin: the tree must be one a refit
 // can serve (PTMI_E_UNSUPPORTED otherwise, nothing touched). refit_ready: waits for the work in flight and makes the plan at the first
 // edit after an upload. refit_written: everything behind the write - the triangle images, the light triangles, both trees, the root
 // boxes, the header, the cost and the status (updates grows by one; refit_ms counts from t0, when the entry point was entered).
 int refit_begin(ptmi_ctx *c);
 int refit_ready(ptmi_ctx *c);
 int refit_written(ptmi_ctx *c, std::chrono::steady_clock::time_point t0);
+
+// scene_pose.hip: a REFUSABLE POSE, the part of ptmi_transform_groups and ptmi_pose_skin between their own host checks and their own
+// counters. Every live record a pose moves is a function of a rest record and of the call's matrix records, and the call is all or
+// nothing without a staging buffer: a check pass transforms the vertices and leaves the smallest offending triangle in the check
+// word, and only when that is still "none" does the write pass run. In order: refit_begin; the device is selected and drained; stage;
+// pass(false); the check word is read (one asynchronous copy, one stream synchronise); a refusal sets *first_bad and the error, before
+// refit_ready, so that a refused first edit leaves no plan and no status behind; refit_ready; pass(true); motion_widen over [lo, hi];
+// refit_written(t0). moves false: nothing is staged, checked or written, and the refit still runs.
+// (a reference to a callable of the caller's, which outlives the call: nothing is owned or allocated)
+template <class Sig> struct FnRef;
+template <class R, class... A> struct FnRef<R(A...)> {
+    void *fn; R (*call)(void *, A...);
+    template <class F> FnRef(F &f) : fn(&f), call([](void *p, A... a) -> R { return (*static_cast<F *>(p))(a...); }) {}
+    R operator()(A... a) const { return call(fn, a...); }
+};
+struct PoseCall {
+    FnRef<int()> stage;                         // the call's records to the device, and "none" to the check word
+    FnRef<int(bool write)> pass;                // the launches of one pass
+    bool moves = true;
+    uint32_t *check_word = nullptr;             // device memory (pt_transform.h kPoseHead)
+    uint32_t *first_bad = nullptr;              // the status field a refusal sets
+    const char *how = "";                       // "transformed", "skinned": the word of the refusal
+    uint32_t lo = 0, hi = 0;                    // the lowest and the highest triangle the write pass may touch
+};
+int pose_refusable(ptmi_ctx *c, std::chrono::steady_clock::time_point t0, const PoseCall &p);
+// rest rows [first, first + count) from the live records of their triangles, on c's stream: row e is triangle list[e] (device memory),
+// or triangle e where list is NULL
+int pose_snapshot(ptmi_ctx *c, uint32_t first, uint32_t count, const void *list, void *rest);
+// the host checks of n 96-byte matrix records (`noun` i of `type` in the messages): the reserved words, then what id_ok(i, record)
+// has to say about the id word (which group, which joint: the caller's own rule, in the place its message has always had), then that m
+// and nm are finite. PTMI_E_INVALID with the reason in err.
+template <class IdOk>
+int check_matrix_records(const ptmi_group_transform *recs, uint32_t n, const char *noun, const char *type, std::string &err, IdOk id_ok) {
+    for (uint32_t i = 0; i < n; i++) {
+        const ptmi_group_transform &o = recs[i];
+        if (o.reserved0 || o.reserved1) return fail(err, PTMI_E_INVALID, "%s %u: %s.reserved must be 0", noun, i, type);
+        if (const int rc = id_ok(i, o)) return rc;
+        for (float v : o.m) if (!std::isfinite(v)) return fail(err, PTMI_E_INVALID, "%s %u: a matrix entry is not finite", noun, i);
+        for (float v : o.nm) if (!std::isfinite(v)) return fail(err, PTMI_E_INVALID, "%s %u: a normal-matrix entry is not finite", noun, i);
+    }
+    return PTMI_OK;
+}
 
 // scene_transform.hip: the table goes with its scene (ptmi_upload_scene; the buffers have gone with the others); records
 // [first, first + count) that ptmi_update_triangles has just written become the rest pose of their triangles, on c's stream

@@ -6,46 +6,33 @@
 // listed triangle's live record becomes the blend of its joints' matrices applied to its rest record, and the refit of
 // ptmi_update_triangles follows (scene_update.hip refit_written: the same routine, not a copy).
 //
-// All-or-nothing by a CHECK PASS followed by a WRITE PASS, one kernel template, as in scene_transform.hip: the check pass skins the
-// three vertices, applies ptmi_update_triangles' vertex checks and leaves the smallest offending triangle in word 0 of
-// buf[kSkinJoints]; only when that word is still "none" does the write pass run.
+// All-or-nothing by a CHECK PASS followed by a WRITE PASS, the sequence every pose source runs (scene_pose.hip pose_refusable; the
+// check word is word 0 of buf[kSkinJoints]). This file's own: the list and the corner records, the blend, and k_skin, one kernel
+// template for both passes: the check pass skins the three vertices and applies ptmi_update_triangles' vertex checks.
 //
-// Layout: the kernel walks the LIST, eight lanes per listed triangle, one float4 each. Lane q < 6 of an octet loads float4 q of the
-// rest record and float4 q of the corner records, so neighbouring lanes read neighbouring float4 of both arrays; the corner record of
-// corner k (joints in float4 2k, weights in float4 2k + 1) reaches the lanes that need it through __shfl. Lanes 0-2 blend the 12 entries
-// of m for their corner and transform a vertex, lanes 3-5 blend the 9 entries of nm and transform a normal; no lane blends both, and
-// lanes 6 and 7 idle. The stores go to whole 128-byte lines of the live records, scattered as the list is. Because the list ascends,
-// the lowest set bit of the check pass's ballot is the smallest offender of the wave: one atomicMin per wave.
+// Layout: the kernel walks the LIST, eight lanes per listed triangle, one float4 each (pt_transform.h Octet has the coordinates and why
+// lanes 6 and 7 idle). Lane q < 6 of an octet loads float4 q of the rest record and float4 q of the corner records, so neighbouring
+// lanes read neighbouring float4 of both arrays; the corner record of corner k (joints in float4 2k, weights in float4 2k + 1) reaches
+// the lanes that need it through __shfl. Lanes 0-2 blend the 12 entries of m for their corner and transform a vertex, lanes 3-5 blend
+// the 9 entries of nm and transform a normal; no lane blends both. The stores go to whole 128-byte lines of the live records,
+// scattered as the list is. Because the list ascends, the smallest offending entry of a wave is its smallest offending triangle.
 // The joint records sit in LDS up to kLdsJoints = 512 of them (48 KB); a second instantiation of the same template reads them from
 // global memory up to 65 536. Either way one launch covers the whole list.
 #include "ptmi_ctx.h"
-#include "pt_transform.h"
+#include "pt_dev_scratch.h"
+#include "pt_transform.h"   // the arithmetic, the octet layout, the check tail and the constants, shared with scene_transform.hip
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstring>
 
 namespace {
 
-constexpr int TB = 256;
-constexpr int kOctets = TB / 8;              // listed triangles per block and round
 constexpr uint32_t kLdsJoints = 512u;        // joint records a block keeps in LDS
 constexpr uint32_t kMaxJoints = 65536u;
-constexpr uint32_t kNone = 0xFFFFFFFFu;
-constexpr size_t kHeadBytes = 16;            // in front of the joint records; word 0: the check pass's smallest offender
 static_assert(sizeof(ptmi_skin_corner) == 32 && 3 * sizeof(ptmi_skin_corner) == kRestQ * sizeof(float4), "three corner records are 6 float4");
 static_assert(sizeof(struct ptmi_skin_status) == 32, "ptmi_skin_status is 32 bytes");
 static_assert(kLdsJoints * sizeof(ptmi_joint_transform) == 48u * 1024u, "the joint records of the LDS instantiation take 48 KB");
-
-// the live records of the list entries [first, first + count) to their rest pose: a thread per float4
-__global__ void __launch_bounds__(TB) k_skin_snapshot(uint32_t first, uint32_t count, const uint32_t *__restrict__ list,
-                                                      const float4 *__restrict__ live, float4 *__restrict__ rest) {
-    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
-    if (i >= (size_t)count * kRestQ) return;
-    const size_t e = first + i / kRestQ, q = i % kRestQ;
-    rest[e * kRestQ + q] = live[(size_t)list[e] * kLiveQ + q];
-}
 
 // word e of the blend of four joint records (24 words each, at J) by the weights w: the order of include/ptmi.h, every slot evaluated
 __device__ __forceinline__ float blend(const float *J, uint4 j, float4 w, int e) {
@@ -66,23 +53,22 @@ __global__ void __launch_bounds__(TB) k_skin(uint32_t n_listed, const uint32_t *
         __syncthreads();
     }
     const float *J = LDS ? reinterpret_cast<const float *>(s_joints4) : reinterpret_cast<const float *>(joints);
-    const uint32_t lane = threadIdx.x & 63u, l8 = threadIdx.x & 7u, head = lane & ~7u;
-    const uint32_t corner = l8 < 3u ? l8 : (l8 < 6u ? l8 - 3u : 0u);    // whose corner record this lane blends by
-    const int src = (int)(head + 2u * corner);
-    const uint32_t stride = gridDim.x * kOctets;
+    const Octet o = octet_here();
+    const uint32_t corner = o.l8 < 3u ? o.l8 : (o.l8 < 6u ? o.l8 - 3u : 0u);    // whose corner record this lane blends by
+    const int src = (int)(o.head + 2u * corner);
     uint32_t worst = kNone;                                              // the smallest offending list entry this lane has seen
-    for (uint32_t base = blockIdx.x * kOctets; base < n_listed; base += stride) {
-        const uint32_t entry = base + (threadIdx.x >> 3);
+    for (uint32_t base = blockIdx.x * kOctets; base < n_listed; base += octet_stride()) {
+        const uint32_t entry = base + o.slot;
         const bool listed = entry < n_listed;
         float4 p = make_float4(0.0f, 0.0f, 0.0f, 0.0f), cq = p;
         uint32_t tri = 0u;
-        if (listed && l8 < 6u) {
-            p = rest[(size_t)entry * kRestQ + l8];
-            cq = corners[(size_t)entry * kRestQ + l8];
+        if (listed && o.l8 < 6u) {
+            p = rest[(size_t)entry * kRestQ + o.l8];
+            cq = corners[(size_t)entry * kRestQ + o.l8];
         }
         if (WRITE) {
-            if (listed && l8 == 0u) tri = list[entry];
-            tri = (uint32_t)__shfl((int)tri, (int)head);
+            if (listed && o.l8 == 0u) tri = list[entry];
+            tri = (uint32_t)__shfl((int)tri, (int)o.head);
         }
         uint4 j;
         float4 w;
@@ -90,41 +76,21 @@ __global__ void __launch_bounds__(TB) k_skin(uint32_t n_listed, const uint32_t *
         j.z = (uint32_t)__shfl(__float_as_int(cq.z), src); j.w = (uint32_t)__shfl(__float_as_int(cq.w), src);
         w.x = __shfl(cq.x, src + 1); w.y = __shfl(cq.y, src + 1); w.z = __shfl(cq.z, src + 1); w.w = __shfl(cq.w, src + 1);
         float4 r = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (listed && l8 < (WRITE ? 6u : 3u)) {
+        if (listed && o.l8 < (WRITE ? 6u : 3u)) {
             float b[kOpWords] = {};                                      // the blended record: m for a vertex lane, nm for a normal lane
-            if (l8 < 3u) {
+            if (o.l8 < 3u) {
 #pragma unroll
                 for (int e = 0; e < 12; e++) b[kOpM + e] = blend(J, j, w, kOpM + e);
             } else {
 #pragma unroll
                 for (int e = 0; e < 9; e++) b[kOpNm + e] = blend(J, j, w, kOpNm + e);
             }
-            r = transform_row(b, l8, p);
-            if (WRITE) live[(size_t)tri * kLiveQ + l8] = r;
+            r = transform_row(b, o.l8, p);
+            if (WRITE) live[(size_t)tri * kLiveQ + o.l8] = r;
         }
-        if (!WRITE) {
-            // lane 0 of the octet holds a = v0', lanes 1 and 2 hold b and d
-            const float4 a = make_float4(__shfl(r.x, (int)head), __shfl(r.y, (int)head), __shfl(r.z, (int)head), 0.0f);
-            const bool bad = listed && l8 < 3u && vertex_bad(a, r, own && l8 != 0u);
-            const unsigned long long mask = __ballot(bad);
-            if (mask) {                                                  // entries ascend with the lane: the lowest set bit is the smallest
-                const uint32_t l = (uint32_t)__ffsll((long long)mask) - 1u;
-                worst = min(worst, base + ((threadIdx.x & ~63u) >> 3) + (l >> 3));
-            }
-        }
+        if (!WRITE) worst = check_tail(o, r, listed, own, base, worst);
     }
-    if (!WRITE && lane == 0u && worst != kNone) atomicMin(first_bad, list[worst]);   // (the list ascends: the smallest entry is the smallest triangle)
-}
-
-dim3 blocks_for(size_t threads) { return dim3((unsigned)((threads + TB - 1) / TB)); }
-
-int snapshot(ptmi_ctx *c, uint32_t first, uint32_t count, const void *list, void *rest) {
-    if (!count) return PTMI_OK;
-    k_skin_snapshot<<<blocks_for((size_t)count * kRestQ), TB, 0, c->stream>>>(first, count, static_cast<const uint32_t *>(list),
-                                                                              reinterpret_cast<const float4 *>(c->sc.tris),
-                                                                              static_cast<float4 *>(rest));
-    HIP_TRY(c, hipGetLastError());
-    return PTMI_OK;
+    if (!WRITE && o.lane == 0u && worst != kNone) atomicMin(first_bad, list[worst]);   // (the list ascends: the smallest entry is the smallest triangle)
 }
 
 uint32_t *head_of(ptmi_ctx *c) { return static_cast<uint32_t *>(c->buf[kSkinJoints]); }
@@ -133,13 +99,12 @@ uint32_t *head_of(ptmi_ctx *c) { return static_cast<uint32_t *>(c->buf[kSkinJoin
 template <bool WRITE>
 int run_pass(ptmi_ctx *c) {
     const uint32_t n = c->skin.n_skinned, nj = c->skin.n_joints;
-    const uint32_t want = (n + kOctets - 1) / kOctets, most = (uint32_t)std::max(1, c->n_cu) * 8u;
     const bool lds = nj <= kLdsJoints;
     const auto kernel = lds ? k_skin<WRITE, true> : k_skin<WRITE, false>;
-    kernel<<<dim3(std::min(want, most)), TB, lds ? (size_t)nj * sizeof(ptmi_joint_transform) : 0, c->stream>>>(
+    kernel<<<pose_blocks(n, c->n_cu), TB, lds ? (size_t)nj * sizeof(ptmi_joint_transform) : 0, c->stream>>>(
         n, static_cast<const uint32_t *>(c->buf[kSkinList]), static_cast<const float4 *>(c->buf[kSkinCorners]),
         static_cast<const float4 *>(c->buf[kSkinRest]),
-        reinterpret_cast<const float4 *>(static_cast<const char *>(c->buf[kSkinJoints]) + kHeadBytes), nj,
+        reinterpret_cast<const float4 *>(static_cast<const char *>(c->buf[kSkinJoints]) + kPoseHeadBytes), nj,
         reinterpret_cast<float4 *>(const_cast<ptmi_triangle *>(c->sc.tris)), c->sc.own, head_of(c));
     HIP_TRY(c, hipGetLastError());
     return PTMI_OK;
@@ -172,14 +137,10 @@ int pt_check_skin_pose(const ptmi_ctx *c, const ptmi_joint_transform *joints, ui
     if (!c->skin.present) return fail(err, PTMI_E_STATE, "no skin is in place (ptmi_set_skin)");
     if (!joints) return fail(err, PTMI_E_INVALID, "joints is NULL");
     if (n_joints != c->skin.n_joints) return fail(err, PTMI_E_INVALID, "%u joints: the skin was set with %u", n_joints, c->skin.n_joints);
-    for (uint32_t i = 0; i < n_joints; i++) {
-        const ptmi_joint_transform &o = joints[i];
-        if (o.reserved0 || o.reserved1) return fail(err, PTMI_E_INVALID, "joint %u: ptmi_joint_transform.reserved must be 0", i);
+    return check_matrix_records(joints, n_joints, "joint", "ptmi_joint_transform", err, [&](uint32_t i, const ptmi_joint_transform &o) -> int {
         if (o.group != i) return fail(err, PTMI_E_INVALID, "record %u names joint %u: a pose lists every joint in order", i, o.group);
-        for (float v : o.m) if (!std::isfinite(v)) return fail(err, PTMI_E_INVALID, "joint %u: a matrix entry is not finite", i);
-        for (float v : o.nm) if (!std::isfinite(v)) return fail(err, PTMI_E_INVALID, "joint %u: a normal-matrix entry is not finite", i);
-    }
-    return PTMI_OK;
+        return PTMI_OK;
+    });
 }
 
 PT_HOST {
@@ -196,7 +157,7 @@ int skin_rebase(ptmi_ctx *c, uint32_t first, uint32_t count) {
     const uint32_t e0 = (uint32_t)(std::lower_bound(l.begin(), l.end(), first) - l.begin());
     const uint64_t end = (uint64_t)first + count;
     const uint32_t e1 = end > kNone ? (uint32_t)l.size() : (uint32_t)(std::lower_bound(l.begin(), l.end(), (uint32_t)end) - l.begin());
-    return snapshot(c, e0, e1 - e0, c->buf[kSkinList], c->buf[kSkinRest]);
+    return pose_snapshot(c, e0, e1 - e0, c->buf[kSkinList], c->buf[kSkinRest]);
 }
 
 }  // namespace pt_host
@@ -212,23 +173,22 @@ int ptmi_set_skin(ptmi_ctx *c, const uint32_t *triangle, const ptmi_skin_corner 
     HIP_TRY(c, sync_all(c));
     if (!triangle || n == 0u) { skin_forget(c); return PTMI_OK; }
     const size_t rec = (size_t)n * kRestQ * sizeof(float4);
-    void *list = nullptr, *corn = nullptr, *rest = nullptr, *jnt = nullptr;
-    hipError_t e = hipMalloc(&list, (size_t)n * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&corn, rec);
-    if (e == hipSuccess) e = hipMalloc(&rest, rec);
-    if (e == hipSuccess) e = hipMalloc(&jnt, kHeadBytes + (size_t)n_joints * sizeof(ptmi_joint_transform));
-    if (e == hipSuccess) e = hipMemcpy(list, triangle, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(corn, corners, rec, hipMemcpyHostToDevice);
+    DevScratch fresh;                                               // freed on every way out but the last
+    uint32_t *list = fresh.get<uint32_t>(n);
+    char *corn = fresh.get<char>(rec), *rest = fresh.get<char>(rec), *jnt = fresh.get<char>(kPoseHeadBytes + (size_t)n_joints * sizeof(ptmi_joint_transform));
+    hipError_t e = fresh.error;
     int rs = PTMI_OK;
-    if (e == hipSuccess && !(rs = snapshot(c, 0u, n, list, rest))) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess || rs) {
-        dfree(list); dfree(corn); dfree(rest); dfree(jnt);
-        if (rs) return rs;
+    if (hip_ok(e) && hip_ok(e = hipMemcpy(list, triangle, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice)) &&
+        hip_ok(e = hipMemcpy(corn, corners, rec, hipMemcpyHostToDevice)) && !(rs = pose_snapshot(c, 0u, n, list, rest)))
+        e = hipStreamSynchronize(c->stream);
+    if (rs) return rs;
+    if (!hip_ok(e)) {
         (void)hipGetLastError();
         return fail(c, PTMI_E_HIP, "the skin could not be made: %s (the previous skin, if any, is still in place)", hipGetErrorString(e));
     }
     skin_forget(c);
-    c->buf[kSkinList] = list; c->buf[kSkinCorners] = corn; c->buf[kSkinRest] = rest; c->buf[kSkinJoints] = jnt;
+    c->buf[kSkinList] = fresh.keep(list); c->buf[kSkinCorners] = fresh.keep(corn); c->buf[kSkinRest] = fresh.keep(rest);
+    c->buf[kSkinJoints] = fresh.keep(jnt);
     c->skin_list.assign(triangle, triangle + n);
     c->skin.present = 1u; c->skin.n_joints = n_joints; c->skin.n_skinned = n; c->skin.first_bad = kNone;
     return PTMI_OK;
@@ -238,27 +198,18 @@ int ptmi_pose_skin(ptmi_ctx *c, const ptmi_joint_transform *joints, uint32_t n_j
     if (!c) return PTMI_E_INVALID;
     const auto t0 = std::chrono::steady_clock::now();
     int rc = pt_check_skin_pose(c, joints, n_joints, c->err);
-    if (rc || (rc = refit_begin(c))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, sync_all(c));                                        // nothing in flight reads the scene any more
+    if (rc) return rc;
     uint32_t *head = head_of(c);
-    HIP_TRY(c, hipMemsetAsync(head, 0xFF, kHeadBytes, c->stream));  // "none" in the check pass's word
-    HIP_TRY(c, hipMemcpy(reinterpret_cast<char *>(head) + kHeadBytes, joints, (size_t)n_joints * sizeof(ptmi_joint_transform), hipMemcpyHostToDevice));
-    // the check pass: nothing of the scene is written before it has found nothing
-    if ((rc = run_pass<false>(c))) return rc;
-    uint32_t bad = kNone;
-    HIP_TRY(c, hipMemcpyAsync(&bad, head, sizeof bad, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (bad != kNone) {
-        c->skin.first_bad = bad;
-        return fail(c, PTMI_E_INVALID, "triangle %u: a skinned vertex is not finite%s (nothing was changed)", bad,
-                    c->sc.own ? ", or an edge is too long for float32 arithmetic" : "");
-    }
-    if ((rc = refit_ready(c))) return rc;                           // the plan, at the first edit after an upload
-    if ((rc = run_pass<true>(c))) return rc;
-    const uint32_t lo = c->skin_list.front(), hi = c->skin_list.back();
-    motion_widen(c, lo, hi - lo + 1u);                              // while motion is on: from the lowest to the highest listed triangle
-    if ((rc = refit_written(c, t0))) return rc;
+    auto stage = [&]() -> int {
+        HIP_TRY(c, hipMemsetAsync(head, 0xFF, kPoseHeadBytes, c->stream));  // "none" in the check word
+        HIP_TRY(c, hipMemcpy(reinterpret_cast<char *>(head) + kPoseHeadBytes, joints, (size_t)n_joints * sizeof(ptmi_joint_transform), hipMemcpyHostToDevice));
+        return PTMI_OK;
+    };
+    auto pass = [&](bool write) { return write ? run_pass<true>(c) : run_pass<false>(c); };
+    PoseCall p{stage, pass};
+    p.check_word = head; p.first_bad = &c->skin.first_bad; p.how = "skinned";
+    p.lo = c->skin_list.front(); p.hi = c->skin_list.back();       // from the lowest to the highest listed triangle
+    if ((rc = pose_refusable(c, t0, p))) return rc;
     c->skin.poses++; c->skin.first_bad = kNone;
     c->skin.pose_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return PTMI_OK;
