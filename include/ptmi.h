@@ -847,6 +847,65 @@ int ptmi_multi_set_skin(ptmi_multi *m, const uint32_t *triangle, const ptmi_skin
 int ptmi_multi_pose_skin(ptmi_multi *m, const ptmi_joint_transform *joints, uint32_t n_joints);
 int ptmi_multi_skin_status(ptmi_multi *m, struct ptmi_skin_status *out);
 
+/* ---- morphed meshes on the device: morph targets / blend shapes -----------------------------
+ * ptmi_set_morph takes a LIST of morphed triangles (triangle[]: indices in uploaded order, strictly ascending, as for the skin) and a
+ * sparse table of deltas in compressed-row form: row e, the records of listed triangle e, is deltas[row_start[e] .. row_start[e + 1])
+ * with row_start[0] == 0 (n_morphed + 1 words). A row holds one record per target that displaces the triangle, strictly ascending by
+ * `target`, and may be empty; a loader drops a record whose 18 numbers are all zero. row_start NULL together with deltas NULL: every
+ * row is empty. The call snapshots the REST POSE of the listed triangles from the live records, keeps the list, the rows, the records
+ * and the rest pose on the device and zeroes `poses`. triangle NULL or n_morphed 0 removes the morph. PTMI_E_INVALID: no scene, an
+ * index >= the uploaded count, a list that is not strictly ascending, row_start or deltas NULL where records exist, a row_start that
+ * is not non-decreasing from 0, a target >= n_targets or not strictly ascending within its row, a non-zero reserved word, a delta
+ * component that is not finite, n_targets 0. PTMI_E_UNSUPPORTED: more than 8 192 targets (the weights of a pose live in LDS: 32 KB).
+ * A failed call keeps the previous morph. ptmi_upload_scene removes the morph; ptmi_rebuild_tree, ptmi_update_materials and
+ * ptmi_update_lights leave it alone.
+ * ptmi_pose_morph takes one weight per target. Poses are ABSOLUTE, from the rest pose. Per corner of a listed triangle (vertex p,
+ * normal q, both starting as the rest record's), in float32, in the order written, no FMA, denormals kept:
+ *   for the records of the row, in order, with w = weights[record.target]:
+ *       w == 0 (either sign): the record is SKIPPED (not loaded, not added)
+ *       else, per component k:  p_k = p_k + w * dv_k      q_k = q_k + w * dn_k          (the product rounded, then the sum)
+ *   vertex' = p.   normal' = q / sqrt(l2) where l2 = (q.x * q.x + q.y * q.y) + q.z * q.z > 0, else q (ptmi_transform_groups' tail)
+ * A triangle of which no record was applied keeps its rest bits, normals included: nothing is renormalised, so an all-zero pose
+ * restores the rest pose bit for bit (the skip is part of the contract: -0 + 0 * d would be +0). The uvs, material_index and the
+ * padding words keep their bits. Afterwards the call runs the refit of ptmi_update_triangles: the state is bit for bit what
+ * ptmi_update_triangles(0, n_triangles, the morphed records) leaves and ptmi_scene_update_status.updates grows by one, except that
+ * while motion is on the dirty range is [lowest, highest] of the triangles whose live record was written.
+ * All-or-nothing. On the host: PTMI_E_STATE without a morph; PTMI_E_INVALID for weights NULL, n_targets different from the morph's,
+ * a weight that is not finite; PTMI_E_UNSUPPORTED where ptmi_update_triangles gives it. On the device, before anything is written,
+ * a check pass applies ptmi_update_triangles' vertex checks to the morphed vertices (as ptmi_pose_skin does): on a failure the call
+ * returns PTMI_E_INVALID, first_bad holds the smallest offending triangle index and the context is otherwise unchanged; on success
+ * first_bad is 0xFFFFFFFF.
+ * Interactions. ptmi_update_triangles re-bases the morph's rest rows inside its range. The morph and the triangle groups keep separate
+ * rest poses, under the last-writer rule. MORPH AND SKIN COMPOSE, in glTF's order (morph, then skin): for a triangle that the morph
+ * and the skin in place both list, ptmi_pose_morph writes its result to the SKIN'S REST ROW of that triangle, not to the live record,
+ * and sets skin_stale = 1; the next successful ptmi_pose_skin brings the live records up to date and clears it. Which entries those
+ * are is settled by whichever of ptmi_set_skin / ptmi_set_morph ran last (removals included; skin_stale is cleared then). If every
+ * listed triangle is in the skin, no live record changes and ptmi_pose_morph runs no refit: `updates` does not grow. */
+typedef struct ptmi_morph_delta {    /* 96 bytes: one target's displacement of one listed triangle */
+    float dv0[3]; uint32_t target;   /* which target this record belongs to */
+    float dv1[3]; uint32_t reserved0;    /* reserved words must be 0 */
+    float dv2[3]; uint32_t reserved1;
+    float dn0[3]; uint32_t reserved2;
+    float dn1[3]; uint32_t reserved3;
+    float dn2[3]; uint32_t reserved4;
+} ptmi_morph_delta;
+struct ptmi_morph_status {            /* a struct tag only; 48 bytes. Without a morph every word is zero. */
+    uint32_t present, n_targets, n_morphed, n_records;
+    uint32_t n_in_skin;               /* listed triangles that the skin in place lists too */
+    uint32_t poses, active_targets;   /* successful ptmi_pose_morph calls since the morph was set; non-zero weights of the last one */
+    uint32_t first_bad, skin_stale, reserved;   /* the last call's check pass (0xFFFFFFFF: none); a pose waits for ptmi_pose_skin */
+    double   pose_ms;                 /* wall time of the last successful ptmi_pose_morph, its refit (if any) included */
+};
+int ptmi_set_morph(ptmi_ctx *ctx, const uint32_t *triangle, const uint32_t *row_start, const ptmi_morph_delta *deltas,
+                   uint32_t n_morphed, uint32_t n_targets);
+int ptmi_pose_morph(ptmi_ctx *ctx, const float *weights, uint32_t n_targets);
+int ptmi_morph_status(ptmi_ctx *ctx, struct ptmi_morph_status *out);
+/* on every device, checked once before any device changes; the status of device 0 */
+int ptmi_multi_set_morph(ptmi_multi *m, const uint32_t *triangle, const uint32_t *row_start, const ptmi_morph_delta *deltas,
+                         uint32_t n_morphed, uint32_t n_targets);
+int ptmi_multi_pose_morph(ptmi_multi *m, const float *weights, uint32_t n_targets);
+int ptmi_multi_morph_status(ptmi_multi *m, struct ptmi_morph_status *out);
+
 /* ---- alpha cutouts ---------------------------------------------------------------------------
  * A per-material cutoff table for the loaded scene, one float per uploaded material. cutoff = 0: the material is opaque (the state of
  * every material without a table). cutoff > 0: a hit on the material is NOT THERE where the alpha of its albedo map's texel at the hit

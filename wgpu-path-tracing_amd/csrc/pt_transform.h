@@ -1,4 +1,5 @@
-// pt_transform.h — what scene_transform.hip (triangle groups) and scene_skin.hip (skinning) share on the device: one float4 of a rest
+// pt_transform.h — what scene_transform.hip (triangle groups), scene_skin.hip (skinning) and, for the layout, the check tail and the
+// constants, scene_morph.hip (morph targets) share on the device: one float4 of a rest
 // record through a 96-byte matrix record, ptmi_update_triangles' checks on a transformed vertex, the eight-lanes-per-record layout of
 // their kernels and the tail of their check pass, and the constants of their launches and buffers. Said once so that the two features
 // cannot disagree on a bit (include/ptmi.h ptmi_transform_groups has the formulas). The snapshot kernel and the host sequence they share

@@ -11,9 +11,10 @@
 //   alpha.hip          alpha cutouts: the cutoff table, the two resolve loops between the existing kernels, their debug entry points
 //   scene_rebuild.hip  the walked own-leaf tree rebuilt in place: the unit list on the device, the swap (ptmi_rebuild_tree)
 //   motion.hip         reprojection across a geometry edit: the previous positions, their commit, the motion plane (ptmi_set_motion)
-//   scene_pose.hip     what the two below share on the host: the check-then-write sequence of a pose, the rest-pose snapshot
+//   scene_pose.hip     what the three below share on the host: the check-then-write sequence of a pose, the rest-pose snapshot
 //   scene_transform.hip  triangle groups moved by matrix on the device: the table, the rest pose, the check and write kernel
 //   scene_skin.hip     skinned triangles posed on the device: the list, the corner records, the rest pose, the check and write kernel
+//   scene_morph.hip    morphed triangles posed on the device: the list, the sparse delta rows, the rest pose, the check and write kernel
 #pragma once
 #include "ptmi.h"
 #include "pt_device.h"
@@ -65,6 +66,10 @@ int pt_check_group_transforms(const ptmi_ctx *c, const ptmi_group_transform *ops
 int pt_check_skin(const ptmi_ctx *c, const uint32_t *triangle, const ptmi_skin_corner *corners, uint32_t n_skinned, uint32_t n_joints,
                   std::string &err);
 int pt_check_skin_pose(const ptmi_ctx *c, const ptmi_joint_transform *joints, uint32_t n_joints, std::string &err);
+// likewise for ptmi_set_morph and ptmi_pose_morph (scene_morph.hip)
+int pt_check_morph(const ptmi_ctx *c, const uint32_t *triangle, const uint32_t *row_start, const ptmi_morph_delta *deltas,
+                   uint32_t n_morphed, uint32_t n_targets, std::string &err);
+int pt_check_morph_pose(const ptmi_ctx *c, const float *weights, uint32_t n_targets, std::string &err);
 // Adaptive rounds driven from outside, one at a time (ptmi_multi_dispatch_adaptive with neighbourhood = 1; dispatch.hip).
 // pt_adaptive_check: everything ptmi_dispatch_adaptive checks before it enqueues, with its error codes; *ap = the params with their defaults.
 int pt_adaptive_check(ptmi_ctx *c, const ptmi_camera *cam, const ptmi_adaptive_params *params, ptmi_adaptive_params *ap);
@@ -109,6 +114,15 @@ enum SceneBuf {
     kSkinRest,                         // their rest pose: v0, v1, v2, n0, n1, n2, 6 float4 each
     kSkinJoints,                       // the head with the check word (pt_transform.h kPoseHead), then the joint records of the
                                        // ptmi_pose_skin call at hand
+    // the morph (ptmi_set_morph; scene_morph.hip), gone with the next upload; per LISTED triangle (entry), in list order:
+    kMorphList,                        // the listed triangles' indices, ascending
+    kMorphRows,                        // entries + 1 words: entry e's records are [rows[e], rows[e + 1])
+    kMorphTargets,                     // per record, its target word: what the kernel tests before it loads the record
+    kMorphDeltas,                      // the records: ptmi_morph_delta = 6 float4 each
+    kMorphRest,                        // the entries' rest pose: v0, v1, v2, n0, n1, n2, 6 float4 each
+    kMorphSkinRow,                     // per entry: the row of kSkinRest its result goes to, kNone for the live record
+    kMorphWeights,                     // the head with the check word (pt_transform.h kPoseHead), then the weights of the
+                                       // ptmi_pose_morph call at hand
     kSceneBufs
 };
 
@@ -229,6 +243,11 @@ struct ptmi_ctx {
     std::vector<uint32_t> skin_list;                   // the host's copy of the list (empty: no skin), for the re-base of a range
     struct ptmi_skin_status skin{};                    // what ptmi_skin_status reports
 
+    // the morph (ptmi_set_morph; scene_morph.hip): the buffers are buf[kMorphList] .. buf[kMorphWeights]
+    std::vector<uint32_t> morph_list;                  // the host's copy of the list (empty: no morph), for the re-base and the relink
+    uint32_t morph_lo = 0, morph_hi = 0;               // the lowest and the highest listed triangle that is NOT in the skin (lo > hi: none)
+    struct ptmi_morph_status morph{};                  // what ptmi_morph_status reports
+
     // output (binding 0)
     uint32_t W = 0, H = 0;
     void *plane[kFramePlanes] = {};                    // indexed by FramePlane, W x H pixels each (absent: NULL)
@@ -294,13 +313,15 @@ int refit_begin(ptmi_ctx *c);
 int refit_ready(ptmi_ctx *c);
 int refit_written(ptmi_ctx *c, std::chrono::steady_clock::time_point t0);
 
-// scene_pose.hip: a REFUSABLE POSE, the part of ptmi_transform_groups and ptmi_pose_skin between their own host checks and their own
+// scene_pose.hip: a REFUSABLE POSE, the part of ptmi_transform_groups, ptmi_pose_skin and ptmi_pose_morph between their own host checks and their own
 // counters. Every live record a pose moves is a function of a rest record and of the call's matrix records, and the call is all or
 // nothing without a staging buffer: a check pass transforms the vertices and leaves the smallest offending triangle in the check
 // word, and only when that is still "none" does the write pass run. In order: refit_begin; the device is selected and drained; stage;
 // pass(false); the check word is read (one asynchronous copy, one stream synchronise); a refusal sets *first_bad and the error, before
 // refit_ready, so that a refused first edit leaves no plan and no status behind; refit_ready; pass(true); motion_widen over [lo, hi];
-// refit_written(t0). moves false: nothing is staged, checked or written, and the refit still runs.
+// refit_written(t0). moves false: nothing is staged, checked or written, and the refit still runs. refit false (a morph whose every
+// entry goes to the skin's rest rows): no live record is written, so after pass(true) the stream is drained and that is all - no plan,
+// no dirty range, no refit, `updates` stays.
 // (a reference to a callable of the caller's, which outlives the call: nothing is owned or allocated)
 template <class Sig> struct FnRef;
 template <class R, class... A> struct FnRef<R(A...)> {
@@ -312,9 +333,10 @@ struct PoseCall {
     FnRef<int()> stage;                         // the call's records to the device, and "none" to the check word
     FnRef<int(bool write)> pass;                // the launches of one pass
     bool moves = true;
+    bool refit = true;                          // the write pass touches live records
     uint32_t *check_word = nullptr;             // device memory (pt_transform.h kPoseHead)
     uint32_t *first_bad = nullptr;              // the status field a refusal sets
-    const char *how = "";                       // "transformed", "skinned": the word of the refusal
+    const char *how = "";                       // "transformed", "skinned", "morphed": the word of the refusal
     uint32_t lo = 0, hi = 0;                    // the lowest and the highest triangle the write pass may touch
 };
 int pose_refusable(ptmi_ctx *c, std::chrono::steady_clock::time_point t0, const PoseCall &p);
@@ -343,6 +365,12 @@ int groups_rebase(ptmi_ctx *c, uint32_t first, uint32_t count);
 // scene_skin.hip: the same two for the skin; the re-base takes the listed triangles inside the range
 void skin_forget(ptmi_ctx *c);
 int skin_rebase(ptmi_ctx *c, uint32_t first, uint32_t count);
+// scene_morph.hip: the same two for the morph. morph_relink: the entry -> skin row map (buf[kMorphSkinRow]) and what follows from it
+// (n_in_skin, the range of the entries that go to live records; skin_stale cleared), from the two lists as they stand: called by
+// whichever of ptmi_set_skin / ptmi_set_morph ran last, removals included. Nothing to do without a morph.
+void morph_forget(ptmi_ctx *c);
+int morph_rebase(ptmi_ctx *c, uint32_t first, uint32_t count);
+int morph_relink(ptmi_ctx *c);
 
 // scene_image.hip: the own-leaf image of the loaded scene built anew from what is on the device (ptmi_rebuild_tree), by the code an
 // upload builds it with. d_which: the unit list (n_units entries, device memory). buf: new device buffers for the entries a rebuild

@@ -578,6 +578,28 @@ int ptmi_multi_skin_status(ptmi_multi *m, struct ptmi_skin_status *out) {
     return rc ? cfail(m, 0, rc, "ptmi_skin_status") : PTMI_OK;
 }
 
+// The morph on every device (scene_morph.hip), by the same rule.
+int ptmi_multi_set_morph(ptmi_multi *m, const uint32_t *triangle, const uint32_t *row_start, const ptmi_morph_delta *deltas,
+                         uint32_t n_morphed, uint32_t n_targets) {
+    if (!m) return PTMI_E_INVALID;
+    std::string why;
+    const int rc = pt_check_morph(m->d[0].ctx, triangle, row_start, deltas, n_morphed, n_targets, why);
+    if (rc) return mfail(m, rc, "%s", why.c_str());
+    return each_ctx(m, "ptmi_set_morph", ptmi_set_morph, triangle, row_start, deltas, n_morphed, n_targets);
+}
+int ptmi_multi_pose_morph(ptmi_multi *m, const float *weights, uint32_t n_targets) {
+    if (!m) return PTMI_E_INVALID;
+    std::string why;
+    const int rc = pt_check_morph_pose(m->d[0].ctx, weights, n_targets, why);
+    if (rc) return mfail(m, rc, "%s", why.c_str());
+    return each_ctx(m, "ptmi_pose_morph", ptmi_pose_morph, weights, n_targets);
+}
+int ptmi_multi_morph_status(ptmi_multi *m, struct ptmi_morph_status *out) {
+    if (!m || !out) return PTMI_E_INVALID;
+    const int rc = ptmi_morph_status(m->d[0].ctx, out);
+    return rc ? cfail(m, 0, rc, "ptmi_morph_status") : PTMI_OK;
+}
+
 int ptmi_multi_resize(ptmi_multi *m, uint32_t w, uint32_t h) {
     if (!m) return PTMI_E_INVALID;
     int rc = each_ctx(m, "ptmi_resize", ptmi_resize, w, h);

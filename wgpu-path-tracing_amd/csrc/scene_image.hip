@@ -485,6 +485,7 @@ int pt_install_scene(ptmi_ctx *c, PtPrepared *prep) {
     lane_views(c->lane);
     groups_forget(c);                          // the group table named the old scene's triangles (its buffers went with the others above)
     skin_forget(c);                            // ... and so did the skin
+    morph_forget(c);                           // ... and the morph
     c->st.leaves_used = h.leaves_used;
     c->st.leaf_tris_used = h.max_leaf_tris;
     c->st.tree_builder_used = b.tree_builder_used;

@@ -1,6 +1,6 @@
-// scene_pose.hip — what the two pose sources share on the host (scene_transform.hip: triangle groups; scene_skin.hip: the skin;
-// DESIGN.md §17 "The shared pose sequence"): the check-then-write sequence of a refusable pose and the snapshot of a rest pose.
-// ptmi_ctx.h has the contract of both; pt_transform.h has what the two kernels share on the device.
+// scene_pose.hip — what the three pose sources share on the host (scene_transform.hip: triangle groups; scene_skin.hip: the skin;
+// scene_morph.hip: the morph; DESIGN.md §17 "The shared pose sequence"): the check-then-write sequence of a refusable pose and the
+// snapshot of a rest pose. ptmi_ctx.h has the contract of both; pt_transform.h has what their kernels share on the device.
 #include "ptmi_ctx.h"
 #include "pt_transform.h"
 
@@ -45,6 +45,11 @@ int pose_refusable(ptmi_ctx *c, std::chrono::steady_clock::time_point t0, const 
             return fail(c, PTMI_E_INVALID, "triangle %u: a %s vertex is not finite%s (nothing was changed)", bad, p.how,
                         c->sc.own ? ", or an edge is too long for float32 arithmetic" : "");
         }
+    }
+    if (!p.refit) {                                                 // no live record is written: the pass, and nothing of the refit
+        if (p.moves && (rc = p.pass(true))) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return PTMI_OK;
     }
     if ((rc = refit_ready(c))) return rc;                           // the plan, at the first edit after an upload
     if (p.moves) {

@@ -171,7 +171,7 @@ int ptmi_set_skin(ptmi_ctx *c, const uint32_t *triangle, const ptmi_skin_corner 
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, sync_all(c));
-    if (!triangle || n == 0u) { skin_forget(c); return PTMI_OK; }
+    if (!triangle || n == 0u) { skin_forget(c); return morph_relink(c); }   // (a morph in place writes to the live records again)
     const size_t rec = (size_t)n * kRestQ * sizeof(float4);
     DevScratch fresh;                                               // freed on every way out but the last
     uint32_t *list = fresh.get<uint32_t>(n);
@@ -191,7 +191,7 @@ int ptmi_set_skin(ptmi_ctx *c, const uint32_t *triangle, const ptmi_skin_corner 
     c->buf[kSkinJoints] = fresh.keep(jnt);
     c->skin_list.assign(triangle, triangle + n);
     c->skin.present = 1u; c->skin.n_joints = n_joints; c->skin.n_skinned = n; c->skin.first_bad = kNone;
-    return PTMI_OK;
+    return morph_relink(c);                                         // a morph in place: its entries that this list names go to the new rest rows
 }
 
 int ptmi_pose_skin(ptmi_ctx *c, const ptmi_joint_transform *joints, uint32_t n_joints) {
@@ -211,6 +211,7 @@ int ptmi_pose_skin(ptmi_ctx *c, const ptmi_joint_transform *joints, uint32_t n_j
     p.lo = c->skin_list.front(); p.hi = c->skin_list.back();       // from the lowest to the highest listed triangle
     if ((rc = pose_refusable(c, t0, p))) return rc;
     c->skin.poses++; c->skin.first_bad = kNone;
+    c->morph.skin_stale = 0u;                                       // what ptmi_pose_morph left in the rest rows is in the live records now
     c->skin.pose_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return PTMI_OK;
 }

@@ -568,6 +568,7 @@ int ptmi_update_triangles(ptmi_ctx *c, uint32_t first, uint32_t count, const ptm
         motion_widen(c, first, count);                          // while motion is on: the previous positions stay, the dirty range grows
         if ((rc = groups_rebase(c, first, count))) return rc;   // while a group table is in place: these records are their triangles' rest pose
         if ((rc = skin_rebase(c, first, count))) return rc;     // ... and while a skin is: the rest pose of the listed triangles among them
+        if ((rc = morph_rebase(c, first, count))) return rc;    // ... and while a morph is: likewise
     }
     return refit_written(c, t0);
 }

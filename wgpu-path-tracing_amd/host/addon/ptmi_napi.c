@@ -431,6 +431,62 @@ static napi_value js_skin_status(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* setMorph(handle, Uint32Array | null triangles, Uint32Array | null rowStart, deltas blob | null, nTargets): ptmi_set_morph; rowStart
+ * holds one word more than triangles, the blob whole 96-byte ptmi_morph_delta records, as many as rowStart's last word; null
+ * triangles remove the morph */
+static napi_value js_set_morph(napi_env env, napi_callback_info info) {
+    napi_value argv[5];
+    handle *h = get_handle(env, info, 5, argv);
+    if (!h) return NULL;
+    void *t, *r, *d; size_t tn, rn, dn;
+    uint32_t n_targets = 0;
+    if (!get_bytes(env, argv[1], &t, &tn) || !get_bytes(env, argv[2], &r, &rn) || !get_bytes(env, argv[3], &d, &dn)) return NULL;
+    NAPI_OK(env, napi_get_value_uint32(env, argv[4], &n_targets));
+    if (tn % sizeof(uint32_t)) { napi_throw_range_error(env, NULL, "the triangle list is not whole uint32 words"); return NULL; }
+    if (t && r && rn != tn + sizeof(uint32_t)) {
+        napi_throw_range_error(env, NULL, "rowStart does not hold one word more than the triangle list");
+        return NULL;
+    }
+    if (d && dn % sizeof(ptmi_morph_delta)) { napi_throw_range_error(env, NULL, "the delta blob is not whole 96-byte records"); return NULL; }
+    if (t && r && tn && ((const uint32_t *)r)[tn / sizeof(uint32_t)] > (d ? dn / sizeof(ptmi_morph_delta) : 0)) {
+        napi_throw_range_error(env, NULL, "rowStart reaches beyond the delta blob");
+        return NULL;
+    }
+    CALL(env, h, set_morph, (const uint32_t *)t, (const uint32_t *)r, (const ptmi_morph_delta *)d, (uint32_t)(tn / sizeof(uint32_t)), n_targets);
+    return NULL;
+}
+
+/* poseMorph(handle, Float32Array weights): ptmi_pose_morph; one weight per target */
+static napi_value js_pose_morph(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    handle *h = get_handle(env, info, 2, argv);
+    if (!h) return NULL;
+    void *p; size_t n;
+    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
+    if (n % sizeof(float)) { napi_throw_range_error(env, NULL, "the weights are not whole float32 words"); return NULL; }
+    CALL(env, h, pose_morph, (const float *)p, (uint32_t)(n / sizeof(float)));
+    return NULL;
+}
+
+/* morphStatus(handle) -> {present, nTargets, nMorphed, nRecords, nInSkin, poses, activeTargets, firstBad, skinStale, poseMs} */
+static napi_value js_morph_status(napi_env env, napi_callback_info info) {
+    napi_value argv[1], out, v;
+    handle *h = get_handle(env, info, 1, argv);
+    if (!h) return NULL;
+    struct ptmi_morph_status st;
+    CALL(env, h, morph_status, &st);
+    NAPI_OK(env, napi_create_object(env, &out));
+    const struct { const char *name; double value; } num[] = {
+        {"present", st.present}, {"nTargets", st.n_targets}, {"nMorphed", st.n_morphed}, {"nRecords", st.n_records},
+        {"nInSkin", st.n_in_skin}, {"poses", st.poses}, {"activeTargets", st.active_targets}, {"firstBad", st.first_bad},
+        {"skinStale", st.skin_stale}, {"poseMs", st.pose_ms}};
+    for (size_t i = 0; i < sizeof num / sizeof num[0]; i++) {
+        NAPI_OK(env, napi_create_double(env, num[i].value, &v));
+        NAPI_OK(env, napi_set_named_property(env, out, num[i].name, v));
+    }
+    return out;
+}
+
 /* rebuildStatus(handle) -> {rebuilds, builderUsed, buildMs, costBefore, costAfter} */
 static napi_value js_rebuild_status(napi_env env, napi_callback_info info) {
     napi_value argv[1], out, v;
@@ -1021,6 +1077,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"setTriangleGroups", js_set_triangle_groups}, {"transformGroups", js_transform_groups}, {"transformStatus", js_transform_status},
         {"normalMatrix", js_normal_matrix},
         {"setSkin", js_set_skin}, {"poseSkin", js_pose_skin}, {"skinStatus", js_skin_status},
+        {"setMorph", js_set_morph}, {"poseMorph", js_pose_morph}, {"morphStatus", js_morph_status},
         {"rebuildTree", js_rebuild_tree}, {"rebuildStatus", js_rebuild_status},
         {"setAlphaCutoff", js_set_alpha_cutoff}, {"alphaStatus", js_alpha_status},
         {"resize", js_resize}, {"setOptions", js_set_options},

@@ -5,7 +5,7 @@
  * node hierarchy. Everything is arithmetic in JS doubles on plain arrays, 4 x 4 matrices column-major as glTF writes them; the one
  * rounding to float32 happens where the joint records are packed (Renderer.poseSkin).
  * Samplers: STEP and LINEAR (rotations by spherical interpolation along the shorter arc). CUBICSPLINE throws. Channels that
- * target morph-target weights are ignored.
+ * target morph-target weights are sampled like the others, one number per target per key (Renderer.poseAt; ptmi_pose_morph).
  */
 
 function lerp(a, b, u) { return a.map(function (x, i) { return x + (b[i] - x) * u; }); }
@@ -40,8 +40,24 @@ function sampleTrack(sampler, width, t, rotation) {
   return rotation ? slerp(key(k), key(k + 1), u) : lerp(key(k), key(k + 1), u);
 }
 
+/** how many morph targets the mesh of a node has (0: none) */
+function targetCount(node) {
+  var n = 0;
+  if (node.mesh) node.mesh.primitives.forEach(function (p) { if (p.targets) n = Math.max(n, p.targets.length); });
+  return n;
+}
+/** the morph weights a node has without an animation: its own `weights`, else its mesh's, else zeros; undefined without targets */
+function defaultWeights(node) {
+  var n = targetCount(node), w = [];
+  if (!n) return undefined;
+  var given = node.weights || node.mesh.weights || [];
+  for (var k = 0; k < n; k++) w.push(given[k] === undefined ? 0 : given[k]);
+  return w;
+}
+
 /** -> per node { translation, rotation, scale, matrix }: the node's own local transform with the animation's channels at t seconds
- *  laid over it. matrix is the node's `matrix` (16 numbers) where it has one and no channel targets it, else null. */
+ *  laid over it. matrix is the node's `matrix` (16 numbers) where it has one and no channel targets it, else null. A node whose mesh
+ *  has morph targets also has `weights`: its default weights (defaultWeights) with a `weights` channel laid over them. */
 function sample(gltf, animationIndex, t) {
   var anim = (gltf.animations || [])[animationIndex];
   if (!anim) throw new RangeError('animation: the file has no animation ' + animationIndex);
@@ -49,8 +65,14 @@ function sample(gltf, animationIndex, t) {
     return { translation: n.translation ? Array.from(n.translation) : [0, 0, 0], rotation: n.rotation ? Array.from(n.rotation) : [0, 0, 0, 1],
       scale: n.scale ? Array.from(n.scale) : [1, 1, 1], matrix: n.matrix ? Array.from(n.matrix) : null };
   });
+  gltf.nodes.forEach(function (n, i) { var w = defaultWeights(n); if (w) out[i].weights = w; });
   anim.channels.forEach(function (c) {
-    if (c.node === undefined || c.path === 'weights') return;
+    if (c.node === undefined) return;
+    if (c.path === 'weights') {
+      var width = targetCount(gltf.nodes[c.node]);
+      if (width) out[c.node].weights = sampleTrack(anim.samplers[c.sampler], width, t, false);
+      return;
+    }
     if (c.path !== 'translation' && c.path !== 'rotation' && c.path !== 'scale') throw new Error('animation: unknown path ' + c.path);
     var o = out[c.node];
     o[c.path] = sampleTrack(anim.samplers[c.sampler], c.path === 'rotation' ? 4 : 3, t, c.path === 'rotation');
@@ -121,4 +143,4 @@ function restPose(gltf) {
   });
 }
 
-module.exports = { sample: sample, worldMatrices: worldMatrices, restPose: restPose, mul4: mul4, invert4: invert4, slerp: slerp };
+module.exports = { defaultWeights: defaultWeights, targetCount: targetCount, sample: sample, worldMatrices: worldMatrices, restPose: restPose, mul4: mul4, invert4: invert4, slerp: slerp };

@@ -7,7 +7,9 @@
  * Beyond the reference: skins ({ joints: node indices, inverseBindMatrices: Float32Array of 16 per joint, column-major, or
  * undefined for identities }), a node's `skin` index, and animations ({ channels: [{ node, path, sampler }], samplers:
  * [{ input, output, interpolation }] }); JOINTS_0 / WEIGHTS_0 come through the attribute reader like every other attribute
- * (normalised integer weights are scaled to [0, 1]).
+ * (normalised integer weights are scaled to [0, 1]). Morph targets: a primitive's `targets` ([{ POSITION?, NORMAL? }] as attribute
+ * readings; TANGENT is ignored), a mesh's `weights` and a node's `weights` (which override the mesh's). Sparse accessors are not read
+ * (the attribute reader needs a bufferView), for morph targets as for everything else.
  * Images are decoded to RGBA8 ({width, height, data}; PNG and JPEG) and texture
  * references are resolved the way postProcessGLTF does (`material.normalTexture.texture.source.image`), which is
  * what src/renderer/atlas.ts:36-48 walks.
@@ -91,7 +93,7 @@ function loadGLB(pathOrBuffer) {
   var rootLights = json.extensions && json.extensions.KHR_lights_punctual ? json.extensions.KHR_lights_punctual.lights : [];
   var meshes = (json.meshes || []).map(function (mesh) {
     return {
-      name: mesh.name,
+      name: mesh.name, weights: mesh.weights ? mesh.weights.slice() : undefined,
       primitives: mesh.primitives.map(function (p) {
         var attributes = {};
         Object.keys(p.attributes).forEach(function (k) { attributes[k] = readAccessor(json, bin, p.attributes[k]); });
@@ -100,6 +102,10 @@ function loadGLB(pathOrBuffer) {
           indices: p.indices !== undefined ? readAccessor(json, bin, p.indices) : undefined,
           material: p.material !== undefined ? materials[p.material] : undefined,
           mode: p.mode === undefined ? 4 : p.mode,
+          targets: p.targets ? p.targets.map(function (t) {
+            return { POSITION: t.POSITION !== undefined ? readAccessor(json, bin, t.POSITION) : undefined,
+              NORMAL: t.NORMAL !== undefined ? readAccessor(json, bin, t.NORMAL) : undefined };
+          }) : undefined,
         };
       }),
     };
@@ -108,6 +114,7 @@ function loadGLB(pathOrBuffer) {
     var o = { name: n.name, matrix: n.matrix, translation: n.translation, rotation: n.rotation, scale: n.scale };
     if (n.mesh !== undefined) o.mesh = meshes[n.mesh];
     if (n.skin !== undefined) o.skin = n.skin;
+    if (n.weights) o.weights = n.weights.slice();
     if (n.extensions && n.extensions.KHR_lights_punctual) o.light = n.extensions.KHR_lights_punctual.light;
     return o;
   });

@@ -104,7 +104,16 @@ export class Renderer {
    *  affine; normalMatrix: 9 numbers, derived through ptmi_normal_matrix when absent. A refused call throws and changes nothing. */
   poseSkin(joints: Array<{ matrix: ArrayLike<number>; normalMatrix?: ArrayLike<number> }>): void;
   skinStatus(): SkinStatus;
-  /** poses the skin of the loaded .glb at t seconds of its animation (STEP and LINEAR samplers; CUBICSPLINE throws) */
+  /** lists the morphed triangles of the loaded scene (ascending indices in the uploaded order) with their 96-byte delta records in
+   *  compressed-row form (rowStart: one word more than triangles; a row ascends by target) for nTargets morph targets, and snapshots
+   *  the rest pose (include/ptmi.h ptmi_set_morph); null removes the morph. loadModel of a .glb with morph targets does it. */
+  setMorph(triangles: Uint32Array | null, rowStart: Uint32Array | null, deltas: ArrayBuffer | ArrayBufferView | null, nTargets: number): void;
+  /** one weight per target (ptmi_pose_morph): every listed triangle becomes its rest pose plus the weighted deltas of its row;
+   *  triangles the skin lists too reach the live records at the next poseSkin. Throws, and changes nothing, where a vertex leaves float32. */
+  poseMorph(weights: ArrayLike<number>): void;
+  morphStatus(): MorphStatus;
+  /** poses the loaded .glb at t seconds of its animation: its morph targets first, then its skin (STEP and LINEAR samplers;
+   *  CUBICSPLINE throws) */
   poseAt(animationIndex: number, t: number): void;
   /** builds the walked own-leaf tree anew from the triangles as they stand on the device and swaps it in (include/ptmi.h
    *  ptmi_rebuild_tree): the image a fresh loadModel of the edited scene would build, with the triangle order, the tables, the alpha
@@ -202,6 +211,11 @@ export interface TransformStatus {
   present: number; nGroups: number; transforms: number; lastMoved: number;
   /** the last call's check pass: the smallest offending triangle, 0xFFFFFFFF for none */
   firstBad: number; transformMs: number;
+}
+/** ptmi_morph_status: the morph in place and the poses since it was set */
+export interface MorphStatus {
+  present: number; nTargets: number; nMorphed: number; nRecords: number; nInSkin: number; poses: number; activeTargets: number;
+  firstBad: number; skinStale: number; poseMs: number;
 }
 /** ptmi_skin_status: the skin in place and the poses since it was set */
 export interface SkinStatus {

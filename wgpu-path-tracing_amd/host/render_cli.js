@@ -26,8 +26,9 @@
  * --alpha-cutout (a .glb scene): materials with alphaMode "MASK" become cutouts at their alphaCutoff (include/ptmi.h
  * ptmi_set_alpha_cutoff): the atlas keeps the alpha of albedo maps, and paths and shadow rays pass where it is below the cutoff, through
  * at most --alpha-layers N holes per segment (default: the library's, 4); the JSON line then also holds alpha: the table's status.
- * --animation N --time S (a .glb scene with a skin): renders one frame posed at S seconds (default 0) of the file's animation N
- * (Renderer.poseAt; include/ptmi.h ptmi_pose_skin); the JSON line then also holds skin: the skin's status.
+ * --animation N --time S (a .glb scene with a skin or morph targets): renders one frame posed at S seconds (default 0) of the file's
+ * animation N (Renderer.poseAt; include/ptmi.h ptmi_pose_morph, ptmi_pose_skin); the JSON line then also holds skin and morph: their
+ * status.
  */
 var fs = require('fs');
 var host = require('./renderer');
@@ -111,7 +112,7 @@ r.loadModel(scenePath).then(function () {
   st.wallMs = ms; st.width = W; st.height = H; st.frames = frames;
   if (status) st.frames = 0;                // no uniform frames: the counts are per pixel
   if (alphaCutout) st.alpha = r.alphaStatus();
-  if (textArg('animation') !== null) st.skin = r.skinStatus();
+  if (textArg('animation') !== null) { st.skin = r.skinStatus(); st.morph = r.morphStatus(); }
   if (status) st.adaptive = { samples: status.samples, minCount: status.minCount, maxCount: status.maxCount, rounds: status.rounds };
   console.log(JSON.stringify(st));
   r.destroy();

@@ -86,8 +86,8 @@ Renderer.prototype.addOnUpdate = function (callback) { this.onUpdateTasks.push(c
 Renderer.prototype.loadModel = function (model, atlas) {
   var self = this;
   return new Promise(function (resolve) {
-    var blobs, cutoff = null, groups = null, skin = null;
-    self.gltf = null; self.skins = null;
+    var blobs, cutoff = null, groups = null, skin = null, morph = null;
+    self.gltf = null; self.skins = null; self.morphs = null;
     if (typeof model === 'string' && /\.glb$/i.test(model)) {
       var gltf = require('./gltf').loadGLB(model);
       var prepared = require('./scene_prep').prepareScene(gltf, { alphaCutout: self.alphaCutout });
@@ -95,6 +95,7 @@ Renderer.prototype.loadModel = function (model, atlas) {
       cutoff = prepared.alphaCutoff || null;
       groups = prepared.triangleGroups || null;
       if (prepared.skinTriangles) { skin = prepared; self.gltf = gltf; }
+      if (prepared.morphTriangles) { morph = prepared; self.gltf = gltf; }
     } else if (typeof model === 'string') {
       var f = sceneFile.readSceneFile(model);
       blobs = f.blobs; atlas = atlas || f.atlas;
@@ -102,6 +103,7 @@ Renderer.prototype.loadModel = function (model, atlas) {
       blobs = model.blobs; atlas = atlas || model.atlas;
       groups = model.triangleGroups || null;                            // what prepareScene returned: a triangle's glTF node
       if (model.skinTriangles) { skin = model; self.gltf = model.gltf || null; }   // ... and its skinned triangles
+      if (model.morphTriangles) { morph = model; self.gltf = model.gltf || null; } // ... and its morphed ones
       if (self.alphaCutout) cutoff = model.alphaCutoff || null;         // what prepareScene({alphaCutout: true}) returned
     } else {
       blobs = pack.packScene(model);
@@ -118,6 +120,11 @@ Renderer.prototype.loadModel = function (model, atlas) {
     if (skin && skin.skinTriangles.length) {
       self.addon.setSkin(self.ctx, skin.skinTriangles, skin.skinCorners, skin.skinJoints);
       self.skins = skin;
+    }
+    // ... and any morph: a .glb's primitives with targets are listed with their deltas (poseMorph / poseAt pose them)
+    if (morph && morph.morphTriangles.length) {
+      self.addon.setMorph(self.ctx, morph.morphTriangles, morph.morphRowStart, morph.morphDeltas, morph.morphTargets);
+      self.morphs = morph;
     }
     self.sceneLoaded = true;
     self.resetOutputBuffer(false);
@@ -360,13 +367,40 @@ Renderer.prototype.poseSkin = function (joints) {
 Renderer.prototype.skinStatus = function () {
   return this.addon.skinStatus(this.ctx);
 };
-/** poses the skin of the loaded .glb at t seconds of its animation animationIndex: the animated local transforms (animation.js
- *  sample: STEP and LINEAR), the node hierarchy composed in double, the joint matrices of scene_prep.skinPose, then poseSkin */
+/**
+ * Morphed meshes posed on the device (include/ptmi.h ptmi_set_morph / ptmi_pose_morph). setMorph lists the morphed triangles (a
+ * Uint32Array of ascending indices in the uploaded order; null removes the morph) with a sparse table of 96-byte delta records in
+ * compressed-row form (rowStart: one word more than triangles; deltas: an ArrayBuffer of ptmi_morph_delta records, ascending by target
+ * within a row) for nTargets targets, and snapshots the rest pose; loadModel of a .glb with morph targets does it. poseMorph takes one
+ * weight per target; poses are absolute, and targets of weight zero cost nothing. Triangles the skin lists too are handed to the
+ * skin's rest pose and reach the live records at the next poseSkin (morph, then skin: glTF's order). A refused call throws and changes
+ * nothing.
+ */
+Renderer.prototype.setMorph = function (triangles, rowStart, deltas, nTargets) {
+  if (triangles && !(triangles instanceof Uint32Array)) throw new TypeError('setMorph: triangles must be a Uint32Array or null');
+  if (triangles && rowStart && !(rowStart instanceof Uint32Array)) throw new TypeError('setMorph: rowStart must be a Uint32Array');
+  if (!this.sceneLoaded) throw new Error('setMorph: needs a loaded scene (loadModel)');
+  this.addon.setMorph(this.ctx, triangles || null, triangles ? rowStart || null : null, triangles ? deltas || null : null, nTargets >>> 0);
+  this.morphs = null;                                                  // (poseAt poses the morph loadModel set, not this one)
+};
+Renderer.prototype.poseMorph = function (weights) {
+  if (!this.sceneLoaded) throw new Error('poseMorph: needs a loaded scene (loadModel)');
+  this.addon.poseMorph(this.ctx, Float32Array.from(weights));
+  this._trianglesEdited();
+};
+/** { present, nTargets, nMorphed, nRecords, nInSkin, poses, activeTargets, firstBad, skinStale, poseMs } of the morph in place */
+Renderer.prototype.morphStatus = function () {
+  return this.addon.morphStatus(this.ctx);
+};
+/** poses the loaded .glb at t seconds of its animation animationIndex: the animated local transforms and morph weights (animation.js
+ *  sample: STEP and LINEAR); the morph first (scene_prep.morphPose, then poseMorph), then the skin: the node hierarchy composed in
+ *  double, the joint matrices of scene_prep.skinPose, then poseSkin */
 Renderer.prototype.poseAt = function (animationIndex, t) {
-  if (!this.skins || !this.gltf) throw new Error('poseAt: needs a loaded .glb with a skin (loadModel)');
-  var animation = require('./animation');
-  var worlds = animation.worldMatrices(this.gltf, animation.sample(this.gltf, animationIndex, t));
-  this.poseSkin(require('./scene_prep').skinPose(this.skins, worlds));
+  if ((!this.skins && !this.morphs) || !this.gltf) throw new Error('poseAt: needs a loaded .glb with a skin or morph targets (loadModel)');
+  var animation = require('./animation'), prep = require('./scene_prep');
+  var locals = animation.sample(this.gltf, animationIndex, t);
+  if (this.morphs) this.poseMorph(prep.morphPose(this.morphs, locals));
+  if (this.skins) this.poseSkin(prep.skinPose(this.skins, animation.worldMatrices(this.gltf, locals)));
 };
 /** { updates, quantisedKept, planMs, refitMs, costBuilt, costNow, rootMin, rootMax } of the triangle updates since loadModel */
 Renderer.prototype.sceneUpdateStatus = function () {

@@ -76,7 +76,7 @@ function buildTriangles(position, normal, uv, index) {
 }
 
 /** gpu.ts:194-299 */
-function processNode(gltf, node, allTriangles, allMaterials, allLights, world, atlas, nodeIndex, skinInstance) {
+function processNode(gltf, node, allTriangles, allMaterials, allLights, world, atlas, nodeIndex, skinInstance, morphInstance) {
   var normalMat = M.transpose(M.inverse(world));
   if (node.light !== undefined) {
     var light = gltf.lights[node.light];
@@ -105,12 +105,19 @@ function processNode(gltf, node, allTriangles, allMaterials, allLights, world, a
       // a skinned primitive is still placed by its node's world matrix (the uploaded bytes are what they are without skinning);
       // its triangles remember their three vertices' JOINTS_0 / WEIGHTS_0 for the skin list
       var skinned = skinInstance && prim.attributes.JOINTS_0 && prim.attributes.WEIGHTS_0 && prim.indices;
+      // ... and a primitive with morph targets its vertices and the targets' deltas, for the morph list
+      var morphed = morphInstance && prim.targets && prim.targets.length && prim.indices;
       tris.forEach(function (t, k) {
         t.materialIndex = allMaterials.length - 1; t.group = nodeIndex;
         if (skinned) {
           var ix = prim.indices.value;
           t.skin = { instance: skinInstance, vertices: [ix[3 * k], ix[3 * k + 1], ix[3 * k + 2]],
             joints: prim.attributes.JOINTS_0.value, weights: prim.attributes.WEIGHTS_0.value };
+        }
+        if (morphed) {
+          var jx = prim.indices.value;
+          t.morph = { instance: morphInstance, vertices: [jx[3 * k], jx[3 * k + 1], jx[3 * k + 2]], targets: prim.targets,
+            normal: normal, world: world, normalMat: normalMat };
         }
         allTriangles.push(t);
       });
@@ -173,6 +180,57 @@ function skinList(allTriangles, presort) {
   return { triangles: Uint32Array.from(listed), corners: corners };
 }
 
+/** The morph list of a prepared scene (Renderer.setMorph): the uploaded indices of the morphed triangles, ascending, the row bounds and
+ *  the 96-byte delta records (include/ptmi.h ptmi_morph_delta), ascending by target within a row, the target offset by its mesh
+ *  instance's targetBase. The deltas are brought to the uploaded space: a position delta through the upper 3 x 3 of the node's world
+ *  matrix N; a corner's normal delta is the normal matrix applied to dn, divided by the length of that matrix applied to the corner's
+ *  local normal (the uploaded normal is that vector normalised), which keeps rest + sum w * delta parallel to the transformed
+ *  n + sum w * dn. A target without NORMAL has zero normal deltas; a record whose 18 numbers are all zero is dropped. */
+function morphList(allTriangles, presort) {
+  var listed = [], rows = [0], recs = [];
+  for (var i = 0; i < presort.length; i++) if (allTriangles[presort[i]].morph) listed.push(i);
+  listed.forEach(function (at) {
+    var m = allTriangles[presort[at]].morph;
+    m.targets.forEach(function (target, k) {
+      var rec = new Float32Array(24), any = false;
+      for (var c = 0; c < 3; c++) {
+        var v = 3 * m.vertices[c], d;
+        if (target.POSITION) {
+          var dp = target.POSITION.value;
+          d = M.transformMat4Upper3x3(M.vec3(dp[v], dp[v + 1], dp[v + 2]), m.world);
+          rec[4 * c] = d[0]; rec[4 * c + 1] = d[1]; rec[4 * c + 2] = d[2];
+        }
+        if (target.NORMAL) {
+          var dn = target.NORMAL.value;
+          var q = M.transformMat4Upper3x3(M.vec3(m.normal[v], m.normal[v + 1], m.normal[v + 2]), m.normalMat);
+          var len = Math.sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
+          d = M.transformMat4Upper3x3(M.vec3(dn[v], dn[v + 1], dn[v + 2]), m.normalMat);
+          if (len > 0) { rec[12 + 4 * c] = d[0] / len; rec[12 + 4 * c + 1] = d[1] / len; rec[12 + 4 * c + 2] = d[2] / len; }
+        }
+      }
+      for (var w = 0; w < 24; w++) if (rec[w] !== 0) any = true;
+      if (!any) return;
+      new Uint32Array(rec.buffer)[3] = m.instance.targetBase + k;
+      recs.push(rec);
+    });
+    rows.push(recs.length);
+  });
+  var deltas = new ArrayBuffer(96 * recs.length), f32 = new Float32Array(deltas);
+  recs.forEach(function (r, e) { f32.set(r, 24 * e); });
+  return { triangles: Uint32Array.from(listed), rowStart: Uint32Array.from(rows), deltas: deltas };
+}
+
+/** The weights of a pose (Renderer.poseMorph) from per-node weights (animation.js sample: out[node].weights): one float per target
+ *  of all morphed mesh instances together, a node without weights in `nodes` taking its defaults */
+function morphPose(prepared, nodes) {
+  var out = new Float32Array(prepared.morphTargets);
+  prepared.morphs.forEach(function (m) {
+    var w = (nodes && nodes[m.node] && nodes[m.node].weights) || m.weights;
+    for (var k = 0; k < m.nTargets; k++) out[m.targetBase + k] = w[k] === undefined ? 0 : w[k];
+  });
+  return out;
+}
+
 /** The joint records of a pose (Renderer.poseSkin) from the world matrix of every node (animation.js worldMatrices: 16 numbers
  *  each, column-major). The rest pose on the device is in world space, placed by the mesh node's world matrix, and glTF poses a
  *  skinned vertex by its joints alone, so the device matrix of joint j is jointWorld_j . inverseBind_j . meshWorld^-1: composed in
@@ -197,7 +255,9 @@ function skinPose(prepared, nodeWorldMatrices) {
  *  A file with skinned primitives (a node with `skin`, JOINTS_0 and WEIGHTS_0) also returns skinTriangles, skinCorners (skinList),
  *  skinJoints (the joints of all skin instances together) and skins: per skinned node { node, skin, joints (node indices),
  *  inverseBind, meshWorldInverse, jointBase } (opts.skins === false, or a file without skins: none of them, and every blob the
- *  same bytes) */
+ *  same bytes). A file with morph targets also returns morphTriangles, morphRowStart, morphDeltas (morphList), morphTargets (the
+ *  targets of all mesh instances together) and morphs: per morphed node { node, targetBase, nTargets, weights (its defaults) }
+ *  (opts.morphs === false, or a file without targets: none of them) */
 function prepareScene(gltf, opts) {
   var alphaCutout = !!(opts && opts.alphaCutout);
   var packed = require('./atlas').packing(gltf, { keepAlpha: alphaCutout });
@@ -219,8 +279,16 @@ function prepareScene(gltf, opts) {
       meshWorldInverse: require('./animation').invert4(Array.from(world.get(node))), jointBase: skinJoints };
     skinJoints += skin.joints.length;
   });
+  var morphs = [], morphTargets = 0;
+  if (!(opts && opts.morphs === false)) gltf.nodes.forEach(function (node, nodeIndex) {
+    var anim = require('./animation'), n = anim.targetCount(node);
+    if (!n) return;
+    morphs[nodeIndex] = { node: nodeIndex, targetBase: morphTargets, nTargets: n, weights: anim.defaultWeights(node) };
+    morphTargets += n;
+  });
   gltf.nodes.forEach(function (node, nodeIndex) {
-    processNode(gltf, node, allTriangles, allMaterials, allLights, world.get(node), packed.materials, nodeIndex, skins[nodeIndex]);
+    processNode(gltf, node, allTriangles, allMaterials, allLights, world.get(node), packed.materials, nodeIndex, skins[nodeIndex],
+      morphs[nodeIndex]);
     // one material per primitive, in the order processNode packs them
     if (alphaCutout && node.mesh) node.mesh.primitives.forEach(function (prim) { allCutoffs.push(alphaCutoffOf(prim.material)); });
   });
@@ -231,10 +299,13 @@ function prepareScene(gltf, opts) {
   var grouped = !(opts && opts.triangleGroups === false);       // false: no tags at all, and no table in the result
   if (grouped) tagGroups(triangles, allTriangles);
   var skinned = allTriangles.some(function (t) { return !!t.skin; });
-  if (skinned) tagPresort(triangles);
+  var morphed = allTriangles.some(function (t) { return !!t.morph; });
+  if (skinned || morphed) tagPresort(triangles);
   var bvh = a.buildBvh(triangles);
   var triangleGroups = grouped ? untagGroups(triangles) : undefined;
-  var skin = skinned ? skinList(allTriangles, untagPresort(triangles)) : undefined;
+  var presort = skinned || morphed ? untagPresort(triangles) : undefined;
+  var skin = skinned ? skinList(allTriangles, presort) : undefined;
+  var morph = morphed ? morphList(allTriangles, presort) : undefined;
   var lights = a.emissiveLights(triangles, materials, pack.packLights(allLights));
   return {
     blobs: { triangles: triangles, materials: materials, bvhNodes: bvh.nodes, lights: lights },
@@ -243,6 +314,9 @@ function prepareScene(gltf, opts) {
     groupNames: grouped ? gltf.nodes.map(function (n, i) { return n.name || 'node' + i; }) : undefined,
     skinTriangles: skin ? skin.triangles : undefined, skinCorners: skin ? skin.corners : undefined,
     skinJoints: skin ? skinJoints : undefined, skins: skin ? skins.filter(Boolean) : undefined,
+    morphTriangles: morph ? morph.triangles : undefined, morphRowStart: morph ? morph.rowStart : undefined,
+    morphDeltas: morph ? morph.deltas : undefined, morphTargets: morph ? morphTargets : undefined,
+    morphs: morph ? morphs.filter(Boolean) : undefined,
     atlas: packed.texture,
     counts: { triangles: allTriangles.length, materials: allMaterials.length, bvhNodes: bvh.nodes.byteLength / pack.BVH_NODE_SIZE,
       lights: lights.byteLength / pack.LIGHT_SIZE, punctualLights: allLights.length },
@@ -250,4 +324,4 @@ function prepareScene(gltf, opts) {
   };
 }
 
-module.exports = { prepareScene: prepareScene, skinPose: skinPose, extractNodeMatrix: extractNodeMatrix, buildMaterial: buildMaterial, alphaCutoffOf: alphaCutoffOf };
+module.exports = { prepareScene: prepareScene, skinPose: skinPose, morphPose: morphPose, extractNodeMatrix: extractNodeMatrix, buildMaterial: buildMaterial, alphaCutoffOf: alphaCutoffOf };

@@ -65,12 +65,15 @@ def encode_png(pixels, color_type=6, filters=None, palette=None, trns=None, dept
 
 def write_glb(path, meshes, nodes, materials, lights=None, images=None, textures=None, skins=None, animations=None):
     """meshes: list of dicts {positions (N,3), normals (N,3), uvs (N,2) or None, indices (M,), material or None,
-    joints (N,4) and weights (N,4) or absent: JOINTS_0 as uint16 and WEIGHTS_0 as float32};
-    nodes: list of dicts {mesh?, skin?, light?, translation?, rotation?, scale?, matrix?, children?};
+    joints (N,4) and weights (N,4) or absent: JOINTS_0 as uint16 and WEIGHTS_0 as float32,
+    targets or absent: morph targets, a list of dicts {positions (N,3) or None, normals (N,3) or None}, morph_weights or absent: the
+    mesh's default weights};
+    nodes: list of dicts {mesh?, skin?, light?, translation?, rotation?, scale?, matrix?, children?, weights?};
     images: list of encoded image files (bytes, PNG); textures: list of image indices (one glTF texture each);
     skins: list of dicts {joints: node indices, inverseBindMatrices: (n,16) column-major or None};
-    animations: list of dicts {channels: [{node, path, sampler}], samplers: [{input: times, output: (k, width), interpolation}]}.
-    Without skins and animations the file is the bytes it always was."""
+    animations: list of dicts {channels: [{node, path, sampler}], samplers: [{input: times, output: (k, width), interpolation}]};
+    a sampler with scalar=True (a `weights` channel) writes its output as k * width scalars.
+    Without skins, animations and targets the file is the bytes it always was."""
     bin_parts, views, accessors = [], [], []
 
     def add(arr, target, ctype, atype):
@@ -99,10 +102,21 @@ def write_glb(path, meshes, nodes, materials, lights=None, images=None, textures
         prim = {"attributes": attrs, "indices": add(np.asarray(m["indices"], np.uint16), 34963, 5123, "SCALAR")}
         if m.get("material") is not None:
             prim["material"] = m["material"]
+        if m.get("targets"):
+            prim["targets"] = []
+            for t in m["targets"]:
+                o = {}
+                if t.get("positions") is not None:
+                    o["POSITION"] = add(np.asarray(t["positions"], np.float32), 34962, 5126, "VEC3")
+                if t.get("normals") is not None:
+                    o["NORMAL"] = add(np.asarray(t["normals"], np.float32), 34962, 5126, "VEC3")
+                prim["targets"].append(o)
         jm.append({"primitives": [prim]})
+        if m.get("morph_weights") is not None:
+            jm[-1]["weights"] = [float(w) for w in m["morph_weights"]]
     jn = []
     for n in nodes:
-        o = {k: n[k] for k in ("mesh", "skin", "translation", "rotation", "scale", "matrix", "children", "name") if k in n}
+        o = {k: n[k] for k in ("mesh", "skin", "translation", "rotation", "scale", "matrix", "children", "name", "weights") if k in n}
         if "light" in n:
             o["extensions"] = {"KHR_lights_punctual": {"light": n["light"]}}
         jn.append(o)
@@ -122,11 +136,11 @@ def write_glb(path, meshes, nodes, materials, lights=None, images=None, textures
             samplers = []
             for sm in an["samplers"]:
                 out = np.asarray(sm["output"], np.float32)
-                out = out.reshape(len(out), -1)
+                out = out.reshape(-1) if sm.get("scalar") else out.reshape(len(out), -1)
                 times = np.asarray(sm["input"], np.float32)
                 i = add(times, None, 5126, "SCALAR")
                 accessors[i]["min"], accessors[i]["max"] = [float(times.min())], [float(times.max())]
-                samplers.append({"input": i, "output": add(out, None, 5126, {3: "VEC3", 4: "VEC4"}[out.shape[1]]),
+                samplers.append({"input": i, "output": add(out, None, 5126, "SCALAR" if out.ndim == 1 else {3: "VEC3", 4: "VEC4"}[out.shape[1]]),
                                  "interpolation": sm.get("interpolation", "LINEAR")})
             doc["animations"].append({"samplers": samplers, "channels": [
                 {"sampler": int(c["sampler"]), "target": {"node": int(c["node"]), "path": c["path"]}} for c in an["channels"]]})

@@ -52,6 +52,7 @@ EXPORTS = [
     "ptmi_set_triangle_groups", "ptmi_transform_groups", "ptmi_transform_status", "ptmi_normal_matrix", "ptmi_debug_read_triangles",
     "ptmi_multi_set_triangle_groups", "ptmi_multi_transform_groups", "ptmi_multi_transform_status",
     "ptmi_set_skin", "ptmi_pose_skin", "ptmi_skin_status", "ptmi_multi_set_skin", "ptmi_multi_pose_skin", "ptmi_multi_skin_status",
+    "ptmi_set_morph", "ptmi_pose_morph", "ptmi_morph_status", "ptmi_multi_set_morph", "ptmi_multi_pose_morph", "ptmi_multi_morph_status",
 ]
 MULTI_LOOPBACK = 1
 MULTI_PLANE_MOMENTS, MULTI_PLANE_OUTPUT = 0x100, 0x200      # gather_planes: with the AOV_* bits
@@ -227,6 +228,18 @@ class SkinStatus(ctypes.Structure):
                 "first_bad": int(self.first_bad), "pose_ms": float(self.pose_ms)}
 
 
+class MorphStatus(ctypes.Structure):
+    """struct ptmi_morph_status: the morph in place and the poses since it was set (include/ptmi.h)"""
+    _fields_ = [("present", ctypes.c_uint32), ("n_targets", ctypes.c_uint32), ("n_morphed", ctypes.c_uint32), ("n_records", ctypes.c_uint32),
+                ("n_in_skin", ctypes.c_uint32), ("poses", ctypes.c_uint32), ("active_targets", ctypes.c_uint32),
+                ("first_bad", ctypes.c_uint32), ("skin_stale", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("pose_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        d = {n: int(getattr(self, n)) for n, _ in self._fields_ if n not in ("reserved", "pose_ms")}
+        d["pose_ms"] = float(self.pose_ms)
+        return d
+
+
 class AlphaParams(ctypes.Structure):
     """ptmi_alpha_params; max_layers 0 picks the default (include/ptmi.h)"""
     _fields_ = [("max_layers", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
@@ -290,6 +303,8 @@ _SHARED = {
     "transform_status": [ctypes.c_void_p],
     "set_skin": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32], "pose_skin": [ctypes.c_void_p, ctypes.c_uint32],
     "skin_status": [ctypes.c_void_p],
+    "set_morph": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32],
+    "pose_morph": [ctypes.c_void_p, ctypes.c_uint32], "morph_status": [ctypes.c_void_p],
 }
 _lib = None
 
@@ -652,6 +667,41 @@ class _Handle:
     def skin_status(self):
         st = SkinStatus()
         self._ck(self._c.skin_status(self.h, ctypes.byref(st)))
+        return st
+
+    # -- morphed triangles posed on the device (include/ptmi.h ptmi_set_morph) ------------------------------------------
+    def set_morph(self, triangles, row_start=None, deltas=None, n_targets=0, n_morphed=None):
+        """lists the morphed triangles (ascending uint32 indices, uploaded order) with their layout.MORPH_DELTA records in
+        compressed-row form (row e: deltas[row_start[e]:row_start[e + 1]], ascending by target) for n_targets targets, and snapshots
+        their rest pose; triangles None removes the morph. row_start / deltas None pass NULL and n_morphed overrides the count passed
+        (for tests)."""
+        if triangles is None:
+            self._ck(self._c.set_morph(self.h, None, None, None, 0, n_targets))
+            return
+        t = np.ascontiguousarray(triangles, np.uint32).reshape(-1)
+        r = None if row_start is None else np.ascontiguousarray(row_start, np.uint32).reshape(-1)
+        d = None if deltas is None else np.ascontiguousarray(deltas, layout.MORPH_DELTA).reshape(-1)
+        if r is not None and len(r) != len(t) + 1:
+            raise ValueError(f"{len(r)} row bounds for {len(t)} triangles: one more than triangles")
+        if r is not None and d is not None and len(r) and int(r.max()) > len(d):
+            raise ValueError(f"row_start reaches {int(r.max())} of {len(d)} records")
+        self._ck(self._c.set_morph(self.h, _p(t) if len(t) else None, _p(r), None if d is None or not len(d) else _p(d),
+                                   len(t) if n_morphed is None else n_morphed, n_targets))
+
+    def pose_morph(self, weights, n_targets=None):
+        """poses the morph: every listed triangle becomes its rest record plus the weighted deltas of its row (targets of weight zero
+        are skipped), and the trees are refitted on the device; triangles the skin in place lists too go to the skin's rest pose
+        instead and wait for pose_skin. weights: one float per target. n_targets overrides the count passed (for tests; weights None
+        then passes NULL)."""
+        if weights is None:
+            self._ck(self._c.pose_morph(self.h, None, n_targets or 0))
+            return
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        self._ck(self._c.pose_morph(self.h, _p(w) if len(w) else None, len(w) if n_targets is None else n_targets))
+
+    def morph_status(self):
+        st = MorphStatus()
+        self._ck(self._c.morph_status(self.h, ctypes.byref(st)))
         return st
 
     # -- alpha cutouts (include/ptmi.h ptmi_set_alpha_cutoff) ---------------------------------------------------------
