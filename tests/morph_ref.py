@@ -39,12 +39,9 @@ def applied_counts(row_start, deltas, weights):
     return total[row_start[1:]] - total[row_start[:-1]]
 
 
-def morphed(tris, rest, listed, row_start, deltas, weights):
-    """the records after pose_morph(weights) where every listed triangle goes to its live record: the listed triangles become their
-    rest pose plus the weighted records of their rows, everything else keeps its bytes. rest: transform_ref.rest_of of the records
-    the morph was set on (indexed by triangle); listed: ascending triangle indices; row_start: len(listed) + 1 bounds; deltas:
-    layout.MORPH_DELTA records."""
-    out = tris.copy()
+def summed(rest, listed, row_start, deltas, weights):
+    """(the six running vectors of every list entry after its row, before the normal tail: a dict of (len(listed), 3) float32 arrays;
+    which entries had a record applied)"""
     listed = np.asarray(listed, np.int64)
     row_start = np.asarray(row_start, np.int64)
     deltas = np.asarray(deltas, layout.MORPH_DELTA).reshape(-1)
@@ -62,6 +59,17 @@ def morphed(tris, rest, listed, row_start, deltas, weights):
             touched[rows] = True
             for f, g in zip(VERTS + NORMALS, DV + DN):
                 acc[f][rows] = acc[f][rows] + w[:, None] * deltas[g][rec]
+    return acc, touched
+
+
+def morphed(tris, rest, listed, row_start, deltas, weights):
+    """the records after pose_morph(weights) where every listed triangle goes to its live record: the listed triangles become their
+    rest pose plus the weighted records of their rows, everything else keeps its bytes. rest: transform_ref.rest_of of the records
+    the morph was set on (indexed by triangle); listed: ascending triangle indices; row_start: len(listed) + 1 bounds; deltas:
+    layout.MORPH_DELTA records."""
+    out = tris.copy()
+    listed = np.asarray(listed, np.int64)
+    acc, touched = summed(rest, listed, row_start, deltas, weights)
     for f in VERTS:
         out[f][listed] = acc[f]
     for f in NORMALS:

@@ -8,7 +8,9 @@ small render, and cost_now. On one upload mode per case B's render also equals t
 The scenes are the smallest that cover: lists of 1 and 5, a scattered third of cornell (332) with rows of 0 .. 3 records mixed, all of
 soup80 with 40 targets of which 3 are non-zero (rows of which no record is applied among them), half of grid80 (6 246: no multiple of
 8 or of 64, the device builder), one target, and 8 192 targets (the whole 32 KB of LDS) every one of which some record names. Lists of
-more than one round of the grid are in tests/test_gpu_morph_rounds.py, the skin beside the morph in tests/test_gpu_morph_skin.py.
+more than one round of the grid are in tests/test_gpu_morph_rounds.py, the skin beside the morph in tests/test_gpu_morph_skin.py, and
+the value edges (normal magnitudes, weights as given, the edge of the vertex check), rows of 8 192 records, refusals with a skin in
+place, the groups beside the morph, the re-base ranges and motion with a mixed list in tests/test_gpu_morph_edges.py.
 
 Every case fails without the feature: the binding has no set_morph."""
 import numpy as np
