@@ -919,7 +919,7 @@ int ptmi_multi_morph_status(ptmi_multi *m, struct ptmi_morph_status *out);
  * (the reference's own rule for shadow rays), on the one-stream schedule whatever ptmi_options.overlap says (the stored option is left
  * alone); a table whose holes no ray meets gives the bits of a render without it. max_layers bounds the holes one ray may pass per
  * segment: a path ray still on a hole after that many takes the hit as opaque, a shadow ray is occluded, and both are counted.
- * LIMITS: alphaMode BLEND stays opaque; a light sample aimed at an emissive triangle ignores that triangle's own cutout; the medium's
+ * LIMITS: alphaMode BLEND stays opaque without ptmi_set_alpha_blend; a light sample aimed at an emissive triangle ignores that triangle's own cutout; the medium's
  * box is not cut by holes; no overlap while active.
  * cutoff NULL or n_materials 0 removes the table. PTMI_E_INVALID: no scene, n_materials different from the uploaded count, an entry
  * that is negative or not finite, max_layers > 32, a non-zero reserved word; a failed call leaves the previous table in place. The call
@@ -939,6 +939,55 @@ int ptmi_alpha_status(ptmi_ctx *ctx, struct ptmi_alpha_status *out);      /* syn
 /* the table on every device, checked once before any device changes; the counters summed over the devices, the rest device 0's */
 int ptmi_multi_set_alpha_cutoff(ptmi_multi *m, const float *cutoff, uint32_t n_materials, const ptmi_alpha_params *params);
 int ptmi_multi_alpha_status(ptmi_multi *m, struct ptmi_alpha_status *out);
+
+/* ---- alpha blending: hashed stochastic transparency -----------------------------------------
+ * A per-material blend table for the loaded scene, one float per uploaded material. An entry < 0: the material is not blended (the
+ * state of every material without a table; hosts write -1). An entry f in [0, 1]: the material is blended with factor f (glTF's
+ * alphaMode BLEND; f is baseColorFactor[3]). A hit on a blended material examines alpha = f * a_texel, one float32 multiply, where
+ * a_texel is the fourth channel of the albedo map's texel at the hit, fetched as for the cutoff rule (no albedo map: 1). The hit is
+ * NOT THERE iff alpha <= xi, with xi = float(h >> 8) * 2^-24 in [0, 1) and h a hash of the ray itself (Wyman and McGuire's hashed
+ * alpha testing), in wrapping uint32 arithmetic:
+ *     mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *     h = 0x9E3779B9;  for w in bits(o.x), bits(o.y), bits(o.z), bits(d.x), bits(d.y), bits(d.z), tri, seed:  h = mix(h ^ w)
+ * (o, d) is the ray of the leg as the resolve loop holds it: the path's own origin and direction (the shadow record's, for a shadow
+ * ray) on the first leg, the stepped origin and the same direction after each hole passed; bits() is the float's IEEE word (so -0.0
+ * and 0.0 differ); tri is the hit triangle's index and seed the table's. So: alpha = 1 is always there, alpha = 0 is never there, and
+ * in between the hit is there with probability alpha. The threshold is no draw from the path's RNG stream: a ray that passes a blended
+ * hit goes on with exactly the bits it would have in a scene without that triangle, as a ray on a cutout hole does (no bounce
+ * counted, no RNG draw, no throughput change), past it by the same step, reporting the distance along its original ray, under the
+ * max_layers bound: a path ray still on an absent hit after that many takes it as opaque, a shadow ray is occluded, both counted
+ * (ptmi_alpha_status). A camera ray's direction changes with every frame's jitter, so frames are decorrelated and the accumulated
+ * image converges to the blend. Shadow rays take the same rule: a light sample's expected visibility through blended layers is the
+ * product of (1 - alpha). Where a cutoff table is in place too, a hit is absent if either rule says so; the cutoff rule is asked
+ * first, and a MASK hole computes no hash and counts no test.
+ * Inactive (no table, or no entry >= 0): every call issues the launches and gives the bits it gives without this feature. Active: the
+ * schedule of an active cutoff table (ptmi_set_alpha_cutoff above: the two resolve loops, one stream), with either table or both;
+ * ptmi_debug_alpha_intersect / _occluded work with either. Each table keeps its own max_layers; the loops run to the larger of those
+ * in place. ptmi_alpha_status's passes and exhausted counts count every hole passed, blended ones included.
+ * LIMITS: coverage only: order-dependent compositing, coloured transmission and refraction are not modelled. A light sample aimed at
+ * an emissive triangle ignores that triangle's own blend; the medium's box is not cut; ptmi_reproject's centre rays and the
+ * first-hit planes take the same rule, so a blended surface appears in about alpha of its pixels or frames and the planes hold the
+ * mixture.
+ * factor NULL or n_materials 0 removes the table. PTMI_E_INVALID: no scene, n_materials different from the uploaded count, an entry
+ * that is not finite or above 1, max_layers > 32, a non-zero reserved word; a failed call leaves the previous table in place. The call
+ * waits for the work in flight and leaves the output and the planes alone. ptmi_upload_scene removes the table; ptmi_upload_atlas and
+ * the ptmi_update_* calls leave it alone. */
+typedef struct ptmi_alpha_blend_params {
+    uint32_t max_layers;      /* absent hits one ray may pass per segment, 1..32; 0 = default (4) */
+    uint32_t seed;            /* the last word of the hash */
+    uint32_t reserved[2];     /* must be 0 */
+} ptmi_alpha_blend_params;    /* 16 bytes */
+/* tests: hits on blended materials that were examined; passes: those found absent (whether or not the ray could still go on) — all
+ * four since ptmi_reset_stats. A struct tag only. */
+struct ptmi_alpha_blend_status {
+    uint32_t present, n_materials, n_blend, max_layers, seed, reserved;   /* a table is in place; its length, entries >= 0, limit, seed */
+    uint64_t path_tests, path_passes, shadow_tests, shadow_passes;
+};                            /* 56 bytes */
+int ptmi_set_alpha_blend(ptmi_ctx *ctx, const float *factor, uint32_t n_materials, const ptmi_alpha_blend_params *params /* NULL: defaults */);
+int ptmi_alpha_blend_status(ptmi_ctx *ctx, struct ptmi_alpha_blend_status *out);      /* synchronises */
+/* the table on every device, checked once before any device changes; the counters summed over the devices, the rest device 0's */
+int ptmi_multi_set_alpha_blend(ptmi_multi *m, const float *factor, uint32_t n_materials, const ptmi_alpha_blend_params *params);
+int ptmi_multi_alpha_blend_status(ptmi_multi *m, struct ptmi_alpha_blend_status *out);
 
 /* ---- statistics ----------------------------------------------------------- */
 int ptmi_get_stats(ptmi_ctx *ctx, ptmi_stats *out);           /* synchronises */
@@ -960,8 +1009,8 @@ int ptmi_debug_intersect(ptmi_ctx *ctx, uint32_t n, const float *o3, const float
  * consulted. */
 int ptmi_debug_occluded(ptmi_ctx *ctx, uint32_t n, const float *o3, const float *d3,
                         const float *dist, uint8_t *occluded);
-/* The two loops of an active alpha cutoff table on caller rays, the very loops the renders run (PTMI_E_STATE without a table that has
- * a positive entry). intersect: `extend`, then the path loop -> the first hit that is there, t measured along the caller's ray (-1 /
+/* The two loops of an active alpha cutoff or blend table on caller rays, the very loops the renders run (PTMI_E_STATE without a
+ * cutoff table that has a positive entry or a blend table that has an entry >= 0). intersect: `extend`, then the path loop -> the first hit that is there, t measured along the caller's ray (-1 /
  * 0xFFFFFFFF: a miss). occluded: the shadow stage of a bounce with the verdict written out instead of added; dist as for
  * ptmi_debug_occluded. layers[i]: the holes ray i passed, or max_layers + 1 for a ray still on a hole after max_layers (its hit is
  * reported as it stands / it is occluded). */

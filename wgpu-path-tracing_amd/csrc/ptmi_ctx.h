@@ -8,7 +8,7 @@
 //   medium.hip         the participating medium: its checks, installation and removal, its debug entry points
 //   medium_grid.hip    the medium's density grid: its checks, upload and removal, its debug entry points
 //   scene_update.hip   edits of a loaded scene in place: ptmi_update_triangles (the refit on the device), _materials, _lights
-//   alpha.hip          alpha cutouts: the cutoff table, the two resolve loops between the existing kernels, their debug entry points
+//   alpha.hip          alpha cutouts and blending: the cutoff and blend tables, the two resolve loops between the existing kernels, their debug entry points
 //   scene_rebuild.hip  the walked own-leaf tree rebuilt in place: the unit list on the device, the swap (ptmi_rebuild_tree)
 //   motion.hip         reprojection across a geometry edit: the previous positions, their commit, the motion plane (ptmi_set_motion)
 //   scene_pose.hip     what the three below share on the host: the check-then-write sequence of a pose, the rest-pose snapshot
@@ -51,6 +51,8 @@ bool pt_ctx_has_medium_grid(const ptmi_ctx *c);
 // the argument checks of ptmi_set_alpha_cutoff that need no context (alpha.hip): PTMI_E_INVALID with the reason in err; cutoff NULL
 // (removal) checks the params alone. And what its other checks compare with: whether c has a scene, and how many materials.
 int pt_check_alpha_cutoff(const float *cutoff, uint32_t n_materials, const ptmi_alpha_params *params, std::string &err);
+// likewise for ptmi_set_alpha_blend: factor NULL (removal) checks the params alone
+int pt_check_alpha_blend(const float *factor, uint32_t n_materials, const ptmi_alpha_blend_params *params, std::string &err);
 bool pt_ctx_has_scene(const ptmi_ctx *c);
 uint32_t pt_ctx_materials(const ptmi_ctx *c);
 hipStream_t pt_ctx_stream(ptmi_ctx *c);
@@ -102,6 +104,7 @@ enum SceneBuf {
     kPlanUnits, kPlanExact,            // own leaves: the unit box of every listed triangle (leaf order); both exact child boxes per node
     kPlanWords,                        // the reduction words of one update and the partial sums of the cost
     kAlphaCutoff,                      // the per-material cutoff table of ptmi_set_alpha_cutoff (alpha.hip); gone with the next upload
+    kAlphaBlend,                       // the per-material blend table of ptmi_set_alpha_blend (alpha.hip); gone with the next upload
     kMotionPrev,                       // the previous positions of ptmi_set_motion (motion.hip): 3 float4 per triangle; re-made by an upload
     // triangle groups (ptmi_set_triangle_groups; scene_transform.hip), gone with the next upload:
     kGroupTab,                         // one group id per uploaded triangle
@@ -212,6 +215,10 @@ struct ptmi_ctx {
     // alpha cutouts (ptmi_set_alpha_cutoff; alpha.hip): the table is buf[kAlphaCutoff], one float per material of the loaded scene
     bool alpha_present = false;                        // a table is in place
     uint32_t alpha_cutout = 0, alpha_layers = 0;       // its positive entries (0: inactive, no launch and no buffer differs); max_layers, resolved
+    // alpha blending (ptmi_set_alpha_blend; alpha.hip): the table is buf[kAlphaBlend], one float per material of the loaded scene
+    bool blend_present = false;                        // a table is in place
+    uint32_t blend_count = 0, blend_layers = 0;        // its entries >= 0 (0: inactive, as above); max_layers, resolved
+    uint32_t blend_seed = 0;                           // ptmi_alpha_blend_params.seed
     DevScene *d_scene = nullptr;                       // sc in device memory (DevScene::self), rewritten whenever sc changes
     DevScene sc{};
     bool have_scene = false;
@@ -395,8 +402,9 @@ void motion_widen(ptmi_ctx *c, uint32_t first, uint32_t count);
 int motion_commit(ptmi_ctx *c);
 inline size_t motion_prev_bytes(uint32_t n_tris) { return n_tris ? (size_t)n_tris * 48u : 16u; }
 
-// alpha.hip. Active: a table with a positive entry is in place; only then do the loops run and the lane carry their arrays.
-inline bool alpha_active(const ptmi_ctx *c) { return c->alpha_cutout != 0u; }
+// alpha.hip. Active: a cutoff table with a positive entry or a blend table with an entry >= 0 is in place; only then do the loops run
+// and the lane carry their arrays.
+inline bool alpha_active(const ptmi_ctx *c) { return c->alpha_cutout != 0u || c->blend_count != 0u; }
 // the path loop on the *count hit records `extend` (variant cfg) has just written for the rays p.O / p.D at queue[i] (NULL: i), on stream s
 void alpha_resolve_paths(ptmi_ctx *c, hipStream_t s, const TraverseConfig &cfg, DevPaths p, const uint32_t *queue, const uint32_t *count,
                          float2 *hits, uint32_t *layers_out);

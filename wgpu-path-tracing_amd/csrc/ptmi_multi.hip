@@ -499,6 +499,34 @@ int ptmi_multi_alpha_status(ptmi_multi *m, struct ptmi_alpha_status *out) {
     return PTMI_OK;
 }
 
+// The alpha blend table on every device (alpha.hip), by the cutoff call's pattern.
+int ptmi_multi_set_alpha_blend(ptmi_multi *m, const float *factor, uint32_t n_materials, const ptmi_alpha_blend_params *params) {
+    if (!m) return PTMI_E_INVALID;
+    std::string why;                        // checked once, before any device changes: a rejected table leaves every shard's in place
+    if (!pt_ctx_has_scene(m->d[0].ctx)) return mfail(m, PTMI_E_INVALID, "no scene uploaded: the table belongs to a scene's materials");
+    const bool remove = !factor || n_materials == 0u;
+    const int rc = pt_check_alpha_blend(remove ? nullptr : factor, n_materials, params, why);
+    if (rc) return mfail(m, rc, "%s", why.c_str());
+    if (!remove && n_materials != pt_ctx_materials(m->d[0].ctx))
+        return mfail(m, PTMI_E_INVALID, "n_materials %u is not the loaded scene's %u", n_materials, pt_ctx_materials(m->d[0].ctx));
+    return each_ctx(m, "ptmi_set_alpha_blend", ptmi_set_alpha_blend, factor, n_materials, params);
+}
+
+int ptmi_multi_alpha_blend_status(ptmi_multi *m, struct ptmi_alpha_blend_status *out) {
+    if (!m || !out) return PTMI_E_INVALID;
+    for (int i = 0; i < (int)m->d.size(); i++) {
+        struct ptmi_alpha_blend_status st;
+        const int rc = ptmi_alpha_blend_status(m->d[i].ctx, &st);
+        if (rc) return cfail(m, i, rc, "ptmi_alpha_blend_status");
+        if (i == 0) *out = st;
+        else {
+            out->path_tests += st.path_tests; out->path_passes += st.path_passes;
+            out->shadow_tests += st.shadow_tests; out->shadow_passes += st.shadow_passes;
+        }
+    }
+    return PTMI_OK;
+}
+
 // The edits of a loaded scene on every device (scene_update.hip). Every device holds the same scene under the same options and checks
 // before it changes anything, so a refused call is refused by the first device and leaves them all as they were.
 int ptmi_multi_update_triangles(ptmi_multi *m, uint32_t first, uint32_t count, const ptmi_triangle *tris) {

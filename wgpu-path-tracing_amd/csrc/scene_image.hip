@@ -481,6 +481,7 @@ int pt_install_scene(ptmi_ctx *c, PtPrepared *prep) {
     }
     // the alpha cutoff table belonged to the old scene's materials (its buffer went with the others above); the loops' arrays go too
     c->alpha_present = false; c->alpha_cutout = c->alpha_layers = 0u;
+    c->blend_present = false; c->blend_count = c->blend_layers = c->blend_seed = 0u;        // ... and so did the blend table
     for (int k = kAlphaO; k <= kAlphaHits; k++) dfree(c->lane.buf[k]);
     lane_views(c->lane);
     groups_forget(c);                          // the group table named the old scene's triangles (its buffers went with the others above)

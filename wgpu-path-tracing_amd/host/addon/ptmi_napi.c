@@ -549,6 +549,40 @@ static napi_value js_alpha_status(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* setAlphaBlend(handle, Float32Array | null, maxLayers, seed): ptmi_set_alpha_blend; one entry per uploaded material, null removes the table */
+static napi_value js_set_alpha_blend(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    handle *h = get_handle(env, info, 4, argv);
+    if (!h) return NULL;
+    void *p; size_t n;
+    ptmi_alpha_blend_params prm = {0};
+    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
+    napi_get_value_uint32(env, argv[2], &prm.max_layers);
+    napi_get_value_uint32(env, argv[3], &prm.seed);
+    if (n % sizeof(float)) { napi_throw_range_error(env, NULL, "blend table is not whole floats"); return NULL; }
+    CALL(env, h, set_alpha_blend, (const float *)p, (uint32_t)(n / sizeof(float)), &prm);
+    return NULL;
+}
+
+/* alphaBlendStatus(handle) -> {present, materials, blend, maxLayers, seed, pathTests, pathPasses, shadowTests, shadowPasses} */
+static napi_value js_alpha_blend_status(napi_env env, napi_callback_info info) {
+    napi_value argv[1], out, v;
+    handle *h = get_handle(env, info, 1, argv);
+    if (!h) return NULL;
+    struct ptmi_alpha_blend_status st;
+    CALL(env, h, alpha_blend_status, &st);
+    NAPI_OK(env, napi_create_object(env, &out));
+    const struct { const char *name; double value; } num[] = {
+        {"present", st.present}, {"materials", st.n_materials}, {"blend", st.n_blend}, {"maxLayers", st.max_layers}, {"seed", st.seed},
+        {"pathTests", (double)st.path_tests}, {"pathPasses", (double)st.path_passes},
+        {"shadowTests", (double)st.shadow_tests}, {"shadowPasses", (double)st.shadow_passes}};
+    for (size_t i = 0; i < sizeof num / sizeof num[0]; i++) {
+        NAPI_OK(env, napi_create_double(env, num[i].value, &v));
+        NAPI_OK(env, napi_set_named_property(env, out, num[i].name, v));
+    }
+    return out;
+}
+
 static napi_value js_resize(napi_env env, napi_callback_info info) {
     napi_value argv[3];
     handle *h = get_handle(env, info, 3, argv);
@@ -1080,6 +1114,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"setMorph", js_set_morph}, {"poseMorph", js_pose_morph}, {"morphStatus", js_morph_status},
         {"rebuildTree", js_rebuild_tree}, {"rebuildStatus", js_rebuild_status},
         {"setAlphaCutoff", js_set_alpha_cutoff}, {"alphaStatus", js_alpha_status},
+        {"setAlphaBlend", js_set_alpha_blend}, {"alphaBlendStatus", js_alpha_blend_status},
         {"resize", js_resize}, {"setOptions", js_set_options},
         {"dispatch", js_dispatch}, {"gather", js_gather}, {"gatherPlanes", js_gather_planes}, {"synchronize", js_synchronize}, {"throttle", js_throttle},
         {"readOutput", js_read_output}, {"writeOutput", js_write_output}, {"setAovs", js_set_aovs}, {"readAov", js_read_aov},

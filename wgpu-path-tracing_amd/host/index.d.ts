@@ -61,17 +61,31 @@ export class Renderer {
                           alphaCutout?: boolean;
                           /** ... with this maxLayers (0 / absent: the library's default, 4) */
                           alphaLayers?: number;
+                          /** loadModel of a .glb keeps the alpha of albedo maps in the atlas and blends every alphaMode "BLEND" material
+                           *  with its baseColorFactor[3] as hashed stochastic transparency (setAlphaBlend; maxLayers = alphaLayers);
+                           *  off (the default): BLEND materials are opaque */
+                          alphaBlend?: boolean;
+                          /** ... with this seed (absent: 0) */
+                          alphaBlendSeed?: number;
                           /** updateTriangles calls rebuildTree() when it leaves sceneUpdateStatus().costNow / costBuilt above this ratio.
                            *  Off (0 / absent) by default; a rebuild was measured to pay from roughly 1.2 - 1.3 (README.md) */
                           rebuildAbove?: number });
   camera: CameraCPU;
   addOnUpdate(callback: (deltaTime: number) => void): void;
-  loadModel(model: string | SceneData | { blobs: SceneBlobs; atlas?: Atlas | null; alphaCutoff?: Float32Array }, atlas?: Atlas): Promise<void>;
+  loadModel(model: string | SceneData | { blobs: SceneBlobs; atlas?: Atlas | null; alphaCutoff?: Float32Array;
+                                         alphaBlend?: Float32Array | null }, atlas?: Atlas): Promise<void>;
   /** alpha cutouts (include/ptmi.h ptmi_set_alpha_cutoff): one cutoff per material of the loaded scene, 0 opaque, > 0: a hit is absent
    *  where the albedo map's alpha is below it; null removes the table, and so does loadModel. Restarts accumulation. */
   setAlphaCutoff(cutoff: Float32Array | null, opts?: { maxLayers?: number }): void;
   /** the table in place and what its loops counted since the statistics were reset; synchronises */
   alphaStatus(): AlphaStatus;
+  /** alpha blending (include/ptmi.h ptmi_set_alpha_blend): one entry per material of the loaded scene, < 0 not blended, f in [0, 1]: a
+   *  hit is absent where f * the albedo map's alpha is at or below a hash of the ray, so it is there with probability alpha and frames
+   *  accumulate to the blend; null removes the table, and so does loadModel. Coverage only: no sorting, no coloured transmission.
+   *  Restarts accumulation. */
+  setAlphaBlend(factor: Float32Array | null, opts?: { maxLayers?: number; seed?: number }): void;
+  /** the blend table in place and what the loops counted for it since the statistics were reset; synchronises */
+  alphaBlendStatus(): AlphaBlendStatus;
   /** the environment map behind every miss: float32 RGBA texels, equirectangular, row 0 at the +Y pole; null removes it.
    *  Restarts accumulation. */
   setEnvironment(texels: Float32Array | null, width?: number, height?: number, opts?: EnvironmentOptions): void;
@@ -205,6 +219,11 @@ export interface MediumOptions {
 export interface AlphaStatus {
   present: number; materials: number; cutout: number; maxLayers: number;
   pathPasses: number; pathExhausted: number; shadowPasses: number; shadowExhausted: number;
+}
+/** ptmi_alpha_blend_status: tests = hits on blended materials examined, passes = those found absent */
+export interface AlphaBlendStatus {
+  present: number; materials: number; blend: number; maxLayers: number; seed: number;
+  pathTests: number; pathPasses: number; shadowTests: number; shadowPasses: number;
 }
 /** ptmi_transform_status: the group table in place and the transforms since it was set */
 export interface TransformStatus {

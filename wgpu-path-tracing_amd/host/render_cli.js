@@ -9,7 +9,7 @@
  *                       --env file.hdr --env-intensity X --env-rotation DEGREES --env-sample 0|1
  *                       --fog sigma_t[,albedo[,g]] --fog-density file.f32 --fog-grid nx,ny,nz --fog-filter nearest|linear
  *                       --devices 0,1,... --loopback --aov albedo|normal|id --aov-out plane.bin
- *                       --alpha-cutout --alpha-layers N --animation N --time S]
+ *                       --alpha-cutout --alpha-blend --alpha-seed N --alpha-layers N --animation N --time S]
  * --batch K traces K frames per dispatch instead of one. --denoise keeps the denoiser's planes and makes --png the tone-mapped
  * denoised image (include/ptmi.h ptmi_denoise, default parameters). --adaptive renders to a noise level instead of --frames
  * (include/ptmi.h ptmi_dispatch_adaptive): rounds until none lists a pixel, or --rounds R of them; the JSON line then also holds
@@ -26,6 +26,9 @@
  * --alpha-cutout (a .glb scene): materials with alphaMode "MASK" become cutouts at their alphaCutoff (include/ptmi.h
  * ptmi_set_alpha_cutoff): the atlas keeps the alpha of albedo maps, and paths and shadow rays pass where it is below the cutoff, through
  * at most --alpha-layers N holes per segment (default: the library's, 4); the JSON line then also holds alpha: the table's status.
+ * --alpha-blend (a .glb scene): materials with alphaMode "BLEND" are blended with their baseColorFactor[3] as hashed stochastic
+ * transparency (include/ptmi.h ptmi_set_alpha_blend; --alpha-seed N: the hash's seed, --alpha-layers as above); the JSON line then
+ * also holds alphaBlend: the table's status.
  * --animation N --time S (a .glb scene with a skin or morph targets): renders one frame posed at S seconds (default 0) of the file's
  * animation N (Renderer.poseAt; include/ptmi.h ptmi_pose_morph, ptmi_pose_skin); the JSON line then also holds skin and morph: their
  * status.
@@ -51,9 +54,10 @@ function textArg(name) {
 var devices = textArg('devices') ? textArg('devices').split(',').map(Number) : null;
 var aov = textArg('aov');
 
-var alphaCutout = process.argv.indexOf('--alpha-cutout') >= 0;
+var alphaCutout = process.argv.indexOf('--alpha-cutout') >= 0, alphaBlend = process.argv.indexOf('--alpha-blend') >= 0;
 var r = new host.Renderer({ width: W, height: H, devices: devices || undefined, loopback: process.argv.indexOf('--loopback') >= 0,
                             alphaCutout: alphaCutout, alphaLayers: arg('alpha-layers', 0),
+                            alphaBlend: alphaBlend, alphaBlendSeed: arg('alpha-seed', 0),
                             options: { maxBounces: arg('bounces', 8), doMis: arg('mis', 1) } });
 r.camera.aperture = arg('aperture', r.camera.aperture);
 r.camera.focusDistance = arg('focus', r.camera.focusDistance);
@@ -112,6 +116,7 @@ r.loadModel(scenePath).then(function () {
   st.wallMs = ms; st.width = W; st.height = H; st.frames = frames;
   if (status) st.frames = 0;                // no uniform frames: the counts are per pixel
   if (alphaCutout) st.alpha = r.alphaStatus();
+  if (alphaBlend) st.alphaBlend = r.alphaBlendStatus();
   if (textArg('animation') !== null) { st.skin = r.skinStatus(); st.morph = r.morphStatus(); }
   if (status) st.adaptive = { samples: status.samples, minCount: status.minCount, maxCount: status.maxCount, rounds: status.rounds };
   console.log(JSON.stringify(st));

@@ -53,6 +53,8 @@ function Renderer(options) {
   this.sceneLoaded = false;
   this.alphaCutout = !!options.alphaCutout;             // loadModel of a .glb keeps albedo alpha and sets the MASK materials' cutoffs
   this.alphaLayers = options.alphaLayers || 0;          // ... with this maxLayers (0: the library's default)
+  this.alphaBlend = !!options.alphaBlend;               // loadModel of a .glb keeps albedo alpha and sets the BLEND materials' factors
+  this.alphaBlendSeed = options.alphaBlendSeed || 0;    // ... with this seed, and alphaLayers as their maxLayers
   this.cameraBytes = new ArrayBuffer(pack.CAMERA_SIZE);
   this.setupCamera();
   this.addon.resize(this.ctx, this.width, this.height);
@@ -86,13 +88,14 @@ Renderer.prototype.addOnUpdate = function (callback) { this.onUpdateTasks.push(c
 Renderer.prototype.loadModel = function (model, atlas) {
   var self = this;
   return new Promise(function (resolve) {
-    var blobs, cutoff = null, groups = null, skin = null, morph = null;
+    var blobs, cutoff = null, blend = null, groups = null, skin = null, morph = null;
     self.gltf = null; self.skins = null; self.morphs = null;
     if (typeof model === 'string' && /\.glb$/i.test(model)) {
       var gltf = require('./gltf').loadGLB(model);
-      var prepared = require('./scene_prep').prepareScene(gltf, { alphaCutout: self.alphaCutout });
+      var prepared = require('./scene_prep').prepareScene(gltf, { alphaCutout: self.alphaCutout, alphaBlend: self.alphaBlend });
       blobs = prepared.blobs; atlas = atlas || prepared.atlas; self.sceneInfo = prepared;
       cutoff = prepared.alphaCutoff || null;
+      blend = prepared.alphaBlend || null;
       groups = prepared.triangleGroups || null;
       if (prepared.skinTriangles) { skin = prepared; self.gltf = gltf; }
       if (prepared.morphTriangles) { morph = prepared; self.gltf = gltf; }
@@ -105,6 +108,7 @@ Renderer.prototype.loadModel = function (model, atlas) {
       if (model.skinTriangles) { skin = model; self.gltf = model.gltf || null; }   // ... and its skinned triangles
       if (model.morphTriangles) { morph = model; self.gltf = model.gltf || null; } // ... and its morphed ones
       if (self.alphaCutout) cutoff = model.alphaCutoff || null;         // what prepareScene({alphaCutout: true}) returned
+      if (self.alphaBlend) blend = model.alphaBlend || null;            // ... and prepareScene({alphaBlend: true})
     } else {
       blobs = pack.packScene(model);
     }
@@ -114,6 +118,7 @@ Renderer.prototype.loadModel = function (model, atlas) {
     else self.addon.uploadAtlas(self.ctx, null, 0, 0, 0);
     // (the upload removed any table: it belonged to the old scene's materials)
     if (cutoff) self.addon.setAlphaCutoff(self.ctx, cutoff, self.alphaLayers);
+    if (blend) self.addon.setAlphaBlend(self.ctx, blend, self.alphaLayers, self.alphaBlendSeed);
     // ... and any group table: a .glb's triangles are tagged with the node they came from (transformGroups moves a node by matrix)
     if (groups && groups.length) self.addon.setTriangleGroups(self.ctx, groups);
     // ... and any skin: a .glb's skinned primitives are listed with their joints and weights (poseSkin / poseAt pose them)
@@ -441,6 +446,23 @@ Renderer.prototype.setAlphaCutoff = function (cutoff, opts) {
 /** { present, materials, cutout, maxLayers, pathPasses, pathExhausted, shadowPasses, shadowExhausted } (include/ptmi.h
  *  ptmi_alpha_status): the table in place and what its loops counted since resetStats; synchronises */
 Renderer.prototype.alphaStatus = function () { return this.addon.alphaStatus(this.ctx); };
+
+/**
+ * Alpha blending as hashed stochastic transparency (include/ptmi.h ptmi_set_alpha_blend): a Float32Array with one entry per material
+ * of the loaded scene, < 0 not blended, f in [0, 1]: a hit is absent where f * the albedo map's alpha is at or below a hash of the ray
+ * (glTF alphaMode BLEND, f = baseColorFactor[3]), or null to remove the table. opts: { maxLayers (absent hits one ray may pass per
+ * segment, 1 .. 32; 0 / absent: the default, 4), seed (the hash's last word; absent: 0) }. new Renderer({ alphaBlend: true }) does this
+ * on loadModel of a .glb from its materials. loadModel removes the table. Accumulation restarts.
+ */
+Renderer.prototype.setAlphaBlend = function (factor, opts) {
+  if (factor && !(factor instanceof Float32Array)) throw new TypeError('setAlphaBlend: factor must be a Float32Array or null');
+  if (factor && !this.sceneLoaded) throw new Error('setAlphaBlend: needs a loaded scene (loadModel)');
+  this.addon.setAlphaBlend(this.ctx, factor || null, (opts && opts.maxLayers) || 0, (opts && opts.seed) || 0);
+  this.frameIndex = 0;
+};
+/** { present, materials, blend, maxLayers, seed, pathTests, pathPasses, shadowTests, shadowPasses } (include/ptmi.h
+ *  ptmi_alpha_blend_status): the table in place and what the loops counted for it since resetStats; synchronises */
+Renderer.prototype.alphaBlendStatus = function () { return this.addon.alphaBlendStatus(this.ctx); };
 
 /** why ptmi_upload_medium_density would refuse rho over dims on medium m with sigmaT times scale (include/ptmi.h), or null */
 function refusal(rho, dims, m, scale) {

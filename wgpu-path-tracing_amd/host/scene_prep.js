@@ -126,7 +126,7 @@ function processNode(gltf, node, allTriangles, allMaterials, allLights, world, a
 }
 
 /** glTF's alpha rule for one material as a cutoff of the alpha table (include/ptmi.h ptmi_set_alpha_cutoff): alphaMode "MASK" cuts
- *  at alphaCutoff (default 0.5); "OPAQUE", "BLEND" (a limit: it stays opaque) and a primitive without a material are 0 */
+ *  at alphaCutoff (default 0.5); "OPAQUE", "BLEND" (opaque under this table: alphaBlendOf) and a primitive without a material are 0 */
 function alphaCutoffOf(material) {
   if (!material || material.alphaMode !== 'MASK') return 0;
   return material.alphaCutoff === undefined || material.alphaCutoff === null ? 0.5 : material.alphaCutoff;
@@ -248,10 +248,20 @@ function skinPose(prepared, nodeWorldMatrices) {
   return out;
 }
 
+/** glTF's alpha rule for one material as an entry of the blend table (include/ptmi.h ptmi_set_alpha_blend): alphaMode "BLEND" is
+ *  blended with factor baseColorFactor[3] (default 1); every other mode and a primitive without a material are -1, not blended */
+function alphaBlendOf(material) {
+  if (!material || material.alphaMode !== 'BLEND') return -1;
+  var f = (material.pbrMetallicRoughness || {}).baseColorFactor;
+  return f && f[3] !== undefined && f[3] !== null ? f[3] : 1;
+}
+
 /** loader.ts:20-40 + gpu.ts:67-150 -> { blobs, atlas, counts, bvhDepth, triangleGroups, groupNames }: triangleGroups holds, per
  *  triangle in the uploaded (reordered) order, the index of the glTF node it came from (Renderer.setTriangleGroups), groupNames
  *  the nodes' names by that index (opts.triangleGroups === false: neither). opts.alphaCutout: the atlas keeps the alpha of albedo maps
  *  and the result carries alphaCutoff, a Float32Array with one cutoff per packed material (else: neither, and every byte as without).
+ *  opts.alphaBlend: the atlas keeps that alpha too, and the result carries alphaBlend, a Float32Array with one blend entry per packed
+ *  material (alphaBlendOf), or null when no material is BLEND; alphaCutout alone leaves BLEND materials opaque.
  *  A file with skinned primitives (a node with `skin`, JOINTS_0 and WEIGHTS_0) also returns skinTriangles, skinCorners (skinList),
  *  skinJoints (the joints of all skin instances together) and skins: per skinned node { node, skin, joints (node indices),
  *  inverseBind, meshWorldInverse, jointBase } (opts.skins === false, or a file without skins: none of them, and every blob the
@@ -259,9 +269,9 @@ function skinPose(prepared, nodeWorldMatrices) {
  *  targets of all mesh instances together) and morphs: per morphed node { node, targetBase, nTargets, weights (its defaults) }
  *  (opts.morphs === false, or a file without targets: none of them) */
 function prepareScene(gltf, opts) {
-  var alphaCutout = !!(opts && opts.alphaCutout);
-  var packed = require('./atlas').packing(gltf, { keepAlpha: alphaCutout });
-  var allTriangles = [], allMaterials = [], allLights = [], allCutoffs = [];
+  var alphaCutout = !!(opts && opts.alphaCutout), alphaBlend = !!(opts && opts.alphaBlend);
+  var packed = require('./atlas').packing(gltf, { keepAlpha: alphaCutout || alphaBlend });
+  var allTriangles = [], allMaterials = [], allLights = [], allCutoffs = [], allBlends = [];
   var parent = new Map();
   gltf.nodes.forEach(function (n) { (n.children || []).forEach(function (c) { parent.set(c, n); }); });
   var world = new Map();
@@ -291,6 +301,7 @@ function prepareScene(gltf, opts) {
       morphs[nodeIndex]);
     // one material per primitive, in the order processNode packs them
     if (alphaCutout && node.mesh) node.mesh.primitives.forEach(function (prim) { allCutoffs.push(alphaCutoffOf(prim.material)); });
+    if (alphaBlend && node.mesh) node.mesh.primitives.forEach(function (prim) { allBlends.push(alphaBlendOf(prim.material)); });
   });
 
   var triangles = pack.packTriangles(allTriangles);             // sorted in place by the BVH build
@@ -310,6 +321,7 @@ function prepareScene(gltf, opts) {
   return {
     blobs: { triangles: triangles, materials: materials, bvhNodes: bvh.nodes, lights: lights },
     alphaCutoff: alphaCutout ? new Float32Array(allCutoffs) : undefined,
+    alphaBlend: alphaBlend ? (allBlends.some(function (f) { return f >= 0; }) ? new Float32Array(allBlends) : null) : undefined,
     triangleGroups: triangleGroups,
     groupNames: grouped ? gltf.nodes.map(function (n, i) { return n.name || 'node' + i; }) : undefined,
     skinTriangles: skin ? skin.triangles : undefined, skinCorners: skin ? skin.corners : undefined,
@@ -324,4 +336,5 @@ function prepareScene(gltf, opts) {
   };
 }
 
-module.exports = { prepareScene: prepareScene, skinPose: skinPose, morphPose: morphPose, extractNodeMatrix: extractNodeMatrix, buildMaterial: buildMaterial, alphaCutoffOf: alphaCutoffOf };
+module.exports = { prepareScene: prepareScene, skinPose: skinPose, morphPose: morphPose, extractNodeMatrix: extractNodeMatrix, buildMaterial: buildMaterial, alphaCutoffOf: alphaCutoffOf,
+  alphaBlendOf: alphaBlendOf };

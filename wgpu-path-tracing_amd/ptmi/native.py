@@ -49,6 +49,7 @@ EXPORTS = [
     "ptmi_rebuild_tree", "ptmi_rebuild_status", "ptmi_multi_rebuild_tree", "ptmi_multi_rebuild_status",
     "ptmi_set_alpha_cutoff", "ptmi_alpha_status", "ptmi_multi_set_alpha_cutoff", "ptmi_multi_alpha_status",
     "ptmi_debug_alpha_intersect", "ptmi_debug_alpha_occluded",
+    "ptmi_set_alpha_blend", "ptmi_alpha_blend_status", "ptmi_multi_set_alpha_blend", "ptmi_multi_alpha_blend_status",
     "ptmi_set_triangle_groups", "ptmi_transform_groups", "ptmi_transform_status", "ptmi_normal_matrix", "ptmi_debug_read_triangles",
     "ptmi_multi_set_triangle_groups", "ptmi_multi_transform_groups", "ptmi_multi_transform_status",
     "ptmi_set_skin", "ptmi_pose_skin", "ptmi_skin_status", "ptmi_multi_set_skin", "ptmi_multi_pose_skin", "ptmi_multi_skin_status",
@@ -255,6 +256,22 @@ class AlphaStatus(ctypes.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class AlphaBlendParams(ctypes.Structure):
+    """ptmi_alpha_blend_params; max_layers 0 picks the default (include/ptmi.h)"""
+    _fields_ = [("max_layers", ctypes.c_uint32), ("seed", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
+
+
+class AlphaBlendStatus(ctypes.Structure):
+    """struct ptmi_alpha_blend_status: the blend table in place and what the loops counted for it since reset_stats (include/ptmi.h)"""
+    _fields_ = [("present", ctypes.c_uint32), ("n_materials", ctypes.c_uint32), ("n_blend", ctypes.c_uint32),
+                ("max_layers", ctypes.c_uint32), ("seed", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("path_tests", ctypes.c_uint64), ("path_passes", ctypes.c_uint64),
+                ("shadow_tests", ctypes.c_uint64), ("shadow_passes", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
 class Stats(ctypes.Structure):
     _fields_ = [("paths", ctypes.c_uint64), ("segments", ctypes.c_uint64), ("shadow_rays", ctypes.c_uint64),
                 ("dispatches", ctypes.c_uint64), ("frames", ctypes.c_uint64),
@@ -299,6 +316,7 @@ _SHARED = {
     "scene_update_status": [ctypes.c_void_p],
     "rebuild_tree": [ctypes.c_void_p], "rebuild_status": [ctypes.c_void_p],
     "set_alpha_cutoff": [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p], "alpha_status": [ctypes.c_void_p],
+    "set_alpha_blend": [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p], "alpha_blend_status": [ctypes.c_void_p],
     "set_triangle_groups": [ctypes.c_void_p, ctypes.c_uint32], "transform_groups": [ctypes.c_void_p, ctypes.c_uint32],
     "transform_status": [ctypes.c_void_p],
     "set_skin": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32], "pose_skin": [ctypes.c_void_p, ctypes.c_uint32],
@@ -721,6 +739,23 @@ class _Handle:
         self._ck(self._c.alpha_status(self.h, ctypes.byref(st)))
         return st
 
+    # -- alpha blending (include/ptmi.h ptmi_set_alpha_blend) ----------------------------------------------------------
+    def set_alpha_blend(self, factor, max_layers=0, seed=0, reserved=(0, 0), n_materials=None):
+        """The per-material blend table of the loaded scene: one float per uploaded material, < 0 = not blended, f in [0, 1] = a
+        hit is absent where f * the albedo map's alpha <= the ray's own hash. factor None removes the table. max_layers 0 picks the
+        default; n_materials overrides the array's length (for tests)."""
+        prm = AlphaBlendParams(max_layers, seed, (ctypes.c_uint32 * 2)(*reserved))
+        if factor is None:
+            self._ck(self._c.set_alpha_blend(self.h, None, 0, ctypes.byref(prm)))
+            return
+        a = np.ascontiguousarray(factor, np.float32).reshape(-1)
+        self._ck(self._c.set_alpha_blend(self.h, _p(a), len(a) if n_materials is None else n_materials, ctypes.byref(prm)))
+
+    def alpha_blend_status(self):
+        st = AlphaBlendStatus()
+        self._ck(self._c.alpha_blend_status(self.h, ctypes.byref(st)))
+        return st
+
     def upload_environment(self, texels, intensity=0.0, rotation=0.0, sample=0, reserved=(0, 0, 0, 0, 0)):
         """The environment map behind every miss (include/ptmi.h ptmi_upload_environment): (H, W, 4) float16 / float32 texels,
         equirectangular, row 0 at the +Y pole. texels None removes it."""
@@ -1084,7 +1119,7 @@ class Context(_Handle):
         return occ
 
     def debug_alpha_intersect(self, o, d):
-        """debug_intersect through the path loop of the active cutoff table: (t along the given ray, triangle, holes passed)"""
+        """debug_intersect through the path loop of the active cutoff or blend table: (t along the given ray, triangle, holes passed)"""
         o, d = np.ascontiguousarray(o, np.float32), np.ascontiguousarray(d, np.float32)
         n = len(o)
         t, tri, layers = np.zeros(n, np.float32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
