@@ -188,6 +188,40 @@ int ptmi_get_options(const ptmi_ctx *ctx, ptmi_options *opt);
  * frame index incremented by the caller (renderer.ts:453). Asynchronous. */
 int ptmi_dispatch(ptmi_ctx *ctx, const ptmi_camera *camera, uint32_t n_frames);
 int ptmi_synchronize(ptmi_ctx *ctx);
+
+/* ---- camera projections: orthographic and equirectangular beside the pinhole ----------------
+ * The camera record carries its projection in the two words at offset 88, which the reference pads with (ptmi_layout.h: PTMI_PROJ_*,
+ * ptmi_camera_set_projection). They are honoured only while the context's switch is on. While it is off, the default, the words are
+ * not read, every launch is the kernel it was and every result keeps its bits: a caller that leaves garbage in the padding is
+ * unaffected. While it is on, every entry that takes a camera - ptmi_dispatch, ptmi_dispatch_adaptive, ptmi_reproject (both cameras),
+ * ptmi_debug_raygen, ptmi_debug_center_rays and their ptmi_multi counterparts - reads word 0:
+ *   PTMI_PROJ_PERSPECTIVE   the kernels of the switch off; word 1 is not read.
+ *   PTMI_PROJ_ORTHOGRAPHIC  word 1 = the bits of ymag, the half-height in world units; not finite or not > 0: PTMI_E_INVALID.
+ *   PTMI_PROJ_EQUIRECT      word 1 is not read; fov and aspect are not read.
+ *   anything else           PTMI_E_INVALID.
+ * A rejected camera means nothing was enqueued or written.
+ * The rays, operation by operation in the kernels' float32 (pt_math.h: scale3 / add3 are per-component * and +, normalize3 and
+ * sincos are the kernels' own, ptmi_debug_math op 5 / 6), with uvx = (px / width) * 2 - 1, uvy = (py / height) * 2 - 1 at the
+ * point (px, py) = (x + jitter x, y + jitter y) of pixel (x, y), as for the pinhole:
+ *   orthographic   a = ((right * uvx) * ymag) * aspect,  b = (up * uvy) * ymag,  origin0 = (position + a) + b,  dir = normalize(forward)
+ *                  (the pinhole's expression with ymag where tan(fov / 2) stands, applied to the origin)
+ *   equirect       lon = uvx * pi, lat = uvy * (pi * 0.5f), (so, co) = sincos(lon), (sl, cl) = sincos(lat),
+ *                  dir = normalize((forward * (cl * co) + right * (cl * so)) + up * sl),  origin0 = position
+ *                  (forward at the image centre, right at a quarter of the width to its right, up at the top row)
+ * The lens (aperture > 0) is the pinhole's with origin0 where position stands: the focal point is origin0 + dir * focus_distance,
+ * the disc lies in right / up, and the same two draws are taken. The centre rays of ptmi_reproject use the same formulas at
+ * (x + 0.5, y + 0.5) without the lens. Both projections expect forward, right, up orthonormal to within rounding; this is not
+ * validated. Consequence: pixel (x, y, frame) of either projection is pixel (x, y, frame) of a pinhole camera with position = origin0,
+ * forward = the direction before normalize, fov = 0 and everything else equal - the same seed, draws, lens and path, bit for bit
+ * (where no component of that forward is a zero: the pinhole adds +0 to it).
+ * ptmi_reproject: an orthographic `from` projects sx = dot(v, right) / (ymag * aspect), sy = dot(v, up) / ymag where zf > 0, and its
+ * depth is dist = zf - the t along a ray that starts on the camera plane - in the tolerance test and the motion plane's z. An
+ * orthographic `to` needs only its centre rays, so any pairing of pinhole and orthographic works. An equirectangular `from` or `to`
+ * is PTMI_E_INVALID with nothing written: its inverse needs atan2 / asin, which are outside the arithmetic contract.
+ * on: 0 or 1 (else PTMI_E_INVALID). Synchronises. Nothing is allocated either way. The ABI version stays 4: the record's size and
+ * members are unchanged. */
+int ptmi_set_projections(ptmi_ctx *ctx, uint32_t on);
+int ptmi_get_projections(const ptmi_ctx *ctx, uint32_t *on);
 /* Back-pressure for a caller that enqueues dispatches from a loop without reading results — a preview loop; the reference paces
  * itself on requestAnimationFrame (renderer.ts:456-473). Blocks until at most max_in_flight of this context's dispatches have
  * not yet finished on the device and reports how many still are (in_flight may be NULL). max_in_flight = 0xFFFFFFFF only polls.
@@ -338,7 +372,8 @@ int ptmi_adaptive_status(ptmi_ctx *ctx, struct ptmi_adaptive_status *out);
  *      ALBEDO and ID into context-owned history planes (made by the first call since ptmi_resize, all or nothing). The live planes
  *      are then rewritten in place.
  *   2. the centre ray of every pixel under `to`: the camera ray of ptmi_dispatch with the jitter replaced by (0.5, 0.5), no lens
- *      sample and no RNG (aperture is ignored): origin = to.position (ptmi_debug_center_rays returns them).
+ *      sample and no RNG (aperture is ignored): origin = to.position, or the pixel's point of the camera plane of an orthographic
+ *      `to` (ptmi_set_projections) (ptmi_debug_center_rays returns them).
  *   3. their closest hits (t, tri), by the traversal kernel of ptmi_dispatch, as ptmi_debug_intersect runs it.
  *   4. per pixel, all in float32, left to right, no FMA, with the correctly rounded / and sqrt, and dot(a, b) = a.x*b.x + a.y*b.y + a.z*b.z:
  *      MISS (tri == 0xFFFFFFFF): every live plane of the pixel becomes zero, the ids 0xFFFFFFFF twice, the count 0. Else
@@ -370,8 +405,9 @@ typedef struct ptmi_reproject_params {
 struct ptmi_reproject_status { uint64_t carried, disoccluded, missed, samples; };   /* 32 bytes */
 /* Asynchronous on the context's stream. params NULL: the defaults. PTMI_E_STATE: no scene, no output buffer, the NORMAL or the
  * moments plane off, match_ids = 2 with the ID plane off. PTMI_E_INVALID: from or to NULL, a camera of another size than the
- * context's, depth_tolerance negative or not finite, max_history > 2^24, match_ids > 2, a non-zero reserved word. A failed call
- * writes nothing. */
+ * context's, depth_tolerance negative or not finite, max_history > 2^24, match_ids > 2, a non-zero reserved word; with
+ * ptmi_set_projections on, a camera whose projection words are rejected, or an equirectangular camera on either side (its inverse
+ * needs atan2 / asin, outside the arithmetic contract: left for later). A failed call writes nothing. */
 int ptmi_reproject(ptmi_ctx *ctx, const ptmi_camera *from, const ptmi_camera *to, const ptmi_reproject_params *params);
 int ptmi_reproject_status(ptmi_ctx *ctx, struct ptmi_reproject_status *out);    /* synchronises */
 
@@ -639,6 +675,10 @@ int ptmi_multi_set_aovs(ptmi_multi *m, uint32_t mask);
 int ptmi_multi_get_aovs(const ptmi_multi *m, uint32_t *mask);
 int ptmi_multi_set_moments(ptmi_multi *m, uint32_t on);
 int ptmi_multi_get_moments(const ptmi_multi *m, uint32_t *on);
+/* ptmi_set_projections on every device (checked once, before any device changes): ptmi_multi_dispatch and
+ * ptmi_multi_dispatch_adaptive then honour the camera's projection words, and reject a bad camera before any device enqueues. */
+int ptmi_multi_set_projections(ptmi_multi *m, uint32_t on);
+int ptmi_multi_get_projections(const ptmi_multi *m, uint32_t *on);
 /* Assembles the named planes in device 0's own planes, ordered after every device's work so far. Asynchronous, like ptmi_multi_gather.
  * planes: any combination of PTMI_AOV_*, PTMI_MULTI_PLANE_MOMENTS and PTMI_MULTI_PLANE_OUTPUT. An unknown bit: PTMI_E_INVALID; a bit
  * of a plane that is off: PTMI_E_STATE; 0 does nothing. ONE pass whatever the set: one pack kernel per device writes its rows of every
@@ -998,7 +1038,9 @@ int ptmi_reset_stats(ptmi_ctx *ctx);
 int ptmi_debug_raygen(ptmi_ctx *ctx, const ptmi_camera *camera, uint32_t n, const uint32_t *xs,
                       const uint32_t *ys, const uint32_t *frames, float *o3, float *d3, uint32_t *rng);
 /* the centre rays ptmi_reproject traces for `camera` (step 2 there), for the n = width*height pixels of the context's size, index
- * y*width+x. o3/d3: n*3 floats each, n_floats_each must be n*3 (else, or with a camera of another size: PTMI_E_INVALID). */
+ * y*width+x. o3/d3: n*3 floats each, n_floats_each must be n*3 (else, or with a camera of another size: PTMI_E_INVALID). The origin
+ * is per pixel: camera->position for the pinhole and the equirectangular projection, the pixel's point of the camera plane for an
+ * orthographic camera (ptmi_set_projections). */
 int ptmi_debug_center_rays(ptmi_ctx *ctx, const ptmi_camera *camera, float *o3, float *d3, size_t n_floats_each);
 /* extend kernel (pt.wgsl:248-296) on caller rays: t = -1 / tri = 0xFFFFFFFF on miss. Raw: an alpha cutoff table is not consulted. */
 int ptmi_debug_intersect(ptmi_ctx *ctx, uint32_t n, const float *o3, const float *d3,

@@ -17,6 +17,7 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #ifdef __cplusplus
 #define PTMI_STATIC_ASSERT(c, m) static_assert(c, m)
@@ -96,8 +97,26 @@ typedef struct ptmi_camera {
     uint32_t frame_index;           /* 76 */
     float aperture;                 /* 80 */
     float focus_distance;           /* 84 */
-    uint32_t _p3[2];                /* 88 */
+    uint32_t _p3[2];                /* 88  the projection words: padding in the reference, and here until ptmi_set_projections(1) */
 } ptmi_camera;
+
+/* The camera's projection (include/ptmi.h, ptmi_set_projections). The reference's uniform ends in two padding words; while the
+ * context's switch is on they say how the camera projects, and while it is off (the default) nothing reads them.
+ *   word 0 (offset 88): PTMI_PROJ_*
+ *   word 1 (offset 92): the bits of a float, the orthographic half-height in world units (glTF's ymag; the half-width is
+ *                       ymag * aspect). Read for PTMI_PROJ_ORTHOGRAPHIC only.
+ * The member names stay the reference's, so the words are reached through these helpers. */
+#define PTMI_PROJ_PERSPECTIVE  0u   /* the reference's pinhole: fov, aspect */
+#define PTMI_PROJ_ORTHOGRAPHIC 1u   /* parallel rays along forward from the plane through position: ymag, aspect */
+#define PTMI_PROJ_EQUIRECT     2u   /* 360 x 180 degrees about position: longitude along x, latitude along y; fov and aspect unread */
+#define PTMI_CAMERA_PROJECTION_OFFSET 88u
+#define PTMI_CAMERA_YMAG_OFFSET       92u
+static inline uint32_t ptmi_camera_projection(const ptmi_camera *c) { return c->_p3[0]; }
+static inline float ptmi_camera_ymag(const ptmi_camera *c) { float f; memcpy(&f, &c->_p3[1], sizeof f); return f; }
+static inline void ptmi_camera_set_projection(ptmi_camera *c, uint32_t kind, float ymag) {
+    c->_p3[0] = kind;
+    memcpy(&c->_p3[1], &ymag, sizeof ymag);
+}
 
 /* outputBuffer: array<vec3f> — 16 B per pixel, index y*W+x, row 0 = image
  * bottom (pt.wgsl:104, :753; renderer.ts:272-279). */
@@ -150,5 +169,7 @@ PTMI_STATIC_ASSERT(offsetof(ptmi_camera, height) == 72, "Camera.height");
 PTMI_STATIC_ASSERT(offsetof(ptmi_camera, frame_index) == 76, "Camera.frameIndex");
 PTMI_STATIC_ASSERT(offsetof(ptmi_camera, aperture) == 80, "Camera.aperture");
 PTMI_STATIC_ASSERT(offsetof(ptmi_camera, focus_distance) == 84, "Camera.focusDistance");
+PTMI_STATIC_ASSERT(offsetof(ptmi_camera, _p3) == PTMI_CAMERA_PROJECTION_OFFSET, "Camera: the projection word");
+PTMI_STATIC_ASSERT(offsetof(ptmi_camera, _p3) + 4 == PTMI_CAMERA_YMAG_OFFSET, "Camera: the ymag word");
 
 #endif /* PTMI_LAYOUT_H */

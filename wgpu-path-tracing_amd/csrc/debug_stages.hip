@@ -43,15 +43,17 @@ extern "C" {
 int ptmi_debug_raygen(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n, const uint32_t *xs, const uint32_t *ys,
                       const uint32_t *frames, float *o3, float *d3, uint32_t *rng) {
     if (!c || !cam || !xs || !ys || !frames || !o3 || !d3) return PTMI_E_INVALID;
-    if (n == 0) return PTMI_OK;
-    int rc = stage_begin(c, n);
+    uint32_t proj;
+    int rc = pt_check_camera(c, cam, &proj, c->err);
     if (rc) return rc;
+    if (n == 0) return PTMI_OK;
+    if ((rc = stage_begin(c, n))) return rc;
     Lane &ln = c->lane;
     uint32_t *dx = ln.queue[0], *dy = ln.queue[1], *df = reinterpret_cast<uint32_t *>(ln.hits);
     HIP_TRY(c, hipMemcpyAsync(dx, xs, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(dy, ys, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(df, frames, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    pt_launch_raygen_list(c->stream, *cam, n, dx, dy, df, ln.paths);
+    pt_launch_raygen_list(c->stream, *cam, proj, n, dx, dy, df, ln.paths);
     std::vector<float4> o(n), d(n);
     HIP_TRY(c, hipMemcpyAsync(o.data(), ln.paths.O, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(d.data(), ln.paths.D, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
@@ -68,11 +70,13 @@ int ptmi_debug_center_rays(ptmi_ctx *c, const ptmi_camera *cam, float *o3, float
         return fail(c, PTMI_E_INVALID, "camera says %ux%u but the output buffer is %ux%u", cam->width, cam->height, c->W, c->H);
     const size_t n = (size_t)c->W * c->H;
     if (n_floats_each != n * 3) return fail(c, PTMI_E_INVALID, "expected %zu floats each, got %zu", n * 3, n_floats_each);
-    int rc = stage_begin(c, n);
+    uint32_t proj;
+    int rc = pt_check_camera(c, cam, &proj, c->err);
     if (rc) return rc;
+    if ((rc = stage_begin(c, n))) return rc;
     Lane &ln = c->lane;
     const DevBand whole{c->W, c->H, 0u, c->H, 1u, 1u, 0u, c->H};
-    pt_launch_center_rays(c->stream, c->n_cu * 8, *cam, whole, ln.paths, &c->d_control[kCwQueue]);
+    pt_launch_center_rays(c->stream, c->n_cu * 8, *cam, proj, whole, ln.paths, &c->d_control[kCwQueue]);
     std::vector<float4> o(n), d(n);
     HIP_TRY(c, hipMemcpyAsync(o.data(), ln.paths.O, n * 16, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(d.data(), ln.paths.D, n * 16, hipMemcpyDeviceToHost, c->stream));

@@ -114,6 +114,8 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
     if (!cam) return fail(c, PTMI_E_INVALID, "camera is NULL");
     if (cam->width != c->W || cam->height != c->H)
         return fail(c, PTMI_E_INVALID, "camera says %ux%u but the output buffer is %ux%u", cam->width, cam->height, c->W, c->H);
+    uint32_t proj;
+    if ((rc = pt_check_camera(c, cam, &proj, c->err))) return rc;
     if (n_frames == 0 || (ap && rounds == 0)) return PTMI_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     if (ap && (rc = make_planes(c, group_set(kByAdaptive), (size_t)c->W * c->H, c->plane))) return rc;
@@ -202,7 +204,7 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         auto batch = [&](uint32_t frame0, uint32_t fb) -> int {
             const DevPixels px = ap ? DevPixels{band, 0u, c->ad.list, &c->d_control[kCwAdActive], mom, &ct[kCtAdTraced]}
                                     : DevPixels{band, frame0, nullptr, nullptr, nullptr, nullptr};
-            { Timed t(c, kRaygen, t3, ms); pt_launch_raygen(ms, blocks, *cam, px, fb, bp, &qlen[0]); }
+            { Timed t(c, kRaygen, t3, ms); pt_launch_raygen(ms, blocks, *cam, proj, px, fb, bp, &qlen[0]); }
             int cur = 0;
             for (uint32_t b = 0; b < maxb; b++) {
                 const bool tail = b > rb;                                   // the state is in the tail arrays
@@ -298,6 +300,8 @@ int pt_adaptive_check(ptmi_ctx *c, const ptmi_camera *cam, const ptmi_adaptive_p
     if (!cam) return fail(c, PTMI_E_INVALID, "camera is NULL");
     if (cam->width != c->W || cam->height != c->H)
         return fail(c, PTMI_E_INVALID, "camera says %ux%u but the output buffer is %ux%u", cam->width, cam->height, c->W, c->H);
+    uint32_t proj;
+    if ((rc = pt_check_camera(c, cam, &proj, c->err))) return rc;
     *out = ap;
     return PTMI_OK;
 }
@@ -368,6 +372,10 @@ int ptmi_reproject(ptmi_ctx *c, const ptmi_camera *from, const ptmi_camera *to, 
     for (const ptmi_camera *cam : {from, to})
         if (cam->width != c->W || cam->height != c->H)
             return fail(c, PTMI_E_INVALID, "a camera says %ux%u but the output buffer is %ux%u", cam->width, cam->height, c->W, c->H);
+    uint32_t from_proj, to_proj;
+    if ((rc = pt_check_camera(c, from, &from_proj, c->err)) || (rc = pt_check_camera(c, to, &to_proj, c->err))) return rc;
+    if (from_proj == PTMI_PROJ_EQUIRECT || to_proj == PTMI_PROJ_EQUIRECT)
+        return fail(c, PTMI_E_INVALID, "reprojection %s an equirectangular camera is not supported", from_proj == PTMI_PROJ_EQUIRECT ? "from" : "to");
     const ptmi_reproject_params zero = {};
     const ptmi_reproject_params &q = params ? *params : zero;
     if (!std::isfinite(q.depth_tolerance) || q.depth_tolerance < 0.0f)
@@ -403,12 +411,12 @@ int ptmi_reproject(ptmi_ctx *c, const ptmi_camera *from, const ptmi_camera *to, 
     for (const auto &cp : copies)
         if (cp.on) HIP_TRY(c, hipMemcpyAsync(c->plane[cp.to], cp.from, plane_bytes(cp.to, npix), hipMemcpyDeviceToDevice, s));
     const int blocks = c->n_cu * 8;
-    pt_launch_center_rays(s, blocks, *to, band, ln.paths, &c->d_control[kCwQueue]);
+    pt_launch_center_rays(s, blocks, *to, to_proj, band, ln.paths, &c->d_control[kCwQueue]);
     launch_extend(c, s, cfg, ln.paths, nullptr, &c->d_control[kCwQueue], ln.hits);
     // the first surface that is there, as the first-hit planes recorded it: without this every pixel seen through a hole is disoccluded
     if (alpha_active(c)) alpha_resolve_paths(c, s, cfg, ln.paths, nullptr, &c->d_control[kCwQueue], ln.hits, nullptr);
     ReprojectArgs a{};
-    a.from = *from; a.band = band;
+    a.from = *from; a.from_proj = from_proj; a.band = band;
     a.max_history = q.max_history ? q.max_history : 32u;
     a.depth_tolerance = q.depth_tolerance > 0.0f ? q.depth_tolerance : 0.02f;
     a.match_ids = q.match_ids == 2u || (q.match_ids == 0u && have_ids) ? 1u : 0u;

@@ -10,28 +10,48 @@ namespace {
 
 constexpr int BLOCK = 256;
 
-// pt.wgsl:721-733: the pinhole direction through the point (px, py) of the image plane, in pixels
-PT_DEV v3 camera_dir(const ptmi_camera &cam, float px, float py) {
+// The ray through the point (px, py) of the image plane, in pixels, before the lens: its direction, and its origin in org0. PROJ is the
+// camera's projection (ptmi_layout.h PTMI_PROJ_*; include/ptmi.h ptmi_set_projections states each expression):
+//   PERSPECTIVE   pt.wgsl:721-733, the pinhole: the code of every launch while the context's switch is off
+//   ORTHOGRAPHIC  the pinhole's expression with ymag where th stands, applied to the origin; every ray runs along forward
+//   EQUIRECT      longitude uvx * pi about up, latitude uvy * pi / 2 towards up; fov and aspect are not read
+template <int PROJ>
+PT_DEV v3 camera_dir(const ptmi_camera &cam, float px, float py, v3 &org0) {
     float uvx = (px / (float)cam.width) * 2.0f - 1.0f;
     float uvy = (py / (float)cam.height) * 2.0f - 1.0f;
-    float th = tan1(cam.fov * 0.5f);
     v3 fw = mk3(cam.forward[0], cam.forward[1], cam.forward[2]);
     v3 rt = mk3(cam.right[0], cam.right[1], cam.right[2]);
     v3 up = mk3(cam.up[0], cam.up[1], cam.up[2]);
-    v3 a = scale3(scale3(scale3(rt, uvx), th), cam.aspect);
-    v3 b = scale3(scale3(up, uvy), th);
-    return normalize3(add3(add3(fw, a), b));
+    org0 = mk3(cam.position[0], cam.position[1], cam.position[2]);
+    if constexpr (PROJ == (int)PTMI_PROJ_ORTHOGRAPHIC) {
+        const float ymag = __uint_as_float(cam._p3[1]);
+        v3 a = scale3(scale3(scale3(rt, uvx), ymag), cam.aspect);
+        v3 b = scale3(scale3(up, uvy), ymag);
+        org0 = add3(add3(org0, a), b);
+        return normalize3(fw);
+    } else if constexpr (PROJ == (int)PTMI_PROJ_EQUIRECT) {
+        const float lon = uvx * PT_PI, lat = uvy * (PT_PI * 0.5f);
+        float so, co, sl, cl;
+        sincos1(lon, so, co); sincos1(lat, sl, cl);
+        return normalize3(add3(add3(scale3(fw, cl * co), scale3(rt, cl * so)), scale3(up, sl)));
+    } else {
+        float th = tan1(cam.fov * 0.5f);
+        v3 a = scale3(scale3(scale3(rt, uvx), th), cam.aspect);
+        v3 b = scale3(scale3(up, uvy), th);
+        return normalize3(add3(add3(fw, a), b));
+    }
 }
 
-// pt.wgsl:719-750
+// pt.wgsl:719-750; the lens takes the projection's origin where the pinhole has its position
+template <int PROJ>
 PT_DEV void camera_ray(const ptmi_camera &cam, uint32_t x, uint32_t y, uint32_t frame, v3 &org, v3 &dir,
                        uint32_t &rng) {
     rng = rng_seed(x, y, frame);
     float jx = rng_f(rng), jy = rng_f(rng);
     v3 rt = mk3(cam.right[0], cam.right[1], cam.right[2]);
     v3 up = mk3(cam.up[0], cam.up[1], cam.up[2]);
-    v3 pos = mk3(cam.position[0], cam.position[1], cam.position[2]);
-    dir = camera_dir(cam, (float)x + jx, (float)y + jy);
+    v3 pos;
+    dir = camera_dir<PROJ>(cam, (float)x + jx, (float)y + jy, pos);
     org = pos;
     if (cam.aperture > 0.0f) {
         v3 focal = madd3(dir, cam.focus_distance, pos);
@@ -69,7 +89,7 @@ struct ListedPixels {                   // the *n_active pixels of the list, eac
     PT_DEV uint32_t first_frame(size_t oi) const { return (uint32_t)mom[oi].z; }
 };
 
-template <class Pixels>
+template <int PROJ, class Pixels>
 PT_DEV void raygen(const ptmi_camera &cam, const Pixels &px, uint32_t n_frames, DevPaths P, uint32_t *__restrict__ count_out) {
     const DevBand &band = px.band;
     const uint32_t n = px.entries();
@@ -79,13 +99,20 @@ PT_DEV void raygen(const ptmi_camera &cam, const Pixels &px, uint32_t n_frames, 
         const uint32_t k = p / n, pix = px.pixel(p - k * n);
         const uint32_t y = band.row_of(pix / band.width), x = pix % band.width;
         v3 o, d; uint32_t rng;
-        camera_ray(cam, x, y, px.first_frame((size_t)y * band.width + x) + k, o, d, rng);
+        camera_ray<PROJ>(cam, x, y, px.first_frame((size_t)y * band.width + x) + k, o, d, rng);
         init_path(P, p, o, d, rng);
     }
 }
+// The kernels that take a camera come once per projection. The pinhole's keep their names and their code; the others are the
+// instantiations of the templates beside them, launched only for a camera that names their projection (ptmi_set_projections).
 __global__ __launch_bounds__(BLOCK) void k_raygen(ptmi_camera cam, DevBand band, uint32_t frame0, uint32_t n_frames,
                                                   DevPaths P, uint32_t *__restrict__ count_out) {
-    raygen(cam, DensePixels{band, frame0}, n_frames, P, count_out);
+    raygen<PTMI_PROJ_PERSPECTIVE>(cam, DensePixels{band, frame0}, n_frames, P, count_out);
+}
+template <int PROJ>
+__global__ __launch_bounds__(BLOCK) void k_raygen_proj(ptmi_camera cam, DevBand band, uint32_t frame0, uint32_t n_frames,
+                                                       DevPaths P, uint32_t *__restrict__ count_out) {
+    raygen<PROJ>(cam, DensePixels{band, frame0}, n_frames, P, count_out);
 }
 
 // ptmi_reproject's centre rays: camera_ray with the jitter replaced by (0.5, 0.5), no lens sample, no RNG. Path p is the band-local pixel p.
@@ -94,19 +121,42 @@ __global__ __launch_bounds__(BLOCK) void k_center_rays(ptmi_camera cam, DevBand 
     if (blockIdx.x == 0 && threadIdx.x == 0) *count_out = total;
     for (uint32_t p = blockIdx.x * BLOCK + threadIdx.x; p < total; p += gridDim.x * BLOCK) {
         const uint32_t y = band.row_of(p / band.width), x = p % band.width;
-        const v3 d = camera_dir(cam, (float)x + 0.5f, (float)y + 0.5f);
+        v3 o;
+        const v3 d = camera_dir<PTMI_PROJ_PERSPECTIVE>(cam, (float)x + 0.5f, (float)y + 0.5f, o);
         P.O[p] = make_float4(cam.position[0], cam.position[1], cam.position[2], 0.0f);
         P.D[p] = make_float4(d.x, d.y, d.z, 0.0f);
     }
 }
+// ... and those of the other projections, whose origin is the projection's own
+template <int PROJ>
+__global__ __launch_bounds__(BLOCK) void k_center_rays_proj(ptmi_camera cam, DevBand band, DevPaths P, uint32_t *__restrict__ count_out) {
+    const uint32_t total = band.rows * band.width;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *count_out = total;
+    for (uint32_t p = blockIdx.x * BLOCK + threadIdx.x; p < total; p += gridDim.x * BLOCK) {
+        const uint32_t y = band.row_of(p / band.width), x = p % band.width;
+        v3 o;
+        const v3 d = camera_dir<PROJ>(cam, (float)x + 0.5f, (float)y + 0.5f, o);
+        P.O[p] = make_float4(o.x, o.y, o.z, 0.0f);
+        P.D[p] = make_float4(d.x, d.y, d.z, 0.0f);
+    }
+}
 
-__global__ __launch_bounds__(BLOCK) void k_raygen_list(ptmi_camera cam, uint32_t n, const uint32_t *xs,
-                                                       const uint32_t *ys, const uint32_t *frames, DevPaths P) {
+template <int PROJ>
+PT_DEV void raygen_list(const ptmi_camera &cam, uint32_t n, const uint32_t *xs, const uint32_t *ys, const uint32_t *frames, DevPaths P) {
     uint32_t p = blockIdx.x * BLOCK + threadIdx.x;
     if (p >= n) return;
     v3 o, d; uint32_t rng;
-    camera_ray(cam, xs[p], ys[p], frames[p], o, d, rng);
+    camera_ray<PROJ>(cam, xs[p], ys[p], frames[p], o, d, rng);
     init_path(P, p, o, d, rng);
+}
+__global__ __launch_bounds__(BLOCK) void k_raygen_list(ptmi_camera cam, uint32_t n, const uint32_t *xs,
+                                                       const uint32_t *ys, const uint32_t *frames, DevPaths P) {
+    raygen_list<PTMI_PROJ_PERSPECTIVE>(cam, n, xs, ys, frames, P);
+}
+template <int PROJ>
+__global__ __launch_bounds__(BLOCK) void k_raygen_list_proj(ptmi_camera cam, uint32_t n, const uint32_t *xs,
+                                                            const uint32_t *ys, const uint32_t *frames, DevPaths P) {
+    raygen_list<PROJ>(cam, n, xs, ys, frames, P);
 }
 
 // ---- ordered compaction ------------------------------------------------------
@@ -496,7 +546,15 @@ __global__ __launch_bounds__(BLOCK) void k_ad_raygen(ptmi_camera cam, DevBand ba
                                                      const float4 *__restrict__ mom, DevPaths P, uint32_t *__restrict__ count_out,
                                                      unsigned long long *__restrict__ traced) {
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(traced, (unsigned long long)(*n_active * n_frames));
-    raygen(cam, ListedPixels{band, list, n_active, mom}, n_frames, P, count_out);
+    raygen<PTMI_PROJ_PERSPECTIVE>(cam, ListedPixels{band, list, n_active, mom}, n_frames, P, count_out);
+}
+template <int PROJ>
+__global__ __launch_bounds__(BLOCK) void k_ad_raygen_proj(ptmi_camera cam, DevBand band, const uint32_t *__restrict__ list,
+                                                          const uint32_t *__restrict__ n_active, uint32_t n_frames,
+                                                          const float4 *__restrict__ mom, DevPaths P, uint32_t *__restrict__ count_out,
+                                                          unsigned long long *__restrict__ traced) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(traced, (unsigned long long)(*n_active * n_frames));
+    raygen<PROJ>(cam, ListedPixels{band, list, n_active, mom}, n_frames, P, count_out);
 }
 __global__ __launch_bounds__(BLOCK) void k_ad_accumulate(DevBand band, const uint32_t *__restrict__ list, const uint32_t *__restrict__ n_active,
                                                          uint32_t n_frames, const float4 *__restrict__ mom, const float *__restrict__ L,
@@ -681,19 +739,30 @@ __global__ void k_exact_math(int which, unsigned long long *out) {
 void pt_launch_exact_math(hipStream_t s, int which, unsigned long long *out) {
     hipLaunchKernelGGL(k_exact_math, dim3(256 * 16), dim3(256), 0, s, which, out);
 }
-void pt_launch_raygen(hipStream_t s, int blocks, const ptmi_camera &cam, DevPixels px, uint32_t n_frames, DevPaths p,
+// proj: the camera's projection as pt_check_camera resolved it (PTMI_PROJ_PERSPECTIVE while the context's switch is off)
+void pt_launch_raygen(hipStream_t s, int blocks, const ptmi_camera &cam, uint32_t proj, DevPixels px, uint32_t n_frames, DevPaths p,
                       uint32_t *count_out) {
-    if (px.list)
-        hipLaunchKernelGGL(k_ad_raygen, dim3(blocks), dim3(BLOCK), 0, s, cam, px.band, px.list, px.n_active, n_frames, px.mom, p, count_out,
-                           px.traced);
-    else hipLaunchKernelGGL(k_raygen, dim3(blocks), dim3(BLOCK), 0, s, cam, px.band, px.frame0, n_frames, p, count_out);
+    const dim3 g(blocks), b(BLOCK);
+    if (px.list) {
+        auto *const k = proj == PTMI_PROJ_ORTHOGRAPHIC ? k_ad_raygen_proj<PTMI_PROJ_ORTHOGRAPHIC>
+                      : proj == PTMI_PROJ_EQUIRECT ? k_ad_raygen_proj<PTMI_PROJ_EQUIRECT> : k_ad_raygen;
+        hipLaunchKernelGGL(k, g, b, 0, s, cam, px.band, px.list, px.n_active, n_frames, px.mom, p, count_out, px.traced);
+    } else {
+        auto *const k = proj == PTMI_PROJ_ORTHOGRAPHIC ? k_raygen_proj<PTMI_PROJ_ORTHOGRAPHIC>
+                      : proj == PTMI_PROJ_EQUIRECT ? k_raygen_proj<PTMI_PROJ_EQUIRECT> : k_raygen;
+        hipLaunchKernelGGL(k, g, b, 0, s, cam, px.band, px.frame0, n_frames, p, count_out);
+    }
 }
-void pt_launch_center_rays(hipStream_t s, int blocks, const ptmi_camera &cam, DevBand band, DevPaths p, uint32_t *count_out) {
-    hipLaunchKernelGGL(k_center_rays, dim3(blocks), dim3(BLOCK), 0, s, cam, band, p, count_out);
+void pt_launch_center_rays(hipStream_t s, int blocks, const ptmi_camera &cam, uint32_t proj, DevBand band, DevPaths p, uint32_t *count_out) {
+    auto *const k = proj == PTMI_PROJ_ORTHOGRAPHIC ? k_center_rays_proj<PTMI_PROJ_ORTHOGRAPHIC>
+                  : proj == PTMI_PROJ_EQUIRECT ? k_center_rays_proj<PTMI_PROJ_EQUIRECT> : k_center_rays;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(BLOCK), 0, s, cam, band, p, count_out);
 }
-void pt_launch_raygen_list(hipStream_t s, const ptmi_camera &cam, uint32_t n, const uint32_t *xs,
+void pt_launch_raygen_list(hipStream_t s, const ptmi_camera &cam, uint32_t proj, uint32_t n, const uint32_t *xs,
                            const uint32_t *ys, const uint32_t *frames, DevPaths p) {
-    hipLaunchKernelGGL(k_raygen_list, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, cam, n, xs, ys, frames, p);
+    auto *const k = proj == PTMI_PROJ_ORTHOGRAPHIC ? k_raygen_list_proj<PTMI_PROJ_ORTHOGRAPHIC>
+                  : proj == PTMI_PROJ_EQUIRECT ? k_raygen_list_proj<PTMI_PROJ_EQUIRECT> : k_raygen_list;
+    hipLaunchKernelGGL(k, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, cam, n, xs, ys, frames, p);
 }
 void pt_launch_compact(hipStream_t s, int tiles, const uint32_t *queue, const uint32_t *count,
                        const uint64_t *alive_mask, const uint64_t *shadow_mask, const uint32_t *counts, uint32_t *tile_sums,

@@ -327,10 +327,11 @@ struct DevPixels {
     const uint32_t *list, *n_active; const float4 *mom;
     unsigned long long *traced;         // listed: the word kCtAdTraced, += the batch's paths (a plain dispatch counts its paths on the host)
 };
-// *count_out = entries * n_frames
-void pt_launch_raygen(hipStream_t s, int blocks, const ptmi_camera &cam, DevPixels px, uint32_t n_frames, DevPaths p,
+// *count_out = entries * n_frames. proj (here and below): the camera's projection, PTMI_PROJ_*, as pt_check_camera resolved it: the
+// pinhole's kernels for PTMI_PROJ_PERSPECTIVE, which is all a context with ptmi_set_projections off ever passes
+void pt_launch_raygen(hipStream_t s, int blocks, const ptmi_camera &cam, uint32_t proj, DevPixels px, uint32_t n_frames, DevPaths p,
                       uint32_t *count_out);
-void pt_launch_raygen_list(hipStream_t s, const ptmi_camera &cam, uint32_t n, const uint32_t *xs,
+void pt_launch_raygen_list(hipStream_t s, const ptmi_camera &cam, uint32_t proj, uint32_t n, const uint32_t *xs,
                            const uint32_t *ys, const uint32_t *frames, DevPaths p);
 void pt_launch_extend(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &sc, DevPaths p,
                       const uint32_t *queue, const uint32_t *count, float2 *hits);
@@ -442,7 +443,7 @@ void pt_launch_denoise(hipStream_t s, const DenoiseArgs &a, const float4 *radian
                        const float4 *moments, float4 *guide, float *grad, float4 *cv, float4 *tmp, float4 *out);
 // reprojection (reproject.hip, ptmi_reproject; the contract is stated in include/ptmi.h). The centre rays of the band's pixels under
 // `cam` go to p.O / p.D at the band-local pixel index, *count_out = their number: what `extend` then traces with a null queue.
-void pt_launch_center_rays(hipStream_t s, int blocks, const ptmi_camera &cam, DevBand band, DevPaths p, uint32_t *count_out);
+void pt_launch_center_rays(hipStream_t s, int blocks, const ptmi_camera &cam, uint32_t proj, DevBand band, DevPaths p, uint32_t *count_out);
 struct ReprojectArgs {
     ptmi_camera from;
     DevBand band;
@@ -458,6 +459,9 @@ struct ReprojectArgs {
     const float2 *uv;                                   // (u, v) of the hits, by band-local pixel (pt_launch_hit_uv)
     uint32_t dirty_first, dirty_end;                    // the triangles updated since the last commit: [dirty_first, dirty_end)
     float4 *motion;                                     // the motion plane; status[kCtRpMoved], [kCtRpMovedCarried] +=
+    // the projection of `from` (ptmi_set_projections): PTMI_PROJ_PERSPECTIVE or PTMI_PROJ_ORTHOGRAPHIC, whose ymag is from's second
+    // projection word. Last, so that the pinhole's kernels find every other argument where they always did.
+    uint32_t from_proj;
 };
 void pt_launch_reproject(hipStream_t s, const ReprojectArgs &a);
 // prev[3 i .. 3 i + 2] = (v0, v1, v2) of triangle i, w = 0, for first <= i < first + count (motion.hip: the commit, and the fill)

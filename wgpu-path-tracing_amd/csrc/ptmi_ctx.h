@@ -11,6 +11,7 @@
 //   alpha.hip          alpha cutouts and blending: the cutoff and blend tables, the two resolve loops between the existing kernels, their debug entry points
 //   scene_rebuild.hip  the walked own-leaf tree rebuilt in place: the unit list on the device, the swap (ptmi_rebuild_tree)
 //   motion.hip         reprojection across a geometry edit: the previous positions, their commit, the motion plane (ptmi_set_motion)
+//   projection.hip     camera projections: the switch, and the check of a camera's projection words (ptmi_set_projections)
 //   scene_pose.hip     what the three below share on the host: the check-then-write sequence of a pose, the rest-pose snapshot
 //   scene_transform.hip  triangle groups moved by matrix on the device: the table, the rest pose, the check and write kernel
 //   scene_skin.hip     skinned triangles posed on the device: the list, the corner records, the rest pose, the check and write kernel
@@ -72,6 +73,9 @@ int pt_check_skin_pose(const ptmi_ctx *c, const ptmi_joint_transform *joints, ui
 int pt_check_morph(const ptmi_ctx *c, const uint32_t *triangle, const uint32_t *row_start, const ptmi_morph_delta *deltas,
                    uint32_t n_morphed, uint32_t n_targets, std::string &err);
 int pt_check_morph_pose(const ptmi_ctx *c, const float *weights, uint32_t n_targets, std::string &err);
+// The projection a camera asks of c (ptmi_set_projections; dispatch.hip): *kind = PTMI_PROJ_PERSPECTIVE while c's switch is off, the
+// words unread; else word 0, checked with the word it makes meaningful: PTMI_E_INVALID with the reason in err. Changes nothing.
+int pt_check_camera(const ptmi_ctx *c, const ptmi_camera *cam, uint32_t *kind, std::string &err);
 // Adaptive rounds driven from outside, one at a time (ptmi_multi_dispatch_adaptive with neighbourhood = 1; dispatch.hip).
 // pt_adaptive_check: everything ptmi_dispatch_adaptive checks before it enqueues, with its error codes; *ap = the params with their defaults.
 int pt_adaptive_check(ptmi_ctx *c, const ptmi_camera *cam, const ptmi_adaptive_params *params, ptmi_adaptive_params *ap);
@@ -261,6 +265,7 @@ struct ptmi_ctx {
     float4 *d_out = nullptr;                           // what dispatches write: plane[kOut] or the caller's buffer (ptmi_bind_output_device)
     uint32_t aov_mask = 0;                             // ptmi_set_aovs: a plane is present while its bit is set and the output buffer exists
     bool moments_on = false;                           // ptmi_set_moments: likewise
+    bool projections_on = false;                       // ptmi_set_projections: a camera's projection words are read (pt_check_camera)
     // the counter and control words (pt_device.h CounterWord, ControlWord): made and zeroed by ptmi_create
     unsigned long long *d_counters = nullptr;          // kCounterWords
     uint32_t *d_control = nullptr;                     // kControlWords

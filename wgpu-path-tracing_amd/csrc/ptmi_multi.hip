@@ -660,6 +660,11 @@ int ptmi_multi_get_options(const ptmi_multi *m, ptmi_options *o) {
 
 int ptmi_multi_dispatch(ptmi_multi *m, const ptmi_camera *cam, uint32_t n_frames) {
     if (!m) return PTMI_E_INVALID;
+    if (cam) {                              // a camera the projection switch rejects: once, before any device enqueues
+        std::string why; uint32_t proj;
+        const int bad = pt_check_camera(m->d[0].ctx, cam, &proj, why);
+        if (bad) return mfail(m, bad, "%s", why.c_str());
+    }
     // One ptmi_dispatch of 64 frames is ~45 launches and ~110 event calls: 1.15 ms of host time (profiles/r04_multi.json). Enqueued
     // in turn from one thread, device i would start i x that after device 0 — 8 ms at N = 8 against 16 ms of device time per step of
     // configs[4] — so every device gets its own enqueuing thread for the call (contexts are independent: own device, own streams;
@@ -752,6 +757,16 @@ int ptmi_multi_get_moments(const ptmi_multi *m, uint32_t *on) {
     if (!m || !on) return PTMI_E_INVALID;
     *on = m->moments_on ? 1u : 0u;
     return PTMI_OK;
+}
+
+int ptmi_multi_set_projections(ptmi_multi *m, uint32_t on) {
+    if (!m) return PTMI_E_INVALID;
+    if (on > 1u) return mfail(m, PTMI_E_INVALID, "on = %u is not 0 or 1", on);
+    return each_ctx(m, "ptmi_set_projections", ptmi_set_projections, on);
+}
+int ptmi_multi_get_projections(const ptmi_multi *m, uint32_t *on) {
+    if (!m || !on) return PTMI_E_INVALID;
+    return ptmi_get_projections(m->d[0].ctx, on);
 }
 
 int ptmi_multi_gather_planes(ptmi_multi *m, uint32_t planes) {

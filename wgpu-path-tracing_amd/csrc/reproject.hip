@@ -7,10 +7,14 @@
 // centre-ray kernel of pipeline.hip, then `extend`); the hit point is projected into `from`, and the four snapshot pixels around it
 // that show the same surface (depth within the tolerance, same material when ids are compared) and hold samples are blended.
 //
-// k_reproject<true> is the pass while ptmi_set_motion is on: a hit on a triangle that moved since the history was rendered is projected
+// k_reproject<true, *> is the pass while ptmi_set_motion is on: a hit on a triangle that moved since the history was rendered is projected
 // from where its point was then (the hit's barycentrics on the previous positions), and every pixel writes the motion plane. The moved
 // test starts with the dirty range, two kernel arguments, so a wave whose hits all lie outside it reads nothing more than
-// k_reproject<false>, which is the kernel of a context with motion off, unchanged.
+// k_reproject<false, *>, which is the kernel of a context with motion off, unchanged.
+//
+// ORTHO is the projection of `from` (ptmi_set_projections): an orthographic camera's image coordinates are the point's right / up
+// components over the half extents, with no perspective divide, and its depth is zf, the t along a ray that starts on the camera
+// plane. k_reproject<*, false> is the pinhole's kernel, unchanged. The camera `to` enters through its centre rays alone.
 //
 // k_hit_uv writes the barycentrics that pass reads (ReprojectArgs::uv); ptmi_debug_intersect reports them too.
 #include "pt_device.h"
@@ -31,7 +35,7 @@ PT_DEV bool same_bits3(float4 p, const float *q) {
            __float_as_uint(p.z) == __float_as_uint(q[2]);
 }
 
-template <bool MOTION> __global__ __launch_bounds__(RX * RY) void k_reproject(ReprojectArgs a) {
+template <bool MOTION, bool ORTHO> __global__ __launch_bounds__(RX * RY) void k_reproject(ReprojectArgs a) {
     const DevBand &band = a.band;
     const uint32_t W = band.width, H = band.height;
     const uint32_t x = blockIdx.x * RX + threadIdx.x, l = blockIdx.y * RY + threadIdx.y;
@@ -70,11 +74,11 @@ template <bool MOTION> __global__ __launch_bounds__(RX * RY) void k_reproject(Re
             }
             const float vx = Px - cam.position[0], vy = Py - cam.position[1], vz = Pz - cam.position[2];
             const float zf = dot_plain(vx, vy, vz, cam.forward[0], cam.forward[1], cam.forward[2]);
-            const float dist = sqrt1(dot_plain(vx, vy, vz, vx, vy, vz));
-            const float th = tan1(cam.fov * 0.5f);
+            const float dist = ORTHO ? zf : sqrt1(dot_plain(vx, vy, vz, vx, vy, vz));
+            const float th = ORTHO ? __uint_as_float(cam._p3[1]) : tan1(cam.fov * 0.5f);      // orthographic: ymag, the half-height
             if (zf > 0.0f) {
-                const float sx = dot_plain(vx, vy, vz, cam.right[0], cam.right[1], cam.right[2]) / (zf * th * cam.aspect);
-                const float sy = dot_plain(vx, vy, vz, cam.up[0], cam.up[1], cam.up[2]) / (zf * th);
+                const float sx = dot_plain(vx, vy, vz, cam.right[0], cam.right[1], cam.right[2]) / (ORTHO ? th * cam.aspect : zf * th * cam.aspect);
+                const float sy = dot_plain(vx, vy, vz, cam.up[0], cam.up[1], cam.up[2]) / (ORTHO ? th : zf * th);
                 const float fx = (sx + 1.0f) * 0.5f * (float)W - 0.5f;
                 const float fy = (sy + 1.0f) * 0.5f * (float)H - 0.5f;
                 if (__builtin_isfinite(fx) && __builtin_isfinite(fy)) {
@@ -170,6 +174,8 @@ void pt_launch_hit_uv(hipStream_t s, uint32_t n, const DevScene &sc, DevPaths p,
 
 void pt_launch_reproject(hipStream_t s, const ReprojectArgs &a) {
     const dim3 grid((a.band.width + RX - 1) / RX, (a.band.rows + RY - 1) / RY), block(RX, RY);
-    if (a.motion) hipLaunchKernelGGL(k_reproject<true>, grid, block, 0, s, a);
-    else hipLaunchKernelGGL(k_reproject<false>, grid, block, 0, s, a);
+    const bool ortho = a.from_proj == PTMI_PROJ_ORTHOGRAPHIC;
+    auto *const k = a.motion ? (ortho ? k_reproject<true, true> : k_reproject<true, false>)
+                             : (ortho ? k_reproject<false, true> : k_reproject<false, false>);
+    hipLaunchKernelGGL(k, grid, block, 0, s, a);
 }

@@ -802,6 +802,28 @@ static napi_value js_set_moments(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* setProjections(h, on): ptmi_set_projections / ptmi_multi_set_projections. While on, bytes 88..95 of every camera blob are read */
+static napi_value js_set_projections(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    handle *h = get_handle(env, info, 2, argv);
+    if (!h) return NULL;
+    bool on = false;
+    napi_get_value_bool(env, argv[1], &on);
+    CALL(env, h, set_projections, on ? 1u : 0u);
+    return NULL;
+}
+
+/* getProjections(h) -> boolean */
+static napi_value js_get_projections(napi_env env, napi_callback_info info) {
+    napi_value argv[1], out;
+    handle *h = get_handle(env, info, 1, argv);
+    if (!h) return NULL;
+    uint32_t on = 0;
+    CALL(env, h, get_projections, &on);
+    napi_get_boolean(env, on != 0, &out);
+    return out;
+}
+
 /* denoise(h, {iterations, demodulate, phiColor, phiNormal, phiDepth} or null, Float32Array dst of width*height*4) */
 static napi_value js_denoise(napi_env env, napi_callback_info info) {
     napi_value argv[3];
@@ -1124,6 +1146,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"reproject", js_reproject}, {"reprojectStatus", js_reproject_status},
         {"setMotion", js_set_motion}, {"motionCommit", js_motion_commit}, {"motionStatus", js_motion_status}, {"readMotion", js_read_motion},
         {"debugMotionPrev", js_debug_motion_prev},
+        {"setProjections", js_set_projections}, {"getProjections", js_get_projections},
         {"buildBvh", js_build_bvh}, {"emissiveLights", js_emissive_lights},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

@@ -10,6 +10,8 @@
  * (normalised integer weights are scaled to [0, 1]). Morph targets: a primitive's `targets` ([{ POSITION?, NORMAL? }] as attribute
  * readings; TANGENT is ignored), a mesh's `weights` and a node's `weights` (which override the mesh's). Sparse accessors are not read
  * (the attribute reader needs a bufferView), for morph targets as for everything else.
+ * Cameras: `cameras` ({ name, type: 'perspective' | 'orthographic', perspective: { yfov, aspectRatio?, znear, zfar? } or
+ * orthographic: { xmag, ymag, znear, zfar } } as the file has them) and a node's `camera`, resolved to that object.
  * Images are decoded to RGBA8 ({width, height, data}; PNG and JPEG) and texture
  * references are resolved the way postProcessGLTF does (`material.normalTexture.texture.source.image`), which is
  * what src/renderer/atlas.ts:36-48 walks.
@@ -110,11 +112,17 @@ function loadGLB(pathOrBuffer) {
       }),
     };
   });
+  var cameras = (json.cameras || []).map(function (c) {
+    if (c.type !== 'perspective' && c.type !== 'orthographic') throw new Error('camera "' + (c.name || '') + '": unknown type ' + c.type);
+    if (!c[c.type]) throw new Error('camera "' + (c.name || '') + '" has no ' + c.type + ' object');
+    return JSON.parse(JSON.stringify(c));
+  });
   var nodes = (json.nodes || []).map(function (n) {
     var o = { name: n.name, matrix: n.matrix, translation: n.translation, rotation: n.rotation, scale: n.scale };
     if (n.mesh !== undefined) o.mesh = meshes[n.mesh];
     if (n.skin !== undefined) o.skin = n.skin;
     if (n.weights) o.weights = n.weights.slice();
+    if (n.camera !== undefined) { o.camera = cameras[n.camera]; o.cameraIndex = n.camera; }
     if (n.extensions && n.extensions.KHR_lights_punctual) o.light = n.extensions.KHR_lights_punctual.light;
     return o;
   });
@@ -134,7 +142,7 @@ function loadGLB(pathOrBuffer) {
       }) };
   });
   return { nodes: nodes, meshes: meshes, materials: materials, textures: textures, images: images, lights: rootLights,
-    skins: skins, animations: animations, json: json };
+    skins: skins, animations: animations, cameras: cameras, json: json };
 }
 
 module.exports = { parseGLB: parseGLB, readAccessor: readAccessor, loadGLB: loadGLB };

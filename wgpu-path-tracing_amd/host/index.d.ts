@@ -14,6 +14,17 @@ export interface TriangleCPU {
 export interface CameraCPU {
   position: number[]; forward: number[]; right: number[]; up: number[]; fov: number; aspect: number;
   width: number; height: number; frameIndex: number; aperture: number; focusDistance: number;
+  /** the two words the reference pads with (include/ptmi_layout.h): read only by a Renderer made with { projections: true } */
+  projection?: Projection | 0 | 1 | 2;
+  /** the orthographic half-height in world units (glTF's ymag); the half-width is ymag * aspect */
+  ymag?: number;
+}
+export type Projection = 'perspective' | 'orthographic' | 'equirect';
+/** a camera of a loaded .glb, in world space (scene_prep.js sceneCameras): a glTF camera looks down its node's -Z with +Y up */
+export interface SceneCamera {
+  name: string; node: number; camera: number; type: 'perspective' | 'orthographic';
+  position: number[]; forward: number[]; right: number[]; up: number[];
+  yfov?: number; aspectRatio?: number; znear?: number; zfar?: number; xmag?: number; ymag?: number;
 }
 export interface LightCPU { position: Vec3; lightType: number; color: Vec3; intensity: number; triangleIndex: number; }
 export interface BVHNode { aabb: { min: Vec3; max: Vec3 }; left: number; right: number; triangleOffset: number; triangleCount: number; }
@@ -67,6 +78,9 @@ export class Renderer {
                           alphaBlend?: boolean;
                           /** ... with this seed (absent: 0) */
                           alphaBlendSeed?: number;
+                          /** honour the camera's projection words (include/ptmi.h ptmi_set_projections): what setProjection and an
+                           *  orthographic useSceneCamera need. Off by default: every launch and every bit is then as without it */
+                          projections?: boolean;
                           /** updateTriangles calls rebuildTree() when it leaves sceneUpdateStatus().costNow / costBuilt above this ratio.
                            *  Off (0 / absent) by default; a rebuild was measured to pay from roughly 1.2 - 1.3 (README.md) */
                           rebuildAbove?: number });
@@ -168,6 +182,17 @@ export class Renderer {
    *  restarts the accumulation: the next adaptive round is preceded by reproject(previous camera, current camera) and continues
    *  from the per-pixel counts that leaves (include/ptmi.h ptmi_reproject). Turns the 'normal' plane on; throws with several devices */
   setReproject(params: ReprojectParams | null): void;
+  /** 'perspective' (camera.fov), 'orthographic' (params.ymag: the half-height in world units, finite and > 0) or 'equirect' (the full
+   *  sphere about camera.position; best with a 2:1 frame). Needs { projections: true }; camera.forward / right / up must be orthonormal.
+   *  Throws for 'equirect' while setReproject is set (and setReproject throws under an 'equirect' camera): that inverse is not
+   *  implemented. Restarts the accumulation. */
+  setProjection(kind: Projection, params?: { ymag?: number }): void;
+  /** the cameras of the loaded .glb ([] for any other model) */
+  sceneCameras(): SceneCamera[];
+  /** looks through camera i of the loaded .glb: position, basis, yfov or ymag, and the projection. The frame keeps its size: where the
+   *  file's aspect ratio differs from the frame's, the vertical extent (yfov / ymag) is kept and the frame's aspect is used. znear and
+   *  zfar are not modelled. */
+  useSceneCamera(i: number): void;
   /** of the last reprojection (include/ptmi.h ptmi_reproject_status); synchronises */
   reprojectStatus(): { carried: number; disoccluded: number; missed: number; samples: number };
   /** motion on / off (include/ptmi.h ptmi_set_motion): while on, a reprojection follows the triangles updateTriangles moved, and with

@@ -71,13 +71,24 @@ function packLights(lights) {
   return buf;
 }
 
-/** pt.wgsl:53-65 — the 96-byte uniform rewritten every frame (renderer.ts:403-413) */
+/** the camera's projection word (include/ptmi_layout.h PTMI_PROJ_*), by the name Renderer.setProjection takes */
+var PROJECTIONS = { perspective: 0, orthographic: 1, equirect: 2 };
+
+/** pt.wgsl:53-65 — the 96-byte uniform rewritten every frame (renderer.ts:403-413). The two words the reference pads with carry the
+ *  projection (include/ptmi_layout.h): camera.projection, a name of PROJECTIONS or its number (absent: 0, the pinhole), and
+ *  camera.ymag, the orthographic half-height in world units (absent: 0). A context reads them only after setProjections(true). */
 function packCamera(camera, out) {
   var buf = out || new ArrayBuffer(CAMERA_SIZE);
   var f = new Float32Array(buf), u = new Uint32Array(buf);
   put3(f, 0, camera.position); put3(f, 4, camera.forward); put3(f, 8, camera.right); put3(f, 12, camera.up);
   f[15] = camera.fov; f[16] = camera.aspect; u[17] = camera.width; u[18] = camera.height; u[19] = camera.frameIndex;
   f[20] = camera.aperture; f[21] = camera.focusDistance;
+  var kind = camera.projection || 0;
+  if (typeof kind === 'string') {
+    if (!(kind in PROJECTIONS)) throw new Error('unknown projection ' + kind);
+    kind = PROJECTIONS[kind];
+  }
+  u[22] = kind; f[23] = camera.ymag || 0;
   return buf;
 }
 
@@ -92,5 +103,5 @@ function packScene(sceneData) {
 module.exports = {
   TRIANGLE_SIZE: TRIANGLE_SIZE, MATERIAL_SIZE: MATERIAL_SIZE, BVH_NODE_SIZE: BVH_NODE_SIZE, LIGHT_SIZE: LIGHT_SIZE,
   CAMERA_SIZE: CAMERA_SIZE, packTriangles: packTriangles, packMaterials: packMaterials, packBVH: packBVH,
-  packLights: packLights, packCamera: packCamera, packScene: packScene,
+  packLights: packLights, packCamera: packCamera, packScene: packScene, PROJECTIONS: PROJECTIONS,
 };

@@ -5,7 +5,7 @@
  *  .bin blobs, the atlas (atlas.bin = rgba16float texels, atlas_rgba8.bin = the 8-bit canvas), triangle_groups.bin (one uint32 per
  *  triangle: the glTF node it came from), for a file with skins skin_triangles.bin (the uploaded indices of the skinned triangles,
  *  uint32) and skin_corners.bin (three 32-byte corner records each), for a file with morph targets morph_triangles.bin,
- *  morph_rows.bin (uint32 each) and morph_deltas.bin (96-byte delta records), and info.json.
+ *  morph_rows.bin (uint32 each) and morph_deltas.bin (96-byte delta records), and info.json (counts, names, and the file's cameras).
  *  No GPU needed. */
 var fs = require('fs'), path = require('path');
 var s = require('./scene_prep').prepareScene(require('./gltf').loadGLB(process.argv[2]));
@@ -26,6 +26,6 @@ if (s.morphTriangles) {
 }
 var skins = s.skins && s.skins.map(function (k) { return { node: k.node, skin: k.skin, joints: k.joints, jointBase: k.jointBase }; });
 fs.writeFileSync(path.join(dir, 'info.json'), JSON.stringify({ counts: s.counts, bvhDepth: s.bvhDepth, groupNames: s.groupNames,
-  skinJoints: s.skinJoints, skins: skins, morphTargets: s.morphTargets, morphs: s.morphs,
+  skinJoints: s.skinJoints, skins: skins, morphTargets: s.morphTargets, morphs: s.morphs, cameras: s.cameras,
   atlas: { width: a.width, height: a.height, format: a.format } }));
 console.log(JSON.stringify(s.counts));

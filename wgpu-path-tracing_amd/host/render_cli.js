@@ -9,7 +9,8 @@
  *                       --env file.hdr --env-intensity X --env-rotation DEGREES --env-sample 0|1
  *                       --fog sigma_t[,albedo[,g]] --fog-density file.f32 --fog-grid nx,ny,nz --fog-filter nearest|linear
  *                       --devices 0,1,... --loopback --aov albedo|normal|id --aov-out plane.bin
- *                       --alpha-cutout --alpha-blend --alpha-seed N --alpha-layers N --animation N --time S]
+ *                       --alpha-cutout --alpha-blend --alpha-seed N --alpha-layers N --animation N --time S
+ *                       --camera N --projection ortho|panorama --ymag V --hdr out.hdr]
  * --batch K traces K frames per dispatch instead of one. --denoise keeps the denoiser's planes and makes --png the tone-mapped
  * denoised image (include/ptmi.h ptmi_denoise, default parameters). --adaptive renders to a noise level instead of --frames
  * (include/ptmi.h ptmi_dispatch_adaptive): rounds until none lists a pixel, or --rounds R of them; the JSON line then also holds
@@ -32,6 +33,12 @@
  * --animation N --time S (a .glb scene with a skin or morph targets): renders one frame posed at S seconds (default 0) of the file's
  * animation N (Renderer.poseAt; include/ptmi.h ptmi_pose_morph, ptmi_pose_skin); the JSON line then also holds skin and morph: their
  * status.
+ * --camera N (a .glb scene) looks through the file's camera N (Renderer.useSceneCamera: position, basis, yfov or ymag, projection; the
+ * frame keeps --width x --height, so the file's vertical extent is kept and its aspect ratio is not). --projection ortho renders
+ * orthographically with the half-height --ymag V in world units (default 1); --projection panorama renders the full sphere about the
+ * camera position as an equirectangular image (include/ptmi.h ptmi_set_projections), best with a 2:1 frame. --hdr out.hdr also writes
+ * the output buffer as a Radiance file, top row first; for a panorama it is laid out as an environment map (hdr_encode.js), so that
+ * --env out.hdr lights another scene with what this camera saw. The JSON line then also holds projection.
  */
 var fs = require('fs');
 var host = require('./renderer');
@@ -58,6 +65,7 @@ var alphaCutout = process.argv.indexOf('--alpha-cutout') >= 0, alphaBlend = proc
 var r = new host.Renderer({ width: W, height: H, devices: devices || undefined, loopback: process.argv.indexOf('--loopback') >= 0,
                             alphaCutout: alphaCutout, alphaLayers: arg('alpha-layers', 0),
                             alphaBlend: alphaBlend, alphaBlendSeed: arg('alpha-seed', 0),
+                            projections: textArg('camera') !== null || textArg('projection') !== null,
                             options: { maxBounces: arg('bounces', 8), doMis: arg('mis', 1) } });
 r.camera.aperture = arg('aperture', r.camera.aperture);
 r.camera.focusDistance = arg('focus', r.camera.focusDistance);
@@ -92,6 +100,12 @@ r.loadModel(scenePath).then(function () {
     r.setMediumDensity(rho, dims, { filter: textArg('fog-filter') || 'nearest' });
   }
   if (textArg('animation') !== null) r.poseAt(arg('animation', 0), arg('time', 0));
+  if (textArg('camera') !== null) r.useSceneCamera(arg('camera', 0));
+  var projection = textArg('projection');
+  if (projection !== null) {
+    if (projection !== 'ortho' && projection !== 'panorama') throw new Error('--projection: ortho or panorama, not ' + projection);
+    r.setProjection(projection === 'ortho' ? 'orthographic' : 'equirect', { ymag: arg('ymag', r.camera.ymag || 1) });
+  } else if (textArg('ymag') !== null && r.camera.projection === 'orthographic') r.setProjection('orthographic', { ymag: arg('ymag', 1) });
   var t0 = Date.now();
   var status = null;
   if (adaptive) {
@@ -106,6 +120,12 @@ r.loadModel(scenePath).then(function () {
   var ms = Date.now() - t0;
   fs.writeFileSync(outPath, Buffer.from(out.buffer));
   if (aov && textArg('aov-out')) { var plane = r.readAov(aov); fs.writeFileSync(textArg('aov-out'), Buffer.from(plane.buffer)); }
+  if (textArg('hdr')) {
+    var enc = require('./hdr_encode'), top = new Float32Array(out.length);
+    if (r.camera.projection === 'equirect') top = enc.panoramaToEnvironment(out, W, H);
+    else for (var row = 0; row < H; row++) top.set(out.subarray((H - 1 - row) * W * 4, (H - row) * W * 4), row * W * 4);
+    fs.writeFileSync(textArg('hdr'), enc.encodeHDR(top, W, H));
+  }
   var pi = process.argv.indexOf('--png');
   if (pi >= 0) {
     var img;
@@ -118,6 +138,7 @@ r.loadModel(scenePath).then(function () {
   if (alphaCutout) st.alpha = r.alphaStatus();
   if (alphaBlend) st.alphaBlend = r.alphaBlendStatus();
   if (textArg('animation') !== null) { st.skin = r.skinStatus(); st.morph = r.morphStatus(); }
+  if (r.projections) st.projection = { kind: r.camera.projection || 'perspective', ymag: r.camera.ymag || 0 };
   if (status) st.adaptive = { samples: status.samples, minCount: status.minCount, maxCount: status.maxCount, rounds: status.rounds };
   console.log(JSON.stringify(st));
   r.destroy();

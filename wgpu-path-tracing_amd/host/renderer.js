@@ -66,6 +66,8 @@ function Renderer(options) {
   this.reprojectFrom = null;                // ... kept here while a camera change waits for the next round to reproject
   this.rebuildAbove = options.rebuildAbove || 0;        // updateTriangles rebuilds the walked tree above this costNow / costBuilt (0: never)
   this.motion = false;                      // setMotion: reprojection carries the samples across updateTriangles too
+  this.projections = !!options.projections; // the camera's projection words are honoured (setProjection, useSceneCamera)
+  if (this.projections) this.addon.setProjections(this.ctx, true);
   if (options.adaptive) this.setAdaptive(options.adaptive);
 }
 
@@ -77,6 +79,42 @@ Renderer.prototype.setupCamera = function () {
     frameIndex: 0, focusDistance: 5.0, aperture: 0.001,
   };
 };
+
+/** The camera's projection (include/ptmi.h ptmi_set_projections): 'perspective' (the reference's pinhole: camera.fov),
+ *  'orthographic' (params.ymag: the half-height in world units, finite and > 0; the half-width is ymag * aspect) or 'equirect' (the
+ *  full sphere about camera.position: longitude across the width, latitude up the height; a 2:1 frame gives square degrees). Needs
+ *  new Renderer({projections: true}): without it the library does not read the camera's projection words. forward / right / up must
+ *  be orthonormal. 'equirect' cannot be combined with setReproject: its inverse is outside the library's arithmetic contract. Restarts
+ *  accumulation. */
+Renderer.prototype.setProjection = function (kind, params) {
+  if (!(kind in pack.PROJECTIONS)) throw new Error("setProjection: 'perspective', 'orthographic' or 'equirect', not " + kind);
+  if (!this.projections && kind !== 'perspective') throw new Error('setProjection needs new Renderer({projections: true})');
+  if (kind === 'equirect' && this.reproject) throw new Error('an equirectangular camera cannot be reprojected: call setReproject(null) first');
+  var ymag = params && params.ymag !== undefined ? Number(params.ymag) : this.camera.ymag || 0;
+  if (kind === 'orthographic' && !(ymag > 0 && isFinite(ymag))) throw new Error('setProjection: orthographic needs a finite ymag > 0');
+  this.camera.projection = kind; this.camera.ymag = ymag;
+  this.resetOutputBuffer(false);
+};
+
+/** The cameras of the loaded .glb (scene_prep.js: name, type, position, forward, right, up, and yfov / aspectRatio / znear or xmag /
+ *  ymag). useSceneCamera(i) looks through camera i: position, basis, fov or ymag, and the projection. The frame keeps its size: where
+ *  the file's aspect ratio differs from the frame's, the vertical extent (yfov / ymag) is kept and the frame's aspect is used. znear
+ *  and zfar are not modelled. An orthographic camera needs new Renderer({projections: true}). */
+Renderer.prototype.sceneCameras = function () { return (this.sceneInfo && this.sceneInfo.cameras) || []; };
+Renderer.prototype.useSceneCamera = function (i) {
+  var cams = this.sceneCameras();
+  if (!(i >= 0 && i < cams.length)) throw new Error('useSceneCamera: the scene has ' + cams.length + ' cameras, no camera ' + i);
+  var kind = lookThrough(this.camera, cams[i]);
+  this.setProjection(kind, { ymag: this.camera.ymag });
+};
+/** what useSceneCamera sets on a camera object from a scene camera entry: position, basis, and fov (perspective) or ymag
+ *  (orthographic). aspect, width and height stay the frame's. Returns the projection's name. */
+function lookThrough(cam, c) {
+  cam.position = c.position.slice(); cam.forward = c.forward.slice(); cam.right = c.right.slice(); cam.up = c.up.slice();
+  if (c.type === 'orthographic') { cam.ymag = c.ymag; cam.projection = 'orthographic'; }
+  else { cam.fov = c.yfov; cam.projection = 'perspective'; }
+  return cam.projection;
+}
 
 Renderer.prototype.addOnUpdate = function (callback) { this.onUpdateTasks.push(callback); };
 
@@ -678,6 +716,8 @@ Renderer.prototype.renderAdaptive = function (rounds) {
  *  continues from the per-pixel counts that leaves. Turns the 'normal' plane on (the pass reads its depth); it stays on afterwards. */
 Renderer.prototype.setReproject = function (params) {
   if (this.multi) throw new Error('setReproject: reprojection is not supported with several devices');
+  if (params && this.camera.projection === 'equirect')
+    throw new Error('setReproject: an equirectangular camera cannot be reprojected (setProjection); its inverse is outside the arithmetic contract');
   if (params && !((this.aovMask || 0) & 2)) {
     this.addon.setAovs(this.ctx, (this.aovMask || 0) | 2);
     this.aovMask = (this.aovMask || 0) | 2;
@@ -737,4 +777,5 @@ function setupRenderer(options) {
 
 module.exports = { Renderer: Renderer, setupRenderer: setupRenderer, pack: pack, readSceneFile: sceneFile.readSceneFile,
   atlas: require('./atlas'), decodePNG: require('./png_decode').decodePNG, decodeHDR: require('./hdr_decode').decodeHDR,
-  decodeJPEG: require('./jpeg_decode').decodeJPEG, Controller: require('./controller').Controller };
+  decodeJPEG: require('./jpeg_decode').decodeJPEG, Controller: require('./controller').Controller,
+  encodeHDR: require('./hdr_encode').encodeHDR, lookThrough: lookThrough };

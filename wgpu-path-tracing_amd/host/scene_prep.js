@@ -256,6 +256,26 @@ function alphaBlendOf(material) {
   return f && f[3] !== undefined && f[3] !== null ? f[3] : 1;
 }
 
+/** The cameras of a file, one entry per node that carries one, in node order: { name, node, camera (the index in gltf.cameras), type,
+ *  position, forward, right, up } in world space from the node's world matrix - a glTF camera looks down its node's -Z with +Y up, so
+ *  forward / right / up are the normalised images of (0, 0, -1), (1, 0, 0), (0, 1, 0) (orthonormal for a node without scale or shear,
+ *  which is what glTF asks of camera nodes) - plus yfov, aspectRatio (undefined: the viewport's), znear for a perspective camera and
+ *  xmag, ymag for an orthographic one. znear / zfar are carried for the caller; the renderer clips nothing. */
+function sceneCameras(gltf, world) {
+  var out = [];
+  gltf.nodes.forEach(function (node, nodeIndex) {
+    if (!node.camera) return;
+    var w = world.get(node), c = node.camera;
+    var axis = function (x, y, z) { return Array.from(M.normalize(M.transformMat4Upper3x3(M.vec3(x, y, z), w))); };
+    var e = { name: c.name || node.name || 'camera' + out.length, node: nodeIndex, camera: node.cameraIndex, type: c.type,
+      position: [w[12], w[13], w[14]], forward: axis(0, 0, -1), right: axis(1, 0, 0), up: axis(0, 1, 0) };
+    if (c.type === 'perspective') { e.yfov = c.perspective.yfov; e.aspectRatio = c.perspective.aspectRatio; e.znear = c.perspective.znear; }
+    else { e.xmag = c.orthographic.xmag; e.ymag = c.orthographic.ymag; e.znear = c.orthographic.znear; e.zfar = c.orthographic.zfar; }
+    out.push(e);
+  });
+  return out;
+}
+
 /** loader.ts:20-40 + gpu.ts:67-150 -> { blobs, atlas, counts, bvhDepth, triangleGroups, groupNames }: triangleGroups holds, per
  *  triangle in the uploaded (reordered) order, the index of the glTF node it came from (Renderer.setTriangleGroups), groupNames
  *  the nodes' names by that index (opts.triangleGroups === false: neither). opts.alphaCutout: the atlas keeps the alpha of albedo maps
@@ -267,7 +287,7 @@ function alphaBlendOf(material) {
  *  inverseBind, meshWorldInverse, jointBase } (opts.skins === false, or a file without skins: none of them, and every blob the
  *  same bytes). A file with morph targets also returns morphTriangles, morphRowStart, morphDeltas (morphList), morphTargets (the
  *  targets of all mesh instances together) and morphs: per morphed node { node, targetBase, nTargets, weights (its defaults) }
- *  (opts.morphs === false, or a file without targets: none of them) */
+ *  (opts.morphs === false, or a file without targets: none of them). cameras: the file's cameras (sceneCameras; [] without any). */
 function prepareScene(gltf, opts) {
   var alphaCutout = !!(opts && opts.alphaCutout), alphaBlend = !!(opts && opts.alphaBlend);
   var packed = require('./atlas').packing(gltf, { keepAlpha: alphaCutout || alphaBlend });
@@ -330,11 +350,12 @@ function prepareScene(gltf, opts) {
     morphDeltas: morph ? morph.deltas : undefined, morphTargets: morph ? morphTargets : undefined,
     morphs: morph ? morphs.filter(Boolean) : undefined,
     atlas: packed.texture,
+    cameras: sceneCameras(gltf, world),
     counts: { triangles: allTriangles.length, materials: allMaterials.length, bvhNodes: bvh.nodes.byteLength / pack.BVH_NODE_SIZE,
       lights: lights.byteLength / pack.LIGHT_SIZE, punctualLights: allLights.length },
     bvhDepth: bvh.depth,
   };
 }
 
-module.exports = { prepareScene: prepareScene, skinPose: skinPose, morphPose: morphPose, extractNodeMatrix: extractNodeMatrix, buildMaterial: buildMaterial, alphaCutoffOf: alphaCutoffOf,
+module.exports = { prepareScene: prepareScene, sceneCameras: sceneCameras, skinPose: skinPose, morphPose: morphPose, extractNodeMatrix: extractNodeMatrix, buildMaterial: buildMaterial, alphaCutoffOf: alphaCutoffOf,
   alphaBlendOf: alphaBlendOf };

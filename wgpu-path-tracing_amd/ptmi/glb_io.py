@@ -63,7 +63,7 @@ def encode_png(pixels, color_type=6, filters=None, palette=None, trns=None, dept
     return b"\x89PNG\r\n\x1a\n" + body
 
 
-def write_glb(path, meshes, nodes, materials, lights=None, images=None, textures=None, skins=None, animations=None):
+def write_glb(path, meshes, nodes, materials, lights=None, images=None, textures=None, skins=None, animations=None, cameras=None):
     """meshes: list of dicts {positions (N,3), normals (N,3), uvs (N,2) or None, indices (M,), material or None,
     joints (N,4) and weights (N,4) or absent: JOINTS_0 as uint16 and WEIGHTS_0 as float32,
     targets or absent: morph targets, a list of dicts {positions (N,3) or None, normals (N,3) or None}, morph_weights or absent: the
@@ -72,8 +72,10 @@ def write_glb(path, meshes, nodes, materials, lights=None, images=None, textures
     images: list of encoded image files (bytes, PNG); textures: list of image indices (one glTF texture each);
     skins: list of dicts {joints: node indices, inverseBindMatrices: (n,16) column-major or None};
     animations: list of dicts {channels: [{node, path, sampler}], samplers: [{input: times, output: (k, width), interpolation}]};
-    a sampler with scalar=True (a `weights` channel) writes its output as k * width scalars.
-    Without skins, animations and targets the file is the bytes it always was."""
+    a sampler with scalar=True (a `weights` channel) writes its output as k * width scalars;
+    cameras: list of glTF camera objects as the file holds them ({type, perspective | orthographic: {...}, name?}), named by a node's
+    `camera` index.
+    Without skins, animations, targets and cameras the file is the bytes it always was."""
     bin_parts, views, accessors = [], [], []
 
     def add(arr, target, ctype, atype):
@@ -116,7 +118,7 @@ def write_glb(path, meshes, nodes, materials, lights=None, images=None, textures
             jm[-1]["weights"] = [float(w) for w in m["morph_weights"]]
     jn = []
     for n in nodes:
-        o = {k: n[k] for k in ("mesh", "skin", "translation", "rotation", "scale", "matrix", "children", "name", "weights") if k in n}
+        o = {k: n[k] for k in ("mesh", "skin", "camera", "translation", "rotation", "scale", "matrix", "children", "name", "weights") if k in n}
         if "light" in n:
             o["extensions"] = {"KHR_lights_punctual": {"light": n["light"]}}
         jn.append(o)
@@ -157,6 +159,8 @@ def write_glb(path, meshes, nodes, materials, lights=None, images=None, textures
             doc["images"].append({"bufferView": len(views) - 1, "mimeType": "image/png"})
         doc["textures"] = [{"source": int(i)} for i in (textures if textures is not None else range(len(images)))]
         doc["buffers"] = [{"byteLength": sum(len(b) for b in bin_parts)}]
+    if cameras:
+        doc["cameras"] = cameras
     if lights:
         doc["extensions"] = {"KHR_lights_punctual": {"lights": lights}}
         doc["extensionsUsed"] = ["KHR_lights_punctual"]

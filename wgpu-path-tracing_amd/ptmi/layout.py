@@ -61,12 +61,28 @@ assert LIGHT.fields["light_type"][1] == 12 and LIGHT.fields["triangle_index"][1]
 assert CAMERA.fields["fov"][1] == 60 and CAMERA.fields["focus_distance"][1] == 84
 
 
+# the camera's projection words (include/ptmi_layout.h PTMI_PROJ_*): _p3[0] = the kind, _p3[1] = the bits of ymag. Read only by a
+# context with set_projections(True)
+PROJ_PERSPECTIVE, PROJ_ORTHOGRAPHIC, PROJ_EQUIRECT = 0, 1, 2
+PROJECTIONS = {"perspective": PROJ_PERSPECTIVE, "orthographic": PROJ_ORTHOGRAPHIC, "equirect": PROJ_EQUIRECT}
+assert CAMERA.fields["_p3"][1] == 88
+
+
+def set_projection(camera, projection=PROJ_PERSPECTIVE, ymag=0.0):
+    """writes the two projection words of a camera record in place (a name of PROJECTIONS or a number; ymag: the orthographic
+    half-height in world units) and returns it"""
+    camera["_p3"] = (PROJECTIONS.get(projection, projection), np.float32(ymag).view(np.uint32))
+    return camera
+
+
 def make_camera(width, height, *, position=(0.0, 1.0, 2.8), forward=(0.0, 0.0, -1.0),
                 right=(1.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), fov=np.pi / 3, aspect=None,
-                frame_index=0, aperture=0.001, focus_distance=5.0):
+                frame_index=0, aperture=0.001, focus_distance=5.0, projection=PROJ_PERSPECTIVE, ymag=0.0):
     """The 96-byte camera uniform; defaults are the reference's setupCamera
-    (src/renderer/renderer.ts:136-150)."""
+    (src/renderer/renderer.ts:136-150). projection / ymag: the two words the reference pads with (set_projection); the defaults
+    leave them zero."""
     c = np.zeros((), CAMERA)
+    set_projection(c, projection, ymag)
     c["position"], c["forward"], c["right"], c["up"] = position, forward, right, up
     c["fov"] = fov
     c["aspect"] = (width / height) if aspect is None else aspect

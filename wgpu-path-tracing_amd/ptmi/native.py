@@ -54,6 +54,7 @@ EXPORTS = [
     "ptmi_multi_set_triangle_groups", "ptmi_multi_transform_groups", "ptmi_multi_transform_status",
     "ptmi_set_skin", "ptmi_pose_skin", "ptmi_skin_status", "ptmi_multi_set_skin", "ptmi_multi_pose_skin", "ptmi_multi_skin_status",
     "ptmi_set_morph", "ptmi_pose_morph", "ptmi_morph_status", "ptmi_multi_set_morph", "ptmi_multi_pose_morph", "ptmi_multi_morph_status",
+    "ptmi_set_projections", "ptmi_get_projections", "ptmi_multi_set_projections", "ptmi_multi_get_projections",
 ]
 MULTI_LOOPBACK = 1
 MULTI_PLANE_MOMENTS, MULTI_PLANE_OUTPUT = 0x100, 0x200      # gather_planes: with the AOV_* bits
@@ -323,6 +324,7 @@ _SHARED = {
     "skin_status": [ctypes.c_void_p],
     "set_morph": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32],
     "pose_morph": [ctypes.c_void_p, ctypes.c_uint32], "morph_status": [ctypes.c_void_p],
+    "set_projections": [ctypes.c_uint32], "get_projections": [ctypes.POINTER(ctypes.c_uint32)],
 }
 _lib = None
 
@@ -878,6 +880,16 @@ class _Handle:
         """whether the sample-moments plane is on"""
         m = ctypes.c_uint32(0)
         self._ck(self._c.get_moments(self.h, ctypes.byref(m)))
+        return bool(m.value)
+
+    # -- camera projections (include/ptmi.h ptmi_set_projections) ------------------------------------------------
+    def set_projections(self, on=True):
+        """while on, the projection words of every camera this handle is given are honoured (layout.make_camera(projection=, ymag=))"""
+        self._ck(self._c.set_projections(self.h, int(on)))
+
+    def projections(self):
+        m = ctypes.c_uint32(0)
+        self._ck(self._c.get_projections(self.h, ctypes.byref(m)))
         return bool(m.value)
 
     def read_moments(self):
