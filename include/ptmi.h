@@ -222,6 +222,58 @@ int ptmi_synchronize(ptmi_ctx *ctx);
  * members are unchanged. */
 int ptmi_set_projections(ptmi_ctx *ctx, uint32_t on);
 int ptmi_get_projections(const ptmi_ctx *ctx, uint32_t *on);
+
+/* ---- lightmap baking: paths that start at surface texels instead of a camera -----------------
+ * A bake answers "what light arrives at this surface?": the output buffer is read as a lightmap, texel (x, y) = entry y * width + x
+ * (row 0 at the bottom, as everywhere) standing for lightmap coordinate ((x + 0.5) / width, (y + 0.5) / height). The caller says where
+ * each texel lies in the scene (ptmi_bake_texel, ptmi_layout.h: position, normal, covered); ptmi/bake.py and host/bake.js rasterise a
+ * mesh's lightmap UVs into such records.
+ *
+ * ptmi_upload_bake_surface: width x height records, which must be the context's current size (else PTMI_E_INVALID). A covered record
+ * whose position is not finite, or whose normal is not finite or has a squared length (float32) of zero or infinity, is
+ * PTMI_E_INVALID, and the surface that was in place stays in place. The device keeps the records (width * height * 32 bytes) and the
+ * list of the covered texels in ascending texel index, which is the order paths and folds walk them in. texels NULL removes the
+ * surface; so does a ptmi_resize to another size. Synchronises.
+ *
+ * ptmi_dispatch_bake: n_frames frames of every covered texel, from params->first_frame on, through the bounce loop of ptmi_dispatch
+ * and everything that belongs to it: batch sizing, the traversal pick, the side stream, statistics, sky, medium, both alpha modes,
+ * in-place edits and poses. Only the first ray differs. For covered texel (x, y) at frame f, in the kernels' float32 (pt_math.h):
+ *   rng = seed(x, y, f);  r1 = rand(rng);  r2 = rand(rng)              the pinhole's two jitter draws, and nothing else
+ *   n = normalize(normal);  (sp, cp) = sincos((2 pi) * r1);  z = sqrt(1 - r2);  sr = sqrt(r2)
+ *   (T, B) = the frame shade builds around n (pt.wgsl:624-634);  raw = lincomb3(T, cp * sr, B, sp * sr, n, z)
+ *   origin = fma(raw, bias, position) per component;  dir = normalize(raw)
+ * which is the continuation of a path that bounced diffusely at the texel (pt.wgsl:299-307, :691 with bias where EPSILON stands), so
+ * a bake inherits the renderer's self-intersection behaviour. It is also pixel (x, y, f) of a pinhole camera with position = origin,
+ * forward = raw, fov = 0, aperture = 0: the same seed, draws and path, bit for bit (where no component of raw is a zero).
+ * Per sample the clamp is the reference's 2.5, and the output buffer holds the running mean of the incoming radiance under
+ * cosine-weighted directions: E / pi, the radiance a white Lambertian texel would reflect; the engine multiplies by albedo. Frame
+ * first_frame = 0 overwrites, as for a camera. Uncovered texels are neither read nor written. While the moments plane is on
+ * (ptmi_set_moments), covered texels fold their moments too, with the count first_frame + n_frames.
+ * LIMIT: punctual lights reach a texel only through later bounces - a ray cannot hit them, and there is no next-event sample at the
+ * texel itself. Emissive triangles and the sky are seen directly. This is the usual baked-indirect split.
+ * params NULL: first_frame 0, bias 1e-6f (the reference's EPSILON). bias must be finite and >= 0 and is used exactly as given; the
+ * reserved words must be 0. PTMI_E_INVALID, with nothing enqueued or written: no surface in place, a first-hit plane on
+ * (ptmi_set_aovs mask non-zero), tile options that do not cover the whole frame, a bad bias. n_frames = 0 or no covered texel:
+ * PTMI_OK, nothing written. Asynchronous, like ptmi_dispatch.
+ *
+ * ptmi_bake_dilate: gutter fill. Leaves the output buffer alone and writes a dilated copy to dst_rgba (width * height * 4 floats,
+ * else PTMI_E_INVALID); needs a surface. Per texel a state: 1 covered, 2 filled by an earlier pass, 0 empty. Pass k: every state-0
+ * texel looks at its 8 neighbours in the order dy = -1, 0, 1 outer, dx = -1, 0, 1 inner (itself and anything outside the frame
+ * skipped), takes those whose state was non-zero BEFORE this pass, sums their rgb in that order in float32 starting from +0, and if
+ * any were taken becomes sum / (float)count (one IEEE division per channel) with state 2. dst.w carries the state as a float; rgb of
+ * state-0 texels is 0. passes = 0 is the masked copy. Synchronises.
+ *
+ * ptmi_debug_bake_rays: the first ray of texel (xs[i], ys[i]) at frames[i] under params, as ptmi_debug_raygen returns a camera's:
+ * origin, direction, and the RNG state it leaves. An uncovered texel returns zeros; a texel outside the surface is PTMI_E_INVALID.
+ * The ABI version stays 4: new calls only. */
+typedef struct ptmi_bake_params { uint32_t first_frame; float bias; uint32_t _reserved[2]; } ptmi_bake_params;
+struct ptmi_bake_status { uint32_t present, width, height, covered; };
+int ptmi_upload_bake_surface(ptmi_ctx *ctx, const ptmi_bake_texel *texels, uint32_t width, uint32_t height);
+int ptmi_dispatch_bake(ptmi_ctx *ctx, const ptmi_bake_params *params, uint32_t n_frames);
+int ptmi_bake_status(ptmi_ctx *ctx, struct ptmi_bake_status *out);
+int ptmi_bake_dilate(ptmi_ctx *ctx, uint32_t passes, float *dst_rgba, size_t n_floats);
+int ptmi_debug_bake_rays(ptmi_ctx *ctx, const ptmi_bake_params *params, uint32_t n, const uint32_t *xs, const uint32_t *ys,
+                         const uint32_t *frames, float *o3, float *d3, uint32_t *rng);
 /* Back-pressure for a caller that enqueues dispatches from a loop without reading results — a preview loop; the reference paces
  * itself on requestAnimationFrame (renderer.ts:456-473). Blocks until at most max_in_flight of this context's dispatches have
  * not yet finished on the device and reports how many still are (in_flight may be NULL). max_in_flight = 0xFFFFFFFF only polls.

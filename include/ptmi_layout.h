@@ -122,6 +122,17 @@ static inline void ptmi_camera_set_projection(ptmi_camera *c, uint32_t kind, flo
  * bottom (pt.wgsl:104, :753; renderer.ts:272-279). */
 #define PTMI_OUTPUT_STRIDE 16u
 
+/* A texel of a bake surface (include/ptmi.h, ptmi_upload_bake_surface): where the lightmap texel lies on the scene's surface. No
+ * counterpart in the reference. 32 B, read by the device as two float4. */
+typedef struct ptmi_bake_texel {
+    float position[3];              /* 0   the surface point, world space */
+    uint32_t covered;               /* 12  0: an empty texel, never traced and never written; non-zero: traced */
+    float normal[3];                /* 16  the surface normal there: any finite non-zero length, normalised on the device */
+    uint32_t _pad;                  /* 28 */
+} ptmi_bake_texel;
+PTMI_STATIC_ASSERT(sizeof(ptmi_bake_texel) == 32, "a bake texel is two float4");
+PTMI_STATIC_ASSERT(offsetof(ptmi_bake_texel, normal) == 16, "BakeTexel.normal");
+
 PTMI_STATIC_ASSERT(sizeof(ptmi_material) == 128, "Material is 128 B");
 PTMI_STATIC_ASSERT(offsetof(ptmi_material, metallic) == 12, "Material.metallic");
 PTMI_STATIC_ASSERT(offsetof(ptmi_material, roughness) == 16, "Material.roughness");

@@ -107,22 +107,29 @@ struct Timed {
 // the raygen in front of it and the folds behind it.
 // map (with ap; ptmi_multi_dispatch_adaptive): the round selects from the whole-frame flag map and never restarts (pt_adaptive_flags
 // has); count_call = false: a further round of one call, which ptmi_stats.dispatches has already counted.
+// bake (ptmi_dispatch_bake, which has checked it: bake_check; no camera, no ap): n_frames frames of every covered texel of the surface
+// in place, from bake->first_frame. A third raygen and a third pair of folds; a batch's pixels are the covered texels.
 int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_adaptive_params *ap, uint32_t rounds,
-             const DevFlagMap *map = nullptr, bool count_call = true) {
+             const DevFlagMap *map = nullptr, bool count_call = true, const ptmi_bake_params *bake = nullptr) {
     int rc = check_ready(c, true);
     if (rc) return rc;
-    if (!cam) return fail(c, PTMI_E_INVALID, "camera is NULL");
-    if (cam->width != c->W || cam->height != c->H)
-        return fail(c, PTMI_E_INVALID, "camera says %ux%u but the output buffer is %ux%u", cam->width, cam->height, c->W, c->H);
-    uint32_t proj;
-    if ((rc = pt_check_camera(c, cam, &proj, c->err))) return rc;
-    if (n_frames == 0 || (ap && rounds == 0)) return PTMI_OK;
+    static const ptmi_camera no_camera{};                       // what a bake's raygen is handed and never reads
+    uint32_t proj = PTMI_PROJ_PERSPECTIVE;
+    if (bake) cam = &no_camera;
+    else {
+        if (!cam) return fail(c, PTMI_E_INVALID, "camera is NULL");
+        if (cam->width != c->W || cam->height != c->H)
+            return fail(c, PTMI_E_INVALID, "camera says %ux%u but the output buffer is %ux%u", cam->width, cam->height, c->W, c->H);
+        if ((rc = pt_check_camera(c, cam, &proj, c->err))) return rc;
+    }
+    if (n_frames == 0 || (ap && rounds == 0) || (bake && c->bake_covered == 0u)) return PTMI_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     if (ap && (rc = make_planes(c, group_set(kByAdaptive), (size_t)c->W * c->H, c->plane))) return rc;
     const DevBand band = pt_band_of(c->opt, c->W, c->H);
     if (band.y0 >= band.y1) return fail(c, PTMI_E_INVALID, "tile rows [%u,%u) outside the %u-row frame", band.y0, band.y1, c->H);
     if (band.rows == 0) return PTMI_OK;                         // more parts than strips: nothing to render here
-    const uint64_t npix = (uint64_t)band.rows * band.width;
+    const uint64_t npix = bake ? c->bake_covered : (uint64_t)band.rows * band.width;
+    const uint32_t first_frame = bake ? bake->first_frame : cam->frame_index;
     uint32_t F = c->opt.frames_per_batch;
     // ~128 Mi paths, ~23 GB of state: the last bounces' small queues cost a fixed time per batch, so fewer, larger batches
     // (measured at 1080p, Msamples/s: 32 frames 8 920, 64 frames 9 150 - 9 275, 128 frames 9 270 - 9 310, when that time was ~3 ms.
@@ -199,11 +206,13 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         float4 *const mom = plane_as<float4>(c, kMoments);
         unsigned long long *const ct = c->d_counters;
         uint32_t *const qlen = &c->d_control[kCwQueue], *const slen = &c->d_control[kCwShadow];    // queue lengths by bounce; shadow, by parity
-        if (ap && !map && cam->frame_index == 0u) { pt_launch_adaptive_restart(ms, blocks, band, mom); c->ad_rounds = 0; }
+        if (ap && !map && first_frame == 0u) { pt_launch_adaptive_restart(ms, blocks, band, mom); c->ad_rounds = 0; }
         // a batch: fb frames of every pixel from frame0 on, or (ap) of every listed pixel from its own count on
         auto batch = [&](uint32_t frame0, uint32_t fb) -> int {
-            const DevPixels px = ap ? DevPixels{band, 0u, c->ad.list, &c->d_control[kCwAdActive], mom, &ct[kCtAdTraced]}
-                                    : DevPixels{band, frame0, nullptr, nullptr, nullptr, nullptr};
+            const DevPixels px = ap ? DevPixels{band, 0u, c->ad.list, &c->d_control[kCwAdActive], mom, &ct[kCtAdTraced], nullptr, nullptr, 0u, 0.0f}
+                               : bake ? DevPixels{band, frame0, nullptr, nullptr, nullptr, nullptr, c->d_bake_texels, c->d_bake_covered,
+                                                  c->bake_covered, bake->bias}
+                                      : DevPixels{band, frame0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0.0f};
             { Timed t(c, kRaygen, t3, ms); pt_launch_raygen(ms, blocks, *cam, proj, px, fb, bp, &qlen[0]); }
             int cur = 0;
             for (uint32_t b = 0; b < maxb; b++) {
@@ -262,7 +271,7 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
             c->ad_rounds += rounds;
         } else {
             for (uint32_t f0 = 0; f0 < n_frames; f0 += F)
-                if ((rc = batch(cam->frame_index + f0, std::min(F, n_frames - f0)))) return rc;
+                if ((rc = batch(first_frame + f0, std::min(F, n_frames - f0)))) return rc;
         }
     }
     HIP_TRY(c, hipGetLastError());
@@ -335,6 +344,13 @@ int ptmi_dispatch_adaptive(ptmi_ctx *c, const ptmi_camera *cam, const ptmi_adapt
     const int rc = pt_adaptive_check(c, cam, params, &ap);
     if (rc) return rc;
     return dispatch(c, cam, ap.step, &ap, rounds);
+}
+
+int ptmi_dispatch_bake(ptmi_ctx *c, const ptmi_bake_params *params, uint32_t n_frames) {
+    ptmi_bake_params bp;
+    const int rc = bake_check(c, params, &bp);
+    if (rc) return rc;
+    return dispatch(c, nullptr, n_frames, nullptr, 0, nullptr, true, &bp);
 }
 
 int ptmi_adaptive_status(ptmi_ctx *c, struct ptmi_adaptive_status *out) {

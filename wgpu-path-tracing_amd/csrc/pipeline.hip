@@ -89,6 +89,35 @@ struct ListedPixels {                   // the *n_active pixels of the list, eac
     PT_DEV uint32_t first_frame(size_t oi) const { return (uint32_t)mom[oi].z; }
 };
 
+struct BakedPixels {                    // the n covered texels of a bake surface (ascending frame indices; whole frame), all from frame0
+    DevBand band; const uint32_t *covered; uint32_t n, frame0;
+    PT_DEV uint32_t entries() const { return n; }
+    PT_DEV uint32_t pixel(uint32_t j) const { return covered[j]; }
+    PT_DEV uint32_t first_frame(size_t) const { return frame0; }
+};
+
+// The first ray of a bake path (include/ptmi.h ptmi_dispatch_bake): the continuation of a path that bounced diffusely at the texel.
+// constructTBN, pt.wgsl:624-634, as shade.hip has it; randomCosineDirection in that frame as sample_bsdf's diffuse lobe forms it.
+PT_DEV void bake_tbn(v3 N, v3 &T, v3 &B) {
+    T = mk3(1.0f, 0.0f, 0.0f);
+    if (__builtin_fabsf(N.x) > 0.9f) T = mk3(0.0f, 1.0f, 0.0f);
+    B = normalize3(cross3(N, T));
+    T = normalize3(cross3(B, N));
+}
+// t0 = (position, covered), t1 = (normal, pad): the two float4 of a ptmi_bake_texel
+PT_DEV void bake_ray(float4 t0, float4 t1, float bias, uint32_t x, uint32_t y, uint32_t frame, v3 &org, v3 &dir, uint32_t &rng) {
+    rng = rng_seed(x, y, frame);
+    const float r1 = rng_f(rng), r2 = rng_f(rng);           // the pinhole's two jitter draws
+    const v3 n = normalize3(xyz(t1));
+    const float phi = (2.0f * PT_PI) * r1;
+    float sp, cp; sincos1(phi, sp, cp);
+    const float z = sqrt1(1.0f - r2), sr = sqrt1(r2);
+    v3 T, B; bake_tbn(n, T, B);
+    const v3 raw = lincomb3(T, cp * sr, B, sp * sr, n, z);
+    org = madd3(raw, bias, xyz(t0));                        // pt.wgsl:691 with bias where EPSILON stands
+    dir = normalize3(raw);
+}
+
 template <int PROJ, class Pixels>
 PT_DEV void raygen(const ptmi_camera &cam, const Pixels &px, uint32_t n_frames, DevPaths P, uint32_t *__restrict__ count_out) {
     const DevBand &band = px.band;
@@ -157,6 +186,33 @@ template <int PROJ>
 __global__ __launch_bounds__(BLOCK) void k_raygen_list_proj(ptmi_camera cam, uint32_t n, const uint32_t *xs,
                                                             const uint32_t *ys, const uint32_t *frames, DevPaths P) {
     raygen_list<PROJ>(cam, n, xs, ys, frames, P);
+}
+
+// Ray generation over a bake surface: raygen's walk of the source (path k * entries + j is frame frame0 + k of entry j), each path
+// from its texel's record. The list holds covered texels only, so every record read here is one the upload checked.
+__global__ __launch_bounds__(BLOCK) void k_bake_raygen(BakedPixels px, const float4 *__restrict__ texels, float bias, uint32_t n_frames,
+                                                       DevPaths P, uint32_t *__restrict__ count_out) {
+    const uint32_t n = px.entries();
+    const uint32_t total = n * n_frames;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *count_out = total;
+    for (uint32_t p = blockIdx.x * BLOCK + threadIdx.x; p < total; p += gridDim.x * BLOCK) {
+        const uint32_t k = p / n, pix = px.pixel(p - k * n);
+        const uint32_t y = pix / px.band.width, x = pix % px.band.width;
+        v3 o, d; uint32_t rng;
+        bake_ray(texels[2 * (size_t)pix], texels[2 * (size_t)pix + 1], bias, x, y, px.first_frame(pix) + k, o, d, rng);
+        init_path(P, p, o, d, rng);
+    }
+}
+// ptmi_debug_bake_rays: texel (xs[p], ys[p]) at frames[p]; the caller has checked that it lies inside the surface
+__global__ __launch_bounds__(BLOCK) void k_bake_rays(const float4 *__restrict__ texels, uint32_t width, float bias, uint32_t n,
+                                                     const uint32_t *xs, const uint32_t *ys, const uint32_t *frames, DevPaths P) {
+    const uint32_t p = blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const size_t pix = (size_t)ys[p] * width + xs[p];
+    const float4 t0 = texels[2 * pix], t1 = texels[2 * pix + 1];
+    v3 o = mk3(0.0f, 0.0f, 0.0f), d = o; uint32_t rng = 0u;
+    if (__float_as_uint(t0.w) != 0u) bake_ray(t0, t1, bias, xs[p], ys[p], frames[p], o, d, rng);
+    init_path(P, p, o, d, rng);
 }
 
 // ---- ordered compaction ------------------------------------------------------
@@ -430,6 +486,16 @@ __global__ __launch_bounds__(BLOCK) void k_accumulate_moments(DevBand band, uint
                                                               const float *__restrict__ L, uint32_t l_stride,
                                                               float4 *__restrict__ mom) {
     fold_moments(DensePixels{band, frame0}, n_frames, L, l_stride, mom);
+}
+
+// ... and over a bake surface's covered texels (ptmi_dispatch_bake): no first-hit fold, a bake is refused while those planes are on
+__global__ __launch_bounds__(BLOCK) void k_bake_accumulate(BakedPixels px, uint32_t n_frames, const float *__restrict__ L, uint32_t l_stride,
+                                                           float4 *__restrict__ out) {
+    fold_radiance(px, n_frames, L, l_stride, out);
+}
+__global__ __launch_bounds__(BLOCK) void k_bake_accumulate_moments(BakedPixels px, uint32_t n_frames, const float *__restrict__ L,
+                                                                   uint32_t l_stride, float4 *__restrict__ mom) {
+    fold_moments(px, n_frames, L, l_stride, mom);
 }
 
 // ---- adaptive sampling (ptmi_dispatch_adaptive; the rule is stated in include/ptmi.h) ------------------------------------------
@@ -743,7 +809,10 @@ void pt_launch_exact_math(hipStream_t s, int which, unsigned long long *out) {
 void pt_launch_raygen(hipStream_t s, int blocks, const ptmi_camera &cam, uint32_t proj, DevPixels px, uint32_t n_frames, DevPaths p,
                       uint32_t *count_out) {
     const dim3 g(blocks), b(BLOCK);
-    if (px.list) {
+    if (px.bake_texels) {
+        hipLaunchKernelGGL(k_bake_raygen, g, b, 0, s, BakedPixels{px.band, px.covered, px.n_covered, px.frame0}, px.bake_texels, px.bias,
+                           n_frames, p, count_out);
+    } else if (px.list) {
         auto *const k = proj == PTMI_PROJ_ORTHOGRAPHIC ? k_ad_raygen_proj<PTMI_PROJ_ORTHOGRAPHIC>
                       : proj == PTMI_PROJ_EQUIRECT ? k_ad_raygen_proj<PTMI_PROJ_EQUIRECT> : k_ad_raygen;
         hipLaunchKernelGGL(k, g, b, 0, s, cam, px.band, px.list, px.n_active, n_frames, px.mom, p, count_out, px.traced);
@@ -763,6 +832,10 @@ void pt_launch_raygen_list(hipStream_t s, const ptmi_camera &cam, uint32_t proj,
     auto *const k = proj == PTMI_PROJ_ORTHOGRAPHIC ? k_raygen_list_proj<PTMI_PROJ_ORTHOGRAPHIC>
                   : proj == PTMI_PROJ_EQUIRECT ? k_raygen_list_proj<PTMI_PROJ_EQUIRECT> : k_raygen_list;
     hipLaunchKernelGGL(k, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, cam, n, xs, ys, frames, p);
+}
+void pt_launch_bake_rays(hipStream_t s, const float4 *texels, uint32_t width, float bias, uint32_t n, const uint32_t *xs,
+                         const uint32_t *ys, const uint32_t *frames, DevPaths p) {
+    hipLaunchKernelGGL(k_bake_rays, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, texels, width, bias, n, xs, ys, frames, p);
 }
 void pt_launch_compact(hipStream_t s, int tiles, const uint32_t *queue, const uint32_t *count,
                        const uint64_t *alive_mask, const uint64_t *shadow_mask, const uint32_t *counts, uint32_t *tile_sums,
@@ -792,7 +865,10 @@ void pt_launch_repack(hipStream_t s, int blocks, const uint32_t *count, const ui
     hipLaunchKernelGGL(k_repack, dim3(blocks), dim3(BLOCK), 0, s, count, queue, from, to, pid);
 }
 void pt_launch_accumulate(hipStream_t s, int blocks, DevPixels px, uint32_t n_frames, const float *L, uint32_t l_stride, float4 *out) {
-    if (px.list)
+    if (px.bake_texels)
+        hipLaunchKernelGGL(k_bake_accumulate, dim3(blocks), dim3(BLOCK), 0, s, BakedPixels{px.band, px.covered, px.n_covered, px.frame0},
+                           n_frames, L, l_stride, out);
+    else if (px.list)
         hipLaunchKernelGGL(k_ad_accumulate, dim3(blocks), dim3(BLOCK), 0, s, px.band, px.list, px.n_active, n_frames, px.mom, L, l_stride, out);
     else hipLaunchKernelGGL(k_accumulate, dim3(blocks), dim3(BLOCK), 0, s, px.band, px.frame0, n_frames, L, l_stride, out);
 }
@@ -807,7 +883,10 @@ void pt_launch_accumulate_aov(hipStream_t s, int blocks, DevPixels px, uint32_t 
 }
 void pt_launch_accumulate_moments(hipStream_t s, int blocks, DevPixels px, uint32_t n_frames, const float *L, uint32_t l_stride,
                                   float4 *mom) {
-    if (px.list)
+    if (px.bake_texels)
+        hipLaunchKernelGGL(k_bake_accumulate_moments, dim3(blocks), dim3(BLOCK), 0, s,
+                           BakedPixels{px.band, px.covered, px.n_covered, px.frame0}, n_frames, L, l_stride, mom);
+    else if (px.list)
         hipLaunchKernelGGL(k_ad_accumulate_moments, dim3(blocks), dim3(BLOCK), 0, s, px.band, px.list, px.n_active, n_frames, L, l_stride, mom);
     else hipLaunchKernelGGL(k_accumulate_moments, dim3(blocks), dim3(BLOCK), 0, s, px.band, px.frame0, n_frames, L, l_stride, mom);
 }

@@ -326,6 +326,9 @@ struct DevPixels {
     DevBand band; uint32_t frame0;
     const uint32_t *list, *n_active; const float4 *mom;
     unsigned long long *traced;         // listed: the word kCtAdTraced, += the batch's paths (a plain dispatch counts its paths on the host)
+    // a bake (ptmi_dispatch_bake; bake_texels NULL: not one): the n_covered covered texels of `covered` (ascending frame indices; the
+    // band is the whole frame), every one from frame0 on, each path starting at its texel's record instead of the camera
+    const float4 *bake_texels; const uint32_t *covered; uint32_t n_covered; float bias;
 };
 // *count_out = entries * n_frames. proj (here and below): the camera's projection, PTMI_PROJ_*, as pt_check_camera resolved it: the
 // pinhole's kernels for PTMI_PROJ_PERSPECTIVE, which is all a context with ptmi_set_projections off ever passes
@@ -333,6 +336,13 @@ void pt_launch_raygen(hipStream_t s, int blocks, const ptmi_camera &cam, uint32_
                       uint32_t *count_out);
 void pt_launch_raygen_list(hipStream_t s, const ptmi_camera &cam, uint32_t proj, uint32_t n, const uint32_t *xs,
                            const uint32_t *ys, const uint32_t *frames, DevPaths p);
+// the bake rays of n texels (xs, ys) at `frames` (ptmi_debug_bake_rays): path i = the ray of texel i, zeros for an uncovered texel
+void pt_launch_bake_rays(hipStream_t s, const float4 *texels, uint32_t width, float bias, uint32_t n, const uint32_t *xs,
+                         const uint32_t *ys, const uint32_t *frames, DevPaths p);
+// gutter fill (bake.hip, ptmi_bake_dilate): a = the masked copy of `out` (rgb of covered texels, w = 1; zeros elsewhere), then `passes`
+// passes of the rule of include/ptmi.h ping-ponging between a and b; returns the plane that holds the result
+float4 *pt_launch_bake_dilate(hipStream_t s, uint32_t W, uint32_t H, uint32_t passes, const float4 *texels, const float4 *out,
+                              float4 *a, float4 *b);
 void pt_launch_extend(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &sc, DevPaths p,
                       const uint32_t *queue, const uint32_t *count, float2 *hits);
 void pt_launch_extend_own(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &sc, DevPaths p,

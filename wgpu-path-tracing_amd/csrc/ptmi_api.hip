@@ -109,6 +109,7 @@ const struct { const char *name; size_t (*bytes)(size_t px); bool zeroed; PlaneG
     {"id history", per_pixel<8>, false, kByReproject},
     {"float canvas", per_pixel<16>, false, kByBlit}, {"8-bit canvas", per_pixel<4>, false, kByBlit},
     {"motion", per_pixel<16>, true, kWithFrame},
+    {"dilate ping", per_pixel<16>, false, kByBake}, {"dilate pong", per_pixel<16>, false, kByBake},
 };
 // sets of planes: a bit per FramePlane
 constexpr uint32_t kAllPlanes = (1u << kFramePlanes) - 1u;
@@ -340,6 +341,7 @@ int ptmi_destroy(ptmi_ctx *c) {
     }
     for (void *&p : c->buf) dfree(p);
     dfree(c->d_atlas); dfree(c->d_env); dfree(c->d_env_alias); dfree(c->d_med_grid);
+    bake_forget(c);
     drop_planes(c, kAllPlanes);
     dfree(c->d_counters); dfree(c->d_control); dfree(c->d_scene);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -413,7 +415,8 @@ int ptmi_resize(ptmi_ctx *c, uint32_t w, uint32_t h) {
         for (void *&p : fresh) dfree(p);
         return fail(c, PTMI_E_HIP, "sync_all failed: %s", hipGetErrorString(e));
     }
-    drop_planes(c, kAllPlanes);                       // the denoiser's, the adaptive, the history and the blit planes come back at their first use
+    drop_planes(c, kAllPlanes);                       // the denoiser's, the adaptive, the history, the blit and the dilate planes come back at their first use
+    if (w != c->W || h != c->H) bake_forget(c);       // a bake surface is a surface of one size
     std::copy(fresh, fresh + kFramePlanes, c->plane);
     c->W = w; c->H = h;
     c->d_out = plane_as<float4>(c, kOut);

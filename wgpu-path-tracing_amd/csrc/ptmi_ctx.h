@@ -16,6 +16,7 @@
 //   scene_transform.hip  triangle groups moved by matrix on the device: the table, the rest pose, the check and write kernel
 //   scene_skin.hip     skinned triangles posed on the device: the list, the corner records, the rest pose, the check and write kernel
 //   scene_morph.hip    morphed triangles posed on the device: the list, the sparse delta rows, the rest pose, the check and write kernel
+//   bake.hip           lightmap baking: the surface's records and covered list, the checks of a bake, the gutter fill, the debug rays
 #pragma once
 #include "ptmi.h"
 #include "pt_device.h"
@@ -145,6 +146,7 @@ enum FramePlane {
     kRpOut, kRpMoments, kRpNormal, kRpAlbedo, kRpId,   // reprojection: the snapshot of the output, moments and first-hit planes
     kBlitF32, kBlitU8,                             // canvas staging of ptmi_blit
     kMotion,                                       // the motion plane of ptmi_set_motion: where each pixel's surface was in `from`
+    kBakeA, kBakeB,                                // ptmi_bake_dilate: the two ping-pong planes (rgb, state)
     kFramePlanes
 };
 
@@ -266,6 +268,11 @@ struct ptmi_ctx {
     uint32_t aov_mask = 0;                             // ptmi_set_aovs: a plane is present while its bit is set and the output buffer exists
     bool moments_on = false;                           // ptmi_set_moments: likewise
     bool projections_on = false;                       // ptmi_set_projections: a camera's projection words are read (pt_check_camera)
+    // the bake surface (ptmi_upload_bake_surface; bake.hip): W x H records of two float4 and the ascending list of the covered texels;
+    // gone with a ptmi_resize to another size
+    float4 *d_bake_texels = nullptr;                   // NULL: no surface in place
+    uint32_t *d_bake_covered = nullptr;
+    uint32_t bake_covered = 0;                         // entries of the list
     // the counter and control words (pt_device.h CounterWord, ControlWord): made and zeroed by ptmi_create
     unsigned long long *d_counters = nullptr;          // kCounterWords
     uint32_t *d_control = nullptr;                     // kControlWords
@@ -300,7 +307,7 @@ hipError_t sync_all(ptmi_ctx *c);
 size_t bytes_per_path(bool aov, bool env_w, bool alpha);
 void lane_views(Lane &ln);
 int ensure_capacity(ptmi_ctx *c, Lane &ln, size_t n);
-enum PlaneGroup { kWithFrame, kByDenoise, kByAdaptive, kByReproject, kByBlit };     // when a plane is made (the kFrame table)
+enum PlaneGroup { kWithFrame, kByDenoise, kByAdaptive, kByReproject, kByBlit, kByBake };     // when a plane is made (the kFrame table)
 constexpr uint32_t bit(FramePlane k) { return 1u << k; }                            // sets of planes: a bit per FramePlane
 uint32_t group_set(PlaneGroup g);
 size_t plane_bytes(FramePlane k, size_t px);                                        // what plane k takes for px pixels
@@ -310,6 +317,11 @@ int check_ready(ptmi_ctx *c, bool need_output);
 // dispatch.hip
 void drain_events(ptmi_ctx *c);
 hipError_t quiesce(ptmi_ctx *c);
+
+// bake.hip. bake_forget: the surface goes (the caller has synchronised). bake_check: everything ptmi_dispatch_bake checks before it
+// enqueues, with its error codes, changing nothing; *out = the params with their defaults.
+void bake_forget(ptmi_ctx *c);
+int bake_check(ptmi_ctx *c, const ptmi_bake_params *params, ptmi_bake_params *out);
 
 // scene_update.hip: the plan of ptmi_update_triangles. make_plan reads the topology of both hierarchies as they stand and leaves the
 // context's scene alone (a failure leaves no plan behind; the caller drops what is left); walked_cost: the cost of the walked hierarchy

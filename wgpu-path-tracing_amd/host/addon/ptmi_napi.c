@@ -996,6 +996,79 @@ static napi_value js_debug_motion_prev(napi_env env, napi_callback_info info) {
     return argv[3];
 }
 
+/* ---- lightmap baking (include/ptmi.h ptmi_upload_bake_surface ...): one device's handle only, like reprojection ---- */
+
+/* {firstFrame, bias} or null -> ptmi_bake_params; absent members take the C defaults */
+static void get_bake_params(napi_env env, napi_value v, ptmi_bake_params *prm) {
+    napi_valuetype t;
+    memset(prm, 0, sizeof *prm);
+    prm->bias = 1e-6f;
+    if (napi_typeof(env, v, &t) == napi_ok && t == napi_object) {
+        prm->first_frame = get_u32_prop(env, v, "firstFrame", 0);
+        prm->bias = get_f32_prop(env, v, "bias", 1e-6f);
+    }
+}
+
+/* uploadBakeSurface(h, texels (32-byte records) or null, width, height) */
+static napi_value js_upload_bake_surface(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    handle *h = get_single_handle(env, info, 4, argv, "uploadBakeSurface");
+    if (!h) return NULL;
+    void *p; size_t n; uint32_t w = 0, hh = 0;
+    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
+    napi_get_value_uint32(env, argv[2], &w); napi_get_value_uint32(env, argv[3], &hh);
+    if (p && n != (size_t)w * hh * sizeof(ptmi_bake_texel)) {
+        napi_throw_range_error(env, NULL, "uploadBakeSurface: expected width * height records of 32 bytes"); return NULL;
+    }
+    int rc = ptmi_upload_bake_surface(h->ctx, (const ptmi_bake_texel *)p, w, hh);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_upload_bake_surface");
+    return NULL;
+}
+
+/* dispatchBake(h, {firstFrame, bias} or null, frames): ptmi_dispatch_bake */
+static napi_value js_dispatch_bake(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    handle *h = get_single_handle(env, info, 3, argv, "dispatchBake");
+    if (!h) return NULL;
+    ptmi_bake_params prm;
+    uint32_t frames = 1;
+    get_bake_params(env, argv[1], &prm);
+    napi_get_value_uint32(env, argv[2], &frames);
+    int rc = ptmi_dispatch_bake(h->ctx, &prm, frames);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_dispatch_bake");
+    return NULL;
+}
+
+/* bakeStatus(h) -> {present, width, height, covered} */
+static napi_value js_bake_status(napi_env env, napi_callback_info info) {
+    napi_value argv[1];
+    handle *h = get_single_handle(env, info, 1, argv, "bakeStatus");
+    if (!h) return NULL;
+    struct ptmi_bake_status s;
+    int rc = ptmi_bake_status(h->ctx, &s);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_bake_status");
+    napi_value o;
+    NAPI_OK(env, napi_create_object(env, &o));
+    set_num(env, o, "present", (double)s.present); set_num(env, o, "width", (double)s.width);
+    set_num(env, o, "height", (double)s.height); set_num(env, o, "covered", (double)s.covered);
+    return o;
+}
+
+/* bakeDilate(h, passes, Float32Array dst of width*height*4): the gutter-filled copy of the output buffer, w = the state */
+static napi_value js_bake_dilate(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    handle *h = get_single_handle(env, info, 3, argv, "bakeDilate");
+    if (!h) return NULL;
+    uint32_t passes = 0;
+    napi_get_value_uint32(env, argv[1], &passes);
+    void *p; size_t n;
+    if (!get_bytes(env, argv[2], &p, &n)) return NULL;
+    if (!check_canvas(env, h, "bakeDilate", "Float32Array", 4, p, n)) return NULL;
+    int rc = ptmi_bake_dilate(h->ctx, passes, (float *)p, n / 4);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_bake_dilate");
+    return argv[2];
+}
+
 /* readMoments(h, Float32Array dst of width*height*4): the sample-moments plane */
 static napi_value js_read_moments(napi_env env, napi_callback_info info) {
     napi_value argv[2];
@@ -1147,6 +1220,8 @@ static napi_value init(napi_env env, napi_value exports) {
         {"setMotion", js_set_motion}, {"motionCommit", js_motion_commit}, {"motionStatus", js_motion_status}, {"readMotion", js_read_motion},
         {"debugMotionPrev", js_debug_motion_prev},
         {"setProjections", js_set_projections}, {"getProjections", js_get_projections},
+        {"uploadBakeSurface", js_upload_bake_surface}, {"dispatchBake", js_dispatch_bake}, {"bakeStatus", js_bake_status},
+        {"bakeDilate", js_bake_dilate},
         {"buildBvh", js_build_bvh}, {"emissiveLights", js_emissive_lights},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

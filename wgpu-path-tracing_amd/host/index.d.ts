@@ -159,6 +159,15 @@ export class Renderer {
   moveCamera(forward: number, right: number, up: number): void;
   rotateCamera(yaw: number, pitch: number): void;
   readOutput(): Float32Array;
+  /** a lightmap of the loaded scene (include/ptmi.h ptmi_dispatch_bake, ptmi_bake_dilate): its triangles rasterised over their lightmap
+   *  coordinates (a .glb's TEXCOORD_1, else TEXCOORD_0; any other model: the triangles' own uv), `frames` paths from every covered
+   *  texel. width*height float4, row y at v = (y + 0.5) / height: the mean incoming radiance under the cosine law (E / pi; multiply by
+   *  albedo); w is 0, or with dilate > 0 the texel's state (1 covered, 2 filled, 0 empty). Defaults: the frame's size, 64 frames, no
+   *  dilation, bias 1e-6. The frame takes the lightmap's size and accumulation restarts. Punctual lights reach a texel only through
+   *  later bounces. Throws with several devices and while first-hit planes are on; synchronises */
+  bake(opts?: { width?: number; height?: number; frames?: number; dilate?: number; bias?: number }): Float32Array;
+  /** what the last bake() baked */
+  lastBake?: { width: number; height: number; frames: number; covered: number };
   /** first-hit planes (include/ptmi.h ptmi_set_aovs); with several devices each keeps its strips and readAov assembles the plane */
   setAovs(names: Array<'albedo' | 'normal' | 'id'>): void;
   /** width*height entries, index y*width+x: 'albedo' / 'normal' 4 floats each, 'id' 2 uint32 (triangle, material) */

@@ -10,7 +10,8 @@
  *                       --fog sigma_t[,albedo[,g]] --fog-density file.f32 --fog-grid nx,ny,nz --fog-filter nearest|linear
  *                       --devices 0,1,... --loopback --aov albedo|normal|id --aov-out plane.bin
  *                       --alpha-cutout --alpha-blend --alpha-seed N --alpha-layers N --animation N --time S
- *                       --camera N --projection ortho|panorama --ymag V --hdr out.hdr]
+ *                       --camera N --projection ortho|panorama --ymag V --hdr out.hdr
+ *                       --bake W,H --bake-dilate N --bake-bias B]
  * --batch K traces K frames per dispatch instead of one. --denoise keeps the denoiser's planes and makes --png the tone-mapped
  * denoised image (include/ptmi.h ptmi_denoise, default parameters). --adaptive renders to a noise level instead of --frames
  * (include/ptmi.h ptmi_dispatch_adaptive): rounds until none lists a pixel, or --rounds R of them; the JSON line then also holds
@@ -39,6 +40,11 @@
  * camera position as an equirectangular image (include/ptmi.h ptmi_set_projections), best with a 2:1 frame. --hdr out.hdr also writes
  * the output buffer as a Radiance file, top row first; for a panorama it is laid out as an environment map (hdr_encode.js), so that
  * --env out.hdr lights another scene with what this camera saw. The JSON line then also holds projection.
+ * --bake W,H bakes a W x H lightmap instead of rendering from the camera (Renderer.bake; include/ptmi.h ptmi_dispatch_bake): --frames
+ * samples per covered texel over the scene's lightmap coordinates (a .glb's TEXCOORD_1, else TEXCOORD_0), --bake-dilate N gutter-fill
+ * passes (default 0), --bake-bias B the origin offset along the first ray (default 1e-6). out.f32 and --hdr then hold the lightmap
+ * (row y at v = (y + 0.5) / H; w: 0, or with --bake-dilate the texel's state), --png its tone-mapped image, and the JSON line bake:
+ * { width, height, frames, covered }. Not with --devices, --denoise, --aov or --adaptive.
  */
 var fs = require('fs');
 var host = require('./renderer');
@@ -107,8 +113,14 @@ r.loadModel(scenePath).then(function () {
     r.setProjection(projection === 'ortho' ? 'orthographic' : 'equirect', { ymag: arg('ymag', r.camera.ymag || 1) });
   } else if (textArg('ymag') !== null && r.camera.projection === 'orthographic') r.setProjection('orthographic', { ymag: arg('ymag', 1) });
   var t0 = Date.now();
-  var status = null;
-  if (adaptive) {
+  var status = null, out = null;
+  if (textArg('bake') !== null) {
+    var size = textArg('bake').split(',').map(Number);
+    if (size.length !== 2 || !(size[0] > 0) || !(size[1] > 0)) throw new Error('--bake: W,H');
+    if (devices || denoise || aov || adaptive) throw new Error('--bake does not go with --devices, --denoise, --aov or --adaptive');
+    out = r.bake({ width: size[0], height: size[1], frames: frames, dilate: arg('bake-dilate', 0), bias: arg('bake-bias', 1e-6) });
+    W = size[0]; H = size[1];
+  } else if (adaptive) {
     r.setAdaptive(adaptive);
     var rounds = arg('rounds', 0);
     if (rounds > 0) r.renderAdaptive(rounds);
@@ -116,7 +128,7 @@ r.loadModel(scenePath).then(function () {
     status = r.adaptiveStatus();
   } else
     while (r.frameIndex < frames) r.renderFrame(Math.min(batch, frames - r.frameIndex));
-  var out = r.readOutput();
+  if (!out) out = r.readOutput();
   var ms = Date.now() - t0;
   fs.writeFileSync(outPath, Buffer.from(out.buffer));
   if (aov && textArg('aov-out')) { var plane = r.readAov(aov); fs.writeFileSync(textArg('aov-out'), Buffer.from(plane.buffer)); }
@@ -139,6 +151,7 @@ r.loadModel(scenePath).then(function () {
   if (alphaBlend) st.alphaBlend = r.alphaBlendStatus();
   if (textArg('animation') !== null) { st.skin = r.skinStatus(); st.morph = r.morphStatus(); }
   if (r.projections) st.projection = { kind: r.camera.projection || 'perspective', ymag: r.camera.ymag || 0 };
+  if (r.lastBake) st.bake = r.lastBake;
   if (status) st.adaptive = { samples: status.samples, minCount: status.minCount, maxCount: status.maxCount, rounds: status.rounds };
   console.log(JSON.stringify(st));
   r.destroy();

@@ -127,7 +127,7 @@ Renderer.prototype.loadModel = function (model, atlas) {
   var self = this;
   return new Promise(function (resolve) {
     var blobs, cutoff = null, blend = null, groups = null, skin = null, morph = null;
-    self.gltf = null; self.skins = null; self.morphs = null;
+    self.gltf = null; self.skins = null; self.morphs = null; self.lightmapUvs = null;
     if (typeof model === 'string' && /\.glb$/i.test(model)) {
       var gltf = require('./gltf').loadGLB(model);
       var prepared = require('./scene_prep').prepareScene(gltf, { alphaCutout: self.alphaCutout, alphaBlend: self.alphaBlend });
@@ -135,6 +135,7 @@ Renderer.prototype.loadModel = function (model, atlas) {
       cutoff = prepared.alphaCutoff || null;
       blend = prepared.alphaBlend || null;
       groups = prepared.triangleGroups || null;
+      self.lightmapUvs = prepared.lightmapUvs || null;
       if (prepared.skinTriangles) { skin = prepared; self.gltf = gltf; }
       if (prepared.morphTriangles) { morph = prepared; self.gltf = gltf; }
     } else if (typeof model === 'string') {
@@ -143,6 +144,7 @@ Renderer.prototype.loadModel = function (model, atlas) {
     } else if (model.blobs) {
       blobs = model.blobs; atlas = atlas || model.atlas;
       groups = model.triangleGroups || null;                            // what prepareScene returned: a triangle's glTF node
+      self.lightmapUvs = model.lightmapUvs || null;                     // ... and its lightmap coordinates
       if (model.skinTriangles) { skin = model; self.gltf = model.gltf || null; }   // ... and its skinned triangles
       if (model.morphTriangles) { morph = model; self.gltf = model.gltf || null; } // ... and its morphed ones
       if (self.alphaCutout) cutoff = model.alphaCutoff || null;         // what prepareScene({alphaCutout: true}) returned
@@ -151,6 +153,7 @@ Renderer.prototype.loadModel = function (model, atlas) {
       blobs = pack.packScene(model);
     }
     self.addon.uploadScene(self.ctx, blobs.triangles, blobs.materials, blobs.bvhNodes, blobs.lights);
+    self.sceneTriangles = blobs.triangles;            // bake() rasterises them
     self.sceneBounds = rootBox(blobs.bvhNodes);       // setMedium({ bounds: 'scene' })
     if (atlas) self.addon.uploadAtlas(self.ctx, atlas.data, atlas.width, atlas.height, atlas.format || 1);
     else self.addon.uploadAtlas(self.ctx, null, 0, 0, 0);
@@ -615,6 +618,57 @@ Renderer.prototype.rotateCamera = function (yaw, pitch) {
 Renderer.prototype.readOutput = function () {
   var out = new Float32Array(this.width * this.height * 4);
   this.addon.readOutput(this.ctx, out);
+  return out;
+};
+
+/**
+ * A lightmap of the loaded scene (include/ptmi.h ptmi_upload_bake_surface, ptmi_dispatch_bake, ptmi_bake_dilate): opts = { width,
+ * height (default: the frame's), frames (samples per texel, default 64), dilate (gutter-fill passes, default 0), bias (default 1e-6) }.
+ * The scene's triangles are rasterised over their lightmap coordinates (bake.js: a .glb's TEXCOORD_1, else TEXCOORD_0; any other
+ * model: the triangles' own uv0..2), every covered texel traces `frames` paths from its surface point, and the result is the
+ * width * height float4 lightmap, index y * width + x with row y at lightmap coordinate v = (y + 0.5) / height: the mean incoming
+ * radiance under the cosine law, E / pi, which the engine multiplies by albedo. w is 0, or with dilate > 0 the texel's state: 1
+ * covered, 2 filled, 0 empty. Texels lie where the triangles were when they were loaded: later edits and poses are traced but do not
+ * move them. One device only; the first-hit planes must be off. The frame takes the lightmap's size (resize) and accumulation
+ * restarts; lastBake = { width, height, frames, covered } says what was baked. Synchronises.
+ */
+Renderer.prototype.bake = function (opts) {
+  opts = opts || {};
+  if (!this.sceneLoaded || !this.sceneTriangles) throw new Error('bake: needs a loaded scene (loadModel)');
+  if (this.multi) throw new Error('bake: one device only');
+  if (this.aovMask) throw new Error('bake: turn the first-hit planes off first (setAovs([]), setDenoise(false), setReproject(null))');
+  var W = opts.width || this.width, H = opts.height || this.height;
+  var frames = opts.frames === undefined ? 64 : opts.frames;
+  var t = this.sceneTriangles;
+  var f = t instanceof ArrayBuffer ? new Float32Array(t) : new Float32Array(t.buffer, t.byteOffset, Math.floor(t.byteLength / 4));
+  var n = Math.floor(f.length / 32);
+  var positions = new Float32Array(9 * n), normals = new Float32Array(9 * n), uvs = this.lightmapUvs;
+  var own = !uvs || uvs.length !== 6 * n;
+  if (own) uvs = new Float32Array(6 * n);
+  for (var i = 0; i < n; i++)
+    for (var c = 0; c < 3; c++) {
+      for (var k = 0; k < 3; k++) {
+        positions[9 * i + 3 * c + k] = f[32 * i + 4 * c + k];
+        normals[9 * i + 3 * c + k] = f[32 * i + 12 + 4 * c + k];
+      }
+      if (own) { uvs[6 * i + 2 * c] = f[32 * i + 24 + 2 * c]; uvs[6 * i + 2 * c + 1] = f[32 * i + 25 + 2 * c]; }
+    }
+  var surface = require('./bake').rasterise(positions, normals, uvs, W, H);
+  this.stop();
+  if (W !== this.width || H !== this.height) this.resize(W, H);
+  this.addon.uploadBakeSurface(this.ctx, surface.texels, W, H);
+  var out = new Float32Array(W * H * 4);
+  try {
+    this.addon.writeOutput(this.ctx, out);                              // uncovered texels read as zeros
+    this.addon.dispatchBake(this.ctx, { firstFrame: 0, bias: opts.bias === undefined ? 1e-6 : opts.bias }, frames);
+    if (opts.dilate > 0) this.addon.bakeDilate(this.ctx, opts.dilate, out);
+    else this.addon.readOutput(this.ctx, out);
+  } finally {
+    this.addon.uploadBakeSurface(this.ctx, null, 0, 0);
+  }
+  this.lastBake = { width: W, height: H, frames: frames, covered: surface.covered };
+  this.reprojectFrom = null;
+  this.frameIndex = 0;                      // the output buffer holds a lightmap now: a camera's accumulation starts over
   return out;
 };
 

@@ -93,6 +93,8 @@ function processNode(gltf, node, allTriangles, allMaterials, allLights, world, a
     node.mesh.primitives.forEach(function (prim) {
       var position = prim.attributes.POSITION.value, normal = prim.attributes.NORMAL.value;
       var uv = prim.attributes.TEXCOORD_0 ? prim.attributes.TEXCOORD_0.value : undefined;
+      // the lightmap coordinates a bake rasterises (Renderer.bake): glTF's second set, or the first where a file has only one
+      var uvLight = prim.attributes.TEXCOORD_1 ? prim.attributes.TEXCOORD_1.value : uv;
       var tp = new Float32Array(position.length), tn = new Float32Array(normal.length);
       for (var i = 0; i < position.length; i += 3) {
         var p = M.transformMat4(M.vec3(position[i], position[i + 1], position[i + 2]), world);
@@ -109,6 +111,10 @@ function processNode(gltf, node, allTriangles, allMaterials, allLights, world, a
       var morphed = morphInstance && prim.targets && prim.targets.length && prim.indices;
       tris.forEach(function (t, k) {
         t.materialIndex = allMaterials.length - 1; t.group = nodeIndex;
+        if (uvLight && prim.indices) {
+          var lx = prim.indices.value, l0 = lx[3 * k] * 2, l1 = lx[3 * k + 1] * 2, l2 = lx[3 * k + 2] * 2;
+          t.lightmapUv = [uvLight[l0], uvLight[l0 + 1], uvLight[l1], uvLight[l1 + 1], uvLight[l2], uvLight[l2 + 1]];
+        }
         if (skinned) {
           var ix = prim.indices.value;
           t.skin = { instance: skinInstance, vertices: [ix[3 * k], ix[3 * k + 1], ix[3 * k + 2]],
@@ -147,7 +153,7 @@ function untagGroups(triangles) {
 }
 
 /** The same ride for the skin: every triangle's PRE-SORT index in a second padding word (byte 92, _p5, behind n2), read back and
- *  zeroed after the build. Only written when the file has a skinned primitive. */
+ *  zeroed after the build. Only written when the file has a skinned or morphed primitive, or lightmap coordinates to carry. */
 var PRESORT_WORD = 23;
 function tagPresort(triangles) {
   var u = new Uint32Array(triangles);
@@ -157,6 +163,17 @@ function untagPresort(triangles) {
   var u = new Uint32Array(triangles), at = new Uint32Array(u.length / 32);
   for (var i = 0; i < at.length; i++) { at[i] = u[i * 32 + PRESORT_WORD]; u[i * 32 + PRESORT_WORD] = 0; }
   return at;
+}
+
+/** The lightmap coordinates of a prepared scene (Renderer.bake): per triangle in the uploaded (reordered) order, its three corners'
+ *  TEXCOORD_1 (TEXCOORD_0 where the primitive has no second set; zeros where it has neither), 6 floats each. */
+function lightmapList(allTriangles, presort) {
+  var out = new Float32Array(presort.length * 6);
+  for (var i = 0; i < presort.length; i++) {
+    var uv = allTriangles[presort[i]].lightmapUv;
+    if (uv) out.set(uv, 6 * i);
+  }
+  return out;
 }
 
 /** The skin list of a prepared scene (Renderer.setSkin): the uploaded indices of the skinned triangles, ascending, and three 32-byte
@@ -287,7 +304,8 @@ function sceneCameras(gltf, world) {
  *  inverseBind, meshWorldInverse, jointBase } (opts.skins === false, or a file without skins: none of them, and every blob the
  *  same bytes). A file with morph targets also returns morphTriangles, morphRowStart, morphDeltas (morphList), morphTargets (the
  *  targets of all mesh instances together) and morphs: per morphed node { node, targetBase, nTargets, weights (its defaults) }
- *  (opts.morphs === false, or a file without targets: none of them). cameras: the file's cameras (sceneCameras; [] without any). */
+ *  (opts.morphs === false, or a file without targets: none of them). lightmapUvs: per uploaded triangle its corners' lightmap
+ *  coordinates (lightmapList; a file without texture coordinates: undefined). cameras: the file's cameras (sceneCameras; [] without any). */
 function prepareScene(gltf, opts) {
   var alphaCutout = !!(opts && opts.alphaCutout), alphaBlend = !!(opts && opts.alphaBlend);
   var packed = require('./atlas').packing(gltf, { keepAlpha: alphaCutout || alphaBlend });
@@ -331,10 +349,11 @@ function prepareScene(gltf, opts) {
   if (grouped) tagGroups(triangles, allTriangles);
   var skinned = allTriangles.some(function (t) { return !!t.skin; });
   var morphed = allTriangles.some(function (t) { return !!t.morph; });
-  if (skinned || morphed) tagPresort(triangles);
+  var lightmapped = allTriangles.some(function (t) { return !!t.lightmapUv; });
+  if (skinned || morphed || lightmapped) tagPresort(triangles);
   var bvh = a.buildBvh(triangles);
   var triangleGroups = grouped ? untagGroups(triangles) : undefined;
-  var presort = skinned || morphed ? untagPresort(triangles) : undefined;
+  var presort = skinned || morphed || lightmapped ? untagPresort(triangles) : undefined;
   var skin = skinned ? skinList(allTriangles, presort) : undefined;
   var morph = morphed ? morphList(allTriangles, presort) : undefined;
   var lights = a.emissiveLights(triangles, materials, pack.packLights(allLights));
@@ -349,6 +368,7 @@ function prepareScene(gltf, opts) {
     morphTriangles: morph ? morph.triangles : undefined, morphRowStart: morph ? morph.rowStart : undefined,
     morphDeltas: morph ? morph.deltas : undefined, morphTargets: morph ? morphTargets : undefined,
     morphs: morph ? morphs.filter(Boolean) : undefined,
+    lightmapUvs: lightmapped ? lightmapList(allTriangles, presort) : undefined,
     atlas: packed.texture,
     cameras: sceneCameras(gltf, world),
     counts: { triangles: allTriangles.length, materials: allMaterials.length, bvhNodes: bvh.nodes.byteLength / pack.BVH_NODE_SIZE,

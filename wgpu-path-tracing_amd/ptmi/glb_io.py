@@ -65,6 +65,7 @@ def encode_png(pixels, color_type=6, filters=None, palette=None, trns=None, dept
 
 def write_glb(path, meshes, nodes, materials, lights=None, images=None, textures=None, skins=None, animations=None, cameras=None):
     """meshes: list of dicts {positions (N,3), normals (N,3), uvs (N,2) or None, indices (M,), material or None,
+    uvs1 (N,2) or absent: TEXCOORD_1, the lightmap coordinates,
     joints (N,4) and weights (N,4) or absent: JOINTS_0 as uint16 and WEIGHTS_0 as float32,
     targets or absent: morph targets, a list of dicts {positions (N,3) or None, normals (N,3) or None}, morph_weights or absent: the
     mesh's default weights};
@@ -98,6 +99,8 @@ def write_glb(path, meshes, nodes, materials, lights=None, images=None, textures
                  "NORMAL": add(np.asarray(m["normals"], np.float32), 34962, 5126, "VEC3")}
         if m.get("uvs") is not None:
             attrs["TEXCOORD_0"] = add(np.asarray(m["uvs"], np.float32), 34962, 5126, "VEC2")
+        if m.get("uvs1") is not None:
+            attrs["TEXCOORD_1"] = add(np.asarray(m["uvs1"], np.float32), 34962, 5126, "VEC2")
         if m.get("joints") is not None:
             attrs["JOINTS_0"] = add(np.asarray(m["joints"], np.uint16), 34962, 5123, "VEC4")
             attrs["WEIGHTS_0"] = add(np.asarray(m["weights"], np.float32), 34962, 5126, "VEC4")

@@ -55,6 +55,7 @@ EXPORTS = [
     "ptmi_set_skin", "ptmi_pose_skin", "ptmi_skin_status", "ptmi_multi_set_skin", "ptmi_multi_pose_skin", "ptmi_multi_skin_status",
     "ptmi_set_morph", "ptmi_pose_morph", "ptmi_morph_status", "ptmi_multi_set_morph", "ptmi_multi_pose_morph", "ptmi_multi_morph_status",
     "ptmi_set_projections", "ptmi_get_projections", "ptmi_multi_set_projections", "ptmi_multi_get_projections",
+    "ptmi_upload_bake_surface", "ptmi_dispatch_bake", "ptmi_bake_status", "ptmi_bake_dilate", "ptmi_debug_bake_rays",
 ]
 MULTI_LOOPBACK = 1
 MULTI_PLANE_MOMENTS, MULTI_PLANE_OUTPUT = 0x100, 0x200      # gather_planes: with the AOV_* bits
@@ -273,6 +274,18 @@ class AlphaBlendStatus(ctypes.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
+class BakeParams(ctypes.Structure):
+    """ptmi_bake_params (include/ptmi.h ptmi_dispatch_bake)"""
+    _fields_ = [("first_frame", ctypes.c_uint32), ("bias", ctypes.c_float), ("reserved", ctypes.c_uint32 * 2)]
+
+
+class BakeStatus(ctypes.Structure):
+    _fields_ = [("present", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("covered", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class Stats(ctypes.Structure):
     _fields_ = [("paths", ctypes.c_uint64), ("segments", ctypes.c_uint64), ("shadow_rays", ctypes.c_uint64),
                 ("dispatches", ctypes.c_uint64), ("frames", ctypes.c_uint64),
@@ -325,6 +338,14 @@ _SHARED = {
     "set_morph": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32],
     "pose_morph": [ctypes.c_void_p, ctypes.c_uint32], "morph_status": [ctypes.c_void_p],
     "set_projections": [ctypes.c_uint32], "get_projections": [ctypes.POINTER(ctypes.c_uint32)],
+}
+# lightmap baking (include/ptmi.h ptmi_upload_bake_surface ...): a single context's calls, arguments after the handle
+_BAKE = {
+    "ptmi_upload_bake_surface": [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32],
+    "ptmi_dispatch_bake": [ctypes.c_void_p, ctypes.c_uint32],
+    "ptmi_bake_status": [ctypes.c_void_p],
+    "ptmi_bake_dilate": [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t],
+    "ptmi_debug_bake_rays": [ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 6,
 }
 _lib = None
 
@@ -399,6 +420,9 @@ def load():
         L.ptmi_normal_matrix.restype = None
         L.ptmi_normal_matrix.argtypes = [vp, vp]
         L.ptmi_debug_read_triangles.argtypes = [vp, u32, u32, vp]
+        for name, args in _BAKE.items():                        # (a tool that loads an older build of the ABI takes them off EXPORTS)
+            if name in EXPORTS:
+                getattr(L, name).argtypes = [vp] + args
         _lib = L
     return _lib
 
@@ -985,6 +1009,51 @@ class Context(_Handle):
         o, d = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
         self._ck(self.L.ptmi_debug_center_rays(self.h, _p(camera), _p(o), _p(d), o.size))
         return o, d
+
+    # -- lightmap baking (include/ptmi.h ptmi_upload_bake_surface, ptmi_dispatch_bake) ---------------------------
+    @staticmethod
+    def _bake_params(first_frame, bias, reserved):
+        """None where every argument is its default: the call then passes NULL"""
+        if first_frame == 0 and bias is None and tuple(reserved) == (0, 0):
+            return None
+        return ctypes.byref(BakeParams(first_frame, 1e-6 if bias is None else bias, (ctypes.c_uint32 * 2)(*reserved)))
+
+    def upload_bake_surface(self, texels, width=None, height=None):
+        """texels: (H, W) layout.BAKE_TEXEL records (ptmi.bake.rasterise makes them), the context's size; None removes the surface.
+        width / height override what the array's shape says (for tests)."""
+        if texels is None:
+            self._ck(self.L.ptmi_upload_bake_surface(self.h, None, 0, 0))
+            return
+        t = np.ascontiguousarray(texels, layout.BAKE_TEXEL)
+        assert t.ndim == 2, "a bake surface is an (H, W) array of BAKE_TEXEL records"
+        h, w = t.shape
+        self._ck(self.L.ptmi_upload_bake_surface(self.h, _p(t), w if width is None else width, h if height is None else height))
+
+    def dispatch_bake(self, n_frames=1, first_frame=0, bias=None, reserved=(0, 0)):
+        """n_frames frames of every covered texel from first_frame on, folded into the output buffer read as a lightmap. bias None:
+        the default, 1e-6. Asynchronous."""
+        self._ck(self.L.ptmi_dispatch_bake(self.h, self._bake_params(first_frame, bias, reserved), n_frames))
+
+    def bake_status(self):
+        st = BakeStatus()
+        self._ck(self.L.ptmi_bake_status(self.h, ctypes.byref(st)))
+        return st
+
+    def bake_dilate(self, passes=1, n_floats=None):
+        """the gutter-filled copy of the output buffer, (H, W, 4) float32: rgb, and w = 1 covered / 2 filled / 0 empty. n_floats
+        overrides the count passed (for tests)."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._ck(self.L.ptmi_bake_dilate(self.h, passes, _p(out), out.size if n_floats is None else n_floats))
+        return out
+
+    def debug_bake_rays(self, xs, ys, frames, first_frame=0, bias=None, reserved=(0, 0)):
+        """the first ray of texel (xs[i], ys[i]) at frames[i]: origins, directions (n, 3) float32 and RNG states (n,) uint32"""
+        xs, ys, frames = (np.ascontiguousarray(a, np.uint32) for a in (xs, ys, frames))
+        n = len(xs)
+        o, d, rng = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
+        self._ck(self.L.ptmi_debug_bake_rays(self.h, self._bake_params(first_frame, bias, reserved), n, _p(xs), _p(ys), _p(frames),
+                                             _p(o), _p(d), _p(rng)))
+        return o, d, rng
 
     # -- motion: reprojection across a geometry edit (include/ptmi.h ptmi_set_motion) ---------------------------
     def set_motion(self, on=True):
