@@ -1,8 +1,8 @@
 """Adaptive sampling on the GPU (include/ptmi.h ptmi_dispatch_adaptive) against tests/adaptive_ref.py, bit for bit: radiance and the
 moments plane (hence the counts) against the model fed the oracle's per-path radiance; the first-hit planes against what a plain
 dispatch of count[pixel] frames leaves at each pixel (tests/aov_ref.py restates the normals in float64, so the bit-exact reference
-for a plane folded per pixel in frame order is the plain dispatch; that reference is this code base itself, but k_accumulate_aov and
-k_ad_accumulate_aov are one body (fold_aov in csrc/pipeline.hip) over two pixel sources: what tests/test_gpu_aov.py pins for the plain
+for a plane folded per pixel in frame order is the plain dispatch; that reference is this code base itself, but k_fold_aov<DensePixels> and
+k_fold_aov<ListedPixels> are one body (fold_aov in csrc/pipeline.hip) over two pixel sources: what tests/test_gpu_aov.py pins for the plain
 fold against tests/aov_ref.py holds for both walks, and this test pins the listed source). Also the counters, the batch and
 round splits, bands and strips, the life cycle and errors, and the Node binding."""
 import json

@@ -22,7 +22,7 @@ import numpy as np
 import scene_update_ref as ref
 
 WORD = 64                             # triangles per ballot word
-TILE_WORDS = 1024                     # csrc/scene_rebuild.hip TILE_WORDS
+TILE_WORDS = 1024                     # csrc/pt_ballot_list.h TILE_WORDS
 TILE = WORD * TILE_WORDS              # 65 536 triangles per tile
 LEAF_MAX_TRIS = ref.LEAF_MAX_TRIS
 LIGHT_EMISSIVE = 0                    # ptmi.layout.LIGHT_EMISSIVE

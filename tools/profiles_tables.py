@@ -15,6 +15,11 @@ def load(name):
     return json.load(open(p)) if os.path.exists(p) else None
 
 
+# how rocprofv3 names the kernels of a stage: today's names (templates: "name<") and the ones the committed CSVs of earlier rounds carry
+STAGE_KERNELS = {"k_shade": ("k_shade(",), "k_raygen": ("k_raygen(", "k_first_rays<"), "k_accumulate": ("k_accumulate(", "k_fold_radiance<"),
+                 "k_scatter2": ("k_scatter2(",), "k_scatter": ("k_scatter(",), "k_tile_sums": ("k_tile_sums(",)}
+
+
 def n(x, d=0):
     s = f"{x:,.{d}f}".replace(",", " ")
     return s
@@ -42,7 +47,7 @@ for c in (1, 3, 2, 4):
         for row in csv.DictReader(open(p)):
             nm = row["Name"]
             key = ("shadow" if "ShadowIO" in nm else "extend") if ("k_trace" in nm or "k_own" in nm) else \
-                  next((k for k in ("k_shade", "k_raygen", "k_accumulate", "k_scatter2", "k_scatter", "k_tile_sums") if k + "(" in nm), None)
+                  next((k for k in STAGE_KERNELS if any(a in nm for a in STAGE_KERNELS[k])), None)
             if key:
                 stats[key] = (int(row["Calls"]), float(row["TotalDurationNs"]) / 1e6, float(row["AverageNs"]) / 1e3)
     print("| kernel | launches per step | ms per step (events) | µs per launch (events) | rocprofv3: calls, total ms, mean µs | B/unit | units per launch | achieved GB/s | of 8 TB/s | counters: 2·FETCH+WRITE per launch | counter GB/s |")

@@ -189,7 +189,7 @@ int ptmi_debug_bake_rays(ptmi_ctx *c, const ptmi_bake_params *params, uint32_t n
     HIP_TRY(c, hipMemcpyAsync(dx, xs, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(dy, ys, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(df, frames, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    pt_launch_bake_rays(c->stream, c->d_bake_texels, c->W, bp.bias, n, dx, dy, df, ln.paths);
+    pt_launch_raygen_list(c->stream, BakeSurface{c->d_bake_texels, bp.bias}, c->W, n, dx, dy, df, ln.paths);
     std::vector<float4> o(n), d(n);
     HIP_TRY(c, hipMemcpyAsync(o.data(), ln.paths.O, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(d.data(), ln.paths.D, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));

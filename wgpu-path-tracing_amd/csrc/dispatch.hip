@@ -108,15 +108,13 @@ struct Timed {
 // map (with ap; ptmi_multi_dispatch_adaptive): the round selects from the whole-frame flag map and never restarts (pt_adaptive_flags
 // has); count_call = false: a further round of one call, which ptmi_stats.dispatches has already counted.
 // bake (ptmi_dispatch_bake, which has checked it: bake_check; no camera, no ap): n_frames frames of every covered texel of the surface
-// in place, from bake->first_frame. A third raygen and a third pair of folds; a batch's pixels are the covered texels.
+// in place, from bake->first_frame: the surface is the batch's ray source and its covered texels are the batch's pixels.
 int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_adaptive_params *ap, uint32_t rounds,
              const DevFlagMap *map = nullptr, bool count_call = true, const ptmi_bake_params *bake = nullptr) {
     int rc = check_ready(c, true);
     if (rc) return rc;
-    static const ptmi_camera no_camera{};                       // what a bake's raygen is handed and never reads
     uint32_t proj = PTMI_PROJ_PERSPECTIVE;
-    if (bake) cam = &no_camera;
-    else {
+    if (!bake) {
         if (!cam) return fail(c, PTMI_E_INVALID, "camera is NULL");
         if (cam->width != c->W || cam->height != c->H)
             return fail(c, PTMI_E_INVALID, "camera says %ux%u but the output buffer is %ux%u", cam->width, cam->height, c->W, c->H);
@@ -207,13 +205,13 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         unsigned long long *const ct = c->d_counters;
         uint32_t *const qlen = &c->d_control[kCwQueue], *const slen = &c->d_control[kCwShadow];    // queue lengths by bounce; shadow, by parity
         if (ap && !map && first_frame == 0u) { pt_launch_adaptive_restart(ms, blocks, band, mom); c->ad_rounds = 0; }
-        // a batch: fb frames of every pixel from frame0 on, or (ap) of every listed pixel from its own count on
+        const DevRays rays = bake ? DevRays{BakeSurface{c->d_bake_texels, bake->bias}} : DevRays{CameraSource{cam, proj}};
+        // a batch: fb frames of every pixel (bake: covered texel) from frame0 on, or (ap) of every listed pixel from its own count on
         auto batch = [&](uint32_t frame0, uint32_t fb) -> int {
-            const DevPixels px = ap ? DevPixels{band, 0u, c->ad.list, &c->d_control[kCwAdActive], mom, &ct[kCtAdTraced], nullptr, nullptr, 0u, 0.0f}
-                               : bake ? DevPixels{band, frame0, nullptr, nullptr, nullptr, nullptr, c->d_bake_texels, c->d_bake_covered,
-                                                  c->bake_covered, bake->bias}
-                                      : DevPixels{band, frame0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0.0f};
-            { Timed t(c, kRaygen, t3, ms); pt_launch_raygen(ms, blocks, *cam, proj, px, fb, bp, &qlen[0]); }
+            const DevPixels px = ap     ? DevPixels{ListedPixels{band, c->ad.list, &c->d_control[kCwAdActive], mom, &ct[kCtAdTraced]}}
+                                 : bake ? DevPixels{BakedPixels{band, c->d_bake_covered, c->bake_covered, frame0}}
+                                        : DevPixels{DensePixels{band, frame0}};
+            { Timed t(c, kRaygen, t3, ms); pt_launch_raygen(ms, blocks, rays, px, fb, bp, &qlen[0]); }
             int cur = 0;
             for (uint32_t b = 0; b < maxb; b++) {
                 const bool tail = b > rb;                                   // the state is in the tail arrays
@@ -263,8 +261,7 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         };
         if (ap) {
             for (uint32_t r = 0; r < rounds; r++) {
-                if (map) pt_launch_adaptive_list_map(ms, blocks, band, *ap, mom, *map, c->ad);
-                else pt_launch_adaptive_list(ms, blocks, band, *ap, mom, c->ad);
+                pt_launch_adaptive_list(ms, blocks, band, *ap, mom, map, c->ad);
                 for (uint32_t f0 = 0; f0 < n_frames; f0 += F)
                     if ((rc = batch(0u, std::min(F, n_frames - f0)))) return rc;
             }

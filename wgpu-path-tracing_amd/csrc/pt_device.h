@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <initializer_list>
+#include <variant>
 #include "ptmi_layout.h"
 #include "ptmi.h"
 
@@ -319,26 +320,47 @@ inline uint32_t pt_variant_code(const TraverseConfig &cfg) { return (uint32_t)cf
 size_t pt_spill_bytes(int blocks);
 
 // ---- launchers (each enqueues on `s`; grids are persistent, sized by the caller) ----
-// The pixels a batch walks, in ray generation and the three folds: every pixel of the band from frame `frame0` on (list == NULL:
-// plain dispatch), or the *n_active band-local pixels of `list`, each from its own frame index mom[pixel].z (adaptive dispatch).
-// n_frames frames of each: path k * entries + j is frame k of entry j.
-struct DevPixels {
+// A batch has two axes: the pixels it walks and where each path's first ray comes from. Ray generation and the three folds are each one
+// kernel over both (pipeline.hip); the launchers below turn the run-time choice into the instantiation.
+//
+// The pixels, as the kernels see them. A source answers three questions: how many entries, the band-local pixel (local row * width + x)
+// of entry j, the first frame of the pixel at frame index oi; and it may count the batch's paths. n_frames frames of each entry: path
+// k * entries + j is frame first_frame + k of entry j. (Device code only: the answers read device memory.)
+struct DensePixels {                    // every pixel of the band, all from frame0 (ptmi_dispatch)
     DevBand band; uint32_t frame0;
-    const uint32_t *list, *n_active; const float4 *mom;
-    unsigned long long *traced;         // listed: the word kCtAdTraced, += the batch's paths (a plain dispatch counts its paths on the host)
-    // a bake (ptmi_dispatch_bake; bake_texels NULL: not one): the n_covered covered texels of `covered` (ascending frame indices; the
-    // band is the whole frame), every one from frame0 on, each path starting at its texel's record instead of the camera
-    const float4 *bake_texels; const uint32_t *covered; uint32_t n_covered; float bias;
+    __device__ uint32_t entries() const { return band.rows * band.width; }
+    __device__ uint32_t pixel(uint32_t j) const { return j; }
+    __device__ uint32_t first_frame(size_t) const { return frame0; }
+    __device__ void count_paths(uint32_t) const {}                  // (a plain dispatch counts its paths on the host)
 };
-// *count_out = entries * n_frames. proj (here and below): the camera's projection, PTMI_PROJ_*, as pt_check_camera resolved it: the
-// pinhole's kernels for PTMI_PROJ_PERSPECTIVE, which is all a context with ptmi_set_projections off ever passes
-void pt_launch_raygen(hipStream_t s, int blocks, const ptmi_camera &cam, uint32_t proj, DevPixels px, uint32_t n_frames, DevPaths p,
-                      uint32_t *count_out);
-void pt_launch_raygen_list(hipStream_t s, const ptmi_camera &cam, uint32_t proj, uint32_t n, const uint32_t *xs,
-                           const uint32_t *ys, const uint32_t *frames, DevPaths p);
-// the bake rays of n texels (xs, ys) at `frames` (ptmi_debug_bake_rays): path i = the ray of texel i, zeros for an uncovered texel
-void pt_launch_bake_rays(hipStream_t s, const float4 *texels, uint32_t width, float bias, uint32_t n, const uint32_t *xs,
-                         const uint32_t *ys, const uint32_t *frames, DevPaths p);
+struct ListedPixels {                   // the *n_active pixels of the list, each from its own count mom[oi].z (ptmi_dispatch_adaptive)
+    DevBand band; const uint32_t *list, *n_active; const float4 *mom;
+    unsigned long long *traced;         // the word kCtAdTraced, += the batch's paths (ptmi_stats.paths)
+    __device__ uint32_t entries() const { return *n_active; }
+    __device__ uint32_t pixel(uint32_t j) const { return list[j]; }
+    __device__ uint32_t first_frame(size_t oi) const { return (uint32_t)mom[oi].z; }
+    __device__ void count_paths(uint32_t paths) const { atomicAdd(traced, (unsigned long long)paths); }
+};
+struct BakedPixels {                    // the n covered texels of a bake surface (ascending frame indices; the band is the whole
+    DevBand band; const uint32_t *covered; uint32_t n, frame0;     // frame), all from frame0 (ptmi_dispatch_bake)
+    __device__ uint32_t entries() const { return n; }
+    __device__ uint32_t pixel(uint32_t j) const { return covered[j]; }
+    __device__ uint32_t first_frame(size_t) const { return frame0; }
+    __device__ void count_paths(uint32_t) const {}
+};
+using DevPixels = std::variant<DensePixels, ListedPixels, BakedPixels>;
+// Where a path's first ray comes from, as the host names it: the camera (proj: its projection, PTMI_PROJ_*, as pt_check_camera resolved
+// it; PTMI_PROJ_PERSPECTIVE is all a context with ptmi_set_projections off ever passes), or the records of a bake surface
+// (ptmi_upload_bake_surface; a path starts at its texel's record, `bias` along its first direction).
+struct CameraSource { const ptmi_camera *cam; uint32_t proj; };
+struct BakeSurface { const float4 *texels; float bias; };
+using DevRays = std::variant<CameraSource, BakeSurface>;
+// the first rays of a batch: *count_out = entries * n_frames
+void pt_launch_raygen(hipStream_t s, int blocks, const DevRays &rays, const DevPixels &px, uint32_t n_frames, DevPaths p, uint32_t *count_out);
+// the first rays of n pixels (xs, ys) of a frame `width` wide at `frames` (ptmi_debug_raygen, ptmi_debug_bake_rays): path i = the ray
+// of pixel i; a bake surface answers zeros for an uncovered texel
+void pt_launch_raygen_list(hipStream_t s, const DevRays &rays, uint32_t width, uint32_t n, const uint32_t *xs, const uint32_t *ys,
+                           const uint32_t *frames, DevPaths p);
 // gutter fill (bake.hip, ptmi_bake_dilate): a = the masked copy of `out` (rgb of covered texels, w = 1; zeros elsewhere), then `passes`
 // passes of the rule of include/ptmi.h ping-ponging between a and b; returns the plane that holds the result
 float4 *pt_launch_bake_dilate(hipStream_t s, uint32_t W, uint32_t H, uint32_t passes, const float4 *texels, const float4 *out,
@@ -405,12 +427,13 @@ void pt_launch_compact(hipStream_t s, int tiles, const uint32_t *queue, const ui
                        unsigned long long *stats, uint32_t bounce, int do_scatter);
 // the three folds of a batch over its pixels (DevPixels), each pixel's frames in ascending order. Listed pixels read their frame index
 // from mom.z, which the moments fold moves on: it goes last.
-void pt_launch_accumulate(hipStream_t s, int blocks, DevPixels px, uint32_t n_frames, const float *L, uint32_t l_stride, float4 *out);
-// the first-hit planes (ptmi_set_aovs) from the batch's bounce-0 records; a NULL plane is not written
-void pt_launch_accumulate_aov(hipStream_t s, int blocks, DevPixels px, uint32_t n_frames, const float4 *rec,
+void pt_launch_accumulate(hipStream_t s, int blocks, const DevPixels &px, uint32_t n_frames, const float *L, uint32_t l_stride, float4 *out);
+// the first-hit planes (ptmi_set_aovs) from the batch's bounce-0 records; a NULL plane is not written. Not over baked pixels: a bake is
+// refused while these planes are on (bake.hip bake_check)
+void pt_launch_accumulate_aov(hipStream_t s, int blocks, const DevPixels &px, uint32_t n_frames, const float4 *rec,
                               const ptmi_triangle *tris, uint32_t n_tris, float4 *albedo, float4 *normal, uint2 *ids);
-// the sample-moments plane (ptmi_set_moments) from the batch's per-path radiance; listed pixels: mom is px.mom
-void pt_launch_accumulate_moments(hipStream_t s, int blocks, DevPixels px, uint32_t n_frames, const float *L, uint32_t l_stride,
+// the sample-moments plane (ptmi_set_moments) from the batch's per-path radiance; listed pixels: mom is the source's mom
+void pt_launch_accumulate_moments(hipStream_t s, int blocks, const DevPixels &px, uint32_t n_frames, const float *L, uint32_t l_stride,
                                   float4 *mom);
 // adaptive sampling (ptmi_dispatch_adaptive; kernels in pipeline.hip): the context's buffers of a round
 struct DevAdaptive {
@@ -422,9 +445,7 @@ struct DevAdaptive {
 };
 uint32_t pt_adaptive_tiles(uint32_t npix);
 void pt_launch_adaptive_restart(hipStream_t s, int blocks, DevBand band, float4 *mom);          // every count of the band back to 0
-// select + list build: ad.ballot, ad.list and the two control words of this round from the moments plane
-void pt_launch_adaptive_list(hipStream_t s, int blocks, DevBand band, const ptmi_adaptive_params &ap, const float4 *mom, DevAdaptive ad);
-// (ray generation and the folds of a round: pt_launch_raygen / pt_launch_accumulate* with the list as their DevPixels)
+// (ray generation and the folds of a round: pt_launch_raygen / pt_launch_accumulate* over the list as ListedPixels)
 void pt_launch_adaptive_status(hipStream_t s, int blocks, DevBand band, const float4 *mom, DevAdaptive ad);
 // Adaptive rounds over several devices (ptmi_multi_dispatch_adaptive with neighbourhood = 1): the NOISY flag of every pixel of the frame,
 // one byte each, as the devices' shares one after the other. Share r holds the rows of part r (DevBand::row_of) of a frame dealt out
@@ -440,9 +461,10 @@ struct DevFlagMap {
 };
 // flags[band-local pixel] = the pixel is NOISY (the rule of k_ad_select, per pixel)
 void pt_launch_adaptive_flags(hipStream_t s, int blocks, DevBand band, const ptmi_adaptive_params &ap, const float4 *mom, uint8_t *flags);
-// pt_launch_adaptive_list with the neighbourhood looked up in the whole-frame map instead of the band's own moments
-void pt_launch_adaptive_list_map(hipStream_t s, int blocks, DevBand band, const ptmi_adaptive_params &ap, const float4 *mom, DevFlagMap fm,
-                                 DevAdaptive ad);
+// select + list build: ad.ballot, ad.list and the two control words of this round from the moments plane. fm: the neighbourhood is
+// looked up in the whole-frame map; NULL: in the band's own moments
+void pt_launch_adaptive_list(hipStream_t s, int blocks, DevBand band, const ptmi_adaptive_params &ap, const float4 *mom,
+                             const DevFlagMap *fm, DevAdaptive ad);
 // the denoiser (denoise.hip, ptmi_denoise): a prepass into guide / grad / cv, then `iterations` a-trous passes ping-ponging between
 // cv and tmp, the last remodulating into out. albedo NULL: no demodulation. cv is overwritten.
 struct DenoiseArgs {

@@ -8,14 +8,15 @@
 //   units     the builders' unit list: the triangles some reachable reference leaf lists, ascending. Every node of kRefWnodes is
 //             reachable (an upload numbers only those), so: one ballot word per 64 triangles, a leaf child ORs the bits of its range
 //             into at most two words (atomicOr: ranges of different leaves share words; the result does not depend on the order);
-//             then an ordered compaction in pipeline.hip's idiom: per-tile popcount totals, then every tile sums the totals in front
-//             of it, scans its own popcounts and each wave walks its 64 words. On the device path nothing per triangle crosses the bus.
+//             then the ordered list of the set bits (pt_ballot_list.h, the bodies the compaction of a bounce uses: per-tile popcount
+//             totals, then scatter_tile). On the device path nothing per triangle crosses the bus.
 //   build     scene_image.hip rebuild_own_image: the code an upload builds own leaves with (which builder, which limits, the 16-bit
 //             copies), reading the context's buffers; new buffers, the context untouched
 //   swap      every holder of the old pointers moves together: the SceneBuf table, DevScene and its device copy, the image header, the
 //             statistics, and the update plan, which described the old topology and is re-made here. The old buffers and the old plan are
 //             kept until the new plan stands, so a failure anywhere puts them back: the call is all-or-nothing.
 // Every kernel of one launch reads only what earlier launches wrote (scene_update.hip's rule): no hand-off inside a launch.
+#include "pt_ballot_list.h"
 #include "ptmi_ctx.h"
 #include "wide_node.h"
 
@@ -24,8 +25,6 @@
 
 namespace {
 
-constexpr int TILE_WORDS = 1024;             // ballot words (x 64 triangles) per tile = threads per workgroup
-constexpr int TILE_WAVES = TILE_WORDS / 64;
 constexpr int TB = 256;
 
 __device__ __forceinline__ void flag_range(uint32_t ref, uint32_t n_tris, unsigned long long *words) {
@@ -51,67 +50,20 @@ __global__ void k_flag_root(uint32_t ref, uint32_t n_tris, unsigned long long *w
     if (ref != PT_REF_NONE && (ref & PT_REF_LEAF)) flag_range(ref, n_tris, words);
 }
 
-__global__ void __launch_bounds__(TILE_WORDS) k_unit_tile_sums(uint32_t nwords, const unsigned long long *__restrict__ words,
+__global__ void __launch_bounds__(TILE_WORDS) k_unit_tile_sums(uint32_t nwords, const uint64_t *__restrict__ words,
                                                                uint32_t *__restrict__ tile_sums) {
-    __shared__ uint32_t wsum[TILE_WAVES];
-    const uint32_t w = blockIdx.x * TILE_WORDS + threadIdx.x;
-    uint32_t c = w < nwords ? (uint32_t)__popcll(words[w]) : 0u;
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
-    if ((threadIdx.x & 63u) == 0u) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int i = 0; i < TILE_WAVES; i++) t += wsum[i];
-        tile_sums[blockIdx.x] = t;
-    }
+    tile_total(nwords, words, tile_sums);
 }
-
-// the set bits' positions, ascending, into which[]; their number into *count (the last tile writes it)
-__global__ void __launch_bounds__(TILE_WORDS) k_unit_scatter(uint32_t nwords, const unsigned long long *__restrict__ words,
+// the set bits' positions, ascending, into which[] (`cap` entries of room); their number into *count (the last tile writes it)
+__global__ void __launch_bounds__(TILE_WORDS) k_unit_scatter(uint32_t nwords, const uint64_t *__restrict__ words,
                                                              const uint32_t *__restrict__ tile_sums, uint32_t cap, uint32_t *__restrict__ which,
                                                              uint32_t *__restrict__ count) {
-    __shared__ uint32_t wtot[TILE_WAVES];
-    __shared__ uint32_t tile_base;
-    const uint32_t tile = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    // totals of the tiles in front of this one
-    uint32_t pre = 0;
-    for (uint32_t t = threadIdx.x; t < tile; t += TILE_WORDS) pre += tile_sums[t];
-    for (int off = 32; off > 0; off >>= 1) pre += __shfl_down(pre, off);
-    if (lane == 0) wtot[wave] = pre;
-    __syncthreads();
-    if (threadIdx.x == 0) { uint32_t t = 0; for (int i = 0; i < TILE_WAVES; i++) t += wtot[i]; tile_base = t; }
-    __syncthreads();
-    const uint32_t base0 = tile_base;
-    __syncthreads();
-    // exclusive scan of this tile's popcounts
-    const uint32_t w = tile * TILE_WORDS + threadIdx.x;
-    const unsigned long long m = w < nwords ? words[w] : 0ull;
-    const uint32_t c = (uint32_t)__popcll(m);
-    uint32_t inc = c;
-    for (int off = 1; off < 64; off <<= 1) { const uint32_t v = __shfl_up(inc, off); if (lane >= (uint32_t)off) inc += v; }
-    if (lane == 63u) wtot[wave] = inc;
-    __syncthreads();
-    uint32_t wbase = 0;
-    for (uint32_t i = 0; i < wave; i++) wbase += wtot[i];
-    const uint32_t my_off = base0 + wbase + inc - c;                  // where this lane's word starts
-    if (tile == gridDim.x - 1 && threadIdx.x == TILE_WORDS - 1) *count = my_off + c;
-    // the wave walks its 64 words: lane L keeps triangle 64 w + L iff bit L of word w is set, at the word's start + the set bits below L
-    const uint32_t mlo = (uint32_t)m, mhi = (uint32_t)(m >> 32);
-    const uint32_t w0 = tile * TILE_WORDS + wave * 64u;
-    for (uint32_t j = 0; j < 64u; j++) {
-        const uint32_t jlo = __shfl(mlo, (int)j), jhi = __shfl(mhi, (int)j), jbase = __shfl(my_off, (int)j);
-        const unsigned long long jm = ((unsigned long long)jhi << 32) | jlo;
-        if (jm == 0ull) continue;
-        if ((jm >> lane) & 1ull) {
-            const uint32_t at = jbase + (uint32_t)__popcll(jm & ((1ull << lane) - 1ull));
-            if (at < cap) which[at] = (w0 + j) * 64u + lane;
-        }
-    }
+    scatter_tile<false, true>(blockIdx.x, nwords, nullptr, words, tile_sums, which, count, TileStats{}, cap);
 }
 
 // The unit list of the loaded scene in device memory: *d_which (n_tris entries of room, owned by the caller's Scratch) and its length.
 int unit_list(ptmi_ctx *c, Scratch<uint32_t> &which, uint32_t &n_units) {
-    const uint32_t nt = c->sc.n_tris, nwords = (nt + 63u) / 64u, tiles = (nwords + TILE_WORDS - 1) / TILE_WORDS;
+    const uint32_t nt = c->sc.n_tris, nwords = (nt + 63u) / 64u, tiles = pt_ballot_tiles(nt);
     hipStream_t st = c->stream;
     Scratch<unsigned long long> words;
     Scratch<uint32_t> sums;                                          // the tile totals, then the count
@@ -123,8 +75,9 @@ int unit_list(ptmi_ctx *c, Scratch<uint32_t> &which, uint32_t &n_units) {
         k_flag_leaves<<<dim3((c->n_ref_wnodes + TB - 1) / TB), TB, 0, st>>>(c->n_ref_wnodes, c->sc.ref_wnodes, nt, words.p);
     else
         k_flag_root<<<1, 1, 0, st>>>(c->sc.ref_root_ref, nt, words.p);
-    k_unit_tile_sums<<<tiles, TILE_WORDS, 0, st>>>(nwords, words.p, sums.p);
-    k_unit_scatter<<<tiles, TILE_WORDS, 0, st>>>(nwords, words.p, sums.p, nt, which.p, sums.p + tiles);
+    const uint64_t *const bits = reinterpret_cast<const uint64_t *>(words.p);      // (atomicOr has no uint64_t form)
+    k_unit_tile_sums<<<tiles, TILE_WORDS, 0, st>>>(nwords, bits, sums.p);
+    k_unit_scatter<<<tiles, TILE_WORDS, 0, st>>>(nwords, bits, sums.p, nt, which.p, sums.p + tiles);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(&n_units, sums.p + tiles, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
