@@ -274,6 +274,82 @@ int ptmi_bake_status(ptmi_ctx *ctx, struct ptmi_bake_status *out);
 int ptmi_bake_dilate(ptmi_ctx *ctx, uint32_t passes, float *dst_rgba, size_t n_floats);
 int ptmi_debug_bake_rays(ptmi_ctx *ctx, const ptmi_bake_params *params, uint32_t n, const uint32_t *xs, const uint32_t *ys,
                          const uint32_t *frames, float *o3, float *d3, uint32_t *rng);
+
+/* ---- light probes: radiance gathered at points in free space -----------------------------------
+ * A probe answers "what light arrives at this point?", for the objects that move through a baked scene. The context's frame
+ * (ptmi_resize) is read as the probe ATLAS: with tile size N (a power of two, 4 ... 64; 8 is the practical minimum, see the errors
+ * below), cols = width / N and rows = height / N, probe i owns the N x N texels of tile (i % cols, i / cols), row 0 at the bottom as
+ * everywhere. A texel of a tile stands for a solid angle about the probe under the octahedral map below (the one DDGI atlases use).
+ *
+ * ptmi_upload_probes: count probes (ptmi_probe, ptmi_layout.h: position, enabled) with tile size `tile`. PTMI_E_INVALID, with the
+ * probes that were in place left in place: tile not a power of two in [4, 64]; the context's width or height not a multiple of tile
+ * (or no output buffer); count 0 or above cols * rows; an enabled probe whose position is not finite. The device keeps the records,
+ * the two tables below and the list of the frame indices of every texel of every enabled probe in ascending frame index, which is
+ * the order paths and folds walk them in. probes NULL removes the probes; so does a ptmi_resize to another size. Probes and a bake
+ * surface are independent state. Synchronises.
+ *
+ * ptmi_dispatch_probes: n_frames frames of every listed texel, from params->first_frame on, through the bounce loop of ptmi_dispatch
+ * exactly as ptmi_dispatch_bake runs it: batch sizing, the 2^32 limit, statistics over the listed texels, the moments fold while
+ * ptmi_set_moments is on, sky, medium, both alpha modes, edits and poses. Only the first ray differs. For texel (x, y) of an enabled
+ * probe at frame f, in the kernels' float32, each operation rounded once and none fused (pt_math.h):
+ *   rng = seed(x, y, f);  r1 = rand(rng);  r2 = rand(rng)                  the pinhole's two jitter draws, and nothing else
+ *   s = 2 / N (exact);  a = ((float)(x % N) + r1) * s - 1;  b = ((float)(y % N) + r2) * s - 1        sum, product, difference
+ *   w = (1 - |a|) - |b|
+ *   if (w < 0) { a' = copysign(1 - |b|, a);  b' = copysign(1 - |a|, b); } else { a' = a;  b' = b; }
+ *   raw = (a', b', w) in world axes;  origin = position;  dir = normalize(raw)
+ * It is pixel (x, y, f) of a pinhole camera with position = origin, forward = raw, fov = 0, aperture = 0: the same seed, draws and
+ * path, bit for bit (where no component of raw is a zero). Per sample the clamp is the reference's 2.5, and a texel of the output
+ * buffer holds the running mean of the incoming radiance over the texel's footprint. Frame first_frame = 0 overwrites. Texels of
+ * disabled probes and of tiles past count are neither read nor written.
+ * LIMIT: punctual lights are deltas and reach a probe only through later bounces - a ray cannot hit them, and there is no next-event
+ * sample at the probe itself. Emissive triangles and the sky are seen directly.
+ * params NULL: first_frame 0; the reserved words must be 0. PTMI_E_INVALID, with nothing enqueued or written and the statistics as
+ * they were: no probes in place, a first-hit plane on (ptmi_set_aovs mask non-zero), tile options that do not cover the whole frame,
+ * a non-zero reserved word. n_frames = 0 or no enabled probe: PTMI_OK, nothing written. Asynchronous, like ptmi_dispatch.
+ *
+ * THE TABLES depend on N only; they are built on the host in float64 with + - * / and sqrt alone and rounded once to float32. For
+ * texel t = ty * N + tx, its centre put through the map above: a = (tx + 0.5) * (2 / N) - 1, b likewise from ty, w, a', b' as above,
+ *   p = (a', b', w);  len = sqrt((a' a' + b' b') + w w);  d_t = p / len (three divisions)
+ *   dw_t = (4 / (N N)) / ((len len) len)                                    the map's Jacobian, du dv / |p|^3
+ *   every dw_t is then multiplied by (4 pi) / sum, the sum taken over ascending t from 0, pi = 3.141592653589793
+ *   basis[t][k] = Y_k(d_t) * dw_t, with (x, y, z) = d_t and
+ *     Y_0 = 0.28209479177387814
+ *     Y_1 = 0.4886025119029199 * y        Y_2 = 0.4886025119029199 * z        Y_3 = 0.4886025119029199 * x
+ *     Y_4 = (1.0925484305920792 * x) * y  Y_5 = (1.0925484305920792 * y) * z  Y_6 = 0.31539156525252005 * ((3 * z) * z - 1)
+ *     Y_7 = (1.0925484305920792 * x) * z  Y_8 = 0.5462742152960396 * (x * x - y * y)
+ * The rule is second order in 1 / N. Largest absolute SH9 coefficient error against the analytic value, N = 8 / 16 / 32 / 64:
+ * constant radiance 0.085 / 0.020 / 0.0050 / 0.0012, a clamped cosine 0.029 / 0.0053 / 0.0014 / 0.00034; N = 4 is allowed but
+ * coarse (1.4 on the constant).
+ * ptmi_debug_probe_tables (host only, no context): dir_dw4 = N * N * 4 floats (d_t, dw_t), basis9 = N * N * 9 floats; either may be
+ * NULL. Any power of two in [2, 64] (2 is the smallest irradiance tile's table); else PTMI_E_INVALID.
+ *
+ * ptmi_probe_sh: c[i][k][ch] = sum_t basis[t][k] * L_i[t][ch] over probe i's tile of the output buffer as it stands (owned or bound,
+ * read in place): count * 27 floats, k major and rgb minor; a disabled probe gives zeros. One wave per probe, in float32: lane l
+ * starts from +0 and takes texels t = l, l + 64, ... in ascending order, each term acc = acc + (basis * L) - a rounded product, then
+ * a rounded sum, never fused; then for s = 32, 16, ..., 1: v[l] = v[l] + v[l + s]; lane 0 holds the result. Synchronises.
+ * PTMI_E_INVALID: no probes in place, n_floats != count * 27.
+ *
+ * ptmi_probe_irradiance: per probe an m x m octahedral tile (m a power of two, 2 ... 16, m <= N; else PTMI_E_INVALID), texel j =
+ *   (1 / pi) * sum_t max(0, dot(n_j, d_t)) * dw_t * L_i[t][ch]
+ * with n_j the float32 direction d_j of the table built at tile m. This is E / pi, the unit a bake's texel has, so one shader term
+ * serves lightmap and probe. dst_rgba: count * m * m * 4 floats, probe major, then j = jy * m + jx; w = 1 for an enabled probe, and
+ * a disabled probe's texels are all zeros. In float32, one wave per output texel with the lanes splitting t as above:
+ *   c = fma(n.z, d.z, fma(n.y, d.y, n.x * d.x));  c = c > 0 ? c : 0;  wgt = c * dw_t;  acc = acc + (wgt * L)       nothing else fused
+ * then the same butterfly, and lane 0 writes acc * 0.318309886f. Synchronises. PTMI_E_INVALID: no probes, a bad m, a wrong n_floats.
+ *
+ * ptmi_debug_probe_rays: the first ray of texel (xs[i], ys[i]) at frames[i], as ptmi_debug_bake_rays returns a bake's; zeros for a
+ * texel of a disabled probe or of a tile past count; a texel outside the atlas is PTMI_E_INVALID.
+ * The ABI version stays 4: new calls only. */
+typedef struct ptmi_probe_params { uint32_t first_frame; uint32_t _reserved[3]; } ptmi_probe_params;
+struct ptmi_probe_status { uint32_t present, tile, count, enabled, texels; };
+int ptmi_upload_probes(ptmi_ctx *ctx, const ptmi_probe *probes, uint32_t count, uint32_t tile);
+int ptmi_dispatch_probes(ptmi_ctx *ctx, const ptmi_probe_params *params, uint32_t n_frames);
+int ptmi_probe_status(ptmi_ctx *ctx, struct ptmi_probe_status *out);
+int ptmi_probe_sh(ptmi_ctx *ctx, float *dst, size_t n_floats);
+int ptmi_probe_irradiance(ptmi_ctx *ctx, uint32_t m, float *dst_rgba, size_t n_floats);
+int ptmi_debug_probe_rays(ptmi_ctx *ctx, const ptmi_probe_params *params, uint32_t n, const uint32_t *xs, const uint32_t *ys,
+                          const uint32_t *frames, float *o3, float *d3, uint32_t *rng);
+int ptmi_debug_probe_tables(uint32_t tile, float *dir_dw4, float *basis9);
 /* Back-pressure for a caller that enqueues dispatches from a loop without reading results — a preview loop; the reference paces
  * itself on requestAnimationFrame (renderer.ts:456-473). Blocks until at most max_in_flight of this context's dispatches have
  * not yet finished on the device and reports how many still are (in_flight may be NULL). max_in_flight = 0xFFFFFFFF only polls.

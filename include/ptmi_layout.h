@@ -133,6 +133,15 @@ typedef struct ptmi_bake_texel {
 PTMI_STATIC_ASSERT(sizeof(ptmi_bake_texel) == 32, "a bake texel is two float4");
 PTMI_STATIC_ASSERT(offsetof(ptmi_bake_texel, normal) == 16, "BakeTexel.normal");
 
+/* A light probe (include/ptmi.h, ptmi_upload_probes): a point in free space whose incoming radiance is gathered into one tile of the
+ * probe atlas. No counterpart in the reference. 16 B, read by the device as one float4. */
+typedef struct ptmi_probe {
+    float position[3];              /* 0   world space */
+    uint32_t enabled;               /* 12  0: the probe's tile is never traced and never written; non-zero: traced */
+} ptmi_probe;
+PTMI_STATIC_ASSERT(sizeof(ptmi_probe) == 16, "a probe is one float4");
+PTMI_STATIC_ASSERT(offsetof(ptmi_probe, enabled) == 12, "Probe.enabled");
+
 PTMI_STATIC_ASSERT(sizeof(ptmi_material) == 128, "Material is 128 B");
 PTMI_STATIC_ASSERT(offsetof(ptmi_material, metallic) == 12, "Material.metallic");
 PTMI_STATIC_ASSERT(offsetof(ptmi_material, roughness) == 16, "Material.roughness");

@@ -87,12 +87,17 @@ int bake_check(ptmi_ctx *c, const ptmi_bake_params *params, ptmi_bake_params *ou
     ptmi_bake_params bp;
     if ((rc = resolve_params(c, params, &bp))) return rc;
     if (!c->d_bake_texels) return fail(c, PTMI_E_INVALID, "no bake surface in place (ptmi_upload_bake_surface)");
-    if (c->aov_mask) return fail(c, PTMI_E_INVALID, "a bake has no first hit: turn the first-hit planes off (ptmi_set_aovs(0))");
+    if ((rc = listed_check(c, "a bake"))) return rc;
+    *out = bp;
+    return PTMI_OK;
+}
+
+int listed_check(ptmi_ctx *c, const char *what) {
+    if (c->aov_mask) return fail(c, PTMI_E_INVALID, "%s has no first hit: turn the first-hit planes off (ptmi_set_aovs(0))", what);
     const DevBand band = pt_band_of(c->opt, c->W, c->H);
     if (band.y0 != 0u || band.y1 != c->H || band.parts > 1u || band.rows != c->H)
-        return fail(c, PTMI_E_INVALID, "a bake covers the whole frame: the tile options select rows [%u,%u), part %u of %u", band.y0, band.y1,
-                    band.part, band.parts);
-    *out = bp;
+        return fail(c, PTMI_E_INVALID, "%s covers the whole frame: the tile options select rows [%u,%u), part %u of %u", what, band.y0,
+                    band.y1, band.part, band.parts);
     return PTMI_OK;
 }
 

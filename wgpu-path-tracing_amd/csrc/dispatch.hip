@@ -107,27 +107,28 @@ struct Timed {
 // the raygen in front of it and the folds behind it.
 // map (with ap; ptmi_multi_dispatch_adaptive): the round selects from the whole-frame flag map and never restarts (pt_adaptive_flags
 // has); count_call = false: a further round of one call, which ptmi_stats.dispatches has already counted.
-// bake (ptmi_dispatch_bake, which has checked it: bake_check; no camera, no ap): n_frames frames of every covered texel of the surface
-// in place, from bake->first_frame: the surface is the batch's ray source and its covered texels are the batch's pixels.
+// listed (ptmi_dispatch_bake and ptmi_dispatch_probes, which have checked it: bake_check, probes_check; no camera, no ap): n_frames
+// frames of every texel of listed->list, from listed->first_frame: listed->rays is the batch's ray source and the list is the batch's
+// pixels (a bake: the surface and its covered texels; probes: the probe records and the texels of the enabled probes' tiles).
 int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_adaptive_params *ap, uint32_t rounds,
-             const DevFlagMap *map = nullptr, bool count_call = true, const ptmi_bake_params *bake = nullptr) {
+             const DevFlagMap *map = nullptr, bool count_call = true, const ListedRays *listed = nullptr) {
     int rc = check_ready(c, true);
     if (rc) return rc;
     uint32_t proj = PTMI_PROJ_PERSPECTIVE;
-    if (!bake) {
+    if (!listed) {
         if (!cam) return fail(c, PTMI_E_INVALID, "camera is NULL");
         if (cam->width != c->W || cam->height != c->H)
             return fail(c, PTMI_E_INVALID, "camera says %ux%u but the output buffer is %ux%u", cam->width, cam->height, c->W, c->H);
         if ((rc = pt_check_camera(c, cam, &proj, c->err))) return rc;
     }
-    if (n_frames == 0 || (ap && rounds == 0) || (bake && c->bake_covered == 0u)) return PTMI_OK;
+    if (n_frames == 0 || (ap && rounds == 0) || (listed && listed->count == 0u)) return PTMI_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     if (ap && (rc = make_planes(c, group_set(kByAdaptive), (size_t)c->W * c->H, c->plane))) return rc;
     const DevBand band = pt_band_of(c->opt, c->W, c->H);
     if (band.y0 >= band.y1) return fail(c, PTMI_E_INVALID, "tile rows [%u,%u) outside the %u-row frame", band.y0, band.y1, c->H);
     if (band.rows == 0) return PTMI_OK;                         // more parts than strips: nothing to render here
-    const uint64_t npix = bake ? c->bake_covered : (uint64_t)band.rows * band.width;
-    const uint32_t first_frame = bake ? bake->first_frame : cam->frame_index;
+    const uint64_t npix = listed ? listed->count : (uint64_t)band.rows * band.width;
+    const uint32_t first_frame = listed ? listed->first_frame : cam->frame_index;
     uint32_t F = c->opt.frames_per_batch;
     // ~128 Mi paths, ~23 GB of state: the last bounces' small queues cost a fixed time per batch, so fewer, larger batches
     // (measured at 1080p, Msamples/s: 32 frames 8 920, 64 frames 9 150 - 9 275, 128 frames 9 270 - 9 310, when that time was ~3 ms.
@@ -205,12 +206,12 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         unsigned long long *const ct = c->d_counters;
         uint32_t *const qlen = &c->d_control[kCwQueue], *const slen = &c->d_control[kCwShadow];    // queue lengths by bounce; shadow, by parity
         if (ap && !map && first_frame == 0u) { pt_launch_adaptive_restart(ms, blocks, band, mom); c->ad_rounds = 0; }
-        const DevRays rays = bake ? DevRays{BakeSurface{c->d_bake_texels, bake->bias}} : DevRays{CameraSource{cam, proj}};
-        // a batch: fb frames of every pixel (bake: covered texel) from frame0 on, or (ap) of every listed pixel from its own count on
+        const DevRays rays = listed ? listed->rays : DevRays{CameraSource{cam, proj}};
+        // a batch: fb frames of every pixel (listed: listed texel) from frame0 on, or (ap) of every listed pixel from its own count on
         auto batch = [&](uint32_t frame0, uint32_t fb) -> int {
             const DevPixels px = ap     ? DevPixels{ListedPixels{band, c->ad.list, &c->d_control[kCwAdActive], mom, &ct[kCtAdTraced]}}
-                                 : bake ? DevPixels{BakedPixels{band, c->d_bake_covered, c->bake_covered, frame0}}
-                                        : DevPixels{DensePixels{band, frame0}};
+                                 : listed ? DevPixels{BakedPixels{band, listed->list, listed->count, frame0}}
+                                          : DevPixels{DensePixels{band, frame0}};
             { Timed t(c, kRaygen, t3, ms); pt_launch_raygen(ms, blocks, rays, px, fb, bp, &qlen[0]); }
             int cur = 0;
             for (uint32_t b = 0; b < maxb; b++) {
@@ -347,7 +348,15 @@ int ptmi_dispatch_bake(ptmi_ctx *c, const ptmi_bake_params *params, uint32_t n_f
     ptmi_bake_params bp;
     const int rc = bake_check(c, params, &bp);
     if (rc) return rc;
-    return dispatch(c, nullptr, n_frames, nullptr, 0, nullptr, true, &bp);
+    const ListedRays listed{BakeSurface{c->d_bake_texels, bp.bias}, c->d_bake_covered, c->bake_covered, bp.first_frame};
+    return dispatch(c, nullptr, n_frames, nullptr, 0, nullptr, true, &listed);
+}
+
+int ptmi_dispatch_probes(ptmi_ctx *c, const ptmi_probe_params *params, uint32_t n_frames) {
+    ListedRays listed;
+    const int rc = probes_check(c, params, &listed);
+    if (rc) return rc;
+    return dispatch(c, nullptr, n_frames, nullptr, 0, nullptr, true, &listed);
 }
 
 int ptmi_adaptive_status(ptmi_ctx *c, struct ptmi_adaptive_status *out) {

@@ -79,7 +79,7 @@ PT_DEV void init_path(DevPaths P, uint32_t p, v3 o, v3 d, uint32_t rng) {
 // not materialised: extend / shade / compact take a null queue as "slot i holds path i".
 //
 // Where a path's first ray comes from (pt_device.h DevRays, as the kernels see it). A ray source answers: for pixel (x, y) at `frame`,
-// frame index fp, the origin, the direction and the RNG state behind them.
+// frame index fp, the origin, the direction and the RNG state behind them. Three sources: CameraRays, BakeRays, ProbeRays.
 template <int PROJ>
 struct CameraRays {                     // the camera of projection PROJ (CameraSource)
     ptmi_camera cam;
@@ -115,6 +115,32 @@ struct BakeRays {                       // the records of a bake surface (BakeSu
         const float4 t0 = texels[2 * fp], t1 = texels[2 * fp + 1];
         o = d = mk3(0.0f, 0.0f, 0.0f); rng = 0u;
         if (__float_as_uint(t0.w) != 0u) bake_ray(t0, t1, bias, x, y, frame, o, d, rng);
+    }
+};
+
+// The first ray of a probe path (include/ptmi.h ptmi_dispatch_probes): from the probe, along the octahedral direction of the jittered
+// point of its texel. Every line rounds once: the build contracts nothing.
+PT_DEV void probe_ray(float4 probe, uint32_t tile, uint32_t x, uint32_t y, uint32_t frame, v3 &org, v3 &dir, uint32_t &rng) {
+    rng = rng_seed(x, y, frame);
+    const float r1 = rng_f(rng), r2 = rng_f(rng);           // the pinhole's two jitter draws
+    const float s = 2.0f / (float)tile;                     // exact: tile is a power of two
+    const float a = ((float)(x & (tile - 1u)) + r1) * s - 1.0f;
+    const float b = ((float)(y & (tile - 1u)) + r2) * s - 1.0f;
+    const float fa = __builtin_fabsf(a), fb = __builtin_fabsf(b);
+    const float w = (1.0f - fa) - fb;
+    v3 raw = mk3(a, b, w);
+    if (w < 0.0f) { raw.x = __builtin_copysignf(1.0f - fb, a); raw.y = __builtin_copysignf(1.0f - fa, b); }
+    org = xyz(probe);
+    dir = normalize3(raw);
+}
+struct ProbeRays {                      // the probes of a probe atlas (ProbeSet); zeros for a texel of a disabled probe or past the last
+    const float4 *__restrict__ probes; uint32_t shift, cols, count;
+    PT_DEV void ray(uint32_t x, uint32_t y, uint32_t frame, size_t, v3 &o, v3 &d, uint32_t &rng) const {
+        const uint32_t i = (y >> shift) * cols + (x >> shift);
+        o = d = mk3(0.0f, 0.0f, 0.0f); rng = 0u;
+        if ((x >> shift) >= cols || i >= count) return;
+        const float4 p = probes[i];
+        if (__float_as_uint(p.w) != 0u) probe_ray(p, 1u << shift, x, y, frame, o, d, rng);
     }
 };
 
@@ -617,6 +643,7 @@ void with_proj(uint32_t proj, F &&f) {
 template <class F>
 void with_rays(const DevRays &rays, F &&f) {
     if (const BakeSurface *b = std::get_if<BakeSurface>(&rays)) return f(BakeRays{b->texels, b->bias});
+    if (const ProbeSet *p = std::get_if<ProbeSet>(&rays)) return f(ProbeRays{p->probes, p->shift, p->cols, p->count});
     const CameraSource &c = std::get<CameraSource>(rays);
     with_proj(c.proj, [&](auto proj) { f(CameraRays<decltype(proj)::value>{*c.cam}); });
 }

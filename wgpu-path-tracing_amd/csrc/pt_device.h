@@ -341,8 +341,9 @@ struct ListedPixels {                   // the *n_active pixels of the list, eac
     __device__ uint32_t first_frame(size_t oi) const { return (uint32_t)mom[oi].z; }
     __device__ void count_paths(uint32_t paths) const { atomicAdd(traced, (unsigned long long)paths); }
 };
-struct BakedPixels {                    // the n covered texels of a bake surface (ascending frame indices; the band is the whole
-    DevBand band; const uint32_t *covered; uint32_t n, frame0;     // frame), all from frame0 (ptmi_dispatch_bake)
+struct BakedPixels {                    // the n covered texels of a bake surface, or the n texels of the enabled probes of a probe atlas
+    DevBand band; const uint32_t *covered; uint32_t n, frame0;     // (ascending frame indices; the band is the whole frame), all from
+                                                                    // frame0 (ptmi_dispatch_bake, ptmi_dispatch_probes)
     __device__ uint32_t entries() const { return n; }
     __device__ uint32_t pixel(uint32_t j) const { return covered[j]; }
     __device__ uint32_t first_frame(size_t) const { return frame0; }
@@ -354,7 +355,10 @@ using DevPixels = std::variant<DensePixels, ListedPixels, BakedPixels>;
 // (ptmi_upload_bake_surface; a path starts at its texel's record, `bias` along its first direction).
 struct CameraSource { const ptmi_camera *cam; uint32_t proj; };
 struct BakeSurface { const float4 *texels; float bias; };
-using DevRays = std::variant<CameraSource, BakeSurface>;
+// ... or the probes of a probe atlas (ptmi_upload_probes; a path starts at the probe whose tile holds its texel, along the texel's
+// octahedral direction): `count` records, tiles of 1 << shift texels a side, `cols` tiles a row.
+struct ProbeSet { const float4 *probes; uint32_t shift, cols, count; };
+using DevRays = std::variant<CameraSource, BakeSurface, ProbeSet>;
 // the first rays of a batch: *count_out = entries * n_frames
 void pt_launch_raygen(hipStream_t s, int blocks, const DevRays &rays, const DevPixels &px, uint32_t n_frames, DevPaths p, uint32_t *count_out);
 // the first rays of n pixels (xs, ys) of a frame `width` wide at `frames` (ptmi_debug_raygen, ptmi_debug_bake_rays): path i = the ray
@@ -365,6 +369,15 @@ void pt_launch_raygen_list(hipStream_t s, const DevRays &rays, uint32_t width, u
 // passes of the rule of include/ptmi.h ping-ponging between a and b; returns the plane that holds the result
 float4 *pt_launch_bake_dilate(hipStream_t s, uint32_t W, uint32_t H, uint32_t passes, const float4 *texels, const float4 *out,
                               float4 *a, float4 *b);
+// The two reductions of a probe atlas (probes.hip; include/ptmi.h states both sums). `out` is the frame, W texels a row; probe i owns
+// the tile (i % cols, i / cols) of 1 << shift texels a side.
+struct DevProbeAtlas { const float4 *out; const float4 *probes; uint32_t W, shift, cols, count; };
+// sh[i * 27 + k * 3 + ch] from basis9 (9 floats per texel of a tile): one wave per probe
+void pt_launch_probe_sh(hipStream_t s, DevProbeAtlas a, const float *basis9, float *sh);
+// irr[(i * m * m + j) * 4 ...] from dir_dw (d_t, dw_t per texel of a tile) and normals (the m * m directions of the tile-m table): one
+// workgroup per probe, the probe's tile and dir_dw staged in pt_probe_irradiance_lds(shift) bytes of dynamic LDS
+size_t pt_probe_irradiance_lds(uint32_t shift);
+void pt_launch_probe_irradiance(hipStream_t s, DevProbeAtlas a, const float4 *dir_dw, const float4 *normals, uint32_t m, float4 *irr);
 void pt_launch_extend(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &sc, DevPaths p,
                       const uint32_t *queue, const uint32_t *count, float2 *hits);
 void pt_launch_extend_own(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &sc, DevPaths p,

@@ -342,6 +342,7 @@ int ptmi_destroy(ptmi_ctx *c) {
     for (void *&p : c->buf) dfree(p);
     dfree(c->d_atlas); dfree(c->d_env); dfree(c->d_env_alias); dfree(c->d_med_grid);
     bake_forget(c);
+    probes_forget(c);
     drop_planes(c, kAllPlanes);
     dfree(c->d_counters); dfree(c->d_control); dfree(c->d_scene);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -416,7 +417,7 @@ int ptmi_resize(ptmi_ctx *c, uint32_t w, uint32_t h) {
         return fail(c, PTMI_E_HIP, "sync_all failed: %s", hipGetErrorString(e));
     }
     drop_planes(c, kAllPlanes);                       // the denoiser's, the adaptive, the history, the blit and the dilate planes come back at their first use
-    if (w != c->W || h != c->H) bake_forget(c);       // a bake surface is a surface of one size
+    if (w != c->W || h != c->H) { bake_forget(c); probes_forget(c); }      // a bake surface and a probe atlas are of one size
     std::copy(fresh, fresh + kFramePlanes, c->plane);
     c->W = w; c->H = h;
     c->d_out = plane_as<float4>(c, kOut);

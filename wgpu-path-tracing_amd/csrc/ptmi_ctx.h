@@ -17,6 +17,7 @@
 //   scene_skin.hip     skinned triangles posed on the device: the list, the corner records, the rest pose, the check and write kernel
 //   scene_morph.hip    morphed triangles posed on the device: the list, the sparse delta rows, the rest pose, the check and write kernel
 //   bake.hip           lightmap baking: the surface's records and covered list, the checks of a bake, the gutter fill, the debug rays
+//   probes.hip         light probes: the records, tables and texel list, the checks of a probe dispatch, the SH9 and irradiance reductions
 #pragma once
 #include "ptmi.h"
 #include "pt_device.h"
@@ -273,6 +274,14 @@ struct ptmi_ctx {
     float4 *d_bake_texels = nullptr;                   // NULL: no surface in place
     uint32_t *d_bake_covered = nullptr;
     uint32_t bake_covered = 0;                         // entries of the list
+    // the probes (ptmi_upload_probes; probes.hip): the records, the ascending list of the texels of the enabled probes' tiles, and the
+    // two tables of the tile size; gone with a ptmi_resize to another size
+    float4 *d_probes = nullptr;                        // NULL: no probes in place
+    uint32_t *d_probe_list = nullptr;
+    float4 *d_probe_dir_dw = nullptr;                  // tile * tile entries: (d_t, dw_t)
+    float *d_probe_basis = nullptr;                    // tile * tile * 9
+    float4 *d_probe_normals = nullptr;                 // room for the 16 x 16 directions of ptmi_probe_irradiance's output tile
+    struct ptmi_probe_status probe{};                  // what ptmi_probe_status reports (texels: entries of the list)
     // the counter and control words (pt_device.h CounterWord, ControlWord): made and zeroed by ptmi_create
     unsigned long long *d_counters = nullptr;          // kCounterWords
     uint32_t *d_control = nullptr;                     // kControlWords
@@ -322,6 +331,16 @@ hipError_t quiesce(ptmi_ctx *c);
 // enqueues, with its error codes, changing nothing; *out = the params with their defaults.
 void bake_forget(ptmi_ctx *c);
 int bake_check(ptmi_ctx *c, const ptmi_bake_params *params, ptmi_bake_params *out);
+// A listed first-ray source, as ptmi_dispatch_bake and ptmi_dispatch_probes describe theirs to dispatch(): where the first rays come from,
+// the ascending frame indices of the texels that get them (device memory), how many, and the first frame.
+struct ListedRays { DevRays rays; const uint32_t *list; uint32_t count, first_frame; };
+// what every listed dispatch requires of the context (`what`: "a bake", "a probe dispatch"): no first-hit plane, the whole frame
+int listed_check(ptmi_ctx *c, const char *what);
+
+// probes.hip. probes_forget: the probes go (the caller has synchronised). probes_check: everything ptmi_dispatch_probes checks before
+// it enqueues, with its error codes, changing nothing; *out = the listed source of the probes in place under the params.
+void probes_forget(ptmi_ctx *c);
+int probes_check(ptmi_ctx *c, const ptmi_probe_params *params, ListedRays *out);
 
 // scene_update.hip: the plan of ptmi_update_triangles. make_plan reads the topology of both hierarchies as they stand and leaves the
 // context's scene alone (a failure leaves no plan behind; the caller drops what is left); walked_cost: the cost of the walked hierarchy

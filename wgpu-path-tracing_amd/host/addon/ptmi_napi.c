@@ -1069,6 +1069,81 @@ static napi_value js_bake_dilate(napi_env env, napi_callback_info info) {
     return argv[2];
 }
 
+/* ---- light probes (include/ptmi.h ptmi_upload_probes ...): one device's handle only, like baking ---- */
+
+/* uploadProbes(h, records (16 bytes each) or null, tile) */
+static napi_value js_upload_probes(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    handle *h = get_single_handle(env, info, 3, argv, "uploadProbes");
+    if (!h) return NULL;
+    void *p; size_t n; uint32_t tile = 0;
+    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
+    napi_get_value_uint32(env, argv[2], &tile);
+    if (p && (n % sizeof(ptmi_probe) || n / sizeof(ptmi_probe) > 0xFFFFFFFFu)) {
+        napi_throw_range_error(env, NULL, "uploadProbes: expected records of 16 bytes"); return NULL;
+    }
+    int rc = ptmi_upload_probes(h->ctx, (const ptmi_probe *)p, p ? (uint32_t)(n / sizeof(ptmi_probe)) : 0u, tile);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_upload_probes");
+    return NULL;
+}
+
+/* dispatchProbes(h, {firstFrame} or null, frames): ptmi_dispatch_probes */
+static napi_value js_dispatch_probes(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    handle *h = get_single_handle(env, info, 3, argv, "dispatchProbes");
+    if (!h) return NULL;
+    ptmi_probe_params prm;
+    napi_valuetype t;
+    uint32_t frames = 1;
+    memset(&prm, 0, sizeof prm);
+    if (napi_typeof(env, argv[1], &t) == napi_ok && t == napi_object) prm.first_frame = get_u32_prop(env, argv[1], "firstFrame", 0);
+    napi_get_value_uint32(env, argv[2], &frames);
+    int rc = ptmi_dispatch_probes(h->ctx, &prm, frames);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_dispatch_probes");
+    return NULL;
+}
+
+/* probeStatus(h) -> {present, tile, count, enabled, texels} */
+static napi_value js_probe_status(napi_env env, napi_callback_info info) {
+    napi_value argv[1];
+    handle *h = get_single_handle(env, info, 1, argv, "probeStatus");
+    if (!h) return NULL;
+    struct ptmi_probe_status s;
+    int rc = ptmi_probe_status(h->ctx, &s);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_probe_status");
+    napi_value o;
+    NAPI_OK(env, napi_create_object(env, &o));
+    set_num(env, o, "present", (double)s.present); set_num(env, o, "tile", (double)s.tile); set_num(env, o, "count", (double)s.count);
+    set_num(env, o, "enabled", (double)s.enabled); set_num(env, o, "texels", (double)s.texels);
+    return o;
+}
+
+/* probeSh(h, Float32Array dst of count * 27): SH9 of every probe's tile */
+static napi_value js_probe_sh(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    handle *h = get_single_handle(env, info, 2, argv, "probeSh");
+    if (!h) return NULL;
+    void *p; size_t n;
+    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
+    int rc = ptmi_probe_sh(h->ctx, (float *)p, n / 4);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_probe_sh");
+    return argv[1];
+}
+
+/* probeIrradiance(h, m, Float32Array dst of count * m * m * 4): the m x m irradiance tile (E / pi) of every probe */
+static napi_value js_probe_irradiance(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    handle *h = get_single_handle(env, info, 3, argv, "probeIrradiance");
+    if (!h) return NULL;
+    uint32_t m = 0;
+    napi_get_value_uint32(env, argv[1], &m);
+    void *p; size_t n;
+    if (!get_bytes(env, argv[2], &p, &n)) return NULL;
+    int rc = ptmi_probe_irradiance(h->ctx, m, (float *)p, n / 4);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_probe_irradiance");
+    return argv[2];
+}
+
 /* readMoments(h, Float32Array dst of width*height*4): the sample-moments plane */
 static napi_value js_read_moments(napi_env env, napi_callback_info info) {
     napi_value argv[2];
@@ -1222,6 +1297,8 @@ static napi_value init(napi_env env, napi_value exports) {
         {"setProjections", js_set_projections}, {"getProjections", js_get_projections},
         {"uploadBakeSurface", js_upload_bake_surface}, {"dispatchBake", js_dispatch_bake}, {"bakeStatus", js_bake_status},
         {"bakeDilate", js_bake_dilate},
+        {"uploadProbes", js_upload_probes}, {"dispatchProbes", js_dispatch_probes}, {"probeStatus", js_probe_status},
+        {"probeSh", js_probe_sh}, {"probeIrradiance", js_probe_irradiance},
         {"buildBvh", js_build_bvh}, {"emissiveLights", js_emissive_lights},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

@@ -168,6 +168,15 @@ export class Renderer {
   bake(opts?: { width?: number; height?: number; frames?: number; dilate?: number; bias?: number }): Float32Array;
   /** what the last bake() baked */
   lastBake?: { width: number; height: number; frames: number; covered: number };
+  /** light probes of the loaded scene (include/ptmi.h ptmi_dispatch_probes, ptmi_probe_sh, ptmi_probe_irradiance): probes at
+   *  `positions` (3 numbers each) or at the cell centres of `grid`, each with a tile x tile octahedral tile (default 8) of the atlas
+   *  (probe i owns tile (i % cols, i / cols); probes.js atlasSize gives the size), `frames` paths per atlas texel (default 64).
+   *  radiance: width*height float4; sh: 27 floats per probe (k major, rgb minor); irradiance: m*m float4 per probe (E / pi, w = 1), or
+   *  null without `irradiance: m`. The frame takes the atlas's size and accumulation restarts. Punctual lights reach a probe only
+   *  through later bounces. Throws with several devices and while first-hit planes are on; synchronises */
+  bakeProbes(opts: { positions?: ArrayLike<number>; grid?: { min: number[]; max: number[]; counts: number[] }; enabled?: ArrayLike<number | boolean>;
+                     tile?: number; frames?: number; irradiance?: number }):
+    { radiance: Float32Array; sh: Float32Array; irradiance: Float32Array | null; width: number; height: number; count: number };
   /** first-hit planes (include/ptmi.h ptmi_set_aovs); with several devices each keeps its strips and readAov assembles the plane */
   setAovs(names: Array<'albedo' | 'normal' | 'id'>): void;
   /** width*height entries, index y*width+x: 'albedo' / 'normal' 4 floats each, 'id' 2 uint32 (triangle, material) */

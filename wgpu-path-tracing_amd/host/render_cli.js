@@ -11,7 +11,8 @@
  *                       --devices 0,1,... --loopback --aov albedo|normal|id --aov-out plane.bin
  *                       --alpha-cutout --alpha-blend --alpha-seed N --alpha-layers N --animation N --time S
  *                       --camera N --projection ortho|panorama --ymag V --hdr out.hdr
- *                       --bake W,H --bake-dilate N --bake-bias B]
+ *                       --bake W,H --bake-dilate N --bake-bias B
+ *                       --probes nx,ny,nz --probe-tile N --probe-irradiance M]
  * --batch K traces K frames per dispatch instead of one. --denoise keeps the denoiser's planes and makes --png the tone-mapped
  * denoised image (include/ptmi.h ptmi_denoise, default parameters). --adaptive renders to a noise level instead of --frames
  * (include/ptmi.h ptmi_dispatch_adaptive): rounds until none lists a pixel, or --rounds R of them; the JSON line then also holds
@@ -45,6 +46,12 @@
  * passes (default 0), --bake-bias B the origin offset along the first ray (default 1e-6). out.f32 and --hdr then hold the lightmap
  * (row y at v = (y + 0.5) / H; w: 0, or with --bake-dilate the texel's state), --png its tone-mapped image, and the JSON line bake:
  * { width, height, frames, covered }. Not with --devices, --denoise, --aov or --adaptive.
+ * --probes nx,ny,nz gathers light probes instead of rendering from the camera (Renderer.bakeProbes; include/ptmi.h
+ * ptmi_dispatch_probes): an nx x ny x nz lattice over the scene's bounds with a probe at every cell centre (probes.js grid), so the
+ * outermost probes stand half a cell inside the bounds; --probe-tile N the atlas tile (default 8), --frames samples per atlas texel,
+ * --probe-irradiance M also the M x M irradiance tiles. out.f32 then holds the radiance atlas (its size in the JSON line's probes:
+ * { width, height, count, tile }), and beside it <out minus .f32>.sh.f32 holds 27 floats per probe and, with --probe-irradiance,
+ * <out minus .f32>.irr.f32 the M * M float4 per probe. Not with --devices, --denoise, --aov, --adaptive or --bake.
  */
 var fs = require('fs');
 var host = require('./renderer');
@@ -113,13 +120,24 @@ r.loadModel(scenePath).then(function () {
     r.setProjection(projection === 'ortho' ? 'orthographic' : 'equirect', { ymag: arg('ymag', r.camera.ymag || 1) });
   } else if (textArg('ymag') !== null && r.camera.projection === 'orthographic') r.setProjection('orthographic', { ymag: arg('ymag', 1) });
   var t0 = Date.now();
-  var status = null, out = null;
+  var status = null, out = null, probeSet = null;
   if (textArg('bake') !== null) {
     var size = textArg('bake').split(',').map(Number);
     if (size.length !== 2 || !(size[0] > 0) || !(size[1] > 0)) throw new Error('--bake: W,H');
     if (devices || denoise || aov || adaptive) throw new Error('--bake does not go with --devices, --denoise, --aov or --adaptive');
     out = r.bake({ width: size[0], height: size[1], frames: frames, dilate: arg('bake-dilate', 0), bias: arg('bake-bias', 1e-6) });
     W = size[0]; H = size[1];
+  } else if (textArg('probes') !== null) {
+    var counts = textArg('probes').split(',').map(Number);
+    if (counts.length !== 3 || !(counts[0] > 0) || !(counts[1] > 0) || !(counts[2] > 0)) throw new Error('--probes: nx,ny,nz');
+    if (devices || denoise || aov || adaptive) throw new Error('--probes does not go with --devices, --denoise, --aov or --adaptive');
+    if (!r.sceneBounds) throw new Error('--probes needs a scene with a hierarchy (its bounds)');
+    var stem = outPath.replace(/\.f32$/, '');
+    probeSet = r.bakeProbes({ grid: { min: r.sceneBounds.min, max: r.sceneBounds.max, counts: counts }, tile: arg('probe-tile', 8),
+                              frames: frames, irradiance: arg('probe-irradiance', 0) });
+    out = probeSet.radiance; W = probeSet.width; H = probeSet.height;
+    fs.writeFileSync(stem + '.sh.f32', Buffer.from(probeSet.sh.buffer));
+    if (probeSet.irradiance) fs.writeFileSync(stem + '.irr.f32', Buffer.from(probeSet.irradiance.buffer));
   } else if (adaptive) {
     r.setAdaptive(adaptive);
     var rounds = arg('rounds', 0);
@@ -152,6 +170,7 @@ r.loadModel(scenePath).then(function () {
   if (textArg('animation') !== null) { st.skin = r.skinStatus(); st.morph = r.morphStatus(); }
   if (r.projections) st.projection = { kind: r.camera.projection || 'perspective', ymag: r.camera.ymag || 0 };
   if (r.lastBake) st.bake = r.lastBake;
+  if (probeSet) st.probes = { width: W, height: H, count: probeSet.count, tile: arg('probe-tile', 8) };
   if (status) st.adaptive = { samples: status.samples, minCount: status.minCount, maxCount: status.maxCount, rounds: status.rounds };
   console.log(JSON.stringify(st));
   r.destroy();

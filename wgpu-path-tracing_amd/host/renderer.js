@@ -672,6 +672,44 @@ Renderer.prototype.bake = function (opts) {
   return out;
 };
 
+/**
+ * Light probes of the loaded scene (include/ptmi.h ptmi_upload_probes, ptmi_dispatch_probes, ptmi_probe_sh, ptmi_probe_irradiance):
+ * opts = { positions (3 numbers per probe) | grid: { min, max, counts } (probes.js: cell centres), enabled (flags per probe, default
+ * all), tile (N, default 8), frames (samples per atlas texel, default 64), irradiance (m, default 0: none) }. Every texel of every
+ * enabled probe's N x N tile traces `frames` paths from the probe along its octahedral direction. Returns { radiance: the
+ * width * height float4 atlas (probe i owns tile (i % cols, i / cols), row 0 at the bottom), sh: 27 floats per probe (k major, rgb
+ * minor), irradiance: m * m float4 per probe (E / pi, w = 1) or null, width, height, count }. One device only; the first-hit planes
+ * must be off. The frame takes the atlas's size (probes.js atlasSize) and accumulation restarts. Synchronises.
+ */
+Renderer.prototype.bakeProbes = function (opts) {
+  opts = opts || {};
+  var probes = require('./probes');
+  if (!this.sceneLoaded) throw new Error('bakeProbes: needs a loaded scene (loadModel)');
+  if (this.multi) throw new Error('bakeProbes: one device only');
+  if (this.aovMask) throw new Error('bakeProbes: turn the first-hit planes off first (setAovs([]), setDenoise(false), setReproject(null))');
+  var positions = opts.positions || (opts.grid && probes.grid(opts.grid.min, opts.grid.max, opts.grid.counts));
+  if (!positions || positions.length < 3) throw new Error('bakeProbes: positions or grid');
+  var count = Math.floor(positions.length / 3);
+  var tile = opts.tile || 8, frames = opts.frames === undefined ? 64 : opts.frames, m = opts.irradiance || 0;
+  var size = probes.atlasSize(count, tile), W = size.width, H = size.height;
+  this.stop();
+  if (W !== this.width || H !== this.height) this.resize(W, H);
+  this.addon.uploadProbes(this.ctx, probes.records(positions, opts.enabled), tile);
+  var radiance = new Float32Array(W * H * 4), sh = new Float32Array(count * 27), irr = m ? new Float32Array(count * m * m * 4) : null;
+  try {
+    this.addon.writeOutput(this.ctx, radiance);                         // tiles of disabled probes read as zeros
+    this.addon.dispatchProbes(this.ctx, { firstFrame: 0 }, frames);
+    this.addon.readOutput(this.ctx, radiance);
+    this.addon.probeSh(this.ctx, sh);
+    if (irr) this.addon.probeIrradiance(this.ctx, m, irr);
+  } finally {
+    this.addon.uploadProbes(this.ctx, null, 0);
+  }
+  this.reprojectFrom = null;
+  this.frameIndex = 0;                      // the output buffer holds a probe atlas now: a camera's accumulation starts over
+  return { radiance: radiance, sh: sh, irradiance: irr, width: W, height: H, count: count };
+};
+
 /** The reference's blit pass (renderer.ts:434-449, blit.wgsl): tone-mapped 8-bit canvas, row 0 = top. */
 Renderer.prototype.blit = function () {
   var out = new Uint8Array(this.width * this.height * 4);

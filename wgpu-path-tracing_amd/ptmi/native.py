@@ -56,6 +56,8 @@ EXPORTS = [
     "ptmi_set_morph", "ptmi_pose_morph", "ptmi_morph_status", "ptmi_multi_set_morph", "ptmi_multi_pose_morph", "ptmi_multi_morph_status",
     "ptmi_set_projections", "ptmi_get_projections", "ptmi_multi_set_projections", "ptmi_multi_get_projections",
     "ptmi_upload_bake_surface", "ptmi_dispatch_bake", "ptmi_bake_status", "ptmi_bake_dilate", "ptmi_debug_bake_rays",
+    "ptmi_upload_probes", "ptmi_dispatch_probes", "ptmi_probe_status", "ptmi_probe_sh", "ptmi_probe_irradiance",
+    "ptmi_debug_probe_rays", "ptmi_debug_probe_tables",
 ]
 MULTI_LOOPBACK = 1
 MULTI_PLANE_MOMENTS, MULTI_PLANE_OUTPUT = 0x100, 0x200      # gather_planes: with the AOV_* bits
@@ -286,6 +288,19 @@ class BakeStatus(ctypes.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class ProbeParams(ctypes.Structure):
+    """ptmi_probe_params (include/ptmi.h ptmi_dispatch_probes)"""
+    _fields_ = [("first_frame", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+class ProbeStatus(ctypes.Structure):
+    _fields_ = [("present", ctypes.c_uint32), ("tile", ctypes.c_uint32), ("count", ctypes.c_uint32), ("enabled", ctypes.c_uint32),
+                ("texels", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class Stats(ctypes.Structure):
     _fields_ = [("paths", ctypes.c_uint64), ("segments", ctypes.c_uint64), ("shadow_rays", ctypes.c_uint64),
                 ("dispatches", ctypes.c_uint64), ("frames", ctypes.c_uint64),
@@ -346,6 +361,15 @@ _BAKE = {
     "ptmi_bake_status": [ctypes.c_void_p],
     "ptmi_bake_dilate": [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t],
     "ptmi_debug_bake_rays": [ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 6,
+}
+# light probes (include/ptmi.h ptmi_upload_probes ...): likewise
+_PROBES = {
+    "ptmi_upload_probes": [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32],
+    "ptmi_dispatch_probes": [ctypes.c_void_p, ctypes.c_uint32],
+    "ptmi_probe_status": [ctypes.c_void_p],
+    "ptmi_probe_sh": [ctypes.c_void_p, ctypes.c_size_t],
+    "ptmi_probe_irradiance": [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t],
+    "ptmi_debug_probe_rays": [ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 6,
 }
 _lib = None
 
@@ -420,9 +444,11 @@ def load():
         L.ptmi_normal_matrix.restype = None
         L.ptmi_normal_matrix.argtypes = [vp, vp]
         L.ptmi_debug_read_triangles.argtypes = [vp, u32, u32, vp]
-        for name, args in _BAKE.items():                        # (a tool that loads an older build of the ABI takes them off EXPORTS)
+        for name, args in list(_BAKE.items()) + list(_PROBES.items()):      # (a tool that loads an older build of the ABI takes them off EXPORTS)
             if name in EXPORTS:
                 getattr(L, name).argtypes = [vp] + args
+        if "ptmi_debug_probe_tables" in EXPORTS:
+            L.ptmi_debug_probe_tables.argtypes = [u32, vp, vp]
         _lib = L
     return _lib
 
@@ -441,6 +467,17 @@ def image_stats(scene):
     keys = ("wide_nodes", "leaves", "depth", "quantised_nodes", "stream_dwords", "containment_violations",
             "mean_area_growth", "stream_mismatches")
     return dict(zip(keys, list(out)))
+
+
+def probe_tables(tile):
+    """Host-only: the two tables of a probe tile (include/ptmi.h ptmi_debug_probe_tables): (tile * tile, 4) float32 (d_t, dw_t) and
+    (tile * tile, 9) float32 basis"""
+    L = load()
+    dir_dw, basis = np.zeros((tile * tile, 4), np.float32), np.zeros((tile * tile, 9), np.float32)
+    rc = L.ptmi_debug_probe_tables(tile, _p(dir_dw), _p(basis))
+    if rc != 0:
+        raise PtmiError(rc, L.ptmi_last_error(None).decode())
+    return dir_dw, basis
 
 
 def normal_matrix(m):
@@ -1053,6 +1090,55 @@ class Context(_Handle):
         o, d, rng = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
         self._ck(self.L.ptmi_debug_bake_rays(self.h, self._bake_params(first_frame, bias, reserved), n, _p(xs), _p(ys), _p(frames),
                                              _p(o), _p(d), _p(rng)))
+        return o, d, rng
+
+    # -- light probes (include/ptmi.h ptmi_upload_probes, ptmi_dispatch_probes) -----------------------------------
+    @staticmethod
+    def _probe_params(first_frame, reserved):
+        """None where every argument is its default: the call then passes NULL"""
+        if first_frame == 0 and tuple(reserved) == (0, 0, 0):
+            return None
+        return ctypes.byref(ProbeParams(first_frame, (ctypes.c_uint32 * 3)(*reserved)))
+
+    def upload_probes(self, probes, tile=8, count=None):
+        """probes: layout.PROBE records (ptmi.probes.records makes them) for an atlas of tile x tile tiles, the context's size; None
+        removes the probes. count overrides the array's length (for tests)."""
+        if probes is None:
+            self._ck(self.L.ptmi_upload_probes(self.h, None, 0, 0))
+            return
+        p = np.ascontiguousarray(probes, layout.PROBE).ravel()
+        self._ck(self.L.ptmi_upload_probes(self.h, _p(p), len(p) if count is None else count, tile))
+
+    def dispatch_probes(self, n_frames=1, first_frame=0, reserved=(0, 0, 0)):
+        """n_frames frames of every texel of the enabled probes' tiles from first_frame on, folded into the output buffer read as the
+        probe atlas. Asynchronous."""
+        self._ck(self.L.ptmi_dispatch_probes(self.h, self._probe_params(first_frame, reserved), n_frames))
+
+    def probe_status(self):
+        st = ProbeStatus()
+        self._ck(self.L.ptmi_probe_status(self.h, ctypes.byref(st)))
+        return st
+
+    def probe_sh(self, n_floats=None):
+        """SH9 of every probe's tile of the output buffer: (count, 9, 3) float32. n_floats overrides the count passed (for tests)."""
+        out = np.zeros((self.probe_status().count, 9, 3), np.float32)
+        self._ck(self.L.ptmi_probe_sh(self.h, _p(out), out.size if n_floats is None else n_floats))
+        return out
+
+    def probe_irradiance(self, m, n_floats=None):
+        """the m x m irradiance tile (E / pi) of every probe: (count, m, m, 4) float32, w = 1 for an enabled probe"""
+        n = self.probe_status().count
+        out = np.zeros((n, m, m, 4) if 0 < m <= 64 else (n, 1, 1, 4), np.float32)
+        self._ck(self.L.ptmi_probe_irradiance(self.h, m, _p(out), out.size if n_floats is None else n_floats))
+        return out
+
+    def debug_probe_rays(self, xs, ys, frames, first_frame=0, reserved=(0, 0, 0)):
+        """the first ray of texel (xs[i], ys[i]) at frames[i]: origins, directions (n, 3) float32 and RNG states (n,) uint32"""
+        xs, ys, frames = (np.ascontiguousarray(a, np.uint32) for a in (xs, ys, frames))
+        n = len(xs)
+        o, d, rng = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
+        self._ck(self.L.ptmi_debug_probe_rays(self.h, self._probe_params(first_frame, reserved), n, _p(xs), _p(ys), _p(frames),
+                                              _p(o), _p(d), _p(rng)))
         return o, d, rng
 
     # -- motion: reprojection across a geometry edit (include/ptmi.h ptmi_set_motion) ---------------------------
