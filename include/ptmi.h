@@ -350,6 +350,77 @@ int ptmi_probe_irradiance(ptmi_ctx *ctx, uint32_t m, float *dst_rgba, size_t n_f
 int ptmi_debug_probe_rays(ptmi_ctx *ctx, const ptmi_probe_params *params, uint32_t n, const uint32_t *xs, const uint32_t *ys,
                           const uint32_t *frames, float *o3, float *d3, uint32_t *rng);
 int ptmi_debug_probe_tables(uint32_t tile, float *dir_dw4, float *basis9);
+
+/* ---- probe visibility: first-hit depth moments and Chebyshev tiles -----------------------------
+ * A probe lattice leaks light through walls unless every probe also knows how far it sees. While the switch below is on, a probe
+ * dispatch records per radiance texel the mean distance, the mean squared distance and the hit fraction of the texel's first rays
+ * (the DEPTH PLANE), and ptmi_probe_visibility filters each probe's depth tile into a small octahedral tile a shader tests with
+ * Chebyshev's inequality (INTEGRATION.md §1.21 has the recipe).
+ *
+ * ptmi_set_probe_depth: params->max_distance must be finite and > 0 and the reserved words 0, else PTMI_E_INVALID with the previous
+ * state left in place (the switch, max_distance and the plane's contents). params NULL turns the switch off. While it is on the
+ * context owns one more frame plane, a float4 per texel of the frame: made with the frame, zeroed when made, following ptmi_resize
+ * exactly as the moments plane does (a resize gives a fresh zeroed plane); turning the switch on while it is on keeps the plane's
+ * contents and takes the new max_distance. With the switch off the plane does not exist: ptmi_read_probe_depth,
+ * ptmi_write_probe_depth and ptmi_probe_visibility return PTMI_E_STATE (so they do before the first ptmi_resize), and
+ * ptmi_probe_depth_device_ptr NULL. Synchronises. ptmi_get_probe_depth: *on, and in *out (may be NULL) the params while on.
+ * ptmi_read_probe_depth / ptmi_write_probe_depth: the whole plane, width * height * 4 floats (else PTMI_E_INVALID); both synchronise.
+ * Writing restores a plane cached elsewhere.
+ *
+ * With the switch on ptmi_dispatch_probes keeps the first-hit record of every path's first ray - (albedo, t) and (normal,
+ * bits(triangle)), 32 bytes a path, the record the first-hit planes of ptmi_set_aovs are folded from, written by the same kernel
+ * instantiation - and after the radiance fold of a batch folds it into the depth plane. Per listed texel, for the batch's frames in
+ * ascending order, in float32, each operation rounded once and none fused except inside mix:
+ *   hit = bits(rec[2 li + 1].w) != 0xFFFFFFFF                               li = k * listed + j: frame first_frame + k of entry j
+ *   d   = hit ? min(rec[2 li].w, max_distance) : max_distance
+ *   x   = (d, d * d, hit ? 1 : 0)
+ *   frame f = 0: acc = x;  f > 0: t = 1 / (float)(f + 1), acc = mix(acc, x, t) = fma(x, t, acc * (1 - t))   the radiance's running mean
+ *   plane[texel] = (acc[0], acc[1], acc[2], 0)
+ * first_frame = 0 overwrites; n frames in one call equal n calls of one; texels of disabled probes and of tiles past count are neither
+ * read nor written. A miss counts as max_distance: for a probe nothing closer than the clamp is as good as nothing at all.
+ * WHAT DEPTH MEANS is what the record holds. The alpha resolve loops run before shade, so the depth is that of the first surface
+ * that is PRESENT: a ray through the hole of a cutout, or through a blended surface that is absent for this sample, records what
+ * lies behind. Under a medium it is the distance to the surface behind the fog: a scatter event on the first ray ends the segment
+ * early but does not shorten the record, which is the surface hit the ray had been given all the same. Fog changes a probe's
+ * radiance, not what it can see.
+ * The radiance, the moments plane and the statistics of a probe dispatch keep their bits with the switch on; ptmi_dispatch,
+ * ptmi_dispatch_adaptive and ptmi_dispatch_bake keep their launches and their bits whatever the switch says, and get no record array
+ * on its account. A probe dispatch with the switch on counts the record array in its automatic batch size. ptmi_dispatch_probes
+ * with a first-hit plane on (ptmi_set_aovs) stays refused.
+ *
+ * ptmi_probe_visibility: per probe a side x side tile, side = m + 2 * border, m a power of two in 2 ... 16 with m <= N (the rule of
+ * ptmi_probe_irradiance), sharpness_log2 = s in 0 ... 6, border 0 or 1. Interior texel j = (jx, jy), stored at (jx + border,
+ * jy + border), is the depth tile D of the probe filtered by a power-cosine lobe about n_j, the float32 direction d_j of the table
+ * built at tile m:
+ *   v_j = sum_t w_jt * D[t].xyz / sum_t w_jt,   w_jt = max(0, dot(n_j, d_t))^(2^s) * dw_t,   written as (v_j.x, v_j.y, v_j.z, 1)
+ * The exponent is a power of two so that the lobe is s squarings - the same bits on every machine and in numpy, where powf has
+ * none to offer; s = 6 is cos^64, next to DDGI's cos^50. In float32, one workgroup per probe and one wave per output texel, lane l
+ * from +0 over tile texels t = l, l + 64, ... in ascending order:
+ *   c = fma(n.z, d.z, fma(n.y, d.y, n.x * d.x));  c = c > 0 ? c : 0              as ptmi_probe_irradiance
+ *   p = c;  s times: p = p * p;  wgt = p * dw_t
+ *   a0 = a0 + wgt * D[t].x;  a1 = a1 + wgt * D[t].y;  a2 = a2 + wgt * D[t].z;  a3 = a3 + wgt     rounded product, rounded sum
+ * then the butterfly of ptmi_probe_sh over the four sums, and lane 0 writes (a0 / a3, a1 / a3, a2 / a3, 1), IEEE divisions. a3 is
+ * positive because m <= N: both tables are texel centres of the same map and N / m is a whole number, so n_j's point of the square
+ * is the centre of one of the tile's texels (N / m odd) or the corner four of them share (even), and the nearest of those has a
+ * cosine to n_j above 0.5 (the worst pair, N = 4 with m = 2, has 0.89). Its weight is then above 2^-64 * dw_t with dw_t above 1e-4
+ * at N = 64, a normal float32, and adding non-negative terms to it never takes it away. A disabled probe's tile is all zeros, border
+ * included.
+ * border = 1 surrounds the m x m interior with the texels a bilinear tap finds across the edge of the octahedral square, copies
+ * written by the same kernel after the interior. With e = m - 1, in interior coordinates:
+ *   (-1, y) <- (0, e - y)     (m, y) <- (e, e - y)     (x, -1) <- (e - x, 0)     (x, m) <- (e - x, e)
+ *   corners (-1, -1) <- (e, e)   (m, -1) <- (0, e)   (-1, m) <- (e, 0)   (m, m) <- (0, 0)
+ * dst_rgba: count * side * side * 4 floats, probe major, rows from the bottom. Reads the depth plane in place; synchronises.
+ * PTMI_E_STATE: the switch is off. PTMI_E_INVALID: params NULL, no probes in place, a bad m, s or border, a non-zero reserved word,
+ * n_floats wrong. A refusal writes nothing. There are no ptmi_multi_* counterparts, because probes have none.
+ * The ABI version stays 4: new calls only. */
+typedef struct ptmi_probe_depth_params { float max_distance; uint32_t _reserved[3]; } ptmi_probe_depth_params;
+typedef struct ptmi_probe_visibility_params { uint32_t m, sharpness_log2, border, _reserved; } ptmi_probe_visibility_params;
+int ptmi_set_probe_depth(ptmi_ctx *ctx, const ptmi_probe_depth_params *params);
+int ptmi_get_probe_depth(ptmi_ctx *ctx, uint32_t *on, ptmi_probe_depth_params *out);
+int ptmi_read_probe_depth(ptmi_ctx *ctx, float *dst_rgba, size_t n_floats);
+int ptmi_write_probe_depth(ptmi_ctx *ctx, const float *src_rgba, size_t n_floats);
+void *ptmi_probe_depth_device_ptr(ptmi_ctx *ctx);
+int ptmi_probe_visibility(ptmi_ctx *ctx, const ptmi_probe_visibility_params *params, float *dst_rgba, size_t n_floats);
 /* Back-pressure for a caller that enqueues dispatches from a loop without reading results — a preview loop; the reference paces
  * itself on requestAnimationFrame (renderer.ts:456-473). Blocks until at most max_in_flight of this context's dispatches have
  * not yet finished on the device and reports how many still are (in_flight may be NULL). max_in_flight = 0xFFFFFFFF only polls.

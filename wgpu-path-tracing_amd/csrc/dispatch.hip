@@ -109,7 +109,8 @@ struct Timed {
 // has); count_call = false: a further round of one call, which ptmi_stats.dispatches has already counted.
 // listed (ptmi_dispatch_bake and ptmi_dispatch_probes, which have checked it: bake_check, probes_check; no camera, no ap): n_frames
 // frames of every texel of listed->list, from listed->first_frame: listed->rays is the batch's ray source and the list is the batch's
-// pixels (a bake: the surface and its covered texels; probes: the probe records and the texels of the enabled probes' tiles).
+// pixels (a bake: the surface and its covered texels; probes: the probe records and the texels of the enabled probes' tiles; with
+// listed->depth_max > 0 shade(0) leaves its first-hit records as it does for the first-hit planes, for the depth plane's fold).
 int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_adaptive_params *ap, uint32_t rounds,
              const DevFlagMap *map = nullptr, bool count_call = true, const ListedRays *listed = nullptr) {
     int rc = check_ready(c, true);
@@ -135,6 +136,7 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
     // About 1.2 ms of it, 0.15 ms per launch of `shade`, were the per-wave atomics of its statistics, which the compaction now sums:
     // a launch of `shade` on a queue of no segments takes ~0.05 ms, not ~0.2; profiles/README.md, "Shade's statistics in the compaction")
     const bool auto_F = F == 0;
+    const bool depth = listed && listed->depth_max > 0.0f;      // a probe dispatch that folds the depth plane: it keeps the first-hit records
     Lane &ln = c->lane;
     if (auto_F) {
         F = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(64, (128ull << 20) / npix));
@@ -145,7 +147,7 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
             const uint64_t held = (uint64_t)ln.cap * bytes_per_path(ln.aov != nullptr, ln.paths.W != nullptr, ln.alpha.RO != nullptr);
             const uint64_t room = (uint64_t)((double)(free_b + held) * 0.9);
-            F = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(F, room / (npix * bytes_per_path(c->aov_mask != 0, c->sc.env.sampled != 0, alpha_active(c)))));
+            F = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(F, room / (npix * bytes_per_path(c->aov_mask != 0 || depth, c->sc.env.sampled != 0, alpha_active(c)))));
         }
     }
     F = std::min(F, n_frames);
@@ -163,7 +165,7 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
     TraverseConfig cfg, cfg_shadow;
     if ((rc = traverse_pick(c, true, cfg)) || (rc = traverse_pick(c, false, cfg_shadow))) return rc;      // refused before anything is made
     for (;;) {
-        rc = ensure_capacity(c, ln, (size_t)(npix * F));
+        rc = ensure_capacity(c, ln, (size_t)(npix * F), depth);
         if (rc == PTMI_OK) break;
         // out of device memory with a batch size the library chose: halve it and try again (hipMemGetInfo is a snapshot; another
         // context may have allocated since). A size the caller asked for fails loudly.
@@ -201,7 +203,7 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         DevPaths tp = ln.tail;
         tp.L = bp.L; tp.l_stride = bp.l_stride;
         if (!env_w) tp.W = nullptr;
-        float4 *const aov_rec = c->aov_mask ? ln.aov : nullptr;         // written by shade(0), read by the fold after the last bounce
+        float4 *const aov_rec = c->aov_mask || depth ? ln.aov : nullptr;      // written by shade(0), read by the folds after the last bounce
         float4 *const mom = plane_as<float4>(c, kMoments);
         unsigned long long *const ct = c->d_counters;
         uint32_t *const qlen = &c->d_control[kCwQueue], *const slen = &c->d_control[kCwShadow];    // queue lengths by bounce; shadow, by parity
@@ -252,7 +254,8 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
             }
             Timed t(c, kAccumulate, t3, ms);
             pt_launch_accumulate(ms, blocks, px, fb, bp.L, bp.l_stride, c->d_out);
-            if (aov_rec)
+            if (depth) pt_launch_accumulate_probe_depth(ms, blocks, px, fb, aov_rec, listed->depth_max, plane_as<float4>(c, kProbeDepth));
+            if (c->aov_mask)
                 pt_launch_accumulate_aov(ms, blocks, px, fb, aov_rec, c->sc.tris, c->sc.n_tris, plane_as<float4>(c, kAovAlbedo),
                                          plane_as<float4>(c, kAovNormal), plane_as<uint2>(c, kAovId));
             // the moments fold goes last: it moves mom.z on, where the other two read the listed pixels' counts. An adaptive dispatch

@@ -335,6 +335,29 @@ PT_DEV void fold_aov(const Pixels &px, uint32_t n_frames, const float4 *__restri
     }
 }
 
+// The probe depth plane (ptmi_set_probe_depth; include/ptmi.h states the fold) from the same records, for the texels of a probe dispatch:
+// (mean d, mean d * d, hit fraction, 0) with d the first hit's distance clamped to max_distance and a miss at max_distance, the means
+// following the fold of the radiance.
+template <class Pixels>
+PT_DEV void fold_probe_depth(const Pixels &px, uint32_t n_frames, const float4 *__restrict__ rec, float max_distance,
+                             float4 *__restrict__ plane) {
+    const uint32_t n = px.entries();
+    for (uint32_t j = blockIdx.x * BLOCK + threadIdx.x; j < n; j += gridDim.x * BLOCK) {
+        const size_t oi = px.band.frame_pixel(px.pixel(j));
+        const uint32_t frame0 = px.first_frame(oi);
+        const float4 p = plane[oi];
+        float acc[3] = {p.x, p.y, p.z};
+        for (uint32_t k = 0; k < n_frames; k++) {
+            const size_t li = (size_t)k * n + j;
+            const float t = ld_stream(&rec[2 * li]).w;
+            const bool hit = __float_as_uint(ld_stream(&rec[2 * li + 1]).w) != 0xFFFFFFFFu;
+            const float d = hit ? min1(t, max_distance) : max_distance;
+            fold(acc, {d, d * d, hit ? 1.0f : 0.0f}, frame0 + k);
+        }
+        plane[oi] = n_frames ? make_float4(acc[0], acc[1], acc[2], 0.0f) : p;
+    }
+}
+
 // The sample-moments plane (ptmi_set_moments) from the same clamped per-frame radiance fold_radiance folds: per pixel
 // (mean of l, mean of l^2, frames folded, 0) with l = 0.2126 r + 0.7152 g + 0.0722 b (left to right, no FMA), the means following
 // the output buffer's fold. `mom` carries no __restrict__: a listed source reads its frame index from the same plane.
@@ -367,6 +390,11 @@ __global__ __launch_bounds__(BLOCK) void k_fold_aov(Pixels px, uint32_t n_frames
                                                     const ptmi_triangle *__restrict__ tris, uint32_t n_tris, float4 *__restrict__ albedo,
                                                     float4 *__restrict__ normal, uint2 *__restrict__ ids) {
     fold_aov(px, n_frames, rec, tris, n_tris, albedo, normal, ids);
+}
+template <class Pixels>
+__global__ __launch_bounds__(BLOCK) void k_fold_probe_depth(Pixels px, uint32_t n_frames, const float4 *__restrict__ rec, float max_distance,
+                                                            float4 *__restrict__ plane) {
+    fold_probe_depth(px, n_frames, rec, max_distance, plane);
 }
 template <class Pixels>
 __global__ __launch_bounds__(BLOCK) void k_fold_moments(Pixels px, uint32_t n_frames, const float *__restrict__ L, uint32_t l_stride,
@@ -709,6 +737,15 @@ void pt_launch_accumulate_aov(hipStream_t s, int blocks, const DevPixels &px, ui
         // no first-hit fold over a bake surface: a bake is refused while those planes are on (bake.hip bake_check)
         if constexpr (std::is_same_v<decltype(src), BakedPixels>) abort();
         else hipLaunchKernelGGL(k_fold_aov<decltype(src)>, dim3(blocks), dim3(BLOCK), 0, s, src, n_frames, rec, tris, n_tris, albedo, normal, ids);
+    }, px);
+}
+void pt_launch_accumulate_probe_depth(hipStream_t s, int blocks, const DevPixels &px, uint32_t n_frames, const float4 *rec, float max_distance,
+                                      float4 *plane) {
+    std::visit([&](auto src) {
+        // the depth plane is folded over the texels of a probe dispatch and over nothing else (dispatch.hip)
+        if constexpr (std::is_same_v<decltype(src), BakedPixels>)
+            hipLaunchKernelGGL(k_fold_probe_depth<BakedPixels>, dim3(blocks), dim3(BLOCK), 0, s, src, n_frames, rec, max_distance, plane);
+        else abort();
     }, px);
 }
 void pt_launch_accumulate_moments(hipStream_t s, int blocks, const DevPixels &px, uint32_t n_frames, const float *L, uint32_t l_stride,

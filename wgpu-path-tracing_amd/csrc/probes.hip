@@ -1,8 +1,9 @@
-// probes.hip — light probes (include/ptmi.h ptmi_upload_probes, ptmi_dispatch_probes, ptmi_probe_sh, ptmi_probe_irradiance; DESIGN.md
-// §23): the probe records, the texel list of the enabled probes' tiles and the two float64 tables of a tile size, the checks of a probe
-// dispatch, the debug rays, and the two reductions that turn a probe's radiance tile into what an engine reads. The probe's ray
-// generation is with the other ray sources (pipeline.hip ProbeRays); its pixels are BakedPixels and its bounce loop the plain
-// dispatch's (dispatch.hip).
+// probes.hip — light probes (include/ptmi.h ptmi_upload_probes, ptmi_dispatch_probes, ptmi_probe_sh, ptmi_probe_irradiance,
+// ptmi_probe_visibility): the probe records, the texel list of the enabled probes' tiles and the two float64 tables
+// of a tile size, the checks of a probe dispatch, the debug rays, and the reductions that turn a probe's tiles into what an engine
+// reads: SH9 and irradiance from the radiance tile, visibility from the depth tile. The probe's ray generation is with the other ray
+// sources (pipeline.hip ProbeRays); its pixels are BakedPixels, its folds pipeline.hip's (fold_probe_depth among them) and its bounce
+// loop the plain dispatch's (dispatch.hip); the depth plane's switch is with the other planes' (ptmi_api.hip).
 // No counterpart in the reference, which renders from a camera only.
 #include "ptmi_ctx.h"
 #include "pt_math.h"
@@ -97,6 +98,59 @@ __global__ __launch_bounds__(BLOCK) void k_probe_irradiance(DevProbeAtlas a, con
     }
 }
 
+// Visibility tiles (include/ptmi.h ptmi_probe_visibility): k_probe_irradiance's shape over the probe's tile of the depth plane, with a
+// power-cosine lobe of s squarings for the clamped cosine, a fourth sum for the weights and a division for the 1 / pi. The same 28 B a
+// texel of dynamic LDS. With border = 1 the lane that writes an interior texel of the tile's rim writes the ring texels that copy it
+// as well (up to three): every ring texel has one source, so nothing is read back and nothing is written twice.
+__global__ __launch_bounds__(BLOCK) void k_probe_visibility(DevProbeAtlas a, const float4 *__restrict__ dir_dw,
+                                                            const float4 *__restrict__ normals, uint32_t m, uint32_t sharp, uint32_t border,
+                                                            float4 *__restrict__ vis) {
+    extern __shared__ float4 lds[];
+    const uint32_t i = blockIdx.x, N = 1u << a.shift, NN = N << a.shift, mm = m * m, side = m + 2u * border;
+    float4 *const dst = vis + (size_t)i * side * side;
+    if (__float_as_uint(a.probes[i].w) == 0u) {                     // (the whole workgroup)
+        for (uint32_t j = threadIdx.x; j < side * side; j += BLOCK) dst[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    float4 *const tab = lds;
+    float *const dx = reinterpret_cast<float *>(lds + NN), *const dy = dx + NN, *const dz = dy + NN;
+    const float4 *const tile = a.out + (size_t)((i / a.cols) << a.shift) * a.W + ((i % a.cols) << a.shift);
+    for (uint32_t t = threadIdx.x; t < NN; t += BLOCK) {
+        const float4 D = tile[(size_t)(t >> a.shift) * a.W + (t & (N - 1u))];
+        tab[t] = dir_dw[t]; dx[t] = D.x; dy[t] = D.y; dz[t] = D.z;
+    }
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t j = threadIdx.x >> 6; j < mm; j += WAVES) {
+        const v3 n = xyz(normals[j]);
+        float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (uint32_t t = lane; t < NN; t += 64u) {
+            const float4 d = tab[t];
+            float p = dot3(n, xyz(d));
+            p = p > 0.0f ? p : 0.0f;
+            for (uint32_t k = 0; k < sharp; k++) p = __fmul_rn(p, p);
+            const float wgt = __fmul_rn(p, d.w);
+            acc[0] = __fadd_rn(acc[0], __fmul_rn(wgt, dx[t]));
+            acc[1] = __fadd_rn(acc[1], __fmul_rn(wgt, dy[t]));
+            acc[2] = __fadd_rn(acc[2], __fmul_rn(wgt, dz[t]));
+            acc[3] = __fadd_rn(acc[3], wgt);
+        }
+        butterfly(acc);
+        if (lane != 0u) continue;
+        const float4 v = make_float4(__fdiv_rn(acc[0], acc[3]), __fdiv_rn(acc[1], acc[3]), __fdiv_rn(acc[2], acc[3]), 1.0f);
+        const uint32_t x = j % m, y = j / m, e = m - 1u;
+        dst[(size_t)(y + border) * side + (x + border)] = v;
+        if (border == 0u) continue;
+        // the ring texels that copy this one under the octahedral wrap (include/ptmi.h has the table), bordered coordinates
+        if (x == 0u) dst[(size_t)(e - y + 1u) * side] = v;                          // (-1, e - y)
+        if (x == e) dst[(size_t)(e - y + 1u) * side + (m + 1u)] = v;                // (m, e - y)
+        if (y == 0u) dst[e - x + 1u] = v;                                           // (e - x, -1)
+        if (y == e) dst[(size_t)(m + 1u) * side + (e - x + 1u)] = v;                // (e - x, m)
+        if ((x == 0u || x == e) && (y == 0u || y == e))                             // the opposite corner of the ring
+            dst[(size_t)(y ? 0u : m + 1u) * side + (x ? 0u : m + 1u)] = v;
+    }
+}
+
 // ---- the tables (include/ptmi.h states them): float64, + - * / and sqrt alone, rounded once ---------------------------------------
 constexpr double PI64 = 3.141592653589793;
 
@@ -132,15 +186,14 @@ void probe_tables(uint32_t N, float *dir_dw, float *basis) {
     }
 }
 
-// the default dynamic-LDS cap is 64 KB: raise it to what the largest tile takes, once per device
-void allow_irradiance_lds() {
-    static std::atomic<uint64_t> raised{0};
+// the default dynamic-LDS cap is 64 KB: raise it for `kernel` to what the largest tile takes, once per device. The attribute is a
+// kernel's own, so each of the two kernels that stage a tile has its own `raised`.
+void allow_tile_lds(const void *kernel, std::atomic<uint64_t> &raised) {
     int dev = 0;
     (void)hipGetDevice(&dev);
     const uint64_t bit = 1ull << (dev & 63);
     if (raised.load(std::memory_order_relaxed) & bit) return;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_probe_irradiance), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)pt_probe_irradiance_lds(6));
+    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pt_probe_irradiance_lds(6));
     raised.fetch_or(bit, std::memory_order_relaxed);
 }
 
@@ -176,8 +229,17 @@ void pt_launch_probe_sh(hipStream_t s, DevProbeAtlas a, const float *basis9, flo
     hipLaunchKernelGGL(k_probe_sh, dim3((a.count + WAVES - 1) / WAVES), dim3(BLOCK), 0, s, a, basis9, sh);
 }
 void pt_launch_probe_irradiance(hipStream_t s, DevProbeAtlas a, const float4 *dir_dw, const float4 *normals, uint32_t m, float4 *irr) {
-    allow_irradiance_lds();
+    static std::atomic<uint64_t> raised{0};
+    allow_tile_lds(reinterpret_cast<const void *>(k_probe_irradiance), raised);
     hipLaunchKernelGGL(k_probe_irradiance, dim3(a.count), dim3(BLOCK), pt_probe_irradiance_lds(a.shift), s, a, dir_dw, normals, m, irr);
+}
+
+void pt_launch_probe_visibility(hipStream_t s, DevProbeAtlas depth, const float4 *dir_dw, const float4 *normals, uint32_t m, uint32_t sharpness_log2,
+                                uint32_t border, float4 *vis) {
+    static std::atomic<uint64_t> raised{0};
+    allow_tile_lds(reinterpret_cast<const void *>(k_probe_visibility), raised);
+    hipLaunchKernelGGL(k_probe_visibility, dim3(depth.count), dim3(BLOCK), pt_probe_irradiance_lds(depth.shift), s, depth, dir_dw, normals, m,
+                       sharpness_log2, border, vis);
 }
 
 PT_HOST {
@@ -194,7 +256,8 @@ int probes_check(ptmi_ctx *c, const ptmi_probe_params *params, ListedRays *out) 
     if ((rc = resolve_params(c, params, &pp))) return rc;
     if (!c->d_probes) return fail(c, PTMI_E_INVALID, "no probes in place (ptmi_upload_probes)");
     if ((rc = listed_check(c, "a probe dispatch"))) return rc;
-    *out = ListedRays{probe_set(c), c->d_probe_list, c->probe.texels, pp.first_frame};
+    *out = ListedRays{probe_set(c), c->d_probe_list, c->probe.texels, pp.first_frame,
+                      c->probe_depth_on && c->plane[kProbeDepth] ? c->probe_depth.max_distance : 0.0f};
     return PTMI_OK;
 }
 
@@ -300,6 +363,34 @@ int ptmi_probe_irradiance(ptmi_ctx *c, uint32_t m, float *dst, size_t n_floats) 
     pt_launch_probe_irradiance(c->stream, probe_atlas(c), c->d_probe_dir_dw, c->d_probe_normals, m, irr.p);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(dst, irr.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PTMI_OK;
+}
+
+int ptmi_probe_visibility(ptmi_ctx *c, const ptmi_probe_visibility_params *params, float *dst, size_t n_floats) {
+    if (!c) return PTMI_E_INVALID;
+    if (!c->probe_depth_on) return fail(c, PTMI_E_STATE, "the probe depth plane is off (ptmi_set_probe_depth)");
+    if (!c->plane[kProbeDepth]) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
+    if (!params) return fail(c, PTMI_E_INVALID, "params is NULL");
+    const ptmi_probe_visibility_params q = *params;
+    if (q._reserved) return fail(c, PTMI_E_INVALID, "the reserved word of ptmi_probe_visibility_params is not zero");
+    if (q.sharpness_log2 > 6u) return fail(c, PTMI_E_INVALID, "sharpness_log2 = %u is above 6", q.sharpness_log2);
+    if (q.border > 1u) return fail(c, PTMI_E_INVALID, "border = %u is not 0 or 1", q.border);
+    if (c->d_probes && (!tile_ok(q.m, 2u, 16u) || q.m > c->probe.tile))
+        return fail(c, PTMI_E_INVALID, "m = %u is not a power of two in [2, min(16, tile = %u)]", q.m, c->probe.tile);
+    const size_t side = (size_t)q.m + 2u * q.border, n = (size_t)c->probe.count * side * side * 4u;
+    const int rc = reduction_ready(c, dst, n_floats, n);
+    if (rc) return rc;
+    std::vector<float> normals((size_t)q.m * q.m * 4);
+    probe_tables(q.m, normals.data(), nullptr);
+    Scratch<float4> vis;
+    HIP_TRY(c, hipMalloc(&vis.p, n * sizeof(float)));
+    HIP_TRY(c, hipMemcpyAsync(c->d_probe_normals, normals.data(), normals.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    DevProbeAtlas depth = probe_atlas(c);
+    depth.out = plane_as<float4>(c, kProbeDepth);
+    pt_launch_probe_visibility(c->stream, depth, c->d_probe_dir_dw, c->d_probe_normals, q.m, q.sharpness_log2, q.border, vis.p);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(dst, vis.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return PTMI_OK;
 }

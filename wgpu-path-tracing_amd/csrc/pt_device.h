@@ -378,6 +378,11 @@ void pt_launch_probe_sh(hipStream_t s, DevProbeAtlas a, const float *basis9, flo
 // workgroup per probe, the probe's tile and dir_dw staged in pt_probe_irradiance_lds(shift) bytes of dynamic LDS
 size_t pt_probe_irradiance_lds(uint32_t shift);
 void pt_launch_probe_irradiance(hipStream_t s, DevProbeAtlas a, const float4 *dir_dw, const float4 *normals, uint32_t m, float4 *irr);
+// vis[(i * side * side + (jy + border) * side + jx + border) * 4 ...], side = m + 2 * border, from the probes' tiles of the depth plane
+// (depth.out), filtered by the cos^(2^sharpness_log2) lobe about each normal; border = 1: the ring of wrapped copies too. The LDS of
+// pt_probe_irradiance_lds(shift).
+void pt_launch_probe_visibility(hipStream_t s, DevProbeAtlas depth, const float4 *dir_dw, const float4 *normals, uint32_t m, uint32_t sharpness_log2,
+                                uint32_t border, float4 *vis);
 void pt_launch_extend(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &sc, DevPaths p,
                       const uint32_t *queue, const uint32_t *count, float2 *hits);
 void pt_launch_extend_own(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &sc, DevPaths p,
@@ -445,6 +450,10 @@ void pt_launch_accumulate(hipStream_t s, int blocks, const DevPixels &px, uint32
 // refused while these planes are on (bake.hip bake_check)
 void pt_launch_accumulate_aov(hipStream_t s, int blocks, const DevPixels &px, uint32_t n_frames, const float4 *rec,
                               const ptmi_triangle *tris, uint32_t n_tris, float4 *albedo, float4 *normal, uint2 *ids);
+// the probe depth plane (ptmi_set_probe_depth) from the same records: (mean d, mean d^2, hit fraction, 0) with d the first hit's distance
+// clamped to max_distance, a miss max_distance. Over baked pixels only: a probe dispatch is the only one that folds it
+void pt_launch_accumulate_probe_depth(hipStream_t s, int blocks, const DevPixels &px, uint32_t n_frames, const float4 *rec, float max_distance,
+                                      float4 *plane);
 // the sample-moments plane (ptmi_set_moments) from the batch's per-path radiance; listed pixels: mom is the source's mom
 void pt_launch_accumulate_moments(hipStream_t s, int blocks, const DevPixels &px, uint32_t n_frames, const float *L, uint32_t l_stride,
                                   float4 *mom);

@@ -110,14 +110,17 @@ const struct { const char *name; size_t (*bytes)(size_t px); bool zeroed; PlaneG
     {"float canvas", per_pixel<16>, false, kByBlit}, {"8-bit canvas", per_pixel<4>, false, kByBlit},
     {"motion", per_pixel<16>, true, kWithFrame},
     {"dilate ping", per_pixel<16>, false, kByBake}, {"dilate pong", per_pixel<16>, false, kByBake},
+    {"probe depth", per_pixel<16>, true, kWithFrame},
 };
 // sets of planes: a bit per FramePlane
 constexpr uint32_t kAllPlanes = (1u << kFramePlanes) - 1u;
 static_assert(PTMI_AOV_ALBEDO << kAovAlbedo == bit(kAovAlbedo) && PTMI_AOV_NORMAL << kAovAlbedo == bit(kAovNormal) &&
               PTMI_AOV_ID << kAovAlbedo == bit(kAovId), "an AOV mask, shifted, is its set of planes");
-// the planes that exist whenever the output buffer does: the output, the AOV planes of the mask, the moments and the motion plane while on
+// the planes that exist whenever the output buffer does: the output, the AOV planes of the mask, the moments, the motion and the probe
+// depth plane while on
 uint32_t frame_set(const ptmi_ctx *c) {
-    return bit(kOut) | c->aov_mask << kAovAlbedo | (c->moments_on ? bit(kMoments) : 0u) | (c->motion_on ? bit(kMotion) : 0u);
+    return bit(kOut) | c->aov_mask << kAovAlbedo | (c->moments_on ? bit(kMoments) : 0u) | (c->motion_on ? bit(kMotion) : 0u) |
+           (c->probe_depth_on ? bit(kProbeDepth) : 0u);
 }
 // which: one PTMI_AOV_* bit (else kFramePlanes)
 FramePlane aov_plane_of(uint32_t which) {
@@ -182,8 +185,8 @@ hipError_t sync_all(ptmi_ctx *c) {
 
 size_t bytes_per_path(bool aov, bool env_w, bool alpha) { return lane_bytes_per_path(aov, env_w, alpha); }
 
-int ensure_capacity(ptmi_ctx *c, Lane &ln, size_t n) {
-    const bool aov = c->aov_mask != 0, env_w = c->sc.env.sampled != 0, alpha = alpha_active(c);
+int ensure_capacity(ptmi_ctx *c, Lane &ln, size_t n, bool first_hit) {
+    const bool aov = c->aov_mask != 0 || first_hit, env_w = c->sc.env.sampled != 0, alpha = alpha_active(c);
     if (n <= ln.cap && (!aov || ln.aov) && (!env_w || ln.paths.W) && (!alpha || ln.alpha.RO)) return PTMI_OK;
     HIP_TRY(c, sync_all(c));
     free_batch(ln);
@@ -403,7 +406,8 @@ int ptmi_upload_atlas(ptmi_ctx *c, const void *texels, uint32_t w, uint32_t h, i
 }
 
 // The planes of the new size are made before anything of the old size goes, so a failed call leaves the context as it was; for the
-// length of the call both exist, at most 72 B per pixel of the new size (output, three AOV planes, moments), small beside a batch.
+// length of the call both exist, at most 104 B per pixel of the new size (output, three AOV planes, moments, motion, probe depth), small
+// beside a batch.
 int ptmi_resize(ptmi_ctx *c, uint32_t w, uint32_t h) {
     if (!c) return PTMI_E_INVALID;
     if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 28)) return fail(c, PTMI_E_INVALID, "bad size %ux%u", w, h);
@@ -525,7 +529,8 @@ int ptmi_set_aovs(ptmi_ctx *c, uint32_t mask) {
     if (rc) return rc;
     drop_planes(c, (kAovAll & ~mask) << kAovAlbedo);
     c->aov_mask = mask;
-    if (!mask) { dfree(c->lane.buf[kAovRec]); lane_views(c->lane); }      // the records live only while a plane is on (ensure_capacity makes them)
+    if (!mask) { dfree(c->lane.buf[kAovRec]); lane_views(c->lane); }      // the records live only while a plane is on (ensure_capacity makes them;
+                                                                          // a probe dispatch that folds the depth plane makes its own again)
     return PTMI_OK;
 }
 
@@ -580,6 +585,58 @@ int ptmi_read_moments(ptmi_ctx *c, float *dst, size_t n_floats) {
 }
 
 void *ptmi_moments_device_ptr(ptmi_ctx *c) { return c && c->moments_on ? c->plane[kMoments] : nullptr; }
+
+// (the fold and the reduction of the plane: dispatch.hip, probes.hip)
+int ptmi_set_probe_depth(ptmi_ctx *c, const ptmi_probe_depth_params *params) {
+    if (!c) return PTMI_E_INVALID;
+    if (params) {
+        if (!std::isfinite(params->max_distance) || !(params->max_distance > 0.0f))
+            return fail(c, PTMI_E_INVALID, "max_distance %g is not finite and > 0", (double)params->max_distance);
+        for (uint32_t r : params->_reserved) if (r) return fail(c, PTMI_E_INVALID, "a reserved word of ptmi_probe_depth_params is not zero");
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, sync_all(c));                     // nothing in flight writes a plane or a record that goes
+    if (params) {
+        const int rc = make_planes(c, bit(kProbeDepth), (size_t)c->W * c->H, c->plane);      // a plane already on keeps its contents
+        if (rc) return rc;
+        c->probe_depth = *params;
+    } else {
+        drop_planes(c, bit(kProbeDepth));
+        c->probe_depth = {};
+        if (!c->aov_mask) { dfree(c->lane.buf[kAovRec]); lane_views(c->lane); }      // the records a probe dispatch kept for the fold
+    }
+    c->probe_depth_on = params != nullptr;
+    return PTMI_OK;
+}
+
+int ptmi_get_probe_depth(ptmi_ctx *c, uint32_t *on, ptmi_probe_depth_params *out) {
+    if (!c || !on) return PTMI_E_INVALID;
+    *on = c->probe_depth_on ? 1u : 0u;
+    if (out) *out = c->probe_depth;
+    return PTMI_OK;
+}
+
+int ptmi_read_probe_depth(ptmi_ctx *c, float *dst, size_t n_floats) {
+    if (!c) return PTMI_E_INVALID;
+    if (!dst) return fail(c, PTMI_E_INVALID, "dst is NULL");
+    if (!c->probe_depth_on) return fail(c, PTMI_E_STATE, "the probe depth plane is off (ptmi_set_probe_depth)");
+    if (!c->plane[kProbeDepth]) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
+    return read_plane(c, kProbeDepth, c->plane[kProbeDepth], dst, n_floats, 4);
+}
+
+int ptmi_write_probe_depth(ptmi_ctx *c, const float *src, size_t n_floats) {
+    if (!c) return PTMI_E_INVALID;
+    if (!src) return fail(c, PTMI_E_INVALID, "src is NULL");
+    if (!c->probe_depth_on) return fail(c, PTMI_E_STATE, "the probe depth plane is off (ptmi_set_probe_depth)");
+    if (!c->plane[kProbeDepth]) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
+    if (n_floats != (size_t)c->W * c->H * 4) return fail(c, PTMI_E_INVALID, "expected %zu floats, got %zu", (size_t)c->W * c->H * 4, n_floats);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, sync_all(c));
+    HIP_TRY(c, hipMemcpy(c->plane[kProbeDepth], src, n_floats * 4, hipMemcpyHostToDevice));
+    return PTMI_OK;
+}
+
+void *ptmi_probe_depth_device_ptr(ptmi_ctx *c) { return c && c->probe_depth_on ? c->plane[kProbeDepth] : nullptr; }
 
 int ptmi_denoise(ptmi_ctx *c, const ptmi_denoise_params *p, float *dst_rgba, size_t n_floats) {
     if (!c) return PTMI_E_INVALID;

@@ -17,7 +17,8 @@
 //   scene_skin.hip     skinned triangles posed on the device: the list, the corner records, the rest pose, the check and write kernel
 //   scene_morph.hip    morphed triangles posed on the device: the list, the sparse delta rows, the rest pose, the check and write kernel
 //   bake.hip           lightmap baking: the surface's records and covered list, the checks of a bake, the gutter fill, the debug rays
-//   probes.hip         light probes: the records, tables and texel list, the checks of a probe dispatch, the SH9 and irradiance reductions
+//   probes.hip         light probes: the records, tables and texel list, the checks of a probe dispatch, the SH9, irradiance and
+//                      visibility reductions, the depth plane's switch
 #pragma once
 #include "ptmi.h"
 #include "pt_device.h"
@@ -148,6 +149,7 @@ enum FramePlane {
     kBlitF32, kBlitU8,                             // canvas staging of ptmi_blit
     kMotion,                                       // the motion plane of ptmi_set_motion: where each pixel's surface was in `from`
     kBakeA, kBakeB,                                // ptmi_bake_dilate: the two ping-pong planes (rgb, state)
+    kProbeDepth,                                   // the depth plane of ptmi_set_probe_depth: (mean d, mean d^2, hit fraction, 0) per probe texel
     kFramePlanes
 };
 
@@ -160,7 +162,8 @@ enum LaneBuf {
     kTailO, kTailD, kTailC, kPid,                  // state by queue slot after the repack, and the path id of each such slot
     kQueue0, kQueue1,
     kOcc,                                          // occlusion bytes (ptmi_debug_occluded)
-    kAovRec,                                       // first-hit records of bounce 0 (k_shade<true>); only while AOV planes are on
+    kAovRec,                                       // first-hit records of bounce 0 (k_shade<true>); only while AOV planes are on, or
+                                                   // made by a probe dispatch while the probe depth plane is
     kPathW, kTailW,                                // the environment's MIS weight of a bounce ray, by path and (after the repack) by queue
                                                    // slot; only while a sampled environment is in place
     kAlphaO, kAlphaD, kAlphaList0, kAlphaList1, kAlphaHits,   // alpha cutouts (pt_device.h DevAlpha): scratch rays, the two retry lists,
@@ -199,6 +202,7 @@ struct Lane {
     hipStream_t side = nullptr;           // `shadow` of bounce b beside the kernels of bounce b + 1
     hipEvent_t ev_ready = nullptr, ev_shadow[2] = {nullptr, nullptr};
     float4 *aov = nullptr;                // first-hit records of bounce 0, 32 B per path (k_shade<true>); only while AOV planes are on
+                                          // or since a probe dispatch with the depth plane on
     DevAlpha alpha{};                     // the alpha resolve loops' arrays (RO NULL: none); cutoff, control, stats and max_layers are set per use
 };
 
@@ -282,6 +286,8 @@ struct ptmi_ctx {
     float *d_probe_basis = nullptr;                    // tile * tile * 9
     float4 *d_probe_normals = nullptr;                 // room for the 16 x 16 directions of ptmi_probe_irradiance's output tile
     struct ptmi_probe_status probe{};                  // what ptmi_probe_status reports (texels: entries of the list)
+    bool probe_depth_on = false;                       // ptmi_set_probe_depth: plane[kProbeDepth] is present while on and the output buffer exists
+    ptmi_probe_depth_params probe_depth{};             // ... and its params while on
     // the counter and control words (pt_device.h CounterWord, ControlWord): made and zeroed by ptmi_create
     unsigned long long *d_counters = nullptr;          // kCounterWords
     uint32_t *d_control = nullptr;                     // kControlWords
@@ -315,7 +321,8 @@ void default_options(ptmi_options &o);
 hipError_t sync_all(ptmi_ctx *c);
 size_t bytes_per_path(bool aov, bool env_w, bool alpha);
 void lane_views(Lane &ln);
-int ensure_capacity(ptmi_ctx *c, Lane &ln, size_t n);
+// first_hit: the caller needs the first-hit records although no AOV plane is on (a probe dispatch with the depth plane on)
+int ensure_capacity(ptmi_ctx *c, Lane &ln, size_t n, bool first_hit = false);
 enum PlaneGroup { kWithFrame, kByDenoise, kByAdaptive, kByReproject, kByBlit, kByBake };     // when a plane is made (the kFrame table)
 constexpr uint32_t bit(FramePlane k) { return 1u << k; }                            // sets of planes: a bit per FramePlane
 uint32_t group_set(PlaneGroup g);
@@ -333,7 +340,8 @@ void bake_forget(ptmi_ctx *c);
 int bake_check(ptmi_ctx *c, const ptmi_bake_params *params, ptmi_bake_params *out);
 // A listed first-ray source, as ptmi_dispatch_bake and ptmi_dispatch_probes describe theirs to dispatch(): where the first rays come from,
 // the ascending frame indices of the texels that get them (device memory), how many, and the first frame.
-struct ListedRays { DevRays rays; const uint32_t *list; uint32_t count, first_frame; };
+// depth_max > 0 (probes with ptmi_set_probe_depth on): the batch keeps its first-hit records and folds them into the depth plane.
+struct ListedRays { DevRays rays; const uint32_t *list; uint32_t count, first_frame; float depth_max = 0.0f; };
 // what every listed dispatch requires of the context (`what`: "a bake", "a probe dispatch"): no first-hit plane, the whole frame
 int listed_check(ptmi_ctx *c, const char *what);
 

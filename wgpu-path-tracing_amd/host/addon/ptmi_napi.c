@@ -1144,6 +1144,83 @@ static napi_value js_probe_irradiance(napi_env env, napi_callback_info info) {
     return argv[2];
 }
 
+/* ---- probe visibility (include/ptmi.h ptmi_set_probe_depth, ptmi_probe_visibility) ---- */
+
+/* setProbeDepth(h, maxDistance or null): the depth plane on with this clamp, or off */
+static napi_value js_set_probe_depth(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    handle *h = get_single_handle(env, info, 2, argv, "setProbeDepth");
+    if (!h) return NULL;
+    ptmi_probe_depth_params prm;
+    napi_valuetype t;
+    double d = 0.0;
+    memset(&prm, 0, sizeof prm);
+    const int on = napi_typeof(env, argv[1], &t) == napi_ok && t == napi_number && napi_get_value_double(env, argv[1], &d) == napi_ok;
+    prm.max_distance = (float)d;
+    int rc = ptmi_set_probe_depth(h->ctx, on ? &prm : NULL);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_set_probe_depth");
+    return NULL;
+}
+
+/* getProbeDepth(h) -> maxDistance while the plane is on, else null */
+static napi_value js_get_probe_depth(napi_env env, napi_callback_info info) {
+    napi_value argv[1];
+    handle *h = get_single_handle(env, info, 1, argv, "getProbeDepth");
+    if (!h) return NULL;
+    uint32_t on = 0;
+    ptmi_probe_depth_params prm;
+    int rc = ptmi_get_probe_depth(h->ctx, &on, &prm);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_get_probe_depth");
+    napi_value v;
+    if (on) NAPI_OK(env, napi_create_double(env, (double)prm.max_distance, &v));
+    else NAPI_OK(env, napi_get_null(env, &v));
+    return v;
+}
+
+/* readProbeDepth(h, Float32Array dst of width*height*4): the depth plane */
+static napi_value js_read_probe_depth(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    handle *h = get_single_handle(env, info, 2, argv, "readProbeDepth");
+    if (!h) return NULL;
+    void *p; size_t n;
+    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
+    int rc = ptmi_read_probe_depth(h->ctx, (float *)p, n / 4);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_read_probe_depth");
+    return argv[1];
+}
+
+/* writeProbeDepth(h, Float32Array src of width*height*4): restores a cached plane */
+static napi_value js_write_probe_depth(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    handle *h = get_single_handle(env, info, 2, argv, "writeProbeDepth");
+    if (!h) return NULL;
+    void *p; size_t n;
+    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
+    int rc = ptmi_write_probe_depth(h->ctx, (const float *)p, n / 4);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_write_probe_depth");
+    return NULL;
+}
+
+/* probeVisibility(h, {m, sharpness, border}, Float32Array dst of count * side * side * 4), side = m + 2 * border */
+static napi_value js_probe_visibility(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    handle *h = get_single_handle(env, info, 3, argv, "probeVisibility");
+    if (!h) return NULL;
+    ptmi_probe_visibility_params prm;
+    napi_valuetype t;
+    memset(&prm, 0, sizeof prm);
+    if (napi_typeof(env, argv[1], &t) == napi_ok && t == napi_object) {
+        prm.m = get_u32_prop(env, argv[1], "m", 0);
+        prm.sharpness_log2 = get_u32_prop(env, argv[1], "sharpness", 6);
+        prm.border = get_u32_prop(env, argv[1], "border", 0);
+    }
+    void *p; size_t n;
+    if (!get_bytes(env, argv[2], &p, &n)) return NULL;
+    int rc = ptmi_probe_visibility(h->ctx, &prm, (float *)p, n / 4);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_probe_visibility");
+    return argv[2];
+}
+
 /* readMoments(h, Float32Array dst of width*height*4): the sample-moments plane */
 static napi_value js_read_moments(napi_env env, napi_callback_info info) {
     napi_value argv[2];
@@ -1299,6 +1376,8 @@ static napi_value init(napi_env env, napi_value exports) {
         {"bakeDilate", js_bake_dilate},
         {"uploadProbes", js_upload_probes}, {"dispatchProbes", js_dispatch_probes}, {"probeStatus", js_probe_status},
         {"probeSh", js_probe_sh}, {"probeIrradiance", js_probe_irradiance},
+        {"setProbeDepth", js_set_probe_depth}, {"getProbeDepth", js_get_probe_depth}, {"readProbeDepth", js_read_probe_depth},
+        {"writeProbeDepth", js_write_probe_depth}, {"probeVisibility", js_probe_visibility},
         {"buildBvh", js_build_bvh}, {"emissiveLights", js_emissive_lights},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

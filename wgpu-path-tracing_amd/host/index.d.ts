@@ -173,10 +173,16 @@ export class Renderer {
    *  (probe i owns tile (i % cols, i / cols); probes.js atlasSize gives the size), `frames` paths per atlas texel (default 64).
    *  radiance: width*height float4; sh: 27 floats per probe (k major, rgb minor); irradiance: m*m float4 per probe (E / pi, w = 1), or
    *  null without `irradiance: m`. The frame takes the atlas's size and accumulation restarts. Punctual lights reach a probe only
-   *  through later bounces. Throws with several devices and while first-hit planes are on; synchronises */
+   *  through later bounces. Throws with several devices and while first-hit planes are on; synchronises.
+   *  visibility (include/ptmi.h ptmi_set_probe_depth, ptmi_probe_visibility): also depth, width*height float4 (mean distance, mean
+   *  squared distance, hit fraction, 0), and visibility, (tile + 2 * border)^2 float4 per probe; sharpness is the log2 of the lobe's
+   *  exponent (default 6), maxDistance defaults to 1.5 cell diagonals of `grid`; with border the irradiance tiles get their ring of
+   *  wrapped texels too, (m + 2)^2 float4 per probe */
   bakeProbes(opts: { positions?: ArrayLike<number>; grid?: { min: number[]; max: number[]; counts: number[] }; enabled?: ArrayLike<number | boolean>;
-                     tile?: number; frames?: number; irradiance?: number }):
-    { radiance: Float32Array; sh: Float32Array; irradiance: Float32Array | null; width: number; height: number; count: number };
+                     tile?: number; frames?: number; irradiance?: number;
+                     visibility?: { tile: number; sharpness?: number; maxDistance?: number; border?: boolean } | null }):
+    { radiance: Float32Array; sh: Float32Array; irradiance: Float32Array | null; depth: Float32Array | null; visibility: Float32Array | null;
+      width: number; height: number; count: number };
   /** first-hit planes (include/ptmi.h ptmi_set_aovs); with several devices each keeps its strips and readAov assembles the plane */
   setAovs(names: Array<'albedo' | 'normal' | 'id'>): void;
   /** width*height entries, index y*width+x: 'albedo' / 'normal' 4 floats each, 'id' 2 uint32 (triangle, material) */

@@ -8,6 +8,14 @@
  *     position = lo + (hi - lo) * ((i + 0.5) / n)
  * atlasSize(count, tile) -> { width, height }: cols = the smallest integer with cols * cols >= count, rows = ceil(count / cols).
  * records(positions, enabled) -> ArrayBuffer of 16-byte ptmi_probe records; enabled: flags per probe (absent: every probe).
+ * maxDistance(lo, hi, counts) -> the default clamp of the probe depth plane (ptmi_set_probe_depth) for that lattice, 1.5 times the
+ *   cell diagonal (DDGI's convention): with c = (hi - lo) / n along each axis, in doubles, rounded once by Math.fround,
+ *     1.5 * sqrt((cx * cx + cy * cy) + cz * cz)
+ * addBorder(tiles, m) -> Float32Array: count tiles of m x m x 4 floats (ptmi_probe_irradiance's, or ptmi_probe_visibility's with
+ *   border = 0) with the ring of texels a bilinear tap needs across the edge of the octahedral square: (m + 2) x (m + 2) x 4 each,
+ *   interior texel (x, y) at (x + 1, y + 1). A pure index permutation, the table of include/ptmi.h: with e = m - 1,
+ *     (-1, y) <- (0, e - y)    (m, y) <- (e, e - y)    (x, -1) <- (e - x, 0)    (x, m) <- (e - x, e)
+ *     corners (-1, -1) <- (e, e)   (m, -1) <- (0, e)   (-1, m) <- (e, 0)   (m, m) <- (0, 0)
  */
 
 function grid(lo, hi, counts) {
@@ -41,4 +49,31 @@ function records(positions, enabled) {
   return buf;
 }
 
-module.exports = { grid: grid, atlasSize: atlasSize, records: records };
+function maxDistance(lo, hi, counts) {
+  var cx = (hi[0] - lo[0]) / counts[0], cy = (hi[1] - lo[1]) / counts[1], cz = (hi[2] - lo[2]) / counts[2];
+  return Math.fround(1.5 * Math.sqrt((cx * cx + cy * cy) + cz * cz));
+}
+
+// the interior texel that texel (x, y) of the bordered tile copies, x and y in interior coordinates (-1 ... m)
+function borderSource(x, y, m) {
+  var e = m - 1, outX = x < 0 || x > e, outY = y < 0 || y > e;
+  if (outX && outY) return [x < 0 ? e : 0, y < 0 ? e : 0];
+  if (outX) return [x < 0 ? 0 : e, e - y];
+  if (outY) return [e - x, y < 0 ? 0 : e];
+  return [x, y];
+}
+
+function addBorder(tiles, m) {
+  var side = m + 2, count = Math.floor(tiles.length / (m * m * 4));
+  var out = new Float32Array(count * side * side * 4);
+  for (var i = 0; i < count; i++)
+    for (var y = -1; y <= m; y++)
+      for (var x = -1; x <= m; x++) {
+        var s = borderSource(x, y, m);
+        var from = ((i * m + s[1]) * m + s[0]) * 4, to = ((i * side + y + 1) * side + x + 1) * 4;
+        out[to] = tiles[from]; out[to + 1] = tiles[from + 1]; out[to + 2] = tiles[from + 2]; out[to + 3] = tiles[from + 3];
+      }
+  return out;
+}
+
+module.exports = { grid: grid, atlasSize: atlasSize, records: records, maxDistance: maxDistance, addBorder: addBorder };

@@ -12,7 +12,8 @@
  *                       --alpha-cutout --alpha-blend --alpha-seed N --alpha-layers N --animation N --time S
  *                       --camera N --projection ortho|panorama --ymag V --hdr out.hdr
  *                       --bake W,H --bake-dilate N --bake-bias B
- *                       --probes nx,ny,nz --probe-tile N --probe-irradiance M]
+ *                       --probes nx,ny,nz --probe-tile N --probe-irradiance M
+ *                       --probe-visibility M [--probe-sharpness S] [--probe-max-distance D] [--probe-border]]
  * --batch K traces K frames per dispatch instead of one. --denoise keeps the denoiser's planes and makes --png the tone-mapped
  * denoised image (include/ptmi.h ptmi_denoise, default parameters). --adaptive renders to a noise level instead of --frames
  * (include/ptmi.h ptmi_dispatch_adaptive): rounds until none lists a pixel, or --rounds R of them; the JSON line then also holds
@@ -52,6 +53,10 @@
  * --probe-irradiance M also the M x M irradiance tiles. out.f32 then holds the radiance atlas (its size in the JSON line's probes:
  * { width, height, count, tile }), and beside it <out minus .f32>.sh.f32 holds 27 floats per probe and, with --probe-irradiance,
  * <out minus .f32>.irr.f32 the M * M float4 per probe. Not with --devices, --denoise, --aov, --adaptive or --bake.
+ * --probe-visibility M also gathers the probes' depth and writes <out minus .f32>.vis.f32, the M x M visibility tiles (mean distance,
+ * mean squared distance, hit fraction, 1; include/ptmi.h ptmi_probe_visibility): --probe-sharpness S the log2 of the lobe's exponent
+ * (default 6), --probe-max-distance D the clamp (default 1.5 cell diagonals of the lattice), --probe-border a ring of wrapped texels
+ * for bilinear taps around every visibility tile and every irradiance tile of out.irr.f32: (M + 2)^2 float4 per probe.
  */
 var fs = require('fs');
 var host = require('./renderer');
@@ -133,11 +138,15 @@ r.loadModel(scenePath).then(function () {
     if (devices || denoise || aov || adaptive) throw new Error('--probes does not go with --devices, --denoise, --aov or --adaptive');
     if (!r.sceneBounds) throw new Error('--probes needs a scene with a hierarchy (its bounds)');
     var stem = outPath.replace(/\.f32$/, '');
+    var visTile = arg('probe-visibility', 0);
     probeSet = r.bakeProbes({ grid: { min: r.sceneBounds.min, max: r.sceneBounds.max, counts: counts }, tile: arg('probe-tile', 8),
-                              frames: frames, irradiance: arg('probe-irradiance', 0) });
+                              frames: frames, irradiance: arg('probe-irradiance', 0),
+                              visibility: visTile ? { tile: visTile, sharpness: arg('probe-sharpness', 6), maxDistance: arg('probe-max-distance', 0),
+                                                      border: process.argv.indexOf('--probe-border') >= 0 } : null });
     out = probeSet.radiance; W = probeSet.width; H = probeSet.height;
     fs.writeFileSync(stem + '.sh.f32', Buffer.from(probeSet.sh.buffer));
     if (probeSet.irradiance) fs.writeFileSync(stem + '.irr.f32', Buffer.from(probeSet.irradiance.buffer));
+    if (probeSet.visibility) fs.writeFileSync(stem + '.vis.f32', Buffer.from(probeSet.visibility.buffer));
   } else if (adaptive) {
     r.setAdaptive(adaptive);
     var rounds = arg('rounds', 0);

@@ -680,6 +680,11 @@ Renderer.prototype.bake = function (opts) {
  * width * height float4 atlas (probe i owns tile (i % cols, i / cols), row 0 at the bottom), sh: 27 floats per probe (k major, rgb
  * minor), irradiance: m * m float4 per probe (E / pi, w = 1) or null, width, height, count }. One device only; the first-hit planes
  * must be off. The frame takes the atlas's size (probes.js atlasSize) and accumulation restarts. Synchronises.
+ * visibility: { tile (m), sharpness (log2 of the lobe's exponent, default 6), maxDistance (default: probes.js maxDistance of the grid),
+ * border (default false) } additionally gathers the depth plane (ptmi_set_probe_depth) and returns depth: the width * height float4
+ * plane (mean distance, mean squared distance, hit fraction, 0), and visibility: (m + 2 * border)^2 float4 per probe
+ * (ptmi_probe_visibility; INTEGRATION.md 1.21 has the shader's test). With border the irradiance tiles get their ring of wrapped
+ * texels too (probes.js addBorder): (m + 2)^2 float4 per probe.
  */
 Renderer.prototype.bakeProbes = function (opts) {
   opts = opts || {};
@@ -692,22 +697,43 @@ Renderer.prototype.bakeProbes = function (opts) {
   var count = Math.floor(positions.length / 3);
   var tile = opts.tile || 8, frames = opts.frames === undefined ? 64 : opts.frames, m = opts.irradiance || 0;
   var size = probes.atlasSize(count, tile), W = size.width, H = size.height;
+  var vis = opts.visibility || null, visMax = 0;
+  if (vis) {
+    visMax = vis.maxDistance || (opts.grid ? probes.maxDistance(opts.grid.min, opts.grid.max, opts.grid.counts) : 0);
+    if (!(visMax > 0)) throw new Error('bakeProbes: visibility.maxDistance (positions have no lattice to take it from)');
+    if (!vis.tile) throw new Error('bakeProbes: visibility.tile');
+  }
   this.stop();
   if (W !== this.width || H !== this.height) this.resize(W, H);
   this.addon.uploadProbes(this.ctx, probes.records(positions, opts.enabled), tile);
   var radiance = new Float32Array(W * H * 4), sh = new Float32Array(count * 27), irr = m ? new Float32Array(count * m * m * 4) : null;
+  var depth = null, visibility = null;
   try {
+    if (vis) {
+      this.addon.setProbeDepth(this.ctx, visMax);
+      depth = new Float32Array(W * H * 4);
+      this.addon.writeProbeDepth(this.ctx, depth);                      // a plane left on by the caller: this gather's alone
+    }
     this.addon.writeOutput(this.ctx, radiance);                         // tiles of disabled probes read as zeros
     this.addon.dispatchProbes(this.ctx, { firstFrame: 0 }, frames);
     this.addon.readOutput(this.ctx, radiance);
     this.addon.probeSh(this.ctx, sh);
     if (irr) this.addon.probeIrradiance(this.ctx, m, irr);
+    if (vis) {
+      var side = vis.tile + (vis.border ? 2 : 0);
+      this.addon.readProbeDepth(this.ctx, depth);
+      visibility = new Float32Array(count * side * side * 4);
+      this.addon.probeVisibility(this.ctx, { m: vis.tile, sharpness: vis.sharpness === undefined ? 6 : vis.sharpness, border: vis.border ? 1 : 0 },
+                                 visibility);
+      if (irr && vis.border) irr = probes.addBorder(irr, m);
+    }
   } finally {
+    if (vis) this.addon.setProbeDepth(this.ctx, null);
     this.addon.uploadProbes(this.ctx, null, 0);
   }
   this.reprojectFrom = null;
   this.frameIndex = 0;                      // the output buffer holds a probe atlas now: a camera's accumulation starts over
-  return { radiance: radiance, sh: sh, irradiance: irr, width: W, height: H, count: count };
+  return { radiance: radiance, sh: sh, irradiance: irr, depth: depth, visibility: visibility, width: W, height: H, count: count };
 };
 
 /** The reference's blit pass (renderer.ts:434-449, blit.wgsl): tone-mapped 8-bit canvas, row 0 = top. */

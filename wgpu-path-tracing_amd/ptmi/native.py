@@ -58,6 +58,8 @@ EXPORTS = [
     "ptmi_upload_bake_surface", "ptmi_dispatch_bake", "ptmi_bake_status", "ptmi_bake_dilate", "ptmi_debug_bake_rays",
     "ptmi_upload_probes", "ptmi_dispatch_probes", "ptmi_probe_status", "ptmi_probe_sh", "ptmi_probe_irradiance",
     "ptmi_debug_probe_rays", "ptmi_debug_probe_tables",
+    "ptmi_set_probe_depth", "ptmi_get_probe_depth", "ptmi_read_probe_depth", "ptmi_write_probe_depth", "ptmi_probe_depth_device_ptr",
+    "ptmi_probe_visibility",
 ]
 MULTI_LOOPBACK = 1
 MULTI_PLANE_MOMENTS, MULTI_PLANE_OUTPUT = 0x100, 0x200      # gather_planes: with the AOV_* bits
@@ -301,6 +303,16 @@ class ProbeStatus(ctypes.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class ProbeDepthParams(ctypes.Structure):
+    """ptmi_probe_depth_params (include/ptmi.h ptmi_set_probe_depth)"""
+    _fields_ = [("max_distance", ctypes.c_float), ("reserved", ctypes.c_uint32 * 3)]
+
+
+class ProbeVisibilityParams(ctypes.Structure):
+    """ptmi_probe_visibility_params (include/ptmi.h ptmi_probe_visibility)"""
+    _fields_ = [("m", ctypes.c_uint32), ("sharpness_log2", ctypes.c_uint32), ("border", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 class Stats(ctypes.Structure):
     _fields_ = [("paths", ctypes.c_uint64), ("segments", ctypes.c_uint64), ("shadow_rays", ctypes.c_uint64),
                 ("dispatches", ctypes.c_uint64), ("frames", ctypes.c_uint64),
@@ -370,6 +382,12 @@ _PROBES = {
     "ptmi_probe_sh": [ctypes.c_void_p, ctypes.c_size_t],
     "ptmi_probe_irradiance": [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t],
     "ptmi_debug_probe_rays": [ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 6,
+    "ptmi_set_probe_depth": [ctypes.c_void_p],
+    "ptmi_get_probe_depth": [ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p],
+    "ptmi_read_probe_depth": [ctypes.c_void_p, ctypes.c_size_t],
+    "ptmi_write_probe_depth": [ctypes.c_void_p, ctypes.c_size_t],
+    "ptmi_probe_depth_device_ptr": [],
+    "ptmi_probe_visibility": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t],
 }
 _lib = None
 
@@ -449,6 +467,8 @@ def load():
                 getattr(L, name).argtypes = [vp] + args
         if "ptmi_debug_probe_tables" in EXPORTS:
             L.ptmi_debug_probe_tables.argtypes = [u32, vp, vp]
+        if "ptmi_probe_depth_device_ptr" in EXPORTS:
+            L.ptmi_probe_depth_device_ptr.restype = vp
         _lib = L
     return _lib
 
@@ -1140,6 +1160,44 @@ class Context(_Handle):
         self._ck(self.L.ptmi_debug_probe_rays(self.h, self._probe_params(first_frame, reserved), n, _p(xs), _p(ys), _p(frames),
                                               _p(o), _p(d), _p(rng)))
         return o, d, rng
+
+    # -- probe visibility (include/ptmi.h ptmi_set_probe_depth, ptmi_probe_visibility) --------------------------
+    def set_probe_depth(self, max_distance=None, reserved=(0, 0, 0)):
+        """turns the probe depth plane on with this clamp (ptmi.probes.max_distance gives a lattice's default); None turns it off"""
+        if max_distance is None:
+            self._ck(self.L.ptmi_set_probe_depth(self.h, None))
+            return
+        self._ck(self.L.ptmi_set_probe_depth(self.h, ctypes.byref(ProbeDepthParams(max_distance, (ctypes.c_uint32 * 3)(*reserved)))))
+
+    def get_probe_depth(self):
+        """the clamp (a float) while the plane is on, else None"""
+        on, p = ctypes.c_uint32(0), ProbeDepthParams()
+        self._ck(self.L.ptmi_get_probe_depth(self.h, ctypes.byref(on), ctypes.byref(p)))
+        return float(p.max_distance) if on.value else None
+
+    def read_probe_depth(self, n_floats=None):
+        """(H, W, 4) float32: (mean d, mean d^2, hit fraction, 0) per probe texel. n_floats overrides the count passed (for tests)."""
+        out = np.zeros((max(self.height, 1), max(self.width, 1), 4), np.float32)
+        self._ck(self.L.ptmi_read_probe_depth(self.h, _p(out), out.size if n_floats is None else n_floats))
+        return out
+
+    def write_probe_depth(self, plane, n_floats=None):
+        """restores a cached plane: W * H * 4 float32"""
+        a = np.ascontiguousarray(plane, np.float32)
+        self._ck(self.L.ptmi_write_probe_depth(self.h, _p(a), a.size if n_floats is None else n_floats))
+
+    def probe_depth_device_ptr(self):
+        return self.L.ptmi_probe_depth_device_ptr(self.h)
+
+    def probe_visibility(self, m, sharpness_log2=6, border=False, reserved=0, n_floats=None):
+        """the visibility tile of every probe, the depth plane filtered by cos^(2^sharpness_log2): (count, side, side, 4) float32 with
+        side = m + 2 * border, (mean d, mean d^2, hit fraction, 1); zeros for a disabled probe"""
+        n, b = self.probe_status().count, int(border)
+        side = m + 2 * b if 0 < m <= 64 and 0 <= b <= 1 else 1
+        out = np.zeros((n, side, side, 4), np.float32)
+        q = ProbeVisibilityParams(m, sharpness_log2, b, reserved)
+        self._ck(self.L.ptmi_probe_visibility(self.h, ctypes.byref(q), _p(out), out.size if n_floats is None else n_floats))
+        return out
 
     # -- motion: reprojection across a geometry edit (include/ptmi.h ptmi_set_motion) ---------------------------
     def set_motion(self, on=True):
