@@ -1228,6 +1228,39 @@ int ptmi_alpha_blend_status(ptmi_ctx *ctx, struct ptmi_alpha_blend_status *out);
 int ptmi_multi_set_alpha_blend(ptmi_multi *m, const float *factor, uint32_t n_materials, const ptmi_alpha_blend_params *params);
 int ptmi_multi_alpha_blend_status(ptmi_multi *m, struct ptmi_alpha_blend_status *out);
 
+/* ---- the frame scissor -------------------------------------- */
+/* A plain ptmi_dispatch traces no camera path of a pixel none of whose camera rays can meet the scene's root box: such a path ends at
+ * bounce 0 with radiance 0 whatever its random numbers, so the output, the planes and every field of ptmi_stats are what they are
+ * without the scissor, bit for bit (the paths not traced are added to segments and segments_by_bounce[0]). The rectangle is worked out
+ * per dispatch, on the host, from the camera and the root box, for every jitter and every lens sample, with margins for rounding. It
+ * is not applied (reason says why) to anything a miss can still contribute to, or whose pixels are not the whole band.
+ * PTMI_SCISSOR=0 in the environment when the context is created switches it off.
+ * ptmi_scissor_status: the last dispatch of any kind that had something to enqueue (zeros before the first; a dispatch of 0 frames,
+ * of a context that owns no row of the frame, or of an empty texel list returns before the scissor is looked at and leaves the
+ * previous status in place); skipped counts since ptmi_reset_stats. Does not
+ * synchronise: everything it reports is known on the host when the dispatch returns. */
+enum {
+    PTMI_SCISSOR_APPLIED = 0,
+    PTMI_SCISSOR_OFF = 1,            /* PTMI_SCISSOR=0 */
+    PTMI_SCISSOR_NOT_PLAIN = 2,      /* ptmi_dispatch_adaptive, ptmi_dispatch_bake, ptmi_dispatch_probes */
+    PTMI_SCISSOR_ENVIRONMENT = 3,    /* an environment map is in place (sampled or looked up): a miss adds its radiance */
+    PTMI_SCISSOR_MEDIUM = 4,         /* a medium is in place: a ray may scatter before it leaves */
+    PTMI_SCISSOR_AOV = 5,            /* a first-hit plane is on: a miss writes its record */
+    PTMI_SCISSOR_MOMENTS = 6,        /* the moments plane is on */
+    PTMI_SCISSOR_ALPHA = 7,          /* an active cutoff or blend table */
+    PTMI_SCISSOR_PROJECTION = 8,     /* the camera is not a perspective camera */
+    PTMI_SCISSOR_NO_PROMISE = 9,     /* the camera is inside the (inflated) box, a corner of it is not in front of the camera, a field
+                                        is not finite or out of the range the argument covers, or the scene is empty */
+    PTMI_SCISSOR_NOTHING = 10        /* the rectangle holds every pixel of the context's rows: nothing to skip */
+};
+struct ptmi_scissor_status {
+    uint32_t x0, x1, y0, y1;  /* the rectangle [x0, x1) x [y0, y1) in frame pixels; the whole frame where none was worked out */
+    uint32_t applied;         /* 1: the last dispatch traced the pixels inside only */
+    uint32_t reason;          /* PTMI_SCISSOR_* */
+    uint64_t skipped;         /* paths not traced since ptmi_reset_stats */
+};                            /* 32 bytes */
+int ptmi_scissor_status(ptmi_ctx *ctx, struct ptmi_scissor_status *out);
+
 /* ---- statistics ----------------------------------------------------------- */
 int ptmi_get_stats(ptmi_ctx *ctx, ptmi_stats *out);           /* synchronises */
 int ptmi_reset_stats(ptmi_ctx *ctx);

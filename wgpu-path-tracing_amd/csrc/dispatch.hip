@@ -3,6 +3,7 @@
 //
 // Replaces the reference's dispatch (src/renderer/renderer.ts: updateCamera + dispatch :403-431).
 #include "ptmi_ctx.h"
+#include "scene/frame_scissor.h"
 
 #include <algorithm>
 #include <cmath>
@@ -98,6 +99,45 @@ struct Timed {
     }
 };
 
+// The frame scissor of a dispatch: the part of the band whose pixels have a camera ray that can meet the scene's root
+// box. A path of any other pixel misses at bounce 0 and ends with radiance 0, so while nothing can see a miss — no environment, no
+// medium, no first-hit or moments plane, no alpha table — a plain dispatch traces the pixels inside only (ScissoredPixels) and folds
+// zeros for the rest. Leaves the verdict in c->scissor; true: applied, with the band-local rows [l0, l1) and the columns [x0, x1).
+struct ScissorRect { uint32_t l0, l1, x0, x1; };
+bool frame_scissor(ptmi_ctx *c, const ptmi_camera *cam, uint32_t proj, const DevBand &band, bool plain, ScissorRect &r) {
+    struct ptmi_scissor_status &st = c->scissor;
+    st.x0 = 0u; st.x1 = c->W; st.y0 = 0u; st.y1 = c->H; st.applied = 0u;
+    const auto no = [&](uint32_t reason) { st.reason = reason; return false; };
+    if (!c->scissor_on) return no(PTMI_SCISSOR_OFF);
+    if (!plain) return no(PTMI_SCISSOR_NOT_PLAIN);
+    if (c->sc.env.tab) return no(PTMI_SCISSOR_ENVIRONMENT);
+    if (c->sc.med.on) return no(PTMI_SCISSOR_MEDIUM);
+    if (c->aov_mask) return no(PTMI_SCISSOR_AOV);
+    if (c->plane[kMoments]) return no(PTMI_SCISSOR_MOMENTS);
+    if (alpha_active(c)) return no(PTMI_SCISSOR_ALPHA);
+    if (proj != PTMI_PROJ_PERSPECTIVE) return no(PTMI_SCISSOR_PROJECTION);
+    if (c->sc.root_ref == PT_REF_NONE) return no(PTMI_SCISSOR_NO_PROMISE);
+    // the box a ray has to meet before it meets anything: the walked tree's (padded) root and the uploaded tree's, which irregular rays walk
+    float lo[3], hi[3];
+    for (int k = 0; k < 3; k++) {
+        lo[k] = std::min(c->sc.root_min[k], c->sc.ref_root_min[k]);
+        hi[k] = std::max(c->sc.root_max[k], c->sc.ref_root_max[k]);
+    }
+    ptmi_camera pin = *cam;
+    ptmi_camera_set_projection(&pin, PTMI_PROJ_PERSPECTIVE, 0.0f);      // (the words are unread while the context's switch is off)
+    const int why = pt_frame_scissor(&pin, lo, hi, &st.x0, &st.x1, &st.y0, &st.y1);
+    if (why != PT_SCISSOR_RECT) return no(why == PT_SCISSOR_PROJECTION ? PTMI_SCISSOR_PROJECTION : PTMI_SCISSOR_NO_PROMISE);
+    // row_of is increasing: the band's rows inside [y0, y1) are one range of local rows
+    r.l0 = 0u;
+    while (r.l0 < band.rows && band.row_of(r.l0) < st.y0) r.l0++;
+    r.l1 = r.l0;
+    while (r.l1 < band.rows && band.row_of(r.l1) < st.y1) r.l1++;
+    r.x0 = st.x0; r.x1 = st.x1;
+    if (r.l0 == 0u && r.l1 == band.rows && r.x0 == 0u && r.x1 == band.width) return no(PTMI_SCISSOR_NOTHING);
+    st.reason = PTMI_SCISSOR_APPLIED; st.applied = 1u;
+    return true;
+}
+
 #ifndef PT_REPACK
 #define PT_REPACK 1          /* A/B switch: 0 leaves the path state at the path id for every bounce (no tail arrays in use) */
 #endif
@@ -178,6 +218,10 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
     c->st.frames_per_batch_used = F;
     c->st.radiance_stride_bytes = (walks_memory_quantised(cfg) || walks_memory_quantised(cfg_shadow)) ? 16u : 12u;
     c->st.shade_tables = PT_SHADE_LDS_BUDGET | ((uint32_t)pt_shade_stage(c->sc.n_mats, c->sc.n_lights) << 28);
+    // (the batch size and the capacity above are the whole band's, scissor or not: frames_per_batch_used and the memory stay what they were)
+    ScissorRect sr{};
+    const bool scissored = frame_scissor(c, cam, proj, band, !ap && !listed, sr);
+    const uint64_t skipped_px = scissored ? npix - (uint64_t)(sr.l1 - sr.l0) * (sr.x1 - sr.x0) : 0u;
     const int blocks = c->n_cu * 8;
 #ifndef PT_SHADE_WGS_PER_CU
 #define PT_SHADE_WGS_PER_CU 16
@@ -213,6 +257,7 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         auto batch = [&](uint32_t frame0, uint32_t fb) -> int {
             const DevPixels px = ap     ? DevPixels{ListedPixels{band, c->ad.list, &c->d_control[kCwAdActive], mom, &ct[kCtAdTraced]}}
                                  : listed ? DevPixels{BakedPixels{band, listed->list, listed->count, frame0}}
+                                 : scissored ? DevPixels{ScissoredPixels{band, sr.l0, sr.l1, sr.x0, sr.x1, frame0, ct}}
                                           : DevPixels{DensePixels{band, frame0}};
             { Timed t(c, kRaygen, t3, ms); pt_launch_raygen(ms, blocks, rays, px, fb, bp, &qlen[0]); }
             int cur = 0;
@@ -283,6 +328,7 @@ int dispatch(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n_frames, const ptmi_
         if (c->in_flight.size() > kMaxDispatchesInFlight) HIP_TRY(c, throttle(c, kMaxDispatchesInFlight));
     }
     if (!ap) { c->st.paths += npix * n_frames; c->st.frames += n_frames; }      // adaptive: counted on the device (kCtAdTraced)
+    c->scissor.skipped += skipped_px * n_frames;
     if (count_call) c->st.dispatches += 1;
     return PTMI_OK;
 }
@@ -360,6 +406,12 @@ int ptmi_dispatch_probes(ptmi_ctx *c, const ptmi_probe_params *params, uint32_t 
     const int rc = probes_check(c, params, &listed);
     if (rc) return rc;
     return dispatch(c, nullptr, n_frames, nullptr, 0, nullptr, true, &listed);
+}
+
+int ptmi_scissor_status(ptmi_ctx *c, struct ptmi_scissor_status *out) {
+    if (!c || !out) return PTMI_E_INVALID;
+    *out = c->scissor;
+    return PTMI_OK;
 }
 
 int ptmi_adaptive_status(ptmi_ctx *c, struct ptmi_adaptive_status *out) {

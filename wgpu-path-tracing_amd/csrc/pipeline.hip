@@ -151,7 +151,7 @@ PT_DEV void raygen(const Rays &rays, const Pixels &px, uint32_t n_frames, DevPat
     const DevBand &band = px.band;
     const uint32_t n = px.entries();
     const uint32_t total = n * n_frames;
-    if (blockIdx.x == 0 && threadIdx.x == 0) { px.count_paths(total); *count_out = total; }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { px.count_paths(total, n_frames); *count_out = total; }
     for (uint32_t p = blockIdx.x * BLOCK + threadIdx.x; p < total; p += gridDim.x * BLOCK) {
         const uint32_t k = p / n, pix = px.pixel(p - k * n);
         const uint32_t y = band.row_of(pix / band.width), x = pix % band.width;
@@ -292,17 +292,24 @@ PT_DEV rgb_sc ld_clamped(const float *__restrict__ L, uint32_t l_stride, size_t 
 }
 
 // The three folds of a batch, each written once over the pixel source (pt_device.h).
-// pt.wgsl:751-761 for the batch's frames in ascending order
+// pt.wgsl:751-761 for the batch's frames in ascending order. Scissored pixels: the walk is the whole band, and a pixel outside the
+// scissor takes the same steps with the radiance its untraced paths would have left, zeros, without reading L.
 template <class Pixels>
 PT_DEV void fold_radiance(const Pixels &px, uint32_t n_frames, const float *__restrict__ L, uint32_t l_stride, float4 *__restrict__ out) {
+    constexpr bool SCISSORED = std::is_same_v<Pixels, ScissoredPixels>;
     const uint32_t n = px.entries();
-    for (uint32_t j = blockIdx.x * BLOCK + threadIdx.x; j < n; j += gridDim.x * BLOCK) {
-        const size_t oi = px.band.frame_pixel(px.pixel(j));
+    uint32_t walk = n;
+    if constexpr (SCISSORED) walk = px.band.rows * px.band.width;
+    for (uint32_t j = blockIdx.x * BLOCK + threadIdx.x; j < walk; j += gridDim.x * BLOCK) {
+        uint32_t pix = j, e = j;                                // the band-local pixel; its entry
+        if constexpr (SCISSORED) e = px.fold_entry(j); else pix = px.pixel(j);
+        const size_t oi = px.band.frame_pixel(pix);
         const uint32_t frame0 = px.first_frame(oi);
         const float4 o = out[oi];
         float acc[3] = {o.x, o.y, o.z};
         for (uint32_t k = 0; k < n_frames; k++) {
-            const rgb_sc c = ld_clamped(L, l_stride, (size_t)k * n + j);
+            rgb_sc c{0.0f, 0.0f, 0.0f};
+            if (!SCISSORED || e != ScissoredPixels::kOutside) c = ld_clamped(L, l_stride, (size_t)k * n + e);
             fold(acc, {c.x, c.y, c.z}, frame0 + k);
         }
         out[oi] = n_frames ? make_float4(acc[0], acc[1], acc[2], 0.0f) : o;
@@ -734,8 +741,9 @@ void pt_launch_accumulate(hipStream_t s, int blocks, const DevPixels &px, uint32
 void pt_launch_accumulate_aov(hipStream_t s, int blocks, const DevPixels &px, uint32_t n_frames, const float4 *rec,
                               const ptmi_triangle *tris, uint32_t n_tris, float4 *albedo, float4 *normal, uint2 *ids) {
     std::visit([&](auto src) {
-        // no first-hit fold over a bake surface: a bake is refused while those planes are on (bake.hip bake_check)
-        if constexpr (std::is_same_v<decltype(src), BakedPixels>) abort();
+        // no first-hit fold over a bake surface: a bake is refused while those planes are on (bake.hip bake_check); none over scissored
+        // pixels: the scissor is off while they are (dispatch.hip)
+        if constexpr (std::is_same_v<decltype(src), BakedPixels> || std::is_same_v<decltype(src), ScissoredPixels>) abort();
         else hipLaunchKernelGGL(k_fold_aov<decltype(src)>, dim3(blocks), dim3(BLOCK), 0, s, src, n_frames, rec, tris, n_tris, albedo, normal, ids);
     }, px);
 }
@@ -751,7 +759,8 @@ void pt_launch_accumulate_probe_depth(hipStream_t s, int blocks, const DevPixels
 void pt_launch_accumulate_moments(hipStream_t s, int blocks, const DevPixels &px, uint32_t n_frames, const float *L, uint32_t l_stride,
                                   float4 *mom) {
     std::visit([&](auto src) {
-        hipLaunchKernelGGL(k_fold_moments<decltype(src)>, dim3(blocks), dim3(BLOCK), 0, s, src, n_frames, L, l_stride, mom);
+        if constexpr (std::is_same_v<decltype(src), ScissoredPixels>) abort();      // the scissor is off while the plane is on
+        else hipLaunchKernelGGL(k_fold_moments<decltype(src)>, dim3(blocks), dim3(BLOCK), 0, s, src, n_frames, L, l_stride, mom);
     }, px);
 }
 void pt_launch_adaptive_restart(hipStream_t s, int blocks, DevBand band, float4 *mom) {

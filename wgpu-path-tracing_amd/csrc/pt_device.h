@@ -324,14 +324,35 @@ size_t pt_spill_bytes(int blocks);
 // kernel over both (pipeline.hip); the launchers below turn the run-time choice into the instantiation.
 //
 // The pixels, as the kernels see them. A source answers three questions: how many entries, the band-local pixel (local row * width + x)
-// of entry j, the first frame of the pixel at frame index oi; and it may count the batch's paths. n_frames frames of each entry: path
-// k * entries + j is frame first_frame + k of entry j. (Device code only: the answers read device memory.)
+// of entry j, the first frame of the pixel at frame index oi; and it may count the batch's paths (count_paths: the batch's paths and
+// its frames, from one thread of raygen). n_frames frames of each entry: path k * entries + j is frame first_frame + k of entry j.
+// (Device code only: the answers read device memory.)
 struct DensePixels {                    // every pixel of the band, all from frame0 (ptmi_dispatch)
     DevBand band; uint32_t frame0;
     __device__ uint32_t entries() const { return band.rows * band.width; }
     __device__ uint32_t pixel(uint32_t j) const { return j; }
     __device__ uint32_t first_frame(size_t) const { return frame0; }
-    __device__ void count_paths(uint32_t) const {}                  // (a plain dispatch counts its paths on the host)
+    __device__ void count_paths(uint32_t, uint32_t) const {}        // (a plain dispatch counts its paths on the host)
+};
+// The pixels of the band inside the frame scissor (ptmi_dispatch while nothing can see a miss; dispatch.hip frame_scissor): local rows
+// [l0, l1) x columns [x0, x1), all from frame0. Every path of a pixel outside ends at bounce 0 with radiance 0 and is not traced: the
+// segment counters get those paths here, and the fold of the radiance walks the whole band with zeros for them (fold_entry).
+struct ScissoredPixels {
+    DevBand band; uint32_t l0, l1, x0, x1, frame0;
+    unsigned long long *stats;          // the counter block: kCtSegments and kCtByBounce + 0 += the paths not traced
+    __device__ uint32_t entries() const { return (l1 - l0) * (x1 - x0); }
+    __device__ uint32_t pixel(uint32_t j) const { const uint32_t w = x1 - x0; return (l0 + j / w) * band.width + x0 + j % w; }
+    __device__ uint32_t first_frame(size_t) const { return frame0; }
+    __device__ void count_paths(uint32_t, uint32_t n_frames) const {
+        const unsigned long long skipped = (unsigned long long)(band.rows * band.width - entries()) * n_frames;
+        atomicAdd(&stats[kCtSegments], skipped); atomicAdd(&stats[kCtByBounce], skipped);
+    }
+    // band-local pixel -> its entry, or kOutside
+    static constexpr uint32_t kOutside = 0xFFFFFFFFu;
+    __device__ uint32_t fold_entry(uint32_t pix) const {
+        const uint32_t l = pix / band.width, x = pix % band.width;
+        return l >= l0 && l < l1 && x >= x0 && x < x1 ? (l - l0) * (x1 - x0) + (x - x0) : kOutside;
+    }
 };
 struct ListedPixels {                   // the *n_active pixels of the list, each from its own count mom[oi].z (ptmi_dispatch_adaptive)
     DevBand band; const uint32_t *list, *n_active; const float4 *mom;
@@ -339,7 +360,7 @@ struct ListedPixels {                   // the *n_active pixels of the list, eac
     __device__ uint32_t entries() const { return *n_active; }
     __device__ uint32_t pixel(uint32_t j) const { return list[j]; }
     __device__ uint32_t first_frame(size_t oi) const { return (uint32_t)mom[oi].z; }
-    __device__ void count_paths(uint32_t paths) const { atomicAdd(traced, (unsigned long long)paths); }
+    __device__ void count_paths(uint32_t paths, uint32_t) const { atomicAdd(traced, (unsigned long long)paths); }
 };
 struct BakedPixels {                    // the n covered texels of a bake surface, or the n texels of the enabled probes of a probe atlas
     DevBand band; const uint32_t *covered; uint32_t n, frame0;     // (ascending frame indices; the band is the whole frame), all from
@@ -347,9 +368,9 @@ struct BakedPixels {                    // the n covered texels of a bake surfac
     __device__ uint32_t entries() const { return n; }
     __device__ uint32_t pixel(uint32_t j) const { return covered[j]; }
     __device__ uint32_t first_frame(size_t) const { return frame0; }
-    __device__ void count_paths(uint32_t) const {}
+    __device__ void count_paths(uint32_t, uint32_t) const {}
 };
-using DevPixels = std::variant<DensePixels, ListedPixels, BakedPixels>;
+using DevPixels = std::variant<DensePixels, ListedPixels, BakedPixels, ScissoredPixels>;
 // Where a path's first ray comes from, as the host names it: the camera (proj: its projection, PTMI_PROJ_*, as pt_check_camera resolved
 // it; PTMI_PROJ_PERSPECTIVE is all a context with ptmi_set_projections off ever passes), or the records of a bake surface
 // (ptmi_upload_bake_surface; a path starts at its texel's record, `bias` along its first direction).

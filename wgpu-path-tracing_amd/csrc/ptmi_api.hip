@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 
 namespace {
@@ -324,6 +325,7 @@ int ptmi_create(int device_ordinal, ptmi_ctx **out) {
         ptmi_destroy(c); return fail(nullptr, PTMI_E_HIP, "device allocation failed");
     }
     c->ad.control = c->d_control; c->ad.counters = c->d_counters;
+    if (const char *e = std::getenv("PTMI_SCISSOR")) c->scissor_on = std::strcmp(e, "0") != 0;     // A/B runs and tests: 0 switches it off
     *out = c;
     return PTMI_OK;
 }
@@ -704,6 +706,7 @@ int ptmi_reset_stats(ptmi_ctx *c) {
     HIP_TRY(c, hipMemset(c->d_counters, 0, kCtDispatchEnd * sizeof(unsigned long long)));      // not the status words of the last calls
     const ptmi_stats old = c->st;
     std::memset(&c->st, 0, sizeof c->st);
+    c->scissor.skipped = 0;
     c->st.bvh_depth = stats_depth(c);
     c->st.upload_ms = old.upload_ms; c->st.upload_tree_ms = old.upload_tree_ms; c->st.upload_copy_ms = old.upload_copy_ms;
     c->st.leaves_used = old.leaves_used; c->st.leaf_tris_used = old.leaf_tris_used; c->st.tree_builder_used = old.tree_builder_used;

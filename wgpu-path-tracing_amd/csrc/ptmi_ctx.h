@@ -295,6 +295,10 @@ struct ptmi_ctx {
     DevAdaptive ad{};
     uint32_t ad_rounds = 0;                            // rounds since the last restart
 
+    // the frame scissor (dispatch.hip frame_scissor; ptmi_scissor_status)
+    bool scissor_on = true;                            // PTMI_SCISSOR=0 in the environment of ptmi_create: never applied
+    struct ptmi_scissor_status scissor{};              // the last dispatch's rectangle and verdict; skipped: since ptmi_reset_stats
+
     // statistics
     ptmi_stats st{};
     std::vector<EventPair> pending;

@@ -60,7 +60,11 @@ EXPORTS = [
     "ptmi_debug_probe_rays", "ptmi_debug_probe_tables",
     "ptmi_set_probe_depth", "ptmi_get_probe_depth", "ptmi_read_probe_depth", "ptmi_write_probe_depth", "ptmi_probe_depth_device_ptr",
     "ptmi_probe_visibility",
+    "ptmi_scissor_status",
 ]
+# ptmi_scissor_status.reason (include/ptmi.h PTMI_SCISSOR_*)
+(SCISSOR_APPLIED, SCISSOR_OFF, SCISSOR_NOT_PLAIN, SCISSOR_ENVIRONMENT, SCISSOR_MEDIUM, SCISSOR_AOV, SCISSOR_MOMENTS, SCISSOR_ALPHA,
+ SCISSOR_PROJECTION, SCISSOR_NO_PROMISE, SCISSOR_NOTHING) = range(11)
 MULTI_LOOPBACK = 1
 MULTI_PLANE_MOMENTS, MULTI_PLANE_OUTPUT = 0x100, 0x200      # gather_planes: with the AOV_* bits
 # first-hit planes (include/ptmi.h ptmi_set_aovs): name -> (bit, numpy dtype, channels)
@@ -313,6 +317,15 @@ class ProbeVisibilityParams(ctypes.Structure):
     _fields_ = [("m", ctypes.c_uint32), ("sharpness_log2", ctypes.c_uint32), ("border", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class ScissorStatus(ctypes.Structure):
+    """struct ptmi_scissor_status: the frame scissor of the last dispatch, and the paths not traced since reset_stats (include/ptmi.h)"""
+    _fields_ = [("x0", ctypes.c_uint32), ("x1", ctypes.c_uint32), ("y0", ctypes.c_uint32), ("y1", ctypes.c_uint32),
+                ("applied", ctypes.c_uint32), ("reason", ctypes.c_uint32), ("skipped", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class Stats(ctypes.Structure):
     _fields_ = [("paths", ctypes.c_uint64), ("segments", ctypes.c_uint64), ("shadow_rays", ctypes.c_uint64),
                 ("dispatches", ctypes.c_uint64), ("frames", ctypes.c_uint64),
@@ -469,6 +482,8 @@ def load():
             L.ptmi_debug_probe_tables.argtypes = [u32, vp, vp]
         if "ptmi_probe_depth_device_ptr" in EXPORTS:
             L.ptmi_probe_depth_device_ptr.restype = vp
+        if "ptmi_scissor_status" in EXPORTS:
+            L.ptmi_scissor_status.argtypes = [vp, vp]
         _lib = L
     return _lib
 
@@ -1054,6 +1069,13 @@ class Context(_Handle):
         assert from_cam.dtype == layout.CAMERA and to_cam.dtype == layout.CAMERA
         prm = ReprojectParams(max_history, depth_tolerance, match_ids, (ctypes.c_uint32 * 5)(*reserved))
         self._ck(self.L.ptmi_reproject(self.h, _p(from_cam), _p(to_cam), ctypes.byref(prm)))
+
+    def scissor_status(self):
+        """The frame scissor of the last dispatch (include/ptmi.h ptmi_scissor_status): its rectangle, whether it was applied, the
+        reason when not, and the paths it has spared since reset_stats."""
+        st = ScissorStatus()
+        self._ck(self.L.ptmi_scissor_status(self.h, ctypes.byref(st)))
+        return st
 
     def reproject_status(self):
         st = ReprojectStatus()
