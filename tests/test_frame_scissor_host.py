@@ -10,6 +10,11 @@ wider per side than the bounding rectangle of the pixels one of whose rays hits:
 into a pixel without reaching one of its sampled points.
 
 Set B: the cases that must answer "whole frame".
+
+Set C: boxes and bases beyond Cornell — flat, line, point, tiny, long and far from the origin; scaled, left-handed and skewed bases; frames
+of one column and of one row; fov from 0.05 to 3; lenses focused in front of and behind the box; aspect != W / H; cameras as near as 1.05
+box radii. No premise is checked here: the function may answer "whole frame" (then it must leave the whole frame), but not often, and
+whenever it answers a rectangle the same rays as in set A must miss outside it.
 """
 import ctypes
 import itertools
@@ -221,3 +226,134 @@ def test_set_b_whole_frame(fn, box):
 def test_a_box_off_the_frame_leaves_no_pixel(fn, box):
     why, rect = scissor(fn, layout.make_camera(96, 54, position=(30.0, 1.0, 2.8)), box)
     assert why == RECT and rect == (0, 0, 0, 0)
+
+
+# ---- set C -----------------------------------------------------------------------------------------------------------------------------
+C_BOXES = {
+    "flat in y": ((-1.0, 0.0, -1.0), (1.0, 0.0, 1.0)),
+    "flat in z": ((-1.0, -1.0, 0.0), (1.0, 1.0, 0.0)),
+    "line": ((-1.0, 0.0, 0.0), (1.0, 0.0, 0.0)),
+    "point": ((0.25, 0.5, -0.75), (0.25, 0.5, -0.75)),
+    "1e-3 cube": ((-5e-4, -5e-4, -5e-4), (5e-4, 5e-4, 5e-4)),
+    "beam": ((-50.0, -0.1, -0.1), (50.0, 0.1, 0.1)),
+    "far cube": ((999.0, -2001.0, 499.0), (1001.0, -1999.0, 501.0)),
+}
+C_DISTANCES = (1.05, 1.5, 3.0, 10.0)                            # in box radii (half the diagonal; the point: 1)
+C_BASES = ("orthonormal", "scaled", "left-handed", "skewed")
+C_FRAMES = ((96, 54), (64, 64), (1, 37), (200, 1), (33, 97))
+C_FOVS = (0.05, 0.6, 1.4, 2.5, 3.0)
+C_LENSES = ((0.0, 1.0), (0.01, 0.5), (0.05, 2.0))               # (aperture, focus), both in camera distances
+# look-at offsets from the box centre, in box radii
+C_OFFSETS = ((0.0, 0.0, 0.0), (0.2, 0.0, 0.0), (0.0, -0.15, 0.1), (-0.1, 0.1, 0.0), (0.05, 0.05, -0.2))
+C_N = 420                                                       # = 7 * 4 * 5 * 3: box x distance x frame x lens, each combination once
+
+
+def c_box(name):
+    lo, hi = (np.array(v, np.float32) for v in C_BOXES[name])
+    return lo, hi
+
+
+def c_cameras():
+    """(camera, box, (box, distance, basis, frame, fov, lens)) for i < C_N. Box, distance, frame and lens go by i modulo their lists'
+    lengths, which are pairwise coprime; the basis and the fov by strides of their own; the direction by a seeded generator."""
+    rng = np.random.default_rng(25)
+    names = list(C_BOXES)
+    for i in range(C_N):
+        name, dist, basis = names[i % 7], C_DISTANCES[i % 4], C_BASES[(i // 7) % 4]
+        (w, h), fov, (ap, focus) = C_FRAMES[i % 5], C_FOVS[(i // 4) % 5], C_LENSES[i % 3]
+        lo, hi = (b.astype(np.float64) for b in c_box(name))
+        radius = np.linalg.norm(hi - lo) * 0.5 or 1.0
+        d = rng.normal(size=3)
+        d /= np.linalg.norm(d)
+        r = dist * radius
+        centre = (lo + hi) * 0.5
+        pos = centre + r * d
+        fw, rt, up = look_at(pos, centre + np.array(C_OFFSETS[(i // 3) % 5]) * radius)
+        if basis == "scaled":
+            fw, rt, up = fw * 2.5, rt * 0.4, up * 1.7
+        elif basis == "left-handed":
+            rt = -rt
+        elif basis == "skewed":
+            rt = rt + 0.3 * up
+            up = up + 0.2 * fw
+        cam = layout.make_camera(w, h, position=pos, forward=fw, right=rt, up=up, fov=fov, aperture=ap * r, focus_distance=focus * r,
+                                 aspect=0.7 if (i + i // 7) % 7 == 6 else None)     # one in seven, on another box each time
+        yield cam, c_box(name), (name, dist, basis, (w, h), fov, (ap, focus))
+
+
+def edge_pixels(cam, box, n=20001):
+    """(H, W) bool: the pinhole image of a point of one of the box's twelve edges falls in the pixel, n points per edge, in float64. An
+    image thinner than a pixel (a line, a beam, a plate seen edge-on) slips between the sampled rays of rays_hit; its outline does not
+    slip through here, and the bounds of a convex image on the frame are reached on its outline or where rays_hit finds them."""
+    W, H = int(cam["width"]), int(cam["height"])
+    pos, fw, rt, up = cam_f64(cam)
+    th, aspect = np.tan(float(cam["fov"]) * 0.5), float(cam["aspect"])
+    lo, hi = box[0].astype(np.float64), box[1].astype(np.float64)
+    c = np.array(list(itertools.product(*zip(lo, hi))))
+    t = np.linspace(0.0, 1.0, n)[:, None]
+    out = np.zeros((H, W), bool)
+    for a in range(8):
+        for k in (1, 2, 4):
+            if a & k:
+                continue
+            q = c[a] + t * (c[a | k] - c[a]) - pos
+            s, u, v = np.linalg.solve(np.stack([fw, rt, up], axis=1), q.T)
+            ok = s > 0.0
+            px, py = (u[ok] / s[ok] / (th * aspect) + 1.0) * 0.5 * W, (v[ok] / s[ok] / th + 1.0) * 0.5 * H
+            on = (px >= 0.0) & (px < W) & (py >= 0.0) & (py < H)
+            out[py[on].astype(int), px[on].astype(int)] = True
+    return out
+
+
+def test_set_c_rectangles_hold_beyond_cornell(fn):
+    answers = {}
+    seen = [set() for _ in range(6)]
+    aspects = tight = 0
+    for i, (cam, box, what) in enumerate(c_cameras()):
+        W, H = int(cam["width"]), int(cam["height"])
+        why, (x0, x1, y0, y1) = scissor(fn, cam, box)
+        answers[why] = answers.get(why, 0) + 1
+        if why != RECT:
+            assert (x0, x1, y0, y1) == (0, W, 0, H), (i, what, why)
+            continue
+        assert 0 <= x0 <= x1 <= W and 0 <= y0 <= y1 <= H
+        for s, v in zip(seen, what):
+            s.add(v)
+        aspects += float(cam["aspect"]) == float(np.float32(0.7))
+        hit = rays_hit(cam, box)
+        outside = np.ones((H, W), bool)
+        outside[y0:y1, x0:x1] = False
+        assert not (hit & outside).any(), (i, what, (x0, x1, y0, y1), np.argwhere(hit & outside)[:4])
+        if what[5][0] == 0.0 and what[2] == "orthonormal":
+            # against the box the function projects: far from the origin its 2^-16 margin is many pixels, by design
+            big = inflated(cam, box)
+            near = rays_hit(cam, big) | edge_pixels(cam, big)
+            if near.any():
+                yy, xx = np.nonzero(near)
+                assert x0 >= xx.min() - 3 and x1 <= xx.max() + 1 + 3 and y0 >= yy.min() - 3 and y1 <= yy.max() + 1 + 3, \
+                    (i, what, (x0, x1, y0, y1), (xx.min(), xx.max() + 1, yy.min(), yy.max() + 1))
+                tight += 1
+    print("set C answers:", answers)
+    assert answers.get(RECT, 0) >= 0.85 * C_N, answers
+    assert set(answers) <= {RECT, INSIDE, BEHIND}, answers
+    # ... and those that answered a rectangle cover every listed value
+    assert seen[0] == set(C_BOXES) and seen[1] == set(C_DISTANCES) and seen[2] == set(C_BASES)
+    assert seen[3] == set(C_FRAMES) and seen[4] == set(C_FOVS) and seen[5] == set(C_LENSES)
+    assert aspects > 0 and tight > 0
+
+
+def test_set_c_aspect_is_0_7_on_every_seventh_camera():
+    a = [float(c["aspect"]) for c, _, _ in c_cameras()]
+    assert len(a) == C_N and sum(v == float(np.float32(0.7)) for v in a) == C_N // 7
+
+
+def test_the_widest_frame_that_is_promised(fn, box):
+    """65 536 pixels a side is the last size with a rectangle; one more answers "whole frame" """
+    W, H = 65536, 2
+    cam = layout.make_camera(W, H, aperture=0.0)
+    why, (x0, x1, y0, y1) = scissor(fn, cam, box)
+    assert why == RECT and 0 < x0 < x1 < W and (y0, y1) == (0, H)
+    hit = rays_hit(cam, box)
+    assert hit.any() and not hit[:, :x0].any() and not hit[:, x1:].any()
+    assert scissor(fn, layout.make_camera(W + 1, H, aperture=0.0), box) == (DEGENERATE, (0, W + 1, 0, H))
+    assert scissor(fn, layout.make_camera(H, W + 1, aperture=0.0), box) == (DEGENERATE, (0, H, 0, W + 1))
