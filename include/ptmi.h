@@ -275,6 +275,40 @@ int ptmi_bake_dilate(ptmi_ctx *ctx, uint32_t passes, float *dst_rgba, size_t n_f
 int ptmi_debug_bake_rays(ptmi_ctx *ctx, const ptmi_bake_params *params, uint32_t n, const uint32_t *xs, const uint32_t *ys,
                          const uint32_t *frames, float *o3, float *d3, uint32_t *rng);
 
+/* ---- denoising a lightmap: a chart-aware a-trous filter over the bake surface ------------------
+ * ptmi_bake_denoise filters the output buffer, read as the lightmap of the surface in place, with the 5x5 B3-spline a-trous wavelet of
+ * ptmi_denoise (taps at offsets of 2^i texels in pass i), guided by the surface instead of by first-hit planes: a bake has none, and
+ * neighbours in a lightmap atlas need not be neighbours in the scene. It reads the surface's records, the output buffer and the
+ * moments plane (ptmi_set_moments must be on during the bake, so that covered texels have folded theirs) and writes none of them; the
+ * result is a context-owned plane. Uncovered texels are never read. Single device, like the rest of the bake. Not on the parity path:
+ * its contract is a tolerance against tests/bake_denoise_ref.py, which restates every expression (csrc/bake_denoise.hip lists them):
+ *   prepass  per covered texel: n^ = normal / |normal|; the footprint f = the smallest non-zero distance to a covered 4-neighbour's
+ *            position (0 if there is none); variance of the mean = max(0, m2 - m1^2) / max(frames, 1) from the moments plane
+ *   pass i   a covered centre p with finite values takes the taps q inside the map that are covered and finite, each weighted
+ *            h h w_n w_x w_l:  w_n = max(0, n^_p . n^_q)^phi_normal,
+ *            w_l = exp(-|l_p - l_q| / (phi_color sqrt(g3x3(var)_p) + 1e-6)) as in ptmi_denoise,
+ *            w_x = exp(-e / (phi_position f_p + 1e-6)),  e = max(|n^_p . D|, |D| - 4 |offset| f_p),  D = P_q - P_p, |offset| in texels.
+ *            colour = sum w c / sum w, variance = sum w^2 var / (sum w)^2. A covered centre that is not finite keeps its value.
+ *            A tap on the centre's plane within 4 footprints per texel of offset (the chart stretch tolerated) has e = 0; a parallel
+ *            surface is cut by the plane term, a far part of the same plane by the distance term; a tap of another chart that does
+ *            agree in the scene is accepted, which is what heals seams.
+ *   then     (rgb, 1) for covered texels and zeros for the others, and `dilate` passes of ptmi_bake_dilate's rule on that plane.
+ * dst_rgba NULL: asynchronous on the context's stream (read the result through ptmi_bake_denoised_device_ptr after
+ * ptmi_synchronize); else synchronises and copies width * height float4, w being the state ptmi_bake_dilate documents (1 covered,
+ * 2 filled, 0 empty). PTMI_E_INVALID: no surface in place, a negative or non-finite phi, iterations > 10, a non-zero reserved word, a
+ * wrong n_floats. PTMI_E_STATE: the moments plane off, no output buffer. A refused call writes nothing. */
+typedef struct ptmi_bake_denoise_params {
+    uint32_t iterations;    /* 1..10; 0 -> 5 */
+    uint32_t dilate;        /* gutter passes on the filtered result, ptmi_bake_dilate's rule; 0: none */
+    float phi_color;        /* 0 -> 4 */
+    float phi_normal;       /* 0 -> 128 */
+    float phi_position;     /* 0 -> 1, in texel footprints */
+    uint32_t reserved[3];   /* must be 0 */
+} ptmi_bake_denoise_params;
+int ptmi_bake_denoise(ptmi_ctx *ctx, const ptmi_bake_denoise_params *params, float *dst_rgba, size_t n_floats);
+/* the filtered plane's device address; NULL before the first ptmi_bake_denoise since the last ptmi_resize */
+void *ptmi_bake_denoised_device_ptr(ptmi_ctx *ctx);
+
 /* ---- light probes: radiance gathered at points in free space -----------------------------------
  * A probe answers "what light arrives at this point?", for the objects that move through a baked scene. The context's frame
  * (ptmi_resize) is read as the probe ATLAS: with tile size N (a power of two, 4 ... 64; 8 is the practical minimum, see the errors
@@ -480,6 +514,10 @@ int ptmi_set_moments(ptmi_ctx *ctx, uint32_t on);
 int ptmi_get_moments(const ptmi_ctx *ctx, uint32_t *on);
 /* n_floats: width*height*4, else PTMI_E_INVALID; the plane off (or before ptmi_resize): PTMI_E_STATE. Synchronises. */
 int ptmi_read_moments(ptmi_ctx *ctx, float *dst, size_t n_floats);
+/* The counterpart of ptmi_write_output for the plane: width*height*4 floats replace its contents, so that a checkpointed render or
+ * bake that had the plane on can be resumed (write both, then go on from the next frame), and a filter can be given chosen variances.
+ * The same sizes and errors as ptmi_read_moments. Synchronises. */
+int ptmi_write_moments(ptmi_ctx *ctx, const float *src, size_t n_floats);
 /* NULL while the plane is off */
 void *ptmi_moments_device_ptr(ptmi_ctx *ctx);
 

@@ -62,13 +62,16 @@ int resolve_params(ptmi_ctx *c, const ptmi_bake_params *params, ptmi_bake_params
 
 }  // namespace
 
+void pt_launch_bake_dilate_pass(hipStream_t s, uint32_t W, uint32_t H, const float4 *src, float4 *dst) {
+    hipLaunchKernelGGL(k_bake_dilate, dim3((W * H + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, W, H, src, dst);
+}
+
 float4 *pt_launch_bake_dilate(hipStream_t s, uint32_t W, uint32_t H, uint32_t passes, const float4 *texels, const float4 *out,
                               float4 *a, float4 *b) {
     const uint32_t n = W * H;
-    const dim3 g((n + BLOCK - 1) / BLOCK), blk(BLOCK);
-    hipLaunchKernelGGL(k_bake_mask, g, blk, 0, s, n, texels, out, a);
+    hipLaunchKernelGGL(k_bake_mask, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, n, texels, out, a);
     for (uint32_t k = 0; k < passes; k++) {
-        hipLaunchKernelGGL(k_bake_dilate, g, blk, 0, s, W, H, a, b);
+        pt_launch_bake_dilate_pass(s, W, H, a, b);
         std::swap(a, b);
     }
     return a;

@@ -390,6 +390,8 @@ void pt_launch_raygen_list(hipStream_t s, const DevRays &rays, uint32_t width, u
 // passes of the rule of include/ptmi.h ping-ponging between a and b; returns the plane that holds the result
 float4 *pt_launch_bake_dilate(hipStream_t s, uint32_t W, uint32_t H, uint32_t passes, const float4 *texels, const float4 *out,
                               float4 *a, float4 *b);
+// one such pass on a masked plane the caller has (bake_denoise.hip): src is the state before the pass, and only dst is written
+void pt_launch_bake_dilate_pass(hipStream_t s, uint32_t W, uint32_t H, const float4 *src, float4 *dst);
 // The two reductions of a probe atlas (probes.hip; include/ptmi.h states both sums). `out` is the frame, W texels a row; probe i owns
 // the tile (i % cols, i / cols) of 1 << shift texels a side.
 struct DevProbeAtlas { const float4 *out; const float4 *probes; uint32_t W, shift, cols, count; };

@@ -112,6 +112,8 @@ const struct { const char *name; size_t (*bytes)(size_t px); bool zeroed; PlaneG
     {"motion", per_pixel<16>, true, kWithFrame},
     {"dilate ping", per_pixel<16>, false, kByBake}, {"dilate pong", per_pixel<16>, false, kByBake},
     {"probe depth", per_pixel<16>, true, kWithFrame},
+    {"lightmap guide (normal)", per_pixel<16>, false, kByBakeDenoise}, {"lightmap guide (position)", per_pixel<16>, false, kByBakeDenoise},
+    {"denoised lightmap", per_pixel<16>, false, kByBakeDenoise},
 };
 // sets of planes: a bit per FramePlane
 constexpr uint32_t kAllPlanes = (1u << kFramePlanes) - 1u;
@@ -422,7 +424,7 @@ int ptmi_resize(ptmi_ctx *c, uint32_t w, uint32_t h) {
         for (void *&p : fresh) dfree(p);
         return fail(c, PTMI_E_HIP, "sync_all failed: %s", hipGetErrorString(e));
     }
-    drop_planes(c, kAllPlanes);                       // the denoiser's, the adaptive, the history, the blit and the dilate planes come back at their first use
+    drop_planes(c, kAllPlanes);                       // the denoisers', the adaptive, the history, the blit and the dilate planes come back at their first use
     if (w != c->W || h != c->H) { bake_forget(c); probes_forget(c); }      // a bake surface and a probe atlas are of one size
     std::copy(fresh, fresh + kFramePlanes, c->plane);
     c->W = w; c->H = h;
@@ -584,6 +586,18 @@ int ptmi_read_moments(ptmi_ctx *c, float *dst, size_t n_floats) {
     if (!c->moments_on) return fail(c, PTMI_E_STATE, "the moments plane is off (ptmi_set_moments)");
     if (!c->plane[kMoments]) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
     return read_plane(c, kMoments, c->plane[kMoments], dst, n_floats, 4);
+}
+
+int ptmi_write_moments(ptmi_ctx *c, const float *src, size_t n_floats) {
+    if (!c) return PTMI_E_INVALID;
+    if (!src) return fail(c, PTMI_E_INVALID, "src is NULL");
+    if (!c->moments_on) return fail(c, PTMI_E_STATE, "the moments plane is off (ptmi_set_moments)");
+    if (!c->plane[kMoments]) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
+    if (n_floats != (size_t)c->W * c->H * 4) return fail(c, PTMI_E_INVALID, "expected %zu floats, got %zu", (size_t)c->W * c->H * 4, n_floats);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, sync_all(c));
+    HIP_TRY(c, hipMemcpy(c->plane[kMoments], src, n_floats * 4, hipMemcpyHostToDevice));
+    return PTMI_OK;
 }
 
 void *ptmi_moments_device_ptr(ptmi_ctx *c) { return c && c->moments_on ? c->plane[kMoments] : nullptr; }

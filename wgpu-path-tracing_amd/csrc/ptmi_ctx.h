@@ -17,6 +17,7 @@
 //   scene_skin.hip     skinned triangles posed on the device: the list, the corner records, the rest pose, the check and write kernel
 //   scene_morph.hip    morphed triangles posed on the device: the list, the sparse delta rows, the rest pose, the check and write kernel
 //   bake.hip           lightmap baking: the surface's records and covered list, the checks of a bake, the gutter fill, the debug rays
+//   bake_denoise.hip   the lightmap filter: its kernels, launches and entry points (ptmi_bake_denoise)
 //   probes.hip         light probes: the records, tables and texel list, the checks of a probe dispatch, the SH9, irradiance and
 //                      visibility reductions, the depth plane's switch
 #pragma once
@@ -148,8 +149,10 @@ enum FramePlane {
     kRpOut, kRpMoments, kRpNormal, kRpAlbedo, kRpId,   // reprojection: the snapshot of the output, moments and first-hit planes
     kBlitF32, kBlitU8,                             // canvas staging of ptmi_blit
     kMotion,                                       // the motion plane of ptmi_set_motion: where each pixel's surface was in `from`
-    kBakeA, kBakeB,                                // ptmi_bake_dilate: the two ping-pong planes (rgb, state)
+    kBakeA, kBakeB,                                // ptmi_bake_dilate: the two ping-pong planes (rgb, state); ptmi_bake_denoise's too
+                                                   // (rgb, variance; then rgb, state)
     kProbeDepth,                                   // the depth plane of ptmi_set_probe_depth: (mean d, mean d^2, hit fraction, 0) per probe texel
+    kBdGuideN, kBdGuideP, kBdOut,                  // ptmi_bake_denoise: guide (unit normal, footprint), guide (position, 1), the result
     kFramePlanes
 };
 
@@ -327,7 +330,7 @@ size_t bytes_per_path(bool aov, bool env_w, bool alpha);
 void lane_views(Lane &ln);
 // first_hit: the caller needs the first-hit records although no AOV plane is on (a probe dispatch with the depth plane on)
 int ensure_capacity(ptmi_ctx *c, Lane &ln, size_t n, bool first_hit = false);
-enum PlaneGroup { kWithFrame, kByDenoise, kByAdaptive, kByReproject, kByBlit, kByBake };     // when a plane is made (the kFrame table)
+enum PlaneGroup { kWithFrame, kByDenoise, kByAdaptive, kByReproject, kByBlit, kByBake, kByBakeDenoise };     // when a plane is made (the kFrame table)
 constexpr uint32_t bit(FramePlane k) { return 1u << k; }                            // sets of planes: a bit per FramePlane
 uint32_t group_set(PlaneGroup g);
 size_t plane_bytes(FramePlane k, size_t px);                                        // what plane k takes for px pixels

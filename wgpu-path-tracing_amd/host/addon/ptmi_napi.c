@@ -802,6 +802,17 @@ static napi_value js_set_moments(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* getMoments(h) -> boolean */
+static napi_value js_get_moments(napi_env env, napi_callback_info info) {
+    napi_value argv[1], out;
+    handle *h = get_handle(env, info, 1, argv);
+    if (!h) return NULL;
+    uint32_t on = 0;
+    CALL(env, h, get_moments, &on);
+    napi_get_boolean(env, on != 0, &out);
+    return out;
+}
+
 /* setProjections(h, on): ptmi_set_projections / ptmi_multi_set_projections. While on, bytes 88..95 of every camera blob are read */
 static napi_value js_set_projections(napi_env env, napi_callback_info info) {
     napi_value argv[2];
@@ -1067,6 +1078,43 @@ static napi_value js_bake_dilate(napi_env env, napi_callback_info info) {
     int rc = ptmi_bake_dilate(h->ctx, passes, (float *)p, n / 4);
     if (rc) return throw_ptmi(env, h, rc, "ptmi_bake_dilate");
     return argv[2];
+}
+
+/* bakeDenoise(h, {iterations, dilate, phiColor, phiNormal, phiPosition} or null, Float32Array dst of width*height*4): the filtered
+ * lightmap (ptmi_bake_denoise), w = the state; absent members take the C defaults */
+static napi_value js_bake_denoise(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    handle *h = get_single_handle(env, info, 3, argv, "bakeDenoise");
+    if (!h) return NULL;
+    ptmi_bake_denoise_params prm;
+    memset(&prm, 0, sizeof prm);
+    napi_valuetype t;
+    if (napi_typeof(env, argv[1], &t) == napi_ok && t == napi_object) {
+        prm.iterations = get_u32_prop(env, argv[1], "iterations", 0);
+        prm.dilate = get_u32_prop(env, argv[1], "dilate", 0);
+        prm.phi_color = get_f32_prop(env, argv[1], "phiColor", 0.0f);
+        prm.phi_normal = get_f32_prop(env, argv[1], "phiNormal", 0.0f);
+        prm.phi_position = get_f32_prop(env, argv[1], "phiPosition", 0.0f);
+    }
+    void *p; size_t n;
+    if (!get_bytes(env, argv[2], &p, &n)) return NULL;
+    if (!check_canvas(env, h, "bakeDenoise", "Float32Array", 4, p, n)) return NULL;
+    int rc = ptmi_bake_denoise(h->ctx, &prm, (float *)p, n / 4);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_bake_denoise");
+    return argv[2];
+}
+
+/* writeMoments(h, Float32Array src of width*height*4): ptmi_write_moments */
+static napi_value js_write_moments(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    handle *h = get_single_handle(env, info, 2, argv, "writeMoments");
+    if (!h) return NULL;
+    void *p; size_t n;
+    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
+    if (!check_canvas(env, h, "writeMoments", "Float32Array", 4, p, n)) return NULL;
+    int rc = ptmi_write_moments(h->ctx, (const float *)p, n / 4);
+    if (rc) return throw_ptmi(env, h, rc, "ptmi_write_moments");
+    return NULL;
 }
 
 /* ---- light probes (include/ptmi.h ptmi_upload_probes ...): one device's handle only, like baking ---- */
@@ -1373,7 +1421,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"debugMotionPrev", js_debug_motion_prev},
         {"setProjections", js_set_projections}, {"getProjections", js_get_projections},
         {"uploadBakeSurface", js_upload_bake_surface}, {"dispatchBake", js_dispatch_bake}, {"bakeStatus", js_bake_status},
-        {"bakeDilate", js_bake_dilate},
+        {"bakeDilate", js_bake_dilate}, {"bakeDenoise", js_bake_denoise}, {"getMoments", js_get_moments}, {"writeMoments", js_write_moments},
         {"uploadProbes", js_upload_probes}, {"dispatchProbes", js_dispatch_probes}, {"probeStatus", js_probe_status},
         {"probeSh", js_probe_sh}, {"probeIrradiance", js_probe_irradiance},
         {"setProbeDepth", js_set_probe_depth}, {"getProbeDepth", js_get_probe_depth}, {"readProbeDepth", js_read_probe_depth},

@@ -164,10 +164,13 @@ export class Renderer {
    *  texel. width*height float4, row y at v = (y + 0.5) / height: the mean incoming radiance under the cosine law (E / pi; multiply by
    *  albedo); w is 0, or with dilate > 0 the texel's state (1 covered, 2 filled, 0 empty). Defaults: the frame's size, 64 frames, no
    *  dilation, bias 1e-6. The frame takes the lightmap's size and accumulation restarts. Punctual lights reach a texel only through
-   *  later bounces. Throws with several devices and while first-hit planes are on; synchronises */
-  bake(opts?: { width?: number; height?: number; frames?: number; dilate?: number; bias?: number }): Float32Array;
-  /** what the last bake() baked */
-  lastBake?: { width: number; height: number; frames: number; covered: number };
+   *  later bounces. denoise: true, or the parameters (0 or absent: the default), returns the lightmap filtered over the bake surface
+   *  (include/ptmi.h ptmi_bake_denoise), w the texel's state, gutter-filled after the filter when dilate > 0; the sample-moments plane
+   *  is on for the bake and as it was afterwards. Throws with several devices and while first-hit planes are on; synchronises */
+  bake(opts?: { width?: number; height?: number; frames?: number; dilate?: number; bias?: number;
+                denoise?: boolean | { iterations?: number; phiColor?: number; phiNormal?: number; phiPosition?: number } }): Float32Array;
+  /** what the last bake() baked; denoised: true after a filtered one */
+  lastBake?: { width: number; height: number; frames: number; covered: number; denoised?: boolean };
   /** light probes of the loaded scene (include/ptmi.h ptmi_dispatch_probes, ptmi_probe_sh, ptmi_probe_irradiance): probes at
    *  `positions` (3 numbers each) or at the cell centres of `grid`, each with a tile x tile octahedral tile (default 8) of the atlas
    *  (probe i owns tile (i % cols, i / cols); probes.js atlasSize gives the size), `frames` paths per atlas texel (default 64).

@@ -11,7 +11,7 @@
  *                       --devices 0,1,... --loopback --aov albedo|normal|id --aov-out plane.bin
  *                       --alpha-cutout --alpha-blend --alpha-seed N --alpha-layers N --animation N --time S
  *                       --camera N --projection ortho|panorama --ymag V --hdr out.hdr
- *                       --bake W,H --bake-dilate N --bake-bias B
+ *                       --bake W,H --bake-dilate N --bake-bias B --bake-denoise --bake-denoise-iterations N
  *                       --probes nx,ny,nz --probe-tile N --probe-irradiance M
  *                       --probe-visibility M [--probe-sharpness S] [--probe-max-distance D] [--probe-border]]
  * --batch K traces K frames per dispatch instead of one. --denoise keeps the denoiser's planes and makes --png the tone-mapped
@@ -46,7 +46,9 @@
  * samples per covered texel over the scene's lightmap coordinates (a .glb's TEXCOORD_1, else TEXCOORD_0), --bake-dilate N gutter-fill
  * passes (default 0), --bake-bias B the origin offset along the first ray (default 1e-6). out.f32 and --hdr then hold the lightmap
  * (row y at v = (y + 0.5) / H; w: 0, or with --bake-dilate the texel's state), --png its tone-mapped image, and the JSON line bake:
- * { width, height, frames, covered }. Not with --devices, --denoise, --aov or --adaptive.
+ * { width, height, frames, covered }. --bake-denoise filters the lightmap over the bake surface before the gutter fill (include/ptmi.h
+ * ptmi_bake_denoise, default parameters; --bake-denoise-iterations N passes, default 5): w is then the texel's state, and bake also
+ * holds denoised: true. Not with --devices, --denoise, --aov or --adaptive.
  * --probes nx,ny,nz gathers light probes instead of rendering from the camera (Renderer.bakeProbes; include/ptmi.h
  * ptmi_dispatch_probes): an nx x ny x nz lattice over the scene's bounds with a probe at every cell centre (probes.js grid), so the
  * outermost probes stand half a cell inside the bounds; --probe-tile N the atlas tile (default 8), --frames samples per atlas texel,
@@ -130,7 +132,8 @@ r.loadModel(scenePath).then(function () {
     var size = textArg('bake').split(',').map(Number);
     if (size.length !== 2 || !(size[0] > 0) || !(size[1] > 0)) throw new Error('--bake: W,H');
     if (devices || denoise || aov || adaptive) throw new Error('--bake does not go with --devices, --denoise, --aov or --adaptive');
-    out = r.bake({ width: size[0], height: size[1], frames: frames, dilate: arg('bake-dilate', 0), bias: arg('bake-bias', 1e-6) });
+    out = r.bake({ width: size[0], height: size[1], frames: frames, dilate: arg('bake-dilate', 0), bias: arg('bake-bias', 1e-6),
+      denoise: process.argv.indexOf('--bake-denoise') >= 0 ? { iterations: arg('bake-denoise-iterations', 0) } : false });
     W = size[0]; H = size[1];
   } else if (textArg('probes') !== null) {
     var counts = textArg('probes').split(',').map(Number);

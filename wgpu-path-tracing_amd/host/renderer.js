@@ -623,14 +623,16 @@ Renderer.prototype.readOutput = function () {
 
 /**
  * A lightmap of the loaded scene (include/ptmi.h ptmi_upload_bake_surface, ptmi_dispatch_bake, ptmi_bake_dilate): opts = { width,
- * height (default: the frame's), frames (samples per texel, default 64), dilate (gutter-fill passes, default 0), bias (default 1e-6) }.
+ * height (default: the frame's), frames (samples per texel, default 64), dilate (gutter-fill passes, default 0), bias (default 1e-6),
+ * denoise (true, or { iterations, phiColor, phiNormal, phiPosition }, 0 or absent: the default; include/ptmi.h ptmi_bake_denoise) }.
  * The scene's triangles are rasterised over their lightmap coordinates (bake.js: a .glb's TEXCOORD_1, else TEXCOORD_0; any other
  * model: the triangles' own uv0..2), every covered texel traces `frames` paths from its surface point, and the result is the
  * width * height float4 lightmap, index y * width + x with row y at lightmap coordinate v = (y + 0.5) / height: the mean incoming
  * radiance under the cosine law, E / pi, which the engine multiplies by albedo. w is 0, or with dilate > 0 the texel's state: 1
- * covered, 2 filled, 0 empty. Texels lie where the triangles were when they were loaded: later edits and poses are traced but do not
+ * covered, 2 filled, 0 empty. With denoise the result is the filtered lightmap (w: the state, gutter-filled when dilate > 0): the
+ * sample-moments plane is on for the length of the bake and as it was afterwards. Texels lie where the triangles were when they were loaded: later edits and poses are traced but do not
  * move them. One device only; the first-hit planes must be off. The frame takes the lightmap's size (resize) and accumulation
- * restarts; lastBake = { width, height, frames, covered } says what was baked. Synchronises.
+ * restarts; lastBake = { width, height, frames, covered } (and denoised: true after a filtered one) says what was baked. Synchronises.
  */
 Renderer.prototype.bake = function (opts) {
   opts = opts || {};
@@ -658,15 +660,23 @@ Renderer.prototype.bake = function (opts) {
   if (W !== this.width || H !== this.height) this.resize(W, H);
   this.addon.uploadBakeSurface(this.ctx, surface.texels, W, H);
   var out = new Float32Array(W * H * 4);
+  var denoise = opts.denoise ? (typeof opts.denoise === 'object' ? opts.denoise : {}) : null;
+  var momentsWere = this.addon.getMoments(this.ctx);
   try {
+    if (denoise && !momentsWere) this.addon.setMoments(this.ctx, true);   // the filter's variance: folded during the bake
     this.addon.writeOutput(this.ctx, out);                              // uncovered texels read as zeros
     this.addon.dispatchBake(this.ctx, { firstFrame: 0, bias: opts.bias === undefined ? 1e-6 : opts.bias }, frames);
-    if (opts.dilate > 0) this.addon.bakeDilate(this.ctx, opts.dilate, out);
+    if (denoise)
+      this.addon.bakeDenoise(this.ctx, { iterations: denoise.iterations || 0, dilate: opts.dilate > 0 ? opts.dilate : 0,
+        phiColor: denoise.phiColor || 0, phiNormal: denoise.phiNormal || 0, phiPosition: denoise.phiPosition || 0 }, out);
+    else if (opts.dilate > 0) this.addon.bakeDilate(this.ctx, opts.dilate, out);
     else this.addon.readOutput(this.ctx, out);
   } finally {
+    if (denoise && !momentsWere) this.addon.setMoments(this.ctx, false);
     this.addon.uploadBakeSurface(this.ctx, null, 0, 0);
   }
   this.lastBake = { width: W, height: H, frames: frames, covered: surface.covered };
+  if (denoise) this.lastBake.denoised = true;
   this.reprojectFrom = null;
   this.frameIndex = 0;                      // the output buffer holds a lightmap now: a camera's accumulation starts over
   return out;

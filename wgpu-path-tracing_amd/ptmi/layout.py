@@ -44,6 +44,9 @@ SKIN_CORNER = np.dtype([("joint", U, 4), ("weight", F, 4)])
 
 # ptmi_bake_texel (include/ptmi.h ptmi_upload_bake_surface): where a lightmap texel lies on the scene's surface
 BAKE_TEXEL = np.dtype([("position", F, 3), ("covered", U), ("normal", F, 3), ("_pad", U)])
+# ptmi_bake_denoise_params (include/ptmi.h ptmi_bake_denoise): the lightmap filter's parameters, 0 picking a field's default
+BAKE_DENOISE_PARAMS = np.dtype([("iterations", U), ("dilate", U), ("phi_color", F), ("phi_normal", F), ("phi_position", F),
+                                ("reserved", U, 3)])
 # ptmi_probe (include/ptmi.h ptmi_upload_probes): a point in free space whose incoming radiance one tile of the probe atlas gathers
 PROBE = np.dtype([("position", F, 3), ("enabled", U)])
 
@@ -58,6 +61,7 @@ LIGHT_EMISSIVE, LIGHT_DIRECTIONAL, LIGHT_POINT = 0, 1, 2
 assert MATERIAL.itemsize == 128 and TRIANGLE.itemsize == 128
 assert SKIN_CORNER.itemsize == 32
 assert BAKE_TEXEL.itemsize == 32 and BAKE_TEXEL.fields["normal"][1] == 16
+assert BAKE_DENOISE_PARAMS.itemsize == 32 and BAKE_DENOISE_PARAMS.fields["phi_position"][1] == 16
 assert PROBE.itemsize == 16 and PROBE.fields["enabled"][1] == 12
 assert MORPH_DELTA.itemsize == 96 and MORPH_DELTA.fields["target"][1] == 12 and MORPH_DELTA.fields["dn0"][1] == 48
 assert BVH_NODE.itemsize == 48 and LIGHT.itemsize == 48 and CAMERA.itemsize == 96

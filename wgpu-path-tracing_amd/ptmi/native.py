@@ -61,6 +61,7 @@ EXPORTS = [
     "ptmi_set_probe_depth", "ptmi_get_probe_depth", "ptmi_read_probe_depth", "ptmi_write_probe_depth", "ptmi_probe_depth_device_ptr",
     "ptmi_probe_visibility",
     "ptmi_scissor_status",
+    "ptmi_bake_denoise", "ptmi_bake_denoised_device_ptr", "ptmi_write_moments",
 ]
 # ptmi_scissor_status.reason (include/ptmi.h PTMI_SCISSOR_*)
 (SCISSOR_APPLIED, SCISSOR_OFF, SCISSOR_NOT_PLAIN, SCISSOR_ENVIRONMENT, SCISSOR_MEDIUM, SCISSOR_AOV, SCISSOR_MOMENTS, SCISSOR_ALPHA,
@@ -294,6 +295,12 @@ class BakeStatus(ctypes.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class BakeDenoiseParams(ctypes.Structure):
+    """ptmi_bake_denoise_params (include/ptmi.h ptmi_bake_denoise); 0 picks a field's default"""
+    _fields_ = [("iterations", ctypes.c_uint32), ("dilate", ctypes.c_uint32), ("phi_color", ctypes.c_float),
+                ("phi_normal", ctypes.c_float), ("phi_position", ctypes.c_float), ("reserved", ctypes.c_uint32 * 3)]
+
+
 class ProbeParams(ctypes.Structure):
     """ptmi_probe_params (include/ptmi.h ptmi_dispatch_probes)"""
     _fields_ = [("first_frame", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
@@ -386,6 +393,9 @@ _BAKE = {
     "ptmi_bake_status": [ctypes.c_void_p],
     "ptmi_bake_dilate": [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t],
     "ptmi_debug_bake_rays": [ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 6,
+    "ptmi_bake_denoise": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t],
+    "ptmi_bake_denoised_device_ptr": [],
+    "ptmi_write_moments": [ctypes.c_void_p, ctypes.c_size_t],
 }
 # light probes (include/ptmi.h ptmi_upload_probes ...): likewise
 _PROBES = {
@@ -482,6 +492,8 @@ def load():
             L.ptmi_debug_probe_tables.argtypes = [u32, vp, vp]
         if "ptmi_probe_depth_device_ptr" in EXPORTS:
             L.ptmi_probe_depth_device_ptr.restype = vp
+        if "ptmi_bake_denoised_device_ptr" in EXPORTS:
+            L.ptmi_bake_denoised_device_ptr.restype = vp
         if "ptmi_scissor_status" in EXPORTS:
             L.ptmi_scissor_status.argtypes = [vp, vp]
         _lib = L
@@ -1124,6 +1136,26 @@ class Context(_Handle):
         out = np.zeros((self.height, self.width, 4), np.float32)
         self._ck(self.L.ptmi_bake_dilate(self.h, passes, _p(out), out.size if n_floats is None else n_floats))
         return out
+
+    def bake_denoise(self, iterations=0, dilate=0, phi_color=0.0, phi_normal=0.0, phi_position=0.0, reserved=(0, 0, 0), dst=True,
+                     n_floats=None):
+        """the filtered lightmap (include/ptmi.h ptmi_bake_denoise), (H, W, 4) float32: rgb, and w = 1 covered / 2 filled by one of
+        the `dilate` gutter passes / 0 empty. Needs a surface and set_moments() during the bake; 0 picks a parameter's default.
+        dst=False: only queue it on the context's stream (bake_denoised_device_ptr) and return None. n_floats overrides the count
+        passed (for tests)."""
+        prm = BakeDenoiseParams(iterations, dilate, phi_color, phi_normal, phi_position, (ctypes.c_uint32 * 3)(*reserved))
+        out = np.zeros((self.height, self.width, 4), np.float32) if dst else None
+        n = (0 if out is None else out.size) if n_floats is None else n_floats
+        self._ck(self.L.ptmi_bake_denoise(self.h, ctypes.byref(prm), _p(out), n))
+        return out
+
+    def bake_denoised_device_ptr(self):
+        return self.L.ptmi_bake_denoised_device_ptr(self.h)
+
+    def write_moments(self, plane, n_floats=None):
+        """replaces the moments plane: W * H * 4 float32 (read_moments' layout). n_floats overrides the count passed (for tests)."""
+        a = np.ascontiguousarray(plane, np.float32)
+        self._ck(self.L.ptmi_write_moments(self.h, _p(a), a.size if n_floats is None else n_floats))
 
     def debug_bake_rays(self, xs, ys, frames, first_frame=0, bias=None, reserved=(0, 0)):
         """the first ray of texel (xs[i], ys[i]) at frames[i]: origins, directions (n, 3) float32 and RNG states (n,) uint32"""
