@@ -157,6 +157,30 @@ def test_gpu_matches_reference(ctx, scene_factory, name, dof):
     close_to_ref(ctx.denoise(), denoise_ref.denoise(rad, nrm, alb, mom))
 
 
+def test_gpu_matches_reference_past_one_workgroup(ctx, scene_factory):
+    """A frame wider than one 64 x 4 workgroup: 70 x 37 has two workgroup columns, the second 6 pixels wide, and a last row of
+    workgroups with one row of pixels in it. The camera stands 0.9 to the left of the reference's, so that the box's opening, which
+    is half the frame wide, reaches into the second column: the oracle's centre rays hit in 1092 pixels of the first column and 171 of
+    the second, and miss in 1276 and 51; the last row has hits. At 7 iterations the last step is 64: every tap but some of the
+    centre's own row falls outside the frame, and the four tap rows above and below are skipped whole."""
+    sc = scene_factory("cornell_spheres")
+    W, H = 70, 37
+    cam = layout.make_camera(W, H, position=(-0.9, 1.0, 2.8))
+    setup(ctx, sc, W, H)
+    run(ctx, cam, [3, 3])
+    rad, nrm, alb, mom = gpu_inputs(ctx)
+    hit = (nrm[..., :3] != 0).any(axis=-1)
+    for part in (hit[:, :64], hit[:, 64:]):
+        assert 20 < part.sum() < part.size - 20
+    assert hit[36].any() and np.isfinite(rad).all()
+    for it in (1, 5, 7):
+        for dm in (1, 2):
+            got = ctx.denoise(iterations=it, demodulate=dm)
+            ref = denoise_ref.denoise(rad, nrm, alb, mom, iterations=it, demodulate=dm == 2)
+            close_to_ref(got, ref)
+            assert not np.array_equal(bits(got[..., :3]), bits(rad[..., :3]))
+
+
 # 3 -----------------------------------------------------------------------------------------------------------------------------------
 # Measured with tests/denoise_ref.py on oracle renders of this Cornell box (moments from Oracle.trace_path), default parameters:
 # K = 4.37 at 64x64 and 4.06 at 96x96 against 1024 spp (the bar is test_denoise_host.K = 4.37 / 2); the mean change denoising

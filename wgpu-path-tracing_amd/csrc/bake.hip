@@ -1,6 +1,7 @@
 // bake.hip — lightmap baking (include/ptmi.h ptmi_upload_bake_surface, ptmi_dispatch_bake): the surface's records and
-// the list of its covered texels, the checks of a bake, the gutter fill and the debug rays. The bake's ray generation and folds are
-// with the other pixel sources (pipeline.hip BakedPixels); its bounce loop is the plain dispatch's (dispatch.hip).
+// the list of its covered texels, the checks of a bake, the gutter fill and the debug rays' checks (the rays themselves:
+// debug_stages.hip's listed-rays routine). The bake's ray generation and folds are with the other pixel sources (pipeline.hip
+// BakedPixels); its bounce loop is the plain dispatch's (dispatch.hip).
 // No counterpart in the reference, which renders from a camera only.
 #include "ptmi_ctx.h"
 
@@ -188,26 +189,7 @@ int ptmi_debug_bake_rays(ptmi_ctx *c, const ptmi_bake_params *params, uint32_t n
     if (!c->d_bake_texels) return fail(c, PTMI_E_INVALID, "no bake surface in place (ptmi_upload_bake_surface)");
     for (uint32_t i = 0; i < n; i++)
         if (xs[i] >= c->W || ys[i] >= c->H) return fail(c, PTMI_E_INVALID, "texel (%u, %u) outside the %ux%u surface", xs[i], ys[i], c->W, c->H);
-    if (n == 0) return PTMI_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, sync_all(c));
-    if ((rc = ensure_capacity(c, c->lane, n))) return rc;
-    Lane &ln = c->lane;
-    uint32_t *dx = ln.queue[0], *dy = ln.queue[1], *df = reinterpret_cast<uint32_t *>(ln.hits);
-    HIP_TRY(c, hipMemcpyAsync(dx, xs, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(dy, ys, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(df, frames, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    pt_launch_raygen_list(c->stream, BakeSurface{c->d_bake_texels, bp.bias}, c->W, n, dx, dy, df, ln.paths);
-    std::vector<float4> o(n), d(n);
-    HIP_TRY(c, hipMemcpyAsync(o.data(), ln.paths.O, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d.data(), ln.paths.D, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, sync_all(c));
-    for (uint32_t i = 0; i < n; i++) {
-        o3[3 * i] = o[i].x; o3[3 * i + 1] = o[i].y; o3[3 * i + 2] = o[i].z;
-        d3[3 * i] = d[i].x; d3[3 * i + 1] = d[i].y; d3[3 * i + 2] = d[i].z;
-        if (rng) std::memcpy(&rng[i], &o[i].w, 4);
-    }
-    return PTMI_OK;
+    return debug_listed_rays(c, BakeSurface{c->d_bake_texels, bp.bias}, c->W, n, xs, ys, frames, o3, d3, rng);
 }
 
 }  // extern "C"

@@ -29,23 +29,19 @@
 //
 // The kernels are the plain global-memory form: 64 x 4 workgroups, so a wave is one 64-texel row segment and every tap row of a plane
 // is one coalesced 1 KiB load. A lane whose texel is uncovered leaves after its guide load, so a wave of 64 uncovered texels retires
-// there; a tap whose guide N is zero loads neither its position nor its colour. (An LDS-tiled form for steps 1 and 2 was not built.)
+// there; a tap whose guide N is zero loads neither its position nor its colour. The pass itself is pt_atrous.h's, shared with
+// denoise.hip; what is the lightmap's own is the prepass and SurfaceGuide below: w_x, and the uncovered texels masked out.
 #include "ptmi_ctx.h"
-#include "pt_math.h"
+#include "pt_atrous.h"
 
 #include <algorithm>
-#include <cmath>
 
 namespace {
 
-constexpr int DX = 64, DY = 4;
+using namespace pt_atrous;
+
 constexpr float kStretch = 4.0f;
 
-PT_DEV float lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
-PT_DEV bool finite4(float4 v) {
-    return __builtin_isfinite(v.x) && __builtin_isfinite(v.y) && __builtin_isfinite(v.z) && __builtin_isfinite(v.w);
-}
-PT_DEV bool nonzero3(float4 g) { return g.x != 0.0f || g.y != 0.0f || g.z != 0.0f; }
 PT_DEV float len3(float x, float y, float z) { return __builtin_sqrtf(x * x + y * y + z * z); }
 
 __global__ __launch_bounds__(DX * DY) void k_bd_prepass(uint32_t W, uint32_t H, const float4 *__restrict__ texels,
@@ -80,106 +76,34 @@ __global__ __launch_bounds__(DX * DY) void k_bd_prepass(uint32_t W, uint32_t H, 
     cv[i] = make_float4(c.x, c.y, c.z, max1(0.0f, m.y - m.x * m.x) / max1(m.z, 1.0f));
 }
 
-// LAST: the final pass, which writes (rgb, 1) for covered texels and zeros for the others; the other passes write (rgb, variance) for
-// covered texels only
-template <bool LAST>
-__global__ __launch_bounds__(DX * DY) void k_bd_pass(uint32_t W, uint32_t H, uint32_t step, float phi_c, float phi_n, float phi_x,
-                                                     const float4 *__restrict__ guide_n, const float4 *__restrict__ guide_p,
-                                                     const float4 *__restrict__ src, float4 *__restrict__ dst) {
-    const uint32_t x = blockIdx.x * DX + threadIdx.x, y = blockIdx.y * DY + threadIdx.y;
-    if (x >= W || y >= H) return;
-    const size_t i = (size_t)y * W + x;
-    const float4 gp = guide_n[i];
-    if (!nonzero3(gp)) {
-        if (LAST) dst[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        return;
+// The guide plane is guide N = (unit normal or 0 where uncovered, footprint); guide P is the policy's own.
+struct SurfaceGuide {
+    const float4 *guide_p;
+    float phi_x;
+    static constexpr bool kMasked = true;
+    struct Centre { float4 pp; float den_x; };
+    PT_DEV Centre centre(size_t i, float4 gp) const { return {guide_p[i], phi_x * gp.w + 1e-6f}; }
+    PT_DEV float weight(const Centre &at, float4 gp, float4, size_t qi, float off) const {
+        const float4 pq = guide_p[qi];
+        const float ex = pq.x - at.pp.x, ey = pq.y - at.pp.y, ez = pq.z - at.pp.z;
+        const float dist = len3(ex, ey, ez);
+        const float plane = __builtin_fabsf(gp.x * ex + gp.y * ey + gp.z * ez);
+        const float e = max1(plane, dist - kStretch * off * gp.w);
+        return __builtin_expf(-e / at.den_x);
     }
-    const float4 cp = src[i];
-    float4 o = cp;
-    if (finite4(cp)) {
-        // g3x3(var): the centre is covered and finite, so the weight sum is at least 1/4
-        float sv = 0.0f, sk = 0.0f;
-        for (int dy = -1; dy <= 1; dy++) {
-            const int qy = (int)y + dy;
-            if (qy < 0 || qy >= (int)H) continue;
-            for (int dx = -1; dx <= 1; dx++) {
-                const int qx = (int)x + dx;
-                if (qx < 0 || qx >= (int)W) continue;
-                const size_t qi = (size_t)qy * W + qx;
-                if (!nonzero3(guide_n[qi])) continue;
-                const float4 q = src[qi];
-                if (!finite4(q)) continue;
-                const float k = (dy == 0 ? 0.5f : 0.25f) * (dx == 0 ? 0.5f : 0.25f);
-                sv = sv + k * q.w;
-                sk = sk + k;
-            }
-        }
-        const float lp = lum(cp.x, cp.y, cp.z);
-        const float den_l = phi_c * __builtin_sqrtf(sv / sk) + 1e-6f;
-        const float fp = gp.w;
-        const float den_x = phi_x * fp + 1e-6f;
-        const float4 pp = guide_p[i];
-        constexpr float h[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
-        const float w0 = h[2] * h[2];
-        float sw = w0, sr = w0 * cp.x, sg = w0 * cp.y, sb = w0 * cp.z, s2 = w0 * w0 * cp.w;
-#pragma unroll
-        for (int dy = -2; dy <= 2; dy++) {
-            const int qy = (int)y + dy * (int)step;
-            if (qy < 0 || qy >= (int)H) continue;
-#pragma unroll
-            for (int dx = -2; dx <= 2; dx++) {
-                if (dx == 0 && dy == 0) continue;
-                const int qx = (int)x + dx * (int)step;
-                if (qx < 0 || qx >= (int)W) continue;
-                const size_t qi = (size_t)qy * W + qx;
-                const float4 gq = guide_n[qi];
-                if (!nonzero3(gq)) continue;
-                const float4 q = src[qi];
-                if (!finite4(q)) continue;
-                const float4 pq = guide_p[qi];
-                const float wn = __builtin_powf(max1(0.0f, gp.x * gq.x + gp.y * gq.y + gp.z * gq.z), phi_n);
-                const float ex = pq.x - pp.x, ey = pq.y - pp.y, ez = pq.z - pp.z;
-                const float dist = len3(ex, ey, ez);
-                const float plane = __builtin_fabsf(gp.x * ex + gp.y * ey + gp.z * ez);
-                const float off = (float)step * __builtin_sqrtf((float)(dx * dx + dy * dy));
-                const float e = max1(plane, dist - kStretch * off * fp);
-                const float wx = __builtin_expf(-e / den_x);
-                const float wl = __builtin_expf(-__builtin_fabsf(lp - lum(q.x, q.y, q.z)) / den_l);
-                const float w = h[dy + 2] * h[dx + 2] * wn * wx * wl;
-                sw = sw + w;
-                sr = sr + w * q.x; sg = sg + w * q.y; sb = sb + w * q.z;
-                s2 = s2 + w * w * q.w;
-            }
-        }
-        o = make_float4(sr / sw, sg / sw, sb / sw, s2 / (sw * sw));
-    }
-    if (LAST) o.w = 1.0f;
-    dst[i] = o;
-}
-
-struct BakeDenoiseArgs {
-    uint32_t W, H, iterations, dilate;
-    float phi_color, phi_normal, phi_position;
+    // (rgb, 1): the masked plane bake.hip's k_bake_mask makes
+    PT_DEV void finish(size_t, float4 &o) const { o.w = 1.0f; }
 };
 
-// The prepass, the passes and the gutter fill on stream s. a and b are the ping-pong planes; the result lands in `out` whatever the
-// counts are: the last pass of the filter writes there when no gutter pass follows, else the last gutter pass does.
-void launch(hipStream_t s, const BakeDenoiseArgs &p, const float4 *texels, const float4 *radiance, const float4 *moments, float4 *guide_n,
-            float4 *guide_p, float4 *a, float4 *b, float4 *out) {
-    const dim3 grid((p.W + DX - 1) / DX, (p.H + DY - 1) / DY), block(DX, DY);
-    hipLaunchKernelGGL(k_bd_prepass, grid, block, 0, s, p.W, p.H, texels, radiance, moments, guide_n, guide_p, a);
-    float4 *src = a, *spare = b;
-    for (uint32_t it = 0; it + 1u < p.iterations; it++) {
-        hipLaunchKernelGGL(k_bd_pass<false>, grid, block, 0, s, p.W, p.H, 1u << it, p.phi_color, p.phi_normal, p.phi_position, guide_n,
-                           guide_p, src, spare);
-        std::swap(src, spare);
-    }
-    float4 *const masked = p.dilate ? spare : out;
-    hipLaunchKernelGGL(k_bd_pass<true>, grid, block, 0, s, p.W, p.H, 1u << (p.iterations - 1u), p.phi_color, p.phi_normal,
-                       p.phi_position, guide_n, guide_p, src, masked);
-    std::swap(src, spare);                                        // src: the masked plane; spare: free
-    for (uint32_t k = 0; k < p.dilate; k++) {
-        float4 *const to = k + 1u == p.dilate ? out : spare;
+// The prepass, the passes and `dilate` passes of the gutter fill on stream s. a and b are the ping-pong planes; the result lands in
+// `out` whatever the counts are: the last pass of the filter writes there when no gutter pass follows, else the last gutter pass does.
+void launch(hipStream_t s, const AtrousArgs &p, uint32_t dilate, const float4 *texels, const float4 *radiance, const float4 *moments,
+            float4 *guide_n, float4 *guide_p, float4 *a, float4 *b, float4 *out) {
+    hipLaunchKernelGGL(k_bd_prepass, grid(p.W, p.H), block(), 0, s, p.W, p.H, texels, radiance, moments, guide_n, guide_p, a);
+    float4 *src = launch_passes(s, p, guide_n, SurfaceGuide{guide_p, p.phi_geo}, a, b, dilate ? nullptr : out);
+    float4 *spare = src == a ? b : a;                             // src: the masked plane; spare: free
+    for (uint32_t k = 0; k < dilate; k++) {
+        float4 *const to = k + 1u == dilate ? out : spare;
         pt_launch_bake_dilate_pass(s, p.W, p.H, src, to);
         spare = src; src = to;
     }
@@ -193,34 +117,21 @@ int ptmi_bake_denoise(ptmi_ctx *c, const ptmi_bake_denoise_params *p, float *dst
     if (!c) return PTMI_E_INVALID;
     const ptmi_bake_denoise_params zero = {};
     const ptmi_bake_denoise_params &q = p ? *p : zero;
-    if (q.iterations > 10u) return fail(c, PTMI_E_INVALID, "iterations = %u is above 10", q.iterations);
-    if (q.reserved[0] || q.reserved[1] || q.reserved[2]) return fail(c, PTMI_E_INVALID, "a reserved word of ptmi_bake_denoise_params is not zero");
-    const float phis[3] = {q.phi_color, q.phi_normal, q.phi_position};
-    for (float f : phis)
-        if (!std::isfinite(f) || f < 0.0f) return fail(c, PTMI_E_INVALID, "phi %g is negative or not finite", (double)f);
-    if (!c->d_out) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
+    AtrousArgs a;
+    int rc = atrous_params(c, q.iterations, q.reserved, " of ptmi_bake_denoise_params", q.phi_color, q.phi_normal, q.phi_position, &a);
+    if (rc) return rc;
     if (!c->d_bake_texels) return fail(c, PTMI_E_INVALID, "no bake surface in place (ptmi_upload_bake_surface)");
     const size_t npix = (size_t)c->W * c->H;
     if (dst_rgba && n_floats != npix * 4) return fail(c, PTMI_E_INVALID, "expected %zu floats, got %zu", npix * 4, n_floats);
     if (!c->moments_on || !c->plane[kMoments]) return fail(c, PTMI_E_STATE, "the bake denoiser needs the moments plane (ptmi_set_moments)");
     HIP_TRY(c, hipSetDevice(c->device));
-    const int rc = make_planes(c, group_set(kByBake) | group_set(kByBakeDenoise), npix, c->plane);
-    if (rc) return rc;
-    BakeDenoiseArgs a;
-    a.W = c->W; a.H = c->H;
-    a.iterations = q.iterations ? q.iterations : 5u;
+    if ((rc = make_planes(c, group_set(kByBake) | group_set(kByBakeDenoise), npix, c->plane))) return rc;
     // a pass fills the texels one step (in the maximum norm) further from the covered ones, and none is farther than the longer side
-    a.dilate = std::min(q.dilate, std::max(c->W, c->H));
-    a.phi_color = q.phi_color > 0.0f ? q.phi_color : 4.0f;
-    a.phi_normal = q.phi_normal > 0.0f ? q.phi_normal : 128.0f;
-    a.phi_position = q.phi_position > 0.0f ? q.phi_position : 1.0f;
-    launch(c->stream, a, c->d_bake_texels, c->d_out, plane_as<float4>(c, kMoments), plane_as<float4>(c, kBdGuideN),
+    const uint32_t dilate = std::min(q.dilate, std::max(c->W, c->H));
+    launch(c->stream, a, dilate, c->d_bake_texels, c->d_out, plane_as<float4>(c, kMoments), plane_as<float4>(c, kBdGuideN),
            plane_as<float4>(c, kBdGuideP), plane_as<float4>(c, kBakeA), plane_as<float4>(c, kBakeB), plane_as<float4>(c, kBdOut));
     HIP_TRY(c, hipGetLastError());
-    if (!dst_rgba) return PTMI_OK;
-    HIP_TRY(c, quiesce(c));
-    HIP_TRY(c, hipMemcpy(dst_rgba, c->plane[kBdOut], npix * 16, hipMemcpyDeviceToHost));
-    return PTMI_OK;
+    return dst_rgba ? read_plane(c, kBdOut, c->plane[kBdOut], dst_rgba, n_floats, 4) : PTMI_OK;
 }
 
 void *ptmi_bake_denoised_device_ptr(ptmi_ctx *c) { return c ? c->plane[kBdOut] : nullptr; }

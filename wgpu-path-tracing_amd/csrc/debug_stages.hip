@@ -1,5 +1,7 @@
 // debug_stages.hip — the per-stage entry points of include/ptmi.h (ptmi_debug_*): one stage of the pipeline on the caller's rays, for
-// the parity tests. (Those of the traversal image are with the image, scene_image.hip.)
+// the parity tests. (Those of the traversal image are with the image, scene_image.hip.) debug_listed_rays is the first rays of listed
+// pixels from any ray source: ptmi_debug_raygen here, ptmi_debug_bake_rays (bake.hip) and ptmi_debug_probe_rays (probes.hip) are
+// their own checks and one call of it.
 #include "ptmi_ctx.h"
 
 #include <cstring>
@@ -37,6 +39,29 @@ void unpack3(const std::vector<float4> &o, const std::vector<float4> &d, float *
 
 }  // namespace
 
+PT_HOST {
+
+int debug_listed_rays(ptmi_ctx *c, const DevRays &rays, uint32_t width, uint32_t n, const uint32_t *xs, const uint32_t *ys,
+                      const uint32_t *frames, float *o3, float *d3, uint32_t *rng) {
+    if (n == 0) return PTMI_OK;
+    const int rc = stage_begin(c, n);
+    if (rc) return rc;
+    Lane &ln = c->lane;
+    uint32_t *dx = ln.queue[0], *dy = ln.queue[1], *df = reinterpret_cast<uint32_t *>(ln.hits);
+    HIP_TRY(c, hipMemcpyAsync(dx, xs, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dy, ys, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(df, frames, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    pt_launch_raygen_list(c->stream, rays, width, n, dx, dy, df, ln.paths);
+    std::vector<float4> o(n), d(n);
+    HIP_TRY(c, hipMemcpyAsync(o.data(), ln.paths.O, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d.data(), ln.paths.D, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, sync_all(c));
+    unpack3(o, d, o3, d3, rng);
+    return PTMI_OK;
+}
+
+}  // namespace pt_host
+
 extern "C" {
 
 // ---- per-stage entry points ------------------------------------------------------
@@ -46,20 +71,7 @@ int ptmi_debug_raygen(ptmi_ctx *c, const ptmi_camera *cam, uint32_t n, const uin
     uint32_t proj;
     int rc = pt_check_camera(c, cam, &proj, c->err);
     if (rc) return rc;
-    if (n == 0) return PTMI_OK;
-    if ((rc = stage_begin(c, n))) return rc;
-    Lane &ln = c->lane;
-    uint32_t *dx = ln.queue[0], *dy = ln.queue[1], *df = reinterpret_cast<uint32_t *>(ln.hits);
-    HIP_TRY(c, hipMemcpyAsync(dx, xs, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(dy, ys, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(df, frames, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    pt_launch_raygen_list(c->stream, CameraSource{cam, proj}, cam->width, n, dx, dy, df, ln.paths);
-    std::vector<float4> o(n), d(n);
-    HIP_TRY(c, hipMemcpyAsync(o.data(), ln.paths.O, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d.data(), ln.paths.D, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, sync_all(c));
-    unpack3(o, d, o3, d3, rng);
-    return PTMI_OK;
+    return debug_listed_rays(c, CameraSource{cam, proj}, cam->width, n, xs, ys, frames, o3, d3, rng);
 }
 
 int ptmi_debug_center_rays(ptmi_ctx *c, const ptmi_camera *cam, float *o3, float *d3, size_t n_floats_each) {

@@ -14,17 +14,13 @@
 //   last pass remodulates with the same clamped albedo and writes (rgb, 0).
 // Every expression is written in the order tests/denoise_ref.py restates it; the library builds with -ffp-contract=off, so the only
 // differences to a float32 numpy restatement are exp and pow (a few ulp).
-#include "pt_device.h"
-#include "pt_math.h"
+// The pass itself is pt_atrous.h's, shared with bake_denoise.hip; what is the camera's own is the prepass and DepthGuide below: w_z,
+// a miss written through, and the remodulation.
+#include "pt_atrous.h"
 
 namespace {
 
-constexpr int DX = 64, DY = 4;          // a wave is one 64-pixel row segment: every tap row is one coalesced 1 KiB load
-
-PT_DEV float lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
-PT_DEV bool finite4(float4 v) {
-    return __builtin_isfinite(v.x) && __builtin_isfinite(v.y) && __builtin_isfinite(v.z) && __builtin_isfinite(v.w);
-}
+using namespace pt_atrous;
 
 __global__ __launch_bounds__(DX * DY) void k_dn_prepass(uint32_t W, uint32_t H, const float4 *__restrict__ radiance,
                                                         const float4 *__restrict__ normal, const float4 *__restrict__ albedo,
@@ -60,94 +56,31 @@ __global__ __launch_bounds__(DX * DY) void k_dn_prepass(uint32_t W, uint32_t H, 
     cv[i] = o;
 }
 
-// LAST: the final pass, which remodulates (albedo non-NULL) and writes (rgb, 0); the others write (rgb, variance)
-template <bool LAST>
-__global__ __launch_bounds__(DX * DY) void k_dn_pass(uint32_t W, uint32_t H, uint32_t step, float phi_c, float phi_n, float phi_z,
-                                                     const float4 *__restrict__ guide, const float *__restrict__ grad,
-                                                     const float4 *__restrict__ src, const float4 *__restrict__ albedo,
-                                                     float4 *__restrict__ dst) {
-    const uint32_t x = blockIdx.x * DX + threadIdx.x, y = blockIdx.y * DY + threadIdx.y;
-    if (x >= W || y >= H) return;
-    const size_t i = (size_t)y * W + x;
-    const float4 cp = src[i];
-    const float4 gp = guide[i];
-    float4 o = cp;
-    if (finite4(cp) && (gp.x != 0.0f || gp.y != 0.0f || gp.z != 0.0f)) {
-        // g3x3(var): the centre is finite, so the weight sum is at least 1/4
-        float sv = 0.0f, sk = 0.0f;
-        for (int dy = -1; dy <= 1; dy++) {
-            const int qy = (int)y + dy;
-            if (qy < 0 || qy >= (int)H) continue;
-            for (int dx = -1; dx <= 1; dx++) {
-                const int qx = (int)x + dx;
-                if (qx < 0 || qx >= (int)W) continue;
-                const float4 q = src[(size_t)qy * W + qx];
-                if (!finite4(q)) continue;
-                const float k = (dy == 0 ? 0.5f : 0.25f) * (dx == 0 ? 0.5f : 0.25f);
-                sv = sv + k * q.w;
-                sk = sk + k;
-            }
-        }
-        const float lp = lum(cp.x, cp.y, cp.z);
-        const float den_l = phi_c * __builtin_sqrtf(sv / sk) + 1e-6f;
-        const float gz = grad[i];
-        constexpr float h[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
-        const float w0 = h[2] * h[2];
-        float sw = w0, sr = w0 * cp.x, sg = w0 * cp.y, sb = w0 * cp.z, s2 = w0 * w0 * cp.w;
-#pragma unroll
-        for (int dy = -2; dy <= 2; dy++) {
-            const int qy = (int)y + dy * (int)step;
-            if (qy < 0 || qy >= (int)H) continue;
-#pragma unroll
-            for (int dx = -2; dx <= 2; dx++) {
-                if (dx == 0 && dy == 0) continue;
-                const int qx = (int)x + dx * (int)step;
-                if (qx < 0 || qx >= (int)W) continue;
-                const size_t qi = (size_t)qy * W + qx;
-                const float4 q = src[qi];
-                const float4 gq = guide[qi];
-                if (!finite4(q) || (gq.x == 0.0f && gq.y == 0.0f && gq.z == 0.0f)) continue;
-                const float wn = __builtin_powf(max1(0.0f, gp.x * gq.x + gp.y * gq.y + gp.z * gq.z), phi_n);
-                const float off = (float)step * __builtin_sqrtf((float)(dx * dx + dy * dy));
-                const float wz = __builtin_expf(-__builtin_fabsf(gp.w - gq.w) / (phi_z * off * gz + 1e-6f));
-                const float wl = __builtin_expf(-__builtin_fabsf(lp - lum(q.x, q.y, q.z)) / den_l);
-                const float w = h[dy + 2] * h[dx + 2] * wn * wz * wl;
-                sw = sw + w;
-                sr = sr + w * q.x; sg = sg + w * q.y; sb = sb + w * q.z;
-                s2 = s2 + w * w * q.w;
-            }
-        }
-        o = make_float4(sr / sw, sg / sw, sb / sw, s2 / (sw * sw));
+// The guide plane is (unit normal or 0 on a miss, depth). A miss carries a value (the sky, the background), so nothing is masked.
+struct DepthGuide {
+    const float *grad;
+    const float4 *albedo;               // NULL: no demodulation
+    float phi_z;
+    static constexpr bool kMasked = false;
+    struct Centre { float gz; };
+    PT_DEV Centre centre(size_t i, float4) const { return {grad[i]}; }
+    PT_DEV float weight(Centre at, float4 gp, float4 gq, size_t, float off) const {
+        return __builtin_expf(-__builtin_fabsf(gp.w - gq.w) / (phi_z * off * at.gz + 1e-6f));
     }
-    if (LAST) {
+    // remodulates and writes (rgb, 0)
+    PT_DEV void finish(size_t i, float4 &o) const {
         if (albedo) {
             const float4 a = albedo[i];
             if (a.w > 0.0f) { o.x = o.x * max1(a.x, 1e-3f); o.y = o.y * max1(a.y, 1e-3f); o.z = o.z * max1(a.z, 1e-3f); }
         }
         o.w = 0.0f;
     }
-    dst[i] = o;
-}
+};
 
 }  // namespace
 
-void pt_launch_denoise(hipStream_t s, const DenoiseArgs &a, const float4 *radiance, const float4 *normal, const float4 *albedo,
+void pt_launch_denoise(hipStream_t s, const AtrousArgs &a, const float4 *radiance, const float4 *normal, const float4 *albedo,
                        const float4 *moments, float4 *guide, float *grad, float4 *cv, float4 *tmp, float4 *out) {
-    const dim3 grid((a.W + DX - 1) / DX, (a.H + DY - 1) / DY), block(DX, DY);
-    hipLaunchKernelGGL(k_dn_prepass, grid, block, 0, s, a.W, a.H, radiance, normal, albedo, moments, guide, grad, cv);
-    const float4 *src = cv;
-    float4 *spare = tmp;
-    for (uint32_t it = 0; it < a.iterations; it++) {
-        const uint32_t step = 1u << it;
-        if (it + 1u == a.iterations) {
-            hipLaunchKernelGGL(k_dn_pass<true>, grid, block, 0, s, a.W, a.H, step, a.phi_color, a.phi_normal, a.phi_depth, guide, grad,
-                               src, albedo, out);
-        } else {
-            hipLaunchKernelGGL(k_dn_pass<false>, grid, block, 0, s, a.W, a.H, step, a.phi_color, a.phi_normal, a.phi_depth, guide,
-                               grad, src, nullptr, spare);
-            float4 *const read_next = spare;
-            spare = const_cast<float4 *>(src);
-            src = read_next;
-        }
-    }
+    hipLaunchKernelGGL(k_dn_prepass, grid(a.W, a.H), block(), 0, s, a.W, a.H, radiance, normal, albedo, moments, guide, grad, cv);
+    launch_passes(s, a, guide, DepthGuide{grad, albedo, a.phi_geo}, cv, tmp, out);
 }

@@ -1,7 +1,8 @@
 // probes.hip — light probes (include/ptmi.h ptmi_upload_probes, ptmi_dispatch_probes, ptmi_probe_sh, ptmi_probe_irradiance,
 // ptmi_probe_visibility): the probe records, the texel list of the enabled probes' tiles and the two float64 tables
 // of a tile size, the checks of a probe dispatch, the debug rays, and the reductions that turn a probe's tiles into what an engine
-// reads: SH9 and irradiance from the radiance tile, visibility from the depth tile. The probe's ray generation is with the other ray
+// reads: SH9 from the radiance tile, and irradiance from it and visibility from the depth tile by one tile gather over a lobe policy
+// (k_probe_gather, gather_tiles). The debug rays are debug_stages.hip's listed-rays routine. The probe's ray generation is with the other ray
 // sources (pipeline.hip ProbeRays); its pixels are BakedPixels, its folds pipeline.hip's (fold_probe_depth among them) and its bounce
 // loop the plain dispatch's (dispatch.hip); the depth plane's switch is with the other planes' (ptmi_api.hip).
 // No counterpart in the reference, which renders from a camera only.
@@ -11,7 +12,6 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
-#include <cstring>
 #include <vector>
 
 namespace {
@@ -59,88 +59,80 @@ __global__ __launch_bounds__(BLOCK) void k_probe_sh(DevProbeAtlas a, const float
     }
 }
 
-// Irradiance tiles: one workgroup per probe. Every one of the m * m output texels sums over all N * N texels of the probe's tile, so the
-// tile (as three planes, 12 B a texel) and the (d, dw) table (16 B) are staged once in dynamic LDS: 28 B a texel, 112 KB at N = 64,
-// which leaves one workgroup per CU there and five at N = 32. A wave takes output texels wave, wave + WAVES, ...; its lanes split t as
-// k_probe_sh's do, so consecutive lanes read consecutive LDS words (no bank conflict) and one b128 each of the table.
-__global__ __launch_bounds__(BLOCK) void k_probe_irradiance(DevProbeAtlas a, const float4 *__restrict__ dir_dw,
-                                                            const float4 *__restrict__ normals, uint32_t m, float4 *__restrict__ irr) {
+// The tile gather of ptmi_probe_irradiance and ptmi_probe_visibility: one workgroup per probe. Every one of the m * m output texels
+// sums over all N * N texels of the probe's tile, so the tile (as three planes, 12 B a texel) and the (d, dw) table (16 B) are staged
+// once in dynamic LDS: 28 B a texel, 112 KB at N = 64, which leaves one workgroup per CU there and five at N = 32. A wave takes output
+// texels wave, wave + WAVES, ...; its lanes split t as k_probe_sh's do, so consecutive lanes read consecutive LDS words (no bank
+// conflict) and one b128 each of the table. A disabled probe's tile is zeros. The lobe policy says the rest:
+//   SUMS          3: the three channels; 4: the weights too
+//   side(m)       the output tile's side
+//   shape(c)      the lobe's value from the clamped cosine c
+//   store(...)    lane 0's finish of output texel j from the wave's sums
+template <class Lobe>
+__global__ __launch_bounds__(BLOCK) void k_probe_gather(DevProbeAtlas a, const float4 *__restrict__ dir_dw,
+                                                        const float4 *__restrict__ normals, uint32_t m, const Lobe lobe,
+                                                        float4 *__restrict__ out) {
     extern __shared__ float4 lds[];
-    const uint32_t i = blockIdx.x, N = 1u << a.shift, NN = N << a.shift, mm = m * m;
-    float4 *const dst = irr + (size_t)i * mm;
+    const uint32_t i = blockIdx.x, N = 1u << a.shift, NN = N << a.shift, mm = m * m, out_texels = lobe.side(m) * lobe.side(m);
+    float4 *const dst = out + (size_t)i * out_texels;
     if (__float_as_uint(a.probes[i].w) == 0u) {                     // (the whole workgroup)
-        for (uint32_t j = threadIdx.x; j < mm; j += BLOCK) dst[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        for (uint32_t j = threadIdx.x; j < out_texels; j += BLOCK) dst[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         return;
     }
     float4 *const tab = lds;
-    float *const r = reinterpret_cast<float *>(lds + NN), *const g = r + NN, *const b = g + NN;
+    float *const c0 = reinterpret_cast<float *>(lds + NN), *const c1 = c0 + NN, *const c2 = c1 + NN;
     const float4 *const tile = a.out + (size_t)((i / a.cols) << a.shift) * a.W + ((i % a.cols) << a.shift);
     for (uint32_t t = threadIdx.x; t < NN; t += BLOCK) {
         const float4 L = tile[(size_t)(t >> a.shift) * a.W + (t & (N - 1u))];
-        tab[t] = dir_dw[t]; r[t] = L.x; g[t] = L.y; b[t] = L.z;
+        tab[t] = dir_dw[t]; c0[t] = L.x; c1[t] = L.y; c2[t] = L.z;
     }
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u;
     for (uint32_t j = threadIdx.x >> 6; j < mm; j += WAVES) {
         const v3 n = xyz(normals[j]);
-        float acc[3] = {0.0f, 0.0f, 0.0f};
+        float acc[Lobe::SUMS] = {};
         for (uint32_t t = lane; t < NN; t += 64u) {
             const float4 d = tab[t];
             float c = dot3(n, xyz(d));
             c = c > 0.0f ? c : 0.0f;
-            const float wgt = __fmul_rn(c, d.w);
-            acc[0] = __fadd_rn(acc[0], __fmul_rn(wgt, r[t]));
-            acc[1] = __fadd_rn(acc[1], __fmul_rn(wgt, g[t]));
-            acc[2] = __fadd_rn(acc[2], __fmul_rn(wgt, b[t]));
+            const float wgt = __fmul_rn(lobe.shape(c), d.w);
+            acc[0] = __fadd_rn(acc[0], __fmul_rn(wgt, c0[t]));
+            acc[1] = __fadd_rn(acc[1], __fmul_rn(wgt, c1[t]));
+            acc[2] = __fadd_rn(acc[2], __fmul_rn(wgt, c2[t]));
+            if constexpr (Lobe::SUMS == 4) acc[3] = __fadd_rn(acc[3], wgt);
         }
         butterfly(acc);
-        if (lane == 0u) dst[j] = make_float4(__fmul_rn(acc[0], INV_PI), __fmul_rn(acc[1], INV_PI), __fmul_rn(acc[2], INV_PI), 1.0f);
+        if (lane == 0u) lobe.store(dst, m, j, acc);
     }
 }
 
-// Visibility tiles (include/ptmi.h ptmi_probe_visibility): k_probe_irradiance's shape over the probe's tile of the depth plane, with a
-// power-cosine lobe of s squarings for the clamped cosine, a fourth sum for the weights and a division for the 1 / pi. The same 28 B a
-// texel of dynamic LDS. With border = 1 the lane that writes an interior texel of the tile's rim writes the ring texels that copy it
-// as well (up to three): every ring texel has one source, so nothing is read back and nothing is written twice.
-__global__ __launch_bounds__(BLOCK) void k_probe_visibility(DevProbeAtlas a, const float4 *__restrict__ dir_dw,
-                                                            const float4 *__restrict__ normals, uint32_t m, uint32_t sharp, uint32_t border,
-                                                            float4 *__restrict__ vis) {
-    extern __shared__ float4 lds[];
-    const uint32_t i = blockIdx.x, N = 1u << a.shift, NN = N << a.shift, mm = m * m, side = m + 2u * border;
-    float4 *const dst = vis + (size_t)i * side * side;
-    if (__float_as_uint(a.probes[i].w) == 0u) {                     // (the whole workgroup)
-        for (uint32_t j = threadIdx.x; j < side * side; j += BLOCK) dst[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        return;
+// Irradiance (what the documents call k_probe_irradiance): the clamped cosine over the radiance tile, times 1 / pi.
+struct IrradianceLobe {
+    static constexpr int SUMS = 3;
+    PT_HD uint32_t side(uint32_t m) const { return m; }
+    PT_DEV float shape(float c) const { return c; }
+    PT_DEV void store(float4 *dst, uint32_t, uint32_t j, const float (&acc)[3]) const {
+        dst[j] = make_float4(__fmul_rn(acc[0], INV_PI), __fmul_rn(acc[1], INV_PI), __fmul_rn(acc[2], INV_PI), 1.0f);
     }
-    float4 *const tab = lds;
-    float *const dx = reinterpret_cast<float *>(lds + NN), *const dy = dx + NN, *const dz = dy + NN;
-    const float4 *const tile = a.out + (size_t)((i / a.cols) << a.shift) * a.W + ((i % a.cols) << a.shift);
-    for (uint32_t t = threadIdx.x; t < NN; t += BLOCK) {
-        const float4 D = tile[(size_t)(t >> a.shift) * a.W + (t & (N - 1u))];
-        tab[t] = dir_dw[t]; dx[t] = D.x; dy[t] = D.y; dz[t] = D.z;
+};
+
+// Visibility (include/ptmi.h ptmi_probe_visibility; what the documents call k_probe_visibility): over the probe's tile of the depth
+// plane, a power-cosine lobe of `sharp` squarings of the clamped cosine, divided by the sum of the weights. With border = 1 the lane
+// that writes an interior texel of the tile's rim writes the ring texels that copy it as well (up to three): every ring texel has one
+// source, so nothing is read back and nothing is written twice.
+struct VisibilityLobe {
+    uint32_t sharp, border;
+    static constexpr int SUMS = 4;
+    PT_HD uint32_t side(uint32_t m) const { return m + 2u * border; }
+    PT_DEV float shape(float p) const {
+        for (uint32_t k = 0; k < sharp; k++) p = __fmul_rn(p, p);
+        return p;
     }
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u;
-    for (uint32_t j = threadIdx.x >> 6; j < mm; j += WAVES) {
-        const v3 n = xyz(normals[j]);
-        float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        for (uint32_t t = lane; t < NN; t += 64u) {
-            const float4 d = tab[t];
-            float p = dot3(n, xyz(d));
-            p = p > 0.0f ? p : 0.0f;
-            for (uint32_t k = 0; k < sharp; k++) p = __fmul_rn(p, p);
-            const float wgt = __fmul_rn(p, d.w);
-            acc[0] = __fadd_rn(acc[0], __fmul_rn(wgt, dx[t]));
-            acc[1] = __fadd_rn(acc[1], __fmul_rn(wgt, dy[t]));
-            acc[2] = __fadd_rn(acc[2], __fmul_rn(wgt, dz[t]));
-            acc[3] = __fadd_rn(acc[3], wgt);
-        }
-        butterfly(acc);
-        if (lane != 0u) continue;
+    PT_DEV void store(float4 *dst, uint32_t m, uint32_t j, const float (&acc)[4]) const {
         const float4 v = make_float4(__fdiv_rn(acc[0], acc[3]), __fdiv_rn(acc[1], acc[3]), __fdiv_rn(acc[2], acc[3]), 1.0f);
-        const uint32_t x = j % m, y = j / m, e = m - 1u;
+        const uint32_t x = j % m, y = j / m, e = m - 1u, side = m + 2u * border;
         dst[(size_t)(y + border) * side + (x + border)] = v;
-        if (border == 0u) continue;
+        if (border == 0u) return;
         // the ring texels that copy this one under the octahedral wrap (include/ptmi.h has the table), bordered coordinates
         if (x == 0u) dst[(size_t)(e - y + 1u) * side] = v;                          // (-1, e - y)
         if (x == e) dst[(size_t)(e - y + 1u) * side + (m + 1u)] = v;                // (m, e - y)
@@ -149,7 +141,7 @@ __global__ __launch_bounds__(BLOCK) void k_probe_visibility(DevProbeAtlas a, con
         if ((x == 0u || x == e) && (y == 0u || y == e))                             // the opposite corner of the ring
             dst[(size_t)(y ? 0u : m + 1u) * side + (x ? 0u : m + 1u)] = v;
     }
-}
+};
 
 // ---- the tables (include/ptmi.h states them): float64, + - * / and sqrt alone, rounded once ---------------------------------------
 constexpr double PI64 = 3.141592653589793;
@@ -186,14 +178,19 @@ void probe_tables(uint32_t N, float *dir_dw, float *basis) {
     }
 }
 
-// the default dynamic-LDS cap is 64 KB: raise it for `kernel` to what the largest tile takes, once per device. The attribute is a
-// kernel's own, so each of the two kernels that stage a tile has its own `raised`.
-void allow_tile_lds(const void *kernel, std::atomic<uint64_t> &raised) {
+// what k_probe_gather stages for a tile of 1 << shift texels a side
+size_t tile_lds(uint32_t shift) { return ((size_t)1 << (2u * shift)) * (sizeof(float4) + 3u * sizeof(float)); }
+
+// the default dynamic-LDS cap is 64 KB: raise it for k_probe_gather<Lobe> to what the largest tile takes, once per device. The
+// attribute is a kernel's own, so each instantiation has its own `raised`.
+template <class Lobe>
+void allow_tile_lds() {
+    static std::atomic<uint64_t> raised{0};
     int dev = 0;
     (void)hipGetDevice(&dev);
     const uint64_t bit = 1ull << (dev & 63);
     if (raised.load(std::memory_order_relaxed) & bit) return;
-    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pt_probe_irradiance_lds(6));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_probe_gather<Lobe>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds(6));
     raised.fetch_or(bit, std::memory_order_relaxed);
 }
 
@@ -221,25 +218,36 @@ int reduction_ready(ptmi_ctx *c, const float *dst, size_t n_floats, size_t want)
     return PTMI_OK;
 }
 
-}  // namespace
+// What ptmi_probe_irradiance and ptmi_probe_visibility do once their own parameters are checked: the check of m, reduction_ready, the
+// m * m directions of the output tile to the device, k_probe_gather<Lobe> over the probes' tiles of `frame` (the output buffer, the
+// depth plane) into scratch, and the copy of the count * side * side float4 to dst.
+template <class Lobe>
+int gather_tiles(ptmi_ctx *c, const float4 *frame, uint32_t m, const Lobe &lobe, float *dst, size_t n_floats) {
+    if (c->d_probes && (!tile_ok(m, 2u, 16u) || m > c->probe.tile))
+        return fail(c, PTMI_E_INVALID, "m = %u is not a power of two in [2, min(16, tile = %u)]", m, c->probe.tile);
+    const size_t side = lobe.side(m), n = (size_t)c->probe.count * side * side * 4u;
+    const int rc = reduction_ready(c, dst, n_floats, n);
+    if (rc) return rc;
+    std::vector<float> normals((size_t)m * m * 4);
+    probe_tables(m, normals.data(), nullptr);
+    Scratch<float4> tiles;
+    HIP_TRY(c, hipMalloc(&tiles.p, n * sizeof(float)));
+    HIP_TRY(c, hipMemcpyAsync(c->d_probe_normals, normals.data(), normals.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    DevProbeAtlas a = probe_atlas(c);
+    a.out = frame;
+    allow_tile_lds<Lobe>();
+    hipLaunchKernelGGL(k_probe_gather<Lobe>, dim3(a.count), dim3(BLOCK), tile_lds(a.shift), c->stream, a, c->d_probe_dir_dw,
+                       c->d_probe_normals, m, lobe, tiles.p);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(dst, tiles.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PTMI_OK;
+}
 
-size_t pt_probe_irradiance_lds(uint32_t shift) { return ((size_t)1 << (2u * shift)) * (sizeof(float4) + 3u * sizeof(float)); }
+}  // namespace
 
 void pt_launch_probe_sh(hipStream_t s, DevProbeAtlas a, const float *basis9, float *sh) {
     hipLaunchKernelGGL(k_probe_sh, dim3((a.count + WAVES - 1) / WAVES), dim3(BLOCK), 0, s, a, basis9, sh);
-}
-void pt_launch_probe_irradiance(hipStream_t s, DevProbeAtlas a, const float4 *dir_dw, const float4 *normals, uint32_t m, float4 *irr) {
-    static std::atomic<uint64_t> raised{0};
-    allow_tile_lds(reinterpret_cast<const void *>(k_probe_irradiance), raised);
-    hipLaunchKernelGGL(k_probe_irradiance, dim3(a.count), dim3(BLOCK), pt_probe_irradiance_lds(a.shift), s, a, dir_dw, normals, m, irr);
-}
-
-void pt_launch_probe_visibility(hipStream_t s, DevProbeAtlas depth, const float4 *dir_dw, const float4 *normals, uint32_t m, uint32_t sharpness_log2,
-                                uint32_t border, float4 *vis) {
-    static std::atomic<uint64_t> raised{0};
-    allow_tile_lds(reinterpret_cast<const void *>(k_probe_visibility), raised);
-    hipLaunchKernelGGL(k_probe_visibility, dim3(depth.count), dim3(BLOCK), pt_probe_irradiance_lds(depth.shift), s, depth, dir_dw, normals, m,
-                       sharpness_log2, border, vis);
 }
 
 PT_HOST {
@@ -350,21 +358,7 @@ int ptmi_probe_sh(ptmi_ctx *c, float *dst, size_t n_floats) {
 
 int ptmi_probe_irradiance(ptmi_ctx *c, uint32_t m, float *dst, size_t n_floats) {
     if (!c) return PTMI_E_INVALID;
-    if (c->d_probes && (!tile_ok(m, 2u, 16u) || m > c->probe.tile))
-        return fail(c, PTMI_E_INVALID, "m = %u is not a power of two in [2, min(16, tile = %u)]", m, c->probe.tile);
-    const size_t n = (size_t)c->probe.count * m * m * 4u;
-    const int rc = reduction_ready(c, dst, n_floats, n);
-    if (rc) return rc;
-    std::vector<float> normals((size_t)m * m * 4);
-    probe_tables(m, normals.data(), nullptr);
-    Scratch<float4> irr;
-    HIP_TRY(c, hipMalloc(&irr.p, n * sizeof(float)));
-    HIP_TRY(c, hipMemcpyAsync(c->d_probe_normals, normals.data(), normals.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    pt_launch_probe_irradiance(c->stream, probe_atlas(c), c->d_probe_dir_dw, c->d_probe_normals, m, irr.p);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(dst, irr.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return PTMI_OK;
+    return gather_tiles(c, c->d_out, m, IrradianceLobe{}, dst, n_floats);
 }
 
 int ptmi_probe_visibility(ptmi_ctx *c, const ptmi_probe_visibility_params *params, float *dst, size_t n_floats) {
@@ -376,23 +370,7 @@ int ptmi_probe_visibility(ptmi_ctx *c, const ptmi_probe_visibility_params *param
     if (q._reserved) return fail(c, PTMI_E_INVALID, "the reserved word of ptmi_probe_visibility_params is not zero");
     if (q.sharpness_log2 > 6u) return fail(c, PTMI_E_INVALID, "sharpness_log2 = %u is above 6", q.sharpness_log2);
     if (q.border > 1u) return fail(c, PTMI_E_INVALID, "border = %u is not 0 or 1", q.border);
-    if (c->d_probes && (!tile_ok(q.m, 2u, 16u) || q.m > c->probe.tile))
-        return fail(c, PTMI_E_INVALID, "m = %u is not a power of two in [2, min(16, tile = %u)]", q.m, c->probe.tile);
-    const size_t side = (size_t)q.m + 2u * q.border, n = (size_t)c->probe.count * side * side * 4u;
-    const int rc = reduction_ready(c, dst, n_floats, n);
-    if (rc) return rc;
-    std::vector<float> normals((size_t)q.m * q.m * 4);
-    probe_tables(q.m, normals.data(), nullptr);
-    Scratch<float4> vis;
-    HIP_TRY(c, hipMalloc(&vis.p, n * sizeof(float)));
-    HIP_TRY(c, hipMemcpyAsync(c->d_probe_normals, normals.data(), normals.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    DevProbeAtlas depth = probe_atlas(c);
-    depth.out = plane_as<float4>(c, kProbeDepth);
-    pt_launch_probe_visibility(c->stream, depth, c->d_probe_dir_dw, c->d_probe_normals, q.m, q.sharpness_log2, q.border, vis.p);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(dst, vis.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return PTMI_OK;
+    return gather_tiles(c, plane_as<float4>(c, kProbeDepth), q.m, VisibilityLobe{q.sharpness_log2, q.border}, dst, n_floats);
 }
 
 int ptmi_debug_probe_rays(ptmi_ctx *c, const ptmi_probe_params *params, uint32_t n, const uint32_t *xs, const uint32_t *ys,
@@ -405,26 +383,7 @@ int ptmi_debug_probe_rays(ptmi_ctx *c, const ptmi_probe_params *params, uint32_t
     if (!c->d_probes) return fail(c, PTMI_E_INVALID, "no probes in place (ptmi_upload_probes)");
     for (uint32_t i = 0; i < n; i++)
         if (xs[i] >= c->W || ys[i] >= c->H) return fail(c, PTMI_E_INVALID, "texel (%u, %u) outside the %ux%u atlas", xs[i], ys[i], c->W, c->H);
-    if (n == 0) return PTMI_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, sync_all(c));
-    if ((rc = ensure_capacity(c, c->lane, n))) return rc;
-    Lane &ln = c->lane;
-    uint32_t *dx = ln.queue[0], *dy = ln.queue[1], *df = reinterpret_cast<uint32_t *>(ln.hits);
-    HIP_TRY(c, hipMemcpyAsync(dx, xs, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(dy, ys, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(df, frames, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    pt_launch_raygen_list(c->stream, probe_set(c), c->W, n, dx, dy, df, ln.paths);
-    std::vector<float4> o(n), d(n);
-    HIP_TRY(c, hipMemcpyAsync(o.data(), ln.paths.O, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d.data(), ln.paths.D, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, sync_all(c));
-    for (uint32_t i = 0; i < n; i++) {
-        o3[3 * i] = o[i].x; o3[3 * i + 1] = o[i].y; o3[3 * i + 2] = o[i].z;
-        d3[3 * i] = d[i].x; d3[3 * i + 1] = d[i].y; d3[3 * i + 2] = d[i].z;
-        if (rng) std::memcpy(&rng[i], &o[i].w, 4);
-    }
-    return PTMI_OK;
+    return debug_listed_rays(c, probe_set(c), c->W, n, xs, ys, frames, o3, d3, rng);
 }
 
 }  // extern "C"

@@ -392,20 +392,11 @@ float4 *pt_launch_bake_dilate(hipStream_t s, uint32_t W, uint32_t H, uint32_t pa
                               float4 *a, float4 *b);
 // one such pass on a masked plane the caller has (bake_denoise.hip): src is the state before the pass, and only dst is written
 void pt_launch_bake_dilate_pass(hipStream_t s, uint32_t W, uint32_t H, const float4 *src, float4 *dst);
-// The two reductions of a probe atlas (probes.hip; include/ptmi.h states both sums). `out` is the frame, W texels a row; probe i owns
-// the tile (i % cols, i / cols) of 1 << shift texels a side.
+// What the reductions of a probe atlas read (probes.hip; include/ptmi.h states their sums). `out` is the frame, W texels a row; probe
+// i owns the tile (i % cols, i / cols) of 1 << shift texels a side.
 struct DevProbeAtlas { const float4 *out; const float4 *probes; uint32_t W, shift, cols, count; };
 // sh[i * 27 + k * 3 + ch] from basis9 (9 floats per texel of a tile): one wave per probe
 void pt_launch_probe_sh(hipStream_t s, DevProbeAtlas a, const float *basis9, float *sh);
-// irr[(i * m * m + j) * 4 ...] from dir_dw (d_t, dw_t per texel of a tile) and normals (the m * m directions of the tile-m table): one
-// workgroup per probe, the probe's tile and dir_dw staged in pt_probe_irradiance_lds(shift) bytes of dynamic LDS
-size_t pt_probe_irradiance_lds(uint32_t shift);
-void pt_launch_probe_irradiance(hipStream_t s, DevProbeAtlas a, const float4 *dir_dw, const float4 *normals, uint32_t m, float4 *irr);
-// vis[(i * side * side + (jy + border) * side + jx + border) * 4 ...], side = m + 2 * border, from the probes' tiles of the depth plane
-// (depth.out), filtered by the cos^(2^sharpness_log2) lobe about each normal; border = 1: the ring of wrapped copies too. The LDS of
-// pt_probe_irradiance_lds(shift).
-void pt_launch_probe_visibility(hipStream_t s, DevProbeAtlas depth, const float4 *dir_dw, const float4 *normals, uint32_t m, uint32_t sharpness_log2,
-                                uint32_t border, float4 *vis);
 void pt_launch_extend(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &sc, DevPaths p,
                       const uint32_t *queue, const uint32_t *count, float2 *hits);
 void pt_launch_extend_own(hipStream_t s, int blocks, const TraverseConfig &cfg, const DevScene &sc, DevPaths p,
@@ -510,13 +501,15 @@ void pt_launch_adaptive_flags(hipStream_t s, int blocks, DevBand band, const ptm
 // looked up in the whole-frame map; NULL: in the band's own moments
 void pt_launch_adaptive_list(hipStream_t s, int blocks, DevBand band, const ptmi_adaptive_params &ap, const float4 *mom,
                              const DevFlagMap *fm, DevAdaptive ad);
+// The resolved parameters of an a-trous filter (pt_atrous.h: the pass the two denoisers share): phi_geo is the phi of the filter's own
+// geometric weight, ptmi_denoise_params.phi_depth or ptmi_bake_denoise_params.phi_position.
+struct AtrousArgs {
+    uint32_t W, H, iterations;
+    float phi_color, phi_normal, phi_geo;
+};
 // the denoiser (denoise.hip, ptmi_denoise): a prepass into guide / grad / cv, then `iterations` a-trous passes ping-ponging between
 // cv and tmp, the last remodulating into out. albedo NULL: no demodulation. cv is overwritten.
-struct DenoiseArgs {
-    uint32_t W, H, iterations;
-    float phi_color, phi_normal, phi_depth;
-};
-void pt_launch_denoise(hipStream_t s, const DenoiseArgs &a, const float4 *radiance, const float4 *normal, const float4 *albedo,
+void pt_launch_denoise(hipStream_t s, const AtrousArgs &a, const float4 *radiance, const float4 *normal, const float4 *albedo,
                        const float4 *moments, float4 *guide, float *grad, float4 *cv, float4 *tmp, float4 *out);
 // reprojection (reproject.hip, ptmi_reproject; the contract is stated in include/ptmi.h). The centre rays of the band's pixels under
 // `cam` go to p.O / p.D at the band-local pixel index, *count_out = their number: what `extend` then traces with a null queue.

@@ -139,17 +139,6 @@ void drop_planes(ptmi_ctx *c, uint32_t set) {
     view_planes(c);
 }
 
-// Copies a whole plane to the host once everything in flight has finished. src: the plane, or the buffer bound in its place. n: the
-// caller's count of `unit`-byte elements (4: floats, 1: bytes), which must be the plane's.
-int read_plane(ptmi_ctx *c, FramePlane k, const void *src, void *dst, size_t n, size_t unit) {
-    const size_t bytes = kFrame[k].bytes((size_t)c->W * c->H);
-    if (n * unit != bytes) return fail(c, PTMI_E_INVALID, "expected %zu %s, got %zu", bytes / unit, unit == 4 ? "floats" : "bytes", n);
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, quiesce(c));
-    HIP_TRY(c, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-    return PTMI_OK;
-}
-
 // a fresh moments plane (ptmi_resize, ptmi_set_moments): no round has listed anything in it
 int reset_adaptive_rounds(ptmi_ctx *c) {
     static_assert(kCwAdActive == kCwAdPixels + 1, "the round's two words, zeroed as one");
@@ -171,6 +160,27 @@ int fail(std::string &err, int code, const char *fmt, ...) {
 int fail(const ptmi_ctx *c, int code, const char *fmt, ...) {
     va_list ap; va_start(ap, fmt); vfail(c ? c->err : g_create_err, fmt, ap); va_end(ap);
     return code;
+}
+
+int read_plane(ptmi_ctx *c, FramePlane k, const void *src, void *dst, size_t n, size_t unit) {
+    const size_t bytes = kFrame[k].bytes((size_t)c->W * c->H);
+    if (n * unit != bytes) return fail(c, PTMI_E_INVALID, "expected %zu %s, got %zu", bytes / unit, unit == 4 ? "floats" : "bytes", n);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, quiesce(c));
+    HIP_TRY(c, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    return PTMI_OK;
+}
+
+int atrous_params(ptmi_ctx *c, uint32_t iterations, const uint32_t (&reserved)[3], const char *of, float phi_color, float phi_normal,
+                  float phi_geo, AtrousArgs *out) {
+    if (iterations > 10u) return fail(c, PTMI_E_INVALID, "iterations = %u is above 10", iterations);
+    if (reserved[0] || reserved[1] || reserved[2]) return fail(c, PTMI_E_INVALID, "a reserved word%s is not zero", of);
+    for (float f : {phi_color, phi_normal, phi_geo})
+        if (!std::isfinite(f) || f < 0.0f) return fail(c, PTMI_E_INVALID, "phi %g is negative or not finite", (double)f);
+    if (!c->d_out) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
+    *out = AtrousArgs{c->W, c->H, iterations ? iterations : 5u, phi_color > 0.0f ? phi_color : 4.0f,
+                      phi_normal > 0.0f ? phi_normal : 128.0f, phi_geo > 0.0f ? phi_geo : 1.0f};
+    return PTMI_OK;
 }
 
 void default_options(ptmi_options &o) {
@@ -658,13 +668,11 @@ int ptmi_denoise(ptmi_ctx *c, const ptmi_denoise_params *p, float *dst_rgba, siz
     if (!c) return PTMI_E_INVALID;
     const ptmi_denoise_params zero = {};
     const ptmi_denoise_params &q = p ? *p : zero;
-    if (q.iterations > 10u) return fail(c, PTMI_E_INVALID, "iterations = %u is above 10", q.iterations);
-    if (q.demodulate > 2u) return fail(c, PTMI_E_INVALID, "unknown demodulate %u", q.demodulate);
-    if (q.reserved[0] || q.reserved[1] || q.reserved[2]) return fail(c, PTMI_E_INVALID, "a reserved word is not zero");
-    const float phis[3] = {q.phi_color, q.phi_normal, q.phi_depth};
-    for (float f : phis)
-        if (!std::isfinite(f) || f < 0.0f) return fail(c, PTMI_E_INVALID, "phi %g is negative or not finite", (double)f);
-    if (!c->d_out) return fail(c, PTMI_E_STATE, "no output buffer (ptmi_resize)");
+    // (an unknown demodulate is refused after iterations above 10 and before everything else)
+    if (q.iterations <= 10u && q.demodulate > 2u) return fail(c, PTMI_E_INVALID, "unknown demodulate %u", q.demodulate);
+    AtrousArgs da;
+    int rc = atrous_params(c, q.iterations, q.reserved, "", q.phi_color, q.phi_normal, q.phi_depth, &da);
+    if (rc) return rc;
     const size_t npix = (size_t)c->W * c->H;
     if (dst_rgba && n_floats != npix * 4) return fail(c, PTMI_E_INVALID, "expected %zu floats, got %zu", npix * 4, n_floats);
     if (!(c->aov_mask & PTMI_AOV_NORMAL) || !c->plane[kAovNormal])
@@ -674,14 +682,7 @@ int ptmi_denoise(ptmi_ctx *c, const ptmi_denoise_params *p, float *dst_rgba, siz
     if (q.demodulate == 2u && !have_albedo) return fail(c, PTMI_E_STATE, "demodulate = 2 needs the ALBEDO plane (ptmi_set_aovs)");
     const bool demod = q.demodulate == 2u || (q.demodulate == 0u && have_albedo);
     HIP_TRY(c, hipSetDevice(c->device));
-    const int rc = make_planes(c, group_set(kByDenoise), npix, c->plane);
-    if (rc) return rc;
-    DenoiseArgs da;
-    da.W = c->W; da.H = c->H;
-    da.iterations = q.iterations ? q.iterations : 5u;
-    da.phi_color = q.phi_color > 0.0f ? q.phi_color : 4.0f;
-    da.phi_normal = q.phi_normal > 0.0f ? q.phi_normal : 128.0f;
-    da.phi_depth = q.phi_depth > 0.0f ? q.phi_depth : 1.0f;
+    if ((rc = make_planes(c, group_set(kByDenoise), npix, c->plane))) return rc;
     pt_launch_denoise(c->stream, da, c->d_out, plane_as<float4>(c, kAovNormal), demod ? plane_as<float4>(c, kAovAlbedo) : nullptr,
                       plane_as<float4>(c, kMoments), plane_as<float4>(c, kDnGuide), plane_as<float>(c, kDnGrad), plane_as<float4>(c, kDnA),
                       plane_as<float4>(c, kDnB), plane_as<float4>(c, kDnOut));

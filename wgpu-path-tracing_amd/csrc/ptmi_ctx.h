@@ -3,7 +3,7 @@
 //   scene_image.hip    scene validation, the traversal image, ptmi_upload_scene
 //   traverse_pick.hip  which variant a traversal kernel runs as, and the launch of one
 //   dispatch.hip       the wavefront dispatch loop, adaptive sampling, reprojection, event timing
-//   debug_stages.hip   the per-stage debug entry points
+//   debug_stages.hip   the per-stage debug entry points; the listed first rays the bake's and the probes' debug entries share
 //   environment.hip    the environment map: its tables, upload and removal, its debug entry points
 //   medium.hip         the participating medium: its checks, installation and removal, its debug entry points
 //   medium_grid.hip    the medium's density grid: its checks, upload and removal, its debug entry points
@@ -17,7 +17,8 @@
 //   scene_skin.hip     skinned triangles posed on the device: the list, the corner records, the rest pose, the check and write kernel
 //   scene_morph.hip    morphed triangles posed on the device: the list, the sparse delta rows, the rest pose, the check and write kernel
 //   bake.hip           lightmap baking: the surface's records and covered list, the checks of a bake, the gutter fill, the debug rays
-//   bake_denoise.hip   the lightmap filter: its kernels, launches and entry points (ptmi_bake_denoise)
+//   bake_denoise.hip   the lightmap filter: its prepass, guide policy, launches and entry points (ptmi_bake_denoise); the a-trous
+//                      pass is pt_atrous.h's, shared with denoise.hip
 //   probes.hip         light probes: the records, tables and texel list, the checks of a probe dispatch, the SH9, irradiance and
 //                      visibility reductions, the depth plane's switch
 #pragma once
@@ -336,10 +337,24 @@ uint32_t group_set(PlaneGroup g);
 size_t plane_bytes(FramePlane k, size_t px);                                        // what plane k takes for px pixels
 int make_planes(ptmi_ctx *c, uint32_t set, size_t px, void **into);
 int check_ready(ptmi_ctx *c, bool need_output);
+// Copies a whole plane to the host once everything in flight has finished. src: the plane, or the buffer bound in its place. n: the
+// caller's count of `unit`-byte elements (4: floats, 1: bytes), which must be the plane's.
+int read_plane(ptmi_ctx *c, FramePlane k, const void *src, void *dst, size_t n, size_t unit);
+// What ptmi_denoise_params and ptmi_bake_denoise_params have in common, checked in the order both entry points refuse in: iterations
+// above 10, a reserved word (`of`: what the message adds after "a reserved word"), a phi that is negative or not finite, no output
+// buffer. *out = the frame's size and the values with their defaults in place (5 / 4 / 128 / 1).
+int atrous_params(ptmi_ctx *c, uint32_t iterations, const uint32_t (&reserved)[3], const char *of, float phi_color, float phi_normal,
+                  float phi_geo, AtrousArgs *out);
 
 // dispatch.hip
 void drain_events(ptmi_ctx *c);
 hipError_t quiesce(ptmi_ctx *c);
+
+// debug_stages.hip: the first rays of the n listed pixels (xs, ys) of a frame `width` wide at `frames`, from `rays`, as the caller's
+// packed triples (rng, may be NULL: the word beside each origin). What ptmi_debug_raygen, ptmi_debug_bake_rays and
+// ptmi_debug_probe_rays do once their own checks have passed.
+int debug_listed_rays(ptmi_ctx *c, const DevRays &rays, uint32_t width, uint32_t n, const uint32_t *xs, const uint32_t *ys,
+                      const uint32_t *frames, float *o3, float *d3, uint32_t *rng);
 
 // bake.hip. bake_forget: the surface goes (the caller has synchronised). bake_check: everything ptmi_dispatch_bake checks before it
 // enqueues, with its error codes, changing nothing; *out = the params with their defaults.
